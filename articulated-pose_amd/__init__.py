@@ -10,7 +10,6 @@ Module names mirror the reference tree so its call sites drop in:
 """
 __version__ = "0.1.0"
 
-# Importing this package has NO side effects on the process (until round 4 it exported GPU_MAX_HW_QUEUES=32 here).  The one runtime
-# setting the throughput deployment needs -- one hardware queue per batch in flight -- is requested by pipeline.AncshPipeline when it is
-# built with more than four slots (see pipeline.ensure_hardware_queues), and a host that initialises HIP first sets it itself
-# (include/ancsh_hip.h "THROUGHPUT NOTE"; bench.py does so at its top).
+# Importing this package has NO side effects on the process.  The number of hardware queues (GPU_MAX_HW_QUEUES) belongs to the host:
+# neither the package nor bench.py changes it; pipeline.AncshPipeline warns when it has more batches in flight than queues
+# (see pipeline.check_hardware_queues and include/ancsh_hip.h "THROUGHPUT NOTE").

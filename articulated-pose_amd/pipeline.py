@@ -15,12 +15,12 @@ from .network import Network
 from .pose import PoseSolver
 
 
-def ensure_hardware_queues(slots, want=32):
-    """Every batch in flight sits on its own HIP stream, and each stream needs its own hardware queue: with the runtime's default of 4
-    a 1.6 ms stage-B kernel of one batch blocks other batches' kernels queued behind it (3.5 vs 2.35 ms/step measured at 4 vs 24
-    queues).  The HIP runtime reads GPU_MAX_HW_QUEUES once, when it initialises.  Called by AncshPipeline for slots > 4: if the
-    variable is unset and HIP is not up yet it is set here; if HIP is already initialised it cannot be changed any more -> a
-    warning that names what the host should export.  Returns the effective value (None = unknown / runtime default)."""
+def check_hardware_queues(slots):
+    """Every batch in flight sits on its own HIP stream; streams share the process's hardware queues, and where there are fewer
+    queues than batches in flight a 1.6 ms stage-B kernel of one batch holds back other batches' kernels queued behind it.  The
+    HIP runtime reads GPU_MAX_HW_QUEUES once, when it initialises; the host owns that setting and the package never changes it.
+    Called by AncshPipeline: warns when the setting (unset: the runtime's default of 4) is below the slot count.  Returns the
+    value the host set (None = unset / not an integer)."""
     import os
     import warnings
     raw = os.environ.get("GPU_MAX_HW_QUEUES")
@@ -29,21 +29,11 @@ def ensure_hardware_queues(slots, want=32):
     except ValueError:
         warnings.warn("GPU_MAX_HW_QUEUES=%r is not an integer: ignored by this check (the HIP runtime decides what it makes of it)" % raw)
         cur = None
-    if slots <= 4:
-        return cur
-    want = max(want, slots)                    # never fewer queues than batches in flight
-    if cur is not None:
-        if cur < slots:
-            warnings.warn("AncshPipeline(slots=%d) with GPU_MAX_HW_QUEUES=%d: batches in flight will share hardware queues and wait behind "
-                          "each other's long pose kernels; export GPU_MAX_HW_QUEUES>=%d before the process initialises HIP" % (slots, cur, slots))
-        return cur
-    if torch.cuda.is_initialized():
-        warnings.warn("AncshPipeline(slots=%d): HIP is already initialised with the runtime's default of 4 hardware queues, so the %d batches "
-                      "in flight will wait behind each other's long pose kernels (~1.5x slower steps).  Export GPU_MAX_HW_QUEUES=%d before the "
-                      "first HIP call of the process (bench.py does so at its top)" % (slots, slots, want))
-        return None
-    os.environ["GPU_MAX_HW_QUEUES"] = str(want)
-    return want
+    have = 4 if cur is None else cur
+    if have < slots:
+        warnings.warn("AncshPipeline(slots=%d) on %d hardware queues (GPU_MAX_HW_QUEUES): batches in flight share hardware queues and "
+                      "wait behind each other's long pose kernels" % (slots, have))
+    return cur
 
 
 class _Slot(object):
@@ -89,7 +79,7 @@ class AncshPipeline(object):
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None):
         self.K, self.B, self.N = num_parts, batch_size, num_points
-        self.hw_queues = ensure_hardware_queues(max(1, slots))        # before the first HIP call this object makes
+        self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)

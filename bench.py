@@ -16,11 +16,6 @@ import os
 import sys
 import time
 
-# One HIP stream per batch in flight must map to its own hardware queue, or a 5 ms stage-B straggler kernel of one
-# batch holds back another batch's kernels queued behind it (measured: 4 queues -> 3.5 ms/step, 24 -> 2.35 ms/step).
-# The HIP runtime reads this when it initialises, i.e. before the first device call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -792,6 +787,43 @@ def emit(line, sidecar=True):
     return final
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, path):
+    """Write every array of `outputs` (nested dicts of tensors / arrays; keys starting with "_" are the fit's internal scratch, not
+    outputs) as <path>/<dotted.name>.npy: float64 stays float64, everything else becomes float32 (int64 -> float64).  Above
+    DUMP_MAX_BYTES in all, every array is cut to the same fraction of its elements, chosen by a generator seeded with its name: the
+    same arguments give the same sample.  Returns {name: shape written}."""
+    import zlib
+    flat, seen = {}, set()
+
+    def walk(prefix, o):
+        if isinstance(o, dict):
+            for k in sorted(o):
+                if not str(k).startswith("_"):
+                    walk(prefix + (str(k),), o[k])
+        elif torch.is_tensor(o) or isinstance(o, np.ndarray):
+            key = (o.data_ptr(), tuple(o.shape), tuple(o.stride())) if torch.is_tensor(o) else id(o)
+            if key not in seen:               # the same tensor under two names (e.g. the pose record): written once
+                seen.add(key)
+                a = o.detach().cpu().numpy() if torch.is_tensor(o) else o
+                flat[".".join(prefix)] = a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+    walk((), outputs)
+    total = sum(a.nbytes for a in flat.values())
+    keep = min(1.0, DUMP_MAX_BYTES / float(total)) if total else 1.0
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in flat.items():
+        if keep < 1.0:
+            k = int(a.size * keep)
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def print_last(text):
     """The contract line must be the LAST line of stdout.  Native libraries write to C stdio, which is fully buffered on a pipe and
     flushed at exit -- RCCL's "Librccl path : ..." banner came out AFTER the JSON line that Python had printed and flushed long before.
@@ -861,11 +893,16 @@ def main():
     ap.add_argument("--ops-brief", action="store_true", help="with --ops-only: the graded five-launch figure (beyond the Infinity Cache) "
                                                               "and the three-launch form only")
     ap.add_argument("--dump-kernels", action="store_true", help="per-call event timings to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the outputs the step hands its caller) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all (a seeded sample of each array beyond that)")
     ap.add_argument("--profile-lead-sa", type=int, default=100, help="the same for the fused SA launches (the roofline's kernel)")
     ap.add_argument("--profile-lead", type=int, default=6,
                     help="per-kernel timing pass: launches of the same call issued back-to-back before each timed one, so the timed "
                          "launch runs at the loaded clock instead of on a chip that idled while Python prepared the call (0 = cold)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.leg:
         args.no_ops = args.no_value_configs = args.no_cpu_baseline = args.no_network_inputs = args.no_bf16x3 = True
     if args.bf16x3:
@@ -998,16 +1035,19 @@ def main():
         from articulated_pose_amd.dist import RecordGatherer
         gatherer = RecordGatherer(rec_shape, rec_dtype, dev, dst=0, group=data_group)
 
+    last = {}
+
     def timed(pipe, steps, warmup):
-        """warmup untimed steps, then exactly `steps` steps between barrier + full synchronise on both sides; max over ranks (s)."""
+        """warmup untimed steps, then exactly `steps` steps between barrier + full synchronise on both sides; max over ranks (s).
+        last["out"]: the outputs the last step handed back (valid after the closing synchronise, until that slot runs again)."""
         def step():
             if full:
-                sharded.step()                              # next batch on its slot's stream + its record gather (RCCL: same stream)
+                last["out"] = sharded.step()[1]             # next batch on its slot's stream + its record gather (RCCL: same stream)
                 return
             e = engines[turn[0] % len(engines)]
             turn[0] += 1
             with torch.cuda.stream(e.stream):
-                out = e()
+                out = last["out"] = e()
                 if use_dist:
                     gatherer.gather(torch.cat([out[k] for k in keys], dim=2), lane=id(e), stream=e.stream)
 
@@ -1046,6 +1086,13 @@ def main():
         return dt
 
     dt = timed(pipe if full else None, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the device: the last step's slot is reused by no later work of this process until then
+        outs = dict(last["out"])
+        if full and sharded.gatherer is not None:
+            outs["records"] = sharded.records()          # the world's gathered (global_batch, K, 26) records
+        written = dump_outputs(outs, args.dump_outputs)
+        print("bench.py: %d arrays of the last timed step written to %s" % (len(written), args.dump_outputs), file=sys.stderr, flush=True)
 
     if args.only_timed:
         if use_dist:

@@ -18,10 +18,9 @@
  * THROUGHPUT NOTE for a host that links this library directly.  The network kernels are throughput-bound, the pose fit is
  * latency-bound (stage B: one of a batch's 12 800 LM fits may run MINPACK's whole 4200-evaluation budget in a single lane, ~1.6 ms,
  * exactly as scipy does): a lone batch of 32 clouds takes ~3.5 ms, while >= 16 batches in flight on SEPARATE HIP streams sustain
- * ~1.57 ms per batch (bench.py keeps 20).  Each such stream needs its own hardware queue: export GPU_MAX_HW_QUEUES=32 BEFORE the
- * first HIP call -- with the runtime's default of 4 queues one batch's LM kernel holds back other batches' kernels queued behind
- * it (measured 3.5 ms per batch at 4 queues against 2.35 at 24 with identical kernels).  The Python package sets the variable on
- * import; a C / C++ host has to do it itself.  Create those streams ONCE and reuse them: a process that has used more than
+ * ~1.57 ms per batch (bench.py keeps 20).  Streams share the process's hardware queues (GPU_MAX_HW_QUEUES, a host setting that
+ * neither this library nor the Python package changes): where batches in flight outnumber the queues, one batch's LM kernel holds
+ * back other batches' kernels queued behind it.  Create those streams ONCE and reuse them: a process that has used more than
  * ~20-24 distinct streams over its lifetime runs the same pipeline 5-25 % slower (every stream that has been used keeps a
  * hardware queue; profiles/r04_step_sensitivity.txt).  Nothing in this ABI creates streams or threads.
  */

@@ -1,5 +1,6 @@
 """Non-finite input coordinates (depth sensors produce them) have DEFINED behaviour, the same on the HIP path, in the CPU oracle and
--- for the operators the reference ships as CUDA -- in the reference's own kernels compiled into oracle/_ref:
+-- for the operators the reference ships as CUDA -- in the reference's own kernels (compiled into oracle/_ref and run on these inputs by
+tests/golden/gen_ref_ops_golden.py; their outputs are held as the digests of tests/golden/ref_ops.json):
 
   farthest_point_sample  tf_sampling_g.cu:143-149: d2 = min(d, td) is fminf (a NaN distance leaves td alone), so a NaN / Inf point keeps
                          its initial 1e38 and is PICKED as soon as the scan reaches it -- and then picked again for every later sample
@@ -14,30 +15,19 @@
   pose fit               a cloud with a non-finite value in P / part-NOCS / mask / joint axes gets an all-NaN record
                          (ancsh_pose_poison_records); the other clouds of the batch are untouched, bit for bit.
 Never a silently finite answer from a poisoned cloud."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import cloud
+from helpers import cloud, digest, ref_ops
 
 pytestmark = pytest.mark.gpu
-REF_SO = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libancsh_ref_gfx950.so")
 
 
 @pytest.fixture(scope="module")
 def ops(dev):
     from articulated_pose_amd import tf_ops
     return tf_ops
-
-
-@pytest.fixture(scope="module")
-def ref():
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built")
-    return ctypes.CDLL(REF_SO)
 
 
 def T(a, dev):
@@ -58,45 +48,61 @@ def poison(x, rng, frac, values):
 VALUES = {"nan": [np.nan], "inf": [np.inf, -np.inf], "mixed": [np.nan, np.inf, -np.inf]}
 
 
-@pytest.mark.parametrize("what", ["nan", "inf", "mixed"])
-@pytest.mark.parametrize("n,m", [(1024, 512), (512, 128), (2048, 512), (700, 33)])
-def test_fps_with_non_finite_points(ops, oracle, ref, dev, what, n, m):
+WHATS = ["nan", "inf", "mixed"]
+FPS_SHAPES = [(1024, 512), (512, 128), (2048, 512), (700, 33)]
+BALL_SHAPES = [(1024, 512, 0.2, 64), (512, 128, 0.4, 64), (2048, 512, 0.2, 64), (333, 77, 0.3, 16), (5000, 33, 0.15, 32)]
+THREE_NN_SHAPES = [(512, 128), (1024, 512), (77, 2)]
+
+
+def fps_inputs(what, n, m):
     rng = np.random.RandomState(n + m + len(what))
     x = poison(cloud(rng, 6, n, "grid"), rng, 0.01, VALUES[what])
     x[5] = cloud(rng, 1, n, "grid")[0]                                     # one clean cloud in the batch
     x[4, 0, 1] = VALUES[what][0]                                           # ... and one whose FIRST point (always sample 0) is poisoned
+    return x
+
+
+def ball_inputs(oracle, what, n, m, r, ns):
+    rng = np.random.RandomState(3 * n + m + len(what))
+    x = poison(cloud(rng, 4, n, "grid"), rng, 0.01, VALUES[what])
+    q = oracle.gather_point(x, oracle.farthest_point_sample(m, x))         # the reference's own centres: mostly the poisoned point
+    q[:, : m // 2] = x[:, : m // 2] if m // 2 <= n else q[:, : m // 2]     # ... half of them replaced by ordinary points of the cloud
+    return x, q
+
+
+def three_nn_inputs(n, m):
+    rng = np.random.RandomState(n + 7 * m)
+    x1 = poison(cloud(rng, 2, n, "grid"), rng, 0.02, VALUES["mixed"])
+    x2 = poison(cloud(rng, 2, m, "grid"), rng, 0.05, VALUES["mixed"])
+    return x1, x2
+
+
+@pytest.mark.parametrize("what", WHATS)
+@pytest.mark.parametrize("n,m", FPS_SHAPES)
+def test_fps_with_non_finite_points(ops, oracle, dev, what, n, m):
+    x = fps_inputs(what, n, m)
     want = oracle.farthest_point_sample(m, x)
     xt = T(x, dev)
     got = ops.farthest_point_sample(m, xt).cpu().numpy()
     np.testing.assert_array_equal(got, want)
-    out = torch.zeros((6, m), dtype=torch.int32, device=dev)
-    temp = torch.zeros((32, n), dtype=torch.float32, device=dev)
-    assert ref.ref_farthest_point_sample(6, n, m, ctypes.c_void_p(xt.data_ptr()), ctypes.c_void_p(temp.data_ptr()),
-                                         ctypes.c_void_p(out.data_ptr())) == 0
-    np.testing.assert_array_equal(got, out.cpu().numpy())                  # the reference's own kernel says the same
+    assert digest(got) == ref_ops("nonfinite_fps/%s/%d/%d" % (what, n, m))  # the reference's own kernel says the same
     bad = ~np.isfinite(x).all(axis=2)
     for i in range(4):                                                     # the documented degeneration: one bad point, picked again and again
         assert bad[i, got[i, 1]] and (got[i, 1:] == got[i, 1]).all()
 
 
-@pytest.mark.parametrize("what", ["nan", "inf", "mixed"])
-@pytest.mark.parametrize("n,m,r,ns", [(1024, 512, 0.2, 64), (512, 128, 0.4, 64), (2048, 512, 0.2, 64), (333, 77, 0.3, 16), (5000, 33, 0.15, 32)])
-def test_ball_query_and_grouping_with_non_finite_points(ops, oracle, ref, dev, what, n, m, r, ns):
-    rng = np.random.RandomState(3 * n + m + len(what))
-    x = poison(cloud(rng, 4, n, "grid"), rng, 0.01, VALUES[what])
-    q = oracle.gather_point(x, oracle.farthest_point_sample(m, x))         # the reference's own centres: mostly the poisoned point
-    q[:, : m // 2] = x[:, : m // 2] if m // 2 <= n else q[:, : m // 2]     # ... half of them replaced by ordinary points of the cloud
+@pytest.mark.parametrize("what", WHATS)
+@pytest.mark.parametrize("n,m,r,ns", BALL_SHAPES)
+def test_ball_query_and_grouping_with_non_finite_points(ops, oracle, dev, what, n, m, r, ns):
+    x, q = ball_inputs(oracle, what, n, m, r, ns)
     widx, wcnt = oracle.query_ball_point(r, ns, x, q)
     xt, qt = T(x, dev), T(q, dev)
     gidx, gcnt = ops.query_ball_point(r, ns, xt, qt)
     np.testing.assert_array_equal(gcnt.cpu().numpy(), wcnt)
     np.testing.assert_array_equal(gidx.cpu().numpy(), widx)
-    idx = torch.zeros((4, m, ns), dtype=torch.int32, device=dev)
-    cnt = torch.zeros((4, m), dtype=torch.int32, device=dev)
-    vp = ctypes.c_void_p
-    assert ref.ref_query_ball_point(4, n, m, ctypes.c_float(r), ns, vp(xt.data_ptr()), vp(qt.data_ptr()), vp(idx.data_ptr()), vp(cnt.data_ptr())) == 0
-    np.testing.assert_array_equal(gcnt.cpu().numpy(), cnt.cpu().numpy())
-    np.testing.assert_array_equal(gidx.cpu().numpy(), idx.cpu().numpy())
+    key = "nonfinite_ball/%s/%d/%d/%g/%d" % (what, n, m, r, ns)
+    assert digest(gcnt) == ref_ops(key + "/cnt")
+    assert digest(gidx) == ref_ops(key + "/idx")
     if what == "nan":
         nanrow = np.isnan(x).any(axis=2)
         first = np.array([np.flatnonzero(nanrow[i])[0] for i in range(4)])
@@ -130,19 +136,15 @@ def test_ball_query_schedules_agree_on_non_finite_points(ops, dev, what):
     assert torch.equal(idx3, idx0) and torch.equal(cnt3, cnt0) and np.array_equal(g3.cpu().numpy(), g0.cpu().numpy(), equal_nan=True)
 
 
-@pytest.mark.parametrize("n,m", [(512, 128), (1024, 512), (77, 2)])
+@pytest.mark.parametrize("n,m", THREE_NN_SHAPES)
 def test_three_nn_with_non_finite_points(ops, oracle, dev, n, m):
-    rng = np.random.RandomState(n + 7 * m)
-    x1 = poison(cloud(rng, 2, n, "grid"), rng, 0.02, VALUES["mixed"])
-    x2 = poison(cloud(rng, 2, m, "grid"), rng, 0.05, VALUES["mixed"])
+    x1, x2 = three_nn_inputs(n, m)
     wd, wi = oracle.three_nn(x1, x2)
     gd, gi = ops.three_nn(T(x1, dev), T(x2, dev))
     np.testing.assert_array_equal(gi.cpu().numpy(), wi)
     np.testing.assert_array_equal(gd.cpu().numpy(), wd)
-    if oracle.have_ref_interp():
-        rd, ri = oracle.ref_three_nn(x1, x2)
-        np.testing.assert_array_equal(gi.cpu().numpy(), ri)
-        np.testing.assert_array_equal(gd.cpu().numpy(), rd)
+    assert digest(gi) == ref_ops("nonfinite_three_nn/%d/%d/idx" % (n, m))
+    assert digest(gd) == ref_ops("nonfinite_three_nn/%d/%d/dist" % (n, m))
 
 
 def _synth(rng, b, n):

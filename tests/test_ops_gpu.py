@@ -1,31 +1,21 @@
 """GPU parity of the PointNet++ operators: HIP (through the C ABI) vs the CPU oracle, bit-exact
-for indices / counts / copies, and vs the reference's own .cu kernels compiled into oracle/_ref."""
-import ctypes
+for indices / counts / copies, and vs the reference's own .cu kernels and host loops (compiled into oracle/_ref and run on these
+inputs by tests/golden/gen_ref_ops_golden.py; their outputs are held as the digests of tests/golden/ref_ops.json)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import cloud
+from helpers import cloud, digest, ref_ops
 
 pytestmark = pytest.mark.gpu
-
-REF_SO = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
-                      "libancsh_ref_gfx950.so")
 
 
 @pytest.fixture(scope="module")
 def ops(dev):
     from articulated_pose_amd import tf_ops
     return tf_ops
-
-
-@pytest.fixture(scope="module")
-def ref():
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built")
-    return ctypes.CDLL(REF_SO)
 
 
 def T(a, dev):
@@ -42,39 +32,45 @@ def test_fps_matches_oracle(ops, oracle, dev, kind, n, m):
     np.testing.assert_array_equal(got, want)
 
 
+def fps_large_inputs(kind):
+    return cloud(np.random.RandomState(77), 2, 9000, kind)
+
+
 @pytest.mark.parametrize("kind", ["uniform", "coarse"])
-def test_fps_large_cloud_kernel(ops, oracle, ref, dev, kind):
+def test_fps_large_cloud_kernel(ops, oracle, dev, kind):
     """n > 8192: the large-cloud kernel (running minima in the caller's scratch) against the oracle and the reference's own
     kernel; without the scratch the C ABI refuses with EINVAL instead of computing something else."""
     from articulated_pose_amd import _lib
     from articulated_pose_amd.tf_ops.tf_sampling import farthest_point_sample_gather
-    rng = np.random.RandomState(77)
     n, m = 9000, 40
-    x = cloud(rng, 2, n, kind)
+    x = fps_large_inputs(kind)
     xt = T(x, dev)
     want = oracle.farthest_point_sample(m, x)
     np.testing.assert_array_equal(ops.farthest_point_sample(m, xt).cpu().numpy(), want)
     idx, xyz = farthest_point_sample_gather(m, xt)
     np.testing.assert_array_equal(idx.cpu().numpy(), want)
     np.testing.assert_array_equal(xyz.cpu().numpy(), oracle.gather_point(x, want))
-    out = torch.zeros((2, m), dtype=torch.int32, device=dev)
-    temp = torch.zeros((32, n), dtype=torch.float32, device=dev)
-    assert ref.ref_farthest_point_sample(2, n, m, ctypes.c_void_p(xt.data_ptr()), ctypes.c_void_p(temp.data_ptr()),
-                                         ctypes.c_void_p(out.data_ptr())) == 0
     if kind == "coarse":                       # lattice input: exact arithmetic, the reference kernel is directly comparable
-        np.testing.assert_array_equal(out.cpu().numpy(), want)
+        assert digest(want) == ref_ops("fps_large/coarse")
+    out = torch.zeros((2, m), dtype=torch.int32, device=dev)
     with pytest.raises(ValueError):
         _lib.call("ancsh_farthest_point_sample", 2, n, m, _lib.ptr(xt), 0, _lib.ptr(out))
 
 
-@pytest.mark.parametrize("n,m", [(10, 5), (1000, 64), (8192, 100), (9001, 33), (20000, 257)])
-def test_prob_sample(ops, oracle, ref, dev, n, m):
-    """ProbSample: indices AND the cumulative sums (order-dependent float additions) equal to the oracle's simulation of the
-    reference block scan and to the reference's own kernels (oracle/_ref), bit for bit."""
-    from articulated_pose_amd import _lib
+PROB_SHAPES = [(10, 5), (1000, 64), (8192, 100), (9001, 33), (20000, 257)]
+
+
+def prob_sample_inputs(n, m):
     rng = np.random.RandomState(n + m)
-    p = rng.rand(3, n).astype(np.float32)
-    r = rng.rand(3, m).astype(np.float32)
+    return rng.rand(3, n).astype(np.float32), rng.rand(3, m).astype(np.float32)
+
+
+@pytest.mark.parametrize("n,m", PROB_SHAPES)
+def test_prob_sample(ops, oracle, dev, n, m):
+    """ProbSample: indices AND the cumulative sums (order-dependent float additions) equal to the oracle's simulation of the
+    reference block scan and to the reference's own kernels, bit for bit."""
+    from articulated_pose_amd import _lib
+    p, r = prob_sample_inputs(n, m)
     want, want_cdf = oracle.prob_sample(p, r)
     pt, rt = T(p, dev), T(r, dev)
     np.testing.assert_array_equal(ops.prob_sample(pt, rt).cpu().numpy(), want)
@@ -82,11 +78,8 @@ def test_prob_sample(ops, oracle, ref, dev, n, m):
     out = torch.zeros((3, m), dtype=torch.int32, device=dev)
     _lib.call("ancsh_prob_sample", 3, n, m, _lib.ptr(pt), _lib.ptr(rt), _lib.ptr(temp), _lib.ptr(out))
     np.testing.assert_array_equal(temp.cpu().numpy(), want_cdf)
-    rtemp, rout = torch.zeros_like(temp), torch.zeros_like(out)
-    vp = ctypes.c_void_p
-    assert ref.ref_prob_sample(3, n, m, vp(pt.data_ptr()), vp(rt.data_ptr()), vp(rtemp.data_ptr()), vp(rout.data_ptr())) == 0
-    np.testing.assert_array_equal(rtemp.cpu().numpy(), want_cdf)
-    np.testing.assert_array_equal(rout.cpu().numpy(), want)
+    assert digest(temp) == ref_ops("prob_sample/%d/%d/cdf" % (n, m))
+    assert digest(out) == ref_ops("prob_sample/%d/%d/idx" % (n, m))
     with pytest.raises(ValueError):
         ops.prob_sample(pt[0], rt)
 
@@ -147,23 +140,26 @@ def test_group_point_multi_equals_separate_calls(ops, dev):
         assert torch.equal(got, ops.group_point(p, i))
 
 
-@pytest.mark.parametrize("n,m,k", [(64, 5, 8), (1024, 33, 32), (300, 7, 300), (2048, 3, 64), (5, 2, 9)])
-def test_select_top_k_and_knn_point(ops, oracle, ref, dev, n, m, k):
+TOP_K_SHAPES = [(64, 5, 8), (1024, 33, 32), (300, 7, 300), (2048, 3, 64), (5, 2, 9)]
+
+
+def top_k_inputs(n, m, k):
+    """The distances and the generator the knn half goes on drawing from."""
+    rng = np.random.RandomState(n + m + k)
+    return (rng.randint(0, 40, (2, m, n)) / 8.0).astype(np.float32), rng
+
+
+@pytest.mark.parametrize("n,m,k", TOP_K_SHAPES)
+def test_select_top_k_and_knn_point(ops, oracle, dev, n, m, k):
     """select_top_k: ALL n columns (sorted head and the swap-permuted tail) equal to the oracle and to the reference's own
     selection_sort_gpu; knn_point = its first k columns over on-the-fly squared distances.  Coarse lattice: many exact ties."""
-    rng = np.random.RandomState(n + m + k)
-    dist = (rng.randint(0, 40, (2, m, n)) / 8.0).astype(np.float32)
+    dist, rng = top_k_inputs(n, m, k)
     wi, wo = oracle.select_top_k(k, dist)
     gi, go = ops.select_top_k(k, T(dist, dev))
     np.testing.assert_array_equal(gi.cpu().numpy(), wi)
     np.testing.assert_array_equal(go.cpu().numpy(), wo)
-    ri = torch.zeros((2, m, n), dtype=torch.int32, device=dev)
-    ro = torch.zeros((2, m, n), dtype=torch.float32, device=dev)
-    vp = ctypes.c_void_p
-    dt = T(dist, dev)
-    assert ref.ref_selection_sort(2, n, m, k, vp(dt.data_ptr()), vp(ri.data_ptr()), vp(ro.data_ptr())) == 0
-    np.testing.assert_array_equal(ri.cpu().numpy(), wi)
-    np.testing.assert_array_equal(ro.cpu().numpy(), wo)
+    assert digest(gi) == ref_ops("top_k/%d/%d/%d/idx" % (n, m, k))
+    assert digest(go) == ref_ops("top_k/%d/%d/%d/dist" % (n, m, k))
     if k <= n:
         x1, x2 = cloud(rng, 2, n, "coarse"), cloud(rng, 2, m, "coarse")
         wv, wx = oracle.knn_point(k, x1, x2)
@@ -205,27 +201,34 @@ def test_three_nn(ops, oracle, dev, n, m, kind):
     np.testing.assert_array_equal(gd.cpu().numpy(), wd)   # includes +inf slots when m < 3
 
 
-@pytest.mark.parametrize("n,m", [(128, 1), (77, 2), (512, 128), (1024, 512), (2048, 512), (300, 2500)])
-@pytest.mark.parametrize("kind", ["uniform", "grid", "coarse", "tiled"])
-def test_three_nn_and_interpolate_vs_reference_loops(ops, oracle, dev, n, m, kind):
-    """HIP == the reference's own threenn_cpu / threeinterpolate_cpu (tf_interpolate.cpp:60-127 compiled where it lies
-    into oracle/_ref/libancsh_ref_interp.so): distances, indices (incl. +inf / index-0 slots for m < 3) and interpolated
-    rows bit for bit."""
-    if not oracle.have_ref_interp():
-        pytest.skip("oracle/_ref/libancsh_ref_interp.so not built")
-    from articulated_pose_amd.tf_ops.tf_interpolate import three_weights
+REF_LOOP_SHAPES = [(128, 1), (77, 2), (512, 128), (1024, 512), (2048, 512), (300, 2500)]
+REF_LOOP_KINDS = ["uniform", "grid", "coarse", "tiled"]
+
+
+def ref_loop_inputs(n, m, kind):
+    """The two clouds and the interpolated points of test_three_nn_and_interpolate_vs_reference_loops."""
     rng = np.random.RandomState(n + 5 * m)
     x1, x2 = cloud(rng, 2, n, kind), cloud(rng, 2, m, kind)
     if kind == "tiled":
         x1[:, : min(n, m)] = x2[:, : min(n, m)]
-    rd, ri = oracle.ref_three_nn(x1, x2)
-    gd, gi = ops.three_nn(T(x1, dev), T(x2, dev))
-    np.testing.assert_array_equal(gi.cpu().numpy(), ri)
-    np.testing.assert_array_equal(gd.cpu().numpy(), rd)
-    w = three_weights(gd)
     pts = rng.randn(2, m, 40).astype(np.float32)
-    got = ops.three_interpolate(T(pts, dev), gi, w).cpu().numpy()
-    np.testing.assert_array_equal(got, oracle.ref_three_interpolate(pts, ri, w.cpu().numpy()))
+    return x1, x2, pts
+
+
+@pytest.mark.parametrize("n,m", REF_LOOP_SHAPES)
+@pytest.mark.parametrize("kind", REF_LOOP_KINDS)
+def test_three_nn_and_interpolate_vs_reference_loops(ops, oracle, dev, n, m, kind):
+    """HIP == the reference's own threenn_cpu / threeinterpolate_cpu (tf_interpolate.cpp:60-127): distances, indices (incl. +inf /
+    index-0 slots for m < 3) and interpolated rows bit for bit (the reference interpolated with the weights of its own distances)."""
+    from articulated_pose_amd.tf_ops.tf_interpolate import three_weights
+    x1, x2, pts = ref_loop_inputs(n, m, kind)
+    key = "loops/%s/%d/%d" % (kind, n, m)
+    gd, gi = ops.three_nn(T(x1, dev), T(x2, dev))
+    assert digest(gi) == ref_ops(key + "/idx")
+    assert digest(gd) == ref_ops(key + "/dist")
+    w = three_weights(gd)
+    got = ops.three_interpolate(T(pts, dev), gi, w)
+    assert digest(got) == ref_ops(key + "/out")
 
 
 def test_three_weights_and_interpolate(ops, oracle, dev):
@@ -249,45 +252,50 @@ def test_three_weights_and_interpolate(ops, oracle, dev):
 # ---- the reference's own CUDA sources, compiled by hipcc for gfx950 (oracle/_ref) -------------
 # Inputs on a 2^-8 lattice: every squared distance is exact in float32, so the result does not
 # depend on the compiler's FMA contraction; exact ties exercise the reference's tie-breaking.
-@pytest.mark.parametrize("kind", ["grid", "coarse", "tiled"])
-@pytest.mark.parametrize("n,m", [(1024, 512), (512, 128), (2048, 512), (3000, 100), (3500, 64)])
-def test_fps_vs_reference_kernel(ops, oracle, ref, dev, kind, n, m):
+FPS_KINDS = ["grid", "coarse", "tiled"]
+FPS_SHAPES = [(1024, 512), (512, 128), (2048, 512), (3000, 100), (3500, 64)]
+BALL_KINDS = ["grid", "coarse"]
+BALL_SHAPES = [(1024, 512, 0.2, 64), (512, 128, 0.4, 64), (2048, 300, 0.25, 32)]
+
+
+def fps_kernel_inputs(kind, n, m):
     rng = np.random.RandomState(n + m + 11)
     x = cloud(rng, 34, n, kind)     # 34 clouds > 32 blocks: exercises the reference's grid-stride loop
     if kind == "tiled":
         x = (np.round(x * 256) / 256).astype(np.float32)
-    xt = T(x, dev)
-    out = torch.zeros((34, m), dtype=torch.int32, device=dev)
-    temp = torch.zeros((32, n), dtype=torch.float32, device=dev)
-    rc = ref.ref_farthest_point_sample(34, n, m, ctypes.c_void_p(xt.data_ptr()), ctypes.c_void_p(temp.data_ptr()),
-                                       ctypes.c_void_p(out.data_ptr()))
-    assert rc == 0
-    want = out.cpu().numpy()
-    np.testing.assert_array_equal(ops.farthest_point_sample(m, xt).cpu().numpy(), want)
-    np.testing.assert_array_equal(oracle.farthest_point_sample(m, x[:4]), want[:4])
+    return x
 
 
-@pytest.mark.parametrize("kind", ["grid", "coarse"])
-@pytest.mark.parametrize("n,m,r,ns", [(1024, 512, 0.2, 64), (512, 128, 0.4, 64), (2048, 300, 0.25, 32)])
-def test_ball_query_group_vs_reference_kernel(ops, oracle, ref, dev, kind, n, m, r, ns):
+def ball_kernel_inputs(oracle, kind, n, m, r, ns):
+    """Clouds, their FPS centres and the features grouped by the indices."""
     rng = np.random.RandomState(n + m + 13)
     x = cloud(rng, 5, n, kind)
     q = oracle.gather_point(x, oracle.farthest_point_sample(m, x))
+    feats = np.random.RandomState(n + m + 17).randn(5, n, 16).astype(np.float32)
+    return x, q, feats
+
+
+@pytest.mark.parametrize("kind", FPS_KINDS)
+@pytest.mark.parametrize("n,m", FPS_SHAPES)
+def test_fps_vs_reference_kernel(ops, oracle, dev, kind, n, m):
+    x = fps_kernel_inputs(kind, n, m)
+    got = ops.farthest_point_sample(m, T(x, dev)).cpu().numpy()
+    assert digest(got) == ref_ops("fps_kernel/%s/%d/%d" % (kind, n, m))
+    np.testing.assert_array_equal(oracle.farthest_point_sample(m, x[:4]), got[:4])
+
+
+@pytest.mark.parametrize("kind", BALL_KINDS)
+@pytest.mark.parametrize("n,m,r,ns", BALL_SHAPES)
+def test_ball_query_group_vs_reference_kernel(ops, oracle, dev, kind, n, m, r, ns):
+    x, q, feats = ball_kernel_inputs(oracle, kind, n, m, r, ns)
+    key = "ball_kernel/%s/%d/%d/%g/%d" % (kind, n, m, r, ns)
     xt, qt = T(x, dev), T(q, dev)
-    idx = torch.zeros((5, m, ns), dtype=torch.int32, device=dev)
-    cnt = torch.zeros((5, m), dtype=torch.int32, device=dev)
-    vp = ctypes.c_void_p
-    assert ref.ref_query_ball_point(5, n, m, ctypes.c_float(r), ns, vp(xt.data_ptr()), vp(qt.data_ptr()),
-                                    vp(idx.data_ptr()), vp(cnt.data_ptr())) == 0
     gidx, gcnt = ops.query_ball_point(r, ns, xt, qt)
-    np.testing.assert_array_equal(gidx.cpu().numpy(), idx.cpu().numpy())
-    np.testing.assert_array_equal(gcnt.cpu().numpy(), cnt.cpu().numpy())
+    assert digest(gidx) == ref_ops(key + "/idx")
+    assert digest(gcnt) == ref_ops(key + "/cnt")
     widx, wcnt = oracle.query_ball_point(r, ns, x, q)
-    np.testing.assert_array_equal(widx, idx.cpu().numpy())
-    feats = torch.randn((5, n, 16), device=dev)
-    out = torch.zeros((5, m, ns, 16), device=dev)
-    assert ref.ref_group_point(5, n, 16, m, ns, vp(feats.data_ptr()), vp(idx.data_ptr()), vp(out.data_ptr())) == 0
-    assert torch.equal(ops.group_point(feats, idx), out)
+    np.testing.assert_array_equal(widx, gidx.cpu().numpy())
+    assert digest(ops.group_point(T(feats, dev), gidx)) == ref_ops(key + "/group")
 
 
 def test_argument_errors(ops, dev):
