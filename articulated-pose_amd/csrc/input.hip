@@ -45,6 +45,66 @@ __global__ __launch_bounds__(256) void input_sample_kernel(int num_points, int n
     }
 }
 
+// ---- the streaming sampler: graph-capturable, every size read from device memory (include/ancsh_hip.h) -------------------
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {     // the pose generator's finaliser (pose.hip)
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// the sampler's keys: bits 60..63 set, which no pose draw key (problem << 40 | iteration << 8 | k) has below 2^20 problems
+constexpr unsigned long long SAMPLE_TAG = 0xF000000000000000ull;
+
+// pi(i): a 4-round Feistel network on 2h bits (round r: L, R = R, L ^ (splitmix64(key[r] ^ R) & mask)), cycle-walked into [0, T):
+// a bijection of [0, 2^2h) restricted to the cycle of i until it lands below T, so a bijection of [0, T).  2^2h < 4T: < 4 walks
+// on average.
+__device__ __forceinline__ unsigned long long feistel_index(unsigned long long i, unsigned long long T, int h,
+                                                            const unsigned long long key[4]) {
+    const unsigned long long mask = (1ull << h) - 1ull;
+    unsigned long long x = i;
+    do {
+        unsigned long long L = x >> h, R = x & mask;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned long long t = L ^ (splitmix64(key[r] ^ R) & mask);
+            L = R;
+            R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= T);
+    return x;
+}
+
+// one thread per sampled row; the gathered source row (16 B for nchan = 4) of a cloud of a few thousand rows is L2-resident
+__global__ __launch_bounds__(256) void input_sample_stream_kernel(int num_points, int nchan, const float *__restrict__ rows,
+                                                                  long capacity, const int *__restrict__ offsets,
+                                                                  const float *__restrict__ norm_factor, int jcls_col,
+                                                                  const unsigned long long *__restrict__ seed, float *__restrict__ P,
+                                                                  int *__restrict__ joint_cls, int *__restrict__ perm_out) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_points) return;
+    const long r0 = offsets[b], r1 = offsets[b + 1];
+    if (r0 < 0 || r1 <= r0 || r1 > capacity) return;     // empty or outside the rows buffer (the host refuses both): outputs untouched
+    const unsigned long long n_raw = (unsigned long long)(r1 - r0), n = (unsigned long long)num_points;
+    const unsigned long long T = n_raw >= n ? n_raw : (n / n_raw + 1) * n_raw;      // the tiled size (lib/dataset.py:290-293)
+    int w = 0;
+    while ((1ull << w) < T) w += 2;
+    const unsigned long long s = *seed;
+    unsigned long long key[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) key[r] = splitmix64(s ^ splitmix64(SAMPLE_TAG | ((unsigned long long)b << 8) | (unsigned)r));
+    const unsigned long long t = feistel_index((unsigned long long)i, T, w / 2, key);
+    const float *src = rows + (size_t)(r0 + (long)(t % n_raw)) * nchan;
+    const float nf = norm_factor[b];
+    const size_t o = (size_t)b * num_points + i;
+    P[o * 3] = src[0] * nf;
+    P[o * 3 + 1] = src[1] * nf;
+    P[o * 3 + 2] = src[2] * nf;
+    joint_cls[o] = (int)src[jcls_col];                  // C truncation, as np.asarray(x, np.int32)
+    if (perm_out) perm_out[o] = (int)t;
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
@@ -67,4 +127,21 @@ extern "C" int ancsh_input_sample(int nclouds, int num_points, int nchan, const 
     hipLaunchKernelGGL(input_sample_kernel, dim3((unsigned)bx, nclouds), dim3(256), 0, (hipStream_t)stream, num_points, nchan, rows,
                        offsets, perm, norm_factor, cls_col, jcls_col, n_parts, P, chan_out, mask_array, joint_cls_mask);
     return check_launch("input_sample");
+}
+
+extern "C" int ancsh_input_sample_stream(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                                         const float *norm_factor, int jcls_col, const unsigned long long *seed, float *P,
+                                         int *joint_cls, int *perm_out, void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0 && num_points > 0 && num_points < (1 << 30), "input_sample_stream: bad shape nclouds=%d num_points=%d",
+                  nclouds, num_points);
+    ANCSH_REQUIRE(nchan >= 4, "input_sample_stream: rows need x y z and the joint-class channel (nchan=%d < 4)", nchan);
+    ANCSH_REQUIRE(jcls_col >= 3 && jcls_col < nchan, "input_sample_stream: jcls_col=%d must name a channel in [3,%d)", jcls_col, nchan);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "input_sample_stream: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(nclouds <= 65535, "input_sample_stream: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(seed, "input_sample_stream: null seed pointer");
+    ANCSH_REQUIRE(rows && offsets && norm_factor && P && joint_cls, "input_sample_stream: null pointer");
+    if (nclouds == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(input_sample_stream_kernel, dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream, num_points,
+                       nchan, rows, capacity, offsets, norm_factor, jcls_col, seed, P, joint_cls, perm_out);
+    return check_launch("input_sample_stream");
 }

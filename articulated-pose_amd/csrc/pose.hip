@@ -41,6 +41,13 @@ __device__ __forceinline__ int device_draw(unsigned long long seed, int prob, in
     const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)prob << 40) ^ ((unsigned long long)iter << 8) ^ (unsigned)k));
     return (int)(h % (unsigned long long)n);
 }
+// The generator key of a sampling kernel.  DSEED = false (the by-value entries): `arg` is the key itself.  DSEED = true (the
+// *_dseed entries): `arg` is the address of a uint64 in device memory, read here once per kernel -- a captured graph then replays
+// with whatever the host last wrote there -- plus `add` (1 in the stage-B kernels: the by-value caller passes seed + 1 itself).
+template <bool DSEED>
+__device__ __forceinline__ unsigned long long kernel_seed(unsigned long long arg, unsigned add) {
+    return DSEED ? *(const unsigned long long *__restrict__)arg + add : arg;
+}
 
 // ---- block reductions (256 threads = 4 waves) -----------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
@@ -212,10 +219,12 @@ __device__ __forceinline__ void load_draw3(const int *draws, unsigned long long 
 #endif
 constexpr int A_CHUNK = A_CHUNK_N;   // points staged per LDS pass (24 B each)
 
+template <bool DSEED>
 __global__ __launch_bounds__(256) void ransac_single_score_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                   const float *__restrict__ tgt, float th, int niter,
-                                                                  const int *__restrict__ draws, unsigned long long seed,
+                                                                  const int *__restrict__ draws, unsigned long long seed_arg,
                                                                   int *__restrict__ scores) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
     // structure-of-arrays tile so that ds_read_b128 hands each lane 4 consecutive points per coordinate and the residual
     // arithmetic runs on packed-f32 (v_pk_mul/fma/add_f32: two points per lane per instruction)
     __shared__ __attribute__((aligned(16))) float pl[6][A_CHUNK];
@@ -312,10 +321,12 @@ __global__ __launch_bounds__(256) void soa_quads_kernel(const int *__restrict__ 
 #else
 #define POSE_SCORE_ATTR
 #endif
+template <bool DSEED>
 __global__ __launch_bounds__(256) POSE_SCORE_ATTR void ransac_single_score_sreg_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                        const float *__restrict__ tgt, const float *__restrict__ quads,
                                                                        int cap_quads, float th, int niter, const int *__restrict__ draws,
-                                                                       unsigned long long seed, int *__restrict__ scores) {
+                                                                       unsigned long long seed_arg, int *__restrict__ scores) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
     const int prob = blockIdx.y, h = blockIdx.x * 256 + threadIdx.x;
     const int r0 = off[prob], n = off[prob + 1] - r0;
     // lanes without a hypothesis (past niter) score the identity model and drop the result: no divergence inside the point loop
@@ -496,13 +507,15 @@ __device__ __forceinline__ int compact_flagged(bool flag, int i, int n, const fl
     return base + total;
 }
 
+template <bool DSEED>
 __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                    const float *__restrict__ tgt, float th, int niter,
-                                                                   const int *__restrict__ draws, unsigned long long seed,
+                                                                   const int *__restrict__ draws, unsigned long long seed_arg,
                                                                    const int *__restrict__ scores, int max_n,
                                                                    double *__restrict__ out_model,
                                                                    unsigned char *__restrict__ out_inliers,
                                                                    int *__restrict__ out_best, FitExtras E) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *red = (double *)smem;                       // 64 doubles
     int *wcnt = (int *)(red + 64);                      // 4 ints for compact_flagged + 4 for the tie counts
@@ -852,10 +865,12 @@ __device__ __forceinline__ void load_hyp_samples(const float *__restrict__ src, 
         }
 }
 
+template <bool DSEED>
 __global__ __launch_bounds__(64) void ransac_joint_init_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                const float *__restrict__ src, const float *__restrict__ tgt,
-                                                               int niter, const int *__restrict__ draws, unsigned long long seed,
+                                                               int niter, const int *__restrict__ draws, unsigned long long seed_arg,
                                                                double *__restrict__ scores, double *__restrict__ models) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
     const int prob = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -884,11 +899,13 @@ constexpr int HYP_CHUNK_SMALL = 64;   // ... of a launch too small to fill the c
 constexpr long HYP_SMALL_LAUNCH = 8192;   // fits per launch up to which the small chunk is used
 constexpr int HYP_REFILL = 16;    // idle lanes that trigger a refill (a refill costs the whole wave ~1 trip of latency)
 
+template <bool DSEED>
 __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                              const float *__restrict__ src, const float *__restrict__ tgt,
                                                              const float *__restrict__ joint_dir, int niter,
-                                                             const int *__restrict__ draws, unsigned long long seed,
+                                                             const int *__restrict__ draws, unsigned long long seed_arg,
                                                              double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
     const int prob = blockIdx.y;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -1085,11 +1102,13 @@ struct HypProblemCoop {
     }
 };
 
+template <bool DSEED>
 __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                   const float *__restrict__ src, const float *__restrict__ tgt,
                                                                   const float *__restrict__ joint_dir, int niter,
-                                                                  const int *__restrict__ draws, unsigned long long seed,
+                                                                  const int *__restrict__ draws, unsigned long long seed_arg,
                                                                   double *__restrict__ models, int *__restrict__ lm_stat) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
     __shared__ double xch[64 / COOP_G][COOP_XCH];
     const int prob = blockIdx.y, lane = threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
@@ -1142,10 +1161,12 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__r
     }
 }
 
+template <bool DSEED>
 __global__ __launch_bounds__(64) void ransac_joint_model_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                 const float *__restrict__ src, const float *__restrict__ tgt,
-                                                                int niter, const int *__restrict__ draws, unsigned long long seed,
+                                                                int niter, const int *__restrict__ draws, unsigned long long seed_arg,
                                                                 double *__restrict__ models) {
+    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
     const int prob = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -1299,6 +1320,7 @@ __device__ __forceinline__ void block_prep_part(float (*cs)[3], float (*ct)[3], 
     quat_to_rotvec(q, rv);
 }
 
+template <bool DSEED>
 __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                   const float *__restrict__ src, const float *__restrict__ tgt,
                                                                   const float *__restrict__ joint_dir, double th, int niter,
@@ -1373,14 +1395,15 @@ __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__r
         m1 = compact_flagged(f, i, n1, src, tgt, (size_t)a1, c1s, c1t, m1, wcnt);
     }
     if (E.tie) {                                       // block-uniform; one inlier of either part moves the joint score by 1/6 (:192)
+        const unsigned long long tseed = kernel_seed<DSEED>(E.seed, 1);
         const double *sp = scores + (size_t)prob * niter;
         const double near = best_score - (1.0 / 6.0 + 1e-9);
         for (int h = threadIdx.x; h < niter + 255 - (niter + 255) % 256; h += 256) {
             bool degenerate = false;
             if (h < niter && sp[h] >= near) {
                 int i0[3], i1[3];
-                load_draw3(E.draws, E.seed, prob, niter, h, 0, 6, n0, i0);
-                load_draw3(E.draws, E.seed, prob, niter, h, 3, 6, n1, i1);
+                load_draw3(E.draws, tseed, prob, niter, h, 0, 6, n0, i0);
+                load_draw3(E.draws, tseed, prob, niter, h, 3, 6, n1, i1);
                 degenerate = i0[0] == i0[1] || i0[0] == i0[2] || i0[1] == i0[2] || i1[0] == i1[1] || i1[0] == i1[2] || i1[1] == i1[2];
             }
             n_near += __popcll(__ballot(degenerate));
@@ -1918,6 +1941,7 @@ extern "C" long ancsh_ransac_single_quads_floats(long rows, int nprob) {
     return 24 * single_quads_needed(rows, nprob);
 }
 
+template <bool DSEED>
 static int ransac_single_impl(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
                               const int *draws, unsigned long long seed, int max_n, double *out_model,
                               unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
@@ -1937,15 +1961,15 @@ static int ransac_single_impl(int nprob, const int *off, const float *src, const
         ANCSH_REQUIRE((((uintptr_t)scratch_quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
         const int cap = (int)single_quads_needed(rows, nprob);
         hipLaunchKernelGGL(soa_quads_kernel, dim3((max_n + 7 + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, scratch_quads, cap);
-        hipLaunchKernelGGL(ransac_single_score_sreg_kernel, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
+        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<DSEED>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
                            (const float *)scratch_quads, cap, inlier_th, niter, draws, seed, scratch_scores);
     } else {
-        hipLaunchKernelGGL(ransac_single_score_kernel, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, inlier_th,
+        hipLaunchKernelGGL(ransac_single_score_kernel<DSEED>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, inlier_th,
                            niter, draws, seed, scratch_scores);
     }
     const size_t lds = 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_single_finish_kernel, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel<DSEED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ransac_single_finish_kernel<DSEED>, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
                        scratch_scores, max_n, out_model, out_inliers, out_best, E);
     return check_launch("ransac_single");
 }
@@ -1953,8 +1977,8 @@ static int ransac_single_impl(int nprob, const int *off, const float *src, const
 extern "C" int ancsh_ransac_single(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
                                    const int *draws, unsigned long long seed, int max_n, double *out_model,
                                    unsigned char *out_inliers, int *out_best, int *scratch_scores, void *stream) {
-    return ransac_single_impl(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                              scratch_scores, nullptr, 0, no_extras(), stream);
+    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+                                     scratch_scores, nullptr, 0, no_extras(), stream);
 }
 
 // The same call with the hypotheses scored from SCALAR registers: scratch_quads (32-byte aligned, ancsh_ransac_single_quads_floats(rows,
@@ -1965,8 +1989,8 @@ extern "C" int ancsh_ransac_single_ex(int nprob, const int *off, const float *sr
                                       unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
                                       long rows, void *stream) {
     ANCSH_REQUIRE(scratch_quads, "ransac_single_ex: scratch_quads is NULL (ancsh_ransac_single is the call without it)");
-    return ransac_single_impl(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                              scratch_scores, scratch_quads, rows, no_extras(), stream);
+    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+                                     scratch_scores, scratch_quads, rows, no_extras(), stream);
 }
 
 // ancsh_ransac_single_ex (scratch_quads != NULL) / ancsh_ransac_single (NULL) that ALSO writes each fit straight into the pose record
@@ -1977,10 +2001,11 @@ extern "C" int ancsh_ransac_single_rec(int nprob, const int *off, const float *s
                                        long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_single_rec", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                              scratch_scores, scratch_quads, rows, E, stream);
+    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+                                     scratch_scores, scratch_quads, rows, E, stream);
 }
 
+template <bool DSEED>
 static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
                              const float *joint_dir, double inlier_th, int niter, const int *draws,
                              unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
@@ -1996,7 +2021,7 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
     ANCSH_REQUIRE(inlier_th > 0.0, "ransac_joint: inlier_th must be positive");
     inlier_th = sq_threshold_f64(inlier_th);      // the kernels compare squared residuals
     const dim3 per_hyp((niter + 63) / 64, nprob);
-    hipLaunchKernelGGL(ransac_joint_init_kernel, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
+    hipLaunchKernelGGL(ransac_joint_init_kernel<DSEED>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
                        scratch_models);
     // Two schedules of the same fits (identical MINPACK state machine, results equal to ~1e-7, not to the last bit: the eight-lane
     // callbacks are a different instruction stream and the f64 code is compiled with contraction on):
@@ -2007,19 +2032,19 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
     //     (measured on 64 x 200 fits: 1.27 vs 1.6 ms; the tail is MINPACK's serial lmpar on rank-deficient samples, which no lane
     //     split shortens) at ~5 % lower pipeline throughput.
     if (lm_schedule == ANCSH_LM_LATENCY) {
-        hipLaunchKernelGGL(ransac_joint_lm_coop_kernel, dim3((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob), dim3(64), 0, st,
+        hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<DSEED>, dim3((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob), dim3(64), 0, st,
                            rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
     } else {
         const int chunk = (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK;
-        hipLaunchKernelGGL(ransac_joint_lm_kernel, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
+        hipLaunchKernelGGL(ransac_joint_lm_kernel<DSEED>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
                            joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
     }
-    hipLaunchKernelGGL(ransac_joint_model_kernel, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
+    hipLaunchKernelGGL(ransac_joint_model_kernel<DSEED>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
     hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, inlier_th,
                        niter, scratch_models, scratch_scores);
     const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_joint_finish_kernel, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<DSEED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ransac_joint_finish_kernel<DSEED>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
                        niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
     return check_launch("ransac_joint");
 }
@@ -2029,8 +2054,8 @@ extern "C" int ancsh_ransac_joint(int nprob, const int *rng0, const int *rng1, c
                                   unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
                                   int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
                                   int *lm_stat, void *stream) {
-    return ransac_joint_impl(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                             out_best, out_score, scratch_scores, scratch_models, lm_stat, ANCSH_LM_AUTO, no_extras(), stream);
+    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, ANCSH_LM_AUTO, no_extras(), stream);
 }
 
 extern "C" int ancsh_ransac_joint_ex(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
@@ -2038,8 +2063,8 @@ extern "C" int ancsh_ransac_joint_ex(int nprob, const int *rng0, const int *rng1
                                      unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
                                      int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
                                      int *lm_stat, int lm_schedule, void *stream) {
-    return ransac_joint_impl(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                             out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, no_extras(), stream);
+    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, no_extras(), stream);
 }
 
 extern "C" int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
@@ -2051,8 +2076,35 @@ extern "C" int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_joint_rec", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
     E.draws = draws; E.seed = seed;
-    return ransac_joint_impl(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                             out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
+    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
+}
+
+// ancsh_ransac_single_rec / ancsh_ransac_joint_rec with the generator key read from device memory (include/ancsh_hip.h): the kernels
+// are the by-value ones instantiated with DSEED = true, the key travels as the address in the same 64-bit argument
+extern "C" int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+                                             const int *draws, const unsigned long long *seed, int max_n, double *out_model,
+                                             unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
+                                             long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
+    ANCSH_REQUIRE(seed, "ransac_single_rec_dseed: null seed pointer");
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_single_rec_dseed", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
+    return ransac_single_impl<true>(nprob, off, src, tgt, inlier_th, niter, draws, (unsigned long long)(uintptr_t)seed, max_n, out_model,
+                                    out_inliers, out_best, scratch_scores, scratch_quads, rows, E, stream);
+}
+
+extern "C" int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                            const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                            const unsigned long long *seed, int max_n, double *out_model, unsigned char *out_inliers,
+                                            int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
+                                            int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
+                                            void *stream) {
+    ANCSH_REQUIRE(seed, "ransac_joint_rec_dseed: null seed pointer");
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_joint_rec_dseed", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
+    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)seed;
+    return ransac_joint_impl<true>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
+                                   out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
 }
 
 extern "C" int ancsh_umeyama(int nprob, const int *off, const float *src, const float *tgt, double *out, void *stream) {

@@ -90,3 +90,58 @@ def create_unit_data_batch(clouds, num_points, norm_factors, n_parts, perms=None
     for key, c0, w in _OUT:
         out[key] = chan[:, :, c0] if w == 1 else chan[:, :, c0:c0 + w]
     return out
+
+
+# ---- raw clouds for the streaming pipeline ---------------------------------------------------------------------------------
+RAW_NCHAN, RAW_JCLS_COL = 4, 3      # a raw cloud row: x y z joint_cls (a pack_cloud row sliced with [:, [0, 1, 2, 17]])
+
+
+def check_raw_clouds(clouds, norm_factors, max_clouds=None):
+    """Validate a batch of raw clouds before anything is enqueued: 1..max_clouds non-empty (n_raw, 4) arrays and one finite
+    norm factor per cloud.  -> (list of contiguous float32 (n_raw, 4) arrays, float32 (B,) norm factors); ValueError otherwise."""
+    if not isinstance(clouds, (list, tuple)):
+        raise ValueError("clouds must be a list of (n_raw, 4) arrays")
+    if not 1 <= len(clouds) <= (max_clouds or 65535):
+        raise ValueError("a batch holds 1..%d clouds, got %d" % (max_clouds or 65535, len(clouds)))
+    out = []
+    for i, c in enumerate(clouds):
+        c = np.ascontiguousarray(c.cpu().numpy() if torch.is_tensor(c) else c, np.float32)
+        if c.ndim != 2 or c.shape[1] != RAW_NCHAN or c.shape[0] == 0:
+            raise ValueError("cloud %d: expected a non-empty (n_raw, %d) array [x y z joint_cls], got shape %s" % (i, RAW_NCHAN, c.shape))
+        out.append(c)
+    nf = np.asarray(norm_factors, np.float32).reshape(-1)
+    if nf.size != len(out) or not np.isfinite(nf).all():
+        raise ValueError("norm_factors: one finite value per cloud (%d clouds, got %s)" % (len(out), nf.tolist()))
+    return out, nf
+
+
+def seed_bits(seed):
+    """The uint64 generator key `seed` as the int64 with the same bits (how the device buffers hold it)."""
+    return int(np.uint64(int(seed) % (1 << 64)).view(np.int64))
+
+
+def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", return_perm=False):
+    """Eager wrapper of the streaming sampler (ancsh_input_sample_stream, include/ancsh_hip.h): clouds = list of (n_raw, 4) float32
+    arrays [x y z joint_cls]; cloud b's num_points rows are raw rows pi_b(i) % n_raw for the keyed bijection pi_b of the tiled cloud
+    (the reference's tiling rule, tiled_size) drawn from `seed` (uint64).
+    -> dict(P (B,N,3) float32 = xyz * norm_factor, joint_cls (B,N) int32 [, perm (B,N) int32 = pi_b(i)]) on `device`."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    clouds, nf = check_raw_clouds(clouds, norm_factors)
+    B = len(clouds)
+    offsets = np.zeros(B + 1, np.int32)
+    offsets[1:] = np.cumsum([c.shape[0] for c in clouds])
+    rows = torch.from_numpy(np.concatenate(clouds, axis=0)).to(dev)
+    off = torch.from_numpy(offsets).to(dev)
+    nf_d = torch.from_numpy(nf).to(dev)
+    seed_d = torch.tensor([seed_bits(seed)], dtype=torch.int64, device=dev)
+    P = torch.empty((B, num_points, 3), dtype=torch.float32, device=dev)
+    jcls = torch.empty((B, num_points), dtype=torch.int32, device=dev)
+    perm = torch.empty((B, num_points), dtype=torch.int32, device=dev) if return_perm else None
+    _lib.call("ancsh_input_sample_stream", B, int(num_points), RAW_NCHAN, _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(off),
+              _lib.ptr(nf_d), RAW_JCLS_COL, _lib.ptr(seed_d), _lib.ptr(P), _lib.ptr(jcls), _lib.ptr(perm))
+    out = dict(P=P, joint_cls=jcls)
+    if return_perm:
+        out["perm"] = perm
+    return out

@@ -6,8 +6,11 @@
     pose fit       (per-part RANSAC + articulated LM)      evaluation/pose_multi_process.py
 
 The whole step is ~100 asynchronous launches on one HIP stream; `AncshPipeline` captures them once
-into a hipGraph and replays it per batch.
+into a hipGraph and replays it per batch.  With `raw_capacity` set the captured step starts from raw clouds of any size
+(sampled on the GPU) and draws a fresh RANSAC sample stream per batch: submit() / retire() / stream_batches().
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -39,7 +42,7 @@ def check_hardware_queues(slots):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device):
+    def __init__(self, B, N, K, device, raw_capacity=None):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -50,6 +53,32 @@ class _Slot(object):
         self.stream = torch.cuda.Stream(device=device)
         self.graph = None
         self.out = None
+        if raw_capacity is not None:
+            # streaming: raw rows + a header [seed (int64 bits) | offsets (B+1) int32 | norm factors (B) float32] on the device, their
+            # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again
+            from .dataset import RAW_NCHAN
+            self.raw_rows = torch.zeros((raw_capacity, RAW_NCHAN), **f)
+            self.hdr = torch.zeros((2 + (B + 1) + B,), dtype=torch.int32, device=device)
+            self.h_rows = torch.zeros((raw_capacity, RAW_NCHAN), dtype=torch.float32).pin_memory()
+            self.h_hdr = torch.zeros((2 + (B + 1) + B,), dtype=torch.int32).pin_memory()
+            self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
+            self.h2d_done = torch.cuda.Event()
+            self.d2h_done = torch.cuda.Event()
+            hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
+            self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[2:B + 3],
+                                                                   hdr[B + 3:2 * B + 3].view(np.float32))
+            # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
+            rs = np.random.RandomState(0)
+            self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
+            self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
+            self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
+            self.np_nf[:] = 1.0
+            self.raw_rows.copy_(self.h_rows)
+            self.hdr.copy_(self.h_hdr)
+
+    def header(self, B):
+        """(seed (1,) int64, offsets (B+1,) int32, norm factors (B,) float32) views of the device header."""
+        return self.hdr[:2].view(torch.int64), self.hdr[2:B + 3], self.hdr[B + 3:2 * B + 3].view(torch.float32)
 
 
 class AncshPipeline(object):
@@ -77,8 +106,17 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None):
+                 arithmetic=None, raw_capacity=None):
         self.K, self.B, self.N = num_parts, batch_size, num_points
+        # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
+        # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls) per batch, padding included
+        if raw_capacity is not None:
+            if not couple:
+                raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
+            if not 1 <= int(raw_capacity) < (1 << 30):
+                raise ValueError("raw_capacity must be in [1, 2^30) rows")
+            raw_capacity = int(raw_capacity)
+        self.raw_capacity = raw_capacity
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
@@ -102,10 +140,13 @@ class AncshPipeline(object):
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device) for _ in range(max(1, slots))]
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
+        self._prepared = False
+        self._inflight = collections.deque()       # (slot, tag, seed, valid clouds) of submitted, unretired batches, oldest first
+        self._submitted = 0
 
     # single-slot conveniences (slot 0)
     @property
@@ -133,8 +174,18 @@ class AncshPipeline(object):
             return self.paired.predict(P, geom)          # every backbone layer of both networks in one grouped launch
         return self.ancsh.predict(P, geom), self.npcs.predict(P, geom)
 
+    def _sample(self, sl):
+        """The captured step's first launch when streaming: the slot's raw clouds -> its P / joint_cls."""
+        from . import _lib
+        from .dataset import RAW_JCLS_COL, RAW_NCHAN
+        seed, off, nf = sl.header(self.B)
+        _lib.call("ancsh_input_sample_stream", self.B, self.N, RAW_NCHAN, _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off),
+                  _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P), _lib.ptr(sl.joint_cls), None)
+        return seed
+
     def _run(self, sl=None):
         sl = sl or self.slots[0]
+        seed_dev = self._sample(sl) if self.raw_capacity is not None else None
         from . import pointnet_util
         geom = pointnet_util.Geometry()       # FPS / ball query / 3-NN depend only on P: computed once, used by both nets
         if self.arithmetic is None:
@@ -151,7 +202,7 @@ class AncshPipeline(object):
             nocs, mask, axis = n["nocs_per_point"], n["W"], a["joint_axis_per_point"]
         else:
             nocs, mask, axis = sl.pred_nocs, sl.pred_mask, sl.pred_axis
-        sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed)
+        sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev)
         return dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
 
     def prepare(self):
@@ -174,6 +225,7 @@ class AncshPipeline(object):
                     with torch.cuda.stream(sl.stream):
                         sl.graph.replay()
             self.synchronize()
+        self._prepared = True
         return self
 
     def next_slot(self):
@@ -202,3 +254,71 @@ class AncshPipeline(object):
     def synchronize(self):
         for sl in self.slots:
             sl.stream.synchronize()
+
+    # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
+    def submit(self, clouds, norm_factors, seed=None, tag=None):
+        """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
+        sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.  A short batch
+        is padded with copies of its first cloud, whose records retire() drops.  seed: the generator key of the batch's sampling and
+        of its pose fit (stage B uses seed + 1); None = self.seed + 2k for the k-th submitted batch (2k + 1 is its stage B).
+        Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
+        RuntimeError.  Either way the pipeline stays usable."""
+        if self.raw_capacity is None:
+            raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
+        from .dataset import check_raw_clouds, seed_bits
+        clouds, nf = check_raw_clouds(clouds, norm_factors, self.B)
+        n_valid = len(clouds)
+        padded = clouds + [clouds[0]] * (self.B - n_valid)
+        rows = sum(c.shape[0] for c in padded)
+        if rows > self.raw_capacity:
+            raise ValueError("the batch needs %d raw rows (short batches are padded with their first cloud), raw_capacity is %d"
+                             % (rows, self.raw_capacity))
+        if len(self._inflight) == len(self.slots):
+            raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
+        if not self._prepared:
+            self.prepare()
+        seed = self.seed + 2 * self._submitted if seed is None else int(seed)
+        sl = self.slots[self._next]
+        sl.h2d_done.synchronize()                  # the previous batch's copies out of the pinned staging have completed
+        sl.np_seed[0] = seed_bits(seed)
+        np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
+        sl.np_off[0] = 0
+        np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
+        sl.np_nf[:n_valid] = nf
+        sl.np_nf[n_valid:] = nf[0]
+        cur = torch.cuda.current_stream(self.device)
+        if cur != sl.stream and not cur.query():
+            sl.stream.wait_stream(cur)
+        with torch.cuda.stream(sl.stream):
+            sl.raw_rows[:rows].copy_(sl.h_rows[:rows], non_blocking=True)
+            sl.hdr.copy_(sl.h_hdr, non_blocking=True)
+            sl.h2d_done.record(sl.stream)
+            if sl.graph is not None:
+                sl.graph.replay()
+            else:
+                sl.out = self._run(sl)
+            # right behind the replay on the same stream: the next replay's pool reuses the record's block (see step())
+            sl.h_record.copy_(sl.out["record"], non_blocking=True)
+            sl.d2h_done.record(sl.stream)
+        self._next = (self._next + 1) % len(self.slots)
+        self._submitted += 1
+        self._inflight.append((sl, tag, seed, n_valid))
+
+    def retire(self):
+        """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
+        records, a fresh host array."""
+        if not self._inflight:
+            raise RuntimeError("retire(): no batch in flight")
+        sl, tag, seed, n_valid = self._inflight.popleft()
+        sl.d2h_done.synchronize()
+        return tag, seed, sl.h_record[:n_valid].numpy().copy()
+
+    def stream_batches(self, batches):
+        """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
+        batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order."""
+        for k, item in enumerate(batches):
+            if len(self._inflight) == len(self.slots):
+                yield self.retire()
+            self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
+        while self._inflight:
+            yield self.retire()

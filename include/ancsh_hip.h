@@ -41,7 +41,8 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 7 since round 6 (5: round 5, 4: round 4, 3: round 3).  Operator entry points are only ever added: a library of version v serves every caller
+int ancsh_abi_version(void);   /* 8: + ancsh_input_sample_stream, ancsh_ransac_single_rec_dseed, ancsh_ransac_joint_rec_dseed (the streaming pipeline);
+                                 * 7 since round 6 (5: round 5, 4: round 4, 3: round 3).  Operator entry points are only ever added: a library of version v serves every caller
                                  * written for <= v.  The one removal, in 7: ancsh_hbm_copy -- bench.py's HBM-copy yardstick, never an operator -- left the library
                                  * (tools/microbench/membw.hip, its own .so) */
 const char *ancsh_last_error(void);
@@ -534,6 +535,22 @@ int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng1, const fl
                            double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
                            int *tie_stats, double tie_window, void *stream);
 
+/* ancsh_ransac_single_rec / ancsh_ransac_joint_rec with the generator key in DEVICE memory: `seed` points at one uint64 that the
+ * kernels read when they run, so a captured graph replays with whatever the host last wrote there (a fresh sample stream per batch;
+ * the by-value key is frozen into the graph).  Stage A uses *seed, stage B *seed + 1 -- the pair PoseSolver.solve(seed=s) passes to
+ * the by-value entries (s, s + 1) -- so solve(seed_dev=[s]) gives the bytes of solve(seed=s).  Explicit draws still override the
+ * generator.  The kernels are the by-value ones instantiated with the key read once per kernel; the by-value entries are unchanged
+ * (same code, registers and occupancy: profiles/r07_pose_resource_usage_{before,after}.txt).  seed == NULL is refused. */
+int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+                                  const int *draws, const unsigned long long *seed, int max_n, double *out_model,
+                                  unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
+                                  double *record, int K, int *tie_stats, float tie_window, void *stream);
+int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                 const float *joint_dir, double inlier_th, int niter, const int *draws, const unsigned long long *seed,
+                                 int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
+                                 double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+                                 int *tie_stats, double tie_window, void *stream);
+
 /* Batched estimateSimilarityUmeyama (lib/aligning.py:580-622; GT poses of evaluation/compute_gt_pose.py:87).
  * Problem p = rows [off[p], off[p+1]) of src/tgt.  out (nprob,32) float64: Scales(3) | Rotation(9, the
  * reference's TRANSPOSED matrix) | Translation(3) | OutTransform (4x4 row-major, 16) | pad(1). */
@@ -590,6 +607,26 @@ int ancsh_part_extents(int b, int n, int K, int nocs_channels, const float *nocs
 int ancsh_input_sample(int nclouds, int num_points, int nchan, const float *rows, const int *offsets, const int *perm,
                        const float *norm_factor, int cls_col, int jcls_col, int n_parts, float *P, float *chan_out,
                        float *mask_array, float *joint_cls_mask, void *stream);
+
+/* The sampler of the streaming pipeline: one launch per batch in which every size-dependent value is read from DEVICE memory,
+ * so one captured graph serves any cloud sizes up to `capacity` rows.  Cloud b owns raw rows [offsets[b], offsets[b+1]) of `rows`
+ * (capacity x nchan float32: x y z, then channels; nchan >= 4).  With n_raw = offsets[b+1] - offsets[b] and N = num_points, the
+ * reference's tiled size (lib/dataset.py:290-293) is T = n_raw if n_raw >= N else (N / n_raw + 1) * n_raw, and sampled row i of
+ * cloud b is raw row pi_b(i) % n_raw, where pi_b is a keyed bijection of [0, T) -- so the N rows are N distinct rows of the tiled
+ * cloud, as np.random.permutation(T)[:N] picks them (:341-351), without a sort, a scan or per-cloud host work:
+ *   w  = the smallest even number with 2^w >= T, h = w / 2, mask = 2^h - 1;
+ *   key[r] = splitmix64(s ^ splitmix64(0xF000000000000000 | b << 8 | r)), r = 0..3, s = *seed (uint64, device memory);
+ *   F(x): L = x >> h, R = x & mask; four rounds of  (L, R) = (R, L ^ (splitmix64(key[r] ^ R) & mask)); F(x) = L << h | R;
+ *   pi_b(i) = the first of F(i), F(F(i)), ... that is < T (cycle walking: 2^w < 4T, < 4 rounds of F on average).
+ * splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ * (all mod 2^64; the pose generator's finaliser; the tag bits 60..63 keep the sampler's keys apart from its draw keys).
+ * Outputs: P (nclouds, N, 3) = xyz * norm_factor[b] (:346); joint_cls (nclouds, N) int32 = the C truncation of channel jcls_col
+ * (np.asarray(x, np.int32)); perm_out (nclouds, N) int32 = pi_b(i) (NULL: not written).  A cloud with n_raw == 0 or rows outside
+ * [0, capacity) leaves its outputs untouched (callers refuse such clouds on the host).  Checked before any launch: nchan >= 4,
+ * 3 <= jcls_col < nchan, 0 <= capacity < 2^30, nclouds <= 65535 (grid), null pointers (perm_out may be NULL). */
+int ancsh_input_sample_stream(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                              const float *norm_factor, int jcls_col, const unsigned long long *seed, float *P, int *joint_cls,
+                              int *perm_out, void *stream);
 
 /* ---- test-time losses of predict_and_save (lib/network.py:430-498, lib/loss.py:54-182) ------- */
 
