@@ -55,6 +55,13 @@ SIGNATURES = {
     "ancsh_fp1_chain_grouped_f16x2": [_c_int] * 6 + [_vp] * 4 + [_vp],
     "ancsh_fp2_chain_grouped_bf16x3": [_c_int] * 8 + [_vp] * 6 + [_vp],
     "ancsh_fp2_chain_grouped_f16x2": [_c_int] * 8 + [_vp] * 6 + [_vp],
+    # the F16x2 range guard: the unguarded arguments + (unsigned *range_flags, int flag_bit0) before the stream
+    "ancsh_sa_module_fused_f16x2_grouped_guarded": [_c_int] * 9 + [_vp] * 4 + [_vp, _vp, _vp, _c_int, _vp],
+    "ancsh_sa_module_fused_partial_f16x2_grouped_guarded": [_c_int] * 8 + [_vp] * 6 + [_vp, _c_int, _vp],
+    "ancsh_mlp_chain_grouped_fp_f16x2_guarded": [_c_int] * 5 + [_vp] * 7 + [_vp, _c_int, _vp],
+    "ancsh_sa3_chain_grouped_f16x2_guarded": [_c_int] * 7 + [_vp] * 4 + [_vp, _c_int, _vp],
+    "ancsh_fp1_chain_grouped_f16x2_guarded": [_c_int] * 6 + [_vp] * 4 + [_vp, _c_int, _vp],
+    "ancsh_fp2_chain_grouped_f16x2_guarded": [_c_int] * 8 + [_vp] * 6 + [_vp, _c_int, _vp],
     "ancsh_iou_3d": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_joint_params": [_c_int] * 5 + [_vp] * 9 + [_vp],
     "ancsh_part_extents": [_c_int] * 4 + [_vp] * 3 + [_c_int] + [_vp] * 4 + [_vp],

@@ -38,7 +38,7 @@ def _head_dims(K, mixed_pred, early_split_nocs):
     return out_dims, all(n <= 32 for n in head_widths)
 
 
-def _fused_tail(scope, P, K, mixed_pred, early_split_nocs):
+def _fused_tail(scope, P, K, mixed_pred, early_split_nocs, arith=None):
     """build_pointnet2_shared up to fa_layer2, then fa_layer3's interpolation and EVERYTHING after it (three
     fa_layer3 convs, fc1, nocs_net, joint_net) as one kernel.  Returns the logits matrix (rows, ld) in the layout
     ancsh_head_activations expects, or None when the shapes are not the ANCSH ones."""
@@ -49,9 +49,9 @@ def _fused_tail(scope, P, K, mixed_pred, early_split_nocs):
     with tf_util.variable_scope('est_net'):
         l0_xyz = P
         l1_xyz, l1_points, _ = pu.pointnet_sa_module(l0_xyz, P[:, :, 3:3], npoint=512, radius=0.2, nsample=64, mlp=[64, 64, 128],
-                                                      mlp2=None, group_all=False, is_training=False, bn_decay=None, scope='layer1')
+                                                      mlp2=None, group_all=False, is_training=False, bn_decay=None, scope='layer1', arith=arith)
         l2_xyz, l2_points, _ = pu.pointnet_sa_module(l1_xyz, l1_points, npoint=128, radius=0.4, nsample=64, mlp=[128, 128, 256],
-                                                      mlp2=None, group_all=False, is_training=False, bn_decay=None, scope='layer2')
+                                                      mlp2=None, group_all=False, is_training=False, bn_decay=None, scope='layer2', arith=arith)
         l3_xyz, l3_points, _ = pu.pointnet_sa_module(l2_xyz, l2_points, npoint=None, radius=None, nsample=None,
                                                       mlp=[256, 512, 1024], mlp2=None, group_all=True, is_training=False,
                                                       bn_decay=None, scope='layer3')
@@ -65,11 +65,12 @@ def _fused_tail(scope, P, K, mixed_pred, early_split_nocs):
 CH_SAVE, CH_RESTORE = 1, 2       # ancsh_mlp_chain_grouped op flags
 
 
-def _bf16x3_head_params(layer):
-    """a head block (128 -> n <= 32) for ancsh_mlp_chain_grouped_fp_bf16x3 / _f16x2: kernel padded to 32 columns and split into the active
-    scheme's planes, bias / scale / shift padded to 32 entries; cached on the layer dict (per scheme)"""
+def _bf16x3_head_params(layer, scheme=None):
+    """a head block (128 -> n <= 32) for ancsh_mlp_chain_grouped_fp_bf16x3 / _f16x2: kernel padded to 32 columns and split into the
+    scheme's planes (None: the active one), bias / scale / shift padded to 32 entries; cached on the layer dict (per scheme)"""
     from . import pointnet_util
-    key = "split_head_" + pointnet_util.SPLIT_SCHEME
+    scheme = pointnet_util.SPLIT_SCHEME if scheme is None else scheme
+    key = "split_head_" + scheme
     if key not in layer:
         w = layer["w"]
         k, n = w.shape
@@ -77,11 +78,11 @@ def _bf16x3_head_params(layer):
         w32 = torch.zeros((k, 32), dtype=torch.float32, device=dev)
         w32[:, :n] = w
         pad = lambda v, fill: torch.cat([v, torch.full((32 - n,), fill, dtype=torch.float32, device=dev)]).contiguous()
-        layer[key] = (pointnet_util._split_pack(w32), pad(layer["b"], 0.0), pad(layer["scale"], 1.0), pad(layer["shift"], 0.0))
+        layer[key] = (pointnet_util._split_pack(w32, scheme), pad(layer["b"], 0.0), pad(layer["scale"], 1.0), pad(layer["shift"], 0.0))
     return layer[key]
 
 
-def _tail_program(rows, K, mixed_pred, early_split_nocs, dev, bf16x3=False):
+def _tail_program(rows, K, mixed_pred, early_split_nocs, dev, bf16x3=False, scheme=None):
     """The one-tile chain program of ONE network (called inside its outer variable scope, the reference's 'SPFN'): fa_layer3's three
     convs, fc1 and every head, each layer rewriting the wave's tile in place.  The trunk `net` (fc1's output) has two 128-wide
     consumers only with early_split_nocs (fc11_1 and fc3_0, lib/architecture.py:111,198): fc1 then carries CH_SAVE and fc3_0
@@ -102,7 +103,8 @@ def _tail_program(rows, K, mixed_pred, early_split_nocs, dev, bf16x3=False):
         if bf16x3:
             # opt-in experiment (csrc/tail_bf16x3.hip): bf16x3-packed kernels; two register tiles, so no save / restore flags
             from . import pointnet_util
-            par = _bf16x3_head_params(layer) if out is not None else (pointnet_util._bf16x3_weight(layer), layer["b"], layer["scale"], layer["shift"])
+            par = (_bf16x3_head_params(layer, scheme) if out is not None else
+                   (pointnet_util._bf16x3_weight(layer, 0, scheme), layer["b"], layer["scale"], layer["shift"]))
             ops.extend([k, n, 1 if act else 0, 0, ld if out is not None else 0])
             ptrs.extend([_lib.ptr(v) for v in par] + [_lib.ptr(out)])
             keep.append(layer)
@@ -132,7 +134,7 @@ def _tail_program(rows, K, mixed_pred, early_split_nocs, dev, bf16x3=False):
     return ops, ptrs, logits, ld, keep
 
 
-def run_tail_programs_bf16x3(programs, fp):
+def run_tail_programs_bf16x3(programs, fp, arith=None):
     """programs built with _tail_program(..., bf16x3=True); fp = (b, n, m, points2 (G * b, m, 128), idx, weight (b, n, 3), xyz (b, n, 3)), n % 64 == 0:
     ONE ancsh_mlp_chain_grouped_fp_bf16x3 launch per pair of networks (opt-in experiment, csrc/tail_bf16x3.hip)."""
     import ctypes
@@ -146,8 +148,10 @@ def run_tail_programs_bf16x3(programs, fp):
         ops_tab = (ctypes.c_void_p * k)(*[ctypes.cast(o, ctypes.c_void_p) for o in c_ops])
         ptr_tab = (ctypes.c_void_p * k)(*[ctypes.cast(o, ctypes.c_void_p) for o in c_ptrs])
         from . import pointnet_util
-        _lib.call(pointnet_util.split_name("ancsh_mlp_chain_grouped_fp_bf16x3"), k, b, n, m, 128, _lib.ptr(points2[g0 * b:]), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(xyz),
-                  ctypes.cast(nops, ctypes.c_void_p), ctypes.cast(ops_tab, ctypes.c_void_p), ctypes.cast(ptr_tab, ctypes.c_void_p))
+        ar = pointnet_util.arithmetic(arith)
+        ar.with_bit(ar.flag_bit0 + g0).call("ancsh_mlp_chain_grouped_fp_bf16x3", k, b, n, m, 128, _lib.ptr(points2[g0 * b:]), _lib.ptr(idx), _lib.ptr(weight),
+                                            _lib.ptr(xyz), ctypes.cast(nops, ctypes.c_void_p), ctypes.cast(ops_tab, ctypes.c_void_p),
+                                            ctypes.cast(ptr_tab, ctypes.c_void_p))
 
 
 def run_tail_programs(x, rows, programs, fp=None):
@@ -191,7 +195,7 @@ def _tail_chain(x, rows, K, mixed_pred, early_split_nocs):
 
 
 def get_per_point_model_new(scope, P, n_max_parts, is_training, bn_decay, early_split=False, early_split_nocs=False,
-                            mixed_pred=False, pred_joint=False, pred_joint_ind=False):
+                            mixed_pred=False, pred_joint=False, pred_joint_ind=False, arith=None):
     '''
         Inputs:
             - P: BxNx3 tensor, the input point cloud
@@ -208,14 +212,14 @@ def get_per_point_model_new(scope, P, n_max_parts, is_training, bn_decay, early_
     fused = None
     if FUSED_TAIL:
         with tf_util.variable_scope(scope):
-            fused = _fused_tail(scope, P, K, mixed_pred, early_split_nocs)
+            fused = _fused_tail(scope, P, K, mixed_pred, early_split_nocs, arith)
     if fused is not None:
         logits, ld = fused
         dev = P.device
     else:
       with tf_util.variable_scope(scope):
         out_dims = [K, 3 * K] + ([K, 3 * K] if mixed_pred else []) + [1]
-        net = build_pointnet2_shared('est_net', X=P, out_dims=out_dims, is_training=is_training, bn_decay=bn_decay)
+        net = build_pointnet2_shared('est_net', X=P, out_dims=out_dims, is_training=is_training, bn_decay=bn_decay, arith=arith)
         dev = net.device
         n_head = sum(out_dims)
         ld = (n_head + 10 + 3) // 4 * 4

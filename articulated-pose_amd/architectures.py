@@ -25,7 +25,7 @@ FP_LEVELS = (("fa_layer1", (256, 256)), ("fa_layer2", (256, 128)), ("fa_layer3",
 TRUNK_WIDTH = 128
 
 
-def build_pointnet2_shared(scope, X, out_dims, is_training, bn_decay):
+def build_pointnet2_shared(scope, X, out_dims, is_training, bn_decay, arith=None):
     """X (B, N, 3 + C) -> per-point trunk features (B, N, 128).  `out_dims` is accepted for signature parity; the heads are
     built by the caller (lib/architecture.py)."""
     with tf_util.variable_scope(scope):
@@ -34,7 +34,7 @@ def build_pointnet2_shared(scope, X, out_dims, is_training, bn_decay):
         for name, npoint, radius, nsample, mlp, group_all in SA_LEVELS:
             new_xyz, new_feats, _ = pointnet_sa_module(xyz[-1], feats[-1], npoint=npoint, radius=radius, nsample=nsample,
                                                        mlp=list(mlp), mlp2=None, group_all=group_all, is_training=is_training,
-                                                       bn_decay=bn_decay, scope=name)
+                                                       bn_decay=bn_decay, scope=name, arith=arith)
             xyz.append(new_xyz)
             feats.append(new_feats)
         up = feats[-1]

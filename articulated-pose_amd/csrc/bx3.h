@@ -14,6 +14,13 @@
 //            is for networks whose activations stay far inside that range (ANCSH: unit-diagonal clouds, batch-normalised layers: O(1..100));
 //            f16 subnormals are exact on this hardware (v_cvt_pk_f16_f32 rounds to nearest even into them, the f16 MFMA does not flush
 //            them: tools/f16_probe.hip on an MI355X).
+//            RANGE GUARD (opt-in: the GUARD template flag of every F16x2 kernel, the ancsh_*_f16x2*_guarded entry points): every
+//            activation the scheme converts to f16 also feeds a per-lane max |x| (RangeMax below: one v_max3_f32 with abs modifiers per
+//            value pair), folded into a wave-uniform bit by one ballot per epilogue / staging loop; at the end one atomicOr per flagged
+//            (wave, cloud) sets the bit of the (cloud, network) in a flag word.  The rule is exact: a flag iff some converted operand has |x| > 65504 (+-inf flags, NaN does
+//            not -- it poisons the cloud's outputs by itself).  hi is the only term that can overflow: mid = f16((x - hi) * 2^11) is at
+//            most ulp(hi) / 2 * 2^11 <= 32768 wherever hi is finite.  Weights are static and checked once on the host.  NOT checked:
+//            precision lost to f16's subnormal range (|x| < 2^-14 keeps fewer than 22 bits) -- the guard is about range only.
 //
 // Shared by the fused set-abstraction levels (sa_bf16x3.hip) and the per-point tail chain (tail_bf16x3.hip).  OPT-IN experiment code: f32
 // is the graded arithmetic.
@@ -111,6 +118,45 @@ struct F16x2 {
 template <class S>
 __device__ __forceinline__ uint4 bx_u4(const BxFrag &f) { return __builtin_bit_cast(uint4, f); }
 
+// ---- the F16x2 range guard (see the head comment) ----------------------------------------------------------------------------
+// RangeMax<false> is empty and every call on it vanishes: a GUARD = false kernel is the unguarded kernel instruction for instruction.
+// RangeMax<true>: m = this lane's max |x| since the last flush (a VGPR live only within an epilogue or a staging loop, never across the
+// MFMA loops, where these kernels run at their register limit: a max kept live for the whole kernel spilled up to 2.3 KB per lane in the
+// tail), hit = some lane has seen |x| > 65504 (wave-uniform, an SGPR: one ballot per flush).
+constexpr float F16_MAX = 65504.f;
+template <bool G>
+struct RangeMax {
+    __device__ __forceinline__ void add2(float, float) {}
+    __device__ __forceinline__ void flush() {}
+};
+template <>
+struct RangeMax<true> {
+    float m = 0.f;
+    bool hit = false;
+    // __builtin_fmaxf: maxNum, a NaN operand is ignored (nmax / v_maximum would propagate it and flag every NaN cloud)
+    __device__ __forceinline__ void add2(float a, float b) { m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b))); }
+    __device__ __forceinline__ void flush() {
+        hit = hit || __ballot(m > F16_MAX) != 0;
+        m = 0.f;
+    }
+};
+// the guarded instantiations exist for F16x2 only (Bf16x3 has f32's range)
+template <class S>
+constexpr bool guardable() { return S::NP == 2; }
+// argument check of the guarded entry points, before any launch: a flag word per geometry cloud, bits flag_bit0 .. flag_bit0 + ngroups - 1
+static inline int guard_args(const char *who, int ngroups, const unsigned *range_flags, int flag_bit0) {
+    ANCSH_REQUIRE(range_flags, "%s: null range_flags", who);
+    ANCSH_REQUIRE(ngroups >= 1 && flag_bit0 >= 0 && flag_bit0 + ngroups <= 32, "%s: flag_bit0=%d + ngroups=%d must stay within the 32 bits of a flag word",
+                  who, flag_bit0, ngroups);
+    return ANCSH_OK;
+}
+// wave-uniform call, every lane of the wave present: the last flush, then one atomicOr per wave that has seen |x| > 65504
+__device__ __forceinline__ void range_flag(RangeMax<false> &, unsigned *, long, int) {}
+__device__ __forceinline__ void range_flag(RangeMax<true> &rg, unsigned *flags, long cloud, int bit) {
+    rg.flush();
+    if (rg.hit && (threadIdx.x & 63) == 0) atomicOr(flags + cloud, 1u << bit);
+}
+
 // ---- register-resident layers ------------------------------------------------------------------------------------------------
 // The 8 halves a lane holds of an activation fragment -- point l31, channels 16 kb + 8 (lane >> 5) + 0..7 -- are the SAME registers
 // whether the tile is used as the A operand (points as rows) or as the B operand (points as columns).  A hidden layer is therefore
@@ -142,8 +188,9 @@ __device__ __forceinline__ EpiRaw bx3_epi_load(const Bx3Layer &L, int i) {
 }
 
 // raw: in = tile i's constants (bx3_epi_load), out = tile i + 1's when i + 1 < TM
-template <class S, int P, bool RELU, int NF, int TM>
-__device__ __forceinline__ void bx3_tile_epilogue(const Bx3Layer &L, int i, EpiRaw &raw, const fx16 (&acc)[P][S::NACC], BxFrag (&Y)[P][NF][S::NP]) {
+template <class S, int P, bool RELU, int NF, int TM, bool G>
+__device__ __forceinline__ void bx3_tile_epilogue(const Bx3Layer &L, int i, EpiRaw &raw, const fx16 (&acc)[P][S::NACC], BxFrag (&Y)[P][NF][S::NP],
+                                                  RangeMax<G> &rg) {
     // register r = 4 q + t holds channel 32 i + 4 khalf + 8 q + t of point l31
     // bias folded into the shift ONCE per tile, shared by the P point blocks: (v + b) * sc + sh = v * sc + (b * sc + sh) -- VALU time is
     // matrix-pipe time for these kernels (tools/mfma_bf16_ub.hip: 16-bit MFMA and VALU issue strictly one after the other)
@@ -168,6 +215,8 @@ __device__ __forceinline__ void bx3_tile_epilogue(const Bx3Layer &L, int i, EpiR
 #if defined(BX3_KO_SPLIT)      /* timing experiment only (tools/experiments): one conversion instead of the split */
             for (int pl = 0; pl < S::NP; ++pl) { s01[pl] = __builtin_bit_cast(u32, __builtin_convertvector(a01, bf16x2v)); s23[pl] = __builtin_bit_cast(u32, __builtin_convertvector(a23, bf16x2v)); }
 #else
+            rg.add2(a01.x, a01.y);
+            rg.add2(a23.x, a23.y);
             S::split2(a01.x, a01.y, s01);
             S::split2(a23.x, a23.y, s23);
 #endif
@@ -191,6 +240,7 @@ __device__ __forceinline__ void bx3_tile_epilogue(const Bx3Layer &L, int i, EpiR
             Y[p][2 * i + 1][pl] = BxFrag{{y[2][pl][0], y[2][pl][1], y[3][pl][0], y[3][pl][1]}};
         }
     }
+    rg.flush();
 }
 
 template <class S, int P>
@@ -207,9 +257,9 @@ __device__ __forceinline__ void bx3_zero(fx16 (&acc)[P][S::NACC]) {
 // accumulators of point block p start from the f32 row init[p][0:N] of THIS lane's point (the first layer's per-point partial sums over the
 // feature channels, see ancsh_sa_module_fused_partial) instead of zero.  Never holds more than X + Y: the order for two waves per SIMD
 // (the other wave hides the weight stream's latency) and for a layer whose input must survive it.
-template <class S, int KB, int N, int P, bool RELU = true>
+template <class S, int KB, int N, int P, bool RELU = true, bool G>
 __device__ __forceinline__ void bx3_hidden(const Bx3Layer &L, const BxFrag (&X)[P][KB][S::NP], BxFrag (&Y)[P][N / 16][S::NP],
-                                           const float *const (&init)[P]) {
+                                           const float *const (&init)[P], RangeMax<G> &rg) {
     constexpr int TM = N / 32;
     const int lane = threadIdx.x & 63, khalf = lane >> 5;
     const uint4 *Wp = L.w + lane;
@@ -241,7 +291,7 @@ __device__ __forceinline__ void bx3_hidden(const Bx3Layer &L, const BxFrag (&X)[
                 for (int p = 0; p < P; ++p)
                     acc[p][S::PC[t]] = S::mfma(W[S::PW[t]], bx_u4<S>(X[p][kb][S::PA[t]]), acc[p][S::PC[t]]);
         }
-        bx3_tile_epilogue<S, P, RELU, N / 16, 0>(L, i, raw, acc, Y);      // TM = 0: no look-ahead, the next tile loads its own before its k loop
+        bx3_tile_epilogue<S, P, RELU, N / 16, 0>(L, i, raw, acc, Y, rg);      // TM = 0: no look-ahead, the next tile loads its own before its k loop
     }
 }
 
@@ -251,8 +301,8 @@ __device__ __forceinline__ void bx3_hidden(const Bx3Layer &L, const BxFrag (&X)[
 // SIMD and no spare registers for the compiler to hoist the loads -- measured on the bf16x3 tail chain: 159 us against 42 us of pure
 // MFMA issue per wave, 118 us with this order).  X is dead when the epilogue forms Y, so Y may take X's registers; NOT for a layer
 // whose input must survive it.
-template <class S, int KB, int N, int P, bool RELU = true>
-__device__ __forceinline__ void bx3_hidden_kouter(const Bx3Layer &L, const BxFrag (&X)[P][KB][S::NP], BxFrag (&Y)[P][N / 16][S::NP]) {
+template <class S, int KB, int N, int P, bool RELU = true, bool G>
+__device__ __forceinline__ void bx3_hidden_kouter(const Bx3Layer &L, const BxFrag (&X)[P][KB][S::NP], BxFrag (&Y)[P][N / 16][S::NP], RangeMax<G> &rg) {
     constexpr int TM = N / 32;
     const int lane = threadIdx.x & 63;
     const uint4 *Wp = L.w + lane;
@@ -290,7 +340,7 @@ __device__ __forceinline__ void bx3_hidden_kouter(const Bx3Layer &L, const BxFra
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, N / 16, TM>(L, i, raw, acc[i], Y);
+    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, N / 16, TM>(L, i, raw, acc[i], Y, rg);
 }
 
 
@@ -298,9 +348,9 @@ __device__ __forceinline__ void bx3_hidden_kouter(const Bx3Layer &L, const BxFra
 // every output tile's weight fragments and -- PARTIAL levels -- every tile's accumulator start (the per-point partial sums, gathered by
 // idx) before the first MFMA.  In bx3_hidden's order each of the N / 32 tiles paid its own L2 round trips for 6 MFMAs of work
 // (kernel trace of the F16x2 feature level: four serial load / wait-for-all groups before the second layer starts, ~5 us per wave).
-template <class S, int N, int P, bool RELU = true>
+template <class S, int N, int P, bool RELU = true, bool G>
 __device__ __forceinline__ void bx3_first_kouter(const Bx3Layer &L, const BxFrag (&X)[P][1][S::NP], BxFrag (&Y)[P][N / 16][S::NP],
-                                                 const float *const (&init)[P]) {
+                                                 const float *const (&init)[P], RangeMax<G> &rg) {
     constexpr int TM = N / 32;
     const int lane = threadIdx.x & 63, khalf = lane >> 5;
     const uint4 *Wp = L.w + lane;
@@ -332,7 +382,7 @@ __device__ __forceinline__ void bx3_first_kouter(const Bx3Layer &L, const BxFrag
             for (int p = 0; p < P; ++p)
                 acc[i][p][S::PC[t]] = S::mfma(w[i][S::PW[t]], bx_u4<S>(X[p][0][S::PA[t]]), acc[i][p][S::PC[t]]);
 #pragma unroll
-    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, N / 16, TM>(L, i, raw, acc[i], Y);
+    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, N / 16, TM>(L, i, raw, acc[i], Y, rg);
 }
 
 }  // namespace ancsh

@@ -40,9 +40,11 @@ struct MsTile {
 };
 
 // stage f32 values v[0..7] (8 consecutive channels c0 .. c0 + 7 of one row; c0 % 8 == 0) as the scheme's planes
-template <class S>
-__device__ __forceinline__ void ms_store8(const MsTile<S> &T, int row, int c0, const float (&v)[8]) {
+template <class S, bool G>
+__device__ __forceinline__ void ms_store8(const MsTile<S> &T, int row, int c0, const float (&v)[8], RangeMax<G> &rg) {
     u32 s[4][S::NP];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rg.add2(v[2 * j], v[2 * j + 1]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) S::split2(v[2 * j], v[2 * j + 1], s[j]);
 #pragma unroll
@@ -93,9 +95,9 @@ __device__ __forceinline__ void ms_k_loop(const uint4 *Wp, int TN, int j0, const
 
 // epilogue of a TRANSPOSED tile (channels 32 i ..): BN (+ ReLU) of the lane's 4 x 4 channels of point l31 of every point block, then either the
 // split planes into the LDS tile (hidden layer) or float4 runs of a global f32 row
-template <class S, bool RELU, bool TO_LDS>
+template <class S, bool RELU, bool TO_LDS, bool G>
 __device__ __forceinline__ void ms_epilogue(const Bx3Layer &L, int i, const fx16 (&acc)[MS_P][S::NACC], const MsTile<S> &T, float *out, int out_ld,
-                                            long row0) {
+                                            long row0, RangeMax<G> &rg) {
     const int lane = threadIdx.x & 63, khalf = lane >> 5, l31 = lane & 31;
     const int c0 = 32 * i + 4 * khalf;
 #pragma unroll
@@ -111,6 +113,8 @@ __device__ __forceinline__ void ms_epilogue(const Bx3Layer &L, int i, const fx16
             if (RELU) { a01.x = nmax(a01.x, 0.f); a01.y = nmax(a01.y, 0.f); a23.x = nmax(a23.x, 0.f); a23.y = nmax(a23.y, 0.f); }
             if (TO_LDS) {
                 u32 s01[S::NP], s23[S::NP];
+                rg.add2(a01.x, a01.y);
+                rg.add2(a23.x, a23.y);
                 S::split2(a01.x, a01.y, s01);
                 S::split2(a23.x, a23.y, s23);
 #pragma unroll
@@ -120,12 +124,13 @@ __device__ __forceinline__ void ms_epilogue(const Bx3Layer &L, int i, const fx16
             }
         }
     }
+    rg.flush();
 }
 
 // a hidden layer K -> N over the whole workgroup, in place: every wave computes N / 32 / NW tiles for both point blocks, then -- between two
 // barriers -- rewrites the tile.  init != nullptr: every row's accumulators start from init[0:N] (fa_layer1: the cloud's single-source share).
-template <class S, int NW, int K, int N, bool RELU>
-__device__ __forceinline__ void ms_hidden(const Bx3Layer &L, MsTile<S> &T, const float *init) {
+template <class S, int NW, int K, int N, bool RELU, bool G>
+__device__ __forceinline__ void ms_hidden(const Bx3Layer &L, MsTile<S> &T, const float *init, RangeMax<G> &rg) {
     constexpr int KB = (K + 15) / 16, TN = N / 32, TW = TN / NW;
     static_assert(TN % NW == 0, "output tiles per wave");
     const int lane = threadIdx.x & 63, khalf = lane >> 5;
@@ -147,7 +152,7 @@ __device__ __forceinline__ void ms_hidden(const Bx3Layer &L, MsTile<S> &T, const
     __syncthreads();                                   // every wave has read the whole tile
     T.ld = ms_ld(N);                                   // the tile takes the output's row stride
 #pragma unroll
-    for (int j = 0; j < TW; ++j) ms_epilogue<S, RELU, true>(L, wave * TW + j, acc[j], T, nullptr, 0, 0);
+    for (int j = 0; j < TW; ++j) ms_epilogue<S, RELU, true>(L, wave * TW + j, acc[j], T, nullptr, 0, 0, rg);
     __syncthreads();                                   // (N % 16 == 0 for every layer here: the next layer reads no k-block padding)
 }
 
@@ -162,8 +167,9 @@ __device__ __forceinline__ void ms_out_rows(const Bx3Layer &L, const MsTile<S> &
 #pragma unroll
     for (int j = 0; j < TW; ++j) bx3_zero<S, MS_P>(acc[j]);
     ms_k_loop<S, KB, TW, true>(L.w + lane, TN, wave * TW, T, acc);
+    RangeMax<false> none;                              // f32 rows out: nothing converted
 #pragma unroll
-    for (int j = 0; j < TW; ++j) ms_epilogue<S, true, false>(L, wave * TW + j, acc[j], T, out, N, row0);
+    for (int j = 0; j < TW; ++j) ms_epilogue<S, true, false>(L, wave * TW + j, acc[j], T, out, N, row0, none);
 }
 
 // layer3's last layer: K -> N, ReLU, max over the tile's 64 rows -> out[0:N]; NORMAL orientation, the wave's N / 32 / NW tiles in groups of TG
@@ -201,9 +207,12 @@ __device__ __forceinline__ void ms_out_pooled(const Bx3Layer &L, const MsTile<S>
 // ---- layer3: rows [xyz (3) | features (256)] -> 256 -> 512 -> 1024, max over the tile's 64 rows ------------------------------------
 // 8 waves (two per SIMD: 1 / 2 / 4 output tiles per wave and layer; with four waves the 512- and 1024-wide layers' accumulators spilled)
 constexpr int SA3S_NW = 8;
-template <class S>
+// GUARD (F16x2 only, every kernel of this file): range_flags[geometry cloud] |= 1 << (flag_bit0 + group) when a value a wave of the tile
+// converts to f16 has |x| > 65504 (bx3.h); a 64-row tile never straddles clouds
+template <class S, bool GUARD = false>
 __global__ __launch_bounds__(64 * SA3S_NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void sa3_split16_kernel(int bgeo, int npts, long tiles, const float *__restrict__ xyz, const float *__restrict__ feats, MsGroups GL, float *__restrict__ out) {
+void sa3_split16_kernel(int bgeo, int npts, long tiles, const float *__restrict__ xyz, const float *__restrict__ feats, MsGroups GL, float *__restrict__ out,
+                        unsigned *__restrict__ range_flags, int flag_bit0) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
     const int tid = threadIdx.x;
     const long tile = blockIdx.x;
@@ -213,6 +222,7 @@ void sa3_split16_kernel(int bgeo, int npts, long tiles, const float *__restrict_
     const int grp = (int)(cloud / bgeo);
     const long cg = cloud - (long)grp * bgeo;                  // geometry cloud
     MsTile<S> T{smem16, ms_ld(259)};
+    RangeMax<GUARD> rg;
     // stage [xyz | features | 0 ..]: channels 0..2 xyz, 3..258 features, 259..271 zero.  A thread owns 8 consecutive channels of a row.
     {
         constexpr int C8 = 272 / 8;                            // 34 groups of 8 channels per row
@@ -226,43 +236,49 @@ void sa3_split16_kernel(int bgeo, int npts, long tiles, const float *__restrict_
                 const int c = c0 + u;
                 v[u] = c < 3 ? x[c] : (c < 259 ? f[c - 3] : 0.f);
             }
-            ms_store8<S>(T, r, c0, v);
+            ms_store8<S>(T, r, c0, v, rg);
         }
     }
+    rg.flush();
     __syncthreads();
-    ms_hidden<S, SA3S_NW, 259, 256, true>(GL.L[grp][0], T, nullptr);
-    ms_hidden<S, SA3S_NW, 256, 512, true>(GL.L[grp][1], T, nullptr);
+    ms_hidden<S, SA3S_NW, 259, 256, true>(GL.L[grp][0], T, nullptr, rg);
+    ms_hidden<S, SA3S_NW, 256, 512, true>(GL.L[grp][1], T, nullptr, rg);
     ms_out_pooled<S, SA3S_NW, 512, 1024, 2>(GL.L[grp][2], T, out + (size_t)tile * 1024);
+    range_flag(rg, range_flags, cg, flag_bit0 + grp);
 }
 
 // ---- fa_layer1: rows = level-2 points, skip features 256 -> 256 (chain continued from init[cloud]) -> 256 ----------------------------
 constexpr int FPS_NW = 4;       // the feature-propagation levels: four waves, one per SIMD
-template <class S>
+template <class S, bool GUARD = false>
 __global__ __launch_bounds__(64 * FPS_NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void fp1_split16_kernel(int npts, long tiles, const float *__restrict__ skip, const float *__restrict__ init, int rows_per_group, MsGroups GL,
-                        float *__restrict__ out) {
+                        float *__restrict__ out, unsigned *__restrict__ range_flags, int flag_bit0) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
     const int tid = threadIdx.x;
     const long row0 = (long)blockIdx.x * MS_R;
     const long cloud = row0 / npts;                            // npts % 64 == 0: a tile never straddles clouds
     const int grp = (int)(row0 / rows_per_group);
     MsTile<S> T{smem16, ms_ld(256)};
+    RangeMax<GUARD> rg;
     for (int e = tid; e < MS_R * 32; e += 64 * FPS_NW) {        // 32 groups of 8 channels per row
         const int r = e >> 5, c0 = (e & 31) * 8;
         const float4 a = *reinterpret_cast<const float4 *>(skip + (size_t)(row0 + r) * 256 + c0), b = *reinterpret_cast<const float4 *>(skip + (size_t)(row0 + r) * 256 + c0 + 4);
         const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        ms_store8<S>(T, r, c0, v);
+        ms_store8<S>(T, r, c0, v, rg);
     }
+    rg.flush();
     __syncthreads();
-    ms_hidden<S, FPS_NW, 256, 256, true>(GL.L[grp][0], T, init + (size_t)cloud * 256);
+    ms_hidden<S, FPS_NW, 256, 256, true>(GL.L[grp][0], T, init + (size_t)cloud * 256, rg);
     ms_out_rows<S, FPS_NW, 256, 256>(GL.L[grp][1], T, out, row0);
+    range_flag(rg, range_flags, cloud - (long)grp * (rows_per_group / npts), flag_bit0 + grp);
 }
 
 // ---- fa_layer2: rows = level-1 points, [three_interpolate(level-2 features) (256) | level-1 features (128)] -> 256 -> 128 ------------
-template <class S>
+template <class S, bool GUARD = false>
 __global__ __launch_bounds__(64 * FPS_NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void fp2_split16_kernel(int bgeo, int n, int m, long tiles, const float *__restrict__ points2, const int *__restrict__ idx, const float *__restrict__ weight,
-                        const float *__restrict__ points1, int rows_per_group, MsGroups GL, float *__restrict__ out) {
+                        const float *__restrict__ points1, int rows_per_group, MsGroups GL, float *__restrict__ out, unsigned *__restrict__ range_flags,
+                        int flag_bit0) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
     const int tid = threadIdx.x;
     long tile = blockIdx.x;
@@ -279,6 +295,7 @@ void fp2_split16_kernel(int bgeo, int n, int m, long tiles, const float *__restr
     const long cg = cloud % bgeo;
     const int grp = (int)(row0 / rows_per_group);
     MsTile<S> T{smem16, ms_ld(384)};
+    RangeMax<GUARD> rg;
     const long g0 = cg * n + (row0 - cloud * n);               // first row of the tile in the geometry arrays
     // interpolated part: p[i1] * w1 + p[i2] * w2 + p[i3] * w3 in that order, unfused (tf_interpolate.cpp:107-127); 32 groups of 8 channels per row
     for (int e = tid; e < MS_R * 32; e += 64 * FPS_NW) {
@@ -301,17 +318,19 @@ void fp2_split16_kernel(int bgeo, int n, int m, long tiles, const float *__restr
             v[4 * h + 2] = a[0][h].z * w[0] + a[1][h].z * w[1] + a[2][h].z * w[2];
             v[4 * h + 3] = a[0][h].w * w[0] + a[1][h].w * w[1] + a[2][h].w * w[2];
         }
-        ms_store8<S>(T, r, c0, v);
+        ms_store8<S>(T, r, c0, v, rg);
     }
     for (int e = tid; e < MS_R * 16; e += 64 * FPS_NW) {        // skip part: 16 groups of 8 channels per row
         const int r = e >> 4, c0 = (e & 15) * 8;
         const float4 a = *reinterpret_cast<const float4 *>(points1 + (size_t)(row0 + r) * 128 + c0), b = *reinterpret_cast<const float4 *>(points1 + (size_t)(row0 + r) * 128 + c0 + 4);
         const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        ms_store8<S>(T, r, 256 + c0, v);
+        ms_store8<S>(T, r, 256 + c0, v, rg);
     }
+    rg.flush();
     __syncthreads();
-    ms_hidden<S, FPS_NW, 384, 256, true>(GL.L[grp][0], T, nullptr);
+    ms_hidden<S, FPS_NW, 384, 256, true>(GL.L[grp][0], T, nullptr, rg);
     ms_out_rows<S, FPS_NW, 256, 128>(GL.L[grp][1], T, out, row0);
+    range_flag(rg, range_flags, cg, flag_bit0 + grp);
 }
 
 static int ms_layers(const float *const *params, int ngroups, int nlayers, MsGroups &GL, const char *who) {
@@ -332,9 +351,10 @@ static int ms_layers(const float *const *params, int ngroups, int nlayers, MsGro
 template <class S>
 static size_t ms_lds_bytes(int kmax) { return (size_t)S::NP * MS_R * ms_ld(kmax) * sizeof(unsigned short); }
 
+// range_flags != nullptr: the GUARD instantiations (checked by the entry point, guard_args)
 template <class S>
 static int sa3_split16(const char *who, int ngroups, int b, int npts, int cfeat, int c1, int c2, int c3, const float *xyz, const float *feats,
-                       const float *const *params, float *out, void *stream) {
+                       const float *const *params, float *out, void *stream, unsigned *range_flags = nullptr, int flag_bit0 = 0) {
     ANCSH_REQUIRE(ngroups >= 1 && ngroups <= ANCSH_MAX_GROUPS, "%s: ngroups=%d must be in [1,%d]", who, ngroups, ANCSH_MAX_GROUPS);
     ANCSH_REQUIRE(b >= 0 && npts > 0 && npts % MS_R == 0, "%s: bad shape b=%d npts=%d (npts must be a multiple of %d)", who, b, npts, MS_R);
     ANCSH_REQUIRE(cfeat == 256 && c1 == 256 && c2 == 512 && c3 == 1024, "%s: unsupported layer shape (cfeat=%d mlp=[%d,%d,%d])", who, cfeat, c1, c2, c3);
@@ -345,14 +365,23 @@ static int sa3_split16(const char *who, int ngroups, int b, int npts, int cfeat,
     const long tiles = (long)ngroups * b * (npts / MS_R);
     const size_t lds = ms_lds_bytes<S>(512);
     ANCSH_REQUIRE(lds <= 160 * 1024, "%s: a 64-row tile of 512 channels needs %zu bytes of LDS in this scheme (160 KB per CU): layer3 takes the f32 chain", who, lds);
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            (void)hipFuncSetAttribute((const void *)sa3_split16_kernel<S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((sa3_split16_kernel<S, true>), dim3((unsigned)tiles), dim3(64 * SA3S_NW), lds, (hipStream_t)stream, b, npts, tiles, xyz, feats, GL, out,
+                               range_flags, flag_bit0);
+            return check_launch(who);
+        }
+    }
     (void)hipFuncSetAttribute((const void *)sa3_split16_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(sa3_split16_kernel<S>, dim3((unsigned)tiles), dim3(64 * SA3S_NW), lds, (hipStream_t)stream, b, npts, tiles, xyz, feats, GL, out);
+    hipLaunchKernelGGL(sa3_split16_kernel<S>, dim3((unsigned)tiles), dim3(64 * SA3S_NW), lds, (hipStream_t)stream, b, npts, tiles, xyz, feats, GL, out,
+                       (unsigned *)nullptr, 0);
     return check_launch(who);
 }
 
 template <class S>
 static int fp1_split16(const char *who, int ngroups, int b, int npts, int cskip, int c1, int c2, const float *skip, const float *init,
-                       const float *const *params, float *out, void *stream) {
+                       const float *const *params, float *out, void *stream, unsigned *range_flags = nullptr, int flag_bit0 = 0) {
     ANCSH_REQUIRE(ngroups >= 1 && ngroups <= ANCSH_MAX_GROUPS, "%s: ngroups=%d must be in [1,%d]", who, ngroups, ANCSH_MAX_GROUPS);
     ANCSH_REQUIRE(b >= 0 && npts > 0 && npts % MS_R == 0, "%s: bad shape b=%d npts=%d (npts must be a multiple of %d)", who, b, npts, MS_R);
     ANCSH_REQUIRE(cskip == 256 && c1 == 256 && c2 == 256, "%s: unsupported layer shape (%d -> %d -> %d)", who, cskip, c1, c2);
@@ -363,14 +392,24 @@ static int fp1_split16(const char *who, int ngroups, int b, int npts, int cskip,
     ANCSH_REQUIRE((((uintptr_t)skip | (uintptr_t)init | (uintptr_t)out) & 15) == 0, "%s: skip / init / out must be 16-byte aligned", who);
     const long tiles = (long)ngroups * b * (npts / MS_R);
     const size_t lds = ms_lds_bytes<S>(256);
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            (void)hipFuncSetAttribute((const void *)fp1_split16_kernel<S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((fp1_split16_kernel<S, true>), dim3((unsigned)tiles), dim3(64 * FPS_NW), lds, (hipStream_t)stream, npts, tiles, skip, init, b * npts, GL,
+                               out, range_flags, flag_bit0);
+            return check_launch(who);
+        }
+    }
     (void)hipFuncSetAttribute((const void *)fp1_split16_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(fp1_split16_kernel<S>, dim3((unsigned)tiles), dim3(64 * FPS_NW), lds, (hipStream_t)stream, npts, tiles, skip, init, b * npts, GL, out);
+    hipLaunchKernelGGL(fp1_split16_kernel<S>, dim3((unsigned)tiles), dim3(64 * FPS_NW), lds, (hipStream_t)stream, npts, tiles, skip, init, b * npts, GL, out,
+                       (unsigned *)nullptr, 0);
     return check_launch(who);
 }
 
 template <class S>
 static int fp2_split16(const char *who, int ngroups, int b, int m, int n, int c2, int c1, int n1, int n2, const float *points2, const int *idx,
-                       const float *weight, const float *points1, const float *const *params, float *out, void *stream) {
+                       const float *weight, const float *points1, const float *const *params, float *out, void *stream, unsigned *range_flags = nullptr,
+                       int flag_bit0 = 0) {
     ANCSH_REQUIRE(ngroups >= 1 && ngroups <= ANCSH_MAX_GROUPS, "%s: ngroups=%d must be in [1,%d]", who, ngroups, ANCSH_MAX_GROUPS);
     ANCSH_REQUIRE(b >= 0 && m > 0 && n > 0 && n % MS_R == 0, "%s: bad shape b=%d m=%d n=%d (n must be a multiple of %d)", who, b, m, n, MS_R);
     ANCSH_REQUIRE(c2 == 256 && c1 == 128 && n1 == 256 && n2 == 128, "%s: unsupported layer shape ([%d | %d] -> %d -> %d)", who, c2, c1, n1, n2);
@@ -381,9 +420,17 @@ static int fp2_split16(const char *who, int ngroups, int b, int m, int n, int c2
     ANCSH_REQUIRE((((uintptr_t)points2 | (uintptr_t)points1 | (uintptr_t)out) & 15) == 0, "%s: points2 / points1 / out must be 16-byte aligned", who);
     const long tiles = (long)ngroups * b * (n / MS_R);
     const size_t lds = ms_lds_bytes<S>(384);
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            (void)hipFuncSetAttribute((const void *)fp2_split16_kernel<S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((fp2_split16_kernel<S, true>), dim3((unsigned)tiles), dim3(64 * FPS_NW), lds, (hipStream_t)stream, b, n, m, tiles, points2, idx, weight,
+                               points1, b * n, GL, out, range_flags, flag_bit0);
+            return check_launch(who);
+        }
+    }
     (void)hipFuncSetAttribute((const void *)fp2_split16_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(fp2_split16_kernel<S>, dim3((unsigned)tiles), dim3(64 * FPS_NW), lds, (hipStream_t)stream, b, n, m, tiles, points2, idx, weight, points1,
-                       b * n, GL, out);
+                       b * n, GL, out, (unsigned *)nullptr, 0);
     return check_launch(who);
 }
 
@@ -418,4 +465,24 @@ extern "C" int ancsh_fp2_chain_grouped_bf16x3(int ngroups, int b, int m, int n, 
 extern "C" int ancsh_fp2_chain_grouped_f16x2(int ngroups, int b, int m, int n, int c2, int c1, int n1, int n2, const float *points2, const int *idx,
                                              const float *weight, const float *points1, const float *const *params, float *out, void *stream) {
     return fp2_split16<F16x2>("fp2_chain_grouped_f16x2", ngroups, b, m, n, c2, c1, n1, n2, points2, idx, weight, points1, params, out, stream);
+}
+
+// ... guarded (bx3.h's range guard): range_flags (b words, one per geometry cloud) |= 1 << (flag_bit0 + g) for every (cloud, network g) with an
+// activation the scheme converts to f16 beyond +-65504.  -1 before any launch for a NULL range_flags or flag_bit0 + ngroups > 32.
+extern "C" int ancsh_sa3_chain_grouped_f16x2_guarded(int ngroups, int b, int npts, int cfeat, int c1, int c2, int c3, const float *xyz, const float *feats,
+                                                     const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream) {
+    if (int rc = guard_args("sa3_chain_grouped_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return sa3_split16<F16x2>("sa3_chain_grouped_f16x2_guarded", ngroups, b, npts, cfeat, c1, c2, c3, xyz, feats, params, out, stream, range_flags, flag_bit0);
+}
+extern "C" int ancsh_fp1_chain_grouped_f16x2_guarded(int ngroups, int b, int npts, int cskip, int c1, int c2, const float *skip, const float *init,
+                                                     const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream) {
+    if (int rc = guard_args("fp1_chain_grouped_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return fp1_split16<F16x2>("fp1_chain_grouped_f16x2_guarded", ngroups, b, npts, cskip, c1, c2, skip, init, params, out, stream, range_flags, flag_bit0);
+}
+extern "C" int ancsh_fp2_chain_grouped_f16x2_guarded(int ngroups, int b, int m, int n, int c2, int c1, int n1, int n2, const float *points2, const int *idx,
+                                                     const float *weight, const float *points1, const float *const *params, float *out,
+                                                     unsigned *range_flags, int flag_bit0, void *stream) {
+    if (int rc = guard_args("fp2_chain_grouped_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return fp2_split16<F16x2>("fp2_chain_grouped_f16x2_guarded", ngroups, b, m, n, c2, c1, n1, n2, points2, idx, weight, points1, params, out, stream,
+                              range_flags, flag_bit0);
 }

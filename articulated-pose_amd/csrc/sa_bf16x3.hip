@@ -123,10 +123,12 @@ struct Bx3Nets {
 // the three coordinate products on the 16-bit pipe.
 // groups = ngroups * geo_groups neighbourhoods, network-major: neighbourhood g of network g / geo_groups reads the SHARED geometry
 // (xyz, new_xyz, idx) of neighbourhood g % geo_groups, its own network's partial rows and parameters, and writes out row g.
-template <class S, int C1, int C2, int C3, bool PARTIAL, int WAVES>
+// GUARD (F16x2 only): range_flags[b] |= 1 << (flag_bit0 + net) when a value the wave converts to f16 has |x| > 65504 (bx3.h)
+template <class S, int C1, int C2, int C3, bool PARTIAL, int WAVES, bool GUARD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 void sa_bf16x3_reg_kernel(int n, int m, long groups, long geo_groups, const float *__restrict__ xyz, const float *__restrict__ partial,
-                          const float *__restrict__ new_xyz, const int *__restrict__ idx, Bx3Nets NL, float *__restrict__ out) {
+                          const float *__restrict__ new_xyz, const int *__restrict__ idx, Bx3Nets NL, float *__restrict__ out,
+                          unsigned *__restrict__ range_flags, int flag_bit0) {
     constexpr int P = 2;
     const int lane = threadIdx.x & 63, khalf = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -148,6 +150,7 @@ void sa_bf16x3_reg_kernel(int n, int m, long groups, long geo_groups, const floa
     const long b = gg / m;                                     // its cloud
     const long bn = (geo_groups / m) * net + b;                // the cloud's row block in the network-major arrays
     const Bx3Layer &L1 = NL.L[net][0], &L2 = NL.L[net][1], &L3 = NL.L[net][2];
+    RangeMax<GUARD> rg;
     BxFrag X0[P][1][S::NP];
     const float *init[P];
 #pragma unroll
@@ -156,6 +159,8 @@ void sa_bf16x3_reg_kernel(int n, int m, long groups, long geo_groups, const floa
         const float *pt = xyz + ((size_t)b * n + ii) * 3, *c = new_xyz + (size_t)gg * 3;
         const float dx = pt[0] - c[0], dy = pt[1] - c[1], dz = pt[2] - c[2];
         u32 s01[S::NP], s2[S::NP];
+        rg.add2(dx, dy);
+        rg.add2(dz, 0.f);
         S::split2(dx, dy, s01);
         S::split2(dz, 0.f, s2);
         // channels 0..2 live in the lower lanes' elements 0..2; everything else of the 16-channel block is zero
@@ -163,13 +168,14 @@ void sa_bf16x3_reg_kernel(int n, int m, long groups, long geo_groups, const floa
         for (int pl = 0; pl < S::NP; ++pl) X0[p][0][pl] = BxFrag{{khalf ? 0u : s01[pl], khalf ? 0u : s2[pl], 0u, 0u}};
         init[p] = PARTIAL ? partial + ((size_t)bn * n + ii) * C1 : nullptr;
     }
+    rg.flush();
     BxFrag X1[P][C1 / 16][S::NP], X2[P][C2 / 16][S::NP];
     const float *const none[P] = {nullptr, nullptr};
 #ifndef SA_SPLIT16_FIRST_KOUTER
 #define SA_SPLIT16_FIRST_KOUTER 1       /* 0: the first layer in bx3_hidden's tile-by-tile order (tools/experiments) */
 #endif
-    if (SA_SPLIT16_FIRST_KOUTER && (WAVES == 1 || S::NACC * (C1 / 32) <= 4)) bx3_first_kouter<S, C1, P>(L1, X0, X1, init);
-    else bx3_hidden<S, 1, C1, P>(L1, X0, X1, init);
+    if (SA_SPLIT16_FIRST_KOUTER && (WAVES == 1 || S::NACC * (C1 / 32) <= 4)) bx3_first_kouter<S, C1, P>(L1, X0, X1, init, rg);
+    else bx3_hidden<S, 1, C1, P>(L1, X0, X1, init, rg);
     float pm[C3 / 32];
 #ifndef SA_SPLIT16_KOUTER_2W
 #define SA_SPLIT16_KOUTER_2W 0          /* tools/experiments: k-block-outer layers for the two-waves-per-SIMD level too */
@@ -178,16 +184,17 @@ void sa_bf16x3_reg_kernel(int n, int m, long groups, long geo_groups, const floa
         // one wave per SIMD: nothing hides the weight stream's L2 latency unless it is double-buffered under the MFMAs (k-block loop
         // outside; bx3.h): 332 -> 295 us for the bf16x3 feature level.  With two waves per SIMD the other wave already hides it and the
         // longer live ranges cost more than they buy (255 -> 311 us measured for the feature-less level): output-tile-outer order.
-        bx3_hidden_kouter<S, C1 / 16, C2, P>(L2, X1, X2);
+        bx3_hidden_kouter<S, C1 / 16, C2, P>(L2, X1, X2, rg);
         bx3_pooled_kouter<S, C2 / 16, C3, P, (C3 / 32 >= 8 ? 4 : 2)>(L3, X2, pm);
     } else {
-        bx3_hidden<S, C1 / 16, C2, P>(L2, X1, X2, none);
+        bx3_hidden<S, C1 / 16, C2, P>(L2, X1, X2, none, rg);
         bx3_pooled<S, C2 / 16, C3, P>(L3, X2, pm);
     }
     if (lane < 32) {
 #pragma unroll
         for (int j = 0; j < C3 / 32; ++j) out[(size_t)g * C3 + j * 32 + lane] = pm[j];
     }
+    range_flag(rg, range_flags, b, flag_bit0 + net);         // a wave's 64 rows are one neighbourhood: one cloud
 }
 
 static int bx3_reg_layers(const float *const *params, Bx3Layer (&L)[3], const char *who) {
@@ -241,9 +248,11 @@ static int bx3_nets(int ngroups, const float *const *params, Bx3Nets &NL, const 
     return ANCSH_OK;
 }
 
+// range_flags != nullptr: the GUARD instantiation (the caller has checked flags / flag_bit0, guard_args below)
 template <class S>
 static int sa_split16(const char *who, int ngroups, int b, int n, int m, int nsample, int cfeat, int c1, int c2, int c3, const float *xyz,
-                      const float *new_xyz, const int *idx, const float *const *params, float *out, void *stream) {
+                      const float *new_xyz, const int *idx, const float *const *params, float *out, void *stream,
+                      unsigned *range_flags = nullptr, int flag_bit0 = 0) {
     ANCSH_REQUIRE(b >= 0 && n > 0 && m > 0, "%s: bad shape b=%d n=%d m=%d", who, b, n, m);
     ANCSH_REQUIRE(nsample == 64, "%s: nsample must be 64 (got %d)", who, nsample);
     ANCSH_REQUIRE(cfeat == 0 && c1 == 64 && c2 == 64 && c3 == 128, "%s: unsupported layer shape (cfeat=%d mlp=[%d,%d,%d]); "
@@ -256,14 +265,22 @@ static int sa_split16(const char *who, int ngroups, int b, int n, int m, int nsa
 #ifndef SA_SPLIT16_SA1_WAVES
 #define SA_SPLIT16_SA1_WAVES 2
 #endif
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            hipLaunchKernelGGL((sa_bf16x3_reg_kernel<S, 64, 64, 128, false, SA_SPLIT16_SA1_WAVES, true>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0,
+                               (hipStream_t)stream, n, m, groups, geo, xyz, (const float *)nullptr, new_xyz, idx, NL, out, range_flags, flag_bit0);
+            return check_launch(who);
+        }
+    }
     hipLaunchKernelGGL((sa_bf16x3_reg_kernel<S, 64, 64, 128, false, SA_SPLIT16_SA1_WAVES>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, m,
-                       groups, geo, xyz, (const float *)nullptr, new_xyz, idx, NL, out);
+                       groups, geo, xyz, (const float *)nullptr, new_xyz, idx, NL, out, (unsigned *)nullptr, 0);
     return check_launch(who);
 }
 
 template <class S>
 static int sa_partial_split16(const char *who, int ngroups, int b, int n, int m, int nsample, int c1, int c2, int c3, const float *xyz,
-                              const float *partial, const float *new_xyz, const int *idx, const float *const *params, float *out, void *stream) {
+                              const float *partial, const float *new_xyz, const int *idx, const float *const *params, float *out, void *stream,
+                              unsigned *range_flags = nullptr, int flag_bit0 = 0) {
     ANCSH_REQUIRE(b >= 0 && n > 0 && m > 0, "%s: bad shape b=%d n=%d m=%d", who, b, n, m);
     ANCSH_REQUIRE(nsample == 64, "%s: nsample must be 64 (got %d)", who, nsample);
     ANCSH_REQUIRE(c1 == 128 && c2 == 128 && c3 == 256, "%s: unsupported layer shape (mlp=[%d,%d,%d])", who, c1, c2, c3);
@@ -273,8 +290,15 @@ static int sa_partial_split16(const char *who, int ngroups, int b, int n, int m,
     ANCSH_REQUIRE(xyz && partial && new_xyz && idx && out, "%s: null pointer", who);
     ANCSH_REQUIRE((((uintptr_t)partial) & 15) == 0, "%s: partial must be 16-byte aligned", who);
     const long geo = (long)b * m, groups = geo * ngroups;
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            hipLaunchKernelGGL((sa_bf16x3_reg_kernel<S, 128, 128, 256, true, 1, true>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, m,
+                               groups, geo, xyz, partial, new_xyz, idx, NL, out, range_flags, flag_bit0);
+            return check_launch(who);
+        }
+    }
     hipLaunchKernelGGL((sa_bf16x3_reg_kernel<S, 128, 128, 256, true, 1>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, m,
-                       groups, geo, xyz, partial, new_xyz, idx, NL, out);
+                       groups, geo, xyz, partial, new_xyz, idx, NL, out, (unsigned *)nullptr, 0);
     return check_launch(who);
 }
 
@@ -304,6 +328,15 @@ extern "C" int ancsh_sa_module_fused_f16x2_grouped(int ngroups, int b, int n, in
                                                    const float *const *params, float *out, void *stream) {
     return sa_split16<F16x2>("sa_module_fused_f16x2", ngroups, b, n, m, nsample, cfeat, c1, c2, c3, xyz, new_xyz, idx, params, out, stream);
 }
+// ... guarded (bx3.h's range guard): range_flags (b words) |= 1 << (flag_bit0 + g) for every (cloud, network g) with an activation the scheme
+// converts to f16 beyond +-65504.  -1 before any launch for a NULL range_flags or flag_bit0 + ngroups > 32.
+extern "C" int ancsh_sa_module_fused_f16x2_grouped_guarded(int ngroups, int b, int n, int m, int nsample, int cfeat, int c1, int c2, int c3,
+                                                           const float *xyz, const float *feats, const float *new_xyz, const int *idx,
+                                                           const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream) {
+    if (int rc = guard_args("sa_module_fused_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return sa_split16<F16x2>("sa_module_fused_f16x2_guarded", ngroups, b, n, m, nsample, cfeat, c1, c2, c3, xyz, new_xyz, idx, params, out, stream,
+                             range_flags, flag_bit0);
+}
 extern "C" int ancsh_sa_module_fused_bf16x3(int b, int n, int m, int nsample, int cfeat, int c1, int c2, int c3, const float *xyz,
                                             const float *feats, const float *new_xyz, const int *idx, const float *const *params,
                                             float *out, void *stream) {
@@ -321,6 +354,14 @@ extern "C" int ancsh_sa_module_fused_partial_f16x2_grouped(int ngroups, int b, i
                                                            const float *xyz, const float *partial, const float *new_xyz, const int *idx,
                                                            const float *const *params, float *out, void *stream) {
     return sa_partial_split16<F16x2>("sa_module_fused_partial_f16x2", ngroups, b, n, m, nsample, c1, c2, c3, xyz, partial, new_xyz, idx, params, out, stream);
+}
+extern "C" int ancsh_sa_module_fused_partial_f16x2_grouped_guarded(int ngroups, int b, int n, int m, int nsample, int c1, int c2, int c3,
+                                                                   const float *xyz, const float *partial, const float *new_xyz, const int *idx,
+                                                                   const float *const *params, float *out, unsigned *range_flags, int flag_bit0,
+                                                                   void *stream) {
+    if (int rc = guard_args("sa_module_fused_partial_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return sa_partial_split16<F16x2>("sa_module_fused_partial_f16x2_guarded", ngroups, b, n, m, nsample, c1, c2, c3, xyz, partial, new_xyz, idx, params, out,
+                                     stream, range_flags, flag_bit0);
 }
 extern "C" int ancsh_sa_module_fused_partial_bf16x3(int b, int n, int m, int nsample, int c1, int c2, int c3, const float *xyz,
                                                     const float *partial, const float *new_xyz, const int *idx,

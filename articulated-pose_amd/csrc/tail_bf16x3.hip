@@ -85,8 +85,8 @@ __device__ __forceinline__ void tb_load_input(float *T, const TailBxLoad &F, int
 
 // first layer: K = 131 (9 k-blocks: 8 of interpolated channels from the LDS tile, 1 holding xyz), N = 128, both point blocks; k-block
 // outer so that the input fragments are formed once and dropped: acc[P][4] (128 VGPRs) live, Y written at the end.
-template <class S, int P, bool RELU>
-__device__ __forceinline__ void tb_first(const Bx3Layer &L, const float *T, BxFrag (&Y)[P][8][S::NP]) {
+template <class S, int P, bool RELU, bool G>
+__device__ __forceinline__ void tb_first(const Bx3Layer &L, const float *T, BxFrag (&Y)[P][8][S::NP], RangeMax<G> &rg) {
     constexpr int TM = 4, KB = 9;
     const int lane = threadIdx.x & 63, khalf = lane >> 5, l31 = lane & 31;
     const uint4 *Wp = L.w + lane;
@@ -121,6 +121,10 @@ __device__ __forceinline__ void tb_first(const Bx3Layer &L, const float *T, BxFr
                 v1 = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             u32 s0[S::NP], s1[S::NP], s2[S::NP], s3[S::NP];
+            rg.add2(v0.x, v0.y);
+            rg.add2(v0.z, v0.w);
+            rg.add2(v1.x, v1.y);
+            rg.add2(v1.z, v1.w);
             S::split2(v0.x, v0.y, s0);
             S::split2(v0.z, v0.w, s1);
             S::split2(v1.x, v1.y, s2);
@@ -128,6 +132,7 @@ __device__ __forceinline__ void tb_first(const Bx3Layer &L, const float *T, BxFr
 #pragma unroll
             for (int pl = 0; pl < S::NP; ++pl) X[p][pl] = BxFrag{{s0[pl], s1[pl], s2[pl], s3[pl]}};
         }
+        rg.flush();
         if (kb == KB - 1) raw = bx3_epi_load(L, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -140,7 +145,7 @@ __device__ __forceinline__ void tb_first(const Bx3Layer &L, const float *T, BxFr
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, 8, TM>(L, i, raw, acc[i], Y);
+    for (int i = 0; i < TM; ++i) bx3_tile_epilogue<S, P, RELU, 8, TM>(L, i, raw, acc[i], Y, rg);
 }
 
 // a head block: n <= 32 outputs (weights / bias / scale / shift padded to 32 columns by the host) in the NORMAL orientation (activations
@@ -183,19 +188,20 @@ __device__ __forceinline__ void tb_head(const TailBxOp &O, const BxFrag (&X)[P][
 }
 
 // KEEP: the input tile is read again later (fc11_1 leaves the trunk in place): output-tile-outer order, which never holds more than X + Y
-template <class S, int P, bool RELU, bool KEEP = false>
-__device__ __forceinline__ void tb_hidden(const TailBxOp &O, const BxFrag (&X)[P][8][S::NP], BxFrag (&Y)[P][8][S::NP]) {
+template <class S, int P, bool RELU, bool KEEP = false, bool G>
+__device__ __forceinline__ void tb_hidden(const TailBxOp &O, const BxFrag (&X)[P][8][S::NP], BxFrag (&Y)[P][8][S::NP], RangeMax<G> &rg) {
     if (KEEP) {
         const float *const none[P] = {nullptr, nullptr};
-        bx3_hidden<S, 8, 128, P, RELU>(O.L, X, Y, none);
+        bx3_hidden<S, 8, 128, P, RELU>(O.L, X, Y, none, rg);
     } else {
-        bx3_hidden_kouter<S, 8, 128, P, RELU>(O.L, X, Y);
+        bx3_hidden_kouter<S, 8, 128, P, RELU>(O.L, X, Y, rg);
     }
 }
 
-template <class S>
+// GUARD (F16x2 only): range_flags[cloud] |= 1 << (flag_bit0 + blockIdx.y) when a value the wave converts to f16 has |x| > 65504 (bx3.h)
+template <class S, bool GUARD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void tail_bx3_kernel(long rows, TailBxGroups G, TailBxLoad F) {
+void tail_bx3_kernel(long rows, TailBxGroups G, TailBxLoad F, unsigned *__restrict__ range_flags, int flag_bit0) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int P = 2;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -216,22 +222,24 @@ void tail_bx3_kernel(long rows, TailBxGroups G, TailBxLoad F) {
     tb_load_input(T, F, blockIdx.y, row0);
 #endif
     bx3_fence();
+    RangeMax<GUARD> rg;
     BxFrag X[P][8][S::NP], Y[P][8][S::NP];
-    tb_first<S, P, true>(Pg.op[0].L, T, X);
-    tb_hidden<S, P, true>(Pg.op[1], X, Y);
-    tb_hidden<S, P, true>(Pg.op[2], Y, X);
-    tb_hidden<S, P, true>(Pg.op[3], X, Y);                 // Y = the trunk
+    tb_first<S, P, true>(Pg.op[0].L, T, X, rg);
+    tb_hidden<S, P, true>(Pg.op[1], X, Y, rg);
+    tb_hidden<S, P, true>(Pg.op[2], Y, X, rg);
+    tb_hidden<S, P, true>(Pg.op[3], X, Y, rg);             // Y = the trunk
     int i = 4;
     for (int h = 0; h < Pg.nh1; ++h, ++i) tb_head<S, P>(Pg.op[i], Y, row0);
     if (Pg.split) {                                        // block-uniform
-        tb_hidden<S, P, false, true>(Pg.op[i], Y, X);      // fc11_1 (no activation: lib/architecture.py:111); the trunk stays in Y
+        tb_hidden<S, P, false, true>(Pg.op[i], Y, X, rg);  // fc11_1 (no activation: lib/architecture.py:111); the trunk stays in Y
         ++i;
         for (int h = 0; h < Pg.nh2; ++h, ++i) tb_head<S, P>(Pg.op[i], X, row0);
     }
-    tb_hidden<S, P, true>(Pg.op[i], Y, X);
-    tb_hidden<S, P, true>(Pg.op[i + 1], X, Y);
+    tb_hidden<S, P, true>(Pg.op[i], Y, X, rg);
+    tb_hidden<S, P, true>(Pg.op[i + 1], X, Y, rg);
     i += 2;
     for (int h = 0; h < Pg.nh3; ++h, ++i) tb_head<S, P>(Pg.op[i], Y, row0);
+    range_flag(rg, range_flags, row0 / F.n, flag_bit0 + (int)blockIdx.y);     // 64 rows never straddle clouds
 }
 
 }  // namespace ancsh
@@ -248,7 +256,8 @@ using namespace ancsh;
 // tail with and without early_split_nocs.
 template <class S>
 static int tail_split16(int ngroups, int b, int n, int m, int c2, const float *points2, const int *idx, const float *weight, const float *xyz,
-                        const int *nops, const int *const *ops, const void *const *const *ptrs, void *stream) {
+                        const int *nops, const int *const *ops, const void *const *const *ptrs, void *stream, unsigned *range_flags = nullptr,
+                        int flag_bit0 = 0) {
     ANCSH_REQUIRE(ngroups >= 1 && ngroups <= TB_MAX_GROUPS, "mlp_chain_grouped_fp_bf16x3: ngroups %d outside 1..%d", ngroups, TB_MAX_GROUPS);
     ANCSH_REQUIRE(b >= 0 && n > 0 && m > 0 && n % 64 == 0, "mlp_chain_grouped_fp_bf16x3: bad shape b=%d n=%d (a multiple of 64) m=%d", b, n, m);
     ANCSH_REQUIRE(c2 == 128, "mlp_chain_grouped_fp_bf16x3: the interpolated part must have 128 channels (got %d)", c2);
@@ -308,8 +317,17 @@ static int tail_split16(int ngroups, int b, int n, int m, int c2, const float *p
     F.points2 = points2; F.idx = idx; F.weight = weight; F.xyz = xyz; F.n = n; F.m = m; F.b = b;
     const long rows = (long)b * n;
     const size_t lds = sizeof(float) * 4 * 64 * TB_LD;
+    if constexpr (guardable<S>()) {
+        if (range_flags) {
+            (void)hipFuncSetAttribute((const void *)tail_bx3_kernel<S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((tail_bx3_kernel<S, true>), dim3((unsigned)((rows + 255) / 256), ngroups), dim3(256), lds, (hipStream_t)stream, rows, G, F,
+                               range_flags, flag_bit0);
+            return check_launch("mlp_chain_grouped_fp_bf16x3");
+        }
+    }
     (void)hipFuncSetAttribute((const void *)tail_bx3_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(tail_bx3_kernel<S>, dim3((unsigned)((rows + 255) / 256), ngroups), dim3(256), lds, (hipStream_t)stream, rows, G, F);
+    hipLaunchKernelGGL(tail_bx3_kernel<S>, dim3((unsigned)((rows + 255) / 256), ngroups), dim3(256), lds, (hipStream_t)stream, rows, G, F,
+                       (unsigned *)nullptr, 0);
     return check_launch("mlp_chain_grouped_fp_bf16x3");
 }
 
@@ -323,4 +341,12 @@ extern "C" int ancsh_mlp_chain_grouped_fp_f16x2(int ngroups, int b, int n, int m
                                                 const float *weight, const float *xyz, const int *nops, const int *const *ops,
                                                 const void *const *const *ptrs, void *stream) {
     return tail_split16<F16x2>(ngroups, b, n, m, c2, points2, idx, weight, xyz, nops, ops, ptrs, stream);
+}
+// ... guarded (bx3.h's range guard): range_flags (b words) |= 1 << (flag_bit0 + g) for every (cloud, network g) with an activation the scheme
+// converts to f16 beyond +-65504.  -1 before any launch for a NULL range_flags or flag_bit0 + ngroups > 32.
+extern "C" int ancsh_mlp_chain_grouped_fp_f16x2_guarded(int ngroups, int b, int n, int m, int c2, const float *points2, const int *idx,
+                                                        const float *weight, const float *xyz, const int *nops, const int *const *ops,
+                                                        const void *const *const *ptrs, unsigned *range_flags, int flag_bit0, void *stream) {
+    if (int rc = guard_args("mlp_chain_grouped_fp_f16x2_guarded", ngroups, range_flags, flag_bit0)) return rc;
+    return tail_split16<F16x2>(ngroups, b, n, m, c2, points2, idx, weight, xyz, nops, ops, ptrs, stream, range_flags, flag_bit0);
 }

@@ -35,22 +35,25 @@ class Network(object):
         self.device = torch.device(device)
         self.scope = scope
 
-    def predict(self, P, geometry=None):
+    def predict(self, P, geometry=None, arithmetic=None, range_flags=None, flag_bit0=0):
         """P: (B,N,3) float32 tensor/ndarray -> dict of device tensors (the reference's pred_dict).
         geometry: optional pointnet_util.Geometry -- empty: filled with this forward's sampling / grouping /
-        3-NN results; non-empty (from another network's forward on the SAME P): reused instead of recomputed."""
+        3-NN results; non-empty (from another network's forward on the SAME P): reused instead of recomputed.
+        arithmetic: None = the module globals (ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME), or 'f32' | 'bf16x3' | 'f16x2' for this forward only
+        (pointnet_util.arithmetic); range_flags: a (B,) int32 device tensor the F16x2 range guard ORs bit flag_bit0 into (F16x2 only)."""
         if not torch.is_tensor(P):
             P = torch.from_numpy(np.ascontiguousarray(P, np.float32))
         P = P.to(self.device)
         if tf_util._state["weights"] is not self.weights:
             tf_util.set_variables(self.weights)
         from . import pointnet_util
+        arith = pointnet_util.arithmetic(arithmetic, range_flags, flag_bit0)
         pointnet_util.use_geometry(geometry)
         try:
             return architecture.get_per_point_model_new(
                 scope=self.scope, P=P, n_max_parts=self.n_max_parts, is_training=False, bn_decay=None,
                 mixed_pred=self.is_mixed, pred_joint=True, pred_joint_ind=True,
-                early_split=self.early_split_nocs, early_split_nocs=self.early_split_nocs)
+                early_split=self.early_split_nocs, early_split_nocs=self.early_split_nocs, arith=arith)
         finally:
             pointnet_util.use_geometry(None)
 

@@ -115,23 +115,22 @@ class PairedNetworks(object):
         l1_up = self._conv(F2[1], h, B * 512, 256, 256, 128)                                                      # (G*B*512, 128)
         return l1_up
 
-    def _mid_chains_split16(self, B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2):
+    def _mid_chains_split16(self, B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2, ar):
         """the three levels on the 16-bit matrix pipe (opt-in experiment, level 4: csrc/mid_bf16x3.hip); layer3 keeps the f32 chain where the
         scheme's planes of a 64 x 512 tile do not fit the LDS (bf16x3)"""
         G, dev = len(self.nets), self.device
         f = dict(dtype=torch.float32, device=dev)
-        name = pointnet_util.split_name
 
         def params(layers_per_level, row0s):
             return _table([_lib.ptr(v) for g in range(G) for ls, r0 in zip(layers_per_level, row0s)
-                           for v in (pointnet_util._bf16x3_weight(ls[g], r0), ls[g]["b"], ls[g]["scale"], ls[g]["shift"])])
+                           for v in (pointnet_util._bf16x3_weight(ls[g], r0, ar.scheme), ls[g]["b"], ls[g]["scale"], ls[g]["shift"])])
 
         npts = l2_points.shape[1]
-        if pointnet_util.SPLIT_SCHEME == "f16x2":
+        if ar.scheme == "f16x2":
             p3 = params(L3, (0, 0, 0))
             nparts = npts // 64
             tile_max = torch.empty((G * B, nparts, 1024), **f)
-            _lib.call(name("ancsh_sa3_chain_grouped_bf16x3"), G, B, npts, 256, 256, 512, 1024, _lib.ptr(l2_xyz), _lib.ptr(l2_points), p3.p, _lib.ptr(tile_max))
+            ar.call("ancsh_sa3_chain_grouped_bf16x3", G, B, npts, 256, 256, 512, 1024, _lib.ptr(l2_xyz), _lib.ptr(l2_points), p3.p, _lib.ptr(tile_max))
         else:
             p3 = _table([_lib.ptr(v) for g in range(G) for ls in L3 for v in (tf_util.packed_weight(ls[g], 0), ls[g]["b"], ls[g]["scale"], ls[g]["shift"])])
             nparts = npts // 32
@@ -142,12 +141,12 @@ class PairedNetworks(object):
         _lib.call("ancsh_fp_single_source_init", G, B, 1024, 256, nparts, _lib.ptr(tile_max), w1.p, _lib.ptr(init))      # exact f32 chain (VALU), as in the f32 path
         p1 = params(F1, (1024, 0))
         l2_up = torch.empty((G * B * npts, 256), **f)
-        _lib.call(name("ancsh_fp1_chain_grouped_bf16x3"), G, B, npts, 256, 256, 256, _lib.ptr(l2_points), _lib.ptr(init), p1.p, _lib.ptr(l2_up))
+        ar.call("ancsh_fp1_chain_grouped_bf16x3", G, B, npts, 256, 256, 256, _lib.ptr(l2_points), _lib.ptr(init), p1.p, _lib.ptr(l2_up))
         n1 = l1_points.shape[1]
         p2 = params(F2, (0, 0))
         l1_up = torch.empty((G * B * n1, 128), **f)
-        _lib.call(name("ancsh_fp2_chain_grouped_bf16x3"), G, B, npts, n1, 256, 128, 256, 128, _lib.ptr(l2_up), _lib.ptr(fi2), _lib.ptr(fw2), _lib.ptr(l1_points),
-                  p2.p, _lib.ptr(l1_up))
+        ar.call("ancsh_fp2_chain_grouped_bf16x3", G, B, npts, n1, 256, 128, 256, 128, _lib.ptr(l2_up), _lib.ptr(fi2), _lib.ptr(fw2), _lib.ptr(l1_points),
+                p2.p, _lib.ptr(l1_up))
         return l1_up
 
     def _mid_chains(self, B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2):
@@ -181,14 +180,18 @@ class PairedNetworks(object):
         return l1_up
 
     # ---- forward -------------------------------------------------------------------------------------------------------------
-    def predict(self, P, geometry=None):
+    def predict(self, P, geometry=None, arithmetic=None, range_flags=None):
+        """-> [pred dict per network].  arithmetic: None = the module globals (ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME), or 'f32' | 'bf16x3' |
+        'f16x2' for this forward only (pointnet_util.arithmetic); range_flags: a (B,) int32 device tensor into which the F16x2 range guard
+        ORs bit g for network g (F16x2 only; csrc/bx3.h)."""
+        ar = pointnet_util.arithmetic(arithmetic, range_flags)
         if not torch.is_tensor(P):
             import numpy as np
             P = torch.from_numpy(np.ascontiguousarray(P, np.float32))
         P = P.to(self.device).contiguous().float()
         _lib.require_cuda(P)
         if not self.eligible():
-            return [n.predict(P, geometry) for n in self.nets]
+            return [n.predict(P, geometry, ar.with_bit(g)) for g, n in enumerate(self.nets)]
         G, (B, N, _), dev = len(self.nets), P.shape, self.device
         est = self.scope + "/est_net/"
         geo = geometry if geometry is not None else pointnet_util.Geometry()
@@ -205,12 +208,12 @@ class PairedNetworks(object):
             for l in ls:
                 tf_util.packed_weight(l)
         l1_points = torch.empty((G * B, 512, 128), **f)
-        bx3 = pointnet_util.SA_BF16X3        # opt-in: the SA levels on the bf16 matrix pipe (six bf16 products per f32 product, csrc/sa_bf16x3.hip)
+        bx3 = ar.level                       # opt-in: the SA levels on the bf16 matrix pipe (six bf16 products per f32 product, csrc/sa_bf16x3.hip)
         if bx3 >= 1:
             p1 = _table([_lib.ptr(v) for g in range(G) for i in range(3)
-                         for v in (pointnet_util._bf16x3_weight(L1[i][g]), L1[i][g]["b"], L1[i][g]["scale"], L1[i][g]["shift"])])
-            _lib.call(pointnet_util.split_name("ancsh_sa_module_fused_bf16x3_grouped"), G, B, N, 512, 64, 0, 64, 64, 128, _lib.ptr(P), None, _lib.ptr(l1_xyz),
-                      _lib.ptr(idx1), p1.p, _lib.ptr(l1_points))
+                         for v in (pointnet_util._bf16x3_weight(L1[i][g], 0, ar.scheme), L1[i][g]["b"], L1[i][g]["scale"], L1[i][g]["shift"])])
+            ar.call("ancsh_sa_module_fused_bf16x3_grouped", G, B, N, 512, 64, 0, 64, 64, 128, _lib.ptr(P), None, _lib.ptr(l1_xyz),
+                    _lib.ptr(idx1), p1.p, _lib.ptr(l1_points))
         else:
             p1 = _table([_lib.ptr(L1[i][g][k]) for g in range(G) for i in range(3) for k in ("w_packed", "b", "scale", "shift")])
             _lib.call("ancsh_sa_module_fused_grouped", G, B, N, 512, 64, 0, 64, 64, 128, _lib.ptr(P), None, _lib.ptr(l1_xyz), _lib.ptr(idx1),
@@ -226,10 +229,10 @@ class PairedNetworks(object):
         l2_points = torch.empty((G * B, 128, 256), **f)
         if bx3 >= 2:
             p2 = _table([_lib.ptr(v) for g in range(G) for v in
-                         ([pointnet_util._bf16x3_xyz_weight(first[g], 128), first[g]["b"], first[g]["scale"], first[g]["shift"]] +
-                          [x for i in (1, 2) for x in (pointnet_util._bf16x3_weight(L2[i][g]), L2[i][g]["b"], L2[i][g]["scale"], L2[i][g]["shift"])])])
-            _lib.call(pointnet_util.split_name("ancsh_sa_module_fused_partial_bf16x3_grouped"), G, B, 512, 128, 64, 128, 128, 256, _lib.ptr(l1_xyz), _lib.ptr(partial),
-                      _lib.ptr(l2_xyz), _lib.ptr(idx2), p2.p, _lib.ptr(l2_points))
+                         ([pointnet_util._bf16x3_xyz_weight(first[g], 128, ar.scheme), first[g]["b"], first[g]["scale"], first[g]["shift"]] +
+                          [x for i in (1, 2) for x in (pointnet_util._bf16x3_weight(L2[i][g], 0, ar.scheme), L2[i][g]["b"], L2[i][g]["scale"], L2[i][g]["shift"])])])
+            ar.call("ancsh_sa_module_fused_partial_bf16x3_grouped", G, B, 512, 128, 64, 128, 128, 256, _lib.ptr(l1_xyz), _lib.ptr(partial),
+                    _lib.ptr(l2_xyz), _lib.ptr(idx2), p2.p, _lib.ptr(l2_points))
         else:
             p2 = _table([_lib.ptr(v) for g in range(G) for v in
                          ([first[g]["w_xyz_packed"], first[g]["b"], first[g]["scale"], first[g]["shift"]] +
@@ -241,7 +244,7 @@ class PairedNetworks(object):
         F1 = [self._layers("fa_layer1/conv_%d" % i) for i in range(2)]
         F2 = [self._layers("fa_layer2/conv_%d" % i) for i in range(2)]
         if bx3 >= 4 and l2_points.shape[1] % 64 == 0 and l1_points.shape[1] % 64 == 0:
-            l1_up = self._mid_chains_split16(B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2)
+            l1_up = self._mid_chains_split16(B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2, ar)
         elif MID_CHAIN:
             l1_up = self._mid_chains(B, l2_xyz, l2_points, l1_points, fi2, fw2, L3, F1, F2)
         else:
@@ -252,9 +255,9 @@ class PairedNetworks(object):
         for net in self.nets:
             tf_util.set_variables(net.weights)
             with tf_util.variable_scope(self.scope):
-                progs.append(architecture._tail_program(B * N, net.n_max_parts, net.is_mixed, net.early_split_nocs, dev, bf16x3=tail_bx3))
+                progs.append(architecture._tail_program(B * N, net.n_max_parts, net.is_mixed, net.early_split_nocs, dev, bf16x3=tail_bx3, scheme=ar.scheme))
         if tail_bx3:
-            architecture.run_tail_programs_bf16x3(progs, (B, N, 512, l1_up.view(G * B, 512, 128), fi3, fw3, P))
+            architecture.run_tail_programs_bf16x3(progs, (B, N, 512, l1_up.view(G * B, 512, 128), fi3, fw3, P), ar)
         elif TAIL_FP and N % 128 == 0:
             # fa_layer3's input rows [interpolated (128) | xyz (3)] are built in the chain's tile load: both networks' chains in ONE launch
             # (two waves per SIMD), no (G * B, N, 132) concat buffer written and read back, no interpolate + concat launch

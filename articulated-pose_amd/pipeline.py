@@ -39,10 +39,32 @@ def check_hardware_queues(slots):
     return cur
 
 
+def f16x2_weight_violations(nets):
+    """The weight half of the F16x2 range guard (the kernels check the activations): every kernel the F16x2 path packs -- all rows of
+    every layer the split-16 launches run, except layer2/conv0's feature rows 3.. and fa_layer1/conv_0's rows ..1023, which stay f32
+    (per-point partial sums, the single-source share) -- against f16's largest value.  nets = [(label, Network)];
+    -> [(label:layer, max |w|)] with |w| > 65504 (NaN ignored).  Host-side, no GPU needed."""
+    from .pointnet_util import f16_range_violations
+    from .weights import layer_table
+    kernels = []
+    for label, net in nets:
+        for full, cin, cout, _bn, _kind in layer_table(net.n_max_parts, net.is_mixed, net.early_split_nocs, net.scope):
+            w = net.weights.get(full + "/weights")
+            if w is None:
+                continue
+            w = np.asarray(w.detach().cpu() if torch.is_tensor(w) else w).reshape(-1, np.shape(w)[-1])
+            if full.endswith("/layer2/conv0"):
+                w = w[:3]
+            elif full.endswith("/fa_layer1/conv_0"):
+                w = w[1024:]
+            kernels.append(("%s:%s" % (label, full), w))
+    return f16_range_violations(kernels)
+
+
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -53,6 +75,10 @@ class _Slot(object):
         self.stream = torch.cuda.Stream(device=device)
         self.graph = None
         self.out = None
+        # range guard (F16x2): the flag words the guarded launches OR into, and the f32 graph of the same step that refits flagged clouds
+        self.flags = torch.zeros((B,), dtype=torch.int32, device=device) if range_guard else None
+        self.graph32 = None
+        self.out32 = None
         if raw_capacity is not None:
             # streaming: raw rows + a header [seed (int64 bits) | offsets (B+1) int32 | norm factors (B) float32] on the device, their
             # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again
@@ -64,6 +90,9 @@ class _Slot(object):
             self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
+            if range_guard:
+                self.h_flags = torch.zeros((B,), dtype=torch.int32).pin_memory()
+                self.h_record32 = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
             self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[2:B + 3],
                                                                    hdr[B + 3:2 * B + 3].view(np.float32))
@@ -106,7 +135,7 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None):
+                 arithmetic=None, raw_capacity=None, range_guard=False):
         self.K, self.B, self.N = num_parts, batch_size, num_points
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls) per batch, padding included
@@ -121,6 +150,17 @@ class AncshPipeline(object):
         self.device = torch.device(device)
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
+        # range_guard (F16x2 only): the guarded kernels flag every (cloud, network) with an activation beyond f16's range, and flagged clouds
+        # are refit by an f32 graph of the same step (streaming: retire() does it; step(): out["range_flags"] + rerun_f32()).  The weights
+        # the F16x2 path packs are checked here, once.
+        self.range_guard = bool(range_guard)
+        if self.range_guard:
+            if arithmetic != "f16x2":
+                raise ValueError("range_guard=True needs arithmetic='f16x2' (f32 and bf16x3 have f32's range)")
+            bad = f16x2_weight_violations([("ancsh", self.ancsh), ("npcs", self.npcs)])
+            if bad:
+                raise ValueError("range_guard: weights beyond f16's range (|w| > 65504) in " +
+                                 ", ".join("%s (max |w| = %.6g)" % nb for nb in bad))
         # few batches in flight = a latency deployment: the LM fits take the eight-lanes-per-fit schedule (an EXPLICIT choice of this
         # class, overridable with lm_schedule; the C ABI's default schedule never depends on slots or batch size).  The two
         # schedules agree to ~1e-7, not to the last bit: pass lm_schedule="throughput" for bytes equal to a many-slot pipeline.
@@ -134,13 +174,14 @@ class AncshPipeline(object):
         if arithmetic not in (None, "f32", "bf16x3", "f16x2"):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.arithmetic = arithmetic
+        self.f32_reruns = 0                 # batches retire() refit in f32 (range guard)
         # both networks layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         import os
         from .paired import PairedNetworks
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity) for _ in range(max(1, slots))]
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -169,10 +210,10 @@ class AncshPipeline(object):
             sl.draws_a = torch.as_tensor(np.ascontiguousarray(draws_a, np.int32)).to(self.device)
             sl.draws_b = None if draws_b is None else torch.as_tensor(np.ascontiguousarray(draws_b, np.int32)).to(self.device)
 
-    def _networks(self, P, geom):
+    def _networks(self, P, geom, arithmetic, flags):
         if self.paired is not None:
-            return self.paired.predict(P, geom)          # every backbone layer of both networks in one grouped launch
-        return self.ancsh.predict(P, geom), self.npcs.predict(P, geom)
+            return self.paired.predict(P, geom, arithmetic, flags)          # every backbone layer of both networks in one grouped launch
+        return self.ancsh.predict(P, geom, arithmetic, flags, 0), self.npcs.predict(P, geom, arithmetic, flags, 1)
 
     def _sample(self, sl):
         """The captured step's first launch when streaming: the slot's raw clouds -> its P / joint_cls."""
@@ -183,27 +224,26 @@ class AncshPipeline(object):
                   _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P), _lib.ptr(sl.joint_cls), None)
         return seed
 
-    def _run(self, sl=None):
+    def _run(self, sl=None, f32=False):
+        """The step on slot sl: in the pipeline's arithmetic, or (f32=True: the range guard's refit) in f32 from the same slot inputs."""
         sl = sl or self.slots[0]
+        guard = self.range_guard and not f32
+        if guard:
+            sl.flags.zero_()                  # the captured step's first node: the guarded launches only OR into the words
         seed_dev = self._sample(sl) if self.raw_capacity is not None else None
         from . import pointnet_util
         geom = pointnet_util.Geometry()       # FPS / ball query / 3-NN depend only on P: computed once, used by both nets
-        if self.arithmetic is None:
-            a, n = self._networks(sl.P, geom)
-        else:
-            keep = pointnet_util.SA_BF16X3, pointnet_util.SPLIT_SCHEME
-            level = {"f32": 0, "bf16x3": 3, "f16x2": 4}[self.arithmetic]
-            pointnet_util.SA_BF16X3, pointnet_util.SPLIT_SCHEME = level, (self.arithmetic if level else keep[1])
-            try:
-                a, n = self._networks(sl.P, geom)
-            finally:
-                pointnet_util.SA_BF16X3, pointnet_util.SPLIT_SCHEME = keep
+        # the arithmetic goes down the layer helpers explicitly (None: the module globals); nothing global is changed
+        a, n = self._networks(sl.P, geom, "f32" if f32 else self.arithmetic, sl.flags if guard else None)
         if self.couple:
             nocs, mask, axis = n["nocs_per_point"], n["W"], a["joint_axis_per_point"]
         else:
             nocs, mask, axis = sl.pred_nocs, sl.pred_mask, sl.pred_axis
         sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev)
-        return dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
+        out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
+        if guard:
+            out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
+        return out
 
     def prepare(self):
         torch.cuda.synchronize(self.device)
@@ -211,11 +251,19 @@ class AncshPipeline(object):
             with torch.cuda.stream(sl.stream):
                 for _ in range(2):
                     sl.out = self._run(sl)
+                if self.range_guard:
+                    for _ in range(2):
+                        sl.out32 = self._run(sl, f32=True)
             sl.stream.synchronize()
             if self._use_graph:
                 sl.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(sl.graph, stream=sl.stream):
                     sl.out = self._run(sl)
+                if self.range_guard:
+                    # the refit: a second graph per slot, captured from the same slot inputs (raw rows + header, or P / joint_cls)
+                    sl.graph32 = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(sl.graph32, stream=sl.stream):
+                        sl.out32 = self._run(sl, f32=True)
         if self._use_graph:
             # first launches of the instantiated graphs (the runtime uploads an executable graph on its first launch), all slots in
             # flight together as in steady state; results are those of the eager passes above
@@ -223,6 +271,8 @@ class AncshPipeline(object):
             for _ in range(int(os.environ.get("ANCSH_PREPARE_REPLAYS", "2"))):
                 for sl in self.slots:
                     with torch.cuda.stream(sl.stream):
+                        if sl.graph32 is not None:
+                            sl.graph32.replay()
                         sl.graph.replay()
             self.synchronize()
         self._prepared = True
@@ -250,6 +300,20 @@ class AncshPipeline(object):
             else:
                 sl.out = self._run(sl)
         return sl, sl.out
+
+    def rerun_f32(self, slot):
+        """Range guard: replay slot's f32 graph (the same step from the same slot inputs, in f32) on its stream and return its outputs --
+        asynchronous, valid once slot.stream is synchronised and until that slot's next step() or rerun_f32().  slot: a _Slot (as step()
+        returns it) or its index.  For the clouds whose out["range_flags"] word is non-zero after step()."""
+        if not self.range_guard:
+            raise RuntimeError("rerun_f32() needs AncshPipeline(..., arithmetic='f16x2', range_guard=True)")
+        sl = self.slots[slot] if isinstance(slot, int) else slot
+        with torch.cuda.stream(sl.stream):
+            if sl.graph32 is not None:
+                sl.graph32.replay()
+            else:
+                sl.out32 = self._run(sl, f32=True)
+        return sl.out32
 
     def synchronize(self):
         for sl in self.slots:
@@ -299,26 +363,42 @@ class AncshPipeline(object):
                 sl.out = self._run(sl)
             # right behind the replay on the same stream: the next replay's pool reuses the record's block (see step())
             sl.h_record.copy_(sl.out["record"], non_blocking=True)
+            if self.range_guard:
+                sl.h_flags.copy_(sl.flags, non_blocking=True)
             sl.d2h_done.record(sl.stream)
         self._next = (self._next + 1) % len(self.slots)
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self):
+    def retire(self, flags=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
-        records, a fresh host array."""
+        records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
+        (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
+        the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
+        without the guard)."""
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
-        return tag, seed, sl.h_record[:n_valid].numpy().copy()
+        record = sl.h_record[:n_valid].numpy().copy()
+        words = sl.h_flags[:n_valid].numpy().copy() if self.range_guard else np.zeros((n_valid,), np.int32)
+        hit = np.flatnonzero(words)
+        if hit.size:
+            self.rerun_f32(sl)
+            with torch.cuda.stream(sl.stream):
+                sl.h_record32.copy_(sl.out32["record"], non_blocking=True)
+            sl.stream.synchronize()
+            record[hit] = sl.h_record32.numpy()[hit]
+            self.f32_reruns += 1
+        return (tag, seed, record, words) if flags else (tag, seed, record)
 
-    def stream_batches(self, batches):
+    def stream_batches(self, batches, flags=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
-        batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order."""
+        batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
+        flag words, see retire())."""
         for k, item in enumerate(batches):
             if len(self._inflight) == len(self.slots):
-                yield self.retire()
+                yield self.retire(flags)
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._inflight:
-            yield self.retire()
+            yield self.retire(flags)

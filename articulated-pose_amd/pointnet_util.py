@@ -127,36 +127,100 @@ SA_BF16X3 = int(_os.environ.get('ANCSH_SA_BF16X3', '0'))      # 1: the level wit
 SPLIT_SCHEME = _os.environ.get('ANCSH_SPLIT_SCHEME', 'bf16x3')
 
 
-def split_name(entry):
-    """ABI name of a split-16 entry point for the active scheme: '..._bf16x3...' -> '..._f16x2...' when SPLIT_SCHEME == 'f16x2'"""
-    if SPLIT_SCHEME not in ('bf16x3', 'f16x2'):
-        raise ValueError("ANCSH_SPLIT_SCHEME must be bf16x3 or f16x2, got %r" % (SPLIT_SCHEME,))
-    return entry.replace('bf16x3', SPLIT_SCHEME)
+def split_name(entry, scheme=None):
+    """ABI name of a split-16 entry point for `scheme` (None: the active SPLIT_SCHEME): '..._bf16x3...' -> '..._f16x2...' for 'f16x2'"""
+    scheme = SPLIT_SCHEME if scheme is None else scheme
+    if scheme not in ('bf16x3', 'f16x2'):
+        raise ValueError("ANCSH_SPLIT_SCHEME must be bf16x3 or f16x2, got %r" % (scheme,))
+    return entry.replace('bf16x3', scheme)
 
 
-def _split_pack(w):
-    """(k, n % 32 == 0) f32 kernel on the device -> its planes in MFMA fragment order for the active scheme"""
+class Arithmetic(object):
+    """The arithmetic of one forward, passed explicitly down the layer helpers instead of read from the module globals:
+    level = SA_BF16X3's meaning (0: f32 everywhere; 1 / 2: the SA levels; 3: + the tail; 4: + the mid-section), scheme = the split scheme,
+    range_flags = None or a (B,) int32 device tensor the F16x2 range guard ORs into (bit flag_bit0 + network; csrc/bx3.h)."""
+
+    __slots__ = ("level", "scheme", "range_flags", "flag_bit0")
+
+    def __init__(self, level, scheme, range_flags=None, flag_bit0=0):
+        if range_flags is not None:
+            if scheme != 'f16x2' or level < 1:
+                raise ValueError("range_flags: the range guard is for the F16x2 scheme only (Bf16x3 and f32 have f32's range)")
+            if range_flags.dtype != torch.int32 or not range_flags.is_cuda or not range_flags.is_contiguous():
+                raise ValueError("range_flags must be a contiguous int32 device tensor, one word per cloud")
+        self.level, self.scheme, self.range_flags, self.flag_bit0 = int(level), scheme, range_flags, int(flag_bit0)
+
+    def with_bit(self, flag_bit0):
+        return Arithmetic(self.level, self.scheme, self.range_flags, flag_bit0)
+
+    def name(self, entry):
+        """the ABI name of a split-16 entry point in this arithmetic (+ '_guarded' when the range guard is on)"""
+        return split_name(entry, self.scheme) + ("_guarded" if self.range_flags is not None else "")
+
+    def call(self, entry, *args):
+        """a split-16 launch: the guarded form takes (range_flags, flag_bit0) after the unguarded arguments"""
+        if self.range_flags is not None:
+            args = args + (_lib.ptr(self.range_flags), self.flag_bit0)
+        _lib.call(self.name(entry), *args)
+
+
+ARITHMETICS = {"f32": (0, None), "bf16x3": (3, "bf16x3"), "f16x2": (4, "f16x2")}
+
+
+def arithmetic(spec=None, range_flags=None, flag_bit0=0):
+    """An Arithmetic from spec: None = the module globals (ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME, read now), 'f32' | 'bf16x3' | 'f16x2'
+    (AncshPipeline's levels: bf16x3 at level 3, f16x2 at level 4), or an Arithmetic (returned as it is)."""
+    if isinstance(spec, Arithmetic):
+        return spec
+    if spec is None:
+        return Arithmetic(SA_BF16X3, SPLIT_SCHEME, range_flags, flag_bit0)     # (an unknown scheme raises where a split-16 name is formed)
+    if spec not in ARITHMETICS:
+        raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
+    level, scheme = ARITHMETICS[spec]
+    return Arithmetic(level, scheme or SPLIT_SCHEME, range_flags, flag_bit0)
+
+
+def _split_pack(w, scheme=None):
+    """(k, n % 32 == 0) f32 kernel on the device -> its planes in MFMA fragment order for `scheme` (None: the active one)"""
     k, n = w.shape
-    nbytes = getattr(_lib.lib(), split_name("ancsh_sa_packed_weight_bytes_bf16x3"))(k, n)
+    nbytes = getattr(_lib.lib(), split_name("ancsh_sa_packed_weight_bytes_bf16x3", scheme))(k, n)
     packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    _lib.call(split_name("ancsh_sa_pack_weights_bf16x3"), k, n, _lib.ptr(w), _lib.ptr(packed))
+    _lib.call(split_name("ancsh_sa_pack_weights_bf16x3", scheme), k, n, _lib.ptr(w), _lib.ptr(packed))
     return packed
 
 
-def _bf16x3_weight(layer, row0=0):
+def _bf16x3_weight(layer, row0=0, scheme=None):
     """the layer's kernel (rows row0..) split into the scheme's 16-bit planes in MFMA fragment order, cached on the layer dict (per scheme)"""
-    key = "w_%s_%d" % (SPLIT_SCHEME, row0)
+    scheme = SPLIT_SCHEME if scheme is None else scheme
+    key = "w_%s_%d" % (scheme, row0)
     if key not in layer:
-        layer[key] = _split_pack(layer["w"][row0:].contiguous())
+        layer[key] = _split_pack(layer["w"][row0:].contiguous(), scheme)
     return layer[key]
 
 
-def _bf16x3_xyz_weight(first, c1):
+def _bf16x3_xyz_weight(first, c1, scheme=None):
     """the three coordinate rows of a feature level's first layer (tf_util.sa_first_layer_split) in the split packing, cached"""
-    key = "w_xyz_" + SPLIT_SCHEME
+    scheme = SPLIT_SCHEME if scheme is None else scheme
+    key = "w_xyz_" + scheme
     if key not in first:
-        first[key] = _split_pack(first["w"][:3].contiguous())
+        first[key] = _split_pack(first["w"][:3].contiguous(), scheme)
     return first[key]
+
+
+F16_MAX = 65504.0
+
+
+def f16_range_violations(named_kernels):
+    """The weight half of the F16x2 range guard (the kernels check the activations): named_kernels = iterable of (name, array-like) ->
+    [(name, max |w|)] for every kernel with some |w| > 65504, the largest value f16 holds (NaN ignored, +-inf counted).  Host-side."""
+    import numpy as np
+    bad = []
+    for name, w in named_kernels:
+        a = np.abs(np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float64))
+        a = a[~np.isnan(a)]
+        if a.size and a.max() > F16_MAX:
+            bad.append((name, float(a.max())))
+    return bad
 
 
 def _sample_and_query(npoint, radius, nsample, xyz):
@@ -192,8 +256,9 @@ def precompute_geometry(xyz, geometry, scope='SPFN/est_net'):
     return geometry
 
 
-def _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, knn, use_xyz):
+def _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, knn, use_xyz, arith=None):
     import ctypes
+    ar = arithmetic(arith)
     if not FUSED_SA or group_all or knn or mlp2 is not None or not use_xyz or nsample != 64:
         return None
     c = 0 if points is None else points.shape[2]
@@ -204,10 +269,10 @@ def _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, kn
     new_xyz, idx = _sample_and_query(npoint, radius, nsample, xyz)
     layers = [tf_util.get_layer_sa_packed(tf_util.current_scope('conv%d' % i), xyz.device) for i in range(3)]
     out = torch.empty((b, npoint, mlp[2]), dtype=torch.float32, device=xyz.device)
-    if SA_BF16X3 >= 1 and c == 0:
-        ptrs = (ctypes.c_void_p * 12)(*[_lib.ptr(v) for l in layers for v in (_bf16x3_weight(l), l["b"], l["scale"], l["shift"])])
-        _lib.call(split_name("ancsh_sa_module_fused_bf16x3_grouped"), 1, b, n, npoint, nsample, 0, mlp[0], mlp[1], mlp[2], _lib.ptr(xyz), None,
-                  _lib.ptr(new_xyz), _lib.ptr(idx), ctypes.cast(ptrs, ctypes.c_void_p), _lib.ptr(out))
+    if ar.level >= 1 and c == 0:
+        ptrs = (ctypes.c_void_p * 12)(*[_lib.ptr(v) for l in layers for v in (_bf16x3_weight(l, 0, ar.scheme), l["b"], l["scale"], l["shift"])])
+        ar.call("ancsh_sa_module_fused_bf16x3_grouped", 1, b, n, npoint, nsample, 0, mlp[0], mlp[1], mlp[2], _lib.ptr(xyz), None,
+                _lib.ptr(new_xyz), _lib.ptr(idx), ctypes.cast(ptrs, ctypes.c_void_p), _lib.ptr(out))
         return new_xyz, out, idx
     if c == 0:
         ptrs = (ctypes.c_void_p * 12)(*[_lib.ptr(l[k]) for l in layers for k in ("w_packed", "b", "scale", "shift")])
@@ -225,11 +290,11 @@ def _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, kn
     else:
         _lib.call("ancsh_conv1x1", b * n, c, mlp[0], _lib.ptr(feats), c, _lib.ptr(first["w_feat"]), None, None, None, 2, _lib.ptr(partial),
                   mlp[0], 0)
-    if SA_BF16X3 >= 2:
-        ptrs = (ctypes.c_void_p * 12)(*([_lib.ptr(_bf16x3_xyz_weight(first, mlp[0]))] + [_lib.ptr(first[k]) for k in ("b", "scale", "shift")] +
-                                        [_lib.ptr(v) for l in layers[1:] for v in (_bf16x3_weight(l), l["b"], l["scale"], l["shift"])]))
-        _lib.call(split_name("ancsh_sa_module_fused_partial_bf16x3_grouped"), 1, b, n, npoint, nsample, mlp[0], mlp[1], mlp[2], _lib.ptr(xyz), _lib.ptr(partial),
-                  _lib.ptr(new_xyz), _lib.ptr(idx), ctypes.cast(ptrs, ctypes.c_void_p), _lib.ptr(out))
+    if ar.level >= 2:
+        ptrs = (ctypes.c_void_p * 12)(*([_lib.ptr(_bf16x3_xyz_weight(first, mlp[0], ar.scheme))] + [_lib.ptr(first[k]) for k in ("b", "scale", "shift")] +
+                                        [_lib.ptr(v) for l in layers[1:] for v in (_bf16x3_weight(l, 0, ar.scheme), l["b"], l["scale"], l["shift"])]))
+        ar.call("ancsh_sa_module_fused_partial_bf16x3_grouped", 1, b, n, npoint, nsample, mlp[0], mlp[1], mlp[2], _lib.ptr(xyz), _lib.ptr(partial),
+                _lib.ptr(new_xyz), _lib.ptr(idx), ctypes.cast(ptrs, ctypes.c_void_p), _lib.ptr(out))
         return new_xyz, out, idx
     ptrs = (ctypes.c_void_p * 12)(*([_lib.ptr(first["w_xyz_packed"])] + [_lib.ptr(first[k]) for k in ("b", "scale", "shift")] +
                                     [_lib.ptr(l[k]) for l in layers[1:] for k in ("w_packed", "b", "scale", "shift")]))
@@ -239,7 +304,7 @@ def _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, kn
 
 
 def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, is_training, bn_decay, scope,
-                       bn=True, pooling='max', knn=False, use_xyz=True, use_nchw=False, reuse=False):
+                       bn=True, pooling='max', knn=False, use_xyz=True, use_nchw=False, reuse=False, arith=None):
     '''Set-abstraction level (pointnet_util.py:94-161): sample + group, the shared MLP `mlp` on every neighbour, max over the
     neighbourhood, optional `mlp2` on the pooled vector.  Returns new_xyz (B, npoint, 3), new_points (B, npoint, mlp[-1] or
     mlp2[-1]) and idx (B, npoint, nsample) int32.  Only pooling='max', NHWC, inference.'''
@@ -248,7 +313,7 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
     if use_nchw:
         raise NotImplementedError("NHWC only")
     with tf_util.variable_scope(scope):
-        fused = _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, knn, use_xyz)
+        fused = _try_fused_sa(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, knn, use_xyz, arith)
         if fused is not None:
             return fused
         if group_all:

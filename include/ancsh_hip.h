@@ -41,7 +41,8 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 8: + ancsh_input_sample_stream, ancsh_ransac_single_rec_dseed, ancsh_ransac_joint_rec_dseed (the streaming pipeline);
+int ancsh_abi_version(void);   /* 9: + the F16x2 range guard (ancsh_*_f16x2*_guarded);
+                                 * 8: + ancsh_input_sample_stream, ancsh_ransac_single_rec_dseed, ancsh_ransac_joint_rec_dseed (the streaming pipeline);
                                  * 7 since round 6 (5: round 5, 4: round 4, 3: round 3).  Operator entry points are only ever added: a library of version v serves every caller
                                  * written for <= v.  The one removal, in 7: ancsh_hbm_copy -- bench.py's HBM-copy yardstick, never an operator -- left the library
                                  * (tools/microbench/membw.hip, its own .so) */
@@ -284,6 +285,20 @@ int ancsh_sa_module_fused_f16x2_grouped(int ngroups, int b, int n, int m, int ns
 int ancsh_sa_module_fused_partial_f16x2_grouped(int ngroups, int b, int n, int m, int nsample, int c1, int c2, int c3,
                                                 const float *xyz, const float *partial, const float *new_xyz, const int *idx,
                                                 const float *const *params, float *out, void *stream);
+/* RANGE GUARD of the F16x2 scheme: the six ancsh_*_f16x2*_guarded entry points take the arguments of their unguarded forms plus
+ * range_flags / flag_bit0 and compute the same outputs, bit for bit.  range_flags holds one word per GEOMETRY cloud (b words); group g of
+ * the launch ORs bit flag_bit0 + g into the word of every cloud for which some activation the scheme converts to f16 has |x| > 65504
+ * (+-inf included; NaN never flags).  A paired launch (group 0 = ANCSH, 1 = NPCS) and two one-network launches with flag_bit0 = 0 / 1 fill
+ * the same layout.  The words are only ever ORed: the caller zeroes them.  Weights are NOT checked (static: check them once on the host),
+ * and neither is precision lost to f16's subnormal range (|x| < 2^-14).  Cost: one v_max3_f32 per converted value pair, one ballot per wave
+ * and one atomic per flagged (wave, cloud).  Returns -1 before any launch for a NULL range_flags or flag_bit0 < 0 or flag_bit0 + ngroups > 32. */
+int ancsh_sa_module_fused_f16x2_grouped_guarded(int ngroups, int b, int n, int m, int nsample, int cfeat, int c1, int c2, int c3,
+                                                const float *xyz, const float *feats, const float *new_xyz, const int *idx,
+                                                const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream);
+int ancsh_sa_module_fused_partial_f16x2_grouped_guarded(int ngroups, int b, int n, int m, int nsample, int c1, int c2, int c3,
+                                                        const float *xyz, const float *partial, const float *new_xyz, const int *idx,
+                                                        const float *const *params, float *out, unsigned *range_flags, int flag_bit0,
+                                                        void *stream);
 
 /* Weight layout of ancsh_sa_module_fused: the MFMA B fragments of four consecutive k-steps as one 16-byte load per lane,
  *   packed[((slot*ceil(n/32) + j)*64 + lane)*4 + q] = w[2*(4*slot + q) + (lane >> 5)][j*32 + (lane & 31)]   (0 past row k-1 / column n-1).
@@ -373,6 +388,9 @@ int ancsh_mlp_chain_grouped_fp_bf16x3(int ngroups, int b, int n, int m, int c2, 
 int ancsh_mlp_chain_grouped_fp_f16x2(int ngroups, int b, int n, int m, int c2, const float *points2, const int *idx, const float *weight,
                                      const float *xyz, const int *nops, const int *const *ops, const void *const *const *ptrs,
                                      void *stream);      /* the F16x2 scheme; weights packed by ancsh_sa_pack_weights_f16x2 */
+int ancsh_mlp_chain_grouped_fp_f16x2_guarded(int ngroups, int b, int n, int m, int c2, const float *points2, const int *idx, const float *weight,
+                                             const float *xyz, const int *nops, const int *const *ops, const void *const *const *ptrs,
+                                             unsigned *range_flags, int flag_bit0, void *stream);     /* ... with the range guard (see above) */
 
 /* ... and the MIDDLE of the backbone (ancsh_sa3_chain_grouped / ancsh_fp1_chain_grouped / ancsh_fp2_chain_grouped) on the 16-bit matrix pipe
  * (csrc/mid_bf16x3.hip): the activations of a 64-row tile live in LDS as the scheme's 16-bit planes, the workgroup's waves split every layer
@@ -392,6 +410,14 @@ int ancsh_fp2_chain_grouped_bf16x3(int ngroups, int b, int m, int n, int c2, int
                                    const float *weight, const float *points1, const float *const *params, float *out, void *stream);
 int ancsh_fp2_chain_grouped_f16x2(int ngroups, int b, int m, int n, int c2, int c1, int n1, int n2, const float *points2, const int *idx,
                                   const float *weight, const float *points1, const float *const *params, float *out, void *stream);
+/* ... the F16x2 forms with the range guard (see ancsh_sa_module_fused_f16x2_grouped_guarded) */
+int ancsh_sa3_chain_grouped_f16x2_guarded(int ngroups, int b, int npts, int cfeat, int c1, int c2, int c3, const float *xyz, const float *feats,
+                                          const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream);
+int ancsh_fp1_chain_grouped_f16x2_guarded(int ngroups, int b, int npts, int cskip, int c1, int c2, const float *skip, const float *init,
+                                          const float *const *params, float *out, unsigned *range_flags, int flag_bit0, void *stream);
+int ancsh_fp2_chain_grouped_f16x2_guarded(int ngroups, int b, int m, int n, int c2, int c1, int n1, int n2, const float *points2, const int *idx,
+                                          const float *weight, const float *points1, const float *const *params, float *out,
+                                          unsigned *range_flags, int flag_bit0, void *stream);
 
 /* tf.reduce_max over nsample (pointnet_util.py:134): x (groups, nsample, c) -> y (groups, c). */
 int ancsh_group_max(long groups, int nsample, int c, const float *x, float *y, void *stream);

@@ -2,7 +2,11 @@
 fit + record D2H per batch) against load_inputs + step() on the same clouds, at configs[2]'s shape (K = 3, 32 x 1024, 10000 / 200
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
-    python tools/stream_bench.py [--passes 5] [--slots 20]
+    python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K]
+
+--arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
+--overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
+line then also carries the rerun count, the latency of the batches that reran and the device memory the streaming pipeline holds.
 """
 import argparse
 import json
@@ -26,7 +30,13 @@ def main():
     ap.add_argument("--passes", type=int, default=5, help="timed passes over the 640 clouds (20 batches each)")
     ap.add_argument("--slots", type=int, default=20)
     ap.add_argument("--clouds", type=int, default=640)
+    ap.add_argument("--arithmetic", choices=("f32", "f16x2"), default=None)
+    ap.add_argument("--range-guard", action="store_true")
+    ap.add_argument("--overflow-every", type=int, default=0)
     args = ap.parse_args()
+    if args.range_guard and args.arithmetic != "f16x2":
+        ap.error("--range-guard needs --arithmetic f16x2")
+    extra = args.arithmetic is not None
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
     sizes = rs.randint(700, 3001, args.clouds)
@@ -35,10 +45,18 @@ def main():
         c = make_cloud(i, N=int(n), K=K)
         raw.append(np.concatenate([c["P"], c["cls_gt"][:, None].astype(np.float32)], 1))
     batches = [(raw[i:i + B], np.ones(B, np.float32)) for i in range(0, len(raw) - B + 1, B)]
+    if args.overflow_every:
+        for k in range(0, len(batches), args.overflow_every):
+            batches[k][1][k % B] = 1.0e6
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
 
     # streaming
-    pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000).prepare()
+    torch.cuda.synchronize()
+    mem0 = torch.cuda.mem_get_info(dev)[0]
+    pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
+                         range_guard=args.range_guard).prepare()
+    torch.cuda.synchronize()
+    pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
         pass
     torch.cuda.synchronize()
@@ -50,12 +68,17 @@ def main():
             t_sub[it[2]] = time.perf_counter()
             yield it
     t0 = time.perf_counter()
-    n_out = 0
+    n_out, rerun_lat = 0, []
+    reruns0 = pipe.f32_reruns
     for tag, seed, rec in pipe.stream_batches(timed(work)):
         lat.append(time.perf_counter() - t_sub[tag])
+        if pipe.f32_reruns != reruns0:
+            rerun_lat.append(lat[-1])
+            reruns0 = pipe.f32_reruns
         n_out += rec.shape[0]
     torch.cuda.synchronize()
     t_stream = time.perf_counter() - t0
+    pipe_reruns, pipe_paired = pipe.f32_reruns, pipe.paired is not None
     del pipe
     torch.cuda.synchronize()
 
@@ -64,7 +87,7 @@ def main():
     for k, (c, nf) in enumerate(batches):
         s = sample_raw_batch(c, N, nf, k, dev)
         pre.append((s["P"].cpu().numpy(), s["joint_cls"].cpu().numpy()))
-    base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots)
+    base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, arithmetic=args.arithmetic)
     base.load_inputs(*pre[0])
     base.prepare()
 
@@ -95,6 +118,11 @@ def main():
             "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "couple": True,
                       "distinct_clouds": len(batches) * B, "timed_batches": args.passes * len(batches)},
             "baseline": "load_inputs (pageable, synchronous) + step(), the slot's previous record read back before its next batch"}
+    if extra:
+        line.update({"arithmetic": args.arithmetic, "range_guard": args.range_guard, "overflow_every": args.overflow_every,
+                     "f32_reruns": pipe_reruns, "paired": pipe_paired, "stream_device_bytes": int(pipe_bytes),
+                     "rerun_batch_latency_ms": [round(1e3 * x, 2) for x in rerun_lat[:8]],
+                     "batch_latency_ms_median": round(1e3 * float(np.median(lat)), 2)})
     print(json.dumps(line))
 
 
