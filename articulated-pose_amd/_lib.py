@@ -97,6 +97,12 @@ SIGNATURES = {
     "ancsh_ransac_joint_rec_dseed": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
                                     + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp],
     "ancsh_input_sample_stream": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp],
+    # the key block (ancsh_stream_key: seed, cloud_base) in place of the bare device seed: keys that follow a cloud's global index
+    "ancsh_input_sample_stream_keyed": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp],
+    "ancsh_ransac_single_rec_dkey": [_c_int, _vp, _vp, _vp, _c_float, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long,
+                                     _vp, _c_int, _vp, _c_float, _vp],
+    "ancsh_ransac_joint_rec_dkey": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
+                                   + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

@@ -75,7 +75,10 @@ __device__ __forceinline__ unsigned long long feistel_index(unsigned long long i
     return x;
 }
 
-// one thread per sampled row; the gathered source row (16 B for nchan = 4) of a cloud of a few thousand rows is L2-resident
+// one thread per sampled row; the gathered source row (16 B for nchan = 4) of a cloud of a few thousand rows is L2-resident.
+// KEYED: `seed` is the address of an ancsh_stream_key (its seed first) and the round keys use the global cloud index cloud_base + b;
+// unkeyed, the base is a constant 0 and the code is that of the plain entry.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void input_sample_stream_kernel(int num_points, int nchan, const float *__restrict__ rows,
                                                                   long capacity, const int *__restrict__ offsets,
                                                                   const float *__restrict__ norm_factor, int jcls_col,
@@ -91,9 +94,10 @@ __global__ __launch_bounds__(256) void input_sample_stream_kernel(int num_points
     int w = 0;
     while ((1ull << w) < T) w += 2;
     const unsigned long long s = *seed;
+    const int cb = KEYED ? b + ((const ancsh_stream_key *)seed)->cloud_base : b;
     unsigned long long key[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) key[r] = splitmix64(s ^ splitmix64(SAMPLE_TAG | ((unsigned long long)b << 8) | (unsigned)r));
+    for (int r = 0; r < 4; ++r) key[r] = splitmix64(s ^ splitmix64(SAMPLE_TAG | ((unsigned long long)cb << 8) | (unsigned)r));
     const unsigned long long t = feistel_index((unsigned long long)i, T, w / 2, key);
     const float *src = rows + (size_t)(r0 + (long)(t % n_raw)) * nchan;
     const float nf = norm_factor[b];
@@ -141,7 +145,25 @@ extern "C" int ancsh_input_sample_stream(int nclouds, int num_points, int nchan,
     ANCSH_REQUIRE(seed, "input_sample_stream: null seed pointer");
     ANCSH_REQUIRE(rows && offsets && norm_factor && P && joint_cls, "input_sample_stream: null pointer");
     if (nclouds == 0) return ANCSH_OK;
-    hipLaunchKernelGGL(input_sample_stream_kernel, dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream, num_points,
+    hipLaunchKernelGGL(input_sample_stream_kernel<false>, dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream, num_points,
                        nchan, rows, capacity, offsets, norm_factor, jcls_col, seed, P, joint_cls, perm_out);
     return check_launch("input_sample_stream");
+}
+
+extern "C" int ancsh_input_sample_stream_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity,
+                                               const int *offsets, const float *norm_factor, int jcls_col, const ancsh_stream_key *key,
+                                               float *P, int *joint_cls, int *perm_out, void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0 && num_points > 0 && num_points < (1 << 30), "input_sample_stream_keyed: bad shape nclouds=%d num_points=%d",
+                  nclouds, num_points);
+    ANCSH_REQUIRE(nchan >= 4, "input_sample_stream_keyed: rows need x y z and the joint-class channel (nchan=%d < 4)", nchan);
+    ANCSH_REQUIRE(jcls_col >= 3 && jcls_col < nchan, "input_sample_stream_keyed: jcls_col=%d must name a channel in [3,%d)", jcls_col,
+                  nchan);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "input_sample_stream_keyed: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(nclouds <= 65535, "input_sample_stream_keyed: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(key, "input_sample_stream_keyed: null key pointer");
+    ANCSH_REQUIRE(rows && offsets && norm_factor && P && joint_cls, "input_sample_stream_keyed: null pointer");
+    if (nclouds == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(input_sample_stream_kernel<true>, dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream,
+                       num_points, nchan, rows, capacity, offsets, norm_factor, jcls_col, &key->seed, P, joint_cls, perm_out);
+    return check_launch("input_sample_stream_keyed");
 }

@@ -41,13 +41,37 @@ __device__ __forceinline__ int device_draw(unsigned long long seed, int prob, in
     const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)prob << 40) ^ ((unsigned long long)iter << 8) ^ (unsigned)k));
     return (int)(h % (unsigned long long)n);
 }
-// The generator key of a sampling kernel.  DSEED = false (the by-value entries): `arg` is the key itself.  DSEED = true (the
-// *_dseed entries): `arg` is the address of a uint64 in device memory, read here once per kernel -- a captured graph then replays
-// with whatever the host last wrote there -- plus `add` (1 in the stage-B kernels: the by-value caller passes seed + 1 itself).
-template <bool DSEED>
+// The generator key of a sampling kernel, by key mode KM:
+//   KEY_VALUE (the by-value entries): `arg` is the key itself;
+//   KEY_DSEED (the *_dseed entries): `arg` is the address of a uint64 in device memory, read here once per kernel -- a captured graph
+//             then replays with whatever the host last wrote there -- plus `add` (1 in the stage-B kernels: the by-value caller passes
+//             seed + 1 itself);
+//   KEY_DKEY  (the *_dkey entries): `arg` is a DKey: the address of an ancsh_stream_key, whose seed is read as KEY_DSEED reads its
+//             uint64, and the problems per cloud (K in stage A, K - 1 in stage B).  The generator's problem index is shifted by
+//             key.cloud_base * parts (key_problem_base), so a cloud draws the samples of its GLOBAL index whichever launch serves it;
+//             `prob` itself -- offsets, draws, scores, scratch, the record -- stays local.
+// The two older modes keep their kernel argument (one uint64) and a problem base of constant 0: their code is unchanged.
+enum { KEY_VALUE = 0, KEY_DSEED = 1, KEY_DKEY = 2 };
+struct DKey {
+    const ancsh_stream_key *key;
+    int parts;
+};
+template <int KM> struct KeyArgT { typedef unsigned long long type; };
+template <> struct KeyArgT<KEY_DKEY> { typedef DKey type; };
+template <int KM> using KeyArg = typename KeyArgT<KM>::type;
+
+template <int KM>
 __device__ __forceinline__ unsigned long long kernel_seed(unsigned long long arg, unsigned add) {
-    return DSEED ? *(const unsigned long long *__restrict__)arg + add : arg;
+    return KM != KEY_VALUE ? *(const unsigned long long *__restrict__)arg + add : arg;      // an ancsh_stream_key starts with its seed
 }
+template <int KM>
+__device__ __forceinline__ unsigned long long kernel_seed(DKey arg, unsigned add) {
+    return arg.key->seed + add;
+}
+template <int KM>
+__device__ __forceinline__ int key_problem_base(unsigned long long) { return 0; }
+template <int KM>
+__device__ __forceinline__ int key_problem_base(DKey arg) { return arg.key->cloud_base * arg.parts; }
 
 // ---- block reductions (256 threads = 4 waves) -----------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
@@ -204,11 +228,11 @@ __device__ __forceinline__ void inlier2_count_f32(const float R[9], float sc, co
     cnt = cnt + one;
 }
 
-__device__ __forceinline__ void load_draw3(const int *draws, unsigned long long seed, int prob, int niter, int h, int k0,
+__device__ __forceinline__ void load_draw3(const int *draws, unsigned long long seed, int prob, int kbase, int niter, int h, int k0,
                                            int stride, int n, int idx[3]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        int v = draws ? draws[((size_t)prob * niter + h) * stride + k0 + k] : device_draw(seed, prob, h, k0 + k, n);
+        int v = draws ? draws[((size_t)prob * niter + h) * stride + k0 + k] : device_draw(seed, prob + kbase, h, k0 + k, n);
         idx[k] = v < 0 ? 0 : (v >= n ? n - 1 : v);
     }
 }
@@ -219,12 +243,13 @@ __device__ __forceinline__ void load_draw3(const int *draws, unsigned long long 
 #endif
 constexpr int A_CHUNK = A_CHUNK_N;   // points staged per LDS pass (24 B each)
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(256) void ransac_single_score_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                   const float *__restrict__ tgt, float th, int niter,
-                                                                  const int *__restrict__ draws, unsigned long long seed_arg,
+                                                                  const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                   int *__restrict__ scores) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 0);
+    const int kbase = key_problem_base<KM>(seed_arg);
     // structure-of-arrays tile so that ds_read_b128 hands each lane 4 consecutive points per coordinate and the residual
     // arithmetic runs on packed-f32 (v_pk_mul/fma/add_f32: two points per lane per instruction)
     __shared__ __attribute__((aligned(16))) float pl[6][A_CHUNK];
@@ -234,7 +259,7 @@ __global__ __launch_bounds__(256) void ransac_single_score_kernel(const int *__r
     float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, sc = 0.f, tr[3] = {0, 0, 0};
     if (live) {
         int id[3];
-        load_draw3(draws, seed, prob, niter, h, 0, 3, n, id);
+        load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, id);
         float s3[3][3], t3[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -321,19 +346,20 @@ __global__ __launch_bounds__(256) void soa_quads_kernel(const int *__restrict__ 
 #else
 #define POSE_SCORE_ATTR
 #endif
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(256) POSE_SCORE_ATTR void ransac_single_score_sreg_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                        const float *__restrict__ tgt, const float *__restrict__ quads,
                                                                        int cap_quads, float th, int niter, const int *__restrict__ draws,
-                                                                       unsigned long long seed_arg, int *__restrict__ scores) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
+                                                                       KeyArg<KM> seed_arg, int *__restrict__ scores) {
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 0);
+    const int kbase = key_problem_base<KM>(seed_arg);
     const int prob = blockIdx.y, h = blockIdx.x * 256 + threadIdx.x;
     const int r0 = off[prob], n = off[prob + 1] - r0;
     // lanes without a hypothesis (past niter) score the identity model and drop the result: no divergence inside the point loop
     float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, sc = 0.f, tr[3] = {0, 0, 0};
     if (h < niter && n > 0) {
         int id[3];
-        load_draw3(draws, seed, prob, niter, h, 0, 3, n, id);
+        load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, id);
         float s3[3][3], t3[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -507,15 +533,16 @@ __device__ __forceinline__ int compact_flagged(bool flag, int i, int n, const fl
     return base + total;
 }
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                                    const float *__restrict__ tgt, float th, int niter,
-                                                                   const int *__restrict__ draws, unsigned long long seed_arg,
+                                                                   const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                    const int *__restrict__ scores, int max_n,
                                                                    double *__restrict__ out_model,
                                                                    unsigned char *__restrict__ out_inliers,
                                                                    int *__restrict__ out_best, FitExtras E) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 0);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 0);
+    const int kbase = key_problem_base<KM>(seed_arg);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *red = (double *)smem;                       // 64 doubles
     int *wcnt = (int *)(red + 64);                      // 4 ints for compact_flagged + 4 for the tie counts
@@ -536,7 +563,7 @@ __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__
     const int best = block_argmax_first<int>(scores + (size_t)prob * niter, niter, &best_score, red);
     // re-derive the winning hypothesis (same device function => same bits as when it was scored)
     int id[3];
-    load_draw3(draws, seed, prob, niter, best, 0, 3, n, id);
+    load_draw3(draws, seed, prob, kbase, niter, best, 0, 3, n, id);
     float s3[3][3], t3[3][3], R[9], sc, tr[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -572,7 +599,7 @@ __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__
         for (int h = threadIdx.x; h < niter; h += 256) {
             if (sp[h] >= best_score - 1) {
                 int d3[3];
-                load_draw3(draws, seed, prob, niter, h, 0, 3, n, d3);
+                load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, d3);
                 if (d3[0] == d3[1] || d3[0] == d3[2] || d3[1] == d3[2]) {
                     const int slot = atomicAdd(&s_cand[TIE_MAX_CAND], 1);
                     if (slot < TIE_MAX_CAND) s_cand[slot] = h;
@@ -587,7 +614,7 @@ __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__
             const int h = s_cand[c];
             if (h == best) { ++n_near; winner_degenerate = true; continue; }
             int d3[3];
-            load_draw3(draws, seed, prob, niter, h, 0, 3, n, d3);
+            load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, d3);
             float hs[3][3], ht[3][3], hR[9], hsc, htr[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -849,11 +876,11 @@ struct HypSamples {
     float s0[3][3], t0[3][3], s1[3][3], t1[3][3];
 };
 __device__ __forceinline__ void load_hyp_samples(const float *__restrict__ src, const float *__restrict__ tgt, const int *draws,
-                                                 unsigned long long seed, int prob, int niter, int h, int a0, int n0, int a1,
+                                                 unsigned long long seed, int prob, int kbase, int niter, int h, int a0, int n0, int a1,
                                                  int n1, HypSamples &q) {
     int i0[3], i1[3];
-    load_draw3(draws, seed, prob, niter, h, 0, 6, n0, i0);
-    load_draw3(draws, seed, prob, niter, h, 3, 6, n1, i1);
+    load_draw3(draws, seed, prob, kbase, niter, h, 0, 6, n0, i0);
+    load_draw3(draws, seed, prob, kbase, niter, h, 3, 6, n1, i1);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -865,12 +892,13 @@ __device__ __forceinline__ void load_hyp_samples(const float *__restrict__ src, 
         }
 }
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(64) void ransac_joint_init_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                const float *__restrict__ src, const float *__restrict__ tgt,
-                                                               int niter, const int *__restrict__ draws, unsigned long long seed_arg,
+                                                               int niter, const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                double *__restrict__ scores, double *__restrict__ models) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
+    const int kbase = key_problem_base<KM>(seed_arg);
     const int prob = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -882,7 +910,7 @@ __global__ __launch_bounds__(64) void ransac_joint_init_kernel(const int *__rest
         return;
     }
     HypSamples q;
-    load_hyp_samples(src, tgt, draws, seed, prob, niter, h, a0, n0, a1, n1, q);
+    load_hyp_samples(src, tgt, draws, seed, prob, kbase, niter, h, a0, n0, a1, n1, q);
     float sc0, sc0i, sc1, sc1i;
     scales3(q.s0, q.t0, sc0, sc0i);
     scales3(q.s1, q.t1, sc1, sc1i);
@@ -899,13 +927,14 @@ constexpr int HYP_CHUNK_SMALL = 64;   // ... of a launch too small to fill the c
 constexpr long HYP_SMALL_LAUNCH = 8192;   // fits per launch up to which the small chunk is used
 constexpr int HYP_REFILL = 16;    // idle lanes that trigger a refill (a refill costs the whole wave ~1 trip of latency)
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                              const float *__restrict__ src, const float *__restrict__ tgt,
                                                              const float *__restrict__ joint_dir, int niter,
-                                                             const int *__restrict__ draws, unsigned long long seed_arg,
+                                                             const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                              double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
+    const int kbase = key_problem_base<KM>(seed_arg);
     const int prob = blockIdx.y;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -928,7 +957,7 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restri
                     h = mine;
                     const double *mo = models + ((size_t)prob * niter + h) * MODEL_B;
                     HypSamples q;
-                    load_hyp_samples(src, tgt, draws, seed, prob, niter, h, a0, n0, a1, n1, q);
+                    load_hyp_samples(src, tgt, draws, seed, prob, kbase, niter, h, a0, n0, a1, n1, q);
                     center_part3(q.s0, q.t0, (float)mo[6], P.x0, P.y0);
                     center_part3(q.s1, q.t1, (float)mo[7], P.x1, P.y1);
 #pragma unroll
@@ -1102,13 +1131,14 @@ struct HypProblemCoop {
     }
 };
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                   const float *__restrict__ src, const float *__restrict__ tgt,
                                                                   const float *__restrict__ joint_dir, int niter,
-                                                                  const int *__restrict__ draws, unsigned long long seed_arg,
+                                                                  const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                   double *__restrict__ models, int *__restrict__ lm_stat) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
+    const int kbase = key_problem_base<KM>(seed_arg);
     __shared__ double xch[64 / COOP_G][COOP_XCH];
     const int prob = blockIdx.y, lane = threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
@@ -1136,7 +1166,7 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__r
                     h = mine;
                     const double *mo = models + ((size_t)prob * niter + h) * MODEL_B;
                     HypSamples q;
-                    load_hyp_samples(src, tgt, draws, seed, prob, niter, h, a0, n0, a1, n1, q);
+                    load_hyp_samples(src, tgt, draws, seed, prob, kbase, niter, h, a0, n0, a1, n1, q);
                     center_part3(q.s0, q.t0, (float)mo[6], P.x0, P.y0);
                     center_part3(q.s1, q.t1, (float)mo[7], P.x1, P.y1);
 #pragma unroll
@@ -1161,19 +1191,20 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__r
     }
 }
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(64) void ransac_joint_model_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                 const float *__restrict__ src, const float *__restrict__ tgt,
-                                                                int niter, const int *__restrict__ draws, unsigned long long seed_arg,
+                                                                int niter, const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                 double *__restrict__ models) {
-    const unsigned long long seed = kernel_seed<DSEED>(seed_arg, 1);
+    const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
+    const int kbase = key_problem_base<KM>(seed_arg);
     const int prob = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
     if (h >= niter || n0 <= 0 || n1 <= 0) return;
     double *mo = models + ((size_t)prob * niter + h) * MODEL_B;
     HypSamples q;
-    load_hyp_samples(src, tgt, draws, seed, prob, niter, h, a0, n0, a1, n1, q);
+    load_hyp_samples(src, tgt, draws, seed, prob, kbase, niter, h, a0, n0, a1, n1, q);
     double x[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) x[i] = mo[i];
@@ -1320,7 +1351,7 @@ __device__ __forceinline__ void block_prep_part(float (*cs)[3], float (*ct)[3], 
     quat_to_rotvec(q, rv);
 }
 
-template <bool DSEED>
+template <int KM>
 __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
                                                                   const float *__restrict__ src, const float *__restrict__ tgt,
                                                                   const float *__restrict__ joint_dir, double th, int niter,
@@ -1395,15 +1426,17 @@ __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__r
         m1 = compact_flagged(f, i, n1, src, tgt, (size_t)a1, c1s, c1t, m1, wcnt);
     }
     if (E.tie) {                                       // block-uniform; one inlier of either part moves the joint score by 1/6 (:192)
-        const unsigned long long tseed = kernel_seed<DSEED>(E.seed, 1);
+        const unsigned long long tseed = kernel_seed<KM>(E.seed, 1);
+        // KEY_DKEY: E.seed holds the ancsh_stream_key's address and E.K the parts per cloud (the entry checks K >= 2)
+        const int tbase = KM == KEY_DKEY ? ((const ancsh_stream_key *)E.seed)->cloud_base * (E.K - 1) : 0;
         const double *sp = scores + (size_t)prob * niter;
         const double near = best_score - (1.0 / 6.0 + 1e-9);
         for (int h = threadIdx.x; h < niter + 255 - (niter + 255) % 256; h += 256) {
             bool degenerate = false;
             if (h < niter && sp[h] >= near) {
                 int i0[3], i1[3];
-                load_draw3(E.draws, tseed, prob, niter, h, 0, 6, n0, i0);
-                load_draw3(E.draws, tseed, prob, niter, h, 3, 6, n1, i1);
+                load_draw3(E.draws, tseed, prob, tbase, niter, h, 0, 6, n0, i0);
+                load_draw3(E.draws, tseed, prob, tbase, niter, h, 3, 6, n1, i1);
                 degenerate = i0[0] == i0[1] || i0[0] == i0[2] || i0[1] == i0[2] || i1[0] == i1[1] || i1[0] == i1[2] || i1[1] == i1[2];
             }
             n_near += __popcll(__ballot(degenerate));
@@ -1941,9 +1974,9 @@ extern "C" long ancsh_ransac_single_quads_floats(long rows, int nprob) {
     return 24 * single_quads_needed(rows, nprob);
 }
 
-template <bool DSEED>
+template <int KM>
 static int ransac_single_impl(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                              const int *draws, unsigned long long seed, int max_n, double *out_model,
+                              const int *draws, KeyArg<KM> seed, int max_n, double *out_model,
                               unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
                               FitExtras E, void *stream) {
     ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_single: bad sizes nprob=%d niter=%d max_n=%d", nprob, niter, max_n);
@@ -1961,15 +1994,15 @@ static int ransac_single_impl(int nprob, const int *off, const float *src, const
         ANCSH_REQUIRE((((uintptr_t)scratch_quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
         const int cap = (int)single_quads_needed(rows, nprob);
         hipLaunchKernelGGL(soa_quads_kernel, dim3((max_n + 7 + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, scratch_quads, cap);
-        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<DSEED>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
+        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
                            (const float *)scratch_quads, cap, inlier_th, niter, draws, seed, scratch_scores);
     } else {
-        hipLaunchKernelGGL(ransac_single_score_kernel<DSEED>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, inlier_th,
+        hipLaunchKernelGGL(ransac_single_score_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, inlier_th,
                            niter, draws, seed, scratch_scores);
     }
     const size_t lds = 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel<DSEED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_single_finish_kernel<DSEED>, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ransac_single_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
                        scratch_scores, max_n, out_model, out_inliers, out_best, E);
     return check_launch("ransac_single");
 }
@@ -1977,7 +2010,7 @@ static int ransac_single_impl(int nprob, const int *off, const float *src, const
 extern "C" int ancsh_ransac_single(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
                                    const int *draws, unsigned long long seed, int max_n, double *out_model,
                                    unsigned char *out_inliers, int *out_best, int *scratch_scores, void *stream) {
-    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
                                      scratch_scores, nullptr, 0, no_extras(), stream);
 }
 
@@ -1989,7 +2022,7 @@ extern "C" int ancsh_ransac_single_ex(int nprob, const int *off, const float *sr
                                       unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
                                       long rows, void *stream) {
     ANCSH_REQUIRE(scratch_quads, "ransac_single_ex: scratch_quads is NULL (ancsh_ransac_single is the call without it)");
-    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
                                      scratch_scores, scratch_quads, rows, no_extras(), stream);
 }
 
@@ -2001,14 +2034,14 @@ extern "C" int ancsh_ransac_single_rec(int nprob, const int *off, const float *s
                                        long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_single_rec", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl<false>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
                                      scratch_scores, scratch_quads, rows, E, stream);
 }
 
-template <bool DSEED>
+template <int KM>
 static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
                              const float *joint_dir, double inlier_th, int niter, const int *draws,
-                             unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+                             KeyArg<KM> seed, int max_n, double *out_model, unsigned char *out_inliers,
                              int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
                              int *lm_stat, int lm_schedule, FitExtras E, void *stream) {
     ANCSH_REQUIRE(lm_schedule >= ANCSH_LM_AUTO && lm_schedule <= ANCSH_LM_LATENCY, "ransac_joint: unknown lm_schedule %d", lm_schedule);
@@ -2021,7 +2054,7 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
     ANCSH_REQUIRE(inlier_th > 0.0, "ransac_joint: inlier_th must be positive");
     inlier_th = sq_threshold_f64(inlier_th);      // the kernels compare squared residuals
     const dim3 per_hyp((niter + 63) / 64, nprob);
-    hipLaunchKernelGGL(ransac_joint_init_kernel<DSEED>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
+    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
                        scratch_models);
     // Two schedules of the same fits (identical MINPACK state machine, results equal to ~1e-7, not to the last bit: the eight-lane
     // callbacks are a different instruction stream and the f64 code is compiled with contraction on):
@@ -2032,19 +2065,19 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
     //     (measured on 64 x 200 fits: 1.27 vs 1.6 ms; the tail is MINPACK's serial lmpar on rank-deficient samples, which no lane
     //     split shortens) at ~5 % lower pipeline throughput.
     if (lm_schedule == ANCSH_LM_LATENCY) {
-        hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<DSEED>, dim3((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob), dim3(64), 0, st,
+        hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<KM>, dim3((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob), dim3(64), 0, st,
                            rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
     } else {
         const int chunk = (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK;
-        hipLaunchKernelGGL(ransac_joint_lm_kernel<DSEED>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
+        hipLaunchKernelGGL(ransac_joint_lm_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
                            joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
     }
-    hipLaunchKernelGGL(ransac_joint_model_kernel<DSEED>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
+    hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
     hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, inlier_th,
                        niter, scratch_models, scratch_scores);
     const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<DSEED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_joint_finish_kernel<DSEED>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ransac_joint_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
                        niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
     return check_launch("ransac_joint");
 }
@@ -2054,7 +2087,7 @@ extern "C" int ancsh_ransac_joint(int nprob, const int *rng0, const int *rng1, c
                                   unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
                                   int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
                                   int *lm_stat, void *stream) {
-    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
                                     out_best, out_score, scratch_scores, scratch_models, lm_stat, ANCSH_LM_AUTO, no_extras(), stream);
 }
 
@@ -2063,7 +2096,7 @@ extern "C" int ancsh_ransac_joint_ex(int nprob, const int *rng0, const int *rng1
                                      unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
                                      int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
                                      int *lm_stat, int lm_schedule, void *stream) {
-    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
                                     out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, no_extras(), stream);
 }
 
@@ -2076,12 +2109,12 @@ extern "C" int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_joint_rec", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
     E.draws = draws; E.seed = seed;
-    return ransac_joint_impl<false>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
                                     out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
 }
 
 // ancsh_ransac_single_rec / ancsh_ransac_joint_rec with the generator key read from device memory (include/ancsh_hip.h): the kernels
-// are the by-value ones instantiated with DSEED = true, the key travels as the address in the same 64-bit argument
+// are the by-value ones instantiated with KEY_DSEED, the key travels as the address in the same 64-bit argument
 extern "C" int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
                                              const int *draws, const unsigned long long *seed, int max_n, double *out_model,
                                              unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
@@ -2089,7 +2122,7 @@ extern "C" int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const fl
     ANCSH_REQUIRE(seed, "ransac_single_rec_dseed: null seed pointer");
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_single_rec_dseed", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl<true>(nprob, off, src, tgt, inlier_th, niter, draws, (unsigned long long)(uintptr_t)seed, max_n, out_model,
+    return ransac_single_impl<KEY_DSEED>(nprob, off, src, tgt, inlier_th, niter, draws, (unsigned long long)(uintptr_t)seed, max_n, out_model,
                                     out_inliers, out_best, scratch_scores, scratch_quads, rows, E, stream);
 }
 
@@ -2103,8 +2136,42 @@ extern "C" int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const in
     FitExtras E = no_extras();
     if (int rc = make_extras("ransac_joint_rec_dseed", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
     E.draws = draws; E.seed = (unsigned long long)(uintptr_t)seed;
-    return ransac_joint_impl<true>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
+    return ransac_joint_impl<KEY_DSEED>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
                                    out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
+}
+
+// ... with the key block of include/ancsh_hip.h (ancsh_stream_key): the KEY_DKEY instantiations, whose generator problem index is
+// prob + key->cloud_base * K (stage A) / prob + key->cloud_base * (K - 1) (stage B).  K is required here even without a record: it is
+// the problem count of one cloud.  cloud_base lives in device memory, so (cloud_base + B) * K < 2^20 -- which keeps the draw keys clear
+// of the sampler's tag bits -- is the caller's to check where it writes the block (AncshPipeline.submit, dataset.check_stream_key).
+extern "C" int ancsh_ransac_single_rec_dkey(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+                                            const int *draws, const ancsh_stream_key *key, int max_n, double *out_model,
+                                            unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
+                                            long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
+    ANCSH_REQUIRE(key, "ransac_single_rec_dkey: null key pointer");
+    ANCSH_REQUIRE(K >= 1 && nprob >= 0 && nprob % K == 0 && nprob < (1 << 20),
+                  "ransac_single_rec_dkey: nprob (%d) must be a multiple of K (%d) below 2^20", nprob, K);
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_single_rec_dkey", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
+    return ransac_single_impl<KEY_DKEY>(nprob, off, src, tgt, inlier_th, niter, draws, DKey{key, K}, max_n, out_model, out_inliers,
+                                        out_best, scratch_scores, scratch_quads, rows, E, stream);
+}
+
+extern "C" int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                           const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                           const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers,
+                                           int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
+                                           int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
+                                           void *stream) {
+    ANCSH_REQUIRE(key, "ransac_joint_rec_dkey: null key pointer");
+    ANCSH_REQUIRE(K >= 2 && nprob >= 0 && nprob % (K - 1) == 0 && nprob < (1 << 20),
+                  "ransac_joint_rec_dkey: nprob (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", nprob, K);
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_joint_rec_dkey", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
+    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)key;
+    return ransac_joint_impl<KEY_DKEY>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, DKey{key, K - 1}, max_n,
+                                       out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
+                                       E, stream);
 }
 
 extern "C" int ancsh_umeyama(int nprob, const int *off, const float *src, const float *tgt, double *out, void *stream) {

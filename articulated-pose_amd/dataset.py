@@ -120,10 +120,31 @@ def seed_bits(seed):
     return int(np.uint64(int(seed) % (1 << 64)).view(np.int64))
 
 
-def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", return_perm=False):
+STREAM_KEY_PROBLEMS = 1 << 20       # (cloud_base + clouds) * K must stay below: the draw keys then keep clear of the sampler's tag bits
+
+
+def check_stream_key(cloud_base, n_clouds, K):
+    """Host-side bound of a key block (include/ancsh_hip.h, ancsh_stream_key): cloud_base >= 0 and (cloud_base + n_clouds) * K < 2^20,
+    so no generator problem index of the launch reaches the sampler's tag bits.  -> int(cloud_base); ValueError otherwise."""
+    cb = int(cloud_base)
+    if cb < 0 or (cb + int(n_clouds)) * max(1, int(K)) >= STREAM_KEY_PROBLEMS:
+        raise ValueError("cloud_base %d with %d clouds of %d parts: (cloud_base + clouds) * K must be in [0, 2^20)" % (cb, n_clouds, K))
+    return cb
+
+
+def stream_key_words(seed, cloud_base=0):
+    """The 16-byte ancsh_stream_key {uint64 seed, int32 cloud_base, int32 reserved = 0} as four int32 words (how the device holds it)."""
+    w = np.zeros(4, np.int32)
+    w[:2].view(np.int64)[0] = seed_bits(seed)
+    w[2] = int(cloud_base)
+    return w
+
+
+def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", return_perm=False, cloud_base=None):
     """Eager wrapper of the streaming sampler (ancsh_input_sample_stream, include/ancsh_hip.h): clouds = list of (n_raw, 4) float32
     arrays [x y z joint_cls]; cloud b's num_points rows are raw rows pi_b(i) % n_raw for the keyed bijection pi_b of the tiled cloud
-    (the reference's tiling rule, tiled_size) drawn from `seed` (uint64).
+    (the reference's tiling rule, tiled_size) drawn from `seed` (uint64).  cloud_base: None = the plain entry; an int = the key block
+    (ancsh_input_sample_stream_keyed): cloud b is keyed as global cloud cloud_base + b.
     -> dict(P (B,N,3) float32 = xyz * norm_factor, joint_cls (B,N) int32 [, perm (B,N) int32 = pi_b(i)]) on `device`."""
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -135,11 +156,15 @@ def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", re
     rows = torch.from_numpy(np.concatenate(clouds, axis=0)).to(dev)
     off = torch.from_numpy(offsets).to(dev)
     nf_d = torch.from_numpy(nf).to(dev)
-    seed_d = torch.tensor([seed_bits(seed)], dtype=torch.int64, device=dev)
+    if cloud_base is None:
+        entry, seed_d = "ancsh_input_sample_stream", torch.tensor([seed_bits(seed)], dtype=torch.int64, device=dev)
+    else:
+        entry = "ancsh_input_sample_stream_keyed"
+        seed_d = torch.from_numpy(stream_key_words(seed, check_stream_key(cloud_base, B, 1))).to(dev)
     P = torch.empty((B, num_points, 3), dtype=torch.float32, device=dev)
     jcls = torch.empty((B, num_points), dtype=torch.int32, device=dev)
     perm = torch.empty((B, num_points), dtype=torch.int32, device=dev) if return_perm else None
-    _lib.call("ancsh_input_sample_stream", B, int(num_points), RAW_NCHAN, _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(off),
+    _lib.call(entry, B, int(num_points), RAW_NCHAN, _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(off),
               _lib.ptr(nf_d), RAW_JCLS_COL, _lib.ptr(seed_d), _lib.ptr(P), _lib.ptr(jcls), _lib.ptr(perm))
     out = dict(P=P, joint_cls=jcls)
     if return_perm:

@@ -4,11 +4,13 @@ collective, and ONE gather (RCCL over xGMI; backend "nccl" on ROCm) of fixed-siz
 records closes the batch.  The reference has no distributed code at all: its only parallelism is
 multiprocessing.Process over contiguous slices (evaluation/pose_multi_process.py:53-67), whose
 partition rule is kept here."""
+import collections
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -297,10 +299,15 @@ class ShardedPipeline(object):
 
     Without an initialised process group (or world 1) it is a plain AncshPipeline whose records() are the local ones.
     `pipeline_factory(num_parts, weights_ancsh, weights_npcs, n_local, num_points, device, slots=..., **kw)` builds the per-rank
-    pipeline (default AncshPipeline; the gloo CPU tests inject a stand-in with the same step()/slot interface)."""
+    pipeline (default AncshPipeline; the gloo CPU tests inject a stand-in with the same step()/slot interface).
+
+    raw_capacity (rows PER RANK): the streaming entry -- submit() / retire() / stream_batches() of raw clouds, every rank iterating the
+    same global batches.  The per-rank pipeline is then built with raw_capacity and keyed=True, and each rank submits its shard with
+    cloud_base = lo, so a cloud is sampled and fitted as its global index whatever the world size (include/ancsh_hip.h,
+    ancsh_stream_key); its records are gathered on `dst` over the gloo control group (the default group init_groups creates)."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
-                 slots=1, pipeline_factory=None, gather_single=False, **pipeline_kw):
+                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, **pipeline_kw):
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size() if self.distributed else 1
         self.rank = dist.get_rank() if self.distributed else 0
@@ -312,6 +319,13 @@ class ShardedPipeline(object):
         self.ragged = global_batch % self.world != 0
         if pipeline_factory is None:
             from .pipeline import AncshPipeline as pipeline_factory
+        self.raw_capacity = None if raw_capacity is None else int(raw_capacity)
+        if self.raw_capacity is not None:
+            pipeline_kw.update(raw_capacity=self.raw_capacity, keyed=True)
+            if self.world > 1 and "gloo" not in str(dist.get_backend()):
+                raise ValueError("stream_batches gathers host records over the default process group, which must be gloo (dist.init_groups "
+                                 "creates it); got %r" % dist.get_backend())
+        self.seed = int(pipeline_kw.get("seed", 0))      # batch k of a stream: seed + 2k on every rank (AncshPipeline's default is 0)
         self.pipe = pipeline_factory(num_parts, weights_ancsh, weights_npcs, self.n_local, num_points, device, slots=slots, **pipeline_kw)
         self.gatherer = RecordGatherer((self.n_max, num_parts, 26), torch.float64, device, dst, data_group) \
             if self.world > 1 or (gather_single and self.distributed) else None      # gather_single: run the collective even with one rank
@@ -319,6 +333,9 @@ class ShardedPipeline(object):
         # flight, so a slot's record is gathered right before the slot is reused (its batch finished long ago); flush() drains
         self.lagged = self.gatherer is not None and self.gatherer.host_staged
         self._pending, self._pad = [], {}
+        self._stream = collections.deque()       # streaming: (tag, seed, n_valid, submitted here) of unretired global batches, oldest first
+        self._stream_submitted = 0
+        self._stream_bufs = None
 
     # ---- inputs -------------------------------------------------------------------------------------------------------------
     def load_inputs(self, P, joint_cls, pred=None, slot=None, is_global=True):
@@ -401,3 +418,98 @@ class ShardedPipeline(object):
         self.step()
         self.synchronize()
         return self.records()
+
+    # ---- streaming: raw clouds of global batches in, records gathered on dst (raw_capacity set) --------------------------------------
+    def shard_of(self, n_valid, rank=None):
+        """[s, e) of the global batch's clouds that rank `rank` (default: this one) serves when the batch holds n_valid clouds: its
+        balanced_range over global_batch cut at n_valid (a short batch leaves trailing ranks fewer clouds, or none)."""
+        lo, hi = balanced_range(self.global_batch, self.world, self.rank if rank is None else rank)
+        return min(lo, n_valid), min(hi, n_valid)
+
+    def _check_batch(self, clouds, norm_factors):
+        """The checks of AncshPipeline.submit on EVERY rank's shard, so that every rank raises the same ValueError (before anything is
+        enqueued and before any collective) or none does.  -> (clouds, norm factors) as check_raw_clouds returns them."""
+        from .dataset import check_raw_clouds, check_stream_key
+        clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch)
+        for r in range(self.world):
+            s, e = self.shard_of(len(clouds), r)
+            if e == s:
+                continue
+            lo, hi = balanced_range(self.global_batch, self.world, r)
+            check_stream_key(lo, hi - lo, self.K)
+            rows = sum(c.shape[0] for c in clouds[s:e]) + (hi - lo - (e - s)) * clouds[s].shape[0]      # + padding with its first cloud
+            if rows > self.raw_capacity:
+                raise ValueError("rank %d's shard of the batch (clouds %d..%d) needs %d raw rows (short shards are padded with their first "
+                                 "cloud), raw_capacity is %d per rank" % (r, s, e - 1, rows, self.raw_capacity))
+        return clouds, nf
+
+    def submit(self, clouds, norm_factors, tag=None):
+        """Enqueue one GLOBAL batch (every rank calls this with the same batch): clouds = 1..global_batch raw (n_raw, 4) arrays, one norm
+        factor each.  This rank submits its shard -- nothing when a short batch leaves it no cloud -- to its pipeline with seed
+        seed + 2k (k = global batches submitted so far) and cloud_base = lo.  A bad batch raises ValueError on every rank, a full
+        in-flight window RuntimeError on every rank; either way nothing is enqueued and the stream stays usable.  World 1: the
+        local pipeline's submit."""
+        if self.raw_capacity is None:
+            raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
+        if self.world == 1:
+            return self.pipe.submit(clouds, norm_factors, tag=tag)
+        clouds, nf = self._check_batch(clouds, norm_factors)
+        if len(self._stream) == len(self.pipe.slots):
+            raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.pipe.slots))
+        seed = self.seed + 2 * self._stream_submitted
+        s, e = self.shard_of(len(clouds))
+        if e > s:
+            self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo)
+        self._stream.append((tag, seed, len(clouds), e > s))
+        self._stream_submitted += 1
+
+    def retire(self, flags=False):
+        """Wait for the oldest global batch and gather its records on dst (every rank calls this): dst -> (tag, seed, record
+        (n_valid, K, 26) float64 in global cloud order), the other ranks -> (tag, seed, None).  flags=True: + the range-guard flag
+        words (n_valid,) int32 on dst (None elsewhere).  The gather is one fixed-size (n_max, K, 26) float64 dist.gather over the
+        default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
+        World 1: the local pipeline's retire()."""
+        if self.world == 1:
+            return self.pipe.retire(flags)
+        if not self._stream:
+            raise RuntimeError("retire(): no batch in flight")
+        tag, seed, n_valid, here = self._stream.popleft()
+        s, e = self.shard_of(n_valid)
+        rec = np.zeros((self.n_max, self.K, 26), np.float64)
+        words = np.zeros((self.n_max,), np.int32)
+        if here:
+            got = self.pipe.retire(flags)
+            rec[:e - s] = got[2]
+            if flags:
+                words[:e - s] = got[3]
+        on_dst = self.rank == self.dst
+        if self._stream_bufs is None and on_dst:
+            self._stream_bufs = ([torch.empty((self.n_max, self.K, 26), dtype=torch.float64) for _ in range(self.world)],
+                                 [torch.empty((self.n_max,), dtype=torch.int32) for _ in range(self.world)])
+        bufs = self._stream_bufs if on_dst else (None, None)
+        dist.gather(torch.from_numpy(rec), bufs[0], dst=self.dst)
+        if flags:
+            dist.gather(torch.from_numpy(words), bufs[1], dst=self.dst)
+        if not on_dst:
+            return (tag, seed, None, None) if flags else (tag, seed, None)
+        cut = [self.shard_of(n_valid, r) for r in range(self.world)]
+        record = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+        if not flags:
+            return tag, seed, record
+        return tag, seed, record, np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+
+    def stream_batches(self, batches, flags=False):
+        """Generator over submit / retire of GLOBAL batches (every rank iterates the same batches): batches yields (clouds, norm_factors)
+        or (clouds, norm_factors, tag) (tag defaults to the batch's index); up to len(slots) batches stay in flight; yields (tag, seed,
+        record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
+        ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
+        seed, lm_schedule).  World 1 (or no process group): the local pipeline's stream_batches."""
+        if self.world == 1:
+            yield from self.pipe.stream_batches(batches, flags)
+            return
+        for k, item in enumerate(batches):
+            if len(self._stream) == len(self.pipe.slots):
+                yield self.retire(flags)
+            self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
+        while self._stream:
+            yield self.retire(flags)

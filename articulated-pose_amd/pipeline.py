@@ -64,7 +64,7 @@ def f16x2_weight_violations(nets):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -81,12 +81,15 @@ class _Slot(object):
         self.out32 = None
         if raw_capacity is not None:
             # streaming: raw rows + a header [seed (int64 bits) | offsets (B+1) int32 | norm factors (B) float32] on the device, their
-            # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again
+            # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again.
+            # keyed: the header leads with the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) instead of the seed
             from .dataset import RAW_NCHAN
+            self.keyed = bool(keyed)
+            lead = 4 if self.keyed else 2
             self.raw_rows = torch.zeros((raw_capacity, RAW_NCHAN), **f)
-            self.hdr = torch.zeros((2 + (B + 1) + B,), dtype=torch.int32, device=device)
+            self.hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32, device=device)
             self.h_rows = torch.zeros((raw_capacity, RAW_NCHAN), dtype=torch.float32).pin_memory()
-            self.h_hdr = torch.zeros((2 + (B + 1) + B,), dtype=torch.int32).pin_memory()
+            self.h_hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32).pin_memory()
             self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
@@ -94,8 +97,9 @@ class _Slot(object):
                 self.h_flags = torch.zeros((B,), dtype=torch.int32).pin_memory()
                 self.h_record32 = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
-            self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[2:B + 3],
-                                                                   hdr[B + 3:2 * B + 3].view(np.float32))
+            self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[lead:lead + B + 1],
+                                                                   hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
+            self.np_base = hdr[2:3] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
             # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
             rs = np.random.RandomState(0)
             self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
@@ -106,7 +110,10 @@ class _Slot(object):
             self.hdr.copy_(self.h_hdr)
 
     def header(self, B):
-        """(seed (1,) int64, offsets (B+1,) int32, norm factors (B,) float32) views of the device header."""
+        """(seed (1,) int64 -- keyed: the key block (4,) int32 --, offsets (B+1,) int32, norm factors (B,) float32) views of the device
+        header."""
+        if self.keyed:
+            return self.hdr[:4], self.hdr[4:B + 5], self.hdr[B + 5:2 * B + 5].view(torch.float32)
         return self.hdr[:2].view(torch.int64), self.hdr[2:B + 3], self.hdr[B + 3:2 * B + 3].view(torch.float32)
 
 
@@ -135,7 +142,7 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None, range_guard=False):
+                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False):
         self.K, self.B, self.N = num_parts, batch_size, num_points
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls) per batch, padding included
@@ -146,6 +153,12 @@ class AncshPipeline(object):
                 raise ValueError("raw_capacity must be in [1, 2^30) rows")
             raw_capacity = int(raw_capacity)
         self.raw_capacity = raw_capacity
+        # keyed (streaming only): the slot header leads with a key block (include/ancsh_hip.h, ancsh_stream_key) whose cloud_base
+        # submit() writes with the seed, and the sampler / pose fit key cloud b as global cloud cloud_base + b (the _keyed / _dkey
+        # entries): one captured graph then serves a shard at any offset of a global batch (dist.ShardedPipeline.stream_batches)
+        if keyed and raw_capacity is None:
+            raise ValueError("keyed=True keys the streaming header: it needs raw_capacity")
+        self.keyed = bool(keyed)
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
@@ -181,7 +194,8 @@ class AncshPipeline(object):
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard) for _ in range(max(1, slots))]
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed)
+                      for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -216,12 +230,14 @@ class AncshPipeline(object):
         return self.ancsh.predict(P, geom, arithmetic, flags, 0), self.npcs.predict(P, geom, arithmetic, flags, 1)
 
     def _sample(self, sl):
-        """The captured step's first launch when streaming: the slot's raw clouds -> its P / joint_cls."""
+        """The captured step's first launch when streaming: the slot's raw clouds -> its P / joint_cls.  -> the device key: the seed
+        (1,) int64, or (keyed) the key block."""
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
-        _lib.call("ancsh_input_sample_stream", self.B, self.N, RAW_NCHAN, _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off),
-                  _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P), _lib.ptr(sl.joint_cls), None)
+        _lib.call("ancsh_input_sample_stream_keyed" if self.keyed else "ancsh_input_sample_stream", self.B, self.N, RAW_NCHAN,
+                  _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P),
+                  _lib.ptr(sl.joint_cls), None)
         return seed
 
     def _run(self, sl=None, f32=False):
@@ -230,7 +246,8 @@ class AncshPipeline(object):
         guard = self.range_guard and not f32
         if guard:
             sl.flags.zero_()                  # the captured step's first node: the guarded launches only OR into the words
-        seed_dev = self._sample(sl) if self.raw_capacity is not None else None
+        key = self._sample(sl) if self.raw_capacity is not None else None
+        seed_dev, key_dev = (None, key) if self.keyed else (key, None)
         from . import pointnet_util
         geom = pointnet_util.Geometry()       # FPS / ball query / 3-NN depend only on P: computed once, used by both nets
         # the arithmetic goes down the layer helpers explicitly (None: the module globals); nothing global is changed
@@ -239,7 +256,8 @@ class AncshPipeline(object):
             nocs, mask, axis = n["nocs_per_point"], n["W"], a["joint_axis_per_point"]
         else:
             nocs, mask, axis = sl.pred_nocs, sl.pred_mask, sl.pred_axis
-        sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev)
+        sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
+                                key_dev=key_dev)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
@@ -320,16 +338,22 @@ class AncshPipeline(object):
             sl.stream.synchronize()
 
     # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
-    def submit(self, clouds, norm_factors, seed=None, tag=None):
+    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0):
         """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
         sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.  A short batch
         is padded with copies of its first cloud, whose records retire() drops.  seed: the generator key of the batch's sampling and
         of its pose fit (stage B uses seed + 1); None = self.seed + 2k for the k-th submitted batch (2k + 1 is its stage B).
+        cloud_base (keyed=True only; written into the pinned header with the seed): the global index of the batch's cloud 0 -- cloud b
+        is sampled and fitted as global cloud cloud_base + b; (cloud_base + batch_size) * num_parts must stay below 2^20.
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
-        from .dataset import check_raw_clouds, seed_bits
+        from .dataset import check_raw_clouds, check_stream_key, seed_bits
+        if self.keyed:
+            cloud_base = check_stream_key(cloud_base, self.B, self.K)
+        elif cloud_base != 0:
+            raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
         clouds, nf = check_raw_clouds(clouds, norm_factors, self.B)
         n_valid = len(clouds)
         padded = clouds + [clouds[0]] * (self.B - n_valid)
@@ -345,6 +369,8 @@ class AncshPipeline(object):
         sl = self.slots[self._next]
         sl.h2d_done.synchronize()                  # the previous batch's copies out of the pinned staging have completed
         sl.np_seed[0] = seed_bits(seed)
+        if self.keyed:
+            sl.np_base[0] = cloud_base
         np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
         sl.np_off[0] = 0
         np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])

@@ -35,7 +35,7 @@ TIE_WINDOW = 32 * 2.0 ** -27      # default half-width of the tie window on the 
 
 
 def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max_n=None, scalar_points=True, record=None, K=0,
-                        tie_window=None, seed_dev=None):
+                        tie_window=None, seed_dev=None, key_dev=None):
     """Batched ransac(dataset, single_transformation_estimator, single_transformation_verifier, th, niter).
     off (nprob+1) int32 row offsets into src/tgt (rows,3) float32 device tensors.
     scalar_points: score the hypotheses with the parts' points in scalar registers (ancsh_ransac_single_ex: a padded quad copy of
@@ -44,6 +44,8 @@ def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max
     (ancsh_ransac_single_rec); tie_window: not None -> `tie` (nprob, 2) int32 [borderline points of the winner, degenerate
     contenders] (see include/ancsh_hip.h).  seed_dev: optional one-element int64 device tensor holding the generator key (its
     uint64 bits), read when the kernels run (ancsh_ransac_single_rec_dseed) -- `seed` is then unused.
+    key_dev: optional 16-byte device key block (ancsh_stream_key: seed, cloud_base; e.g. four int32 words) instead of seed_dev
+    (ancsh_ransac_single_rec_dkey): the generator keys problem p as p + cloud_base * K, so it needs K.
     -> dict(model (nprob,13) f64 [R(9) s t(3)], inliers (rows) uint8, best (nprob,2) int32 [iter, score])."""
     dev = src.device
     nprob = off.numel() - 1
@@ -59,10 +61,11 @@ def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max
     quads, tie = None, None
     if scalar_points:
         quads = torch.empty((_lib.lib().ancsh_ransac_single_quads_floats(rows, nprob),), dtype=torch.float32, device=dev)
-    if seed_dev is not None:
+    if key_dev is not None or seed_dev is not None:
         tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_single_rec_dseed", nprob, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter),
-                  _lib.ptr(d), _lib.ptr(seed_dev), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores), _lib.ptr(quads),
+        _lib.call("ancsh_ransac_single_rec_dkey" if key_dev is not None else "ancsh_ransac_single_rec_dseed", nprob, _lib.ptr(off),
+                  _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter), _lib.ptr(d), _lib.ptr(key_dev if key_dev is not None else seed_dev),
+                  max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores), _lib.ptr(quads),
                   rows, _lib.ptr(record), int(K), _lib.ptr(tie), float(tie_window or 0.0))
     elif record is not None or tie_window is not None:
         tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
@@ -82,11 +85,13 @@ LM_SCHEDULES = {"auto": 0, "throughput": 1, "latency": 2}     # ANCSH_LM_* of in
 
 
 def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=None, seed=0, max_n=None, want_lm_stat=False,
-                       lm_schedule="auto", record=None, K=0, tie_window=None, seed_dev=None):
+                       lm_schedule="auto", record=None, K=0, tie_window=None, seed_dev=None, key_dev=None):
     """Batched ransac(dataset, joint_transformation_estimator, joint_transformation_verifier, th, niter).
     rng0/rng1 (nprob,2) int32 [start,end) rows of part 0 / part j; joint_dir (nprob,3) float32.
     seed_dev: optional one-element int64 device tensor; the kernels use its value + 1 (ancsh_ransac_joint_rec_dseed: stage B of the
     key that stage A reads there) and `seed` is unused.
+    key_dev: optional 16-byte device key block (ancsh_stream_key) instead of seed_dev (ancsh_ransac_joint_rec_dkey: its seed + 1, problem
+    p keyed as p + cloud_base * (K - 1); needs K).
     -> dict(model (nprob,26) f64 [R0 s0 t0 R1 s1 t1], inliers (nprob,2,max_n) uint8, best (nprob), score (nprob))."""
     dev = src.device
     nprob = rng0.shape[0]
@@ -102,10 +107,11 @@ def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=
     if d is not None and d.numel() != nprob * niter * 6:
         raise ValueError("draws must have shape (nprob, niter, 6)")
     tie = None
-    if seed_dev is not None:
+    if key_dev is not None or seed_dev is not None:
         tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_joint_rec_dseed", nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir),
-                  float(inlier_th), int(niter), _lib.ptr(d), _lib.ptr(seed_dev), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
+        _lib.call("ancsh_ransac_joint_rec_dkey" if key_dev is not None else "ancsh_ransac_joint_rec_dseed", nprob, _lib.ptr(rng0),
+                  _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th), int(niter), _lib.ptr(d),
+                  _lib.ptr(key_dev if key_dev is not None else seed_dev), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
                   _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule], _lib.ptr(record), int(K),
                   _lib.ptr(tie), float(tie_window or 0.0))
     elif record is not None or tie_window is not None:      # the finish kernel also fills the record's nonlinear columns / the tie counts
@@ -170,7 +176,8 @@ class PoseSolver(object):
         self.lm_schedule = lm_schedule         # "latency": eight lanes per LM fit (a lone batch finishes sooner); "throughput": one
         self.want_lm_stat = want_lm_stat       # also return per-hypothesis (status, nfev) of the stage-B LM fits
 
-    def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls, draws_a=None, draws_b=None, seed=0, seed_dev=None):
+    def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls, draws_a=None, draws_b=None, seed=0, seed_dev=None,
+              key_dev=None):
         """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and it is the
         latency-bound half (64 waves for 1.6 ms: MINPACK's longest trajectory), so it is ISSUED FIRST: its LM kernel then runs
         under the full-chip scoring kernel of other batches in flight, and a batch ends with 0.3 ms of stage A instead of idling
@@ -178,10 +185,13 @@ class PoseSolver(object):
         but the partition.
         seed_dev: a one-element int64 device tensor holding the generator key (its uint64 bits) instead of `seed`: the kernels read
         it when they run, so a captured step draws a fresh sample stream per batch from whatever was written there last; the
-        bytes equal those of seed=<that value>."""
+        bytes equal those of seed=<that value>.
+        key_dev: a 16-byte device key block (include/ancsh_hip.h, ancsh_stream_key; dataset.stream_key_words) instead of either: its
+        seed is read as seed_dev's, and cloud b is keyed as global cloud cloud_base + b -- so a shard of clouds [lo, hi) solved with
+        cloud_base = lo gives the bytes of rows [lo, hi) of the whole batch's solve(seed=<that seed>)."""
         out = self._partition(P, nocs_pred, mask_pred)
-        self.solve_stage_b(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev)
-        return self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev))
+        self.solve_stage_b(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev)
+        return self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):
         """Part labels + per-part RANSAC / Kabsch (stage A, :238-272): needs only the part-NOCS network's outputs."""
@@ -222,12 +232,12 @@ class PoseSolver(object):
         return dict(labels=labels, part_index=pidx, off=off, counts=counts, record=record, _src=src, _tgt=tgt, _max_n=max_n, _shape=(B, N),
                     _rng=(rng0, rng1), _inputs=(P, nocs, W))
 
-    def _stage_a_fits(self, out, draws_a=None, seed=0, seed_dev=None):
+    def _stage_a_fits(self, out, draws_a=None, seed=0, seed_dev=None, key_dev=None):
         dev, K = self.device, self.K
         B, N = out["_shape"]
         a = ransac_single_batch(out["off"], out["_src"], out["_tgt"], self.th, self.niter_a,
                                 None if draws_a is None else _i32(draws_a, dev).reshape(B * K, self.niter_a, 3), seed, out["_max_n"],
-                                record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev)
+                                record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev)
         out.update(baseline=out["record"][:, :, :13], best_a=a["best"].view(B, K, 2), inliers_a=a["inliers"].view(B, N))
         if a["tie"] is not None:
             out["tie_a"] = a["tie"].view(B, K, 2)
@@ -235,8 +245,9 @@ class PoseSolver(object):
             out["nonlinear"] = out["record"][:, :, 13:]           # a one-part object: the finish kernel wrote the baseline there too
         return out
 
-    def solve_stage_b(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None):
-        """Articulated joint fit (stage B, :274-341) on top of a solve_stage_a result (key seed + 1, or *seed_dev + 1 read on the device)."""
+    def solve_stage_b(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None):
+        """Articulated joint fit (stage B, :274-341) on top of a solve_stage_a result (key seed + 1, or *seed_dev + 1 / the key block's
+        seed + 1 read on the device)."""
         dev, K = self.device, self.K
         B, N = out["_shape"]
         src, tgt, max_n = out["_src"], out["_tgt"], out["_max_n"]
@@ -249,7 +260,7 @@ class PoseSolver(object):
             b = ransac_joint_batch(rng0, rng1, src, tgt, jdir.view(-1, 3), self.th, self.niter_b,
                                    None if draws_b is None else _i32(draws_b, dev).reshape(B * (K - 1), self.niter_b, 6),
                                    seed + 1, max_n, want_lm_stat=self.want_lm_stat, lm_schedule=self.lm_schedule,
-                                   record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev)
+                                   record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev)
             if self.want_lm_stat:
                 out["lm_stat"] = b["lm_stat"].view(B, K - 1, self.niter_b, 2)
             out["nonlinear"] = out["record"][:, :, 13:]

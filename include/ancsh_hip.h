@@ -41,7 +41,8 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 9: + the F16x2 range guard (ancsh_*_f16x2*_guarded);
+int ancsh_abi_version(void);   /* 10: + ancsh_input_sample_stream_keyed, ancsh_ransac_single_rec_dkey, ancsh_ransac_joint_rec_dkey (ancsh_stream_key);
+                                 * 9: + the F16x2 range guard (ancsh_*_f16x2*_guarded);
                                  * 8: + ancsh_input_sample_stream, ancsh_ransac_single_rec_dseed, ancsh_ransac_joint_rec_dseed (the streaming pipeline);
                                  * 7 since round 6 (5: round 5, 4: round 4, 3: round 3).  Operator entry points are only ever added: a library of version v serves every caller
                                  * written for <= v.  The one removal, in 7: ancsh_hbm_copy -- bench.py's HBM-copy yardstick, never an operator -- left the library
@@ -577,6 +578,34 @@ int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const int *rng1, co
                                  double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
                                  int *tie_stats, double tie_window, void *stream);
 
+/* The key block of a sharded stream, in device memory (16 bytes).  seed: the generator key, as *seed of the _dseed entries.
+ * cloud_base: the GLOBAL index of the launch's cloud 0.  A cloud then draws the same samples whichever launch serves it and at
+ * whatever position: cloud b of a launch with base c gets the samples of cloud c + b of a launch with base 0.  reserved: unused (0). */
+typedef struct {
+    unsigned long long seed;
+    int cloud_base;
+    int reserved;
+} ancsh_stream_key;
+
+/* ancsh_ransac_single_rec_dseed / ancsh_ransac_joint_rec_dseed with the key block: the generator's problem index becomes
+ * prob + key->cloud_base * K (stage A, prob = b * K + part) and prob + key->cloud_base * (K - 1) (stage B, prob = b * (K - 1) + joint);
+ * stage B still adds 1 to the seed.  Only the generator's key moves: offsets, draws, scores, scratch and the record stay indexed by the
+ * local prob, and explicit draws still override the generator.  So the fits of clouds [lo, hi) with cloud_base = lo equal rows [lo, hi)
+ * of the whole batch's by-value fit (seed s, s + 1) byte for byte.  K is required (it is the problem count of one cloud): nprob must be
+ * a multiple of K (stage A) / K - 1 >= 1 (stage B), below 2^20.  The draw keys stay clear of the sampler's tag bits 60..63 while
+ * (cloud_base + B) * K < 2^20, B = the launch's clouds; cloud_base is in device memory, so that bound is the caller's to keep where it
+ * writes the block (AncshPipeline.submit refuses larger bases).  The kernels are the by-value ones instantiated with a third key mode;
+ * the by-value and _dseed instantiations are unchanged (profiles/r09_sharded_stream_isa_compare.txt).  key == NULL is refused. */
+int ancsh_ransac_single_rec_dkey(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+                                 const int *draws, const ancsh_stream_key *key, int max_n, double *out_model,
+                                 unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
+                                 double *record, int K, int *tie_stats, float tie_window, void *stream);
+int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                const float *joint_dir, double inlier_th, int niter, const int *draws, const ancsh_stream_key *key,
+                                int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
+                                double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+                                int *tie_stats, double tie_window, void *stream);
+
 /* Batched estimateSimilarityUmeyama (lib/aligning.py:580-622; GT poses of evaluation/compute_gt_pose.py:87).
  * Problem p = rows [off[p], off[p+1]) of src/tgt.  out (nprob,32) float64: Scales(3) | Rotation(9, the
  * reference's TRANSPOSED matrix) | Translation(3) | OutTransform (4x4 row-major, 16) | pad(1). */
@@ -653,6 +682,15 @@ int ancsh_input_sample(int nclouds, int num_points, int nchan, const float *rows
 int ancsh_input_sample_stream(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
                               const float *norm_factor, int jcls_col, const unsigned long long *seed, float *P, int *joint_cls,
                               int *perm_out, void *stream);
+
+/* ancsh_input_sample_stream with the key block (ancsh_stream_key above) in place of the bare seed: the Feistel round keys use the
+ * GLOBAL cloud index, key[r] = splitmix64(s ^ splitmix64(0xF000000000000000 | (cloud_base + b) << 8 | r)), s = key->seed.  So clouds
+ * [lo, hi) sampled with cloud_base = lo give P, joint_cls and perm_out equal to rows [lo, hi) of the whole batch sampled with base 0,
+ * and base 0 gives the bytes of ancsh_input_sample_stream.  Same checks; key == NULL is refused.  The kernel is the unkeyed one with a
+ * template flag; the unkeyed instantiation is unchanged. */
+int ancsh_input_sample_stream_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                                    const float *norm_factor, int jcls_col, const ancsh_stream_key *key, float *P, int *joint_cls,
+                                    int *perm_out, void *stream);
 
 /* ---- test-time losses of predict_and_save (lib/network.py:430-498, lib/loss.py:54-182) ------- */
 

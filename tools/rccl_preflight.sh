@@ -9,6 +9,9 @@
 #      of tests/test_dist_gpu.py::test_sharded_pipeline_equals_single_process with the nccl backend and one GPU per rank);
 #   4. the drop-in entry point `python -m articulated_pose_amd.pose_multi_process` on 2 ranks over a synthetic results tree
 #      (tests/test_entry_gpu.py's tree): both per-worker pickles written, their union = the single-rank pickle.
+#   5. the sharded stream, dist.ShardedPipeline.stream_batches, on 2..N ranks (one GPU each): 50 ragged global batches (short ones leave
+#      trailing ranks fewer clouds or none) give on rank 0 the tags, seeds and records of one AncshPipeline.stream_batches, byte for byte
+#      (the logic of tests/test_sharded_stream_gpu.py::test_sharded_stream_equals_single_process with one GPU per rank).
 # Usage: tools/rccl_preflight.sh [N_GPUS=2]      (from the repo root; exits non-zero at the first failed check)
 set -u
 N=${1:-2}
@@ -98,4 +101,60 @@ PY
 echo "== 4. pose_multi_process on $N ranks =="
 timeout 900 python -m pytest tests/test_entry_gpu.py -x -q -k "pose_multi_process or evaluation_sh" 2>&1 | tail -3
 [ "${PIPESTATUS[0]}" -eq 0 ] || fail "entry-point tests"
+echo "== 5. dist.ShardedPipeline.stream_batches on 2..$N ranks == one-GPU AncshPipeline.stream_batches =="
+cat > "$OUT/stream.py" <<'PY'
+import os, sys
+import numpy as np, torch
+sys.path.insert(0, os.getcwd())
+import articulated_pose_amd
+from articulated_pose_amd import dist as D
+from articulated_pose_amd.synthetic import passthrough_pose_problem
+world, G = int(sys.argv[1]), int(sys.argv[3])                     # G: the global batch, the same for both runs of a pair
+if D.wants_self_launch(world):
+    sys.exit(D.launch_local_ranks(world, [sys.executable] + sys.argv, timeout=800))
+local = int(os.environ.get("LOCAL_RANK", "0"))
+dev = torch.device("cuda", local % torch.cuda.device_count() if world > 1 else 0)
+torch.cuda.set_device(dev)
+K, N, count = 3, 512, 50
+pb = passthrough_pose_problem(K, 6, N, seed=3)
+rs = np.random.RandomState(17)
+batches = []
+for k in range(count):
+    nb = G if k % 7 else int(rs.randint(1, G))                    # every 7th batch short: trailing ranks hold fewer clouds, or none
+    clouds = []
+    for _ in range(nb):
+        src, n = rs.randint(6), int(rs.randint(N // 3, 3 * N))
+        idx = rs.randint(0, N, n)
+        c = np.concatenate([pb["P"][src][idx] + rs.normal(0, 2e-3, (n, 3)).astype(np.float32), pb["cls"][src][idx, None]], 1)
+        clouds.append(c.astype(np.float32))
+    batches.append((clouds, rs.uniform(0.9, 1.1, nb).astype(np.float32), "b%d" % k))
+kw = dict(couple=True, slots=4, niter_a=256, niter_b=32, seed=100, lm_schedule="throughput")
+if world == 1:
+    from articulated_pose_amd.pipeline import AncshPipeline
+    got = list(AncshPipeline(K, pb["w_ancsh"], pb["w_npcs"], G, N, dev, raw_capacity=G * 3 * N, **kw).stream_batches(batches))
+else:
+    import torch.distributed as dist
+    D.init_groups("nccl", dev)                                        # the stream gathers over the gloo control group
+    sp = D.ShardedPipeline(K, pb["w_ancsh"], pb["w_npcs"], G, N, dev, raw_capacity=-(-G // world) * 3 * N, **kw)
+    got = list(sp.stream_batches(batches))
+    if dist.get_rank() != 0:
+        got = None
+    dist.barrier(); dist.destroy_process_group()
+if got is not None:
+    np.savez(sys.argv[2], tags=np.array([t for t, _, _ in got]), seeds=np.array([s for _, s, _ in got]),
+             records=np.concatenate([r for _, _, r in got]))
+PY
+for W in $(seq 2 "$N"); do
+  G=$((4 * W + 1))                                                # a ragged split on every world size
+  timeout 900 python "$OUT/stream.py" 1 "$OUT/stream1_$W.npz" "$G" || fail "one-GPU stream"
+  timeout 900 python "$OUT/stream.py" "$W" "$OUT/streamN_$W.npz" "$G" || fail "sharded stream on $W ranks"
+  python - "$OUT/stream1_$W.npz" "$OUT/streamN_$W.npz" "$W" <<'PY' || fail "sharded stream records differ from the one-GPU stream"
+import sys, numpy as np
+a, b = np.load(sys.argv[1]), np.load(sys.argv[2])
+assert list(a["tags"]) == list(b["tags"]) and list(a["seeds"]) == list(b["seeds"]) and len(a["tags"]) == 50
+assert a["records"].shape == b["records"].shape and np.array_equal(a["records"].view(np.int64), b["records"].view(np.int64))
+print("sharded stream on %s ranks == one-GPU stream, byte for byte: %d records" % (sys.argv[3], len(a["records"])))
+PY
+done
+
 echo "PREFLIGHT OK ($N GPUs)"
