@@ -92,6 +92,10 @@ extern "C" int ancsh_iou_3d(int npairs, int nres, const double *bbox1, const dou
     return check_launch("iou_3d");
 }
 
+// The shared passes of the three evaluation kernels below.  Included HERE, where their helpers used to be defined: the order of the
+// functions in the module decides how the compiler inlines them, and joint_params_kernel keeps its instruction stream only in this order.
+#include "part_stats.h"
+
 namespace ancsh {
 
 // ---- joint parameters from the per-point heads (evaluation/eval_joint_params.py:143-199) --------------------------------
@@ -104,23 +108,7 @@ namespace ancsh {
 // One workgroup per (cloud, part) and per (cloud, joint).  float32 element arithmetic in numpy's order (the inputs are float32
 // .h5 arrays); medians are exact selections (ordered compaction + bitonic sort per channel, as joint_direction_kernel in
 // pose.hip); the reductions behind std / mean run in float64 (numpy: pairwise float32 -- equal to ~1e-7, tests bound 1e-6).
-template <int K_MAX>
-__device__ __forceinline__ int argmax_row(const float *m, int K) {
-    int c = 0;
-    float best = m[0];
-    for (int k = 1; k < K; ++k) { const float v = m[k]; if (v > best) { best = v; c = k; } }    // np.argmax: first maximum
-    return c;
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
+// The passes live in part_stats.h (ANCSH_PART_SIMILARITY, ANCSH_COMPACT_JOINT_VOTES, ANCSH_SORT_VOTE_COLUMNS), shared with articulation_kernel.
 __global__ __launch_bounds__(256) void joint_params_kernel(int n, int K, int G, int axis_mean, const float *__restrict__ gocs,
                                                            const float *__restrict__ nocs, const float *__restrict__ mask,
                                                            const float *__restrict__ heatmap, const float *__restrict__ unitvec,
@@ -134,32 +122,7 @@ __global__ __launch_bounds__(256) void joint_params_kernel(int n, int K, int G, 
     if ((int)blockIdx.y < K) {           // ---- similarity global NOCS -> part NOCS of part j
         if (!nocs || !st) return;
         const int j = blockIdx.y;
-        double sx = 0, sxx = 0, sy = 0, syy = 0, m = 0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int c = mask ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;
-            if (c != j) continue;
-            const float *x = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * j), *y = nocs + (p0 + i) * 3 * K + 3 * j;
-            const float xm = ((x[0] + x[1]) + x[2]) / 3.0f, ym = ((y[0] + y[1]) + y[2]) / 3.0f;    // np.mean(., axis=1) in float32
-            sx += xm; sxx += (double)xm * xm; sy += ym; syy += (double)ym * ym; m += 1.0;
-        }
-        sx = block_sum_f64(sx, red); sxx = block_sum_f64(sxx, red); sy = block_sum_f64(sy, red); syy = block_sum_f64(syy, red);
-        m = block_sum_f64(m, red);
-        const double vx = sxx / m - (sx / m) * (sx / m), vy = syy / m - (sy / m) * (sy / m);
-        const float scale = (float)sqrt(vy > 0 ? vy : 0.0) / (float)sqrt(vx > 0 ? vx : 0.0);      // float32 / float32 (np.std of float32)
-        double t[3] = {0, 0, 0};
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int c = mask ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;
-            if (c != j) continue;
-            const float *x = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * j), *y = nocs + (p0 + i) * 3 * K + 3 * j;
-#pragma unroll
-            for (int c3 = 0; c3 < 3; ++c3) t[c3] += (double)(y[c3] - scale * x[c3]);
-        }
-        for (int c3 = 0; c3 < 3; ++c3) t[c3] = block_sum_f64(t[c3], red);
-        if (threadIdx.x == 0) {
-            double *o = st + ((size_t)b * K + j) * 4;
-            o[0] = m > 0 ? (double)scale : NAN;
-            for (int c3 = 0; c3 < 3; ++c3) o[1 + c3] = m > 0 ? t[c3] / m : NAN;
-        }
+        ANCSH_PART_SIMILARITY(n, K, G, j, p0, gocs, nocs, mask, red, st + ((size_t)b * K + j) * 4)
         return;
     }
     // ---- joint j: ordered compaction of the votes (index order), then per-channel median (or mean of the axis)
@@ -167,29 +130,7 @@ __global__ __launch_bounds__(256) void joint_params_kernel(int n, int K, int G, 
     int npow2 = 1;
     while (npow2 < n) npow2 <<= 1;
     int cnt = 0;
-    for (int c0 = 0; c0 < n; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        const bool f = i < n && joint_cls[p0 + i] == j;
-        const unsigned long long mm = __ballot(f);
-        __syncthreads();
-        if (lane == 0) wcnt[wave] = __popcll(mm);
-        __syncthreads();
-        int start = cnt;
-        for (int w = 0; w < wave; ++w) start += wcnt[w];
-        if (f) {
-            const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(mm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mm, 0));
-            const int c = (mask && G != 3) ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;
-            const float *g = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * c);
-            const float w1 = 1.0f - heatmap[p0 + i];
-#pragma unroll
-            for (int c3 = 0; c3 < 3; ++c3) {
-                jp_vals[c3 * npow2 + pos] = axis[(p0 + i) * 3 + c3];
-                const float off = (unitvec[(p0 + i) * 3 + c3] * w1) * 0.2f;      // unitvec * (1 - heatmap) * thres_r, float32
-                jp_vals[(3 + c3) * npow2 + pos] = g[c3] + off;
-            }
-        }
-        cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    }
+    ANCSH_COMPACT_JOINT_VOTES(n, K, G, p0, npow2, gocs, mask, heatmap, unitvec, axis, joint_cls[p0 + i] == j, jp_vals, wcnt, lane, wave, cnt)
     __syncthreads();
     double *o = joint + ((size_t)b * (K - 1) + (j - 1)) * 6;
     if (axis_mean && threadIdx.x < 3) {      // np.mean(orient_gt[idx], axis=0): float32 accumulation row by row, then / count
@@ -199,41 +140,13 @@ __global__ __launch_bounds__(256) void joint_params_kernel(int n, int K, int G, 
         o[3 + threadIdx.x] = cnt > 0 ? (double)(s / (float)cnt) : NAN;
     }
     __syncthreads();
-    int p2 = 1;
-    while (p2 < cnt) p2 <<= 1;
-    for (int e = cnt + threadIdx.x; e < p2; e += 256)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) jp_vals[c * npow2 + e] = INFINITY;
-    __syncthreads();
-    for (int k = 2; k <= p2; k <<= 1)
-        for (int s = k >> 1; s > 0; s >>= 1) {
-            for (int e = threadIdx.x; e < p2; e += 256) {
-                const int partner = e ^ s;
-                if (partner > e) {
-                    const bool up = (e & k) == 0;
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        float *v = jp_vals + c * npow2;
-                        const float a = v[e], bb = v[partner];
-                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    ANCSH_SORT_VOTE_COLUMNS(jp_vals, npow2, cnt)
     if (threadIdx.x < 6) {
-        const float *v = jp_vals + threadIdx.x * npow2;
-        float med = NAN;
-        if (cnt > 0) med = (cnt & 1) ? v[cnt / 2] : (v[cnt / 2 - 1] + v[cnt / 2]) * 0.5f;
+        ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, threadIdx.x)
         if (threadIdx.x >= 3) o[threadIdx.x - 3] = med;            // joint point
         else if (!axis_mean) o[3 + threadIdx.x] = med;            // joint axis
     }
 }
-
-// np.max / np.min PROPAGATE a NaN (compute_miou.py:196-208 takes np.max(abs(nocs - 0.5)) per part: a NaN prediction gives a NaN extent);
-// fmaxf / fmin would drop it
-__device__ __forceinline__ float np_maxf(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
-__device__ __forceinline__ double np_min(double a, double b) { return a != a ? a : (b != b ? b : fmin(a, b)); }
 
 // ---- amodal-box extents and boundaries of the predicted parts (evaluation/compute_miou.py:196-208, eval_pose_err.py:253-268) ----
 // Per cloud and part j (points whose predicted mask row has its first maximum at j):
@@ -242,7 +155,8 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
 //                  ([P 1] . pinv(rt_0^T))[:, 0] with rt_0 = compose_rt(R0, t0) in FLOAT32 (:25-30) = sum_c (P_c - t0_c) * R0[c][0],
 //                  float64 products of the float32-rounded pose (the reference's float32 pinv differs from this inverse by ~1e-7)
 //   count_j      = points of the part (0 -> the reference's np.max raises and its bare except drops the frame)
-// One workgroup per cloud, all its parts in one pass; HBM-bound: the mask, the point and the point's own NOCS slot are read once.
+// One workgroup per cloud, all its parts in one pass (part_stats.h); HBM-bound: the mask, the point and the point's own NOCS slot are
+// read once.
 __global__ __launch_bounds__(256) void part_extents_kernel(int n, int K, int C, const float *__restrict__ nocs, const float *__restrict__ mask,
                                                            const float *__restrict__ P, int ldp, const double *__restrict__ pose0,
                                                            float *__restrict__ scale_pred, double *__restrict__ dynam,
@@ -257,41 +171,7 @@ __global__ __launch_bounds__(256) void part_extents_kernel(int n, int K, int C, 
     const double r00 = (double)(float)ps[0], r10 = (double)(float)ps[3], r20 = (double)(float)ps[6];
     const double t0 = (double)(float)ps[9], t1 = (double)(float)ps[10], t2 = (double)(float)ps[11];
     const double m30 = (double)(float)(-(t0 * r00 + t1 * r10 + t2 * r20));      // the inverse's translation entry, float32 like the pinv's
-    // one pass over the cloud: every part's running extents in registers (the part index only selects, it never addresses)
-    float m[KM][3];
-    double mn[KM];
-    int cnt[KM];
-#pragma unroll
-    for (int j = 0; j < KM; ++j) { m[j][0] = m[j][1] = m[j][2] = -INFINITY; mn[j] = INFINITY; cnt[j] = 0; }
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int c = argmax_row<KM>(mask + (p0 + i) * K, K);
-        const float *q = nocs + (p0 + i) * C + (C == 3 ? 0 : 3 * c);
-        const float a0 = fabsf(q[0] - 0.5f), a1 = fabsf(q[1] - 0.5f), a2 = fabsf(q[2] - 0.5f);
-        const float *x = P + (p0 + i) * ldp;
-        // numpy: [x y z 1] . M[:, 0] accumulated left to right in float64
-        const double v = (((double)x[0] * r00 + (double)x[1] * r10) + (double)x[2] * r20) + m30;
-#pragma unroll
-        for (int j = 0; j < KM; ++j) {
-            const bool mine = c == j;
-            m[j][0] = mine ? np_maxf(m[j][0], a0) : m[j][0];
-            m[j][1] = mine ? np_maxf(m[j][1], a1) : m[j][1];
-            m[j][2] = mine ? np_maxf(m[j][2], a2) : m[j][2];
-            mn[j] = mine ? np_min(mn[j], v) : mn[j];
-            cnt[j] += mine ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < KM; ++j) {
-        if (j >= K) break;                                      // K is uniform: the unused parts cost nothing past this point
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            m[j][0] = np_maxf(m[j][0], __shfl_xor(m[j][0], o, 64)); m[j][1] = np_maxf(m[j][1], __shfl_xor(m[j][1], o, 64));
-            m[j][2] = np_maxf(m[j][2], __shfl_xor(m[j][2], o, 64));
-            mn[j] = np_min(mn[j], __shfl_xor(mn[j], o, 64));
-            cnt[j] += __shfl_xor(cnt[j], o, 64);
-        }
-        if (lane == 0) { smax[wave][j][0] = m[j][0]; smax[wave][j][1] = m[j][1]; smax[wave][j][2] = m[j][2]; smin[wave][j] = mn[j]; scnt[wave][j] = cnt[j]; }
-    }
+    ANCSH_PART_EXTENTS_PASS(true, n, K, C, p0, nocs, mask, P, ldp, r00, r10, r20, m30, smax, smin, scnt, lane, wave)
     __syncthreads();
     if ((int)threadIdx.x < K) {
         const int j = threadIdx.x;
@@ -302,6 +182,116 @@ __global__ __launch_bounds__(256) void part_extents_kernel(int n, int K, int C, 
         for (int k = 0; k < 3; ++k)
             scale_pred[o * 3 + k] = c > 0 ? 2.0f * np_maxf(np_maxf(smax[0][j][k], smax[1][j][k]), np_maxf(smax[2][j][k], smax[3][j][k])) : NAN;
         dynam[o] = c > 0 ? np_min(np_min(smin[0][j], smin[1][j]), np_min(smin[2][j], smin[3][j])) : NAN;
+    }
+}
+
+// np.argmax of a row of C floats: the first maximum, or the first NaN (numpy and torch.argmax rank NaN above every number)
+__device__ __forceinline__ int argmax_first_nan(const float *m, int C) {
+    float best = m[0];
+    if (best != best) return 0;
+    int c = 0;
+    for (int k = 1; k < C; ++k) {
+        const float v = m[k];
+        if (v != v) return k;
+        if (v > best) { best = v; c = k; }
+    }
+    return c;
+}
+
+// ---- articulation block of the streamed step (pred side of compute_miou.py:196-222 and eval_joint_params.py:143-220) ----------------
+// Per cloud b, row j of art (b, K, 12) float64, from the pose record's nonlinear R_j (cols 13..21), s_j (22), t_j (23..25):
+//   0..2   box size     s_j * scale_pred_j,  scale_pred_j = 2 max |nocs_npcs_j - 0.5| over the NPCS network's part j   (:196-200, 214-217)
+//   3..5   box centre   s_j * R_j (1/2, 1/2, 1/2) + t_j: the centre of get_3d_bbox(scale, shift=1/2) taken to camera space  (:217-222)
+//   6..8   pivot        R_0 (s_0 (p_j s2 + t2)) + t_0;  p_j = per-channel median of the ANCSH votes of joint class j, (s2, t2) = the ANCSH
+//                       part-0 similarity global -> part NOCS                                               (eval_joint_params.py:214-219)
+//   9..11  axis         R_0 a_j;  a_j = per-channel median of joint_axis_per_point over the same points, not normalised    (:220)
+// Row 0's joint columns are NaN; an empty part or joint class gives NaN in its own columns; a cloud whose part-0 nonlinear pose has a NaN
+// (a poisoned record) gets an all-NaN block.  Workgroup (b, 0): every part's box (ANCSH_PART_EXTENTS_PASS); workgroup (b, j >= 1): joint j,
+// recomputing part 0's similarity so that nothing waits for another workgroup.  The joint class is the first argmax of the ANCSH
+// index_per_point (JC channels: joint j >= JC has no points).  The optional debug outputs joint_nocs (b, K-1, 6), st0 (b, 4) and
+// extent (b, K, 3) are bit-equal to ancsh_joint_params' joint / st row 0 and ancsh_part_extents' scale_pred.
+__global__ __launch_bounds__(256) void articulation_kernel(int n, int K, int G, int JC, const float *__restrict__ gocs,
+                                                           const float *__restrict__ nocs, const float *__restrict__ mask,
+                                                           const float *__restrict__ heatmap, const float *__restrict__ unitvec,
+                                                           const float *__restrict__ axis, const float *__restrict__ joint_index,
+                                                           const float *__restrict__ npcs_nocs, const float *__restrict__ npcs_mask,
+                                                           const double *__restrict__ record, double *__restrict__ art,
+                                                           double *__restrict__ joint_nocs, double *__restrict__ st0, float *__restrict__ extent) {
+    extern __shared__ float art_vals[];   // 6 * npow2 floats (joint blocks)
+    __shared__ double red[4];
+    __shared__ double sst[4];
+    __shared__ int wcnt[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t p0 = (size_t)b * n;
+    const double *rec = record + (size_t)b * K * 26;
+    bool poisoned = false;
+    for (int c = 13; c < 26; ++c) poisoned |= rec[c] != rec[c];
+    double *ab = art + (size_t)b * K * 12;
+    if (blockIdx.y == 0) {               // ---- the boxes of all parts
+        constexpr int KM = 8;
+        __shared__ float smax[4][KM][3];
+        __shared__ int scnt[4][KM];
+        double (*smin)[KM] = nullptr;                      // no boundary pass: never written
+        const float *P = nullptr;
+        ANCSH_PART_EXTENTS_PASS(false, n, K, 3 * K, p0, npcs_nocs, npcs_mask, P, 0, 0.0, 0.0, 0.0, 0.0, smax, smin, scnt, lane, wave)
+        __syncthreads();
+        if ((int)threadIdx.x < K) {
+            const int j = threadIdx.x;
+            const int c = scnt[0][j] + scnt[1][j] + scnt[2][j] + scnt[3][j];
+            const double *r = rec + j * 26 + 13, s = r[9], *t = r + 10;
+            double *o = ab + j * 12;
+            const bool dead = poisoned || c == 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float e = c > 0 ? 2.0f * np_maxf(np_maxf(smax[0][j][k], smax[1][j][k]), np_maxf(smax[2][j][k], smax[3][j][k])) : NAN;
+                if (extent) extent[((size_t)b * K + j) * 3 + k] = e;
+                o[k] = dead ? NAN : s * (double)e;
+                o[3 + k] = dead ? NAN : s * ((r[3 * k] * 0.5 + r[3 * k + 1] * 0.5) + r[3 * k + 2] * 0.5) + t[k];
+            }
+            if (j == 0)
+#pragma unroll
+                for (int k = 6; k < 12; ++k) o[k] = NAN;
+        }
+        if (K == 1 && st0 && threadIdx.x < 4) st0[(size_t)b * 4 + threadIdx.x] = NAN;      // no joint workgroup: no similarity either
+        return;
+    }
+    // ---- joint j: part 0's similarity, the votes' medians, then camera space through part 0's pose
+    const int j = blockIdx.y;
+    ANCSH_PART_SIMILARITY(n, K, G, 0, p0, gocs, nocs, mask, red, sst)
+    int npow2 = 1;
+    while (npow2 < n) npow2 <<= 1;
+    int cnt = 0;
+    ANCSH_COMPACT_JOINT_VOTES(n, K, G, p0, npow2, gocs, mask, heatmap, unitvec, axis, argmax_first_nan(joint_index + (p0 + i) * JC, JC) == j,
+                              art_vals, wcnt, lane, wave, cnt)
+    __syncthreads();
+    ANCSH_SORT_VOTE_COLUMNS(art_vals, npow2, cnt)          // ends on a barrier: sst is visible too
+    __shared__ double smed[6];
+    if (threadIdx.x < 6) {
+        ANCSH_VOTE_MEDIAN(med, art_vals, npow2, cnt, threadIdx.x)
+        smed[threadIdx.x] = med;                           // 0..2 axis, 3..5 pivot
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s2 = sst[0];
+        const double *r = rec + 13, s0 = r[9], *t0 = r + 10;     // part 0's nonlinear pose
+        double pp[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pp[k] = s0 * (smed[3 + k] * s2 + sst[1 + k]);
+        double *o = ab + j * 12;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double *rk = r + 3 * k;
+            o[6 + k] = poisoned ? NAN : ((pp[0] * rk[0] + pp[1] * rk[1]) + pp[2] * rk[2]) + t0[k];
+            o[9 + k] = poisoned ? NAN : (smed[0] * rk[0] + smed[1] * rk[1]) + smed[2] * rk[2];
+        }
+        if (joint_nocs) {
+            double *q = joint_nocs + ((size_t)b * (K - 1) + (j - 1)) * 6;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { q[k] = smed[3 + k]; q[3 + k] = smed[k]; }
+        }
+        if (st0 && j == 1)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) st0[(size_t)b * 4 + k] = sst[k];
     }
 }
 
@@ -337,4 +327,27 @@ extern "C" int ancsh_joint_params(int b, int n, int K, int gocs_channels, int ax
     hipLaunchKernelGGL(joint_params_kernel, dim3(b, K + K - 1), dim3(256), lds, (hipStream_t)stream, n, K, gocs_channels, axis_mean ? 1 : 0,
                        gocs, nocs, mask, heatmap, unitvec, joint_axis, joint_cls, st, joint);
     return check_launch("joint_params");
+}
+
+extern "C" int ancsh_articulation_rec(int b, int n, int K, int gocs_channels, int joint_channels, const float *gocs, const float *nocs,
+                                      const float *mask, const float *heatmap, const float *unitvec, const float *joint_axis,
+                                      const float *joint_index, const float *npcs_nocs, const float *npcs_mask, const double *record,
+                                      double *art, double *joint_nocs, double *st0, float *extent, void *stream) {
+    using namespace ancsh;
+    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 8, "articulation_rec: bad sizes b=%d n=%d K=%d (K <= 8)", b, n, K);
+    ANCSH_REQUIRE(gocs_channels == 3 || gocs_channels == 3 * K, "articulation_rec: gocs must have 3 or 3K = %d channels, got %d", 3 * K,
+                  gocs_channels);
+    ANCSH_REQUIRE(joint_channels >= 1 && joint_channels <= 8, "articulation_rec: joint_channels %d (1..8)", joint_channels);
+    ANCSH_REQUIRE(n <= ANCSH_ARTICULATION_MAX_N, "articulation_rec: n %d too large for the LDS-resident medians (<= %d)", n,
+                  ANCSH_ARTICULATION_MAX_N);
+    if (b == 0) return ANCSH_OK;
+    ANCSH_REQUIRE(gocs && nocs && mask && heatmap && unitvec && joint_axis && joint_index && npcs_nocs && npcs_mask && record && art,
+                  "articulation_rec: null pointer");
+    int npow2 = 1;
+    while (npow2 < n) npow2 <<= 1;
+    const size_t lds = K > 1 ? (size_t)6 * npow2 * sizeof(float) : 0;
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)articulation_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(articulation_kernel, dim3(b, K), dim3(256), lds, (hipStream_t)stream, n, K, gocs_channels, joint_channels, gocs, nocs,
+                       mask, heatmap, unitvec, joint_axis, joint_index, npcs_nocs, npcs_mask, record, art, joint_nocs, st0, extent);
+    return check_launch("articulation_rec");
 }

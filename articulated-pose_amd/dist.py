@@ -304,10 +304,20 @@ class ShardedPipeline(object):
     raw_capacity (rows PER RANK): the streaming entry -- submit() / retire() / stream_batches() of raw clouds, every rank iterating the
     same global batches.  The per-rank pipeline is then built with raw_capacity and keyed=True, and each rank submits its shard with
     cloud_base = lo, so a cloud is sampled and fitted as its global index whatever the world size (include/ancsh_hip.h,
-    ancsh_stream_key); its records are gathered on `dst` over the gloo control group (the default group init_groups creates)."""
+    ancsh_stream_key); its records are gathered on `dst` over the gloo control group (the default group init_groups creates).
+    articulation=True (with raw_capacity only): the stream also yields the (n_valid, K, 12) articulation blocks, packed with the records
+    into the same gather; step() / records() over RCCL do not carry them."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
-                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, **pipeline_kw):
+                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, **pipeline_kw):
+        # articulation (raw streams only): every rank's pipeline appends the (n, K, 12) articulation block, and retire() gathers it with the
+        # records in the SAME gather -- one (n_max, K, 38) float64 row per rank, split on dst.  step() / records() (the RCCL path) do not
+        # carry it.
+        if articulation and raw_capacity is None:
+            raise ValueError("articulation=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
+        self.articulation = bool(articulation)
+        if self.articulation:
+            pipeline_kw.update(articulation=True)
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size() if self.distributed else 1
         self.rank = dist.get_rank() if self.distributed else 0
@@ -463,53 +473,66 @@ class ShardedPipeline(object):
         self._stream.append((tag, seed, len(clouds), e > s))
         self._stream_submitted += 1
 
-    def retire(self, flags=False):
+    def retire(self, flags=False, articulation=False):
         """Wait for the oldest global batch and gather its records on dst (every rank calls this): dst -> (tag, seed, record
         (n_valid, K, 26) float64 in global cloud order), the other ranks -> (tag, seed, None).  flags=True: + the range-guard flag
         words (n_valid,) int32 on dst (None elsewhere).  The gather is one fixed-size (n_max, K, 26) float64 dist.gather over the
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
+        articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
+        the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows.
         World 1: the local pipeline's retire()."""
+        if articulation and not self.articulation:
+            raise RuntimeError("retire(articulation=True) needs ShardedPipeline(..., articulation=True)")
         if self.world == 1:
-            return self.pipe.retire(flags)
+            return self.pipe.retire(flags, True) if articulation else self.pipe.retire(flags)
         if not self._stream:
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        rec = np.zeros((self.n_max, self.K, 26), np.float64)
+        width = 38 if self.articulation else 26         # [record (26) | articulation block (12)]: one gather either way
+        rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
         if here:
-            got = self.pipe.retire(flags)
-            rec[:e - s] = got[2]
+            got = self.pipe.retire(flags, True) if self.articulation else self.pipe.retire(flags)
+            rec[:e - s, :, :26] = got[2]
+            if self.articulation:
+                rec[:e - s, :, 26:] = got[-1]
             if flags:
                 words[:e - s] = got[3]
         on_dst = self.rank == self.dst
         if self._stream_bufs is None and on_dst:
-            self._stream_bufs = ([torch.empty((self.n_max, self.K, 26), dtype=torch.float64) for _ in range(self.world)],
+            self._stream_bufs = ([torch.empty((self.n_max, self.K, width), dtype=torch.float64) for _ in range(self.world)],
                                  [torch.empty((self.n_max,), dtype=torch.int32) for _ in range(self.world)])
         bufs = self._stream_bufs if on_dst else (None, None)
         dist.gather(torch.from_numpy(rec), bufs[0], dst=self.dst)
         if flags:
             dist.gather(torch.from_numpy(words), bufs[1], dst=self.dst)
         if not on_dst:
-            return (tag, seed, None, None) if flags else (tag, seed, None)
+            out = (tag, seed, None, None) if flags else (tag, seed, None)
+            return out + (None,) if articulation else out
         cut = [self.shard_of(n_valid, r) for r in range(self.world)]
-        record = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
-        if not flags:
-            return tag, seed, record
-        return tag, seed, record, np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+        packed = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+        record = np.ascontiguousarray(packed[:, :, :26])
+        out = (tag, seed, record)
+        if flags:
+            out += (np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0),)
+        return out + (np.ascontiguousarray(packed[:, :, 26:]),) if articulation else out
 
-    def stream_batches(self, batches, flags=False):
+    def stream_batches(self, batches, flags=False, articulation=False):
         """Generator over submit / retire of GLOBAL batches (every rank iterates the same batches): batches yields (clouds, norm_factors)
         or (clouds, norm_factors, tag) (tag defaults to the batch's index); up to len(slots) batches stay in flight; yields (tag, seed,
         record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
         ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
-        seed, lm_schedule).  World 1 (or no process group): the local pipeline's stream_batches."""
+        seed, lm_schedule).  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order (see retire()).  World 1
+        (or no process group): the local pipeline's stream_batches."""
+        if articulation and not self.articulation:
+            raise RuntimeError("stream_batches(articulation=True) needs ShardedPipeline(..., articulation=True)")
         if self.world == 1:
-            yield from self.pipe.stream_batches(batches, flags)
+            yield from (self.pipe.stream_batches(batches, flags, True) if articulation else self.pipe.stream_batches(batches, flags))
             return
         for k, item in enumerate(batches):
             if len(self._stream) == len(self.pipe.slots):
-                yield self.retire(flags)
+                yield self.retire(flags, articulation)
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._stream:
-            yield self.retire(flags)
+            yield self.retire(flags, articulation)

@@ -64,7 +64,7 @@ def f16x2_weight_violations(nets):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -96,6 +96,9 @@ class _Slot(object):
             if range_guard:
                 self.h_flags = torch.zeros((B,), dtype=torch.int32).pin_memory()
                 self.h_record32 = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
+            # articulation: the pinned (B, K, 12) block, copied right behind the record (and the f32 graph's, for flagged clouds)
+            self.h_art = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation else None
+            self.h_art32 = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation and range_guard else None
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
             self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[lead:lead + B + 1],
                                                                    hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
@@ -142,8 +145,20 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False):
+                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False):
         self.K, self.B, self.N = num_parts, batch_size, num_points
+        # articulation: the captured step ends with one more launch (ancsh_articulation_rec) that turns the networks' heads and the pose
+        # record into the (B, K, 12) block of part boxes and camera-space joints (pose.joint_params.articulation_batch): out["articulation"],
+        # and retire(articulation=True) / stream_batches(articulation=True) when streaming.  It reads the networks' own outputs
+        # (couple=True) and keeps its joint medians in LDS (num_points <= ARTICULATION_MAX_N).
+        self.articulation = bool(articulation)
+        if self.articulation:
+            from .pose.joint_params import ARTICULATION_MAX_N
+            if not couple:
+                raise ValueError("articulation=True reads the networks' heads: it needs couple=True")
+            if not 1 <= int(num_points) <= ARTICULATION_MAX_N:
+                raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
+                                 % (ARTICULATION_MAX_N, num_points))
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls) per batch, padding included
         if raw_capacity is not None:
@@ -194,7 +209,7 @@ class AncshPipeline(object):
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed)
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation)
                       for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
@@ -259,6 +274,9 @@ class AncshPipeline(object):
         sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
                                 key_dev=key_dev)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
+        if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
+            from .pose.joint_params import articulation_batch
+            out["articulation"] = articulation_batch(a, n, sol["record"])
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
         return out
@@ -304,7 +322,8 @@ class AncshPipeline(object):
     def step(self):
         """Issue the next batch (asynchronous).  Returns (slot, outputs); outputs are valid once slot.stream is synchronised -- and
         only until the slot's NEXT step: a captured step owns its memory pool, so while a replay is in flight an output buffer may hold
-        another tensor of the step (the pose record shares its block with the farthest-point indices, which the replay writes first).
+        another tensor of the step (the pose record shares its block with the farthest-point indices, which the replay writes first; the
+        same holds for out["articulation"], the (B, K, 12) block of articulation=True).
         Whatever the caller enqueued on ITS current stream before calling step() (a clone or a gather of the slot's previous outputs) is
         ordered before the new batch: the slot's stream waits for that stream here.  A consumer on any other stream is the caller's to order."""
         sl = self.slots[self._next]
@@ -389,6 +408,8 @@ class AncshPipeline(object):
                 sl.out = self._run(sl)
             # right behind the replay on the same stream: the next replay's pool reuses the record's block (see step())
             sl.h_record.copy_(sl.out["record"], non_blocking=True)
+            if self.articulation:
+                sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
             if self.range_guard:
                 sl.h_flags.copy_(sl.flags, non_blocking=True)
             sl.d2h_done.record(sl.stream)
@@ -396,35 +417,46 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self, flags=False):
+    def retire(self, flags=False, articulation=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
-        without the guard)."""
+        without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
+        block as the last element (flagged clouds: the f32 graph's rows, like their records)."""
+        if articulation and not self.articulation:
+            raise RuntimeError("retire(articulation=True) needs AncshPipeline(..., articulation=True)")
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
         record = sl.h_record[:n_valid].numpy().copy()
+        art = sl.h_art[:n_valid].numpy().copy() if articulation else None
         words = sl.h_flags[:n_valid].numpy().copy() if self.range_guard else np.zeros((n_valid,), np.int32)
         hit = np.flatnonzero(words)
         if hit.size:
             self.rerun_f32(sl)
             with torch.cuda.stream(sl.stream):
                 sl.h_record32.copy_(sl.out32["record"], non_blocking=True)
+                if self.articulation:
+                    sl.h_art32.copy_(sl.out32["articulation"], non_blocking=True)
             sl.stream.synchronize()
             record[hit] = sl.h_record32.numpy()[hit]
+            if articulation:
+                art[hit] = sl.h_art32.numpy()[hit]
             self.f32_reruns += 1
-        return (tag, seed, record, words) if flags else (tag, seed, record)
+        out = (tag, seed, record, words) if flags else (tag, seed, record)
+        return out + (art,) if articulation else out
 
-    def stream_batches(self, batches, flags=False):
+    def stream_batches(self, batches, flags=False, articulation=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
         batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
-        flag words, see retire())."""
+        flag words; articulation=True: + the (n_valid, K, 12) articulation block, last -- see retire())."""
+        if articulation and not self.articulation:
+            raise RuntimeError("stream_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
         for k, item in enumerate(batches):
             if len(self._inflight) == len(self.slots):
-                yield self.retire(flags)
+                yield self.retire(flags, articulation)
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._inflight:
-            yield self.retire(flags)
+            yield self.retire(flags, articulation)

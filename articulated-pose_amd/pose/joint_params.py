@@ -74,3 +74,34 @@ def joint_errors(pred, gt):
     """(angle_err, dist_err), each (B, K-1): axis_diff_degree and dist_between_3d_lines of the camera-space joints (:244-256)."""
     return (axis_diff_degree_batch(gt["joint_axis_cam"], pred["joint_axis_cam"]),
             dist_between_3d_lines_batch(gt["joint_pt_cam"], gt["joint_axis_cam"], pred["joint_pt_cam"], pred["joint_axis_cam"]))
+
+
+ARTICULATION_MAX_N = 4096       # include/ancsh_hip.h, ANCSH_ARTICULATION_MAX_N: the medians' six LDS columns of the next power of two of N
+
+
+def articulation_batch(ancsh_pred, npcs_pred, record, debug=False):
+    """The articulation block of a batch in ONE launch (ancsh_articulation_rec, csrc/metrics.hip): ancsh_pred / npcs_pred = the two
+    networks' output dicts (device tensors, (B, N, .) float32: the ANCSH gocs / nocs / W / heatmap / unitvec / joint_axis / index heads and
+    the NPCS nocs / W), record = the (B, K, 26) float64 pose record (the nonlinear R | s | t in columns 13..25).  Returns art (B, K, 12)
+    float64 on the device, row j = [box size (3) | box centre (3) | joint j pivot (3) | joint j axis (3)] in camera space (row 0: NaN
+    joint columns; a poisoned record: an all-NaN block; include/ancsh_hip.h).  debug=True: (art, dict(joint_nocs (B, K-1, 6), st0 (B, 4),
+    extent (B, K, 3) float32)) -- bit-equal to ancsh_joint_params' joint / st row 0 and ancsh_part_extents' scale_pred.
+    No host synchronisation and no allocation beyond the outputs: the captured streaming step calls it."""
+    dev = record.device
+    _lib.require_cuda(record)
+    g = _f32(ancsh_pred["gocs_per_point"], dev)
+    B, N, G = g.shape
+    K = record.shape[1]
+    idx = _f32(ancsh_pred["index_per_point"], dev)
+    if record.dtype != torch.float64 or tuple(record.shape) != (B, K, 26) or not record.is_contiguous():
+        raise ValueError("record must be a contiguous (B, K, 26) float64 tensor")
+    art = torch.empty((B, K, 12), dtype=torch.float64, device=dev)
+    dbg = dict(joint_nocs=torch.empty((B, max(K - 1, 0), 6), dtype=torch.float64, device=dev),
+               st0=torch.empty((B, 4), dtype=torch.float64, device=dev),
+               extent=torch.empty((B, K, 3), dtype=torch.float32, device=dev)) if debug else {}
+    _lib.call("ancsh_articulation_rec", B, N, K, G, idx.shape[2], _lib.ptr(g), _lib.ptr(_f32(ancsh_pred["nocs_per_point"], dev)),
+              _lib.ptr(_f32(ancsh_pred["W"], dev)), _lib.ptr(_f32(ancsh_pred["heatmap_per_point"], dev)),
+              _lib.ptr(_f32(ancsh_pred["unitvec_per_point"], dev)), _lib.ptr(_f32(ancsh_pred["joint_axis_per_point"], dev)), _lib.ptr(idx),
+              _lib.ptr(_f32(npcs_pred["nocs_per_point"], dev)), _lib.ptr(_f32(npcs_pred["W"], dev)), _lib.ptr(record), _lib.ptr(art),
+              _lib.ptr(dbg.get("joint_nocs") if K > 1 else None), _lib.ptr(dbg.get("st0")), _lib.ptr(dbg.get("extent")))
+    return (art, dbg) if debug else art

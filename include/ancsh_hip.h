@@ -652,6 +652,29 @@ int ancsh_joint_params(int b, int n, int K, int gocs_channels, int axis_mean, co
 int ancsh_part_extents(int b, int n, int K, int nocs_channels, const float *nocs, const float *mask, const float *P, int ldp,
                        const double *pose0, float *scale_pred, double *dynam, int *count, void *stream);
 
+/* Articulation block of a streamed batch, one launch after the pose fit and the record poison (ABI 11): the pred side of
+ * evaluation/compute_miou.py:196-222 (amodal boxes) and evaluation/eval_joint_params.py:143-220 (joints in camera space), fused.
+ * Inputs (b,n,.) float32 row-major, the two networks' heads:
+ *   ANCSH: gocs (gocs_channels = 3K or 3), nocs (3K) part NOCS, mask (K) = W, heatmap (1), unitvec (3), joint_axis (3), joint_index (joint_channels)
+ *     = index_per_point (joint class = its first argmax, np.argmax; joint j >= joint_channels has no points);
+ *   NPCS: npcs_nocs (3K), npcs_mask (K) = W;  record (b,K,26) float64: the pose record, nonlinear R_j 13..21 (row-major), s_j 22, t_j 23..25.
+ * art (b,K,12) float64, row j:
+ *   0..2   s_j * scale_pred_j, scale_pred_j = 2 max |npcs_nocs_j - 0.5| over the points whose npcs_mask first maximum is j  (:196-200, 214-217)
+ *   3..5   s_j R_j (1/2,1/2,1/2) + t_j: the centre of get_3d_bbox(scale, shift=1/2) (lib/d3_utils.py:8) in camera space  (:217-222)
+ *   6..8   (j >= 1) pivot R_0 (s_0 (p_j s2 + t2)) + t_0: p_j = per-channel median over joint class j of gocs + unitvec (1 - heatmap) 0.2,
+ *          (s2, t2) = part 0's similarity global -> part NOCS (ancsh_joint_params' st row 0)     (eval_joint_params.py:143-187, 214-219)
+ *   9..11  (j >= 1) axis R_0 a_j: a_j = per-channel median of joint_axis over the same points, not normalised        (:176-187, 220)
+ *   row 0's 6..11 NaN.  An empty part / joint class: NaN in its own columns; a NaN in part 0's nonlinear pose (a poisoned record):
+ *   the cloud's whole block NaN.  K = 1: box columns only.
+ * Optional (NULL to skip), bit-equal to the offline kernels: joint_nocs (b,K-1,6) = ancsh_joint_params' joint, st0 (b,4) = its st row 0
+ * (NaN for K = 1), extent (b,K,3) float32 = ancsh_part_extents' scale_pred.  K <= 8, n <= ANCSH_ARTICULATION_MAX_N (LDS-resident medians:
+ * 6 columns of the next power of two of n floats). */
+#define ANCSH_ARTICULATION_MAX_N 4096
+int ancsh_articulation_rec(int b, int n, int K, int gocs_channels, int joint_channels, const float *gocs, const float *nocs,
+                           const float *mask, const float *heatmap, const float *unitvec, const float *joint_axis,
+                           const float *joint_index, const float *npcs_nocs, const float *npcs_mask, const double *record,
+                           double *art, double *joint_nocs, double *st0, float *extent, void *stream);
+
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 
 /* One launch for a ragged batch: cloud b owns raw rows [offsets[b], offsets[b+1]) of `rows` (nchan floats each:

@@ -2,11 +2,12 @@
 fit + record D2H per batch) against load_inputs + step() on the same clouds, at configs[2]'s shape (K = 3, 32 x 1024, 10000 / 200
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
-    python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K]
+    python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
 line then also carries the rerun count, the latency of the batches that reran and the device memory the streaming pipeline holds.
+--articulation streams with AncshPipeline(articulation=True) (the record plus the (n, K, 12) articulation block per cloud).
 """
 import argparse
 import json
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--arithmetic", choices=("f32", "f16x2"), default=None)
     ap.add_argument("--range-guard", action="store_true")
     ap.add_argument("--overflow-every", type=int, default=0)
+    ap.add_argument("--articulation", action="store_true", help="stream with AncshPipeline(articulation=True) and retire the blocks too")
     args = ap.parse_args()
     if args.range_guard and args.arithmetic != "f16x2":
         ap.error("--range-guard needs --arithmetic f16x2")
@@ -54,7 +56,7 @@ def main():
     torch.cuda.synchronize()
     mem0 = torch.cuda.mem_get_info(dev)[0]
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
-                         range_guard=args.range_guard).prepare()
+                         range_guard=args.range_guard, articulation=args.articulation).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
@@ -68,9 +70,11 @@ def main():
             t_sub[it[2]] = time.perf_counter()
             yield it
     t0 = time.perf_counter()
-    n_out, rerun_lat = 0, []
+    n_out, rerun_lat, n_blocks = 0, [], 0
     reruns0 = pipe.f32_reruns
-    for tag, seed, rec in pipe.stream_batches(timed(work)):
+    for item in pipe.stream_batches(timed(work), articulation=args.articulation):
+        tag, seed, rec = item[:3]
+        n_blocks += item[-1].shape[0] if args.articulation else 0
         lat.append(time.perf_counter() - t_sub[tag])
         if pipe.f32_reruns != reruns0:
             rerun_lat.append(lat[-1])
@@ -123,6 +127,8 @@ def main():
                      "f32_reruns": pipe_reruns, "paired": pipe_paired, "stream_device_bytes": int(pipe_bytes),
                      "rerun_batch_latency_ms": [round(1e3 * x, 2) for x in rerun_lat[:8]],
                      "batch_latency_ms_median": round(1e3 * float(np.median(lat)), 2)})
+    if args.articulation:
+        line.update({"articulation": True, "blocks_out": n_blocks})
     print(json.dumps(line))
 
 
