@@ -104,6 +104,7 @@ SIGNATURES = {
                                      _vp, _c_int, _vp, _c_float, _vp],
     "ancsh_ransac_joint_rec_dkey": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
                                    + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp],
+    "ancsh_raw_point_labels": [_c_int] * 5 + [_vp, _c_long] + [_vp] * 8 + [_vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

@@ -195,6 +195,127 @@ __global__ __launch_bounds__(256) void fp_concat_kernel(int m, int c2, int n, co
     }
 }
 
+// ---- per-raw-point labels of a streamed batch (include/ancsh_hip.h, ancsh_raw_point_labels) ------------------------------------
+// A workgroup takes tiles of RPL_ROWS raw rows of one cloud (grid-stride over the cloud's tiles: the grid is sized from capacity and
+// nclouds only, every size comes from device offsets).  The cloud's sampled points sit in LDS as float4 (one NN_CHUNK at a time);
+// each group of NN_SEG lanes scans every NN_SEG-th candidate for RPL_Q queries at once, so one ds_read_b128 serves RPL_Q distances.
+// The in-lane cascade and the butterfly merge are three_nn_kernel's, hence the same lexicographic (distance, index) top three; the
+// weights and each interpolated channel are three_nn_kernel's / three_interpolate_kernel's arithmetic, channel by channel.
+constexpr int RPL_Q = 4;                                   // queries per lane
+constexpr int RPL_ROWS = (256 / NN_SEG) * RPL_Q;           // raw rows per tile: 128
+
+__global__ __launch_bounds__(256) void raw_point_labels_kernel(int num_points, int K, int G, int nchan, const float *__restrict__ rows,
+                                                               long capacity, const int *__restrict__ offsets,
+                                                               const float *__restrict__ norm_factor, const float *__restrict__ P,
+                                                               const float *__restrict__ W, const float *__restrict__ nocs,
+                                                               const float *__restrict__ gocs, int *__restrict__ labels,
+                                                               float *__restrict__ values) {
+    __shared__ float4 known[NN_CHUNK];
+    const int b = blockIdx.y;
+    const long r0 = offsets[b], r1 = offsets[b + 1];
+    if (r0 < 0 || r1 <= r0 || r1 > capacity) return;     // empty or outside the rows buffer (the host refuses both): rows untouched
+    const int n_raw = (int)(r1 - r0);
+    const int ntiles = (n_raw + RPL_ROWS - 1) / RPL_ROWS;
+    if ((int)blockIdx.x >= ntiles) return;
+    const float nf = norm_factor[b];
+    const int seg = threadIdx.x & (NN_SEG - 1);
+    const int grp = threadIdx.x / NN_SEG;
+    const float *pk = P + (size_t)b * num_points * 3;
+    const bool one_chunk = num_points <= NN_CHUNK;
+    if (one_chunk) {                                       // staged once for every tile of the workgroup
+        for (int e = threadIdx.x; e < num_points; e += 256)
+            known[e] = make_float4(pk[e * 3], pk[e * 3 + 1], pk[e * 3 + 2], 0.f);
+        __syncthreads();
+    }
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        float qx[RPL_Q], qy[RPL_Q], qz[RPL_Q];
+        Top3 t[RPL_Q];
+#pragma unroll
+        for (int u = 0; u < RPL_Q; ++u) {
+            int i = tile * RPL_ROWS + grp + u * (256 / NN_SEG);
+            i = i < n_raw ? i : n_raw - 1;                 // a dead query scans a live row's neighbours and writes nothing
+            const float *s = rows + (size_t)(r0 + i) * nchan;
+            qx[u] = s[0] * nf; qy[u] = s[1] * nf; qz[u] = s[2] * nf;     // the streaming sampler's products (input.hip)
+            t[u] = {INFINITY, INFINITY, INFINITY, 0x7fffffff, 0x7fffffff, 0x7fffffff};
+        }
+        for (int base = 0; base < num_points; base += NN_CHUNK) {
+            const int cnt = (num_points - base) < NN_CHUNK ? (num_points - base) : NN_CHUNK;
+            if (!one_chunk) {
+                __syncthreads();
+                for (int e = threadIdx.x; e < cnt; e += 256) {
+                    const float *s = pk + (size_t)(base + e) * 3;
+                    known[e] = make_float4(s[0], s[1], s[2], 0.f);
+                }
+                __syncthreads();
+            }
+            for (int k = seg; k < cnt; k += NN_SEG) {
+                const float4 c = known[k];
+                const int kk = base + k;
+#pragma unroll
+                for (int u = 0; u < RPL_Q; ++u) {
+                    const float dx = c.x - qx[u], dy = c.y - qy[u], dz = c.z - qz[u];
+                    const float d = dx * dx + dy * dy + dz * dz;       // three_nn_kernel's ((dx*dx + dy*dy) + dz*dz)
+                    if (d < t[u].d1) { t[u].d3 = t[u].d2; t[u].i3 = t[u].i2; t[u].d2 = t[u].d1; t[u].i2 = t[u].i1; t[u].d1 = d; t[u].i1 = kk; }
+                    else if (d < t[u].d2) { t[u].d3 = t[u].d2; t[u].i3 = t[u].i2; t[u].d2 = d; t[u].i2 = kk; }
+                    else if (d < t[u].d3) { t[u].d3 = d; t[u].i3 = kk; }
+                }
+            }
+        }
+        // merge the NN_SEG partial lists of each query: afterwards every lane of the group holds the same top three
+#pragma unroll
+        for (int u = 0; u < RPL_Q; ++u) {
+#pragma unroll
+            for (int o = 1; o < NN_SEG; o <<= 1) {
+                const float e1 = __shfl_xor(t[u].d1, o, 64), e2 = __shfl_xor(t[u].d2, o, 64), e3 = __shfl_xor(t[u].d3, o, 64);
+                const int f1 = __shfl_xor(t[u].i1, o, 64), f2 = __shfl_xor(t[u].i2, o, 64), f3 = __shfl_xor(t[u].i3, o, 64);
+                nn_insert(t[u], e1, f1);
+                nn_insert(t[u], e2, f2);
+                nn_insert(t[u], e3, f3);
+            }
+        }
+        // epilogue: lane seg of the group finishes query seg (RPL_Q <= NN_SEG)
+#pragma unroll
+        for (int u = 0; u < RPL_Q; ++u) {
+            const int i = tile * RPL_ROWS + grp + u * (256 / NN_SEG);
+            if (seg != u || i >= n_raw) continue;
+            const int a1 = t[u].i1 == 0x7fffffff ? 0 : t[u].i1, a2 = t[u].i2 == 0x7fffffff ? 0 : t[u].i2,
+                      a3 = t[u].i3 == 0x7fffffff ? 0 : t[u].i3;
+            const float d0 = fmaxf(t[u].d1, 1e-10f), d1 = fmaxf(t[u].d2, 1e-10f), d2 = fmaxf(t[u].d3, 1e-10f);
+            const float v0 = __fdiv_rn(1.0f, d0), v1 = __fdiv_rn(1.0f, d1), v2 = __fdiv_rn(1.0f, d2);
+            const float norm = (v0 + v1) + v2;
+            const float w1 = __fdiv_rn(v0, norm), w2 = __fdiv_rn(v1, norm), w3 = __fdiv_rn(v2, norm);
+            // W: every channel, first maximum (np.argmax); any non-finite channel or query -> label -1
+            const float *pw = W + (size_t)b * num_points * K;
+            bool ok = isfinite(qx[u]) && isfinite(qy[u]) && isfinite(qz[u]);
+            int lab = 0;
+            float best = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float v = pw[(size_t)a1 * K + k] * w1 + pw[(size_t)a2 * K + k] * w2 + pw[(size_t)a3 * K + k] * w3;
+                ok = ok && isfinite(v);
+                if (k == 0 || v > best) { best = v; lab = k; }
+            }
+            const size_t row = (size_t)(r0 + i);
+            float *out = values + row * 7;
+            if (!ok) {
+                labels[row] = -1;
+                for (int c = 0; c < 7; ++c) out[c] = NAN;
+                continue;
+            }
+            labels[row] = lab;
+            out[0] = best;
+            const float *pn = nocs + (size_t)b * num_points * 3 * K;
+            const float *pg = gocs + (size_t)b * num_points * G;
+            const int gc = G == 3 ? 0 : 3 * lab;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int l = 3 * lab + c;
+                out[1 + c] = pn[(size_t)a1 * 3 * K + l] * w1 + pn[(size_t)a2 * 3 * K + l] * w2 + pn[(size_t)a3 * 3 * K + l] * w3;
+                out[4 + c] = pg[(size_t)a1 * G + gc + c] * w1 + pg[(size_t)a2 * G + gc + c] * w2 + pg[(size_t)a3 * G + gc + c] * w3;
+            }
+        }
+    }
+}
+
 static int launch_interp(int b, int m, int c, int n, const float *points, const int *idx, const float *weight,
                          float *out, int out_ld, int out_off, hipStream_t st) {
     ANCSH_REQUIRE(b >= 0 && m > 0 && c >= 0 && n >= 0, "ThreeInterpolate expects (b,m,c) points shape");
@@ -294,4 +415,26 @@ extern "C" int ancsh_fp_interpolate_concat_ex(int b, int m, int c2, int n, const
 extern "C" int ancsh_three_interpolate_ex(int b, int m, int c, int n, const float *points, const int *idx,
                                           const float *weight, float *out, int out_ld, int out_off, void *stream) {
     return launch_interp(b, m, c, n, points, idx, weight, out, out_ld, out_off, (hipStream_t)stream);
+}
+
+extern "C" int ancsh_raw_point_labels(int nclouds, int num_points, int K, int gocs_channels, int nchan, const float *rows, long capacity,
+                                      const int *offsets, const float *norm_factor, const float *P, const float *W, const float *nocs,
+                                      const float *gocs, int *labels, float *values, void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0 && num_points > 0 && num_points < (1 << 24), "raw_point_labels: bad shape nclouds=%d num_points=%d", nclouds,
+                  num_points);
+    ANCSH_REQUIRE(nclouds <= 65535, "raw_point_labels: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(K >= 1 && K <= 8, "raw_point_labels: K=%d must be in [1, 8]", K);
+    ANCSH_REQUIRE(gocs_channels == 3 || gocs_channels == 3 * K, "raw_point_labels: gocs_channels=%d must be 3 or 3K=%d", gocs_channels, 3 * K);
+    ANCSH_REQUIRE(nchan >= 3, "raw_point_labels: rows need the 3 coordinate channels (nchan=%d)", nchan);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "raw_point_labels: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(rows && offsets && norm_factor && P && W && nocs && gocs && labels && values, "raw_point_labels: null pointer");
+    if (nclouds == 0 || capacity == 0) return ANCSH_OK;
+    // x: tiles of the largest cloud the rows buffer admits, capped so that small clouds do not leave most workgroups idle (a larger
+    // cloud loops over its tiles); fixed by (capacity, nclouds), so one captured graph serves every batch
+    long gx = (capacity + RPL_ROWS - 1) / RPL_ROWS;
+    const long cap = (4096 + nclouds - 1) / nclouds;
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(raw_point_labels_kernel, dim3((unsigned)gx, nclouds), dim3(256), 0, (hipStream_t)stream, num_points, K,
+                       gocs_channels, nchan, rows, capacity, offsets, norm_factor, P, W, nocs, gocs, labels, values);
+    return check_launch("raw_point_labels");
 }

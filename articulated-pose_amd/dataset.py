@@ -170,3 +170,49 @@ def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", re
     if return_perm:
         out["perm"] = perm
     return out
+
+
+DENSE_VALUES = 7        # per raw row: [W_label | part NOCS (3) | NAOCS (3)] (include/ancsh_hip.h, ancsh_raw_point_labels)
+
+
+def raw_point_labels(raw_rows, offsets, norm_factors, P, npcs_pred, ancsh_pred, out=None):
+    """Part label and head values of every RAW row of a streamed batch (ancsh_raw_point_labels, one launch): the FP module's 3-NN
+    inverse-distance upsampling (pointnet_util.py:219-229) from each cloud's sampled points P to its raw rows.
+    raw_rows (capacity, >= 3) float32 [x y z ...], offsets (B+1,) int32 (cloud b owns rows [offsets[b], offsets[b+1])), norm_factors (B,)
+    float32, P (B, N, 3) the sampled points (raw xyz * norm factor), npcs_pred / ancsh_pred the two networks' output dicts (the NPCS W and
+    nocs_per_point heads, the ANCSH gocs_per_point head).  -> (labels (capacity,) int32, values (capacity, 7) float32) device tensors:
+    labels = the first argmax of the interpolated W (-1 for a non-finite point or W), values = [W_label | nocs of the label's part | gocs of
+    the label's part (or the 3-channel gocs)], NaN with label -1.  Rows beyond offsets[B] are left as `out` holds them (freshly allocated:
+    -1 / NaN).  out = (labels, values): preallocated outputs (the captured streaming step passes slot-owned buffers); no host sync."""
+    dev = P.device if torch.is_tensor(P) else torch.device("cuda:0")
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+
+    def f32(a):
+        return torch.as_tensor(a).to(dev, torch.float32).contiguous()
+    rows, P = f32(raw_rows), f32(P)
+    off = torch.as_tensor(offsets).to(dev, torch.int32).contiguous()
+    nf = f32(norm_factors).reshape(-1)
+    if "gocs_per_point" not in ancsh_pred:
+        raise ValueError("raw_point_labels reads the ANCSH network's gocs_per_point head (mixed_pred weights)")
+    W, nocs, gocs = f32(npcs_pred["W"]), f32(npcs_pred["nocs_per_point"]), f32(ancsh_pred["gocs_per_point"])
+    if P.dim() != 3 or P.shape[2] != 3 or rows.dim() != 2:
+        raise ValueError("P must be (B, N, 3) and raw_rows (capacity, channels)")
+    B, N = P.shape[:2]
+    K = W.shape[2] if W.dim() == 3 else 0
+    if tuple(W.shape) != (B, N, K) or tuple(nocs.shape) != (B, N, 3 * K) or gocs.dim() != 3 or tuple(gocs.shape[:2]) != (B, N):
+        raise ValueError("heads must be W (B, N, K), nocs_per_point (B, N, 3K) and gocs_per_point (B, N, 3 or 3K) for P (B, N, 3)")
+    if tuple(off.shape) != (B + 1,) or tuple(nf.shape) != (B,):
+        raise ValueError("offsets must be (B+1,) and norm_factors (B,) for %d clouds" % B)
+    cap = rows.shape[0]
+    if out is None:
+        labels = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        values = torch.full((cap, DENSE_VALUES), float("nan"), dtype=torch.float32, device=dev)
+    else:
+        labels, values = out
+        if labels.dtype != torch.int32 or values.dtype != torch.float32 or tuple(labels.shape) != (cap,) or \
+                tuple(values.shape) != (cap, DENSE_VALUES) or not (labels.is_contiguous() and values.is_contiguous()):
+            raise ValueError("out must be contiguous (labels (%d,) int32, values (%d, %d) float32)" % (cap, cap, DENSE_VALUES))
+    _lib.call("ancsh_raw_point_labels", B, N, K, int(gocs.shape[2]), int(rows.shape[1]), _lib.ptr(rows), cap, _lib.ptr(off),
+              _lib.ptr(nf), _lib.ptr(P), _lib.ptr(W), _lib.ptr(nocs), _lib.ptr(gocs), _lib.ptr(labels), _lib.ptr(values))
+    return labels, values

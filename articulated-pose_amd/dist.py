@@ -306,10 +306,12 @@ class ShardedPipeline(object):
     cloud_base = lo, so a cloud is sampled and fitted as its global index whatever the world size (include/ancsh_hip.h,
     ancsh_stream_key); its records are gathered on `dst` over the gloo control group (the default group init_groups creates).
     articulation=True (with raw_capacity only): the stream also yields the (n_valid, K, 12) articulation blocks, packed with the records
-    into the same gather; step() / records() over RCCL do not carry them."""
+    into the same gather; step() / records() over RCCL do not carry them.
+    dense=True (with raw_capacity only): the stream also yields every raw row's (labels, values, offsets) (AncshPipeline(dense=True)),
+    gathered on dst in global cloud order by one more padded gather per batch."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
-                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, **pipeline_kw):
+                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, **pipeline_kw):
         # articulation (raw streams only): every rank's pipeline appends the (n, K, 12) articulation block, and retire() gathers it with the
         # records in the SAME gather -- one (n_max, K, 38) float64 row per rank, split on dst.  step() / records() (the RCCL path) do not
         # carry it.
@@ -318,6 +320,11 @@ class ShardedPipeline(object):
         self.articulation = bool(articulation)
         if self.articulation:
             pipeline_kw.update(articulation=True)
+        if dense and raw_capacity is None:
+            raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
+        self.dense = bool(dense)
+        if self.dense:
+            pipeline_kw.update(dense=True)
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size() if self.distributed else 1
         self.rank = dist.get_rank() if self.distributed else 0
@@ -343,7 +350,7 @@ class ShardedPipeline(object):
         # flight, so a slot's record is gathered right before the slot is reused (its batch finished long ago); flush() drains
         self.lagged = self.gatherer is not None and self.gatherer.host_staged
         self._pending, self._pad = [], {}
-        self._stream = collections.deque()       # streaming: (tag, seed, n_valid, submitted here) of unretired global batches, oldest first
+        self._stream = collections.deque()       # streaming: (tag, seed, n_valid, submitted here, raw rows per cloud) of unretired global batches
         self._stream_submitted = 0
         self._stream_bufs = None
 
@@ -470,33 +477,70 @@ class ShardedPipeline(object):
         s, e = self.shard_of(len(clouds))
         if e > s:
             self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo)
-        self._stream.append((tag, seed, len(clouds), e > s))
+        self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
 
-    def retire(self, flags=False, articulation=False):
+    def _local_kw(self, articulation, dense):
+        """retire / stream_batches keywords for the per-rank pipeline: only the blocks asked for (a stand-in need not know the others)."""
+        kw = {}
+        if articulation:
+            kw["articulation"] = True
+        if dense:
+            kw["dense"] = True
+        return kw
+
+    def _gather_dense(self, got, sizes, n_valid):
+        """The raw rows of one global batch on dst: every rank pads its shard's rows to the largest shard's count (all ranks know every
+        shard's rows: they iterate the same batch) and sends [label | the 7 values' bits] int32 rows in ONE gather.  dst -> (labels (R,) int32,
+        values (R, 7) float32, offsets (n_valid+1,) int64) in global cloud order; other ranks -> None."""
+        from .dataset import DENSE_VALUES
+        cut = [self.shard_of(n_valid, r) for r in range(self.world)]
+        counts = [int(sizes[a:b].sum()) for a, b in cut]
+        width = 1 + DENSE_VALUES
+        buf = np.zeros((max(1, max(counts)), width), np.int32)          # int32 words: the values' bits travel untouched
+        if got is not None:
+            labels, values, _ = got
+            buf[:labels.shape[0], 0] = labels
+            buf[:labels.shape[0], 1:] = values.view(np.int32)
+        on_dst = self.rank == self.dst
+        bufs = [torch.empty(buf.shape, dtype=torch.int32) for _ in range(self.world)] if on_dst else None
+        dist.gather(torch.from_numpy(buf), bufs, dst=self.dst)
+        if not on_dst:
+            return None
+        rows = np.concatenate([bufs[r].numpy()[:n] for r, n in enumerate(counts)], axis=0)
+        off = np.zeros(n_valid + 1, np.int64)
+        np.cumsum(sizes, out=off[1:])
+        return np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:]).view(np.float32), off
+
+    def retire(self, flags=False, articulation=False, dense=False):
         """Wait for the oldest global batch and gather its records on dst (every rank calls this): dst -> (tag, seed, record
         (n_valid, K, 26) float64 in global cloud order), the other ranks -> (tag, seed, None).  flags=True: + the range-guard flag
         words (n_valid,) int32 on dst (None elsewhere).  The gather is one fixed-size (n_max, K, 26) float64 dist.gather over the
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
         articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
         the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows.
+        dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
+        batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
         if articulation and not self.articulation:
             raise RuntimeError("retire(articulation=True) needs ShardedPipeline(..., articulation=True)")
+        if dense and not self.dense:
+            raise RuntimeError("retire(dense=True) needs ShardedPipeline(..., dense=True)")
         if self.world == 1:
-            return self.pipe.retire(flags, True) if articulation else self.pipe.retire(flags)
+            return self.pipe.retire(flags, **self._local_kw(articulation, dense))
         if not self._stream:
             raise RuntimeError("retire(): no batch in flight")
-        tag, seed, n_valid, here = self._stream.popleft()
+        tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
         width = 38 if self.articulation else 26         # [record (26) | articulation block (12)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
+        got = None
         if here:
-            got = self.pipe.retire(flags, True) if self.articulation else self.pipe.retire(flags)
+            got = self.pipe.retire(flags, **self._local_kw(self.articulation, self.dense))
             rec[:e - s, :, :26] = got[2]
             if self.articulation:
-                rec[:e - s, :, 26:] = got[-1]
+                rec[:e - s, :, 26:] = got[-2 if self.dense else -1]
             if flags:
                 words[:e - s] = got[3]
         on_dst = self.rank == self.dst
@@ -507,32 +551,38 @@ class ShardedPipeline(object):
         dist.gather(torch.from_numpy(rec), bufs[0], dst=self.dst)
         if flags:
             dist.gather(torch.from_numpy(words), bufs[1], dst=self.dst)
+        dn = self._gather_dense(got[-1] if got is not None else None, sizes, n_valid) if self.dense else None
         if not on_dst:
             out = (tag, seed, None, None) if flags else (tag, seed, None)
-            return out + (None,) if articulation else out
+            out = out + (None,) if articulation else out
+            return out + (None,) if dense else out
         cut = [self.shard_of(n_valid, r) for r in range(self.world)]
         packed = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
         record = np.ascontiguousarray(packed[:, :, :26])
         out = (tag, seed, record)
         if flags:
             out += (np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0),)
-        return out + (np.ascontiguousarray(packed[:, :, 26:]),) if articulation else out
+        out = out + (np.ascontiguousarray(packed[:, :, 26:]),) if articulation else out
+        return out + (dn,) if dense else out
 
-    def stream_batches(self, batches, flags=False, articulation=False):
+    def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """Generator over submit / retire of GLOBAL batches (every rank iterates the same batches): batches yields (clouds, norm_factors)
         or (clouds, norm_factors, tag) (tag defaults to the batch's index); up to len(slots) batches stay in flight; yields (tag, seed,
         record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
         ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
-        seed, lm_schedule).  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order (see retire()).  World 1
-        (or no process group): the local pipeline's stream_batches."""
+        seed, lm_schedule).  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
+        (labels, values, offsets) in global cloud order, last (see retire()).  World 1 (or no process group): the local pipeline's
+        stream_batches."""
         if articulation and not self.articulation:
             raise RuntimeError("stream_batches(articulation=True) needs ShardedPipeline(..., articulation=True)")
+        if dense and not self.dense:
+            raise RuntimeError("stream_batches(dense=True) needs ShardedPipeline(..., dense=True)")
         if self.world == 1:
-            yield from (self.pipe.stream_batches(batches, flags, True) if articulation else self.pipe.stream_batches(batches, flags))
+            yield from self.pipe.stream_batches(batches, flags, **self._local_kw(articulation, dense))
             return
         for k, item in enumerate(batches):
             if len(self._stream) == len(self.pipe.slots):
-                yield self.retire(flags, articulation)
+                yield self.retire(flags, articulation, dense)
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._stream:
-            yield self.retire(flags, articulation)
+            yield self.retire(flags, articulation, dense)

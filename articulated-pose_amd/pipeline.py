@@ -64,7 +64,7 @@ def f16x2_weight_violations(nets):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -99,6 +99,17 @@ class _Slot(object):
             # articulation: the pinned (B, K, 12) block, copied right behind the record (and the f32 graph's, for flagged clouds)
             self.h_art = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation else None
             self.h_art32 = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation and range_guard else None
+            # dense: the per-raw-row labels / values the captured step writes (slot-owned, outside the graph's pool, so a later replay
+            # never hands their memory to another tensor), the f32 graph's own pair (range guard), and their pinned copies
+            self.dense = self.dense32 = self.h_dense = self.h_dense32 = None
+            if dense:
+                from .dataset import DENSE_VALUES
+                pair = lambda **d: (torch.full((raw_capacity,), -1, dtype=torch.int32, **d),
+                                    torch.full((raw_capacity, DENSE_VALUES), float("nan"), dtype=torch.float32, **d))
+                pinned = lambda: tuple(t.pin_memory() for t in pair())
+                self.dense, self.h_dense = pair(device=device), pinned()
+                if range_guard:
+                    self.dense32, self.h_dense32 = pair(device=device), pinned()
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
             self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[lead:lead + B + 1],
                                                                    hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
@@ -145,7 +156,7 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False):
+                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False):
         self.K, self.B, self.N = num_parts, batch_size, num_points
         # articulation: the captured step ends with one more launch (ancsh_articulation_rec) that turns the networks' heads and the pose
         # record into the (B, K, 12) block of part boxes and camera-space joints (pose.joint_params.articulation_batch): out["articulation"],
@@ -174,6 +185,12 @@ class AncshPipeline(object):
         if keyed and raw_capacity is None:
             raise ValueError("keyed=True keys the streaming header: it needs raw_capacity")
         self.keyed = bool(keyed)
+        # dense (streaming only): the captured step ends with one more launch (ancsh_raw_point_labels) that carries the NPCS network's
+        # part label / probability / part NOCS and the ANCSH network's NAOCS from the sampled points to every raw row (3-NN inverse-distance
+        # weights, the FP module's rule) into slot-owned buffers; retire(dense=True) / stream_batches(dense=True) return them per batch
+        if dense and raw_capacity is None:
+            raise ValueError("dense=True labels the raw rows of a stream: it needs raw_capacity")
+        self.dense = bool(dense)
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
@@ -209,8 +226,8 @@ class AncshPipeline(object):
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation)
-                      for _ in range(max(1, slots))]
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
+                            self.dense) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -277,6 +294,10 @@ class AncshPipeline(object):
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
             out["articulation"] = articulation_batch(a, n, sol["record"])
+        if self.dense:                   # the last launch: every raw row of the slot's batch, into the slot's own (capacity, .) buffers
+            from .dataset import raw_point_labels
+            _, off, nf = sl.header(self.B)
+            out["dense"] = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.dense32 if f32 else sl.dense)
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
         return out
@@ -410,6 +431,10 @@ class AncshPipeline(object):
             sl.h_record.copy_(sl.out["record"], non_blocking=True)
             if self.articulation:
                 sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
+            if self.dense:               # the valid clouds' raw rows only (padding clouds follow them)
+                rv = int(sl.np_off[n_valid])
+                for h, d in zip(sl.h_dense, sl.dense):
+                    h[:rv].copy_(d[:rv], non_blocking=True)
             if self.range_guard:
                 sl.h_flags.copy_(sl.flags, non_blocking=True)
             sl.d2h_done.record(sl.stream)
@@ -417,21 +442,28 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self, flags=False, articulation=False):
+    def retire(self, flags=False, articulation=False, dense=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
-        block as the last element (flagged clouds: the f32 graph's rows, like their records)."""
+        block (flagged clouds: the f32 graph's rows, like their records).  dense=True (a pipeline built with dense=True): + (labels (R,)
+        int32, values (R, 7) float32, offsets (n_valid+1,) int64) as the last element: the valid clouds' R raw rows in submission order,
+        cloud c's rows [offsets[c], offsets[c+1]) (raw_point_labels; flagged clouds: the f32 graph's rows)."""
         if articulation and not self.articulation:
             raise RuntimeError("retire(articulation=True) needs AncshPipeline(..., articulation=True)")
+        if dense and not self.dense:
+            raise RuntimeError("retire(dense=True) needs AncshPipeline(..., dense=True)")
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
         record = sl.h_record[:n_valid].numpy().copy()
         art = sl.h_art[:n_valid].numpy().copy() if articulation else None
+        off = sl.np_off[:n_valid + 1].astype(np.int64)          # the batch's own offsets: a slot's staging is rewritten only after it retires
+        rv = int(off[-1])
+        dn = (sl.h_dense[0][:rv].numpy().copy(), sl.h_dense[1][:rv].numpy().copy(), off) if dense else None
         words = sl.h_flags[:n_valid].numpy().copy() if self.range_guard else np.zeros((n_valid,), np.int32)
         hit = np.flatnonzero(words)
         if hit.size:
@@ -440,23 +472,34 @@ class AncshPipeline(object):
                 sl.h_record32.copy_(sl.out32["record"], non_blocking=True)
                 if self.articulation:
                     sl.h_art32.copy_(sl.out32["articulation"], non_blocking=True)
+                if self.dense:
+                    for h, d in zip(sl.h_dense32, sl.dense32):
+                        h[:rv].copy_(d[:rv], non_blocking=True)
             sl.stream.synchronize()
             record[hit] = sl.h_record32.numpy()[hit]
             if articulation:
                 art[hit] = sl.h_art32.numpy()[hit]
+            if dense:
+                for c in hit:
+                    a, e = off[c], off[c + 1]
+                    dn[0][a:e], dn[1][a:e] = sl.h_dense32[0].numpy()[a:e], sl.h_dense32[1].numpy()[a:e]
             self.f32_reruns += 1
         out = (tag, seed, record, words) if flags else (tag, seed, record)
-        return out + (art,) if articulation else out
+        out = out + (art,) if articulation else out
+        return out + (dn,) if dense else out
 
-    def stream_batches(self, batches, flags=False, articulation=False):
+    def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
         batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
-        flag words; articulation=True: + the (n_valid, K, 12) articulation block, last -- see retire())."""
+        flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
+        last -- see retire())."""
         if articulation and not self.articulation:
             raise RuntimeError("stream_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
+        if dense and not self.dense:
+            raise RuntimeError("stream_batches(dense=True) needs AncshPipeline(..., dense=True)")
         for k, item in enumerate(batches):
             if len(self._inflight) == len(self.slots):
-                yield self.retire(flags, articulation)
+                yield self.retire(flags, articulation, dense)
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._inflight:
-            yield self.retire(flags, articulation)
+            yield self.retire(flags, articulation, dense)

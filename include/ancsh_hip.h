@@ -41,7 +41,9 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 10: + ancsh_input_sample_stream_keyed, ancsh_ransac_single_rec_dkey, ancsh_ransac_joint_rec_dkey (ancsh_stream_key);
+int ancsh_abi_version(void);   /* 12: + ancsh_raw_point_labels (per-raw-point labels and head values of a streamed batch);
+                                 * 11: + ancsh_articulation_rec (the streamed articulation block);
+                                 * 10: + ancsh_input_sample_stream_keyed, ancsh_ransac_single_rec_dkey, ancsh_ransac_joint_rec_dkey (ancsh_stream_key);
                                  * 9: + the F16x2 range guard (ancsh_*_f16x2*_guarded);
                                  * 8: + ancsh_input_sample_stream, ancsh_ransac_single_rec_dseed, ancsh_ransac_joint_rec_dseed (the streaming pipeline);
                                  * 7 since round 6 (5: round 5, 4: round 4, 3: round 3).  Operator entry points are only ever added: a library of version v serves every caller
@@ -714,6 +716,24 @@ int ancsh_input_sample_stream(int nclouds, int num_points, int nchan, const floa
 int ancsh_input_sample_stream_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
                                     const float *norm_factor, int jcls_col, const ancsh_stream_key *key, float *P, int *joint_cls,
                                     int *perm_out, void *stream);
+
+/* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
+ * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows
+ * [offsets[b], offsets[b+1]) of `rows` (capacity x nchan float32, x y z first), norm factor norm_factor[b], sampled points P (nclouds,
+ * num_points, 3) and the heads W (nclouds, num_points, K), nocs (.., 3K) of the NPCS network and gocs (.., gocs_channels = 3 or 3K) of
+ * the ANCSH network.  For raw row r = (x, y, z):
+ *   q = (x * nf, y * nf, z * nf), the f32 products ancsh_input_sample_stream writes into P (a sampled row is at distance 0 from its copy);
+ *   its 3-NN among P[b] with ancsh_three_nn's arithmetic ((dx*dx + dy*dy) + dz*dz, no contraction) and (distance, index) order, and
+ *   ancsh_three_nn_weights' weights; each needed channel interpolated in ancsh_three_interpolate's order;
+ *   labels[r] (int32) = the first k of the largest interpolated W_k (np.argmax), -1 if q or any interpolated W channel is non-finite;
+ *   values[r] (7 float32) = [W_label | nocs[3l..3l+2] | gocs[3l..3l+2], or gocs[0..2] when gocs_channels = 3]; all NaN when the label is -1.
+ * Bit-equal to ancsh_three_nn_weights + ancsh_three_interpolate per cloud on (q, P[b]) followed by the selection.  Rows outside
+ * [offsets[0], offsets[nclouds]) are left untouched, as is a cloud whose rows are empty or outside [0, capacity).  Graph-capturable: the
+ * grid depends on (capacity, nclouds) only, every cloud size is read from device offsets; no host sync, no allocation.  Checked before
+ * any launch: nclouds <= 65535, 1 <= K <= 8, gocs_channels in {3, 3K}, nchan >= 3, 0 <= capacity < 2^30, null pointers. */
+int ancsh_raw_point_labels(int nclouds, int num_points, int K, int gocs_channels, int nchan, const float *rows, long capacity,
+                           const int *offsets, const float *norm_factor, const float *P, const float *W, const float *nocs,
+                           const float *gocs, int *labels, float *values, void *stream);
 
 /* ---- test-time losses of predict_and_save (lib/network.py:430-498, lib/loss.py:54-182) ------- */
 

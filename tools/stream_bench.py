@@ -2,12 +2,13 @@
 fit + record D2H per batch) against load_inputs + step() on the same clouds, at configs[2]'s shape (K = 3, 32 x 1024, 10000 / 200
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
-    python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation]
+    python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
 line then also carries the rerun count, the latency of the batches that reran and the device memory the streaming pipeline holds.
 --articulation streams with AncshPipeline(articulation=True) (the record plus the (n, K, 12) articulation block per cloud).
+--dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 """
 import argparse
 import json
@@ -35,6 +36,7 @@ def main():
     ap.add_argument("--range-guard", action="store_true")
     ap.add_argument("--overflow-every", type=int, default=0)
     ap.add_argument("--articulation", action="store_true", help="stream with AncshPipeline(articulation=True) and retire the blocks too")
+    ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     args = ap.parse_args()
     if args.range_guard and args.arithmetic != "f16x2":
         ap.error("--range-guard needs --arithmetic f16x2")
@@ -56,7 +58,7 @@ def main():
     torch.cuda.synchronize()
     mem0 = torch.cuda.mem_get_info(dev)[0]
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
-                         range_guard=args.range_guard, articulation=args.articulation).prepare()
+                         range_guard=args.range_guard, articulation=args.articulation, dense=args.dense).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
@@ -70,11 +72,12 @@ def main():
             t_sub[it[2]] = time.perf_counter()
             yield it
     t0 = time.perf_counter()
-    n_out, rerun_lat, n_blocks = 0, [], 0
+    n_out, rerun_lat, n_blocks, n_rows = 0, [], 0, 0
     reruns0 = pipe.f32_reruns
-    for item in pipe.stream_batches(timed(work), articulation=args.articulation):
+    for item in pipe.stream_batches(timed(work), articulation=args.articulation, dense=args.dense):
         tag, seed, rec = item[:3]
-        n_blocks += item[-1].shape[0] if args.articulation else 0
+        n_blocks += item[-2 if args.dense else -1].shape[0] if args.articulation else 0
+        n_rows += item[-1][0].shape[0] if args.dense else 0
         lat.append(time.perf_counter() - t_sub[tag])
         if pipe.f32_reruns != reruns0:
             rerun_lat.append(lat[-1])
@@ -129,6 +132,8 @@ def main():
                      "batch_latency_ms_median": round(1e3 * float(np.median(lat)), 2)})
     if args.articulation:
         line.update({"articulation": True, "blocks_out": n_blocks})
+    if args.dense:
+        line.update({"dense": True, "raw_rows_out": n_rows, "dense_d2h_bytes_per_batch": round(n_rows * 32 / (args.passes * len(batches)))})
     print(json.dumps(line))
 
 
