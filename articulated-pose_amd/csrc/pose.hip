@@ -178,7 +178,7 @@ __device__ __forceinline__ bool inlier_f32(const float R[9], float sc, const flo
 //     (the winner itself, or a contender whose inlier mask differs from the winner's).  Such a sample's centred points are collinear, its 3 x 3 covariance has
 //     rank 1, and the rotation the reference takes from np.linalg.svd is LAPACK's completion of a null space that rounding noise
 //     selects: implementation-defined in the reference itself (include/ancsh_hip.h has the measured figures).
-constexpr int TIE_MAX_CAND = 16;       // degenerate contenders examined one by one in stage A's finish kernel
+constexpr int TIE_MAX_CAND = 16;       // degenerate contenders (the lowest-numbered besides the winner) examined one by one in stage A's finish kernel
 struct FitExtras {
     double *record;
     int K;
@@ -592,27 +592,39 @@ __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__
         // the winner itself when its sample is degenerate, and every other such hypothesis whose inlier mask differs from the winner's
         // in at least one point.  (Round 5 counted every degenerate contender: 24.5 % of the fits at N = 1024, almost all of them
         // hypotheses with the winner's own mask, which cannot change the refit whoever scores them.)
-        __shared__ int s_cand[TIE_MAX_CAND + 1];
-        if (threadIdx.x == 0) s_cand[TIE_MAX_CAND] = 0;
-        __syncthreads();
+        // The winner's degeneracy comes from its own sample (id[], block-uniform) and the winner never takes a slot; the slots go to the
+        // LOWEST-NUMBERED other contenders, found by an ordered compaction per 256-hypothesis step (ballot + mbcnt prefix within a wave,
+        // the four wave counts through LDS), so the sign is exact and the count does not depend on which lanes ran first.
+        const bool winner_degenerate = id[0] == id[1] || id[0] == id[2] || id[1] == id[2];
+        __shared__ int s_cand[TIE_MAX_CAND];
         const int *sp = scores + (size_t)prob * niter;
-        for (int h = threadIdx.x; h < niter; h += 256) {
-            if (sp[h] >= best_score - 1) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int found = 0;                                  // other contenders below the current step (block-uniform)
+        for (int h0 = 0; h0 < niter; h0 += 256) {       // block-uniform trip count
+            const int h = h0 + threadIdx.x;
+            bool cand = false;
+            if (h < niter && h != best && sp[h] >= best_score - 1) {
                 int d3[3];
                 load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, d3);
-                if (d3[0] == d3[1] || d3[0] == d3[2] || d3[1] == d3[2]) {
-                    const int slot = atomicAdd(&s_cand[TIE_MAX_CAND], 1);
-                    if (slot < TIE_MAX_CAND) s_cand[slot] = h;
-                }
+                cand = d3[0] == d3[1] || d3[0] == d3[2] || d3[1] == d3[2];
             }
+            const unsigned long long m = __ballot(cand);
+            __syncthreads();                            // every thread is done reading wcnt[0..3] (previous step / compact_flagged)
+            if (lane == 0) wcnt[wave] = __popcll(m);
+            __syncthreads();
+            int start = found;
+            for (int w = 0; w < wave; ++w) start += wcnt[w];
+            if (cand) {
+                const int slot = start + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+                if (slot < TIE_MAX_CAND) s_cand[slot] = h;
+            }
+            found += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
         }
         __syncthreads();
-        const int found = s_cand[TIE_MAX_CAND], ncand = found < TIE_MAX_CAND ? found : TIE_MAX_CAND;
-        n_near = found - ncand;                         // more contenders than slots: the rest counted as changing (conservative)
-        bool winner_degenerate = false;
+        const int ncand = found < TIE_MAX_CAND ? found : TIE_MAX_CAND;
+        n_near = found - ncand + (winner_degenerate ? 1 : 0);   // contenders beyond the slots counted as changing (conservative)
         for (int c = 0; c < ncand; ++c) {               // block-uniform trip count
             const int h = s_cand[c];
-            if (h == best) { ++n_near; winner_degenerate = true; continue; }
             int d3[3];
             load_draw3(draws, seed, prob, kbase, niter, h, 0, 3, n, d3);
             float hs[3][3], ht[3][3], hR[9], hsc, htr[3];

@@ -158,7 +158,9 @@ class PoseSolver(object):
         tie_a (B,K,2), tie_b (B,K-1,2) int32: how implementation-sensitive each fit is -- [points within `tie_window` of the inlier
         threshold under the winning hypothesis, DEGENERATE contenders = hypotheses within one inlier of the winning score whose 3-point
         sample repeats an index (their rotation is implementation-defined in the reference itself); stage A counts only those that would
-        change the consensus set and makes the count NEGATIVE when the winner's own sample is degenerate -- the sharp per-fit warning]
+        change the consensus set and makes the count NEGATIVE exactly when the winner's own sample is degenerate -- the sharp per-fit
+        warning, read from the winner's sample itself; of the OTHER contenders it examines the 16 lowest-numbered hypotheses and counts
+        any beyond them as changing, so the count is deterministic]
         (include/ancsh_hip.h, ancsh_ransac_single_rec; what the counts did and did not predict: profiles/r06_pose_tie_rate_K3.txt)
     A part with no predicted points gives NaN rows (the reference raises inside randint)."""
 
@@ -190,7 +192,7 @@ class PoseSolver(object):
         seed is read as seed_dev's, and cloud b is keyed as global cloud cloud_base + b -- so a shard of clouds [lo, hi) solved with
         cloud_base = lo gives the bytes of rows [lo, hi) of the whole batch's solve(seed=<that seed>)."""
         out = self._partition(P, nocs_pred, mask_pred)
-        self.solve_stage_b(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev)
+        self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev)
         return self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):
@@ -247,7 +249,11 @@ class PoseSolver(object):
 
     def solve_stage_b(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None):
         """Articulated joint fit (stage B, :274-341) on top of a solve_stage_a result (key seed + 1, or *seed_dev + 1 / the key block's
-        seed + 1 read on the device)."""
+        seed + 1 read on the device).  The records are poisoned again afterwards, now with the joint-axis field among the inputs: a
+        cloud with a non-finite value there gets an all-NaN record on this path too."""
+        return self._poison(self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev))
+
+    def _stage_b_fits(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None):
         dev, K = self.device, self.K
         B, N = out["_shape"]
         src, tgt, max_n = out["_src"], out["_tgt"], out["_max_n"]

@@ -501,10 +501,13 @@ int ancsh_ransac_single_ex(int nprob, const int *off, const float *src, const fl
  *         differs in the last bits (LAPACK's SVD there, Horn's quaternion here) may count such a point on the other side;
  *     [1] DEGENERATE CONTENDERS THAT WOULD CHANGE THE CONSENSUS SET: hypotheses whose score is within one inlier of the winning score,
  *         whose 3-point sample repeats an index (np.random.randint draws WITH replacement, :38) and which -- had they won -- would have
- *         handed the refit another inlier mask than the winner's (the winner itself counts when its own sample is degenerate).  Until
+ *         handed the refit another inlier mask than the winner's (the winner itself counts once when its own sample is degenerate; of
+ *         the others the 16 lowest-numbered hypotheses are examined, and any beyond them are counted as changing: the count is the same
+ *         from run to run and from launch to launch).  Until
  *         round 5 every degenerate contender was counted (20-25 % of the fits at N = 1024: nearly all of them hypotheses with the
  *         winner's own mask, which cannot change the result whoever scores them).  The count is NEGATIVE when the winner's own sample is
- *         degenerate -- the one case in which the fit's consensus set is implementation-defined for certain (measured at 10000 / 200 on
+ *         degenerate, and only then (read from the winner's own sample: exact however many contenders there are) -- the one case in
+ *         which the fit's consensus set is implementation-defined for certain (measured at 10000 / 200 on
  *         624 fits, profiles/r06_pose_tie_rate_K3.txt: 3 such fits, all 3 on another set than the reference arithmetic; a positive count
  *         fired on 22.9 % of the fits and held 1 of the other 4 flips: as a per-fit warning only the sign is sharp).  The centred points of such a sample are
  *         collinear, the 3 x 3 covariance has rank 1, and the rotation the reference takes from np.linalg.svd (lib/d3_utils.py:214) is

@@ -47,6 +47,54 @@ def problem(cid, N, K):
     return c, p
 
 
+def squeezed_problem(cid, N, K, joint_type="revolute", keep=None, kind="plain"):
+    """A cloud of make_cloud / make_predictions whose parts in `keep` ({part: m}, part >= 1) keep only their first m predicted points;
+    the rest are relabelled to part 0 (outliers there: their part-NOCS is another part's).  kind shapes the kept points of every
+    squeezed part with m >= 4 (smaller parts stay as predicted):
+      plain       as predicted (noise, outliers and label flips included);
+      coincident  points consistent with the part's transform (P = s R x + t exactly), the second (m = 4) or the second and third
+                  (m >= 5) a copy of the first: >= 3 distinct points, but most 3-point samples hold two copies;
+      collinear   m - 1 points on a line of the part's NOCS cube and one off it, all consistent with the part's transform: the
+                  consensus set has rank 2, most samples are collinear (rank 1);
+      unrelated   camera points replaced by points spread over [-2, 2]^3 (any m): no three of them fit one similarity, so every
+                  score is 0-2 and nearly every hypothesis is within one inlier of the winner."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import articulated_pose_amd  # noqa: F401
+    from articulated_pose_amd.synthetic import make_cloud, make_predictions
+    c = make_cloud(cid, N=N, K=K, joint_type=joint_type)
+    p = make_predictions(c, K, seed=cid)
+    c, p = dict(c, P=c["P"].copy()), {k: v.copy() for k, v in p.items()}
+    W, P, nocs = p["instance_per_point"], c["P"], p["nocs_per_point"]
+    lab = np.argmax(W, 1)
+    rng = np.random.RandomState(10 * cid + 1)
+    for j, m in sorted((keep or {}).items()):
+        assert j >= 1
+        idx = np.nonzero(lab == j)[0]
+        move = idx[m:]
+        W[move] = 0.05 / max(K - 1, 1)
+        W[move, 0] = 0.95
+        kept = idx[:m]
+        Rj, sj, tj = c["R"][j], float(c["s"][j]), c["t"][j]
+        place = lambda x: (sj * np.asarray(x, np.float64) @ Rj.T + tj).astype(np.float32)
+        if kind == "unrelated":
+            P[kept] = rng.uniform(-2.0, 2.0, (m, 3)).astype(np.float32)
+        elif kind in ("coincident", "collinear") and m >= 4:
+            x = c["nocs_gt"][kept].astype(np.float64)
+            if kind == "collinear":
+                a, b = x[0], x[1]
+                x[:m - 1] = a + np.linspace(0.0, 1.0, m - 1)[:, None] * (b - a)
+                d = (b - a) / np.linalg.norm(b - a)
+                off = np.cross(d, [1.0, 0.0, 0.0] if abs(d[0]) < 0.9 else [0.0, 1.0, 0.0])
+                x[m - 1] = 0.5 * (a + b) + 0.3 * off / np.linalg.norm(off)
+            else:
+                x[1:2 if m == 4 else 3] = x[0]
+            x = x.astype(np.float32)
+            nocs[kept, 3 * j:3 * j + 3] = x
+            P[kept] = place(x)
+    return c, p
+
+
 def pack(ref, K):
     """solve_cloud's result -> flat arrays: base / nonl (K,13) [R row-major, s, t], iter_a / score_a (K), iter_b / score_b (K-1)."""
     def m13(rst):
@@ -63,9 +111,9 @@ def pack(ref, K):
 
 def reference_fit(args):
     """One cloud through oracle/pose_oracle.solve_cloud on its replayed draws (worker body: picklable arguments)."""
-    cid, N, K, na, nb, seed0 = args
+    cid, N, K, na, nb, seed0 = args[:6]
     from oracle import pose_oracle as PO
-    c, p = problem(cid, N, K)
+    c, p = problem(cid, N, K) if len(args) < 7 else squeezed_problem(cid, N, K, **args[6])
     counts = np.bincount(np.argmax(p["instance_per_point"], 1), minlength=K)
     da, db = replay_draws(seed0 + cid, counts, na, nb)
     ref = PO.solve_cloud(c["P"], p["nocs_per_point"], p["instance_per_point"], p["joint_axis_per_point"], p["joint_cls_gt"], K,
@@ -74,9 +122,11 @@ def reference_fit(args):
     return pack(ref, K)
 
 
-def reference_fits(cids, N, K, na, nb, seed0=100, workers=1):
-    """[pack(...)] for every cloud id, on `workers` single-threaded processes (spawned: the caller may hold a HIP context)."""
-    jobs = [(int(c), N, K, na, nb, seed0) for c in cids]
+def reference_fits(cids, N, K, na, nb, seed0=100, workers=1, specs=None):
+    """[pack(...)] for every cloud id, on `workers` single-threaded processes (spawned: the caller may hold a HIP context).
+    specs: optional list of squeezed_problem keyword dicts (joint_type, keep, kind), one per cloud id; N and K may then be lists."""
+    per = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
+    jobs = [(int(c), per(N, i), per(K, i), na, nb, seed0) + (() if specs is None else (specs[i],)) for i, c in enumerate(cids)]
     if workers <= 1 or len(jobs) <= 1:
         return [reference_fit(j) for j in jobs]
     import multiprocessing as mp
@@ -243,6 +293,51 @@ def repeated_index(draw3):
     trajectory then starts from a rotation no other implementation reproduces (tests/test_pose_sweep_gpu.py, seed 23)."""
     d = [int(x) for x in draw3]
     return len(set(d)) < 3
+
+
+TIE_MAX_CAND = 16        # the other degenerate contenders stage A's finish kernel examines one by one (csrc/pose.hip)
+
+
+def _repeated_rows(d):
+    """Row-wise repeated_index of an (m, 3) index array -> (m,) bool."""
+    d = np.asarray(d).reshape(-1, 3)
+    return (d[:, 0] == d[:, 1]) | (d[:, 0] == d[:, 2]) | (d[:, 1] == d[:, 2])
+
+
+def stage_a_contenders(scores, draws, best):
+    """The degenerate contenders of ONE stage-A fit, recounted from the per-hypothesis scores (niter,) and the sample stream
+    (niter, 3) that produced them; best = the winning hypothesis (-1: an empty part, no fit).  A contender scores within one inlier of
+    the winner and its sample repeats an index (repeated_index).  -> (winner_degenerate, others): whether the winner's own sample is
+    degenerate, and the OTHER contenders' hypothesis numbers in ascending order (int64).  The finish kernel's tie[1] has magnitude
+    winner_degenerate + (those of the first TIE_MAX_CAND others whose inlier mask differs from the winner's) + (the others beyond the
+    first TIE_MAX_CAND), and is negative exactly when winner_degenerate."""
+    scores = np.asarray(scores).ravel()
+    best = int(best)
+    if best < 0 or scores.size == 0:
+        return False, np.zeros(0, np.int64)
+    deg = _repeated_rows(draws)
+    near = scores >= scores[best] - 1
+    near[best] = False
+    return bool(deg[best]), np.nonzero(near & deg)[0].astype(np.int64)
+
+
+def stage_a_tie_bounds(scores, draws, best):
+    """[lo, hi] of |tie[1]| for one stage-A fit (see stage_a_contenders) and the sign it must carry (-1 | 1)."""
+    wd, others = stage_a_contenders(scores, draws, best)
+    c = len(others)
+    return int(wd) + max(c - TIE_MAX_CAND, 0), int(wd) + c, -1 if wd else 1
+
+
+def stage_b_contenders(hyp_scores, draws, best_score):
+    """Stage B's tie[1] as the joint finish kernel defines it: hypotheses -- the winner included -- whose joint score is
+    >= best_score - (1/6 + 1e-9) (one inlier of either part moves the score by 1/6) and whose 6-draw (niter, 6) repeats an index in
+    either half.  An empty problem (no hypotheses, or best_score < 0) counts 0."""
+    hyp_scores = np.asarray(hyp_scores, np.float64).ravel()
+    if hyp_scores.size == 0 or best_score < 0:
+        return 0
+    d = np.asarray(draws).reshape(-1, 6)
+    deg = _repeated_rows(d[:, :3]) | _repeated_rows(d[:, 3:])
+    return int(np.count_nonzero((hyp_scores >= float(best_score) - (1.0 / 6.0 + 1e-9)) & deg))
 
 
 def check_rows(rows, ill_value_bars=True, ill_max_dscore=None):

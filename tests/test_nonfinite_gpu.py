@@ -237,6 +237,28 @@ def test_pose_fit_gives_nan_records_for_poisoned_clouds(dev, K):
     assert np.isnan(a[:, :, 13:]).all()                                                   # stage B did not run: "not fitted", never stale memory
 
 
+@pytest.mark.parametrize("K", [2, 3])
+def test_standalone_stage_b_poisons_a_nonfinite_joint_axis(dev, K):
+    """solve_stage_a then solve_stage_b (the two-step flow) with cloud 1's joint-axis field NaN at one point: that cloud's record is all
+    NaN -- stage B poisons again once the axis field is among the inputs -- and every other cloud equals solve() on the same inputs and
+    draws, bit for bit."""
+    from articulated_pose_amd.pose import PoseSolver
+    from articulated_pose_amd.synthetic import make_cloud, make_predictions
+    N, B = 512, 4
+    clouds = [make_cloud(320 + i, N=N, K=K) for i in range(B)]
+    preds = [make_predictions(c, K, seed=i) for i, c in enumerate(clouds)]
+    st = lambda key, src: np.stack([x[key] for x in src]).copy()
+    P, nocs, W, axis, cls = st("P", clouds), st("nocs_per_point", preds), st("instance_per_point", preds), st("joint_axis_per_point", preds), st("joint_cls_gt", preds)
+    axis[1, 7, 2] = np.nan
+    solver = PoseSolver(K, 0.1, 200, 16, dev)
+    whole = solver.solve(P, nocs, W, axis, cls, seed=9)["record"].cpu().numpy()
+    out = solver.solve_stage_a(P, nocs, W, seed=9)
+    two = solver.solve_stage_b(out, axis, cls, seed=9)["record"].cpu().numpy()
+    assert np.isnan(two[1]).all() and np.isnan(whole[1]).all()
+    np.testing.assert_array_equal(two[[0, 2, 3]], whole[[0, 2, 3]])
+    assert np.isfinite(two[[0, 2, 3]]).all()
+
+
 def test_pipeline_record_of_a_poisoned_cloud_is_nan(dev):
     """End to end (both networks + fit, coupled data flow): one cloud of the batch has 1 % NaN points -> its record is NaN, the others' are finite."""
     from articulated_pose_amd.pipeline import AncshPipeline
