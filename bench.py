@@ -9,6 +9,10 @@ One "step" = one pass of the hot path over one batch of synthetic clouds PER RAN
 batch 32 per GPU, independent clouds, no data-path collective; one RCCL gather of the result records to
 rank 0 closes each step when N > 1).  Inputs are resident in HBM before the timed region.  Prints ONE
 JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds every side
+measurement after the timed steps (per-kernel roofline, op-level figures, the other configurations and precisions, the
+latency leg, the CPU baseline).
 """
 import argparse
 import json
@@ -837,7 +841,11 @@ def print_last(text):
     print(text, flush=True)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  A plain run measures the headline figure and nothing else; every side measurement (per-kernel roofline pass,
+    op-level figures, the other configurations, precisions and data flows, the latency leg, the CPU baseline) needs --full, and a
+    --leg of a --full run does its own per-kernel pass only.  args.kernel_pass: whether this process takes its own per-kernel pass
+    (and, with --bf16x3, the parity of the split-16 arithmetic)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
@@ -866,6 +874,11 @@ def main():
                          "path -- communicator creation, gather on the slot streams, all-reduce of the timing -- on a single GPU)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--ops-only", action="store_true", help="print the op-level ball_query + group figures (roofline_ops) and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every side measurement after the timed steps: the per-kernel roofline pass, the op-level figures, "
+                         "the production-data-flow leg, the split-16 legs, the latency leg, the other BASELINE configurations and the CPU "
+                         "baseline (the --no-* options below skip single ones).  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
     ap.add_argument("--only-timed", action="store_true",
                     help="stop after the timed steps (no per-kernel pass, op-level figures, CPU baseline): the command to put under a "
                          "kernel trace or PMC collection when only the pipelined step itself is of interest")
@@ -900,11 +913,17 @@ def main():
     ap.add_argument("--profile-lead", type=int, default=6,
                     help="per-kernel timing pass: launches of the same call issued back-to-back before each timed one, so the timed "
                          "launch runs at the loaded clock instead of on a chip that idled while Python prepared the call (0 = cold)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
-    if args.leg:
+    if args.leg or not args.full:
         args.no_ops = args.no_value_configs = args.no_cpu_baseline = args.no_network_inputs = args.no_bf16x3 = True
+    args.kernel_pass = args.full or args.leg
+    return args
+
+
+def main():
+    args = parse_args()
     if args.bf16x3:
         from articulated_pose_amd import pointnet_util
         if args.split_scheme:
@@ -1105,10 +1124,10 @@ def main():
                                        world, ", 1 %s gather of pose records per step" % collective_note if use_dist else "")}))
         return
 
-    # per-kernel durations: the same launches issued eagerly, each bracketed by HIP events on the launch stream
+    # per-kernel durations (--full, or a --leg of one): the same launches issued eagerly, each bracketed by HIP events on the launch stream
     roof = {}
     POSE_WORK["rows"] = B * N
-    if rank == 0 and full:
+    if rank == 0 and full and args.kernel_pass:
         # LM work of one step: sum of MINPACK function evaluations over the step's (K-1)*B*200 hypothesis fits (one eager pass
         # with the per-hypothesis statistics switched on; outside the timed region)
         pipe.solver.want_lm_stat = True
@@ -1118,7 +1137,7 @@ def main():
         pipe.solver.want_lm_stat = False
         if st is not None:
             POSE_WORK["lm_evals"] = float(st[..., 1].sum().item())
-    if rank == 0:
+    if rank == 0 and args.kernel_pass:
         passes = max(3, min(args.steps, 8))
         with torch.cuda.stream(stream):
             eager()
@@ -1181,7 +1200,8 @@ def main():
                             (" (fused SA levels, mid-section, tail chain)" if pointnet_util.SA_BF16X3 >= 4 else " (fused SA levels + tail chain; mid-section f32)") + \
                             (" / f64 (joint LM)" if full else "")
             line["split_scheme"] = args.split_scheme
-            line["bf16x3_parity"] = bf16x3_parity(K, (w_ancsh, w_npcs) if full else (w_ancsh,), P, dev)
+            if args.kernel_pass:
+                line["bf16x3_parity"] = bf16x3_parity(K, (w_ancsh, w_npcs) if full else (w_ancsh,), P, dev)
         if full and world == 1 and not networked and not args.no_network_inputs:
             # the PRODUCTION data flow in the same timed loop (hand-built weights whose heads emit a usable segmentation /
             # part-NOCS; the fit consumes the networks' OWN outputs): shows what the synthetic-prediction default does to `value`.

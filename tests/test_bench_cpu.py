@@ -182,3 +182,18 @@ def test_a_leg_hands_its_full_record_to_the_parent_on_stdout(capsys):
     b.print_last(b.emit(full, sidecar=False))
     out = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     assert len(out) == 2 and json.loads(out[0])["bench_detail"] == full and "detail" not in json.loads(out[1])
+
+
+def test_a_plain_run_takes_no_side_measurement():
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline and nothing else; --full adds the per-kernel pass and every side leg
+    (each --no-* option still skips its own), and a --leg of a --full run does its per-kernel pass and no leg of its own."""
+    b = _bench()
+    legs = ("no_ops", "no_value_configs", "no_cpu_baseline", "no_network_inputs", "no_bf16x3")
+    plain = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and not plain.kernel_pass and all(getattr(plain, k) for k in legs)
+    full = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and full.kernel_pass and not any(getattr(full, k) for k in legs)
+    some = b.parse_args(["--full", "--no-cpu-baseline"])
+    assert some.no_cpu_baseline and not any(getattr(some, k) for k in legs if k != "no_cpu_baseline")
+    leg = b.parse_args(["--leg", "--steps", "256", "--warmup", "24"])
+    assert leg.kernel_pass and all(getattr(leg, k) for k in legs)

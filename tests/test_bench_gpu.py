@@ -48,7 +48,7 @@ def _free_port():
 
 
 def test_bench_single_gpu_line(dev):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--slots", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--slots", "2", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _last_json(r.stdout, r.stderr)
@@ -168,16 +168,39 @@ def test_bench_rccl_code_path_single_rank(dev):
     assert line["n_gpus"] == 1 and line["value"] > 0 and "1 RCCL gather" in line["config"]["parallelism"]
 
 
+def test_plain_run_takes_only_the_headline(dev):
+    """The driver times `python3 bench.py --gpus 1 --steps 20 --warmup 5` several times per change: such a plain run sets up, warms
+    up, times the steps and prints the line -- the same headline fields as a --full run, no side leg -- and the fresh process spends
+    at most 30 s beyond its warm-up and timed steps."""
+    import time
+    steps, warmup = 20, 5
+    t0 = time.time()
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _last_json(r.stdout, r.stderr)
+    assert line["metric"] == "point-clouds/sec (N=1024, eyeglasses ANCSH infer+pose-fit)" and line["unit"] == "point-clouds/sec"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32 (network) / f64 (joint LM)"
+    assert line["steps"] == steps and line["warmup"] == warmup and line["config"]["batches_in_flight"] == 20
+    assert abs(line["value"] - 32 * 1000.0 / line["ms_per_step"]) / line["value"] < 1e-3
+    side = ("roofline", "roofline_all", "roofline_ops", "value_network_inputs", "value_bf16x3", "value_f16x2", "value_latency",
+            "value_configs", "cpu_baseline", "bf16x3_parity")
+    assert [k for k in side if k in line] == []
+    outside = wall - (steps + warmup) * line["ms_per_step"] * 1e-3
+    assert outside < 30.0, (wall, line["ms_per_step"])
+
+
 def test_driver_command_is_not_slowed_by_the_side_measurements(dev):
-    """The driver times `python3 bench.py --gpus 1 --steps 20 --warmup 5`.  The line's extra legs (op-level figures, the
-    production-data-flow leg, the per-kernel pass, the other BASELINE configs, the split-bf16 figure, the CPU baseline) must not leak
-    into the timed loop: on a 20-step run a fixed cost shows at once (taking the op-level graphs in the same process BEFORE the
-    pipeline cost the timed loop ~50 ms: 4.1 instead of 1.6 ms/step).  The full line's ms_per_step has to agree with the bare timed
-    loop of a fresh process, every leg has to be there, and the whole command has to stay a one-minute affair."""
+    """The driver's command with every side measurement, `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`.  The line's extra
+    legs (op-level figures, the production-data-flow leg, the per-kernel pass, the other BASELINE configs, the split-bf16 figure, the
+    CPU baseline) must not leak into the timed loop: on a 20-step run a fixed cost shows at once (taking the op-level graphs in the same
+    process BEFORE the pipeline cost the timed loop ~50 ms: 4.1 instead of 1.6 ms/step).  The full line's ms_per_step has to agree with
+    the bare timed loop of a fresh process, every leg has to be there, and the whole command has to stay a one-minute affair."""
     import time
     args = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
     t0 = time.time()
-    full = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    full = subprocess.run([sys.executable, "bench.py"] + args + ["--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0
     assert full.returncode == 0, full.stderr[-3000:]
     bare = subprocess.run([sys.executable, "bench.py"] + args + ["--only-timed"], cwd=ROOT, capture_output=True, text=True, timeout=900)

@@ -105,7 +105,7 @@ if os.path.exists(stats) and os.path.exists(line):
     per_step = (lj.get("roofline_all", {}).get("shared_mlp_fused_sa", {}) or {}).get("launches_per_step", 4)
     G = max(1, 4 // max(1, per_step))
     sa1g, sa2g = G * sa1, G * sa2
-    out = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline (%s_kernel_stats_bench_default.csv): average "
+    out = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline (%s_kernel_stats_bench_default.csv): average "
                      "duration over ALL launches of the command, i.e. mostly graph replays with 16 batches in flight (kernels of other "
                      "batches share the chip), plus the eager profiling passes" % tag,
            "sa1_fused_us": t1, "sa2_fused_us": t2,
