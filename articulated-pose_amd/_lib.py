@@ -105,6 +105,11 @@ SIGNATURES = {
     "ancsh_ransac_joint_rec_dkey": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
                                    + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp],
     "ancsh_raw_point_labels": [_c_int] * 5 + [_vp, _c_long] + [_vp] * 8 + [_vp],
+    # ABI 13: the joint association from the ANCSH network's index head, and xyz-only raw rows
+    "ancsh_pose_joint_direction_pred": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp],
+    "ancsh_pose_poison_records_pred": [_c_int, _c_int, _c_int] + [_vp] * 4 + [_c_int, _vp, _vp, _vp],
+    "ancsh_input_sample_stream_xyz": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ancsh_input_sample_stream_xyz_keyed": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

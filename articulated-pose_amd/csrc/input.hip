@@ -78,7 +78,9 @@ __device__ __forceinline__ unsigned long long feistel_index(unsigned long long i
 // one thread per sampled row; the gathered source row (16 B for nchan = 4) of a cloud of a few thousand rows is L2-resident.
 // KEYED: `seed` is the address of an ancsh_stream_key (its seed first) and the round keys use the global cloud index cloud_base + b;
 // unkeyed, the base is a constant 0 and the code is that of the plain entry.
-template <bool KEYED>
+// XYZ: rows without a joint-class channel (nchan >= 3; a 12-byte row is not 16-byte aligned, so the three coordinates are read as the
+// scalar loads below) and no joint_cls output; jcls_col / joint_cls are never read.  P and perm_out are those of the 4-column kernel.
+template <bool KEYED, bool XYZ = false>
 __global__ __launch_bounds__(256) void input_sample_stream_kernel(int num_points, int nchan, const float *__restrict__ rows,
                                                                   long capacity, const int *__restrict__ offsets,
                                                                   const float *__restrict__ norm_factor, int jcls_col,
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void input_sample_stream_kernel(int num_points
     P[o * 3] = src[0] * nf;
     P[o * 3 + 1] = src[1] * nf;
     P[o * 3 + 2] = src[2] * nf;
-    joint_cls[o] = (int)src[jcls_col];                  // C truncation, as np.asarray(x, np.int32)
+    if (!XYZ) joint_cls[o] = (int)src[jcls_col];        // C truncation, as np.asarray(x, np.int32)
     if (perm_out) perm_out[o] = (int)t;
 }
 
@@ -166,4 +168,37 @@ extern "C" int ancsh_input_sample_stream_keyed(int nclouds, int num_points, int 
     hipLaunchKernelGGL(input_sample_stream_kernel<true>, dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream,
                        num_points, nchan, rows, capacity, offsets, norm_factor, jcls_col, &key->seed, P, joint_cls, perm_out);
     return check_launch("input_sample_stream_keyed");
+}
+
+// the xyz-only twins (rows of nchan >= 3 channels, x y z first; no joint-class channel, no joint_cls output): the kernel above with XYZ
+extern "C" int ancsh_input_sample_stream_xyz(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                                             const float *norm_factor, const unsigned long long *seed, float *P, int *perm_out,
+                                             void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0 && num_points > 0 && num_points < (1 << 30), "input_sample_stream_xyz: bad shape nclouds=%d num_points=%d",
+                  nclouds, num_points);
+    ANCSH_REQUIRE(nchan >= 3, "input_sample_stream_xyz: rows need x y z (nchan=%d < 3)", nchan);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "input_sample_stream_xyz: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(nclouds <= 65535, "input_sample_stream_xyz: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(seed, "input_sample_stream_xyz: null seed pointer");
+    ANCSH_REQUIRE(rows && offsets && norm_factor && P, "input_sample_stream_xyz: null pointer");
+    if (nclouds == 0) return ANCSH_OK;
+    hipLaunchKernelGGL((input_sample_stream_kernel<false, true>), dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream,
+                       num_points, nchan, rows, capacity, offsets, norm_factor, 0, seed, P, nullptr, perm_out);
+    return check_launch("input_sample_stream_xyz");
+}
+
+extern "C" int ancsh_input_sample_stream_xyz_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity,
+                                                   const int *offsets, const float *norm_factor, const ancsh_stream_key *key, float *P,
+                                                   int *perm_out, void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0 && num_points > 0 && num_points < (1 << 30),
+                  "input_sample_stream_xyz_keyed: bad shape nclouds=%d num_points=%d", nclouds, num_points);
+    ANCSH_REQUIRE(nchan >= 3, "input_sample_stream_xyz_keyed: rows need x y z (nchan=%d < 3)", nchan);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "input_sample_stream_xyz_keyed: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(nclouds <= 65535, "input_sample_stream_xyz_keyed: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(key, "input_sample_stream_xyz_keyed: null key pointer");
+    ANCSH_REQUIRE(rows && offsets && norm_factor && P, "input_sample_stream_xyz_keyed: null pointer");
+    if (nclouds == 0) return ANCSH_OK;
+    hipLaunchKernelGGL((input_sample_stream_kernel<true, true>), dim3((num_points + 255) / 256, nclouds), dim3(256), 0, (hipStream_t)stream,
+                       num_points, nchan, rows, capacity, offsets, norm_factor, 0, &key->seed, P, nullptr, perm_out);
+    return check_launch("input_sample_stream_xyz_keyed");
 }

@@ -1567,9 +1567,11 @@ __global__ __launch_bounds__(256) void partition_kernel(int n, int K, const floa
 // A cloud with a non-finite value anywhere in the fit's inputs has no defined pose (the reference's own np.linalg.svd raises
 // LinAlgError on it, np.argmax / np.median of NaN rows are arbitrary): its (K, 26) record rows become NaN, whatever the fit kernels
 // made of it -- a poisoned cloud never yields a silently finite answer.  One workgroup per cloud; axis may be NULL.
+// IDX (the predicted joint association): the (n, jc) index head is scanned as well; the plain instantiation never reads index / jc.
+template <bool IDX>
 __global__ __launch_bounds__(1024) void poison_records_kernel(int n, int K, const float *__restrict__ P, const float *__restrict__ nocs,
                                                               const float *__restrict__ W, const float *__restrict__ axis,
-                                                              double *__restrict__ record) {
+                                                              double *__restrict__ record, int jc, const float *__restrict__ index) {
     const int b = blockIdx.x;
     bool bad = false;
     // 1024 threads, eight independent loads in flight per thread: the scan is a handful of memory latencies, not a per-element loop
@@ -1586,9 +1588,60 @@ __global__ __launch_bounds__(1024) void poison_records_kernel(int n, int K, cons
     scan(nocs + (size_t)b * n * 3 * K, (long)n * 3 * K);
     scan(W + (size_t)b * n * K, (long)n * K);
     if (axis) scan(axis + (size_t)b * n * 3, (long)n * 3);
+    if (IDX) scan(index + (size_t)b * n * jc, (long)n * jc);
     if (__syncthreads_or(bad))
         for (int i = threadIdx.x; i < K * 26; i += 1024) record[(size_t)b * K * 26 + i] = __builtin_nan("");
 }
+
+// ---- the passes of the joint-direction medians, shared by joint_direction_kernel and joint_direction_pred_kernel.  STATEMENT MACROS
+// (as csrc/part_stats.h): expanded in place they give joint_direction_kernel the instruction stream it had before the second kernel.
+// ANCSH_JD_COMPACT: ordered compaction of cloud b's points whose IS_J (a boolean expression of the point index i, evaluated only for
+// i < n) holds into three LDS columns of npow2 floats (joint_axis rows, in point order); cnt ends as their number on every thread.
+#define ANCSH_JD_COMPACT(IS_J)                                                                                                        \
+    for (int c0 = 0; c0 < n; c0 += 256) {                                                                                             \
+        const int i = c0 + threadIdx.x;                                                                                               \
+        const bool f = i < n && (IS_J);                                                                                               \
+        const unsigned long long m = __ballot(f);                                                                                     \
+        __syncthreads();                                                                                                              \
+        if (lane == 0) wcnt[wave] = __popcll(m);                                                                                      \
+        __syncthreads();                                                                                                              \
+        int start = cnt;                                                                                                              \
+        for (int w = 0; w < wave; ++w) start += wcnt[w];                                                                              \
+        if (f) {                                                                                                                      \
+            const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));       \
+            _Pragma("unroll") for (int c = 0; c < 3; ++c) vals[c * npow2 + pos] = axis[((size_t)b * n + i) * 3 + c];                 \
+        }                                                                                                                             \
+        cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];                                                                                 \
+    }
+// ANCSH_JD_MEDIAN: +inf padding to the next power of two, a bitonic sort of each column, and np.median of each (the middle element or
+// the float32 mean of the middle two; NaN without a point) into out[b, j - 1, :]
+#define ANCSH_JD_MEDIAN                                                                                                               \
+    int p2 = 1;                                                                                                                       \
+    while (p2 < cnt) p2 <<= 1;                                                                                                        \
+    for (int e = cnt + threadIdx.x; e < p2; e += 256)                                                                                 \
+        _Pragma("unroll") for (int c = 0; c < 3; ++c) vals[c * npow2 + e] = INFINITY;                                                 \
+    __syncthreads();                                                                                                                  \
+    for (int k = 2; k <= p2; k <<= 1)                                                                                                 \
+        for (int s = k >> 1; s > 0; s >>= 1) {                                                                                        \
+            for (int e = threadIdx.x; e < p2; e += 256) {                                                                             \
+                const int partner = e ^ s;                                                                                            \
+                if (partner > e) {                                                                                                    \
+                    const bool up = (e & k) == 0;                                                                                     \
+                    _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                   \
+                        float *v = vals + c * npow2;                                                                                  \
+                        const float a = v[e], bb = v[partner];                                                                       \
+                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }                                                            \
+                    }                                                                                                                 \
+                }                                                                                                                     \
+            }                                                                                                                         \
+            __syncthreads();                                                                                                          \
+        }                                                                                                                             \
+    if (threadIdx.x < 3) {                                                                                                            \
+        const float *v = vals + threadIdx.x * npow2;                                                                                  \
+        float med = NAN;                                                                                                              \
+        if (cnt > 0) med = (cnt & 1) ? v[cnt / 2] : (v[cnt / 2 - 1] + v[cnt / 2]) * 0.5f;                                             \
+        out[((size_t)b * (K - 1) + (j - 1)) * 3 + threadIdx.x] = med;                                                                 \
+    }
 
 // jt_axis = np.median(joint_axis_per_point[joint_cls == j], 0)  (:295): one workgroup per (cloud, joint)
 __global__ __launch_bounds__(256) void joint_direction_kernel(int n, int K, const float *__restrict__ axis,
@@ -1599,50 +1652,34 @@ __global__ __launch_bounds__(256) void joint_direction_kernel(int n, int K, cons
     int npow2 = 1;
     while (npow2 < n) npow2 <<= 1;
     int cnt = 0;
-    for (int c0 = 0; c0 < n; c0 += 256) {
-        const int i = c0 + threadIdx.x;
-        const bool f = i < n && joint_cls[(size_t)b * n + i] == j;
-        const unsigned long long m = __ballot(f);
-        __syncthreads();
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int start = cnt;
-        for (int w = 0; w < wave; ++w) start += wcnt[w];
-        if (f) {
-            const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-#pragma unroll
-            for (int c = 0; c < 3; ++c) vals[c * npow2 + pos] = axis[((size_t)b * n + i) * 3 + c];
-        }
-        cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    ANCSH_JD_COMPACT(joint_cls[(size_t)b * n + i] == j)
+    ANCSH_JD_MEDIAN
+}
+
+// np.argmax of one row of jc floats: the first maximum, and the first NaN when the row holds one (numpy treats NaN as the maximum)
+__device__ __forceinline__ int np_argmax_row(const float *r, int jc) {
+    int c = 0;
+    float best = r[0];
+    for (int k = 1; k < jc && best == best; ++k) {
+        const float v = r[k];
+        if (!(v <= best)) { best = v; c = k; }     // v > best, or v is NaN
     }
-    int p2 = 1;
-    while (p2 < cnt) p2 <<= 1;
-    for (int e = cnt + threadIdx.x; e < p2; e += 256)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) vals[c * npow2 + e] = INFINITY;
-    __syncthreads();
-    for (int k = 2; k <= p2; k <<= 1)
-        for (int s = k >> 1; s > 0; s >>= 1) {
-            for (int e = threadIdx.x; e < p2; e += 256) {
-                const int partner = e ^ s;
-                if (partner > e) {
-                    const bool up = (e & k) == 0;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float *v = vals + c * npow2;
-                        const float a = v[e], bb = v[partner];
-                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    if (threadIdx.x < 3) {
-        const float *v = vals + threadIdx.x * npow2;
-        float med = NAN;
-        if (cnt > 0) med = (cnt & 1) ? v[cnt / 2] : (v[cnt / 2 - 1] + v[cnt / 2]) * 0.5f;
-        out[((size_t)b * (K - 1) + (j - 1)) * 3 + threadIdx.x] = med;
-    }
+    return c;
+}
+
+// jt_axis = np.median(joint_axis_per_point[np.argmax(index_per_point, 1) == j], 0)  (lib/parallel_ancsh_pose.py:339-343,366): the joint
+// association from the ANCSH network's index head (jc channels per point) instead of a label array, the argmax taken while compacting --
+// the bytes of joint_direction_kernel fed np.argmax(index, -1).  One workgroup per (cloud, joint).
+__global__ __launch_bounds__(256) void joint_direction_pred_kernel(int n, int K, int jc, const float *__restrict__ axis,
+                                                                   const float *__restrict__ index, float *__restrict__ out) {
+    extern __shared__ float vals[];   // 3 * npow2 floats
+    __shared__ int wcnt[4];
+    const int b = blockIdx.x, j = blockIdx.y + 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int npow2 = 1;
+    while (npow2 < n) npow2 <<= 1;
+    int cnt = 0;
+    ANCSH_JD_COMPACT(np_argmax_row(index + ((size_t)b * n + i) * jc, jc) == j)
+    ANCSH_JD_MEDIAN
 }
 
 // estimateSimilarityUmeyama (lib/aligning.py:580-622) for a batch of (source, target) point sets, float64.
@@ -1937,8 +1974,22 @@ extern "C" int ancsh_pose_poison_records(int b, int n, int K, const float *P, co
     ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 16, "pose_poison_records: bad shape b=%d n=%d K=%d", b, n, K);
     if (b == 0) return ANCSH_OK;
     ANCSH_REQUIRE(P && nocs && W && record, "pose_poison_records: null pointer");
-    hipLaunchKernelGGL(poison_records_kernel, dim3(b), dim3(1024), 0, (hipStream_t)stream, n, K, P, nocs, W, joint_axis, record);
+    hipLaunchKernelGGL(poison_records_kernel<false>, dim3(b), dim3(1024), 0, (hipStream_t)stream, n, K, P, nocs, W, joint_axis, record, 0,
+                       nullptr);
     return check_launch("pose_poison_records");
+}
+
+extern "C" int ancsh_pose_poison_records_pred(int b, int n, int K, const float *P, const float *nocs, const float *W,
+                                              const float *joint_axis, int joint_channels, const float *joint_index, double *record,
+                                              void *stream) {
+    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 16, "pose_poison_records_pred: bad shape b=%d n=%d K=%d", b, n, K);
+    ANCSH_REQUIRE(joint_channels >= 1 && joint_channels <= 64, "pose_poison_records_pred: joint_channels=%d must be in [1,64]",
+                  joint_channels);
+    ANCSH_REQUIRE(P && nocs && W && joint_index && record, "pose_poison_records_pred: null pointer");
+    if (b == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(poison_records_kernel<true>, dim3(b), dim3(1024), 0, (hipStream_t)stream, n, K, P, nocs, W, joint_axis, record,
+                       joint_channels, joint_index);
+    return check_launch("pose_poison_records_pred");
 }
 
 extern "C" int ancsh_pose_joint_direction(int b, int n, int K, const float *joint_axis, const int *joint_cls, float *out,
@@ -1953,6 +2004,24 @@ extern "C" int ancsh_pose_joint_direction(int b, int n, int K, const float *join
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)joint_direction_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(joint_direction_kernel, dim3(b, K - 1), dim3(256), lds, (hipStream_t)stream, n, K, joint_axis, joint_cls, out);
     return check_launch("pose_joint_direction");
+}
+
+extern "C" int ancsh_pose_joint_direction_pred(int b, int n, int K, int joint_channels, const float *joint_axis, const float *joint_index,
+                                               float *out, void *stream) {
+    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 2 && K <= 16, "pose_joint_direction_pred: bad shape b=%d n=%d K=%d (K >= 2: a joint)", b, n, K);
+    ANCSH_REQUIRE(n <= 8192, "pose_joint_direction_pred: n %d > 8192", n);
+    ANCSH_REQUIRE(joint_channels >= 1 && joint_channels <= 64, "pose_joint_direction_pred: joint_channels=%d must be in [1,64]",
+                  joint_channels);
+    ANCSH_REQUIRE(joint_axis && joint_index && out, "pose_joint_direction_pred: null pointer");
+    if (b == 0) return ANCSH_OK;
+    int npow2 = 1;
+    while (npow2 < n) npow2 <<= 1;
+    const size_t lds = (size_t)3 * npow2 * sizeof(float);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void *)joint_direction_pred_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(joint_direction_pred_kernel, dim3(b, K - 1), dim3(256), lds, (hipStream_t)stream, n, K, joint_channels, joint_axis,
+                       joint_index, out);
+    return check_launch("pose_joint_direction_pred");
 }
 
 static FitExtras no_extras() {

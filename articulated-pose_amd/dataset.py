@@ -96,16 +96,25 @@ def create_unit_data_batch(clouds, num_points, norm_factors, n_parts, perms=None
 RAW_NCHAN, RAW_JCLS_COL = 4, 3      # a raw cloud row: x y z joint_cls (a pack_cloud row sliced with [:, [0, 1, 2, 17]])
 
 
-def check_raw_clouds(clouds, norm_factors, max_clouds=None):
+def check_raw_clouds(clouds, norm_factors, max_clouds=None, xyz_only=False):
     """Validate a batch of raw clouds before anything is enqueued: 1..max_clouds non-empty (n_raw, 4) arrays and one finite
-    norm factor per cloud.  -> (list of contiguous float32 (n_raw, 4) arrays, float32 (B,) norm factors); ValueError otherwise."""
+    norm factor per cloud.  -> (list of contiguous float32 (n_raw, 4) arrays, float32 (B,) norm factors); ValueError otherwise.
+    xyz_only=True (a stream whose joint association comes from the network): (n_raw, 3) xyz clouds or (n_raw, 4) ones, whose 4th
+    column is dropped, so one frame source drives both modes -> contiguous float32 (n_raw, 3) arrays."""
     if not isinstance(clouds, (list, tuple)):
-        raise ValueError("clouds must be a list of (n_raw, 4) arrays")
+        raise ValueError("clouds must be a list of (n_raw, %s) arrays" % ("3 or 4" if xyz_only else RAW_NCHAN))
     if not 1 <= len(clouds) <= (max_clouds or 65535):
         raise ValueError("a batch holds 1..%d clouds, got %d" % (max_clouds or 65535, len(clouds)))
     out = []
     for i, c in enumerate(clouds):
-        c = np.ascontiguousarray(c.cpu().numpy() if torch.is_tensor(c) else c, np.float32)
+        c = np.asarray(c.cpu().numpy() if torch.is_tensor(c) else c)
+        if xyz_only:
+            if c.ndim != 2 or c.shape[1] not in (3, RAW_NCHAN) or c.shape[0] == 0:
+                raise ValueError("cloud %d: expected a non-empty (n_raw, 3) array [x y z] (or (n_raw, 4), 4th column ignored), got shape %s"
+                                 % (i, c.shape))
+            out.append(np.ascontiguousarray(c[:, :3], np.float32))
+            continue
+        c = np.ascontiguousarray(c, np.float32)
         if c.ndim != 2 or c.shape[1] != RAW_NCHAN or c.shape[0] == 0:
             raise ValueError("cloud %d: expected a non-empty (n_raw, %d) array [x y z joint_cls], got shape %s" % (i, RAW_NCHAN, c.shape))
         out.append(c)
@@ -140,16 +149,18 @@ def stream_key_words(seed, cloud_base=0):
     return w
 
 
-def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", return_perm=False, cloud_base=None):
+def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", return_perm=False, cloud_base=None, xyz_only=False):
     """Eager wrapper of the streaming sampler (ancsh_input_sample_stream, include/ancsh_hip.h): clouds = list of (n_raw, 4) float32
     arrays [x y z joint_cls]; cloud b's num_points rows are raw rows pi_b(i) % n_raw for the keyed bijection pi_b of the tiled cloud
     (the reference's tiling rule, tiled_size) drawn from `seed` (uint64).  cloud_base: None = the plain entry; an int = the key block
     (ancsh_input_sample_stream_keyed): cloud b is keyed as global cloud cloud_base + b.
+    xyz_only=True: the xyz twins (ancsh_input_sample_stream_xyz / _xyz_keyed) on (n_raw, 3) clouds (a 4th column is dropped): the same
+    P and perm, no joint_cls.
     -> dict(P (B,N,3) float32 = xyz * norm_factor, joint_cls (B,N) int32 [, perm (B,N) int32 = pi_b(i)]) on `device`."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
-    clouds, nf = check_raw_clouds(clouds, norm_factors)
+    clouds, nf = check_raw_clouds(clouds, norm_factors, xyz_only=xyz_only)
     B = len(clouds)
     offsets = np.zeros(B + 1, np.int32)
     offsets[1:] = np.cumsum([c.shape[0] for c in clouds])
@@ -162,8 +173,12 @@ def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", re
         entry = "ancsh_input_sample_stream_keyed"
         seed_d = torch.from_numpy(stream_key_words(seed, check_stream_key(cloud_base, B, 1))).to(dev)
     P = torch.empty((B, num_points, 3), dtype=torch.float32, device=dev)
-    jcls = torch.empty((B, num_points), dtype=torch.int32, device=dev)
     perm = torch.empty((B, num_points), dtype=torch.int32, device=dev) if return_perm else None
+    if xyz_only:
+        _lib.call(entry.replace("_stream", "_stream_xyz"), B, int(num_points), 3, _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(off),
+                  _lib.ptr(nf_d), _lib.ptr(seed_d), _lib.ptr(P), _lib.ptr(perm))
+        return dict(P=P, perm=perm) if return_perm else dict(P=P)
+    jcls = torch.empty((B, num_points), dtype=torch.int32, device=dev)
     _lib.call(entry, B, int(num_points), RAW_NCHAN, _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(off),
               _lib.ptr(nf_d), RAW_JCLS_COL, _lib.ptr(seed_d), _lib.ptr(P), _lib.ptr(jcls), _lib.ptr(perm))
     out = dict(P=P, joint_cls=jcls)

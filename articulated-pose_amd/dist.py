@@ -308,10 +308,19 @@ class ShardedPipeline(object):
     articulation=True (with raw_capacity only): the stream also yields the (n_valid, K, 12) articulation blocks, packed with the records
     into the same gather; step() / records() over RCCL do not carry them.
     dense=True (with raw_capacity only): the stream also yields every raw row's (labels, values, offsets) (AncshPipeline(dense=True)),
-    gathered on dst in global cloud order by one more padded gather per batch."""
+    gathered on dst in global cloud order by one more padded gather per batch.
+    joint_source ("gt" | "predicted"): passed to every rank's pipeline (AncshPipeline(joint_source=...)).  "predicted": solve(P, None,
+    pred) and load_inputs(P, None, pred) need no labels, and the raw stream takes (n_raw, 3) xyz clouds (or (n_raw, 4), 4th column
+    ignored) through the keyed xyz sampler."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
-                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, **pipeline_kw):
+                 slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
+                 **pipeline_kw):
+        from .pipeline import check_joint_source
+        self.joint_source = check_joint_source(joint_source)
+        if joint_source != "gt":           # the default is not passed on: a per-rank stand-in built before joint_source need not know it
+            pipeline_kw.update(joint_source=joint_source)
+        self.couple = bool(pipeline_kw.get("couple", True))
         # articulation (raw streams only): every rank's pipeline appends the (n, K, 12) articulation block, and retire() gathers it with the
         # records in the SAME gather -- one (n_max, K, 38) float64 row per rank, split on dst.  step() / records() (the RCCL path) do not
         # carry it.
@@ -355,12 +364,15 @@ class ShardedPipeline(object):
         self._stream_bufs = None
 
     # ---- inputs -------------------------------------------------------------------------------------------------------------
-    def load_inputs(self, P, joint_cls, pred=None, slot=None, is_global=True):
-        """is_global: arrays hold the whole batch (global_batch leading) and this rank takes rows [lo, hi); else they ARE the shard."""
+    def load_inputs(self, P, joint_cls=None, pred=None, slot=None, is_global=True):
+        """is_global: arrays hold the whole batch (global_batch leading) and this rank takes rows [lo, hi); else they ARE the shard.
+        joint_cls: None with joint_source="predicted" (the association is pred['index_per_point'] or the network's own head)."""
+        from .pipeline import check_joint_inputs
+        check_joint_inputs(self.joint_source, self.couple, joint_cls, pred)
         if is_global:
             if len(P) != self.global_batch:
                 raise ValueError("expected %d clouds, got %d" % (self.global_batch, len(P)))
-            cut = lambda a: a[self.lo:self.hi]
+            cut = lambda a: None if a is None else a[self.lo:self.hi]
             P, joint_cls = cut(P), cut(joint_cls)
             pred = None if pred is None else {k: cut(v) for k, v in pred.items()}
         self.pipe.load_inputs(P, joint_cls, pred, slot=slot)
@@ -427,7 +439,7 @@ class ShardedPipeline(object):
             parts.append(bufs[r][: e - s])
         return torch.cat(parts, dim=0)
 
-    def solve(self, P, joint_cls, pred=None, is_global=True):
+    def solve(self, P, joint_cls=None, pred=None, is_global=True):
         """One global batch end to end: shard, run, gather, wait.  Returns records() (dst) / None (other ranks)."""
         self.load_inputs(P, joint_cls, pred, is_global=is_global)
         if getattr(self.pipe, "slots", None) and getattr(self.pipe.slots[0], "out", None) is None and hasattr(self.pipe, "prepare"):
@@ -447,7 +459,7 @@ class ShardedPipeline(object):
         """The checks of AncshPipeline.submit on EVERY rank's shard, so that every rank raises the same ValueError (before anything is
         enqueued and before any collective) or none does.  -> (clouds, norm factors) as check_raw_clouds returns them."""
         from .dataset import check_raw_clouds, check_stream_key
-        clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch)
+        clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch, xyz_only=self.joint_source == "predicted")
         for r in range(self.world):
             s, e = self.shard_of(len(clouds), r)
             if e == s:

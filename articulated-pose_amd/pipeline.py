@@ -61,16 +61,40 @@ def f16x2_weight_violations(nets):
     return f16_range_violations(kernels)
 
 
+JOINT_SOURCES = ("gt", "predicted")
+
+
+def check_joint_source(joint_source):
+    """-> joint_source if it names one of JOINT_SOURCES; ValueError otherwise (before anything touches the GPU)."""
+    if joint_source not in JOINT_SOURCES:
+        raise ValueError("joint_source must be one of %s, got %r" % (JOINT_SOURCES, joint_source))
+    return joint_source
+
+
+def check_joint_inputs(joint_source, couple, joint_cls, pred):
+    """The joint association a load_inputs() call must carry, checked before anything is copied: "gt" needs joint_cls (a label per
+    point); "predicted" with couple=False needs pred["index_per_point"] (the ANCSH network's index head, (B, N, C)); "predicted" with
+    couple=True reads the head from the step's own forward and needs neither.  ValueError otherwise."""
+    check_joint_source(joint_source)
+    if joint_source == "gt":
+        if joint_cls is None:
+            raise ValueError("joint_source='gt' fits the joints from joint_cls: load_inputs(P, joint_cls, ...) needs it")
+    elif not couple and (pred is None or pred.get("index_per_point") is None):
+        raise ValueError("joint_source='predicted' with couple=False reads the joint association from pred['index_per_point']: "
+                         "load_inputs(P, None, pred=...) must include it")
+
+
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
         self.pred_nocs = torch.zeros((B, N, 3 * K), **f)
         self.pred_mask = torch.zeros((B, N, K), **f)
         self.pred_axis = torch.zeros((B, N, 3), **f)
+        self.pred_index = None                  # joint_source="predicted", couple=False: the (B, N, C) index head load_inputs() supplies
         self.draws_a = self.draws_b = None      # optional replayed sample streams (see AncshPipeline.load_draws)
         self.stream = torch.cuda.Stream(device=device)
         self.graph = None
@@ -83,12 +107,14 @@ class _Slot(object):
             # streaming: raw rows + a header [seed (int64 bits) | offsets (B+1) int32 | norm factors (B) float32] on the device, their
             # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again.
             # keyed: the header leads with the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) instead of the seed
+            # xyz (joint_source="predicted"): rows of x y z only -- no joint-class column, a quarter fewer bytes per batch to the device
             from .dataset import RAW_NCHAN
             self.keyed = bool(keyed)
+            self.nchan = 3 if xyz else RAW_NCHAN
             lead = 4 if self.keyed else 2
-            self.raw_rows = torch.zeros((raw_capacity, RAW_NCHAN), **f)
+            self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
             self.hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32, device=device)
-            self.h_rows = torch.zeros((raw_capacity, RAW_NCHAN), dtype=torch.float32).pin_memory()
+            self.h_rows = torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
             self.h_hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32).pin_memory()
             self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             self.h2d_done = torch.cuda.Event()
@@ -117,7 +143,8 @@ class _Slot(object):
             # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
             rs = np.random.RandomState(0)
             self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
-            self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
+            if not xyz:
+                self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
             self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
             self.np_nf[:] = 1.0
             self.raw_rows.copy_(self.h_rows)
@@ -156,7 +183,14 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False):
+                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt"):
+        # joint_source: stage B's joint association.  "gt" (default) = a label per point -- load_inputs' joint_cls, or the 4th column
+        # [x y z joint_cls] of a streamed raw row (the rendered test split's ground truth, evaluation/parallel_ancsh_pose.py:295).
+        # "predicted" = the argmax of the ANCSH network's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366), from the step's
+        # own forward (couple=True) or load_inputs' pred["index_per_point"] (couple=False): no label is read, a stream takes plain
+        # (n_raw, 3) xyz clouds (a 4th column is accepted and ignored) and its slots hold 3-column rows.  Same launch count either way.
+        self.joint_source = check_joint_source(joint_source)
+        self.predicted = joint_source == "predicted"
         self.K, self.B, self.N = num_parts, batch_size, num_points
         # articulation: the captured step ends with one more launch (ancsh_articulation_rec) that turns the networks' heads and the pose
         # record into the (B, K, 12) block of part boxes and camera-space joints (pose.joint_params.articulation_batch): out["articulation"],
@@ -171,7 +205,7 @@ class AncshPipeline(object):
                 raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
                                  % (ARTICULATION_MAX_N, num_points))
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
-        # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls) per batch, padding included
+        # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls; predicted: x y z) per batch, padding included
         if raw_capacity is not None:
             if not couple:
                 raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
@@ -227,7 +261,7 @@ class AncshPipeline(object):
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
-                            self.dense) for _ in range(max(1, slots))]
+                            self.dense, xyz=self.predicted) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -240,14 +274,38 @@ class AncshPipeline(object):
     def P(self):
         return self.slots[0].P
 
-    def load_inputs(self, P, joint_cls, pred=None, slot=None):
+    def load_inputs(self, P, joint_cls=None, pred=None, slot=None):
+        """P (B, N, 3); joint_cls (B, N) int (joint_source="gt"; ignored when "predicted"); pred: the pose stage's inputs for couple=False
+        (nocs_per_point, instance_per_point, joint_axis_per_point and, when "predicted", index_per_point (B, N, C)).  The joint
+        association is checked (check_joint_inputs) before anything is copied."""
+        check_joint_inputs(self.joint_source, self.couple, joint_cls, pred)
+        index = None
+        if self.predicted and pred is not None and pred.get("index_per_point") is not None:
+            index = torch.as_tensor(pred["index_per_point"])
+            if index.dim() != 3 or tuple(index.shape[:2]) != (self.B, self.N):
+                raise ValueError("pred['index_per_point'] must be (%d, %d, C), got %s" % (self.B, self.N, tuple(index.shape)))
+            if self._prepared and any(sl.pred_index is not None and sl.pred_index.shape != index.shape for sl in self.slots):
+                raise ValueError("pred['index_per_point'] changed shape after prepare(): the captured step reads a (B, N, %d) buffer"
+                                 % self.slots[0].pred_index.shape[2])
         for sl in (self.slots if slot is None else [self.slots[slot]]):
             sl.P.copy_(torch.as_tensor(P))
-            sl.joint_cls.copy_(torch.as_tensor(np.asarray(joint_cls, np.int32)) if not torch.is_tensor(joint_cls) else joint_cls)
+            if not self.predicted:
+                sl.joint_cls.copy_(torch.as_tensor(np.asarray(joint_cls, np.int32)) if not torch.is_tensor(joint_cls) else joint_cls)
             if pred is not None:
                 sl.pred_nocs.copy_(torch.as_tensor(pred["nocs_per_point"]))
                 sl.pred_mask.copy_(torch.as_tensor(pred["instance_per_point"]))
                 sl.pred_axis.copy_(torch.as_tensor(pred["joint_axis_per_point"]))
+            if index is not None:
+                if sl.pred_index is None or sl.pred_index.shape != index.shape:
+                    sl.pred_index = torch.zeros(tuple(index.shape), dtype=torch.float32, device=self.device)
+                sl.pred_index.copy_(index)
+
+    def _check_index_loaded(self):
+        """joint_source="predicted" with couple=False: every slot needs the index head load_inputs() supplies -- checked before any GPU
+        work of prepare() / step()."""
+        if self.predicted and not self.couple and any(sl.pred_index is None for sl in self.slots):
+            raise ValueError("joint_source='predicted' with couple=False: no index head loaded -- call load_inputs(P, None, "
+                             "pred={..., 'index_per_point': ...}) first")
 
     def load_draws(self, draws_a, draws_b, slot=None):
         """Replay explicit 3-point sample streams (e.g. numpy's, `pose.parallel_ancsh_pose.draws_from_seed`) instead of the
@@ -267,6 +325,10 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.predicted:                 # xyz rows: the sampler's xyz twin, same P (no joint_cls: the fit reads the index head)
+            _lib.call("ancsh_input_sample_stream_xyz_keyed" if self.keyed else "ancsh_input_sample_stream_xyz", self.B, self.N, sl.nchan,
+                      _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), _lib.ptr(seed), _lib.ptr(sl.P), None)
+            return seed
         _lib.call("ancsh_input_sample_stream_keyed" if self.keyed else "ancsh_input_sample_stream", self.B, self.N, RAW_NCHAN,
                   _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P),
                   _lib.ptr(sl.joint_cls), None)
@@ -286,10 +348,12 @@ class AncshPipeline(object):
         a, n = self._networks(sl.P, geom, "f32" if f32 else self.arithmetic, sl.flags if guard else None)
         if self.couple:
             nocs, mask, axis = n["nocs_per_point"], n["W"], a["joint_axis_per_point"]
+            index = a["index_per_point"] if self.predicted else None
         else:
-            nocs, mask, axis = sl.pred_nocs, sl.pred_mask, sl.pred_axis
-        sol = self.solver.solve(sl.P, nocs, mask, axis, sl.joint_cls, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
-                                key_dev=key_dev)
+            nocs, mask, axis, index = sl.pred_nocs, sl.pred_mask, sl.pred_axis, sl.pred_index if self.predicted else None
+        assoc = dict(joint_index=index) if self.predicted else dict(joint_cls=sl.joint_cls)      # one of them: the solver refuses both
+        sol = self.solver.solve(sl.P, nocs, mask, axis, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
+                                key_dev=key_dev, **assoc)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
@@ -303,6 +367,7 @@ class AncshPipeline(object):
         return out
 
     def prepare(self):
+        self._check_index_loaded()
         torch.cuda.synchronize(self.device)
         for sl in self.slots:
             with torch.cuda.stream(sl.stream):
@@ -347,6 +412,7 @@ class AncshPipeline(object):
         same holds for out["articulation"], the (B, K, 12) block of articulation=True).
         Whatever the caller enqueued on ITS current stream before calling step() (a clone or a gather of the slot's previous outputs) is
         ordered before the new batch: the slot's stream waits for that stream here.  A consumer on any other stream is the caller's to order."""
+        self._check_index_loaded()
         sl = self.slots[self._next]
         self._next = (self._next + 1) % len(self.slots)
         cur = torch.cuda.current_stream(self.device)
@@ -380,7 +446,8 @@ class AncshPipeline(object):
     # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
     def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0):
         """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
-        sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.  A short batch
+        sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.
+        joint_source="predicted": (n_raw, 3) xyz clouds, or (n_raw, 4) ones whose 4th column is ignored.  A short batch
         is padded with copies of its first cloud, whose records retire() drops.  seed: the generator key of the batch's sampling and
         of its pose fit (stage B uses seed + 1); None = self.seed + 2k for the k-th submitted batch (2k + 1 is its stage B).
         cloud_base (keyed=True only; written into the pinned header with the seed): the global index of the batch's cloud 0 -- cloud b
@@ -394,7 +461,7 @@ class AncshPipeline(object):
             cloud_base = check_stream_key(cloud_base, self.B, self.K)
         elif cloud_base != 0:
             raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
-        clouds, nf = check_raw_clouds(clouds, norm_factors, self.B)
+        clouds, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
         n_valid = len(clouds)
         padded = clouds + [clouds[0]] * (self.B - n_valid)
         rows = sum(c.shape[0] for c in padded)

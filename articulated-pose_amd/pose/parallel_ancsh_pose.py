@@ -178,8 +178,8 @@ class PoseSolver(object):
         self.lm_schedule = lm_schedule         # "latency": eight lanes per LM fit (a lone batch finishes sooner); "throughput": one
         self.want_lm_stat = want_lm_stat       # also return per-hypothesis (status, nfev) of the stage-B LM fits
 
-    def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls, draws_a=None, draws_b=None, seed=0, seed_dev=None,
-              key_dev=None):
+    def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls=None, draws_a=None, draws_b=None, seed=0, seed_dev=None,
+              key_dev=None, joint_index=None):
         """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and it is the
         latency-bound half (64 waves for 1.6 ms: MINPACK's longest trajectory), so it is ISSUED FIRST: its LM kernel then runs
         under the full-chip scoring kernel of other batches in flight, and a batch ends with 0.3 ms of stage A instead of idling
@@ -190,9 +190,16 @@ class PoseSolver(object):
         bytes equal those of seed=<that value>.
         key_dev: a 16-byte device key block (include/ancsh_hip.h, ancsh_stream_key; dataset.stream_key_words) instead of either: its
         seed is read as seed_dev's, and cloud b is keyed as global cloud cloud_base + b -- so a shard of clouds [lo, hi) solved with
-        cloud_base = lo gives the bytes of rows [lo, hi) of the whole batch's solve(seed=<that seed>)."""
+        cloud_base = lo gives the bytes of rows [lo, hi) of the whole batch's solve(seed=<that seed>).
+        joint_cls / joint_index -- exactly one of them: the joint association of stage B's directions.  joint_cls (B,N) int = a label
+        per point (the ANCSH record's joint_cls_gt, :295); joint_index (B,N,C) float32 = the ANCSH network's index_per_point head, whose
+        np.argmax per point is the label (lib/parallel_ancsh_pose.py:339-343,366; ancsh_pose_joint_direction_pred, which takes it while
+        compacting, and ancsh_pose_poison_records_pred, which also poisons a cloud with a non-finite index value).  The records then
+        equal those of joint_cls = np.argmax(joint_index, -1); a joint no point selects has a NaN direction and NaN stage-B rows
+        (certain when K - 1 >= C)."""
+        _one_association(joint_cls, joint_index)
         out = self._partition(P, nocs_pred, mask_pred)
-        self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev)
+        self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index)
         return self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):
@@ -208,7 +215,13 @@ class PoseSolver(object):
         B, N = out["_shape"]
         P, nocs, W = out["_inputs"]
         axis = out.get("_axis")                   # stage B's joint-axis field (K > 1 and stage B ran)
-        _lib.call("ancsh_pose_poison_records", B, N, self.K, _lib.ptr(P), _lib.ptr(nocs), _lib.ptr(W), _lib.ptr(axis), _lib.ptr(out["record"]))
+        index = out.get("_index")                 # stage B's index head (joint_index given): scanned too, by the one poison launch
+        if index is not None:
+            _lib.call("ancsh_pose_poison_records_pred", B, N, self.K, _lib.ptr(P), _lib.ptr(nocs), _lib.ptr(W), _lib.ptr(axis),
+                      int(index.shape[2]), _lib.ptr(index), _lib.ptr(out["record"]))
+        else:
+            _lib.call("ancsh_pose_poison_records", B, N, self.K, _lib.ptr(P), _lib.ptr(nocs), _lib.ptr(W), _lib.ptr(axis),
+                      _lib.ptr(out["record"]))
         return out
 
     def _partition(self, P, nocs_pred, mask_pred):
@@ -247,22 +260,33 @@ class PoseSolver(object):
             out["nonlinear"] = out["record"][:, :, 13:]           # a one-part object: the finish kernel wrote the baseline there too
         return out
 
-    def solve_stage_b(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None):
+    def solve_stage_b(self, out, joint_axis_per_point, joint_cls=None, draws_b=None, seed=0, seed_dev=None, key_dev=None,
+                      joint_index=None):
         """Articulated joint fit (stage B, :274-341) on top of a solve_stage_a result (key seed + 1, or *seed_dev + 1 / the key block's
         seed + 1 read on the device).  The records are poisoned again afterwards, now with the joint-axis field among the inputs: a
-        cloud with a non-finite value there gets an all-NaN record on this path too."""
-        return self._poison(self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev))
+        cloud with a non-finite value there gets an all-NaN record on this path too.  joint_cls / joint_index: exactly one, as in solve()
+        (with joint_index the index head is among the poison's inputs as well)."""
+        _one_association(joint_cls, joint_index)
+        return self._poison(self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index))
 
-    def _stage_b_fits(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None):
+    def _stage_b_fits(self, out, joint_axis_per_point, joint_cls, draws_b=None, seed=0, seed_dev=None, key_dev=None, joint_index=None):
         dev, K = self.device, self.K
         B, N = out["_shape"]
         src, tgt, max_n = out["_src"], out["_tgt"], out["_max_n"]
         rng0, rng1 = out["_rng"]                                   # written by the partition kernel
         if K > 1:
-            axis, jcls = _f32(joint_axis_per_point, dev), _i32(joint_cls, dev)
+            axis = _f32(joint_axis_per_point, dev)
             out["_axis"] = axis
             jdir = torch.empty((B, K - 1, 3), dtype=torch.float32, device=dev)
-            _lib.call("ancsh_pose_joint_direction", B, N, K, _lib.ptr(axis), _lib.ptr(jcls), _lib.ptr(jdir))
+            if joint_index is not None:            # the network's association: argmax of the index head, taken by the direction kernel
+                index = _f32(joint_index, dev)
+                if index.dim() != 3 or tuple(index.shape[:2]) != (B, N):
+                    raise ValueError("joint_index must be (B, N, C) for %d clouds of %d points, got %s" % (B, N, tuple(index.shape)))
+                out["_index"] = index
+                _lib.call("ancsh_pose_joint_direction_pred", B, N, K, int(index.shape[2]), _lib.ptr(axis), _lib.ptr(index), _lib.ptr(jdir))
+            else:
+                jcls = _i32(joint_cls, dev)
+                _lib.call("ancsh_pose_joint_direction", B, N, K, _lib.ptr(axis), _lib.ptr(jcls), _lib.ptr(jdir))
             b = ransac_joint_batch(rng0, rng1, src, tgt, jdir.view(-1, 3), self.th, self.niter_b,
                                    None if draws_b is None else _i32(draws_b, dev).reshape(B * (K - 1), self.niter_b, 6),
                                    seed + 1, max_n, want_lm_stat=self.want_lm_stat, lm_schedule=self.lm_schedule,
@@ -279,6 +303,13 @@ class PoseSolver(object):
         else:
             out["nonlinear"] = out["record"][:, :, 13:]          # K = 1: filled by _stage_a_fits' finish kernel
         return out
+
+
+def _one_association(joint_cls, joint_index):
+    """Stage B's joint association: ground-truth labels or the network's index head, exactly one of them."""
+    if (joint_cls is None) == (joint_index is None):
+        raise ValueError("give exactly one of joint_cls (a label per point) and joint_index (the index_per_point head), got %s"
+                         % ("both" if joint_cls is not None else "neither"))
 
 
 def _model_to_rst(m):
@@ -320,11 +351,18 @@ def records_from_solution(sol, rts_list=None):
     return recs
 
 
+JOINT_SOURCES = ("gt", "predicted")
+
+
 def solver_ransac_nonlinear(s_ind, e_ind, test_exp, baseline_exp, choose_threshold, num_parts, test_group, problem_ins,
-                            rts_all, file_name, base_path=None, batch_size=32, seed=0, device="cuda:0"):
+                            rts_all, file_name, base_path=None, batch_size=32, seed=0, device="cuda:0", joint_source="gt"):
     """Same positional signature as the reference entry point (:196): solves test_group[s_ind:e_ind] and
     pickles {basename: record}.  Records are read with prediction_io.load_record from
-    <base_path>/results/test_pred/<exp>/<basename>.{h5,npz} (USE_BASELINE: NOCS + mask from baseline_exp)."""
+    <base_path>/results/test_pred/<exp>/<basename>.{h5,npz} (USE_BASELINE: NOCS + mask from baseline_exp).
+    joint_source: "gt" = stage B associates points to joints by the record's joint_cls_gt (:295); "predicted" = by the argmax of the
+    record's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366) -- what the ground-truth association is worth."""
+    if joint_source not in JOINT_SOURCES:
+        raise ValueError("joint_source must be one of %s, got %r" % (JOINT_SOURCES, joint_source))
     from .. import prediction_io
     base_path = base_path or os.environ.get("ANCSH_BASE_PATH", ".")
     solver = PoseSolver(num_parts, choose_threshold, device=device)
@@ -336,7 +374,8 @@ def solver_ransac_nonlinear(s_ind, e_ind, test_exp, baseline_exp, choose_thresho
         fb = [prediction_io.load_record(os.path.join(base_path, 'results/test_pred', str(baseline_exp)), n) for n in chunk]
         sol = solver.solve(np.stack([r['P'][:, :3] for r in f]), np.stack([r['nocs_per_point'] for r in fb]),
                            np.stack([r['instance_per_point'] for r in fb]), np.stack([r['joint_axis_per_point'] for r in f]),
-                           np.stack([r['joint_cls_gt'] for r in f]), seed=seed + c0)
+                           **({"joint_index": np.stack([r['index_per_point'] for r in f])} if joint_source == "predicted" else
+                              {"joint_cls": np.stack([r['joint_cls_gt'] for r in f])}), seed=seed + c0)
         gts = [rts_all[n] for n in chunk] if rts_all is not None else None
         for n, rec in zip(chunk, records_from_solution(sol, gts)):
             all_rts[n] = rec

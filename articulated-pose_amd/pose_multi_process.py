@@ -15,6 +15,7 @@ import time
 from .dist import launch_local_ranks, shard_range, wants_self_launch
 from .global_info import get_test_group, global_info
 from .pose import solver_ransac_nonlinear
+from .pose.parallel_ancsh_pose import JOINT_SOURCES
 
 
 def _device_index():
@@ -23,7 +24,7 @@ def _device_index():
     return int(os.environ.get('LOCAL_RANK', 0)) % max(1, torch.cuda.device_count())
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--domain', default='unseen', help='which sub test set to choose')
     ap.add_argument('--nocs', default='ANCSH', help='which sub test set to choose')
@@ -31,7 +32,14 @@ def main(argv=None):
     ap.add_argument('--base_path', default=None)
     ap.add_argument('--batch_size', type=int, default=32)
     ap.add_argument('--gpus', type=int, default=None, help='worker ranks to start, one per MI355X (default: every visible GPU)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--joint_source', default='gt', choices=JOINT_SOURCES,
+                    help="stage B's joint association: the record's joint_cls_gt (gt, the reference's rule) or the argmax of its "
+                         "index_per_point head (predicted: what a depth frame without labels gets)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if 'WORLD_SIZE' not in os.environ or wants_self_launch(args.gpus or 0):
         import torch
         n_ranks = args.gpus or torch.cuda.device_count()
@@ -54,7 +62,7 @@ def main(argv=None):
     t0 = time.time()
     solver_ransac_nonlinear(s, e, d.exp, d.baseline, choose_threshold, d.num_parts, test_group, [], rts_all, sub,
                             base_path=my_dir, batch_size=args.batch_size, seed=rank,
-                            device='cuda:%d' % _device_index())
+                            device='cuda:%d' % _device_index(), joint_source=args.joint_source)
     print('rank {}: {} clouds in {:.2f} s -> {}'.format(rank, e - s, time.time() - t0, sub))
 
 

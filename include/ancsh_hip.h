@@ -41,7 +41,9 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 12: + ancsh_raw_point_labels (per-raw-point labels and head values of a streamed batch);
+int ancsh_abi_version(void);   /* 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
+                                 *     ancsh_input_sample_stream_xyz_keyed (the joint association from the network's index head; xyz-only raw rows);
+                                 * 12: + ancsh_raw_point_labels (per-raw-point labels and head values of a streamed batch);
                                  * 11: + ancsh_articulation_rec (the streamed articulation block);
                                  * 10: + ancsh_input_sample_stream_keyed, ancsh_ransac_single_rec_dkey, ancsh_ransac_joint_rec_dkey (ancsh_stream_key);
                                  * 9: + the F16x2 range guard (ancsh_*_f16x2*_guarded);
@@ -458,10 +460,27 @@ int ancsh_pose_partition(int b, int n, int K, const float *W, const float *P, co
 int ancsh_pose_poison_records(int b, int n, int K, const float *P, const float *nocs, const float *W, const float *joint_axis,
                               double *record, void *stream);
 
+/* ancsh_pose_poison_records for a fit whose joint association comes from the ANCSH network's index head (ABI 13): the same scan plus
+ * joint_index (b, n, joint_channels) float32, so a non-finite value there poisons the cloud's record as well.  The predicted-association
+ * fit calls this INSTEAD of ancsh_pose_poison_records (one launch either way).  Checked before any launch: the shape, 1 <= joint_channels
+ * <= 64, null pointers (joint_axis may be NULL). */
+int ancsh_pose_poison_records_pred(int b, int n, int K, const float *P, const float *nocs, const float *W, const float *joint_axis,
+                                   int joint_channels, const float *joint_index, double *record, void *stream);
+
 /* jt_axis = np.median(joint_axis_per_point[joint_cls == j], 0), j = 1..K-1 (:295).
  * joint_axis (b,n,3), joint_cls (b,n) int32 -> out (b, K-1, 3) float32 (NaN for an empty selection). */
 int ancsh_pose_joint_direction(int b, int n, int K, const float *joint_axis, const int *joint_cls, float *out,
                                void *stream);
+
+/* jt_axis = np.median(joint_axis_per_point[np.argmax(joint_index, 1) == j], 0), j = 1..K-1 (lib/parallel_ancsh_pose.py:339-343,366;
+ * evaluation/eval_joint_params.py:133-134): the joint association taken from the ANCSH network's index head instead of a label array
+ * (ABI 13).  joint_index (b, n, joint_channels) float32; the argmax is np.argmax's (the first maximum; a row holding a NaN selects its
+ * first NaN channel), taken while compacting, in the same launch.  The result is the bytes of ancsh_pose_joint_direction fed
+ * np.argmax(joint_index, -1).astype(np.int32) -- NaN for a joint no point selects.  Such a joint is CERTAIN when K - 1 >= joint_channels
+ * (the reference's rule: drawer, K = 4, with the 3-wide head never selects joint 3).  Checked before any launch: 2 <= K <= 16,
+ * 1 <= n <= 8192, 1 <= joint_channels <= 64, null pointers. */
+int ancsh_pose_joint_direction_pred(int b, int n, int K, int joint_channels, const float *joint_axis, const float *joint_index,
+                                    float *out, void *stream);
 
 /* Batched replacement of ransac(dataset, single_transformation_estimator, single_transformation_verifier,
  * inlier_th, niter) (:20-54, with transform_pts / rotate_pts / scale_pts of lib/d3_utils.py:206-246).
@@ -719,6 +738,16 @@ int ancsh_input_sample_stream(int nclouds, int num_points, int nchan, const floa
 int ancsh_input_sample_stream_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
                                     const float *norm_factor, int jcls_col, const ancsh_stream_key *key, float *P, int *joint_cls,
                                     int *perm_out, void *stream);
+
+/* The xyz-only twins of the two entries above (ABI 13): rows of nchan >= 3 channels, x y z first, no joint-class channel, no
+ * joint_cls output.  P and perm_out are bit-equal to those of ancsh_input_sample_stream / _keyed on the same xyz, seed, key and
+ * cloud_base (the permutation depends only on n_raw, the key and the cloud index).  The same kernel behind a template flag; the 4-column
+ * instantiations are unchanged.  Checked before any launch: nchan >= 3, 0 <= capacity < 2^30, nclouds <= 65535, null seed / key, null
+ * pointers (perm_out may be NULL). */
+int ancsh_input_sample_stream_xyz(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                                  const float *norm_factor, const unsigned long long *seed, float *P, int *perm_out, void *stream);
+int ancsh_input_sample_stream_xyz_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
+                                        const float *norm_factor, const ancsh_stream_key *key, float *P, int *perm_out, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -3,12 +3,15 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
+                                 [--joint-source {gt,predicted}]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
 line then also carries the rerun count, the latency of the batches that reran and the device memory the streaming pipeline holds.
 --articulation streams with AncshPipeline(articulation=True) (the record plus the (n, K, 12) articulation block per cloud).
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
+--joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
+head) and submits (n_raw, 3) xyz clouds: no label column crosses to the device.
 """
 import argparse
 import json
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--overflow-every", type=int, default=0)
     ap.add_argument("--articulation", action="store_true", help="stream with AncshPipeline(articulation=True) and retire the blocks too")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
+    ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
+                    help="predicted: the joint association from the network's index head; (n_raw, 3) xyz clouds are submitted")
     args = ap.parse_args()
     if args.range_guard and args.arithmetic != "f16x2":
         ap.error("--range-guard needs --arithmetic f16x2")
@@ -48,6 +53,9 @@ def main():
     for i, n in enumerate(sizes):
         c = make_cloud(i, N=int(n), K=K)
         raw.append(np.concatenate([c["P"], c["cls_gt"][:, None].astype(np.float32)], 1))
+    predicted = args.joint_source == "predicted"
+    if predicted:
+        raw = [np.ascontiguousarray(r[:, :3]) for r in raw]
     batches = [(raw[i:i + B], np.ones(B, np.float32)) for i in range(0, len(raw) - B + 1, B)]
     if args.overflow_every:
         for k in range(0, len(batches), args.overflow_every):
@@ -58,7 +66,8 @@ def main():
     torch.cuda.synchronize()
     mem0 = torch.cuda.mem_get_info(dev)[0]
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
-                         range_guard=args.range_guard, articulation=args.articulation, dense=args.dense).prepare()
+                         range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
+                         joint_source=args.joint_source).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
@@ -92,9 +101,9 @@ def main():
     # baseline: the same clouds sampled once up front, then load_inputs + step() per batch, the slot's previous record read back
     pre = []
     for k, (c, nf) in enumerate(batches):
-        s = sample_raw_batch(c, N, nf, k, dev)
-        pre.append((s["P"].cpu().numpy(), s["joint_cls"].cpu().numpy()))
-    base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, arithmetic=args.arithmetic)
+        s = sample_raw_batch(c, N, nf, k, dev, xyz_only=predicted)
+        pre.append((s["P"].cpu().numpy(), None if predicted else s["joint_cls"].cpu().numpy()))
+    base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, arithmetic=args.arithmetic, joint_source=args.joint_source)
     base.load_inputs(*pre[0])
     base.prepare()
 
@@ -132,6 +141,8 @@ def main():
                      "batch_latency_ms_median": round(1e3 * float(np.median(lat)), 2)})
     if args.articulation:
         line.update({"articulation": True, "blocks_out": n_blocks})
+    if predicted:
+        line.update({"joint_source": "predicted"})
     if args.dense:
         line.update({"dense": True, "raw_rows_out": n_rows, "dense_d2h_bytes_per_batch": round(n_rows * 32 / (args.passes * len(batches)))})
     print(json.dumps(line))
