@@ -110,6 +110,13 @@ SIGNATURES = {
     "ancsh_pose_poison_records_pred": [_c_int, _c_int, _c_int] + [_vp] * 4 + [_c_int, _vp, _vp, _vp],
     "ancsh_input_sample_stream_xyz": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _vp],
     "ancsh_input_sample_stream_xyz_keyed": [_c_int, _c_int, _c_int, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _vp],
+    # ABI 14: a joint kind per stage-B problem (0 revolute, 1 prismatic) -- the entry's arguments, then joint_kind, then the stream
+    "ancsh_ransac_joint_rec_kind": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]
+                                   + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, _vp],
+    "ancsh_ransac_joint_rec_dseed_kind": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
+                                         + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, _vp],
+    "ancsh_ransac_joint_rec_dkey_kind": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
+                                        + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, _vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

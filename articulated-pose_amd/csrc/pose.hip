@@ -699,7 +699,8 @@ struct PartFd {
     double ju[3];      // Rod(J, r)
     double jd[3][3];   // jd[c][q] = (Rod(J, r + h_q e_q)[c] - Rod(J, r)[c]) / h_q
 
-    __device__ __forceinline__ void begin(const double r[3], const double J[3]) {
+    // the point rows' half of begin(): all a prismatic problem needs (its constraint rows never rotate the joint direction)
+    __device__ __forceinline__ void begin_points(const double r[3]) {
         b = rod_prepare(r[0], r[1], r[2]);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -710,6 +711,9 @@ struct PartFd {
 #pragma unroll
         for (int i = 0; i < 6; ++i) blk[i] = 0.0;
         gv[0] = gv[1] = gv[2] = 0.0;
+    }
+    __device__ __forceinline__ void begin(const double r[3], const double J[3]) {
+        begin_points(r);
         rod_apply(b, J[0], J[1], J[2], ju[0], ju[1], ju[2]);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -768,8 +772,43 @@ __device__ __forceinline__ void assemble_normal(const PartFd &p0, const double b
     }
 }
 
-// Thread-local articulated problem on 3 + 3 sampled points.
-struct HypProblem {
+// ---- the prismatic objective (objective_eval_r, :70-81, isweight=False) -------------------------------------------------------------
+// The point rows are the revolute problem's; the wj joint rows give way to THREE rows r0 - r1 of weight 1: a slider does not turn
+// against its base at all.  The joint direction does not enter (a NaN direction is never read).  The rows' Jacobian is the forward
+// difference MINPACK forms, not the constants +-1: row c moves only with r0_c and r1_c,
+//   d0[c] = (((r0_c + h0_c) - r1_c) - f_c) / h0_c,   d1[c] = ((r0_c - (r1_c + h1_c)) - f_c) / h1_c,   f_c = r0_c - r1_c,
+// (every other entry is (f_c - f_c) / h = 0 exactly), with the steps and reciprocals of the point rows (PartFd::begin_points).
+__device__ __forceinline__ double prismatic_cost(const double x[6]) {
+    const double a = x[0] - x[3], b = x[1] - x[4], c = x[2] - x[5];
+    return a * a + b * b + c * c;
+}
+__device__ __forceinline__ void assemble_normal_prismatic(const double x[6], const double blk0[6], const double g0[3],
+                                                          const double blk1[6], const double g1[3], double A[21], double g[6]) {
+    double f[3], d0[3], d1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double h0 = fd_step(x[c]), h1 = fd_step(x[3 + c]);
+        f[c] = x[c] - x[3 + c];
+        d0[c] = (((x[c] + h0) - x[3 + c]) - f[c]) * fast_rcp(h0);
+        d1[c] = ((x[c] - (x[3 + c] + h1)) - f[c]) * fast_rcp(h1);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double v = 0.0;
+            if (i < 3) v = (i == j ? d0[i] * d0[i] : 0.0) + blk0[i * (i + 1) / 2 + j];
+            else if (j >= 3) v = (i == j ? d1[i - 3] * d1[i - 3] : 0.0) + blk1[(i - 3) * (i - 2) / 2 + (j - 3)];
+            else if (i - 3 == j) v = d1[j] * d0[j];
+            A[i * (i + 1) / 2 + j] = v;
+        }
+        g[i] = i < 3 ? d0[i] * f[i] + g0[i] : d1[i - 3] * f[i - 3] + g1[i - 3];
+    }
+}
+
+// Thread-local articulated problem on 3 + 3 sampled points.  PRISM: the prismatic objective above (J, wj unused).
+template <bool PRISM>
+struct HypProblemT {
     double x0[3][3], y0[3][3], x1[3][3], y1[3][3], J[3], wj;
 
     __device__ __forceinline__ double cost(const double x[6]) const {
@@ -784,23 +823,29 @@ struct HypProblem {
             const double d = y1[i][0] - ox, e = y1[i][1] - oy, f = y1[i][2] - oz;
             s += d * d + e * e + f * f;
         }
-        double ux, uy, uz, wx, wy, wz;
-        rod_apply(r0, J[0], J[1], J[2], ux, uy, uz);
-        rod_apply(r1, J[0], J[1], J[2], wx, wy, wz);
-        s += wj * ((ux - wx) * (ux - wx) + (uy - wy) * (uy - wy) + (uz - wz) * (uz - wz));
-        return s;
+        if constexpr (PRISM) {
+            return s + prismatic_cost(x);
+        } else {
+            double ux, uy, uz, wx, wy, wz;
+            rod_apply(r0, J[0], J[1], J[2], ux, uy, uz);
+            rod_apply(r1, J[0], J[1], J[2], wx, wy, wz);
+            s += wj * ((ux - wx) * (ux - wx) + (uy - wy) * (uy - wy) + (uz - wz) * (uz - wz));
+            return s;
+        }
     }
     __device__ __forceinline__ void normal(const double x[6], double A[21], double g[6]) const {
         PartFd p0, p1;
-        p0.begin(x, J);
+        if constexpr (PRISM) p0.begin_points(x); else p0.begin(x, J);
 #pragma unroll
         for (int i = 0; i < 3; ++i) p0.point(x0[i][0], x0[i][1], x0[i][2], y0[i][0], y0[i][1], y0[i][2]);
-        p1.begin(x + 3, J);
+        if constexpr (PRISM) p1.begin_points(x + 3); else p1.begin(x + 3, J);
 #pragma unroll
         for (int i = 0; i < 3; ++i) p1.point(x1[i][0], x1[i][1], x1[i][2], y1[i][0], y1[i][1], y1[i][2]);
-        assemble_normal(p0, p0.blk, p0.gv, p1, p1.blk, p1.gv, wj, A, g);
+        if constexpr (PRISM) assemble_normal_prismatic(x, p0.blk, p0.gv, p1.blk, p1.gv, A, g);
+        else assemble_normal(p0, p0.blk, p0.gv, p1, p1.blk, p1.gv, wj, A, g);
     }
 };
+typedef HypProblemT<false> HypProblem;
 
 // scale_pts both ways on 3 points: s = <A,b>/(<A,A>+1e-6), s_inv = <A,b>/(<b,b>+1e-6); float32 results
 __device__ __forceinline__ void scales3(const float s[3][3], const float t[3][3], float &sc, float &sc_inv) {
@@ -939,12 +984,16 @@ constexpr int HYP_CHUNK_SMALL = 64;   // ... of a launch too small to fill the c
 constexpr long HYP_SMALL_LAUNCH = 8192;   // fits per launch up to which the small chunk is used
 constexpr int HYP_REFILL = 16;    // idle lanes that trigger a refill (a refill costs the whole wave ~1 trip of latency)
 
-template <int KM>
-__global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
-                                                             const float *__restrict__ src, const float *__restrict__ tgt,
-                                                             const float *__restrict__ joint_dir, int niter,
-                                                             const int *__restrict__ draws, KeyArg<KM> seed_arg,
-                                                             double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
+// The joint kind (0 revolute, non-zero prismatic) is a property of the problem, and prob = blockIdx.y (blockIdx.x in the finish
+// kernel): every lane of a block runs the same objective.  Each LM kernel's body is therefore a function of <key mode, PRISM>; the
+// kernels of the entries without a kind array instantiate PRISM = false alone (registers, scratch and occupancy as before kinds existed:
+// profiles/r14_pose_resource_usage_{before,after,diff}.txt), and the *_kind_kernel twins take the block-uniform branch on joint_kind[prob].
+template <int KM, bool PRISM>
+__device__ __forceinline__ void ransac_joint_lm_run(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                    const float *__restrict__ src, const float *__restrict__ tgt,
+                                                    const float *__restrict__ joint_dir, int niter,
+                                                    const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                    double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
     const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
     const int kbase = key_problem_base<KM>(seed_arg);
     const int prob = blockIdx.y;
@@ -953,9 +1002,11 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restri
     if (n0 <= 0 || n1 <= 0) return;
     const int c1 = min(niter, (int)(blockIdx.x + 1) * chunk);
     int next = blockIdx.x * chunk;              // wave-uniform: first hypothesis of the chunk not yet handed out
-    HypProblem P;
-    P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
-    P.wj = 3.0;   // min(3,3) copies of the joint axis (:134)
+    HypProblemT<PRISM> P;
+    if constexpr (!PRISM) {
+        P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
+        P.wj = 3.0;   // min(3,3) copies of the joint axis (:134)
+    }
     Lm6 S;
     bool active = false;
     int h = 0;
@@ -996,6 +1047,26 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restri
     }
 }
 
+template <int KM>
+__global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                             const float *__restrict__ src, const float *__restrict__ tgt,
+                                                             const float *__restrict__ joint_dir, int niter,
+                                                             const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                             double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
+    ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
+}
+
+template <int KM>
+__global__ __launch_bounds__(64) void ransac_joint_lm_kind_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                                  const float *__restrict__ src, const float *__restrict__ tgt,
+                                                                  const float *__restrict__ joint_dir, int niter,
+                                                                  const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                                  double *__restrict__ models, int *__restrict__ lm_stat, int chunk,
+                                                                  const int *__restrict__ joint_kind) {
+    if (joint_kind[blockIdx.y] != 0) ransac_joint_lm_run<KM, true>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
+    else ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
+}
+
 // ---- lane-group-cooperative LM --------------------------------------------------------------------------------------------
 // The kernel above keeps one fit in one lane: its duration is the LONGEST fit of the batch (1500-evaluation trajectories,
 // ~1.6 ms), every one of its ~2000 instructions per evaluation issued for a single live lane.  Here EIGHT lanes share a fit.
@@ -1017,7 +1088,12 @@ __device__ __forceinline__ void group_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-struct HypProblemCoop {
+// PRISM (the prismatic objective, see assemble_normal_prismatic): role 6's share of cost() is the three constraint rows r0 - r1
+// (weight 1), and normal() needs no jd / ju exchange -- the constraint rows' entries come from x, which every lane holds.  The group
+// record keeps its layout and size; a prismatic fit simply leaves the jd, rh and ju slots unused (one record layout for both kinds,
+// one 7 KB array per block handed in by the kernel).
+template <bool PRISM>
+struct HypProblemCoopT {
     double x0[3][3], y0[3][3], x1[3][3], y1[3][3], J[3], wj;
     double *xch;      // this group's LDS record
     int role;         // lane & 7
@@ -1040,6 +1116,8 @@ struct HypProblemCoop {
             rod_apply(r, px, py, pz, ox, oy, oz);
             const double a = tx - ox, b = ty - oy, c = tz - oz;
             partial = a * a + b * b + c * c;
+        } else if constexpr (PRISM) {
+            partial = prismatic_cost(x);
         } else {
             const Rod r0 = rod_prepare(x[0], x[1], x[2]), r1 = rod_prepare(x[3], x[4], x[5]);
             double ux, uy, uz, wx, wy, wz;
@@ -1053,7 +1131,7 @@ struct HypProblemCoop {
         double s = 0.0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { s += cs[k]; s += cs[3 + k]; }     // the serial order: part 0 point k, part 1 point k
-        s += wj * cs[6];
+        if constexpr (PRISM) s += cs[6]; else s += wj * cs[6];
         group_lds_fence();                                             // the record is reused by the next callback
         return s;
     }
@@ -1085,13 +1163,15 @@ struct HypProblemCoop {
                     if (q == 0) { fx[(p1 ? 9 : 0) + i * 3] = f0; fx[(p1 ? 9 : 0) + i * 3 + 1] = f1; fx[(p1 ? 9 : 0) + i * 3 + 2] = f2; }
                 }
             }
-            double ux, uy, uz, vx, vy, vz;
-            rod_apply(b, J[0], J[1], J[2], ux, uy, uz);
-            rod_apply(pr, J[0], J[1], J[2], vx, vy, vz);
-            if (wr) {
-                jdx[cr * 3] = vx; jdx[cr * 3 + 1] = vy; jdx[cr * 3 + 2] = vz;
-                rhx[cr] = rh;
-                if (q == 0) { jux[(p1 ? 3 : 0)] = ux; jux[(p1 ? 3 : 0) + 1] = uy; jux[(p1 ? 3 : 0) + 2] = uz; }
+            if constexpr (!PRISM) {
+                double ux, uy, uz, vx, vy, vz;
+                rod_apply(b, J[0], J[1], J[2], ux, uy, uz);
+                rod_apply(pr, J[0], J[1], J[2], vx, vy, vz);
+                if (wr) {
+                    jdx[cr * 3] = vx; jdx[cr * 3 + 1] = vy; jdx[cr * 3 + 2] = vz;
+                    rhx[cr] = rh;
+                    if (q == 0) { jux[(p1 ? 3 : 0)] = ux; jux[(p1 ? 3 : 0) + 1] = uy; jux[(p1 ? 3 : 0) + 2] = uz; }
+                }
             }
         }
         group_lds_fence();
@@ -1118,6 +1198,9 @@ struct HypProblemCoop {
                 }
             }
         }
+        if constexpr (PRISM) {
+            assemble_normal_prismatic(x, blk[0], gv[0], blk[1], gv[1], A, g);
+        } else {
         double f[3], a[3][6];
 #pragma unroll
         for (int c = 0; c < 3; ++c) f[c] = jux[c] - jux[3 + c];
@@ -1139,19 +1222,21 @@ struct HypProblemCoop {
             }
             g[i] = wj * (a[0][i] * f[0] + a[1][i] * f[1] + a[2][i] * f[2]) + (i < 3 ? gv[0][i] : gv[1][i - 3]);
         }
+        }
         group_lds_fence();                                             // the record is reused by the next callback
     }
 };
+typedef HypProblemCoopT<false> HypProblemCoop;
 
-template <int KM>
-__global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
-                                                                  const float *__restrict__ src, const float *__restrict__ tgt,
-                                                                  const float *__restrict__ joint_dir, int niter,
-                                                                  const int *__restrict__ draws, KeyArg<KM> seed_arg,
-                                                                  double *__restrict__ models, int *__restrict__ lm_stat) {
+template <int KM, bool PRISM>
+__device__ __forceinline__ void ransac_joint_lm_coop_run(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                         const float *__restrict__ src, const float *__restrict__ tgt,
+                                                         const float *__restrict__ joint_dir, int niter,
+                                                         const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                         double *__restrict__ models, int *__restrict__ lm_stat,
+                                                         double (*xch)[COOP_XCH]) {
     const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
     const int kbase = key_problem_base<KM>(seed_arg);
-    __shared__ double xch[64 / COOP_G][COOP_XCH];
     const int prob = blockIdx.y, lane = threadIdx.x;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
@@ -1160,9 +1245,11 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__r
     int next = blockIdx.x * COOP_HYP_PER_WAVE;          // wave-uniform: first hypothesis of the chunk not yet handed out
     const int grp = lane / COOP_G;
     const unsigned long long leaders = 0x0101010101010101ull;        // lane 0 of every group
-    HypProblemCoop P;
-    P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
-    P.wj = 3.0;   // min(3,3) copies of the joint axis (:134)
+    HypProblemCoopT<PRISM> P;
+    if constexpr (!PRISM) {
+        P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
+        P.wj = 3.0;   // min(3,3) copies of the joint axis (:134)
+    }
     P.xch = xch[grp];
     P.role = lane & (COOP_G - 1);
     Lm6 S;
@@ -1201,6 +1288,28 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__r
             active = false;
         }
     }
+}
+
+template <int KM>
+__global__ __launch_bounds__(64) void ransac_joint_lm_coop_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                                  const float *__restrict__ src, const float *__restrict__ tgt,
+                                                                  const float *__restrict__ joint_dir, int niter,
+                                                                  const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                                  double *__restrict__ models, int *__restrict__ lm_stat) {
+    __shared__ double xch[64 / COOP_G][COOP_XCH];
+    ransac_joint_lm_coop_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, xch);
+}
+
+template <int KM>
+__global__ __launch_bounds__(64) void ransac_joint_lm_coop_kind_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                                       const float *__restrict__ src, const float *__restrict__ tgt,
+                                                                       const float *__restrict__ joint_dir, int niter,
+                                                                       const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                                       double *__restrict__ models, int *__restrict__ lm_stat,
+                                                                       const int *__restrict__ joint_kind) {
+    __shared__ double xch[64 / COOP_G][COOP_XCH];      // one record array serves whichever body the block runs
+    if (joint_kind[blockIdx.y] != 0) ransac_joint_lm_coop_run<KM, true>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, xch);
+    else ransac_joint_lm_coop_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, xch);
 }
 
 template <int KM>
@@ -1277,7 +1386,9 @@ __global__ __launch_bounds__(256) void ransac_joint_verify_kernel(const int *__r
 }
 
 // Workgroup-cooperative articulated problem over LDS-resident inliers (final refit :32 -> :106-184).
-struct BlockProblem {
+// PRISM: the prismatic objective; its three constraint rows are added once after block_sum, as assemble_normal adds the joint rows.
+template <bool PRISM>
+struct BlockProblemT {
     const float (*x0)[3];
     const float (*y0)[3];
     const float (*x1)[3];
@@ -1300,16 +1411,20 @@ struct BlockProblem {
             s[0] += a * a + b * b + c * c;
         }
         block_sum<1>(s, red, 4);
-        double ux, uy, uz, wx, wy, wz;
-        rod_apply(r0, J[0], J[1], J[2], ux, uy, uz);
-        rod_apply(r1, J[0], J[1], J[2], wx, wy, wz);
-        return s[0] + wj * ((ux - wx) * (ux - wx) + (uy - wy) * (uy - wy) + (uz - wz) * (uz - wz));
+        if constexpr (PRISM) {
+            return s[0] + prismatic_cost(x);
+        } else {
+            double ux, uy, uz, wx, wy, wz;
+            rod_apply(r0, J[0], J[1], J[2], ux, uy, uz);
+            rod_apply(r1, J[0], J[1], J[2], wx, wy, wz);
+            return s[0] + wj * ((ux - wx) * (ux - wx) + (uy - wy) * (uy - wy) + (uz - wz) * (uz - wz));
+        }
     }
     __device__ __forceinline__ void normal(const double x[6], double A[21], double g[6]) const {
         PartFd p0, p1;
-        p0.begin(x, J);
+        if constexpr (PRISM) p0.begin_points(x); else p0.begin(x, J);
         for (int i = threadIdx.x; i < n0; i += 256) p0.point(x0[i][0], x0[i][1], x0[i][2], y0[i][0], y0[i][1], y0[i][2]);
-        p1.begin(x + 3, J);
+        if constexpr (PRISM) p1.begin_points(x + 3); else p1.begin(x + 3, J);
         for (int i = threadIdx.x; i < n1; i += 256) p1.point(x1[i][0], x1[i][1], x1[i][2], y1[i][0], y1[i][1], y1[i][2]);
         double v[18];
 #pragma unroll
@@ -1317,9 +1432,11 @@ struct BlockProblem {
 #pragma unroll
         for (int i = 0; i < 3; ++i) { v[6 + i] = p0.gv[i]; v[15 + i] = p1.gv[i]; }
         block_sum<18>(v, red, 4);
-        assemble_normal(p0, v, v + 6, p1, v + 9, v + 15, wj, A, g);
+        if constexpr (PRISM) assemble_normal_prismatic(x, v, v + 6, v + 9, v + 15, A, g);
+        else assemble_normal(p0, v, v + 6, p1, v + 9, v + 15, wj, A, g);
     }
 };
+typedef BlockProblemT<false> BlockProblem;
 
 // pairwise scale sums of one part over LDS-resident inliers -> (s, s_inv) as float32
 __device__ __forceinline__ void block_scales(const float (*cs)[3], const float (*ct)[3], int n, double *red, float &sc,
@@ -1363,16 +1480,19 @@ __device__ __forceinline__ void block_prep_part(float (*cs)[3], float (*ct)[3], 
     quat_to_rotvec(q, rv);
 }
 
-template <int KM>
-__global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
-                                                                  const float *__restrict__ src, const float *__restrict__ tgt,
-                                                                  const float *__restrict__ joint_dir, double th, int niter,
-                                                                  const double *__restrict__ scores,
-                                                                  const double *__restrict__ models, int max_n,
-                                                                  double *__restrict__ out_model,
-                                                                  unsigned char *__restrict__ out_inliers,
-                                                                  int *__restrict__ out_best, double *__restrict__ out_score, FitExtras E) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// PRISM: the refit minimises the prismatic objective.  The *_kind_kernel below runs the whole body of one kind or the other per block
+// (not a branch at the refit alone): the revolute half is then the instruction stream of the kernel without kinds, to the last bit of
+// the f64 code that is compiled with contraction on.
+template <int KM, bool PRISM>
+__device__ __forceinline__ void ransac_joint_finish_run(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                        const float *__restrict__ src, const float *__restrict__ tgt,
+                                                        const float *__restrict__ joint_dir, double th, int niter,
+                                                        const double *__restrict__ scores,
+                                                        const double *__restrict__ models, int max_n,
+                                                        double *__restrict__ out_model,
+                                                        unsigned char *__restrict__ out_inliers,
+                                                        int *__restrict__ out_best, double *__restrict__ out_score, const FitExtras &E,
+                                                        unsigned char *smem) {
     double *red = (double *)smem;                      // 24*4 doubles
     int *wcnt = (int *)(red + 128);
     float(*c0s)[3] = (float(*)[3])(wcnt + 8);
@@ -1474,13 +1594,21 @@ __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__r
     block_prep_part(c0s, c0t, m0, sc0i, red, sm0, tm0, x);
     block_prep_part(c1s, c1t, m1, sc1i, red, sm1, tm1, x + 3);
     __syncthreads();
-    BlockProblem P;
-    P.x0 = c0s; P.y0 = c0t; P.x1 = c1s; P.y1 = c1t;
-    P.n0 = m0; P.n1 = m1;
-    P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
-    P.wj = (double)(m0 < m1 ? m0 : m1);
-    P.red = red;
-    lmdif6(P, x, 1e-4, 1e-8, 1e-8, 4200, nullptr);
+    if constexpr (PRISM) {                             // 3 (m0 + m1) + 3 rows: no min(m0, m1) copies, no joint direction
+        BlockProblemT<true> P;
+        P.x0 = c0s; P.y0 = c0t; P.x1 = c1s; P.y1 = c1t;
+        P.n0 = m0; P.n1 = m1;
+        P.red = red;
+        lmdif6(P, x, 1e-4, 1e-8, 1e-8, 4200, nullptr);
+    } else {
+        BlockProblem P;
+        P.x0 = c0s; P.y0 = c0t; P.x1 = c1s; P.y1 = c1t;
+        P.n0 = m0; P.n1 = m1;
+        P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
+        P.wj = (double)(m0 < m1 ? m0 : m1);
+        P.red = red;
+        lmdif6(P, x, 1e-4, 1e-8, 1e-8, 4200, nullptr);
+    }
     rotvec_to_mat(x, R0);
     rotvec_to_mat(x + 3, R1);
     if (threadIdx.x == 0) {
@@ -1501,6 +1629,39 @@ __global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__r
             if (rec0) rec0[a] = om[a];
         }
     }
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void ransac_joint_finish_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                                  const float *__restrict__ src, const float *__restrict__ tgt,
+                                                                  const float *__restrict__ joint_dir, double th, int niter,
+                                                                  const double *__restrict__ scores,
+                                                                  const double *__restrict__ models, int max_n,
+                                                                  double *__restrict__ out_model,
+                                                                  unsigned char *__restrict__ out_inliers,
+                                                                  int *__restrict__ out_best, double *__restrict__ out_score, FitExtras E) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ransac_joint_finish_run<KM, false>(rng0, rng1, src, tgt, joint_dir, th, niter, scores, models, max_n, out_model, out_inliers, out_best,
+                                       out_score, E, smem);
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void ransac_joint_finish_kind_kernel(const int *__restrict__ rng0, const int *__restrict__ rng1,
+                                                                       const float *__restrict__ src, const float *__restrict__ tgt,
+                                                                       const float *__restrict__ joint_dir, double th, int niter,
+                                                                       const double *__restrict__ scores,
+                                                                       const double *__restrict__ models, int max_n,
+                                                                       double *__restrict__ out_model,
+                                                                       unsigned char *__restrict__ out_inliers,
+                                                                       int *__restrict__ out_best, double *__restrict__ out_score, FitExtras E,
+                                                                       const int *__restrict__ joint_kind) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (joint_kind[blockIdx.x] != 0)
+        ransac_joint_finish_run<KM, true>(rng0, rng1, src, tgt, joint_dir, th, niter, scores, models, max_n, out_model, out_inliers, out_best,
+                                          out_score, E, smem);
+    else
+        ransac_joint_finish_run<KM, false>(rng0, rng1, src, tgt, joint_dir, th, niter, scores, models, max_n, out_model, out_inliers, out_best,
+                                           out_score, E, smem);
 }
 
 // ================================ glue kernels =====================================================
@@ -2124,7 +2285,7 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
                              const float *joint_dir, double inlier_th, int niter, const int *draws,
                              KeyArg<KM> seed, int max_n, double *out_model, unsigned char *out_inliers,
                              int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                             int *lm_stat, int lm_schedule, FitExtras E, void *stream) {
+                             int *lm_stat, int lm_schedule, FitExtras E, void *stream, const int *joint_kind = nullptr) {
     ANCSH_REQUIRE(lm_schedule >= ANCSH_LM_AUTO && lm_schedule <= ANCSH_LM_LATENCY, "ransac_joint: unknown lm_schedule %d", lm_schedule);
     ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_joint: bad sizes");
     ANCSH_REQUIRE(max_n <= 3072, "ransac_joint: max_n %d > 3072 (refit keeps both parts' inliers in LDS)", max_n);
@@ -2145,22 +2306,52 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
     //   * eight lanes per fit (ANCSH_LM_LATENCY, explicit only): the long fits that set the launch's duration run ~1.25x faster
     //     (measured on 64 x 200 fits: 1.27 vs 1.6 ms; the tail is MINPACK's serial lmpar on rank-deficient samples, which no lane
     //     split shortens) at ~5 % lower pipeline throughput.
+    // joint_kind (the *_kind entries): the same launches with the kernels that branch, block-uniformly, on the problem's kind; without
+    // it the kernels are the revolute-only ones, untouched
     if (lm_schedule == ANCSH_LM_LATENCY) {
-        hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<KM>, dim3((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob), dim3(64), 0, st,
-                           rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
+        const dim3 grid((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob);
+        if (joint_kind)
+            hipLaunchKernelGGL(ransac_joint_lm_coop_kind_kernel<KM>, grid, dim3(64), 0, st, rng0, rng1, src, tgt, joint_dir, niter, draws, seed,
+                               scratch_models, lm_stat, joint_kind);
+        else
+            hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<KM>, grid, dim3(64), 0, st,
+                               rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
     } else {
         const int chunk = (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK;
-        hipLaunchKernelGGL(ransac_joint_lm_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
-                           joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
+        if (joint_kind)
+            hipLaunchKernelGGL(ransac_joint_lm_kind_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
+                               joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk, joint_kind);
+        else
+            hipLaunchKernelGGL(ransac_joint_lm_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
+                               joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
     }
     hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
     hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, inlier_th,
                        niter, scratch_models, scratch_scores);
     const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
+    if (joint_kind) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(ransac_joint_finish_kind_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
+                           niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E, joint_kind);
+        return check_launch("ransac_joint");
+    }
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(ransac_joint_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
                        niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
     return check_launch("ransac_joint");
+}
+
+// joint_kind of the *_kind entries: NULL is "all revolute".  A host-side array (pinned or registered host memory) is checked here --
+// every entry 0 or 1 -- because here the host can see it; a device array is not read by the host (no synchronisation), and the kernels
+// take any non-zero entry as prismatic.
+static int check_joint_kind(const char *who, int nprob, const int *joint_kind) {
+    if (!joint_kind || nprob <= 0) return ANCSH_OK;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, joint_kind) != hipSuccess) { (void)hipGetLastError(); return ANCSH_OK; }
+    if (at.type != hipMemoryTypeHost) return ANCSH_OK;
+    for (int p = 0; p < nprob; ++p)
+        ANCSH_REQUIRE(joint_kind[p] == 0 || joint_kind[p] == 1, "%s: joint_kind[%d] = %d (0 revolute, 1 prismatic)", who, p, joint_kind[p]);
+    return ANCSH_OK;
 }
 
 extern "C" int ancsh_ransac_joint(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
@@ -2253,6 +2444,55 @@ extern "C" int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int
     return ransac_joint_impl<KEY_DKEY>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, DKey{key, K - 1}, max_n,
                                        out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
                                        E, stream);
+}
+
+// The three record entries with a joint kind per problem (ABI 14, include/ancsh_hip.h): joint_kind NULL = the entry without it.
+extern "C" int ancsh_ransac_joint_rec_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                           const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                           unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+                                           int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
+                                           int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
+                                           const int *joint_kind, void *stream) {
+    if (int rc = check_joint_kind("ransac_joint_rec_kind", nprob, joint_kind)) return rc;
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_joint_rec_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
+    E.draws = draws; E.seed = seed;
+    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
+                                        out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream, joint_kind);
+}
+
+extern "C" int ancsh_ransac_joint_rec_dseed_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                                 const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                                 const unsigned long long *seed, int max_n, double *out_model,
+                                                 unsigned char *out_inliers, int *out_best, double *out_score, double *scratch_scores,
+                                                 double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+                                                 int *tie_stats, double tie_window, const int *joint_kind, void *stream) {
+    ANCSH_REQUIRE(seed, "ransac_joint_rec_dseed_kind: null seed pointer");
+    if (int rc = check_joint_kind("ransac_joint_rec_dseed_kind", nprob, joint_kind)) return rc;
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_joint_rec_dseed_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
+    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)seed;
+    return ransac_joint_impl<KEY_DSEED>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
+                                        out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream,
+                                        joint_kind);
+}
+
+extern "C" int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                                const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                                const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers,
+                                                int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
+                                                int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats,
+                                                double tie_window, const int *joint_kind, void *stream) {
+    ANCSH_REQUIRE(key, "ransac_joint_rec_dkey_kind: null key pointer");
+    ANCSH_REQUIRE(K >= 2 && nprob >= 0 && nprob % (K - 1) == 0 && nprob < (1 << 20),
+                  "ransac_joint_rec_dkey_kind: nprob (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", nprob, K);
+    if (int rc = check_joint_kind("ransac_joint_rec_dkey_kind", nprob, joint_kind)) return rc;
+    FitExtras E = no_extras();
+    if (int rc = make_extras("ransac_joint_rec_dkey_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
+    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)key;
+    return ransac_joint_impl<KEY_DKEY>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, DKey{key, K - 1}, max_n,
+                                       out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
+                                       E, stream, joint_kind);
 }
 
 extern "C" int ancsh_umeyama(int nprob, const int *off, const float *src, const float *tgt, double *out, void *stream) {

@@ -311,12 +311,18 @@ class ShardedPipeline(object):
     gathered on dst in global cloud order by one more padded gather per batch.
     joint_source ("gt" | "predicted"): passed to every rank's pipeline (AncshPipeline(joint_source=...)).  "predicted": solve(P, None,
     pred) and load_inputs(P, None, pred) need no labels, and the raw stream takes (n_raw, 3) xyz clouds (or (n_raw, 4), 4th column
-    ignored) through the keyed xyz sampler."""
+    ignored) through the keyed xyz sampler.
+    joint_types (None | "revolute" | "prismatic" | K - 1 of them): passed to every rank's pipeline (AncshPipeline(joint_types=...)); the
+    kind array repeats per cloud, so a shard's slice of it is the shard's own array and sharded streams stay byte-equal to one GPU's."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 **pipeline_kw):
+                 joint_types=None, **pipeline_kw):
         from .pipeline import check_joint_source
+        from .pose.parallel_ancsh_pose import check_joint_types
+        check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
+        if joint_types is not None:        # the kinds belong to the object class, so every rank's shard gets the same K - 1 of them per cloud
+            pipeline_kw.update(joint_types=joint_types)
         self.joint_source = check_joint_source(joint_source)
         if joint_source != "gt":           # the default is not passed on: a per-rank stand-in built before joint_source need not know it
             pipeline_kw.update(joint_source=joint_source)

@@ -22,10 +22,15 @@ _DATASETS = dict(
     drawer=DatasetInfo(4, ['46123', '45841', '46440'], [], '3.3', '3.31', 'sapien', _DRAWER_ORDER),
 )
 
+# kind of joint j = 1..K-1 of every category: the drawer's three sliders are prismatic, every other category's joints are hinges.  Used only
+# where a caller asks for it (pose_multi_process --joint_types category); the default everywhere is the revolute objective.
+JOINT_TYPES = {name: tuple(['prismatic' if name == 'drawer' else 'revolute'] * (d.num_parts - 1)) for name, d in _DATASETS.items()}
+
 
 class global_info(object):
     def __init__(self, base_path=None, group_path=None):
         self.datasets = _DATASETS
+        self.joint_types = JOINT_TYPES
         self.base_path = base_path or os.environ.get('ANCSH_BASE_PATH', os.getcwd())
         self.group_path = group_path or os.environ.get('ANCSH_GROUP_PATH', self.base_path)     # global_info.py:193: where the sapien set lives
 

@@ -183,7 +183,13 @@ class AncshPipeline(object):
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
-                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt"):
+                 arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
+                 joint_types=None):
+        # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
+        # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
+        # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
+        from .pose.parallel_ancsh_pose import check_joint_types
+        check_joint_types(joint_types, num_parts)
         # joint_source: stage B's joint association.  "gt" (default) = a label per point -- load_inputs' joint_cls, or the 4th column
         # [x y z joint_cls] of a streamed raw row (the rendered test split's ground truth, evaluation/parallel_ancsh_pose.py:295).
         # "predicted" = the argmax of the ANCSH network's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366), from the step's
@@ -246,7 +252,9 @@ class AncshPipeline(object):
         # tie_window: None (default) = no tie statistics in the step (nobody reads them in a pipeline; the per-fit diagnostics of
         # PoseSolver -- tie_a / tie_b -- cost the stage-A finish kernel ~20 us a batch); pass parallel_ancsh_pose.TIE_WINDOW to get them
         self.solver = PoseSolver(num_parts, inlier_th, niter_a, niter_b, device,
-                                 lm_schedule=lm_schedule or ("latency" if max(1, slots) <= 2 else "auto"), tie_window=tie_window)
+                                 lm_schedule=lm_schedule or ("latency" if max(1, slots) <= 2 else "auto"), tie_window=tie_window,
+                                 joint_types=joint_types)
+        self.solver.prepare(batch_size)     # the (B * (K - 1)) joint-kind array (None when every joint is revolute): never built inside a captured step
         self.couple, self.seed = couple, seed
         # arithmetic of the shared-MLP layers: None = whatever ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME say (default: f32, the graded arithmetic);
         # "f32" | "bf16x3" | "f16x2" pins it for THIS pipeline (the split-16 experiment: bf16x3 at level 3, f16x2 at level 4 -- DESIGN section 8)

@@ -82,16 +82,52 @@ def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max
 
 
 LM_SCHEDULES = {"auto": 0, "throughput": 1, "latency": 2}     # ANCSH_LM_* of include/ancsh_hip.h
+JOINT_KINDS = {"revolute": 0, "prismatic": 1}                 # ANCSH_JOINT_* of include/ancsh_hip.h
+
+
+def check_joint_types(joint_types, num_parts):
+    """Validate a joint_types argument for an object of num_parts parts, on the host, before anything touches the GPU.
+    None -> None (every joint revolute: the entries without a kind array); one string -> that kind for all K - 1 joints; a sequence of
+    K - 1 strings -> joint j = 1..K-1 in order.  -> a tuple of K - 1 kind codes (JOINT_KINDS), or None.  ValueError names the
+    offending entry."""
+    if joint_types is None:
+        return None
+    nj = max(int(num_parts) - 1, 0)
+    if isinstance(joint_types, str):
+        if joint_types not in JOINT_KINDS:
+            raise ValueError("joint_types must be one of %s, got %r" % (tuple(JOINT_KINDS), joint_types))
+        return (JOINT_KINDS[joint_types],) * nj
+    if not isinstance(joint_types, (list, tuple)):
+        raise ValueError("joint_types must be None, one of %s, or a sequence of %d of them (one per joint), got %r"
+                         % (tuple(JOINT_KINDS), nj, joint_types))
+    if len(joint_types) != nj:
+        raise ValueError("joint_types must name the %d joints of a %d-part object, got %d entries: %r"
+                         % (nj, num_parts, len(joint_types), list(joint_types)))
+    for j, t in enumerate(joint_types):
+        if not isinstance(t, str) or t not in JOINT_KINDS:
+            raise ValueError("joint_types[%d] (joint %d) must be one of %s, got %r" % (j, j + 1, tuple(JOINT_KINDS), t))
+    return tuple(JOINT_KINDS[t] for t in joint_types)
+
+
+def joint_kind_tensor(kinds, B, device):
+    """The (B * (K - 1)) int32 device array of the *_kind entries for B clouds of one object class (problem p = b * (K - 1) + q);
+    kinds: check_joint_types' tuple, or None -> None."""
+    if kinds is None:
+        return None
+    return torch.tensor(list(kinds) * int(B), dtype=torch.int32).to(device)
 
 
 def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=None, seed=0, max_n=None, want_lm_stat=False,
-                       lm_schedule="auto", record=None, K=0, tie_window=None, seed_dev=None, key_dev=None):
+                       lm_schedule="auto", record=None, K=0, tie_window=None, seed_dev=None, key_dev=None, joint_kind=None):
     """Batched ransac(dataset, joint_transformation_estimator, joint_transformation_verifier, th, niter).
     rng0/rng1 (nprob,2) int32 [start,end) rows of part 0 / part j; joint_dir (nprob,3) float32.
     seed_dev: optional one-element int64 device tensor; the kernels use its value + 1 (ancsh_ransac_joint_rec_dseed: stage B of the
     key that stage A reads there) and `seed` is unused.
     key_dev: optional 16-byte device key block (ancsh_stream_key) instead of seed_dev (ancsh_ransac_joint_rec_dkey: its seed + 1, problem
     p keyed as p + cloud_base * (K - 1); needs K).
+    joint_kind: optional (nprob) int32 device tensor, 0 revolute / 1 prismatic per problem (the ancsh_ransac_joint_rec*_kind entries:
+    a prismatic problem minimises objective_eval_r, :70-81, and never reads its joint_dir row); None = every problem revolute, the
+    launches of the entries without it.
     -> dict(model (nprob,26) f64 [R0 s0 t0 R1 s1 t1], inliers (nprob,2,max_n) uint8, best (nprob), score (nprob))."""
     dev = src.device
     nprob = rng0.shape[0]
@@ -107,7 +143,18 @@ def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=
     if d is not None and d.numel() != nprob * niter * 6:
         raise ValueError("draws must have shape (nprob, niter, 6)")
     tie = None
-    if key_dev is not None or seed_dev is not None:
+    if joint_kind is not None:
+        if joint_kind.dtype != torch.int32 or joint_kind.numel() != nprob or not joint_kind.is_contiguous():
+            raise ValueError("joint_kind must be a contiguous int32 tensor of %d entries (one per problem)" % nprob)
+        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
+        name, key = (("ancsh_ransac_joint_rec_dkey_kind", _lib.ptr(key_dev)) if key_dev is not None else
+                     ("ancsh_ransac_joint_rec_dseed_kind", _lib.ptr(seed_dev)) if seed_dev is not None else
+                     ("ancsh_ransac_joint_rec_kind", int(seed)))
+        _lib.call(name, nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th),
+                  int(niter), _lib.ptr(d), key, max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(score), _lib.ptr(sc),
+                  _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule], _lib.ptr(record), int(K), _lib.ptr(tie),
+                  float(tie_window or 0.0), _lib.ptr(joint_kind))
+    elif key_dev is not None or seed_dev is not None:
         tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
         _lib.call("ancsh_ransac_joint_rec_dkey" if key_dev is not None else "ancsh_ransac_joint_rec_dseed", nprob, _lib.ptr(rng0),
                   _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th), int(niter), _lib.ptr(d),
@@ -124,7 +171,7 @@ def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=
         _lib.call("ancsh_ransac_joint_ex", nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir),
                   float(inlier_th), int(niter), _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
                   _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule])
-    return dict(model=model, inliers=inl, best=best, score=score, lm_stat=stat, hyp_models=mo, hyp_scores=sc, tie=tie, _keep=(d,))
+    return dict(model=model, inliers=inl, best=best, score=score, lm_stat=stat, hyp_models=mo, hyp_scores=sc, tie=tie, _keep=(d, joint_kind))
 
 
 def draws_from_seed(seed, counts, niter_a, niter_b):
@@ -165,7 +212,13 @@ class PoseSolver(object):
     A part with no predicted points gives NaN rows (the reference raises inside randint)."""
 
     def __init__(self, num_parts, inlier_th=0.1, niter_a=10000, niter_b=200, device="cuda:0", want_lm_stat=False,
-                 max_part_points=None, lm_schedule="auto", tie_window=TIE_WINDOW):
+                 max_part_points=None, lm_schedule="auto", tie_window=TIE_WINDOW, joint_types=None):
+        # joint_types: None (every joint revolute, objective_eval :56-68), "revolute" / "prismatic" for all joints, or K - 1 of them
+        # for joints 1..K-1 -- a prismatic joint is fitted with objective_eval_r (:70-81): its part does not turn against part 0.
+        # Checked here, on the host; "revolute" everywhere is None (the same launches as without the argument).
+        kinds = check_joint_types(joint_types, num_parts)
+        self.joint_kinds = kinds if kinds is not None and any(kinds) else None
+        self._kind_dev = {}                    # B -> the (B * (K - 1)) device array, built once per batch size (prepare())
         self.K, self.th, self.niter_a, self.niter_b = num_parts, inlier_th, niter_a, niter_b
         self.tie_window = tie_window           # None: no tie counts
         self.device = torch.device(device)
@@ -177,6 +230,15 @@ class PoseSolver(object):
             raise ValueError("lm_schedule must be one of %s" % sorted(LM_SCHEDULES))
         self.lm_schedule = lm_schedule         # "latency": eight lanes per LM fit (a lone batch finishes sooner); "throughput": one
         self.want_lm_stat = want_lm_stat       # also return per-hypothesis (status, nfev) of the stage-B LM fits
+
+    def prepare(self, B):
+        """Build the per-problem joint-kind array of a B-cloud batch ahead of time (a host-to-device copy: call it before a step is
+        captured; solve() calls it itself otherwise).  -> the (B * (K - 1)) int32 device tensor, or None when every joint is revolute."""
+        if self.joint_kinds is None or self.K < 2:
+            return None
+        if B not in self._kind_dev:
+            self._kind_dev[B] = joint_kind_tensor(self.joint_kinds, B, self.device)
+        return self._kind_dev[B]
 
     def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls=None, draws_a=None, draws_b=None, seed=0, seed_dev=None,
               key_dev=None, joint_index=None):
@@ -195,8 +257,10 @@ class PoseSolver(object):
         per point (the ANCSH record's joint_cls_gt, :295); joint_index (B,N,C) float32 = the ANCSH network's index_per_point head, whose
         np.argmax per point is the label (lib/parallel_ancsh_pose.py:339-343,366; ancsh_pose_joint_direction_pred, which takes it while
         compacting, and ancsh_pose_poison_records_pred, which also poisons a cloud with a non-finite index value).  The records then
-        equal those of joint_cls = np.argmax(joint_index, -1); a joint no point selects has a NaN direction and NaN stage-B rows
-        (certain when K - 1 >= C)."""
+        equal those of joint_cls = np.argmax(joint_index, -1); a joint no point selects has a NaN direction (certain when K - 1 >= C).
+        Fitted as a revolute joint it gets no joint fit: every evaluation of the objective is NaN, MINPACK accepts no step, and the row
+        holds the unrefined Kabsch start of the winning sample (finite, not NaN: tests/test_prismatic_gpu.py).  A prismatic joint
+        (joint_types) does not read its direction and is fitted like any other."""
         _one_association(joint_cls, joint_index)
         out = self._partition(P, nocs_pred, mask_pred)
         self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index)
@@ -290,7 +354,8 @@ class PoseSolver(object):
             b = ransac_joint_batch(rng0, rng1, src, tgt, jdir.view(-1, 3), self.th, self.niter_b,
                                    None if draws_b is None else _i32(draws_b, dev).reshape(B * (K - 1), self.niter_b, 6),
                                    seed + 1, max_n, want_lm_stat=self.want_lm_stat, lm_schedule=self.lm_schedule,
-                                   record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev)
+                                   record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev,
+                                   joint_kind=self.prepare(B))
             if self.want_lm_stat:
                 out["lm_stat"] = b["lm_stat"].view(B, K - 1, self.niter_b, 2)
             out["nonlinear"] = out["record"][:, :, 13:]
@@ -355,17 +420,21 @@ JOINT_SOURCES = ("gt", "predicted")
 
 
 def solver_ransac_nonlinear(s_ind, e_ind, test_exp, baseline_exp, choose_threshold, num_parts, test_group, problem_ins,
-                            rts_all, file_name, base_path=None, batch_size=32, seed=0, device="cuda:0", joint_source="gt"):
+                            rts_all, file_name, base_path=None, batch_size=32, seed=0, device="cuda:0", joint_source="gt",
+                            joint_types=None):
     """Same positional signature as the reference entry point (:196): solves test_group[s_ind:e_ind] and
     pickles {basename: record}.  Records are read with prediction_io.load_record from
     <base_path>/results/test_pred/<exp>/<basename>.{h5,npz} (USE_BASELINE: NOCS + mask from baseline_exp).
     joint_source: "gt" = stage B associates points to joints by the record's joint_cls_gt (:295); "predicted" = by the argmax of the
-    record's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366) -- what the ground-truth association is worth."""
+    record's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366) -- what the ground-truth association is worth.
+    joint_types: None (revolute, what the reference's evaluation script runs: its ransac() never forwards joint_type), one kind for all
+    joints or one per joint (PoseSolver); a trailing keyword, so the positional signature of the reference's callers does not move."""
     if joint_source not in JOINT_SOURCES:
         raise ValueError("joint_source must be one of %s, got %r" % (JOINT_SOURCES, joint_source))
+    check_joint_types(joint_types, num_parts)
     from .. import prediction_io
     base_path = base_path or os.environ.get("ANCSH_BASE_PATH", ".")
-    solver = PoseSolver(num_parts, choose_threshold, device=device)
+    solver = PoseSolver(num_parts, choose_threshold, device=device, joint_types=joint_types)
     names = [test_group[i].split('.')[0] for i in range(s_ind, e_ind) if test_group[i].split('_')[0] not in problem_ins]
     all_rts = {}
     for c0 in range(0, len(names), batch_size):

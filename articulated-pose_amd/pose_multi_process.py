@@ -15,7 +15,21 @@ import time
 from .dist import launch_local_ranks, shard_range, wants_self_launch
 from .global_info import get_test_group, global_info
 from .pose import solver_ransac_nonlinear
-from .pose.parallel_ancsh_pose import JOINT_SOURCES
+from .pose.parallel_ancsh_pose import JOINT_KINDS, JOINT_SOURCES, check_joint_types
+
+JOINT_TYPE_CHOICES = ('category',) + tuple(JOINT_KINDS)
+
+
+def resolve_joint_types(choice, item, infos):
+    """--joint_types -> PoseSolver's joint_types: 'revolute' = None (the reference's evaluation script: today's pickles, byte for byte),
+    'prismatic' = every joint, 'category' = global_info's table for `item`.  ValueError for anything else, before any GPU work."""
+    if choice not in JOINT_TYPE_CHOICES:
+        raise ValueError("joint_types must be one of %s, got %r" % (JOINT_TYPE_CHOICES, choice))
+    if choice == 'revolute':
+        return None
+    types = list(infos.joint_types[item]) if choice == 'category' else choice
+    check_joint_types(types, infos.datasets[item].num_parts)
+    return types
 
 
 def _device_index():
@@ -35,6 +49,9 @@ def build_parser():
     ap.add_argument('--joint_source', default='gt', choices=JOINT_SOURCES,
                     help="stage B's joint association: the record's joint_cls_gt (gt, the reference's rule) or the argmax of its "
                          "index_per_point head (predicted: what a depth frame without labels gets)")
+    ap.add_argument('--joint_types', default='revolute', choices=JOINT_TYPE_CHOICES,
+                    help="stage B's objective per joint: revolute (the reference's evaluation script, the default), prismatic (the "
+                         "shared-rotation objective for every joint) or category (global_info's table: the drawer's sliders prismatic)")
     return ap
 
 
@@ -48,6 +65,7 @@ def main(argv=None):
             raise SystemExit(launch_local_ranks(n_ranks, cmd))
     infos = global_info(args.base_path)
     d = infos.datasets[args.item]
+    joint_types = resolve_joint_types(args.joint_types, args.item, infos)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     my_dir = infos.base_path
     choose_threshold = 0.1
@@ -62,7 +80,7 @@ def main(argv=None):
     t0 = time.time()
     solver_ransac_nonlinear(s, e, d.exp, d.baseline, choose_threshold, d.num_parts, test_group, [], rts_all, sub,
                             base_path=my_dir, batch_size=args.batch_size, seed=rank,
-                            device='cuda:%d' % _device_index(), joint_source=args.joint_source)
+                            device='cuda:%d' % _device_index(), joint_source=args.joint_source, joint_types=joint_types)
     print('rank {}: {} clouds in {:.2f} s -> {}'.format(rank, e - s, time.time() - t0, sub))
 
 

@@ -41,7 +41,9 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
+int ancsh_abi_version(void);   /* 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
+                                 *     stage-B problem: the prismatic objective);
+                                 * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
                                  *     ancsh_input_sample_stream_xyz_keyed (the joint association from the network's index head; xyz-only raw rows);
                                  * 12: + ancsh_raw_point_labels (per-raw-point labels and head values of a streamed batch);
                                  * 11: + ancsh_articulation_rec (the streamed articulation block);
@@ -629,6 +631,45 @@ int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int *rng1, con
                                 int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
                                 double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
                                 int *tie_stats, double tie_window, void *stream);
+
+/* ancsh_ransac_joint_rec / _rec_dseed / _rec_dkey with a JOINT KIND per problem (ABI 14).  joint_kind (nprob) int32 in device memory,
+ * problem p = b * (K - 1) + q as everywhere in stage B: ANCSH_JOINT_REVOLUTE (0) fits the revolute objective of the entries above
+ * (objective_eval, :56-68: the two rotations agree on the joint direction, R0 u = R1 u), ANCSH_JOINT_PRISMATIC (1) the prismatic one
+ * (objective_eval_r, :70-81, what joint_transformation_estimator(..., joint_type='prismatic') minimises, :150-152): the point rows are
+ * the same, and the min(n0, n1) joint rows give way to three rows r0 - r1 of weight 1 between the two rotation VECTORS -- a slider
+ * does not turn against its base.  Every hypothesis fit (3 * 6 + 3 = 21 rows) and the refit on the consensus set (3 (n0 + n1) + 3
+ * rows) of a prismatic problem minimise it, with MINPACK's forward differences as for the revolute rows; scales, centring, the Kabsch
+ * start, ftol, maxfev, the translations, the verifier and the score are shared.  Kinds may be mixed freely inside one call: the kind is
+ * uniform per problem, a problem is a block index, so no lane ever diverges on it.
+ *   - joint_kind == NULL, or all zeros: the bytes of the entry without it (record, model, masks, best, score, tie counts, lm_stat).
+ *     With NULL the launches ARE that entry's; otherwise the same number of launches runs kernels that branch per block, whose
+ *     revolute half is the same code (profiles/r14_pose_resource_usage_{before,after,diff}.txt: the kernels of the entries without a
+ *     kind array keep their registers, scratch and occupancy).
+ *   - a device array is never read by the host (no synchronisation, so the call can be captured): the kernels take ANY non-zero entry
+ *     as prismatic.  The only valid host-side array is PINNED or REGISTERED host memory (hipHostMalloc / hipHostRegister, which the
+ *     kernels can read): a plain pageable host pointer is not a valid argument -- the runtime reports it as unregistered memory, it
+ *     cannot be told from a bad pointer and is not examined.  A pinned / registered array is checked before anything is launched, and an entry other
+ *     than 0 / 1 is ANCSH_EINVAL with the offending index in ancsh_last_error().  Nothing traps or asserts on the device.
+ *   - a prismatic problem does not read joint_dir[p]: it may hold NaN (a joint no point selects under
+ *     ancsh_pose_joint_direction_pred) and the fit is finite all the same.  joint_dir itself must still be a valid (nprob, 3) array. */
+#define ANCSH_JOINT_REVOLUTE 0
+#define ANCSH_JOINT_PRISMATIC 1
+int ancsh_ransac_joint_rec_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                const float *joint_dir, double inlier_th, int niter, const int *draws, unsigned long long seed,
+                                int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
+                                double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+                                int *tie_stats, double tie_window, const int *joint_kind, void *stream);
+int ancsh_ransac_joint_rec_dseed_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                      const float *joint_dir, double inlier_th, int niter, const int *draws,
+                                      const unsigned long long *seed, int max_n, double *out_model, unsigned char *out_inliers,
+                                      int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat,
+                                      int lm_schedule, double *record, int K, int *tie_stats, double tie_window, const int *joint_kind,
+                                      void *stream);
+int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                     const float *joint_dir, double inlier_th, int niter, const int *draws, const ancsh_stream_key *key,
+                                     int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
+                                     double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+                                     int *tie_stats, double tie_window, const int *joint_kind, void *stream);
 
 /* Batched estimateSimilarityUmeyama (lib/aligning.py:580-622; GT poses of evaluation/compute_gt_pose.py:87).
  * Problem p = rows [off[p], off[p+1]) of src/tgt.  out (nprob,32) float64: Scales(3) | Rotation(9, the
