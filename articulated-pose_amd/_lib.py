@@ -117,6 +117,9 @@ SIGNATURES = {
                                          + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, _vp],
     "ancsh_ransac_joint_rec_dkey_kind": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp, _c_int]
                                         + [_vp] * 7 + [_c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, _vp],
+    # the depth front end (no ABI bump: detected by its symbol): nclouds, depth_type, depth, mask, pixel_capacity, geom, cam, rows, capacity,
+    # offsets, counts, scratch, stream
+    "ancsh_depth_unproject_stream": [_c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

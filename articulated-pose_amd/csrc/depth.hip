@@ -1,0 +1,232 @@
+// depth.hip -- the depth front end of the streaming pipeline (gfx950): masked depth crops -> packed camera-space rows.
+//
+// Reference: tools/preprocess_data.py:259-298 -- a label mask picks the pixels (np.where, row-major), projMat back-projects them into
+// camera space (cloud_cam_real).  Here a ragged batch of crops is TWO launches in front of the xyz sampler (input.hip), every size read
+// from device memory (include/ancsh_hip.h, ancsh_depth_unproject_stream):
+//   count   : block (x, b) counts the valid pixels of chunk x of cloud b's crop -> scratch[b * chunks + x];
+//   scatter : block (x, b) sums the counts in front of its chunk (one block reduction over <= (b + 1) * chunks ints), recomputes validity
+//             and writes its rows in pixel order.  No atomics, no workgroup waits for another: the order is a pure function of the input.
+// A lane reads 16 bytes of depth (8 uint16 / 4 float32 pixels) and the matching mask bytes per step; the groups are aligned in the pixel
+// buffer, not in the crop, so a crop may start at any pixel.  The data is a few MB per batch: the two launches, not HBM, are the cost.
+#include "common.h"
+
+namespace ancsh {
+
+constexpr int DEPTH_THREADS = 256, DEPTH_WAVES = DEPTH_THREADS / 64;
+constexpr int DEPTH_CHUNKS = ANCSH_DEPTH_MAX_CHUNKS;
+constexpr int DEPTH_GEOM = 5, DEPTH_CAM = 7;            // ints / floats per cloud
+
+__device__ __forceinline__ bool depth_ok(unsigned short d) { return d != 0; }
+__device__ __forceinline__ bool depth_ok(float d) { return d > 0.f && d < __builtin_inff(); }       // NaN fails both
+
+// cloud b's crop: its first pixel `start`, width w and pixel count (0: a crop the host would have refused -- h or w < 1, or outside the
+// pixel buffer; such a cloud is handled like one without a valid pixel)
+__device__ __forceinline__ long depth_crop(const int *__restrict__ geom, int b, long pixel_capacity, long &start, int &w) {
+    const int *g = geom + (size_t)b * DEPTH_GEOM;
+    start = g[0];
+    const int h = g[1];
+    w = g[2];
+    if (start < 0 || h < 1 || w < 1) return 0;
+    const long n = (long)h * w;
+    return n <= pixel_capacity - start ? n : 0;
+}
+
+// the pixels [lo, hi) of the buffer that chunk x of `chunks` owns
+__device__ __forceinline__ void depth_chunk(long start, long n, int x, int chunks, long &lo, long &hi) {
+    const long per = (n + chunks - 1) / chunks;
+    lo = start + (long)x * per;
+    hi = start + ((long)(x + 1) * per < n ? (long)(x + 1) * per : n);
+    if (lo > hi) lo = hi;
+}
+
+// the V = 16 / sizeof(T) pixels [a0, a0 + V) of the buffer (a0 a multiple of V) -> d[], and the bit set of those that are valid pixels of
+// [lo, hi).  A group that reaches past the buffer's end is read pixel by pixel.
+template <typename T>
+__device__ __forceinline__ unsigned depth_group(const T *__restrict__ depth, const unsigned char *__restrict__ mask, long a0, long lo, long hi,
+                                                long pixel_capacity, T (&d)[16 / sizeof(T)]) {
+    constexpr int V = 16 / sizeof(T);
+    union { uint4 q; T e[V]; } u;
+    union { uint2 q; unsigned char e[8]; } m;
+    if (a0 + V <= pixel_capacity) {
+        u.q = *reinterpret_cast<const uint4 *>(depth + a0);
+        if (!mask) m.q = make_uint2(~0u, ~0u);
+        else if (V == 8) m.q = *reinterpret_cast<const uint2 *>(mask + a0);
+        else m.q = make_uint2(*reinterpret_cast<const unsigned *>(mask + a0), 0u);
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const bool in = a0 + k < pixel_capacity;
+            u.e[k] = in ? depth[a0 + k] : T(0);
+            m.e[k] = in && (!mask || mask[a0 + k]) ? 1 : 0;
+        }
+    }
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        d[k] = u.e[k];
+        const long a = a0 + k;
+        if (a >= lo && a < hi && m.e[k] && depth_ok(u.e[k])) bits |= 1u << k;
+    }
+    return bits;
+}
+
+__device__ __forceinline__ long depth_block_sum(long v, long *s_red) {      // sum over the block, uniform result
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();                                                    // s_red may still be read from an earlier call
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long t = 0;
+#pragma unroll
+    for (int k = 0; k < DEPTH_WAVES; ++k) t += s_red[k];
+    return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEPTH_THREADS) void depth_count_kernel(const T *__restrict__ depth, const unsigned char *__restrict__ mask,
+                                                                    long pixel_capacity, const int *__restrict__ geom, int chunks,
+                                                                    int *__restrict__ scratch) {
+    constexpr int V = 16 / sizeof(T);
+    __shared__ long s_red[DEPTH_WAVES];
+    const int b = blockIdx.y, x = blockIdx.x;
+    long start, lo, hi;
+    int w;
+    const long n = depth_crop(geom, b, pixel_capacity, start, w);
+    depth_chunk(start, n, x, chunks, lo, hi);
+    long c = 0;
+    if (hi > lo) {
+        const long g0 = lo / V, ng = (hi - 1) / V - g0 + 1;
+        for (long g = threadIdx.x; g < ng; g += DEPTH_THREADS) {
+            T d[V];
+            c += __popc(depth_group<T>(depth, mask, (g0 + g) * V, lo, hi, pixel_capacity, d));
+        }
+    }
+    const long t = depth_block_sum(c, s_red);
+    if (threadIdx.x == 0) scratch[(size_t)b * chunks + x] = (int)t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEPTH_THREADS) void depth_scatter_kernel(int nclouds, const T *__restrict__ depth,
+                                                                      const unsigned char *__restrict__ mask, long pixel_capacity,
+                                                                      const int *__restrict__ geom, const float *__restrict__ cam, int chunks,
+                                                                      const int *__restrict__ scratch, float *__restrict__ rows, long capacity,
+                                                                      int *__restrict__ offsets, int *__restrict__ counts) {
+    constexpr int V = 16 / sizeof(T);
+    __shared__ long s_red[DEPTH_WAVES];
+    __shared__ long s_own[2];
+    __shared__ int s_wave[2][DEPTH_WAVES];
+    const int b = blockIdx.y, x = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // rows in front of this chunk: max(count, 1) of every earlier cloud (an empty cloud owns one NaN row), and this cloud's earlier chunks
+    long before = 0;
+    for (int c = threadIdx.x; c <= b; c += DEPTH_THREADS) {
+        const int *s = scratch + (size_t)c * chunks;
+        long tot = 0, head = 0;
+        for (int k = 0; k < chunks; ++k) {
+            if (k == x) head = tot;
+            tot += s[k];
+        }
+        if (c < b) before += tot > 1 ? tot : 1;
+        else s_own[0] = tot, s_own[1] = head;
+    }
+    const long cloud_base = depth_block_sum(before, s_red);             // its barriers publish s_own
+    const long total = s_own[0];
+    long base = cloud_base + s_own[1];
+    if (x == 0 && threadIdx.x == 0) {
+        const long end = cloud_base + (total > 1 ? total : 1);
+        offsets[b] = (int)(cloud_base < 0x7fffffffL ? cloud_base : 0x7fffffffL);
+        counts[b] = (int)total;
+        if (b == nclouds - 1) offsets[nclouds] = (int)(end < 0x7fffffffL ? end : 0x7fffffffL);
+        if (total == 0 && cloud_base < capacity) {
+            const float q = __builtin_nanf("");
+            rows[cloud_base * 3] = q, rows[cloud_base * 3 + 1] = q, rows[cloud_base * 3 + 2] = q;
+        }
+    }
+    long start, lo, hi;
+    int w;
+    const long n = depth_crop(geom, b, pixel_capacity, start, w);
+    depth_chunk(start, n, x, chunks, lo, hi);
+    if (hi <= lo) return;                                               // uniform
+    const int row0 = geom[(size_t)b * DEPTH_GEOM + 3], col0 = geom[(size_t)b * DEPTH_GEOM + 4];
+    const float *A = cam + (size_t)b * DEPTH_CAM;
+    const float A00 = A[0], A01 = A[1], A02 = A[2], A10 = A[3], A11 = A[4], A12 = A[5], scale = A[6];
+    const long g0 = lo / V, ng = (hi - 1) / V - g0 + 1;
+    int buf = 0;
+    for (long gb = 0; gb < ng; gb += DEPTH_THREADS, buf ^= 1) {         // uniform trip count: every wave reaches the barrier
+        const long g = gb + threadIdx.x;
+        T d[V];
+        const unsigned bits = g < ng ? depth_group<T>(depth, mask, (g0 + g) * V, lo, hi, pixel_capacity, d) : 0u;
+        const int c = __popc(bits);
+        int incl = c;                                                   // inclusive scan over the wave, in lane (= pixel) order
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o);
+            if (lane >= o) incl += t;
+        }
+        if (lane == 63) s_wave[buf][wave] = incl;
+        __syncthreads();                                                // s_wave is double-buffered: one barrier per step
+        int wave_base = 0, step = 0;
+#pragma unroll
+        for (int k = 0; k < DEPTH_WAVES; ++k) {
+            const int v = s_wave[buf][k];
+            if (k < wave) wave_base += v;
+            step += v;
+        }
+        if (bits) {
+            long r = base + wave_base + (incl - c);
+            const long p0 = (g0 + g) * V - start;                       // crop position of the group's first pixel; < 0 only in front of lo
+            int i = p0 >= 0 ? (int)(p0 / w) : 0, j = (int)(p0 - (long)i * w);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                if (bits >> k & 1u) {
+                    const float row = (float)(row0 + i), col = (float)(col0 + j);
+                    const float z = (float)d[k] * scale;
+                    const float gx = fmaf(A01, row, fmaf(A00, col, A02)), gy = fmaf(A11, row, fmaf(A10, col, A12));
+                    if (r < capacity) rows[r * 3] = z * gx, rows[r * 3 + 1] = z * gy, rows[r * 3 + 2] = z;
+                    ++r;
+                }
+                if (++j == w) j = 0, ++i;
+            }
+        }
+        base += step;
+    }
+}
+
+template <typename T>
+static void depth_launch(int nclouds, const void *depth, const unsigned char *mask, long pixel_capacity, const int *geom, const float *cam,
+                         float *rows, long capacity, int *offsets, int *counts, int *scratch, hipStream_t st) {
+    // the grid is a function of (pixel_capacity, nclouds) alone: ~2048 pixels of an even share per chunk, at most DEPTH_CHUNKS chunks a cloud
+    long chunks = (pixel_capacity / nclouds + 2047) / 2048;
+    chunks = chunks < 1 ? 1 : chunks > DEPTH_CHUNKS ? DEPTH_CHUNKS : chunks;
+    const dim3 grid((unsigned)chunks, nclouds);
+    hipLaunchKernelGGL(depth_count_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, (const T *)depth, mask, pixel_capacity, geom, (int)chunks,
+                       scratch);
+    hipLaunchKernelGGL(depth_scatter_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, nclouds, (const T *)depth, mask, pixel_capacity, geom, cam,
+                       (int)chunks, scratch, rows, capacity, offsets, counts);
+}
+
+}  // namespace ancsh
+
+using namespace ancsh;
+
+extern "C" int ancsh_depth_unproject_stream(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
+                                            const int *geom, const float *cam, float *rows, long capacity, int *offsets, int *counts,
+                                            int *scratch, void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0, "depth_unproject_stream: bad shape nclouds=%d", nclouds);
+    ANCSH_REQUIRE(nclouds <= 65535, "depth_unproject_stream: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
+                  "depth_unproject_stream: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 30), "depth_unproject_stream: pixel_capacity=%ld pixels out of range",
+                  pixel_capacity);
+    ANCSH_REQUIRE(capacity >= pixel_capacity, "depth_unproject_stream: capacity=%ld rows is below pixel_capacity=%ld", capacity,
+                  pixel_capacity);
+    ANCSH_REQUIRE(depth && geom && cam && rows && offsets && counts && scratch, "depth_unproject_stream: null pointer");
+    ANCSH_REQUIRE(((size_t)depth & 15) == 0 && ((size_t)mask & 7) == 0,
+                  "depth_unproject_stream: depth must be 16-byte aligned and mask 8-byte aligned (the crops inside them may start anywhere)");
+    if (nclouds == 0) return ANCSH_OK;
+    if (depth_type == ANCSH_DEPTH_U16)
+        depth_launch<unsigned short>(nclouds, depth, mask, pixel_capacity, geom, cam, rows, capacity, offsets, counts, scratch,
+                                     (hipStream_t)stream);
+    else
+        depth_launch<float>(nclouds, depth, mask, pixel_capacity, geom, cam, rows, capacity, offsets, counts, scratch, (hipStream_t)stream);
+    return check_launch("depth_unproject_stream");
+}

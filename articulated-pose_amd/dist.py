@@ -321,6 +321,9 @@ class ShardedPipeline(object):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
+        if pipeline_kw.get("depth_capacity") is not None:
+            raise ValueError("ShardedPipeline does not shard the depth front end (depth_capacity): stream depth frames through "
+                             "AncshPipeline.submit_depth on one GPU")
         if joint_types is not None:        # the kinds belong to the object class, so every rank's shard gets the same K - 1 of them per cloud
             pipeline_kw.update(joint_types=joint_types)
         self.joint_source = check_joint_source(joint_source)

@@ -87,7 +87,8 @@ def check_joint_inputs(joint_source, couple, joint_cls, pred):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False):
+    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
+                 depth=None):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -113,9 +114,13 @@ class _Slot(object):
             self.nchan = 3 if xyz else RAW_NCHAN
             lead = 4 if self.keyed else 2
             self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
-            self.hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32, device=device)
-            self.h_rows = torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
-            self.h_hdr = torch.zeros((lead + (B + 1) + B,), dtype=torch.int32).pin_memory()
+            # depth (the depth front end; raw_capacity = its pixel capacity): the rows are unprojected on the device, so they have no pinned
+            # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam)
+            from .depth import CAM_WORDS, GEOM_WORDS
+            words = lead + (B + 1) + B + ((GEOM_WORDS + CAM_WORDS) * B if depth else 0)
+            self.hdr = torch.zeros((words,), dtype=torch.int32, device=device)
+            self.h_rows = None if depth else torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
+            self.h_hdr = torch.zeros((words,), dtype=torch.int32).pin_memory()
             self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
@@ -137,9 +142,12 @@ class _Slot(object):
                 if range_guard:
                     self.dense32, self.h_dense32 = pair(device=device), pinned()
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
-            self.np_rows, self.np_seed, self.np_off, self.np_nf = (self.h_rows.numpy(), hdr[:2].view(np.int64), hdr[lead:lead + B + 1],
-                                                                   hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
+            self.np_rows, self.np_seed, self.np_off, self.np_nf = (None if depth else self.h_rows.numpy(), hdr[:2].view(np.int64),
+                                                                   hdr[lead:lead + B + 1], hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
             self.np_base = hdr[2:3] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
+            if depth:
+                self._init_depth(B, lead, raw_capacity, depth, device)
+                return
             # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
             rs = np.random.RandomState(0)
             self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
@@ -149,6 +157,46 @@ class _Slot(object):
             self.np_nf[:] = 1.0
             self.raw_rows.copy_(self.h_rows)
             self.hdr.copy_(self.h_hdr)
+
+    def _init_depth(self, B, lead, capacity, depth, device):
+        """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
+        counts with their pinned copy, and host / device views of the header's geometry and camera blocks.  Until the first submit:
+        B crops of random depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes)."""
+        from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS
+        npt, tt, _ = DEPTH_DTYPES[depth]
+        self.pix = torch.zeros((capacity,), dtype=tt, device=device)
+        self.mask = torch.zeros((capacity,), dtype=torch.uint8, device=device)
+        self.h_pix = torch.zeros((capacity,), dtype=tt).pin_memory()
+        self.h_mask = torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
+        self.scratch = torch.zeros((B * MAX_CHUNKS,), dtype=torch.int32, device=device)
+        self.counts = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.h_counts = torch.zeros((B,), dtype=torch.int32).pin_memory()
+        g0 = lead + 2 * B + 1
+        c0 = g0 + GEOM_WORDS * B
+        hdr = self.h_hdr.numpy()
+        self.np_pix, self.np_mask = self.h_pix.numpy().view(npt), self.h_mask.numpy()
+        self.np_geom = hdr[g0:c0].reshape(B, GEOM_WORDS)
+        self.np_cam = hdr[c0:c0 + CAM_WORDS * B].view(np.float32).reshape(B, CAM_WORDS)
+        self.geom = self.hdr[g0:c0].view(B, GEOM_WORDS)
+        self.cam = self.hdr[c0:c0 + CAM_WORDS * B].view(torch.float32).view(B, CAM_WORDS)
+        rs = np.random.RandomState(0)
+        per = capacity // B
+        w = max(1, int(np.sqrt(per)))
+        h = per // w
+        if npt == np.uint16:
+            self.np_pix[:] = rs.randint(32768, 65536, capacity).astype(np.uint16)
+            scale = 1.0 / 65535.0
+        else:
+            self.np_pix[:] = rs.uniform(0.5, 1.0, capacity).astype(np.float32)
+            scale = 1.0
+        self.np_mask[:] = 1
+        for b in range(B):
+            self.np_geom[b] = (b * per, h, w, 0, 0)
+            self.np_cam[b] = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
+        self.np_nf[:] = 1.0
+        self.pix.copy_(self.h_pix)
+        self.mask.copy_(self.h_mask)
+        self.hdr.copy_(self.h_hdr)
 
     def header(self, B):
         """(seed (1,) int64 -- keyed: the key block (4,) int32 --, offsets (B+1,) int32, norm factors (B,) float32) views of the device
@@ -184,7 +232,7 @@ class AncshPipeline(object):
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None):
+                 joint_types=None, depth_capacity=None, depth_dtype="uint16"):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -210,6 +258,25 @@ class AncshPipeline(object):
             if not 1 <= int(num_points) <= ARTICULATION_MAX_N:
                 raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
                                  % (ARTICULATION_MAX_N, num_points))
+        # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
+        # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
+        # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
+        # (ancsh_depth_unproject_stream, at most two launches) in front of the xyz sampler.  It takes raw_capacity's place.
+        self.depth_dtype = None
+        if depth_capacity is not None:
+            from .depth import check_depth_dtype
+            self.depth_dtype = check_depth_dtype(depth_dtype)
+            if raw_capacity is not None:
+                raise ValueError("depth_capacity takes raw_capacity's place: pass one of them")
+            if not self.predicted:
+                raise ValueError("depth_capacity needs joint_source='predicted': a depth pixel carries no joint label")
+            if dense:
+                raise ValueError("dense=True with the depth front end is not supported: its product is a label image, which needs a "
+                                 "pixel index per row")
+            if not int(batch_size) <= int(depth_capacity) < (1 << 30):
+                raise ValueError("depth_capacity must be in [batch_size, 2^30) pixels")
+            raw_capacity = int(depth_capacity)
+        self.depth_capacity = None if depth_capacity is None else int(depth_capacity)
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls; predicted: x y z) per batch, padding included
         if raw_capacity is not None:
@@ -269,7 +336,7 @@ class AncshPipeline(object):
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
-                            self.dense, xyz=self.predicted) for _ in range(max(1, slots))]
+                            self.dense, xyz=self.predicted, depth=self.depth_dtype) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -333,6 +400,9 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.depth_dtype is not None:   # the depth front end: the slot's crops -> its rows, offsets and counts, in front of the xyz sampler
+            from .depth import depth_unproject
+            depth_unproject(sl.pix, sl.mask, sl.geom, sl.cam, out=(sl.raw_rows, off, sl.counts), scratch=sl.scratch)
         if self.predicted:                 # xyz rows: the sampler's xyz twin, same P (no joint_cls: the fit reads the index head)
             _lib.call("ancsh_input_sample_stream_xyz_keyed" if self.keyed else "ancsh_input_sample_stream_xyz", self.B, self.N, sl.nchan,
                       _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), _lib.ptr(seed), _lib.ptr(sl.P), None)
@@ -464,6 +534,8 @@ class AncshPipeline(object):
         RuntimeError.  Either way the pipeline stays usable."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
+        if self.depth_dtype is not None:
+            raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
         from .dataset import check_raw_clouds, check_stream_key, seed_bits
         if self.keyed:
             cloud_base = check_stream_key(cloud_base, self.B, self.K)
@@ -517,6 +589,69 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
+    def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0):
+        """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
+        (depth_crop (h, w) of the pipeline's depth_dtype, mask_crop (h, w) bool / integer or None = every pixel, (row0, col0) = the crop's
+        origin in the full image); norm_factors = one finite float per frame; cameras = one 6-vector of unprojection coefficients
+        (depth.unprojection_from_intrinsics / unprojection_from_projmat) or one per frame; depth_scale = one value or one per frame
+        (depth unit -> the cloud's unit).  The valid pixels of each crop (mask non-zero and a usable depth) become the frame's cloud on the
+        device; a frame without one gives an all-NaN record and count 0.  A short batch is padded with its first frame (whose pixels are
+        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base: as submit().  Bad input
+        raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.  Either way the pipeline stays usable."""
+        if self.depth_dtype is None:
+            raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
+        from .dataset import check_stream_key, seed_bits
+        from .depth import check_depth_frames, pack_depth_frames
+        if self.keyed:
+            cloud_base = check_stream_key(cloud_base, self.B, self.K)
+        elif cloud_base != 0:
+            raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
+        depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
+        n_valid = len(depths)
+        pixels = sum(d.size for d in depths)
+        padded = pixels + (self.B - n_valid) * depths[0].size
+        if padded > self.depth_capacity:
+            raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
+                             % (padded, self.depth_capacity))
+        if len(self._inflight) == len(self.slots):
+            raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
+        if not self._prepared:
+            self.prepare()
+        seed = self.seed + 2 * self._submitted if seed is None else int(seed)
+        sl = self.slots[self._next]
+        sl.h2d_done.synchronize()                  # the previous batch's copies out of the pinned staging have completed
+        sl.np_seed[0] = seed_bits(seed)
+        if self.keyed:
+            sl.np_base[0] = cloud_base
+        pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
+        sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
+        sl.np_cam[:n_valid] = cam
+        sl.np_cam[n_valid:] = cam[0]
+        sl.np_nf[:n_valid] = nf
+        sl.np_nf[n_valid:] = nf[0]
+        cur = torch.cuda.current_stream(self.device)
+        if cur != sl.stream and not cur.query():
+            sl.stream.wait_stream(cur)
+        with torch.cuda.stream(sl.stream):
+            sl.pix[:pixels].copy_(sl.h_pix[:pixels], non_blocking=True)
+            sl.mask[:pixels].copy_(sl.h_mask[:pixels], non_blocking=True)
+            sl.hdr.copy_(sl.h_hdr, non_blocking=True)
+            sl.h2d_done.record(sl.stream)
+            if sl.graph is not None:
+                sl.graph.replay()
+            else:
+                sl.out = self._run(sl)
+            sl.h_record.copy_(sl.out["record"], non_blocking=True)      # right behind the replay (see submit())
+            sl.h_counts.copy_(sl.counts, non_blocking=True)
+            if self.articulation:
+                sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
+            if self.range_guard:
+                sl.h_flags.copy_(sl.flags, non_blocking=True)
+            sl.d2h_done.record(sl.stream)
+        self._next = (self._next + 1) % len(self.slots)
+        self._submitted += 1
+        self._inflight.append((sl, tag, seed, n_valid))
+
     def retire(self, flags=False, articulation=False, dense=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
@@ -525,7 +660,8 @@ class AncshPipeline(object):
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
         block (flagged clouds: the f32 graph's rows, like their records).  dense=True (a pipeline built with dense=True): + (labels (R,)
         int32, values (R, 7) float32, offsets (n_valid+1,) int64) as the last element: the valid clouds' R raw rows in submission order,
-        cloud c's rows [offsets[c], offsets[c+1]) (raw_point_labels; flagged clouds: the f32 graph's rows)."""
+        cloud c's rows [offsets[c], offsets[c+1]) (raw_point_labels; flagged clouds: the f32 graph's rows).  A pipeline built with
+        depth_capacity appends the valid-pixel counts (n_valid,) int32 of the batch's frames as the last element."""
         if articulation and not self.articulation:
             raise RuntimeError("retire(articulation=True) needs AncshPipeline(..., articulation=True)")
         if dense and not self.dense:
@@ -536,6 +672,7 @@ class AncshPipeline(object):
         sl.d2h_done.synchronize()
         record = sl.h_record[:n_valid].numpy().copy()
         art = sl.h_art[:n_valid].numpy().copy() if articulation else None
+        counts = sl.h_counts[:n_valid].numpy().copy() if self.depth_dtype is not None else None
         off = sl.np_off[:n_valid + 1].astype(np.int64)          # the batch's own offsets: a slot's staging is rewritten only after it retires
         rv = int(off[-1])
         dn = (sl.h_dense[0][:rv].numpy().copy(), sl.h_dense[1][:rv].numpy().copy(), off) if dense else None
@@ -561,7 +698,8 @@ class AncshPipeline(object):
             self.f32_reruns += 1
         out = (tag, seed, record, words) if flags else (tag, seed, record)
         out = out + (art,) if articulation else out
-        return out + (dn,) if dense else out
+        out = out + (dn,) if dense else out
+        return out + (counts,) if counts is not None else out
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
@@ -578,3 +716,21 @@ class AncshPipeline(object):
             self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
         while self._inflight:
             yield self.retire(flags, articulation, dense)
+
+    def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False):
+        """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
+        last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base; yields what retire() returns, in
+        submission order, the valid-pixel counts last."""
+        if articulation and not self.articulation:
+            raise RuntimeError("stream_depth_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
+        for k, item in enumerate(batches):
+            if len(self._inflight) == len(self.slots):
+                yield self.retire(flags, articulation)
+            item = tuple(item)
+            kw = dict(cameras=cameras, depth_scale=depth_scale)
+            if isinstance(item[-1], dict):
+                kw.update(item[-1])
+                item = item[:-1]
+            self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
+        while self._inflight:
+            yield self.retire(flags, articulation)

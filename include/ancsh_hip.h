@@ -790,6 +790,38 @@ int ancsh_input_sample_stream_xyz(int nclouds, int num_points, int nchan, const 
 int ancsh_input_sample_stream_xyz_keyed(int nclouds, int num_points, int nchan, const float *rows, long capacity, const int *offsets,
                                         const float *norm_factor, const ancsh_stream_key *key, float *P, int *perm_out, void *stream);
 
+/* The depth front end of the streaming pipeline (tools/preprocess_data.py:259-298: a mask picks the pixels, projMat back-projects them
+ * into camera space, cloud_cam_real): masked depth crops -> the packed rows and offsets the samplers above read, in at most TWO launches
+ * in which every size-dependent value is read from DEVICE memory, so one captured graph serves any crop sizes.  The ABI version is
+ * unchanged; callers detect the entry by its symbol.
+ *   depth : pixel_capacity depth values, uint16 (depth_type = ANCSH_DEPTH_U16) or float32 (ANCSH_DEPTH_F32), 16-byte aligned;
+ *   mask  : pixel_capacity bytes, 8-byte aligned, or NULL = every pixel of a crop;
+ *   geom  : (nclouds, 5) int32 {start, h, w, row0, col0}: cloud b's h x w crop lies row-major at depth[start .. start + h*w) (any start, not
+ *           a prefix sum: clouds may share pixels, e.g. the padding clouds of a short batch) and its pixel (0, 0) is pixel (row0, col0) of
+ *           the full image;
+ *   cam   : (nclouds, 7) float32 {A00, A01, A02, A10, A11, A12, depth_scale}.
+ * Pixel (i, j) of the crop, depth d, is VALID when its mask byte is non-zero (or mask == NULL) and d != 0 (uint16) / d > 0 && d < +inf
+ * (float32: NaN, Inf, zero and negative depths are dropped).  Its point, with row = (float)(row0 + i), col = (float)(col0 + j), in exactly
+ * this f32 arithmetic (no contraction):
+ *   z = (float)d * depth_scale;  x = z * fmaf(A01, row, fmaf(A00, col, A02));  y = z * fmaf(A11, row, fmaf(A10, col, A12)).
+ * Outputs: counts (nclouds) int32 = valid pixels per cloud; offsets (nclouds + 1) int32, offsets[0] = 0, offsets[b+1] = offsets[b] +
+ * max(counts[b], 1) (saturating at 2^31 - 1); rows (capacity, 3) float32: cloud b's valid pixels in the row-major order of its crop
+ * (np.where(mask)) at rows [offsets[b], offsets[b] + counts[b]).  A cloud without a valid pixel -- or whose crop has h < 1, w < 1 or lies
+ * outside [0, pixel_capacity), which callers refuse on the host -- gets ONE row of three NaNs and counts[b] = 0: the sampler then hands the
+ * network a non-finite cloud, whose record alone is poisoned.  Rows at and beyond offsets[nclouds] or capacity are left untouched; the
+ * sum of h*w over the clouds should not exceed capacity (a cloud whose rows would pass it is cut there and refused by the samplers).
+ * Deterministic byte for byte: a count pass (block (x, b) counts chunk x of cloud b's crop into scratch[b * chunks + x]) and a scatter pass
+ * (each block sums the counts in front of its chunk and writes its rows in pixel order); no atomics, no block waits for another.
+ * scratch: nclouds * ANCSH_DEPTH_MAX_CHUNKS int32 of working memory.  Graph-capturable: the grid depends on (pixel_capacity, nclouds) only;
+ * no host sync, no allocation.  nclouds == 0 launches nothing.  Checked before any launch: 0 <= nclouds <= 65535, depth_type,
+ * 0 <= pixel_capacity < 2^30, capacity >= pixel_capacity, null pointers (mask may be NULL), the two alignments. */
+#define ANCSH_DEPTH_U16 0
+#define ANCSH_DEPTH_F32 1
+#define ANCSH_DEPTH_MAX_CHUNKS 64
+int ancsh_depth_unproject_stream(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
+                                 const int *geom, const float *cam, float *rows, long capacity, int *offsets, int *counts, int *scratch,
+                                 void *stream);
+
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows
  * [offsets[b], offsets[b+1]) of `rows` (capacity x nchan float32, x y z first), norm factor norm_factor[b], sampled points P (nclouds,

@@ -1,0 +1,141 @@
+"""Throughput of the depth front end (AncshPipeline(depth_capacity=...).stream_depth_batches: uint16 depth crops + masks in, pose records
+out; the unprojection and the compaction of the valid pixels run inside the captured step) against the xyz stream on the same frames,
+at configs[2]'s shape (K = 3, 32 x 1024, 10000 / 200 hypotheses, couple=True, synthetic weights, 20 slots, predicted joints).  Three legs,
+alternated in one process for --rounds rounds:
+  a: the xyz stream fed clouds unprojected on the host BEFORE the clock starts (the best case without the front end);
+  b: the xyz stream with the numpy unprojection of each batch inside the timed loop (what a user of a depth camera does today);
+  c: the depth stream.
+Leg a runs twice in the first round: a2 / a is the run-to-run spread the ratios are read against.  Prints one JSON line.
+
+    python tools/depth_stream_bench.py [--rounds 3] [--passes 8] [--slots 20] [--legs abc]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import articulated_pose_amd  # noqa: E402,F401
+from articulated_pose_amd.depth import unprojection_from_intrinsics  # noqa: E402
+from articulated_pose_amd.pipeline import AncshPipeline  # noqa: E402
+from articulated_pose_amd.synthetic import make_cloud  # noqa: E402
+from articulated_pose_amd.weights import synthetic_weights  # noqa: E402
+
+SIDE, SCALE, POINTS = 256, 2.5e-4, 6000
+
+
+def make_frame(rs, P, target):
+    """A uint16 depth crop + mask that show the cloud P (n, 3), centred 1.5 units in front of a pinhole camera whose focal length is
+    searched so that the object covers about `target` pixels (a depth camera sees a surface: most pixels of the silhouette are valid).
+    The object's pixels carry its depth, the rest of its bounding box a background depth outside the mask; 2 % holes.
+    -> ((depth crop, mask crop, origin), focal length)."""
+    P = P - P.mean(0)
+    P = P * (0.5 / np.abs(P).max())
+    z = P[:, 2] + 1.5
+    lo, hi = 10.0, 250.0
+    for _ in range(12):
+        f = 0.5 * (lo + hi)
+        col = np.rint(f * P[:, 0] / z + SIDE / 2).astype(int)
+        row = np.rint(f * P[:, 1] / z + SIDE / 2).astype(int)
+        lo, hi = (f, hi) if len(np.unique(row * SIDE + col)) < target else (lo, f)
+    depth = np.full((SIDE, SIDE), 3.0)
+    mask = np.zeros((SIDE, SIDE), bool)
+    depth[row, col], mask[row, col] = z, True
+    depth[rs.uniform(size=depth.shape) < 0.02] = 0.0
+    r0, r1, c0, c1 = row.min(), row.max() + 1, col.min(), col.max() + 1
+    return (np.rint(depth[r0:r1, c0:c1] / SCALE).astype(np.uint16), mask[r0:r1, c0:c1].copy(), (int(r0), int(c0))), f
+
+
+def host_unproject(frame, A):
+    """The numpy back-projection a user runs per frame today (float32, np.where order)."""
+    d, m, (r0, c0) = frame
+    i, j = np.nonzero(m & (d != 0))
+    z = d[i, j].astype(np.float32) * np.float32(SCALE)
+    col, row = (j + c0).astype(np.float32), (i + r0).astype(np.float32)
+    return np.stack([z * (A[0] * col + A[1] * row + A[2]), z * (A[3] * col + A[4] * row + A[5]), z], 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=8, help="passes over the 640 frames (20 batches) per timed leg")
+    ap.add_argument("--slots", type=int, default=20)
+    ap.add_argument("--clouds", type=int, default=640)
+    ap.add_argument("--legs", default="abc", help="the legs to run (a profiler run times one: --legs c)")
+    args = ap.parse_args()
+    K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
+    rs = np.random.RandomState(0)
+    sizes = rs.randint(700, 3001, args.clouds)
+    made = [make_frame(rs, make_cloud(i, N=POINTS, K=K)["P"], int(n)) for i, n in enumerate(sizes)]
+    frames = [m[0] for m in made]
+    cams = np.stack([unprojection_from_intrinsics(m[1], m[1], SIDE / 2, SIDE / 2) for m in made])
+    A = cams.astype(np.float32)
+    nf = np.ones(B, np.float32)
+    starts = range(0, len(frames) - B + 1, B)
+    fbatches = [(frames[i:i + B], nf, dict(cameras=cams[i:i + B])) for i in starts]
+    unproject = lambda k: [host_unproject(f, A[k * B + c]) for c, f in enumerate(fbatches[k][0])]
+    cbatches = [(unproject(k), nf) for k in range(len(fbatches))]
+    valid = np.array([len(c) for cl, _ in cbatches for c in cl])
+    pixels = np.array([f[0].size for f in frames[:len(fbatches) * B]])
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted")
+    xyz = AncshPipeline(K, wa, wn, B, N, dev, raw_capacity=B * 3000, **kw).prepare() if set(args.legs) & set("ab") else None
+    cap = int(max(sum(f[0].size for f in fb[0]) for fb in fbatches))
+    depth = AncshPipeline(K, wa, wn, B, N, dev, depth_capacity=cap, depth_dtype="uint16", **kw).prepare() if "c" in args.legs else None
+    torch.cuda.synchronize()
+
+    def drain(gen):
+        n = 0
+        for item in gen:
+            n += item[2].shape[0]
+        torch.cuda.synchronize()
+        return n
+
+    def leg(name, passes):
+        t0 = time.perf_counter()
+        if name == "a":
+            n = drain(xyz.stream_batches(cbatches[k] for _ in range(passes) for k in range(len(cbatches))))
+        elif name == "b":
+            n = drain(xyz.stream_batches((unproject(k), nf) for _ in range(passes) for k in range(len(fbatches))))
+        else:
+            n = drain(depth.stream_depth_batches((fbatches[k] for _ in range(passes) for k in range(len(fbatches))), None, SCALE))
+        return n / (time.perf_counter() - t0)
+
+    for name in args.legs:                      # warm-up: every slot replayed with real input
+        leg(name, 1)
+    rates = {name: [] for name in args.legs}
+    spread = None
+    for r in range(args.rounds):
+        for name in args.legs:
+            rates[name].append(leg(name, args.passes))
+            if name == "a" and r == 0:
+                again = leg("a", args.passes)
+                spread = again / rates["a"][0]
+    med = {name: float(np.median(v)) for name, v in rates.items()}
+    hdr = lambda p: 4 * p.slots[0].hdr.numel()
+    line = {"metric": "clouds/s, depth stream (c) vs xyz stream on host-unprojected clouds (a: untimed, b: timed numpy unprojection)",
+            "clouds_per_s": {k: round(v, 1) for k, v in med.items()},
+            "clouds_per_s_rounds": {k: [round(x, 1) for x in v] for k, v in rates.items()},
+            "valid_pixels_per_frame": [int(valid.min()), int(valid.max())], "crop_pixels_per_frame": [int(pixels.min()), int(pixels.max())],
+            "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "joint_source": "predicted",
+                      "depth_dtype": "uint16", "frames": len(fbatches) * B, "passes": args.passes, "rounds": args.rounds}}
+    if "a" in med and "c" in med:
+        line["c_over_a"] = round(med["c"] / med["a"], 4)
+    if "b" in med and "c" in med:
+        line["c_over_b"] = round(med["c"] / med["b"], 4)
+    if spread is not None:
+        line["a_over_a"] = round(spread, 4)
+    nb = len(fbatches)
+    if xyz is not None:
+        line["h2d_bytes_per_batch_a"] = int(round(12 * valid.sum() / nb + hdr(xyz)))
+    if depth is not None:
+        line["h2d_bytes_per_batch_c"] = int(round(3 * pixels.sum() / nb + hdr(depth)))
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
