@@ -191,17 +191,115 @@ __global__ __launch_bounds__(DEPTH_THREADS) void depth_scatter_kernel(int ncloud
     }
 }
 
+// the grid is a function of (pixel_capacity, nclouds) alone: ~2048 pixels of an even share per chunk, at most DEPTH_CHUNKS chunks a cloud
+static long depth_chunks(long pixel_capacity, int nclouds) {
+    const long chunks = (pixel_capacity / nclouds + 2047) / 2048;
+    return chunks < 1 ? 1 : chunks > DEPTH_CHUNKS ? DEPTH_CHUNKS : chunks;
+}
+
 template <typename T>
 static void depth_launch(int nclouds, const void *depth, const unsigned char *mask, long pixel_capacity, const int *geom, const float *cam,
                          float *rows, long capacity, int *offsets, int *counts, int *scratch, hipStream_t st) {
-    // the grid is a function of (pixel_capacity, nclouds) alone: ~2048 pixels of an even share per chunk, at most DEPTH_CHUNKS chunks a cloud
-    long chunks = (pixel_capacity / nclouds + 2047) / 2048;
-    chunks = chunks < 1 ? 1 : chunks > DEPTH_CHUNKS ? DEPTH_CHUNKS : chunks;
+    const long chunks = depth_chunks(pixel_capacity, nclouds);
     const dim3 grid((unsigned)chunks, nclouds);
     hipLaunchKernelGGL(depth_count_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, (const T *)depth, mask, pixel_capacity, geom, (int)chunks,
                        scratch);
     hipLaunchKernelGGL(depth_scatter_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, nclouds, (const T *)depth, mask, pixel_capacity, geom, cam,
                        (int)chunks, scratch, rows, capacity, offsets, counts);
+}
+
+// ---- the inverse of the compaction: per-row labels / values -> per-pixel images (include/ancsh_hip.h, ancsh_depth_label_images) ----------
+// `total` dwords at `out`, dword e = value(e): whole 16-byte vectors where the address allows, single dwords in front of and behind them.
+// Consecutive lanes store consecutive addresses either way.
+template <typename F>
+__device__ __forceinline__ void depth_store_span(unsigned *__restrict__ out, long total, F value) {
+    long head = (long)(((16 - ((size_t)out & 15)) & 15) >> 2);
+    head = head < total ? head : total;
+    const long body = (total - head) >> 2;
+    for (long e = threadIdx.x; e < head; e += DEPTH_THREADS) out[e] = value(e);
+    uint4 *o4 = reinterpret_cast<uint4 *>(out + head);
+    for (long v = threadIdx.x; v < body; v += DEPTH_THREADS) {
+        const long e = head + 4 * v;
+        o4[v] = make_uint4(value(e), value(e + 1), value(e + 2), value(e + 3));
+    }
+    for (long e = head + 4 * body + threadIdx.x; e < total; e += DEPTH_THREADS) out[e] = value(e);
+}
+
+// Block (x, b) on the count / scatter passes' grid and chunking.  Its first row is offsets[b] + the counts of cloud b's earlier chunks, read
+// from the scratch the count pass left.  Per step of 256 groups: validity and the wave scan exactly as depth_scatter_kernel ranks its rows ->
+// the source row of every pixel of the step in LDS (-1: not a valid pixel, or a row cut at capacity); then the block stores the step's
+// labels and values as two contiguous spans.  labels / values travel as their bits (NaN payloads survive).
+template <typename T>
+__global__ __launch_bounds__(DEPTH_THREADS) void depth_label_images_kernel(const T *__restrict__ depth, const unsigned char *__restrict__ mask,
+                                                                           long pixel_capacity, const int *__restrict__ geom, int chunks,
+                                                                           const int *__restrict__ scratch, const int *__restrict__ offsets,
+                                                                           const unsigned *__restrict__ labels,
+                                                                           const unsigned *__restrict__ values, long capacity,
+                                                                           const int *__restrict__ dest, unsigned *__restrict__ img_labels,
+                                                                           unsigned *__restrict__ img_values, long image_capacity) {
+    constexpr int V = 16 / sizeof(T), STEP = DEPTH_THREADS * V;
+    __shared__ int s_wave[DEPTH_WAVES];
+    __shared__ int s_src[STEP];
+    const int b = blockIdx.y, x = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long start, lo, hi;
+    int w;
+    const long n = depth_crop(geom, b, pixel_capacity, start, w);
+    const long d0 = dest[b];
+    if (n == 0 || d0 < 0 || n > image_capacity - d0) return;            // uniform: a silenced cloud, an empty crop, an image past the buffer
+    depth_chunk(start, n, x, chunks, lo, hi);
+    if (hi <= lo) return;                                               // uniform
+    long base = offsets[b];
+    for (int k = 0; k < x; ++k) base += scratch[(size_t)b * chunks + k];        // <= 63 broadcast loads
+    const long g0 = lo / V, ng = (hi - 1) / V - g0 + 1;
+    for (long gb = 0; gb < ng; gb += DEPTH_THREADS) {                   // uniform trip count: every wave reaches the barriers
+        const long g = gb + threadIdx.x;
+        T d[V];
+        const unsigned bits = g < ng ? depth_group<T>(depth, mask, (g0 + g) * V, lo, hi, pixel_capacity, d) : 0u;
+        const int c = __popc(bits);
+        int incl = c;                                                   // inclusive scan over the wave, in lane (= pixel) order
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o);
+            if (lane >= o) incl += t;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();                                                // also: the previous step's readers of s_src are done
+        int wave_base = 0, step = 0;
+#pragma unroll
+        for (int k = 0; k < DEPTH_WAVES; ++k) {
+            const int v = s_wave[k];
+            if (k < wave) wave_base += v;
+            step += v;
+        }
+        long r = base + wave_base + (incl - c);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const bool on = bits >> k & 1u;
+            s_src[threadIdx.x * V + k] = on && r >= 0 && r < capacity ? (int)r : -1;
+            r += on;
+        }
+        __syncthreads();                                                // s_src is published; s_wave may be rewritten
+        const long a0 = (g0 + gb) * V;                                  // the step's window of the pixel buffer, cut to the chunk
+        const long pa = a0 > lo ? a0 : lo, pb = a0 + STEP < hi ? a0 + STEP : hi;
+        const int *src = s_src + (pa - a0);
+        const long q0 = d0 + (pa - start);
+        depth_store_span(img_labels + q0, pb - pa, [&](long e) { const int s = src[e]; return s >= 0 ? labels[s] : 0xffffffffu; });
+        depth_store_span(img_values + q0 * 7, (pb - pa) * 7, [&](long e) {
+            const int p = (int)(e / 7), s = src[p];
+            return s >= 0 ? values[(size_t)s * 7 + (e - p * 7)] : (unsigned)ANCSH_LABEL_NAN_BITS;
+        });
+        base += step;
+    }
+}
+
+template <typename T>
+static void depth_label_images_launch(int nclouds, const void *depth, const unsigned char *mask, long pixel_capacity, const int *geom,
+                                      const int *offsets, const int *scratch, const int *labels, const float *values, long capacity,
+                                      const int *dest, int *img_labels, float *img_values, long image_capacity, hipStream_t st) {
+    const long chunks = depth_chunks(pixel_capacity, nclouds);          // the count pass's chunking: scratch[b * chunks + x] is its layout
+    hipLaunchKernelGGL(depth_label_images_kernel<T>, dim3((unsigned)chunks, nclouds), dim3(DEPTH_THREADS), 0, st, (const T *)depth, mask,
+                       pixel_capacity, geom, (int)chunks, scratch, offsets, (const unsigned *)labels, (const unsigned *)values, capacity, dest,
+                       (unsigned *)img_labels, (unsigned *)img_values, image_capacity);
 }
 
 }  // namespace ancsh
@@ -229,4 +327,31 @@ extern "C" int ancsh_depth_unproject_stream(int nclouds, int depth_type, const v
     else
         depth_launch<float>(nclouds, depth, mask, pixel_capacity, geom, cam, rows, capacity, offsets, counts, scratch, (hipStream_t)stream);
     return check_launch("depth_unproject_stream");
+}
+
+extern "C" int ancsh_depth_label_images(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
+                                        const int *geom, const int *offsets, const int *scratch, const int *labels, const float *values,
+                                        long capacity, const int *dest, int *img_labels, float *img_values, long image_capacity,
+                                        void *stream) {
+    ANCSH_REQUIRE(nclouds >= 0, "depth_label_images: bad shape nclouds=%d", nclouds);
+    ANCSH_REQUIRE(nclouds <= 65535, "depth_label_images: %d clouds exceed the 65535-cloud grid range; split the batch", nclouds);
+    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
+                  "depth_label_images: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 30), "depth_label_images: pixel_capacity=%ld pixels out of range",
+                  pixel_capacity);
+    ANCSH_REQUIRE(capacity >= 0 && capacity < (1L << 30), "depth_label_images: capacity=%ld rows out of range", capacity);
+    ANCSH_REQUIRE(image_capacity >= 0 && image_capacity < (1L << 30), "depth_label_images: image_capacity=%ld pixels out of range",
+                  image_capacity);
+    ANCSH_REQUIRE(depth && geom && offsets && scratch && labels && values && dest && img_labels && img_values,
+                  "depth_label_images: null pointer");
+    ANCSH_REQUIRE(((size_t)depth & 15) == 0 && ((size_t)mask & 7) == 0,
+                  "depth_label_images: depth must be 16-byte aligned and mask 8-byte aligned (the crops inside them may start anywhere)");
+    if (nclouds == 0) return ANCSH_OK;
+    if (depth_type == ANCSH_DEPTH_U16)
+        depth_label_images_launch<unsigned short>(nclouds, depth, mask, pixel_capacity, geom, offsets, scratch, labels, values, capacity,
+                                                  dest, img_labels, img_values, image_capacity, (hipStream_t)stream);
+    else
+        depth_label_images_launch<float>(nclouds, depth, mask, pixel_capacity, geom, offsets, scratch, labels, values, capacity, dest,
+                                         img_labels, img_values, image_capacity, (hipStream_t)stream);
+    return check_launch("depth_label_images");
 }

@@ -164,6 +164,74 @@ def depth_unproject(depth, mask, geom, cam, capacity=None, out=None, scratch=Non
     return rows, offsets, counts
 
 
+LABEL_VALUES = 7        # per pixel, as per raw row: [W of the label | part NOCS (3) | NAOCS (3)] (dataset.DENSE_VALUES)
+LABEL_NAN_BITS = 0x7fc00000     # ANCSH_LABEL_NAN_BITS: the float32 NaN of a pixel without a row
+
+
+def depth_label_images(depth, mask, geom, dest, offsets, labels, values, out=None, scratch=None):
+    """ancsh_depth_label_images on device tensors (no host sync): the per-row labels (capacity,) int32 / values (capacity, 7) float32 of
+    ancsh_raw_point_labels back on the pixel grid.  depth, mask, geom: what depth_unproject() was given; offsets (B+1,) int32 and scratch:
+    what it wrote (pass the SAME scratch tensor to both calls: it carries the per-chunk counts); dest (B,) int32: where cloud b's h * w
+    image starts in the image buffers, < 0 = the cloud writes nothing.  -> (img_labels (image_capacity,) int32, img_values
+    (image_capacity, 7) float32); out = the same pair preallocated (a captured step passes slot-owned buffers), else pixel_capacity
+    elements prefilled with -1 / NaN.  A pixel without a row reads -1 / NaN; elements of no cloud's image keep what they held."""
+    if not depth.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = depth.device
+    kinds = {torch.float32: 1, torch.int16: 0}
+    if hasattr(torch, "uint16"):
+        kinds[torch.uint16] = 0
+    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
+    cap_px = int(depth.shape[0])
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (cap_px,) or not mask.is_contiguous()):
+        raise ValueError("mask must be a contiguous (%d,) uint8 tensor" % cap_px)
+    B = int(geom.shape[0])
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or not geom.is_contiguous():
+        raise ValueError("geom must be (B, 5) int32, contiguous")
+    for name, t, n in (("dest", dest, B), ("offsets", offsets, B + 1)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous (%d,) int32 tensor" % (name, n))
+    cap = int(labels.shape[0]) if labels.dim() == 1 else -1
+    if labels.dtype != torch.int32 or values.dtype != torch.float32 or cap < 0 or tuple(values.shape) != (cap, LABEL_VALUES) \
+            or not (labels.is_contiguous() and values.is_contiguous()):
+        raise ValueError("labels must be (capacity,) int32 and values (capacity, %d) float32, contiguous" % LABEL_VALUES)
+    if scratch is None or scratch.dtype != torch.int32 or scratch.numel() < B * MAX_CHUNKS or not scratch.is_contiguous():
+        raise ValueError("scratch must be the (>= %d,) int32 tensor depth_unproject() was given" % (B * MAX_CHUNKS))
+    if out is None:
+        out = (torch.full((cap_px,), -1, dtype=torch.int32, device=dev),
+               torch.full((cap_px, LABEL_VALUES), float("nan"), dtype=torch.float32, device=dev))
+    img_labels, img_values = out
+    icap = int(img_labels.shape[0]) if img_labels.dim() == 1 else -1
+    if img_labels.dtype != torch.int32 or img_values.dtype != torch.float32 or icap < 0 or tuple(img_values.shape) != (icap, LABEL_VALUES) \
+            or not (img_labels.is_contiguous() and img_values.is_contiguous()):
+        raise ValueError("out must be contiguous (img_labels (n,) int32, img_values (n, %d) float32)" % LABEL_VALUES)
+    if any(not t.is_cuda for t in (geom, dest, offsets, labels, values, scratch, img_labels, img_values)) or (mask is not None and not mask.is_cuda):
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.call("ancsh_depth_label_images", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(mask), cap_px, _lib.ptr(geom), _lib.ptr(offsets),
+              _lib.ptr(scratch), _lib.ptr(labels), _lib.ptr(values), cap, _lib.ptr(dest), _lib.ptr(img_labels), _lib.ptr(img_values), icap)
+    return img_labels, img_values
+
+
+def cut_label_images(labels, values, shapes, first=0):
+    """One batch's flat host image buffers -> its per-frame images (pure numpy): labels (>= n,) int32, values (>= n, 7) float32, shapes =
+    the frames' (h, w) in submission order, frame k's image at element `first` + the pixels of the frames before it (pack_depth_frames'
+    layout).  -> [(labels (h, w) int32, values (h, w, 7) float32)], fresh arrays."""
+    labels, values = np.asarray(labels), np.asarray(values)
+    if labels.dtype != np.int32 or labels.ndim != 1 or values.dtype != np.float32 or values.shape != (labels.shape[0], LABEL_VALUES):
+        raise ValueError("expected labels (n,) int32 and values (n, %d) float32" % LABEL_VALUES)
+    out, a = [], int(first)
+    for k, hw in enumerate(shapes):
+        h, w = (int(v) for v in hw)
+        if h < 1 or w < 1:
+            raise ValueError("frame %d: expected a non-empty (h, w), got %r" % (k, tuple(hw)))
+        if a < 0 or a + h * w > labels.shape[0]:
+            raise ValueError("frame %d: pixels [%d, %d) lie outside the %d-pixel buffers" % (k, a, a + h * w, labels.shape[0]))
+        out.append((labels[a:a + h * w].reshape(h, w).copy(), values[a:a + h * w].reshape(h, w, LABEL_VALUES).copy()))
+        a += h * w
+    return out
+
+
 def unproject_depth_batch(frames, cameras, depth_scale, depth_dtype, device="cuda:0"):
     """Eager wrapper: a batch of depth frames -> (clouds: list of (count, 3) float32 arrays in row-major pixel order -- a frame without a
     valid pixel gives one NaN row --, counts (n,) int32).  One host sync; the streaming pipeline (AncshPipeline.submit_depth) has none."""

@@ -88,7 +88,7 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None):
+                 depth=None, label_images=False):
         f = dict(dtype=torch.float32, device=device)
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
@@ -117,7 +117,8 @@ class _Slot(object):
             # depth (the depth front end; raw_capacity = its pixel capacity): the rows are unprojected on the device, so they have no pinned
             # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam)
             from .depth import CAM_WORDS, GEOM_WORDS
-            words = lead + (B + 1) + B + ((GEOM_WORDS + CAM_WORDS) * B if depth else 0)
+            # label_images: + the per-cloud image start (ancsh_depth_label_images' dest) behind them
+            words = lead + (B + 1) + B + ((GEOM_WORDS + CAM_WORDS) * B if depth else 0) + (B if label_images else 0)
             self.hdr = torch.zeros((words,), dtype=torch.int32, device=device)
             self.h_rows = None if depth else torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
             self.h_hdr = torch.zeros((words,), dtype=torch.int32).pin_memory()
@@ -146,7 +147,7 @@ class _Slot(object):
                                                                    hdr[lead:lead + B + 1], hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
             self.np_base = hdr[2:3] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
             if depth:
-                self._init_depth(B, lead, raw_capacity, depth, device)
+                self._init_depth(B, lead, raw_capacity, depth, device, range_guard, label_images)
                 return
             # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
             rs = np.random.RandomState(0)
@@ -158,7 +159,7 @@ class _Slot(object):
             self.raw_rows.copy_(self.h_rows)
             self.hdr.copy_(self.h_hdr)
 
-    def _init_depth(self, B, lead, capacity, depth, device):
+    def _init_depth(self, B, lead, capacity, depth, device, range_guard=False, label_images=False):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
         counts with their pinned copy, and host / device views of the header's geometry and camera blocks.  Until the first submit:
         B crops of random depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes)."""
@@ -179,6 +180,19 @@ class _Slot(object):
         self.np_cam = hdr[c0:c0 + CAM_WORDS * B].view(np.float32).reshape(B, CAM_WORDS)
         self.geom = self.hdr[g0:c0].view(B, GEOM_WORDS)
         self.cam = self.hdr[c0:c0 + CAM_WORDS * B].view(torch.float32).view(B, CAM_WORDS)
+        # label_images: the per-row labels / values of the captured step (device only: nobody reads rows), the images they are carried back
+        # into with their pinned twins (4 + 28 bytes per pixel of capacity), the f32 graph's own set (range guard), and dest in the header
+        self.rowlab = self.rowlab32 = self.img = self.img32 = self.h_img = self.h_img32 = self.dest = self.np_dest = None
+        if label_images:
+            from .depth import LABEL_VALUES
+            pair = lambda **d: (torch.full((capacity,), -1, dtype=torch.int32, **d),
+                                torch.full((capacity, LABEL_VALUES), float("nan"), dtype=torch.float32, **d))
+            pinned = lambda: tuple(t.pin_memory() for t in pair())
+            self.rowlab, self.img, self.h_img = pair(device=device), pair(device=device), pinned()
+            if range_guard:
+                self.rowlab32, self.img32, self.h_img32 = pair(device=device), pair(device=device), pinned()
+            e0 = c0 + CAM_WORDS * B
+            self.np_dest, self.dest = hdr[e0:e0 + B], self.hdr[e0:e0 + B]
         rs = np.random.RandomState(0)
         per = capacity // B
         w = max(1, int(np.sqrt(per)))
@@ -193,6 +207,8 @@ class _Slot(object):
         for b in range(B):
             self.np_geom[b] = (b * per, h, w, 0, 0)
             self.np_cam[b] = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
+        if label_images:
+            self.np_dest[:] = self.np_geom[:, 0]
         self.np_nf[:] = 1.0
         self.pix.copy_(self.h_pix)
         self.mask.copy_(self.h_mask)
@@ -232,7 +248,7 @@ class AncshPipeline(object):
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, depth_capacity=None, depth_dtype="uint16"):
+                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -271,12 +287,20 @@ class AncshPipeline(object):
             if not self.predicted:
                 raise ValueError("depth_capacity needs joint_source='predicted': a depth pixel carries no joint label")
             if dense:
-                raise ValueError("dense=True with the depth front end is not supported: its product is a label image, which needs a "
-                                 "pixel index per row")
+                raise ValueError("dense=True labels the raw rows of an xyz stream; with the depth front end its product is a label "
+                                 "image: pass label_images=True")
             if not int(batch_size) <= int(depth_capacity) < (1 << 30):
                 raise ValueError("depth_capacity must be in [batch_size, 2^30) pixels")
             raw_capacity = int(depth_capacity)
         self.depth_capacity = None if depth_capacity is None else int(depth_capacity)
+        # label_images (the depth front end only): the captured step ends with two more launches -- ancsh_raw_point_labels on the slot's
+        # unprojected rows, exactly as dense=True calls it, and ancsh_depth_label_images, which carries the rows back to the pixels they
+        # came from -- and retire(label_images=True) / stream_depth_batches(label_images=True) return per frame an (h, w) label image and
+        # an (h, w, 7) value image aligned with the submitted crop.  Costs 32 bytes of pinned memory per pixel of depth_capacity and slot
+        # (twice with the range guard).
+        if label_images and depth_capacity is None:
+            raise ValueError("label_images=True carries the labels back to the pixels of depth frames: it needs depth_capacity")
+        self.label_images = bool(label_images)
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls; predicted: x y z) per batch, padding included
         if raw_capacity is not None:
@@ -336,7 +360,7 @@ class AncshPipeline(object):
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
-                            self.dense, xyz=self.predicted, depth=self.depth_dtype) for _ in range(max(1, slots))]
+                            self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -440,6 +464,13 @@ class AncshPipeline(object):
             from .dataset import raw_point_labels
             _, off, nf = sl.header(self.B)
             out["dense"] = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.dense32 if f32 else sl.dense)
+        if self.label_images:            # the last two launches: the slot's unprojected rows, then back to the pixels they came from
+            from .dataset import raw_point_labels
+            from .depth import depth_label_images
+            _, off, nf = sl.header(self.B)
+            rl = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.rowlab32 if f32 else sl.rowlab)
+            out["label_images"] = depth_label_images(sl.pix, sl.mask, sl.geom, sl.dest, off, rl[0], rl[1],
+                                                     out=sl.img32 if f32 else sl.img, scratch=sl.scratch)
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
         return out
@@ -627,6 +658,9 @@ class AncshPipeline(object):
         sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
         sl.np_cam[:n_valid] = cam
         sl.np_cam[n_valid:] = cam[0]
+        if self.label_images:                      # a valid frame's image lies where its crop does; a padding cloud writes none
+            sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
+            sl.np_dest[n_valid:] = -1
         sl.np_nf[:n_valid] = nf
         sl.np_nf[n_valid:] = nf[0]
         cur = torch.cuda.current_stream(self.device)
@@ -645,6 +679,9 @@ class AncshPipeline(object):
             sl.h_counts.copy_(sl.counts, non_blocking=True)
             if self.articulation:
                 sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
+            if self.label_images:        # the valid frames' pixels only
+                for h, d in zip(sl.h_img, sl.img):
+                    h[:pixels].copy_(d[:pixels], non_blocking=True)
             if self.range_guard:
                 sl.h_flags.copy_(sl.flags, non_blocking=True)
             sl.d2h_done.record(sl.stream)
@@ -652,7 +689,7 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self, flags=False, articulation=False, dense=False):
+    def retire(self, flags=False, articulation=False, dense=False, label_images=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
@@ -661,11 +698,16 @@ class AncshPipeline(object):
         block (flagged clouds: the f32 graph's rows, like their records).  dense=True (a pipeline built with dense=True): + (labels (R,)
         int32, values (R, 7) float32, offsets (n_valid+1,) int64) as the last element: the valid clouds' R raw rows in submission order,
         cloud c's rows [offsets[c], offsets[c+1]) (raw_point_labels; flagged clouds: the f32 graph's rows).  A pipeline built with
-        depth_capacity appends the valid-pixel counts (n_valid,) int32 of the batch's frames as the last element."""
+        depth_capacity appends the valid-pixel counts (n_valid,) int32 of the batch's frames as the last element.  label_images=True (a
+        pipeline built with label_images=True): + a list with one (labels (h, w) int32, values (h, w, 7) float32) pair per valid frame,
+        aligned with the submitted crop, behind the articulation block and in front of the counts: a valid pixel holds its row's label and
+        [W of the label | part NOCS | NAOCS] (as dense), every other pixel -1 / NaN (flagged clouds: the f32 graph's images)."""
         if articulation and not self.articulation:
             raise RuntimeError("retire(articulation=True) needs AncshPipeline(..., articulation=True)")
         if dense and not self.dense:
             raise RuntimeError("retire(dense=True) needs AncshPipeline(..., dense=True)")
+        if label_images and not self.label_images:
+            raise RuntimeError("retire(label_images=True) needs AncshPipeline(..., depth_capacity=<pixels>, label_images=True)")
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
@@ -676,6 +718,12 @@ class AncshPipeline(object):
         off = sl.np_off[:n_valid + 1].astype(np.int64)          # the batch's own offsets: a slot's staging is rewritten only after it retires
         rv = int(off[-1])
         dn = (sl.h_dense[0][:rv].numpy().copy(), sl.h_dense[1][:rv].numpy().copy(), off) if dense else None
+        imgs = None
+        if label_images:                 # the batch's own geometry: a slot's staging is rewritten only after it retires
+            from .depth import cut_label_images
+            shapes = [(int(g[1]), int(g[2])) for g in sl.np_geom[:n_valid]]
+            pixels = sum(h * w for h, w in shapes)
+            imgs = cut_label_images(sl.h_img[0].numpy()[:pixels], sl.h_img[1].numpy()[:pixels], shapes)
         words = sl.h_flags[:n_valid].numpy().copy() if self.range_guard else np.zeros((n_valid,), np.int32)
         hit = np.flatnonzero(words)
         if hit.size:
@@ -687,6 +735,9 @@ class AncshPipeline(object):
                 if self.dense:
                     for h, d in zip(sl.h_dense32, sl.dense32):
                         h[:rv].copy_(d[:rv], non_blocking=True)
+                if label_images:
+                    for h, d in zip(sl.h_img32, sl.img32):
+                        h[:pixels].copy_(d[:pixels], non_blocking=True)
             sl.stream.synchronize()
             record[hit] = sl.h_record32.numpy()[hit]
             if articulation:
@@ -695,10 +746,15 @@ class AncshPipeline(object):
                 for c in hit:
                     a, e = off[c], off[c + 1]
                     dn[0][a:e], dn[1][a:e] = sl.h_dense32[0].numpy()[a:e], sl.h_dense32[1].numpy()[a:e]
+            if label_images:
+                redo = cut_label_images(sl.h_img32[0].numpy()[:pixels], sl.h_img32[1].numpy()[:pixels], shapes)
+                for c in hit:
+                    imgs[c] = redo[c]
             self.f32_reruns += 1
         out = (tag, seed, record, words) if flags else (tag, seed, record)
         out = out + (art,) if articulation else out
         out = out + (dn,) if dense else out
+        out = out + (imgs,) if label_images else out
         return out + (counts,) if counts is not None else out
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
@@ -717,15 +773,17 @@ class AncshPipeline(object):
         while self._inflight:
             yield self.retire(flags, articulation, dense)
 
-    def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False):
+    def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
         last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base; yields what retire() returns, in
-        submission order, the valid-pixel counts last."""
+        submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them)."""
         if articulation and not self.articulation:
             raise RuntimeError("stream_depth_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
+        if label_images and not self.label_images:
+            raise RuntimeError("stream_depth_batches(label_images=True) needs AncshPipeline(..., depth_capacity=<pixels>, label_images=True)")
         for k, item in enumerate(batches):
             if len(self._inflight) == len(self.slots):
-                yield self.retire(flags, articulation)
+                yield self.retire(flags, articulation, label_images=label_images)
             item = tuple(item)
             kw = dict(cameras=cameras, depth_scale=depth_scale)
             if isinstance(item[-1], dict):
@@ -733,4 +791,4 @@ class AncshPipeline(object):
                 item = item[:-1]
             self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
         while self._inflight:
-            yield self.retire(flags, articulation)
+            yield self.retire(flags, articulation, label_images=label_images)

@@ -41,7 +41,9 @@ extern "C" {
 #define ANCSH_ACT_RAW 2   /* y = the raw k-ordered accumulator: no bias, no BN (bias/scale/shift may be NULL) */
 
 /* library / diagnostics */
-int ancsh_abi_version(void);   /* 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
+int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
+                                 *     ancsh_depth_label_images (the depth front end and its label / NOCS images);
+                                 * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
                                  * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
                                  *     ancsh_input_sample_stream_xyz_keyed (the joint association from the network's index head; xyz-only raw rows);
@@ -821,6 +823,32 @@ int ancsh_input_sample_stream_xyz_keyed(int nclouds, int num_points, int nchan, 
 int ancsh_depth_unproject_stream(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
                                  const int *geom, const float *cam, float *rows, long capacity, int *offsets, int *counts, int *scratch,
                                  void *stream);
+
+/* The inverse of the depth front end's compaction: the per-row labels / values of ancsh_raw_point_labels back on the pixel grid of the
+ * crops ancsh_depth_unproject_stream read -- per cloud a label image and a 7-channel value image (the NOCS map), in ONE launch on the
+ * depth entry's grid.  The ABI version is unchanged; callers detect the entry by its symbol.
+ *   nclouds, depth_type, depth, mask, pixel_capacity, geom : exactly what the ancsh_depth_unproject_stream call was given;
+ *   offsets (nclouds + 1), scratch : what that call WROTE (scratch holds the count pass's per-chunk counts: nothing may write it
+ *           between the two calls);
+ *   labels (capacity) int32, values (capacity, 7) float32 : per row, as ancsh_raw_point_labels writes them (nchan = 3);
+ *   dest (nclouds) int32 : cloud b's image starts at element dest[b] of the image buffers; dest[b] < 0 silences the cloud (the padding
+ *           clouds of a short batch alias another cloud's pixels but hold other labels);
+ *   img_labels (image_capacity) int32, img_values (image_capacity, 7) float32 : the images.
+ * For cloud b with crop h x w at `start` and dest[b] >= 0, pixel (i, j), q = dest[b] + i * w + j: the pixel is VALID by the depth entry's
+ * rule; rank = the valid pixels in front of it in row-major order; r = offsets[b] + rank.  Valid and r < capacity: img_labels[q] =
+ * labels[r] and img_values[q][0..6] = values[r][0..6], bit for bit (NaN payloads included).  Otherwise (background, hole, masked out, a
+ * row cut at capacity): img_labels[q] = -1 and seven NaNs of the bit pattern ANCSH_LABEL_NAN_BITS, the one ancsh_raw_point_labels writes
+ * with label -1.  Every pixel of the crop is written (no prefill needed); image elements of no cloud's crop are left untouched.  A cloud
+ * with dest[b] < 0, with a crop the depth entry treats as empty (h < 1, w < 1, outside [0, pixel_capacity)), or with dest[b] + h * w >
+ * image_capacity writes NOTHING.  Images of different clouds must not overlap (clouds may share source pixels).  Deterministic byte for
+ * byte: no atomics, no block waits for another.  Graph-capturable: the grid depends on (pixel_capacity, nclouds) only, every size is read
+ * from device memory; no host sync, no allocation.  nclouds == 0 launches nothing.  Checked before any launch: 0 <= nclouds <= 65535,
+ * depth_type, 0 <= pixel_capacity < 2^30, 0 <= capacity, image_capacity < 2^30, null pointers (mask may be NULL), the two alignments
+ * (depth 16 bytes, mask 8 bytes; the outputs need none beyond their element's). */
+#define ANCSH_LABEL_NAN_BITS 0x7fc00000u
+int ancsh_depth_label_images(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
+                             const int *geom, const int *offsets, const int *scratch, const int *labels, const float *values,
+                             long capacity, const int *dest, int *img_labels, float *img_values, long image_capacity, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -6,6 +6,10 @@ alternated in one process for --rounds rounds:
   b: the xyz stream with the numpy unprojection of each batch inside the timed loop (what a user of a depth camera does today);
   c: the depth stream.
 Leg a runs twice in the first round: a2 / a is the run-to-run spread the ratios are read against.  Prints one JSON line.
+Two more legs on request (--legs acde), for the per-frame label / NOCS images:
+  d: the depth stream with label_images=True (the images come back with the records);
+  e: the same product without that option: the numpy unprojection of each batch, the xyz stream with dense=True, and the numpy scatter
+     of the rows into per-frame (h, w) / (h, w, 7) images, all inside the timed loop.
 
     python tools/depth_stream_bench.py [--rounds 3] [--passes 8] [--slots 20] [--legs abc]
 """
@@ -59,6 +63,15 @@ def host_unproject(frame, A):
     return np.stack([z * (A[0] * col + A[1] * row + A[2]), z * (A[3] * col + A[4] * row + A[5]), z], 1)
 
 
+def host_images(frame, labels, values):
+    """The numpy scatter of one cloud's dense rows back into its frame: what leg e does per frame."""
+    d, m, _ = frame
+    ok = m & (d != 0)
+    il, iv = np.full(d.shape, -1, np.int32), np.full(d.shape + (7,), np.nan, np.float32)
+    il[ok], iv[ok] = labels, values
+    return il, iv
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -86,6 +99,9 @@ def main():
     xyz = AncshPipeline(K, wa, wn, B, N, dev, raw_capacity=B * 3000, **kw).prepare() if set(args.legs) & set("ab") else None
     cap = int(max(sum(f[0].size for f in fb[0]) for fb in fbatches))
     depth = AncshPipeline(K, wa, wn, B, N, dev, depth_capacity=cap, depth_dtype="uint16", **kw).prepare() if "c" in args.legs else None
+    depth_img = AncshPipeline(K, wa, wn, B, N, dev, depth_capacity=cap, depth_dtype="uint16", label_images=True,
+                              **kw).prepare() if "d" in args.legs else None
+    xyz_dense = AncshPipeline(K, wa, wn, B, N, dev, raw_capacity=B * 3000, dense=True, **kw).prepare() if "e" in args.legs else None
     torch.cuda.synchronize()
 
     def drain(gen):
@@ -95,14 +111,37 @@ def main():
         torch.cuda.synchronize()
         return n
 
+    def drain_images(gen):             # leg d: the images arrive with the records
+        n = 0
+        for item in gen:
+            assert len(item[-2]) == item[2].shape[0]
+            n += item[2].shape[0]
+        torch.cuda.synchronize()
+        return n
+
+    def drain_dense(gen):              # leg e: the rows of every cloud scattered into its frame on the host
+        n = 0
+        for item in gen:
+            labels, values, off = item[-1]
+            imgs = [host_images(f, labels[off[c]:off[c + 1]], values[off[c]:off[c + 1]]) for c, f in enumerate(fbatches[item[0]][0])]
+            n += len(imgs)
+        torch.cuda.synchronize()
+        return n
+
     def leg(name, passes):
         t0 = time.perf_counter()
         if name == "a":
             n = drain(xyz.stream_batches(cbatches[k] for _ in range(passes) for k in range(len(cbatches))))
         elif name == "b":
             n = drain(xyz.stream_batches((unproject(k), nf) for _ in range(passes) for k in range(len(fbatches))))
-        else:
+        elif name == "c":
             n = drain(depth.stream_depth_batches((fbatches[k] for _ in range(passes) for k in range(len(fbatches))), None, SCALE))
+        elif name == "d":
+            n = drain_images(depth_img.stream_depth_batches((fbatches[k] for _ in range(passes) for k in range(len(fbatches))), None, SCALE,
+                                                            label_images=True))
+        else:
+            n = drain_dense(xyz_dense.stream_batches(((unproject(k), nf, k) for _ in range(passes) for k in range(len(fbatches))),
+                                                     dense=True))
         return n / (time.perf_counter() - t0)
 
     for name in args.legs:                      # warm-up: every slot replayed with real input
@@ -127,6 +166,10 @@ def main():
         line["c_over_a"] = round(med["c"] / med["a"], 4)
     if "b" in med and "c" in med:
         line["c_over_b"] = round(med["c"] / med["b"], 4)
+    if "d" in med and "c" in med:
+        line["d_over_c"] = round(med["d"] / med["c"], 4)
+    if "d" in med and "e" in med:
+        line["d_over_e"] = round(med["d"] / med["e"], 4)
     if spread is not None:
         line["a_over_a"] = round(spread, 4)
     nb = len(fbatches)
@@ -134,6 +177,10 @@ def main():
         line["h2d_bytes_per_batch_a"] = int(round(12 * valid.sum() / nb + hdr(xyz)))
     if depth is not None:
         line["h2d_bytes_per_batch_c"] = int(round(3 * pixels.sum() / nb + hdr(depth)))
+    if depth_img is not None:
+        line["d2h_image_bytes_per_batch_d"] = int(round(32 * pixels.sum() / nb))
+    if xyz_dense is not None:
+        line["d2h_dense_bytes_per_batch_e"] = int(round(32 * valid.sum() / nb))
     print(json.dumps(line))
 
 
