@@ -14,6 +14,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .stream import check_built_with, only_asked, pack_results, pump, unpack_results
+
 CHILD_ENV = "ANCSH_LOCAL_RANK_CHILD"      # set in the ranks launch_local_ranks() starts: they must not launch again
 
 
@@ -501,15 +503,6 @@ class ShardedPipeline(object):
         self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
 
-    def _local_kw(self, articulation, dense):
-        """retire / stream_batches keywords for the per-rank pipeline: only the blocks asked for (a stand-in need not know the others)."""
-        kw = {}
-        if articulation:
-            kw["articulation"] = True
-        if dense:
-            kw["dense"] = True
-        return kw
-
     def _gather_dense(self, got, sizes, n_valid):
         """The raw rows of one global batch on dst: every rank pads its shard's rows to the largest shard's count (all ranks know every
         shard's rows: they iterate the same batch) and sends [label | the 7 values' bits] int32 rows in ONE gather.  dst -> (labels (R,) int32,
@@ -543,12 +536,9 @@ class ShardedPipeline(object):
         dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
         batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
-        if articulation and not self.articulation:
-            raise RuntimeError("retire(articulation=True) needs ShardedPipeline(..., articulation=True)")
-        if dense and not self.dense:
-            raise RuntimeError("retire(dense=True) needs ShardedPipeline(..., dense=True)")
+        check_built_with(self, "retire", "ShardedPipeline", articulation=articulation, dense=dense)
         if self.world == 1:
-            return self.pipe.retire(flags, **self._local_kw(articulation, dense))
+            return self.pipe.retire(flags, **only_asked(articulation=articulation, dense=dense))
         if not self._stream:
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
@@ -556,14 +546,15 @@ class ShardedPipeline(object):
         width = 38 if self.articulation else 26         # [record (26) | articulation block (12)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
-        got = None
-        if here:
-            got = self.pipe.retire(flags, **self._local_kw(self.articulation, self.dense))
-            rec[:e - s, :, :26] = got[2]
+        got = {}
+        if here:             # the per-rank pipeline's public retire(), with only the keywords it was built for
+            built = dict(articulation=self.articulation, dense=self.dense)
+            got = unpack_results(self.pipe.retire(flags, **only_asked(**built)), flags=flags, **built)
+            rec[:e - s, :, :26] = got["record"]
             if self.articulation:
-                rec[:e - s, :, 26:] = got[-2 if self.dense else -1]
+                rec[:e - s, :, 26:] = got["articulation"]
             if flags:
-                words[:e - s] = got[3]
+                words[:e - s] = got["flags"]
         on_dst = self.rank == self.dst
         if self._stream_bufs is None and on_dst:
             self._stream_bufs = ([torch.empty((self.n_max, self.K, width), dtype=torch.float64) for _ in range(self.world)],
@@ -572,19 +563,17 @@ class ShardedPipeline(object):
         dist.gather(torch.from_numpy(rec), bufs[0], dst=self.dst)
         if flags:
             dist.gather(torch.from_numpy(words), bufs[1], dst=self.dst)
-        dn = self._gather_dense(got[-1] if got is not None else None, sizes, n_valid) if self.dense else None
-        if not on_dst:
-            out = (tag, seed, None, None) if flags else (tag, seed, None)
-            out = out + (None,) if articulation else out
-            return out + (None,) if dense else out
-        cut = [self.shard_of(n_valid, r) for r in range(self.world)]
-        packed = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
-        record = np.ascontiguousarray(packed[:, :, :26])
-        out = (tag, seed, record)
-        if flags:
-            out += (np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0),)
-        out = out + (np.ascontiguousarray(packed[:, :, 26:]),) if articulation else out
-        return out + (dn,) if dense else out
+        dn = self._gather_dense(got.get("dense"), sizes, n_valid) if self.dense else None
+        out = dict(tag=tag, seed=seed, record=None, flags=None, articulation=None, dense=dn)     # what the other ranks return
+        if on_dst:
+            cut = [self.shard_of(n_valid, r) for r in range(self.world)]
+            packed = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+            out["record"] = np.ascontiguousarray(packed[:, :, :26])
+            if flags:
+                out["flags"] = np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
+            if articulation:
+                out["articulation"] = np.ascontiguousarray(packed[:, :, 26:])
+        return pack_results(out, flags=flags, articulation=articulation, dense=dense)
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """Generator over submit / retire of GLOBAL batches (every rank iterates the same batches): batches yields (clouds, norm_factors)
@@ -594,16 +583,10 @@ class ShardedPipeline(object):
         seed, lm_schedule).  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
         (labels, values, offsets) in global cloud order, last (see retire()).  World 1 (or no process group): the local pipeline's
         stream_batches."""
-        if articulation and not self.articulation:
-            raise RuntimeError("stream_batches(articulation=True) needs ShardedPipeline(..., articulation=True)")
-        if dense and not self.dense:
-            raise RuntimeError("stream_batches(dense=True) needs ShardedPipeline(..., dense=True)")
+        check_built_with(self, "stream_batches", "ShardedPipeline", articulation=articulation, dense=dense)
         if self.world == 1:
-            yield from self.pipe.stream_batches(batches, flags, **self._local_kw(articulation, dense))
+            yield from self.pipe.stream_batches(batches, flags, **only_asked(articulation=articulation, dense=dense))
             return
-        for k, item in enumerate(batches):
-            if len(self._stream) == len(self.pipe.slots):
-                yield self.retire(flags, articulation, dense)
-            self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
-        while self._stream:
-            yield self.retire(flags, articulation, dense)
+        yield from pump(batches, self._stream, len(self.pipe.slots),
+                        lambda k, item: self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k),
+                        lambda: self.retire(flags, articulation, dense))

@@ -16,6 +16,8 @@ import torch
 
 from .network import Network
 from .pose import PoseSolver
+from .stream import (Output, check_built_with, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row,
+                     pump, take_dense, take_images)
 
 
 def check_hardware_queues(slots):
@@ -105,64 +107,72 @@ class _Slot(object):
         self.graph32 = None
         self.out32 = None
         if raw_capacity is not None:
-            # streaming: raw rows + a header [seed (int64 bits) | offsets (B+1) int32 | norm factors (B) float32] on the device, their
-            # pinned staging, the pinned record, and the events that say when the staging / the record may be touched again.
+            # streaming: raw rows + a header (stream.header_layout) on the device, their pinned staging, the streamed outputs with their
+            # pinned twins (self.outputs), and the events that say when the staging / the outputs' twins may be touched again.
             # keyed: the header leads with the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) instead of the seed
             # xyz (joint_source="predicted"): rows of x y z only -- no joint-class column, a quarter fewer bytes per batch to the device
             from .dataset import RAW_NCHAN
             self.keyed = bool(keyed)
             self.nchan = 3 if xyz else RAW_NCHAN
-            lead = 4 if self.keyed else 2
-            self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
             # depth (the depth front end; raw_capacity = its pixel capacity): the rows are unprojected on the device, so they have no pinned
-            # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam)
-            from .depth import CAM_WORDS, GEOM_WORDS
-            # label_images: + the per-cloud image start (ancsh_depth_label_images' dest) behind them
-            words = lead + (B + 1) + B + ((GEOM_WORDS + CAM_WORDS) * B if depth else 0) + (B if label_images else 0)
-            self.hdr = torch.zeros((words,), dtype=torch.int32, device=device)
+            # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam) and, with
+            # label_images, the per-cloud image start (ancsh_depth_label_images' dest) behind them
+            self.layout = lay = header_layout(B, self.keyed, bool(depth), label_images)
+            self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
+            self.hdr = torch.zeros((lay.words,), dtype=torch.int32, device=device)
             self.h_rows = None if depth else torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
-            self.h_hdr = torch.zeros((words,), dtype=torch.int32).pin_memory()
-            self.h_record = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
+            self.h_hdr = torch.zeros((lay.words,), dtype=torch.int32).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
-            if range_guard:
-                self.h_flags = torch.zeros((B,), dtype=torch.int32).pin_memory()
-                self.h_record32 = torch.zeros((B, K, 26), dtype=torch.float64).pin_memory()
-            # articulation: the pinned (B, K, 12) block, copied right behind the record (and the f32 graph's, for flagged clouds)
-            self.h_art = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation else None
-            self.h_art32 = torch.zeros((B, K, 12), dtype=torch.float64).pin_memory() if articulation and range_guard else None
-            # dense: the per-raw-row labels / values the captured step writes (slot-owned, outside the graph's pool, so a later replay
-            # never hands their memory to another tensor), the f32 graph's own pair (range guard), and their pinned copies
-            self.dense = self.dense32 = self.h_dense = self.h_dense32 = None
-            if dense:
-                from .dataset import DENSE_VALUES
-                pair = lambda **d: (torch.full((raw_capacity,), -1, dtype=torch.int32, **d),
-                                    torch.full((raw_capacity, DENSE_VALUES), float("nan"), dtype=torch.float32, **d))
-                pinned = lambda: tuple(t.pin_memory() for t in pair())
-                self.dense, self.h_dense = pair(device=device), pinned()
-                if range_guard:
-                    self.dense32, self.h_dense32 = pair(device=device), pinned()
+            # dense / label_images: the per-raw-row (dense) or per-row and per-pixel (rowlab, img) labels / values the captured step writes
+            # (slot-owned, outside the graph's pool, so a later replay never hands their memory to another tensor) and the f32 graph's own
+            # (range guard); rowlab is device only: nobody reads rows.  Their pinned twins cost 4 + 28 bytes per row / pixel of capacity.
+            for name, built in (("dense", dense), ("rowlab", label_images), ("img", label_images)):
+                setattr(self, name, label_buffers(raw_capacity, device) if built else None)
+                setattr(self, name + "32", label_buffers(raw_capacity, device) if built and range_guard else None)
             hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
-            self.np_rows, self.np_seed, self.np_off, self.np_nf = (None if depth else self.h_rows.numpy(), hdr[:2].view(np.int64),
-                                                                   hdr[lead:lead + B + 1], hdr[lead + B + 1:lead + 2 * B + 1].view(np.float32))
-            self.np_base = hdr[2:3] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
+            self.np_rows = None if depth else self.h_rows.numpy()
+            self.np_seed, self.np_off, self.np_nf = hdr[lay.seed].view(np.int64), hdr[lay.off], hdr[lay.nf].view(np.float32)
+            self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
             if depth:
-                self._init_depth(B, lead, raw_capacity, depth, device, range_guard, label_images)
-                return
-            # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
-            rs = np.random.RandomState(0)
-            self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
-            if not xyz:
-                self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
-            self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
-            self.np_nf[:] = 1.0
-            self.raw_rows.copy_(self.h_rows)
-            self.hdr.copy_(self.h_hdr)
+                self._init_depth(B, raw_capacity, depth, device)
+            else:
+                # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
+                rs = np.random.RandomState(0)
+                self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
+                if not xyz:
+                    self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
+                self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
+                self.np_nf[:] = 1.0
+                self.raw_rows.copy_(self.h_rows)
+                self.hdr.copy_(self.h_hdr)
+            # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
+            # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words and the depth
+            # front end's valid-pixel counts are not refit.
+            pinned = lambda dtype, *shape: lambda: (torch.zeros(shape, dtype=dtype).pin_memory(),)
+            labels = lambda: label_buffers(raw_capacity)
+            outs = [Output("record", lambda sl, f32: (sl.pick("out", f32)["record"],), pinned(torch.float64, B, K, 26), refit=range_guard)]
+            if depth:
+                outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
+            if articulation:
+                outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, 12),
+                                   refit=range_guard))
+            if dense:
+                outs.append(Output("dense", lambda sl, f32: sl.pick("dense", f32), labels, refit=range_guard, extent=per_raw_row,
+                                   take=take_dense, patch=patch_dense))
+            if label_images:
+                outs.append(Output("label_images", lambda sl, f32: sl.pick("img", f32), labels, refit=range_guard, extent=per_pixel,
+                                   take=take_images))
+            if range_guard:
+                outs.append(Output("flags", lambda sl, f32: (sl.flags,), pinned(torch.int32, B)))
+            self.outputs = {o.name: o for o in outs}
+            img = self.outputs.get("label_images")
+            self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
 
-    def _init_depth(self, B, lead, capacity, depth, device, range_guard=False, label_images=False):
+    def _init_depth(self, B, capacity, depth, device):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
-        counts with their pinned copy, and host / device views of the header's geometry and camera blocks.  Until the first submit:
-        B crops of random depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes)."""
+        counts, and host / device views of the header's geometry, camera and dest blocks.  Until the first submit: B crops of random
+        depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes)."""
         from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS
         npt, tt, _ = DEPTH_DTYPES[depth]
         self.pix = torch.zeros((capacity,), dtype=tt, device=device)
@@ -171,28 +181,13 @@ class _Slot(object):
         self.h_mask = torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
         self.scratch = torch.zeros((B * MAX_CHUNKS,), dtype=torch.int32, device=device)
         self.counts = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.h_counts = torch.zeros((B,), dtype=torch.int32).pin_memory()
-        g0 = lead + 2 * B + 1
-        c0 = g0 + GEOM_WORDS * B
-        hdr = self.h_hdr.numpy()
+        lay, hdr = self.layout, self.h_hdr.numpy()
         self.np_pix, self.np_mask = self.h_pix.numpy().view(npt), self.h_mask.numpy()
-        self.np_geom = hdr[g0:c0].reshape(B, GEOM_WORDS)
-        self.np_cam = hdr[c0:c0 + CAM_WORDS * B].view(np.float32).reshape(B, CAM_WORDS)
-        self.geom = self.hdr[g0:c0].view(B, GEOM_WORDS)
-        self.cam = self.hdr[c0:c0 + CAM_WORDS * B].view(torch.float32).view(B, CAM_WORDS)
-        # label_images: the per-row labels / values of the captured step (device only: nobody reads rows), the images they are carried back
-        # into with their pinned twins (4 + 28 bytes per pixel of capacity), the f32 graph's own set (range guard), and dest in the header
-        self.rowlab = self.rowlab32 = self.img = self.img32 = self.h_img = self.h_img32 = self.dest = self.np_dest = None
-        if label_images:
-            from .depth import LABEL_VALUES
-            pair = lambda **d: (torch.full((capacity,), -1, dtype=torch.int32, **d),
-                                torch.full((capacity, LABEL_VALUES), float("nan"), dtype=torch.float32, **d))
-            pinned = lambda: tuple(t.pin_memory() for t in pair())
-            self.rowlab, self.img, self.h_img = pair(device=device), pair(device=device), pinned()
-            if range_guard:
-                self.rowlab32, self.img32, self.h_img32 = pair(device=device), pair(device=device), pinned()
-            e0 = c0 + CAM_WORDS * B
-            self.np_dest, self.dest = hdr[e0:e0 + B], self.hdr[e0:e0 + B]
+        self.np_geom = hdr[lay.geom].reshape(B, GEOM_WORDS)
+        self.np_cam = hdr[lay.cam].view(np.float32).reshape(B, CAM_WORDS)
+        self.geom = self.hdr[lay.geom].view(B, GEOM_WORDS)
+        self.cam = self.hdr[lay.cam].view(torch.float32).view(B, CAM_WORDS)
+        self.np_dest, self.dest = (hdr[lay.dest], self.hdr[lay.dest]) if lay.dest is not None else (None, None)
         rs = np.random.RandomState(0)
         per = capacity // B
         w = max(1, int(np.sqrt(per)))
@@ -207,19 +202,22 @@ class _Slot(object):
         for b in range(B):
             self.np_geom[b] = (b * per, h, w, 0, 0)
             self.np_cam[b] = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
-        if label_images:
+        if lay.dest is not None:
             self.np_dest[:] = self.np_geom[:, 0]
         self.np_nf[:] = 1.0
         self.pix.copy_(self.h_pix)
         self.mask.copy_(self.h_mask)
         self.hdr.copy_(self.h_hdr)
 
+    def pick(self, name, f32=False):
+        """Attribute `name` of the step (out, dense, rowlab, img), or (f32=True) its twin of the range guard's f32 graph."""
+        return getattr(self, name + "32" if f32 else name)
+
     def header(self, B):
         """(seed (1,) int64 -- keyed: the key block (4,) int32 --, offsets (B+1,) int32, norm factors (B,) float32) views of the device
         header."""
-        if self.keyed:
-            return self.hdr[:4], self.hdr[4:B + 5], self.hdr[B + 5:2 * B + 5].view(torch.float32)
-        return self.hdr[:2].view(torch.int64), self.hdr[2:B + 3], self.hdr[B + 3:2 * B + 3].view(torch.float32)
+        lay, key = self.layout, self.hdr[self.layout.key]
+        return key if self.keyed else key.view(torch.int64), self.hdr[lay.off], self.hdr[lay.nf].view(torch.float32)
 
 
 class AncshPipeline(object):
@@ -460,17 +458,17 @@ class AncshPipeline(object):
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
             out["articulation"] = articulation_batch(a, n, sol["record"])
-        if self.dense:                   # the last launch: every raw row of the slot's batch, into the slot's own (capacity, .) buffers
+        if self.dense or self.label_images:      # never both: a depth pipeline refuses dense=True
+            # the last launch: every raw row of the slot's batch (label_images: its unprojected rows), into the slot's own (capacity, .) buffers
             from .dataset import raw_point_labels
             _, off, nf = sl.header(self.B)
-            out["dense"] = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.dense32 if f32 else sl.dense)
-        if self.label_images:            # the last two launches: the slot's unprojected rows, then back to the pixels they came from
-            from .dataset import raw_point_labels
-            from .depth import depth_label_images
-            _, off, nf = sl.header(self.B)
-            rl = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.rowlab32 if f32 else sl.rowlab)
-            out["label_images"] = depth_label_images(sl.pix, sl.mask, sl.geom, sl.dest, off, rl[0], rl[1],
-                                                     out=sl.img32 if f32 else sl.img, scratch=sl.scratch)
+            rl = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.pick("dense" if self.dense else "rowlab", f32))
+            if self.dense:
+                out["dense"] = rl
+            else:                        # one more launch: the rows back to the pixels they came from
+                from .depth import depth_label_images
+                out["label_images"] = depth_label_images(sl.pix, sl.mask, sl.geom, sl.dest, off, rl[0], rl[1], out=sl.pick("img", f32),
+                                                         scratch=sl.scratch)
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
         return out
@@ -502,12 +500,23 @@ class AncshPipeline(object):
             for _ in range(int(os.environ.get("ANCSH_PREPARE_REPLAYS", "2"))):
                 for sl in self.slots:
                     with torch.cuda.stream(sl.stream):
-                        if sl.graph32 is not None:
-                            sl.graph32.replay()
-                        sl.graph.replay()
+                        if self.range_guard:
+                            self._replay(sl, f32=True)
+                        self._replay(sl)
             self.synchronize()
         self._prepared = True
         return self
+
+    def _replay(self, sl, f32=False):
+        """The step (f32=True: the range guard's f32 step) on slot sl, enqueued on the current stream: a replay of its captured graph,
+        or without one the launches themselves."""
+        graph = sl.graph32 if f32 else sl.graph
+        if graph is not None:
+            graph.replay()
+        elif f32:
+            sl.out32 = self._run(sl, f32=True)
+        else:
+            sl.out = self._run(sl)
 
     def next_slot(self):
         """The slot the next step() will use: its outputs still hold the batch issued len(slots) steps ago (a consumer that must
@@ -528,10 +537,7 @@ class AncshPipeline(object):
         if cur != sl.stream and not cur.query():     # an idle caller stream (the throughput loop) costs one query, no event and no barrier packet
             sl.stream.wait_stream(cur)
         with torch.cuda.stream(sl.stream):
-            if sl.graph is not None:
-                sl.graph.replay()
-            else:
-                sl.out = self._run(sl)
+            self._replay(sl)
         return sl, sl.out
 
     def rerun_f32(self, slot):
@@ -542,10 +548,7 @@ class AncshPipeline(object):
             raise RuntimeError("rerun_f32() needs AncshPipeline(..., arithmetic='f16x2', range_guard=True)")
         sl = self.slots[slot] if isinstance(slot, int) else slot
         with torch.cuda.stream(sl.stream):
-            if sl.graph32 is not None:
-                sl.graph32.replay()
-            else:
-                sl.out32 = self._run(sl, f32=True)
+            self._replay(sl, f32=True)
         return sl.out32
 
     def synchronize(self):
@@ -567,58 +570,23 @@ class AncshPipeline(object):
             raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
         if self.depth_dtype is not None:
             raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
-        from .dataset import check_raw_clouds, check_stream_key, seed_bits
-        if self.keyed:
-            cloud_base = check_stream_key(cloud_base, self.B, self.K)
-        elif cloud_base != 0:
-            raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
-        clouds, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
-        n_valid = len(clouds)
-        padded = clouds + [clouds[0]] * (self.B - n_valid)
-        rows = sum(c.shape[0] for c in padded)
-        if rows > self.raw_capacity:
-            raise ValueError("the batch needs %d raw rows (short batches are padded with their first cloud), raw_capacity is %d"
-                             % (rows, self.raw_capacity))
-        if len(self._inflight) == len(self.slots):
-            raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
-        if not self._prepared:
-            self.prepare()
-        seed = self.seed + 2 * self._submitted if seed is None else int(seed)
-        sl = self.slots[self._next]
-        sl.h2d_done.synchronize()                  # the previous batch's copies out of the pinned staging have completed
-        sl.np_seed[0] = seed_bits(seed)
-        if self.keyed:
-            sl.np_base[0] = cloud_base
-        np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
-        sl.np_off[0] = 0
-        np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
-        sl.np_nf[:n_valid] = nf
-        sl.np_nf[n_valid:] = nf[0]
-        cur = torch.cuda.current_stream(self.device)
-        if cur != sl.stream and not cur.query():
-            sl.stream.wait_stream(cur)
-        with torch.cuda.stream(sl.stream):
-            sl.raw_rows[:rows].copy_(sl.h_rows[:rows], non_blocking=True)
-            sl.hdr.copy_(sl.h_hdr, non_blocking=True)
-            sl.h2d_done.record(sl.stream)
-            if sl.graph is not None:
-                sl.graph.replay()
-            else:
-                sl.out = self._run(sl)
-            # right behind the replay on the same stream: the next replay's pool reuses the record's block (see step())
-            sl.h_record.copy_(sl.out["record"], non_blocking=True)
-            if self.articulation:
-                sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
-            if self.dense:               # the valid clouds' raw rows only (padding clouds follow them)
-                rv = int(sl.np_off[n_valid])
-                for h, d in zip(sl.h_dense, sl.dense):
-                    h[:rv].copy_(d[:rv], non_blocking=True)
-            if self.range_guard:
-                sl.h_flags.copy_(sl.flags, non_blocking=True)
-            sl.d2h_done.record(sl.stream)
-        self._next = (self._next + 1) % len(self.slots)
-        self._submitted += 1
-        self._inflight.append((sl, tag, seed, n_valid))
+
+        def front():
+            from .dataset import check_raw_clouds
+            valid, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
+            padded = valid + [valid[0]] * (self.B - len(valid))
+            rows = sum(c.shape[0] for c in padded)
+            if rows > self.raw_capacity:
+                raise ValueError("the batch needs %d raw rows (short batches are padded with their first cloud), raw_capacity is %d"
+                                 % (rows, self.raw_capacity))
+
+            def stage(sl):
+                np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
+                sl.np_off[0] = 0
+                np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
+                return [(sl.raw_rows[:rows], sl.h_rows[:rows])]
+            return len(valid), nf, stage
+        self._enqueue(front, seed, tag, cloud_base)
 
     def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0):
         """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
@@ -631,19 +599,41 @@ class AncshPipeline(object):
         raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.  Either way the pipeline stays usable."""
         if self.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
+
+        def front():
+            from .depth import check_depth_frames, pack_depth_frames
+            depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
+            n_valid = len(depths)
+            pixels = sum(d.size for d in depths)
+            padded = pixels + (self.B - n_valid) * depths[0].size
+            if padded > self.depth_capacity:
+                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
+                                 % (padded, self.depth_capacity))
+
+            def stage(sl):
+                pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
+                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
+                sl.np_cam[:n_valid] = cam
+                sl.np_cam[n_valid:] = cam[0]
+                if self.label_images:                      # a valid frame's image lies where its crop does; a padding cloud writes none
+                    sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
+                    sl.np_dest[n_valid:] = -1
+                return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
+            return n_valid, nf, stage
+        self._enqueue(front, seed, tag, cloud_base)
+
+    def _enqueue(self, front, seed, tag, cloud_base):
+        """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
+        (valid clouds, their norm factors, stage); stage(sl) fills the slot's pinned staging and returns its (device, pinned) copies.
+        Checks in order: the key, front()'s, the in-flight window (RuntimeError); only then prepare().  On the slot's stream: the H2D
+        copies with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
+        next replay's pool reuses its block, see step()), d2h_done."""
         from .dataset import check_stream_key, seed_bits
-        from .depth import check_depth_frames, pack_depth_frames
         if self.keyed:
             cloud_base = check_stream_key(cloud_base, self.B, self.K)
         elif cloud_base != 0:
             raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
-        depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
-        n_valid = len(depths)
-        pixels = sum(d.size for d in depths)
-        padded = pixels + (self.B - n_valid) * depths[0].size
-        if padded > self.depth_capacity:
-            raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
-                             % (padded, self.depth_capacity))
+        n_valid, nf, stage = front()
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:
@@ -654,36 +644,19 @@ class AncshPipeline(object):
         sl.np_seed[0] = seed_bits(seed)
         if self.keyed:
             sl.np_base[0] = cloud_base
-        pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
-        sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
-        sl.np_cam[:n_valid] = cam
-        sl.np_cam[n_valid:] = cam[0]
-        if self.label_images:                      # a valid frame's image lies where its crop does; a padding cloud writes none
-            sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
-            sl.np_dest[n_valid:] = -1
+        copies = stage(sl)
         sl.np_nf[:n_valid] = nf
         sl.np_nf[n_valid:] = nf[0]
         cur = torch.cuda.current_stream(self.device)
         if cur != sl.stream and not cur.query():
             sl.stream.wait_stream(cur)
         with torch.cuda.stream(sl.stream):
-            sl.pix[:pixels].copy_(sl.h_pix[:pixels], non_blocking=True)
-            sl.mask[:pixels].copy_(sl.h_mask[:pixels], non_blocking=True)
-            sl.hdr.copy_(sl.h_hdr, non_blocking=True)
+            for dev, host in copies + [(sl.hdr, sl.h_hdr)]:
+                dev.copy_(host, non_blocking=True)
             sl.h2d_done.record(sl.stream)
-            if sl.graph is not None:
-                sl.graph.replay()
-            else:
-                sl.out = self._run(sl)
-            sl.h_record.copy_(sl.out["record"], non_blocking=True)      # right behind the replay (see submit())
-            sl.h_counts.copy_(sl.counts, non_blocking=True)
-            if self.articulation:
-                sl.h_art.copy_(sl.out["articulation"], non_blocking=True)
-            if self.label_images:        # the valid frames' pixels only
-                for h, d in zip(sl.h_img, sl.img):
-                    h[:pixels].copy_(d[:pixels], non_blocking=True)
-            if self.range_guard:
-                sl.h_flags.copy_(sl.flags, non_blocking=True)
+            self._replay(sl)
+            for o in sl.outputs.values():
+                o.copy_out(sl, n_valid)
             sl.d2h_done.record(sl.stream)
         self._next = (self._next + 1) % len(self.slots)
         self._submitted += 1
@@ -701,94 +674,52 @@ class AncshPipeline(object):
         depth_capacity appends the valid-pixel counts (n_valid,) int32 of the batch's frames as the last element.  label_images=True (a
         pipeline built with label_images=True): + a list with one (labels (h, w) int32, values (h, w, 7) float32) pair per valid frame,
         aligned with the submitted crop, behind the articulation block and in front of the counts: a valid pixel holds its row's label and
-        [W of the label | part NOCS | NAOCS] (as dense), every other pixel -1 / NaN (flagged clouds: the f32 graph's images)."""
-        if articulation and not self.articulation:
-            raise RuntimeError("retire(articulation=True) needs AncshPipeline(..., articulation=True)")
-        if dense and not self.dense:
-            raise RuntimeError("retire(dense=True) needs AncshPipeline(..., dense=True)")
-        if label_images and not self.label_images:
-            raise RuntimeError("retire(label_images=True) needs AncshPipeline(..., depth_capacity=<pixels>, label_images=True)")
+        [W of the label | part NOCS | NAOCS] (as dense), every other pixel -1 / NaN (flagged clouds: the f32 graph's images).
+        The tuple's order is stream.RESULT_ORDER (stream.unpack_results reads it by name)."""
+        check_built_with(self, "retire", "AncshPipeline", articulation=articulation, dense=dense, label_images=label_images)
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
-        record = sl.h_record[:n_valid].numpy().copy()
-        art = sl.h_art[:n_valid].numpy().copy() if articulation else None
-        counts = sl.h_counts[:n_valid].numpy().copy() if self.depth_dtype is not None else None
-        off = sl.np_off[:n_valid + 1].astype(np.int64)          # the batch's own offsets: a slot's staging is rewritten only after it retires
-        rv = int(off[-1])
-        dn = (sl.h_dense[0][:rv].numpy().copy(), sl.h_dense[1][:rv].numpy().copy(), off) if dense else None
-        imgs = None
-        if label_images:                 # the batch's own geometry: a slot's staging is rewritten only after it retires
-            from .depth import cut_label_images
-            shapes = [(int(g[1]), int(g[2])) for g in sl.np_geom[:n_valid]]
-            pixels = sum(h * w for h, w in shapes)
-            imgs = cut_label_images(sl.h_img[0].numpy()[:pixels], sl.h_img[1].numpy()[:pixels], shapes)
-        words = sl.h_flags[:n_valid].numpy().copy() if self.range_guard else np.zeros((n_valid,), np.int32)
-        hit = np.flatnonzero(words)
+        asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, counts=self.depth_dtype is not None)
+        # the flag words decide the refit whether or not the caller asked for them
+        want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked[o.name]]
+        got = {o.name: o.value(sl, n_valid) for o in want}
+        got.setdefault("flags", np.zeros((n_valid,), np.int32))
+        hit = np.flatnonzero(got["flags"])
         if hit.size:
+            refit = [o for o in want if o.host32 is not None]
             self.rerun_f32(sl)
             with torch.cuda.stream(sl.stream):
-                sl.h_record32.copy_(sl.out32["record"], non_blocking=True)
-                if self.articulation:
-                    sl.h_art32.copy_(sl.out32["articulation"], non_blocking=True)
-                if self.dense:
-                    for h, d in zip(sl.h_dense32, sl.dense32):
-                        h[:rv].copy_(d[:rv], non_blocking=True)
-                if label_images:
-                    for h, d in zip(sl.h_img32, sl.img32):
-                        h[:pixels].copy_(d[:pixels], non_blocking=True)
+                for o in refit:
+                    o.copy_out(sl, n_valid, f32=True)
             sl.stream.synchronize()
-            record[hit] = sl.h_record32.numpy()[hit]
-            if articulation:
-                art[hit] = sl.h_art32.numpy()[hit]
-            if dense:
-                for c in hit:
-                    a, e = off[c], off[c + 1]
-                    dn[0][a:e], dn[1][a:e] = sl.h_dense32[0].numpy()[a:e], sl.h_dense32[1].numpy()[a:e]
-            if label_images:
-                redo = cut_label_images(sl.h_img32[0].numpy()[:pixels], sl.h_img32[1].numpy()[:pixels], shapes)
-                for c in hit:
-                    imgs[c] = redo[c]
+            for o in refit:
+                o.patch(got[o.name], o.value(sl, n_valid, f32=True), hit)
             self.f32_reruns += 1
-        out = (tag, seed, record, words) if flags else (tag, seed, record)
-        out = out + (art,) if articulation else out
-        out = out + (dn,) if dense else out
-        out = out + (imgs,) if label_images else out
-        return out + (counts,) if counts is not None else out
+        return pack_results(dict(got, tag=tag, seed=seed), **asked)
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
         batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
         flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
         last -- see retire())."""
-        if articulation and not self.articulation:
-            raise RuntimeError("stream_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
-        if dense and not self.dense:
-            raise RuntimeError("stream_batches(dense=True) needs AncshPipeline(..., dense=True)")
-        for k, item in enumerate(batches):
-            if len(self._inflight) == len(self.slots):
-                yield self.retire(flags, articulation, dense)
-            self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k)
-        while self._inflight:
-            yield self.retire(flags, articulation, dense)
+        check_built_with(self, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
+        yield from pump(batches, self._inflight, len(self.slots),
+                        lambda k, item: self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k),
+                        lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
         last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base; yields what retire() returns, in
         submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them)."""
-        if articulation and not self.articulation:
-            raise RuntimeError("stream_depth_batches(articulation=True) needs AncshPipeline(..., articulation=True)")
-        if label_images and not self.label_images:
-            raise RuntimeError("stream_depth_batches(label_images=True) needs AncshPipeline(..., depth_capacity=<pixels>, label_images=True)")
-        for k, item in enumerate(batches):
-            if len(self._inflight) == len(self.slots):
-                yield self.retire(flags, articulation, label_images=label_images)
+        check_built_with(self, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
+
+        def submit(k, item):
             item = tuple(item)
             kw = dict(cameras=cameras, depth_scale=depth_scale)
             if isinstance(item[-1], dict):
                 kw.update(item[-1])
                 item = item[:-1]
             self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
-        while self._inflight:
-            yield self.retire(flags, articulation, label_images=label_images)
+        yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, label_images=label_images))
