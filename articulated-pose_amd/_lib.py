@@ -123,6 +123,9 @@ SIGNATURES = {
     # its inverse for per-row labels (no ABI bump either): nclouds, depth_type, depth, mask, pixel_capacity, geom, offsets, scratch, labels,
     # values, capacity, dest, img_labels, img_values, image_capacity, stream
     "ancsh_depth_label_images": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 5 + [_c_long, _vp, _vp, _vp, _c_long, _vp],
+    # the joint states behind the articulation block (no ABI bump, detected by its symbol): b, n, K, P, ldp, npcs_nocs, npcs_mask, record,
+    # art, wide, stream
+    "ancsh_joint_state_rec": [_c_int] * 3 + [_vp, _c_int] + [_vp] * 5 + [_vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

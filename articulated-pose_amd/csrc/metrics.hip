@@ -168,9 +168,7 @@ __global__ __launch_bounds__(256) void part_extents_kernel(int n, int K, int C, 
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t p0 = (size_t)b * n;
     const double *ps = pose0 + (size_t)b * 12;                  // R0 row-major (9) | t0 (3)
-    const double r00 = (double)(float)ps[0], r10 = (double)(float)ps[3], r20 = (double)(float)ps[6];
-    const double t0 = (double)(float)ps[9], t1 = (double)(float)ps[10], t2 = (double)(float)ps[11];
-    const double m30 = (double)(float)(-(t0 * r00 + t1 * r10 + t2 * r20));      // the inverse's translation entry, float32 like the pinv's
+    ANCSH_POSE0_FIRST_COLUMN(ps, ps + 9, r00, r10, r20, t0, t1, t2, m30)
     ANCSH_PART_EXTENTS_PASS(true, n, K, C, p0, nocs, mask, P, ldp, r00, r10, r20, m30, smax, smin, scnt, lane, wave)
     __syncthreads();
     if ((int)threadIdx.x < K) {

@@ -1,5 +1,5 @@
-// part_stats.h -- per-part and per-joint statistics of one cloud, shared by the evaluation kernels of metrics.hip:
-// joint_params_kernel, part_extents_kernel and articulation_kernel (workgroups of 256 threads, four waves of 64).
+// part_stats.h -- per-part and per-joint statistics of one cloud, shared by the evaluation kernels of metrics.hip (joint_params_kernel,
+// part_extents_kernel, articulation_kernel) and by joint_state_kernel of joint_state.hip (workgroups of 256 threads, four waves of 64).
 // The passes are STATEMENT MACROS, not inline functions: a force-inlined device function is simplified on its own before it is inlined,
 // and that alone changes the code the compiler makes of the kernels that existed before this header (measured: part_extents_kernel
 // 3830 -> 3642 instructions with its unchanged body behind one inline call).  Expanded in place, the macros give those kernels the
@@ -121,6 +121,14 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
     const float *med##_v = jp_vals + (c) * npow2;                                                                                     \
     float med = NAN;                                                                                                                  \
     if (cnt > 0) med = (cnt & 1) ? med##_v[cnt / 2] : (med##_v[cnt / 2 - 1] + med##_v[cnt / 2]) * 0.5f;
+
+// ---- part 0's pose as the boundary pass reads it (eval_pose_err.py:253-268): R = 9 doubles row-major, t = 3 doubles, rounded to float32
+// like compose_rt (:25-30); declares r00 r10 r20 = the first column of R, t0 t1 t2 = the rounded translation and m30 = the inverse's
+// translation entry, float32 like the pinv's
+#define ANCSH_POSE0_FIRST_COLUMN(R, t, r00, r10, r20, t0, t1, t2, m30)                                                                \
+    const double r00 = (double)(float)(R)[0], r10 = (double)(float)(R)[3], r20 = (double)(float)(R)[6];                               \
+    const double t0 = (double)(float)(t)[0], t1 = (double)(float)(t)[1], t2 = (double)(float)(t)[2];                                  \
+    const double m30 = (double)(float)(-(t0 * r00 + t1 * r10 + t2 * r20));
 
 // ---- one pass over a cloud: every part's amodal-box extent max |nocs_j - 0.5| per channel (compute_miou.py:196-200), its point count
 // and, when DYNAM (a literal true / false), its boundary: the min over the part's points of the x coordinate taken back through part 0's

@@ -315,11 +315,13 @@ class ShardedPipeline(object):
     pred) and load_inputs(P, None, pred) need no labels, and the raw stream takes (n_raw, 3) xyz clouds (or (n_raw, 4), 4th column
     ignored) through the keyed xyz sampler.
     joint_types (None | "revolute" | "prismatic" | K - 1 of them): passed to every rank's pipeline (AncshPipeline(joint_types=...)); the
-    kind array repeats per cloud, so a shard's slice of it is the shard's own array and sharded streams stay byte-equal to one GPU's."""
+    kind array repeats per cloud, so a shard's slice of it is the shard's own array and sharded streams stay byte-equal to one GPU's.
+    joint_states=True (with articulation=True): the blocks are the (n_valid, K, 20) ones (AncshPipeline(joint_states=True)), gathered with
+    the records in the same single gather, 26 + 20 doubles a row."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, **pipeline_kw):
+                 joint_types=None, joint_states=False, **pipeline_kw):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
@@ -340,6 +342,13 @@ class ShardedPipeline(object):
         self.articulation = bool(articulation)
         if self.articulation:
             pipeline_kw.update(articulation=True)
+        # joint_states (with articulation): every rank's block is the (n, K, 20) one (AncshPipeline(joint_states=True)) and the gathered row
+        # grows to 26 + 20 doubles: still one gather per batch
+        from .pose.joint_params import check_joint_states
+        self.joint_states = check_joint_states(joint_states, self.articulation)
+        if self.joint_states:
+            pipeline_kw.update(joint_states=True)
+        self.art_width = 20 if self.joint_states else 12
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense = bool(dense)
@@ -532,7 +541,8 @@ class ShardedPipeline(object):
         words (n_valid,) int32 on dst (None elsewhere).  The gather is one fixed-size (n_max, K, 26) float64 dist.gather over the
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
         articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
-        the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows.
+        the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows (joint_states=True: the (n_valid, K, 20)
+        block, 46 a row).
         dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
         batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
@@ -543,7 +553,7 @@ class ShardedPipeline(object):
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        width = 38 if self.articulation else 26         # [record (26) | articulation block (12)]: one gather either way
+        width = 26 + self.art_width if self.articulation else 26      # [record (26) | articulation block (12 or 20)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
         got = {}

@@ -90,8 +90,10 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False):
+                 depth=None, label_images=False, joint_states=False):
         f = dict(dtype=torch.float32, device=device)
+        # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
+        self.art_width = 20 if joint_states else 12
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
         self.pred_nocs = torch.zeros((B, N, 3 * K), **f)
@@ -155,7 +157,7 @@ class _Slot(object):
             if depth:
                 outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
             if articulation:
-                outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, 12),
+                outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, self.art_width),
                                    refit=range_guard))
             if dense:
                 outs.append(Output("dense", lambda sl, f32: sl.pick("dense", f32), labels, refit=range_guard, extent=per_raw_row,
@@ -246,7 +248,7 @@ class AncshPipeline(object):
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False):
+                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -272,6 +274,14 @@ class AncshPipeline(object):
             if not 1 <= int(num_points) <= ARTICULATION_MAX_N:
                 raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
                                  % (ARTICULATION_MAX_N, num_points))
+        # joint_states (with articulation=True): one more launch behind that one (ancsh_joint_state_rec) widens the block to (B, K, 20) --
+        # its 12 columns bit for bit, then per child part the angle of R_0^T R_j (unsigned, and signed about the joint axis), t_j - t_0, its
+        # slide along the axis, the boundary slide dynam_j - canon_j and the part's point count (pose.joint_params.joint_state_batch).  The
+        # wide block IS out["articulation"] and what retire / stream_* return as the articulation block: no new name in the result tuple.
+        # Like the articulation launch it reads the step's own NPCS heads, the ones the record was fitted on: articulation=True, and with it
+        # joint_states=True, refuses couple=False above.
+        from .pose.joint_params import check_joint_states
+        self.joint_states = check_joint_states(joint_states, self.articulation)
         # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
         # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
         # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
@@ -358,7 +368,8 @@ class AncshPipeline(object):
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
-                            self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images) for _ in range(max(1, slots))]
+                            self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
+                            joint_states=self.joint_states) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -458,6 +469,9 @@ class AncshPipeline(object):
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
             out["articulation"] = articulation_batch(a, n, sol["record"])
+            if self.joint_states:        # one more: the block's 12 columns and the joint state behind them, (B, K, 20) float64
+                from .pose.joint_params import joint_state_batch
+                out["articulation"] = joint_state_batch(sl.P, n, sol["record"], out["articulation"])
         if self.dense or self.label_images:      # never both: a depth pipeline refuses dense=True
             # the last launch: every raw row of the slot's batch (label_images: its unprojected rows), into the slot's own (capacity, .) buffers
             from .dataset import raw_point_labels
@@ -668,7 +682,8 @@ class AncshPipeline(object):
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
-        block (flagged clouds: the f32 graph's rows, like their records).  dense=True (a pipeline built with dense=True): + (labels (R,)
+        block (flagged clouds: the f32 graph's rows, like their records); built with joint_states=True it is the (n_valid, K, 20) block
+        whose columns 12..19 hold the joint state.  dense=True (a pipeline built with dense=True): + (labels (R,)
         int32, values (R, 7) float32, offsets (n_valid+1,) int64) as the last element: the valid clouds' R raw rows in submission order,
         cloud c's rows [offsets[c], offsets[c+1]) (raw_point_labels; flagged clouds: the f32 graph's rows).  A pipeline built with
         depth_capacity appends the valid-pixel counts (n_valid,) int32 of the batch's frames as the last element.  label_images=True (a

@@ -105,3 +105,39 @@ def articulation_batch(ancsh_pred, npcs_pred, record, debug=False):
               _lib.ptr(_f32(npcs_pred["nocs_per_point"], dev)), _lib.ptr(_f32(npcs_pred["W"], dev)), _lib.ptr(record), _lib.ptr(art),
               _lib.ptr(dbg.get("joint_nocs") if K > 1 else None), _lib.ptr(dbg.get("st0")), _lib.ptr(dbg.get("extent")))
     return (art, dbg) if debug else art
+
+
+JOINT_STATE_WIDTH = 20          # include/ancsh_hip.h, ancsh_joint_state_rec: the articulation block's 12 columns + 8 of joint state
+
+
+def check_joint_states(joint_states, articulation):
+    """-> bool(joint_states); ValueError (before anything touches the GPU) when it is asked for without the articulation block, whose joint
+    axes it reads and whose columns it carries."""
+    if joint_states and not articulation:
+        raise ValueError("joint_states=True rides inside the articulation block and reads its joint axes: it needs articulation=True")
+    return bool(joint_states)
+
+
+def joint_state_batch(P, npcs_pred, record, art):
+    """The joint states of a batch in ONE launch (ancsh_joint_state_rec, csrc/joint_state.hip), behind articulation_batch: P (B, N, C >= 3)
+    float32 sampled points, npcs_pred = the NPCS network's output dict (nocs_per_point (B, N, 3K), W (B, N, K)), record (B, K, 26) float64,
+    art = articulation_batch's (B, K, 12) block.  Returns the (B, K, 20) float64 block on the device, row j = [art row j (12, bit for bit) |
+    angle of R_0^T R_j, degrees | the same, signed about the joint axis | t_j - t_0 (3) | its slide along the axis | boundary slide
+    dynam_j - canon_j | points of part j] (row 0: NaN in 12..17; include/ancsh_hip.h has the NaN rules).  No host synchronisation and no
+    allocation beyond the output: the captured streaming step calls it."""
+    dev = record.device
+    _lib.require_cuda(record, art, P)
+    B, K = record.shape[:2]
+    if record.dtype != torch.float64 or tuple(record.shape) != (B, K, 26) or not record.is_contiguous():
+        raise ValueError("record must be a contiguous (B, K, 26) float64 tensor")
+    if art.dtype != torch.float64 or tuple(art.shape) != (B, K, 12) or not art.is_contiguous():
+        raise ValueError("art must be a contiguous (B, K, 12) float64 tensor (articulation_batch's block)")
+    P = _f32(P, dev)
+    nocs, mask = _f32(npcs_pred["nocs_per_point"], dev), _f32(npcs_pred["W"], dev)
+    N = P.shape[1] if P.dim() == 3 else -1
+    if P.dim() != 3 or P.shape[0] != B or P.shape[2] < 3 or tuple(nocs.shape) != (B, N, 3 * K) or tuple(mask.shape) != (B, N, K):
+        raise ValueError("P (B, N, >= 3), nocs_per_point (B, N, 3K) and W (B, N, K) must agree with the record's B = %d, K = %d" % (B, K))
+    wide = torch.empty((B, K, JOINT_STATE_WIDTH), dtype=torch.float64, device=dev)
+    _lib.call("ancsh_joint_state_rec", B, N, K, _lib.ptr(P), P.shape[2], _lib.ptr(nocs), _lib.ptr(mask), _lib.ptr(record), _lib.ptr(art),
+              _lib.ptr(wide))
+    return wide

@@ -42,7 +42,8 @@ extern "C" {
 
 /* library / diagnostics */
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
-                                 *     ancsh_depth_label_images (the depth front end and its label / NOCS images);
+                                 *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
+                                 *     streamed joint states);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
                                  * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
@@ -741,6 +742,29 @@ int ancsh_articulation_rec(int b, int n, int K, int gocs_channels, int joint_cha
                            const float *mask, const float *heatmap, const float *unitvec, const float *joint_axis,
                            const float *joint_index, const float *npcs_nocs, const float *npcs_mask, const double *record,
                            double *art, double *joint_nocs, double *st0, float *extent, void *stream);
+
+/* Joint states of a streamed batch, one launch behind ancsh_articulation_rec (no new ABI number: callers detect it by its symbol): the
+ * pred side of evaluation/eval_pose_err.py:304-321 -- the relative rotation R_0^T R_j and the relative translation of every child part
+ * against part 0, as t_j - t_0 (:318) and as the boundary slide dynam_j - canon_j (:263-266, 320) -- per cloud, one workgroup each.
+ * P (b,n,.) float32 rows of ldp floats whose first three are the sampled point; npcs_nocs (b,n,3K), npcs_mask (b,n,K) float32: the NPCS
+ * heads; record (b,K,26) float64: nonlinear R_j 13..21 (row-major), s_j 22, t_j 23..25; art (b,K,12) float64 as ancsh_articulation_rec
+ * wrote it.  wide (b,K,20) float64, row j:
+ *   0..11  art[b][j][0..11], bit for bit (NaN payloads included)
+ *   12     angle_j = atan2(|v|, c) in degrees, c = (tr Rrel - 1) / 2, v = 1/2 (Rrel[2][1] - Rrel[1][2], Rrel[0][2] - Rrel[2][0],
+ *          Rrel[1][0] - Rrel[0][1]), Rrel = R_0^T R_j in float64: rot_diff_degree(I, Rrel) (lib/d3_utils.py:144-148), well conditioned at
+ *          0 and 180 degrees; R_0 = R_j gives exactly 0
+ *   13     atan2(v . a, c) in degrees, a = R_0^T u, u = art[9..11] / |art[9..11]|: the angle signed about the joint axis (NaN for a NaN
+ *          or zero axis)
+ *   14..16 t_j - t_0 in camera space (:318)
+ *   17     (t_j - t_0) . u, the slide along the joint axis (NaN with a NaN axis)
+ *   18     dynam_j - canon_j in float64: dynam_j = ancsh_part_extents' dynam on P and npcs_mask with pose0 = [R_0 | t_0] of the record
+ *          (bit-equal), canon_j = - scale_pred_j[0] / 2 + 0.5 in float32 with ancsh_part_extents' scale_pred on npcs_nocs (bit-equal);
+ *          row 0 gets its own; NaN for a part without points
+ *   19     the points of part j (ancsh_part_extents' count) as a double, every row
+ * Row 0's 12..17 are NaN.  A NaN in part 0's nonlinear pose (record columns 13..25 of row 0): 12..18 of every row NaN; a NaN in part j's:
+ * row j's 12..18 NaN.  K = 1: row 0 only.  1 <= K <= 8, n >= 1, ldp >= 3; b == 0 launches nothing. */
+int ancsh_joint_state_rec(int b, int n, int K, const float *P, int ldp, const float *npcs_nocs, const float *npcs_mask,
+                          const double *record, const double *art, double *wide, void *stream);
 
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 
