@@ -317,11 +317,13 @@ class ShardedPipeline(object):
     joint_types (None | "revolute" | "prismatic" | K - 1 of them): passed to every rank's pipeline (AncshPipeline(joint_types=...)); the
     kind array repeats per cloud, so a shard's slice of it is the shard's own array and sharded streams stay byte-equal to one GPU's.
     joint_states=True (with articulation=True): the blocks are the (n_valid, K, 20) ones (AncshPipeline(joint_states=True)), gathered with
-    the records in the same single gather, 26 + 20 doubles a row."""
+    the records in the same single gather, 26 + 20 doubles a row.
+    fit_quality=True (with raw_capacity only): every rank's streamed record is the (n, K, 39) wide one (AncshPipeline(fit_quality=True)); the
+    gathered row is [record (39) | articulation block], still one gather, and dst returns the wide records."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, joint_states=False, **pipeline_kw):
+                 joint_types=None, joint_states=False, fit_quality=False, **pipeline_kw):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
@@ -349,6 +351,15 @@ class ShardedPipeline(object):
         if self.joint_states:
             pipeline_kw.update(joint_states=True)
         self.art_width = 20 if self.joint_states else 12
+        # fit_quality (raw streams only): every rank streams the (n, K, 39) wide record (AncshPipeline(fit_quality=True)), and retire()
+        # gathers rows of record_width doubles (+ the articulation block): step() / records() (the RCCL path) keep the 26-column record
+        if fit_quality and raw_capacity is None:
+            raise ValueError("fit_quality=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
+        from .pose.quality import FIT_QUALITY_WIDTH, check_fit_quality
+        self.fit_quality = check_fit_quality(fit_quality, pipeline_kw.get("inlier_th", 0.1))
+        if self.fit_quality:
+            pipeline_kw.update(fit_quality=True)
+        self.record_width = FIT_QUALITY_WIDTH if self.fit_quality else 26
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense = bool(dense)
@@ -542,7 +553,7 @@ class ShardedPipeline(object):
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
         articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
         the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows (joint_states=True: the (n_valid, K, 20)
-        block, 46 a row).
+        block, 46 a row; fit_quality=True: the record is the (n_valid, K, 39) wide one and the row 13 doubles longer).
         dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
         batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
@@ -553,16 +564,17 @@ class ShardedPipeline(object):
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        width = 26 + self.art_width if self.articulation else 26      # [record (26) | articulation block (12 or 20)]: one gather either way
+        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39
+        width = rw + self.art_width if self.articulation else rw      # [record (26 or 39) | articulation block (12 or 20)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
         got = {}
         if here:             # the per-rank pipeline's public retire(), with only the keywords it was built for
             built = dict(articulation=self.articulation, dense=self.dense)
             got = unpack_results(self.pipe.retire(flags, **only_asked(**built)), flags=flags, **built)
-            rec[:e - s, :, :26] = got["record"]
+            rec[:e - s, :, :rw] = got["record"]
             if self.articulation:
-                rec[:e - s, :, 26:] = got["articulation"]
+                rec[:e - s, :, rw:] = got["articulation"]
             if flags:
                 words[:e - s] = got["flags"]
         on_dst = self.rank == self.dst
@@ -578,11 +590,11 @@ class ShardedPipeline(object):
         if on_dst:
             cut = [self.shard_of(n_valid, r) for r in range(self.world)]
             packed = np.concatenate([bufs[0][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
-            out["record"] = np.ascontiguousarray(packed[:, :, :26])
+            out["record"] = np.ascontiguousarray(packed[:, :, :rw])
             if flags:
                 out["flags"] = np.concatenate([bufs[1][r].numpy()[:b - a] for r, (a, b) in enumerate(cut)], axis=0)
             if articulation:
-                out["articulation"] = np.ascontiguousarray(packed[:, :, 26:])
+                out["articulation"] = np.ascontiguousarray(packed[:, :, rw:])
         return pack_results(out, flags=flags, articulation=articulation, dense=dense)
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):

@@ -90,8 +90,11 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False, joint_states=False):
+                 depth=None, label_images=False, joint_states=False, fit_quality=False):
         f = dict(dtype=torch.float32, device=device)
+        # columns of a streamed record row, and where the step leaves it: the pose record, or (fit_quality) the wide record -- its 26
+        # columns and the fit quality behind them
+        self.record_width, record_key = (39, "record_wide") if fit_quality else (26, "record")
         # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
         self.art_width = 20 if joint_states else 12
         self.P = torch.zeros((B, N, 3), **f)
@@ -153,7 +156,8 @@ class _Slot(object):
             # front end's valid-pixel counts are not refit.
             pinned = lambda dtype, *shape: lambda: (torch.zeros(shape, dtype=dtype).pin_memory(),)
             labels = lambda: label_buffers(raw_capacity)
-            outs = [Output("record", lambda sl, f32: (sl.pick("out", f32)["record"],), pinned(torch.float64, B, K, 26), refit=range_guard)]
+            outs = [Output("record", lambda sl, f32: (sl.pick("out", f32)[record_key],), pinned(torch.float64, B, K, self.record_width),
+                           refit=range_guard)]
             if depth:
                 outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
             if articulation:
@@ -248,7 +252,7 @@ class AncshPipeline(object):
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False):
+                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -282,6 +286,13 @@ class AncshPipeline(object):
         # joint_states=True, refuses couple=False above.
         from .pose.joint_params import check_joint_states
         self.joint_states = check_joint_states(joint_states, self.articulation)
+        # fit_quality: one more launch behind the fit and the record poison, in front of the articulation launch (ancsh_fit_quality_rec,
+        # pose.quality.fit_quality_batch): out["record_wide"] (B, K, 39) -- the record's 26 columns bit for bit, then per part its points,
+        # stage A's consensus count, stage B's score and the inliers / mean / RMS / median / max residual of the baseline and of the nonlinear
+        # pose over all points of the part.  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the wide one: no new
+        # name in the result tuple.  It reads the solver's own packed rows, so it works with couple=False too.
+        from .pose.quality import check_fit_quality
+        self.fit_quality = check_fit_quality(fit_quality, inlier_th)
         # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
         # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
         # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
@@ -369,7 +380,7 @@ class AncshPipeline(object):
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
                             self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
-                            joint_states=self.joint_states) for _ in range(max(1, slots))]
+                            joint_states=self.joint_states, fit_quality=self.fit_quality) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -464,8 +475,10 @@ class AncshPipeline(object):
             nocs, mask, axis, index = sl.pred_nocs, sl.pred_mask, sl.pred_axis, sl.pred_index if self.predicted else None
         assoc = dict(joint_index=index) if self.predicted else dict(joint_cls=sl.joint_cls)      # one of them: the solver refuses both
         sol = self.solver.solve(sl.P, nocs, mask, axis, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
-                                key_dev=key_dev, **assoc)
+                                key_dev=key_dev, fit_quality=self.fit_quality, **assoc)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
+        if self.fit_quality:             # behind the fit and the record poison: (B, K, 39) float64, one launch (the solver issued it)
+            out["record_wide"] = sol["record_wide"]
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
             out["articulation"] = articulation_batch(a, n, sol["record"])
@@ -678,7 +691,8 @@ class AncshPipeline(object):
 
     def retire(self, flags=False, articulation=False, dense=False, label_images=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
-        records, a fresh host array.  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
+        records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
+        the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation

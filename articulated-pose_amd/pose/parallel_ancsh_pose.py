@@ -241,7 +241,7 @@ class PoseSolver(object):
         return self._kind_dev[B]
 
     def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls=None, draws_a=None, draws_b=None, seed=0, seed_dev=None,
-              key_dev=None, joint_index=None):
+              key_dev=None, joint_index=None, fit_quality=False):
         """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and it is the
         latency-bound half (64 waves for 1.6 ms: MINPACK's longest trajectory), so it is ISSUED FIRST: its LM kernel then runs
         under the full-chip scoring kernel of other batches in flight, and a batch ends with 0.3 ms of stage A instead of idling
@@ -260,11 +260,21 @@ class PoseSolver(object):
         equal those of joint_cls = np.argmax(joint_index, -1); a joint no point selects has a NaN direction (certain when K - 1 >= C).
         Fitted as a revolute joint it gets no joint fit: every evaluation of the objective is NaN, MINPACK accepts no step, and the row
         holds the unrefined Kabsch start of the winning sample (finite, not NaN: tests/test_prismatic_gpu.py).  A prismatic joint
-        (joint_types) does not read its direction and is fitted like any other."""
+        (joint_types) does not read its direction and is fitted like any other.
+        fit_quality=True: one more launch behind the poison (pose.quality.fit_quality_batch) adds "record_wide" (B, K, 39) float64 -- the
+        record's 26 columns bit for bit, then per part its points, both winners' scores and the inliers / mean / RMS / median / max
+        residual of the baseline and of the nonlinear pose over all points of the part.  Without it nothing changes."""
         _one_association(joint_cls, joint_index)
+        if fit_quality:
+            from .quality import check_fit_quality
+            check_fit_quality(True, self.th)
         out = self._partition(P, nocs_pred, mask_pred)
         self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index)
-        return self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
+        out = self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
+        if fit_quality:
+            from .quality import fit_quality_batch
+            out["record_wide"] = fit_quality_batch(out, self.th)
+        return out
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):
         """Part labels + per-part RANSAC / Kabsch (stage A, :238-272): needs only the part-NOCS network's outputs."""

@@ -43,7 +43,7 @@ extern "C" {
 /* library / diagnostics */
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
-                                 *     streamed joint states);
+                                 *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
                                  * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
@@ -765,6 +765,32 @@ int ancsh_articulation_rec(int b, int n, int K, int gocs_channels, int joint_cha
  * row j's 12..18 NaN.  K = 1: row 0 only.  1 <= K <= 8, n >= 1, ldp >= 3; b == 0 launches nothing. */
 int ancsh_joint_state_rec(int b, int n, int K, const float *P, int ldp, const float *npcs_nocs, const float *npcs_mask,
                           const double *record, const double *art, double *wide, void *stream);
+
+/* Fit quality of a pose record, one launch behind the fit and the record poison (no new ABI number: callers detect it by its symbol):
+ * what the reference prints per part and drops (evaluation/parallel_ancsh_pose.py:273, 311, 322) and what its verifiers
+ * (single_transformation_verifier :48-54, joint_transformation_verifier :186-194) say about the poses the record holds.
+ * off (b*K+1) int32, src / tgt (rows,3) float32: ancsh_pose_partition's packed rows, part (c,j) = rows [off[cK+j], off[cK+j+1]), src the
+ * point's own part-NOCS triple, tgt the sampled point; record (b,K,26) float64, read as it stands (after the poison); best_a (b*K,2)
+ * int32 = ancsh_ransac_single*'s out_best, score_b (b*(K-1)) float64 = ancsh_ransac_joint*'s out_score: either may be NULL, its column
+ * is then NaN.  wide (b,K,39) float64, row (c,j):
+ *   0..25  record[c][j][0..25], bit for bit (NaN payloads included)
+ *   26     n_j = off[cK+j+1] - off[cK+j], the points of the part
+ *   27     best_a[cK+j][1], the stage-A winner's consensus count (:273's ninliers)
+ *   28..32 the baseline pose (columns 0..12 = R row-major, s, t): points with rho < inlier_th under this REFIT pose, then the mean, the
+ *          RMS, the median (np.median: the middle order statistic, or (a + b) / 2 of the two middle ones) and the max of rho over all n_j
+ *          points
+ *   33     score_b of the joint fit that produced this row's nonlinear pose: joint 1's for row 0, joint j's for row j >= 1; NaN for K = 1
+ *   34..38 the nonlinear pose (columns 13..25): the same five numbers (K = 1: computed from 13..25 like any other)
+ * rho of a point, float64 (src, tgt promoted), evaluated as written, no contraction:
+ *   y_c = (R_c0 x_0 + R_c1 x_1) + R_c2 x_2;  r_c = (tgt_c - s y_c) - t_c;  rho = sqrt((r_0^2 + r_1^2) + r_2^2)
+ * Counts, medians and maxima are exact; the sums behind mean and RMS are added in a fixed order (the same bytes every run, whatever b and
+ * wherever the part lies in the batch).  n_j = 0: 28..32 and 34..38 NaN.  A NaN among a pose's 13 numbers: that pose's five columns NaN.
+ * A part longer than ANCSH_FIT_QUALITY_MAX_N points is clamped IN THE KERNEL (off lives on the device and is never read by the host, so the
+ * call stays capturable): its row keeps the true n_j in column 26 and gets NaN in 28..32 and 34..38.
+ * 1 <= K <= 16, inlier_th finite and > 0; b == 0 launches nothing. */
+#define ANCSH_FIT_QUALITY_MAX_N 8192      /* the residuals of one pose stay in LDS: the fit's own bound on a part */
+int ancsh_fit_quality_rec(int b, int K, const int *off, const float *src, const float *tgt, const double *record, double inlier_th,
+                          const int *best_a, const double *score_b, double *wide, void *stream);
 
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 

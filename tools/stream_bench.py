@@ -3,13 +3,14 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
-                                 [--joint-source {gt,predicted}] [--joint-states]
+                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
 line then also carries the rerun count, the latency of the batches that reran and the device memory the streaming pipeline holds.
 --articulation streams with AncshPipeline(articulation=True) (the record plus the (n, K, 12) articulation block per cloud).
 --joint-states (with --articulation) streams with AncshPipeline(joint_states=True): the block is the (n, K, 20) one, one more launch a step.
+--fit-quality streams with AncshPipeline(fit_quality=True): the record is the (n, K, 39) wide one, one more launch a step.
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 --joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
 head) and submits (n_raw, 3) xyz clouds: no label column crosses to the device.
@@ -41,6 +42,7 @@ def main():
     ap.add_argument("--overflow-every", type=int, default=0)
     ap.add_argument("--articulation", action="store_true", help="stream with AncshPipeline(articulation=True) and retire the blocks too")
     ap.add_argument("--joint-states", action="store_true", help="with --articulation: AncshPipeline(joint_states=True), the (n, K, 20) block")
+    ap.add_argument("--fit-quality", action="store_true", help="AncshPipeline(fit_quality=True): the streamed record is the (n, K, 39) wide one")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
                     help="predicted: the joint association from the network's index head; (n_raw, 3) xyz clouds are submitted")
@@ -71,7 +73,7 @@ def main():
     mem0 = torch.cuda.mem_get_info(dev)[0]
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
                          range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
-                         joint_source=args.joint_source, joint_states=args.joint_states).prepare()
+                         joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
@@ -147,6 +149,8 @@ def main():
         line.update({"articulation": True, "blocks_out": n_blocks})
     if args.joint_states:
         line.update({"joint_states": True})
+    if args.fit_quality:
+        line.update({"fit_quality": True})
     if predicted:
         line.update({"joint_source": "predicted"})
     if args.dense:
