@@ -129,6 +129,9 @@ SIGNATURES = {
     # the fit quality behind the record (no ABI bump, detected by its symbol): b, K, off, src, tgt, record, inlier_th, best_a, score_b, wide,
     # stream
     "ancsh_fit_quality_rec": [_c_int] * 2 + [_vp] * 4 + [ctypes.c_double] + [_vp] * 3 + [_vp],
+    # the errors against ground truth behind the record (no ABI bump, detected by its symbol): b, n, K, nres, P, ldp, npcs_nocs, npcs_mask,
+    # record, ld, gt, wide, stream
+    "ancsh_gt_error_rec": [_c_int] * 4 + [_vp, _c_int] + [_vp] * 3 + [_c_int] + [_vp] * 2 + [_vp],
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

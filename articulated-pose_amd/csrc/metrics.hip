@@ -8,33 +8,9 @@
 // numpy.linspace's (start + i*step, the last one exactly stop), the projections up.u are sums of three products in
 // (x, y, z) order and the bounds np.dot(u, u).
 #include "common.h"
+#include "iou_grid.h"      // BoxFrame, box_frame, inside: shared with gt_errors.hip
 
 namespace ancsh {
-
-struct BoxFrame {
-    double o[3], u1[3], u2[3], u3[3], d1, d2, d3;
-};
-
-__device__ __forceinline__ void box_frame(const double *bb, BoxFrame &f) {      // bb: 8 x 3 corners, reference's order
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        f.o[c] = bb[4 * 3 + c];
-        f.u1[c] = bb[5 * 3 + c] - bb[4 * 3 + c];
-        f.u2[c] = bb[7 * 3 + c] - bb[4 * 3 + c];
-        f.u3[c] = bb[0 * 3 + c] - bb[4 * 3 + c];
-    }
-    f.d1 = f.u1[0] * f.u1[0] + f.u1[1] * f.u1[1] + f.u1[2] * f.u1[2];
-    f.d2 = f.u2[0] * f.u2[0] + f.u2[1] * f.u2[1] + f.u2[2] * f.u2[2];
-    f.d3 = f.u3[0] * f.u3[0] + f.u3[1] * f.u3[1] + f.u3[2] * f.u3[2];
-}
-
-__device__ __forceinline__ bool inside(const BoxFrame &f, double x, double y, double z) {
-    const double ux = x - f.o[0], uy = y - f.o[1], uz = z - f.o[2];
-    const double p1 = ux * f.u1[0] + uy * f.u1[1] + uz * f.u1[2];
-    const double p2 = ux * f.u2[0] + uy * f.u2[1] + uz * f.u2[2];
-    const double p3 = ux * f.u3[0] + uy * f.u3[1] + uz * f.u3[2];
-    return (p1 > 0.0) & (p1 < f.d1) & (p2 > 0.0) & (p2 < f.d2) & (p3 > 0.0) & (p3 < f.d3);
-}
 
 __global__ __launch_bounds__(256) void iou_3d_kernel(int nres, const double *__restrict__ bbox1, const double *__restrict__ bbox2,
                                                      double *__restrict__ iou, long *__restrict__ counts) {

@@ -319,11 +319,14 @@ class ShardedPipeline(object):
     joint_states=True (with articulation=True): the blocks are the (n_valid, K, 20) ones (AncshPipeline(joint_states=True)), gathered with
     the records in the same single gather, 26 + 20 doubles a row.
     fit_quality=True (with raw_capacity only): every rank's streamed record is the (n, K, 39) wide one (AncshPipeline(fit_quality=True)); the
-    gathered row is [record (39) | articulation block], still one gather, and dst returns the wide records."""
+    gathered row is [record (39) | articulation block], still one gather, and dst returns the wide records.
+    ground_truth=True (with raw_capacity only): every rank's pipeline is built with ground_truth=True and submit() hands it its shard's rows
+    of the batch's (n_valid, K, 19) ground truth; the streamed record is 12 columns wider (the errors, ancsh_gt_error_rec) and travels in
+    the same single gather."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, joint_states=False, fit_quality=False, **pipeline_kw):
+                 joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, **pipeline_kw):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
@@ -360,6 +363,15 @@ class ShardedPipeline(object):
         if self.fit_quality:
             pipeline_kw.update(fit_quality=True)
         self.record_width = FIT_QUALITY_WIDTH if self.fit_quality else 26
+        # ground_truth (raw streams only): every rank streams the record 12 columns wider (AncshPipeline(ground_truth=True)) and gets its
+        # shard's rows of the batch's ground truth from submit()
+        if ground_truth and raw_capacity is None:
+            raise ValueError("ground_truth=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
+        self.ground_truth = bool(ground_truth)
+        if self.ground_truth:
+            from .pose.gt_errors import GT_ERROR_WIDTH
+            pipeline_kw.update(ground_truth=True)
+            self.record_width += GT_ERROR_WIDTH
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense = bool(dense)
@@ -503,23 +515,33 @@ class ShardedPipeline(object):
                                  "cloud), raw_capacity is %d per rank" % (r, s, e - 1, rows, self.raw_capacity))
         return clouds, nf
 
-    def submit(self, clouds, norm_factors, tag=None):
+    def submit(self, clouds, norm_factors, tag=None, gt=None):
         """Enqueue one GLOBAL batch (every rank calls this with the same batch): clouds = 1..global_batch raw (n_raw, 4) arrays, one norm
         factor each.  This rank submits its shard -- nothing when a short batch leaves it no cloud -- to its pipeline with seed
         seed + 2k (k = global batches submitted so far) and cloud_base = lo.  A bad batch raises ValueError on every rank, a full
-        in-flight window RuntimeError on every rank; either way nothing is enqueued and the stream stays usable.  World 1: the
-        local pipeline's submit."""
+        in-flight window RuntimeError on every rank; either way nothing is enqueued and the stream stays usable.  gt
+        (ShardedPipeline(..., ground_truth=True); ValueError otherwise): the batch's (n_valid, K, 19) ground truth, checked whole on
+        every rank; this rank's pipeline gets rows [s, e) of it.  None: a batch without ground truth.  World 1: the local pipeline's
+        submit."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
+        if gt is not None and not self.ground_truth:
+            raise ValueError("gt needs ShardedPipeline(..., ground_truth=True)")
+        more = dict(gt=gt) if self.ground_truth else {}
         if self.world == 1:
-            return self.pipe.submit(clouds, norm_factors, tag=tag)
+            return self.pipe.submit(clouds, norm_factors, tag=tag, **more)
         clouds, nf = self._check_batch(clouds, norm_factors)
+        if gt is not None:
+            from .pose.gt_errors import check_ground_truth
+            gt = check_ground_truth(gt, len(clouds), self.K)
         if len(self._stream) == len(self.pipe.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.pipe.slots))
         seed = self.seed + 2 * self._stream_submitted
         s, e = self.shard_of(len(clouds))
         if e > s:
-            self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo)
+            if self.ground_truth:
+                more = dict(gt=None if gt is None else gt[s:e])
+            self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo, **more)
         self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
 
@@ -553,7 +575,8 @@ class ShardedPipeline(object):
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
         articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
         the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows (joint_states=True: the (n_valid, K, 20)
-        block, 46 a row; fit_quality=True: the record is the (n_valid, K, 39) wide one and the row 13 doubles longer).
+        block, 46 a row; fit_quality=True: the record is the (n_valid, K, 39) wide one and the row 13 doubles longer; ground_truth=True: 12
+        more behind the record's columns).
         dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
         batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
@@ -564,7 +587,7 @@ class ShardedPipeline(object):
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39
+        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39; ground_truth: + 12
         width = rw + self.art_width if self.articulation else rw      # [record (26 or 39) | articulation block (12 or 20)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
@@ -602,13 +625,16 @@ class ShardedPipeline(object):
         or (clouds, norm_factors, tag) (tag defaults to the batch's index); up to len(slots) batches stay in flight; yields (tag, seed,
         record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
         ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
-        seed, lm_schedule).  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
+        seed, lm_schedule).  ShardedPipeline(..., ground_truth=True): batches yields (clouds, norm_factors, gt) or (clouds, norm_factors,
+        gt, tag), as AncshPipeline.stream_batches.  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
         (labels, values, offsets) in global cloud order, last (see retire()).  World 1 (or no process group): the local pipeline's
         stream_batches."""
         check_built_with(self, "stream_batches", "ShardedPipeline", articulation=articulation, dense=dense)
         if self.world == 1:
             yield from self.pipe.stream_batches(batches, flags, **only_asked(articulation=articulation, dense=dense))
             return
+        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag
         yield from pump(batches, self._stream, len(self.pipe.slots),
-                        lambda k, item: self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k),
+                        lambda k, item: self.submit(item[0], item[1], tag=item[2 + g] if len(item) > 2 + g else k,
+                                                    **(dict(gt=item[2] if len(item) > 2 else None) if g else {})),
                         lambda: self.retire(flags, articulation, dense))

@@ -90,11 +90,14 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False, joint_states=False, fit_quality=False):
+                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False):
         f = dict(dtype=torch.float32, device=device)
         # columns of a streamed record row, and where the step leaves it: the pose record, or (fit_quality) the wide record -- its 26
         # columns and the fit quality behind them
         self.record_width, record_key = (39, "record_wide") if fit_quality else (26, "record")
+        if ground_truth:                        # ... and the errors against ground truth behind either (ancsh_gt_error_rec)
+            self.record_width, record_key = self.record_width + 12, "record_gt"
+        self.gt = None
         # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
         self.art_width = 20 if joint_states else 12
         self.P = torch.zeros((B, N, 3), **f)
@@ -129,6 +132,13 @@ class _Slot(object):
             self.h_hdr = torch.zeros((lay.words,), dtype=torch.int32).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
+            if ground_truth:
+                # the batch's ground truth, one (K, 19) float64 block per cloud (pose.gt_errors), and its pinned twin: copied with the
+                # header; all NaN (no ground truth) until a submit says otherwise
+                from .pose.gt_errors import GT_WIDTH
+                self.gt = torch.full((B, K, GT_WIDTH), float("nan"), dtype=torch.float64, device=device)
+                self.h_gt = torch.full((B, K, GT_WIDTH), float("nan"), dtype=torch.float64).pin_memory()
+                self.np_gt = self.h_gt.numpy()
             # dense / label_images: the per-raw-row (dense) or per-row and per-pixel (rowlab, img) labels / values the captured step writes
             # (slot-owned, outside the graph's pool, so a later replay never hands their memory to another tensor) and the f32 graph's own
             # (range guard); rowlab is device only: nobody reads rows.  Their pinned twins cost 4 + 28 bytes per row / pixel of capacity.
@@ -252,7 +262,8 @@ class AncshPipeline(object):
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False):
+                 joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
+                 ground_truth=False):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -293,6 +304,16 @@ class AncshPipeline(object):
         # name in the result tuple.  It reads the solver's own packed rows, so it works with couple=False too.
         from .pose.quality import check_fit_quality
         self.fit_quality = check_fit_quality(fit_quality, inlier_th)
+        # ground_truth (streaming only): a slot holds the batch's (B, K, 19) float64 ground truth (pose.gt_errors.pack_ground_truth's rows,
+        # submit(..., gt=...)), copied in with the header, and one more launch behind the fit, the poison and the fit-quality launch
+        # (ancsh_gt_error_rec, pose.gt_errors.gt_error_batch) turns record + ground truth into the evaluation's per-part numbers:
+        # out["record_gt"] (B, K, 38) -- the record's 26 columns bit for bit, then rpy_err / xyz_err / scale_err / 3-D IoU / relative
+        # rotation error of both poses, the nonlinear pose's relative translation error and the part's points -- or (B, K, 51) behind the
+        # wide record's 39.  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is this widest one.
+        if ground_truth and raw_capacity is None and depth_capacity is None:
+            raise ValueError("ground_truth=True travels in with a streamed batch (submit / submit_depth): it needs raw_capacity or "
+                             "depth_capacity")
+        self.ground_truth = bool(ground_truth)
         # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
         # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
         # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
@@ -380,7 +401,8 @@ class AncshPipeline(object):
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
                             self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
-                            joint_states=self.joint_states, fit_quality=self.fit_quality) for _ in range(max(1, slots))]
+                            joint_states=self.joint_states, fit_quality=self.fit_quality, ground_truth=self.ground_truth)
+                      for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -475,10 +497,12 @@ class AncshPipeline(object):
             nocs, mask, axis, index = sl.pred_nocs, sl.pred_mask, sl.pred_axis, sl.pred_index if self.predicted else None
         assoc = dict(joint_index=index) if self.predicted else dict(joint_cls=sl.joint_cls)      # one of them: the solver refuses both
         sol = self.solver.solve(sl.P, nocs, mask, axis, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
-                                key_dev=key_dev, fit_quality=self.fit_quality, **assoc)
+                                key_dev=key_dev, fit_quality=self.fit_quality, ground_truth=sl.gt, **assoc)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
         if self.fit_quality:             # behind the fit and the record poison: (B, K, 39) float64, one launch (the solver issued it)
             out["record_wide"] = sol["record_wide"]
+        if self.ground_truth:            # behind those: (B, K, 38 or 51) float64, one launch (the solver issued it)
+            out["record_gt"] = sol["record_gt"]
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
             out["articulation"] = articulation_batch(a, n, sol["record"])
@@ -583,7 +607,7 @@ class AncshPipeline(object):
             sl.stream.synchronize()
 
     # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
-    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0):
+    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0, gt=None):
         """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
         sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.
         joint_source="predicted": (n_raw, 3) xyz clouds, or (n_raw, 4) ones whose 4th column is ignored.  A short batch
@@ -591,6 +615,8 @@ class AncshPipeline(object):
         of its pose fit (stage B uses seed + 1); None = self.seed + 2k for the k-th submitted batch (2k + 1 is its stage B).
         cloud_base (keyed=True only; written into the pinned header with the seed): the global index of the batch's cloud 0 -- cloud b
         is sampled and fitted as global cloud cloud_base + b; (cloud_base + batch_size) * num_parts must stay below 2^20.
+        gt (a pipeline built with ground_truth=True; ValueError on any other): the valid clouds' (n_valid, K, 19) ground truth
+        (pose.gt_errors.pack_ground_truth); None = all-NaN rows, a batch without ground truth.  Padding clouds get NaN rows.
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
         if self.raw_capacity is None:
@@ -613,16 +639,16 @@ class AncshPipeline(object):
                 np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
                 return [(sl.raw_rows[:rows], sl.h_rows[:rows])]
             return len(valid), nf, stage
-        self._enqueue(front, seed, tag, cloud_base)
+        self._enqueue(front, seed, tag, cloud_base, gt)
 
-    def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0):
+    def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None):
         """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
         (depth_crop (h, w) of the pipeline's depth_dtype, mask_crop (h, w) bool / integer or None = every pixel, (row0, col0) = the crop's
         origin in the full image); norm_factors = one finite float per frame; cameras = one 6-vector of unprojection coefficients
         (depth.unprojection_from_intrinsics / unprojection_from_projmat) or one per frame; depth_scale = one value or one per frame
         (depth unit -> the cloud's unit).  The valid pixels of each crop (mask non-zero and a usable depth) become the frame's cloud on the
         device; a frame without one gives an all-NaN record and count 0.  A short batch is padded with its first frame (whose pixels are
-        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base: as submit().  Bad input
+        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base, gt: as submit().  Bad input
         raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.  Either way the pipeline stays usable."""
         if self.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
@@ -647,13 +673,13 @@ class AncshPipeline(object):
                     sl.np_dest[n_valid:] = -1
                 return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
             return n_valid, nf, stage
-        self._enqueue(front, seed, tag, cloud_base)
+        self._enqueue(front, seed, tag, cloud_base, gt)
 
-    def _enqueue(self, front, seed, tag, cloud_base):
+    def _enqueue(self, front, seed, tag, cloud_base, gt=None):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
         (valid clouds, their norm factors, stage); stage(sl) fills the slot's pinned staging and returns its (device, pinned) copies.
-        Checks in order: the key, front()'s, the in-flight window (RuntimeError); only then prepare().  On the slot's stream: the H2D
-        copies with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
+        Checks in order: the key, front()'s, the ground truth, the in-flight window (RuntimeError); only then prepare().  On the slot's
+        stream: the H2D copies (the ground truth's with the header's) with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
         next replay's pool reuses its block, see step()), d2h_done."""
         from .dataset import check_stream_key, seed_bits
         if self.keyed:
@@ -661,6 +687,11 @@ class AncshPipeline(object):
         elif cloud_base != 0:
             raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
         n_valid, nf, stage = front()
+        if gt is not None:
+            if not self.ground_truth:
+                raise ValueError("gt needs AncshPipeline(..., ground_truth=True)")
+            from .pose.gt_errors import check_ground_truth
+            gt = check_ground_truth(gt, n_valid, self.K)
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:
@@ -674,6 +705,11 @@ class AncshPipeline(object):
         copies = stage(sl)
         sl.np_nf[:n_valid] = nf
         sl.np_nf[n_valid:] = nf[0]
+        if self.ground_truth:                      # NaN rows for the padding clouds and for a batch without ground truth
+            sl.np_gt[:] = np.nan
+            if gt is not None:
+                sl.np_gt[:n_valid] = gt
+            copies = copies + [(sl.gt, sl.h_gt)]
         cur = torch.cuda.current_stream(self.device)
         if cur != sl.stream and not cur.query():
             sl.stream.wait_stream(cur)
@@ -692,7 +728,9 @@ class AncshPipeline(object):
     def retire(self, flags=False, articulation=False, dense=False, label_images=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
-        the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
+        the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph; built with
+        ground_truth=True: 12 more columns behind either, the errors against the submitted ground truth, ancsh_gt_error_rec, refit
+        alike).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
@@ -730,17 +768,20 @@ class AncshPipeline(object):
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
-        batch's index); up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
+        batch's index) -- a pipeline built with ground_truth=True: (clouds, norm_factors, gt) or (clouds, norm_factors, gt, tag), gt as
+        submit() takes it --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
         flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
         last -- see retire())."""
         check_built_with(self, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
+        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag
         yield from pump(batches, self._inflight, len(self.slots),
-                        lambda k, item: self.submit(item[0], item[1], tag=item[2] if len(item) > 2 else k),
+                        lambda k, item: self.submit(item[0], item[1], tag=item[2 + g] if len(item) > 2 + g else k,
+                                                    **(dict(gt=item[2] if len(item) > 2 else None) if g else {})),
                         lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
-        last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base; yields what retire() returns, in
+        last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base / gt; yields what retire() returns, in
         submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them)."""
         check_built_with(self, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
 

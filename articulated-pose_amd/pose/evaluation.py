@@ -294,3 +294,38 @@ def miou_report(iou_rat, num_parts, domain, nocs):
         rows[k] = a.sum(0) / max(a.shape[0], 1)
     _table(lines, '3D IoU', domain, nocs, rows)
     return lines
+
+
+def stream_tables(rows, num_parts, item, domain, nocs="ANCSH", error_skip=None, device="cpu"):
+    """The scripts' tables from accumulated streamed rows of a ground-truth pipeline (AncshPipeline(..., ground_truth=True)): rows
+    (F, K, 38) float64 -- or (F, K, 51) with fit_quality=True --, one frame per leading index, as retire / stream_batches return them.
+    -> the lines error_report, miou_report and relative_report print, in that order, after the scripts' own skip rules:
+      * the error tables (eval_pose_err.py:111-172) leave out, per key, a frame whose fit failed -- a NaN scale in any part, the
+        poisoned record that stands for the reference's `scale is None` -- and count a NaN translation error as 0; error_skip: a
+        boolean (F,) mask of frames to leave out of THESE tables only (the drawer's instance 45841, :115: the caller knows the names);
+      * the IoU table (compute_miou.py:150-240) keeps, per key, the frames whose K IoU columns are all numbers: a NaN in the pose (the
+        scripts' NaN-translation test), a frame without ground truth and a part without predicted points (both raise inside the
+        scripts' bare except) blank the column;
+      * the relative table (eval_pose_err.py:279-363) keeps the same frames -- the reference asks for a usable record, ground truth and a
+        boundary entry, which needs every part to have points --; its NaN rotation errors count as 0 (relative_report).  The baseline
+        pose has no streamed relative translation error (its boundary comes from the other network's global NOCS): the drawer's
+        baseline line is NaN."""
+    from .gt_errors import (ERR_IOU, ERR_NL_IOU, ERR_NL_REL_ROT, ERR_NL_REL_TRANS, ERR_NL_RPY, ERR_NL_XYZ, ERR_REL_ROT, ERR_RPY, ERR_XYZ,
+                            GT_ERROR_WIDTH)
+    rows = np.asarray(rows, np.float64)
+    if rows.ndim != 3 or rows.shape[1] != num_parts or rows.shape[2] - GT_ERROR_WIDTH not in (26, 39):
+        raise ValueError("rows must be (frames, %d, 38) or (frames, %d, 51) streamed ground-truth rows, got %s" % (num_parts, num_parts, rows.shape))
+    ld = rows.shape[2] - GT_ERROR_WIDTH
+    skip = np.zeros(rows.shape[0], bool) if error_skip is None else np.asarray(error_skip, bool).reshape(rows.shape[0])
+    cols = {"baseline": (9, ERR_RPY, ERR_XYZ, ERR_IOU, ERR_REL_ROT, None),
+            "nonlinear": (22, ERR_NL_RPY, ERR_NL_XYZ, ERR_NL_IOU, ERR_NL_REL_ROT, ERR_NL_REL_TRANS)}
+    r_raw, t_raw, iou_rat, r_diff, t_diff = {}, {}, {}, {}, {}
+    for key, (scale, rpy, xyz, iou, rel_r, rel_t) in cols.items():
+        fitted = ~np.isnan(rows[:, :, scale]).any(1) & ~skip
+        r_raw[key], t_raw[key] = rows[fitted, :, ld + rpy].tolist(), rows[fitted, :, ld + xyz].tolist()
+        boxed = ~np.isnan(rows[:, :, ld + iou]).any(1)
+        iou_rat[key] = rows[boxed, :, ld + iou].tolist()
+        r_diff[key] = rows[boxed, 1:, ld + rel_r].tolist()
+        t_diff[key] = (rows[boxed, 1:, ld + rel_t] if rel_t is not None else np.full((int(boxed.sum()), num_parts - 1), np.nan)).tolist()
+    return (error_report(r_raw, t_raw, num_parts, domain, nocs, device=device) + miou_report(iou_rat, num_parts, domain, nocs) +
+            relative_report(r_diff, t_diff, num_parts, item, domain, nocs))

@@ -241,7 +241,7 @@ class PoseSolver(object):
         return self._kind_dev[B]
 
     def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls=None, draws_a=None, draws_b=None, seed=0, seed_dev=None,
-              key_dev=None, joint_index=None, fit_quality=False):
+              key_dev=None, joint_index=None, fit_quality=False, ground_truth=None):
         """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and it is the
         latency-bound half (64 waves for 1.6 ms: MINPACK's longest trajectory), so it is ISSUED FIRST: its LM kernel then runs
         under the full-chip scoring kernel of other batches in flight, and a batch ends with 0.3 ms of stage A instead of idling
@@ -263,7 +263,12 @@ class PoseSolver(object):
         (joint_types) does not read its direction and is fitted like any other.
         fit_quality=True: one more launch behind the poison (pose.quality.fit_quality_batch) adds "record_wide" (B, K, 39) float64 -- the
         record's 26 columns bit for bit, then per part its points, both winners' scores and the inliers / mean / RMS / median / max
-        residual of the baseline and of the nonlinear pose over all points of the part.  Without it nothing changes."""
+        residual of the baseline and of the nonlinear pose over all points of the part.  Without it nothing changes.
+        ground_truth=gt ((B, K, 19) float64 on the device, pose.gt_errors.pack_ground_truth's rows): one more launch behind those
+        (pose.gt_errors.gt_error_batch, on P and the nocs_pred / mask_pred the fit read) adds "record_gt" (B, K, 38) float64 -- the
+        record's 26 columns bit for bit, then rpy_err / xyz_err / scale_err / 3-D IoU / relative rotation error of both poses, the
+        nonlinear pose's relative translation error and the part's points -- or, with fit_quality=True, (B, K, 51) behind the wide
+        record's 39.  "record" and "record_wide" are unchanged."""
         _one_association(joint_cls, joint_index)
         if fit_quality:
             from .quality import check_fit_quality
@@ -274,6 +279,10 @@ class PoseSolver(object):
         if fit_quality:
             from .quality import fit_quality_batch
             out["record_wide"] = fit_quality_batch(out, self.th)
+        if ground_truth is not None:
+            from .gt_errors import gt_error_batch
+            P32, nocs32, mask32 = out["_inputs"]          # the contiguous float32 tensors the partition read
+            out["record_gt"] = gt_error_batch(P32, nocs32, mask32, out["record_wide"] if fit_quality else out["record"], ground_truth)
         return out
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):

@@ -43,7 +43,8 @@ extern "C" {
 /* library / diagnostics */
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
-                                 *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality);
+                                 *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
+                                 *     against ground truth);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
                                  * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
@@ -791,6 +792,45 @@ int ancsh_joint_state_rec(int b, int n, int K, const float *P, int ldp, const fl
 #define ANCSH_FIT_QUALITY_MAX_N 8192      /* the residuals of one pose stay in LDS: the fit's own bound on a part */
 int ancsh_fit_quality_rec(int b, int K, const int *off, const float *src, const float *tgt, const double *record, double inlier_th,
                           const int *best_a, const double *score_b, double *wide, void *stream);
+
+/* Errors of a pose record against ground truth, one launch behind the fit (and, if built, the fit-quality launch; no new ABI number:
+ * callers detect it by its symbol).  It replaces, per frame and part, the numbers the reference's offline evaluation reports: rpy_err /
+ * xyz_err / scale_err of both poses (evaluation/parallel_ancsh_pose.py, the end of solver_ransac_nonlinear), the 3-D IoU of the amodal
+ * boxes (evaluation/compute_miou.py:150-229 with lib/d3_utils.py:14-69) and the relative rotation and translation error per joint
+ * (evaluation/eval_pose_err.py:279-338, its ground-truth side :304-326; ancsh_joint_state_rec is the pred side).
+ * P (b,n,.) float32 rows of ldp floats whose first three are the sampled point; npcs_nocs (b,n,3K), npcs_mask (b,n,K) float32: the NPCS
+ * heads the record was fitted on; record (b,K,ld) float64 rows, ld = 26 (the record) or 39 (ancsh_fit_quality_rec's wide record): the
+ * baseline pose in 0..12 and the nonlinear pose in 13..25, each R (9, row-major) | s | t (3).
+ * gt (b,K,19) float64, row (c,j), in the space the fit works in (the sampled cloud P = xyz * norm_factor, as compute_gt_pose produces it):
+ *   0..8   R_gt, row-major (pn_gt[...]['rt']['gt'][j][:3,:3])
+ *   9      s_gt (pn_gt[...]['scale']['gt'][j])
+ *   10..12 t_gt
+ *   13..15 NOCS extent of the ground-truth box (bbox3d_all[ins][j][1][0] - bbox3d_all[ins][j][0][0], compute_miou.py)
+ *   16..18 translation of the NAOCS ground-truth pose (gn_gt[...]['rt']['gt'][j][:3,3]); only column ld+10 reads it
+ * wide (b,K,ld+12) float64, row (c,j): columns 0..ld-1 = the input row bit for bit (NaN payloads included), then
+ *   ld+0..2  baseline pose: rpy_err = rot_diff_degree(R, R_gt) in degrees (lib/d3_utils.py:144-148: arccos((tr(R R_gt^T) - 1) / 2) mod
+ *            2 pi, / pi * 180; no clamp, like the reference: a trace above 3 gives NaN); xyz_err = |t - t_gt|; scale_err = |s - s_gt|
+ *   ld+3     baseline pose: 3-D IoU of the ground-truth box against the predicted box (below)
+ *   ld+4     baseline pose, row j >= 1: rot_diff_degree(R_gt0^T R_gtj, R_0^T R_j) (eval_pose_err.py:304-312, 327); row 0: NaN
+ *   ld+5..9  nonlinear pose: the same five numbers
+ *   ld+10    nonlinear pose, row j >= 1: |(t_naocs_j - t_naocs_0) - d_j R_0[:,0]| (:316-326), d_j = dynam_j - canon_j bit-equal to
+ *            ancsh_joint_state_rec's column 18, R_0 = the record's nonlinear part-0 rotation; row 0: NaN
+ *   ld+11    points of predicted NPCS part j (first maximum of npcs_mask; ancsh_part_extents' count) as a double
+ * float64 evaluated as written, no contraction: tr(A B^T) = (d_0 + d_1) + d_2 with d_a = (A_a0 B_a0 + A_a1 B_a1) + A_a2 B_a2;
+ * (A^T B)_ac = (A_0a B_0c + A_1a B_1c) + A_2a B_2c; norms sqrt((x^2 + y^2) + z^2).
+ * 3-D IoU: scale_pred_j = 2 max |npcs_nocs_j - 0.5| over the part's points, float32, bit-equal to ancsh_part_extents; both boxes are
+ * get_3d_bbox(extent, shift = 1/2) * s taken through . R^T + t -- corner = ((sign * (extent / 2) + 1/2) * s), then
+ * ((R_c0 x + R_c1 y) + R_c2 z) + t_c -- with the predicted R and t rounded to float32 first (the reference's compose_rt) and the
+ * ground-truth pose as given; then iou_3d (lib/d3_utils.py:55-69): an nres^3 numpy.linspace grid (the reference uses 50) over the joint
+ * axis-aligned bounds, |inside both| / |inside either|, 1 when the union is empty; grid coordinates and inside tests are ancsh_iou_3d's.
+ * Counts are integers: the same bytes every run and wherever the cloud lies in the batch.
+ * NaN rules: a NaN among a pose's 13 numbers blanks that pose's five columns (and, nonlinear, ld+10); a NaN in part 0's pose blanks that
+ * pose's relative columns (ld+4, or ld+9 and ld+10) of every row; a NaN in a gt entry blanks every column that reads it (rpy_err: 0..8;
+ * xyz_err: 10..12; scale_err: 9; the IoU: 0..15; the relative rotation: 0..8 of rows 0 and j; ld+10: 16..18 of rows 0 and j) -- an all-NaN
+ * gt row is how a frame without ground truth travels; a part without predicted points gets NaN in ld+3, ld+8 and ld+10.  K = 1: row 0
+ * only.  1 <= K <= 8, n >= 1, ldp >= 3, ld in {26, 39}, 2 <= nres <= 64; b == 0 launches nothing. */
+int ancsh_gt_error_rec(int b, int n, int K, int nres, const float *P, int ldp, const float *npcs_nocs, const float *npcs_mask,
+                       const double *record, int ld, const double *gt, double *wide, void *stream);
 
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 

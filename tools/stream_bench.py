@@ -3,7 +3,7 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
-                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality]
+                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
@@ -11,6 +11,8 @@ line then also carries the rerun count, the latency of the batches that reran an
 --articulation streams with AncshPipeline(articulation=True) (the record plus the (n, K, 12) articulation block per cloud).
 --joint-states (with --articulation) streams with AncshPipeline(joint_states=True): the block is the (n, K, 20) one, one more launch a step.
 --fit-quality streams with AncshPipeline(fit_quality=True): the record is the (n, K, 39) wide one, one more launch a step.
+--ground-truth streams with AncshPipeline(ground_truth=True): every batch carries a (32, K, 19) ground truth in, the record comes back 12
+columns wider (the errors against it, ancsh_gt_error_rec), one more launch a step.
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 --joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
 head) and submits (n_raw, 3) xyz clouds: no label column crosses to the device.
@@ -43,6 +45,8 @@ def main():
     ap.add_argument("--articulation", action="store_true", help="stream with AncshPipeline(articulation=True) and retire the blocks too")
     ap.add_argument("--joint-states", action="store_true", help="with --articulation: AncshPipeline(joint_states=True), the (n, K, 20) block")
     ap.add_argument("--fit-quality", action="store_true", help="AncshPipeline(fit_quality=True): the streamed record is the (n, K, 39) wide one")
+    ap.add_argument("--ground-truth", action="store_true",
+                    help="AncshPipeline(ground_truth=True): a ground truth per batch in, the streamed record 12 error columns wider")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
                     help="predicted: the joint association from the network's index head; (n_raw, 3) xyz clouds are submitted")
@@ -66,6 +70,14 @@ def main():
     if args.overflow_every:
         for k in range(0, len(batches), args.overflow_every):
             batches[k][1][k % B] = 1.0e6
+    gts = None
+    if args.ground_truth:        # a rotation about z, a scale, translations and box extents per part: the launch's cost does not depend on them
+        a = rs.uniform(0, 2 * np.pi, (len(batches), B, K))
+        z, o = np.zeros_like(a), np.ones_like(a)
+        R = np.stack([np.cos(a), -np.sin(a), z, np.sin(a), np.cos(a), z, z, z, o], -1)
+        gts = np.concatenate([R, rs.uniform(0.5, 1.5, a.shape + (1,)), rs.uniform(-0.3, 0.3, a.shape + (3,)), rs.uniform(0.3, 0.9, a.shape + (3,)),
+                              rs.uniform(-0.3, 0.3, a.shape + (3,))], -1)
+    with_gt = (lambda k, c, nf: (c, nf, gts[k])) if args.ground_truth else (lambda k, c, nf: (c, nf))
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
 
     # streaming
@@ -73,18 +85,19 @@ def main():
     mem0 = torch.cuda.mem_get_info(dev)[0]
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
                          range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
-                         joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality).prepare()
+                         joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality,
+                         ground_truth=args.ground_truth).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
-    for _ in pipe.stream_batches(batches):          # warm-up: every slot replayed with real input
+    for _ in pipe.stream_batches([with_gt(k, c, nf) for k, (c, nf) in enumerate(batches)]):          # warm-up: every slot replayed with real input
         pass
     torch.cuda.synchronize()
     t_sub, lat = {}, []
-    work = [(c, nf, (p, k)) for p in range(args.passes) for k, (c, nf) in enumerate(batches)]
+    work = [with_gt(k, c, nf) + ((p, k),) for p in range(args.passes) for k, (c, nf) in enumerate(batches)]
 
     def timed(items):
         for it in items:
-            t_sub[it[2]] = time.perf_counter()
+            t_sub[it[-1]] = time.perf_counter()
             yield it
     t0 = time.perf_counter()
     n_out, rerun_lat, n_blocks, n_rows = 0, [], 0, 0
@@ -151,6 +164,8 @@ def main():
         line.update({"joint_states": True})
     if args.fit_quality:
         line.update({"fit_quality": True})
+    if args.ground_truth:
+        line.update({"ground_truth": True, "record_columns": int(rec.shape[2])})
     if predicted:
         line.update({"joint_source": "predicted"})
     if args.dense:
