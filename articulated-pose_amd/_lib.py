@@ -132,6 +132,14 @@ SIGNATURES = {
     # the errors against ground truth behind the record (no ABI bump, detected by its symbol): b, n, K, nres, P, ldp, npcs_nocs, npcs_mask,
     # record, ld, gt, wide, stream
     "ancsh_gt_error_rec": [_c_int] * 4 + [_vp, _c_int] + [_vp] * 3 + [_c_int] + [_vp] * 2 + [_vp],
+    # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
+    # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
+    # [joint_kind,] stream
+    **{"ancsh_pose_fit_rec" + sfx: [_c_int, _vp, _vp, _vp, _c_float, _c_int, _vp, key, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long, _vp, _c_float,
+                                    _c_int, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, key] + [_vp] * 7 + [_c_int, _vp, ctypes.c_double,
+                                    _vp, _c_int] + kind + [_vp]
+       for sfx, key, kind in (("", ctypes.c_ulonglong, []), ("_dseed", _vp, []), ("_dkey", _vp, []),
+                              ("_kind", ctypes.c_ulonglong, [_vp]), ("_dseed_kind", _vp, [_vp]), ("_dkey_kind", _vp, [_vp]))},
     "ancsh_input_sample": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "ancsh_test_losses": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "ancsh_ransac_joint_ex": [_c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, ctypes.c_ulonglong, _c_int]

@@ -533,22 +533,22 @@ __device__ __forceinline__ int compact_flagged(bool flag, int i, int n, const fl
     return base + total;
 }
 
+// Stage A's refit of problem `prob` by one 256-thread workgroup (smem: the launch's dynamic LDS, single_finish_lds(max_n) bytes).  A
+// device function of (problem index, arguments) so that two kernels can run it: ransac_single_finish_kernel below (prob = blockIdx.x)
+// and pose_lm_finish_a_kernel, whose blocks behind the LM fits take one part each.  Every branch around a barrier is block-uniform.
 template <int KM>
-__global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__restrict__ off, const float *__restrict__ src,
-                                                                   const float *__restrict__ tgt, float th, int niter,
-                                                                   const int *__restrict__ draws, KeyArg<KM> seed_arg,
-                                                                   const int *__restrict__ scores, int max_n,
-                                                                   double *__restrict__ out_model,
-                                                                   unsigned char *__restrict__ out_inliers,
-                                                                   int *__restrict__ out_best, FitExtras E) {
+__device__ __forceinline__ void ransac_single_finish_run(int prob, unsigned char *smem, const int *__restrict__ off,
+                                                         const float *__restrict__ src, const float *__restrict__ tgt, float th, int niter,
+                                                         const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                         const int *__restrict__ scores, int max_n, double *__restrict__ out_model,
+                                                         unsigned char *__restrict__ out_inliers, int *__restrict__ out_best,
+                                                         const FitExtras &E) {
     const unsigned long long seed = kernel_seed<KM>(seed_arg, 0);
     const int kbase = key_problem_base<KM>(seed_arg);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *red = (double *)smem;                       // 64 doubles
     int *wcnt = (int *)(red + 64);                      // 4 ints for compact_flagged + 4 for the tie counts
     float(*cs)[3] = (float(*)[3])(wcnt + 8);
     float(*ct)[3] = cs + max_n;
-    const int prob = blockIdx.x;
     const int r0 = off[prob], n = off[prob + 1] - r0;
     double *om = out_model + (size_t)prob * MODEL_A;
     if (n <= 0 || n > max_n) {   // empty part: the reference raises (randint(0)); report instead of dying
@@ -681,6 +681,18 @@ __global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__
             }
         }
     }
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void ransac_single_finish_kernel(const int *__restrict__ off, const float *__restrict__ src,
+                                                                   const float *__restrict__ tgt, float th, int niter,
+                                                                   const int *__restrict__ draws, KeyArg<KM> seed_arg,
+                                                                   const int *__restrict__ scores, int max_n,
+                                                                   double *__restrict__ out_model,
+                                                                   unsigned char *__restrict__ out_inliers,
+                                                                   int *__restrict__ out_best, FitExtras E) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ransac_single_finish_run<KM>(blockIdx.x, smem, off, src, tgt, th, niter, draws, seed_arg, scores, max_n, out_model, out_inliers, out_best, E);
 }
 
 // ================================ stage B ==========================================================
@@ -993,15 +1005,15 @@ __device__ __forceinline__ void ransac_joint_lm_run(const int *__restrict__ rng0
                                                     const float *__restrict__ src, const float *__restrict__ tgt,
                                                     const float *__restrict__ joint_dir, int niter,
                                                     const int *__restrict__ draws, KeyArg<KM> seed_arg,
-                                                    double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
+                                                    double *__restrict__ models, int *__restrict__ lm_stat, int chunk, int prob,
+                                                    int chunk_idx) {
     const unsigned long long seed = kernel_seed<KM>(seed_arg, 1);
     const int kbase = key_problem_base<KM>(seed_arg);
-    const int prob = blockIdx.y;
     const int a0 = rng0[prob * 2], n0 = rng0[prob * 2 + 1] - a0;
     const int a1 = rng1[prob * 2], n1 = rng1[prob * 2 + 1] - a1;
     if (n0 <= 0 || n1 <= 0) return;
-    const int c1 = min(niter, (int)(blockIdx.x + 1) * chunk);
-    int next = blockIdx.x * chunk;              // wave-uniform: first hypothesis of the chunk not yet handed out
+    const int c1 = min(niter, (chunk_idx + 1) * chunk);
+    int next = chunk_idx * chunk;               // wave-uniform: first hypothesis of the chunk not yet handed out
     HypProblemT<PRISM> P;
     if constexpr (!PRISM) {
         P.J[0] = joint_dir[prob * 3]; P.J[1] = joint_dir[prob * 3 + 1]; P.J[2] = joint_dir[prob * 3 + 2];
@@ -1053,7 +1065,7 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_kernel(const int *__restri
                                                              const float *__restrict__ joint_dir, int niter,
                                                              const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                              double *__restrict__ models, int *__restrict__ lm_stat, int chunk) {
-    ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
+    ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk, blockIdx.y, blockIdx.x);
 }
 
 template <int KM>
@@ -1063,8 +1075,77 @@ __global__ __launch_bounds__(64) void ransac_joint_lm_kind_kernel(const int *__r
                                                                   const int *__restrict__ draws, KeyArg<KM> seed_arg,
                                                                   double *__restrict__ models, int *__restrict__ lm_stat, int chunk,
                                                                   const int *__restrict__ joint_kind) {
-    if (joint_kind[blockIdx.y] != 0) ransac_joint_lm_run<KM, true>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
-    else ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk);
+    if (joint_kind[blockIdx.y] != 0) ransac_joint_lm_run<KM, true>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk, blockIdx.y, blockIdx.x);
+    else ransac_joint_lm_run<KM, false>(rng0, rng1, src, tgt, joint_dir, niter, draws, seed_arg, models, lm_stat, chunk, blockIdx.y, blockIdx.x);
+}
+
+// ---- joint LM fits || stage A's refit in ONE launch ------------------------------------------------------------------------
+// The LM launch is 64 waves of which all but one are gone after a fifth of its duration (the longest MINPACK trajectory sets it), and
+// with few hardware queues a batch's launches run one after another on ONE in-order queue: whatever follows the LM kernel waits for its
+// tail with the chip almost empty.  Stage A's refit (one 256-thread workgroup per part, indifferent to occupancy) shares nothing with
+// stage B but the partition, so it rides in the same grid instead of holding the queue for a launch of its own:
+//   blocks [0, n_lm)               : four waves, one LM chunk each -- chunk_id = blockIdx.x * 4 + wave, (prob, chunk in problem) =
+//                                    (chunk_id / chunks_per_prob, chunk_id % chunks_per_prob); a wave past the last chunk returns.  The
+//                                    LM code has no workgroup barrier and no LDS: waves are as independent as in ransac_joint_lm_kernel,
+//                                    and a fit is a function of its own draw only, so the bytes are that kernel's;
+//   blocks [n_lm, n_lm + nprob_a)  : ransac_single_finish_run of part blockIdx.x - n_lm (its scores come from the scoring launch that
+//                                    precedes this one on the stream).
+// LM blocks come first so the long pole starts at once.  The role test reads blockIdx.x alone: block-uniform, so the refit's barriers
+// are safe.  Dynamic LDS is the refit's (the LM blocks ignore it).  Registers are the LM code's (one wave per SIMD either way).
+struct LmArgs {
+    const int *rng0, *rng1;
+    const float *joint_dir;
+    int niter;
+    const int *draws;
+    double *models;
+    int *lm_stat;
+    int chunk, chunks_per_prob, n_chunks, n_lm;
+};
+struct FinishAArgs {
+    const int *off;
+    float th;
+    int niter;
+    const int *draws, *scores;
+    int max_n;
+    double *out_model;
+    unsigned char *out_inliers;
+    int *out_best;
+};
+
+template <int KM, bool KIND>
+__device__ __forceinline__ void pose_lm_finish_a_run(unsigned char *smem, const float *__restrict__ src, const float *__restrict__ tgt,
+                                                     const LmArgs &L, KeyArg<KM> seed_b, const int *__restrict__ joint_kind,
+                                                     const FinishAArgs &A, KeyArg<KM> seed_a, const FitExtras &EA) {
+    if ((int)blockIdx.x >= L.n_lm) {                   // block-uniform
+        ransac_single_finish_run<KM>((int)blockIdx.x - L.n_lm, smem, A.off, src, tgt, A.th, A.niter, A.draws, seed_a, A.scores, A.max_n,
+                                     A.out_model, A.out_inliers, A.out_best, EA);
+        return;
+    }
+    const int chunk_id = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
+    if (chunk_id >= L.n_chunks) return;
+    const int prob = chunk_id / L.chunks_per_prob, chunk_idx = chunk_id - prob * L.chunks_per_prob;
+    if constexpr (KIND) {
+        if (joint_kind[prob] != 0) {
+            ransac_joint_lm_run<KM, true>(L.rng0, L.rng1, src, tgt, L.joint_dir, L.niter, L.draws, seed_b, L.models, L.lm_stat, L.chunk, prob, chunk_idx);
+            return;
+        }
+    }
+    ransac_joint_lm_run<KM, false>(L.rng0, L.rng1, src, tgt, L.joint_dir, L.niter, L.draws, seed_b, L.models, L.lm_stat, L.chunk, prob, chunk_idx);
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void pose_lm_finish_a_kernel(const float *__restrict__ src, const float *__restrict__ tgt, LmArgs L,
+                                                               KeyArg<KM> seed_b, FinishAArgs A, KeyArg<KM> seed_a, FitExtras EA) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    pose_lm_finish_a_run<KM, false>(smem, src, tgt, L, seed_b, nullptr, A, seed_a, EA);
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void pose_lm_finish_a_kind_kernel(const float *__restrict__ src, const float *__restrict__ tgt, LmArgs L,
+                                                                    KeyArg<KM> seed_b, const int *__restrict__ joint_kind, FinishAArgs A,
+                                                                    KeyArg<KM> seed_a, FitExtras EA) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    pose_lm_finish_a_run<KM, true>(smem, src, tgt, L, seed_b, joint_kind, A, seed_a, EA);
 }
 
 // ---- lane-group-cooperative LM --------------------------------------------------------------------------------------------
@@ -2216,33 +2297,57 @@ extern "C" long ancsh_ransac_single_quads_floats(long rows, int nprob) {
     return 24 * single_quads_needed(rows, nprob);
 }
 
+// Stage A's argument checks, all of them before any launch (pose_fit_impl runs both stages' checks first).  nprob == 0 passes after the
+// size checks: the call is then a no-op.
+static int ransac_single_check(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter, int max_n,
+                               double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
+                               long rows) {
+    ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_single: bad sizes nprob=%d niter=%d max_n=%d", nprob, niter, max_n);
+    ANCSH_REQUIRE(max_n <= 6144, "ransac_single: max_n %d > 6144 (refit keeps the inliers in LDS)", max_n);
+    if (nprob == 0) return ANCSH_OK;
+    ANCSH_REQUIRE(off && src && tgt && out_model && out_inliers && out_best && scratch_scores, "ransac_single: null pointer");
+    ANCSH_REQUIRE(inlier_th > 0.f, "ransac_single: inlier_th must be positive");
+    const float th_sq = sq_threshold_f32(inlier_th);
+    if (scratch_quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
+        ANCSH_REQUIRE(rows >= 0 && rows < (1L << 30), "ransac_single_ex: rows=%ld out of range", rows);
+        ANCSH_REQUIRE((((uintptr_t)scratch_quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
+    }
+    return ANCSH_OK;
+}
+
+// th_sq: the squared threshold (the kernels compare squared residuals)
+template <int KM>
+static void ransac_single_launch_score(int nprob, const int *off, const float *src, const float *tgt, float th_sq, int niter,
+                                       const int *draws, KeyArg<KM> seed, int max_n, int *scratch_scores, float *scratch_quads, long rows,
+                                       hipStream_t st) {
+    // the scalar-register kernel counts inliers as clamp((th_sq - s) * 2^126): exact while th_sq - s cannot be denormal, i.e. for any
+    // threshold a fit would use; a squared threshold below 2^-100 or >= 4 (th_sq * 2^126 must stay finite) takes the compare-based kernel
+    // (same scores by construction)
+    if (scratch_quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
+        const int cap = (int)single_quads_needed(rows, nprob);
+        hipLaunchKernelGGL(soa_quads_kernel, dim3((max_n + 7 + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, scratch_quads, cap);
+        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
+                           (const float *)scratch_quads, cap, th_sq, niter, draws, seed, scratch_scores);
+    } else {
+        hipLaunchKernelGGL(ransac_single_score_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, th_sq,
+                           niter, draws, seed, scratch_scores);
+    }
+}
+
+static size_t single_finish_lds(int max_n) { return 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float); }
+
 template <int KM>
 static int ransac_single_impl(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
                               const int *draws, KeyArg<KM> seed, int max_n, double *out_model,
                               unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
                               FitExtras E, void *stream) {
-    ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_single: bad sizes nprob=%d niter=%d max_n=%d", nprob, niter, max_n);
-    ANCSH_REQUIRE(max_n <= 6144, "ransac_single: max_n %d > 6144 (refit keeps the inliers in LDS)", max_n);
+    if (int rc = ransac_single_check(nprob, off, src, tgt, inlier_th, niter, max_n, out_model, out_inliers, out_best, scratch_scores,
+                                     scratch_quads, rows)) return rc;
     if (nprob == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(off && src && tgt && out_model && out_inliers && out_best && scratch_scores, "ransac_single: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    ANCSH_REQUIRE(inlier_th > 0.f, "ransac_single: inlier_th must be positive");
     inlier_th = sq_threshold_f32(inlier_th);     // the kernels compare squared residuals
-    // the scalar-register kernel counts inliers as clamp((th_sq - s) * 2^126): exact while th_sq - s cannot be denormal, i.e. for any
-    // threshold a fit would use; a squared threshold below 2^-100 or >= 4 (th_sq * 2^126 must stay finite) takes the compare-based kernel
-    // (same scores by construction)
-    if (scratch_quads && inlier_th >= 0x1p-100f && inlier_th < 4.0f) {
-        ANCSH_REQUIRE(rows >= 0 && rows < (1L << 30), "ransac_single_ex: rows=%ld out of range", rows);
-        ANCSH_REQUIRE((((uintptr_t)scratch_quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
-        const int cap = (int)single_quads_needed(rows, nprob);
-        hipLaunchKernelGGL(soa_quads_kernel, dim3((max_n + 7 + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, scratch_quads, cap);
-        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
-                           (const float *)scratch_quads, cap, inlier_th, niter, draws, seed, scratch_scores);
-    } else {
-        hipLaunchKernelGGL(ransac_single_score_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, inlier_th,
-                           niter, draws, seed, scratch_scores);
-    }
-    const size_t lds = 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float);
+    ransac_single_launch_score<KM>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, scratch_scores, scratch_quads, rows, st);
+    const size_t lds = single_finish_lds(max_n);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(ransac_single_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
                        scratch_scores, max_n, out_model, out_inliers, out_best, E);
@@ -2280,20 +2385,55 @@ extern "C" int ancsh_ransac_single_rec(int nprob, const int *off, const float *s
                                      scratch_scores, scratch_quads, rows, E, stream);
 }
 
-template <int KM>
-static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                             const float *joint_dir, double inlier_th, int niter, const int *draws,
-                             KeyArg<KM> seed, int max_n, double *out_model, unsigned char *out_inliers,
-                             int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                             int *lm_stat, int lm_schedule, FitExtras E, void *stream, const int *joint_kind = nullptr) {
+// Stage B's argument checks, all of them before any launch.  nprob == 0 passes after the size checks.
+static int ransac_joint_check(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+                              double inlier_th, int niter, int max_n, double *out_model, unsigned char *out_inliers, int *out_best,
+                              double *out_score, double *scratch_scores, double *scratch_models, int lm_schedule) {
     ANCSH_REQUIRE(lm_schedule >= ANCSH_LM_AUTO && lm_schedule <= ANCSH_LM_LATENCY, "ransac_joint: unknown lm_schedule %d", lm_schedule);
     ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_joint: bad sizes");
     ANCSH_REQUIRE(max_n <= 3072, "ransac_joint: max_n %d > 3072 (refit keeps both parts' inliers in LDS)", max_n);
     if (nprob == 0) return ANCSH_OK;
     ANCSH_REQUIRE(rng0 && rng1 && src && tgt && joint_dir && out_model && out_inliers && out_best && out_score &&
                       scratch_scores && scratch_models, "ransac_joint: null pointer");
-    hipStream_t st = (hipStream_t)stream;
     ANCSH_REQUIRE(inlier_th > 0.0, "ransac_joint: inlier_th must be positive");
+    return ANCSH_OK;
+}
+
+static int lm_chunk(int nprob, int niter) { return (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK; }
+
+// what follows the LM fits: models, verification, refit (th_sq: the squared threshold)
+template <int KM>
+static void ransac_joint_launch_tail(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                                     const float *joint_dir, double th_sq, int niter, const int *draws, KeyArg<KM> seed, int max_n,
+                                     double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
+                                     double *scratch_scores, double *scratch_models, const FitExtras &E, hipStream_t st,
+                                     const int *joint_kind) {
+    hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, dim3((niter + 63) / 64, nprob), dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed,
+                       scratch_models);
+    hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, th_sq,
+                       niter, scratch_models, scratch_scores);
+    const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
+    if (joint_kind) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(ransac_joint_finish_kind_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, th_sq,
+                           niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E, joint_kind);
+        return;
+    }
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ransac_joint_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, th_sq,
+                       niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
+}
+
+template <int KM>
+static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+                             const float *joint_dir, double inlier_th, int niter, const int *draws,
+                             KeyArg<KM> seed, int max_n, double *out_model, unsigned char *out_inliers,
+                             int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
+                             int *lm_stat, int lm_schedule, FitExtras E, void *stream, const int *joint_kind = nullptr) {
+    if (int rc = ransac_joint_check(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, max_n, out_model, out_inliers, out_best,
+                                    out_score, scratch_scores, scratch_models, lm_schedule)) return rc;
+    if (nprob == 0) return ANCSH_OK;
+    hipStream_t st = (hipStream_t)stream;
     inlier_th = sq_threshold_f64(inlier_th);      // the kernels compare squared residuals
     const dim3 per_hyp((niter + 63) / 64, nprob);
     hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
@@ -2317,7 +2457,7 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
             hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<KM>, grid, dim3(64), 0, st,
                                rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
     } else {
-        const int chunk = (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK;
+        const int chunk = lm_chunk(nprob, niter);
         if (joint_kind)
             hipLaunchKernelGGL(ransac_joint_lm_kind_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
                                joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk, joint_kind);
@@ -2325,19 +2465,8 @@ static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const 
             hipLaunchKernelGGL(ransac_joint_lm_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
                                joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
     }
-    hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_models);
-    hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, inlier_th,
-                       niter, scratch_models, scratch_scores);
-    const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
-    if (joint_kind) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(ransac_joint_finish_kind_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
-                           niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E, joint_kind);
-        return check_launch("ransac_joint");
-    }
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_joint_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, inlier_th,
-                       niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
+    ransac_joint_launch_tail<KM>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
+                                 out_score, scratch_scores, scratch_models, E, st, joint_kind);
     return check_launch("ransac_joint");
 }
 
@@ -2494,6 +2623,146 @@ extern "C" int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, cons
                                        out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
                                        E, stream, joint_kind);
 }
+
+// ---- the whole fit in one call: both stages' launches on one stream, the LM fits and stage A's refit in ONE kernel -------------------
+// soa_quads, score_sreg, joint_init, pose_lm_finish_a (LM fits || stage A refit), joint_model, joint_verify, joint_finish: seven launches
+// where ancsh_ransac_joint_rec* + ancsh_ransac_single_rec* issue eight, and the bytes of those two calls.  Every argument check of both
+// runs before anything is launched.  A stage without problems, and the eight-lane schedule (ANCSH_LM_LATENCY: another LM kernel), take
+// the existing launches.
+template <int KM>
+static int pose_fit_impl(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+                         const int *draws_a, KeyArg<KM> seed_a, int max_n, double *out_model_a, unsigned char *out_inliers_a,
+                         int *out_best_a, int *scratch_scores_a, float *scratch_quads, long rows, const FitExtras &EA, int nprob_b,
+                         const int *rng0, const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b,
+                         KeyArg<KM> seed_b, double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b,
+                         double *scratch_scores_b, double *scratch_models_b, int *lm_stat, int lm_schedule, const FitExtras &EB,
+                         const int *joint_kind, void *stream) {
+    if (int rc = ransac_single_check(nprob_a, off, src, tgt, inlier_th_a, niter_a, max_n, out_model_a, out_inliers_a, out_best_a,
+                                     scratch_scores_a, scratch_quads, rows)) return rc;
+    if (int rc = ransac_joint_check(nprob_b, rng0, rng1, src, tgt, joint_dir, inlier_th_b, niter_b, max_n, out_model_b, out_inliers_b,
+                                    out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_schedule)) return rc;
+    if (nprob_a == 0 && nprob_b == 0) return ANCSH_OK;
+    if (nprob_a == 0 || nprob_b == 0 || lm_schedule == ANCSH_LM_LATENCY) {        // stage B first, as PoseSolver.solve issues the two calls
+        if (int rc = ransac_joint_impl<KM>(nprob_b, rng0, rng1, src, tgt, joint_dir, inlier_th_b, niter_b, draws_b, seed_b, max_n, out_model_b,
+                                           out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, EB,
+                                           stream, joint_kind)) return rc;
+        return ransac_single_impl<KM>(nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, seed_a, max_n, out_model_a, out_inliers_a,
+                                      out_best_a, scratch_scores_a, scratch_quads, rows, EA, stream);
+    }
+    LmArgs L;
+    L.chunk = lm_chunk(nprob_b, niter_b);                               // the same rule as the LM launch of its own
+    L.chunks_per_prob = (niter_b + L.chunk - 1) / L.chunk;
+    const long n_chunks = (long)L.chunks_per_prob * nprob_b;
+    ANCSH_REQUIRE((n_chunks + 3) / 4 + nprob_a < (1L << 31), "pose_fit: %ld LM chunks + %d parts exceed one grid", n_chunks, nprob_a);
+    hipStream_t st = (hipStream_t)stream;                               // every check has passed: nothing above launches
+    const float th_a = sq_threshold_f32(inlier_th_a);
+    const double th_b = sq_threshold_f64(inlier_th_b);
+    ransac_single_launch_score<KM>(nprob_a, off, src, tgt, th_a, niter_a, draws_a, seed_a, max_n, scratch_scores_a, scratch_quads, rows, st);
+    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, dim3((niter_b + 63) / 64, nprob_b), dim3(64), 0, st, rng0, rng1, src, tgt, niter_b, draws_b,
+                       seed_b, scratch_scores_b, scratch_models_b);
+    L.rng0 = rng0; L.rng1 = rng1; L.joint_dir = joint_dir; L.niter = niter_b; L.draws = draws_b; L.models = scratch_models_b; L.lm_stat = lm_stat;
+    L.n_chunks = (int)n_chunks;
+    L.n_lm = (int)((n_chunks + 3) / 4);                                 // four waves, one chunk each, per LM block
+    FinishAArgs A;
+    A.off = off; A.th = th_a; A.niter = niter_a; A.draws = draws_a; A.scores = scratch_scores_a; A.max_n = max_n;
+    A.out_model = out_model_a; A.out_inliers = out_inliers_a; A.out_best = out_best_a;
+    const size_t lds = single_finish_lds(max_n);
+    const dim3 grid(L.n_lm + nprob_a);
+    if (joint_kind) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)pose_lm_finish_a_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(pose_lm_finish_a_kind_kernel<KM>, grid, dim3(256), lds, st, src, tgt, L, seed_b, joint_kind, A, seed_a, EA);
+    } else {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)pose_lm_finish_a_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(pose_lm_finish_a_kernel<KM>, grid, dim3(256), lds, st, src, tgt, L, seed_b, A, seed_a, EA);
+    }
+    ransac_joint_launch_tail<KM>(nprob_b, rng0, rng1, src, tgt, joint_dir, th_b, niter_b, draws_b, seed_b, max_n, out_model_b, out_inliers_b,
+                                 out_best_b, out_score_b, scratch_scores_b, scratch_models_b, EB, st, joint_kind);
+    return check_launch("pose_fit");
+}
+
+// both stages' extras (record columns, tie counts) from the entries' arguments: ancsh_ransac_single_rec*'s and ancsh_ransac_joint_rec*'s rules
+static int pose_fit_extras(const char *who, int nprob_a, int nprob_b, double *record, int K, int *tie_a, float inlier_th_a, float tie_window_a,
+                           int *tie_b, double inlier_th_b, double tie_window_b, const int *draws_b, unsigned long long seed_b, FitExtras &EA,
+                           FitExtras &EB) {
+    EA = no_extras(); EB = no_extras();
+    // a stage without problems writes nothing: its record geometry and window are not examined (nprob_b == 0 is how a K = 1 caller gets here)
+    if (nprob_a != 0)
+        if (int rc = make_extras(who, nprob_a, record, K, 1, tie_a, (double)inlier_th_a, (double)tie_window_a, EA)) return rc;
+    if (nprob_b != 0)
+        if (int rc = make_extras(who, nprob_b, record, K, 2, tie_b, inlier_th_b, tie_window_b, EB)) return rc;
+    EB.draws = draws_b; EB.seed = seed_b;
+    return ANCSH_OK;
+}
+
+#define POSE_FIT_PARAMS(KEY_T)                                                                                                             \
+    int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a, const int *draws_a, KEY_T key_a,     \
+        int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a, int *scratch_scores_a, float *scratch_quads,        \
+        long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1, const float *joint_dir,            \
+        double inlier_th_b, int niter_b, const int *draws_b, KEY_T key_b, double *out_model_b, unsigned char *out_inliers_b,               \
+        int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat, int lm_schedule,           \
+        int *tie_stats_b, double tie_window_b, double *record, int K
+#define POSE_FIT_CALL(KM, KA, KB, KIND)                                                                                                    \
+    pose_fit_impl<KM>(nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, KA, max_n, out_model_a, out_inliers_a, out_best_a,            \
+                      scratch_scores_a, scratch_quads, rows, EA, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, KB,        \
+                      out_model_b, out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, EB,   \
+                      KIND, stream)
+
+static int pose_fit_rec(const char *who, POSE_FIT_PARAMS(unsigned long long), const int *joint_kind, void *stream) {
+    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
+    FitExtras EA, EB;
+    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
+                                 draws_b, key_b, EA, EB)) return rc;
+    return POSE_FIT_CALL(KEY_VALUE, key_a, key_b, joint_kind);
+}
+
+static int pose_fit_rec_dseed(const char *who, POSE_FIT_PARAMS(const unsigned long long *), const int *joint_kind, void *stream) {
+    ANCSH_REQUIRE((key_a || nprob_a <= 0) && (key_b || nprob_b <= 0), "%s: null seed pointer", who);
+    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
+    FitExtras EA, EB;
+    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
+                                 draws_b, (unsigned long long)(uintptr_t)key_b, EA, EB)) return rc;
+    return POSE_FIT_CALL(KEY_DSEED, (unsigned long long)(uintptr_t)key_a, (unsigned long long)(uintptr_t)key_b, joint_kind);
+}
+
+static int pose_fit_rec_dkey(const char *who, POSE_FIT_PARAMS(const ancsh_stream_key *), const int *joint_kind, void *stream) {
+    ANCSH_REQUIRE((key_a || nprob_a <= 0) && (key_b || nprob_b <= 0), "%s: null key pointer", who);
+    ANCSH_REQUIRE(K >= 1 && nprob_a >= 0 && nprob_a % K == 0 && nprob_a < (1 << 20), "%s: nprob_a (%d) must be a multiple of K (%d) below 2^20", who,
+                  nprob_a, K);
+    ANCSH_REQUIRE(nprob_b == 0 || (K >= 2 && nprob_b > 0 && nprob_b % (K - 1) == 0 && nprob_b < (1 << 20)),
+                  "%s: nprob_b (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", who, nprob_b, K);
+    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
+    FitExtras EA, EB;
+    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
+                                 draws_b, (unsigned long long)(uintptr_t)key_b, EA, EB)) return rc;
+    return POSE_FIT_CALL(KEY_DKEY, (DKey{key_a, K}), (DKey{key_b, K - 1}), joint_kind);
+}
+
+#define POSE_FIT_ARGS                                                                                                                      \
+    nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, key_a, max_n, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,          \
+        scratch_quads, rows, tie_stats_a, tie_window_a, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, key_b, out_model_b,  \
+        out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b, record, K
+
+extern "C" int ancsh_pose_fit_rec(POSE_FIT_PARAMS(unsigned long long), void *stream) {
+    return pose_fit_rec("pose_fit_rec", POSE_FIT_ARGS, nullptr, stream);
+}
+extern "C" int ancsh_pose_fit_rec_dseed(POSE_FIT_PARAMS(const unsigned long long *), void *stream) {
+    return pose_fit_rec_dseed("pose_fit_rec_dseed", POSE_FIT_ARGS, nullptr, stream);
+}
+extern "C" int ancsh_pose_fit_rec_dkey(POSE_FIT_PARAMS(const ancsh_stream_key *), void *stream) {
+    return pose_fit_rec_dkey("pose_fit_rec_dkey", POSE_FIT_ARGS, nullptr, stream);
+}
+extern "C" int ancsh_pose_fit_rec_kind(POSE_FIT_PARAMS(unsigned long long), const int *joint_kind, void *stream) {
+    return pose_fit_rec("pose_fit_rec_kind", POSE_FIT_ARGS, joint_kind, stream);
+}
+extern "C" int ancsh_pose_fit_rec_dseed_kind(POSE_FIT_PARAMS(const unsigned long long *), const int *joint_kind, void *stream) {
+    return pose_fit_rec_dseed("pose_fit_rec_dseed_kind", POSE_FIT_ARGS, joint_kind, stream);
+}
+extern "C" int ancsh_pose_fit_rec_dkey_kind(POSE_FIT_PARAMS(const ancsh_stream_key *), const int *joint_kind, void *stream) {
+    return pose_fit_rec_dkey("pose_fit_rec_dkey_kind", POSE_FIT_ARGS, joint_kind, stream);
+}
+#undef POSE_FIT_PARAMS
+#undef POSE_FIT_CALL
+#undef POSE_FIT_ARGS
 
 extern "C" int ancsh_umeyama(int nprob, const int *off, const float *src, const float *tgt, double *out, void *stream) {
     ANCSH_REQUIRE(nprob >= 0, "umeyama: negative nprob");

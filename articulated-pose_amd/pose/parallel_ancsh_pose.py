@@ -174,6 +174,48 @@ def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=
     return dict(model=model, inliers=inl, best=best, score=score, lm_stat=stat, hyp_models=mo, hyp_scores=sc, tie=tie, _keep=(d, joint_kind))
 
 
+def pose_fit_batch(off, rng0, rng1, src, tgt, joint_dir, inlier_th, niter_a, niter_b, draws_a=None, draws_b=None, seed=0, max_n=None,
+                   want_lm_stat=False, lm_schedule="auto", record=None, K=0, tie_window=None, seed_dev=None, key_dev=None, joint_kind=None):
+    """ransac_joint_batch + ransac_single_batch of one batch in ONE ABI call (ancsh_pose_fit_rec*, include/ancsh_hip.h): stage B's LM
+    fits and stage A's refit share a launch, seven launches instead of eight, every output byte the same.  Arguments as the two
+    functions'; `seed` is stage A's key (stage B takes seed + 1, as PoseSolver.solve passes it).  -> (a, b): the two functions' dicts."""
+    dev = src.device
+    npa, npb = off.numel() - 1, rng0.shape[0]
+    rows = src.shape[0]
+    max_n = int(max_n or rows)
+    E = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    model_a, inl_a, best_a, scores_a = E((npa, 13), torch.float64), E((rows,), torch.uint8), E((npa, 2), torch.int32), E((npa * niter_a,), torch.int32)
+    quads = E((_lib.lib().ancsh_ransac_single_quads_floats(rows, npa),), torch.float32)
+    model_b, inl_b, best_b, score_b = E((npb, 26), torch.float64), E((npb, 2, max_n), torch.uint8), E((npb,), torch.int32), E((npb,), torch.float64)
+    sc_b, mo_b = E((npb * niter_b,), torch.float64), E((npb * niter_b, 26), torch.float64)
+    stat = E((npb, niter_b, 2), torch.int32) if want_lm_stat else None
+    tie_a = E((npa, 2), torch.int32) if tie_window is not None else None
+    tie_b = E((npb, 2), torch.int32) if tie_window is not None else None
+    da = None if draws_a is None else _i32(draws_a, dev)
+    db = None if draws_b is None else _i32(draws_b, dev)
+    if da is not None and da.numel() != npa * niter_a * 3:
+        raise ValueError("draws_a must have shape (nprob_a, niter_a, 3)")
+    if db is not None and db.numel() != npb * niter_b * 6:
+        raise ValueError("draws_b must have shape (nprob_b, niter_b, 6)")
+    if joint_kind is not None and (joint_kind.dtype != torch.int32 or joint_kind.numel() != npb or not joint_kind.is_contiguous()):
+        raise ValueError("joint_kind must be a contiguous int32 tensor of %d entries (one per problem)" % npb)
+    if key_dev is not None:
+        name, key_a, key_b = "ancsh_pose_fit_rec_dkey", _lib.ptr(key_dev), _lib.ptr(key_dev)
+    elif seed_dev is not None:
+        name, key_a, key_b = "ancsh_pose_fit_rec_dseed", _lib.ptr(seed_dev), _lib.ptr(seed_dev)
+    else:
+        name, key_a, key_b = "ancsh_pose_fit_rec", int(seed), int(seed) + 1
+    _lib.call(name + ("_kind" if joint_kind is not None else ""),
+              npa, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter_a), _lib.ptr(da), key_a, max_n, _lib.ptr(model_a),
+              _lib.ptr(inl_a), _lib.ptr(best_a), _lib.ptr(scores_a), _lib.ptr(quads), rows, _lib.ptr(tie_a), float(tie_window or 0.0),
+              npb, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(joint_dir), float(inlier_th), int(niter_b), _lib.ptr(db), key_b, _lib.ptr(model_b),
+              _lib.ptr(inl_b), _lib.ptr(best_b), _lib.ptr(score_b), _lib.ptr(sc_b), _lib.ptr(mo_b), _lib.ptr(stat), LM_SCHEDULES[lm_schedule],
+              _lib.ptr(tie_b), float(tie_window or 0.0), _lib.ptr(record), int(K), *([_lib.ptr(joint_kind)] if joint_kind is not None else []))
+    return (dict(model=model_a, inliers=inl_a, best=best_a, scores=scores_a.view(npa, niter_a), tie=tie_a, _keep=(da, scores_a, quads)),
+            dict(model=model_b, inliers=inl_b, best=best_b, score=score_b, lm_stat=stat, hyp_models=mo_b, hyp_scores=sc_b, tie=tie_b,
+                 _keep=(db, joint_kind)))
+
+
 def draws_from_seed(seed, counts, niter_a, niter_b):
     """Replay np.random.seed(seed) + the reference's randint call order for ONE cloud
     (stage A parts 0..K-1, then joints 1..K-1: evaluation/parallel_ancsh_pose.py:38,110-111).
@@ -211,6 +253,8 @@ class PoseSolver(object):
         (include/ancsh_hip.h, ancsh_ransac_single_rec; what the counts did and did not predict: profiles/r06_pose_tie_rate_K3.txt)
     A part with no predicted points gives NaN rows (the reference raises inside randint)."""
 
+    fused_launch = True       # solve(): both stages in one ABI call, LM fits and stage A's refit in one launch (False: the two calls)
+
     def __init__(self, num_parts, inlier_th=0.1, niter_a=10000, niter_b=200, device="cuda:0", want_lm_stat=False,
                  max_part_points=None, lm_schedule="auto", tie_window=TIE_WINDOW, joint_types=None):
         # joint_types: None (every joint revolute, objective_eval :56-68), "revolute" / "prismatic" for all joints, or K - 1 of them
@@ -242,11 +286,13 @@ class PoseSolver(object):
 
     def solve(self, P, nocs_pred, mask_pred, joint_axis_per_point, joint_cls=None, draws_a=None, draws_b=None, seed=0, seed_dev=None,
               key_dev=None, joint_index=None, fit_quality=False, ground_truth=None):
-        """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and it is the
-        latency-bound half (64 waves for 1.6 ms: MINPACK's longest trajectory), so it is ISSUED FIRST: its LM kernel then runs
-        under the full-chip scoring kernel of other batches in flight, and a batch ends with 0.3 ms of stage A instead of idling
-        the chip through the LM tail (what a short run's drain is made of).  Same results as A-then-B: the stages share nothing
-        but the partition.
+        """Both stages of a batch.  The joint fit (stage B) only needs the partition, not the per-part fits, and its LM kernel is the
+        latency-bound launch (64 waves for 1.6 ms: MINPACK's longest trajectory, all but one wave gone after a fifth of it).  With
+        the lane-per-fit LM schedule both stages go out in ONE call (pose_fit_batch, ancsh_pose_fit_rec*): stage A's scoring first,
+        then stage A's refit INSIDE the LM launch -- on an in-order hardware queue nothing else can overlap the LM tail -- and the
+        batch ends with stage B's model / verify / refit launches.  With the eight-lane schedule ("latency"), or K = 1, or
+        PoseSolver.fused_launch = False, the two calls of before: stage B issued first, then stage A.  Same bytes either way: the
+        stages share nothing but the partition.
         seed_dev: a one-element int64 device tensor holding the generator key (its uint64 bits) instead of `seed`: the kernels read
         it when they run, so a captured step draws a fresh sample stream per batch from whatever was written there last; the
         bytes equal those of seed=<that value>.
@@ -274,8 +320,12 @@ class PoseSolver(object):
             from .quality import check_fit_quality
             check_fit_quality(True, self.th)
         out = self._partition(P, nocs_pred, mask_pred)
-        self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index)
-        out = self._poison(self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev))
+        if self.fused_launch and self.K > 1 and self.lm_schedule != "latency":
+            self._fused_fits(out, joint_axis_per_point, joint_cls, draws_a, draws_b, seed, seed_dev, key_dev, joint_index)
+        else:
+            self._stage_b_fits(out, joint_axis_per_point, joint_cls, draws_b, seed, seed_dev, key_dev, joint_index)
+            self._stage_a_fits(out, draws_a, seed, seed_dev, key_dev)
+        out = self._poison(out)
         if fit_quality:
             from .quality import fit_quality_batch
             out["record_wide"] = fit_quality_batch(out, self.th)
@@ -336,6 +386,11 @@ class PoseSolver(object):
         a = ransac_single_batch(out["off"], out["_src"], out["_tgt"], self.th, self.niter_a,
                                 None if draws_a is None else _i32(draws_a, dev).reshape(B * K, self.niter_a, 3), seed, out["_max_n"],
                                 record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev)
+        return self._publish_a(out, a)
+
+    def _publish_a(self, out, a):
+        K = self.K
+        B, N = out["_shape"]
         out.update(baseline=out["record"][:, :, :13], best_a=a["best"].view(B, K, 2), inliers_a=a["inliers"].view(B, N))
         if a["tie"] is not None:
             out["tie_a"] = a["tie"].view(B, K, 2)
@@ -358,34 +413,62 @@ class PoseSolver(object):
         src, tgt, max_n = out["_src"], out["_tgt"], out["_max_n"]
         rng0, rng1 = out["_rng"]                                   # written by the partition kernel
         if K > 1:
-            axis = _f32(joint_axis_per_point, dev)
-            out["_axis"] = axis
-            jdir = torch.empty((B, K - 1, 3), dtype=torch.float32, device=dev)
-            if joint_index is not None:            # the network's association: argmax of the index head, taken by the direction kernel
-                index = _f32(joint_index, dev)
-                if index.dim() != 3 or tuple(index.shape[:2]) != (B, N):
-                    raise ValueError("joint_index must be (B, N, C) for %d clouds of %d points, got %s" % (B, N, tuple(index.shape)))
-                out["_index"] = index
-                _lib.call("ancsh_pose_joint_direction_pred", B, N, K, int(index.shape[2]), _lib.ptr(axis), _lib.ptr(index), _lib.ptr(jdir))
-            else:
-                jcls = _i32(joint_cls, dev)
-                _lib.call("ancsh_pose_joint_direction", B, N, K, _lib.ptr(axis), _lib.ptr(jcls), _lib.ptr(jdir))
+            jdir = self._joint_directions(out, joint_axis_per_point, joint_cls, joint_index)
             b = ransac_joint_batch(rng0, rng1, src, tgt, jdir.view(-1, 3), self.th, self.niter_b,
                                    None if draws_b is None else _i32(draws_b, dev).reshape(B * (K - 1), self.niter_b, 6),
                                    seed + 1, max_n, want_lm_stat=self.want_lm_stat, lm_schedule=self.lm_schedule,
                                    record=out["record"], K=K, tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev,
                                    joint_kind=self.prepare(B))
-            if self.want_lm_stat:
-                out["lm_stat"] = b["lm_stat"].view(B, K - 1, self.niter_b, 2)
-            out["nonlinear"] = out["record"][:, :, 13:]
-            if b["tie"] is not None:
-                out["tie_b"] = b["tie"].view(B, K - 1, 2)
-            out["best_b"] = b["best"].view(B, K - 1)
-            out["score_b"] = b["score"].view(B, K - 1)          # the winning hypothesis's verifier score (:186-194)
-            out["joint_direction"] = jdir
-            out["inliers_b"] = b["inliers"].view(B, K - 1, 2, max_n)
+            self._publish_b(out, b, jdir)
         else:
             out["nonlinear"] = out["record"][:, :, 13:]          # K = 1: filled by _stage_a_fits' finish kernel
+        return out
+
+    def _joint_directions(self, out, joint_axis_per_point, joint_cls, joint_index):
+        """Stage B's joint directions (K > 1): the per-joint median of the axis field under the given association -> (B, K - 1, 3)."""
+        dev, K = self.device, self.K
+        B, N = out["_shape"]
+        axis = _f32(joint_axis_per_point, dev)
+        out["_axis"] = axis
+        jdir = torch.empty((B, K - 1, 3), dtype=torch.float32, device=dev)
+        if joint_index is not None:            # the network's association: argmax of the index head, taken by the direction kernel
+            index = _f32(joint_index, dev)
+            if index.dim() != 3 or tuple(index.shape[:2]) != (B, N):
+                raise ValueError("joint_index must be (B, N, C) for %d clouds of %d points, got %s" % (B, N, tuple(index.shape)))
+            out["_index"] = index
+            _lib.call("ancsh_pose_joint_direction_pred", B, N, K, int(index.shape[2]), _lib.ptr(axis), _lib.ptr(index), _lib.ptr(jdir))
+        else:
+            jcls = _i32(joint_cls, dev)
+            _lib.call("ancsh_pose_joint_direction", B, N, K, _lib.ptr(axis), _lib.ptr(jcls), _lib.ptr(jdir))
+        return jdir
+
+    def _fused_fits(self, out, joint_axis_per_point, joint_cls, draws_a=None, draws_b=None, seed=0, seed_dev=None, key_dev=None,
+                    joint_index=None):
+        """Both stages in one ABI call (K > 1, lane-per-fit LM schedule): pose_fit_batch; the same `out` entries as the two calls."""
+        dev, K = self.device, self.K
+        B, N = out["_shape"]
+        rng0, rng1 = out["_rng"]
+        jdir = self._joint_directions(out, joint_axis_per_point, joint_cls, joint_index)
+        a, b = pose_fit_batch(out["off"], rng0, rng1, out["_src"], out["_tgt"], jdir.view(-1, 3), self.th, self.niter_a, self.niter_b,
+                              None if draws_a is None else _i32(draws_a, dev).reshape(B * K, self.niter_a, 3),
+                              None if draws_b is None else _i32(draws_b, dev).reshape(B * (K - 1), self.niter_b, 6),
+                              seed, out["_max_n"], want_lm_stat=self.want_lm_stat, lm_schedule=self.lm_schedule, record=out["record"], K=K,
+                              tie_window=self.tie_window, seed_dev=seed_dev, key_dev=key_dev, joint_kind=self.prepare(B))
+        self._publish_b(out, b, jdir)
+        return self._publish_a(out, a)
+
+    def _publish_b(self, out, b, jdir):
+        K, max_n = self.K, out["_max_n"]
+        B, N = out["_shape"]
+        if self.want_lm_stat:
+            out["lm_stat"] = b["lm_stat"].view(B, K - 1, self.niter_b, 2)
+        out["nonlinear"] = out["record"][:, :, 13:]
+        if b["tie"] is not None:
+            out["tie_b"] = b["tie"].view(B, K - 1, 2)
+        out["best_b"] = b["best"].view(B, K - 1)
+        out["score_b"] = b["score"].view(B, K - 1)          # the winning hypothesis's verifier score (:186-194)
+        out["joint_direction"] = jdir
+        out["inliers_b"] = b["inliers"].view(B, K - 1, 2, max_n)
         return out
 
 

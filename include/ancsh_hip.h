@@ -44,7 +44,8 @@ extern "C" {
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
                                  *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
-                                 *     against ground truth);
+                                 *     against ground truth), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
+                                 *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
                                  * 13: + ancsh_pose_joint_direction_pred, ancsh_pose_poison_records_pred, ancsh_input_sample_stream_xyz,
@@ -674,6 +675,69 @@ int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, const int *rng1
                                      int max_n, double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
                                      double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
                                      int *tie_stats, double tie_window, const int *joint_kind, void *stream);
+
+/* THE WHOLE FIT IN ONE CALL: ancsh_ransac_joint_rec* and ancsh_ransac_single_rec* of one batch, issued together on one stream, with
+ * stage B's LM fits and stage A's refit in ONE kernel (no ABI bump: detected by their symbols).  Why: the LM launch is 64 waves of which
+ * all but one are gone after a fifth of its duration, and with few hardware queues a batch's launches run one after another on one
+ * in-order queue -- stage A's refit (one workgroup per part, sharing nothing with stage B but the partition) then held that queue for a
+ * launch of its own.  Here it rides behind the LM blocks of the same grid.  Launches, in order: soa_quads, score_sreg (stage A scoring),
+ * joint_init, pose_lm_finish_a (LM fits || stage A refit), joint_model, joint_verify, joint_finish -- seven where the two calls issue eight.
+ *   - The arguments are the union of the two entries': the `_a` ones are ancsh_ransac_single_rec*'s (nprob_a = b * K problems, off,
+ *     inlier_th_a, niter_a, draws_a (nprob_a, niter_a, 3), key_a, outputs, scratch_scores_a, scratch_quads, rows, tie_stats_a,
+ *     tie_window_a), the `_b` ones ancsh_ransac_joint_rec*'s (nprob_b = b * (K - 1) problems, rng0 / rng1, joint_dir, inlier_th_b, niter_b,
+ *     draws_b (nprob_b, niter_b, 6), key_b, outputs, both scratch arrays, lm_stat, lm_schedule, tie_stats_b, tie_window_b); src, tgt, max_n
+ *     (<= 3072, stage B's bound), record and K are shared.  key_a / key_b: the two calls' own key arguments -- by value the pair (s, s + 1)
+ *     PoseSolver.solve passes, for _dseed / _dkey the same pointer twice (stage B adds 1 to the seed itself).
+ *   - Every output byte equals what the two calls write: the record, both models, masks, winners, scores, tie counts, lm_stat.  The LM
+ *     blocks run ransac_joint_lm_kernel's code, four chunks of hypotheses per 256-thread block (the chunk size follows the launch size as
+ *     there); the refit blocks run ransac_single_finish_kernel's code.  tests/test_pose_fused_launch_gpu.py.
+ *   - Every argument check of both entries runs before anything is launched (same messages).  nprob_a == 0 and nprob_b == 0: nothing is
+ *     launched, ANCSH_OK.  One of them 0: the other stage's existing launches.  lm_schedule == ANCSH_LM_LATENCY (the eight-lane LM
+ *     kernel): the two calls' eight launches, stage B first.  scratch_quads == NULL (or a threshold outside the scalar-register kernel's
+ *     range): one scoring launch instead of soa_quads + score_sreg, as in ancsh_ransac_single_rec.
+ *   - the _kind forms take joint_kind as ancsh_ransac_joint_rec_kind does (NULL = the form without it). */
+int ancsh_pose_fit_rec(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, unsigned long long key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, unsigned long long key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        void *stream);
+int ancsh_pose_fit_rec_dseed(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const unsigned long long * key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const unsigned long long * key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        void *stream);
+int ancsh_pose_fit_rec_dkey(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const ancsh_stream_key * key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const ancsh_stream_key * key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        void *stream);
+int ancsh_pose_fit_rec_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, unsigned long long key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, unsigned long long key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        const int *joint_kind, void *stream);
+int ancsh_pose_fit_rec_dseed_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const unsigned long long * key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const unsigned long long * key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        const int *joint_kind, void *stream);
+int ancsh_pose_fit_rec_dkey_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const ancsh_stream_key * key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0,
+        const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const ancsh_stream_key * key_b,
+        double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b,
+        double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K,
+        const int *joint_kind, void *stream);
 
 /* Batched estimateSimilarityUmeyama (lib/aligning.py:580-622; GT poses of evaluation/compute_gt_pose.py:87).
  * Problem p = rows [off[p], off[p+1]) of src/tgt.  out (nprob,32) float64: Scales(3) | Rotation(9, the

@@ -42,7 +42,7 @@ FAMILIES = [
     ("head_act", "head activations"),
     ("partition", "pose: partition / median"), ("joint_direction", "pose: partition / median"),
     ("ransac_single_score", "pose stage A: scoring"), ("ransac_single_finish", "pose stage A: refit"), ("ransac_single", "pose stage A: other"),
-    ("ransac_joint_lm", "pose stage B: LM fits"), ("ransac_joint_finish", "pose stage B: refit"), ("ransac_joint", "pose stage B: init / models"),
+    ("pose_lm_finish_a", "pose: LM fits || refit A (fused)"), ("ransac_joint_lm", "pose stage B: LM fits"), ("ransac_joint_finish", "pose stage B: refit"), ("ransac_joint", "pose stage B: init / models"),
     ("umeyama", "pose: umeyama"),
 ]
 SIMDS = 1024
@@ -113,11 +113,15 @@ def load_counters(path):
     return {k: v[0] / v[1] for k, v in work.items() if v[1] > 0}
 
 
-def account(rows, steps, trim, marker="ransac_joint_lm", work=None, clock_ghz=2.4):
+MARKERS = ("ransac_joint_lm", "pose_lm_finish_a")     # launched once per step: the LM kernel, or the fused kernel that replaces it
+
+
+def account(rows, steps, trim, marker=MARKERS, work=None, clock_ghz=2.4):
     # a kernel launched exactly once per step marks the step boundaries: the window runs from the start of one marker launch to
     # the start of a later one, inside the LAST `steps` steps of the trace (the timed region; what precedes it is set-up:
     # eager warm-up runs and graph capture), with `trim` of them dropped at both ends (pipeline fill / drain)
-    marks = sorted(r[0] for r in rows if marker in r[4])
+    marker = (marker,) if isinstance(marker, str) else tuple(marker)
+    marks = sorted(r[0] for r in rows if any(m in r[4] for m in marker))
     if len(marks) >= 8:
         if steps:
             marks = marks[-int(steps):]
