@@ -3,6 +3,7 @@ v_mfma_f32_32x32x16_bf16 (csrc/sa_bf16x3.hip).  f32 stays the arithmetic of reco
 the level's outputs agree with the f32 kernel to f32 summation noise, the whole network stays inside the 1e-4 parity bar with the
 part labels unchanged on the test clouds, and the report (max |diff|, label flips, kernel time) is written to gpurun_out/."""
 import ctypes
+import functools
 import json
 import os
 
@@ -368,9 +369,6 @@ def test_split16_forward_sweep(dev, monkeypatch, seed):
     """Seeded sweep of whole paired forwards at the experiment's highest level over ragged shapes -- K = 2 / 3 / 4, 512..2600 points (multiples of
     64 take the split-16 tail, the others fall back to the f32 tail; the SA levels and the mid-section are split-16 either way), 1..4 clouds, the
     two schemes alternating -- against the CPU oracle: labels exact, floats 1e-5."""
-    from articulated_pose_amd import pointnet_util
-    from articulated_pose_amd.network import Network
-    from articulated_pose_amd.paired import PairedNetworks
     from articulated_pose_amd.weights import synthetic_weights
     from oracle import net_oracle
     from test_network_gpu import synth_cloud
@@ -382,12 +380,21 @@ def test_split16_forward_sweep(dev, monkeypatch, seed):
     P = synth_cloud(rng, B, N)
     w_a = synthetic_weights(K, seed=30 + seed)
     w_n = synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=60 + seed)
+    wants = [net_oracle.forward(w, P, K, mixed_pred=mixed, early_split_nocs=mixed) for w, mixed in ((w_a, True), (w_n, False))]
+    _split16_forward_against(dev, monkeypatch, scheme, K, P, w_a, w_n, wants)
+
+
+def _split16_forward_against(dev, monkeypatch, scheme, K, P, w_a, w_n, wants):
+    """the paired forward of both networks at level 4 against the oracle's outputs `wants`: floats 1e-5, labels by the near-tie rule"""
+    from articulated_pose_amd import pointnet_util
+    from articulated_pose_amd.network import Network
+    from articulated_pose_amd.paired import PairedNetworks
+    B, N = P.shape[:2]
     pair = PairedNetworks([Network(K, w_a, "ancsh", dev), Network(K, w_n, "npcs", dev)])
     monkeypatch.setattr(pointnet_util, "SPLIT_SCHEME", scheme)
     monkeypatch.setattr(pointnet_util, "SA_BF16X3", 4)
     got = pair.predict(P)
-    for name, w, mixed, g in (("ancsh", w_a, True, got[0]), ("npcs", w_n, False, got[1])):
-        want = net_oracle.forward(w, P, K, mixed_pred=mixed, early_split_nocs=mixed)
+    for name, want, g in (("ancsh", wants[0], got[0]), ("npcs", wants[1], got[1])):
         gn = {k: v.cpu().numpy() for k, v in g.items()}
         err = max(float(np.abs(gn[k] - want[k]).max()) for k in want)
         assert err <= 1e-5, (scheme, K, N, B, name, err)
@@ -401,3 +408,29 @@ def test_split16_forward_sweep(dev, monkeypatch, seed):
             print("near-tie label: %s K=%d N=%d B=%d %s cloud %d point %d margin %.3e" % (scheme, K, N, B, name, b, i, margin))
             assert margin <= 2e-6, (scheme, K, N, B, name, b, i, margin)
         assert len(flipped) <= 1, (scheme, K, N, B, name, len(flipped))
+
+
+@functools.lru_cache(maxsize=None)
+def _k7_problem():
+    """K = 7, 640 points, 2 clouds, both networks and the oracle's outputs: computed once for both schemes and the redzone run, read-only"""
+    from articulated_pose_amd.weights import synthetic_weights
+    from oracle import net_oracle
+    from test_network_gpu import synth_cloud
+    K = 7
+    P = synth_cloud(np.random.RandomState(7640), 2, 640)
+    w_a = synthetic_weights(K, seed=37)
+    w_n = synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=67)
+    wants = [net_oracle.forward(w, P, K, mixed_pred=mixed, early_split_nocs=mixed) for w, mixed in ((w_a, True), (w_n, False))]
+    return K, P, w_a, w_n, wants
+
+
+@pytest.mark.parametrize("scheme", ["f16x2", "bf16x3"])
+def test_split16_forward_k7(dev, monkeypatch, scheme):
+    """K = 7: the widest head blocks the split-16 tail takes (7, 29 and 21 columns of its 32 padded ones; the 10 joint columns start at
+    column 57 of 68).  The tail does take them -- the launch is counted -- and the sweep's bars hold: floats 1e-5, labels by its near-tie rule."""
+    from articulated_pose_amd import architecture
+    calls = []
+    run = architecture.run_tail_programs_bf16x3
+    monkeypatch.setattr(architecture, "run_tail_programs_bf16x3", lambda *a, **kw: (calls.append(1), run(*a, **kw))[1])
+    _split16_forward_against(dev, monkeypatch, scheme, *_k7_problem())
+    assert len(calls) == 1

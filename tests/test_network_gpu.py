@@ -15,8 +15,12 @@ def synth_cloud(rng, b, n):
     return (c + rng.uniform(-0.45, 0.45, (b, n, 3)) * rng.uniform(0.3, 1.0, (b, 1, 3))).astype(np.float32)
 
 
+# K = 1 and 5..8 (the other half of the head kernel's switch; head blocks of the tail chain up to 29 columns wide at K = 7; K = 8, 33
+# columns, goes layer by layer) on the smallest clouds the backbone takes: SA1 samples 512 points
 @pytest.mark.parametrize("K,N,nocs_type,B", [(3, 1024, "ancsh", 3), (3, 1024, "npcs", 2), (2, 2048, "ancsh", 2),
-                                             (4, 2048, "ancsh", 2), (4, 2048, "npcs", 1), (3, 1000, "ancsh", 1), (2, 777, "npcs", 3)])
+                                             (4, 2048, "ancsh", 2), (4, 2048, "npcs", 1), (3, 1000, "ancsh", 1), (2, 777, "npcs", 3),
+                                             (1, 512, "ancsh", 2), (1, 640, "npcs", 1), (5, 512, "ancsh", 1), (6, 777, "npcs", 2),
+                                             (7, 512, "ancsh", 2), (7, 640, "npcs", 1), (8, 512, "ancsh", 1), (8, 600, "npcs", 2)])
 def test_forward_matches_oracle(dev, K, N, nocs_type, B):
     from articulated_pose_amd.network import Network
     from articulated_pose_amd.weights import synthetic_weights
@@ -295,13 +299,16 @@ def test_packed_conv_network_equals_plain_bitwise(dev):
         assert torch.equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("K,nocs_type", [(3, "ancsh"), (3, "npcs"), (4, "ancsh"), (2, "npcs")])
+@pytest.mark.parametrize("K,nocs_type", [(3, "ancsh"), (3, "npcs"), (4, "ancsh"), (2, "npcs")] +
+                         [(K, t) for K in (1, 5, 6, 7, 8) for t in ("ancsh", "npcs")])
 def test_fused_tail_equals_layerwise_bitwise(dev, K, nocs_type):
-    """csrc/chain.hip (fa_layer3 + fc1 + every head as one launch, activations in LDS) vs one launch per layer."""
+    """csrc/chain.hip (fa_layer3 + fc1 + every head as one launch, activations in LDS) vs one launch per layer.  K = 8 has a head block of 33
+    columns, which the chain does not take: the forward goes layer by layer either way, and says so before any launch."""
     from articulated_pose_amd import architecture
     from articulated_pose_amd.network import Network
     from articulated_pose_amd.weights import synthetic_weights
     mixed = nocs_type == "ancsh"
+    assert architecture._head_dims(K, mixed, mixed)[1] is (K <= 7)
     w = synthetic_weights(K, mixed_pred=mixed, early_split_nocs=mixed, seed=11)
     P = synth_cloud(np.random.RandomState(K), 2, 1024)
     net = Network(K, w, nocs_type, dev)
@@ -342,7 +349,7 @@ def test_fused_sa_ragged_group_counts_bitwise(dev, b, n, npoint):
     assert outs[0][0].shape == (b, npoint, 128) and outs[0][1].shape == (b, npoint, 256)
 
 
-@pytest.mark.parametrize("K,N,B", [(3, 1024, 8), (2, 2048, 3), (4, 2048, 2), (3, 1000, 1), (3, 777, 5)])
+@pytest.mark.parametrize("K,N,B", [(3, 1024, 8), (2, 2048, 3), (4, 2048, 2), (3, 1000, 1), (3, 777, 5), (5, 512, 2), (7, 640, 1), (8, 512, 2)])
 def test_paired_networks_equal_separate_forwards(dev, K, N, B):
     """paired.PairedNetworks: every backbone layer of the ANCSH and the NPCS network in ONE grouped launch (ancsh_*_grouped on
     stacked activations, shared geometry).  All outputs bit-identical to each network's own forward; B = 8 takes the XCD-aware
@@ -356,7 +363,11 @@ def test_paired_networks_equal_separate_forwards(dev, K, N, B):
     n = Network(K, synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1), "npcs", dev)
     alone = [a.predict(P), n.predict(P)]
     pair = PairedNetworks([a, n])
-    assert pair.eligible()
+    assert pair.eligible() is (K <= 7)                   # K = 8: head blocks of 33 columns -> each network's own layer-by-layer forward
+    for g, net in enumerate((a, n)):
+        grouped = net.predict_grouped(P)
+        for k in alone[g]:
+            assert torch.equal(grouped[k], alone[g][k]), (g, "grouped", k)
     for geometry in (None, Geometry()):
         got = pair.predict(P, geometry)
         for g in range(2):

@@ -75,10 +75,11 @@ def test_unaligned_buffers(ops, oracle, dev, seed):
         S.test_three_nn_and_interpolate(ops, oracle, dev, seed)
 
 
-@pytest.mark.parametrize("K,N,B", [(3, 777, 5), (2, 1000, 3), (4, 2048, 2), (3, 1024, 8)])
+@pytest.mark.parametrize("K,N,B", [(3, 777, 5), (2, 1000, 3), (4, 2048, 2), (3, 1024, 8), (7, 640, 2), (8, 512, 1), (1, 512, 3)])
 def test_network_forward_under_redzones(dev, K, N, B):
     """Both forwards (layer API and the grouped / chained launches) with every activation, index and scratch buffer guarded; outputs
-    equal to the unguarded run bit for bit (so no NaN body pattern survives in any head tensor)."""
+    equal to the unguarded run bit for bit (so no NaN body pattern survives in any head tensor).  K = 7 has the widest head blocks the
+    tail chain takes (29 columns; the 10 joint columns start at column 57 of 68), K = 8 goes layer by layer, K = 1 has 1-column blocks."""
     from articulated_pose_amd.network import Network
     from articulated_pose_amd.paired import PairedNetworks
     from articulated_pose_amd.weights import synthetic_weights
@@ -94,6 +95,33 @@ def test_network_forward_under_redzones(dev, K, N, B):
     for g in range(2):
         for k in plain[g]:
             assert torch.equal(alone[g][k], plain[g][k]) and torch.equal(pair[g][k], plain[g][k]), (g, k)
+
+
+@pytest.mark.parametrize("misalign", [0, 4])
+def test_head_activations_under_redzones(dev, oracle, misalign):
+    """every launch of tests/test_heads_gpu.py with each output guarded, and with each output 4 bytes off a 16-byte boundary (the entry
+    promises no alignment): ragged row counts around the 256-thread block, K = 1..8, outputs absent one at a time and all but one"""
+    import test_heads_gpu as HG
+    n = 0
+    for K, mixed in HG.CASES:
+        with guarded(misalign=misalign) as arena:
+            HG.test_head_activations_match_float64(dev, K, mixed)
+            HG.test_optional_outputs(dev, K, mixed)
+            n += arena.check()
+    with guarded(misalign=misalign) as arena:
+        HG.test_saturating_elementwise_logits(dev, oracle)
+        for K, mixed in [(1, 1), (3, 1), (8, 0), (8, 1)]:
+            HG.test_saturating_and_non_finite_softmax_rows(dev, oracle, K, mixed)
+        n += arena.check()
+    assert n > 5000
+
+
+def test_split16_forward_k7_under_redzones(dev, monkeypatch):
+    """the split-16 tail with the widest head blocks it takes (K = 7: 29 of its 32 padded columns, the joint block at column 57 of 68)"""
+    import test_bf16x3_gpu as BX
+    with guarded() as arena:
+        BX.test_split16_forward_k7(dev, monkeypatch, "f16x2")
+        assert arena.check() > 20
 
 
 def test_chains_on_ragged_rows_under_redzones(dev):
