@@ -132,6 +132,11 @@ SIGNATURES = {
     # the errors against ground truth behind the record (no ABI bump, detected by its symbol): b, n, K, nres, P, ldp, npcs_nocs, npcs_mask,
     # record, ld, gt, wide, stream
     "ancsh_gt_error_rec": [_c_int] * 4 + [_vp, _c_int] + [_vp] * 3 + [_c_int] + [_vp] * 2 + [_vp],
+    # the per-point ground truth of a streamed batch behind the articulation launches (no ABI bump, detected by its symbol): b, n, K, nchan,
+    # rows, capacity, offsets, perm, gocs_channels, joint_channels, the ANCSH heads W nocs gocs heatmap unitvec joint_axis joint_index, the
+    # NPCS heads W nocs, art, ld_art, frame, record, ld, type_l, wide, joint_gt, stream
+    "ancsh_point_gt_rec": [_c_int] * 4 + [_vp, _c_long, _vp, _vp, _c_int, _c_int] + [_vp] * 10 + [_c_int, _vp, _vp, _c_int, _c_int, _vp, _vp,
+                                                                                                  _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -116,6 +116,30 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
             __syncthreads();                                                                                                      \
         }
 
+// the same network on columns C0..5 only (C0 a literal): for a caller that takes no median of the columns below C0 (the ground-truth joint
+// axis is a mean, point_gt.hip).  A column's order never depends on another column, so columns C0..5 end as the macro above leaves them.
+#define ANCSH_SORT_VOTE_COLUMNS_FROM(jp_vals, npow2, cnt, C0)                                                                         \
+    int p2 = 1;                                                                                                                   \
+    while (p2 < cnt) p2 <<= 1;                                                                                                    \
+    for (int e = cnt + threadIdx.x; e < p2; e += 256)                                                                             \
+        _Pragma("unroll") for (int c = (C0); c < 6; ++c) jp_vals[c * npow2 + e] = INFINITY;                                       \
+    __syncthreads();                                                                                                              \
+    for (int k = 2; k <= p2; k <<= 1)                                                                                             \
+        for (int s = k >> 1; s > 0; s >>= 1) {                                                                                    \
+            for (int e = threadIdx.x; e < p2; e += 256) {                                                                         \
+                const int partner = e ^ s;                                                                                        \
+                if (partner > e) {                                                                                                \
+                    const bool up = (e & k) == 0;                                                                                 \
+                    _Pragma("unroll") for (int c = (C0); c < 6; ++c) {                                                            \
+                        float *v = jp_vals + c * npow2;                                                                           \
+                        const float a = v[e], bb = v[partner];                                                                    \
+                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }                                                        \
+                    }                                                                                                             \
+                }                                                                                                                 \
+            }                                                                                                                     \
+            __syncthreads();                                                                                                      \
+        }
+
 // med = np.median of sorted column c: the middle element, or the float32 mean of the middle two; NaN without votes
 #define ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, c)                                                                                \
     const float *med##_v = jp_vals + (c) * npow2;                                                                                     \

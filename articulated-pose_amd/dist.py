@@ -322,11 +322,14 @@ class ShardedPipeline(object):
     gathered row is [record (39) | articulation block], still one gather, and dst returns the wide records.
     ground_truth=True (with raw_capacity only): every rank's pipeline is built with ground_truth=True and submit() hands it its shard's rows
     of the batch's (n_valid, K, 19) ground truth; the streamed record is 12 columns wider (the errors, ancsh_gt_error_rec) and travels in
-    the same single gather."""
+    the same single gather.
+    point_ground_truth=True (with raw_capacity and articulation=True): every rank's pipeline is built with point_ground_truth=True, takes
+    its shard's (n_raw, 18) clouds and gets its shard's rows of the batch's (n_valid, 13) frames from submit(); the streamed record is 21
+    columns wider (ancsh_point_gt_rec) and travels in the same single gather."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, **pipeline_kw):
+                 joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False, **pipeline_kw):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
@@ -372,6 +375,16 @@ class ShardedPipeline(object):
             from .pose.gt_errors import GT_ERROR_WIDTH
             pipeline_kw.update(ground_truth=True)
             self.record_width += GT_ERROR_WIDTH
+        # point_ground_truth (raw streams with articulation): every rank streams the record 21 columns wider
+        # (AncshPipeline(point_ground_truth=True)) from its shard's 18-column clouds and frames
+        from .pose.point_gt import POINT_GT_WIDTH, check_point_ground_truth
+        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation)
+        if self.point_ground_truth:
+            if raw_capacity is None:
+                raise ValueError("point_ground_truth=True is carried by the raw stream only (submit / retire / stream_batches): it needs "
+                                 "raw_capacity")
+            pipeline_kw.update(point_ground_truth=True)
+            self.record_width += POINT_GT_WIDTH
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense = bool(dense)
@@ -502,7 +515,11 @@ class ShardedPipeline(object):
         """The checks of AncshPipeline.submit on EVERY rank's shard, so that every rank raises the same ValueError (before anything is
         enqueued and before any collective) or none does.  -> (clouds, norm factors) as check_raw_clouds returns them."""
         from .dataset import check_raw_clouds, check_stream_key
-        clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch, xyz_only=self.joint_source == "predicted")
+        if self.point_ground_truth:
+            from .pose.point_gt import check_point_clouds
+            clouds, nf = check_point_clouds(clouds, norm_factors, self.global_batch)
+        else:
+            clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch, xyz_only=self.joint_source == "predicted")
         for r in range(self.world):
             s, e = self.shard_of(len(clouds), r)
             if e == s:
@@ -515,25 +532,33 @@ class ShardedPipeline(object):
                                  "cloud), raw_capacity is %d per rank" % (r, s, e - 1, rows, self.raw_capacity))
         return clouds, nf
 
-    def submit(self, clouds, norm_factors, tag=None, gt=None):
+    def submit(self, clouds, norm_factors, tag=None, gt=None, frame=None):
         """Enqueue one GLOBAL batch (every rank calls this with the same batch): clouds = 1..global_batch raw (n_raw, 4) arrays, one norm
         factor each.  This rank submits its shard -- nothing when a short batch leaves it no cloud -- to its pipeline with seed
         seed + 2k (k = global batches submitted so far) and cloud_base = lo.  A bad batch raises ValueError on every rank, a full
         in-flight window RuntimeError on every rank; either way nothing is enqueued and the stream stays usable.  gt
         (ShardedPipeline(..., ground_truth=True); ValueError otherwise): the batch's (n_valid, K, 19) ground truth, checked whole on
-        every rank; this rank's pipeline gets rows [s, e) of it.  None: a batch without ground truth.  World 1: the local pipeline's
-        submit."""
+        every rank; this rank's pipeline gets rows [s, e) of it.  None: a batch without ground truth.  frame
+        (ShardedPipeline(..., point_ground_truth=True); ValueError otherwise): the batch's (n_valid, 13) frames, handed out the same
+        way.  World 1: the local pipeline's submit."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
         if gt is not None and not self.ground_truth:
             raise ValueError("gt needs ShardedPipeline(..., ground_truth=True)")
+        if frame is not None and not self.point_ground_truth:
+            raise ValueError("frame needs ShardedPipeline(..., point_ground_truth=True)")
         more = dict(gt=gt) if self.ground_truth else {}
+        if self.point_ground_truth:
+            more["frame"] = frame
         if self.world == 1:
             return self.pipe.submit(clouds, norm_factors, tag=tag, **more)
         clouds, nf = self._check_batch(clouds, norm_factors)
         if gt is not None:
             from .pose.gt_errors import check_ground_truth
             gt = check_ground_truth(gt, len(clouds), self.K)
+        if frame is not None:
+            from .pose.point_gt import check_frames
+            frame = check_frames(frame, len(clouds))
         if len(self._stream) == len(self.pipe.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.pipe.slots))
         seed = self.seed + 2 * self._stream_submitted
@@ -541,6 +566,8 @@ class ShardedPipeline(object):
         if e > s:
             if self.ground_truth:
                 more = dict(gt=None if gt is None else gt[s:e])
+            if self.point_ground_truth:
+                more = dict(more, frame=None if frame is None else frame[s:e])
             self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo, **more)
         self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
@@ -587,7 +614,7 @@ class ShardedPipeline(object):
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39; ground_truth: + 12
+        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39; ground_truth: + 12; point_ground_truth: + 21
         width = rw + self.art_width if self.articulation else rw      # [record (26 or 39) | articulation block (12 or 20)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
@@ -626,15 +653,19 @@ class ShardedPipeline(object):
         record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
         ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
         seed, lm_schedule).  ShardedPipeline(..., ground_truth=True): batches yields (clouds, norm_factors, gt) or (clouds, norm_factors,
-        gt, tag), as AncshPipeline.stream_batches.  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
+        gt, tag), as AncshPipeline.stream_batches; point_ground_truth=True: the frame behind gt, in front of the tag.  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
         (labels, values, offsets) in global cloud order, last (see retire()).  World 1 (or no process group): the local pipeline's
         stream_batches."""
         check_built_with(self, "stream_batches", "ShardedPipeline", articulation=articulation, dense=dense)
         if self.world == 1:
             yield from self.pipe.stream_batches(batches, flags, **only_asked(articulation=articulation, dense=dense))
             return
-        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag
-        yield from pump(batches, self._stream, len(self.pipe.slots),
-                        lambda k, item: self.submit(item[0], item[1], tag=item[2 + g] if len(item) > 2 + g else k,
-                                                    **(dict(gt=item[2] if len(item) > 2 else None) if g else {})),
-                        lambda: self.retire(flags, articulation, dense))
+        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
+        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth
+
+        def submit(k, item):
+            more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
+            if f:
+                more["frame"] = item[2 + g] if len(item) > 2 + g else None
+            self.submit(item[0], item[1], tag=item[2 + g + f] if len(item) > 2 + g + f else k, **more)
+        yield from pump(batches, self._stream, len(self.pipe.slots), submit, lambda: self.retire(flags, articulation, dense))

@@ -90,14 +90,17 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False):
+                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False):
         f = dict(dtype=torch.float32, device=device)
         # columns of a streamed record row, and where the step leaves it: the pose record, or (fit_quality) the wide record -- its 26
         # columns and the fit quality behind them
         self.record_width, record_key = (39, "record_wide") if fit_quality else (26, "record")
         if ground_truth:                        # ... and the errors against ground truth behind either (ancsh_gt_error_rec)
             self.record_width, record_key = self.record_width + 12, "record_gt"
-        self.gt = None
+        if point_ground_truth:                  # ... and the per-point ground truth's 21 columns behind whatever it was (ancsh_point_gt_rec)
+            from .pose.point_gt import POINT_GT_WIDTH
+            self.record_width, record_key = self.record_width + POINT_GT_WIDTH, "record_point_gt"
+        self.gt = self.frame = self.perm = None
         # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
         self.art_width = 20 if joint_states else 12
         self.P = torch.zeros((B, N, 3), **f)
@@ -122,6 +125,17 @@ class _Slot(object):
             from .dataset import RAW_NCHAN
             self.keyed = bool(keyed)
             self.nchan = 3 if xyz else RAW_NCHAN
+            if point_ground_truth:
+                # 18-column rows (dataset.pack_cloud) whichever the joint source, the sampler's permutation (its perm_out) and the batch's
+                # (B, 13) float64 frames -- the ground-truth NAOCS pose of part 0 per cloud, pose.point_gt -- with their pinned twin:
+                # copied with the header; all NaN until a submit says otherwise
+                from .dataset import NCHAN
+                from .pose.point_gt import FRAME_WIDTH
+                self.nchan = NCHAN
+                self.perm = torch.zeros((B, N), dtype=torch.int32, device=device)
+                self.frame = torch.full((B, FRAME_WIDTH), float("nan"), dtype=torch.float64, device=device)
+                self.h_frame = torch.full((B, FRAME_WIDTH), float("nan"), dtype=torch.float64).pin_memory()
+                self.np_frame = self.h_frame.numpy()
             # depth (the depth front end; raw_capacity = its pixel capacity): the rows are unprojected on the device, so they have no pinned
             # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam) and, with
             # label_images, the per-cloud image start (ancsh_depth_label_images' dest) behind them
@@ -155,7 +169,11 @@ class _Slot(object):
                 # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
                 rs = np.random.RandomState(0)
                 self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
-                if not xyz:
+                if point_ground_truth:
+                    self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
+                    self.np_rows[:, 4:self.nchan - 1] = rs.uniform(0.0, 1.0, (raw_capacity, self.nchan - 5))
+                    self.np_rows[:, self.nchan - 1] = rs.randint(0, K, raw_capacity)
+                elif not xyz:
                     self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
                 self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
                 self.np_nf[:] = 1.0
@@ -263,7 +281,7 @@ class AncshPipeline(object):
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
-                 ground_truth=False):
+                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2"):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -314,6 +332,18 @@ class AncshPipeline(object):
             raise ValueError("ground_truth=True travels in with a streamed batch (submit / submit_depth): it needs raw_capacity or "
                              "depth_capacity")
         self.ground_truth = bool(ground_truth)
+        # point_ground_truth (streaming raw clouds, with articulation=True): the slot's rows are dataset.pack_cloud's 18 columns -- x y z and
+        # the per-point ground truth --, the sampler leaves its permutation in the slot, submit(..., frame=...) brings the (n_valid, 13)
+        # ground-truth NAOCS poses of part 0 (pose.point_gt.pack_joint_frame), and one more launch, the last of the articulation group
+        # (ancsh_point_gt_rec, pose.point_gt.point_gt_batch), turns them into both networks' test-time losses (coord_regress_loss: "L2" |
+        # "L1") and each joint's angle and distance error in camera space: out["record_point_gt"] (B, K, ld + 21) behind whatever the
+        # streamed record was (26, 39, 38 or 51 columns).  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is this
+        # widest one.  joint_source="gt" reads the rows' column 17 as the joint label; "predicted" reads it for the losses only.
+        from .pose.point_gt import check_loss_type, check_point_ground_truth
+        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation, depth_capacity is not None)
+        self.coord_regress_loss = check_loss_type(coord_regress_loss)
+        if self.point_ground_truth and raw_capacity is None:
+            raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
         # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
         # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
         # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
@@ -401,7 +431,8 @@ class AncshPipeline(object):
             self.paired = None
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
                             self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
-                            joint_states=self.joint_states, fit_quality=self.fit_quality, ground_truth=self.ground_truth)
+                            joint_states=self.joint_states, fit_quality=self.fit_quality, ground_truth=self.ground_truth,
+                            point_ground_truth=self.point_ground_truth)
                       for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
@@ -471,11 +502,13 @@ class AncshPipeline(object):
             depth_unproject(sl.pix, sl.mask, sl.geom, sl.cam, out=(sl.raw_rows, off, sl.counts), scratch=sl.scratch)
         if self.predicted:                 # xyz rows: the sampler's xyz twin, same P (no joint_cls: the fit reads the index head)
             _lib.call("ancsh_input_sample_stream_xyz_keyed" if self.keyed else "ancsh_input_sample_stream_xyz", self.B, self.N, sl.nchan,
-                      _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), _lib.ptr(seed), _lib.ptr(sl.P), None)
+                      _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), _lib.ptr(seed), _lib.ptr(sl.P), _lib.ptr(sl.perm))
             return seed
-        _lib.call("ancsh_input_sample_stream_keyed" if self.keyed else "ancsh_input_sample_stream", self.B, self.N, RAW_NCHAN,
-                  _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), RAW_JCLS_COL, _lib.ptr(seed), _lib.ptr(sl.P),
-                  _lib.ptr(sl.joint_cls), None)
+        # point_ground_truth: the 18-column rows, whose last column is the joint label, and the slot's perm_out
+        nchan, jcls_col = (sl.nchan, sl.nchan - 1) if self.point_ground_truth else (RAW_NCHAN, RAW_JCLS_COL)
+        _lib.call("ancsh_input_sample_stream_keyed" if self.keyed else "ancsh_input_sample_stream", self.B, self.N, nchan,
+                  _lib.ptr(sl.raw_rows), self.raw_capacity, _lib.ptr(off), _lib.ptr(nf), jcls_col, _lib.ptr(seed), _lib.ptr(sl.P),
+                  _lib.ptr(sl.joint_cls), _lib.ptr(sl.perm))
         return seed
 
     def _run(self, sl=None, f32=False):
@@ -509,6 +542,11 @@ class AncshPipeline(object):
             if self.joint_states:        # one more: the block's 12 columns and the joint state behind them, (B, K, 20) float64
                 from .pose.joint_params import joint_state_batch
                 out["articulation"] = joint_state_batch(sl.P, n, sol["record"], out["articulation"])
+            if self.point_ground_truth:  # the last of the group: the widest record so far and the 21 columns behind it, one launch
+                from .pose.point_gt import point_gt_batch
+                carried = out["record_gt"] if self.ground_truth else out["record_wide"] if self.fit_quality else out["record"]
+                out["record_point_gt"] = point_gt_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, a, n, out["articulation"], sl.frame,
+                                                        carried, self.coord_regress_loss)
         if self.dense or self.label_images:      # never both: a depth pipeline refuses dense=True
             # the last launch: every raw row of the slot's batch (label_images: its unprojected rows), into the slot's own (capacity, .) buffers
             from .dataset import raw_point_labels
@@ -607,7 +645,7 @@ class AncshPipeline(object):
             sl.stream.synchronize()
 
     # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
-    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0, gt=None):
+    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0, gt=None, frame=None):
         """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
         sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.
         joint_source="predicted": (n_raw, 3) xyz clouds, or (n_raw, 4) ones whose 4th column is ignored.  A short batch
@@ -617,6 +655,9 @@ class AncshPipeline(object):
         is sampled and fitted as global cloud cloud_base + b; (cloud_base + batch_size) * num_parts must stay below 2^20.
         gt (a pipeline built with ground_truth=True; ValueError on any other): the valid clouds' (n_valid, K, 19) ground truth
         (pose.gt_errors.pack_ground_truth); None = all-NaN rows, a batch without ground truth.  Padding clouds get NaN rows.
+        A pipeline built with point_ground_truth=True takes (n_raw, 18) clouds (dataset.pack_cloud's rows) whichever the joint source, and
+        frame (ValueError on any other pipeline): the valid clouds' (n_valid, 13) ground-truth NAOCS poses of part 0
+        (pose.point_gt.pack_joint_frame), staged with the header as gt is; None = NaN rows, which blank the joint columns.
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
         if self.raw_capacity is None:
@@ -625,8 +666,12 @@ class AncshPipeline(object):
             raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
 
         def front():
-            from .dataset import check_raw_clouds
-            valid, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
+            if self.point_ground_truth:
+                from .pose.point_gt import check_point_clouds
+                valid, nf = check_point_clouds(clouds, norm_factors, self.B)
+            else:
+                from .dataset import check_raw_clouds
+                valid, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
             padded = valid + [valid[0]] * (self.B - len(valid))
             rows = sum(c.shape[0] for c in padded)
             if rows > self.raw_capacity:
@@ -639,7 +684,7 @@ class AncshPipeline(object):
                 np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
                 return [(sl.raw_rows[:rows], sl.h_rows[:rows])]
             return len(valid), nf, stage
-        self._enqueue(front, seed, tag, cloud_base, gt)
+        self._enqueue(front, seed, tag, cloud_base, gt, frame)
 
     def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None):
         """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
@@ -675,7 +720,7 @@ class AncshPipeline(object):
             return n_valid, nf, stage
         self._enqueue(front, seed, tag, cloud_base, gt)
 
-    def _enqueue(self, front, seed, tag, cloud_base, gt=None):
+    def _enqueue(self, front, seed, tag, cloud_base, gt=None, frame=None):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
         (valid clouds, their norm factors, stage); stage(sl) fills the slot's pinned staging and returns its (device, pinned) copies.
         Checks in order: the key, front()'s, the ground truth, the in-flight window (RuntimeError); only then prepare().  On the slot's
@@ -692,6 +737,11 @@ class AncshPipeline(object):
                 raise ValueError("gt needs AncshPipeline(..., ground_truth=True)")
             from .pose.gt_errors import check_ground_truth
             gt = check_ground_truth(gt, n_valid, self.K)
+        if frame is not None:
+            if not getattr(self, "point_ground_truth", False):
+                raise ValueError("frame needs AncshPipeline(..., point_ground_truth=True)")
+            from .pose.point_gt import check_frames
+            frame = check_frames(frame, n_valid)
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:
@@ -710,6 +760,11 @@ class AncshPipeline(object):
             if gt is not None:
                 sl.np_gt[:n_valid] = gt
             copies = copies + [(sl.gt, sl.h_gt)]
+        if self.point_ground_truth:                # likewise the frames
+            sl.np_frame[:] = np.nan
+            if frame is not None:
+                sl.np_frame[:n_valid] = frame
+            copies = copies + [(sl.frame, sl.h_frame)]
         cur = torch.cuda.current_stream(self.device)
         if cur != sl.stream and not cur.query():
             sl.stream.wait_stream(cur)
@@ -730,7 +785,8 @@ class AncshPipeline(object):
         records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
         the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph; built with
         ground_truth=True: 12 more columns behind either, the errors against the submitted ground truth, ancsh_gt_error_rec, refit
-        alike).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
+        alike; built with point_ground_truth=True: 21 more columns behind whatever that was, both networks' test losses and the joint errors,
+        ancsh_point_gt_rec, refit alike).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation
@@ -769,15 +825,19 @@ class AncshPipeline(object):
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
         batch's index) -- a pipeline built with ground_truth=True: (clouds, norm_factors, gt) or (clouds, norm_factors, gt, tag), gt as
-        submit() takes it --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
+        submit() takes it; built with point_ground_truth=True: the frame (submit()'s) behind the ground truth, in front of the tag --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
         flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
         last -- see retire())."""
         check_built_with(self, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
-        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag
-        yield from pump(batches, self._inflight, len(self.slots),
-                        lambda k, item: self.submit(item[0], item[1], tag=item[2 + g] if len(item) > 2 + g else k,
-                                                    **(dict(gt=item[2] if len(item) > 2 else None) if g else {})),
-                        lambda: self.retire(flags, articulation, dense))
+        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
+        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth
+
+        def submit(k, item):
+            more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
+            if f:
+                more["frame"] = item[2 + g] if len(item) > 2 + g else None
+            self.submit(item[0], item[1], tag=item[2 + g + f] if len(item) > 2 + g + f else k, **more)
+        yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the

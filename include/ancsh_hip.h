@@ -44,7 +44,7 @@ extern "C" {
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
                                  *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
-                                 *     against ground truth), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
+                                 *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
@@ -895,6 +895,53 @@ int ancsh_fit_quality_rec(int b, int K, const int *off, const float *src, const 
  * only.  1 <= K <= 8, n >= 1, ldp >= 3, ld in {26, 39}, 2 <= nres <= 64; b == 0 launches nothing. */
 int ancsh_gt_error_rec(int b, int n, int K, int nres, const float *P, int ldp, const float *npcs_nocs, const float *npcs_mask,
                        const double *record, int ld, const double *gt, double *wide, void *stream);
+
+/* What a streamed batch's PER-POINT ground truth says about it, one launch behind the articulation launches (ancsh_articulation_rec and,
+ * if built, ancsh_joint_state_rec; no new ABI number: callers detect it by its symbol): the test-time losses of both networks
+ * (lib/network.py:257-316 over lib/loss.py: the numbers of test_loss.txt) and step 5 of evaluation.sh, each joint's axis angle error and
+ * line-to-line distance in camera space (evaluation/eval_joint_params.py:189-256).  One workgroup per cloud; every size is an argument or
+ * read from device memory, nothing is allocated and the host never waits: capturable.
+ * rows (capacity, nchan = 18) float32: the raw rows of the batch, dataset.pack_cloud's layout
+ *   x y z | cls | nocs_p 3 | nocs_g 3 | heatmap | unitvec 3 | orient 3 | joint_cls;
+ * offsets (b+1) int32 on the device: cloud c owns rows [offsets[c], offsets[c+1]); perm (b,n) int32: ancsh_input_sample_stream*'s perm_out.
+ * Sampled point i of cloud c is raw row offsets[c] + perm[c][i] % n_raw, and its channels 3..17 are read by ancsh_input_sample's rules:
+ * cls_gt and joint_cls_gt = the C truncation to int32, mask_array = the one-hot of int8(cls) with numpy's negative-index rule,
+ * joint_cls_mask = joint_cls > 0, nocs_gt = nocs_p, nocs_gt_g = nocs_g.
+ * The ANCSH heads (b,n,.) float32: W (K), nocs (3K), gocs (gocs_channels = 3K or 3), heatmap (1), unitvec (3), joint_axis (3), joint_index
+ * (joint_channels); the NPCS heads: npcs_W (K), npcs_nocs (3K).  art (b,K,ld_art) float64, ld_art = 12 (ancsh_articulation_rec's block) or
+ * 20 (ancsh_joint_state_rec's): the predicted joint j in camera space, pivot 6..8 and axis 9..11.  frame (b,13) float64 = [R (9,
+ * row-major) | s | t (3)] of the ground-truth NAOCS pose of part 0 (gn_gt[...]['rt']['gt'][0], gn_gt[...]['scale']['gt'][0]).  record
+ * (b,K,ld) float64 rows, ld = 26 (the record), 39 (ancsh_fit_quality_rec's), 38 or 51 (ancsh_gt_error_rec's behind either).  type_l: 0 =
+ * L2, 1 = L1 (coord_regress_loss).
+ * wide (b,K,ld+21) float64, row (c,j): columns 0..ld-1 = the input row bit for bit (NaN payloads included), then
+ *   ld+0     row j >= 1: angle_err = axis_diff_degree(l_gt, art[9..11]) in degrees (lib/d3_utils.py:137-142: no clamp, min(a, 180 - a))
+ *   ld+1     row j >= 1: dist_err = dist_between_3d_lines(p_gt, l_gt, art[6..8], art[9..11]) (:165-174)
+ *   ld+2..4  row j >= 1: p_gt = R (s p) + t, the ground-truth joint point in camera space (eval_joint_params.py:224-231)
+ *   ld+5..7  row j >= 1: l_gt = R l, the ground-truth joint axis in camera space, not normalised
+ *   ld+8     miou_loss[j] of the ANCSH network;  ld+9  miou_loss[j] of the NPCS network
+ *   ld+10    sampled points with cls_gt == j;  ld+11  sampled points with joint_cls_gt == j
+ *   ld+12..19 the cloud's ANCSH nocs, gocs, heatmap, unitvec, orient and index[0..2] losses, the same bits on every row
+ *   ld+20    the cloud's NPCS nocs_loss, the same bits on every row
+ * The losses are ancsh_test_losses' 5 + K + 3 numbers on the gathered tensors, BIT-EQUAL (float32 values held as doubles): the same
+ * statements and the same accumulation order -- thread tid of 256 takes points tid, tid + 256, ..., float64 partial sums, xor-shuffle
+ * wave sums, four waves added in order.  gocs_loss is NaN when gocs_channels == 3 != 3K (no per-part global NOCS head), the index losses when joint_channels != 3.
+ * (p, l) of joint j in global NOCS are ancsh_joint_params' axis_mean = 1 numbers on the gathered nocs_gt_g, heatmap_gt, unitvec_gt,
+ * orient_gt, joint_cls_gt with gocs_channels = 3, BIT-EQUAL: p = the per-channel exact median of nocs_g + unitvec * (1 - heatmap) * 0.2
+ * over the points of joint class j (float32, numpy's order), l = the float32 mean of their orientations in point order (:189-199).
+ * joint_gt (b,K-1,6) float64, optional (NULL to skip): [p | l] of joints 1..K-1 before the camera transform.
+ * Camera space and errors in float64, evaluated as written, no contraction: x_k = ((R_k0 a_0 + R_k1 a_1) + R_k2 a_2) [+ t_k]; dot and
+ * squared norms (x^2 + y^2) + z^2; angle = acos(dot / (|l_gt| |l|)) * 180 / pi; dist = |((l_gt x l) . (p_gt - p))| / |l_gt x l|.
+ * NaN rules: row 0's ld+0..7 are NaN; a joint class without ground-truth points has ld+0..7 NaN; a NaN in frame blanks ld+0..7 of the
+ * cloud; a NaN in art[j][6..11] (an empty predicted joint class, a poisoned record) blanks ld+0 and ld+1 of row j.  The losses are
+ * whatever the arithmetic gives.  A cloud whose offsets are empty or reach outside capacity (the host refuses both) gets NaN in all 21
+ * columns.  A cloud never changes a neighbour's bytes.  K = 1: row 0 only.
+ * 1 <= K <= 8, nchan == 18, 1 <= n <= ANCSH_ARTICULATION_MAX_N (the votes' six columns stay in LDS), ld in {26, 39, 38, 51}, ld_art in
+ * {12, 20}, 0 <= capacity < 2^30; b == 0 launches nothing. */
+int ancsh_point_gt_rec(int b, int n, int K, int nchan, const float *rows, long capacity, const int *offsets, const int *perm,
+                       int gocs_channels, int joint_channels, const float *W, const float *nocs, const float *gocs, const float *heatmap,
+                       const float *unitvec, const float *joint_axis, const float *joint_index, const float *npcs_W,
+                       const float *npcs_nocs, const double *art, int ld_art, const double *frame, const double *record, int ld, int type_l,
+                       double *wide, double *joint_gt, void *stream);
 
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 

@@ -3,7 +3,7 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
-                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth]
+                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth] [--point-gt] [--no-baseline]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
@@ -13,6 +13,10 @@ line then also carries the rerun count, the latency of the batches that reran an
 --fit-quality streams with AncshPipeline(fit_quality=True): the record is the (n, K, 39) wide one, one more launch a step.
 --ground-truth streams with AncshPipeline(ground_truth=True): every batch carries a (32, K, 19) ground truth in, the record comes back 12
 columns wider (the errors against it, ancsh_gt_error_rec), one more launch a step.
+--point-gt (with --articulation) streams with AncshPipeline(point_ground_truth=True): the clouds are (n_raw, 18) rows with per-point ground
+truth (4.5 times the bytes of an [x y z joint_cls] row over the link), every batch carries (32, 13) frames in, the record comes back 21
+columns wider (both networks' test losses and the joint errors, ancsh_point_gt_rec), one more launch a step.
+--no-baseline skips the load_inputs + step() leg (step_clouds_per_s and ratio are then null): for A/B runs of the stream alone.
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 --joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
 head) and submits (n_raw, 3) xyz clouds: no label column crosses to the device.
@@ -47,6 +51,9 @@ def main():
     ap.add_argument("--fit-quality", action="store_true", help="AncshPipeline(fit_quality=True): the streamed record is the (n, K, 39) wide one")
     ap.add_argument("--ground-truth", action="store_true",
                     help="AncshPipeline(ground_truth=True): a ground truth per batch in, the streamed record 12 error columns wider")
+    ap.add_argument("--point-gt", action="store_true",
+                    help="with --articulation: AncshPipeline(point_ground_truth=True): 18-column clouds and frames in, the record 21 columns wider")
+    ap.add_argument("--no-baseline", action="store_true", help="skip the load_inputs + step() leg")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
                     help="predicted: the joint association from the network's index head; (n_raw, 3) xyz clouds are submitted")
@@ -55,6 +62,8 @@ def main():
         ap.error("--range-guard needs --arithmetic f16x2")
     if args.joint_states and not args.articulation:
         ap.error("--joint-states needs --articulation")
+    if args.point_gt and not args.articulation:
+        ap.error("--point-gt needs --articulation")
     extra = args.arithmetic is not None
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
@@ -64,7 +73,9 @@ def main():
         c = make_cloud(i, N=int(n), K=K)
         raw.append(np.concatenate([c["P"], c["cls_gt"][:, None].astype(np.float32)], 1))
     predicted = args.joint_source == "predicted"
-    if predicted:
+    if args.point_gt:            # 18-column rows: the part label, random ground-truth channels (the launch's cost does not depend on them), the joint label
+        raw = [np.concatenate([r[:, :4], rs.uniform(0, 1, (r.shape[0], 13)).astype(np.float32), r[:, 3:]], 1) for r in raw]
+    elif predicted:
         raw = [np.ascontiguousarray(r[:, :3]) for r in raw]
     batches = [(raw[i:i + B], np.ones(B, np.float32)) for i in range(0, len(raw) - B + 1, B)]
     if args.overflow_every:
@@ -77,7 +88,8 @@ def main():
         R = np.stack([np.cos(a), -np.sin(a), z, np.sin(a), np.cos(a), z, z, z, o], -1)
         gts = np.concatenate([R, rs.uniform(0.5, 1.5, a.shape + (1,)), rs.uniform(-0.3, 0.3, a.shape + (3,)), rs.uniform(0.3, 0.9, a.shape + (3,)),
                               rs.uniform(-0.3, 0.3, a.shape + (3,))], -1)
-    with_gt = (lambda k, c, nf: (c, nf, gts[k])) if args.ground_truth else (lambda k, c, nf: (c, nf))
+    frames = rs.normal(size=(len(batches), B, 13)) if args.point_gt else None
+    with_gt = lambda k, c, nf: (c, nf) + ((gts[k],) if args.ground_truth else ()) + ((frames[k],) if args.point_gt else ())
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
 
     # streaming
@@ -86,7 +98,7 @@ def main():
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
                          range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
                          joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality,
-                         ground_truth=args.ground_truth).prepare()
+                         ground_truth=args.ground_truth, point_ground_truth=args.point_gt).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches([with_gt(k, c, nf) for k, (c, nf) in enumerate(batches)]):          # warm-up: every slot replayed with real input
@@ -119,12 +131,16 @@ def main():
 
     # baseline: the same clouds sampled once up front, then load_inputs + step() per batch, the slot's previous record read back
     pre = []
-    for k, (c, nf) in enumerate(batches):
+    for k, (c, nf) in enumerate([] if args.no_baseline else batches):
+        if args.point_gt:
+            c = [np.ascontiguousarray(r[:, [0, 1, 2, 17]]) for r in c]
         s = sample_raw_batch(c, N, nf, k, dev, xyz_only=predicted)
         pre.append((s["P"].cpu().numpy(), None if predicted else s["joint_cls"].cpu().numpy()))
-    base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, arithmetic=args.arithmetic, joint_source=args.joint_source)
-    base.load_inputs(*pre[0])
-    base.prepare()
+    base = None
+    if not args.no_baseline:
+        base = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, arithmetic=args.arithmetic, joint_source=args.joint_source)
+        base.load_inputs(*pre[0])
+        base.prepare()
 
     def run_steps(items):
         n = 0
@@ -138,17 +154,19 @@ def main():
             base.step()
         base.synchronize()
         return n
-    run_steps(pre)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    run_steps([pre[k] for _ in range(args.passes) for k in range(len(pre))])
-    torch.cuda.synchronize()
-    t_step = time.perf_counter() - t0
+    t_step = None
+    if base is not None:
+        run_steps(pre)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run_steps([pre[k] for _ in range(args.passes) for k in range(len(pre))])
+        torch.cuda.synchronize()
+        t_step = time.perf_counter() - t0
 
     n_clouds = args.passes * len(batches) * B
     line = {"metric": "clouds/s through AncshPipeline.stream_batches (raw clouds %d-%d rows, H2D + sampling + fit + record D2H)" % (sizes.min(), sizes.max()),
-            "stream_clouds_per_s": round(n_clouds / t_stream, 1), "step_clouds_per_s": round(n_clouds / t_step, 1),
-            "ratio": round(t_step / t_stream, 4), "records_out": n_out,
+            "stream_clouds_per_s": round(n_clouds / t_stream, 1), "step_clouds_per_s": round(n_clouds / t_step, 1) if t_step else None,
+            "ratio": round(t_step / t_stream, 4) if t_step else None, "records_out": n_out,
             "batch_latency_ms_min": round(1e3 * min(lat), 2), "batch_latency_ms_max": round(1e3 * max(lat), 2),
             "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "couple": True,
                       "distinct_clouds": len(batches) * B, "timed_batches": args.passes * len(batches)},
@@ -166,6 +184,8 @@ def main():
         line.update({"fit_quality": True})
     if args.ground_truth:
         line.update({"ground_truth": True, "record_columns": int(rec.shape[2])})
+    if args.point_gt:
+        line.update({"point_ground_truth": True, "record_columns": int(rec.shape[2]), "h2d_row_bytes": 72})
     if predicted:
         line.update({"joint_source": "predicted"})
     if args.dense:
