@@ -137,6 +137,9 @@ SIGNATURES = {
     # NPCS heads W nocs, art, ld_art, frame, record, ld, type_l, wide, joint_gt, stream
     "ancsh_point_gt_rec": [_c_int] * 4 + [_vp, _c_long, _vp, _vp, _c_int, _c_int] + [_vp] * 10 + [_c_int, _vp, _vp, _c_int, _c_int, _vp, _vp,
                                                                                                   _vp],
+    # the per-point ground truth itself, built from annotated clouds in front of the sampler (no ABI bump, detected by its symbol): nclouds, K,
+    # src, capacity, offsets, rig, rig_ld, rows, stream
+    "ancsh_point_gt_build": [_c_int, _c_int, _vp, _c_long, _vp, _vp, _c_int, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -325,11 +325,15 @@ class ShardedPipeline(object):
     the same single gather.
     point_ground_truth=True (with raw_capacity and articulation=True): every rank's pipeline is built with point_ground_truth=True, takes
     its shard's (n_raw, 18) clouds and gets its shard's rows of the batch's (n_valid, 13) frames from submit(); the streamed record is 21
-    columns wider (ancsh_point_gt_rec) and travels in the same single gather."""
+    columns wider (ancsh_point_gt_rec) and travels in the same single gather.
+    build_point_gt=True (with point_ground_truth=True): every rank's pipeline builds its rows on the device (AncshPipeline(build_point_gt=
+    True)) from its shard's (n_raw, 7) annotated clouds and its shard's rows of the batch's (n_valid, RIG_WIDTH) rigs, handed out as the
+    frames are."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
-                 joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False, **pipeline_kw):
+                 joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False, build_point_gt=False,
+                 **pipeline_kw):
         from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
@@ -385,6 +389,12 @@ class ShardedPipeline(object):
                                  "raw_capacity")
             pipeline_kw.update(point_ground_truth=True)
             self.record_width += POINT_GT_WIDTH
+        # build_point_gt (with point_ground_truth): every rank builds its shard's rows from 7-column annotated clouds and rigs
+        if build_point_gt and not self.point_ground_truth:
+            raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
+        self.build_point_gt = bool(build_point_gt)
+        if self.build_point_gt:
+            pipeline_kw.update(build_point_gt=True)
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense = bool(dense)
@@ -515,7 +525,10 @@ class ShardedPipeline(object):
         """The checks of AncshPipeline.submit on EVERY rank's shard, so that every rank raises the same ValueError (before anything is
         enqueued and before any collective) or none does.  -> (clouds, norm factors) as check_raw_clouds returns them."""
         from .dataset import check_raw_clouds, check_stream_key
-        if self.point_ground_truth:
+        if self.build_point_gt:
+            from .dataset import check_annotated_clouds
+            clouds, nf = check_annotated_clouds(clouds, norm_factors, self.K, self.global_batch)
+        elif self.point_ground_truth:
             from .pose.point_gt import check_point_clouds
             clouds, nf = check_point_clouds(clouds, norm_factors, self.global_batch)
         else:
@@ -532,7 +545,7 @@ class ShardedPipeline(object):
                                  "cloud), raw_capacity is %d per rank" % (r, s, e - 1, rows, self.raw_capacity))
         return clouds, nf
 
-    def submit(self, clouds, norm_factors, tag=None, gt=None, frame=None):
+    def submit(self, clouds, norm_factors, tag=None, gt=None, frame=None, rig=None):
         """Enqueue one GLOBAL batch (every rank calls this with the same batch): clouds = 1..global_batch raw (n_raw, 4) arrays, one norm
         factor each.  This rank submits its shard -- nothing when a short batch leaves it no cloud -- to its pipeline with seed
         seed + 2k (k = global batches submitted so far) and cloud_base = lo.  A bad batch raises ValueError on every rank, a full
@@ -540,16 +553,24 @@ class ShardedPipeline(object):
         (ShardedPipeline(..., ground_truth=True); ValueError otherwise): the batch's (n_valid, K, 19) ground truth, checked whole on
         every rank; this rank's pipeline gets rows [s, e) of it.  None: a batch without ground truth.  frame
         (ShardedPipeline(..., point_ground_truth=True); ValueError otherwise): the batch's (n_valid, 13) frames, handed out the same
-        way.  World 1: the local pipeline's submit."""
+        way.  rig (ShardedPipeline(..., build_point_gt=True), which takes (n_raw, 7) annotated clouds; ValueError otherwise, and when it is
+        missing there): the batch's (n_valid, RIG_WIDTH) rigs, handed out the same way.  World 1: the local pipeline's submit."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
         if gt is not None and not self.ground_truth:
             raise ValueError("gt needs ShardedPipeline(..., ground_truth=True)")
         if frame is not None and not self.point_ground_truth:
             raise ValueError("frame needs ShardedPipeline(..., point_ground_truth=True)")
+        if rig is not None and not self.build_point_gt:
+            raise ValueError("rig needs ShardedPipeline(..., point_ground_truth=True, build_point_gt=True)")
+        if rig is None and self.build_point_gt:
+            raise ValueError("a pipeline built with build_point_gt=True builds every cloud's rows from its rig: submit(..., rig=...) needs one "
+                             "dataset.pack_joint_rig table per cloud")
         more = dict(gt=gt) if self.ground_truth else {}
         if self.point_ground_truth:
             more["frame"] = frame
+        if self.build_point_gt:
+            more["rig"] = rig
         if self.world == 1:
             return self.pipe.submit(clouds, norm_factors, tag=tag, **more)
         clouds, nf = self._check_batch(clouds, norm_factors)
@@ -559,6 +580,9 @@ class ShardedPipeline(object):
         if frame is not None:
             from .pose.point_gt import check_frames
             frame = check_frames(frame, len(clouds))
+        if rig is not None:
+            from .dataset import check_rigs
+            rig = check_rigs(rig, len(clouds), self.K)
         if len(self._stream) == len(self.pipe.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.pipe.slots))
         seed = self.seed + 2 * self._stream_submitted
@@ -568,6 +592,8 @@ class ShardedPipeline(object):
                 more = dict(gt=None if gt is None else gt[s:e])
             if self.point_ground_truth:
                 more = dict(more, frame=None if frame is None else frame[s:e])
+            if self.build_point_gt:
+                more = dict(more, rig=rig[s:e])
             self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo, **more)
         self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
@@ -653,7 +679,7 @@ class ShardedPipeline(object):
         record) in submission order -- record = the batch's (n_valid, K, 26) records in global cloud order on dst, None on the other
         ranks (flags=True: + the flag words).  The records equal those of one AncshPipeline.stream_batches over the same batches (same
         seed, lm_schedule).  ShardedPipeline(..., ground_truth=True): batches yields (clouds, norm_factors, gt) or (clouds, norm_factors,
-        gt, tag), as AncshPipeline.stream_batches; point_ground_truth=True: the frame behind gt, in front of the tag.  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
+        gt, tag), as AncshPipeline.stream_batches; point_ground_truth=True: the frame behind gt, in front of the tag; build_point_gt=True: the rig behind the frame.  articulation=True: + the (n_valid, K, 12) articulation blocks in global cloud order; dense=True: + the raw rows'
         (labels, values, offsets) in global cloud order, last (see retire()).  World 1 (or no process group): the local pipeline's
         stream_batches."""
         check_built_with(self, "stream_batches", "ShardedPipeline", articulation=articulation, dense=dense)
@@ -661,11 +687,14 @@ class ShardedPipeline(object):
             yield from self.pipe.stream_batches(batches, flags, **only_asked(articulation=articulation, dense=dense))
             return
         g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
-        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth
+        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth,
+        r = 1 if self.build_point_gt else 0          # and the rigs behind the frames
 
         def submit(k, item):
             more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
             if f:
                 more["frame"] = item[2 + g] if len(item) > 2 + g else None
-            self.submit(item[0], item[1], tag=item[2 + g + f] if len(item) > 2 + g + f else k, **more)
+            if r:
+                more["rig"] = item[2 + g + f] if len(item) > 2 + g + f else None
+            self.submit(item[0], item[1], tag=item[2 + g + f + r] if len(item) > 2 + g + f + r else k, **more)
         yield from pump(batches, self._stream, len(self.pipe.slots), submit, lambda: self.retire(flags, articulation, dense))

@@ -90,7 +90,8 @@ class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
     def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False):
+                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False,
+                 build_point_gt=False):
         f = dict(dtype=torch.float32, device=device)
         # columns of a streamed record row, and where the step leaves it: the pose record, or (fit_quality) the wide record -- its 26
         # columns and the fit quality behind them
@@ -100,7 +101,7 @@ class _Slot(object):
         if point_ground_truth:                  # ... and the per-point ground truth's 21 columns behind whatever it was (ancsh_point_gt_rec)
             from .pose.point_gt import POINT_GT_WIDTH
             self.record_width, record_key = self.record_width + POINT_GT_WIDTH, "record_point_gt"
-        self.gt = self.frame = self.perm = None
+        self.gt = self.frame = self.perm = self.src_rows = self.rig = None
         # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
         self.art_width = 20 if joint_states else 12
         self.P = torch.zeros((B, N, 3), **f)
@@ -142,7 +143,20 @@ class _Slot(object):
             self.layout = lay = header_layout(B, self.keyed, bool(depth), label_images)
             self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
             self.hdr = torch.zeros((lay.words,), dtype=torch.int32, device=device)
-            self.h_rows = None if depth else torch.zeros((raw_capacity, self.nchan), dtype=torch.float32).pin_memory()
+            # what travels in: the rows themselves, or (build_point_gt) the 7-column annotated rows the step's first launch builds them from
+            # (ancsh_point_gt_build) -- the 18-column rows then have no pinned twin -- and the batch's (B, RIG_WIDTH) float64 rigs with their
+            # pinned twin, copied with the header; rigs without joints and with identity maps until a submit says otherwise
+            staged = self.nchan
+            if build_point_gt:
+                from .dataset import ANNOTATED_NCHAN, RIG_WIDTH, identity_rig
+                staged = ANNOTATED_NCHAN
+                self.src_rows = torch.zeros((raw_capacity, staged), **f)
+                self.h_rig = torch.zeros((B, RIG_WIDTH(K)), dtype=torch.float64).pin_memory()
+                self.np_rig = self.h_rig.numpy()
+                self.np_rig[:] = identity_rig(K)
+                self.rig = self.h_rig.to(device)
+            self.staged_rows = self.src_rows if build_point_gt else self.raw_rows      # the device buffer submit() copies the clouds into
+            self.h_rows = None if depth else torch.zeros((raw_capacity, staged), dtype=torch.float32).pin_memory()
             self.h_hdr = torch.zeros((lay.words,), dtype=torch.int32).pin_memory()
             self.h2d_done = torch.cuda.Event()
             self.d2h_done = torch.cuda.Event()
@@ -169,7 +183,10 @@ class _Slot(object):
                 # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
                 rs = np.random.RandomState(0)
                 self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
-                if point_ground_truth:
+                if build_point_gt:
+                    self.np_rows[:, 3:6] = rs.uniform(0.0, 1.0, (raw_capacity, 3))
+                    self.np_rows[:, 6] = rs.randint(0, K, raw_capacity)
+                elif point_ground_truth:
                     self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
                     self.np_rows[:, 4:self.nchan - 1] = rs.uniform(0.0, 1.0, (raw_capacity, self.nchan - 5))
                     self.np_rows[:, self.nchan - 1] = rs.randint(0, K, raw_capacity)
@@ -177,7 +194,7 @@ class _Slot(object):
                     self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
                 self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
                 self.np_nf[:] = 1.0
-                self.raw_rows.copy_(self.h_rows)
+                self.staged_rows.copy_(self.h_rows)
                 self.hdr.copy_(self.h_hdr)
             # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
             # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words and the depth
@@ -281,7 +298,7 @@ class AncshPipeline(object):
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
-                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2"):
+                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False):
         # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
         # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
         # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
@@ -344,6 +361,14 @@ class AncshPipeline(object):
         self.coord_regress_loss = check_loss_type(coord_regress_loss)
         if self.point_ground_truth and raw_capacity is None:
             raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
+        # build_point_gt (with point_ground_truth=True): the stream takes (n_raw, 7) annotated clouds [x y z | cx cy cz | part]
+        # (dataset.pack_annotated_cloud) and one rig per cloud (dataset.pack_joint_rig, submit(..., rig=...)), and the captured step's first
+        # launch (ancsh_point_gt_build, in front of the sampler) builds the slot's 18-column rows from them on the device: 28 bytes per row
+        # cross to the device instead of 72, and nothing of the reference's data code runs on the host.  Everything behind it reads the
+        # slot's rows where they lie; result tuples and record widths do not change.
+        if build_point_gt and not self.point_ground_truth:
+            raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
+        self.build_point_gt = bool(build_point_gt)
         # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
         # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
         # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
@@ -432,7 +457,7 @@ class AncshPipeline(object):
         self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
                             self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
                             joint_states=self.joint_states, fit_quality=self.fit_quality, ground_truth=self.ground_truth,
-                            point_ground_truth=self.point_ground_truth)
+                            point_ground_truth=self.point_ground_truth, build_point_gt=self.build_point_gt)
                       for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
@@ -497,6 +522,9 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.build_point_gt:            # the slot's annotated rows and rigs -> its 18-column rows, in front of the unchanged sampler
+            from .dataset import point_gt_build
+            point_gt_build(sl.src_rows, off, sl.rig, self.K, sl.raw_rows)
         if self.depth_dtype is not None:   # the depth front end: the slot's crops -> its rows, offsets and counts, in front of the xyz sampler
             from .depth import depth_unproject
             depth_unproject(sl.pix, sl.mask, sl.geom, sl.cam, out=(sl.raw_rows, off, sl.counts), scratch=sl.scratch)
@@ -645,7 +673,7 @@ class AncshPipeline(object):
             sl.stream.synchronize()
 
     # ---- streaming: raw clouds in, pose records out (raw_capacity set) ---------------------------------------------------------
-    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0, gt=None, frame=None):
+    def submit(self, clouds, norm_factors, seed=None, tag=None, cloud_base=0, gt=None, frame=None, rig=None):
         """Enqueue one batch of raw clouds (asynchronous): clouds = 1..batch_size (n_raw, 4) float32 arrays [x y z joint_cls] of any
         sizes (all of them, plus the padding below, <= raw_capacity rows), norm_factors = one finite float per cloud.
         joint_source="predicted": (n_raw, 3) xyz clouds, or (n_raw, 4) ones whose 4th column is ignored.  A short batch
@@ -658,6 +686,10 @@ class AncshPipeline(object):
         A pipeline built with point_ground_truth=True takes (n_raw, 18) clouds (dataset.pack_cloud's rows) whichever the joint source, and
         frame (ValueError on any other pipeline): the valid clouds' (n_valid, 13) ground-truth NAOCS poses of part 0
         (pose.point_gt.pack_joint_frame), staged with the header as gt is; None = NaN rows, which blank the joint columns.
+        A pipeline built with build_point_gt=True takes (n_raw, 7) annotated clouds (dataset.pack_annotated_cloud: x y z | cx cy cz | part,
+        the part an integer in [0, num_parts)) instead, and rig (ValueError on any other pipeline, and when it is missing on this one): the
+        valid clouds' (n_valid, RIG_WIDTH(num_parts)) tables (dataset.pack_joint_rig), staged with the header as frame is; the padding
+        clouds of a short batch take the first cloud's.
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
         if self.raw_capacity is None:
@@ -666,7 +698,13 @@ class AncshPipeline(object):
             raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
 
         def front():
-            if self.point_ground_truth:
+            if getattr(self, "build_point_gt", False):
+                from .dataset import check_annotated_clouds
+                if rig is None:
+                    raise ValueError("a pipeline built with build_point_gt=True builds every cloud's rows from its rig: submit(..., rig=...) "
+                                     "needs one dataset.pack_joint_rig table per cloud")
+                valid, nf = check_annotated_clouds(clouds, norm_factors, self.K, self.B)
+            elif self.point_ground_truth:
                 from .pose.point_gt import check_point_clouds
                 valid, nf = check_point_clouds(clouds, norm_factors, self.B)
             else:
@@ -682,9 +720,9 @@ class AncshPipeline(object):
                 np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
                 sl.np_off[0] = 0
                 np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
-                return [(sl.raw_rows[:rows], sl.h_rows[:rows])]
+                return [(sl.staged_rows[:rows], sl.h_rows[:rows])]
             return len(valid), nf, stage
-        self._enqueue(front, seed, tag, cloud_base, gt, frame)
+        self._enqueue(front, seed, tag, cloud_base, gt, frame, rig)
 
     def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None):
         """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
@@ -720,10 +758,10 @@ class AncshPipeline(object):
             return n_valid, nf, stage
         self._enqueue(front, seed, tag, cloud_base, gt)
 
-    def _enqueue(self, front, seed, tag, cloud_base, gt=None, frame=None):
+    def _enqueue(self, front, seed, tag, cloud_base, gt=None, frame=None, rig=None):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
         (valid clouds, their norm factors, stage); stage(sl) fills the slot's pinned staging and returns its (device, pinned) copies.
-        Checks in order: the key, front()'s, the ground truth, the in-flight window (RuntimeError); only then prepare().  On the slot's
+        Checks in order: the key, front()'s, the ground truth, the frames, the rigs, the in-flight window (RuntimeError); only then prepare().  On the slot's
         stream: the H2D copies (the ground truth's with the header's) with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
         next replay's pool reuses its block, see step()), d2h_done."""
         from .dataset import check_stream_key, seed_bits
@@ -742,6 +780,11 @@ class AncshPipeline(object):
                 raise ValueError("frame needs AncshPipeline(..., point_ground_truth=True)")
             from .pose.point_gt import check_frames
             frame = check_frames(frame, n_valid)
+        if rig is not None:
+            if not getattr(self, "build_point_gt", False):
+                raise ValueError("rig needs AncshPipeline(..., point_ground_truth=True, build_point_gt=True)")
+            from .dataset import check_rigs
+            rig = check_rigs(rig, n_valid, self.K)
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:
@@ -765,6 +808,10 @@ class AncshPipeline(object):
             if frame is not None:
                 sl.np_frame[:n_valid] = frame
             copies = copies + [(sl.frame, sl.h_frame)]
+        if self.build_point_gt:                    # the rigs; a padding cloud is a copy of the first cloud, rig included
+            sl.np_rig[:n_valid] = rig
+            sl.np_rig[n_valid:] = rig[0]
+            copies = copies + [(sl.rig, sl.h_rig)]
         cur = torch.cuda.current_stream(self.device)
         if cur != sl.stream and not cur.query():
             sl.stream.wait_stream(cur)
@@ -825,18 +872,21 @@ class AncshPipeline(object):
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
         batch's index) -- a pipeline built with ground_truth=True: (clouds, norm_factors, gt) or (clouds, norm_factors, gt, tag), gt as
-        submit() takes it; built with point_ground_truth=True: the frame (submit()'s) behind the ground truth, in front of the tag --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
+        submit() takes it; built with point_ground_truth=True: the frame (submit()'s) behind the ground truth, in front of the tag; built with build_point_gt=True: the rig (submit()'s) behind the frame, in front of the tag --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
         flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
         last -- see retire())."""
         check_built_with(self, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
         g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
-        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth
+        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth,
+        r = 1 if self.build_point_gt else 0          # and the rigs behind the frames
 
         def submit(k, item):
             more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
             if f:
                 more["frame"] = item[2 + g] if len(item) > 2 + g else None
-            self.submit(item[0], item[1], tag=item[2 + g + f] if len(item) > 2 + g + f else k, **more)
+            if r:
+                more["rig"] = item[2 + g + f] if len(item) > 2 + g + f else None
+            self.submit(item[0], item[1], tag=item[2 + g + f + r] if len(item) > 2 + g + f + r else k, **more)
         yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):

@@ -44,7 +44,8 @@ extern "C" {
 int ancsh_abi_version(void);   /* added since without a new number (callers detect them by their symbols): ancsh_depth_unproject_stream,
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
                                  *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
-                                 *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
+                                 *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_point_gt_build (that ground truth built from
+                                 *     annotated clouds), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
@@ -942,6 +943,48 @@ int ancsh_point_gt_rec(int b, int n, int K, int nchan, const float *rows, long c
                        const float *unitvec, const float *joint_axis, const float *joint_index, const float *npcs_W,
                        const float *npcs_nocs, const double *art, int ld_art, const double *frame, const double *record, int ld, int type_l,
                        double *wide, double *joint_gt, void *stream);
+
+/* The per-point ground truth itself, built from annotated clouds in ONE launch in front of the streaming sampler (no new ABI number:
+ * callers detect it by its symbol): the arithmetic of lib/dataset.py:434-700 behind the two h5py lookups -- create_data_shape2motion
+ * (:490-547) and create_data_mobility (:603-699) -- and the sapien rotation of :371-379, which the reference runs per part in numpy on the
+ * host.  Cloud b owns rows [offsets[b], offsets[b+1]) of src (capacity x 7 float32) and of rows (capacity x 18 float32, the layout
+ * ancsh_point_gt_rec reads); offsets (nclouds + 1) int32 on the device.  A source row is [x y z | c (3) | part]: a camera point
+ * (gt_points), its canonical coordinates (gt_coords) and the index of its group in parts_map.  rig (nclouds, rig_ld) float64, rig_ld =
+ * ANCSH_RIG_WIDTH(K), per cloud:
+ *   [0] thres_r   [1] the default joint label (0 shape2motion :539, K sapien :672)   [2] 0: a line entry selects h < thres_r (:543),
+ *   1: h <= thres_r (:683)   [3] non-zero: rotate by R   [4..12] R, row-major (the identity, or the base joint's euler_matrix :371-374)
+ *   [13..15] corner0[0]   [16..18] norm_factors[0] per axis   [19..21] 0.5 * (corner0[1] - corner0[0]) * norm_factors[0]
+ *   then per part j, ANCSH_RIG_PART(K) = 15 + 9K wide, at ANCSH_RIG_HEAD + j * ANCSH_RIG_PART(K):
+ *   [0..2] sub_j (0, or link_xyz[j][0] :613)   [3..5] corner_j[0]   [6..8] factor_j per axis   [9..11] 0.5 * (corner_j[1] - corner_j[0]) *
+ *   factor_j, all of norm_*[j+1]   [12] cls_out   [13] jcls_out, < 0: not set   [14] n_j entries   [15 + 9k ..] entry k:
+ *   [P0 (3) | l (3) | id | kind (0 line, 1 constant, 2 origin) | |l|^2].
+ * For a row of part j, float64 throughout (the seven float32 inputs widened), evaluated as written, no contraction:
+ *   cc = c - sub_j;  g0 = ((cc - corner0[0]) * nf0 + 0.5) - tail0 (:498 / :625);  p0 likewise with part j's own three vectors (:494 / :621);
+ *   heatmap = 0, unitvec = 0, orient = 0, jcls = rig[1]; then entries k = 0 .. n_j - 1 in order, a later one overwriting an earlier one:
+ *     line: d = g0 - P0, off = ((d0 l0 + d1 l1) + d2 l2) * l / |l|^2 - d (lib/d3_utils.py:192-203);  constant: off = 0.5 * thres_r (x3, :633-635);
+ *     origin: the line's formula with d = 0 - P0, and the entry reaches only the part's FIRST row -- the cloud's first row or one whose
+ *     predecessor holds another part value.  This is what the reference computes for a sapien revolute joint: :638 measures the NAOCS
+ *     origin, not the part's points, so the offset is one (1, 3) row and np.where (:683) can name index 0 of the part only;
+ *     h = sqrt((off0^2 + off1^2) + off2^2), u = off / (h + 1e-7);  selected when h < (or <=) thres_r, a constant entry when h > 0; a NaN h
+ *     (a zero axis) selects nothing;  selected: heatmap = 1 - h / thres_r, unitvec = u, orient = l, jcls = id;
+ *   cls = cls_out, joint_cls = jcls_out if set (sapien relabels the whole part, :697-699) else jcls;
+ *   rig[3] set: nocs_p = R (p0 - 0.5) + 0.5, nocs_g = R (g0 - 0.5) + 0.5, unitvec = R unitvec, orient = R orient, each row of R summed
+ *   (x + y) + z; the heat-map is that of the unrotated g0, as in the reference.
+ * rows[r] = [x y z bit for bit | cls | nocs_p | nocs_g | heatmap | unitvec | orient | joint_cls], every value rounded to float32 once, as
+ * the reference's .astype(np.float32) rounds its float64 arrays.  A row whose part is not an integer in [0, K) never indexes the rig: cls =
+ * joint_cls = -1 and NaN in the 13 columns between.  A non-finite c poisons its own row only.  Rows outside [offsets[0], offsets[nclouds])
+ * are left untouched, and so is a cloud whose rows are empty or outside [0, capacity).  Deterministic byte for byte, no atomics.
+ * Graph-capturable: the grid depends on (capacity, nclouds) only, every cloud size is read from device offsets; no host sync, no
+ * allocation.  nclouds == 0 launches nothing.  Checked before any launch: 0 <= nclouds <= 65535, 1 <= K <= 8, rig_ld ==
+ * ANCSH_RIG_WIDTH(K), 0 <= capacity < 2^30, null pointers. */
+#define ANCSH_RIG_ROT 4
+#define ANCSH_RIG_GMAP 13
+#define ANCSH_RIG_HEAD 22
+#define ANCSH_RIG_ENTRY 9
+#define ANCSH_RIG_PART(K) (15 + ANCSH_RIG_ENTRY * (K))
+#define ANCSH_RIG_WIDTH(K) (ANCSH_RIG_HEAD + (K) * ANCSH_RIG_PART(K))
+int ancsh_point_gt_build(int nclouds, int K, const float *src, long capacity, const int *offsets, const double *rig, int rig_ld,
+                         float *rows, void *stream);
 
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 

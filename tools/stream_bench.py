@@ -3,7 +3,8 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
-                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth] [--point-gt] [--no-baseline]
+                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth] [--point-gt [--build-point-gt]]
+                                 [--no-baseline]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
 --overflow-every K, one cloud of every K-th batch has a norm factor of 1e6 (absolute xyz beyond f16's range: flagged, refit in f32).  The
@@ -16,6 +17,9 @@ columns wider (the errors against it, ancsh_gt_error_rec), one more launch a ste
 --point-gt (with --articulation) streams with AncshPipeline(point_ground_truth=True): the clouds are (n_raw, 18) rows with per-point ground
 truth (4.5 times the bytes of an [x y z joint_cls] row over the link), every batch carries (32, 13) frames in, the record comes back 21
 columns wider (both networks' test losses and the joint errors, ancsh_point_gt_rec), one more launch a step.
+--build-point-gt (with --point-gt) streams with AncshPipeline(build_point_gt=True): the clouds are (n_raw, 7) annotated rows [x y z | cx cy cz |
+part] (28 bytes a row over the link instead of 72), every batch carries (32, RIG_WIDTH) rigs in (two revolute joints on part 0,
+dataset.pack_joint_rig), and the step's first launch builds the 18-column rows on the device (ancsh_point_gt_build), one more launch a step.
 --no-baseline skips the load_inputs + step() leg (step_clouds_per_s and ratio are then null): for A/B runs of the stream alone.
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 --joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
@@ -53,6 +57,8 @@ def main():
                     help="AncshPipeline(ground_truth=True): a ground truth per batch in, the streamed record 12 error columns wider")
     ap.add_argument("--point-gt", action="store_true",
                     help="with --articulation: AncshPipeline(point_ground_truth=True): 18-column clouds and frames in, the record 21 columns wider")
+    ap.add_argument("--build-point-gt", action="store_true",
+                    help="with --point-gt: AncshPipeline(build_point_gt=True): 7-column annotated clouds and rigs in, the rows built on the device")
     ap.add_argument("--no-baseline", action="store_true", help="skip the load_inputs + step() leg")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
@@ -64,6 +70,8 @@ def main():
         ap.error("--joint-states needs --articulation")
     if args.point_gt and not args.articulation:
         ap.error("--point-gt needs --articulation")
+    if args.build_point_gt and not args.point_gt:
+        ap.error("--build-point-gt needs --point-gt")
     extra = args.arithmetic is not None
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
@@ -73,7 +81,16 @@ def main():
         c = make_cloud(i, N=int(n), K=K)
         raw.append(np.concatenate([c["P"], c["cls_gt"][:, None].astype(np.float32)], 1))
     predicted = args.joint_source == "predicted"
-    if args.point_gt:            # 18-column rows: the part label, random ground-truth channels (the launch's cost does not depend on them), the joint label
+    rigs = None
+    if args.build_point_gt:      # 7-column rows: random canonical coordinates, the part label; one rig for every cloud (the launch's cost does not depend on it)
+        from articulated_pose_amd.dataset import pack_joint_rig
+        raw = [np.concatenate([r[:, :3], rs.uniform(-0.3, 0.3, (r.shape[0], 3)).astype(np.float32), r[:, 3:]], 1) for r in raw]
+        corners = np.array([[[-0.5, -0.5, -0.5], [0.5, 0.5, 0.5]]] + [[[-0.3, -0.3, -0.3], [0.3, 0.3, 0.3]]] * K)
+        factors = 1.0 / np.linalg.norm(corners[:, 1] - corners[:, 0], axis=1)
+        joints = {"link": {"xyz": [[0, 0, 0], [0.05, 0, 0], [0, -0.05, 0.1]]},
+                  "joint": {"axis": [[0, 0, 0], [1.0, 0.05, 0], [0, 0.1, 1.0]], "parent": [-1, 0, 0]}}
+        rigs = np.tile(pack_joint_rig(corners, factors, joints, [[j] for j in range(K)])[0], (B, 1))
+    elif args.point_gt:          # 18-column rows: the part label, random ground-truth channels (the launch's cost does not depend on them), the joint label
         raw = [np.concatenate([r[:, :4], rs.uniform(0, 1, (r.shape[0], 13)).astype(np.float32), r[:, 3:]], 1) for r in raw]
     elif predicted:
         raw = [np.ascontiguousarray(r[:, :3]) for r in raw]
@@ -89,7 +106,8 @@ def main():
         gts = np.concatenate([R, rs.uniform(0.5, 1.5, a.shape + (1,)), rs.uniform(-0.3, 0.3, a.shape + (3,)), rs.uniform(0.3, 0.9, a.shape + (3,)),
                               rs.uniform(-0.3, 0.3, a.shape + (3,))], -1)
     frames = rs.normal(size=(len(batches), B, 13)) if args.point_gt else None
-    with_gt = lambda k, c, nf: (c, nf) + ((gts[k],) if args.ground_truth else ()) + ((frames[k],) if args.point_gt else ())
+    with_gt = lambda k, c, nf: (c, nf) + ((gts[k],) if args.ground_truth else ()) + ((frames[k],) if args.point_gt else ()) + \
+        ((rigs,) if args.build_point_gt else ())
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
 
     # streaming
@@ -98,7 +116,8 @@ def main():
     pipe = AncshPipeline(K, wa, wn, B, N, dev, couple=True, slots=args.slots, raw_capacity=B * 3000, arithmetic=args.arithmetic,
                          range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
                          joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality,
-                         ground_truth=args.ground_truth, point_ground_truth=args.point_gt).prepare()
+                         ground_truth=args.ground_truth, point_ground_truth=args.point_gt,
+                         **(dict(build_point_gt=True) if args.build_point_gt else {})).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches([with_gt(k, c, nf) for k, (c, nf) in enumerate(batches)]):          # warm-up: every slot replayed with real input
@@ -133,7 +152,7 @@ def main():
     pre = []
     for k, (c, nf) in enumerate([] if args.no_baseline else batches):
         if args.point_gt:
-            c = [np.ascontiguousarray(r[:, [0, 1, 2, 17]]) for r in c]
+            c = [np.ascontiguousarray(r[:, [0, 1, 2, 6 if args.build_point_gt else 17]]) for r in c]
         s = sample_raw_batch(c, N, nf, k, dev, xyz_only=predicted)
         pre.append((s["P"].cpu().numpy(), None if predicted else s["joint_cls"].cpu().numpy()))
     base = None
@@ -185,7 +204,9 @@ def main():
     if args.ground_truth:
         line.update({"ground_truth": True, "record_columns": int(rec.shape[2])})
     if args.point_gt:
-        line.update({"point_ground_truth": True, "record_columns": int(rec.shape[2]), "h2d_row_bytes": 72})
+        line.update({"point_ground_truth": True, "record_columns": int(rec.shape[2]), "h2d_row_bytes": 28 if args.build_point_gt else 72})
+    if args.build_point_gt:
+        line.update({"build_point_gt": True})
     if predicted:
         line.update({"joint_source": "predicted"})
     if args.dense:
