@@ -140,6 +140,9 @@ SIGNATURES = {
     # the per-point ground truth itself, built from annotated clouds in front of the sampler (no ABI bump, detected by its symbol): nclouds, K,
     # src, capacity, offsets, rig, rig_ld, rows, stream
     "ancsh_point_gt_build": [_c_int, _c_int, _vp, _c_long, _vp, _vp, _c_int, _vp, _vp],
+    # the annotated clouds themselves, made from depth and link-label crops (no ABI bump, detected by its symbol): nclouds, depth_type, depth,
+    # labels, pixel_capacity, geom, scene, rows, capacity, offsets, counts, link_counts, scratch, stream
+    "ancsh_depth_annotate_stream": [_c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

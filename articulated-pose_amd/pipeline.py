@@ -178,7 +178,7 @@ class _Slot(object):
             self.np_seed, self.np_off, self.np_nf = hdr[lay.seed].view(np.int64), hdr[lay.off], hdr[lay.nf].view(np.float32)
             self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
             if depth:
-                self._init_depth(B, raw_capacity, depth, device)
+                self._init_depth(B, raw_capacity, depth, device, annotate=build_point_gt)
             else:
                 # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
                 rs = np.random.RandomState(0)
@@ -205,6 +205,8 @@ class _Slot(object):
                            refit=range_guard)]
             if depth:
                 outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
+                if build_point_gt:      # annotated frames: the valid pixels per link (ancsh_depth_annotate_stream's link_counts)
+                    outs.append(Output("link_counts", lambda sl, f32: (sl.link_counts,), pinned(torch.int32, B, 16)))
             if articulation:
                 outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, self.art_width),
                                    refit=range_guard))
@@ -220,17 +222,21 @@ class _Slot(object):
             img = self.outputs.get("label_images")
             self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
 
-    def _init_depth(self, B, capacity, depth, device):
+    def _init_depth(self, B, capacity, depth, device, annotate=False):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
         counts, and host / device views of the header's geometry, camera and dest blocks.  Until the first submit: B crops of random
-        depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes)."""
-        from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS
+        depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes).
+        annotate (annotated frames, ancsh_depth_annotate_stream): the mask buffers carry the link labels -- the same bytes per pixel --, the
+        scratch holds 16 counters per chunk, and the slot owns the (B, SCENE_WIDTH) float64 scene tables with their pinned twin, copied
+        with the header like the rigs, and the per-link counts; the header's camera block is not read.  Until the first submit: one link
+        with the identity map behind that unit camera, every pixel labelled 0."""
+        from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS, SCENE_HEAD, SCENE_MAX_LINKS, SCENE_WIDTH
         npt, tt, _ = DEPTH_DTYPES[depth]
         self.pix = torch.zeros((capacity,), dtype=tt, device=device)
         self.mask = torch.zeros((capacity,), dtype=torch.uint8, device=device)
         self.h_pix = torch.zeros((capacity,), dtype=tt).pin_memory()
         self.h_mask = torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
-        self.scratch = torch.zeros((B * MAX_CHUNKS,), dtype=torch.int32, device=device)
+        self.scratch = torch.zeros((B * MAX_CHUNKS * (SCENE_MAX_LINKS if annotate else 1),), dtype=torch.int32, device=device)
         self.counts = torch.zeros((B,), dtype=torch.int32, device=device)
         lay, hdr = self.layout, self.h_hdr.numpy()
         self.np_pix, self.np_mask = self.h_pix.numpy().view(npt), self.h_mask.numpy()
@@ -249,10 +255,20 @@ class _Slot(object):
         else:
             self.np_pix[:] = rs.uniform(0.5, 1.0, capacity).astype(np.float32)
             scale = 1.0
-        self.np_mask[:] = 1
+        self.np_mask[:] = 0 if annotate else 1
         for b in range(B):
             self.np_geom[b] = (b * per, h, w, 0, 0)
             self.np_cam[b] = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
+        self.scene = self.link_counts = None
+        if annotate:
+            self.h_scene = torch.zeros((B, SCENE_WIDTH), dtype=torch.float64).pin_memory()
+            self.np_scene = self.h_scene.numpy()
+            unit = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5)
+            self.np_scene[:, 0:6], self.np_scene[:, 6], self.np_scene[:, 7:13] = unit, scale, unit
+            self.np_scene[:, 13], self.np_scene[:, 14] = 10, 1
+            self.np_scene[:, SCENE_HEAD + 2:SCENE_HEAD + 14] = np.eye(4)[:3].reshape(12)      # link 0: rank 0, part 0, M = [I | 0]
+            self.scene = self.h_scene.to(device)
+            self.link_counts = torch.zeros((B, SCENE_MAX_LINKS), dtype=torch.int32, device=device)
         if lay.dest is not None:
             self.np_dest[:] = self.np_geom[:, 0]
         self.np_nf[:] = 1.0
@@ -357,9 +373,11 @@ class AncshPipeline(object):
         # streamed record was (26, 39, 38 or 51 columns).  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is this
         # widest one.  joint_source="gt" reads the rows' column 17 as the joint label; "predicted" reads it for the losses only.
         from .pose.point_gt import check_loss_type, check_point_ground_truth
-        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation, depth_capacity is not None)
+        # (depth frames carry no per-point ground truth -- unless build_point_gt=True makes it from link labels and scenes, see below)
+        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation,
+                                                           depth_capacity is not None and not build_point_gt)
         self.coord_regress_loss = check_loss_type(coord_regress_loss)
-        if self.point_ground_truth and raw_capacity is None:
+        if self.point_ground_truth and raw_capacity is None and depth_capacity is None:
             raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
         # build_point_gt (with point_ground_truth=True): the stream takes (n_raw, 7) annotated clouds [x y z | cx cy cz | part]
         # (dataset.pack_annotated_cloud) and one rig per cloud (dataset.pack_joint_rig, submit(..., rig=...)), and the captured step's first
@@ -396,6 +414,15 @@ class AncshPipeline(object):
         if label_images and depth_capacity is None:
             raise ValueError("label_images=True carries the labels back to the pixels of depth frames: it needs depth_capacity")
         self.label_images = bool(label_images)
+        # annotated depth frames (depth_capacity with point_ground_truth=True, build_point_gt=True): a frame is a depth crop, a link-label
+        # crop and one (240,) float64 scene table (depth.pack_frame_scene), and the captured step starts with ancsh_depth_annotate_stream
+        # (two launches: the slot's crops -> its 7-column annotated rows, link-major as dataset.pack_annotated_cloud packs them, offsets,
+        # counts and per-link counts), then ancsh_point_gt_build and the xyz sampler on the 18-column rows: 3 bytes per pixel (uint16) cross
+        # to the device, and nothing of the reference's preprocessing runs on the host.  submit_depth(..., scene=, rig=, frame=).
+        self.link_counts = self.depth_capacity is not None and self.build_point_gt
+        if self.link_counts and self.label_images:
+            raise ValueError("label_images=True carries rows back to pixels in pixel order; the rows of annotated depth frames "
+                             "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
         # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
         # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls; predicted: x y z) per batch, padding included
         if raw_capacity is not None:
@@ -522,10 +549,13 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.link_counts:               # annotated depth frames: the slot's depth and label crops -> its annotated rows, offsets and counts
+            from .depth import depth_annotate
+            depth_annotate(sl.pix, sl.mask, sl.geom, sl.scene, out=(sl.src_rows, off, sl.counts, sl.link_counts), scratch=sl.scratch)
         if self.build_point_gt:            # the slot's annotated rows and rigs -> its 18-column rows, in front of the unchanged sampler
             from .dataset import point_gt_build
             point_gt_build(sl.src_rows, off, sl.rig, self.K, sl.raw_rows)
-        if self.depth_dtype is not None:   # the depth front end: the slot's crops -> its rows, offsets and counts, in front of the xyz sampler
+        if self.depth_dtype is not None and not self.link_counts:   # the depth front end: the slot's crops -> its rows, offsets and counts, in front of the xyz sampler
             from .depth import depth_unproject
             depth_unproject(sl.pix, sl.mask, sl.geom, sl.cam, out=(sl.raw_rows, off, sl.counts), scratch=sl.scratch)
         if self.predicted:                 # xyz rows: the sampler's xyz twin, same P (no joint_cls: the fit reads the index head)
@@ -724,21 +754,39 @@ class AncshPipeline(object):
             return len(valid), nf, stage
         self._enqueue(front, seed, tag, cloud_base, gt, frame, rig)
 
-    def submit_depth(self, frames, norm_factors, cameras, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None):
+    def submit_depth(self, frames, norm_factors, cameras=None, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None, scene=None,
+                     frame=None, rig=None):
         """Enqueue one batch of depth frames (asynchronous; a pipeline built with depth_capacity): frames = 1..batch_size tuples
         (depth_crop (h, w) of the pipeline's depth_dtype, mask_crop (h, w) bool / integer or None = every pixel, (row0, col0) = the crop's
         origin in the full image); norm_factors = one finite float per frame; cameras = one 6-vector of unprojection coefficients
         (depth.unprojection_from_intrinsics / unprojection_from_projmat) or one per frame; depth_scale = one value or one per frame
         (depth unit -> the cloud's unit).  The valid pixels of each crop (mask non-zero and a usable depth) become the frame's cloud on the
         device; a frame without one gives an all-NaN record and count 0.  A short batch is padded with its first frame (whose pixels are
-        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base, gt: as submit().  Bad input
+        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base, gt: as submit().
+        A pipeline built with point_ground_truth=True, build_point_gt=True takes annotated frames: the second element of a frame is its
+        link-label crop (h, w), an integer array whose values outside [0, nlinks) are not object, and scene = one (240,) float64 table
+        (depth.pack_frame_scene) or one per frame carries the camera, the depth scale and every link's map -- cameras stays None and
+        depth_scale is not read.  A frame in which a used link has fewer valid pixels than its scene's minimum gives an all-NaN record and
+        count 0, like one without a valid pixel.  rig (required) and frame: as submit() takes them.  scene, frame or rig on any other
+        pipeline: ValueError.  Bad input
         raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.  Either way the pipeline stays usable."""
         if self.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
+        annotated = getattr(self, "link_counts", False)
+        if scene is not None and not annotated:
+            raise ValueError("scene needs AncshPipeline(..., depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True)")
 
         def front():
-            from .depth import check_depth_frames, pack_depth_frames
-            depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
+            from .depth import check_annotated_frames, check_depth_frames, pack_depth_frames
+            if annotated:
+                if scene is None or rig is None or cameras is not None:
+                    raise ValueError("a pipeline built with point_ground_truth=True, build_point_gt=True takes annotated frames: "
+                                     "submit_depth(frames, norm_factors, scene=..., rig=...) needs one depth.pack_frame_scene table and "
+                                     "one dataset.pack_joint_rig table per frame, and cameras=None (the scene carries the camera)")
+                depths, masks, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scene, self.depth_dtype, self.K, self.B)
+                cam = None
+            else:
+                depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
             n_valid = len(depths)
             pixels = sum(d.size for d in depths)
             padded = pixels + (self.B - n_valid) * depths[0].size
@@ -749,6 +797,10 @@ class AncshPipeline(object):
             def stage(sl):
                 pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
                 sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
+                if annotated:                              # the scenes; a padding cloud is a copy of the first frame, scene included
+                    sl.np_scene[:n_valid] = scenes
+                    sl.np_scene[n_valid:] = scenes[0]
+                    return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels]), (sl.scene, sl.h_scene)]
                 sl.np_cam[:n_valid] = cam
                 sl.np_cam[n_valid:] = cam[0]
                 if self.label_images:                      # a valid frame's image lies where its crop does; a padding cloud writes none
@@ -756,7 +808,7 @@ class AncshPipeline(object):
                     sl.np_dest[n_valid:] = -1
                 return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
             return n_valid, nf, stage
-        self._enqueue(front, seed, tag, cloud_base, gt)
+        self._enqueue(front, seed, tag, cloud_base, gt, frame, rig)
 
     def _enqueue(self, front, seed, tag, cloud_base, gt=None, frame=None, rig=None):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
@@ -827,7 +879,7 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self, flags=False, articulation=False, dense=False, label_images=False):
+    def retire(self, flags=False, articulation=False, dense=False, label_images=False, link_counts=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
         the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph; built with
@@ -845,15 +897,20 @@ class AncshPipeline(object):
         pipeline built with label_images=True): + a list with one (labels (h, w) int32, values (h, w, 7) float32) pair per valid frame,
         aligned with the submitted crop, behind the articulation block and in front of the counts: a valid pixel holds its row's label and
         [W of the label | part NOCS | NAOCS] (as dense), every other pixel -1 / NaN (flagged clouds: the f32 graph's images).
-        The tuple's order is stream.RESULT_ORDER (stream.unpack_results reads it by name)."""
+        The tuple's order is stream.RESULT_ORDER (stream.unpack_results reads it by name).  link_counts=True (a pipeline of annotated
+        depth frames: depth_capacity with point_ground_truth=True, build_point_gt=True): + the (n_valid, 16) int32 valid pixels per link
+        of the batch's frames, behind everything else."""
         check_built_with(self, "retire", "AncshPipeline", articulation=articulation, dense=dense, label_images=label_images)
+        if link_counts and not getattr(self, "link_counts", False):
+            raise RuntimeError("retire(link_counts=True) needs AncshPipeline(..., depth_capacity=<pixels>, point_ground_truth=True, "
+                               "build_point_gt=True)")
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
         asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, counts=self.depth_dtype is not None)
         # the flag words decide the refit whether or not the caller asked for them
-        want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked[o.name]]
+        want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked.get(o.name) or (link_counts and o.name == "link_counts")]
         got = {o.name: o.value(sl, n_valid) for o in want}
         got.setdefault("flags", np.zeros((n_valid,), np.int32))
         hit = np.flatnonzero(got["flags"])
@@ -867,7 +924,12 @@ class AncshPipeline(object):
             for o in refit:
                 o.patch(got[o.name], o.value(sl, n_valid, f32=True), hit)
             self.f32_reruns += 1
-        return pack_results(dict(got, tag=tag, seed=seed), **asked)
+        if getattr(self, "link_counts", False):
+            # annotated frames: a frame without rows (no valid pixel, or a link below the minimum: the reference skips it) carries no
+            # information.  Its pose record and its losses are NaN from the device; ancsh_point_gt_rec's two point counts read 0 there (no
+            # sampled point has a part), and are blanked here, so that the whole row is NaN
+            got["record"][got["counts"] == 0] = np.nan
+        return pack_results(dict(got, tag=tag, seed=seed), **asked) + ((got["link_counts"],) if link_counts else ())
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
@@ -889,10 +951,13 @@ class AncshPipeline(object):
             self.submit(item[0], item[1], tag=item[2 + g + f + r] if len(item) > 2 + g + f + r else k, **more)
         yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, dense))
 
-    def stream_depth_batches(self, batches, cameras, depth_scale=1.0, flags=False, articulation=False, label_images=False):
+    def stream_depth_batches(self, batches, cameras=None, depth_scale=1.0, flags=False, articulation=False, label_images=False,
+                             link_counts=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
-        last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base / gt; yields what retire() returns, in
-        submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them)."""
+        last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base / gt / scene / frame / rig (annotated
+        frames travel with their scene and rig there); yields what retire() returns, in
+        submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them; link_counts=True,
+        annotated frames: the (n_valid, 16) per-link counts behind them)."""
         check_built_with(self, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
 
         def submit(k, item):
@@ -902,4 +967,5 @@ class AncshPipeline(object):
                 kw.update(item[-1])
                 item = item[:-1]
             self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
-        yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, label_images=label_images))
+        yield from pump(batches, self._inflight, len(self.slots), submit,
+                        lambda: self.retire(flags, articulation, label_images=label_images, link_counts=link_counts))

@@ -32,7 +32,8 @@ def check_point_ground_truth(point_ground_truth, articulation, depth=False):
     if point_ground_truth and not articulation:
         raise ValueError("point_ground_truth=True compares against the articulation block's joints: it needs articulation=True")
     if point_ground_truth and depth:
-        raise ValueError("point_ground_truth=True reads 18-column raw rows: depth frames (depth_capacity) carry no per-point ground truth")
+        raise ValueError("point_ground_truth=True reads 18-column raw rows: depth frames (depth_capacity) carry no per-point ground truth "
+                         "(build_point_gt=True makes it on the device from link-label crops and scene tables)")
     return bool(point_ground_truth)
 
 

@@ -45,7 +45,8 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_depth_label_images (the depth front end and its label / NOCS images), ancsh_joint_state_rec (the
                                  *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
                                  *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_point_gt_build (that ground truth built from
-                                 *     annotated clouds), ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
+                                 *     annotated clouds), ancsh_depth_annotate_stream (those clouds made from depth and link-label crops),
+                                 *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
                                  *     stage-B problem: the prismatic objective);
@@ -1093,6 +1094,49 @@ int ancsh_depth_unproject_stream(int nclouds, int depth_type, const void *depth,
 int ancsh_depth_label_images(int nclouds, int depth_type, const void *depth, const unsigned char *mask, long pixel_capacity,
                              const int *geom, const int *offsets, const int *scratch, const int *labels, const float *values,
                              long capacity, const int *dest, int *img_labels, float *img_values, long image_capacity, void *stream);
+
+/* Rendered depth frames annotated on the device: the step of tools/preprocess_data.py:259-320 that makes a frame's gt_points and gt_coords,
+ * and the order in which lib/dataset.py:475-485 concatenates them -- depth crops, link-label crops and one scene table per frame -> the
+ * 7-column rows [x y z | cx cy cz | part] ancsh_point_gt_build reads (dataset.pack_annotated_cloud's), in TWO launches on
+ * ancsh_depth_unproject_stream's grid and chunking.  The ABI version is unchanged; callers detect the entry by its symbol.
+ *   nclouds, depth_type, depth, pixel_capacity, geom : as ancsh_depth_unproject_stream takes them;
+ *   labels : pixel_capacity bytes, 8-byte aligned (never NULL): a pixel's byte is its link index; 255, or any value >= nlinks, is not object;
+ *   scene  : (nclouds, ANCSH_SCENE_WIDTH = 240) float64, 8-byte aligned, per cloud:
+ *     [0..5] A00 A01 A02 A10 A11 A12 of gt_points (cloud_cam_real, :293-296, v1 = row * 2 / H - 1)   [6] depth_scale
+ *     [7..12] C00 C01 C02 C10 C11 C12 of the coordinate point (cloud_cam, :288-291, v = (H - row) * 2 / H - 1)
+ *     [13] min_link_pixels (:279-281: 10)   [14] nlinks, 1..ANCSH_SCENE_MAX_LINKS   [15] reserved, 0
+ *     then per link l, ANCSH_SCENE_LINK = 14 wide, at ANCSH_SCENE_HEAD + 14 l:  [0] rank = the link's position in the flattened
+ *     parts_map, -1 = the link is not used (its pixels are dropped and it does not count for the minimum)   [1] part = its group's index
+ *     [2..13] M, row-major 3 x 4: camera -> URDF frame of the link, the chain of :298-320 composed on the host in float64
+ *     (pinv(viewMat.T) with its first three rows negated, pinv(parts_model2world[l].T), my_canon2urdf_mat.T).
+ * Pixel (i, j) of the crop, label l, depth d, is VALID when l names a used link and d != 0 (uint16) / d > 0 && d < +inf (float32) -- the
+ * rule of ancsh_depth_unproject_stream.  (The reference keeps every labelled pixel, holes included: its renderer leaves none on an object.)
+ * Its row, with row = row0 + i, col = col0 + j as float64, in exactly this float64 arithmetic (no contraction), every output rounded to
+ * float32 once:
+ *   z = d * depth_scale;  x = z * ((A00 col + A01 row) + A02);  y = z * ((A10 col + A11 row) + A12);
+ *   x' = z * ((C00 col + C01 row) + C02);  y' = z * ((C10 col + C11 row) + C12);
+ *   c_a = ((M[a][0] x' + M[a][1] y') + M[a][2] z) + M[a][3], a = 0..2;   the row is [x y z | c_0 c_1 c_2 | part].
+ * A cloud in which a used link has fewer than min_link_pixels valid pixels has no rows (the reference skips such a frame); otherwise its
+ * rows are its valid pixels sorted by (rank of the link, row-major pixel order): a stable counting sort, so the rows of a part are
+ * neighbours, in the order lib/dataset.py:475-485 gives them.
+ * Outputs: link_counts (nclouds, 16) int32 = valid pixels per link (0 for a link that is not used), whether or not the cloud passes the
+ * minimum; counts (nclouds) int32 = rows per cloud; offsets (nclouds + 1) int32, offsets[0] = 0, offsets[b+1] = offsets[b] + max(counts[b],
+ * 1) (saturating at 2^31 - 1); rows (capacity, 7) float32.  A cloud without rows -- or whose crop has h < 1, w < 1 or lies outside [0,
+ * pixel_capacity), or whose scene's nlinks is outside 1..16 -- gets ONE row of seven NaNs and counts[b] = 0: ancsh_point_gt_build makes
+ * an all-NaN row of it, and the cloud's record alone is poisoned.  Rows at and beyond offsets[nclouds] or capacity are left untouched.
+ * Deterministic byte for byte: a count pass (block (x, b) writes the 16-entry histogram of chunk x of cloud b into scratch[(b * chunks + x) *
+ * 16 ..]) and a scatter pass (each block derives every start it needs from the histograms and ranks its pixels with per-link wave
+ * ballots); no atomics, no block waits for another.  scratch: nclouds * ANCSH_DEPTH_MAX_CHUNKS * 16 int32 of working memory.
+ * Graph-capturable: the grid depends on (pixel_capacity, nclouds) only; no host sync, no allocation.  nclouds == 0 launches nothing.
+ * Checked before any launch: 0 <= nclouds <= 65535, depth_type, 0 <= pixel_capacity < 2^30, pixel_capacity <= capacity < 2^30, null
+ * pointers, the three alignments (depth 16 bytes, labels and scene 8 bytes). */
+#define ANCSH_SCENE_WIDTH 240
+#define ANCSH_SCENE_MAX_LINKS 16
+#define ANCSH_SCENE_HEAD 16
+#define ANCSH_SCENE_LINK 14
+int ancsh_depth_annotate_stream(int nclouds, int depth_type, const void *depth, const unsigned char *labels, long pixel_capacity,
+                                const int *geom, const double *scene, float *rows, long capacity, int *offsets, int *counts,
+                                int *link_counts, int *scratch, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows
