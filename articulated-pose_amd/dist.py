@@ -14,7 +14,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .stream import check_built_with, only_asked, pack_results, pump, unpack_results
+from .stream import (check_built_with, check_options, check_side_inputs, only_asked, pack_results, pump, refuse_side_inputs,
+                     require_side_inputs, split_item, unpack_results)
 
 CHILD_ENV = "ANCSH_LOCAL_RANK_CHILD"      # set in the ranks launch_local_ranks() starts: they must not launch again
 
@@ -334,72 +335,30 @@ class ShardedPipeline(object):
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False, build_point_gt=False,
                  **pipeline_kw):
-        from .pipeline import check_joint_source
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
         if pipeline_kw.get("depth_capacity") is not None:
             raise ValueError("ShardedPipeline does not shard the depth front end (depth_capacity): stream depth frames through "
                              "AncshPipeline.submit_depth on one GPU")
-        if joint_types is not None:        # the kinds belong to the object class, so every rank's shard gets the same K - 1 of them per cloud
-            pipeline_kw.update(joint_types=joint_types)
-        self.joint_source = check_joint_source(joint_source)
-        if joint_source != "gt":           # the default is not passed on: a per-rank stand-in built before joint_source need not know it
-            pipeline_kw.update(joint_source=joint_source)
-        self.couple = bool(pipeline_kw.get("couple", True))
-        # articulation (raw streams only): every rank's pipeline appends the (n, K, 12) articulation block, and retire() gathers it with the
-        # records in the SAME gather -- one (n_max, K, 38) float64 row per rank, split on dst.  step() / records() (the RCCL path) do not
-        # carry it.
-        if articulation and raw_capacity is None:
-            raise ValueError("articulation=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
-        self.articulation = bool(articulation)
-        if self.articulation:
-            pipeline_kw.update(articulation=True)
-        # joint_states (with articulation): every rank's block is the (n, K, 20) one (AncshPipeline(joint_states=True)) and the gathered row
-        # grows to 26 + 20 doubles: still one gather per batch
-        from .pose.joint_params import check_joint_states
-        self.joint_states = check_joint_states(joint_states, self.articulation)
-        if self.joint_states:
-            pipeline_kw.update(joint_states=True)
-        self.art_width = 20 if self.joint_states else 12
-        # fit_quality (raw streams only): every rank streams the (n, K, 39) wide record (AncshPipeline(fit_quality=True)), and retire()
-        # gathers rows of record_width doubles (+ the articulation block): step() / records() (the RCCL path) keep the 26-column record
-        if fit_quality and raw_capacity is None:
-            raise ValueError("fit_quality=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
-        from .pose.quality import FIT_QUALITY_WIDTH, check_fit_quality
-        self.fit_quality = check_fit_quality(fit_quality, pipeline_kw.get("inlier_th", 0.1))
-        if self.fit_quality:
-            pipeline_kw.update(fit_quality=True)
-        self.record_width = FIT_QUALITY_WIDTH if self.fit_quality else 26
-        # ground_truth (raw streams only): every rank streams the record 12 columns wider (AncshPipeline(ground_truth=True)) and gets its
-        # shard's rows of the batch's ground truth from submit()
-        if ground_truth and raw_capacity is None:
-            raise ValueError("ground_truth=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity")
-        self.ground_truth = bool(ground_truth)
-        if self.ground_truth:
-            from .pose.gt_errors import GT_ERROR_WIDTH
-            pipeline_kw.update(ground_truth=True)
-            self.record_width += GT_ERROR_WIDTH
-        # point_ground_truth (raw streams with articulation): every rank streams the record 21 columns wider
-        # (AncshPipeline(point_ground_truth=True)) from its shard's 18-column clouds and frames
-        from .pose.point_gt import POINT_GT_WIDTH, check_point_ground_truth
-        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation)
-        if self.point_ground_truth:
-            if raw_capacity is None:
-                raise ValueError("point_ground_truth=True is carried by the raw stream only (submit / retire / stream_batches): it needs "
-                                 "raw_capacity")
-            pipeline_kw.update(point_ground_truth=True)
-            self.record_width += POINT_GT_WIDTH
-        # build_point_gt (with point_ground_truth): every rank builds its shard's rows from 7-column annotated clouds and rigs
-        if build_point_gt and not self.point_ground_truth:
-            raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
-        self.build_point_gt = bool(build_point_gt)
-        if self.build_point_gt:
-            pipeline_kw.update(build_point_gt=True)
+        # what only the raw stream carries (step() / records(), the RCCL path, keep the 26-column record), then the rules shared with
+        # AncshPipeline.  The articulation block travels with the records in the SAME gather -- one (n_max, K, record_width + art_width)
+        # float64 row per rank, split on dst --, the ground truth, frames and rigs are handed out by submit(), shard by shard.
+        for name, asked in (("articulation", articulation), ("fit_quality", fit_quality), ("ground_truth", ground_truth)):
+            if asked and raw_capacity is None:
+                raise ValueError("%s=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity" % name)
+        self.opts = o = check_options(global_batch, None, True, pipeline_kw.get("inlier_th", 0.1), raw_capacity, keyed=raw_capacity is not None,
+                                      articulation=articulation, joint_states=joint_states, fit_quality=fit_quality, ground_truth=ground_truth,
+                                      point_ground_truth=point_ground_truth, build_point_gt=build_point_gt, joint_source=joint_source)
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
-        self.dense = bool(dense)
-        if self.dense:
-            pipeline_kw.update(dense=True)
+        self.dense, self.joint_source, self.record_width, self.art_width = bool(dense), joint_source, o.record_width, o.art_width
+        self.couple = bool(pipeline_kw.get("couple", True))
+        # only what differs from the default is passed on: a per-rank stand-in built before an option need not know it
+        given = dict(joint_types=joint_types, joint_source=None if joint_source == "gt" else joint_source, dense=self.dense)
+        for name in ("articulation", "joint_states", "fit_quality", "ground_truth", "point_ground_truth", "build_point_gt"):
+            setattr(self, name, getattr(o, name))
+            given[name] = getattr(o, name)
+        pipeline_kw.update({k: v for k, v in given.items() if v})
         self.distributed = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size() if self.distributed else 1
         self.rank = dist.get_rank() if self.distributed else 0
@@ -492,7 +451,10 @@ class ShardedPipeline(object):
 
     def records(self, slot=None):
         """dst: the (global_batch, K, 26) f64 records of the batch last issued on `slot` (default: the most recent step), in global
-        cloud order; None on the other ranks.  Valid after synchronize()."""
+        cloud order; None on the other ranks.  Valid after synchronize().  Where the result lives depends on how it was gathered: without a
+        gatherer (world 1) it is the slot's own record on the pipeline's device; over RCCL it is on `device` too; with a host-staged
+        (gloo) data group -- which init_groups may have fallen back to -- it is a CPU tensor.  (gather_records() moves its result back
+        to the records' device; this method does not.)  A caller that needs one place calls .cpu() or .to(device) on it."""
         sl = slot if slot is not None else self.pipe.slots[(self.pipe._next - 1) % len(self.pipe.slots)]
         if self.gatherer is None:
             return sl.out["record"]
@@ -524,15 +486,8 @@ class ShardedPipeline(object):
     def _check_batch(self, clouds, norm_factors):
         """The checks of AncshPipeline.submit on EVERY rank's shard, so that every rank raises the same ValueError (before anything is
         enqueued and before any collective) or none does.  -> (clouds, norm factors) as check_raw_clouds returns them."""
-        from .dataset import check_raw_clouds, check_stream_key
-        if self.build_point_gt:
-            from .dataset import check_annotated_clouds
-            clouds, nf = check_annotated_clouds(clouds, norm_factors, self.K, self.global_batch)
-        elif self.point_ground_truth:
-            from .pose.point_gt import check_point_clouds
-            clouds, nf = check_point_clouds(clouds, norm_factors, self.global_batch)
-        else:
-            clouds, nf = check_raw_clouds(clouds, norm_factors, self.global_batch, xyz_only=self.joint_source == "predicted")
+        from .dataset import check_stream_key
+        clouds, nf = self.opts.rows.check(clouds, norm_factors, self.K, self.global_batch)
         for r in range(self.world):
             s, e = self.shard_of(len(clouds), r)
             if e == s:
@@ -557,44 +512,20 @@ class ShardedPipeline(object):
         missing there): the batch's (n_valid, RIG_WIDTH) rigs, handed out the same way.  World 1: the local pipeline's submit."""
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
-        if gt is not None and not self.ground_truth:
-            raise ValueError("gt needs ShardedPipeline(..., ground_truth=True)")
-        if frame is not None and not self.point_ground_truth:
-            raise ValueError("frame needs ShardedPipeline(..., point_ground_truth=True)")
-        if rig is not None and not self.build_point_gt:
-            raise ValueError("rig needs ShardedPipeline(..., point_ground_truth=True, build_point_gt=True)")
-        if rig is None and self.build_point_gt:
-            raise ValueError("a pipeline built with build_point_gt=True builds every cloud's rows from its rig: submit(..., rig=...) needs one "
-                             "dataset.pack_joint_rig table per cloud")
-        more = dict(gt=gt) if self.ground_truth else {}
-        if self.point_ground_truth:
-            more["frame"] = frame
-        if self.build_point_gt:
-            more["rig"] = rig
+        built, given = self.opts.inputs, dict(gt=gt, frame=frame, rig=rig)
+        refuse_side_inputs(built, given, "ShardedPipeline")
+        require_side_inputs(built, given)
         if self.world == 1:
-            return self.pipe.submit(clouds, norm_factors, tag=tag, **more)
+            return self.pipe.submit(clouds, norm_factors, tag=tag, **{inp.name: given[inp.name] for inp in built})
         clouds, nf = self._check_batch(clouds, norm_factors)
-        if gt is not None:
-            from .pose.gt_errors import check_ground_truth
-            gt = check_ground_truth(gt, len(clouds), self.K)
-        if frame is not None:
-            from .pose.point_gt import check_frames
-            frame = check_frames(frame, len(clouds))
-        if rig is not None:
-            from .dataset import check_rigs
-            rig = check_rigs(rig, len(clouds), self.K)
+        more = check_side_inputs(built, given, len(clouds), self.K, "ShardedPipeline")      # whole, on every rank
         if len(self._stream) == len(self.pipe.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.pipe.slots))
         seed = self.seed + 2 * self._stream_submitted
         s, e = self.shard_of(len(clouds))
         if e > s:
-            if self.ground_truth:
-                more = dict(gt=None if gt is None else gt[s:e])
-            if self.point_ground_truth:
-                more = dict(more, frame=None if frame is None else frame[s:e])
-            if self.build_point_gt:
-                more = dict(more, rig=rig[s:e])
-            self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo, **more)
+            self.pipe.submit(clouds[s:e], nf[s:e], seed=seed, tag=tag, cloud_base=self.lo,
+                             **{name: None if v is None else v[s:e] for name, v in more.items()})
         self._stream.append((tag, seed, len(clouds), e > s, np.array([c.shape[0] for c in clouds], np.int64)))
         self._stream_submitted += 1
 
@@ -686,15 +617,8 @@ class ShardedPipeline(object):
         if self.world == 1:
             yield from self.pipe.stream_batches(batches, flags, **only_asked(articulation=articulation, dense=dense))
             return
-        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
-        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth,
-        r = 1 if self.build_point_gt else 0          # and the rigs behind the frames
 
         def submit(k, item):
-            more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
-            if f:
-                more["frame"] = item[2 + g] if len(item) > 2 + g else None
-            if r:
-                more["rig"] = item[2 + g + f] if len(item) > 2 + g + f else None
-            self.submit(item[0], item[1], tag=item[2 + g + f + r] if len(item) > 2 + g + f + r else k, **more)
+            clouds, norm_factors, side, tag = split_item(item, self.opts.inputs, k)
+            self.submit(clouds, norm_factors, tag=tag, **side)
         yield from pump(batches, self._stream, len(self.pipe.slots), submit, lambda: self.retire(flags, articulation, dense))

@@ -16,8 +16,9 @@ import torch
 
 from .network import Network
 from .pose import PoseSolver
-from .stream import (Output, check_built_with, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row,
-                     pump, take_dense, take_images)
+from .stream import (JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
+                     check_side_inputs, fill_rows, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row, pump,
+                     refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
 
 
 def check_hardware_queues(slots):
@@ -63,16 +64,6 @@ def f16x2_weight_violations(nets):
     return f16_range_violations(kernels)
 
 
-JOINT_SOURCES = ("gt", "predicted")
-
-
-def check_joint_source(joint_source):
-    """-> joint_source if it names one of JOINT_SOURCES; ValueError otherwise (before anything touches the GPU)."""
-    if joint_source not in JOINT_SOURCES:
-        raise ValueError("joint_source must be one of %s, got %r" % (JOINT_SOURCES, joint_source))
-    return joint_source
-
-
 def check_joint_inputs(joint_source, couple, joint_cls, pred):
     """The joint association a load_inputs() call must carry, checked before anything is copied: "gt" needs joint_cls (a label per
     point); "predicted" with couple=False needs pred["index_per_point"] (the ANCSH network's index head, (B, N, C)); "predicted" with
@@ -89,21 +80,9 @@ def check_joint_inputs(joint_source, couple, joint_cls, pred):
 class _Slot(object):
     """Buffers + stream + captured graph of one batch in flight."""
 
-    def __init__(self, B, N, K, device, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, xyz=False,
-                 depth=None, label_images=False, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False,
-                 build_point_gt=False):
+    def __init__(self, B, N, K, device, opts):
         f = dict(dtype=torch.float32, device=device)
-        # columns of a streamed record row, and where the step leaves it: the pose record, or (fit_quality) the wide record -- its 26
-        # columns and the fit quality behind them
-        self.record_width, record_key = (39, "record_wide") if fit_quality else (26, "record")
-        if ground_truth:                        # ... and the errors against ground truth behind either (ancsh_gt_error_rec)
-            self.record_width, record_key = self.record_width + 12, "record_gt"
-        if point_ground_truth:                  # ... and the per-point ground truth's 21 columns behind whatever it was (ancsh_point_gt_rec)
-            from .pose.point_gt import POINT_GT_WIDTH
-            self.record_width, record_key = self.record_width + POINT_GT_WIDTH, "record_point_gt"
-        self.gt = self.frame = self.perm = self.src_rows = self.rig = None
-        # columns of a row of the articulation block: the box and joint columns, or (joint_states) those and the joint state behind them
-        self.art_width = 20 if joint_states else 12
+        self.record_width, self.art_width = opts.record_width, opts.art_width      # columns of a streamed record row / of a row of the articulation block
         self.P = torch.zeros((B, N, 3), **f)
         self.joint_cls = torch.zeros((B, N), dtype=torch.int32, device=device)
         self.pred_nocs = torch.zeros((B, N, 3 * K), **f)
@@ -115,122 +94,96 @@ class _Slot(object):
         self.graph = None
         self.out = None
         # range guard (F16x2): the flag words the guarded launches OR into, and the f32 graph of the same step that refits flagged clouds
-        self.flags = torch.zeros((B,), dtype=torch.int32, device=device) if range_guard else None
+        self.flags = torch.zeros((B,), dtype=torch.int32, device=device) if opts.range_guard else None
         self.graph32 = None
         self.out32 = None
-        if raw_capacity is not None:
-            # streaming: raw rows + a header (stream.header_layout) on the device, their pinned staging, the streamed outputs with their
-            # pinned twins (self.outputs), and the events that say when the staging / the outputs' twins may be touched again.
-            # keyed: the header leads with the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) instead of the seed
-            # xyz (joint_source="predicted"): rows of x y z only -- no joint-class column, a quarter fewer bytes per batch to the device
-            from .dataset import RAW_NCHAN
-            self.keyed = bool(keyed)
-            self.nchan = 3 if xyz else RAW_NCHAN
-            if point_ground_truth:
-                # 18-column rows (dataset.pack_cloud) whichever the joint source, the sampler's permutation (its perm_out) and the batch's
-                # (B, 13) float64 frames -- the ground-truth NAOCS pose of part 0 per cloud, pose.point_gt -- with their pinned twin:
-                # copied with the header; all NaN until a submit says otherwise
-                from .dataset import NCHAN
-                from .pose.point_gt import FRAME_WIDTH
-                self.nchan = NCHAN
-                self.perm = torch.zeros((B, N), dtype=torch.int32, device=device)
-                self.frame = torch.full((B, FRAME_WIDTH), float("nan"), dtype=torch.float64, device=device)
-                self.h_frame = torch.full((B, FRAME_WIDTH), float("nan"), dtype=torch.float64).pin_memory()
-                self.np_frame = self.h_frame.numpy()
-            # depth (the depth front end; raw_capacity = its pixel capacity): the rows are unprojected on the device, so they have no pinned
-            # twin; the header grows by the per-cloud crop geometry and camera (ancsh_depth_unproject_stream's geom and cam) and, with
-            # label_images, the per-cloud image start (ancsh_depth_label_images' dest) behind them
-            self.layout = lay = header_layout(B, self.keyed, bool(depth), label_images)
-            self.raw_rows = torch.zeros((raw_capacity, self.nchan), **f)
-            self.hdr = torch.zeros((lay.words,), dtype=torch.int32, device=device)
-            # what travels in: the rows themselves, or (build_point_gt) the 7-column annotated rows the step's first launch builds them from
-            # (ancsh_point_gt_build) -- the 18-column rows then have no pinned twin -- and the batch's (B, RIG_WIDTH) float64 rigs with their
-            # pinned twin, copied with the header; rigs without joints and with identity maps until a submit says otherwise
-            staged = self.nchan
-            if build_point_gt:
-                from .dataset import ANNOTATED_NCHAN, RIG_WIDTH, identity_rig
-                staged = ANNOTATED_NCHAN
-                self.src_rows = torch.zeros((raw_capacity, staged), **f)
-                self.h_rig = torch.zeros((B, RIG_WIDTH(K)), dtype=torch.float64).pin_memory()
-                self.np_rig = self.h_rig.numpy()
-                self.np_rig[:] = identity_rig(K)
-                self.rig = self.h_rig.to(device)
-            self.staged_rows = self.src_rows if build_point_gt else self.raw_rows      # the device buffer submit() copies the clouds into
-            self.h_rows = None if depth else torch.zeros((raw_capacity, staged), dtype=torch.float32).pin_memory()
-            self.h_hdr = torch.zeros((lay.words,), dtype=torch.int32).pin_memory()
-            self.h2d_done = torch.cuda.Event()
-            self.d2h_done = torch.cuda.Event()
-            if ground_truth:
-                # the batch's ground truth, one (K, 19) float64 block per cloud (pose.gt_errors), and its pinned twin: copied with the
-                # header; all NaN (no ground truth) until a submit says otherwise
-                from .pose.gt_errors import GT_WIDTH
-                self.gt = torch.full((B, K, GT_WIDTH), float("nan"), dtype=torch.float64, device=device)
-                self.h_gt = torch.full((B, K, GT_WIDTH), float("nan"), dtype=torch.float64).pin_memory()
-                self.np_gt = self.h_gt.numpy()
-            # dense / label_images: the per-raw-row (dense) or per-row and per-pixel (rowlab, img) labels / values the captured step writes
-            # (slot-owned, outside the graph's pool, so a later replay never hands their memory to another tensor) and the f32 graph's own
-            # (range guard); rowlab is device only: nobody reads rows.  Their pinned twins cost 4 + 28 bytes per row / pixel of capacity.
-            for name, built in (("dense", dense), ("rowlab", label_images), ("img", label_images)):
-                setattr(self, name, label_buffers(raw_capacity, device) if built else None)
-                setattr(self, name + "32", label_buffers(raw_capacity, device) if built and range_guard else None)
-            hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
-            self.np_rows = None if depth else self.h_rows.numpy()
-            self.np_seed, self.np_off, self.np_nf = hdr[lay.seed].view(np.int64), hdr[lay.off], hdr[lay.nf].view(np.float32)
-            self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
-            if depth:
-                self._init_depth(B, raw_capacity, depth, device, annotate=build_point_gt)
-            else:
-                # until the first submit: clouds of random rows (a defined, non-degenerate input for prepare()'s passes)
-                rs = np.random.RandomState(0)
-                self.np_rows[:, :3] = rs.uniform(-0.5, 0.5, (raw_capacity, 3))
-                if build_point_gt:
-                    self.np_rows[:, 3:6] = rs.uniform(0.0, 1.0, (raw_capacity, 3))
-                    self.np_rows[:, 6] = rs.randint(0, K, raw_capacity)
-                elif point_ground_truth:
-                    self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
-                    self.np_rows[:, 4:self.nchan - 1] = rs.uniform(0.0, 1.0, (raw_capacity, self.nchan - 5))
-                    self.np_rows[:, self.nchan - 1] = rs.randint(0, K, raw_capacity)
-                elif not xyz:
-                    self.np_rows[:, 3] = rs.randint(0, K, raw_capacity)
-                self.np_off[:] = np.arange(B + 1) * (raw_capacity // B)
-                self.np_nf[:] = 1.0
-                self.staged_rows.copy_(self.h_rows)
-                self.hdr.copy_(self.h_hdr)
-            # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
-            # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words and the depth
-            # front end's valid-pixel counts are not refit.
-            pinned = lambda dtype, *shape: lambda: (torch.zeros(shape, dtype=dtype).pin_memory(),)
-            labels = lambda: label_buffers(raw_capacity)
-            outs = [Output("record", lambda sl, f32: (sl.pick("out", f32)[record_key],), pinned(torch.float64, B, K, self.record_width),
-                           refit=range_guard)]
-            if depth:
-                outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
-                if build_point_gt:      # annotated frames: the valid pixels per link (ancsh_depth_annotate_stream's link_counts)
-                    outs.append(Output("link_counts", lambda sl, f32: (sl.link_counts,), pinned(torch.int32, B, 16)))
-            if articulation:
-                outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, self.art_width),
-                                   refit=range_guard))
-            if dense:
-                outs.append(Output("dense", lambda sl, f32: sl.pick("dense", f32), labels, refit=range_guard, extent=per_raw_row,
-                                   take=take_dense, patch=patch_dense))
-            if label_images:
-                outs.append(Output("label_images", lambda sl, f32: sl.pick("img", f32), labels, refit=range_guard, extent=per_pixel,
-                                   take=take_images))
-            if range_guard:
-                outs.append(Output("flags", lambda sl, f32: (sl.flags,), pinned(torch.int32, B)))
-            self.outputs = {o.name: o for o in outs}
-            img = self.outputs.get("label_images")
-            self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
+        self.perm = self.src_rows = None
+        for inp in SIDE_INPUTS:                 # a side input the slot is not built with: no device buffer
+            setattr(self, inp.name, None)
+        if opts.raw_capacity is not None:
+            self._init_stream(B, N, K, device, opts)
+
+    def _init_stream(self, B, N, K, device, opts):
+        """Streaming: raw rows + a header (stream.header_layout) on the device, their pinned staging, the side inputs (stream.SIDE_INPUTS)
+        with their pinned twins, the streamed outputs with theirs (self.outputs), and the events that say when the staging / the outputs'
+        twins may be touched again.  The rows are opts.rows' (stream.ROW_KINDS); with point_ground_truth the sampler leaves its
+        permutation in the slot (its perm_out); with build_point_gt what travels in is the 7-column annotated rows (src_rows) the step's
+        first launch builds the 18-column rows from, which then have no pinned twin.  depth (raw_capacity = the pixel capacity): the rows
+        are unprojected on the device, so they have no pinned twin either."""
+        f = dict(dtype=torch.float32, device=device)
+        cap, kind, depth, range_guard = opts.raw_capacity, opts.rows, opts.depth_dtype, opts.range_guard
+        self.keyed, self.nchan = opts.keyed, kind.nchan
+        if opts.point_ground_truth:
+            self.perm = torch.zeros((B, N), dtype=torch.int32, device=device)
+        self.layout = lay = header_layout(B, self.keyed, bool(depth), opts.label_images)
+        self.raw_rows = torch.zeros((cap, self.nchan), **f)
+        self.hdr = torch.zeros((lay.words,), dtype=torch.int32, device=device)
+        if opts.build_point_gt:
+            self.src_rows = torch.zeros((cap, kind.staged), **f)
+        self.staged_rows = self.src_rows if opts.build_point_gt else self.raw_rows      # the device buffer submit() copies the clouds into
+        self.h_rows = None if depth else torch.zeros((cap, kind.staged), dtype=torch.float32).pin_memory()
+        self.h_hdr = torch.zeros((lay.words,), dtype=torch.int32).pin_memory()
+        self.h2d_done = torch.cuda.Event()
+        self.d2h_done = torch.cuda.Event()
+        # dense / label_images: the per-raw-row (dense) or per-row and per-pixel (rowlab, img) labels / values the captured step writes
+        # (slot-owned, outside the graph's pool, so a later replay never hands their memory to another tensor) and the f32 graph's own
+        # (range guard); rowlab is device only: nobody reads rows.  Their pinned twins cost 4 + 28 bytes per row / pixel of capacity.
+        for name, built in (("dense", opts.dense), ("rowlab", opts.label_images), ("img", opts.label_images)):
+            setattr(self, name, label_buffers(cap, device) if built else None)
+            setattr(self, name + "32", label_buffers(cap, device) if built and range_guard else None)
+        hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
+        self.np_rows = None if depth else self.h_rows.numpy()
+        self.np_seed, self.np_off, self.np_nf = hdr[lay.seed].view(np.int64), hdr[lay.off], hdr[lay.nf].view(np.float32)
+        self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
+        unit = None
+        if depth:
+            unit = self._init_depth(B, cap, depth, device, annotate=opts.link_counts)
+        else:
+            fill_rows(kind, self.np_rows, K)
+            self.np_off[:] = np.arange(B + 1) * (cap // B)
+            self.np_nf[:] = 1.0
+            self.staged_rows.copy_(self.h_rows)
+            self.hdr.copy_(self.h_hdr)
+        for inp in opts.inputs:                # sl.gt / sl.h_gt / sl.np_gt and so on: the device buffer, its pinned twin and its numpy view
+            host = side_host(inp, B, K, unit)
+            setattr(self, "h_" + inp.name, host)
+            setattr(self, "np_" + inp.name, host.numpy())
+            setattr(self, inp.name, host.to(device))
+        # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
+        # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
+        # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
+        pinned = lambda dtype, *shape: lambda: (torch.zeros(shape, dtype=dtype).pin_memory(),)
+        labels = lambda: label_buffers(cap)
+        outs = [Output("record", lambda sl, f32: (sl.pick("out", f32)[opts.record_key],), pinned(torch.float64, B, K, self.record_width),
+                       refit=range_guard)]
+        if depth:
+            outs.append(Output("counts", lambda sl, f32: (sl.counts,), pinned(torch.int32, B)))
+            if opts.link_counts:
+                outs.append(Output("link_counts", lambda sl, f32: (sl.link_counts,), pinned(torch.int32, B, 16)))
+        if opts.articulation:
+            outs.append(Output("articulation", lambda sl, f32: (sl.pick("out", f32)["articulation"],), pinned(torch.float64, B, K, self.art_width),
+                               refit=range_guard))
+        if opts.dense:
+            outs.append(Output("dense", lambda sl, f32: sl.pick("dense", f32), labels, refit=range_guard, extent=per_raw_row,
+                               take=take_dense, patch=patch_dense))
+        if opts.label_images:
+            outs.append(Output("label_images", lambda sl, f32: sl.pick("img", f32), labels, refit=range_guard, extent=per_pixel,
+                               take=take_images))
+        if range_guard:
+            outs.append(Output("flags", lambda sl, f32: (sl.flags,), pinned(torch.int32, B)))
+        self.outputs = {o.name: o for o in outs}
+        img = self.outputs.get("label_images")
+        self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
 
     def _init_depth(self, B, capacity, depth, device, annotate=False):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
         counts, and host / device views of the header's geometry, camera and dest blocks.  Until the first submit: B crops of random
         depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes).
         annotate (annotated frames, ancsh_depth_annotate_stream): the mask buffers carry the link labels -- the same bytes per pixel --, the
-        scratch holds 16 counters per chunk, and the slot owns the (B, SCENE_WIDTH) float64 scene tables with their pinned twin, copied
-        with the header like the rigs, and the per-link counts; the header's camera block is not read.  Until the first submit: one link
-        with the identity map behind that unit camera, every pixel labelled 0."""
-        from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS, SCENE_HEAD, SCENE_MAX_LINKS, SCENE_WIDTH
+        scratch holds 16 counters per chunk, and the slot owns the per-link counts; the header's camera block is not read, the scene
+        tables (a side input) carry the camera.  Until the first submit: every pixel labelled 0.
+        -> the unit camera's six coefficients and the depth scale (what stream.unit_scene builds the slot's first scenes from)."""
+        from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS, SCENE_MAX_LINKS
         npt, tt, _ = DEPTH_DTYPES[depth]
         self.pix = torch.zeros((capacity,), dtype=tt, device=device)
         self.mask = torch.zeros((capacity,), dtype=torch.uint8, device=device)
@@ -256,25 +209,18 @@ class _Slot(object):
             self.np_pix[:] = rs.uniform(0.5, 1.0, capacity).astype(np.float32)
             scale = 1.0
         self.np_mask[:] = 0 if annotate else 1
+        unit = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
         for b in range(B):
             self.np_geom[b] = (b * per, h, w, 0, 0)
-            self.np_cam[b] = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
-        self.scene = self.link_counts = None
-        if annotate:
-            self.h_scene = torch.zeros((B, SCENE_WIDTH), dtype=torch.float64).pin_memory()
-            self.np_scene = self.h_scene.numpy()
-            unit = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5)
-            self.np_scene[:, 0:6], self.np_scene[:, 6], self.np_scene[:, 7:13] = unit, scale, unit
-            self.np_scene[:, 13], self.np_scene[:, 14] = 10, 1
-            self.np_scene[:, SCENE_HEAD + 2:SCENE_HEAD + 14] = np.eye(4)[:3].reshape(12)      # link 0: rank 0, part 0, M = [I | 0]
-            self.scene = self.h_scene.to(device)
-            self.link_counts = torch.zeros((B, SCENE_MAX_LINKS), dtype=torch.int32, device=device)
+            self.np_cam[b] = unit
+        self.link_counts = torch.zeros((B, SCENE_MAX_LINKS), dtype=torch.int32, device=device) if annotate else None
         if lay.dest is not None:
             self.np_dest[:] = self.np_geom[:, 0]
         self.np_nf[:] = 1.0
         self.pix.copy_(self.h_pix)
         self.mask.copy_(self.h_mask)
         self.hdr.copy_(self.h_hdr)
+        return unit
 
     def pick(self, name, f32=False):
         """Attribute `name` of the step (out, dense, rowlab, img), or (f32=True) its twin of the range guard's f32 graph."""
@@ -308,184 +254,91 @@ class AncshPipeline(object):
     slots: batches kept in flight on separate HIP streams (round-robin).  The pose fit is latency-bound
            (a few hundred waves; a degenerate 3-point sample may run MINPACK's full 4200-evaluation budget in
            ONE lane, exactly as scipy does) while the networks are throughput-bound, so overlapping batch i's
-           fit with batch i+1's networks keeps the CUs busy; results equal those of slots=1 (to the last bit for equal lm_schedule; slots <= 2 select the eight-lane LM schedule, see below)."""
+           fit with batch i+1's networks keeps the CUs busy; results equal those of slots=1 (to the last bit for equal lm_schedule; slots <= 2 select the eight-lane LM schedule, see below).
+
+    The options (README, "Streaming"; their rules are stream.check_options, every one checked on the host before anything touches the GPU):
+    joint_types: None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1 (PoseSolver).  A prismatic joint is fitted
+        with the shared-rotation objective and never reads its joint direction; the per-problem kind array is built once, no launch more.
+    joint_source: stage B's joint association.  "gt" = a label per point (load_inputs' joint_cls, or column 3 of a streamed row); "predicted" =
+        the argmax of the ANCSH network's index_per_point head, from the step's own forward (couple=True) or load_inputs'
+        pred["index_per_point"] (couple=False): a stream then takes (n_raw, 3) xyz clouds.  Same launch count either way.
+    lm_schedule: few batches in flight = a latency deployment, so slots <= 2 take the eight-lanes-per-fit schedule unless lm_schedule says
+        otherwise (the C ABI's default never depends on slots or batch size).  The schedules agree to ~1e-7, not to the last bit: pass
+        "throughput" for bytes equal to a many-slot pipeline.
+    tie_window: None = no tie statistics in the step (they cost stage A's finish kernel ~20 us a batch); parallel_ancsh_pose.TIE_WINDOW to get them.
+    arithmetic: of the shared-MLP layers.  None = what ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME say (default f32, the graded arithmetic);
+        "f32" | "bf16x3" | "f16x2" pins it for this pipeline.
+    range_guard (arithmetic="f16x2"): the guarded kernels flag every (cloud, network) with an activation beyond f16's range, and flagged clouds
+        are refit by an f32 graph of the same step (streaming: retire() does it; step(): out["range_flags"] + rerun_f32()).
+    raw_capacity: None = step() on inputs the caller loads; an int = the streaming pipeline (submit / retire / stream_batches), whose slots
+        hold up to raw_capacity raw rows per batch, padding included.  Needs couple=True.
+    keyed (streaming): the header leads with a key block (ancsh_stream_key) whose cloud_base submit() writes with the seed; cloud b is sampled
+        and fitted as global cloud cloud_base + b, so one captured graph serves a shard at any offset (dist.ShardedPipeline).
+    articulation (couple=True, num_points <= ARTICULATION_MAX_N): one more launch (ancsh_articulation_rec) leaves out["articulation"], the
+        (B, K, 12) block of part boxes and camera-space joints; retire(articulation=True) returns it.
+    joint_states (with articulation): one more launch (ancsh_joint_state_rec) widens that block to (B, K, 20), its 12 columns bit for bit and
+        the joint state behind them.  It is still out["articulation"]: no new name in the result tuple.
+    fit_quality: one more launch behind the fit (ancsh_fit_quality_rec) leaves out["record_wide"] (B, K, 39), the record's 26 columns bit for
+        bit and the fit quality behind them.  Works with couple=False too.
+    ground_truth (streaming): submit(..., gt=...) brings a (K, 19) block per cloud and one more launch (ancsh_gt_error_rec) leaves
+        out["record_gt"], 12 error columns behind the record or the wide record.
+    point_ground_truth (streaming, with articulation): the rows are dataset.pack_cloud's 18 columns, submit(..., frame=...) brings part 0's
+        ground-truth NAOCS pose per cloud, and the last launch of the articulation group (ancsh_point_gt_rec) leaves out["record_point_gt"]:
+        both networks' test losses (coord_regress_loss: "L2" | "L1") and the joint errors, 21 columns behind whatever the record was.
+    build_point_gt (with point_ground_truth): the stream takes (n_raw, 7) annotated clouds and one rig per cloud (submit(..., rig=...)), and the
+        step's first launch (ancsh_point_gt_build) builds the 18-column rows on the device.
+    dense (streaming): the last launch (ancsh_raw_point_labels) labels every raw row; retire(dense=True) returns (labels, values, offsets).
+    depth_capacity, depth_dtype: the depth front end (submit_depth / stream_depth_batches) in raw_capacity's place: a slot holds up to
+        depth_capacity pixels of crops and masks, unprojected on the device (ancsh_depth_unproject_stream) in front of the xyz sampler.
+        Needs joint_source="predicted"; refuses dense.
+    label_images (depth): two more launches carry the row labels back to the pixels; retire(label_images=True) returns per frame an (h, w)
+        label image and an (h, w, 7) value image.  32 bytes of pinned memory per pixel of capacity and slot.
+    depth_capacity with point_ground_truth and build_point_gt: annotated depth frames -- depth crop, link-label crop and a scene table per
+        frame (submit_depth(..., scene=, rig=, frame=)); the step starts with ancsh_depth_annotate_stream, then ancsh_point_gt_build and
+        the sampler.  retire(link_counts=True) returns the valid pixels per link.  Refuses label_images: its rows are link-major.
+    In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False):
-        # joint_types: the kind of every joint, None (all revolute) | "revolute" | "prismatic" | K - 1 of them for joints 1..K-1
-        # (PoseSolver): a prismatic joint is fitted with the shared-rotation objective (objective_eval_r) and never reads its joint
-        # direction.  Checked first, on the host; the per-problem kind array is built here, once -- the step gains no launch.
+        # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
-        # joint_source: stage B's joint association.  "gt" (default) = a label per point -- load_inputs' joint_cls, or the 4th column
-        # [x y z joint_cls] of a streamed raw row (the rendered test split's ground truth, evaluation/parallel_ancsh_pose.py:295).
-        # "predicted" = the argmax of the ANCSH network's index_per_point head (lib/parallel_ancsh_pose.py:339-343,366), from the step's
-        # own forward (couple=True) or load_inputs' pred["index_per_point"] (couple=False): no label is read, a stream takes plain
-        # (n_raw, 3) xyz clouds (a 4th column is accepted and ignored) and its slots hold 3-column rows.  Same launch count either way.
-        self.joint_source = check_joint_source(joint_source)
-        self.predicted = joint_source == "predicted"
+        if arithmetic not in (None, "f32", "bf16x3", "f16x2"):
+            raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
+        self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
+                                      arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
+                                      label_images, joint_source, coord_regress_loss)
+        for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
+            setattr(self, name, getattr(o, name))
+        self.joint_source, self.arithmetic = joint_source, arithmetic
         self.K, self.B, self.N = num_parts, batch_size, num_points
-        # articulation: the captured step ends with one more launch (ancsh_articulation_rec) that turns the networks' heads and the pose
-        # record into the (B, K, 12) block of part boxes and camera-space joints (pose.joint_params.articulation_batch): out["articulation"],
-        # and retire(articulation=True) / stream_batches(articulation=True) when streaming.  It reads the networks' own outputs
-        # (couple=True) and keeps its joint medians in LDS (num_points <= ARTICULATION_MAX_N).
-        self.articulation = bool(articulation)
-        if self.articulation:
-            from .pose.joint_params import ARTICULATION_MAX_N
-            if not couple:
-                raise ValueError("articulation=True reads the networks' heads: it needs couple=True")
-            if not 1 <= int(num_points) <= ARTICULATION_MAX_N:
-                raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
-                                 % (ARTICULATION_MAX_N, num_points))
-        # joint_states (with articulation=True): one more launch behind that one (ancsh_joint_state_rec) widens the block to (B, K, 20) --
-        # its 12 columns bit for bit, then per child part the angle of R_0^T R_j (unsigned, and signed about the joint axis), t_j - t_0, its
-        # slide along the axis, the boundary slide dynam_j - canon_j and the part's point count (pose.joint_params.joint_state_batch).  The
-        # wide block IS out["articulation"] and what retire / stream_* return as the articulation block: no new name in the result tuple.
-        # Like the articulation launch it reads the step's own NPCS heads, the ones the record was fitted on: articulation=True, and with it
-        # joint_states=True, refuses couple=False above.
-        from .pose.joint_params import check_joint_states
-        self.joint_states = check_joint_states(joint_states, self.articulation)
-        # fit_quality: one more launch behind the fit and the record poison, in front of the articulation launch (ancsh_fit_quality_rec,
-        # pose.quality.fit_quality_batch): out["record_wide"] (B, K, 39) -- the record's 26 columns bit for bit, then per part its points,
-        # stage A's consensus count, stage B's score and the inliers / mean / RMS / median / max residual of the baseline and of the nonlinear
-        # pose over all points of the part.  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the wide one: no new
-        # name in the result tuple.  It reads the solver's own packed rows, so it works with couple=False too.
-        from .pose.quality import check_fit_quality
-        self.fit_quality = check_fit_quality(fit_quality, inlier_th)
-        # ground_truth (streaming only): a slot holds the batch's (B, K, 19) float64 ground truth (pose.gt_errors.pack_ground_truth's rows,
-        # submit(..., gt=...)), copied in with the header, and one more launch behind the fit, the poison and the fit-quality launch
-        # (ancsh_gt_error_rec, pose.gt_errors.gt_error_batch) turns record + ground truth into the evaluation's per-part numbers:
-        # out["record_gt"] (B, K, 38) -- the record's 26 columns bit for bit, then rpy_err / xyz_err / scale_err / 3-D IoU / relative
-        # rotation error of both poses, the nonlinear pose's relative translation error and the part's points -- or (B, K, 51) behind the
-        # wide record's 39.  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is this widest one.
-        if ground_truth and raw_capacity is None and depth_capacity is None:
-            raise ValueError("ground_truth=True travels in with a streamed batch (submit / submit_depth): it needs raw_capacity or "
-                             "depth_capacity")
-        self.ground_truth = bool(ground_truth)
-        # point_ground_truth (streaming raw clouds, with articulation=True): the slot's rows are dataset.pack_cloud's 18 columns -- x y z and
-        # the per-point ground truth --, the sampler leaves its permutation in the slot, submit(..., frame=...) brings the (n_valid, 13)
-        # ground-truth NAOCS poses of part 0 (pose.point_gt.pack_joint_frame), and one more launch, the last of the articulation group
-        # (ancsh_point_gt_rec, pose.point_gt.point_gt_batch), turns them into both networks' test-time losses (coord_regress_loss: "L2" |
-        # "L1") and each joint's angle and distance error in camera space: out["record_point_gt"] (B, K, ld + 21) behind whatever the
-        # streamed record was (26, 39, 38 or 51 columns).  out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is this
-        # widest one.  joint_source="gt" reads the rows' column 17 as the joint label; "predicted" reads it for the losses only.
-        from .pose.point_gt import check_loss_type, check_point_ground_truth
-        # (depth frames carry no per-point ground truth -- unless build_point_gt=True makes it from link labels and scenes, see below)
-        self.point_ground_truth = check_point_ground_truth(point_ground_truth, self.articulation,
-                                                           depth_capacity is not None and not build_point_gt)
-        self.coord_regress_loss = check_loss_type(coord_regress_loss)
-        if self.point_ground_truth and raw_capacity is None and depth_capacity is None:
-            raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
-        # build_point_gt (with point_ground_truth=True): the stream takes (n_raw, 7) annotated clouds [x y z | cx cy cz | part]
-        # (dataset.pack_annotated_cloud) and one rig per cloud (dataset.pack_joint_rig, submit(..., rig=...)), and the captured step's first
-        # launch (ancsh_point_gt_build, in front of the sampler) builds the slot's 18-column rows from them on the device: 28 bytes per row
-        # cross to the device instead of 72, and nothing of the reference's data code runs on the host.  Everything behind it reads the
-        # slot's rows where they lie; result tuples and record widths do not change.
-        if build_point_gt and not self.point_ground_truth:
-            raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
-        self.build_point_gt = bool(build_point_gt)
-        # depth_capacity: an int = the streaming pipeline with the depth front end (submit_depth / retire / stream_depth_batches): a slot
-        # holds up to depth_capacity pixels of depth crops (depth_dtype: "uint16" | "float32") and their mask bytes per batch, padding
-        # included, and the captured step starts with their unprojection into the slot's depth_capacity camera-space rows
-        # (ancsh_depth_unproject_stream, at most two launches) in front of the xyz sampler.  It takes raw_capacity's place.
-        self.depth_dtype = None
-        if depth_capacity is not None:
-            from .depth import check_depth_dtype
-            self.depth_dtype = check_depth_dtype(depth_dtype)
-            if raw_capacity is not None:
-                raise ValueError("depth_capacity takes raw_capacity's place: pass one of them")
-            if not self.predicted:
-                raise ValueError("depth_capacity needs joint_source='predicted': a depth pixel carries no joint label")
-            if dense:
-                raise ValueError("dense=True labels the raw rows of an xyz stream; with the depth front end its product is a label "
-                                 "image: pass label_images=True")
-            if not int(batch_size) <= int(depth_capacity) < (1 << 30):
-                raise ValueError("depth_capacity must be in [batch_size, 2^30) pixels")
-            raw_capacity = int(depth_capacity)
-        self.depth_capacity = None if depth_capacity is None else int(depth_capacity)
-        # label_images (the depth front end only): the captured step ends with two more launches -- ancsh_raw_point_labels on the slot's
-        # unprojected rows, exactly as dense=True calls it, and ancsh_depth_label_images, which carries the rows back to the pixels they
-        # came from -- and retire(label_images=True) / stream_depth_batches(label_images=True) return per frame an (h, w) label image and
-        # an (h, w, 7) value image aligned with the submitted crop.  Costs 32 bytes of pinned memory per pixel of depth_capacity and slot
-        # (twice with the range guard).
-        if label_images and depth_capacity is None:
-            raise ValueError("label_images=True carries the labels back to the pixels of depth frames: it needs depth_capacity")
-        self.label_images = bool(label_images)
-        # annotated depth frames (depth_capacity with point_ground_truth=True, build_point_gt=True): a frame is a depth crop, a link-label
-        # crop and one (240,) float64 scene table (depth.pack_frame_scene), and the captured step starts with ancsh_depth_annotate_stream
-        # (two launches: the slot's crops -> its 7-column annotated rows, link-major as dataset.pack_annotated_cloud packs them, offsets,
-        # counts and per-link counts), then ancsh_point_gt_build and the xyz sampler on the 18-column rows: 3 bytes per pixel (uint16) cross
-        # to the device, and nothing of the reference's preprocessing runs on the host.  submit_depth(..., scene=, rig=, frame=).
-        self.link_counts = self.depth_capacity is not None and self.build_point_gt
-        if self.link_counts and self.label_images:
-            raise ValueError("label_images=True carries rows back to pixels in pixel order; the rows of annotated depth frames "
-                             "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
-        # raw_capacity: None = step() on inputs the caller loads (load_inputs); an int = the streaming pipeline (submit / retire /
-        # stream) whose slots hold up to raw_capacity raw rows (x y z joint_cls; predicted: x y z) per batch, padding included
-        if raw_capacity is not None:
-            if not couple:
-                raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
-            if not 1 <= int(raw_capacity) < (1 << 30):
-                raise ValueError("raw_capacity must be in [1, 2^30) rows")
-            raw_capacity = int(raw_capacity)
-        self.raw_capacity = raw_capacity
-        # keyed (streaming only): the slot header leads with a key block (include/ancsh_hip.h, ancsh_stream_key) whose cloud_base
-        # submit() writes with the seed, and the sampler / pose fit key cloud b as global cloud cloud_base + b (the _keyed / _dkey
-        # entries): one captured graph then serves a shard at any offset of a global batch (dist.ShardedPipeline.stream_batches)
-        if keyed and raw_capacity is None:
-            raise ValueError("keyed=True keys the streaming header: it needs raw_capacity")
-        self.keyed = bool(keyed)
-        # dense (streaming only): the captured step ends with one more launch (ancsh_raw_point_labels) that carries the NPCS network's
-        # part label / probability / part NOCS and the ANCSH network's NAOCS from the sampled points to every raw row (3-NN inverse-distance
-        # weights, the FP module's rule) into slot-owned buffers; retire(dense=True) / stream_batches(dense=True) return them per batch
-        if dense and raw_capacity is None:
-            raise ValueError("dense=True labels the raw rows of a stream: it needs raw_capacity")
-        self.dense = bool(dense)
+        self.couple, self.seed = couple, seed
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
+        # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
-        # range_guard (F16x2 only): the guarded kernels flag every (cloud, network) with an activation beyond f16's range, and flagged clouds
-        # are refit by an f32 graph of the same step (streaming: retire() does it; step(): out["range_flags"] + rerun_f32()).  The weights
-        # the F16x2 path packs are checked here, once.
-        self.range_guard = bool(range_guard)
-        if self.range_guard:
-            if arithmetic != "f16x2":
-                raise ValueError("range_guard=True needs arithmetic='f16x2' (f32 and bf16x3 have f32's range)")
+        if self.range_guard:                    # the weights the F16x2 path packs are checked here, once
             bad = f16x2_weight_violations([("ancsh", self.ancsh), ("npcs", self.npcs)])
             if bad:
                 raise ValueError("range_guard: weights beyond f16's range (|w| > 65504) in " +
                                  ", ".join("%s (max |w| = %.6g)" % nb for nb in bad))
-        # few batches in flight = a latency deployment: the LM fits take the eight-lanes-per-fit schedule (an EXPLICIT choice of this
-        # class, overridable with lm_schedule; the C ABI's default schedule never depends on slots or batch size).  The two
-        # schedules agree to ~1e-7, not to the last bit: pass lm_schedule="throughput" for bytes equal to a many-slot pipeline.
-        # tie_window: None (default) = no tie statistics in the step (nobody reads them in a pipeline; the per-fit diagnostics of
-        # PoseSolver -- tie_a / tie_b -- cost the stage-A finish kernel ~20 us a batch); pass parallel_ancsh_pose.TIE_WINDOW to get them
-        self.solver = PoseSolver(num_parts, inlier_th, niter_a, niter_b, device,
-                                 lm_schedule=lm_schedule or ("latency" if max(1, slots) <= 2 else "auto"), tie_window=tie_window,
-                                 joint_types=joint_types)
-        self.solver.prepare(batch_size)     # the (B * (K - 1)) joint-kind array (None when every joint is revolute): never built inside a captured step
-        self.couple, self.seed = couple, seed
-        # arithmetic of the shared-MLP layers: None = whatever ANCSH_SA_BF16X3 / ANCSH_SPLIT_SCHEME say (default: f32, the graded arithmetic);
-        # "f32" | "bf16x3" | "f16x2" pins it for THIS pipeline (the split-16 experiment: bf16x3 at level 3, f16x2 at level 4 -- DESIGN section 8)
-        if arithmetic not in (None, "f32", "bf16x3", "f16x2"):
-            raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
-        self.arithmetic = arithmetic
-        self.f32_reruns = 0                 # batches retire() refit in f32 (range guard)
-        # both networks layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         import os
         from .paired import PairedNetworks
         self.paired = PairedNetworks([self.ancsh, self.npcs]) if os.environ.get("ANCSH_PAIRED", "1") != "0" else None
         if self.paired is not None and not self.paired.eligible():
             self.paired = None
-        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, raw_capacity, self.range_guard, self.keyed, self.articulation,
-                            self.dense, xyz=self.predicted, depth=self.depth_dtype, label_images=self.label_images,
-                            joint_states=self.joint_states, fit_quality=self.fit_quality, ground_truth=self.ground_truth,
-                            point_ground_truth=self.point_ground_truth, build_point_gt=self.build_point_gt)
-                      for _ in range(max(1, slots))]
+        # the solver
+        self.solver = PoseSolver(num_parts, inlier_th, niter_a, niter_b, device,
+                                 lm_schedule=lm_schedule or ("latency" if max(1, slots) <= 2 else "auto"), tie_window=tie_window,
+                                 joint_types=joint_types)
+        self.solver.prepare(batch_size)     # the (B * (K - 1)) joint-kind array (None when every joint is revolute): never built inside a captured step
+        self.f32_reruns = 0                 # batches retire() refit in f32 (range guard)
+        # the slots
+        self.slots = [_Slot(batch_size, num_points, num_parts, self.device, o) for _ in range(max(1, slots))]
         self._next = 0
         self._use_graph = use_graph
         self.stream = self.slots[0].stream
@@ -722,29 +575,21 @@ class AncshPipeline(object):
         clouds of a short batch take the first cloud's.
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
-        if self.raw_capacity is None:
+        o = self.opts
+        if o.raw_capacity is None:
             raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
-        if self.depth_dtype is not None:
+        if o.depth_dtype is not None:
             raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
+        side = dict(gt=gt, frame=frame, rig=rig)
 
         def front():
-            if getattr(self, "build_point_gt", False):
-                from .dataset import check_annotated_clouds
-                if rig is None:
-                    raise ValueError("a pipeline built with build_point_gt=True builds every cloud's rows from its rig: submit(..., rig=...) "
-                                     "needs one dataset.pack_joint_rig table per cloud")
-                valid, nf = check_annotated_clouds(clouds, norm_factors, self.K, self.B)
-            elif self.point_ground_truth:
-                from .pose.point_gt import check_point_clouds
-                valid, nf = check_point_clouds(clouds, norm_factors, self.B)
-            else:
-                from .dataset import check_raw_clouds
-                valid, nf = check_raw_clouds(clouds, norm_factors, self.B, xyz_only=self.predicted)
+            require_side_inputs(o.inputs, side)
+            valid, nf = o.rows.check(clouds, norm_factors, self.K, self.B)
             padded = valid + [valid[0]] * (self.B - len(valid))
             rows = sum(c.shape[0] for c in padded)
-            if rows > self.raw_capacity:
+            if rows > o.raw_capacity:
                 raise ValueError("the batch needs %d raw rows (short batches are padded with their first cloud), raw_capacity is %d"
-                                 % (rows, self.raw_capacity))
+                                 % (rows, o.raw_capacity))
 
             def stage(sl):
                 np.concatenate(padded, axis=0, out=sl.np_rows[:rows])
@@ -752,7 +597,7 @@ class AncshPipeline(object):
                 np.cumsum([c.shape[0] for c in padded], out=sl.np_off[1:])
                 return [(sl.staged_rows[:rows], sl.h_rows[:rows])]
             return len(valid), nf, stage
-        self._enqueue(front, seed, tag, cloud_base, gt, frame, rig)
+        self._enqueue(front, seed, tag, cloud_base, **side)
 
     def submit_depth(self, frames, norm_factors, cameras=None, depth_scale=1.0, seed=None, tag=None, cloud_base=0, gt=None, scene=None,
                      frame=None, rig=None):
@@ -770,73 +615,55 @@ class AncshPipeline(object):
         count 0, like one without a valid pixel.  rig (required) and frame: as submit() takes them.  scene, frame or rig on any other
         pipeline: ValueError.  Bad input
         raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.  Either way the pipeline stays usable."""
-        if self.depth_dtype is None:
+        o = self.opts
+        if o.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
-        annotated = getattr(self, "link_counts", False)
-        if scene is not None and not annotated:
-            raise ValueError("scene needs AncshPipeline(..., depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True)")
+        annotated = o.link_counts
+        refuse_side_inputs(o.inputs, dict(scene=scene), "AncshPipeline")
 
         def front():
             from .depth import check_annotated_frames, check_depth_frames, pack_depth_frames
             if annotated:
                 if scene is None or rig is None or cameras is not None:
-                    raise ValueError("a pipeline built with point_ground_truth=True, build_point_gt=True takes annotated frames: "
-                                     "submit_depth(frames, norm_factors, scene=..., rig=...) needs one depth.pack_frame_scene table and "
-                                     "one dataset.pack_joint_rig table per frame, and cameras=None (the scene carries the camera)")
-                depths, masks, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scene, self.depth_dtype, self.K, self.B)
-                cam = None
+                    raise ValueError(SIDE["scene"].missing)
+                depths, masks, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scene, o.depth_dtype, self.K, self.B)
             else:
-                depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, self.depth_dtype, self.B)
+                depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, o.depth_dtype, self.B)
             n_valid = len(depths)
             pixels = sum(d.size for d in depths)
             padded = pixels + (self.B - n_valid) * depths[0].size
-            if padded > self.depth_capacity:
+            if padded > o.depth_capacity:
                 raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
-                                 % (padded, self.depth_capacity))
+                                 % (padded, o.depth_capacity))
 
             def stage(sl):
                 pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
                 sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
-                if annotated:                              # the scenes; a padding cloud is a copy of the first frame, scene included
-                    sl.np_scene[:n_valid] = scenes
-                    sl.np_scene[n_valid:] = scenes[0]
-                    return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels]), (sl.scene, sl.h_scene)]
-                sl.np_cam[:n_valid] = cam
-                sl.np_cam[n_valid:] = cam[0]
-                if self.label_images:                      # a valid frame's image lies where its crop does; a padding cloud writes none
+                if not annotated:                          # (the scenes of annotated frames carry the camera)
+                    sl.np_cam[:n_valid] = cam
+                    sl.np_cam[n_valid:] = cam[0]
+                if o.label_images:                         # a valid frame's image lies where its crop does; a padding cloud writes none
                     sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
                     sl.np_dest[n_valid:] = -1
                 return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
-            return n_valid, nf, stage
-        self._enqueue(front, seed, tag, cloud_base, gt, frame, rig)
+            return n_valid, nf, stage, dict(scene=scenes) if annotated else {}
+        self._enqueue(front, seed, tag, cloud_base, gt=gt, frame=frame, rig=rig)
 
-    def _enqueue(self, front, seed, tag, cloud_base, gt=None, frame=None, rig=None):
+    def _enqueue(self, front, seed, tag, cloud_base, **side):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
-        (valid clouds, their norm factors, stage); stage(sl) fills the slot's pinned staging and returns its (device, pinned) copies.
+        (valid clouds, their norm factors, stage[, side inputs it has checked itself]); stage(sl) fills the slot's pinned staging and
+        returns its (device, pinned) copies.  side: the batch's side inputs by name (stream.SIDE_INPUTS).
         Checks in order: the key, front()'s, the ground truth, the frames, the rigs, the in-flight window (RuntimeError); only then prepare().  On the slot's
-        stream: the H2D copies (the ground truth's with the header's) with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
+        stream: the H2D copies (the side inputs' with the header's) with h2d_done right behind them, the step, the outputs' D2H copies (the record's first, right behind the replay: the
         next replay's pool reuses its block, see step()), d2h_done."""
         from .dataset import check_stream_key, seed_bits
-        if self.keyed:
+        o = self.opts
+        if o.keyed:
             cloud_base = check_stream_key(cloud_base, self.B, self.K)
         elif cloud_base != 0:
             raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
-        n_valid, nf, stage = front()
-        if gt is not None:
-            if not self.ground_truth:
-                raise ValueError("gt needs AncshPipeline(..., ground_truth=True)")
-            from .pose.gt_errors import check_ground_truth
-            gt = check_ground_truth(gt, n_valid, self.K)
-        if frame is not None:
-            if not getattr(self, "point_ground_truth", False):
-                raise ValueError("frame needs AncshPipeline(..., point_ground_truth=True)")
-            from .pose.point_gt import check_frames
-            frame = check_frames(frame, n_valid)
-        if rig is not None:
-            if not getattr(self, "build_point_gt", False):
-                raise ValueError("rig needs AncshPipeline(..., point_ground_truth=True, build_point_gt=True)")
-            from .dataset import check_rigs
-            rig = check_rigs(rig, n_valid, self.K)
+        n_valid, nf, stage, *checked = front()
+        side = check_side_inputs(o.inputs, dict(side, **(checked[0] if checked else {})), n_valid, self.K, "AncshPipeline")
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:
@@ -845,25 +672,14 @@ class AncshPipeline(object):
         sl = self.slots[self._next]
         sl.h2d_done.synchronize()                  # the previous batch's copies out of the pinned staging have completed
         sl.np_seed[0] = seed_bits(seed)
-        if self.keyed:
+        if o.keyed:
             sl.np_base[0] = cloud_base
         copies = stage(sl)
         sl.np_nf[:n_valid] = nf
         sl.np_nf[n_valid:] = nf[0]
-        if self.ground_truth:                      # NaN rows for the padding clouds and for a batch without ground truth
-            sl.np_gt[:] = np.nan
-            if gt is not None:
-                sl.np_gt[:n_valid] = gt
-            copies = copies + [(sl.gt, sl.h_gt)]
-        if self.point_ground_truth:                # likewise the frames
-            sl.np_frame[:] = np.nan
-            if frame is not None:
-                sl.np_frame[:n_valid] = frame
-            copies = copies + [(sl.frame, sl.h_frame)]
-        if self.build_point_gt:                    # the rigs; a padding cloud is a copy of the first cloud, rig included
-            sl.np_rig[:n_valid] = rig
-            sl.np_rig[n_valid:] = rig[0]
-            copies = copies + [(sl.rig, sl.h_rig)]
+        for inp in o.inputs:
+            stage_side_input(inp, getattr(sl, "np_" + inp.name), side[inp.name], n_valid)
+            copies.append((getattr(sl, inp.name), getattr(sl, "h_" + inp.name)))
         cur = torch.cuda.current_stream(self.device)
         if cur != sl.stream and not cur.query():
             sl.stream.wait_stream(cur)
@@ -872,8 +688,8 @@ class AncshPipeline(object):
                 dev.copy_(host, non_blocking=True)
             sl.h2d_done.record(sl.stream)
             self._replay(sl)
-            for o in sl.outputs.values():
-                o.copy_out(sl, n_valid)
+            for out in sl.outputs.values():
+                out.copy_out(sl, n_valid)
             sl.d2h_done.record(sl.stream)
         self._next = (self._next + 1) % len(self.slots)
         self._submitted += 1
@@ -900,17 +716,16 @@ class AncshPipeline(object):
         The tuple's order is stream.RESULT_ORDER (stream.unpack_results reads it by name).  link_counts=True (a pipeline of annotated
         depth frames: depth_capacity with point_ground_truth=True, build_point_gt=True): + the (n_valid, 16) int32 valid pixels per link
         of the batch's frames, behind everything else."""
-        check_built_with(self, "retire", "AncshPipeline", articulation=articulation, dense=dense, label_images=label_images)
-        if link_counts and not getattr(self, "link_counts", False):
-            raise RuntimeError("retire(link_counts=True) needs AncshPipeline(..., depth_capacity=<pixels>, point_ground_truth=True, "
-                               "build_point_gt=True)")
+        check_built_with(self.opts, "retire", "AncshPipeline", articulation=articulation, dense=dense, label_images=label_images,
+                         link_counts=link_counts)
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
-        asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, counts=self.depth_dtype is not None)
+        asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, counts=self.opts.depth_dtype is not None,
+                     link_counts=link_counts)
         # the flag words decide the refit whether or not the caller asked for them
-        want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked.get(o.name) or (link_counts and o.name == "link_counts")]
+        want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked.get(o.name)]
         got = {o.name: o.value(sl, n_valid) for o in want}
         got.setdefault("flags", np.zeros((n_valid,), np.int32))
         hit = np.flatnonzero(got["flags"])
@@ -924,12 +739,12 @@ class AncshPipeline(object):
             for o in refit:
                 o.patch(got[o.name], o.value(sl, n_valid, f32=True), hit)
             self.f32_reruns += 1
-        if getattr(self, "link_counts", False):
+        if self.opts.link_counts:
             # annotated frames: a frame without rows (no valid pixel, or a link below the minimum: the reference skips it) carries no
             # information.  Its pose record and its losses are NaN from the device; ancsh_point_gt_rec's two point counts read 0 there (no
             # sampled point has a part), and are blanked here, so that the whole row is NaN
             got["record"][got["counts"] == 0] = np.nan
-        return pack_results(dict(got, tag=tag, seed=seed), **asked) + ((got["link_counts"],) if link_counts else ())
+        return pack_results(dict(got, tag=tag, seed=seed), **asked)
 
     def stream_batches(self, batches, flags=False, articulation=False, dense=False):
         """(`stream` is slot 0's HIP stream.)  Generator over submit / retire: batches yields (clouds, norm_factors) or (clouds, norm_factors, tag) (tag defaults to the
@@ -937,18 +752,11 @@ class AncshPipeline(object):
         submit() takes it; built with point_ground_truth=True: the frame (submit()'s) behind the ground truth, in front of the tag; built with build_point_gt=True: the rig (submit()'s) behind the frame, in front of the tag --; up to len(slots) batches stay in flight; yields (tag, seed, record) in submission order (flags=True: + the
         flag words; articulation=True: + the (n_valid, K, 12) articulation block; dense=True: + (labels, values, offsets) of the raw rows,
         last -- see retire())."""
-        check_built_with(self, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
-        g = 1 if self.ground_truth else 0       # the ground truth sits in front of the tag,
-        f = 1 if self.point_ground_truth else 0      # and the frames behind the ground truth,
-        r = 1 if self.build_point_gt else 0          # and the rigs behind the frames
+        check_built_with(self.opts, "stream_batches", "AncshPipeline", articulation=articulation, dense=dense)
 
         def submit(k, item):
-            more = dict(gt=item[2] if len(item) > 2 else None) if g else {}
-            if f:
-                more["frame"] = item[2 + g] if len(item) > 2 + g else None
-            if r:
-                more["rig"] = item[2 + g + f] if len(item) > 2 + g + f else None
-            self.submit(item[0], item[1], tag=item[2 + g + f + r] if len(item) > 2 + g + f + r else k, **more)
+            clouds, norm_factors, side, tag = split_item(item, self.opts.inputs, k)
+            self.submit(clouds, norm_factors, tag=tag, **side)
         yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras=None, depth_scale=1.0, flags=False, articulation=False, label_images=False,
@@ -958,7 +766,7 @@ class AncshPipeline(object):
         frames travel with their scene and rig there); yields what retire() returns, in
         submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them; link_counts=True,
         annotated frames: the (n_valid, 16) per-link counts behind them)."""
-        check_built_with(self, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
+        check_built_with(self.opts, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
 
         def submit(k, item):
             item = tuple(item)

@@ -1,10 +1,14 @@
 """What AncshPipeline's streaming half (submit / submit_depth / retire / stream_*) and dist.ShardedPipeline's share, each written once:
-the slot header's layout, the label buffers, the table of streamed outputs, the names and order of what retire() returns, the "asked for x
-but not built with x" guard, and the submit-when-room / retire-when-full loop.  Host-side plumbing only: nothing here launches a kernel."""
+the slot header's layout, the label buffers, the table of streamed outputs, the table of row kinds, the table of side inputs, the one
+check of the options both constructors take, the names and order of what retire() returns, the "asked for x but not built with x"
+guard, and the submit-when-room / retire-when-full loop.  Host-side plumbing only: nothing here launches a kernel."""
 import collections
 
 import numpy as np
 import torch
+
+from . import dataset, depth as depth_mod
+from .pose import gt_errors, joint_params, point_gt, quality
 
 # ---- the slot header ---------------------------------------------------------------------------------------------------------
 # [seed (int64 bits) -- keyed: the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) -- | offsets (B+1) int32 |
@@ -96,10 +100,229 @@ class Output(object):
         return self.take(self.host32 if f32 else self.host, sl, n_valid, self.extent(sl, n_valid))
 
 
+# ---- the row kinds of a stream -----------------------------------------------------------------------------------------------------
+# What a slot's rows are: nchan columns in the slot's raw_rows, `staged` columns in what travels in (annotated rows are built into 18-column
+# rows on the device), check(clouds, norm_factors, K, most) -> (clouds, norm factors) or ValueError, and fill(rows, rs, K, n): the columns
+# behind x y z of the n random rows a slot holds until its first submit (the draws, in this order, are what prepare() sees).
+RowKind = collections.namedtuple("RowKind", "name nchan staged check fill")
+
+
+def _fill_labelled(rows, rs, K, n):
+    rows[:, 3] = rs.randint(0, K, n)
+
+
+def _fill_point_gt(rows, rs, K, n):
+    rows[:, 3] = rs.randint(0, K, n)
+    rows[:, 4:dataset.NCHAN - 1] = rs.uniform(0.0, 1.0, (n, dataset.NCHAN - 5))
+    rows[:, dataset.NCHAN - 1] = rs.randint(0, K, n)
+
+
+def _fill_annotated(rows, rs, K, n):
+    rows[:, 3:6] = rs.uniform(0.0, 1.0, (n, 3))
+    rows[:, 6] = rs.randint(0, K, n)
+
+
+ROW_KINDS = {k.name: k for k in (
+    RowKind("labelled", dataset.RAW_NCHAN, dataset.RAW_NCHAN, lambda c, nf, K, most: dataset.check_raw_clouds(c, nf, most),
+            _fill_labelled),                                                                                      # x y z joint_cls
+    RowKind("xyz", 3, 3, lambda c, nf, K, most: dataset.check_raw_clouds(c, nf, most, xyz_only=True), lambda rows, rs, K, n: None),
+    RowKind("point_gt", dataset.NCHAN, dataset.NCHAN, lambda c, nf, K, most: point_gt.check_point_clouds(c, nf, most), _fill_point_gt),
+    RowKind("annotated", dataset.NCHAN, dataset.ANNOTATED_NCHAN, lambda c, nf, K, most: dataset.check_annotated_clouds(c, nf, K, most),
+            _fill_annotated))}
+
+
+def fill_rows(kind, rows, K):
+    """The (capacity, kind.staged) rows a slot holds until its first submit: a defined, non-degenerate input for prepare()'s passes."""
+    rs = np.random.RandomState(0)
+    rows[:, :3] = rs.uniform(-0.5, 0.5, (rows.shape[0], 3))
+    kind.fill(rows, rs, K, rows.shape[0])
+
+
+# ---- the table of side inputs ------------------------------------------------------------------------------------------------------
+# What travels in with a batch besides its rows or pixels, one float64 block per cloud, staged in pinned memory and copied with the
+# header.  option: the Options flag it is built with, built_with: that option as the refusal spells it; shape(K): a cloud's block;
+# fill(K, unit): what a slot holds until its first submit (unit: the unit camera and depth scale of a depth slot's default crops);
+# check(value, n, K) -> the (n,) + shape(K) array or ValueError (None: the front end has checked it); pad: what the padding clouds of a
+# short batch get, "nan" (and so does a whole batch without the input) or "first" (a copy of the first cloud's); missing: the
+# ValueError of a submit without a required input (None: the input is optional).
+SideInput = collections.namedtuple("SideInput", "name option built_with shape dtype fill check pad missing")
+
+
+def unit_scene(K, unit):
+    """One link with the identity map behind the camera `unit` = (6 unprojection coefficients, depth scale): rank 0, part 0, M = [I | 0]."""
+    s = np.zeros(depth_mod.SCENE_WIDTH)
+    s[0:6], s[6], s[7:13], s[13], s[14] = unit[:6], unit[6], unit[:6], 10, 1
+    s[depth_mod.SCENE_HEAD + 2:depth_mod.SCENE_HEAD + 14] = np.eye(4)[:3].reshape(12)
+    return s
+
+
+ANNOTATED = "point_ground_truth=True, build_point_gt=True"
+SIDE_INPUTS = (             # in the order of their H2D copies; gt, frame, rig is also their order in a stream_batches item
+    SideInput("scene", "link_counts", "depth_capacity=<pixels>, " + ANNOTATED, lambda K: (depth_mod.SCENE_WIDTH,), torch.float64, unit_scene,
+              None, "first",
+              "a pipeline built with " + ANNOTATED + " takes annotated frames: submit_depth(frames, norm_factors, scene=..., rig=...) needs "
+              "one depth.pack_frame_scene table and one dataset.pack_joint_rig table per frame, and cameras=None (the scene carries the "
+              "camera)"),
+    SideInput("gt", "ground_truth", "ground_truth=True", lambda K: (K, gt_errors.GT_WIDTH), torch.float64, lambda K, unit: np.nan,
+              gt_errors.check_ground_truth, "nan", None),
+    SideInput("frame", "point_ground_truth", "point_ground_truth=True", lambda K: (point_gt.FRAME_WIDTH,), torch.float64, lambda K, unit: np.nan,
+              lambda v, n, K: point_gt.check_frames(v, n), "nan", None),
+    SideInput("rig", "build_point_gt", ANNOTATED, lambda K: (dataset.RIG_WIDTH(K),), torch.float64, lambda K, unit: dataset.identity_rig(K),
+              dataset.check_rigs, "first",
+              "a pipeline built with build_point_gt=True builds every cloud's rows from its rig: submit(..., rig=...) needs one "
+              "dataset.pack_joint_rig table per cloud"))
+SIDE = {inp.name: inp for inp in SIDE_INPUTS}
+
+
+def side_host(inp, B, K, unit=None, pin=True):
+    """The (B,) + shape(K) host staging of side input `inp`, holding its fill; pinned unless pin=False."""
+    host = torch.zeros((B,) + inp.shape(K), dtype=inp.dtype)
+    host = host.pin_memory() if pin else host
+    host.numpy()[:] = inp.fill(K, unit)
+    return host
+
+
+def refuse_side_inputs(built, given, cls):
+    """ValueError for the first side input of `given` = {name: value or None} that a `cls` with the side inputs `built` does not take."""
+    for inp in SIDE_INPUTS:
+        if given.get(inp.name) is not None and inp not in built:
+            raise ValueError("%s needs %s(..., %s)" % (inp.name, cls, inp.built_with))
+
+
+def require_side_inputs(built, given):
+    """ValueError for the first of the side inputs `built` that a submit must carry and `given` lacks."""
+    for inp in built:
+        if inp.missing and given.get(inp.name) is None:
+            raise ValueError(inp.missing)
+
+
+def check_side_inputs(built, given, n, K, cls):
+    """Refuse and check, input by input in the table's order -> {name: the checked (n, ...) array, or None} for the side inputs `built`."""
+    out = {}
+    for inp in SIDE_INPUTS:
+        v = given.get(inp.name)
+        if v is not None:
+            refuse_side_inputs(built, {inp.name: v}, cls)
+            v = v if inp.check is None else inp.check(v, n, K)
+        if inp in built:
+            out[inp.name] = v
+    return out
+
+
+def stage_side_input(inp, view, value, n):
+    """Fill a slot's (B, ...) staging `view` from a batch's checked value for its n valid clouds, by the input's padding rule."""
+    if inp.pad == "nan":           # NaN rows for the padding clouds and for a batch without the input
+        view[:] = np.nan
+        if value is not None:
+            view[:n] = value
+    else:                          # a padding cloud is a copy of the first cloud, side input included
+        view[:n] = value
+        view[n:] = value[0]
+
+
+def split_item(item, built, k):
+    """A stream_batches item (clouds, norm_factors[, one value per side input of `built`, in the table's order][, tag]) ->
+    (clouds, norm_factors, {name: value or None}, tag); the tag defaults to k, the batch's index."""
+    names = [inp.name for inp in built]
+    side = {name: item[2 + i] if len(item) > 2 + i else None for i, name in enumerate(names)}
+    return item[0], item[1], side, item[2 + len(names)] if len(item) > 2 + len(names) else k
+
+
+# ---- the options both constructors take --------------------------------------------------------------------------------------------
+JOINT_SOURCES = ("gt", "predicted")
+
+
+def check_joint_source(joint_source):
+    """-> joint_source if it names one of JOINT_SOURCES; ValueError otherwise (before anything touches the GPU)."""
+    if joint_source not in JOINT_SOURCES:
+        raise ValueError("joint_source must be one of %s, got %r" % (JOINT_SOURCES, joint_source))
+    return joint_source
+
+
+Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
+                                 "fit_quality ground_truth point_ground_truth build_point_gt dense label_images link_counts "
+                                 "coord_regress_loss record_width record_key art_width rows inputs")
+OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
+
+
+def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw_capacity=None, depth_capacity=None, depth_dtype="uint16",
+                  keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
+                  ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
+                  coord_regress_loss="L2"):
+    """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
+    (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
+    width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
+    raw_capacity in the result is the slots' capacity: depth_capacity's value on a depth pipeline."""
+    predicted = check_joint_source(joint_source) == "predicted"
+    if articulation:
+        if not couple:
+            raise ValueError("articulation=True reads the networks' heads: it needs couple=True")
+        if num_points is not None and not 1 <= int(num_points) <= joint_params.ARTICULATION_MAX_N:
+            raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
+                             % (joint_params.ARTICULATION_MAX_N, num_points))
+    joint_states = joint_params.check_joint_states(joint_states, bool(articulation))
+    fit_quality = quality.check_fit_quality(fit_quality, inlier_th)
+    if ground_truth and raw_capacity is None and depth_capacity is None:
+        raise ValueError("ground_truth=True travels in with a streamed batch (submit / submit_depth): it needs raw_capacity or "
+                         "depth_capacity")
+    # (depth frames carry no per-point ground truth -- unless build_point_gt=True makes it from link labels and scenes)
+    point_ground_truth = point_gt.check_point_ground_truth(point_ground_truth, bool(articulation),
+                                                           depth_capacity is not None and not build_point_gt)
+    point_gt.check_loss_type(coord_regress_loss)
+    if point_ground_truth and raw_capacity is None and depth_capacity is None:
+        raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
+    if build_point_gt and not point_ground_truth:
+        raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
+    if depth_capacity is not None:
+        depth_dtype = depth_mod.check_depth_dtype(depth_dtype)
+        if raw_capacity is not None:
+            raise ValueError("depth_capacity takes raw_capacity's place: pass one of them")
+        if not predicted:
+            raise ValueError("depth_capacity needs joint_source='predicted': a depth pixel carries no joint label")
+        if dense:
+            raise ValueError("dense=True labels the raw rows of an xyz stream; with the depth front end its product is a label "
+                             "image: pass label_images=True")
+        if not int(batch_size) <= int(depth_capacity) < (1 << 30):
+            raise ValueError("depth_capacity must be in [batch_size, 2^30) pixels")
+        raw_capacity = depth_capacity = int(depth_capacity)
+    if label_images and depth_capacity is None:
+        raise ValueError("label_images=True carries the labels back to the pixels of depth frames: it needs depth_capacity")
+    link_counts = depth_capacity is not None and bool(build_point_gt)      # annotated depth frames
+    if link_counts and label_images:
+        raise ValueError("label_images=True carries rows back to pixels in pixel order; the rows of annotated depth frames "
+                         "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
+    if raw_capacity is not None:
+        if not couple:
+            raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
+        if not 1 <= int(raw_capacity) < (1 << 30):
+            raise ValueError("raw_capacity must be in [1, 2^30) rows")
+        raw_capacity = int(raw_capacity)
+    if keyed and raw_capacity is None:
+        raise ValueError("keyed=True keys the streaming header: it needs raw_capacity")
+    if dense and raw_capacity is None:
+        raise ValueError("dense=True labels the raw rows of a stream: it needs raw_capacity")
+    if range_guard and arithmetic != "f16x2":
+        raise ValueError("range_guard=True needs arithmetic='f16x2' (f32 and bf16x3 have f32's range)")
+    # the streamed record: the pose record, or (fit_quality) the wide record -- its 26 columns and the fit quality behind them --, the
+    # errors against ground truth behind either (ancsh_gt_error_rec), the per-point ground truth's columns behind whatever that was
+    width, key = (quality.FIT_QUALITY_WIDTH, "record_wide") if fit_quality else (26, "record")
+    if ground_truth:
+        width, key = width + gt_errors.GT_ERROR_WIDTH, "record_gt"
+    if point_ground_truth:
+        width, key = width + point_gt.POINT_GT_WIDTH, "record_point_gt"
+    rows = None if raw_capacity is None else ROW_KINDS["annotated" if build_point_gt else "point_gt" if point_ground_truth else
+                                                       "xyz" if predicted else "labelled"]
+    o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
+                bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(dense),
+                bool(label_images), link_counts, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
+    return o._replace(inputs=tuple(i for i in SIDE_INPUTS if raw_capacity is not None and getattr(o, i.option)))
+
+
 # ---- what retire() returns ---------------------------------------------------------------------------------------------------
-RESULT_ORDER = ("tag", "seed", "record", "flags", "articulation", "dense", "label_images", "counts")
+RESULT_ORDER = ("tag", "seed", "record", "flags", "articulation", "dense", "label_images", "counts", "link_counts")
 RESULT_ALWAYS = RESULT_ORDER[:3]
-BUILT_WITH = dict(articulation="articulation=True", dense="dense=True", label_images="depth_capacity=<pixels>, label_images=True")
+BUILT_WITH = dict(articulation="articulation=True", dense="dense=True", label_images="depth_capacity=<pixels>, label_images=True",
+                  link_counts="depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True")
 
 
 def result_names(**asked):

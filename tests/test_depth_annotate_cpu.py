@@ -304,14 +304,16 @@ def test_pipelines_refuse_unsupported_combinations_before_gpu_work():
     with pytest.raises(ValueError, match="depth"):
         ShardedPipeline(3, None, None, 4, 64, "cpu", pipeline_factory=_FakeStreamPipeline, **base)
     # a pipeline of plain depth frames refuses the annotated frames' arguments, one of annotated frames a call without them
+    from articulated_pose_amd.stream import check_options
     pipe = AncshPipeline.__new__(AncshPipeline)
-    pipe.depth_dtype, pipe.link_counts, pipe.keyed, pipe.B, pipe.K = "uint16", False, False, 2, 3
+    depth = dict(depth_capacity=4096, joint_source="predicted")
+    pipe.opts, pipe.B, pipe.K = check_options(**depth), 2, 3
     u = np.ones((3, 4), np.uint16)
     with pytest.raises(ValueError, match="scene needs AncshPipeline"):
         pipe.submit_depth([(u, None, (0, 0))], [1.0], [1, 0, 0, 0, 1, 0], scene=np.zeros(240))
     with pytest.raises(RuntimeError, match="link_counts=True"):
         pipe.retire(link_counts=True)
-    pipe.link_counts = True
+    pipe.opts = check_options(articulation=True, point_ground_truth=True, build_point_gt=True, **depth)
     for kw in (dict(), dict(scene=np.zeros(240)), dict(rig=np.zeros((1, 10))), dict(scene=np.zeros(240), rig=np.zeros((1, 10)), cameras=[1, 0, 0, 0, 1, 0])):
         with pytest.raises(ValueError, match="annotated frames"):
             pipe.submit_depth([(u, np.zeros((3, 4), int), (0, 0))], [1.0], **kw)

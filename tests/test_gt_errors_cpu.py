@@ -96,6 +96,7 @@ def test_pack_ground_truth_reads_the_pickle_shapes():
 def test_constructors_and_submit_refuse_before_a_device_is_touched():
     from articulated_pose_amd.dist import ShardedPipeline
     from articulated_pose_amd.pipeline import AncshPipeline
+    from articulated_pose_amd.stream import check_options
     # the constructors check before they build a network or touch a device ("cpu" never reaches a kernel)
     with pytest.raises(ValueError, match="ground_truth=True .* raw_capacity or depth_capacity"):
         AncshPipeline(3, {}, {}, 2, 64, "cpu", ground_truth=True)
@@ -103,11 +104,11 @@ def test_constructors_and_submit_refuse_before_a_device_is_touched():
         ShardedPipeline(3, {}, {}, 2, 64, "cpu", ground_truth=True)
     # gt on a pipeline built without the option: AncshPipeline's shared enqueue path refuses right after the front end's own checks
     pipe = AncshPipeline.__new__(AncshPipeline)
-    pipe.keyed, pipe.ground_truth, pipe.K, pipe.B = False, False, 3, 2
+    pipe.opts, pipe.K, pipe.B = check_options(raw_capacity=CAP), 3, 2
     front = lambda: (1, np.ones(1, np.float32), None)
     with pytest.raises(ValueError, match="gt needs AncshPipeline"):
         pipe._enqueue(front, None, None, 0, gt=np.zeros((1, 3, 19)))
-    pipe.ground_truth = True
+    pipe.opts = check_options(raw_capacity=CAP, ground_truth=True)
     with pytest.raises(ValueError, match=r"gt must be \(1, 3, 19\)"):
         pipe._enqueue(front, None, None, 0, gt=np.zeros((2, 3, 19)))
     sp = ShardedPipeline(3, None, None, 2, 8, "cpu", pipeline_factory=_FakeStreamPipeline, raw_capacity=CAP)

@@ -56,6 +56,7 @@ def test_entry_rejects_bad_arguments_before_launch():
 
 def test_constructor_and_retire_rules_before_gpu_work():
     from articulated_pose_amd.pipeline import AncshPipeline
+    from articulated_pose_amd.stream import check_options
     base = dict(joint_source="predicted")
     with pytest.raises(ValueError, match="label_images=True .* depth_capacity"):
         AncshPipeline(3, None, None, 2, 512, "cpu", label_images=True, **base)
@@ -67,7 +68,7 @@ def test_constructor_and_retire_rules_before_gpu_work():
             AncshPipeline(3, None, None, 2, 512, "cpu", depth_capacity=4096, dense=True, **dict(base, **extra))
     # a pipeline built without the option refuses to return images, before it looks at its (empty) in-flight window
     pipe = AncshPipeline.__new__(AncshPipeline)
-    pipe.articulation = pipe.dense = pipe.label_images = False
+    pipe.opts = check_options(raw_capacity=4096)
     pipe._inflight = []
     with pytest.raises(RuntimeError, match="label_images=True"):
         pipe.retire(label_images=True)

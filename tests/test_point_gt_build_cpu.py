@@ -174,6 +174,7 @@ def test_pack_functions_refuse_bad_input():
 def test_pipelines_refuse_before_a_device_is_touched():
     from articulated_pose_amd.dist import ShardedPipeline
     from articulated_pose_amd.pipeline import AncshPipeline
+    from articulated_pose_amd.stream import check_options
     # the constructors check before they build a network or touch a device ("cpu" never reaches a kernel)
     with pytest.raises(ValueError, match="build_point_gt=True .* needs point_ground_truth=True"):
         AncshPipeline(3, {}, {}, 2, 64, "cpu", raw_capacity=1000, articulation=True, build_point_gt=True)
@@ -181,8 +182,8 @@ def test_pipelines_refuse_before_a_device_is_touched():
         ShardedPipeline(3, {}, {}, 2, 64, "cpu", raw_capacity=1000, articulation=True, build_point_gt=True)
     _, src, rig, _, K = golden_case("b")
     pipe = AncshPipeline.__new__(AncshPipeline)
-    pipe.raw_capacity, pipe.depth_dtype, pipe.point_ground_truth, pipe.build_point_gt, pipe.keyed = 1000, None, True, True, False
-    pipe.ground_truth, pipe.B, pipe.K, pipe.predicted = False, 2, K, False
+    built = dict(raw_capacity=1000, articulation=True, point_ground_truth=True)
+    pipe.opts, pipe.B, pipe.K = check_options(build_point_gt=True, **built), 2, K
     with pytest.raises(ValueError, match="rig=.* needs one dataset.pack_joint_rig table per cloud"):
         pipe.submit([src], [1.0])
     with pytest.raises(ValueError, match=r"\(n_raw, 7\).*x y z \| cx cy cz \| part.*\(5, 18\)"):
@@ -192,13 +193,13 @@ def test_pipelines_refuse_before_a_device_is_touched():
     with pytest.raises(ValueError, match="integers in"):
         pipe.submit([np.where(np.arange(7) == 6, 0.5, src).astype(np.float32)], [1.0], rig=rig[None])
     # a pipeline built without the option refuses rig=
-    pipe.build_point_gt = False
+    pipe.opts = check_options(**built)
     with pytest.raises(ValueError, match="rig needs AncshPipeline"):
         pipe.submit([np.zeros((5, 18), np.float32)], [1.0], rig=rig[None])
     sp = ShardedPipeline.__new__(ShardedPipeline)
-    sp.raw_capacity, sp.ground_truth, sp.point_ground_truth, sp.build_point_gt = 1000, False, True, False
+    sp.raw_capacity, sp.opts = 1000, check_options(**built)
     with pytest.raises(ValueError, match="rig needs ShardedPipeline"):
         sp.submit([np.zeros((5, 18), np.float32)], [1.0], rig=rig[None])
-    sp.build_point_gt = True
+    sp.opts = check_options(build_point_gt=True, **built)
     with pytest.raises(ValueError, match="needs one dataset.pack_joint_rig table per cloud"):
         sp.submit([src], [1.0])

@@ -56,6 +56,7 @@ def test_constructors_refuse_before_a_device_is_touched():
 def test_clouds_and_frames_are_checked_on_the_host():
     from articulated_pose_amd.pipeline import AncshPipeline
     from articulated_pose_amd.pose import point_gt as PG
+    from articulated_pose_amd.stream import check_options
     assert PG.POINT_GT_WIDTH == 21 == len(PG.POINT_GT_COLUMNS) and PG.FRAME_WIDTH == 13
     assert [PG.PGT_ANGLE_ERR, PG.PGT_DIST_ERR, PG.PGT_MIOU, PG.PGT_NPCS_MIOU, PG.PGT_PART_POINTS, PG.PGT_JOINT_POINTS, PG.PGT_NOCS, PG.PGT_GOCS,
             PG.PGT_HEATMAP, PG.PGT_UNITVEC, PG.PGT_ORIENT, PG.PGT_NPCS_NOCS] == [0, 1, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20]
@@ -63,7 +64,7 @@ def test_clouds_and_frames_are_checked_on_the_host():
     assert [c.dtype for c in good] == [np.float32] * 2 and all(c.flags.c_contiguous for c in good) and nf.dtype == np.float32
     # a 4-column cloud on such a pipeline: refused by the submit path before anything is enqueued, and the message names the 18 columns
     pipe = AncshPipeline.__new__(AncshPipeline)
-    pipe.raw_capacity, pipe.depth_dtype, pipe.point_ground_truth, pipe.keyed, pipe.B, pipe.K, pipe.predicted = 1000, None, True, False, 2, 3, False
+    pipe.opts, pipe.B, pipe.K = check_options(raw_capacity=1000, articulation=True, point_ground_truth=True), 2, 3
     with pytest.raises(ValueError, match=r"\(n_raw, 18\).*x y z \| cls \| nocs_p 3 \| nocs_g 3 \| heatmap \| unitvec 3 \| orient 3 \| joint_cls.*\(7, 4\)"):
         pipe.submit([np.zeros((7, 4), np.float32)], [1.0])
     for bad in ([np.zeros((0, 18))], [np.zeros((3, 17))], "nonsense", []):
@@ -81,11 +82,11 @@ def test_clouds_and_frames_are_checked_on_the_host():
         with pytest.raises(ValueError, match=word):
             PG.check_frames(bad, 2)
     # frame on a pipeline built without the option: refused right after the front end's own checks
-    pipe.point_ground_truth, pipe.ground_truth = False, False
+    built, pipe.opts = pipe.opts, check_options(raw_capacity=1000)
     front = lambda: (1, np.ones(1, np.float32), None)
     with pytest.raises(ValueError, match="frame needs AncshPipeline"):
         pipe._enqueue(front, None, None, 0, frame=np.zeros((1, 13)))
-    pipe.point_ground_truth = True
+    pipe.opts = built
     with pytest.raises(ValueError, match=r"frame must be \(1, 13\)"):
         pipe._enqueue(front, None, None, 0, frame=np.zeros((2, 13)))
 
