@@ -140,6 +140,9 @@ SIGNATURES = {
     # the per-point ground truth itself, built from annotated clouds in front of the sampler (no ABI bump, detected by its symbol): nclouds, K,
     # src, capacity, offsets, rig, rig_ld, rows, stream
     "ancsh_point_gt_build": [_c_int, _c_int, _vp, _c_long, _vp, _vp, _c_int, _vp, _vp],
+    # the ground-truth poses of a streamed batch, fitted directly behind the sampler (no ABI bump, detected by its symbol): b, n, K, nchan, rows,
+    # capacity, offsets, perm, P, ldp, extent, ld_extent, gt, frame, stream
+    "ancsh_gt_pose_build": [_c_int] * 4 + [_vp, _c_long, _vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp],
     # the annotated clouds themselves, made from depth and link-label crops (no ABI bump, detected by its symbol): nclouds, depth_type, depth,
     # labels, pixel_capacity, geom, scene, rows, capacity, offsets, counts, link_counts, scratch, stream
     "ancsh_depth_annotate_stream": [_c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp],

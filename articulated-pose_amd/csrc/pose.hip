@@ -24,6 +24,7 @@
 //     with draws == NULL a counter-based device generator (splitmix64 of seed/problem/iteration) is used.
 #include "common.h"
 #include "pose_math.h"
+#include "umeyama_fit.h"
 
 namespace ancsh {
 namespace pose {
@@ -73,30 +74,7 @@ __device__ __forceinline__ int key_problem_base(unsigned long long) { return 0; 
 template <int KM>
 __device__ __forceinline__ int key_problem_base(DKey arg) { return arg.key->cloud_base * arg.parts; }
 
-// ---- block reductions (256 threads = 4 waves) -----------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// sums K doubles across the workgroup; every thread receives every total.  red: LDS, >= K*nwaves doubles.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double *red, int nwaves) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < K; ++i) v[i] = wave_sum(v[i]);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < K; ++i) red[wave * K + i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double s = 0.0;
-        for (int w = 0; w < nwaves; ++w) s += red[w * K + i];
-        v[i] = s;
-    }
-}
+// ---- block reductions (256 threads = 4 waves): wave_sum and block_sum, umeyama_fit.h ----------------------
 
 // ---- similarity model from a point set held as arrays (thread-local, tiny n) --------------------------
 // transform_pts on 3 sampled points: Kabsch rotation, pairwise scale, mean translation.
@@ -1926,6 +1904,8 @@ __global__ __launch_bounds__(256) void joint_direction_pred_kernel(int n, int K,
 
 // estimateSimilarityUmeyama (lib/aligning.py:580-622) for a batch of (source, target) point sets, float64.
 // out (nprob, 29): Scales(3) | Rotation(9, the reference's TRANSPOSED matrix) | Translation(3) | OutTransform(4x4 row-major minus last row -> 12) ... see header
+#define UMK_SRC(i, c) src[(size_t)(r0 + (i)) * 3 + (c)]
+#define UMK_TGT(i, c) tgt[(size_t)(r0 + (i)) * 3 + (c)]
 __global__ __launch_bounds__(256) void umeyama_kernel(const int *__restrict__ off, const float *__restrict__ src,
                                                       const float *__restrict__ tgt, double *__restrict__ out) {
     __shared__ double red[64];
@@ -1935,60 +1915,9 @@ __global__ __launch_bounds__(256) void umeyama_kernel(const int *__restrict__ of
         if (threadIdx.x < 32) o[threadIdx.x] = NAN;
         return;
     }
-    double sums[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = threadIdx.x; i < n; i += 256)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { sums[c] += src[(size_t)(r0 + i) * 3 + c]; sums[3 + c] += tgt[(size_t)(r0 + i) * 3 + c]; }
-    block_sum<6>(sums, red, 4);
-    double sm[3], tm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { sm[c] = sums[c] / n; tm[c] = sums[3 + c] / n; }
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // Cov*n (9) + sum |s - sm|^2
-    for (int i = threadIdx.x; i < n; i += 256) {
-        double sc[3], tc[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { sc[c] = src[(size_t)(r0 + i) * 3 + c] - sm[c]; tc[c] = tgt[(size_t)(r0 + i) * 3 + c] - tm[c]; }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) acc[a * 3 + b] += tc[a] * sc[b];
-        acc[9] += sc[0] * sc[0] + sc[1] * sc[1] + sc[2] * sc[2];
-    }
-    block_sum<10>(acc, red, 4);
+    ANCSH_UMEYAMA_SUMS(n, UMK_SRC, UMK_TGT, red)        // the arithmetic is stated in umeyama_fit.h, for this kernel and gt_pose_kernel
     if (threadIdx.x != 0) return;
-    double M[9], q[4], R[9];
-#pragma unroll
-    for (int a = 0; a < 9; ++a) M[a] = acc[a] / n;
-    horn_quat(M, q);
-    quat_to_mat(q, R);                       // R = U diag(1,1,d) Vh
-    // sum of the (sign-corrected) singular values = tr(R^T Cov)
-    double trace = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) trace += R[a * 3 + b] * M[a * 3 + b];
-    const double varP = acc[9] / n;
-    const double s = trace / varP;
-    o[0] = o[1] = o[2] = s;
-    // Rotation = (U Vh)^T ; Translation = tmean - smean . (s * Rotation) = tmean - s * R smean
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) o[3 + a * 3 + b] = R[b * 3 + a];
-    double T[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        T[a] = tm[a] - s * (R[a * 3] * sm[0] + R[a * 3 + 1] * sm[1] + R[a * 3 + 2] * sm[2]);
-        o[12 + a] = T[a];
-    }
-    // OutTransform = [[s*R, T],[0,0,0,1]] row-major 4x4
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) o[15 + a * 4 + b] = s * R[a * 3 + b];
-        o[15 + a * 4 + 3] = T[a];
-    }
-    o[27] = 0; o[28] = 0; o[29] = 0; o[30] = 1; o[31] = 0;
+    ANCSH_UMEYAMA_SOLVE(n, o)
 }
 
 

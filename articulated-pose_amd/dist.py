@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .stream import (check_built_with, check_options, check_side_inputs, only_asked, pack_results, pump, refuse_side_inputs,
+from .stream import (check_built_with, check_options, check_side_inputs, only_asked, pack_results, pump, refuse_built_frame, refuse_side_inputs,
                      require_side_inputs, split_item, unpack_results)
 
 CHILD_ENV = "ANCSH_LOCAL_RANK_CHILD"      # set in the ranks launch_local_ranks() starts: they must not launch again
@@ -329,12 +329,14 @@ class ShardedPipeline(object):
     columns wider (ancsh_point_gt_rec) and travels in the same single gather.
     build_point_gt=True (with point_ground_truth=True): every rank's pipeline builds its rows on the device (AncshPipeline(build_point_gt=
     True)) from its shard's (n_raw, 7) annotated clouds and its shard's rows of the batch's (n_valid, RIG_WIDTH) rigs, handed out as the
-    frames are."""
+    frames are.
+    build_gt_pose=True (with point_ground_truth=True): every rank's pipeline fits its shard's ground-truth poses on the device
+    (AncshPipeline(build_gt_pose=True)): submit() takes no frame, and every rank still gets its shard's rows of gt, for the box extents."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, global_batch, num_points, device="cuda:0", data_group=None, dst=0,
                  slots=1, pipeline_factory=None, gather_single=False, raw_capacity=None, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, joint_states=False, fit_quality=False, ground_truth=False, point_ground_truth=False, build_point_gt=False,
-                 **pipeline_kw):
+                 build_gt_pose=False, **pipeline_kw):
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)      # before anything touches a GPU or a process group
         if pipeline_kw.get("depth_capacity") is not None:
@@ -348,14 +350,15 @@ class ShardedPipeline(object):
                 raise ValueError("%s=True is carried by the raw stream only (submit / retire / stream_batches): it needs raw_capacity" % name)
         self.opts = o = check_options(global_batch, None, True, pipeline_kw.get("inlier_th", 0.1), raw_capacity, keyed=raw_capacity is not None,
                                       articulation=articulation, joint_states=joint_states, fit_quality=fit_quality, ground_truth=ground_truth,
-                                      point_ground_truth=point_ground_truth, build_point_gt=build_point_gt, joint_source=joint_source)
+                                      point_ground_truth=point_ground_truth, build_point_gt=build_point_gt, joint_source=joint_source,
+                                      build_gt_pose=build_gt_pose)
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense, self.joint_source, self.record_width, self.art_width = bool(dense), joint_source, o.record_width, o.art_width
         self.couple = bool(pipeline_kw.get("couple", True))
         # only what differs from the default is passed on: a per-rank stand-in built before an option need not know it
         given = dict(joint_types=joint_types, joint_source=None if joint_source == "gt" else joint_source, dense=self.dense)
-        for name in ("articulation", "joint_states", "fit_quality", "ground_truth", "point_ground_truth", "build_point_gt"):
+        for name in ("articulation", "joint_states", "fit_quality", "ground_truth", "point_ground_truth", "build_point_gt", "build_gt_pose"):
             setattr(self, name, getattr(o, name))
             given[name] = getattr(o, name)
         pipeline_kw.update({k: v for k, v in given.items() if v})
@@ -513,6 +516,7 @@ class ShardedPipeline(object):
         if self.raw_capacity is None:
             raise RuntimeError("submit() needs ShardedPipeline(..., raw_capacity=<rows per rank>)")
         built, given = self.opts.inputs, dict(gt=gt, frame=frame, rig=rig)
+        refuse_built_frame(self.opts, frame, "ShardedPipeline")
         refuse_side_inputs(built, given, "ShardedPipeline")
         require_side_inputs(built, given)
         if self.world == 1:

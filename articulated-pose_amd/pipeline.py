@@ -18,7 +18,7 @@ from .network import Network
 from .pose import PoseSolver
 from .stream import (JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
                      check_side_inputs, fill_rows, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row, pump,
-                     refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
+                     refuse_built_frame, refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
 
 
 def check_hardware_queues(slots):
@@ -97,7 +97,7 @@ class _Slot(object):
         self.flags = torch.zeros((B,), dtype=torch.int32, device=device) if opts.range_guard else None
         self.graph32 = None
         self.out32 = None
-        self.perm = self.src_rows = None
+        self.perm = self.src_rows = self.gt_built = self.frame_built = None
         for inp in SIDE_INPUTS:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
         if opts.raw_capacity is not None:
@@ -149,6 +149,9 @@ class _Slot(object):
             setattr(self, "h_" + inp.name, host)
             setattr(self, "np_" + inp.name, host.numpy())
             setattr(self, inp.name, host.to(device))
+        if opts.build_gt_pose:                 # what ancsh_gt_pose_build writes behind the sampler and the two error launches read: slot-owned,
+            self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
+            self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -287,6 +290,10 @@ class AncshPipeline(object):
         both networks' test losses (coord_regress_loss: "L2" | "L1") and the joint errors, 21 columns behind whatever the record was.
     build_point_gt (with point_ground_truth): the stream takes (n_raw, 7) annotated clouds and one rig per cloud (submit(..., rig=...)), and the
         step's first launch (ancsh_point_gt_build) builds the 18-column rows on the device.
+    build_gt_pose (with point_ground_truth): one more launch directly behind the sampler (ancsh_gt_pose_build) fits the ground-truth poses
+        of step 1 of evaluation.sh from the slot's rows, perm and P into slot-owned tables, which the two error launches read: submit takes
+        no frame (ValueError), and of gt (ground_truth=True) only the box extents, columns 13..15 (pose.gt_errors.pack_box_extents; None =
+        NaN extents, so only the two IoU columns are NaN).  step() leaves out["gt_pose"] (B, K, 19) and out["gt_frame"] (B, 13).
     dense (streaming): the last launch (ancsh_raw_point_labels) labels every raw row; retire(dense=True) returns (labels, values, offsets).
     depth_capacity, depth_dtype: the depth front end (submit_depth / stream_depth_batches) in raw_capacity's place: a slot holds up to
         depth_capacity pixels of crops and masks, unprojected on the device (ancsh_depth_unproject_stream) in front of the xyz sampler.
@@ -302,7 +309,7 @@ class AncshPipeline(object):
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
-                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False):
+                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -310,7 +317,7 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -430,6 +437,12 @@ class AncshPipeline(object):
             sl.flags.zero_()                  # the captured step's first node: the guarded launches only OR into the words
         key = self._sample(sl) if self.raw_capacity is not None else None
         seed_dev, key_dev = (None, key) if self.keyed else (key, None)
+        gt_in, frame_in = sl.gt, sl.frame
+        if self.build_gt_pose:            # directly behind the sampler: both ground-truth pose tables from the slot's rows, perm and P, one launch;
+            from .pose.gt_pose import gt_pose_batch      # of the submitted gt only the box extents (columns 13..15) are read, where they lie
+            gt_pose_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, sl.P, None if sl.gt is None else sl.gt[:, :, 13:16],
+                          out=(sl.gt_built, sl.frame_built))
+            gt_in, frame_in = sl.gt_built if self.ground_truth else None, sl.frame_built
         from . import pointnet_util
         geom = pointnet_util.Geometry()       # FPS / ball query / 3-NN depend only on P: computed once, used by both nets
         # the arithmetic goes down the layer helpers explicitly (None: the module globals); nothing global is changed
@@ -441,7 +454,7 @@ class AncshPipeline(object):
             nocs, mask, axis, index = sl.pred_nocs, sl.pred_mask, sl.pred_axis, sl.pred_index if self.predicted else None
         assoc = dict(joint_index=index) if self.predicted else dict(joint_cls=sl.joint_cls)      # one of them: the solver refuses both
         sol = self.solver.solve(sl.P, nocs, mask, axis, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
-                                key_dev=key_dev, fit_quality=self.fit_quality, ground_truth=sl.gt, **assoc)
+                                key_dev=key_dev, fit_quality=self.fit_quality, ground_truth=gt_in, **assoc)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
         if self.fit_quality:             # behind the fit and the record poison: (B, K, 39) float64, one launch (the solver issued it)
             out["record_wide"] = sol["record_wide"]
@@ -456,7 +469,7 @@ class AncshPipeline(object):
             if self.point_ground_truth:  # the last of the group: the widest record so far and the 21 columns behind it, one launch
                 from .pose.point_gt import point_gt_batch
                 carried = out["record_gt"] if self.ground_truth else out["record_wide"] if self.fit_quality else out["record"]
-                out["record_point_gt"] = point_gt_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, a, n, out["articulation"], sl.frame,
+                out["record_point_gt"] = point_gt_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, a, n, out["articulation"], frame_in,
                                                         carried, self.coord_regress_loss)
         if self.dense or self.label_images:      # never both: a depth pipeline refuses dense=True
             # the last launch: every raw row of the slot's batch (label_images: its unprojected rows), into the slot's own (capacity, .) buffers
@@ -469,6 +482,8 @@ class AncshPipeline(object):
                 from .depth import depth_label_images
                 out["label_images"] = depth_label_images(sl.pix, sl.mask, sl.geom, sl.dest, off, rl[0], rl[1], out=sl.pick("img", f32),
                                                          scratch=sl.scratch)
+        if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
+            out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:
             out["range_flags"] = sl.flags     # (B,) int32: bit 0 = the ANCSH network, bit 1 = the NPCS network saw |x| > 65504
         return out
@@ -573,6 +588,8 @@ class AncshPipeline(object):
         the part an integer in [0, num_parts)) instead, and rig (ValueError on any other pipeline, and when it is missing on this one): the
         valid clouds' (n_valid, RIG_WIDTH(num_parts)) tables (dataset.pack_joint_rig), staged with the header as frame is; the padding
         clouds of a short batch take the first cloud's.
+        A pipeline built with build_gt_pose=True fits the ground-truth poses itself: frame is a ValueError (the device builds it), and of gt
+        only columns 13..15, the box extents, are read (pose.gt_errors.pack_box_extents).
         Bad input raises ValueError before anything is enqueued; a full in-flight window (every slot submitted, not retired) raises
         RuntimeError.  Either way the pipeline stays usable."""
         o = self.opts
@@ -580,6 +597,7 @@ class AncshPipeline(object):
             raise RuntimeError("submit() needs AncshPipeline(..., raw_capacity=<rows>)")
         if o.depth_dtype is not None:
             raise RuntimeError("a pipeline built with depth_capacity takes depth frames: submit_depth()")
+        refuse_built_frame(o, frame, "AncshPipeline")
         side = dict(gt=gt, frame=frame, rig=rig)
 
         def front():
@@ -619,6 +637,7 @@ class AncshPipeline(object):
         if o.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
         annotated = o.link_counts
+        refuse_built_frame(o, frame, "AncshPipeline")
         refuse_side_inputs(o.inputs, dict(scene=scene), "AncshPipeline")
 
         def front():

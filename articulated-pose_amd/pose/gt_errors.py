@@ -64,6 +64,24 @@ def pack_ground_truth(rt, scale, box_extent, rt_naocs=None):
     return out
 
 
+def pack_box_extents(box_extent):
+    """The (n, K, 19) ground truth of n frames that holds the part boxes only: NaN everywhere except columns 13..15, which are
+    pack_ground_truth's for the same box_extent (box_extent[f] = K corner tables or a (K, 3) array of extents; None: a NaN frame).  What a
+    pipeline built with build_gt_pose=True reads of its gt: the poses are fitted on the device."""
+    n = len(box_extent)
+    K = next((len(e) for e in box_extent if e is not None), 0)
+    out = np.full((n, K, GT_WIDTH), np.nan)
+    for f in range(n):
+        if box_extent[f] is None:
+            continue
+        if len(box_extent[f]) != K:
+            raise ValueError("pack_box_extents: frame %d does not hold %d parts" % (f, K))
+        for j in range(K):
+            e = np.asarray(box_extent[f][j], np.float64)
+            out[f, j, GT_EXTENT] = e if e.shape == (3,) else np.asarray(box_extent[f][j][1][0], np.float64) - np.asarray(box_extent[f][j][0][0], np.float64)
+    return out
+
+
 def gt_error_batch(P, npcs_nocs, npcs_mask, record, gt, nres=GT_NRES):
     """The errors of a batch in ONE launch: P (B, N, C >= 3) float32 sampled points, npcs_nocs (B, N, 3K) and npcs_mask (B, N, K) float32:
     the heads the record was fitted on, record (B, K, 26) float64 -- or the (B, K, 39) fit-quality wide record --, gt (B, K, 19) float64

@@ -189,6 +189,13 @@ def refuse_side_inputs(built, given, cls):
             raise ValueError("%s needs %s(..., %s)" % (inp.name, cls, inp.built_with))
 
 
+def refuse_built_frame(opts, frame, cls):
+    """ValueError for a frame handed to a `cls` built with build_gt_pose=True: the captured step fits it on the device."""
+    if opts.build_gt_pose and frame is not None:
+        raise ValueError("frame: a %s built with build_gt_pose=True takes no frame -- the device builds it (ancsh_gt_pose_build fits "
+                         "part 0's ground-truth NAOCS pose from the sampled rows inside the step)" % cls)
+
+
 def require_side_inputs(built, given):
     """ValueError for the first of the side inputs `built` that a submit must carry and `given` lacks."""
     for inp in built:
@@ -240,7 +247,7 @@ def check_joint_source(joint_source):
 
 
 Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
-                                 "fit_quality ground_truth point_ground_truth build_point_gt dense label_images link_counts "
+                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts "
                                  "coord_regress_loss record_width record_key art_width rows inputs")
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
@@ -248,11 +255,13 @@ OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # th
 def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw_capacity=None, depth_capacity=None, depth_dtype="uint16",
                   keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
                   ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
-                  coord_regress_loss="L2"):
+                  coord_regress_loss="L2", build_gt_pose=False):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
     (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
     width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
-    raw_capacity in the result is the slots' capacity: depth_capacity's value on a depth pipeline."""
+    raw_capacity in the result is the slots' capacity: depth_capacity's value on a depth pipeline.
+    build_gt_pose (with point_ground_truth): the step fits both ground-truth pose tables itself, so `frame` is no side input and of `gt`
+    only the box extents (columns 13..15) are read."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -273,6 +282,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
         raise ValueError("point_ground_truth=True travels in with a streamed batch's raw rows (submit): it needs raw_capacity")
     if build_point_gt and not point_ground_truth:
         raise ValueError("build_point_gt=True builds the rows point_ground_truth=True reads: it needs point_ground_truth=True")
+    if build_gt_pose and not point_ground_truth:
+        raise ValueError("build_gt_pose=True fits the ground-truth poses from the sampled 18-column rows point_ground_truth=True brings: "
+                         "it needs point_ground_truth=True")
     if depth_capacity is not None:
         depth_dtype = depth_mod.check_depth_dtype(depth_dtype)
         if raw_capacity is not None:
@@ -313,9 +325,11 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     rows = None if raw_capacity is None else ROW_KINDS["annotated" if build_point_gt else "point_gt" if point_ground_truth else
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
-                bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(dense),
+                bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
                 bool(label_images), link_counts, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
-    return o._replace(inputs=tuple(i for i in SIDE_INPUTS if raw_capacity is not None and getattr(o, i.option)))
+    # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
+    return o._replace(inputs=tuple(i for i in SIDE_INPUTS if raw_capacity is not None and getattr(o, i.option)
+                                   and not (build_gt_pose and i.name == "frame")))
 
 
 # ---- what retire() returns ---------------------------------------------------------------------------------------------------

@@ -987,6 +987,37 @@ int ancsh_point_gt_rec(int b, int n, int K, int nchan, const float *rows, long c
 int ancsh_point_gt_build(int nclouds, int K, const float *src, long capacity, const int *offsets, const double *rig, int rig_ld,
                          float *rows, void *stream);
 
+/* The ground-truth poses of a streamed batch, built in ONE launch directly behind the streaming sampler (no new ABI number: callers detect
+ * it by its symbol): step 1 of evaluation.sh, evaluation/compute_gt_pose.py:80-89 run with --nocs ANCSH and with --nocs NAOCS.  rows,
+ * capacity, offsets (b + 1), perm (b, n) and nchan == 18 are what ancsh_point_gt_rec reads: sampled point i of cloud c is raw row
+ * offsets[c] + perm[c][i] % n_raw; cls_gt = the C truncation of channel 3, nocs_p = channels 4..6, nocs_g = channels 7..9.  P (b, n, ldp >= 3)
+ * float32: the sampled, scaled points the networks read (the P of the reference's prediction record).  extent: row (c, j) = the 3 float64
+ * values at extent + (c * K + j) * ld_extent (a pipeline points it at column 13 of the submitted ground truth, ld_extent = 19); NULL = NaN.
+ * gt (b, K, 19) and frame (b, 13) float64, out of place; either may be NULL to skip it.
+ * For part j of cloud c, over the sampled points with cls_gt == j in sample order:
+ *   U_p = estimateSimilarityUmeyama(nocs_p, P),  U_g = estimateSimilarityUmeyama(nocs_g, P)  (lib/aligning.py:580-622),
+ * each THE BITS ancsh_umeyama writes for those rows gathered into a contiguous problem (one statement of the arithmetic, csrc/umeyama_fit.h:
+ * float64, thread t of 256 takes compacted rows t, t + 256, ..., the same reductions in the same order).
+ *   gt[c][j][0..8]   U_p's src -> tgt rotation, row-major: the transpose of ancsh_umeyama's Rotation, compose_rt's upper 3 x 3
+ *   gt[c][j][9]      U_p's scale, float64 as computed        gt[c][j][10..12]  U_p's translation
+ *   gt[c][j][13..15] the extent row, bit for bit (a NaN keeps its payload)      gt[c][j][16..18]  U_g's translation
+ *   frame[c]         [R (9) | s | t (3)] of U_g for part 0
+ * Every R and t entry is rounded to float32 once and widened: compose_rt's float32 matrix, what pack_ground_truth / pack_joint_frame
+ * receive from the pickles.  These are the rows ancsh_gt_error_rec (gt) and ancsh_point_gt_rec (frame) read.
+ * NaN rules.  A non-finite fit: a fit whose 13 numbers [R | s | t] contain a non-finite value gives NaN in all 13 (one point, coincident
+ * NOCS -- varP == 0 --, a non-finite P); U_p's 13 are columns 0..12, of U_g's 13 the row holds 16..18 and the frame all.  An empty part:
+ * if ANY part of the cloud has no sampled ground-truth point the whole cloud is missing -- columns 0..12 and 16..18 of all K rows are NaN
+ * and so is the frame (the reference skips such a record, compute_gt_pose.py:98-99); cls_gt outside [0, K) belongs to no part.  Bad
+ * offsets: a cloud whose rows are empty or reach outside [0, capacity) gets NaN throughout, extent columns included.  A cloud never
+ * changes a neighbour's bytes.  K == 1 is legal.
+ * One workgroup per (part, cloud); each counts all K parts, then compacts its part's samples in order into LDS (n <=
+ * ANCSH_ARTICULATION_MAX_N).  Graph-capturable: every cloud size is read from device memory, nothing is allocated, no atomics, no
+ * workgroup waits for another; the same bytes on every run and wherever the cloud lies in the batch.  b == 0 launches nothing.
+ * Checked before any launch (-1, ancsh_last_error): 0 <= b <= 65535, 1 <= K <= 8, nchan == 18, 1 <= n <= 4096, ldp >= 3, ld_extent >= 3
+ * when extent is set, 0 <= capacity < 2^30, null rows / offsets / perm / P, gt and frame both NULL. */
+int ancsh_gt_pose_build(int b, int n, int K, int nchan, const float *rows, long capacity, const int *offsets, const int *perm,
+                        const float *P, int ldp, const double *extent, int ld_extent, double *gt, double *frame, void *stream);
+
 /* ---- input sampling in front of the network (lib/dataset.py:290-357) ------------------------ */
 
 /* One launch for a ragged batch: cloud b owns raw rows [offsets[b], offsets[b+1]) of `rows` (nchan floats each:

@@ -3,7 +3,7 @@ fit + record D2H per batch) against load_inputs + step() on the same clouds, at 
 hypotheses, couple=True, synthetic weights, 20 slots).  Prints one JSON line.
 
     python tools/stream_bench.py [--passes 5] [--slots 20] [--arithmetic {f32,f16x2}] [--range-guard] [--overflow-every K] [--articulation] [--dense]
-                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth] [--point-gt [--build-point-gt]]
+                                 [--joint-source {gt,predicted}] [--joint-states] [--fit-quality] [--ground-truth] [--point-gt [--build-point-gt] [--build-gt-pose]]
                                  [--no-baseline]
 
 --arithmetic pins both pipelines' arithmetic; --range-guard streams through AncshPipeline(arithmetic="f16x2", range_guard=True); with
@@ -20,6 +20,8 @@ columns wider (both networks' test losses and the joint errors, ancsh_point_gt_r
 --build-point-gt (with --point-gt) streams with AncshPipeline(build_point_gt=True): the clouds are (n_raw, 7) annotated rows [x y z | cx cy cz |
 part] (28 bytes a row over the link instead of 72), every batch carries (32, RIG_WIDTH) rigs in (two revolute joints on part 0,
 dataset.pack_joint_rig), and the step's first launch builds the 18-column rows on the device (ancsh_point_gt_build), one more launch a step.
+--build-gt-pose (with --point-gt) streams with AncshPipeline(build_gt_pose=True): no frames travel in, a ground truth carries only its box
+extents, and one more launch behind the sampler (ancsh_gt_pose_build) fits the ground-truth poses the error launches read.
 --no-baseline skips the load_inputs + step() leg (step_clouds_per_s and ratio are then null): for A/B runs of the stream alone.
 --dense streams with AncshPipeline(dense=True) (the record plus every raw row's label and 7 head values: ancsh_raw_point_labels).
 --joint-source predicted builds both pipelines with joint_source="predicted" (stage B's joint association from the ANCSH network's index
@@ -59,6 +61,8 @@ def main():
                     help="with --articulation: AncshPipeline(point_ground_truth=True): 18-column clouds and frames in, the record 21 columns wider")
     ap.add_argument("--build-point-gt", action="store_true",
                     help="with --point-gt: AncshPipeline(build_point_gt=True): 7-column annotated clouds and rigs in, the rows built on the device")
+    ap.add_argument("--build-gt-pose", action="store_true",
+                    help="with --point-gt: AncshPipeline(build_gt_pose=True): the ground-truth poses fitted on the device, no frames in")
     ap.add_argument("--no-baseline", action="store_true", help="skip the load_inputs + step() leg")
     ap.add_argument("--dense", action="store_true", help="stream with AncshPipeline(dense=True) and retire every raw row's labels too")
     ap.add_argument("--joint-source", choices=("gt", "predicted"), default="gt",
@@ -72,6 +76,8 @@ def main():
         ap.error("--point-gt needs --articulation")
     if args.build_point_gt and not args.point_gt:
         ap.error("--build-point-gt needs --point-gt")
+    if args.build_gt_pose and not args.point_gt:
+        ap.error("--build-gt-pose needs --point-gt")
     extra = args.arithmetic is not None
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
@@ -105,8 +111,10 @@ def main():
         R = np.stack([np.cos(a), -np.sin(a), z, np.sin(a), np.cos(a), z, z, z, o], -1)
         gts = np.concatenate([R, rs.uniform(0.5, 1.5, a.shape + (1,)), rs.uniform(-0.3, 0.3, a.shape + (3,)), rs.uniform(0.3, 0.9, a.shape + (3,)),
                               rs.uniform(-0.3, 0.3, a.shape + (3,))], -1)
-    frames = rs.normal(size=(len(batches), B, 13)) if args.point_gt else None
-    with_gt = lambda k, c, nf: (c, nf) + ((gts[k],) if args.ground_truth else ()) + ((frames[k],) if args.point_gt else ()) + \
+    frames = rs.normal(size=(len(batches), B, 13)) if args.point_gt and not args.build_gt_pose else None
+    if gts is not None and args.build_gt_pose:      # only the box extents travel in
+        gts[..., :13] = gts[..., 16:] = np.nan
+    with_gt = lambda k, c, nf: (c, nf) + ((gts[k],) if args.ground_truth else ()) + ((frames[k],) if frames is not None else ()) + \
         ((rigs,) if args.build_point_gt else ())
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
 
@@ -117,7 +125,8 @@ def main():
                          range_guard=args.range_guard, articulation=args.articulation, dense=args.dense,
                          joint_source=args.joint_source, joint_states=args.joint_states, fit_quality=args.fit_quality,
                          ground_truth=args.ground_truth, point_ground_truth=args.point_gt,
-                         **(dict(build_point_gt=True) if args.build_point_gt else {})).prepare()
+                         **(dict(build_point_gt=True) if args.build_point_gt else {}),
+                         **(dict(build_gt_pose=True) if args.build_gt_pose else {})).prepare()
     torch.cuda.synchronize()
     pipe_bytes = mem0 - torch.cuda.mem_get_info(dev)[0]
     for _ in pipe.stream_batches([with_gt(k, c, nf) for k, (c, nf) in enumerate(batches)]):          # warm-up: every slot replayed with real input
@@ -207,6 +216,8 @@ def main():
         line.update({"point_ground_truth": True, "record_columns": int(rec.shape[2]), "h2d_row_bytes": 28 if args.build_point_gt else 72})
     if args.build_point_gt:
         line.update({"build_point_gt": True})
+    if args.build_gt_pose:
+        line.update({"build_gt_pose": True})
     if predicted:
         line.update({"joint_source": "predicted"})
     if args.dense:
