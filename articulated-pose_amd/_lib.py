@@ -146,6 +146,9 @@ SIGNATURES = {
     # the annotated clouds themselves, made from depth and link-label crops (no ABI bump, detected by its symbol): nclouds, depth_type, depth,
     # labels, pixel_capacity, geom, scene, rows, capacity, offsets, counts, link_counts, scratch, stream
     "ancsh_depth_annotate_stream": [_c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp],
+    # those crops themselves, rendered from articulated triangle meshes (no ABI bump, detected by its symbol): nframes, depth_type, verts, tris,
+    # tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity, stream
+    "ancsh_render_depth_labels": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

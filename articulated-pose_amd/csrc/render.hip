@@ -1,0 +1,196 @@
+// render.hip -- depth and link-label frames of articulated triangle meshes rendered on the GPU (gfx950): the mesh, one render table per frame
+// (the pixel map, the depth scale and every link's model -> camera map) and the depth entries' geometry rows -> the depth crops and label
+// crops ancsh_depth_annotate_stream reads, where it reads them.
+//
+// Reference: tools/render_synthetic.py:180-225 renders one frame at a time with pybullet's getCameraImage on the host.  Pixel parity with
+// that rasteriser is no goal (its two back ends differ from each other); the contract is geometric -- this is the exact inverse of the
+// camera model ancsh_depth_annotate_stream applies to a frame's coordinate point (scene[7..12], depth.coord_unprojection_from_projmat) --
+// and is stated in full in include/ancsh_hip.h (ancsh_render_depth_labels).  THREE launches on a ragged batch of crops:
+//   clear   : block (x, f) sets the z-buffer keys of chunk x of frame f's crop to the empty key (depth.hip's grid and chunking);
+//   raster  : one wave per (triangle, frame): every lane transforms the triangle's three vertices (float64, as written), the wave sweeps
+//             the triangle's bounding box clipped to the crop, 64 pixels a step; a covered pixel (int64 edge functions on 1/256-pixel
+//             fixed point) takes ONE 64-bit integer atomic minimum on its key, (bits of (float)depth) << 32 | triangle index;
+//   resolve : block (x, f) turns the keys of its chunk into depth values and label bytes, background where the key is empty.
+// The minimum of a set does not depend on the order of its elements: the output is a pure function of the input, byte for byte.
+// float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
+#include "depth_common.h"
+
+namespace ancsh {
+
+constexpr int RN_LINKS = ANCSH_SCENE_MAX_LINKS, RN_HEAD = ANCSH_RENDER_HEAD, RN_LINK = ANCSH_RENDER_LINK, RN_WIDTH = ANCSH_RENDER_WIDTH;
+constexpr unsigned long long RN_EMPTY = ~0ull;                         // no real key reaches it: the bits of a float32 are its upper half
+constexpr long RN_FIXED_LIMIT = 1L << 25;                               // |X|, |Y| of a kept vertex, in 1/256 pixel
+
+// the table's integers and its near bound, read defensively: a table that is not one renders background
+__device__ __forceinline__ int render_nlinks(const double *__restrict__ rt) {
+    const double v = rt[8], z_min = rt[7];
+    return v >= 1.0 && v <= (double)RN_LINKS && z_min > 0.0 ? (int)v : 0;      // NaN fails every comparison
+}
+
+__global__ __launch_bounds__(DEPTH_THREADS) void render_clear_kernel(long pixel_capacity, const int *__restrict__ geom, int chunks,
+                                                                     unsigned long long *__restrict__ zbuf) {
+    long start, lo, hi;
+    int w;
+    const long n = depth_crop(geom, blockIdx.y, pixel_capacity, start, w);
+    depth_chunk(start, n, blockIdx.x, chunks, lo, hi);
+    for (long a = lo + threadIdx.x; a < hi; a += DEPTH_THREADS) zbuf[a] = RN_EMPTY;      // [lo, hi) lies inside [0, pixel_capacity)
+}
+
+struct RenderVertex {
+    long X, Y;          // the pixel position in 1/256 pixel: X along the columns, Y along the rows
+    double iz;          // 1 / z
+    bool ok;
+};
+
+// vertex `v` of a link with the map R (row-major 3 x 4) -> its fixed-point pixel and 1 / z; ok = false drops the triangle
+__device__ __forceinline__ RenderVertex render_vertex(const float *__restrict__ v, const double *__restrict__ R, const double *__restrict__ rt) {
+    const double v0 = v[0], v1 = v[1], v2 = v[2];
+    double q[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = ((R[4 * a] * v0 + R[4 * a + 1] * v1) + R[4 * a + 2] * v2) + R[4 * a + 3];
+    const double z = q[2], s = q[0] / z, t = q[1] / z;
+    const double col = (rt[0] * s + rt[1] * t) + rt[2], row = (rt[3] * s + rt[4] * t) + rt[5];
+    const double X = rint(256.0 * col), Y = rint(256.0 * row);
+    RenderVertex o;
+    // z >= z_min > 0; a NaN or an infinity anywhere fails one of these comparisons
+    o.ok = z >= rt[7] && z < __builtin_inf() && fabs(X) < (double)RN_FIXED_LIMIT && fabs(Y) < (double)RN_FIXED_LIMIT;
+    o.X = o.ok ? (long)X : 0;
+    o.Y = o.ok ? (long)Y : 0;
+    o.iz = 1.0 / z;
+    return o;
+}
+
+__device__ __forceinline__ long render_edge(long ax, long ay, long bx, long by, long px, long py) {
+    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+}
+
+__device__ __forceinline__ long lmin(long a, long b) { return a < b ? a : b; }
+__device__ __forceinline__ long lmax(long a, long b) { return a > b ? a : b; }
+__device__ __forceinline__ long floor_div256(long v) { return v >> 8; }                  // arithmetic shift: floor for either sign
+__device__ __forceinline__ long ceil_div256(long v) { return -((-v) >> 8); }
+
+__global__ __launch_bounds__(DEPTH_THREADS) void render_raster_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                      const int *__restrict__ tri_link, int V, int T,
+                                                                      long pixel_capacity, const int *__restrict__ geom,
+                                                                      const double *__restrict__ render,
+                                                                      unsigned long long *__restrict__ zbuf) {
+    const int f = blockIdx.y, lane = threadIdx.x & 63;
+    const int t = (int)(blockIdx.x * DEPTH_WAVES + (threadIdx.x >> 6));                  // uniform over the wave
+    if (t >= T) return;
+    const double *rt = render + (size_t)f * RN_WIDTH;
+    const int nl = render_nlinks(rt);
+    long start;
+    int w;
+    const long n = depth_crop(geom, f, pixel_capacity, start, w);
+    if (nl == 0 || n == 0) return;
+    const int h = (int)(n / w), row0 = geom[(size_t)f * DEPTH_GEOM + 3], col0 = geom[(size_t)f * DEPTH_GEOM + 4];
+    const int ia = tris[3 * (size_t)t], ib = tris[3 * (size_t)t + 1], ic = tris[3 * (size_t)t + 2], l = tri_link[t];
+    if (l < 0 || l >= nl || ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) return;
+    const double *R = rt + RN_HEAD + RN_LINK * l;
+    const RenderVertex a = render_vertex(verts + 3 * (size_t)ia, R, rt), b = render_vertex(verts + 3 * (size_t)ib, R, rt),
+                       c = render_vertex(verts + 3 * (size_t)ic, R, rt);
+    if (!(a.ok && b.ok && c.ok)) return;                                // no clipping: the triangle is dropped whole
+    const long area2 = render_edge(a.X, a.Y, b.X, b.Y, c.X, c.Y);
+    if (area2 == 0) return;
+    // the sample points (256 (row0 + i), 256 (col0 + j)) inside the bounding box, clipped to the crop
+    const long minX = lmin(a.X, lmin(b.X, c.X)), maxX = lmax(a.X, lmax(b.X, c.X)), minY = lmin(a.Y, lmin(b.Y, c.Y)), maxY = lmax(a.Y, lmax(b.Y, c.Y));
+    const long c_lo = lmax(ceil_div256(minX), (long)col0), c_hi = lmin(floor_div256(maxX), (long)col0 + w - 1);
+    const long r_lo = lmax(ceil_div256(minY), (long)row0), r_hi = lmin(floor_div256(maxY), (long)row0 + h - 1);
+    if (c_lo > c_hi || r_lo > r_hi) return;
+    const unsigned ncols = (unsigned)(c_hi - c_lo + 1), count = (unsigned)(r_hi - r_lo + 1) * ncols;     // <= h * w < 2^30
+    const double darea = (double)area2;
+    for (unsigned k = lane; k < count; k += 64) {
+        const unsigned dr = k / ncols, dc = k - dr * ncols;
+        const long r = r_lo + dr, cc = c_lo + dc, px = 256 * cc, py = 256 * r;
+        // every factor is below 2^26 inside the bounding box: the edge values are exact in int64 and in float64
+        const long ea = render_edge(b.X, b.Y, c.X, c.Y, px, py), eb = render_edge(c.X, c.Y, a.X, a.Y, px, py),
+                   ec = render_edge(a.X, a.Y, b.X, b.Y, px, py);
+        const bool in = area2 > 0 ? (ea >= 0 && eb >= 0 && ec >= 0) : (ea <= 0 && eb <= 0 && ec <= 0);
+        if (!in) continue;
+        const double la = (double)ea / darea, lb = (double)eb / darea, lc = (double)ec / darea;
+        const double invz = (la * a.iz + lb * b.iz) + lc * c.iz;
+        const float d = (float)(1.0 / invz);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)t;
+        // (r - row0, cc - col0) is a pixel of the crop, and the crop lies inside [0, pixel_capacity)
+        atomicMin(zbuf + (start + (r - row0) * w + (cc - col0)), key);
+    }
+}
+
+__device__ __forceinline__ unsigned short render_quantise(double v, unsigned short) {    // uint16: rint, kept in 1..65535
+    const double q = rint(v);
+    return q >= 1.0 && q <= 65535.0 ? (unsigned short)q : (unsigned short)0;
+}
+__device__ __forceinline__ float render_quantise(double v, float) {                      // float32: kept when finite and positive
+    const float q = (float)v;
+    return q > 0.f && q < __builtin_inff() ? q : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEPTH_THREADS) void render_resolve_kernel(long pixel_capacity, const int *__restrict__ geom,
+                                                                       const double *__restrict__ render, int chunks,
+                                                                       const int *__restrict__ tri_link, int ntri,
+                                                                       const unsigned long long *__restrict__ zbuf, T *__restrict__ depth,
+                                                                       unsigned char *__restrict__ labels) {
+    const int f = blockIdx.y;
+    long start, lo, hi;
+    int w;
+    const long n = depth_crop(geom, f, pixel_capacity, start, w);
+    depth_chunk(start, n, blockIdx.x, chunks, lo, hi);
+    const double scale = render[(size_t)f * RN_WIDTH + 6];
+    for (long a = lo + threadIdx.x; a < hi; a += DEPTH_THREADS) {       // [lo, hi) lies inside [0, pixel_capacity)
+        const unsigned long long key = zbuf[a];
+        T d = T(0);
+        unsigned char lab = 255;
+        const unsigned t = (unsigned)key;
+        if (key != RN_EMPTY && t < (unsigned)ntri) {
+            const double df = (double)__uint_as_float((unsigned)(key >> 32));
+            d = render_quantise(df / scale, T(0));
+            const int l = tri_link[t];
+            if (d != T(0)) lab = (unsigned char)l;
+        }
+        depth[a] = d;
+        labels[a] = lab;
+    }
+}
+
+template <typename T>
+static void render_launch(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int ntri, const int *geom,
+                          const double *render, void *depth, unsigned char *labels, unsigned long long *zbuf, long pixel_capacity,
+                          hipStream_t st) {
+    const long chunks = depth_chunks(pixel_capacity, nframes);          // depth.hip's grid
+    const dim3 grid((unsigned)chunks, nframes);
+    hipLaunchKernelGGL(render_clear_kernel, grid, dim3(DEPTH_THREADS), 0, st, pixel_capacity, geom, (int)chunks, zbuf);
+    if (ntri > 0)
+        hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((ntri + DEPTH_WAVES - 1) / DEPTH_WAVES), nframes), dim3(DEPTH_THREADS), 0, st,
+                           verts, tris, tri_link, V, ntri, pixel_capacity, geom, render, zbuf);
+    hipLaunchKernelGGL(render_resolve_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, pixel_capacity, geom, render, (int)chunks, tri_link, ntri,
+                       zbuf, (T *)depth, labels);
+}
+
+}  // namespace ancsh
+
+using namespace ancsh;
+
+extern "C" int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                         const int *geom, const double *render, void *depth, unsigned char *labels,
+                                         unsigned long long *zbuf, long pixel_capacity, void *stream) {
+    ANCSH_REQUIRE(nframes >= 0, "render_depth_labels: bad shape nframes=%d", nframes);
+    ANCSH_REQUIRE(nframes <= 65535, "render_depth_labels: %d frames exceed the 65535-frame grid range; split the batch", nframes);
+    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
+                  "render_depth_labels: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 30), "render_depth_labels: pixel_capacity=%ld pixels out of range",
+                  pixel_capacity);
+    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "render_depth_labels: T=%d triangles must be in [0, 2^24)", T);
+    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "render_depth_labels: V=%d vertices must be in [0, 2^24)", V);
+    ANCSH_REQUIRE(verts && tris && tri_link && geom && render && depth && labels && zbuf, "render_depth_labels: null pointer");
+    ANCSH_REQUIRE(((size_t)depth & 15) == 0 && ((size_t)labels & 7) == 0 && ((size_t)render & 7) == 0 && ((size_t)zbuf & 7) == 0,
+                  "render_depth_labels: depth must be 16-byte aligned, labels, render and zbuf 8-byte aligned (the crops inside them may "
+                  "start anywhere)");
+    if (nframes == 0) return ANCSH_OK;
+    if (depth_type == ANCSH_DEPTH_U16)
+        render_launch<unsigned short>(nframes, verts, tris, tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity,
+                                      (hipStream_t)stream);
+    else
+        render_launch<float>(nframes, verts, tris, tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity, (hipStream_t)stream);
+    return check_launch("render_depth_labels");
+}

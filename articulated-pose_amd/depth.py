@@ -9,6 +9,10 @@ The helpers below compute them in float64; they are cast to float32 once, when a
 The second half of the module annotates rendered frames (ancsh_depth_annotate_stream; reference: tools/preprocess_data.py:226-348): a frame
 is then (depth_crop, link-label crop, (row0, col0)) and travels with one float64 scene table (pack_frame_scene) that holds the camera and
 every link's camera-to-URDF map; the device makes the 7-column annotated rows [x y z | cx cy cz | part] dataset.point_gt_build reads.
+
+The third renders such frames on the GPU (ancsh_render_depth_labels; reference: tools/render_synthetic.py:180-225, on the host): the
+triangle meshes of an object's links (pack_mesh) and one float64 render table per frame (pack_render_scene: the inverse of the scene
+table's camera model and link maps) go in, depth crops and link-label crops come out where the annotation reads them.
 """
 import numpy as np
 import torch
@@ -467,3 +471,206 @@ def annotate_depth_batch(frames, scenes, depth_dtype, K, device="cuda:0"):
                                         capacity=total + len(depths))
     off = off.cpu().numpy()
     return rows[:int(off[-1])].cpu().numpy(), off, cnt.cpu().numpy(), lc.cpu().numpy()
+
+
+# ---- rendered frames: articulated triangle meshes -> the depth and link-label crops above (ancsh_render_depth_labels) --------------------
+RENDER_WIDTH, RENDER_HEAD, RENDER_LINK = 208, 16, 12            # include/ancsh_hip.h, ANCSH_RENDER_*
+
+
+def pack_mesh(links):
+    """The mesh of an articulated object for ancsh_render_depth_labels.  links: per link one (vertices (v, 3), faces (f, 3)) pair -- the
+    vertices in the link's model frame, the frame its world pose places (tools/render_synthetic.py loads one mesh per link) -- or None for
+    a link without geometry; at most 16 links.  -> (verts (V, 3) float32, tris (T, 3) int32 -- indices into verts --, tri_link (T,) int32),
+    contiguous; ValueError on a non-finite vertex, a face index out of range or more than 16 links."""
+    if not isinstance(links, (list, tuple)) or len(links) > SCENE_MAX_LINKS:
+        raise ValueError("links: a list of at most %d (vertices, faces) pairs or None, one per link" % SCENE_MAX_LINKS)
+    verts, tris, tri_link, base = [], [], [], 0
+    for l, link in enumerate(links):
+        if link is None:
+            continue
+        try:
+            v, f = link
+            v, f = np.asarray(v, np.float64), np.asarray(f)
+        except (TypeError, ValueError):
+            raise ValueError("link %d: expected (vertices (v, 3), faces (f, 3)) or None" % l)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or (f.size and not np.issubdtype(f.dtype, np.integer)):
+            raise ValueError("link %d: expected vertices (v, 3) and integer faces (f, 3), got %s and %s %s" % (l, v.shape, f.dtype, f.shape))
+        with np.errstate(over="ignore"):
+            v32 = v.astype(np.float32)
+        if not np.isfinite(v32).all():
+            raise ValueError("link %d: every vertex must be finite in float32" % l)
+        if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+            raise ValueError("link %d: a face names a vertex outside [0, %d)" % (l, v.shape[0]))
+        verts.append(v32)
+        tris.append(f.astype(np.int64) + base)
+        tri_link.append(np.full(f.shape[0], l, np.int32))
+        base += v.shape[0]
+    cat = lambda parts, shape, dtype: np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros(shape, dtype)
+    verts, tris, tri_link = cat(verts, (0, 3), np.float32), cat(tris, (0, 3), np.int32), cat(tri_link, (0,), np.int32)
+    if verts.shape[0] >= (1 << 24) or tris.shape[0] >= (1 << 24):
+        raise ValueError("a mesh holds fewer than 2^24 vertices and triangles, got %d and %d" % (verts.shape[0], tris.shape[0]))
+    return verts, tris, tri_link
+
+
+def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, width, depth_scale=1.0, z_min=1e-6):
+    """One frame's render table (RENDER_WIDTH,) float64 for ancsh_render_depth_labels (include/ancsh_hip.h has its layout), from
+    pack_frame_scene's arguments with its conventions: the inverse of what that table makes ancsh_depth_annotate_stream do.  P is the
+    inverse of the affine pixel -> (s, t) map of coord_unprojection_from_projmat(projMat, height, width); R_l is the inverse of the 4 x 4
+    G_l = cam2world @ pinv(model2world_l.T) pack_frame_scene composes for row vectors, stored in column form: R_l (v, 1) is the camera
+    point (x', y', z) of model point v, and M_l of the frame's scene applied to it is canon2urdf_l v."""
+    V, Pm = np.asarray(viewMat, np.float64), np.asarray(projMat, np.float64)
+    if V.shape != (4, 4):
+        raise ValueError("viewMat must be (4, 4), got %s" % (V.shape,))
+    pos, orn = np.asarray(link_world_pos, np.float64), np.asarray(link_world_orn, np.float64)
+    L = pos.shape[0] if pos.ndim == 2 else 0
+    if not 1 <= L <= SCENE_MAX_LINKS or pos.shape != (L, 3) or orn.shape != (L, 4):
+        raise ValueError("link_world_pos must be (L, 3) and link_world_orn (L, 4) [x y z w] for 1..%d links, got %s and %s"
+                         % (SCENE_MAX_LINKS, pos.shape, orn.shape))
+    depth_scale, z_min = float(depth_scale), float(z_min)
+    if not (np.isfinite(depth_scale) and depth_scale > 0 and np.isfinite(z_min) and z_min > 0):
+        raise ValueError("depth_scale and z_min must be finite and > 0, got %r and %r" % (depth_scale, z_min))
+    C = coord_unprojection_from_projmat(Pm, height, width)
+    A = np.array([[C[0], C[1]], [C[3], C[4]]])
+    Ainv = np.linalg.inv(A)
+    table = np.zeros(RENDER_WIDTH)
+    table[0:2], table[3:5] = Ainv[0], Ainv[1]
+    table[2], table[5] = -(Ainv @ np.array([C[2], C[5]]))
+    table[6], table[7], table[8] = depth_scale, z_min, L
+    cam2world = np.linalg.pinv(V.T)
+    cam2world[:3, :] = -cam2world[:3, :]
+    for l in range(L):
+        model2world = _rotation_from_quaternion(orn[l, 3], orn[l, 0], orn[l, 1], orn[l, 2])
+        model2world[:3, 3] = pos[l]
+        G = cam2world @ np.linalg.pinv(model2world.T)
+        table[RENDER_HEAD + RENDER_LINK * l:RENDER_HEAD + RENDER_LINK * (l + 1)] = np.linalg.inv(G).T[:3].reshape(12)
+    if not np.isfinite(table).all():
+        raise ValueError("the camera or a link pose is singular: the render table is not finite")
+    return table
+
+
+def check_render_tables(render, n):
+    """-> render as a C-contiguous (n, RENDER_WIDTH) float64 array (one table is repeated for every frame); ValueError unless every table is
+    finite with depth_scale > 0, z_min > 0, an integer nlinks in 1..16 and zero reserved values."""
+    try:
+        a = np.asarray(render, np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape == (RENDER_WIDTH,):
+        a = np.broadcast_to(a, (n, RENDER_WIDTH))
+    if a.shape != (n, RENDER_WIDTH):
+        raise ValueError("render must be (%d, %d): one depth.pack_render_scene table, or one per frame, got shape %s" % (n, RENDER_WIDTH, a.shape))
+    a = np.ascontiguousarray(a)
+    if not np.isfinite(a).all():
+        raise ValueError("render: every value must be finite")
+    for i, t in enumerate(a):
+        if not (t[6] > 0 and t[7] > 0) or t[8] != np.floor(t[8]) or not 1 <= t[8] <= SCENE_MAX_LINKS or (t[9:RENDER_HEAD] != 0).any():
+            raise ValueError("render table %d: depth_scale and z_min must be > 0, nlinks an integer in [1, %d] and the reserved values 0"
+                             % (i, SCENE_MAX_LINKS))
+    return a
+
+
+def check_crops(crops, max_frames=None):
+    """-> (shapes [(h, w)], origins (n, 2) int32) of 1..max_frames crops (h, w, (row0, col0)) to render; ValueError otherwise (the limits
+    are check_depth_frames')."""
+    if not isinstance(crops, (list, tuple)) or not 1 <= len(crops) <= (max_frames or 65535):
+        raise ValueError("crops: a list of 1..%d (h, w, (row0, col0)) tuples" % (max_frames or 65535))
+    shapes, origins = [], []
+    for i, c in enumerate(crops):
+        try:
+            h, w, (r0, c0) = c
+            ok = all(int(v) == v for v in (h, w, r0, c0)) and h >= 1 and w >= 1 and abs(r0) < (1 << 24) and abs(c0) < (1 << 24) \
+                and r0 + h <= (1 << 24) and c0 + w <= (1 << 24) and h * w < (1 << 30)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("crop %d: expected (h, w, (row0, col0)), integers, h and w >= 1, image rows / columns below 2^24, got %r" % (i, c))
+        shapes.append((int(h), int(w)))
+        origins.append((int(r0), int(c0)))
+    return shapes, np.asarray(origins, np.int32).reshape(len(shapes), 2)
+
+
+def pack_crop_geometry(shapes, origins, geom, first=0):
+    """pack_depth_frames' geometry rows for crops that have no pixels yet: geom (n, 5) int32 {start, h, w, row0, col0}, crop k at pixel
+    `first` + the pixels of the crops before it.  -> the pixel after the last crop."""
+    a = int(first)
+    for k, (h, w) in enumerate(shapes):
+        geom[k] = (a, h, w, origins[k][0], origins[k][1])
+        a += h * w
+    return a
+
+
+def mesh_to_device(mesh, device):
+    """pack_mesh's arrays on the device, as render_depth takes them: (verts, tris, tri_link, V, T); an empty array still owns one element of
+    memory (the entry refuses null pointers)."""
+    verts, tris, tri_link = mesh
+    verts, tris, tri_link = np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(tris, np.int32), np.ascontiguousarray(tri_link, np.int32)
+    if verts.ndim != 2 or verts.shape[1] != 3 or tris.ndim != 2 or tris.shape[1] != 3 or tri_link.shape != (tris.shape[0],):
+        raise ValueError("a mesh is depth.pack_mesh's (verts (V, 3), tris (T, 3), tri_link (T,)), got shapes %s, %s, %s"
+                         % (verts.shape, tris.shape, tri_link.shape))
+    V, T = verts.shape[0], tris.shape[0]
+    if T and (tris.min() < 0 or tris.max() >= V or tri_link.min() < 0 or tri_link.max() >= SCENE_MAX_LINKS):
+        raise ValueError("a mesh's triangles name vertices in [0, %d) and links in [0, %d)" % (V, SCENE_MAX_LINKS))
+    up = lambda a, shape: torch.from_numpy(a if a.size else np.zeros(shape, a.dtype)).to(device)
+    return up(verts, (1, 3)), up(tris, (1, 3)), up(tri_link, (1,)), V, T
+
+
+def render_depth(mesh, geom, render, depth_dtype, out=None, scratch=None, pixel_capacity=None):
+    """ancsh_render_depth_labels on device tensors (no host sync): mesh = mesh_to_device's (verts, tris, tri_link, V, T), geom (B, 5) int32,
+    render (B, RENDER_WIDTH) float64.  -> (depth (pixel_capacity,) int16 bits of uint16 / float32, labels (pixel_capacity,) uint8); out =
+    the same pair preallocated (a captured step passes slot-owned buffers), else pixel_capacity pixels of depth 0 / label 255; scratch: the
+    (pixel_capacity,) int64 z-buffer.  Every pixel of every crop is written, the others keep what they held."""
+    verts, tris, tri_link, V, T = mesh
+    name = check_depth_dtype(depth_dtype)
+    _, tt, kind = DEPTH_DTYPES[name]
+    if not verts.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = verts.device
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
+            or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
+        raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
+    B = int(geom.shape[0])
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
+            or not (geom.is_contiguous() and render.is_contiguous()):
+        raise ValueError("geom must be (B, 5) int32 and render (B, %d) float64, contiguous" % RENDER_WIDTH)
+    if out is None:
+        if pixel_capacity is None:
+            raise ValueError("render_depth needs out=(depth, labels) or pixel_capacity")
+        out = (torch.zeros((int(pixel_capacity),), dtype=tt, device=dev), torch.full((int(pixel_capacity),), NOT_OBJECT, dtype=torch.uint8, device=dev))
+    depth, labels = out
+    kinds = {torch.float32: 1, torch.int16: 0}
+    if hasattr(torch, "uint16"):
+        kinds[torch.uint16] = 0
+    if kinds.get(depth.dtype) != kind or depth.dim() != 1 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 1-d %s tensor" % name)
+    cap_px = int(depth.shape[0])
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
+    if scratch is None:
+        scratch = torch.empty((max(1, cap_px),), dtype=torch.int64, device=dev)
+    elif scratch.dtype != torch.int64 or scratch.numel() < cap_px or not scratch.is_contiguous():
+        raise ValueError("scratch must be a contiguous int64 tensor of >= %d elements" % cap_px)
+    _lib.require_cuda(tris, tri_link, geom, render, depth, labels, scratch)
+    _lib.call("ancsh_render_depth_labels", B, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(geom),
+              _lib.ptr(render), _lib.ptr(depth), _lib.ptr(labels), _lib.ptr(scratch), cap_px)
+    return depth, labels
+
+
+def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"):
+    """Eager wrapper: mesh = pack_mesh's arrays, render_scenes = one pack_render_scene table or one per crop, crops = a list of (h, w,
+    (row0, col0)) -> a list of (depth_crop (h, w) of depth_dtype, label_crop (h, w) uint8, (row0, col0)): exactly the frames
+    AncshPipeline.submit_depth(..., scene=, rig=) and annotate_depth_batch take.  One host sync; the streaming pipeline
+    (AncshPipeline.submit_render) has none, and no pixel of it ever reaches the host."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    name = check_depth_dtype(depth_dtype)
+    shapes, origins = check_crops(crops)
+    tables = check_render_tables(render_scenes, len(shapes))
+    geom = np.zeros((len(shapes), GEOM_WORDS), np.int32)
+    total = pack_crop_geometry(shapes, origins, geom)
+    depth, labels = render_depth(mesh_to_device(mesh, dev), torch.from_numpy(geom).to(dev), torch.from_numpy(tables).to(dev), name,
+                                 pixel_capacity=total)
+    depth, labels = depth.cpu().numpy(), labels.cpu().numpy()
+    depth = depth.view(np.uint16) if name == "uint16" else depth
+    return [(depth[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(), labels[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(),
+             (int(g[3]), int(g[4]))) for g in geom]

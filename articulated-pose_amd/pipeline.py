@@ -16,7 +16,7 @@ import torch
 
 from .network import Network
 from .pose import PoseSolver
-from .stream import (JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
+from .stream import (ALL_INPUTS, JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
                      check_side_inputs, fill_rows, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row, pump,
                      refuse_built_frame, refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
 
@@ -98,7 +98,7 @@ class _Slot(object):
         self.graph32 = None
         self.out32 = None
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
-        for inp in SIDE_INPUTS:                 # a side input the slot is not built with: no device buffer
+        for inp in ALL_INPUTS:                  # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
@@ -137,7 +137,7 @@ class _Slot(object):
         self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
         unit = None
         if depth:
-            unit = self._init_depth(B, cap, depth, device, annotate=opts.link_counts)
+            unit = self._init_depth(B, cap, depth, device, annotate=opts.link_counts, rendered=opts.render)
         else:
             fill_rows(kind, self.np_rows, K)
             self.np_off[:] = np.arange(B + 1) * (cap // B)
@@ -178,24 +178,28 @@ class _Slot(object):
         img = self.outputs.get("label_images")
         self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
 
-    def _init_depth(self, B, capacity, depth, device, annotate=False):
+    def _init_depth(self, B, capacity, depth, device, annotate=False, rendered=False):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
         counts, and host / device views of the header's geometry, camera and dest blocks.  Until the first submit: B crops of random
         depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes).
         annotate (annotated frames, ancsh_depth_annotate_stream): the mask buffers carry the link labels -- the same bytes per pixel --, the
         scratch holds 16 counters per chunk, and the slot owns the per-link counts; the header's camera block is not read, the scene
         tables (a side input) carry the camera.  Until the first submit: every pixel labelled 0.
+        rendered (render_mesh=, ancsh_render_depth_labels): the step writes the pixel and label buffers itself, so they have no pinned
+        staging, and the slot owns the renderer's z-buffer, 8 bytes a pixel.  Until the first submit: the mesh in its model frames in
+        front of the unit camera.
         -> the unit camera's six coefficients and the depth scale (what stream.unit_scene builds the slot's first scenes from)."""
         from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS, SCENE_MAX_LINKS
         npt, tt, _ = DEPTH_DTYPES[depth]
         self.pix = torch.zeros((capacity,), dtype=tt, device=device)
         self.mask = torch.zeros((capacity,), dtype=torch.uint8, device=device)
-        self.h_pix = torch.zeros((capacity,), dtype=tt).pin_memory()
-        self.h_mask = torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
+        self.h_pix = None if rendered else torch.zeros((capacity,), dtype=tt).pin_memory()
+        self.h_mask = None if rendered else torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
+        self.zbuf = torch.zeros((capacity,), dtype=torch.int64, device=device) if rendered else None
         self.scratch = torch.zeros((B * MAX_CHUNKS * (SCENE_MAX_LINKS if annotate else 1),), dtype=torch.int32, device=device)
         self.counts = torch.zeros((B,), dtype=torch.int32, device=device)
         lay, hdr = self.layout, self.h_hdr.numpy()
-        self.np_pix, self.np_mask = self.h_pix.numpy().view(npt), self.h_mask.numpy()
+        self.np_pix, self.np_mask = (None, None) if rendered else (self.h_pix.numpy().view(npt), self.h_mask.numpy())
         self.np_geom = hdr[lay.geom].reshape(B, GEOM_WORDS)
         self.np_cam = hdr[lay.cam].view(np.float32).reshape(B, CAM_WORDS)
         self.geom = self.hdr[lay.geom].view(B, GEOM_WORDS)
@@ -205,13 +209,10 @@ class _Slot(object):
         per = capacity // B
         w = max(1, int(np.sqrt(per)))
         h = per // w
-        if npt == np.uint16:
-            self.np_pix[:] = rs.randint(32768, 65536, capacity).astype(np.uint16)
-            scale = 1.0 / 65535.0
-        else:
-            self.np_pix[:] = rs.uniform(0.5, 1.0, capacity).astype(np.float32)
-            scale = 1.0
-        self.np_mask[:] = 0 if annotate else 1
+        scale = 1.0 / 65535.0 if npt == np.uint16 else 1.0
+        if not rendered:
+            self.np_pix[:] = rs.randint(32768, 65536, capacity).astype(np.uint16) if npt == np.uint16 else rs.uniform(0.5, 1.0, capacity).astype(np.float32)
+            self.np_mask[:] = 0 if annotate else 1
         unit = (1.0 / w, 0.0, -0.5, 0.0, 1.0 / h, -0.5, scale)
         for b in range(B):
             self.np_geom[b] = (b * per, h, w, 0, 0)
@@ -220,8 +221,9 @@ class _Slot(object):
         if lay.dest is not None:
             self.np_dest[:] = self.np_geom[:, 0]
         self.np_nf[:] = 1.0
-        self.pix.copy_(self.h_pix)
-        self.mask.copy_(self.h_mask)
+        if not rendered:
+            self.pix.copy_(self.h_pix)
+            self.mask.copy_(self.h_mask)
         self.hdr.copy_(self.h_hdr)
         return unit
 
@@ -303,13 +305,17 @@ class AncshPipeline(object):
     depth_capacity with point_ground_truth and build_point_gt: annotated depth frames -- depth crop, link-label crop and a scene table per
         frame (submit_depth(..., scene=, rig=, frame=)); the step starts with ancsh_depth_annotate_stream, then ancsh_point_gt_build and
         the sampler.  retire(link_counts=True) returns the valid pixels per link.  Refuses label_images: its rows are link-major.
+    render_mesh (with those annotated-frame options): depth.pack_mesh's arrays, uploaded once and shared by the slots; the step starts with
+        ancsh_render_depth_labels, which renders every frame's depth and label crops into the slot's device buffers in front of
+        ancsh_depth_annotate_stream.  submit_render / stream_render_batches take crop geometry and tables only: no pixel crosses PCIe.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
-                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False):
+                 ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
+                 render_mesh=None):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -317,7 +323,7 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss, build_gt_pose)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -325,6 +331,10 @@ class AncshPipeline(object):
         self.couple, self.seed = couple, seed
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
+        self.mesh = None
+        if o.render:                            # the mesh: checked, then uploaded once and shared by all slots
+            from .depth import mesh_to_device
+            self.mesh = mesh_to_device(render_mesh, self.device)
         # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
@@ -409,6 +419,9 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.render:                    # rendered frames: the mesh and the slot's render tables -> its depth and label crops, on the device
+            from .depth import render_depth
+            render_depth(self.mesh, sl.geom, sl.render, self.depth_dtype, out=(sl.pix, sl.mask), scratch=sl.zbuf)
         if self.link_counts:               # annotated depth frames: the slot's depth and label crops -> its annotated rows, offsets and counts
             from .depth import depth_annotate
             depth_annotate(sl.pix, sl.mask, sl.geom, sl.scene, out=(sl.src_rows, off, sl.counts, sl.link_counts), scratch=sl.scratch)
@@ -636,6 +649,8 @@ class AncshPipeline(object):
         o = self.opts
         if o.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
+        if o.render:
+            raise RuntimeError("a pipeline built with render_mesh= renders its frames on the device: submit_render()")
         annotated = o.link_counts
         refuse_built_frame(o, frame, "AncshPipeline")
         refuse_side_inputs(o.inputs, dict(scene=scene), "AncshPipeline")
@@ -667,6 +682,44 @@ class AncshPipeline(object):
                 return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
             return n_valid, nf, stage, dict(scene=scenes) if annotated else {}
         self._enqueue(front, seed, tag, cloud_base, gt=gt, frame=frame, rig=rig)
+
+    def submit_render(self, crops, norm_factors, render, scene, rig, gt=None, frame=None, seed=None, tag=None, cloud_base=0):
+        """Enqueue one batch of frames the step renders itself (asynchronous; a pipeline built with render_mesh=): crops = 1..batch_size
+        tuples (h, w, (row0, col0)) -- the crop of the full image to render and its origin --, norm_factors = one finite float per
+        frame, render = one (208,) float64 table (depth.pack_render_scene) or one per frame, scene and rig (both required), gt, frame,
+        seed, tag, cloud_base: as submit_depth takes them for annotated frames.  Only the geometry and the tables cross to the device:
+        ancsh_render_depth_labels writes the slot's depth and label crops in front of ancsh_depth_annotate_stream.  A short batch is
+        padded with its first crop (which the padding frames render again, where it lies), and all crops, padding included, must fit
+        depth_capacity pixels.  Bad input raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.
+        Either way the pipeline stays usable."""
+        o = self.opts
+        if not o.render:
+            raise RuntimeError("submit_render() needs AncshPipeline(..., %s); depth frames made elsewhere travel through submit_depth()"
+                               % SIDE["render"].built_with)
+        refuse_built_frame(o, frame, "AncshPipeline")
+
+        def front():
+            from .depth import check_crops, check_scenes, pack_crop_geometry
+            if render is None or scene is None or rig is None:
+                raise ValueError(SIDE["render"].missing)
+            shapes, origins = check_crops(crops, self.B)
+            n_valid = len(shapes)
+            nf = np.asarray(norm_factors, np.float32).reshape(-1)
+            if nf.size != n_valid or not np.isfinite(nf).all():
+                raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n_valid, nf.tolist()))
+            scenes = check_scenes(scene, n_valid, self.K)
+            pixels = sum(h * w for h, w in shapes)
+            padded = pixels + (self.B - n_valid) * shapes[0][0] * shapes[0][1]
+            if padded > o.depth_capacity:
+                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
+                                 % (padded, o.depth_capacity))
+
+            def stage(sl):
+                pack_crop_geometry(shapes, origins, sl.np_geom)
+                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and render the same bytes)
+                return []
+            return n_valid, nf, stage, dict(scene=scenes)
+        self._enqueue(front, seed, tag, cloud_base, render=render, gt=gt, frame=frame, rig=rig)
 
     def _enqueue(self, front, seed, tag, cloud_base, **side):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
@@ -796,3 +849,18 @@ class AncshPipeline(object):
             self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
         yield from pump(batches, self._inflight, len(self.slots), submit,
                         lambda: self.retire(flags, articulation, label_images=label_images, link_counts=link_counts))
+
+    def stream_render_batches(self, batches, flags=False, articulation=False, link_counts=False):
+        """stream_depth_batches over submit_render: batches yields (crops, norm_factors, {render=, scene=, rig=, gt=, frame=, seed=,
+        cloud_base=}) or the same with a tag behind the dict (the tag defaults to the batch's index); yields what stream_depth_batches
+        yields for the same frames, in submission order: the valid-pixel counts last, link_counts=True: the (n_valid, 16) per-link
+        counts behind them."""
+        check_built_with(self.opts, "stream_render_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts)
+
+        def submit(k, item):
+            item = tuple(item)
+            if len(item) < 3 or not isinstance(item[2], dict):
+                raise ValueError("a stream_render_batches item is (crops, norm_factors, {render=, scene=, rig=, ...}[, tag])")
+            self.submit_render(item[0], item[1], tag=item[3] if len(item) > 3 else k, **item[2])
+        yield from pump(batches, self._inflight, len(self.slots), submit,
+                        lambda: self.retire(flags, articulation, link_counts=link_counts))

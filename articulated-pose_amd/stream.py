@@ -174,6 +174,26 @@ SIDE_INPUTS = (             # in the order of their H2D copies; gt, frame, rig i
 SIDE = {inp.name: inp for inp in SIDE_INPUTS}
 
 
+def unit_render(K, unit):
+    """unit_scene's inverse: the pixel map of the camera `unit`, one link with the identity map."""
+    r = np.zeros(depth_mod.RENDER_WIDTH)
+    r[0], r[2], r[4], r[5] = 1.0 / unit[0], -unit[2] / unit[0], 1.0 / unit[4], -unit[5] / unit[4]
+    r[6], r[7], r[8] = unit[6], 1e-6, 1
+    r[depth_mod.RENDER_HEAD:depth_mod.RENDER_HEAD + depth_mod.RENDER_LINK] = np.eye(4)[:3].reshape(12)
+    return r
+
+
+# One more row of the table, kept beside it: the render tables of a pipeline that renders its frames itself (render_mesh=).  It is the
+# first H2D copy of such a batch (the step's first launch reads it) and, like scene, it travels by name, never by position in an item.
+RENDERED = "depth_capacity=<pixels>, " + ANNOTATED + ", render_mesh=<depth.pack_mesh(...)>"
+RENDER_INPUT = SideInput("render", "render", RENDERED, lambda K: (depth_mod.RENDER_WIDTH,), torch.float64, unit_render,
+                         lambda v, n, K: depth_mod.check_render_tables(v, n), "first",
+                         "a pipeline built with render_mesh= renders its frames: submit_render(crops, norm_factors, render=..., scene=..., "
+                         "rig=...) needs one depth.pack_render_scene table per frame")
+ALL_INPUTS = (RENDER_INPUT,) + SIDE_INPUTS
+SIDE[RENDER_INPUT.name] = RENDER_INPUT
+
+
 def side_host(inp, B, K, unit=None, pin=True):
     """The (B,) + shape(K) host staging of side input `inp`, holding its fill; pinned unless pin=False."""
     host = torch.zeros((B,) + inp.shape(K), dtype=inp.dtype)
@@ -184,7 +204,7 @@ def side_host(inp, B, K, unit=None, pin=True):
 
 def refuse_side_inputs(built, given, cls):
     """ValueError for the first side input of `given` = {name: value or None} that a `cls` with the side inputs `built` does not take."""
-    for inp in SIDE_INPUTS:
+    for inp in ALL_INPUTS:
         if given.get(inp.name) is not None and inp not in built:
             raise ValueError("%s needs %s(..., %s)" % (inp.name, cls, inp.built_with))
 
@@ -206,7 +226,7 @@ def require_side_inputs(built, given):
 def check_side_inputs(built, given, n, K, cls):
     """Refuse and check, input by input in the table's order -> {name: the checked (n, ...) array, or None} for the side inputs `built`."""
     out = {}
-    for inp in SIDE_INPUTS:
+    for inp in ALL_INPUTS:
         v = given.get(inp.name)
         if v is not None:
             refuse_side_inputs(built, {inp.name: v}, cls)
@@ -247,7 +267,7 @@ def check_joint_source(joint_source):
 
 
 Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
-                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts "
+                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts render "
                                  "coord_regress_loss record_width record_key art_width rows inputs")
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
@@ -255,13 +275,15 @@ OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # th
 def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw_capacity=None, depth_capacity=None, depth_dtype="uint16",
                   keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
                   ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
-                  coord_regress_loss="L2", build_gt_pose=False):
+                  coord_regress_loss="L2", build_gt_pose=False, render_mesh=None):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
     (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
     width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
     raw_capacity in the result is the slots' capacity: depth_capacity's value on a depth pipeline.
     build_gt_pose (with point_ground_truth): the step fits both ground-truth pose tables itself, so `frame` is no side input and of `gt`
-    only the box extents (columns 13..15) are read."""
+    only the box extents (columns 13..15) are read.
+    render_mesh (annotated depth frames only): the step renders the frames itself from this mesh (depth.pack_mesh), so `render` is one
+    more side input and no pixel travels in."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -303,6 +325,8 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     if link_counts and label_images:
         raise ValueError("label_images=True carries rows back to pixels in pixel order; the rows of annotated depth frames "
                          "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
+    if render_mesh is not None and not link_counts:
+        raise ValueError("render_mesh renders the annotated depth frames of the step on the device: it needs " + RENDERED.rsplit(", ", 1)[0])
     if raw_capacity is not None:
         if not couple:
             raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
@@ -326,9 +350,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), link_counts, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
+                bool(label_images), link_counts, render_mesh is not None, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
-    return o._replace(inputs=tuple(i for i in SIDE_INPUTS if raw_capacity is not None and getattr(o, i.option)
+    return o._replace(inputs=tuple(i for i in ALL_INPUTS if raw_capacity is not None and getattr(o, i.option)
                                    and not (build_gt_pose and i.name == "frame")))
 
 

@@ -46,6 +46,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     streamed joint states), ancsh_fit_quality_rec (the streamed fit quality), ancsh_gt_error_rec (the streamed errors
                                  *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_point_gt_build (that ground truth built from
                                  *     annotated clouds), ancsh_depth_annotate_stream (those clouds made from depth and link-label crops),
+                                 *     ancsh_render_depth_labels (those crops rendered from articulated triangle meshes),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1168,6 +1169,54 @@ int ancsh_depth_label_images(int nclouds, int depth_type, const void *depth, con
 int ancsh_depth_annotate_stream(int nclouds, int depth_type, const void *depth, const unsigned char *labels, long pixel_capacity,
                                 const int *geom, const double *scene, float *rows, long capacity, int *offsets, int *counts,
                                 int *link_counts, int *scratch, void *stream);
+
+/* Depth and link-label frames of an articulated object rendered on the device: triangle meshes, one render table per frame and the depth
+ * entries' geometry rows -> depth crops and label crops in exactly the buffers ancsh_depth_annotate_stream reads.  The reference renders
+ * on the host, one frame at a time (tools/render_synthetic.py:180-225, pybullet's getCameraImage); pixel parity with that rasteriser is no
+ * goal.  The contract is geometric: this entry is the exact inverse of the camera model ancsh_depth_annotate_stream applies to a frame's
+ * coordinate point (scene[7..12], the C coefficients).  The ABI version is unchanged; callers detect the entry by its symbol.
+ *   nframes, depth_type, geom, pixel_capacity : as the depth entries take them; geom (nframes, 5) int32 {start h w row0 col0} names the crop
+ *     to render and where it lies in the pixel buffers;
+ *   verts (V, 3) float32 : every link's vertices in its model frame (the frame the link's world pose places; the URDF visual origin is the
+ *     caller's to apply);  tris (T, 3) int32 : vertex indices;  tri_link (T,) int32 : the link of a triangle, in [0, 16);
+ *   render : (nframes, ANCSH_RENDER_WIDTH = 208) float64, 8-byte aligned, per frame:
+ *     [0..5] P00 P01 P02 P10 P11 P12 : col = (P00 s + P01 t) + P02, row = (P10 s + P11 t) + P12 -- the inverse of the affine map
+ *     s = C00 col + C01 row + C02, t = C10 col + C11 row + C12 of scene[7..12]   [6] depth_scale   [7] z_min > 0   [8] nlinks, 1..16
+ *     [9..15] reserved, 0   then per link l, ANCSH_RENDER_LINK = 12 wide, at ANCSH_RENDER_HEAD + 12 l: R, row-major 3 x 4, model frame ->
+ *     the camera point (x', y', z);
+ *   depth (pixel_capacity) of depth_type, 16-byte aligned; labels (pixel_capacity) bytes, 8-byte aligned; zbuf (pixel_capacity) uint64 of
+ *     working memory, 8-byte aligned.
+ * Everything below is float64, evaluated in exactly the written order (no contraction).
+ *   Vertex v of link l: q_a = ((R[a][0] v0 + R[a][1] v1) + R[a][2] v2) + R[a][3];  z = q_2, s = q_0 / z, t = q_1 / z;  col, row as above;
+ *   fixed point X = rint(256 col), Y = rint(256 row) (int64).  A triangle is dropped WHOLE (no clipping: the reference's camera stands off
+ *   the object) when a vertex has z < z_min, a non-finite value, |X| or |Y| >= 2^25, an index outside [0, V), or when its link is
+ *   outside [0, nlinks).
+ *   The sample point of crop pixel (i, j) is full-image (row0 + i, col0 + j) exactly, no half-pixel offset -- the point
+ *   ancsh_depth_annotate_stream unprojects --: p = (256 (col0 + j), 256 (row0 + i)) in (X, Y).
+ *   Coverage, int64: E_uv(p) = (v.X - u.X)(p.Y - u.Y) - (v.Y - u.Y)(p.X - u.X); for the triangle (a, b, c): area2 = E_ab(c) (zero: the
+ *   triangle is dropped; both orientations are kept, no back-face culling), E_a = E_bc(p), E_b = E_ca(p), E_c = E_ab(p); p is covered
+ *   when E_a, E_b, E_c all have the sign of area2 or are zero.
+ *   Depth, perspective-correct: lambda_k = (double)E_k / (double)area2 (both exact: below 2^53);
+ *   invz = (lambda_a (1 / z_a) + lambda_b (1 / z_b)) + lambda_c (1 / z_c);  d = 1 / invz.
+ *   The pixel keeps the MINIMUM key (bits of (float)d) << 32 | triangle index over the triangles that cover it: the nearest surface, ties
+ *   to the lowest triangle index.  A minimum does not depend on the order: the result is deterministic byte for byte.
+ *   Resolve, df = (double)(float)d: uint16: q = rint(df / depth_scale), written when 1 <= q <= 65535; float32: (float)(df / depth_scale),
+ *   written when finite and positive; labels = tri_link[winner].  Every other pixel of the crop reads depth 0 and label 255.  EVERY pixel
+ *   of every crop is written (no prefill needed); pixels of no crop are left alone.
+ * A frame whose nlinks is outside 1..16 or whose z_min is not > 0 renders an all-background crop; a frame with h < 1 or w < 1 or whose
+ * crop lies outside [0, pixel_capacity) writes nothing.  Crops that share pixels (the padding frames of a short batch alias the first
+ * frame's) must carry the same table: each launch finishes before the next starts, so equal frames write equal bytes.
+ * Three launches: clear (the keys of every crop), raster (one wave per (triangle, frame): the wave sweeps the triangle's bounding box clipped
+ * to the crop, one 64-bit integer atomic minimum per covered pixel), resolve.  Graph-capturable: the grids depend on (pixel_capacity,
+ * nframes, T) only; no host sync, no allocation.  nframes == 0 launches nothing and returns 0; T == 0 renders background.
+ * Checked before any launch: 0 <= nframes <= 65535, depth_type, 0 <= pixel_capacity < 2^30, 0 <= T < 2^24, 0 <= V < 2^24, null pointers,
+ * the alignments (depth 16 bytes; labels, render, zbuf 8 bytes). */
+#define ANCSH_RENDER_WIDTH 208
+#define ANCSH_RENDER_HEAD 16
+#define ANCSH_RENDER_LINK 12
+int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                              const int *geom, const double *render, void *depth, unsigned char *labels, unsigned long long *zbuf,
+                              long pixel_capacity, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -1,0 +1,147 @@
+"""Throughput of the GPU renderer (ancsh_render_depth_labels) and of the stream it feeds: AncshPipeline(..., render_mesh=mesh), whose step
+renders its own depth and link-label crops, against the annotated depth stream fed the SAME frames from host memory, at equal frames and
+configs[2]'s shape (K = 3, 32 x 1024, 10000 / 200 hypotheses, couple=True, synthetic weights, predicted joints).  The object: three
+tessellated boxes, one per link, under random views and openings; one SIDE x SIDE uint16 crop per frame.  Measured:
+  operator: frames/s of the entry alone on one batch of 32 frames (HIP events around --calls back-to-back calls);
+  two legs, alternated in one process for --rounds rounds:
+    r: the rendered stream (geometry, render table and scene table per frame cross to the device: 20 + 1664 + 1920 bytes);
+    d: the annotated depth stream on the frames depth.render_depth_frames made of the same tables BEFORE the clock starts (3 bytes per
+       pixel more; whatever renderer made them on the host is not in the timed loop: the best case without the new entry).
+Prints one JSON line: a record, not a gate.
+
+    python tools/render_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import articulated_pose_amd  # noqa: E402,F401
+from articulated_pose_amd import depth as D  # noqa: E402
+from articulated_pose_amd.dataset import identity_rig  # noqa: E402
+from articulated_pose_amd.pipeline import AncshPipeline  # noqa: E402
+from articulated_pose_amd.weights import synthetic_weights  # noqa: E402
+
+SCALE = 1e-3
+LO, HI = np.array([-0.16, -0.11, -0.06]), np.array([0.16, 0.11, 0.06])
+
+
+def tessellated_box(lo, hi, n):
+    """(vertices, faces) of the box [lo, hi], every face an n x n grid of quads, two triangles each: 12 n^2 triangles."""
+    verts, faces = [], []
+    for axis in range(3):
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        for side in (lo, hi):
+            base = len(verts)
+            for i in range(n + 1):
+                for j in range(n + 1):
+                    p = np.empty(3)
+                    p[axis], p[u], p[v] = side[axis], lo[u] + (hi[u] - lo[u]) * i / n, lo[v] + (hi[v] - lo[v]) * j / n
+                    verts.append(p)
+            for i in range(n):
+                for j in range(n):
+                    a = base + i * (n + 1) + j
+                    faces += [(a, a + 1, a + n + 2), (a, a + n + 2, a + n + 1)]
+    return np.asarray(verts), np.asarray(faces, np.int64)
+
+
+def make_scene(rs, side):
+    """One frame: (render table, scene table) of the three-link object seen from about 1.5 units under a slightly random view."""
+    t, near, far = np.tan(np.radians(20.0)), 0.1, 100.0
+    P = np.array([[1.0 / t, 0, 0, 0], [0, 1.0 / t, 0, 0], [0, 0, (far + near) / (near - far), 2 * far * near / (near - far)], [0, 0, -1.0, 0]])
+    V = np.eye(4)
+    V[:3, :3] = D._rotation_from_rpy(*rs.uniform(-0.5, 0.5, 3))[:3, :3]
+    V[:3, 3] = (rs.uniform(-0.03, 0.03), rs.uniform(-0.03, 0.03), -rs.uniform(1.45, 1.6))
+    opening = rs.uniform(0.1, 1.2)
+    pos = np.array([[0.0, 0.0, 0.0], [0.3, 0.02, 0.12], [-0.34, -0.03, 0.02]])
+    orn = np.array([[0, 0, 0, 1.0], [0, np.sin(opening / 2), 0, np.cos(opening / 2)], [0, 0, np.sin(0.2), np.cos(0.2)]])
+    zero = np.zeros((3, 3))
+    return (D.pack_render_scene(V, P, pos, orn, side, side, depth_scale=SCALE),
+            D.pack_frame_scene(V, P, pos, orn, zero, zero, zero[:2], [[0], [1], [2]], side, side, depth_scale=SCALE))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
+    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--frames", type=int, default=320)
+    ap.add_argument("--side", type=int, default=128, help="the image and the crop: side x side pixels")
+    ap.add_argument("--tess", type=int, default=8, help="quads per box edge: 12 tess^2 triangles per link")
+    ap.add_argument("--calls", type=int, default=200, help="back-to-back calls of the operator between its two events")
+    args = ap.parse_args()
+    K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
+    rs = np.random.RandomState(0)
+    mesh = D.pack_mesh([tessellated_box(LO, HI, args.tess)] * K)
+    crops = [(args.side, args.side, (0, 0))] * B
+    nf, rigs, jf = np.ones(B, np.float32), np.tile(identity_rig(K), (B, 1)), rs.normal(size=(B, 13))
+    rbatches, dbatches, valid = [], [], []
+    for _ in range(args.frames // B):
+        tables = [make_scene(rs, args.side) for _ in range(B)]
+        rt, sc = np.stack([t[0] for t in tables]), np.stack([t[1] for t in tables])
+        frames = D.render_depth_frames(mesh, rt, crops, "uint16", dev)
+        valid.append(np.mean([(f[1] != D.NOT_OBJECT).sum() for f in frames]))
+        rbatches.append((crops, nf, dict(render=rt, scene=sc, rig=rigs, frame=jf)))
+        dbatches.append((frames, nf, dict(scene=sc, rig=rigs, frame=jf)))
+    # the operator alone, on the last batch
+    d_mesh = D.mesh_to_device(mesh, dev)
+    geom = np.zeros((B, D.GEOM_WORDS), np.int32)
+    cap = D.pack_crop_geometry([c[:2] for c in crops], [c[2] for c in crops], geom)
+    d_geom, d_rt = torch.from_numpy(geom).to(dev), torch.from_numpy(rt).to(dev)
+    out = (torch.zeros(cap, dtype=torch.int16, device=dev), torch.zeros(cap, dtype=torch.uint8, device=dev))
+    zbuf = torch.zeros(cap, dtype=torch.int64, device=dev)
+    for _ in range(20):
+        D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    op_ms = []
+    for _ in range(args.rounds):
+        e0.record()
+        for _ in range(args.calls):
+            D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
+        e1.record()
+        torch.cuda.synchronize()
+        op_ms.append(e0.elapsed_time(e1) / args.calls)
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
+              depth_capacity=cap, depth_dtype="uint16")
+    rendered = AncshPipeline(K, wa, wn, B, N, dev, render_mesh=mesh, **kw).prepare()
+    annotated = AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
+    torch.cuda.synchronize()
+
+    def leg(name, passes):
+        t0, n = time.perf_counter(), 0
+        gen = (rendered.stream_render_batches(rbatches[k] for _ in range(passes) for k in range(len(rbatches))) if name == "r" else
+               annotated.stream_depth_batches(dbatches[k] for _ in range(passes) for k in range(len(dbatches))))
+        for _ in gen:
+            n += 1
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / n          # ms per batch of B frames, steady state over the slots
+
+    for name in "rd":                                         # warm-up: every slot replayed with real input
+        leg(name, 1)
+    ms = {name: [] for name in "rd"}
+    for _ in range(args.rounds):
+        for name in "rd":
+            ms[name].append(leg(name, args.passes))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    op = float(np.median(op_ms))
+    print(json.dumps({"metric": "frames/s: the renderer alone; the rendered stream (r) vs the annotated depth stream fed the same frames from the host (d)",
+                      "device": torch.cuda.get_device_name(0), "operator_frames_per_s": round(1e3 * B / op, 1), "operator_ms_per_batch": round(op, 4),
+                      "operator_ms_per_batch_rounds": [round(x, 4) for x in op_ms],
+                      "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
+                      "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()}, "r_over_d": round(med["r"] / med["d"], 4),
+                      "h2d_bytes_per_batch_r": B * (4 * D.GEOM_WORDS + 8 * D.RENDER_WIDTH + 8 * D.SCENE_WIDTH),
+                      "h2d_bytes_per_batch_d": B * (4 * D.GEOM_WORDS + 8 * D.SCENE_WIDTH) + 3 * cap,
+                      "object_pixels_per_frame": round(float(np.mean(valid)), 1), "crop_pixels_per_frame": args.side * args.side,
+                      "triangles": int(mesh[1].shape[0]), "vertices": int(mesh[0].shape[0]),
+                      "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(rbatches) * B,
+                                "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
+
+
+if __name__ == "__main__":
+    main()
