@@ -149,6 +149,12 @@ SIGNATURES = {
     # those crops themselves, rendered from articulated triangle meshes (no ABI bump, detected by its symbol): nframes, depth_type, verts, tris,
     # tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity, stream
     "ancsh_render_depth_labels": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long, _vp],
+    # that entry's and the annotation's tables, built from an object's kinematic table and a pose per frame (no ABI bump, detected by its
+    # symbol): nframes, kin, pose, render, scene, stream
+    "ancsh_pose_scene_build": [_c_int, _vp, _vp, _vp, _vp, _vp],
+    # crops centred on the projected object (no ABI bump, detected by its symbol): nframes, verts, tris, tri_link, V, T, render, geom, bounds,
+    # stream
+    "ancsh_render_centre_crops": [_c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -167,9 +167,90 @@ static void render_launch(int nframes, const float *verts, const int *tris, cons
                        zbuf, (T *)depth, labels);
 }
 
+// ---- crops centred on the projected object (ancsh_render_centre_crops) ---------------------------------------------------------------------
+// Block f owns frame f: its threads stride over the triangles, every referenced vertex goes through render_vertex -- the raster kernel's own
+// transform --, a wave reduces the four bounds of its counted vertices with shuffles and takes ONE integer atomic per bound on the frame's
+// scratch row; the block's first thread then turns the row into the crop's origin.  Minimum and maximum do not depend on the order of
+// their operands: the origin is a pure function of the input.
+constexpr int RN_CENTRE = ANCSH_CROP_CENTRE;
+constexpr int RN_INT_MAX = 2147483647, RN_INT_MIN = -2147483647 - 1;
+
+__global__ __launch_bounds__(DEPTH_THREADS) void render_centre_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                      const int *__restrict__ tri_link, int V, int T,
+                                                                      const double *__restrict__ render, int *__restrict__ geom,
+                                                                      int *__restrict__ bounds) {
+    const int f = blockIdx.x;
+    int *g = geom + (size_t)f * DEPTH_GEOM, *b = bounds + (size_t)f * 4;
+    if (threadIdx.x < 4) atomicExch(b + threadIdx.x, (threadIdx.x & 1) ? RN_INT_MIN : RN_INT_MAX);      // {Xmin Xmax Ymin Ymax}: the empty bounds
+    if (!(g[3] == RN_CENTRE && g[4] == RN_CENTRE)) return;              // uniform over the block: a frame with a real origin is left alone
+    __threadfence();
+    __syncthreads();
+    const double *rt = render + (size_t)f * RN_WIDTH;
+    const int nl = render_nlinks(rt);
+    int xmin = RN_INT_MAX, xmax = RN_INT_MIN, ymin = RN_INT_MAX, ymax = RN_INT_MIN;
+    for (int t = threadIdx.x; t < T && nl > 0; t += DEPTH_THREADS) {
+        const int l = tri_link[t];
+        if (l < 0 || l >= nl) continue;
+        const double *R = rt + RN_HEAD + RN_LINK * l;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = tris[3 * (size_t)t + k];
+            if (i < 0 || i >= V) continue;                              // vertices count one by one, not per dropped triangle
+            const RenderVertex a = render_vertex(verts + 3 * (size_t)i, R, rt);
+            if (!a.ok) continue;
+            const int X = (int)a.X, Y = (int)a.Y;                       // |X|, |Y| < 2^25
+            xmin = X < xmin ? X : xmin;
+            xmax = X > xmax ? X : xmax;
+            ymin = Y < ymin ? Y : ymin;
+            ymax = Y > ymax ? Y : ymax;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const int x0 = __shfl_xor(xmin, o), x1 = __shfl_xor(xmax, o), y0 = __shfl_xor(ymin, o), y1 = __shfl_xor(ymax, o);
+        xmin = x0 < xmin ? x0 : xmin;
+        xmax = x1 > xmax ? x1 : xmax;
+        ymin = y0 < ymin ? y0 : ymin;
+        ymax = y1 > ymax ? y1 : ymax;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(b + 0, xmin);
+        atomicMax(b + 1, xmax);
+        atomicMin(b + 2, ymin);
+        atomicMax(b + 3, ymax);
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int x0 = atomicAdd(b + 0, 0), x1 = atomicAdd(b + 1, 0), y0 = atomicAdd(b + 2, 0), y1 = atomicAdd(b + 3, 0);
+        int row0 = 0, col0 = 0;
+        if (x0 <= x1) {                                                 // a vertex counted; |sum| < 2^26, the shift is arithmetic: floor
+            col0 = ((x0 + x1) >> 9) - (g[2] >> 1);
+            row0 = ((y0 + y1) >> 9) - (g[1] >> 1);
+        }
+        g[3] = row0;
+        g[4] = col0;
+    }
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
+
+extern "C" int ancsh_render_centre_crops(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                         const double *render, int *geom, int *bounds, void *stream) {
+    ANCSH_REQUIRE(nframes >= 0, "render_centre_crops: bad shape nframes=%d", nframes);
+    ANCSH_REQUIRE(nframes <= 65535, "render_centre_crops: %d frames exceed the 65535-frame grid range; split the batch", nframes);
+    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "render_centre_crops: T=%d triangles must be in [0, 2^24)", T);
+    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "render_centre_crops: V=%d vertices must be in [0, 2^24)", V);
+    ANCSH_REQUIRE(verts && tris && tri_link && render && geom && bounds, "render_centre_crops: null pointer");
+    ANCSH_REQUIRE(((size_t)render & 7) == 0 && ((size_t)geom & 3) == 0 && ((size_t)bounds & 3) == 0,
+                  "render_centre_crops: render must be 8-byte aligned, geom and bounds 4-byte aligned");
+    if (nframes == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(render_centre_kernel, dim3(nframes), dim3(DEPTH_THREADS), 0, (hipStream_t)stream, verts, tris, tri_link, V, T, render,
+                       geom, bounds);
+    return check_launch("render_centre_crops");
+}
 
 extern "C" int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
                                          const int *geom, const double *render, void *depth, unsigned char *labels,

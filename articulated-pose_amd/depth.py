@@ -13,6 +13,10 @@ every link's camera-to-URDF map; the device makes the 7-column annotated rows [x
 The third renders such frames on the GPU (ancsh_render_depth_labels; reference: tools/render_synthetic.py:180-225, on the host): the
 triangle meshes of an object's links (pack_mesh) and one float64 render table per frame (pack_render_scene: the inverse of the scene
 table's camera model and link maps) go in, depth crops and link-label crops come out where the annotation reads them.
+
+The fourth builds both tables on the GPU (ancsh_pose_scene_build; reference: pybullet's forward kinematics in
+tools/render_synthetic.py:140-158, 206-217, on the host): an object's kinematic table (pack_kinematics), uploaded once, and one pose per
+frame (pack_pose: joint values and a view matrix) go in; and centres crops on the projected object (ancsh_render_centre_crops).
 """
 import numpy as np
 import torch
@@ -674,3 +678,304 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
     depth = depth.view(np.uint16) if name == "uint16" else depth
     return [(depth[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(), labels[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(),
              (int(g[3]), int(g[4]))) for g in geom]
+
+
+# ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred
+# on the projected object (ancsh_render_centre_crops) ---------------------------------------------------------------------------------------
+KIN_WIDTH, KIN_HEAD, KIN_LINK, POSE_WIDTH = 672, 32, 40, 32             # include/ancsh_hip.h, ANCSH_KIN_* and ANCSH_POSE_WIDTH
+CROP_CENTRE = -(1 << 31)                                                # ANCSH_CROP_CENTRE: row0 = col0 = this asks for a centred crop
+JOINT_KINDS = {"fixed": 0, "revolute": 1, "prismatic": 2}
+_RIGID_TOL = 1e-9
+
+
+def _compose(A, B):
+    """C = A o B of 3 x 4 rigid maps in the contract's order (include/ancsh_hip.h, ancsh_pose_scene_build)."""
+    C = np.empty((3, 4))
+    for i in range(3):
+        for j in range(4):
+            v = (A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j]
+            C[i, j] = v + A[i, 3] if j == 3 else v
+    return C
+
+
+def _joint_motion(kind, a, q):
+    """J(q) (3, 4) of a joint of `kind` about / along the unit axis a, in the contract's order."""
+    J = np.eye(4)[:3].copy()
+    if kind == 1:
+        s, c = np.sin(q), np.cos(q)
+        Kx = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        for i in range(3):
+            for j in range(3):
+                J[i, j] = (c * (1.0 if i == j else 0.0) + s * Kx[i, j]) + ((1.0 - c) * a[i]) * a[j]
+    elif kind == 2:
+        J[:, 3] = q * a
+    return J
+
+
+def _kin_links(kin):
+    """(nlinks, the (nlinks, KIN_LINK) view of a kinematic table's links)."""
+    L = int(kin[14])
+    return L, kin[KIN_HEAD:KIN_HEAD + KIN_LINK * L].reshape(L, KIN_LINK)
+
+
+def _is_rotation(R):
+    return np.isfinite(R).all() and np.abs(R @ R.T - np.eye(3)).max() <= _RIGID_TOL and np.linalg.det(R) > 0
+
+
+def pack_kinematics(projMat, height, width, parents, joint_kinds, joint_xyz, joint_rpy, joint_axis, urdf_link_xyz, urdf_link_rpy,
+                    urdf_joint_xyz, parts_map, depth_scale=1.0, z_min=1e-6, min_link_pixels=10, base=None):
+    """An object's kinematic table (KIN_WIDTH,) float64 for ancsh_pose_scene_build (include/ancsh_hip.h has its layout): the camera of
+    pack_frame_scene and pack_render_scene (projMat, height, width, depth_scale, z_min, min_link_pixels), the tree -- parents (L,): -1 for
+    link 0, the only root, otherwise < l; joint_kinds (L,): "fixed" | "revolute" | "prismatic" or 0 | 1 | 2; joint_xyz, joint_rpy (L, 3): the
+    URDF origin of the joint that carries link l, from the parent link's frame to link l's at q = 0; joint_axis (L, 3): its axis in link l's
+    frame, normalised here (link 0's three rows are not read) -- and what pack_frame_scene reads per link: urdf_link_xyz, urdf_link_rpy,
+    urdf_joint_xyz (the `link == 1 and L == 2` offset rule included) and parts_map.  base: link 0's world pose, (4, 4) or (3, 4) rigid; None =
+    the identity, the reference's.  ValueError for a zero axis on a moving joint, a parent that is not < l, more than 16 links, a
+    non-finite value."""
+    P = np.asarray(projMat, np.float64)
+    parents = np.asarray(parents).reshape(-1)
+    L = parents.shape[0]
+    if not 1 <= L <= SCENE_MAX_LINKS:
+        raise ValueError("an object has 1..%d links, got %d" % (SCENE_MAX_LINKS, L))
+    if parents[0] != -1 or any(not (0 <= parents[l] < l and int(parents[l]) == parents[l]) for l in range(1, L)):
+        raise ValueError("parents: -1 for link 0, the only root; every other link's parent is an integer in [0, l), got %s" % (parents.tolist(),))
+    try:
+        kinds = [JOINT_KINDS[k] if isinstance(k, str) else int(k) for k in joint_kinds]
+    except (KeyError, TypeError, ValueError):
+        kinds = []
+    if len(kinds) != L or any(k not in (0, 1, 2) for k in kinds):
+        raise ValueError("joint_kinds: one of %s (or 0 | 1 | 2) per link, got %r" % (sorted(JOINT_KINDS), joint_kinds))
+    jx, jr, ja = (np.asarray(v, np.float64) for v in (joint_xyz, joint_rpy, joint_axis))
+    xyz, rpy = np.asarray(urdf_link_xyz, np.float64), np.asarray(urdf_link_rpy, np.float64)
+    for name, v in (("joint_xyz", jx), ("joint_rpy", jr), ("joint_axis", ja), ("urdf_link_xyz", xyz), ("urdf_link_rpy", rpy)):
+        if v.shape != (L, 3):
+            raise ValueError("%s must be (%d, 3), got %s" % (name, L, v.shape))
+        if not np.isfinite(v[1:] if name.startswith("joint_") else v).all():
+            raise ValueError("%s: every value must be finite" % name)
+    depth_scale, z_min = float(depth_scale), float(z_min)
+    if not (np.isfinite(depth_scale) and depth_scale > 0 and np.isfinite(z_min) and z_min > 0):
+        raise ValueError("depth_scale and z_min must be finite and > 0, got %r and %r" % (depth_scale, z_min))
+    kin = np.zeros(KIN_WIDTH)
+    kin[0:6] = unprojection_from_projmat(P, height, width)
+    kin[6] = depth_scale
+    C = kin[7:13] = coord_unprojection_from_projmat(P, height, width)
+    kin[13], kin[14] = float(min_link_pixels), L
+    Ainv = np.linalg.inv(np.array([[C[0], C[1]], [C[3], C[4]]]))        # pack_render_scene's pixel map
+    kin[16:18], kin[19:21] = Ainv[0], Ainv[1]
+    kin[18], kin[21] = -(Ainv @ np.array([C[2], C[5]]))
+    kin[22] = z_min
+    flat = [(int(link), j) for j, group in enumerate(parts_map) for link in group]
+    if len(set(l for l, _ in flat)) != len(flat) or any(not 0 <= l < L for l, _ in flat):
+        raise ValueError("parts_map must name each of its links once, all in [0, %d): got %r" % (L, parts_map))
+    rank = {l: (r, j) for r, (l, j) in enumerate(flat)}
+    if base is None:
+        T0 = np.eye(4)[:3]
+    else:
+        T0 = np.asarray(base, np.float64)
+        if T0.shape not in ((4, 4), (3, 4)) or not np.isfinite(T0).all() or not _is_rotation(T0[:3, :3]) \
+                or (T0.shape == (4, 4) and not np.array_equal(T0[3], [0, 0, 0, 1])):
+            raise ValueError("base: link 0's world pose must be a rigid (4, 4) or (3, 4) matrix")
+        T0 = T0[:3]
+    for l in range(L):
+        k = kin[KIN_HEAD + KIN_LINK * l:KIN_HEAD + KIN_LINK * (l + 1)]
+        k[0], k[1] = rank.get(l, (-1, 0))
+        k[2], k[3] = parents[l], kinds[l] if l else 0
+        if l == 0:
+            k[4:16] = T0.reshape(12)
+        else:
+            T = _rotation_from_rpy(*jr[l])
+            T[:3, 3] = jx[l]
+            k[4:16] = T[:3].reshape(12)
+            n = np.linalg.norm(ja[l])
+            if kinds[l] != 0:
+                if not (np.isfinite(n) and n > 0):
+                    raise ValueError("link %d: a %s joint needs a non-zero, finite axis, got %s"
+                                     % (l, "revolute" if kinds[l] == 1 else "prismatic", ja[l].tolist()))
+                k[16:19] = ja[l] / n
+        if l == 1 and L == 2:                                           # pack_frame_scene's rule (tools/preprocess_data.py:239-242)
+            joint = np.asarray(urdf_joint_xyz, np.float64)
+            if joint.ndim != 2 or joint.shape[0] < 1 or joint.shape[1] != 3:
+                raise ValueError("urdf_joint_xyz must be (>= 1, 3) for a two-link object, got %s" % (joint.shape,))
+            offset = joint[0]
+        else:
+            offset = -xyz[l]
+        k[19:28] = _rotation_from_rpy(*rpy[l])[:3, :3].reshape(9)
+        k[28:31] = offset
+    if not np.isfinite(kin).all():
+        raise ValueError("the camera, a joint origin or a link frame is not finite: the kinematic table is not finite")
+    return kin
+
+
+def check_kinematics(kin, K=None):
+    """-> kin as a C-contiguous (KIN_WIDTH,) float64 array; ValueError unless it is finite, holds 1..16 links with parents < l (link 0: -1),
+    joint kinds in {0, 1, 2}, unit axes on moving joints and rotations in T_l and Rc_l (all to 1e-9), depth_scale and z_min > 0, zero
+    reserved values and zero links beyond nlinks; K: the ranks and parts are check_scenes' too."""
+    try:
+        a = np.ascontiguousarray(np.asarray(kin, np.float64))
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape != (KIN_WIDTH,):
+        raise ValueError("kinematics: one (%d,) table (depth.pack_kinematics), got shape %s" % (KIN_WIDTH, a.shape))
+    if not np.isfinite(a).all():
+        raise ValueError("kinematics: every value must be finite")
+    nl = a[14]
+    if nl != np.floor(nl) or not 1 <= nl <= SCENE_MAX_LINKS:
+        raise ValueError("kinematics: nlinks must be an integer in [1, %d], got %r" % (SCENE_MAX_LINKS, float(nl)))
+    if not (a[6] > 0 and a[22] > 0 and a[13] >= 0) or a[15] != 0 or (a[23:KIN_HEAD] != 0).any():
+        raise ValueError("kinematics: depth_scale and z_min must be > 0, min_link_pixels >= 0 and the reserved values 0")
+    L, links = _kin_links(a)
+    if (a[KIN_HEAD + KIN_LINK * L:] != 0).any() or (links[:, 31:] != 0).any():
+        raise ValueError("kinematics: links beyond nlinks and reserved values must be 0")
+    for l, k in enumerate(links):
+        if k[2] != (-1 if l == 0 else np.floor(k[2])) or (l and not 0 <= k[2] < l):
+            raise ValueError("kinematics: link %d's parent must be %s, got %r" % (l, "-1" if l == 0 else "an integer in [0, %d)" % l, float(k[2])))
+        if k[3] not in (0.0, 1.0, 2.0):
+            raise ValueError("kinematics: link %d's joint kind must be 0, 1 or 2, got %r" % (l, float(k[3])))
+        if l and k[3] != 0 and abs(np.linalg.norm(k[16:19]) - 1.0) > _RIGID_TOL:
+            raise ValueError("kinematics: link %d's joint axis must be a unit vector, got %s" % (l, k[16:19].tolist()))
+        if not _is_rotation(k[4:16].reshape(3, 4)[:, :3]) or not _is_rotation(k[19:28].reshape(3, 3)):
+            raise ValueError("kinematics: link %d's T_l and Rc_l must hold rotations" % l)
+    if K is not None:
+        used = links[links[:, 0] != -1]
+        if sorted(used[:, 0].tolist()) != list(range(len(used))) or not ((used[:, 1] >= 0) & (used[:, 1] < K) & (used[:, 1] == np.floor(used[:, 1]))).all():
+            raise ValueError("kinematics: the ranks of the used links must be a permutation of 0 .. %d (-1 = not used) and their parts integers "
+                             "in [0, %d), got %s and %s" % (len(used) - 1, K, links[:, 0].tolist(), links[:, 1].tolist()))
+    return a
+
+
+def pack_pose(q, viewMat):
+    """One frame's pose (POSE_WIDTH,) float64 for ancsh_pose_scene_build: q = up to 16 joint values, link l's at position l (link 0's and
+    those of fixed joints are not read), viewMat = the (4, 4) view matrix in the `.reshape(4, 4).T` form of tools/preprocess_data.py:228
+    (world -> eye), which must be rigid.  ValueError otherwise (check_poses' rules)."""
+    q = np.asarray(q, np.float64).reshape(-1)
+    V = np.asarray(viewMat, np.float64)
+    if q.shape[0] > SCENE_MAX_LINKS:
+        raise ValueError("q holds one joint value per link, at most %d, got %d" % (SCENE_MAX_LINKS, q.shape[0]))
+    if V.shape != (4, 4) or not np.array_equal(V[3], [0, 0, 0, 1]):
+        raise ValueError("viewMat must be a rigid (4, 4) matrix with the last row (0, 0, 0, 1)")
+    pose = np.zeros(POSE_WIDTH)
+    pose[:q.shape[0]] = q
+    pose[16:28] = V[:3].reshape(12)
+    return check_poses(pose, 1)[0]
+
+
+def check_poses(pose, n):
+    """-> pose as a C-contiguous (n, POSE_WIDTH) float64 array (one pose is repeated for every frame); ValueError unless every pose is
+    finite, its view's rotation orthonormal to 1e-9 (and proper) and its reserved values 0."""
+    try:
+        a = np.asarray(pose, np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape == (POSE_WIDTH,):
+        a = np.broadcast_to(a, (n, POSE_WIDTH))
+    if a.shape != (n, POSE_WIDTH):
+        raise ValueError("pose must be (%d, %d): one depth.pack_pose row, or one per frame, got shape %s" % (n, POSE_WIDTH, a.shape))
+    a = np.ascontiguousarray(a)
+    if not np.isfinite(a).all():
+        raise ValueError("pose: every value must be finite")
+    for i, p in enumerate(a):
+        if (p[28:] != 0).any() or not _is_rotation(p[16:28].reshape(3, 4)[:, :3]):
+            raise ValueError("pose %d: the view matrix must be rigid (its rotation orthonormal to 1e-9) and the reserved values 0" % i)
+    return a
+
+
+def forward_kinematics(kin, q):
+    """Every link's world pose (L, 4, 4) float64 of the object `kin` (pack_kinematics) at the joint values q (link l's at position l), in
+    ancsh_pose_scene_build's own order: X_l = T_l o J_l(q_l), composed from each link upwards to the root.  Plain numpy."""
+    kin = check_kinematics(kin)
+    L, links = _kin_links(kin)
+    qq = np.zeros(SCENE_MAX_LINKS)
+    q = np.asarray(q, np.float64).reshape(-1)
+    qq[:min(q.shape[0], SCENE_MAX_LINKS)] = q[:SCENE_MAX_LINKS]
+    X = [_compose(k[4:16].reshape(3, 4), _joint_motion(int(k[3]) if l else 0, k[16:19], qq[l])) for l, k in enumerate(links)]
+    out = np.tile(np.eye(4), (L, 1, 1))
+    for l in range(L):
+        W, p = X[l], int(links[l, 2])
+        while p >= 0:
+            W, p = _compose(X[p], W), int(links[p, 2])
+        out[l, :3] = W
+    return out
+
+
+def pose_scene_build(kin, pose, out=None):
+    """ancsh_pose_scene_build on device tensors (no host sync): kin (KIN_WIDTH,) float64, pose (B, POSE_WIDTH) float64 -> (render (B,
+    RENDER_WIDTH), scene (B, SCENE_WIDTH)) float64; out = the same pair preallocated (a captured step passes slot-owned buffers)."""
+    if not kin.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    B = int(pose.shape[0])
+    if kin.dtype != torch.float64 or tuple(kin.shape) != (KIN_WIDTH,) or pose.dtype != torch.float64 or tuple(pose.shape) != (B, POSE_WIDTH) \
+            or not (kin.is_contiguous() and pose.is_contiguous()):
+        raise ValueError("kin must be (%d,) float64 and pose (B, %d) float64, contiguous" % (KIN_WIDTH, POSE_WIDTH))
+    if out is None:
+        out = (torch.empty((B, RENDER_WIDTH), dtype=torch.float64, device=kin.device), torch.empty((B, SCENE_WIDTH), dtype=torch.float64, device=kin.device))
+    render, scene = out
+    if render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
+            or not (render.is_contiguous() and scene.is_contiguous()):
+        raise ValueError("out must be (render (B, %d), scene (B, %d)) float64, contiguous" % (RENDER_WIDTH, SCENE_WIDTH))
+    _lib.require_cuda(pose, render, scene)
+    _lib.call("ancsh_pose_scene_build", B, _lib.ptr(kin), _lib.ptr(pose), _lib.ptr(render), _lib.ptr(scene))
+    return render, scene
+
+
+def pose_scene_tables(kin, poses, device="cuda:0"):
+    """Eager wrapper: kin = one pack_kinematics table, poses = one pack_pose row or (n, 32) of them -> (render (n, 208), scene (n, 240))
+    float64 numpy arrays read back from ancsh_pose_scene_build: what submit_render and render_depth_frames take.  One host sync."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    kin = check_kinematics(kin)
+    p = np.asarray(poses, np.float64)
+    poses = check_poses(p, 1 if p.ndim == 1 else p.shape[0])
+    render, scene = pose_scene_build(torch.from_numpy(kin).to(dev), torch.from_numpy(poses).to(dev))
+    return render.cpu().numpy(), scene.cpu().numpy()
+
+
+def centre_crop_origins(mesh, geom, render, scratch=None):
+    """ancsh_render_centre_crops on device tensors (no host sync): mesh = mesh_to_device's, geom (B, 5) int32, render (B, RENDER_WIDTH)
+    float64; the rows of geom whose row0 and col0 both hold CROP_CENTRE get the origin that centres their crop on the projected object, in
+    place.  scratch: (B, 4) int32 of working memory.  -> geom."""
+    verts, tris, tri_link, V, T = mesh
+    if not verts.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
+            or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
+        raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
+    B = int(geom.shape[0])
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
+            or not (geom.is_contiguous() and render.is_contiguous()):
+        raise ValueError("geom must be (B, 5) int32 and render (B, %d) float64, contiguous" % RENDER_WIDTH)
+    if scratch is None:
+        scratch = torch.empty((max(1, B), 4), dtype=torch.int32, device=verts.device)
+    elif scratch.dtype != torch.int32 or scratch.numel() < 4 * B or not scratch.is_contiguous():
+        raise ValueError("scratch must be a contiguous int32 tensor of >= %d elements" % (4 * B))
+    _lib.require_cuda(tris, tri_link, geom, render, scratch)
+    _lib.call("ancsh_render_centre_crops", B, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(render),
+              _lib.ptr(geom), _lib.ptr(scratch))
+    return geom
+
+
+def check_posed_crops(crops, max_frames=None):
+    """check_crops for crops whose origin may be None = centred on the projected object -> (shapes, origins (n, 2) int32, CROP_CENTRE in
+    both places of a centred crop)."""
+    if not isinstance(crops, (list, tuple)):
+        raise ValueError("crops: a list of (h, w, (row0, col0) or None) tuples")
+    centred = [isinstance(c, (list, tuple)) and len(c) == 3 and c[2] is None for c in crops]
+    shapes, origins = check_crops([(c[0], c[1], (0, 0)) if m else c for c, m in zip(crops, centred)], max_frames)
+    origins[np.asarray(centred, bool)] = CROP_CENTRE
+    return shapes, origins
+
+
+def centre_crops(mesh, render_tables, sizes, device="cuda:0"):
+    """Eager wrapper: mesh = pack_mesh's arrays, render_tables = one render table or one per crop, sizes = a list of (h, w) -> the (n, 2)
+    int32 origins (row0, col0) that centre each h x w crop on its frame's projected object (ancsh_render_centre_crops; (0, 0) where nothing
+    projects): what submit_render's crops take.  One host sync."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    shapes, origins = check_posed_crops([(h, w, None) for h, w in sizes])
+    tables = check_render_tables(render_tables, len(shapes))
+    geom = np.zeros((len(shapes), GEOM_WORDS), np.int32)
+    pack_crop_geometry(shapes, origins, geom)
+    d_geom = torch.from_numpy(geom).to(dev)
+    centre_crop_origins(mesh_to_device(mesh, dev), d_geom, torch.from_numpy(tables).to(dev))
+    return d_geom.cpu().numpy()[:, 3:5].copy()

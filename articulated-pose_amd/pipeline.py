@@ -16,7 +16,7 @@ import torch
 
 from .network import Network
 from .pose import PoseSolver
-from .stream import (ALL_INPUTS, JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
+from .stream import (ALL_INPUTS, EVERY_INPUT, JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
                      check_side_inputs, fill_rows, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row, pump,
                      refuse_built_frame, refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
 
@@ -98,8 +98,9 @@ class _Slot(object):
         self.graph32 = None
         self.out32 = None
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
-        for inp in ALL_INPUTS:                  # a side input the slot is not built with: no device buffer
+        for inp in EVERY_INPUT:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
+        self.bounds = None
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
 
@@ -149,6 +150,11 @@ class _Slot(object):
             setattr(self, "h_" + inp.name, host)
             setattr(self, "np_" + inp.name, host.numpy())
             setattr(self, inp.name, host.to(device))
+        if opts.posed:                         # what ancsh_pose_scene_build writes and the renderer and the annotation read, and the crop
+            from .depth import RENDER_WIDTH, SCENE_WIDTH         # centring's scratch: slot-owned, never an H2D target
+            self.render = torch.zeros((B, RENDER_WIDTH), dtype=torch.float64, device=device)
+            self.scene = torch.zeros((B, SCENE_WIDTH), dtype=torch.float64, device=device)
+            self.bounds = torch.zeros((B, 4), dtype=torch.int32, device=device)
         if opts.build_gt_pose:                 # what ancsh_gt_pose_build writes behind the sampler and the two error launches read: slot-owned,
             self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
             self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
@@ -308,6 +314,10 @@ class AncshPipeline(object):
     render_mesh (with those annotated-frame options): depth.pack_mesh's arrays, uploaded once and shared by the slots; the step starts with
         ancsh_render_depth_labels, which renders every frame's depth and label crops into the slot's device buffers in front of
         ancsh_depth_annotate_stream.  submit_render / stream_render_batches take crop geometry and tables only: no pixel crosses PCIe.
+    kinematics (with render_mesh): depth.pack_kinematics' table, uploaded once and shared by the slots; the step starts with
+        ancsh_pose_scene_build, which writes the slot's render and scene tables from one pose per frame (depth.pack_pose: joint values and a
+        view matrix), and ancsh_render_centre_crops, which centres the crops that ask for it on the projected object, in front of the
+        renderer.  submit_posed / stream_posed_batches take crops and poses only: 32 doubles per frame cross PCIe.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
@@ -315,7 +325,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None):
+                 render_mesh=None, kinematics=None):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -323,7 +333,7 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -331,10 +341,15 @@ class AncshPipeline(object):
         self.couple, self.seed = couple, seed
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
-        self.mesh = None
+        self.mesh = self.kin = None
+        if o.posed:                             # the kinematic table: checked here, uploaded once below and shared by all slots
+            from .depth import check_kinematics
+            kinematics = check_kinematics(kinematics, num_parts)
         if o.render:                            # the mesh: checked, then uploaded once and shared by all slots
             from .depth import mesh_to_device
             self.mesh = mesh_to_device(render_mesh, self.device)
+        if o.posed:
+            self.kin = torch.from_numpy(kinematics).to(self.device)
         # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
@@ -419,6 +434,10 @@ class AncshPipeline(object):
         from . import _lib
         from .dataset import RAW_JCLS_COL, RAW_NCHAN
         seed, off, nf = sl.header(self.B)
+        if self.posed:                     # posed objects: the slot's poses -> its render and scene tables, then the centred crops' origins
+            from .depth import centre_crop_origins, pose_scene_build
+            pose_scene_build(self.kin, sl.pose, out=(sl.render, sl.scene))
+            centre_crop_origins(self.mesh, sl.geom, sl.render, scratch=sl.bounds)
         if self.render:                    # rendered frames: the mesh and the slot's render tables -> its depth and label crops, on the device
             from .depth import render_depth
             render_depth(self.mesh, sl.geom, sl.render, self.depth_dtype, out=(sl.pix, sl.mask), scratch=sl.zbuf)
@@ -649,6 +668,8 @@ class AncshPipeline(object):
         o = self.opts
         if o.depth_dtype is None:
             raise RuntimeError("submit_depth() needs AncshPipeline(..., depth_capacity=<pixels>)")
+        if o.posed:
+            raise RuntimeError("a pipeline built with kinematics= builds its frames from poses on the device: submit_posed()")
         if o.render:
             raise RuntimeError("a pipeline built with render_mesh= renders its frames on the device: submit_render()")
         annotated = o.link_counts
@@ -696,6 +717,8 @@ class AncshPipeline(object):
         if not o.render:
             raise RuntimeError("submit_render() needs AncshPipeline(..., %s); depth frames made elsewhere travel through submit_depth()"
                                % SIDE["render"].built_with)
+        if o.posed:
+            raise RuntimeError("a pipeline built with kinematics= builds the render and scene tables itself: submit_posed()")
         refuse_built_frame(o, frame, "AncshPipeline")
 
         def front():
@@ -720,6 +743,43 @@ class AncshPipeline(object):
                 return []
             return n_valid, nf, stage, dict(scene=scenes)
         self._enqueue(front, seed, tag, cloud_base, render=render, gt=gt, frame=frame, rig=rig)
+
+    def submit_posed(self, crops, norm_factors, pose, rig, gt=None, frame=None, seed=None, tag=None, cloud_base=0):
+        """Enqueue one batch of frames the step poses, renders and annotates itself (asynchronous; a pipeline built with render_mesh= and
+        kinematics=): crops = 1..batch_size tuples (h, w, (row0, col0)) as submit_render takes them, or (h, w, None) for a crop centred on
+        the projected object (ancsh_render_centre_crops; the origin stays on the device -- depth.centre_crops returns it); norm_factors =
+        one finite float per frame; pose = one (32,) float64 row (depth.pack_pose: joint values and the view matrix) or one per frame; rig
+        (required), gt, frame, seed, tag, cloud_base: as submit_render takes them.  32 doubles per frame cross to the device in place of the
+        two tables' 448: ancsh_pose_scene_build writes the slot's render and scene tables in front of the renderer.  A short batch is padded
+        with its first crop and pose.  Bad input raises ValueError before anything is enqueued; a full in-flight window raises
+        RuntimeError.  Either way the pipeline stays usable."""
+        o = self.opts
+        if not o.posed:
+            raise RuntimeError("submit_posed() needs AncshPipeline(..., %s); this pipeline takes %s()"
+                               % (SIDE["pose"].built_with, "submit_render" if o.render else "submit_depth" if o.depth_dtype is not None else "submit"))
+        refuse_built_frame(o, frame, "AncshPipeline")
+
+        def front():
+            from .depth import check_posed_crops, pack_crop_geometry
+            if pose is None or rig is None:
+                raise ValueError(SIDE["pose"].missing)
+            shapes, origins = check_posed_crops(crops, self.B)
+            n_valid = len(shapes)
+            nf = np.asarray(norm_factors, np.float32).reshape(-1)
+            if nf.size != n_valid or not np.isfinite(nf).all():
+                raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n_valid, nf.tolist()))
+            pixels = sum(h * w for h, w in shapes)
+            padded = pixels + (self.B - n_valid) * shapes[0][0] * shapes[0][1]
+            if padded > o.depth_capacity:
+                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
+                                 % (padded, o.depth_capacity))
+
+            def stage(sl):
+                pack_crop_geometry(shapes, origins, sl.np_geom)
+                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and pose: the same origin, the same bytes)
+                return []
+            return n_valid, nf, stage
+        self._enqueue(front, seed, tag, cloud_base, pose=pose, gt=gt, frame=frame, rig=rig)
 
     def _enqueue(self, front, seed, tag, cloud_base, **side):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
@@ -862,5 +922,19 @@ class AncshPipeline(object):
             if len(item) < 3 or not isinstance(item[2], dict):
                 raise ValueError("a stream_render_batches item is (crops, norm_factors, {render=, scene=, rig=, ...}[, tag])")
             self.submit_render(item[0], item[1], tag=item[3] if len(item) > 3 else k, **item[2])
+        yield from pump(batches, self._inflight, len(self.slots), submit,
+                        lambda: self.retire(flags, articulation, link_counts=link_counts))
+
+    def stream_posed_batches(self, batches, flags=False, articulation=False, link_counts=False):
+        """stream_render_batches over submit_posed: batches yields (crops, norm_factors, {pose=, rig=, gt=, frame=, seed=, cloud_base=}) or
+        the same with a tag behind the dict (the tag defaults to the batch's index); yields what stream_render_batches yields for the same
+        frames."""
+        check_built_with(self.opts, "stream_posed_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts)
+
+        def submit(k, item):
+            item = tuple(item)
+            if len(item) < 3 or not isinstance(item[2], dict):
+                raise ValueError("a stream_posed_batches item is (crops, norm_factors, {pose=, rig=, ...}[, tag])")
+            self.submit_posed(item[0], item[1], tag=item[3] if len(item) > 3 else k, **item[2])
         yield from pump(batches, self._inflight, len(self.slots), submit,
                         lambda: self.retire(flags, articulation, link_counts=link_counts))

@@ -194,6 +194,24 @@ ALL_INPUTS = (RENDER_INPUT,) + SIDE_INPUTS
 SIDE[RENDER_INPUT.name] = RENDER_INPUT
 
 
+def unit_pose(K, unit):
+    """Every joint at 0 and the object 1.5 units in front of the camera: a half turn about x and a step back (the render map is -V o W)."""
+    p = np.zeros(depth_mod.POSE_WIDTH)
+    p[16:28] = [1.0, 0.0, 0.0, 0.0, 0.0, -1.0, 0.0, 0.0, 0.0, 0.0, -1.0, -1.5]
+    return p
+
+
+# And one beside that: the poses of a pipeline that also builds its tables itself (kinematics=).  `render` and `scene` are then no inputs --
+# their slot buffers stay and ancsh_pose_scene_build fills them --, and the pose is the batch's first H2D copy.
+POSED = RENDERED + ", kinematics=<depth.pack_kinematics(...)>"
+POSE_INPUT = SideInput("pose", "posed", POSED, lambda K: (depth_mod.POSE_WIDTH,), torch.float64, unit_pose,
+                       lambda v, n, K: depth_mod.check_poses(v, n), "first",
+                       "a pipeline built with kinematics= builds its tables from poses: submit_posed(crops, norm_factors, pose=..., rig=...) "
+                       "needs one depth.pack_pose row and one dataset.pack_joint_rig table per frame")
+EVERY_INPUT = (POSE_INPUT,) + ALL_INPUTS       # whatever a submit may carry by name (ALL_INPUTS and SIDE_INPUTS are pinned by the tests)
+SIDE[POSE_INPUT.name] = POSE_INPUT
+
+
 def side_host(inp, B, K, unit=None, pin=True):
     """The (B,) + shape(K) host staging of side input `inp`, holding its fill; pinned unless pin=False."""
     host = torch.zeros((B,) + inp.shape(K), dtype=inp.dtype)
@@ -204,7 +222,7 @@ def side_host(inp, B, K, unit=None, pin=True):
 
 def refuse_side_inputs(built, given, cls):
     """ValueError for the first side input of `given` = {name: value or None} that a `cls` with the side inputs `built` does not take."""
-    for inp in ALL_INPUTS:
+    for inp in EVERY_INPUT:
         if given.get(inp.name) is not None and inp not in built:
             raise ValueError("%s needs %s(..., %s)" % (inp.name, cls, inp.built_with))
 
@@ -226,7 +244,7 @@ def require_side_inputs(built, given):
 def check_side_inputs(built, given, n, K, cls):
     """Refuse and check, input by input in the table's order -> {name: the checked (n, ...) array, or None} for the side inputs `built`."""
     out = {}
-    for inp in ALL_INPUTS:
+    for inp in EVERY_INPUT:
         v = given.get(inp.name)
         if v is not None:
             refuse_side_inputs(built, {inp.name: v}, cls)
@@ -267,7 +285,7 @@ def check_joint_source(joint_source):
 
 
 Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
-                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts render "
+                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts render posed "
                                  "coord_regress_loss record_width record_key art_width rows inputs")
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
@@ -275,7 +293,7 @@ OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # th
 def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw_capacity=None, depth_capacity=None, depth_dtype="uint16",
                   keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
                   ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
-                  coord_regress_loss="L2", build_gt_pose=False, render_mesh=None):
+                  coord_regress_loss="L2", build_gt_pose=False, render_mesh=None, kinematics=None):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
     (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
     width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
@@ -283,7 +301,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     build_gt_pose (with point_ground_truth): the step fits both ground-truth pose tables itself, so `frame` is no side input and of `gt`
     only the box extents (columns 13..15) are read.
     render_mesh (annotated depth frames only): the step renders the frames itself from this mesh (depth.pack_mesh), so `render` is one
-    more side input and no pixel travels in."""
+    more side input and no pixel travels in.
+    kinematics (with render_mesh): the step builds the render and scene tables itself from this table (depth.pack_kinematics) and one pose
+    per frame, so `pose` (POSE_INPUT) takes the place of the `render` and `scene` inputs."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -327,6 +347,8 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                          "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
     if render_mesh is not None and not link_counts:
         raise ValueError("render_mesh renders the annotated depth frames of the step on the device: it needs " + RENDERED.rsplit(", ", 1)[0])
+    if kinematics is not None and render_mesh is None:
+        raise ValueError("kinematics poses the mesh the step renders: it needs " + RENDERED)
     if raw_capacity is not None:
         if not couple:
             raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
@@ -350,10 +372,12 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), link_counts, render_mesh is not None, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
+                bool(label_images), link_counts, render_mesh is not None, kinematics is not None, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
-    return o._replace(inputs=tuple(i for i in ALL_INPUTS if raw_capacity is not None and getattr(o, i.option)
-                                   and not (build_gt_pose and i.name == "frame")))
+    # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
+    return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +
+                      tuple(i for i in ALL_INPUTS if raw_capacity is not None and getattr(o, i.option)
+                            and not (build_gt_pose and i.name == "frame") and not (o.posed and i.name in ("render", "scene"))))
 
 
 # ---- what retire() returns ---------------------------------------------------------------------------------------------------

@@ -47,6 +47,8 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     against ground truth), ancsh_point_gt_rec (the streamed per-point ground truth: test losses and joint errors), ancsh_point_gt_build (that ground truth built from
                                  *     annotated clouds), ancsh_depth_annotate_stream (those clouds made from depth and link-label crops),
                                  *     ancsh_render_depth_labels (those crops rendered from articulated triangle meshes),
+                                 *     ancsh_pose_scene_build (that renderer's and the annotation's tables built from joint values and a view),
+                                 *     ancsh_render_centre_crops (crops centred on the projected object),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1217,6 +1219,69 @@ int ancsh_depth_annotate_stream(int nclouds, int depth_type, const void *depth, 
 int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
                               const int *geom, const double *render, void *depth, unsigned char *labels, unsigned long long *zbuf,
                               long pixel_capacity, void *stream);
+
+/* Both tables of a rendered, annotated frame built on the device: an object's kinematic table and one pose per frame (joint values and a
+ * view matrix) -> the render table ancsh_render_depth_labels reads and the scene table ancsh_depth_annotate_stream reads, in exactly their
+ * layouts.  The reference takes the link poses from pybullet's forward kinematics on the host (tools/render_synthetic.py:140-158, 206-217),
+ * and depth.pack_render_scene / depth.pack_frame_scene compose every link's maps with pinv / inv on 4 x 4 matrices, one frame at a time; for
+ * rigid matrices both reduce to the closed forms below, which need no inverse.  The reference rounds the link poses it stores to float32
+ * (tools/preprocess_data.py:235-236, an artefact of its YAML files): poses here are float64 throughout.  The ABI version is unchanged;
+ * callers detect the entry by its symbol.
+ *   kin  : one table per object, ANCSH_KIN_WIDTH = 672 float64 (ANCSH_KIN_HEAD = 32, then 16 links x ANCSH_KIN_LINK = 40), 8-byte aligned:
+ *     head [0..15] the scene table's head, verbatim (A coefficients, depth_scale, C coefficients, min_link_pixels, nlinks, 0)
+ *          [16..21] the render table's pixel map P00 P01 P02 P10 P11 P12   [22] z_min   [23..31] reserved, 0
+ *     link l at 32 + 40 l:  [0] rank  [1] part (as in the scene table)   [2] parent: -1 for link 0, the only root, otherwise < l
+ *          [3] joint kind: 0 fixed, 1 revolute, 2 prismatic   [4..15] T_l, row-major 3 x 4: the URDF joint origin Rz(yaw) Ry(pitch) Rx(roll)
+ *          | xyz, from the parent link's frame to link l's frame at q = 0 (link 0: its world pose; the reference's is the identity)
+ *          [16..18] the unit joint axis a in link l's frame   [19..27] Rc_l, row-major 3 x 3, and [28..30] offset_l: the rotation and the
+ *          offset of the link's canon2urdf map (depth.pack_frame_scene's)   [31..39] reserved, 0
+ *   pose : (nframes, ANCSH_POSE_WIDTH = 32) float64, 8-byte aligned, per frame:
+ *     [0..15] q_l, link l's joint value in radians (revolute) or length units (prismatic); ignored for link 0 and for fixed joints
+ *     [16..27] V, the first three rows of the view matrix (world -> eye, the `.reshape(4, 4).T` form of tools/preprocess_data.py:228),
+ *     row-major 3 x 4; it must be rigid (the host checks it)   [28..31] reserved, 0
+ *   render (nframes, ANCSH_RENDER_WIDTH) and scene (nframes, ANCSH_SCENE_WIDTH) float64, 8-byte aligned: the outputs; every value of every
+ *     frame's tables is written.
+ * Everything below is float64, evaluated in exactly the written order (no contraction); (s, c) = sincos(q) are the only values that are not
+ * a fixed sequence of IEEE operations, and sincos(0) = (0, 1) exactly.  A 3 x 4 map [R | t] stands for the rigid 4 x 4 matrix.
+ *   Composition C = A o B:  C[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j], for j = 3 then + A[i][3].
+ *   Joint motion J_l(q) = [Rj | tj]; fixed joints and link 0: [I | 0]; prismatic: [I | (q a_0, q a_1, q a_2)]; revolute: tj = 0 and
+ *     Rj[i][j] = (c d_ij + s K[i][j]) + ((1 - c) a_i) a_j with d the identity and K = [a]x = {0 -a2 a1; a2 0 -a0; -a1 a0 0}.
+ *   X_l = T_l o J_l (always composed, the identity included).
+ *   World pose, from the leaf upwards: W = X_l, then for p = parent(l), parent(p), ..., 0: W <- X_p o W.
+ *   A_l = V o W = [Ra | ta].  The render map of link l is R_l = -A_l, entry by entry.
+ *   The scene map of link l:  M[i][j] = -((Rc[i][0] Ra[j][0] + Rc[i][1] Ra[j][1]) + Rc[i][2] Ra[j][2]) for j = 0..2, and
+ *     M[i][3] = ((M[i][0] ta_0 + M[i][1] ta_1) + M[i][2] ta_2) + offset_i;  rank and part are copied from kin.
+ *   Heads, copied bit for bit: scene[0..15] = kin[0..15]; render[0..5] = kin[16..21], render[6] = kin[6], render[7] = kin[22],
+ *     render[8] = kin[14], render[9..15] = 0.  Links >= nlinks (nlinks outside 1..16: every link) read 0 in both tables.
+ * M_l (R_l (v, 1), 1) = Rc_l v + offset_l: the two maps are each other's inverse up to the link's canon2urdf map, which is what
+ * depth.pack_render_scene and depth.pack_frame_scene give for the same link poses.
+ * One launch, one thread per (frame, link), the grid a function of nframes alone; no host sync, no allocation: graph-capturable.  A few
+ * thousand double multiply-adds per frame: the launch sits on the floor of a dependent graph node.  nframes == 0 launches nothing and
+ * returns 0.  Checked before any launch: 0 <= nframes <= 65535, null pointers, the 8-byte alignments. */
+#define ANCSH_KIN_WIDTH 672
+#define ANCSH_KIN_HEAD 32
+#define ANCSH_KIN_LINK 40
+#define ANCSH_POSE_WIDTH 32
+int ancsh_pose_scene_build(int nframes, const double *kin, const double *pose, double *render, double *scene, void *stream);
+
+/* Crops centred on the projected object: for every frame whose geometry row holds ANCSH_CROP_CENTRE (INT32_MIN; a real origin lies below
+ * 2^24 in magnitude) in BOTH row0 and col0, the origin that centres the h x w crop on the bounding box of the object's projected vertices is
+ * written into the row; every other frame is left alone, so a second call -- a replay that finds real origins -- is a no-op.
+ *   verts, tris, tri_link, V, T, render : as ancsh_render_depth_labels takes them;  geom (nframes, 5) int32 {start h w row0 col0}: read and,
+ *     for centred frames, row0 and col0 written (start, h, w are untouched);  bounds (nframes, 4) int32 of working memory, initialised here.
+ * A vertex COUNTS when a triangle whose link is in [0, nlinks) references it, its index is in [0, V), and ancsh_render_depth_labels' vertex
+ * transform (the same device function: z, X = rint(256 col), Y = rint(256 row)) keeps it: every value finite, z >= z_min, |X|, |Y| < 2^25.
+ * Vertices count one by one, not per dropped triangle.  With Xmin, Xmax, Ymin, Ymax over the counted vertices (int32):
+ *   col0 = ((Xmin + Xmax) >> 9) - (w >> 1),  row0 = ((Ymin + Ymax) >> 9) - (h >> 1)   (arithmetic shifts: floor);
+ * a frame without a counted vertex (T == 0, nlinks outside 1..16, everything behind z_min) gets (0, 0).
+ * One launch, one block per frame (the grid depends on nframes alone): a wave reduces its vertices' bounds with shuffles and takes one int32
+ * atomicMin / atomicMax per bound on the frame's row of `bounds`; minimum and maximum do not depend on the order of their operands, so the
+ * origins are a pure function of the input.  The padding frames of a short batch carry the first frame's table and crop, so they write the
+ * same origin.  Graph-capturable: no host sync, no allocation.  nframes == 0 launches nothing and returns 0.  Checked before any launch:
+ * 0 <= nframes <= 65535, 0 <= T < 2^24, 0 <= V < 2^24, null pointers, the alignments (render 8 bytes; geom, bounds 4 bytes). */
+#define ANCSH_CROP_CENTRE (-2147483647 - 1)
+int ancsh_render_centre_crops(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T, const double *render,
+                              int *geom, int *bounds, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

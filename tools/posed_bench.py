@@ -1,0 +1,177 @@
+"""What building the per-frame tables costs, on the host and on the device: AncshPipeline(..., render_mesh=mesh, kinematics=kin), whose step
+builds its render and scene tables from one pose per frame (ancsh_pose_scene_build) and centres its crops (ancsh_render_centre_crops),
+against the rendered stream fed tables from depth.pack_render_scene / depth.pack_frame_scene, at tools/render_bench.py's object, frames and
+shape (K = 3, 32 x 1024, 10000 / 200 hypotheses, couple=True, synthetic weights, predicted joints).  Measured:
+  a: microseconds per frame of the two host packers, one core of this machine (--pack-calls calls each);
+  e: the two new entries alone, back to back, on one batch of 32 frames (HIP events around --calls pairs);
+  three legs, alternated in one process for --rounds rounds:
+    b: the rendered stream, its tables packed BEFORE the clock starts (tools/render_bench.py's leg r);
+    c: the same stream, its tables packed inside the loop, one frame at a time: what a user of render_mesh= pays without the new entries;
+    d: the posed stream on the same views and joint values (the poses are 32 doubles each, made before the clock; submit_posed's checks
+       run inside it).
+Prints one JSON line: a record, not a gate.
+
+    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import articulated_pose_amd  # noqa: E402,F401
+from articulated_pose_amd import depth as D  # noqa: E402
+from articulated_pose_amd.dataset import identity_rig  # noqa: E402
+from articulated_pose_amd.pipeline import AncshPipeline  # noqa: E402
+from articulated_pose_amd.weights import synthetic_weights  # noqa: E402
+from render_bench import HI, LO, SCALE, tessellated_box  # noqa: E402
+
+ZERO = np.zeros((3, 3))
+PARTS = [[0], [1], [2]]
+
+
+def projection():
+    t, near, far = np.tan(np.radians(20.0)), 0.1, 100.0
+    return np.array([[1.0 / t, 0, 0, 0], [0, 1.0 / t, 0, 0], [0, 0, (far + near) / (near - far), 2 * far * near / (near - far)], [0, 0, -1.0, 0]])
+
+
+def make_frame(rs):
+    """One frame of render_bench's three-link object: (the view matrix, the opening of link 1's hinge)."""
+    V = np.eye(4)
+    V[:3, :3] = D._rotation_from_rpy(*rs.uniform(-0.5, 0.5, 3))[:3, :3]
+    V[:3, 3] = (rs.uniform(-0.03, 0.03), rs.uniform(-0.03, 0.03), -rs.uniform(1.45, 1.6))
+    return V, rs.uniform(0.1, 1.2)
+
+
+def host_tables(P, V, opening, side):
+    """The two host packers on the link poses the reference takes from its simulator."""
+    pos = np.array([[0.0, 0.0, 0.0], [0.3, 0.02, 0.12], [-0.34, -0.03, 0.02]])
+    orn = np.array([[0, 0, 0, 1.0], [0, np.sin(opening / 2), 0, np.cos(opening / 2)], [0, 0, np.sin(0.2), np.cos(0.2)]])
+    return (D.pack_render_scene(V, P, pos, orn, side, side, depth_scale=SCALE),
+            D.pack_frame_scene(V, P, pos, orn, ZERO, ZERO, ZERO[:2], PARTS, side, side, depth_scale=SCALE))
+
+
+def kinematics(P, side):
+    """The same object as a tree: link 1 hinged about y beside link 0, link 2 fixed on the other side, turned 0.4 about z."""
+    return D.pack_kinematics(P, side, side, [-1, 0, 0], ["fixed", "revolute", "fixed"], [(0, 0, 0), (0.3, 0.02, 0.12), (-0.34, -0.03, 0.02)],
+                             [(0, 0, 0), (0, 0, 0), (0, 0, 0.4)], [(0, 0, 0), (0, 1, 0), (0, 0, 0)], ZERO, ZERO, ZERO[:2], PARTS, depth_scale=SCALE)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
+    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--frames", type=int, default=320)
+    ap.add_argument("--side", type=int, default=128, help="the image and the crop: side x side pixels")
+    ap.add_argument("--tess", type=int, default=8, help="quads per box edge: 12 tess^2 triangles per link")
+    ap.add_argument("--calls", type=int, default=200, help="back-to-back pairs of the two entries between their two events")
+    ap.add_argument("--pack-calls", type=int, default=300, help="calls of each host packer for leg a")
+    args = ap.parse_args()
+    K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
+    rs = np.random.RandomState(0)
+    P, side = projection(), args.side
+    mesh = D.pack_mesh([tessellated_box(LO, HI, args.tess)] * K)
+    kin = kinematics(P, side)
+    crops = [(side, side, (0, 0))] * B
+    nf, rigs, jf = np.ones(B, np.float32), np.tile(identity_rig(K), (B, 1)), rs.normal(size=(B, 13))
+    views, tbatches, pbatches = [], [], []
+    for _ in range(args.frames // B):
+        frames = [make_frame(rs) for _ in range(B)]
+        tables = [host_tables(P, V, o, side) for V, o in frames]
+        views.append(frames)
+        tbatches.append((crops, nf, dict(render=np.stack([t[0] for t in tables]), scene=np.stack([t[1] for t in tables]), rig=rigs, frame=jf)))
+        pbatches.append((crops, nf, dict(pose=np.stack([D.pack_pose([0.0, o, 0.0], V) for V, o in frames]), rig=rigs, frame=jf)))
+    # the device's tables against the host packers', on the last batch
+    rt, sc = D.pose_scene_tables(kin, pbatches[-1][2]["pose"], dev)
+    parity = max(float(np.abs(rt - tbatches[-1][2]["render"]).max()), float(np.abs(sc - tbatches[-1][2]["scene"]).max()))
+    # a: the host packers
+    V, o = views[0][0]
+    pos = np.array([[0.0, 0.0, 0.0], [0.3, 0.02, 0.12], [-0.34, -0.03, 0.02]])
+    orn = np.array([[0, 0, 0, 1.0], [0, np.sin(o / 2), 0, np.cos(o / 2)], [0, 0, np.sin(0.2), np.cos(0.2)]])
+    t0 = time.perf_counter()
+    for _ in range(args.pack_calls):
+        D.pack_render_scene(V, P, pos, orn, side, side, depth_scale=SCALE)
+    t1 = time.perf_counter()
+    for _ in range(args.pack_calls):
+        D.pack_frame_scene(V, P, pos, orn, ZERO, ZERO, ZERO[:2], PARTS, side, side, depth_scale=SCALE)
+    t2 = time.perf_counter()
+    pack_us = {"pack_render_scene": 1e6 * (t1 - t0) / args.pack_calls, "pack_frame_scene": 1e6 * (t2 - t1) / args.pack_calls}
+    # e: the two entries alone
+    d_mesh, d_kin, d_pose = D.mesh_to_device(mesh, dev), torch.from_numpy(kin).to(dev), torch.from_numpy(pbatches[-1][2]["pose"]).to(dev)
+    geom = np.zeros((B, D.GEOM_WORDS), np.int32)
+    cap = D.pack_crop_geometry([c[:2] for c in crops], np.full((B, 2), D.CROP_CENTRE, np.int64), geom)
+    h_geom = torch.from_numpy(geom).pin_memory()
+    d_geom = h_geom.to(dev)
+    out = (torch.zeros((B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((B, D.SCENE_WIDTH), dtype=torch.float64, device=dev))
+    bounds = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+
+    def pair():                                               # every crop asks for its centre again: the second entry does its whole work
+        d_geom.copy_(h_geom, non_blocking=True)
+        D.pose_scene_build(d_kin, d_pose, out=out)
+        D.centre_crop_origins(d_mesh, d_geom, out[0], scratch=bounds)
+    for _ in range(20):
+        pair()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    op_ms = []
+    for _ in range(args.rounds):
+        e0.record()
+        for _ in range(args.calls):
+            pair()
+        e1.record()
+        torch.cuda.synchronize()
+        op_ms.append(e0.elapsed_time(e1) / args.calls)
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
+              depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
+    rendered = AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
+    posed = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, **kw).prepare()
+    torch.cuda.synchronize()
+
+    def packed_in_the_loop(passes):
+        for _ in range(passes):
+            for frames in views:
+                tables = [host_tables(P, V, o, side) for V, o in frames]
+                yield crops, nf, dict(render=np.stack([t[0] for t in tables]), scene=np.stack([t[1] for t in tables]), rig=rigs, frame=jf)
+
+    def leg(name, passes):
+        t0, n = time.perf_counter(), 0
+        gen = (rendered.stream_render_batches(tbatches[k] for _ in range(passes) for k in range(len(tbatches))) if name == "b" else
+               rendered.stream_render_batches(packed_in_the_loop(passes)) if name == "c" else
+               posed.stream_posed_batches(pbatches[k] for _ in range(passes) for k in range(len(pbatches))))
+        for _ in gen:
+            n += 1
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / n          # ms per batch of B frames, steady state over the slots
+
+    for name in "bcd":                                        # warm-up: every slot replayed with real input
+        leg(name, 1)
+    ms = {name: [] for name in "bcd"}
+    for _ in range(args.rounds):
+        for name in "bcd":
+            ms[name].append(leg(name, args.passes))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    op = float(np.median(op_ms))
+    print(json.dumps({"metric": "frames/s: the rendered stream with tables packed before the clock (b) and inside the loop (c) vs the posed stream (d); "
+                                "the host packers (a) and the two new entries alone (e)",
+                      "device": torch.cuda.get_device_name(0), "host_pack_us_per_frame": {k: round(v, 1) for k, v in pack_us.items()},
+                      "host_pack_frames_per_s_one_core": round(1e6 / sum(pack_us.values()), 1),
+                      "entries_us_per_batch": round(1e3 * op, 2), "entries_us_per_batch_rounds": [round(1e3 * x, 2) for x in op_ms],
+                      "entries_frames_per_s": round(1e3 * B / op, 1),
+                      "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
+                      "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                      "d_over_b": round(med["d"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
+                      "h2d_bytes_per_batch_b": B * (4 * D.GEOM_WORDS + 8 * D.RENDER_WIDTH + 8 * D.SCENE_WIDTH),
+                      "h2d_bytes_per_batch_d": B * (4 * D.GEOM_WORDS + 8 * D.POSE_WIDTH),
+                      "max_abs_device_minus_host_tables": parity, "triangles": int(mesh[1].shape[0]), "vertices": int(mesh[0].shape[0]),
+                      "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(tbatches) * B,
+                                "side": side, "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
+
+
+if __name__ == "__main__":
+    main()
