@@ -43,12 +43,15 @@ PM_INL double fast_rsqrt(double x) {
     return r;
 }
 
-// sin/cos for the rotation angles of the fit (|x| stays O(pi); valid to ~1 ulp for |x| < 1e4): two-term
+// sin/cos for the rotation angles of the fit (|x| stays O(pi); valid to ~1 ulp for |x| < 1e4): three-term
 // Cody-Waite reduction by pi/2 + the fdlibm kernel polynomials.  A fraction of the size of the generic
 // library sincos (no Payne-Hanek path), which matters because the LM loop must stay I-cache resident.
+// The first two parts of pi/2 carry 33 bits each and |k| < 2^13, so their products with k are exact and the two
+// subtractions cancel exactly next to a multiple of pi/2; the third part leaves k * 2e-37.  (With two parts, 33 + 53
+// bits, the remainder was off by k * 3.5e-27: a relative error of 6e-11 in cos(fl(pi/2)) and sin(fl(pi)).)
 PM_INL void sincos_compact(double x, double &sn, double &cs) {
     const double k = rint(x * 6.36619772367581382433e-01);
-    const double r = (x - k * 1.57079632673412561417e+00) - k * 6.07710050650619224932e-11;
+    const double r = ((x - k * 1.57079632673412561417e+00) - k * 6.07710050630396597660e-11) - k * 2.02226624879595063154e-21;
     const double z = r * r;
     const double s = r + r * z * (-1.66666666666666324348e-01 + z * (8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 +
                      z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10)))));
@@ -152,6 +155,9 @@ PM_INL void horn_quat(const double M[9], double q[4]) {
 // ~350 flops against ~4000.  Rank-deficient M (a sample with a repeated or collinear point: the optimal rotation is then
 // a one-parameter family and the reference's SVD returns an arbitrary member of it) has a double top root and a vanishing
 // adjugate; those take the shortest-arc rotation between the dominant directions instead, also a member of the family.
+// The directions are read off M = sigma a b^T as the column and the row through its largest entry, i.e. as sigma b[bj] a and
+// sigma a[bi] b: their relative sign is the sign of that entry, so the row is negated when the entry is negative.  Without that the
+// arc takes b to -a, which is the rotation that MINIMISES tr(R^T M) and mirrors the part about the sample's centroid.
 PM_INL double det3(double a, double b, double c, double d, double e, double f, double g, double h, double i) {
     return a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
 }
@@ -201,14 +207,16 @@ PM_INL void horn_quat_fast(const double M[9], double q[4]) {
     if (a3 > best) { best = a3; qw = C03; qx = C13; qy = C23; qz = C33; }
     const double scale3 = fro * sqrt(fro);
     if (!(best > 1e-9 * scale3)) {
-        // rank <= 1: M ~ a b^T (a: target direction, b: source direction); shortest arc taking b to a
+        // rank <= 1: M ~ a b^T (a: target direction, b: source direction); shortest arc taking b to a, with b given the sign of
+        // M[bi][bj] so that a b^T has the sign of M (column and row through the largest entry are sigma b[bj] a and sigma a[bi] b)
         double mx = 0.0;
         int bi = 0, bj = 0;
+        bool neg = false;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 3; ++j)
-                if (fabs(M[i * 3 + j]) > mx) { mx = fabs(M[i * 3 + j]); bi = i; bj = j; }
+                if (fabs(M[i * 3 + j]) > mx) { mx = fabs(M[i * 3 + j]); bi = i; bj = j; neg = M[i * 3 + j] < 0.0; }
         if (!(mx > 0.0)) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; return; }
         double a[3], b[3];
 #pragma unroll
@@ -216,7 +224,9 @@ PM_INL void horn_quat_fast(const double M[9], double q[4]) {
             a[t] = bj == 0 ? M[t * 3] : (bj == 1 ? M[t * 3 + 1] : M[t * 3 + 2]);
             b[t] = bi == 0 ? M[t] : (bi == 1 ? M[3 + t] : M[6 + t]);
         }
-        const double na = fast_rsqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), nb = fast_rsqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+        const double na = fast_rsqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        double nb = fast_rsqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+        nb = neg ? -nb : nb;
 #pragma unroll
         for (int t = 0; t < 3; ++t) { a[t] *= na; b[t] *= nb; }
         const double d = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
