@@ -155,6 +155,13 @@ SIGNATURES = {
     # crops centred on the projected object (no ABI bump, detected by its symbol): nframes, verts, tris, tri_link, V, T, render, geom, bounds,
     # stream
     "ancsh_render_centre_crops": [_c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp],
+    # those three for a library of instances, the instance of a frame in render[9] / pose[28] (no ABI bump, detected by their symbols):
+    # nframes, depth_type, verts, tris, tri_link, V, T, tri_off, ninst, Tmax, geom, render, depth, labels, zbuf, pixel_capacity, stream
+    "ancsh_render_depth_labels_lib": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long, _vp],
+    # nframes, verts, tris, tri_link, V, T, tri_off, ninst, render, geom, bounds, stream
+    "ancsh_render_centre_crops_lib": [_c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp],
+    # nframes, kin, ninst, pose, render, scene, stream
+    "ancsh_pose_scene_build_lib": [_c_int, _vp, _c_int, _vp, _vp, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -46,6 +46,12 @@ inline int check_launch(const char *what) {
     return ANCSH_OK;
 }
 
+// the instance a frame of a library names in a reserved value of its table (render[9], pose[28]): v when it is an integer in [0, ninst),
+// otherwise -1 -- NaN fails every comparison
+__device__ __forceinline__ int instance_index(double v, int ninst) {
+    return v >= 0.0 && v < (double)ninst && v == floor(v) ? (int)v : -1;
+}
+
 #define ANCSH_REQUIRE(cond, ...)          \
     do {                                  \
         if (!(cond)) {                    \

@@ -13,6 +13,9 @@
 //   resolve : block (x, f) turns the keys of its chunk into depth values and label bytes, background where the key is empty.
 // The minimum of a set does not depend on the order of its elements: the output is a pure function of the input, byte for byte.
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
+// A LIBRARY of instances (ancsh_render_depth_labels_lib, ancsh_render_centre_crops_lib): the meshes concatenated, tri_off naming each
+// instance's triangle range, and the instance of a frame in its table's value 9.  The raster and the centring kernels of either kind are
+// wrappers around one device function each (render_raster_wave, render_centre_block); clear and resolve serve both unchanged.
 #include "depth_common.h"
 
 namespace ancsh {
@@ -25,6 +28,19 @@ constexpr long RN_FIXED_LIMIT = 1L << 25;                               // |X|, 
 __device__ __forceinline__ int render_nlinks(const double *__restrict__ rt) {
     const double v = rt[8], z_min = rt[7];
     return v >= 1.0 && v <= (double)RN_LINKS && z_min > 0.0 ? (int)v : 0;      // NaN fails every comparison
+}
+
+// the triangle range [t_lo, t_hi) of a library frame's instance, render[9]: empty for a value that is no integer in [0, ninst) and for offsets
+// that are no range inside [0, T].  One table value and two offsets per wave (raster) or block (centring); nothing is read per pixel
+__device__ __forceinline__ void render_instance_range(const double *__restrict__ rt, const int *__restrict__ tri_off, int ninst, int T,
+                                                      int &t_lo, int &t_hi) {
+    const int i = instance_index(rt[9], ninst);
+    t_lo = t_hi = 0;
+    if (i < 0) return;
+    const int a = tri_off[i], b = tri_off[i + 1];
+    if (a < 0 || b < a || b > T) return;
+    t_lo = a;
+    t_hi = b;
 }
 
 __global__ __launch_bounds__(DEPTH_THREADS) void render_clear_kernel(long pixel_capacity, const int *__restrict__ geom, int chunks,
@@ -69,15 +85,12 @@ __device__ __forceinline__ long lmax(long a, long b) { return a > b ? a : b; }
 __device__ __forceinline__ long floor_div256(long v) { return v >> 8; }                  // arithmetic shift: floor for either sign
 __device__ __forceinline__ long ceil_div256(long v) { return -((-v) >> 8); }
 
-__global__ __launch_bounds__(DEPTH_THREADS) void render_raster_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
-                                                                      const int *__restrict__ tri_link, int V, int T,
-                                                                      long pixel_capacity, const int *__restrict__ geom,
-                                                                      const double *__restrict__ render,
-                                                                      unsigned long long *__restrict__ zbuf) {
-    const int f = blockIdx.y, lane = threadIdx.x & 63;
-    const int t = (int)(blockIdx.x * DEPTH_WAVES + (threadIdx.x >> 6));                  // uniform over the wave
-    if (t >= T) return;
-    const double *rt = render + (size_t)f * RN_WIDTH;
+// one wave rasterises triangle t (uniform over the wave, in [0, T)) into frame f's crop: both raster kernels' body
+__device__ __forceinline__ void render_raster_wave(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                   const int *__restrict__ tri_link, int V, int t, int f, long pixel_capacity,
+                                                   const int *__restrict__ geom, const double *__restrict__ rt,
+                                                   unsigned long long *__restrict__ zbuf) {
+    const int lane = threadIdx.x & 63;
     const int nl = render_nlinks(rt);
     long start;
     int w;
@@ -114,6 +127,33 @@ __global__ __launch_bounds__(DEPTH_THREADS) void render_raster_kernel(const floa
         // (r - row0, cc - col0) is a pixel of the crop, and the crop lies inside [0, pixel_capacity)
         atomicMin(zbuf + (start + (r - row0) * w + (cc - col0)), key);
     }
+}
+
+__global__ __launch_bounds__(DEPTH_THREADS) void render_raster_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                      const int *__restrict__ tri_link, int V, int T,
+                                                                      long pixel_capacity, const int *__restrict__ geom,
+                                                                      const double *__restrict__ render,
+                                                                      unsigned long long *__restrict__ zbuf) {
+    const int f = blockIdx.y;
+    const int t = (int)(blockIdx.x * DEPTH_WAVES + (threadIdx.x >> 6));                  // uniform over the wave
+    if (t >= T) return;
+    render_raster_wave(verts, tris, tri_link, V, t, f, pixel_capacity, geom, render + (size_t)f * RN_WIDTH, zbuf);
+}
+
+// the library's: the wave for LOCAL triangle j of frame f handles global triangle tri_off[i] + j of the frame's instance i.  f is
+// blockIdx.y, so the instance, its range and the early exit are uniform over the wave (and the block)
+__global__ __launch_bounds__(DEPTH_THREADS) void render_raster_lib_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                          const int *__restrict__ tri_link, int V, int T,
+                                                                          const int *__restrict__ tri_off, int ninst, long pixel_capacity,
+                                                                          const int *__restrict__ geom, const double *__restrict__ render,
+                                                                          unsigned long long *__restrict__ zbuf) {
+    const int f = blockIdx.y;
+    const int j = (int)(blockIdx.x * DEPTH_WAVES + (threadIdx.x >> 6));                  // uniform over the wave
+    const double *rt = render + (size_t)f * RN_WIDTH;
+    int t_lo, t_hi;
+    render_instance_range(rt, tri_off, ninst, T, t_lo, t_hi);
+    if (j >= t_hi - t_lo) return;                                       // 0 <= t_lo <= t_hi <= T: t_lo + j stays inside [0, T)
+    render_raster_wave(verts, tris, tri_link, V, t_lo + j, f, pixel_capacity, geom, rt, zbuf);
 }
 
 __device__ __forceinline__ unsigned short render_quantise(double v, unsigned short) {    // uint16: rint, kept in 1..65535
@@ -153,14 +193,19 @@ __global__ __launch_bounds__(DEPTH_THREADS) void render_resolve_kernel(long pixe
     }
 }
 
+// tri_off == nullptr: one object, every frame draws all ntri triangles; otherwise a library of ninst instances whose largest holds tmax
 template <typename T>
-static void render_launch(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int ntri, const int *geom,
-                          const double *render, void *depth, unsigned char *labels, unsigned long long *zbuf, long pixel_capacity,
-                          hipStream_t st) {
+static void render_launch(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int ntri, const int *tri_off,
+                          int ninst, int tmax, const int *geom, const double *render, void *depth, unsigned char *labels,
+                          unsigned long long *zbuf, long pixel_capacity, hipStream_t st) {
     const long chunks = depth_chunks(pixel_capacity, nframes);          // depth.hip's grid
     const dim3 grid((unsigned)chunks, nframes);
     hipLaunchKernelGGL(render_clear_kernel, grid, dim3(DEPTH_THREADS), 0, st, pixel_capacity, geom, (int)chunks, zbuf);
-    if (ntri > 0)
+    if (tri_off) {
+        if (tmax > 0)
+            hipLaunchKernelGGL(render_raster_lib_kernel, dim3((unsigned)((tmax + DEPTH_WAVES - 1) / DEPTH_WAVES), nframes), dim3(DEPTH_THREADS),
+                               0, st, verts, tris, tri_link, V, ntri, tri_off, ninst, pixel_capacity, geom, render, zbuf);
+    } else if (ntri > 0)
         hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((ntri + DEPTH_WAVES - 1) / DEPTH_WAVES), nframes), dim3(DEPTH_THREADS), 0, st,
                            verts, tris, tri_link, V, ntri, pixel_capacity, geom, render, zbuf);
     hipLaunchKernelGGL(render_resolve_kernel<T>, grid, dim3(DEPTH_THREADS), 0, st, pixel_capacity, geom, render, (int)chunks, tri_link, ntri,
@@ -175,10 +220,12 @@ static void render_launch(int nframes, const float *verts, const int *tris, cons
 constexpr int RN_CENTRE = ANCSH_CROP_CENTRE;
 constexpr int RN_INT_MAX = 2147483647, RN_INT_MIN = -2147483647 - 1;
 
-__global__ __launch_bounds__(DEPTH_THREADS) void render_centre_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
-                                                                      const int *__restrict__ tri_link, int V, int T,
-                                                                      const double *__restrict__ render, int *__restrict__ geom,
-                                                                      int *__restrict__ bounds) {
+// the block centres frame f's crop on the vertices of the triangles [t_lo, t_hi) (uniform over the block): both centring kernels' body.
+// library == false: one object, the range is [0, T); true: the range of the frame's instance, read once the frame is known to be centred
+template <bool library>
+__device__ __forceinline__ void render_centre_block(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                    const int *__restrict__ tri_link, int V, int T, const int *__restrict__ tri_off, int ninst,
+                                                    const double *__restrict__ render, int *__restrict__ geom, int *__restrict__ bounds) {
     const int f = blockIdx.x;
     int *g = geom + (size_t)f * DEPTH_GEOM, *b = bounds + (size_t)f * 4;
     if (threadIdx.x < 4) atomicExch(b + threadIdx.x, (threadIdx.x & 1) ? RN_INT_MIN : RN_INT_MAX);      // {Xmin Xmax Ymin Ymax}: the empty bounds
@@ -187,8 +234,10 @@ __global__ __launch_bounds__(DEPTH_THREADS) void render_centre_kernel(const floa
     __syncthreads();
     const double *rt = render + (size_t)f * RN_WIDTH;
     const int nl = render_nlinks(rt);
+    int t_lo = 0, t_hi = T;
+    if (library) render_instance_range(rt, tri_off, ninst, T, t_lo, t_hi);
     int xmin = RN_INT_MAX, xmax = RN_INT_MIN, ymin = RN_INT_MAX, ymax = RN_INT_MIN;
-    for (int t = threadIdx.x; t < T && nl > 0; t += DEPTH_THREADS) {
+    for (int t = t_lo + (int)threadIdx.x; t < t_hi && nl > 0; t += DEPTH_THREADS) {     // t_hi <= T < 2^24: the sum cannot wrap
         const int l = tri_link[t];
         if (l < 0 || l >= nl) continue;
         const double *R = rt + RN_HEAD + RN_LINK * l;
@@ -233,45 +282,113 @@ __global__ __launch_bounds__(DEPTH_THREADS) void render_centre_kernel(const floa
     }
 }
 
+__global__ __launch_bounds__(DEPTH_THREADS) void render_centre_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                      const int *__restrict__ tri_link, int V, int T,
+                                                                      const double *__restrict__ render, int *__restrict__ geom,
+                                                                      int *__restrict__ bounds) {
+    render_centre_block<false>(verts, tris, tri_link, V, T, nullptr, 0, render, geom, bounds);
+}
+
+__global__ __launch_bounds__(DEPTH_THREADS) void render_centre_lib_kernel(const float *__restrict__ verts, const int *__restrict__ tris,
+                                                                          const int *__restrict__ tri_link, int V, int T,
+                                                                          const int *__restrict__ tri_off, int ninst,
+                                                                          const double *__restrict__ render, int *__restrict__ geom,
+                                                                          int *__restrict__ bounds) {
+    render_centre_block<true>(verts, tris, tri_link, V, T, tri_off, ninst, render, geom, bounds);
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
 
+// what both centring entries check, under the entry's name
+static int render_centre_check(const char *name, int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                               const double *render, const int *geom, const int *bounds) {
+    ANCSH_REQUIRE(nframes >= 0, "%s: bad shape nframes=%d", name, nframes);
+    ANCSH_REQUIRE(nframes <= 65535, "%s: %d frames exceed the 65535-frame grid range; split the batch", name, nframes);
+    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "%s: T=%d triangles must be in [0, 2^24)", name, T);
+    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "%s: V=%d vertices must be in [0, 2^24)", name, V);
+    ANCSH_REQUIRE(verts && tris && tri_link && render && geom && bounds, "%s: null pointer", name);
+    ANCSH_REQUIRE(((size_t)render & 7) == 0 && ((size_t)geom & 3) == 0 && ((size_t)bounds & 3) == 0,
+                  "%s: render must be 8-byte aligned, geom and bounds 4-byte aligned", name);
+    return ANCSH_OK;
+}
+
+// what both library entries check of the library itself
+static int render_library_check(const char *name, const int *tri_off, int ninst) {
+    ANCSH_REQUIRE(ninst >= 1 && ninst <= ANCSH_LIBRARY_MAX_INSTANCES, "%s: ninst=%d instances must be in [1, %d]", name, ninst,
+                  ANCSH_LIBRARY_MAX_INSTANCES);
+    ANCSH_REQUIRE(tri_off && ((size_t)tri_off & 3) == 0, "%s: tri_off must be a 4-byte aligned device pointer", name);
+    return ANCSH_OK;
+}
+
 extern "C" int ancsh_render_centre_crops(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T,
                                          const double *render, int *geom, int *bounds, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "render_centre_crops: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 65535, "render_centre_crops: %d frames exceed the 65535-frame grid range; split the batch", nframes);
-    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "render_centre_crops: T=%d triangles must be in [0, 2^24)", T);
-    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "render_centre_crops: V=%d vertices must be in [0, 2^24)", V);
-    ANCSH_REQUIRE(verts && tris && tri_link && render && geom && bounds, "render_centre_crops: null pointer");
-    ANCSH_REQUIRE(((size_t)render & 7) == 0 && ((size_t)geom & 3) == 0 && ((size_t)bounds & 3) == 0,
-                  "render_centre_crops: render must be 8-byte aligned, geom and bounds 4-byte aligned");
+    if (const int rc = render_centre_check("render_centre_crops", nframes, verts, tris, tri_link, V, T, render, geom, bounds)) return rc;
     if (nframes == 0) return ANCSH_OK;
     hipLaunchKernelGGL(render_centre_kernel, dim3(nframes), dim3(DEPTH_THREADS), 0, (hipStream_t)stream, verts, tris, tri_link, V, T, render,
                        geom, bounds);
     return check_launch("render_centre_crops");
 }
 
+extern "C" int ancsh_render_centre_crops_lib(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                             const int *tri_off, int ninst, const double *render, int *geom, int *bounds, void *stream) {
+    if (const int rc = render_centre_check("render_centre_crops_lib", nframes, verts, tris, tri_link, V, T, render, geom, bounds)) return rc;
+    if (const int rc = render_library_check("render_centre_crops_lib", tri_off, ninst)) return rc;
+    if (nframes == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(render_centre_lib_kernel, dim3(nframes), dim3(DEPTH_THREADS), 0, (hipStream_t)stream, verts, tris, tri_link, V, T,
+                       tri_off, ninst, render, geom, bounds);
+    return check_launch("render_centre_crops_lib");
+}
+
+// what both rendering entries check, under the entry's name
+static int render_depth_check(const char *name, int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V,
+                              int T, const int *geom, const double *render, const void *depth, const unsigned char *labels,
+                              const unsigned long long *zbuf, long pixel_capacity) {
+    ANCSH_REQUIRE(nframes >= 0, "%s: bad shape nframes=%d", name, nframes);
+    ANCSH_REQUIRE(nframes <= 65535, "%s: %d frames exceed the 65535-frame grid range; split the batch", name, nframes);
+    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
+                  "%s: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", name, depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 30), "%s: pixel_capacity=%ld pixels out of range", name, pixel_capacity);
+    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "%s: T=%d triangles must be in [0, 2^24)", name, T);
+    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "%s: V=%d vertices must be in [0, 2^24)", name, V);
+    ANCSH_REQUIRE(verts && tris && tri_link && geom && render && depth && labels && zbuf, "%s: null pointer", name);
+    ANCSH_REQUIRE(((size_t)depth & 15) == 0 && ((size_t)labels & 7) == 0 && ((size_t)render & 7) == 0 && ((size_t)zbuf & 7) == 0,
+                  "%s: depth must be 16-byte aligned, labels, render and zbuf 8-byte aligned (the crops inside them may start anywhere)", name);
+    return ANCSH_OK;
+}
+
 extern "C" int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
                                          const int *geom, const double *render, void *depth, unsigned char *labels,
                                          unsigned long long *zbuf, long pixel_capacity, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "render_depth_labels: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 65535, "render_depth_labels: %d frames exceed the 65535-frame grid range; split the batch", nframes);
-    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
-                  "render_depth_labels: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 30), "render_depth_labels: pixel_capacity=%ld pixels out of range",
-                  pixel_capacity);
-    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "render_depth_labels: T=%d triangles must be in [0, 2^24)", T);
-    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "render_depth_labels: V=%d vertices must be in [0, 2^24)", V);
-    ANCSH_REQUIRE(verts && tris && tri_link && geom && render && depth && labels && zbuf, "render_depth_labels: null pointer");
-    ANCSH_REQUIRE(((size_t)depth & 15) == 0 && ((size_t)labels & 7) == 0 && ((size_t)render & 7) == 0 && ((size_t)zbuf & 7) == 0,
-                  "render_depth_labels: depth must be 16-byte aligned, labels, render and zbuf 8-byte aligned (the crops inside them may "
-                  "start anywhere)");
+    if (const int rc = render_depth_check("render_depth_labels", nframes, depth_type, verts, tris, tri_link, V, T, geom, render, depth, labels,
+                                          zbuf, pixel_capacity))
+        return rc;
     if (nframes == 0) return ANCSH_OK;
     if (depth_type == ANCSH_DEPTH_U16)
-        render_launch<unsigned short>(nframes, verts, tris, tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity,
+        render_launch<unsigned short>(nframes, verts, tris, tri_link, V, T, nullptr, 0, 0, geom, render, depth, labels, zbuf, pixel_capacity,
                                       (hipStream_t)stream);
     else
-        render_launch<float>(nframes, verts, tris, tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity, (hipStream_t)stream);
+        render_launch<float>(nframes, verts, tris, tri_link, V, T, nullptr, 0, 0, geom, render, depth, labels, zbuf, pixel_capacity,
+                             (hipStream_t)stream);
     return check_launch("render_depth_labels");
+}
+
+extern "C" int ancsh_render_depth_labels_lib(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V,
+                                             int T, const int *tri_off, int ninst, int Tmax, const int *geom, const double *render,
+                                             void *depth, unsigned char *labels, unsigned long long *zbuf, long pixel_capacity,
+                                             void *stream) {
+    if (const int rc = render_depth_check("render_depth_labels_lib", nframes, depth_type, verts, tris, tri_link, V, T, geom, render, depth,
+                                          labels, zbuf, pixel_capacity))
+        return rc;
+    if (const int rc = render_library_check("render_depth_labels_lib", tri_off, ninst)) return rc;
+    ANCSH_REQUIRE(Tmax >= 0 && Tmax <= T, "render_depth_labels_lib: Tmax=%d, the largest instance's triangle count, must be in [0, T=%d]", Tmax, T);
+    if (nframes == 0) return ANCSH_OK;
+    if (depth_type == ANCSH_DEPTH_U16)
+        render_launch<unsigned short>(nframes, verts, tris, tri_link, V, T, tri_off, ninst, Tmax, geom, render, depth, labels, zbuf,
+                                      pixel_capacity, (hipStream_t)stream);
+    else
+        render_launch<float>(nframes, verts, tris, tri_link, V, T, tri_off, ninst, Tmax, geom, render, depth, labels, zbuf, pixel_capacity,
+                             (hipStream_t)stream);
+    return check_launch("render_depth_labels_lib");
 }

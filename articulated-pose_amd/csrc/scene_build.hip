@@ -9,6 +9,8 @@
 // ONE launch, one thread per (frame, link): the thread composes its link's world pose from the leaf upwards, so it keeps one 3 x 4 map and
 // no per-link array; thread l of a frame also copies value l of either table's head.  float64 arithmetic evaluated as written (the library
 // is built with -ffp-contract=off); the only values that are not a pure sequence of IEEE operations are sincos' two results.
+// A LIBRARY of instances (ancsh_pose_scene_build_lib): a stack of tables, the instance of a frame in its pose's value 28; both kernels are
+// wrappers around sb_frame_link.
 #include "common.h"
 
 namespace ancsh {
@@ -54,15 +56,13 @@ __device__ __forceinline__ void sb_link_map(const double *__restrict__ kl, int l
     sb_compose(T, J, X);
 }
 
-__global__ __launch_bounds__(SB_THREADS) void pose_scene_build_kernel(int nframes, const double *__restrict__ kin,
-                                                                      const double *__restrict__ pose, double *__restrict__ render,
-                                                                      double *__restrict__ scene) {
-    const int t = (int)(blockIdx.x * SB_THREADS + threadIdx.x), f = t / SB_LINKS, l = t % SB_LINKS;
-    if (f >= nframes) return;
-    double *rt = render + (size_t)f * ANCSH_RENDER_WIDTH, *sc = scene + (size_t)f * ANCSH_SCENE_WIDTH;
-    // the heads, value l of each: the scene's verbatim; the render's {P00..P12, depth_scale, z_min, nlinks, 0 ..}
+// thread l of a frame: link l's maps and value l of either head, from the object's table `kin` and the frame's pose `ps` into the frame's
+// tables rt and sc -- both kernels' body.  r9: what the render table's value 9 reads (0 for one object, the instance for a library)
+__device__ __forceinline__ void sb_frame_link(const double *__restrict__ kin, const double *__restrict__ ps, int l, double r9,
+                                              double *__restrict__ rt, double *__restrict__ sc) {
+    // the heads, value l of each: the scene's verbatim; the render's {P00..P12, depth_scale, z_min, nlinks, r9, 0 ..}
     sc[l] = kin[l];
-    rt[l] = l < 6 ? kin[16 + l] : l == 6 ? kin[6] : l == 7 ? kin[22] : l == 8 ? kin[14] : 0.0;
+    rt[l] = l < 6 ? kin[16 + l] : l == 6 ? kin[6] : l == 7 ? kin[22] : l == 8 ? kin[14] : l == 9 ? r9 : 0.0;
     double *R = rt + ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l, *S = sc + ANCSH_SCENE_HEAD + ANCSH_SCENE_LINK * l;
     const double nlv = kin[14];
     const int nl = nlv >= 1.0 && nlv <= (double)SB_LINKS ? (int)nlv : 0;        // NaN fails both comparisons
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(SB_THREADS) void pose_scene_build_kernel(int nframe
         for (int k = 0; k < ANCSH_SCENE_LINK; ++k) S[k] = 0.0;
         return;
     }
-    const double *ps = pose + (size_t)f * ANCSH_POSE_WIDTH, *kl = kin + SB_KIN_HEAD + SB_KIN_LINK * l;
+    const double *kl = kin + SB_KIN_HEAD + SB_KIN_LINK * l;
     double W[12], X[12], C[12];
     sb_link_map(kl, l, ps[l], W);
     // from the leaf upwards: W <- X_p o W for p = parent(l), parent(p), ..., 0.  A parent is < its child (the host checks it; a table that
@@ -109,19 +109,68 @@ __global__ __launch_bounds__(SB_THREADS) void pose_scene_build_kernel(int nframe
     }
 }
 
+__global__ __launch_bounds__(SB_THREADS) void pose_scene_build_kernel(int nframes, const double *__restrict__ kin,
+                                                                      const double *__restrict__ pose, double *__restrict__ render,
+                                                                      double *__restrict__ scene) {
+    const int t = (int)(blockIdx.x * SB_THREADS + threadIdx.x), f = t / SB_LINKS, l = t % SB_LINKS;
+    if (f >= nframes) return;
+    sb_frame_link(kin, pose + (size_t)f * ANCSH_POSE_WIDTH, l, 0.0, render + (size_t)f * ANCSH_RENDER_WIDTH,
+                  scene + (size_t)f * ANCSH_SCENE_WIDTH);
+}
+
+// the library's: frame f reads the table of the instance its pose names, pose[28]; a value that names none zeroes both tables
+__global__ __launch_bounds__(SB_THREADS) void pose_scene_build_lib_kernel(int nframes, const double *__restrict__ kin, int ninst,
+                                                                          const double *__restrict__ pose, double *__restrict__ render,
+                                                                          double *__restrict__ scene) {
+    const int t = (int)(blockIdx.x * SB_THREADS + threadIdx.x), f = t / SB_LINKS, l = t % SB_LINKS;
+    if (f >= nframes) return;
+    const double *ps = pose + (size_t)f * ANCSH_POSE_WIDTH;
+    double *rt = render + (size_t)f * ANCSH_RENDER_WIDTH, *sc = scene + (size_t)f * ANCSH_SCENE_WIDTH;
+    const int i = instance_index(ps[28], ninst);
+    if (i < 0) {                                                        // thread l: value l of both heads and link l of both tables
+        rt[l] = 0.0;
+        sc[l] = 0.0;
+        double *R = rt + ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l, *S = sc + ANCSH_SCENE_HEAD + ANCSH_SCENE_LINK * l;
+#pragma unroll
+        for (int k = 0; k < ANCSH_RENDER_LINK; ++k) R[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < ANCSH_SCENE_LINK; ++k) S[k] = 0.0;
+        return;
+    }
+    sb_frame_link(kin + (size_t)i * ANCSH_KIN_WIDTH, ps, l, (double)i, rt, sc);
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
 
-extern "C" int ancsh_pose_scene_build(int nframes, const double *kin, const double *pose, double *render, double *scene, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "pose_scene_build: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 65535, "pose_scene_build: %d frames exceed the 65535-frame range of the entries that read the tables; split the batch",
+// what both entries check, under the entry's name
+static int pose_scene_check(const char *name, int nframes, const double *kin, const double *pose, const double *render, const double *scene) {
+    ANCSH_REQUIRE(nframes >= 0, "%s: bad shape nframes=%d", name, nframes);
+    ANCSH_REQUIRE(nframes <= 65535, "%s: %d frames exceed the 65535-frame range of the entries that read the tables; split the batch", name,
                   nframes);
-    ANCSH_REQUIRE(kin && pose && render && scene, "pose_scene_build: null pointer");
+    ANCSH_REQUIRE(kin && pose && render && scene, "%s: null pointer", name);
     ANCSH_REQUIRE(((size_t)kin & 7) == 0 && ((size_t)pose & 7) == 0 && ((size_t)render & 7) == 0 && ((size_t)scene & 7) == 0,
-                  "pose_scene_build: kin, pose, render and scene must be 8-byte aligned");
+                  "%s: kin, pose, render and scene must be 8-byte aligned", name);
+    return ANCSH_OK;
+}
+
+extern "C" int ancsh_pose_scene_build(int nframes, const double *kin, const double *pose, double *render, double *scene, void *stream) {
+    if (const int rc = pose_scene_check("pose_scene_build", nframes, kin, pose, render, scene)) return rc;
     if (nframes == 0) return ANCSH_OK;
     const unsigned blocks = (unsigned)(((long)nframes * SB_LINKS + SB_THREADS - 1) / SB_THREADS);
     hipLaunchKernelGGL(pose_scene_build_kernel, dim3(blocks), dim3(SB_THREADS), 0, (hipStream_t)stream, nframes, kin, pose, render, scene);
     return check_launch("pose_scene_build");
+}
+
+extern "C" int ancsh_pose_scene_build_lib(int nframes, const double *kin, int ninst, const double *pose, double *render, double *scene,
+                                          void *stream) {
+    if (const int rc = pose_scene_check("pose_scene_build_lib", nframes, kin, pose, render, scene)) return rc;
+    ANCSH_REQUIRE(ninst >= 1 && ninst <= ANCSH_LIBRARY_MAX_INSTANCES, "pose_scene_build_lib: ninst=%d instances must be in [1, %d]", ninst,
+                  ANCSH_LIBRARY_MAX_INSTANCES);
+    if (nframes == 0) return ANCSH_OK;
+    const unsigned blocks = (unsigned)(((long)nframes * SB_LINKS + SB_THREADS - 1) / SB_THREADS);
+    hipLaunchKernelGGL(pose_scene_build_lib_kernel, dim3(blocks), dim3(SB_THREADS), 0, (hipStream_t)stream, nframes, kin, ninst, pose, render,
+                       scene);
+    return check_launch("pose_scene_build_lib");
 }

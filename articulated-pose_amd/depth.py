@@ -17,6 +17,10 @@ table's camera model and link maps) go in, depth crops and link-label crops come
 The fourth builds both tables on the GPU (ancsh_pose_scene_build; reference: pybullet's forward kinematics in
 tools/render_synthetic.py:140-158, 206-217, on the host): an object's kinematic table (pack_kinematics), uploaded once, and one pose per
 frame (pack_pose: joint values and a view matrix) go in; and centres crops on the projected object (ancsh_render_centre_crops).
+
+The last three take a LIBRARY of object instances in place of one object (the *_lib entries; reference: tools/render_synthetic.py:52, one
+render_data call per instance): pack_mesh_library concatenates the instances' meshes, the kinematics is the (ninst, 672) stack of their
+tables, and a frame names its instance in its own table (pack_pose / pack_render_scene, instance=).
 """
 import numpy as np
 import torch
@@ -516,12 +520,54 @@ def pack_mesh(links):
     return verts, tris, tri_link
 
 
-def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, width, depth_scale=1.0, z_min=1e-6):
+LIBRARY_MAX_INSTANCES = 4096                                            # include/ancsh_hip.h, ANCSH_LIBRARY_MAX_INSTANCES
+
+
+def pack_mesh_library(meshes):
+    """A library of object instances for the *_lib entries (include/ancsh_hip.h): meshes = 1..4096 pack_mesh results, or link lists as
+    pack_mesh takes them.  -> (verts (V, 3) float32, tris (T, 3) int32 with GLOBAL vertex indices -- each instance's base added --, tri_link
+    (T,) int32, tri_off (ninst + 1,) int32: instance i owns triangles [tri_off[i], tri_off[i + 1])), contiguous.  ValueError when a face
+    names a vertex outside its own instance, for more than 4096 instances or 2^24 or more vertices or triangles in all (found from the
+    shapes, before anything is concatenated)."""
+    if not isinstance(meshes, (list, tuple)) or not 1 <= len(meshes) <= LIBRARY_MAX_INSTANCES:
+        raise ValueError("a mesh library holds 1..%d instances (depth.pack_mesh results or link lists), got %s"
+                         % (LIBRARY_MAX_INSTANCES, len(meshes) if isinstance(meshes, (list, tuple)) else type(meshes).__name__))
+    packed = []
+    for i, m in enumerate(meshes):
+        is_packed = isinstance(m, tuple) and len(m) == 3 and all(isinstance(a, np.ndarray) for a in m) and m[0].ndim == 2 and m[2].ndim == 1
+        try:
+            v, t, tl = m if is_packed else pack_mesh(m)
+        except ValueError as e:
+            raise ValueError("instance %d: %s" % (i, e))
+        if v.ndim != 2 or v.shape[1:] != (3,) or t.ndim != 2 or t.shape[1:] != (3,) or tl.shape != (t.shape[0],):
+            raise ValueError("instance %d: expected depth.pack_mesh's (verts (V, 3), tris (T, 3), tri_link (T,)), got shapes %s, %s, %s"
+                             % (i, v.shape, t.shape, tl.shape))
+        packed.append((v, t, tl))
+    V, T = sum(v.shape[0] for v, _, _ in packed), sum(t.shape[0] for _, t, _ in packed)
+    if V >= (1 << 24) or T >= (1 << 24):
+        raise ValueError("a mesh library holds fewer than 2^24 vertices and triangles in all, got %d and %d" % (V, T))
+    verts, tris, tri_link, tri_off, base = [], [], [], [0], 0
+    for i, (v, t, tl) in enumerate(packed):
+        if t.size and (t.min() < 0 or t.max() >= v.shape[0]):
+            raise ValueError("instance %d: a face names a vertex outside its own instance's [0, %d)" % (i, v.shape[0]))
+        if tl.size and (tl.min() < 0 or tl.max() >= SCENE_MAX_LINKS):
+            raise ValueError("instance %d: a triangle's link must be in [0, %d)" % (i, SCENE_MAX_LINKS))
+        verts.append(np.asarray(v, np.float32))
+        tris.append(t.astype(np.int64) + base)
+        tri_link.append(np.asarray(tl, np.int32))
+        base += v.shape[0]
+        tri_off.append(tri_off[-1] + t.shape[0])
+    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate(parts).astype(dtype))
+    return cat(verts, np.float32).reshape(-1, 3), cat(tris, np.int32).reshape(-1, 3), cat(tri_link, np.int32), np.asarray(tri_off, np.int32)
+
+
+def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, width, depth_scale=1.0, z_min=1e-6, instance=0):
     """One frame's render table (RENDER_WIDTH,) float64 for ancsh_render_depth_labels (include/ancsh_hip.h has its layout), from
     pack_frame_scene's arguments with its conventions: the inverse of what that table makes ancsh_depth_annotate_stream do.  P is the
     inverse of the affine pixel -> (s, t) map of coord_unprojection_from_projmat(projMat, height, width); R_l is the inverse of the 4 x 4
     G_l = cam2world @ pinv(model2world_l.T) pack_frame_scene composes for row vectors, stored in column form: R_l (v, 1) is the camera
-    point (x', y', z) of model point v, and M_l of the frame's scene applied to it is canon2urdf_l v."""
+    point (x', y', z) of model point v, and M_l of the frame's scene applied to it is canon2urdf_l v.  instance: the frame's instance of a
+    mesh library (pack_mesh_library), an integer in [0, 4096), written to the table's value 9; 0 for a single mesh."""
     V, Pm = np.asarray(viewMat, np.float64), np.asarray(projMat, np.float64)
     if V.shape != (4, 4):
         raise ValueError("viewMat must be (4, 4), got %s" % (V.shape,))
@@ -539,7 +585,7 @@ def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, 
     table = np.zeros(RENDER_WIDTH)
     table[0:2], table[3:5] = Ainv[0], Ainv[1]
     table[2], table[5] = -(Ainv @ np.array([C[2], C[5]]))
-    table[6], table[7], table[8] = depth_scale, z_min, L
+    table[6], table[7], table[8], table[9] = depth_scale, z_min, L, _instance_value(instance)
     cam2world = np.linalg.pinv(V.T)
     cam2world[:3, :] = -cam2world[:3, :]
     for l in range(L):
@@ -552,9 +598,30 @@ def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, 
     return table
 
 
-def check_render_tables(render, n):
+def _instance_value(instance):
+    """pack_pose's / pack_render_scene's instance argument -> the float64 the table carries; ValueError unless an integer in [0, 4096)."""
+    try:
+        ok = int(instance) == instance and 0 <= instance < LIBRARY_MAX_INSTANCES
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("instance must be an integer in [0, %d), got %r" % (LIBRARY_MAX_INSTANCES, instance))
+    return float(int(instance))
+
+
+def _check_instances(what, values, ninst):
+    """ValueError naming the first frame of `what` whose instance value is no integer in [0, ninst) (NaN fails every comparison)."""
+    if not (isinstance(ninst, (int, np.integer)) and 1 <= ninst <= LIBRARY_MAX_INSTANCES):
+        raise ValueError("ninst: a library holds 1..%d instances, got %r" % (LIBRARY_MAX_INSTANCES, ninst))
+    for i, v in enumerate(values):
+        if not (v >= 0 and v < ninst and v == np.floor(v)):
+            raise ValueError("%s %d: the instance must be an integer in [0, %d), the library's size, got %r" % (what, i, ninst, float(v)))
+
+
+def check_render_tables(render, n, ninst=None):
     """-> render as a C-contiguous (n, RENDER_WIDTH) float64 array (one table is repeated for every frame); ValueError unless every table is
-    finite with depth_scale > 0, z_min > 0, an integer nlinks in 1..16 and zero reserved values."""
+    finite with depth_scale > 0, z_min > 0, an integer nlinks in 1..16 and zero reserved values.  ninst: the tables go with a mesh library of
+    ninst instances, and value 9 must name one of them (None: a single mesh, value 9 is reserved and 0)."""
     try:
         a = np.asarray(render, np.float64)
     except (TypeError, ValueError):
@@ -564,10 +631,13 @@ def check_render_tables(render, n):
     if a.shape != (n, RENDER_WIDTH):
         raise ValueError("render must be (%d, %d): one depth.pack_render_scene table, or one per frame, got shape %s" % (n, RENDER_WIDTH, a.shape))
     a = np.ascontiguousarray(a)
+    if ninst is not None:
+        _check_instances("render table", a[:, 9], ninst)
     if not np.isfinite(a).all():
         raise ValueError("render: every value must be finite")
+    first = 9 if ninst is None else 10                                  # value 9: reserved for a single mesh, the instance of a library
     for i, t in enumerate(a):
-        if not (t[6] > 0 and t[7] > 0) or t[8] != np.floor(t[8]) or not 1 <= t[8] <= SCENE_MAX_LINKS or (t[9:RENDER_HEAD] != 0).any():
+        if not (t[6] > 0 and t[7] > 0) or t[8] != np.floor(t[8]) or not 1 <= t[8] <= SCENE_MAX_LINKS or (t[first:RENDER_HEAD] != 0).any():
             raise ValueError("render table %d: depth_scale and z_min must be > 0, nlinks an integer in [1, %d] and the reserved values 0"
                              % (i, SCENE_MAX_LINKS))
     return a
@@ -603,10 +673,27 @@ def pack_crop_geometry(shapes, origins, geom, first=0):
     return a
 
 
+class DeviceMesh(tuple):
+    """mesh_to_device's result: the 5-tuple (verts, tris, tri_link, V, T) the operators have always taken.  A mesh library carries three more
+    attributes: tri_off, the (ninst + 1,) int32 device tensor; host_tri_off, its host copy; Tmax, the largest instance's triangle count, which
+    sizes the raster grid without a device read.  A single mesh has tri_off = None and ninst = None."""
+    tri_off = host_tri_off = ninst = None
+    Tmax = 0
+
+
+def is_mesh_library(mesh):
+    """True for pack_mesh_library's 4-tuple and for its mesh_to_device form."""
+    return (isinstance(mesh, DeviceMesh) and mesh.tri_off is not None) or (not isinstance(mesh, DeviceMesh) and isinstance(mesh, (list, tuple))
+                                                                         and len(mesh) == 4)
+
+
 def mesh_to_device(mesh, device):
     """pack_mesh's arrays on the device, as render_depth takes them: (verts, tris, tri_link, V, T); an empty array still owns one element of
-    memory (the entry refuses null pointers)."""
-    verts, tris, tri_link = mesh
+    memory (the entry refuses null pointers).  pack_mesh_library's 4-tuple gives a library (DeviceMesh: the same 5-tuple with tri_off, a host
+    copy of it, ninst and Tmax beside it); tri_off must be non-decreasing from 0 to T over 1..4096 instances."""
+    if not isinstance(mesh, (list, tuple)) or len(mesh) not in (3, 4):
+        raise ValueError("a mesh is depth.pack_mesh's 3 arrays or depth.pack_mesh_library's 4")
+    verts, tris, tri_link = mesh[:3]
     verts, tris, tri_link = np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(tris, np.int32), np.ascontiguousarray(tri_link, np.int32)
     if verts.ndim != 2 or verts.shape[1] != 3 or tris.ndim != 2 or tris.shape[1] != 3 or tri_link.shape != (tris.shape[0],):
         raise ValueError("a mesh is depth.pack_mesh's (verts (V, 3), tris (T, 3), tri_link (T,)), got shapes %s, %s, %s"
@@ -615,23 +702,48 @@ def mesh_to_device(mesh, device):
     if T and (tris.min() < 0 or tris.max() >= V or tri_link.min() < 0 or tri_link.max() >= SCENE_MAX_LINKS):
         raise ValueError("a mesh's triangles name vertices in [0, %d) and links in [0, %d)" % (V, SCENE_MAX_LINKS))
     up = lambda a, shape: torch.from_numpy(a if a.size else np.zeros(shape, a.dtype)).to(device)
-    return up(verts, (1, 3)), up(tris, (1, 3)), up(tri_link, (1,)), V, T
+    out = DeviceMesh((up(verts, (1, 3)), up(tris, (1, 3)), up(tri_link, (1,)), V, T))
+    if len(mesh) == 4:
+        off = np.asarray(mesh[3])
+        if off.ndim != 1 or not 2 <= off.shape[0] <= LIBRARY_MAX_INSTANCES + 1 or not np.issubdtype(off.dtype, np.integer) or off[0] != 0 \
+                or off[-1] != T or (np.diff(off) < 0).any():
+            raise ValueError("a mesh library's tri_off is (ninst + 1,) integers for 1..%d instances, non-decreasing from 0 to T = %d, got %s"
+                             % (LIBRARY_MAX_INSTANCES, T, off.tolist() if off.size <= 16 else off.shape))
+        if V >= (1 << 24) or T >= (1 << 24):
+            raise ValueError("a mesh library holds fewer than 2^24 vertices and triangles in all, got %d and %d" % (V, T))
+        out.host_tri_off = np.ascontiguousarray(off, np.int32)
+        out.tri_off = torch.from_numpy(out.host_tri_off.copy()).to(device)
+        out.ninst, out.Tmax = off.shape[0] - 1, int(np.diff(off).max())
+    return out
+
+
+def _check_device_mesh(mesh):
+    """The checks render_depth and centre_crop_origins share -> (verts, tris, tri_link, V, T, tri_off or None, ninst, Tmax)."""
+    verts, tris, tri_link, V, T = mesh
+    if not verts.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
+            or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
+        raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
+    tri_off = getattr(mesh, "tri_off", None)
+    if tri_off is None:
+        return verts, tris, tri_link, V, T, None, None, 0
+    ninst, Tmax = int(mesh.ninst), int(mesh.Tmax)
+    if tri_off.dtype != torch.int32 or tuple(tri_off.shape) != (ninst + 1,) or not tri_off.is_contiguous() or not tri_off.is_cuda:
+        raise ValueError("a mesh library's tri_off must be depth.mesh_to_device's (ninst + 1,) int32 device tensor")
+    return verts, tris, tri_link, V, T, tri_off, ninst, Tmax
 
 
 def render_depth(mesh, geom, render, depth_dtype, out=None, scratch=None, pixel_capacity=None):
     """ancsh_render_depth_labels on device tensors (no host sync): mesh = mesh_to_device's (verts, tris, tri_link, V, T), geom (B, 5) int32,
-    render (B, RENDER_WIDTH) float64.  -> (depth (pixel_capacity,) int16 bits of uint16 / float32, labels (pixel_capacity,) uint8); out =
+    render (B, RENDER_WIDTH) float64.  A mesh library (mesh_to_device of pack_mesh_library's arrays) goes through
+    ancsh_render_depth_labels_lib: frame b draws the instance its table's value 9 names.  -> (depth (pixel_capacity,) int16 bits of uint16 / float32, labels (pixel_capacity,) uint8); out =
     the same pair preallocated (a captured step passes slot-owned buffers), else pixel_capacity pixels of depth 0 / label 255; scratch: the
     (pixel_capacity,) int64 z-buffer.  Every pixel of every crop is written, the others keep what they held."""
-    verts, tris, tri_link, V, T = mesh
     name = check_depth_dtype(depth_dtype)
     _, tt, kind = DEPTH_DTYPES[name]
-    if not verts.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    verts, tris, tri_link, V, T, tri_off, ninst, Tmax = _check_device_mesh(mesh)
     dev = verts.device
-    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
-            or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
-        raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
     B = int(geom.shape[0])
     if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
             or not (geom.is_contiguous() and render.is_contiguous()):
@@ -654,14 +766,18 @@ def render_depth(mesh, geom, render, depth_dtype, out=None, scratch=None, pixel_
     elif scratch.dtype != torch.int64 or scratch.numel() < cap_px or not scratch.is_contiguous():
         raise ValueError("scratch must be a contiguous int64 tensor of >= %d elements" % cap_px)
     _lib.require_cuda(tris, tri_link, geom, render, depth, labels, scratch)
+    if tri_off is not None:                # a library: the instance of a frame is its table's value 9
+        _lib.call("ancsh_render_depth_labels_lib", B, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(tri_off),
+                  ninst, Tmax, _lib.ptr(geom), _lib.ptr(render), _lib.ptr(depth), _lib.ptr(labels), _lib.ptr(scratch), cap_px)
+        return depth, labels
     _lib.call("ancsh_render_depth_labels", B, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(geom),
               _lib.ptr(render), _lib.ptr(depth), _lib.ptr(labels), _lib.ptr(scratch), cap_px)
     return depth, labels
 
 
 def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"):
-    """Eager wrapper: mesh = pack_mesh's arrays, render_scenes = one pack_render_scene table or one per crop, crops = a list of (h, w,
-    (row0, col0)) -> a list of (depth_crop (h, w) of depth_dtype, label_crop (h, w) uint8, (row0, col0)): exactly the frames
+    """Eager wrapper: mesh = pack_mesh's arrays (or pack_mesh_library's: each table's value 9 names its frame's instance), render_scenes =
+    one pack_render_scene table or one per crop, crops = a list of (h, w, (row0, col0)) -> a list of (depth_crop (h, w) of depth_dtype, label_crop (h, w) uint8, (row0, col0)): exactly the frames
     AncshPipeline.submit_depth(..., scene=, rig=) and annotate_depth_batch take.  One host sync; the streaming pipeline
     (AncshPipeline.submit_render) has none, and no pixel of it ever reaches the host."""
     dev = torch.device(device)
@@ -669,10 +785,11 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
         raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
     name = check_depth_dtype(depth_dtype)
     shapes, origins = check_crops(crops)
-    tables = check_render_tables(render_scenes, len(shapes))
+    d_mesh = mesh_to_device(mesh, dev)
+    tables = check_render_tables(render_scenes, len(shapes), d_mesh.ninst)
     geom = np.zeros((len(shapes), GEOM_WORDS), np.int32)
     total = pack_crop_geometry(shapes, origins, geom)
-    depth, labels = render_depth(mesh_to_device(mesh, dev), torch.from_numpy(geom).to(dev), torch.from_numpy(tables).to(dev), name,
+    depth, labels = render_depth(d_mesh, torch.from_numpy(geom).to(dev), torch.from_numpy(tables).to(dev), name,
                                  pixel_capacity=total)
     depth, labels = depth.cpu().numpy(), labels.cpu().numpy()
     depth = depth.view(np.uint16) if name == "uint16" else depth
@@ -843,10 +960,29 @@ def check_kinematics(kin, K=None):
     return a
 
 
-def pack_pose(q, viewMat):
+def check_kinematics_library(kin, K=None):
+    """-> a library's kinematics as a C-contiguous (ninst, KIN_WIDTH) float64 array: np.stack of 1..4096 pack_kinematics tables, each of
+    which passes check_kinematics (the ValueError names the instance).  All instances share K parts; their link counts may differ."""
+    try:
+        a = np.ascontiguousarray(np.asarray(kin, np.float64))
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.ndim != 2 or a.shape[1] != KIN_WIDTH or not 1 <= a.shape[0] <= LIBRARY_MAX_INSTANCES:
+        raise ValueError("kinematics of a library: (ninst, %d) for 1..%d instances (np.stack of depth.pack_kinematics tables), got shape %s"
+                         % (KIN_WIDTH, LIBRARY_MAX_INSTANCES, a.shape))
+    for i, row in enumerate(a):
+        try:
+            check_kinematics(row, K)
+        except ValueError as e:
+            raise ValueError("instance %d: %s" % (i, e))
+    return a
+
+
+def pack_pose(q, viewMat, instance=0):
     """One frame's pose (POSE_WIDTH,) float64 for ancsh_pose_scene_build: q = up to 16 joint values, link l's at position l (link 0's and
     those of fixed joints are not read), viewMat = the (4, 4) view matrix in the `.reshape(4, 4).T` form of tools/preprocess_data.py:228
-    (world -> eye), which must be rigid.  ValueError otherwise (check_poses' rules)."""
+    (world -> eye), which must be rigid.  instance: the frame's instance of a library (pack_mesh_library and a stack of kinematic tables), an
+    integer in [0, 4096), written to value 28; 0 for a single object.  ValueError otherwise (check_poses' rules)."""
     q = np.asarray(q, np.float64).reshape(-1)
     V = np.asarray(viewMat, np.float64)
     if q.shape[0] > SCENE_MAX_LINKS:
@@ -856,12 +992,14 @@ def pack_pose(q, viewMat):
     pose = np.zeros(POSE_WIDTH)
     pose[:q.shape[0]] = q
     pose[16:28] = V[:3].reshape(12)
-    return check_poses(pose, 1)[0]
+    pose[28] = _instance_value(instance)
+    return check_poses(pose, 1, LIBRARY_MAX_INSTANCES)[0]
 
 
-def check_poses(pose, n):
+def check_poses(pose, n, ninst=None):
     """-> pose as a C-contiguous (n, POSE_WIDTH) float64 array (one pose is repeated for every frame); ValueError unless every pose is
-    finite, its view's rotation orthonormal to 1e-9 (and proper) and its reserved values 0."""
+    finite, its view's rotation orthonormal to 1e-9 (and proper) and its reserved values 0.  ninst: the poses go with a library of ninst
+    instances, and value 28 must name one of them (None: a single object, value 28 is reserved and 0)."""
     try:
         a = np.asarray(pose, np.float64)
     except (TypeError, ValueError):
@@ -871,10 +1009,13 @@ def check_poses(pose, n):
     if a.shape != (n, POSE_WIDTH):
         raise ValueError("pose must be (%d, %d): one depth.pack_pose row, or one per frame, got shape %s" % (n, POSE_WIDTH, a.shape))
     a = np.ascontiguousarray(a)
+    first = 28 if ninst is None else 29                                 # value 28: reserved for a single object, the instance of a library
+    if ninst is not None:
+        _check_instances("pose", a[:, 28], ninst)
     if not np.isfinite(a).all():
         raise ValueError("pose: every value must be finite")
     for i, p in enumerate(a):
-        if (p[28:] != 0).any() or not _is_rotation(p[16:28].reshape(3, 4)[:, :3]):
+        if (p[first:] != 0).any() or not _is_rotation(p[16:28].reshape(3, 4)[:, :3]):
             raise ValueError("pose %d: the view matrix must be rigid (its rotation orthonormal to 1e-9) and the reserved values 0" % i)
     return a
 
@@ -899,13 +1040,15 @@ def forward_kinematics(kin, q):
 
 def pose_scene_build(kin, pose, out=None):
     """ancsh_pose_scene_build on device tensors (no host sync): kin (KIN_WIDTH,) float64, pose (B, POSE_WIDTH) float64 -> (render (B,
-    RENDER_WIDTH), scene (B, SCENE_WIDTH)) float64; out = the same pair preallocated (a captured step passes slot-owned buffers)."""
+    RENDER_WIDTH), scene (B, SCENE_WIDTH)) float64; out = the same pair preallocated (a captured step passes slot-owned buffers).  kin (ninst,
+    KIN_WIDTH), a library's stack, goes through ancsh_pose_scene_build_lib: frame b reads the table its pose's value 28 names."""
     if not kin.is_cuda:
         raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
     B = int(pose.shape[0])
-    if kin.dtype != torch.float64 or tuple(kin.shape) != (KIN_WIDTH,) or pose.dtype != torch.float64 or tuple(pose.shape) != (B, POSE_WIDTH) \
-            or not (kin.is_contiguous() and pose.is_contiguous()):
-        raise ValueError("kin must be (%d,) float64 and pose (B, %d) float64, contiguous" % (KIN_WIDTH, POSE_WIDTH))
+    library = kin.dim() == 2               # a library's stack of tables: the instance of a frame is its pose's value 28
+    if kin.dtype != torch.float64 or (tuple(kin.shape) != (KIN_WIDTH,) and not (library and kin.shape[1] == KIN_WIDTH and 1 <= kin.shape[0] <= LIBRARY_MAX_INSTANCES)) \
+            or pose.dtype != torch.float64 or tuple(pose.shape) != (B, POSE_WIDTH) or not (kin.is_contiguous() and pose.is_contiguous()):
+        raise ValueError("kin must be (%d,) float64 -- a library: (ninst, %d) -- and pose (B, %d) float64, contiguous" % (KIN_WIDTH, KIN_WIDTH, POSE_WIDTH))
     if out is None:
         out = (torch.empty((B, RENDER_WIDTH), dtype=torch.float64, device=kin.device), torch.empty((B, SCENE_WIDTH), dtype=torch.float64, device=kin.device))
     render, scene = out
@@ -913,19 +1056,24 @@ def pose_scene_build(kin, pose, out=None):
             or not (render.is_contiguous() and scene.is_contiguous()):
         raise ValueError("out must be (render (B, %d), scene (B, %d)) float64, contiguous" % (RENDER_WIDTH, SCENE_WIDTH))
     _lib.require_cuda(pose, render, scene)
+    if library:
+        _lib.call("ancsh_pose_scene_build_lib", B, _lib.ptr(kin), int(kin.shape[0]), _lib.ptr(pose), _lib.ptr(render), _lib.ptr(scene))
+        return render, scene
     _lib.call("ancsh_pose_scene_build", B, _lib.ptr(kin), _lib.ptr(pose), _lib.ptr(render), _lib.ptr(scene))
     return render, scene
 
 
 def pose_scene_tables(kin, poses, device="cuda:0"):
-    """Eager wrapper: kin = one pack_kinematics table, poses = one pack_pose row or (n, 32) of them -> (render (n, 208), scene (n, 240))
+    """Eager wrapper: kin = one pack_kinematics table (or a library's (ninst, 672) stack: each pose's value 28 names its instance), poses =
+    one pack_pose row or (n, 32) of them -> (render (n, 208), scene (n, 240))
     float64 numpy arrays read back from ancsh_pose_scene_build: what submit_render and render_depth_frames take.  One host sync."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
-    kin = check_kinematics(kin)
+    library = np.ndim(kin) == 2
+    kin = check_kinematics_library(kin) if library else check_kinematics(kin)
     p = np.asarray(poses, np.float64)
-    poses = check_poses(p, 1 if p.ndim == 1 else p.shape[0])
+    poses = check_poses(p, 1 if p.ndim == 1 else p.shape[0], kin.shape[0] if library else None)
     render, scene = pose_scene_build(torch.from_numpy(kin).to(dev), torch.from_numpy(poses).to(dev))
     return render.cpu().numpy(), scene.cpu().numpy()
 
@@ -933,13 +1081,8 @@ def pose_scene_tables(kin, poses, device="cuda:0"):
 def centre_crop_origins(mesh, geom, render, scratch=None):
     """ancsh_render_centre_crops on device tensors (no host sync): mesh = mesh_to_device's, geom (B, 5) int32, render (B, RENDER_WIDTH)
     float64; the rows of geom whose row0 and col0 both hold CROP_CENTRE get the origin that centres their crop on the projected object, in
-    place.  scratch: (B, 4) int32 of working memory.  -> geom."""
-    verts, tris, tri_link, V, T = mesh
-    if not verts.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
-    if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
-            or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
-        raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
+    place.  scratch: (B, 4) int32 of working memory.  -> geom.  A mesh library goes through ancsh_render_centre_crops_lib."""
+    verts, tris, tri_link, V, T, tri_off, ninst, _ = _check_device_mesh(mesh)
     B = int(geom.shape[0])
     if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
             or not (geom.is_contiguous() and render.is_contiguous()):
@@ -949,6 +1092,10 @@ def centre_crop_origins(mesh, geom, render, scratch=None):
     elif scratch.dtype != torch.int32 or scratch.numel() < 4 * B or not scratch.is_contiguous():
         raise ValueError("scratch must be a contiguous int32 tensor of >= %d elements" % (4 * B))
     _lib.require_cuda(tris, tri_link, geom, render, scratch)
+    if tri_off is not None:                # a library: the block of a frame strides over its instance's triangles only
+        _lib.call("ancsh_render_centre_crops_lib", B, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(tri_off), ninst,
+                  _lib.ptr(render), _lib.ptr(geom), _lib.ptr(scratch))
+        return geom
     _lib.call("ancsh_render_centre_crops", B, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(render),
               _lib.ptr(geom), _lib.ptr(scratch))
     return geom
@@ -966,16 +1113,17 @@ def check_posed_crops(crops, max_frames=None):
 
 
 def centre_crops(mesh, render_tables, sizes, device="cuda:0"):
-    """Eager wrapper: mesh = pack_mesh's arrays, render_tables = one render table or one per crop, sizes = a list of (h, w) -> the (n, 2)
+    """Eager wrapper: mesh = pack_mesh's arrays (or pack_mesh_library's), render_tables = one render table or one per crop, sizes = a list of (h, w) -> the (n, 2)
     int32 origins (row0, col0) that centre each h x w crop on its frame's projected object (ancsh_render_centre_crops; (0, 0) where nothing
     projects): what submit_render's crops take.  One host sync."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
     shapes, origins = check_posed_crops([(h, w, None) for h, w in sizes])
-    tables = check_render_tables(render_tables, len(shapes))
+    d_mesh = mesh_to_device(mesh, dev)
+    tables = check_render_tables(render_tables, len(shapes), d_mesh.ninst)
     geom = np.zeros((len(shapes), GEOM_WORDS), np.int32)
     pack_crop_geometry(shapes, origins, geom)
     d_geom = torch.from_numpy(geom).to(dev)
-    centre_crop_origins(mesh_to_device(mesh, dev), d_geom, torch.from_numpy(tables).to(dev))
+    centre_crop_origins(d_mesh, d_geom, torch.from_numpy(tables).to(dev))
     return d_geom.cpu().numpy()[:, 3:5].copy()

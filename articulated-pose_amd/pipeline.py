@@ -314,11 +314,16 @@ class AncshPipeline(object):
     render_mesh (with those annotated-frame options): depth.pack_mesh's arrays, uploaded once and shared by the slots; the step starts with
         ancsh_render_depth_labels, which renders every frame's depth and label crops into the slot's device buffers in front of
         ancsh_depth_annotate_stream.  submit_render / stream_render_batches take crop geometry and tables only: no pixel crosses PCIe.
+    render_mesh = depth.pack_mesh_library's 4 arrays: a library of instances, uploaded once; the frame's instance travels in its table's
+        reserved value -- depth.pack_render_scene(..., instance=i) for submit_render, depth.pack_pose(q, view, instance=i) for submit_posed, where
+        kinematics is the (ninst, 672) np.stack of the instances' tables -- and the step calls the *_lib entries: the same launch count.
     kinematics (with render_mesh): depth.pack_kinematics' table, uploaded once and shared by the slots; the step starts with
         ancsh_pose_scene_build, which writes the slot's render and scene tables from one pose per frame (depth.pack_pose: joint values and a
         view matrix), and ancsh_render_centre_crops, which centres the crops that ask for it on the projected object, in front of the
         renderer.  submit_posed / stream_posed_batches take crops and poses only: 32 doubles per frame cross PCIe.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
+
+    ninst = None                                # a library's size (render_mesh=depth.pack_mesh_library(...)); None for a single object
 
     def __init__(self, num_parts, weights_ancsh, weights_npcs, batch_size, num_points, device="cuda:0",
                  inlier_th=0.1, niter_a=10000, niter_b=200, couple=True, use_graph=True, seed=0, slots=1, lm_schedule=None, tie_window=None,
@@ -342,12 +347,13 @@ class AncshPipeline(object):
         self.hw_queues = check_hardware_queues(max(1, slots))
         self.device = torch.device(device)
         self.mesh = self.kin = None
-        if o.posed:                             # the kinematic table: checked here, uploaded once below and shared by all slots
-            from .depth import check_kinematics
-            kinematics = check_kinematics(kinematics, num_parts)
-        if o.render:                            # the mesh: checked, then uploaded once and shared by all slots
+        if o.posed:                             # the kinematic table (a library: the stack of them): checked here, uploaded once below and shared by all slots
+            from .depth import check_kinematics, check_kinematics_library
+            kinematics = check_kinematics_library(kinematics, num_parts) if np.ndim(kinematics) == 2 else check_kinematics(kinematics, num_parts)
+        if o.render:                            # the mesh (or the library): checked, then uploaded once and shared by all slots
             from .depth import mesh_to_device
             self.mesh = mesh_to_device(render_mesh, self.device)
+            self.ninst = self.mesh.ninst
         if o.posed:
             self.kin = torch.from_numpy(kinematics).to(self.device)
         # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
@@ -795,7 +801,7 @@ class AncshPipeline(object):
         elif cloud_base != 0:
             raise ValueError("cloud_base needs AncshPipeline(..., keyed=True)")
         n_valid, nf, stage, *checked = front()
-        side = check_side_inputs(o.inputs, dict(side, **(checked[0] if checked else {})), n_valid, self.K, "AncshPipeline")
+        side = check_side_inputs(o.inputs, dict(side, **(checked[0] if checked else {})), n_valid, self.K, "AncshPipeline", self.ninst)
         if len(self._inflight) == len(self.slots):
             raise RuntimeError("all %d slots hold unretired batches: retire() one first" % len(self.slots))
         if not self._prepared:

@@ -241,14 +241,21 @@ def require_side_inputs(built, given):
             raise ValueError(inp.missing)
 
 
-def check_side_inputs(built, given, n, K, cls):
-    """Refuse and check, input by input in the table's order -> {name: the checked (n, ...) array, or None} for the side inputs `built`."""
+LIBRARY_CHECKS = dict(pose=depth_mod.check_poses, render=depth_mod.check_render_tables)   # the tables that carry a library frame's instance
+
+
+def check_side_inputs(built, given, n, K, cls, ninst=None):
+    """Refuse and check, input by input in the table's order -> {name: the checked (n, ...) array, or None} for the side inputs `built`.
+    ninst: the pipeline holds a library of ninst instances, and the pose or render tables must each name one of them."""
     out = {}
     for inp in EVERY_INPUT:
         v = given.get(inp.name)
         if v is not None:
             refuse_side_inputs(built, {inp.name: v}, cls)
-            v = v if inp.check is None else inp.check(v, n, K)
+            if ninst is not None and inp.name in LIBRARY_CHECKS:
+                v = LIBRARY_CHECKS[inp.name](v, n, ninst)
+            else:
+                v = v if inp.check is None else inp.check(v, n, K)
         if inp in built:
             out[inp.name] = v
     return out
@@ -303,7 +310,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     render_mesh (annotated depth frames only): the step renders the frames itself from this mesh (depth.pack_mesh), so `render` is one
     more side input and no pixel travels in.
     kinematics (with render_mesh): the step builds the render and scene tables itself from this table (depth.pack_kinematics) and one pose
-    per frame, so `pose` (POSE_INPUT) takes the place of the `render` and `scene` inputs."""
+    per frame, so `pose` (POSE_INPUT) takes the place of the `render` and `scene` inputs.
+    A library: render_mesh = depth.pack_mesh_library's 4 arrays, alone (submit_render: the instance of a frame in render[9]) or with kinematics
+    = the (ninst, 672) stack of its instances' tables (submit_posed: in pose[28]); the two counts must agree."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -349,6 +358,15 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
         raise ValueError("render_mesh renders the annotated depth frames of the step on the device: it needs " + RENDERED.rsplit(", ", 1)[0])
     if kinematics is not None and render_mesh is None:
         raise ValueError("kinematics poses the mesh the step renders: it needs " + RENDERED)
+    if kinematics is not None:             # a stack of tables goes with a mesh library of as many instances, one table with one mesh
+        nkin = np.shape(kinematics)[0] if np.ndim(kinematics) == 2 else None
+        nmesh = max(np.size(render_mesh[3]) - 1, 0) if depth_mod.is_mesh_library(render_mesh) else None
+        if nkin != nmesh:
+            count = lambda n, one, many: one if n is None else many % n
+            raise ValueError("kinematics and render_mesh must hold the same instances: kinematics is %s, render_mesh is %s (a library: "
+                             "depth.pack_mesh_library(...) and np.stack of its instances' depth.pack_kinematics tables)"
+                             % (count(nkin, "a single table", "a stack of %d tables"),
+                                count(nmesh, "a single mesh", "a mesh library of %d instances")))
     if raw_capacity is not None:
         if not couple:
             raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")

@@ -1184,7 +1184,7 @@ int ancsh_depth_annotate_stream(int nclouds, int depth_type, const void *depth, 
  *   render : (nframes, ANCSH_RENDER_WIDTH = 208) float64, 8-byte aligned, per frame:
  *     [0..5] P00 P01 P02 P10 P11 P12 : col = (P00 s + P01 t) + P02, row = (P10 s + P11 t) + P12 -- the inverse of the affine map
  *     s = C00 col + C01 row + C02, t = C10 col + C11 row + C12 of scene[7..12]   [6] depth_scale   [7] z_min > 0   [8] nlinks, 1..16
- *     [9..15] reserved, 0   then per link l, ANCSH_RENDER_LINK = 12 wide, at ANCSH_RENDER_HEAD + 12 l: R, row-major 3 x 4, model frame ->
+ *     [9] reserved, 0 (the *_lib entries: the frame's instance)   [10..15] reserved, 0   then per link l, ANCSH_RENDER_LINK = 12 wide, at ANCSH_RENDER_HEAD + 12 l: R, row-major 3 x 4, model frame ->
  *     the camera point (x', y', z);
  *   depth (pixel_capacity) of depth_type, 16-byte aligned; labels (pixel_capacity) bytes, 8-byte aligned; zbuf (pixel_capacity) uint64 of
  *     working memory, 8-byte aligned.
@@ -1238,7 +1238,8 @@ int ancsh_render_depth_labels(int nframes, int depth_type, const float *verts, c
  *   pose : (nframes, ANCSH_POSE_WIDTH = 32) float64, 8-byte aligned, per frame:
  *     [0..15] q_l, link l's joint value in radians (revolute) or length units (prismatic); ignored for link 0 and for fixed joints
  *     [16..27] V, the first three rows of the view matrix (world -> eye, the `.reshape(4, 4).T` form of tools/preprocess_data.py:228),
- *     row-major 3 x 4; it must be rigid (the host checks it)   [28..31] reserved, 0
+ *     row-major 3 x 4; it must be rigid (the host checks it)   [28] reserved, 0 (ancsh_pose_scene_build_lib: the frame's instance)
+ *     [29..31] reserved, 0
  *   render (nframes, ANCSH_RENDER_WIDTH) and scene (nframes, ANCSH_SCENE_WIDTH) float64, 8-byte aligned: the outputs; every value of every
  *     frame's tables is written.
  * Everything below is float64, evaluated in exactly the written order (no contraction); (s, c) = sincos(q) are the only values that are not
@@ -1282,6 +1283,41 @@ int ancsh_pose_scene_build(int nframes, const double *kin, const double *pose, d
 #define ANCSH_CROP_CENTRE (-2147483647 - 1)
 int ancsh_render_centre_crops(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T, const double *render,
                               int *geom, int *bounds, void *stream);
+
+/* A LIBRARY of object instances behind the three entries above: many meshes and many kinematic tables uploaded once, and the instance of a
+ * frame chosen on the device from a reserved value of the table that already travels per frame -- pose[28] for ancsh_pose_scene_build_lib,
+ * render[9] (which that entry writes) for the two others.  The single-object entries keep their contracts: they read neither value.  The
+ * reference renders one instance after the other on the host (tools/render_synthetic.py:52, one render_data call per name_obj).  The ABI
+ * version is unchanged; callers detect the entries by their symbols.
+ *   The library: the instances' meshes concatenated -- verts (V, 3) float32, tris (T, 3) int32 whose indices are GLOBAL (each instance's
+ *   vertex base already added), tri_link (T,) int32 -- and tri_off (ninst + 1,) int32, non-decreasing, tri_off[0] = 0, tri_off[ninst] = T:
+ *   instance i owns triangles [tri_off[i], tri_off[i + 1]).  kin (ninst, ANCSH_KIN_WIDTH) float64: instance i's table at kin + 672 i.
+ *   1 <= ninst <= ANCSH_LIBRARY_MAX_INSTANCES; V, T < 2^24 as before (the z-buffer key keeps the GLOBAL triangle index in its low word).
+ *   The instance of a frame: i = the value when it is an integer in [0, ninst); any other value (NaN fails every comparison) makes the
+ *   table "not one", as a bad nlinks does.  So do offsets tri_off[i], tri_off[i + 1] that are no range inside [0, T].
+ * ancsh_render_depth_labels_lib: ancsh_render_depth_labels in which frame f draws the triangles of instance render[f][9] only.  The same three
+ *   launches; the raster grid is (ceil(Tmax / 4), nframes): the wave for LOCAL triangle j of frame f handles global triangle tri_off[i] + j
+ *   and returns when that is >= tri_off[i + 1] (f is the block's y index: the lookup, two offsets per wave, is uniform over the wave, and
+ *   nothing is read per pixel).  Tmax is an ARGUMENT: max_i (tri_off[i + 1] - tri_off[i]), computed by the caller from its host copy of
+ *   tri_off and checked here to lie in [0, T]; no device value is read before the launches, so the grids depend on (pixel_capacity, nframes,
+ *   Tmax) only and the entry stays graph-capturable.  A Tmax below the true maximum leaves the triangles past it undrawn.  Keys, ties (the
+ *   lowest triangle index: global order within an instance is local order shifted) and the resolve step are unchanged, so a frame has, byte
+ *   for byte, the depth and labels ancsh_render_depth_labels gives for that instance's own mesh.  A frame without an instance renders an
+ *   all-background crop.  A library with very unequal instances launches idle waves for the small ones: they exit on the range test.
+ * ancsh_render_centre_crops_lib: ancsh_render_centre_crops in which the block of a centred frame strides over its instance's triangles
+ *   only; a frame without an instance counts no vertex and gets (0, 0).
+ * ancsh_pose_scene_build_lib: frame f reads the table kin + 672 i, i = pose[f][28], and writes exactly what ancsh_pose_scene_build writes
+ *   for that table (the same device function, sincos included) except render[9] = (double)i.  A frame without an instance gets both
+ *   tables all zero: nlinks = 0, so the renderer writes background, the annotation counts 0 pixels and the record is all-NaN -- the path
+ *   of a frame the reference skips.
+ * Checked before any launch: what the single-object entry checks, 1 <= ninst <= 4096, tri_off non-null and 4-byte aligned, 0 <= Tmax <= T. */
+#define ANCSH_LIBRARY_MAX_INSTANCES 4096
+int ancsh_render_depth_labels_lib(int nframes, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                  const int *tri_off, int ninst, int Tmax, const int *geom, const double *render, void *depth,
+                                  unsigned char *labels, unsigned long long *zbuf, long pixel_capacity, void *stream);
+int ancsh_render_centre_crops_lib(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T, const int *tri_off,
+                                  int ninst, const double *render, int *geom, int *bounds, void *stream);
+int ancsh_pose_scene_build_lib(int nframes, const double *kin, int ninst, const double *pose, double *render, double *scene, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -9,9 +9,15 @@ shape (K = 3, 32 x 1024, 10000 / 200 hypotheses, couple=True, synthetic weights,
     c: the same stream, its tables packed inside the loop, one frame at a time: what a user of render_mesh= pays without the new entries;
     d: the posed stream on the same views and joint values (the poses are 32 doubles each, made before the clock; submit_posed's checks
        run inside it).
+--instances N (default 1: one object, the single-object entries): N > 1 builds a library of N distinct instances -- boxes of tess - 1, tess and
+tess + 1 quads per edge in turn, so their triangle counts are unequal and their mean stays near one object's, each with its own hinge
+position -- and mixes them within every batch (frame f of batch b shows instance (f + b) mod N); the streams then go through the *_lib
+entries.  --library takes that path for --instances 1 too: the same work through the library's code.  --idle-tess T appends one more instance
+of T quads per edge that no frame shows: it only raises Tmax, the size of the raster grid, so every frame launches idle waves up to it --
+leg r, the renderer alone on one batch (HIP events around --calls calls), and leg d with and without it give what those waves cost.
 Prints one JSON line: a record, not a gate.
 
-    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8] [--instances 1] [--library] [--idle-tess 0]
 """
 import argparse
 import json
@@ -48,17 +54,22 @@ def make_frame(rs):
     return V, rs.uniform(0.1, 1.2)
 
 
-def host_tables(P, V, opening, side):
-    """The two host packers on the link poses the reference takes from its simulator."""
-    pos = np.array([[0.0, 0.0, 0.0], [0.3, 0.02, 0.12], [-0.34, -0.03, 0.02]])
+def hinge(i):
+    """Where instance i's link 1 hangs: instance 0 is render_bench's object, every further one has its hinge 5 mm further out."""
+    return (0.3 + 0.005 * i, 0.02, 0.12)
+
+
+def host_tables(P, V, opening, side, i=0):
+    """The two host packers on the link poses the reference takes from its simulator, for instance i."""
+    pos = np.array([[0.0, 0.0, 0.0], hinge(i), [-0.34, -0.03, 0.02]])
     orn = np.array([[0, 0, 0, 1.0], [0, np.sin(opening / 2), 0, np.cos(opening / 2)], [0, 0, np.sin(0.2), np.cos(0.2)]])
-    return (D.pack_render_scene(V, P, pos, orn, side, side, depth_scale=SCALE),
+    return (D.pack_render_scene(V, P, pos, orn, side, side, depth_scale=SCALE, instance=i),
             D.pack_frame_scene(V, P, pos, orn, ZERO, ZERO, ZERO[:2], PARTS, side, side, depth_scale=SCALE))
 
 
-def kinematics(P, side):
+def kinematics(P, side, i=0):
     """The same object as a tree: link 1 hinged about y beside link 0, link 2 fixed on the other side, turned 0.4 about z."""
-    return D.pack_kinematics(P, side, side, [-1, 0, 0], ["fixed", "revolute", "fixed"], [(0, 0, 0), (0.3, 0.02, 0.12), (-0.34, -0.03, 0.02)],
+    return D.pack_kinematics(P, side, side, [-1, 0, 0], ["fixed", "revolute", "fixed"], [(0, 0, 0), hinge(i), (-0.34, -0.03, 0.02)],
                              [(0, 0, 0), (0, 0, 0), (0, 0, 0.4)], [(0, 0, 0), (0, 1, 0), (0, 0, 0)], ZERO, ZERO, ZERO[:2], PARTS, depth_scale=SCALE)
 
 
@@ -72,26 +83,34 @@ def main():
     ap.add_argument("--tess", type=int, default=8, help="quads per box edge: 12 tess^2 triangles per link")
     ap.add_argument("--calls", type=int, default=200, help="back-to-back pairs of the two entries between their two events")
     ap.add_argument("--pack-calls", type=int, default=300, help="calls of each host packer for leg a")
+    ap.add_argument("--instances", type=int, default=1, help="instances mixed within every batch; above 1: a library through the *_lib entries")
+    ap.add_argument("--library", action="store_true", help="take the library's path for --instances 1 too")
+    ap.add_argument("--idle-tess", type=int, default=0, help="append an instance of this many quads per edge that no frame shows (a library only)")
     args = ap.parse_args()
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
-    P, side = projection(), args.side
-    mesh = D.pack_mesh([tessellated_box(LO, HI, args.tess)] * K)
-    kin = kinematics(P, side)
+    P, side, ninst = projection(), args.side, args.instances
+    if not 1 <= ninst <= D.LIBRARY_MAX_INSTANCES or args.tess < 2:
+        ap.error("--instances must be in [1, %d] and --tess >= 2" % D.LIBRARY_MAX_INSTANCES)
+    library = ninst > 1 or args.library or args.idle_tess > 0
+    tess = [args.tess + (i % 3 - 1 if ninst > 1 else 0) for i in range(ninst)]
+    meshes = [D.pack_mesh([tessellated_box(LO, HI, t)] * K) for t in tess + [args.idle_tess] * (args.idle_tess > 0)]
+    mesh = D.pack_mesh_library(meshes) if library else meshes[0]
+    kin = np.stack([kinematics(P, side, i) for i in range(len(meshes))]) if library else kinematics(P, side)
     crops = [(side, side, (0, 0))] * B
     nf, rigs, jf = np.ones(B, np.float32), np.tile(identity_rig(K), (B, 1)), rs.normal(size=(B, 13))
     views, tbatches, pbatches = [], [], []
-    for _ in range(args.frames // B):
-        frames = [make_frame(rs) for _ in range(B)]
-        tables = [host_tables(P, V, o, side) for V, o in frames]
+    for b in range(args.frames // B):
+        frames = [make_frame(rs) + ((f + b) % ninst,) for f in range(B)]
+        tables = [host_tables(P, V, o, side, i) for V, o, i in frames]
         views.append(frames)
         tbatches.append((crops, nf, dict(render=np.stack([t[0] for t in tables]), scene=np.stack([t[1] for t in tables]), rig=rigs, frame=jf)))
-        pbatches.append((crops, nf, dict(pose=np.stack([D.pack_pose([0.0, o, 0.0], V) for V, o in frames]), rig=rigs, frame=jf)))
+        pbatches.append((crops, nf, dict(pose=np.stack([D.pack_pose([0.0, o, 0.0], V, instance=i) for V, o, i in frames]), rig=rigs, frame=jf)))
     # the device's tables against the host packers', on the last batch
     rt, sc = D.pose_scene_tables(kin, pbatches[-1][2]["pose"], dev)
     parity = max(float(np.abs(rt - tbatches[-1][2]["render"]).max()), float(np.abs(sc - tbatches[-1][2]["scene"]).max()))
     # a: the host packers
-    V, o = views[0][0]
+    V, o, _ = views[0][0]
     pos = np.array([[0.0, 0.0, 0.0], [0.3, 0.02, 0.12], [-0.34, -0.03, 0.02]])
     orn = np.array([[0, 0, 0, 1.0], [0, np.sin(o / 2), 0, np.cos(o / 2)], [0, 0, np.sin(0.2), np.cos(0.2)]])
     t0 = time.perf_counter()
@@ -126,6 +145,17 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         op_ms.append(e0.elapsed_time(e1) / args.calls)
+    # r: the renderer alone, on the tables and origins the pair left behind
+    pix, zbuf = (torch.zeros((cap,), dtype=torch.int16, device=dev), torch.zeros((cap,), dtype=torch.uint8, device=dev)), torch.zeros((cap,), dtype=torch.int64, device=dev)
+    render_ms = []
+    for k in range(args.rounds + 1):
+        e0.record()
+        for _ in range(args.calls):
+            D.render_depth(d_mesh, d_geom, out[0], "uint16", out=pix, scratch=zbuf)
+        e1.record()
+        torch.cuda.synchronize()
+        if k:                                                 # the first round warms up
+            render_ms.append(e0.elapsed_time(e1) / args.calls)
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
@@ -136,7 +166,7 @@ def main():
     def packed_in_the_loop(passes):
         for _ in range(passes):
             for frames in views:
-                tables = [host_tables(P, V, o, side) for V, o in frames]
+                tables = [host_tables(P, V, o, side, i) for V, o, i in frames]
                 yield crops, nf, dict(render=np.stack([t[0] for t in tables]), scene=np.stack([t[1] for t in tables]), rig=rigs, frame=jf)
 
     def leg(name, passes):
@@ -163,12 +193,15 @@ def main():
                       "host_pack_frames_per_s_one_core": round(1e6 / sum(pack_us.values()), 1),
                       "entries_us_per_batch": round(1e3 * op, 2), "entries_us_per_batch_rounds": [round(1e3 * x, 2) for x in op_ms],
                       "entries_frames_per_s": round(1e3 * B / op, 1),
+                      "render_us_per_batch": round(1e3 * float(np.median(render_ms)), 2), "render_us_per_batch_rounds": [round(1e3 * x, 2) for x in render_ms],
                       "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
                       "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()},
                       "d_over_b": round(med["d"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
                       "h2d_bytes_per_batch_b": B * (4 * D.GEOM_WORDS + 8 * D.RENDER_WIDTH + 8 * D.SCENE_WIDTH),
                       "h2d_bytes_per_batch_d": B * (4 * D.GEOM_WORDS + 8 * D.POSE_WIDTH),
                       "max_abs_device_minus_host_tables": parity, "triangles": int(mesh[1].shape[0]), "vertices": int(mesh[0].shape[0]),
+                      "instances": ninst, "library": library, "triangles_per_instance": [int(m[1].shape[0]) for m in meshes], "idle_tess": args.idle_tess,
+                      "mean_triangles_per_frame": round(float(np.mean([meshes[i][1].shape[0] for fr in views for _, _, i in fr])), 1),
                       "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(tbatches) * B,
                                 "side": side, "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
 
