@@ -146,6 +146,10 @@ SIGNATURES = {
     # the annotated clouds themselves, made from depth and link-label crops (no ABI bump, detected by its symbol): nclouds, depth_type, depth,
     # labels, pixel_capacity, geom, scene, rows, capacity, offsets, counts, link_counts, scratch, stream
     "ancsh_depth_annotate_stream": [_c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp],
+    # the inverse of that entry's sort, predictions and ground truth per row back on the pixel grid (no ABI bump, detected by its symbol):
+    # nclouds, depth_type, depth, link_labels, pixel_capacity, geom, scene, offsets, counts, scratch, labels, values, gt_rows, gt_nchan,
+    # capacity, dest, img_labels, img_values, img_gt_labels, img_gt_values, image_capacity, stream
+    "ancsh_depth_annotated_images": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 8 + [_c_int, _c_long] + [_vp] * 5 + [_c_long, _vp],
     # those crops themselves, rendered from articulated triangle meshes (no ABI bump, detected by its symbol): nframes, depth_type, verts, tris,
     # tri_link, V, T, geom, render, depth, labels, zbuf, pixel_capacity, stream
     "ancsh_render_depth_labels": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_long, _vp],

@@ -164,22 +164,6 @@ static void depth_launch(int nclouds, const void *depth, const unsigned char *ma
 }
 
 // ---- the inverse of the compaction: per-row labels / values -> per-pixel images (include/ancsh_hip.h, ancsh_depth_label_images) ----------
-// `total` dwords at `out`, dword e = value(e): whole 16-byte vectors where the address allows, single dwords in front of and behind them.
-// Consecutive lanes store consecutive addresses either way.
-template <typename F>
-__device__ __forceinline__ void depth_store_span(unsigned *__restrict__ out, long total, F value) {
-    long head = (long)(((16 - ((size_t)out & 15)) & 15) >> 2);
-    head = head < total ? head : total;
-    const long body = (total - head) >> 2;
-    for (long e = threadIdx.x; e < head; e += DEPTH_THREADS) out[e] = value(e);
-    uint4 *o4 = reinterpret_cast<uint4 *>(out + head);
-    for (long v = threadIdx.x; v < body; v += DEPTH_THREADS) {
-        const long e = head + 4 * v;
-        o4[v] = make_uint4(value(e), value(e + 1), value(e + 2), value(e + 3));
-    }
-    for (long e = head + 4 * body + threadIdx.x; e < total; e += DEPTH_THREADS) out[e] = value(e);
-}
-
 // Block (x, b) on the count / scatter passes' grid and chunking.  Its first row is offsets[b] + the counts of cloud b's earlier chunks, read
 // from the scratch the count pass left.  Per step of 256 groups: validity and the wave scan exactly as depth_scatter_kernel ranks its rows ->
 // the source row of every pixel of the step in LDS (-1: not a valid pixel, or a row cut at capacity); then the block stores the step's

@@ -1,5 +1,6 @@
 // depth_common.h -- what the depth front end's two entries share (depth.hip: object masks -> xyz rows; depth_annotate.hip: link labels ->
-// annotated rows): the crop geometry, the chunking of a crop over the grid, the validity of a depth value and the block sum.
+// annotated rows; their inverses, rows -> images): the crop geometry, the chunking of a crop over the grid, the validity of a depth value, the
+// block sum and the span store of the image kernels.
 #pragma once
 #include "common.h"
 
@@ -48,6 +49,22 @@ __device__ __forceinline__ long depth_block_sum(long v, long *s_red) {      // s
 static long depth_chunks(long pixel_capacity, int nclouds) {
     const long chunks = (pixel_capacity / nclouds + 2047) / 2048;
     return chunks < 1 ? 1 : chunks > DEPTH_CHUNKS ? DEPTH_CHUNKS : chunks;
+}
+
+// `total` dwords at `out`, dword e = value(e): whole 16-byte vectors where the address allows, single dwords in front of and behind them.
+// Consecutive lanes store consecutive addresses either way.
+template <typename F>
+__device__ __forceinline__ void depth_store_span(unsigned *__restrict__ out, long total, F value) {
+    long head = (long)(((16 - ((size_t)out & 15)) & 15) >> 2);
+    head = head < total ? head : total;
+    const long body = (total - head) >> 2;
+    for (long e = threadIdx.x; e < head; e += DEPTH_THREADS) out[e] = value(e);
+    uint4 *o4 = reinterpret_cast<uint4 *>(out + head);
+    for (long v = threadIdx.x; v < body; v += DEPTH_THREADS) {
+        const long e = head + 4 * v;
+        o4[v] = make_uint4(value(e), value(e + 1), value(e + 2), value(e + 3));
+    }
+    for (long e = head + 4 * body + threadIdx.x; e < total; e += DEPTH_THREADS) out[e] = value(e);
 }
 
 }  // namespace ancsh

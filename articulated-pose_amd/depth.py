@@ -481,6 +481,122 @@ def annotate_depth_batch(frames, scenes, depth_dtype, K, device="cuda:0"):
     return rows[:int(off[-1])].cpu().numpy(), off, cnt.cpu().numpy(), lc.cpu().numpy()
 
 
+# ---- annotated frames, back on the pixel grid: predicted and true part / NOCS images (ancsh_depth_annotated_images) ----------------------
+GT_IMAGE_VALUES = 6     # per pixel of the ground-truth value image: [part NOCS (3) | NAOCS (3)], columns 4..9 of an 18-column row
+
+
+def annotated_image_buffers(capacity, device=None):
+    """(labels (capacity,) int32 -1, values (capacity, 7) float32 NaN, gt_labels (capacity,) int32 -1, gt_values (capacity, 6) float32 NaN):
+    what ancsh_depth_annotated_images writes per pixel, 60 bytes a pixel.  On `device`, or (None) in pinned host memory."""
+    four = (torch.full((capacity,), -1, dtype=torch.int32, device=device),
+            torch.full((capacity, LABEL_VALUES), float("nan"), dtype=torch.float32, device=device),
+            torch.full((capacity,), -1, dtype=torch.int32, device=device),
+            torch.full((capacity, GT_IMAGE_VALUES), float("nan"), dtype=torch.float32, device=device))
+    return four if device is not None else tuple(t.pin_memory() for t in four)
+
+
+def depth_annotated_images(depth, labels, geom, scene, dest, offsets, counts, row_labels, row_values, gt_rows, out=None, scratch=None):
+    """ancsh_depth_annotated_images on device tensors (no host sync): the inverse of depth_annotate()'s sort.  depth, labels (the link-label
+    bytes), geom, scene: what depth_annotate() was given; offsets (B+1,) int32, counts (B,) int32 and scratch: what it wrote (pass the SAME
+    scratch tensor to both calls: it carries the per-chunk histograms); row_labels (capacity,) int32 / row_values (capacity, 7) float32: per
+    row, as dataset.raw_point_labels writes them; gt_rows (capacity, >= 10) float32: dataset.point_gt_build's 18-column rows; dest (B,)
+    int32: where cloud b's h * w images start in the image buffers, < 0 = the cloud writes nothing.  -> (img_labels (image_capacity,)
+    int32, img_values (image_capacity, 7) float32, img_gt_labels (image_capacity,) int32, img_gt_values (image_capacity, 6) float32); out =
+    the same four preallocated (a captured step passes slot-owned buffers), else pixel_capacity elements prefilled with -1 / NaN.  A pixel
+    without a row reads -1 / NaN in all four; elements of no cloud's image keep what they held."""
+    if not depth.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = depth.device
+    kinds = {torch.float32: 1, torch.int16: 0}
+    if hasattr(torch, "uint16"):
+        kinds[torch.uint16] = 0
+    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
+    cap_px = int(depth.shape[0])
+    if labels is None or labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
+    B = int(geom.shape[0])
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
+            or not (geom.is_contiguous() and scene.is_contiguous()):
+        raise ValueError("geom must be (B, 5) int32 and scene (B, %d) float64, contiguous" % SCENE_WIDTH)
+    for name, t, n in (("dest", dest, B), ("offsets", offsets, B + 1), ("counts", counts, B)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous (%d,) int32 tensor" % (name, n))
+    cap = int(row_labels.shape[0]) if row_labels.dim() == 1 else -1
+    if row_labels.dtype != torch.int32 or row_values.dtype != torch.float32 or cap < 0 or tuple(row_values.shape) != (cap, LABEL_VALUES) \
+            or not (row_labels.is_contiguous() and row_values.is_contiguous()):
+        raise ValueError("row_labels must be (capacity,) int32 and row_values (capacity, %d) float32, contiguous" % LABEL_VALUES)
+    if gt_rows.dtype != torch.float32 or gt_rows.dim() != 2 or gt_rows.shape[0] != cap or gt_rows.shape[1] < 10 or not gt_rows.is_contiguous():
+        raise ValueError("gt_rows must be a contiguous (%d, >= 10) float32 tensor (dataset.point_gt_build's rows)" % cap)
+    if scratch is None or scratch.dtype != torch.int32 or scratch.numel() < B * MAX_CHUNKS * SCENE_MAX_LINKS or not scratch.is_contiguous():
+        raise ValueError("scratch must be the (>= %d,) int32 tensor depth_annotate() was given" % (B * MAX_CHUNKS * SCENE_MAX_LINKS))
+    if out is None:
+        out = annotated_image_buffers(cap_px, dev)
+    img_labels, img_values, img_gt_labels, img_gt_values = out
+    icap = int(img_labels.shape[0]) if img_labels.dim() == 1 else -1
+    if img_labels.dtype != torch.int32 or img_gt_labels.dtype != torch.int32 or img_values.dtype != torch.float32 \
+            or img_gt_values.dtype != torch.float32 or icap < 0 or tuple(img_gt_labels.shape) != (icap,) \
+            or tuple(img_values.shape) != (icap, LABEL_VALUES) or tuple(img_gt_values.shape) != (icap, GT_IMAGE_VALUES) \
+            or not all(t.is_contiguous() for t in out):
+        raise ValueError("out must be contiguous (img_labels (n,) int32, img_values (n, %d) float32, img_gt_labels (n,) int32, img_gt_values "
+                         "(n, %d) float32)" % (LABEL_VALUES, GT_IMAGE_VALUES))
+    _lib.require_cuda(labels, geom, scene, dest, offsets, counts, row_labels, row_values, gt_rows, scratch, *out)
+    _lib.call("ancsh_depth_annotated_images", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(labels), cap_px, _lib.ptr(geom), _lib.ptr(scene),
+              _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(scratch), _lib.ptr(row_labels), _lib.ptr(row_values), _lib.ptr(gt_rows),
+              int(gt_rows.shape[1]), cap, _lib.ptr(dest), _lib.ptr(img_labels), _lib.ptr(img_values), _lib.ptr(img_gt_labels),
+              _lib.ptr(img_gt_values), icap)
+    return img_labels, img_values, img_gt_labels, img_gt_values
+
+
+def cut_annotated_images(labels, values, gt_labels, gt_values, shapes, first=0):
+    """cut_label_images for the four image buffers of annotated frames (pure numpy): labels, gt_labels (>= n,) int32, values (>= n, 7) and
+    gt_values (>= n, 6) float32, shapes = the frames' (h, w) in submission order.  -> [(labels (h, w) int32, values (h, w, 7) float32,
+    gt_labels (h, w) int32, gt_values (h, w, 6) float32)], fresh arrays."""
+    gt_labels, gt_values = np.asarray(gt_labels), np.asarray(gt_values)
+    pred = cut_label_images(labels, values, shapes, first)
+    if gt_labels.dtype != np.int32 or gt_labels.shape != np.shape(labels) or gt_values.dtype != np.float32 \
+            or gt_values.shape != (gt_labels.shape[0], GT_IMAGE_VALUES):
+        raise ValueError("expected gt_labels (n,) int32 and gt_values (n, %d) float32 beside labels (n,)" % GT_IMAGE_VALUES)
+    out, a = [], int(first)
+    for (il, iv), (h, w) in zip(pred, ((int(s[0]), int(s[1])) for s in shapes)):
+        out.append((il, iv, gt_labels[a:a + h * w].reshape(h, w).copy(), gt_values[a:a + h * w].reshape(h, w, GT_IMAGE_VALUES).copy()))
+        a += h * w
+    return out
+
+
+def annotated_frame_images(frames, scenes, rigs, depth_dtype, K, norm_factors=None, P=None, npcs_pred=None, ancsh_pred=None, device="cuda:0"):
+    """Eager wrapper, next to annotate_depth_batch: a batch of annotated depth frames (check_annotated_frames) and one dataset.pack_joint_rig
+    table per frame -> per frame (labels (h, w) int32, values (h, w, 7) float32, gt_labels (h, w) int32, gt_values (h, w, 6) float32), aligned
+    with the frame's crop: at a valid pixel the ground-truth part and [part NOCS | NAOCS] of its 18-column row (dataset.point_gt_build) and
+    what dataset.raw_point_labels gives that row from the sampled points P (B, N, 3), the norm factors and the two networks' heads
+    (npcs_pred, ancsh_pred); every other pixel -1 / NaN, and so every pixel of a frame without rows.  P = None: no predictions, labels and
+    values are -1 / NaN everywhere.  One host sync; the streaming pipeline (annotated_images=True) has none."""
+    from .dataset import DENSE_VALUES, NCHAN, check_rigs, point_gt_build, raw_point_labels
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    n = len(frames) if isinstance(frames, (list, tuple)) else 0
+    depths, labels, origins, nf, scenes = check_annotated_frames(frames, np.ones(n) if norm_factors is None else norm_factors, scenes,
+                                                                 depth_dtype, K)
+    rigs = check_rigs(rigs, len(depths), K)
+    name = check_depth_dtype(depth_dtype)
+    total = sum(d.size for d in depths)
+    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
+    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    d_pix, d_lab, d_geom, d_scene = t(pix.view(np.int16) if name == "uint16" else pix), t(lab), t(geom), t(scenes)
+    cap = total + len(depths)
+    scratch = torch.empty((len(depths) * MAX_CHUNKS * SCENE_MAX_LINKS,), dtype=torch.int32, device=dev)
+    rows7, off, cnt, _ = depth_annotate(d_pix, d_lab, d_geom, d_scene, capacity=cap, scratch=scratch)
+    rows18 = point_gt_build(rows7, off, t(rigs), K, torch.zeros((cap, NCHAN), dtype=torch.float32, device=dev))
+    if P is None:
+        rl = (torch.full((cap,), -1, dtype=torch.int32, device=dev), torch.full((cap, DENSE_VALUES), float("nan"), dtype=torch.float32, device=dev))
+    else:
+        rl = raw_point_labels(rows18, off, nf, torch.as_tensor(P).to(dev), npcs_pred, ancsh_pred)
+    out = depth_annotated_images(d_pix, d_lab, d_geom, d_scene, d_geom[:, 0].contiguous(), off, cnt, rl[0], rl[1], rows18, scratch=scratch)
+    return cut_annotated_images(*(o.cpu().numpy() for o in out), [d.shape for d in depths])
+
+
 # ---- rendered frames: articulated triangle meshes -> the depth and link-label crops above (ancsh_render_depth_labels) --------------------
 RENDER_WIDTH, RENDER_HEAD, RENDER_LINK = 208, 16, 12            # include/ancsh_hip.h, ANCSH_RENDER_*
 

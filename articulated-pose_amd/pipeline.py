@@ -18,7 +18,8 @@ from .network import Network
 from .pose import PoseSolver
 from .stream import (ALL_INPUTS, EVERY_INPUT, JOINT_SOURCES, OPTION_FLAGS, SIDE, SIDE_INPUTS, Output, check_built_with, check_joint_source, check_options,  # noqa: F401
                      check_side_inputs, fill_rows, header_layout, label_buffers, pack_results, patch_dense, per_pixel, per_raw_row, pump,
-                     refuse_built_frame, refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_dense, take_images)
+                     refuse_built_frame, refuse_side_inputs, require_side_inputs, side_host, split_item, stage_side_input, take_annotated_images,
+                     take_dense, take_images)
 
 
 def check_hardware_queues(slots):
@@ -116,7 +117,7 @@ class _Slot(object):
         self.keyed, self.nchan = opts.keyed, kind.nchan
         if opts.point_ground_truth:
             self.perm = torch.zeros((B, N), dtype=torch.int32, device=device)
-        self.layout = lay = header_layout(B, self.keyed, bool(depth), opts.label_images)
+        self.layout = lay = header_layout(B, self.keyed, bool(depth), opts.label_images or opts.annotated_images)
         self.raw_rows = torch.zeros((cap, self.nchan), **f)
         self.hdr = torch.zeros((lay.words,), dtype=torch.int32, device=device)
         if opts.build_point_gt:
@@ -129,9 +130,14 @@ class _Slot(object):
         # dense / label_images: the per-raw-row (dense) or per-row and per-pixel (rowlab, img) labels / values the captured step writes
         # (slot-owned, outside the graph's pool, so a later replay never hands their memory to another tensor) and the f32 graph's own
         # (range guard); rowlab is device only: nobody reads rows.  Their pinned twins cost 4 + 28 bytes per row / pixel of capacity.
-        for name, built in (("dense", opts.dense), ("rowlab", opts.label_images), ("img", opts.label_images)):
+        for name, built in (("dense", opts.dense), ("rowlab", opts.label_images or opts.annotated_images), ("img", opts.label_images)):
             setattr(self, name, label_buffers(cap, device) if built else None)
             setattr(self, name + "32", label_buffers(cap, device) if built and range_guard else None)
+        # annotated_images: the four per-pixel images of annotated frames (aimg: predicted labels / values, ground-truth labels / values),
+        # slot-owned like img; rowlab holds the per-row predictions they are gathered from.  Their pinned twins cost 60 bytes per pixel.
+        from .depth import annotated_image_buffers
+        self.aimg = annotated_image_buffers(cap, device) if opts.annotated_images else None
+        self.aimg32 = annotated_image_buffers(cap, device) if opts.annotated_images and range_guard else None
         hdr = self.h_hdr.numpy()               # host views of the pinned staging (written with numpy, no torch op per cloud)
         self.np_rows = None if depth else self.h_rows.numpy()
         self.np_seed, self.np_off, self.np_nf = hdr[lay.seed].view(np.int64), hdr[lay.off], hdr[lay.nf].view(np.float32)
@@ -178,6 +184,9 @@ class _Slot(object):
         if opts.label_images:
             outs.append(Output("label_images", lambda sl, f32: sl.pick("img", f32), labels, refit=range_guard, extent=per_pixel,
                                take=take_images))
+        if opts.annotated_images:
+            outs.append(Output("annotated_images", lambda sl, f32: sl.pick("aimg", f32), lambda: annotated_image_buffers(cap), refit=range_guard,
+                               extent=per_pixel, take=take_annotated_images))
         if range_guard:
             outs.append(Output("flags", lambda sl, f32: (sl.flags,), pinned(torch.int32, B)))
         self.outputs = {o.name: o for o in outs}
@@ -234,7 +243,7 @@ class _Slot(object):
         return unit
 
     def pick(self, name, f32=False):
-        """Attribute `name` of the step (out, dense, rowlab, img), or (f32=True) its twin of the range guard's f32 graph."""
+        """Attribute `name` of the step (out, dense, rowlab, img, aimg), or (f32=True) its twin of the range guard's f32 graph."""
         return getattr(self, name + "32" if f32 else name)
 
     def header(self, B):
@@ -311,6 +320,11 @@ class AncshPipeline(object):
     depth_capacity with point_ground_truth and build_point_gt: annotated depth frames -- depth crop, link-label crop and a scene table per
         frame (submit_depth(..., scene=, rig=, frame=)); the step starts with ancsh_depth_annotate_stream, then ancsh_point_gt_build and
         the sampler.  retire(link_counts=True) returns the valid pixels per link.  Refuses label_images: its rows are link-major.
+    annotated_images (those annotated frames, rendered and posed ones included): two more launches at the step's end --
+        ancsh_raw_point_labels over the slot's 18-column rows, then ancsh_depth_annotated_images, the inverse of the annotation's sort --
+        carry every row's prediction and ground truth back to its pixel; retire(annotated_images=True) returns per frame (labels (h, w),
+        values (h, w, 7), gt_labels (h, w), gt_values (h, w, 6)).  60 bytes of pinned memory per pixel of capacity and slot (twice that
+        with range_guard).
     render_mesh (with those annotated-frame options): depth.pack_mesh's arrays, uploaded once and shared by the slots; the step starts with
         ancsh_render_depth_labels, which renders every frame's depth and label crops into the slot's device buffers in front of
         ancsh_depth_annotate_stream.  submit_render / stream_render_batches take crop geometry and tables only: no pixel crosses PCIe.
@@ -330,7 +344,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None, kinematics=None):
+                 render_mesh=None, kinematics=None, annotated_images=False):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -338,7 +352,7 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -509,17 +523,23 @@ class AncshPipeline(object):
                 carried = out["record_gt"] if self.ground_truth else out["record_wide"] if self.fit_quality else out["record"]
                 out["record_point_gt"] = point_gt_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, a, n, out["articulation"], frame_in,
                                                         carried, self.coord_regress_loss)
-        if self.dense or self.label_images:      # never both: a depth pipeline refuses dense=True
-            # the last launch: every raw row of the slot's batch (label_images: its unprojected rows), into the slot's own (capacity, .) buffers
+        if self.dense or self.label_images or self.annotated_images:      # at most one: a depth pipeline refuses dense=True, annotated frames label_images
+            # the last launch: every raw row of the slot's batch (label_images: its unprojected rows; annotated_images: its 18-column rows),
+            # into the slot's own (capacity, .) buffers
             from .dataset import raw_point_labels
             _, off, nf = sl.header(self.B)
             rl = raw_point_labels(sl.raw_rows, off, nf, sl.P, n, a, out=sl.pick("dense" if self.dense else "rowlab", f32))
             if self.dense:
                 out["dense"] = rl
-            else:                        # one more launch: the rows back to the pixels they came from
+            elif self.label_images:      # one more launch: the rows back to the pixels they came from
                 from .depth import depth_label_images
                 out["label_images"] = depth_label_images(sl.pix, sl.mask, sl.geom, sl.dest, off, rl[0], rl[1], out=sl.pick("img", f32),
                                                          scratch=sl.scratch)
+            else:                        # one more launch: the rows and their ground truth back through the annotation's link-major sort.
+                # (Nothing between the annotation and here writes sl.scratch: its per-chunk histograms are what the inverse ranks with.)
+                from .depth import depth_annotated_images
+                out["annotated_images"] = depth_annotated_images(sl.pix, sl.mask, sl.geom, sl.scene, sl.dest, off, sl.counts, rl[0], rl[1],
+                                                                 sl.raw_rows, out=sl.pick("aimg", f32), scratch=sl.scratch)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:
@@ -703,9 +723,7 @@ class AncshPipeline(object):
                 if not annotated:                          # (the scenes of annotated frames carry the camera)
                     sl.np_cam[:n_valid] = cam
                     sl.np_cam[n_valid:] = cam[0]
-                if o.label_images:                         # a valid frame's image lies where its crop does; a padding cloud writes none
-                    sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
-                    sl.np_dest[n_valid:] = -1
+                self._stage_dest(sl, n_valid)
                 return [(sl.pix[:pixels], sl.h_pix[:pixels]), (sl.mask[:pixels], sl.h_mask[:pixels])]
             return n_valid, nf, stage, dict(scene=scenes) if annotated else {}
         self._enqueue(front, seed, tag, cloud_base, gt=gt, frame=frame, rig=rig)
@@ -746,6 +764,7 @@ class AncshPipeline(object):
             def stage(sl):
                 pack_crop_geometry(shapes, origins, sl.np_geom)
                 sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and render the same bytes)
+                self._stage_dest(sl, n_valid)
                 return []
             return n_valid, nf, stage, dict(scene=scenes)
         self._enqueue(front, seed, tag, cloud_base, render=render, gt=gt, frame=frame, rig=rig)
@@ -783,9 +802,16 @@ class AncshPipeline(object):
             def stage(sl):
                 pack_crop_geometry(shapes, origins, sl.np_geom)
                 sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and pose: the same origin, the same bytes)
+                self._stage_dest(sl, n_valid)
                 return []
             return n_valid, nf, stage
         self._enqueue(front, seed, tag, cloud_base, pose=pose, gt=gt, frame=frame, rig=rig)
+
+    def _stage_dest(self, sl, n_valid):
+        """label_images / annotated_images: a valid frame's images lie where its crop does; a padding cloud writes none."""
+        if self.opts.label_images or self.opts.annotated_images:
+            sl.np_dest[:n_valid] = sl.np_geom[:n_valid, 0]
+            sl.np_dest[n_valid:] = -1
 
     def _enqueue(self, front, seed, tag, cloud_base, **side):
         """What submit() and submit_depth() share.  front() checks the front end's arguments and capacity (ValueError) and returns
@@ -833,7 +859,7 @@ class AncshPipeline(object):
         self._submitted += 1
         self._inflight.append((sl, tag, seed, n_valid))
 
-    def retire(self, flags=False, articulation=False, dense=False, label_images=False, link_counts=False):
+    def retire(self, flags=False, articulation=False, dense=False, label_images=False, link_counts=False, annotated_images=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
         records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
         the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph; built with
@@ -851,17 +877,21 @@ class AncshPipeline(object):
         pipeline built with label_images=True): + a list with one (labels (h, w) int32, values (h, w, 7) float32) pair per valid frame,
         aligned with the submitted crop, behind the articulation block and in front of the counts: a valid pixel holds its row's label and
         [W of the label | part NOCS | NAOCS] (as dense), every other pixel -1 / NaN (flagged clouds: the f32 graph's images).
-        The tuple's order is stream.RESULT_ORDER (stream.unpack_results reads it by name).  link_counts=True (a pipeline of annotated
+        The tuple's order is stream.RESULT_NAMES (stream.unpack_results reads it by name).  link_counts=True (a pipeline of annotated
         depth frames: depth_capacity with point_ground_truth=True, build_point_gt=True): + the (n_valid, 16) int32 valid pixels per link
-        of the batch's frames, behind everything else."""
+        of the batch's frames, behind everything else.  annotated_images=True (a pipeline of annotated frames built with
+        annotated_images=True): + a list with one (labels (h, w) int32, values (h, w, 7) float32, gt_labels (h, w) int32, gt_values (h, w, 6)
+        float32) tuple per valid frame, aligned with the submitted (or rendered) crop, where label_images' pairs would stand: a valid pixel
+        holds its row's predicted label and [W of the label | part NOCS | NAOCS], its row's ground-truth part and [part NOCS | NAOCS];
+        every other pixel, and every pixel of a frame without rows, -1 / NaN (flagged clouds: the f32 graph's images)."""
         check_built_with(self.opts, "retire", "AncshPipeline", articulation=articulation, dense=dense, label_images=label_images,
-                         link_counts=link_counts)
+                         annotated_images=annotated_images, link_counts=link_counts)
         if not self._inflight:
             raise RuntimeError("retire(): no batch in flight")
         sl, tag, seed, n_valid = self._inflight.popleft()
         sl.d2h_done.synchronize()
-        asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, counts=self.opts.depth_dtype is not None,
-                     link_counts=link_counts)
+        asked = dict(flags=flags, articulation=articulation, dense=dense, label_images=label_images, annotated_images=annotated_images,
+                     counts=self.opts.depth_dtype is not None, link_counts=link_counts)
         # the flag words decide the refit whether or not the caller asked for them
         want = [o for o in sl.outputs.values() if o.name in ("record", "flags") or asked.get(o.name)]
         got = {o.name: o.value(sl, n_valid) for o in want}
@@ -898,13 +928,15 @@ class AncshPipeline(object):
         yield from pump(batches, self._inflight, len(self.slots), submit, lambda: self.retire(flags, articulation, dense))
 
     def stream_depth_batches(self, batches, cameras=None, depth_scale=1.0, flags=False, articulation=False, label_images=False,
-                             link_counts=False):
+                             link_counts=False, annotated_images=False):
         """stream_batches over submit_depth: batches yields (frames, norm_factors) or (frames, norm_factors, tag) or, with a dict as the
         last item, per-batch overrides of submit_depth's cameras / depth_scale / seed / cloud_base / gt / scene / frame / rig (annotated
         frames travel with their scene and rig there); yields what retire() returns, in
         submission order, the valid-pixel counts last (label_images=True: the per-frame image pairs in front of them; link_counts=True,
-        annotated frames: the (n_valid, 16) per-link counts behind them)."""
-        check_built_with(self.opts, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images)
+        annotated frames: the (n_valid, 16) per-link counts behind them; annotated_images=True, annotated frames: the per-frame image
+        4-tuples where label_images' pairs would stand)."""
+        check_built_with(self.opts, "stream_depth_batches", "AncshPipeline", articulation=articulation, label_images=label_images,
+                         annotated_images=annotated_images)
 
         def submit(k, item):
             item = tuple(item)
@@ -914,14 +946,16 @@ class AncshPipeline(object):
                 item = item[:-1]
             self.submit_depth(item[0], item[1], tag=item[2] if len(item) > 2 else k, **kw)
         yield from pump(batches, self._inflight, len(self.slots), submit,
-                        lambda: self.retire(flags, articulation, label_images=label_images, link_counts=link_counts))
+                        lambda: self.retire(flags, articulation, label_images=label_images, link_counts=link_counts,
+                                            annotated_images=annotated_images))
 
-    def stream_render_batches(self, batches, flags=False, articulation=False, link_counts=False):
+    def stream_render_batches(self, batches, flags=False, articulation=False, link_counts=False, annotated_images=False):
         """stream_depth_batches over submit_render: batches yields (crops, norm_factors, {render=, scene=, rig=, gt=, frame=, seed=,
         cloud_base=}) or the same with a tag behind the dict (the tag defaults to the batch's index); yields what stream_depth_batches
         yields for the same frames, in submission order: the valid-pixel counts last, link_counts=True: the (n_valid, 16) per-link
-        counts behind them."""
-        check_built_with(self.opts, "stream_render_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts)
+        counts behind them; annotated_images=True: the per-frame image 4-tuples in front of the counts."""
+        check_built_with(self.opts, "stream_render_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts,
+                         annotated_images=annotated_images)
 
         def submit(k, item):
             item = tuple(item)
@@ -929,13 +963,14 @@ class AncshPipeline(object):
                 raise ValueError("a stream_render_batches item is (crops, norm_factors, {render=, scene=, rig=, ...}[, tag])")
             self.submit_render(item[0], item[1], tag=item[3] if len(item) > 3 else k, **item[2])
         yield from pump(batches, self._inflight, len(self.slots), submit,
-                        lambda: self.retire(flags, articulation, link_counts=link_counts))
+                        lambda: self.retire(flags, articulation, link_counts=link_counts, annotated_images=annotated_images))
 
-    def stream_posed_batches(self, batches, flags=False, articulation=False, link_counts=False):
+    def stream_posed_batches(self, batches, flags=False, articulation=False, link_counts=False, annotated_images=False):
         """stream_render_batches over submit_posed: batches yields (crops, norm_factors, {pose=, rig=, gt=, frame=, seed=, cloud_base=}) or
         the same with a tag behind the dict (the tag defaults to the batch's index); yields what stream_render_batches yields for the same
         frames."""
-        check_built_with(self.opts, "stream_posed_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts)
+        check_built_with(self.opts, "stream_posed_batches", "AncshPipeline", articulation=articulation, link_counts=link_counts,
+                         annotated_images=annotated_images)
 
         def submit(k, item):
             item = tuple(item)
@@ -943,4 +978,4 @@ class AncshPipeline(object):
                 raise ValueError("a stream_posed_batches item is (crops, norm_factors, {pose=, rig=, ...}[, tag])")
             self.submit_posed(item[0], item[1], tag=item[3] if len(item) > 3 else k, **item[2])
         yield from pump(batches, self._inflight, len(self.slots), submit,
-                        lambda: self.retire(flags, articulation, link_counts=link_counts))
+                        lambda: self.retire(flags, articulation, link_counts=link_counts, annotated_images=annotated_images))

@@ -12,7 +12,7 @@ from .pose import gt_errors, joint_params, point_gt, quality
 
 # ---- the slot header ---------------------------------------------------------------------------------------------------------
 # [seed (int64 bits) -- keyed: the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) -- | offsets (B+1) int32 |
-#  norm factors (B) float32 | depth: geom (B x GEOM_WORDS) int32 | cam (B x CAM_WORDS) float32 | label_images: dest (B) int32]
+#  norm factors (B) float32 | depth: geom (B x GEOM_WORDS) int32 | cam (B x CAM_WORDS) float32 | label_images / annotated_images: dest (B) int32]
 # The kernels read it through the pointers AncshPipeline._sample passes: the order is theirs, not this module's to change.
 HeaderLayout = collections.namedtuple("HeaderLayout", "key seed base off nf geom cam dest words")
 
@@ -64,6 +64,11 @@ def take_dense(host, sl, n_valid, n):
 def take_images(host, sl, n_valid, n):
     from .depth import cut_label_images
     return cut_label_images(host[0].numpy()[:n], host[1].numpy()[:n], [(int(g[1]), int(g[2])) for g in sl.np_geom[:n_valid]])
+
+
+def take_annotated_images(host, sl, n_valid, n):
+    from .depth import cut_annotated_images
+    return cut_annotated_images(*(h.numpy()[:n] for h in host), [(int(g[1]), int(g[2])) for g in sl.np_geom[:n_valid]])
 
 
 # ... and how the f32 refit's value replaces the flagged clouds' part of it
@@ -292,7 +297,7 @@ def check_joint_source(joint_source):
 
 
 Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
-                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images link_counts render posed "
+                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed "
                                  "coord_regress_loss record_width record_key art_width rows inputs")
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
@@ -300,7 +305,7 @@ OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # th
 def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw_capacity=None, depth_capacity=None, depth_dtype="uint16",
                   keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
                   ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
-                  coord_regress_loss="L2", build_gt_pose=False, render_mesh=None, kinematics=None):
+                  coord_regress_loss="L2", build_gt_pose=False, render_mesh=None, kinematics=None, annotated_images=False):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
     (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
     width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
@@ -312,7 +317,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     kinematics (with render_mesh): the step builds the render and scene tables itself from this table (depth.pack_kinematics) and one pose
     per frame, so `pose` (POSE_INPUT) takes the place of the `render` and `scene` inputs.
     A library: render_mesh = depth.pack_mesh_library's 4 arrays, alone (submit_render: the instance of a frame in render[9]) or with kinematics
-    = the (ninst, 672) stack of its instances' tables (submit_posed: in pose[28]); the two counts must agree."""
+    = the (ninst, 672) stack of its instances' tables (submit_posed: in pose[28]); the two counts must agree.
+    annotated_images (annotated depth frames only, rendered and posed ones included): the step carries every row's prediction and ground
+    truth back to the pixel it came from -- the link-major twin of label_images, which stays refused there."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -353,7 +360,13 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     link_counts = depth_capacity is not None and bool(build_point_gt)      # annotated depth frames
     if link_counts and label_images:
         raise ValueError("label_images=True carries rows back to pixels in pixel order; the rows of annotated depth frames "
-                         "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them")
+                         "(point_ground_truth=True, build_point_gt=True) are link-major: pass one of them (annotated_images=True gives "
+                         "such frames their predicted and ground-truth images)")
+    if annotated_images and not link_counts:
+        raise ValueError("annotated_images=True carries the predictions and the ground truth of annotated depth frames back to their pixels: "
+                         "it needs " + ", ".join(["depth_capacity=<pixels>"] * (depth_capacity is None) +
+                                                 ["point_ground_truth=True"] * (not point_ground_truth) +
+                                                 ["build_point_gt=True"] * (not build_point_gt)))
     if render_mesh is not None and not link_counts:
         raise ValueError("render_mesh renders the annotated depth frames of the step on the device: it needs " + RENDERED.rsplit(", ", 1)[0])
     if kinematics is not None and render_mesh is None:
@@ -390,7 +403,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), link_counts, render_mesh is not None, kinematics is not None, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
+                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, coord_regress_loss, width, key, 20 if joint_states else 12, rows, ())
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +
@@ -401,14 +414,18 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
 # ---- what retire() returns ---------------------------------------------------------------------------------------------------
 RESULT_ORDER = ("tag", "seed", "record", "flags", "articulation", "dense", "label_images", "counts", "link_counts")
 RESULT_ALWAYS = RESULT_ORDER[:3]
+# RESULT_ORDER with the annotated frames' images directly behind label_images (a pipeline has one of the two, never both).  RESULT_ORDER
+# itself stays the nine names its users have always compared it with; every helper below goes by RESULT_NAMES.
+RESULT_NAMES = RESULT_ORDER[:RESULT_ORDER.index("label_images") + 1] + ("annotated_images",) + RESULT_ORDER[RESULT_ORDER.index("label_images") + 1:]
 BUILT_WITH = dict(articulation="articulation=True", dense="dense=True", label_images="depth_capacity=<pixels>, label_images=True",
+                  annotated_images="depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, annotated_images=True",
                   link_counts="depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True")
 
 
 def result_names(**asked):
-    """The names of retire()'s tuple, in its order: tag, seed, record, then those of flags / articulation / dense / label_images /
-    counts that are asked for (counts: always, on a depth pipeline)."""
-    return [k for k in RESULT_ORDER if k in RESULT_ALWAYS or asked.get(k)]
+    """The names of retire()'s tuple, in its order (RESULT_NAMES): tag, seed, record, then those of flags / articulation / dense /
+    label_images / annotated_images / counts / link_counts that are asked for (counts: always, on a depth pipeline)."""
+    return [k for k in RESULT_NAMES if k in RESULT_ALWAYS or asked.get(k)]
 
 
 def pack_results(named, **asked):
@@ -427,7 +444,7 @@ def only_asked(**asked):
 
 def check_built_with(owner, method, cls, **asked):
     """RuntimeError when `method` is asked for an output that `owner` (a `cls`) was not built with."""
-    for name in RESULT_ORDER:
+    for name in RESULT_NAMES:
         if asked.get(name) and not getattr(owner, name):
             raise RuntimeError("%s(%s=True) needs %s(..., %s)" % (method, name, cls, BUILT_WITH[name]))
 

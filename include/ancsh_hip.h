@@ -1172,6 +1172,43 @@ int ancsh_depth_annotate_stream(int nclouds, int depth_type, const void *depth, 
                                 const int *geom, const double *scene, float *rows, long capacity, int *offsets, int *counts,
                                 int *link_counts, int *scratch, void *stream);
 
+/* The inverse of that entry's stable counting sort: what lies per ROW of an annotated frame -- the networks' label and values
+ * (ancsh_raw_point_labels over the 18-column rows, nchan = 18) and the ground truth of those rows (ancsh_point_gt_build) -- back on the
+ * pixel grid of the crops ancsh_depth_annotate_stream read: per cloud a predicted part image and 7-channel value image, and the true part
+ * image and 6-channel NOCS image, in ONE launch on the depth entries' grid and chunking.  The ABI version is unchanged; callers detect the
+ * entry by its symbol.
+ *   nclouds, depth_type, depth, link_labels, pixel_capacity, geom, scene : exactly what the ancsh_depth_annotate_stream call was given;
+ *   offsets (nclouds + 1), counts (nclouds), scratch : what that call WROTE (scratch holds the count pass's per-chunk histograms: nothing
+ *           may write it between the two calls);
+ *   labels (capacity) int32, values (capacity, 7) float32 : per row, as ancsh_raw_point_labels writes them;
+ *   gt_rows (capacity, gt_nchan) float32 : the rows of ancsh_point_gt_build (gt_nchan = 18): column 3 the part, 4..6 the part NOCS, 7..9
+ *           the NAOCS;
+ *   dest (nclouds) int32 : cloud b's images start at element dest[b] of the image buffers; dest[b] < 0 silences the cloud (the padding
+ *           clouds of a short batch alias another cloud's pixels);
+ *   img_labels (image_capacity) int32, img_values (image_capacity, 7) float32 : the predicted images;
+ *   img_gt_labels (image_capacity) int32, img_gt_values (image_capacity, 6) float32 : the true ones.
+ * For cloud b with crop h x w and dest[b] >= 0, pixel (i, j), q = dest[b] + i * w + j: the pixel is VALID by the annotate entry's rule (its
+ * label names a used link and its depth passes) and, in addition, counts[b] > 0 -- a cloud in which a used link is below the scene's
+ * minimum has no rows, and all its pixels read background.  The row of a valid pixel is the one the scatter pass gave it: r = offsets[b] +
+ * the cloud's totals of the links of smaller rank + the valid pixels of its own link in front of it in row-major order.  Valid and r <
+ * capacity, bit for bit (NaN payloads included): img_labels[q] = labels[r]; img_values[q][0..6] = values[r][0..6]; img_gt_labels[q] =
+ * (int)gt_rows[r][3], or -1 when that value is not finite; img_gt_values[q][0..5] = gt_rows[r][4..9].  Otherwise (background, hole, a
+ * link that is not used, a cloud without rows, a row cut at capacity): both labels -1 and every value channel NaN of the bit pattern
+ * ANCSH_LABEL_NAN_BITS.  Every pixel of the crop is written (no prefill needed); image elements of no cloud's crop are left untouched.  A
+ * cloud with dest[b] < 0, with a crop the annotate entry treats as empty (h < 1, w < 1, outside [0, pixel_capacity)), or with dest[b] + h *
+ * w > image_capacity writes NOTHING.  Images of different clouds must not overlap (clouds may share source pixels).  Deterministic byte
+ * for byte: each block derives its links' first rows from its own cloud's histograms and ranks its pixels with per-link wave ballots, as
+ * the scatter pass does; no atomics, no block waits for another.  Graph-capturable: the grid depends on (pixel_capacity, nclouds) only,
+ * every size is read from device memory; no host sync, no allocation.  nclouds == 0 launches nothing.  Checked before any launch: 0 <=
+ * nclouds <= 65535, depth_type, 0 <= pixel_capacity < 2^30, 0 <= capacity < 2^30 (the rows are only read: a capacity below the annotate
+ * call's cuts the rows at and beyond it), gt_nchan >= 10, 0 <= image_capacity < 2^30, null pointers, the annotate entry's three alignments
+ * (depth 16 bytes, link_labels and scene 8 bytes; the outputs need none beyond their element's). */
+int ancsh_depth_annotated_images(int nclouds, int depth_type, const void *depth, const unsigned char *link_labels, long pixel_capacity,
+                                 const int *geom, const double *scene, const int *offsets, const int *counts, const int *scratch,
+                                 const int *labels, const float *values, const float *gt_rows, int gt_nchan, long capacity,
+                                 const int *dest, int *img_labels, float *img_values, int *img_gt_labels, float *img_gt_values,
+                                 long image_capacity, void *stream);
+
 /* Depth and link-label frames of an articulated object rendered on the device: triangle meshes, one render table per frame and the depth
  * entries' geometry rows -> depth crops and label crops in exactly the buffers ancsh_depth_annotate_stream reads.  The reference renders
  * on the host, one frame at a time (tools/render_synthetic.py:180-225, pybullet's getCameraImage); pixel parity with that rasteriser is no

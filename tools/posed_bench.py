@@ -15,9 +15,14 @@ position -- and mixes them within every batch (frame f of batch b shows instance
 entries.  --library takes that path for --instances 1 too: the same work through the library's code.  --idle-tess T appends one more instance
 of T quads per edge that no frame shows: it only raises Tmax, the size of the raster grid, so every frame launches idle waves up to it --
 leg r, the renderer alone on one batch (HIP events around --calls calls), and leg d with and without it give what those waves cost.
+--images: what annotated_images=True costs.  The timed legs are then the posed stream three ways, alternated in one process: d as above; j
+on a pipeline built with annotated_images=True whose stream does not ask for the images (the step's two more launches and the images'
+device-to-host copies are paid, the host never touches them); i on that pipeline with stream_posed_batches(..., annotated_images=True) (the
+host also cuts every batch's four image buffers into per-frame arrays); and the option's two launches alone, HIP events around each in an
+eager step of the same pipeline (three lead launches of the entry in front of the timed one).
 Prints one JSON line: a record, not a gate.
 
-    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8] [--instances 1] [--library] [--idle-tess 0]
+    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8] [--instances 1] [--library] [--idle-tess 0] [--images]
 """
 import argparse
 import json
@@ -86,6 +91,7 @@ def main():
     ap.add_argument("--instances", type=int, default=1, help="instances mixed within every batch; above 1: a library through the *_lib entries")
     ap.add_argument("--library", action="store_true", help="take the library's path for --instances 1 too")
     ap.add_argument("--idle-tess", type=int, default=0, help="append an instance of this many quads per edge that no frame shows (a library only)")
+    ap.add_argument("--images", action="store_true", help="time the posed stream with and without annotated_images=True (legs d, j, i)")
     args = ap.parse_args()
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
@@ -159,8 +165,9 @@ def main():
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
-    rendered = AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
+    rendered = None if args.images else AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
     posed = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, **kw).prepare()
+    imaged = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, annotated_images=True, **kw).prepare() if args.images else None
     torch.cuda.synchronize()
 
     def packed_in_the_loop(passes):
@@ -171,24 +178,44 @@ def main():
 
     def leg(name, passes):
         t0, n = time.perf_counter(), 0
+        poses = (pbatches[k] for _ in range(passes) for k in range(len(pbatches)))
         gen = (rendered.stream_render_batches(tbatches[k] for _ in range(passes) for k in range(len(tbatches))) if name == "b" else
                rendered.stream_render_batches(packed_in_the_loop(passes)) if name == "c" else
-               posed.stream_posed_batches(pbatches[k] for _ in range(passes) for k in range(len(pbatches))))
+               posed.stream_posed_batches(poses) if name == "d" else imaged.stream_posed_batches(poses, annotated_images=name == "i"))
         for _ in gen:
             n += 1
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0) / n          # ms per batch of B frames, steady state over the slots
 
-    for name in "bcd":                                        # warm-up: every slot replayed with real input
+    legs = "dji" if args.images else "bcd"
+    for name in legs:                                         # warm-up: every slot replayed with real input
         leg(name, 1)
-    ms = {name: [] for name in "bcd"}
+    ms = {name: [] for name in legs}
     for _ in range(args.rounds):
-        for name in "bcd":
+        for name in legs:
             ms[name].append(leg(name, args.passes))
     med = {k: float(np.median(v)) for k, v in ms.items()}
     op = float(np.median(op_ms))
+    two = {"ancsh_raw_point_labels": [], "ancsh_depth_annotated_images": []}
+    if args.images:                                           # the two launches alone: an eager step, events around every ABI call
+        from articulated_pose_amd import _lib
+        eager = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, annotated_images=True, use_graph=False, **dict(kw, slots=1))
+        for k in range(args.rounds + 3):
+            if k >= 2:                                        # two passes warm up
+                _lib.profile_start(lead_for={name: 3 for name in two})
+            eager.submit_posed(pbatches[0][0], pbatches[0][1], **pbatches[0][2])
+            for name, _, call_ms in (_lib.profile_stop() if k >= 2 else ()):
+                if name in two:
+                    two[name].append(call_ms)
+            eager.retire()
+    ratios = (dict(j_over_d=round(med["j"] / med["d"], 4), i_over_d=round(med["i"] / med["d"], 4), images_ms_per_batch=round(med["i"] - med["d"], 4),
+                   images_d2h_bytes_per_batch=60 * cap, images_pinned_bytes=60 * cap * args.slots,
+                   images_launch_us={k: round(1e3 * float(np.median(v)), 2) for k, v in two.items()},
+                   images_launch_us_rounds={k: [round(1e3 * x, 2) for x in v] for k, v in two.items()}) if args.images else
+              dict(d_over_b=round(med["d"] / med["b"], 4), d_over_c=round(med["d"] / med["c"], 4)))
     print(json.dumps({"metric": "frames/s: the rendered stream with tables packed before the clock (b) and inside the loop (c) vs the posed stream (d); "
-                                "the host packers (a) and the two new entries alone (e)",
+                                "the host packers (a) and the two new entries alone (e); --images: the posed stream (d) vs the same stream built "
+                                "with annotated_images=True, not asked for (j) and asked for (i)",
                       "device": torch.cuda.get_device_name(0), "host_pack_us_per_frame": {k: round(v, 1) for k, v in pack_us.items()},
                       "host_pack_frames_per_s_one_core": round(1e6 / sum(pack_us.values()), 1),
                       "entries_us_per_batch": round(1e3 * op, 2), "entries_us_per_batch_rounds": [round(1e3 * x, 2) for x in op_ms],
@@ -196,7 +223,7 @@ def main():
                       "render_us_per_batch": round(1e3 * float(np.median(render_ms)), 2), "render_us_per_batch_rounds": [round(1e3 * x, 2) for x in render_ms],
                       "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
                       "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()},
-                      "d_over_b": round(med["d"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
+                      **ratios,
                       "h2d_bytes_per_batch_b": B * (4 * D.GEOM_WORDS + 8 * D.RENDER_WIDTH + 8 * D.SCENE_WIDTH),
                       "h2d_bytes_per_batch_d": B * (4 * D.GEOM_WORDS + 8 * D.POSE_WIDTH),
                       "max_abs_device_minus_host_tables": parity, "triangles": int(mesh[1].shape[0]), "vertices": int(mesh[0].shape[0]),
