@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void input_sample_kernel(int num_points, int n
 }
 
 // ---- the streaming sampler: graph-capturable, every size read from device memory (include/ancsh_hip.h) -------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {     // the pose generator's finaliser (pose.hip)
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {     // the pose generator's finaliser (pose_shared.h)
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;

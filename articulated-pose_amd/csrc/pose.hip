@@ -1,15 +1,13 @@
 // pose.hip -- batched pose fitting for gfx950: per-part RANSAC similarity fit (stage A), per-joint
-// RANSAC with articulated Levenberg-Marquardt refinement (stage B), their full-inlier refits, part
-// partitioning, joint-direction medians and Umeyama alignment.
+// RANSAC with articulated Levenberg-Marquardt refinement (stage B) and their full-inlier refits.  Part
+// partitioning, joint-direction medians and Umeyama alignment are in pose_glue.hip.
 //
 // Reference (all host Python, one process per CPU core, ~10 s per cloud):
 //   evaluation/parallel_ancsh_pose.py:20-33    ransac
 //   evaluation/parallel_ancsh_pose.py:35-54    single_transformation_{estimator,verifier}
 //   evaluation/parallel_ancsh_pose.py:56-68    objective_eval
 //   evaluation/parallel_ancsh_pose.py:106-194  joint_transformation_{estimator,verifier}
-//   evaluation/parallel_ancsh_pose.py:238-341  per-cloud orchestration
 //   lib/d3_utils.py:150-163,206-246            Rodrigues, Kabsch, transform_pts, scale_pts
-//   lib/aligning.py:580-622                    estimateSimilarityUmeyama
 //
 // CDNA4 mapping (this is ALU/latency-bound work on <= 24 KB of points per part, not HBM-bound):
 //   * hypotheses are the parallel axis: one lane = one hypothesis.  The part's points sit in LDS; every
@@ -25,6 +23,7 @@
 #include "common.h"
 #include "pose_math.h"
 #include "umeyama_fit.h"
+#include "pose_shared.h"
 
 namespace ancsh {
 namespace pose {
@@ -32,16 +31,6 @@ namespace pose {
 constexpr int MODEL_A = 13;   // R(9) s t(3)
 constexpr int MODEL_B = 26;   // R0(9) s0 t0(3) R1(9) s1 t1(3)
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ int device_draw(unsigned long long seed, int prob, int iter, int k, int n) {
-    const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)prob << 40) ^ ((unsigned long long)iter << 8) ^ (unsigned)k));
-    return (int)(h % (unsigned long long)n);
-}
 // The generator key of a sampling kernel, by key mode KM:
 //   KEY_VALUE (the by-value entries): `arg` is the key itself;
 //   KEY_DSEED (the *_dseed entries): `arg` is the address of a uint64 in device memory, read here once per kernel -- a captured graph
@@ -1723,395 +1712,17 @@ __global__ __launch_bounds__(256) void ransac_joint_finish_kind_kernel(const int
                                            out_score, E, smem);
 }
 
-// ================================ glue kernels =====================================================
-// labels = argmax(W, axis=1) (first maximum wins, np.argmax); ordered partition of the cloud's points
-// by label; gather of the per-part source (own part-NOCS slot) / target (camera point) arrays
-// (evaluation/parallel_ancsh_pose.py:238-242,259-260).
-__global__ __launch_bounds__(256) void partition_kernel(int n, int K, const float *__restrict__ W, const float *__restrict__ P,
-                                                        const float *__restrict__ nocs, int *__restrict__ labels,
-                                                        int *__restrict__ part_index, int *__restrict__ off,
-                                                        float *__restrict__ src, float *__restrict__ tgt,
-                                                        int *__restrict__ counts, int *__restrict__ rng0, int *__restrict__ rng1) {
-    __shared__ int wcnt[4];
-    __shared__ int part_start[17];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float *Wb = W + (size_t)b * n * K;
-    int base = 0;
-    for (int j = 0; j < K; ++j) {
-        if (threadIdx.x == 0) { off[b * K + j] = b * n + base; part_start[j] = b * n + base; }
-        for (int c0 = 0; c0 < n; c0 += 256) {
-            const int i = c0 + threadIdx.x;
-            bool f = false;
-            if (i < n) {
-                int lab = 0;
-                float bv = Wb[(size_t)i * K];
-                for (int k = 1; k < K; ++k) {
-                    const float v = Wb[(size_t)i * K + k];
-                    if (v > bv) { bv = v; lab = k; }
-                }
-                f = lab == j;
-                if (f && labels) labels[(size_t)b * n + i] = lab;
-            }
-            const unsigned long long m = __ballot(f);
-            __syncthreads();
-            if (lane == 0) wcnt[wave] = __popcll(m);
-            __syncthreads();
-            int start = base;
-            for (int w = 0; w < wave; ++w) start += wcnt[w];
-            if (f) {
-                const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                const size_t row = (size_t)b * n + pos;
-                part_index[row] = i;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    src[row * 3 + c] = nocs[((size_t)b * n + i) * 3 * K + 3 * j + c];
-                    tgt[row * 3 + c] = P[((size_t)b * n + i) * 3 + c];
-                }
-            }
-            base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        }
-    }
-    if (threadIdx.x == 0 && b == gridDim.x - 1) off[gridDim.x * K] = gridDim.x * n;
-    // optional by-products the joint stage consumes (:274-283): points per part and the [start, end) row ranges of part 0 /
-    // part j for every joint j = 1..K-1 -- written here instead of by slicing / stacking `off` in separate launches
-    if (threadIdx.x == 0) part_start[K] = (b + 1) * n;
-    __syncthreads();
-    if ((int)threadIdx.x < K && counts) counts[b * K + threadIdx.x] = part_start[threadIdx.x + 1] - part_start[threadIdx.x];
-    if ((int)threadIdx.x >= 1 && (int)threadIdx.x < K && rng0 && rng1) {
-        const int q = b * (K - 1) + (int)threadIdx.x - 1;
-        rng0[q * 2] = part_start[0]; rng0[q * 2 + 1] = part_start[1];
-        rng1[q * 2] = part_start[threadIdx.x]; rng1[q * 2 + 1] = part_start[threadIdx.x + 1];
-    }
-}
-
-// A cloud with a non-finite value anywhere in the fit's inputs has no defined pose (the reference's own np.linalg.svd raises
-// LinAlgError on it, np.argmax / np.median of NaN rows are arbitrary): its (K, 26) record rows become NaN, whatever the fit kernels
-// made of it -- a poisoned cloud never yields a silently finite answer.  One workgroup per cloud; axis may be NULL.
-// IDX (the predicted joint association): the (n, jc) index head is scanned as well; the plain instantiation never reads index / jc.
-template <bool IDX>
-__global__ __launch_bounds__(1024) void poison_records_kernel(int n, int K, const float *__restrict__ P, const float *__restrict__ nocs,
-                                                              const float *__restrict__ W, const float *__restrict__ axis,
-                                                              double *__restrict__ record, int jc, const float *__restrict__ index) {
-    const int b = blockIdx.x;
-    bool bad = false;
-    // 1024 threads, eight independent loads in flight per thread: the scan is a handful of memory latencies, not a per-element loop
-    const auto scan = [&](const float *p, long cnt) {
-        for (long i0 = threadIdx.x; i0 < cnt; i0 += 8 * 1024) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[i0 + u * 1024 < cnt ? i0 + u * 1024 : i0];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) bad = bad | !(fabsf(v[u]) <= 3.4028234664e38f);      // NaN and +-Inf fail the compare
-        }
-    };
-    scan(P + (size_t)b * n * 3, (long)n * 3);
-    scan(nocs + (size_t)b * n * 3 * K, (long)n * 3 * K);
-    scan(W + (size_t)b * n * K, (long)n * K);
-    if (axis) scan(axis + (size_t)b * n * 3, (long)n * 3);
-    if (IDX) scan(index + (size_t)b * n * jc, (long)n * jc);
-    if (__syncthreads_or(bad))
-        for (int i = threadIdx.x; i < K * 26; i += 1024) record[(size_t)b * K * 26 + i] = __builtin_nan("");
-}
-
-// ---- the passes of the joint-direction medians, shared by joint_direction_kernel and joint_direction_pred_kernel.  STATEMENT MACROS
-// (as csrc/part_stats.h): expanded in place they give joint_direction_kernel the instruction stream it had before the second kernel.
-// ANCSH_JD_COMPACT: ordered compaction of cloud b's points whose IS_J (a boolean expression of the point index i, evaluated only for
-// i < n) holds into three LDS columns of npow2 floats (joint_axis rows, in point order); cnt ends as their number on every thread.
-#define ANCSH_JD_COMPACT(IS_J)                                                                                                        \
-    for (int c0 = 0; c0 < n; c0 += 256) {                                                                                             \
-        const int i = c0 + threadIdx.x;                                                                                               \
-        const bool f = i < n && (IS_J);                                                                                               \
-        const unsigned long long m = __ballot(f);                                                                                     \
-        __syncthreads();                                                                                                              \
-        if (lane == 0) wcnt[wave] = __popcll(m);                                                                                      \
-        __syncthreads();                                                                                                              \
-        int start = cnt;                                                                                                              \
-        for (int w = 0; w < wave; ++w) start += wcnt[w];                                                                              \
-        if (f) {                                                                                                                      \
-            const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));       \
-            _Pragma("unroll") for (int c = 0; c < 3; ++c) vals[c * npow2 + pos] = axis[((size_t)b * n + i) * 3 + c];                 \
-        }                                                                                                                             \
-        cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];                                                                                 \
-    }
-// ANCSH_JD_MEDIAN: +inf padding to the next power of two, a bitonic sort of each column, and np.median of each (the middle element or
-// the float32 mean of the middle two; NaN without a point) into out[b, j - 1, :]
-#define ANCSH_JD_MEDIAN                                                                                                               \
-    int p2 = 1;                                                                                                                       \
-    while (p2 < cnt) p2 <<= 1;                                                                                                        \
-    for (int e = cnt + threadIdx.x; e < p2; e += 256)                                                                                 \
-        _Pragma("unroll") for (int c = 0; c < 3; ++c) vals[c * npow2 + e] = INFINITY;                                                 \
-    __syncthreads();                                                                                                                  \
-    for (int k = 2; k <= p2; k <<= 1)                                                                                                 \
-        for (int s = k >> 1; s > 0; s >>= 1) {                                                                                        \
-            for (int e = threadIdx.x; e < p2; e += 256) {                                                                             \
-                const int partner = e ^ s;                                                                                            \
-                if (partner > e) {                                                                                                    \
-                    const bool up = (e & k) == 0;                                                                                     \
-                    _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                   \
-                        float *v = vals + c * npow2;                                                                                  \
-                        const float a = v[e], bb = v[partner];                                                                       \
-                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }                                                            \
-                    }                                                                                                                 \
-                }                                                                                                                     \
-            }                                                                                                                         \
-            __syncthreads();                                                                                                          \
-        }                                                                                                                             \
-    if (threadIdx.x < 3) {                                                                                                            \
-        const float *v = vals + threadIdx.x * npow2;                                                                                  \
-        float med = NAN;                                                                                                              \
-        if (cnt > 0) med = (cnt & 1) ? v[cnt / 2] : (v[cnt / 2 - 1] + v[cnt / 2]) * 0.5f;                                             \
-        out[((size_t)b * (K - 1) + (j - 1)) * 3 + threadIdx.x] = med;                                                                 \
-    }
-
-// jt_axis = np.median(joint_axis_per_point[joint_cls == j], 0)  (:295): one workgroup per (cloud, joint)
-__global__ __launch_bounds__(256) void joint_direction_kernel(int n, int K, const float *__restrict__ axis,
-                                                              const int *__restrict__ joint_cls, float *__restrict__ out) {
-    extern __shared__ float vals[];   // 3 * npow2 floats
-    __shared__ int wcnt[4];
-    const int b = blockIdx.x, j = blockIdx.y + 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int npow2 = 1;
-    while (npow2 < n) npow2 <<= 1;
-    int cnt = 0;
-    ANCSH_JD_COMPACT(joint_cls[(size_t)b * n + i] == j)
-    ANCSH_JD_MEDIAN
-}
-
-// np.argmax of one row of jc floats: the first maximum, and the first NaN when the row holds one (numpy treats NaN as the maximum)
-__device__ __forceinline__ int np_argmax_row(const float *r, int jc) {
-    int c = 0;
-    float best = r[0];
-    for (int k = 1; k < jc && best == best; ++k) {
-        const float v = r[k];
-        if (!(v <= best)) { best = v; c = k; }     // v > best, or v is NaN
-    }
-    return c;
-}
-
-// jt_axis = np.median(joint_axis_per_point[np.argmax(index_per_point, 1) == j], 0)  (lib/parallel_ancsh_pose.py:339-343,366): the joint
-// association from the ANCSH network's index head (jc channels per point) instead of a label array, the argmax taken while compacting --
-// the bytes of joint_direction_kernel fed np.argmax(index, -1).  One workgroup per (cloud, joint).
-__global__ __launch_bounds__(256) void joint_direction_pred_kernel(int n, int K, int jc, const float *__restrict__ axis,
-                                                                   const float *__restrict__ index, float *__restrict__ out) {
-    extern __shared__ float vals[];   // 3 * npow2 floats
-    __shared__ int wcnt[4];
-    const int b = blockIdx.x, j = blockIdx.y + 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int npow2 = 1;
-    while (npow2 < n) npow2 <<= 1;
-    int cnt = 0;
-    ANCSH_JD_COMPACT(np_argmax_row(index + ((size_t)b * n + i) * jc, jc) == j)
-    ANCSH_JD_MEDIAN
-}
-
-// estimateSimilarityUmeyama (lib/aligning.py:580-622) for a batch of (source, target) point sets, float64.
-// out (nprob, 29): Scales(3) | Rotation(9, the reference's TRANSPOSED matrix) | Translation(3) | OutTransform(4x4 row-major minus last row -> 12) ... see header
-#define UMK_SRC(i, c) src[(size_t)(r0 + (i)) * 3 + (c)]
-#define UMK_TGT(i, c) tgt[(size_t)(r0 + (i)) * 3 + (c)]
-__global__ __launch_bounds__(256) void umeyama_kernel(const int *__restrict__ off, const float *__restrict__ src,
-                                                      const float *__restrict__ tgt, double *__restrict__ out) {
-    __shared__ double red[64];
-    const int prob = blockIdx.x, r0 = off[prob], n = off[prob + 1] - r0;
-    double *o = out + (size_t)prob * 32;
-    if (n <= 0) {
-        if (threadIdx.x < 32) o[threadIdx.x] = NAN;
-        return;
-    }
-    ANCSH_UMEYAMA_SUMS(n, UMK_SRC, UMK_TGT, red)        // the arithmetic is stated in umeyama_fit.h, for this kernel and gt_pose_kernel
-    if (threadIdx.x != 0) return;
-    ANCSH_UMEYAMA_SOLVE(n, o)
-}
-
-
-// estimateSimilarityTransform (lib/aligning.py:17-32): 5-point Umeyama RANSAC (getRANSACInliers :485-507 with
-// evaluateModel :540-547 and set_config :88-103), <= 100 iterations with the reference's SEQUENTIAL early stop,
-// then Umeyama on the winner's inliers.  One workgroup per problem: thread h evaluates hypothesis h against all
-// points (every hypothesis is independent), thread 0 then replays the reference's in-order bookkeeping
-// (strictly-better inlier ratio wins; stop as soon as the best residual drops under StopThreshold) to find which
-// hypothesis the sequential loop would have kept; the workgroup refits on its inliers.
-// Quirk kept: nInliers = np.count_nonzero(InlierIdx) counts non-zero INDICES, so point 0 never counts (:544).
-__device__ __forceinline__ void umeyama_small(const double (*s)[3], const double (*t)[3], int n, double T[12]) {
-    double sm[3] = {0, 0, 0}, tm[3] = {0, 0, 0};
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { sm[c] += s[i][c]; tm[c] += t[i][c]; }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { sm[c] /= n; tm[c] /= n; }
-    double M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
-    for (int i = 0; i < n; ++i) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) M[a * 3 + b] += (t[i][a] - tm[a]) * (s[i][b] - sm[b]);
-            var += (s[i][a] - sm[a]) * (s[i][a] - sm[a]);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) M[a] /= n;
-    var /= n;
-    double q[4], R[9];
-    horn_quat(M, q);
-    quat_to_mat(q, R);
-    double tr = 0.0;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) tr += R[a] * M[a];
-    const double sc = tr / var;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) T[a * 4 + b] = sc * R[a * 3 + b];
-        T[a * 4 + 3] = tm[a] - sc * (R[a * 3] * sm[0] + R[a * 3 + 1] * sm[1] + R[a * 3 + 2] * sm[2]);
-    }
-}
-
-__global__ __launch_bounds__(128) void ransac_umeyama5_kernel(const int *__restrict__ off, const float *__restrict__ src,
-                                                              const float *__restrict__ tgt, int niter,
-                                                              const int *__restrict__ draws, unsigned long long seed,
-                                                              double *__restrict__ out, int *__restrict__ status) {
-    __shared__ double red[64];
-    __shared__ double h_res[128], h_ratio[128];
-    __shared__ double Tsel[12];
-    __shared__ double thr[2];
-    __shared__ int sel;
-    const int prob = blockIdx.x, r0 = off[prob], n = off[prob + 1] - r0, h = threadIdx.x;
-    double *o = out + (size_t)prob * 32;
-    if (n <= 0 || niter > 128) {
-        if (h < 32) o[h] = NAN;
-        if (h == 0) status[prob] = -1;
-        return;
-    }
-    // set_config: PassT = max(TargetNorm/SourceNorm, SourceNorm/TargetNorm) of the mean point norms; StopT = PassT/100
-    double nm[2] = {0, 0};
-    for (int i = h; i < n; i += 128) {
-        const float *ps = src + (size_t)(r0 + i) * 3, *pt = tgt + (size_t)(r0 + i) * 3;
-        nm[0] += sqrt((double)ps[0] * ps[0] + (double)ps[1] * ps[1] + (double)ps[2] * ps[2]);
-        nm[1] += sqrt((double)pt[0] * pt[0] + (double)pt[1] * pt[1] + (double)pt[2] * pt[2]);
-    }
-    block_sum<2>(nm, red, 2);
-    if (h == 0) {
-        const double ts = (nm[1] / n) / (nm[0] / n), st = (nm[0] / n) / (nm[1] / n);
-        thr[0] = st > ts ? st : ts;
-        thr[1] = thr[0] / 100.0;
-    }
-    __syncthreads();
-    const double passT = thr[0], stopT = thr[1];
-    double T[12];
-    if (h < niter) {
-        double s5[5][3], t5[5][3];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            int v = draws ? draws[((size_t)prob * niter + h) * 5 + k] : device_draw(seed, prob, h, k, n);
-            v = v < 0 ? 0 : (v >= n ? n - 1 : v);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { s5[k][c] = src[(size_t)(r0 + v) * 3 + c]; t5[k][c] = tgt[(size_t)(r0 + v) * 3 + c]; }
-        }
-        umeyama_small(s5, t5, 5, T);
-        double rs = 0.0;
-        int cnt = 0;
-        for (int i = 0; i < n; ++i) {
-            const float *ps = src + (size_t)(r0 + i) * 3, *pt = tgt + (size_t)(r0 + i) * 3;
-            double e2 = 0.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double e = (double)pt[a] - (T[a * 4] * ps[0] + T[a * 4 + 1] * ps[1] + T[a * 4 + 2] * ps[2] + T[a * 4 + 3]);
-                e2 += e * e;
-            }
-            rs += e2;                                   // Residual = norm(ResidualVec) = sqrt(sum of squared norms)
-            if (sqrt(e2) < passT && i != 0) ++cnt;      // count_nonzero(InlierIdx): index 0 is never counted
-        }
-        h_res[h] = sqrt(rs);
-        h_ratio[h] = (double)cnt / (double)n;
-    }
-    __syncthreads();
-    if (h == 0) {
-        double bestRes = 1e10, bestRatio = 0.0;
-        int best = -1;                                   // -1: BestInlierIdx stays arange(n)
-        for (int i = 0; i < niter; ++i) {
-            if (h_ratio[i] > bestRatio) { bestRes = h_res[i]; bestRatio = h_ratio[i]; best = i; }
-            if (bestRes < stopT) break;
-        }
-        sel = best;
-        thr[0] = bestRatio;
-    }
-    __syncthreads();
-    const int best = sel;
-    const double bestRatio = thr[0];
-    if (best >= 0 && h == best)
-#pragma unroll
-        for (int a = 0; a < 12; ++a) Tsel[a] = T[a];
-    __syncthreads();
-    if (bestRatio < 0.1) {                              // "[ WARN ] - Something is wrong. Small BestInlierRatio" -> 4 x None
-        if (h < 32) o[h] = NAN;
-        if (h == 0) status[prob] = 1;
-        return;
-    }
-    // Umeyama over the winner's inliers (true inliers INCLUDING index 0: InlierIdx[0] holds it)
-    double sums[7] = {0, 0, 0, 0, 0, 0, 0};
-    auto is_in = [&](int i) {
-        if (best < 0) return true;
-        const float *ps = src + (size_t)(r0 + i) * 3, *pt = tgt + (size_t)(r0 + i) * 3;
-        double e2 = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double e = (double)pt[a] - (Tsel[a * 4] * ps[0] + Tsel[a * 4 + 1] * ps[1] + Tsel[a * 4 + 2] * ps[2] + Tsel[a * 4 + 3]);
-            e2 += e * e;
-        }
-        return sqrt(e2) < passT;
-    };
-    for (int i = h; i < n; i += 128)
-        if (is_in(i)) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { sums[c] += src[(size_t)(r0 + i) * 3 + c]; sums[3 + c] += tgt[(size_t)(r0 + i) * 3 + c]; }
-            sums[6] += 1.0;
-        }
-    block_sum<7>(sums, red, 2);
-    const double m = sums[6];
-    double sm[3], tm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { sm[c] = sums[c] / m; tm[c] = sums[3 + c] / m; }
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = h; i < n; i += 128)
-        if (is_in(i)) {
-            double sc[3], tc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { sc[c] = src[(size_t)(r0 + i) * 3 + c] - sm[c]; tc[c] = tgt[(size_t)(r0 + i) * 3 + c] - tm[c]; }
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) acc[a * 3 + b] += tc[a] * sc[b];
-            acc[9] += sc[0] * sc[0] + sc[1] * sc[1] + sc[2] * sc[2];
-        }
-    block_sum<10>(acc, red, 2);
-    if (h != 0) return;
-    double M[9], q[4], R[9];
-#pragma unroll
-    for (int a = 0; a < 9; ++a) M[a] = acc[a] / m;
-    horn_quat(M, q);
-    quat_to_mat(q, R);
-    double trace = 0.0;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) trace += R[a] * M[a];
-    const double s = trace / (acc[9] / m);
-    o[0] = o[1] = o[2] = s;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) o[3 + a * 3 + b] = R[b * 3 + a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double Tv = tm[a] - s * (R[a * 3] * sm[0] + R[a * 3 + 1] * sm[1] + R[a * 3 + 2] * sm[2]);
-        o[12 + a] = Tv;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) o[15 + a * 4 + b] = s * R[a * 3 + b];
-        o[15 + a * 4 + 3] = Tv;
-    }
-    o[27] = 0; o[28] = 0; o[29] = 0; o[30] = 1; o[31] = bestRatio;
-    status[prob] = 0;
-}
-
 }  // namespace pose
 }  // namespace ancsh
 
 using namespace ancsh;
 using namespace ancsh::pose;
+
+// ================================ the host side =====================================================
+// The nineteen fit entries of include/ancsh_hip.h -- ancsh_ransac_single{,_ex,_rec,_rec_dseed,_rec_dkey}, ancsh_ransac_joint{,_ex,_rec,
+// _rec_dseed,_rec_dkey,_rec_kind,_rec_dseed_kind,_rec_dkey_kind} and ancsh_pose_fit_rec{,_dseed,_dkey}{,_kind} -- are adapters: each
+// fills a FitCall from its parameters and hands it to pose_fit(), which runs every argument check of the stages that are present and
+// then, through one switch on the key mode, the launches.  A new argument of the fit is a new field, read where it is needed.
 
 // T = min{x >= 0 : sqrt(x) >= th} in the given precision (host libm sqrt is correctly rounded, like the
 // reference's numpy sqrt), so that  sqrt(s) < th  <=>  s < T  exactly.
@@ -2128,91 +1739,52 @@ static double sq_threshold_f64(double th) {
     return t;
 }
 
-extern "C" int ancsh_pose_partition(int b, int n, int K, const float *W, const float *P, const float *nocs, int *labels,
-                                    int *part_index, int *off, float *src, float *tgt, int *counts, int *rng0, int *rng1,
-                                    void *stream) {
-    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 16, "pose_partition: bad shape b=%d n=%d K=%d", b, n, K);
-    if (b == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(W && P && nocs && part_index && off && src && tgt, "pose_partition: null pointer");
-    ANCSH_REQUIRE((rng0 == nullptr) == (rng1 == nullptr), "pose_partition: rng0 and rng1 go together");
-    hipLaunchKernelGGL(partition_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, n, K, W, P, nocs, labels, part_index, off,
-                       src, tgt, counts, rng0, rng1);
-    return check_launch("pose_partition");
+// The generator key of one stage as the entry received it (key modes: KeyArg above).  KEY_VALUE: `value`; KEY_DSEED / KEY_DKEY: `dev`, a
+// uint64 / an ancsh_stream_key in device memory.
+struct FitKey { int mode; unsigned long long value; const void *dev; };
+// the 64 bits that travel by value: the key itself or the address (FitExtras.seed of stage B in every mode)
+static unsigned long long key_word(const FitKey &k) { return k.mode == KEY_VALUE ? k.value : (unsigned long long)(uintptr_t)k.dev; }
+// the kernels' key argument; parts: the stage's problems per cloud (K in stage A, K - 1 in stage B), which only KEY_DKEY reads
+template <int KM>
+static KeyArg<KM> key_arg(const FitKey &k, int parts) {
+    if constexpr (KM == KEY_DKEY) return DKey{(const ancsh_stream_key *)k.dev, parts};
+    else return key_word(k);
 }
 
-extern "C" int ancsh_pose_poison_records(int b, int n, int K, const float *P, const float *nocs, const float *W, const float *joint_axis,
-                                         double *record, void *stream) {
-    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 16, "pose_poison_records: bad shape b=%d n=%d K=%d", b, n, K);
-    if (b == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(P && nocs && W && record, "pose_poison_records: null pointer");
-    hipLaunchKernelGGL(poison_records_kernel<false>, dim3(b), dim3(1024), 0, (hipStream_t)stream, n, K, P, nocs, W, joint_axis, record, 0,
-                       nullptr);
-    return check_launch("pose_poison_records");
-}
-
-extern "C" int ancsh_pose_poison_records_pred(int b, int n, int K, const float *P, const float *nocs, const float *W,
-                                              const float *joint_axis, int joint_channels, const float *joint_index, double *record,
-                                              void *stream) {
-    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1 && K <= 16, "pose_poison_records_pred: bad shape b=%d n=%d K=%d", b, n, K);
-    ANCSH_REQUIRE(joint_channels >= 1 && joint_channels <= 64, "pose_poison_records_pred: joint_channels=%d must be in [1,64]",
-                  joint_channels);
-    ANCSH_REQUIRE(P && nocs && W && joint_index && record, "pose_poison_records_pred: null pointer");
-    if (b == 0) return ANCSH_OK;
-    hipLaunchKernelGGL(poison_records_kernel<true>, dim3(b), dim3(1024), 0, (hipStream_t)stream, n, K, P, nocs, W, joint_axis, record,
-                       joint_channels, joint_index);
-    return check_launch("pose_poison_records_pred");
-}
-
-extern "C" int ancsh_pose_joint_direction(int b, int n, int K, const float *joint_axis, const int *joint_cls, float *out,
-                                          void *stream) {
-    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 1, "pose_joint_direction: bad shape");
-    ANCSH_REQUIRE(n <= 8192, "pose_joint_direction: n %d > 8192", n);
-    if (b == 0 || K == 1) return ANCSH_OK;
-    ANCSH_REQUIRE(joint_axis && joint_cls && out, "pose_joint_direction: null pointer");
-    int npow2 = 1;
-    while (npow2 < n) npow2 <<= 1;
-    const size_t lds = (size_t)3 * npow2 * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)joint_direction_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(joint_direction_kernel, dim3(b, K - 1), dim3(256), lds, (hipStream_t)stream, n, K, joint_axis, joint_cls, out);
-    return check_launch("pose_joint_direction");
-}
-
-extern "C" int ancsh_pose_joint_direction_pred(int b, int n, int K, int joint_channels, const float *joint_axis, const float *joint_index,
-                                               float *out, void *stream) {
-    ANCSH_REQUIRE(b >= 0 && n > 0 && K >= 2 && K <= 16, "pose_joint_direction_pred: bad shape b=%d n=%d K=%d (K >= 2: a joint)", b, n, K);
-    ANCSH_REQUIRE(n <= 8192, "pose_joint_direction_pred: n %d > 8192", n);
-    ANCSH_REQUIRE(joint_channels >= 1 && joint_channels <= 64, "pose_joint_direction_pred: joint_channels=%d must be in [1,64]",
-                  joint_channels);
-    ANCSH_REQUIRE(joint_axis && joint_index && out, "pose_joint_direction_pred: null pointer");
-    if (b == 0) return ANCSH_OK;
-    int npow2 = 1;
-    while (npow2 < n) npow2 <<= 1;
-    const size_t lds = (size_t)3 * npow2 * sizeof(float);
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void *)joint_direction_pred_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(joint_direction_pred_kernel, dim3(b, K - 1), dim3(256), lds, (hipStream_t)stream, n, K, joint_channels, joint_axis,
-                       joint_index, out);
-    return check_launch("pose_joint_direction_pred");
-}
-
-static FitExtras no_extras() {
-    FitExtras E;
-    E.record = nullptr; E.K = 0; E.tie = nullptr;
-    E.lo_f = E.hi_f = 0.f; E.lo_d = E.hi_d = 0.0;      // empty window: no point is "borderline"
-    E.draws = nullptr; E.seed = 0;
-    return E;
-}
+// The two stages' own arguments, in the order of the entries' parameter lists.  present = false: the entry has no such stage, and none
+// of its rules is examined -- which is not nprob == 0: an empty stage of a whole-fit entry still has its sizes and schedule checked.
+struct StageA {
+    bool present;
+    int nprob; const int *off; float th; int niter; const int *draws;
+    double *out_model; unsigned char *out_inliers; int *out_best, *scores;
+    float *quads; long rows;      // quads NULL: the LDS-staged scoring kernel
+    int *tie; float tie_window;
+};
+struct StageB {
+    bool present;
+    int nprob; const int *rng0, *rng1; const float *joint_dir; double th; int niter; const int *draws;
+    double *out_model; unsigned char *out_inliers; int *out_best; double *out_score, *scores, *models;
+    int *lm_stat, lm_schedule, *tie; double tie_window;
+    const int *joint_kind;        // NULL: every problem revolute, the kernels without a kind
+};
+struct FitCall {
+    const char *who;              // the entry's name in messages
+    const float *src, *tgt; int max_n; double *record; int K; void *stream;
+    StageA a; FitKey key_a;
+    StageB b; FitKey key_b;
+};
+static bool whole_fit(const FitCall &c) { return c.a.present && c.b.present; }
+static int key_mode(const FitCall &c) { return c.a.present ? c.key_a.mode : c.key_b.mode; }
 
 // min_K: 1 for the per-part fits (nprob = B * K), 2 for the joint fits (nprob = B * (K - 1)).  The tie window is an ABSOLUTE half-width
 // on the residual norm: a point counts when th - w <= |res| < th + w, evaluated on the squared norm the verifiers already compute.
-static int make_extras(const char *who, int nprob, double *record, int K, int min_K, int *tie, double th, double window, FitExtras &E) {
-    E.record = record; E.K = K; E.tie = tie;
-    if (record) {
-        ANCSH_REQUIRE(K >= min_K && nprob % (K - (min_K - 1)) == 0, "%s: record needs K >= %d and nprob (%d) a multiple of %s (K = %d)", who, min_K, nprob,
-                      min_K == 1 ? "K" : "K - 1", K);
-    }
+static int make_extras(const FitCall &c, int nprob, int min_K, int *tie, double th, double window, FitExtras &E) {
+    E.record = c.record; E.K = c.K; E.tie = tie;
+    if (c.record)
+        ANCSH_REQUIRE(c.K >= min_K && nprob % (c.K - (min_K - 1)) == 0, "%s: record needs K >= %d and nprob (%d) a multiple of %s (K = %d)", c.who, min_K,
+                      nprob, min_K == 1 ? "K" : "K - 1", c.K);
     if (tie) {
-        ANCSH_REQUIRE(window >= 0.0 && window < th, "%s: tie_window %g must be in [0, inlier_th)", who, window);
+        ANCSH_REQUIRE(window >= 0.0 && window < th, "%s: tie_window %g must be in [0, inlier_th)", c.who, window);
         const double lo = (th - window) * (th - window), hi = (th + window) * (th + window);
         E.lo_f = (float)lo; E.hi_f = (float)hi; E.lo_d = lo; E.hi_d = hi;
     }
@@ -2220,183 +1792,30 @@ static int make_extras(const char *who, int nprob, double *record, int K, int mi
 }
 
 static long single_quads_needed(long rows, int nprob) { return 2 * ((rows + 7) / 8 + nprob) + 2; }     // quads (24 floats each)
-
 extern "C" long ancsh_ransac_single_quads_floats(long rows, int nprob) {
     if (rows < 0 || nprob < 0) return -1;
     return 24 * single_quads_needed(rows, nprob);
 }
 
-// Stage A's argument checks, all of them before any launch (pose_fit_impl runs both stages' checks first).  nprob == 0 passes after the
-// size checks: the call is then a no-op.
-static int ransac_single_check(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter, int max_n,
-                               double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
-                               long rows) {
-    ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_single: bad sizes nprob=%d niter=%d max_n=%d", nprob, niter, max_n);
-    ANCSH_REQUIRE(max_n <= 6144, "ransac_single: max_n %d > 6144 (refit keeps the inliers in LDS)", max_n);
-    if (nprob == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(off && src && tgt && out_model && out_inliers && out_best && scratch_scores, "ransac_single: null pointer");
-    ANCSH_REQUIRE(inlier_th > 0.f, "ransac_single: inlier_th must be positive");
-    const float th_sq = sq_threshold_f32(inlier_th);
-    if (scratch_quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
-        ANCSH_REQUIRE(rows >= 0 && rows < (1L << 30), "ransac_single_ex: rows=%ld out of range", rows);
-        ANCSH_REQUIRE((((uintptr_t)scratch_quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
-    }
+// The rules of the device key modes.  An entry of one stage examines its pointer and its counts whatever nprob is; a whole-fit entry lets a
+// stage without problems pass (nprob_b == 0 is how a K = 1 caller gets there) and names the count it rejects nprob_a / nprob_b.
+// KEY_DKEY needs K even without a record: it is the problem count of one cloud.  cloud_base lives in device memory, so
+// (cloud_base + B) * K < 2^20 -- which keeps the draw keys clear of the sampler's tag bits -- is the caller's to check where it writes
+// the block (AncshPipeline.submit, dataset.check_stream_key).
+static int check_keys(const FitCall &c) {
+    const StageA &a = c.a; const StageB &b = c.b;
+    const bool whole = whole_fit(c); const int mode = key_mode(c);
+    if (mode == KEY_VALUE) return ANCSH_OK;
+    ANCSH_REQUIRE((!a.present || c.key_a.dev || (whole && a.nprob <= 0)) && (!b.present || c.key_b.dev || (whole && b.nprob <= 0)),
+                  "%s: null %s pointer", c.who, mode == KEY_DSEED ? "seed" : "key");
+    if (mode != KEY_DKEY) return ANCSH_OK;
+    if (a.present)
+        ANCSH_REQUIRE(c.K >= 1 && a.nprob >= 0 && a.nprob % c.K == 0 && a.nprob < (1 << 20), "%s: nprob%s (%d) must be a multiple of K (%d) below 2^20",
+                      c.who, whole ? "_a" : "", a.nprob, c.K);
+    if (b.present)
+        ANCSH_REQUIRE((whole && b.nprob == 0) || (c.K >= 2 && b.nprob >= 0 && b.nprob % (c.K - 1) == 0 && b.nprob < (1 << 20)),
+                      "%s: nprob%s (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", c.who, whole ? "_b" : "", b.nprob, c.K);
     return ANCSH_OK;
-}
-
-// th_sq: the squared threshold (the kernels compare squared residuals)
-template <int KM>
-static void ransac_single_launch_score(int nprob, const int *off, const float *src, const float *tgt, float th_sq, int niter,
-                                       const int *draws, KeyArg<KM> seed, int max_n, int *scratch_scores, float *scratch_quads, long rows,
-                                       hipStream_t st) {
-    // the scalar-register kernel counts inliers as clamp((th_sq - s) * 2^126): exact while th_sq - s cannot be denormal, i.e. for any
-    // threshold a fit would use; a squared threshold below 2^-100 or >= 4 (th_sq * 2^126 must stay finite) takes the compare-based kernel
-    // (same scores by construction)
-    if (scratch_quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
-        const int cap = (int)single_quads_needed(rows, nprob);
-        hipLaunchKernelGGL(soa_quads_kernel, dim3((max_n + 7 + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, scratch_quads, cap);
-        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt,
-                           (const float *)scratch_quads, cap, th_sq, niter, draws, seed, scratch_scores);
-    } else {
-        hipLaunchKernelGGL(ransac_single_score_kernel<KM>, dim3((niter + 255) / 256, nprob), dim3(256), 0, st, off, src, tgt, th_sq,
-                           niter, draws, seed, scratch_scores);
-    }
-}
-
-static size_t single_finish_lds(int max_n) { return 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float); }
-
-template <int KM>
-static int ransac_single_impl(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                              const int *draws, KeyArg<KM> seed, int max_n, double *out_model,
-                              unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads, long rows,
-                              FitExtras E, void *stream) {
-    if (int rc = ransac_single_check(nprob, off, src, tgt, inlier_th, niter, max_n, out_model, out_inliers, out_best, scratch_scores,
-                                     scratch_quads, rows)) return rc;
-    if (nprob == 0) return ANCSH_OK;
-    hipStream_t st = (hipStream_t)stream;
-    inlier_th = sq_threshold_f32(inlier_th);     // the kernels compare squared residuals
-    ransac_single_launch_score<KM>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, scratch_scores, scratch_quads, rows, st);
-    const size_t lds = single_finish_lds(max_n);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_single_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_single_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, off, src, tgt, inlier_th, niter, draws, seed,
-                       scratch_scores, max_n, out_model, out_inliers, out_best, E);
-    return check_launch("ransac_single");
-}
-
-extern "C" int ancsh_ransac_single(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                                   const int *draws, unsigned long long seed, int max_n, double *out_model,
-                                   unsigned char *out_inliers, int *out_best, int *scratch_scores, void *stream) {
-    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                                     scratch_scores, nullptr, 0, no_extras(), stream);
-}
-
-// The same call with the hypotheses scored from SCALAR registers: scratch_quads (32-byte aligned, ancsh_ransac_single_quads_floats(rows,
-// nprob) floats, rows >= off[nprob]) receives a padded four-points-per-record copy of the parts; scores, winner, mask and model are
-// those of ancsh_ransac_single bit for bit.
-extern "C" int ancsh_ransac_single_ex(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                                      const int *draws, unsigned long long seed, int max_n, double *out_model,
-                                      unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
-                                      long rows, void *stream) {
-    ANCSH_REQUIRE(scratch_quads, "ransac_single_ex: scratch_quads is NULL (ancsh_ransac_single is the call without it)");
-    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                                     scratch_scores, scratch_quads, rows, no_extras(), stream);
-}
-
-// ancsh_ransac_single_ex (scratch_quads != NULL) / ancsh_ransac_single (NULL) that ALSO writes each fit straight into the pose record
-// and / or reports how tie-sensitive it is (FitExtras above; include/ancsh_hip.h).  Everything else bit for bit as before.
-extern "C" int ancsh_ransac_single_rec(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                                       const int *draws, unsigned long long seed, int max_n, double *out_model,
-                                       unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
-                                       long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_single_rec", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl<KEY_VALUE>(nprob, off, src, tgt, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                                     scratch_scores, scratch_quads, rows, E, stream);
-}
-
-// Stage B's argument checks, all of them before any launch.  nprob == 0 passes after the size checks.
-static int ransac_joint_check(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
-                              double inlier_th, int niter, int max_n, double *out_model, unsigned char *out_inliers, int *out_best,
-                              double *out_score, double *scratch_scores, double *scratch_models, int lm_schedule) {
-    ANCSH_REQUIRE(lm_schedule >= ANCSH_LM_AUTO && lm_schedule <= ANCSH_LM_LATENCY, "ransac_joint: unknown lm_schedule %d", lm_schedule);
-    ANCSH_REQUIRE(nprob >= 0 && niter > 0 && max_n > 0, "ransac_joint: bad sizes");
-    ANCSH_REQUIRE(max_n <= 3072, "ransac_joint: max_n %d > 3072 (refit keeps both parts' inliers in LDS)", max_n);
-    if (nprob == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(rng0 && rng1 && src && tgt && joint_dir && out_model && out_inliers && out_best && out_score &&
-                      scratch_scores && scratch_models, "ransac_joint: null pointer");
-    ANCSH_REQUIRE(inlier_th > 0.0, "ransac_joint: inlier_th must be positive");
-    return ANCSH_OK;
-}
-
-static int lm_chunk(int nprob, int niter) { return (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK; }
-
-// what follows the LM fits: models, verification, refit (th_sq: the squared threshold)
-template <int KM>
-static void ransac_joint_launch_tail(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                     const float *joint_dir, double th_sq, int niter, const int *draws, KeyArg<KM> seed, int max_n,
-                                     double *out_model, unsigned char *out_inliers, int *out_best, double *out_score,
-                                     double *scratch_scores, double *scratch_models, const FitExtras &E, hipStream_t st,
-                                     const int *joint_kind) {
-    hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, dim3((niter + 63) / 64, nprob), dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed,
-                       scratch_models);
-    hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((niter + 3) / 4, nprob), dim3(256), 0, st, rng0, rng1, src, tgt, th_sq,
-                       niter, scratch_models, scratch_scores);
-    const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * max_n * 3 * sizeof(float);
-    if (joint_kind) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(ransac_joint_finish_kind_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, th_sq,
-                           niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E, joint_kind);
-        return;
-    }
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)ransac_joint_finish_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ransac_joint_finish_kernel<KM>, dim3(nprob), dim3(256), lds, st, rng0, rng1, src, tgt, joint_dir, th_sq,
-                       niter, scratch_scores, scratch_models, max_n, out_model, out_inliers, out_best, out_score, E);
-}
-
-template <int KM>
-static int ransac_joint_impl(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                             const float *joint_dir, double inlier_th, int niter, const int *draws,
-                             KeyArg<KM> seed, int max_n, double *out_model, unsigned char *out_inliers,
-                             int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                             int *lm_stat, int lm_schedule, FitExtras E, void *stream, const int *joint_kind = nullptr) {
-    if (int rc = ransac_joint_check(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, max_n, out_model, out_inliers, out_best,
-                                    out_score, scratch_scores, scratch_models, lm_schedule)) return rc;
-    if (nprob == 0) return ANCSH_OK;
-    hipStream_t st = (hipStream_t)stream;
-    inlier_th = sq_threshold_f64(inlier_th);      // the kernels compare squared residuals
-    const dim3 per_hyp((niter + 63) / 64, nprob);
-    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, per_hyp, dim3(64), 0, st, rng0, rng1, src, tgt, niter, draws, seed, scratch_scores,
-                       scratch_models);
-    // Two schedules of the same fits (identical MINPACK state machine, results equal to ~1e-7, not to the last bit: the eight-lane
-    // callbacks are a different instruction stream and the f64 code is compiled with contraction on):
-    //   * lane per fit: least SIMD time per fit -- the throughput schedule, and what ANCSH_LM_AUTO ALWAYS takes, so that a cloud's
-    //     result does not depend on how many clouds share the launch.  Only the number of hypotheses handed to a wave follows the
-    //     launch size (a small launch spreads over 4x more waves); the order in which hypotheses run enters no result;
-    //   * eight lanes per fit (ANCSH_LM_LATENCY, explicit only): the long fits that set the launch's duration run ~1.25x faster
-    //     (measured on 64 x 200 fits: 1.27 vs 1.6 ms; the tail is MINPACK's serial lmpar on rank-deficient samples, which no lane
-    //     split shortens) at ~5 % lower pipeline throughput.
-    // joint_kind (the *_kind entries): the same launches with the kernels that branch, block-uniformly, on the problem's kind; without
-    // it the kernels are the revolute-only ones, untouched
-    if (lm_schedule == ANCSH_LM_LATENCY) {
-        const dim3 grid((niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, nprob);
-        if (joint_kind)
-            hipLaunchKernelGGL(ransac_joint_lm_coop_kind_kernel<KM>, grid, dim3(64), 0, st, rng0, rng1, src, tgt, joint_dir, niter, draws, seed,
-                               scratch_models, lm_stat, joint_kind);
-        else
-            hipLaunchKernelGGL(ransac_joint_lm_coop_kernel<KM>, grid, dim3(64), 0, st,
-                               rng0, rng1, src, tgt, joint_dir, niter, draws, seed, scratch_models, lm_stat);
-    } else {
-        const int chunk = lm_chunk(nprob, niter);
-        if (joint_kind)
-            hipLaunchKernelGGL(ransac_joint_lm_kind_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
-                               joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk, joint_kind);
-        else
-            hipLaunchKernelGGL(ransac_joint_lm_kernel<KM>, dim3((niter + chunk - 1) / chunk, nprob), dim3(64), 0, st, rng0, rng1, src, tgt,
-                               joint_dir, niter, draws, seed, scratch_models, lm_stat, chunk);
-    }
-    ransac_joint_launch_tail<KM>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers, out_best,
-                                 out_score, scratch_scores, scratch_models, E, st, joint_kind);
-    return check_launch("ransac_joint");
 }
 
 // joint_kind of the *_kind entries: NULL is "all revolute".  A host-side array (pinned or registered host memory) is checked here --
@@ -2412,302 +1831,382 @@ static int check_joint_kind(const char *who, int nprob, const int *joint_kind) {
     return ANCSH_OK;
 }
 
-extern "C" int ancsh_ransac_joint(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                  const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                  unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
-                                  int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                  int *lm_stat, void *stream) {
-    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, ANCSH_LM_AUTO, no_extras(), stream);
-}
-
-extern "C" int ancsh_ransac_joint_ex(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                     const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                     unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
-                                     int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                     int *lm_stat, int lm_schedule, void *stream) {
-    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, no_extras(), stream);
-}
-
-extern "C" int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                      const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                      unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
-                                      int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                      int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
-                                      void *stream) {
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = seed;
-    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                                    out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
-}
-
-// ancsh_ransac_single_rec / ancsh_ransac_joint_rec with the generator key read from device memory (include/ancsh_hip.h): the kernels
-// are the by-value ones instantiated with KEY_DSEED, the key travels as the address in the same 64-bit argument
-extern "C" int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                                             const int *draws, const unsigned long long *seed, int max_n, double *out_model,
-                                             unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
-                                             long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
-    ANCSH_REQUIRE(seed, "ransac_single_rec_dseed: null seed pointer");
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_single_rec_dseed", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl<KEY_DSEED>(nprob, off, src, tgt, inlier_th, niter, draws, (unsigned long long)(uintptr_t)seed, max_n, out_model,
-                                    out_inliers, out_best, scratch_scores, scratch_quads, rows, E, stream);
-}
-
-extern "C" int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                            const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                            const unsigned long long *seed, int max_n, double *out_model, unsigned char *out_inliers,
-                                            int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                            int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
-                                            void *stream) {
-    ANCSH_REQUIRE(seed, "ransac_joint_rec_dseed: null seed pointer");
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec_dseed", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)seed;
-    return ransac_joint_impl<KEY_DSEED>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
-                                   out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream);
-}
-
-// ... with the key block of include/ancsh_hip.h (ancsh_stream_key): the KEY_DKEY instantiations, whose generator problem index is
-// prob + key->cloud_base * K (stage A) / prob + key->cloud_base * (K - 1) (stage B).  K is required here even without a record: it is
-// the problem count of one cloud.  cloud_base lives in device memory, so (cloud_base + B) * K < 2^20 -- which keeps the draw keys clear
-// of the sampler's tag bits -- is the caller's to check where it writes the block (AncshPipeline.submit, dataset.check_stream_key).
-extern "C" int ancsh_ransac_single_rec_dkey(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
-                                            const int *draws, const ancsh_stream_key *key, int max_n, double *out_model,
-                                            unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
-                                            long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
-    ANCSH_REQUIRE(key, "ransac_single_rec_dkey: null key pointer");
-    ANCSH_REQUIRE(K >= 1 && nprob >= 0 && nprob % K == 0 && nprob < (1 << 20),
-                  "ransac_single_rec_dkey: nprob (%d) must be a multiple of K (%d) below 2^20", nprob, K);
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_single_rec_dkey", nprob, record, K, 1, tie_stats, (double)inlier_th, (double)tie_window, E)) return rc;
-    return ransac_single_impl<KEY_DKEY>(nprob, off, src, tgt, inlier_th, niter, draws, DKey{key, K}, max_n, out_model, out_inliers,
-                                        out_best, scratch_scores, scratch_quads, rows, E, stream);
-}
-
-extern "C" int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                           const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                           const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers,
-                                           int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                           int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
-                                           void *stream) {
-    ANCSH_REQUIRE(key, "ransac_joint_rec_dkey: null key pointer");
-    ANCSH_REQUIRE(K >= 2 && nprob >= 0 && nprob % (K - 1) == 0 && nprob < (1 << 20),
-                  "ransac_joint_rec_dkey: nprob (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", nprob, K);
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec_dkey", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)key;
-    return ransac_joint_impl<KEY_DKEY>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, DKey{key, K - 1}, max_n,
-                                       out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
-                                       E, stream);
-}
-
-// The three record entries with a joint kind per problem (ABI 14, include/ancsh_hip.h): joint_kind NULL = the entry without it.
-extern "C" int ancsh_ransac_joint_rec_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                           const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                           unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
-                                           int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                           int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats, double tie_window,
-                                           const int *joint_kind, void *stream) {
-    if (int rc = check_joint_kind("ransac_joint_rec_kind", nprob, joint_kind)) return rc;
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = seed;
-    return ransac_joint_impl<KEY_VALUE>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, seed, max_n, out_model, out_inliers,
-                                        out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream, joint_kind);
-}
-
-extern "C" int ancsh_ransac_joint_rec_dseed_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                                 const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                                 const unsigned long long *seed, int max_n, double *out_model,
-                                                 unsigned char *out_inliers, int *out_best, double *out_score, double *scratch_scores,
-                                                 double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
-                                                 int *tie_stats, double tie_window, const int *joint_kind, void *stream) {
-    ANCSH_REQUIRE(seed, "ransac_joint_rec_dseed_kind: null seed pointer");
-    if (int rc = check_joint_kind("ransac_joint_rec_dseed_kind", nprob, joint_kind)) return rc;
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec_dseed_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)seed;
-    return ransac_joint_impl<KEY_DSEED>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, E.seed, max_n, out_model,
-                                        out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule, E, stream,
-                                        joint_kind);
-}
-
-extern "C" int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
-                                                const float *joint_dir, double inlier_th, int niter, const int *draws,
-                                                const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers,
-                                                int *out_best, double *out_score, double *scratch_scores, double *scratch_models,
-                                                int *lm_stat, int lm_schedule, double *record, int K, int *tie_stats,
-                                                double tie_window, const int *joint_kind, void *stream) {
-    ANCSH_REQUIRE(key, "ransac_joint_rec_dkey_kind: null key pointer");
-    ANCSH_REQUIRE(K >= 2 && nprob >= 0 && nprob % (K - 1) == 0 && nprob < (1 << 20),
-                  "ransac_joint_rec_dkey_kind: nprob (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", nprob, K);
-    if (int rc = check_joint_kind("ransac_joint_rec_dkey_kind", nprob, joint_kind)) return rc;
-    FitExtras E = no_extras();
-    if (int rc = make_extras("ransac_joint_rec_dkey_kind", nprob, record, K, 2, tie_stats, inlier_th, tie_window, E)) return rc;
-    E.draws = draws; E.seed = (unsigned long long)(uintptr_t)key;
-    return ransac_joint_impl<KEY_DKEY>(nprob, rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws, DKey{key, K - 1}, max_n,
-                                       out_model, out_inliers, out_best, out_score, scratch_scores, scratch_models, lm_stat, lm_schedule,
-                                       E, stream, joint_kind);
-}
-
-// ---- the whole fit in one call: both stages' launches on one stream, the LM fits and stage A's refit in ONE kernel -------------------
-// soa_quads, score_sreg, joint_init, pose_lm_finish_a (LM fits || stage A refit), joint_model, joint_verify, joint_finish: seven launches
-// where ancsh_ransac_joint_rec* + ancsh_ransac_single_rec* issue eight, and the bytes of those two calls.  Every argument check of both
-// runs before anything is launched.  A stage without problems, and the eight-lane schedule (ANCSH_LM_LATENCY: another LM kernel), take
-// the existing launches.
-template <int KM>
-static int pose_fit_impl(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
-                         const int *draws_a, KeyArg<KM> seed_a, int max_n, double *out_model_a, unsigned char *out_inliers_a,
-                         int *out_best_a, int *scratch_scores_a, float *scratch_quads, long rows, const FitExtras &EA, int nprob_b,
-                         const int *rng0, const int *rng1, const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b,
-                         KeyArg<KM> seed_b, double *out_model_b, unsigned char *out_inliers_b, int *out_best_b, double *out_score_b,
-                         double *scratch_scores_b, double *scratch_models_b, int *lm_stat, int lm_schedule, const FitExtras &EB,
-                         const int *joint_kind, void *stream) {
-    if (int rc = ransac_single_check(nprob_a, off, src, tgt, inlier_th_a, niter_a, max_n, out_model_a, out_inliers_a, out_best_a,
-                                     scratch_scores_a, scratch_quads, rows)) return rc;
-    if (int rc = ransac_joint_check(nprob_b, rng0, rng1, src, tgt, joint_dir, inlier_th_b, niter_b, max_n, out_model_b, out_inliers_b,
-                                    out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_schedule)) return rc;
-    if (nprob_a == 0 && nprob_b == 0) return ANCSH_OK;
-    if (nprob_a == 0 || nprob_b == 0 || lm_schedule == ANCSH_LM_LATENCY) {        // stage B first, as PoseSolver.solve issues the two calls
-        if (int rc = ransac_joint_impl<KM>(nprob_b, rng0, rng1, src, tgt, joint_dir, inlier_th_b, niter_b, draws_b, seed_b, max_n, out_model_b,
-                                           out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, EB,
-                                           stream, joint_kind)) return rc;
-        return ransac_single_impl<KM>(nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, seed_a, max_n, out_model_a, out_inliers_a,
-                                      out_best_a, scratch_scores_a, scratch_quads, rows, EA, stream);
+// Stage A's argument checks.  nprob == 0 passes after the size checks: the stage is then a no-op.
+static int ransac_single_check(const FitCall &c) {
+    const StageA &a = c.a;
+    ANCSH_REQUIRE(a.nprob >= 0 && a.niter > 0 && c.max_n > 0, "ransac_single: bad sizes nprob=%d niter=%d max_n=%d", a.nprob, a.niter, c.max_n);
+    ANCSH_REQUIRE(c.max_n <= 6144, "ransac_single: max_n %d > 6144 (refit keeps the inliers in LDS)", c.max_n);
+    if (a.nprob == 0) return ANCSH_OK;
+    ANCSH_REQUIRE(a.off && c.src && c.tgt && a.out_model && a.out_inliers && a.out_best && a.scores, "ransac_single: null pointer");
+    ANCSH_REQUIRE(a.th > 0.f, "ransac_single: inlier_th must be positive");
+    const float th_sq = sq_threshold_f32(a.th);
+    if (a.quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
+        ANCSH_REQUIRE(a.rows >= 0 && a.rows < (1L << 30), "ransac_single_ex: rows=%ld out of range", a.rows);
+        ANCSH_REQUIRE((((uintptr_t)a.quads) & 31) == 0, "ransac_single_ex: scratch_quads must be 32-byte aligned");
     }
-    LmArgs L;
-    L.chunk = lm_chunk(nprob_b, niter_b);                               // the same rule as the LM launch of its own
-    L.chunks_per_prob = (niter_b + L.chunk - 1) / L.chunk;
-    const long n_chunks = (long)L.chunks_per_prob * nprob_b;
-    ANCSH_REQUIRE((n_chunks + 3) / 4 + nprob_a < (1L << 31), "pose_fit: %ld LM chunks + %d parts exceed one grid", n_chunks, nprob_a);
-    hipStream_t st = (hipStream_t)stream;                               // every check has passed: nothing above launches
-    const float th_a = sq_threshold_f32(inlier_th_a);
-    const double th_b = sq_threshold_f64(inlier_th_b);
-    ransac_single_launch_score<KM>(nprob_a, off, src, tgt, th_a, niter_a, draws_a, seed_a, max_n, scratch_scores_a, scratch_quads, rows, st);
-    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, dim3((niter_b + 63) / 64, nprob_b), dim3(64), 0, st, rng0, rng1, src, tgt, niter_b, draws_b,
-                       seed_b, scratch_scores_b, scratch_models_b);
-    L.rng0 = rng0; L.rng1 = rng1; L.joint_dir = joint_dir; L.niter = niter_b; L.draws = draws_b; L.models = scratch_models_b; L.lm_stat = lm_stat;
-    L.n_chunks = (int)n_chunks;
-    L.n_lm = (int)((n_chunks + 3) / 4);                                 // four waves, one chunk each, per LM block
-    FinishAArgs A;
-    A.off = off; A.th = th_a; A.niter = niter_a; A.draws = draws_a; A.scores = scratch_scores_a; A.max_n = max_n;
-    A.out_model = out_model_a; A.out_inliers = out_inliers_a; A.out_best = out_best_a;
-    const size_t lds = single_finish_lds(max_n);
-    const dim3 grid(L.n_lm + nprob_a);
-    if (joint_kind) {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)pose_lm_finish_a_kind_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(pose_lm_finish_a_kind_kernel<KM>, grid, dim3(256), lds, st, src, tgt, L, seed_b, joint_kind, A, seed_a, EA);
-    } else {
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)pose_lm_finish_a_kernel<KM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(pose_lm_finish_a_kernel<KM>, grid, dim3(256), lds, st, src, tgt, L, seed_b, A, seed_a, EA);
-    }
-    ransac_joint_launch_tail<KM>(nprob_b, rng0, rng1, src, tgt, joint_dir, th_b, niter_b, draws_b, seed_b, max_n, out_model_b, out_inliers_b,
-                                 out_best_b, out_score_b, scratch_scores_b, scratch_models_b, EB, st, joint_kind);
-    return check_launch("pose_fit");
-}
-
-// both stages' extras (record columns, tie counts) from the entries' arguments: ancsh_ransac_single_rec*'s and ancsh_ransac_joint_rec*'s rules
-static int pose_fit_extras(const char *who, int nprob_a, int nprob_b, double *record, int K, int *tie_a, float inlier_th_a, float tie_window_a,
-                           int *tie_b, double inlier_th_b, double tie_window_b, const int *draws_b, unsigned long long seed_b, FitExtras &EA,
-                           FitExtras &EB) {
-    EA = no_extras(); EB = no_extras();
-    // a stage without problems writes nothing: its record geometry and window are not examined (nprob_b == 0 is how a K = 1 caller gets here)
-    if (nprob_a != 0)
-        if (int rc = make_extras(who, nprob_a, record, K, 1, tie_a, (double)inlier_th_a, (double)tie_window_a, EA)) return rc;
-    if (nprob_b != 0)
-        if (int rc = make_extras(who, nprob_b, record, K, 2, tie_b, inlier_th_b, tie_window_b, EB)) return rc;
-    EB.draws = draws_b; EB.seed = seed_b;
     return ANCSH_OK;
 }
 
-#define POSE_FIT_PARAMS(KEY_T)                                                                                                             \
-    int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a, const int *draws_a, KEY_T key_a,     \
-        int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a, int *scratch_scores_a, float *scratch_quads,        \
-        long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1, const float *joint_dir,            \
-        double inlier_th_b, int niter_b, const int *draws_b, KEY_T key_b, double *out_model_b, unsigned char *out_inliers_b,               \
-        int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat, int lm_schedule,           \
-        int *tie_stats_b, double tie_window_b, double *record, int K
-#define POSE_FIT_CALL(KM, KA, KB, KIND)                                                                                                    \
-    pose_fit_impl<KM>(nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, KA, max_n, out_model_a, out_inliers_a, out_best_a,            \
-                      scratch_scores_a, scratch_quads, rows, EA, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, KB,        \
-                      out_model_b, out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, EB,   \
-                      KIND, stream)
-
-static int pose_fit_rec(const char *who, POSE_FIT_PARAMS(unsigned long long), const int *joint_kind, void *stream) {
-    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
-    FitExtras EA, EB;
-    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
-                                 draws_b, key_b, EA, EB)) return rc;
-    return POSE_FIT_CALL(KEY_VALUE, key_a, key_b, joint_kind);
+// Stage B's argument checks.  nprob == 0 passes after the size checks.
+static int ransac_joint_check(const FitCall &c) {
+    const StageB &b = c.b;
+    ANCSH_REQUIRE(b.lm_schedule >= ANCSH_LM_AUTO && b.lm_schedule <= ANCSH_LM_LATENCY, "ransac_joint: unknown lm_schedule %d", b.lm_schedule);
+    ANCSH_REQUIRE(b.nprob >= 0 && b.niter > 0 && c.max_n > 0, "ransac_joint: bad sizes");
+    ANCSH_REQUIRE(c.max_n <= 3072, "ransac_joint: max_n %d > 3072 (refit keeps both parts' inliers in LDS)", c.max_n);
+    if (b.nprob == 0) return ANCSH_OK;
+    ANCSH_REQUIRE(b.rng0 && b.rng1 && c.src && c.tgt && b.joint_dir && b.out_model && b.out_inliers && b.out_best && b.out_score &&
+                      b.scores && b.models, "ransac_joint: null pointer");
+    ANCSH_REQUIRE(b.th > 0.0, "ransac_joint: inlier_th must be positive");
+    return ANCSH_OK;
 }
 
-static int pose_fit_rec_dseed(const char *who, POSE_FIT_PARAMS(const unsigned long long *), const int *joint_kind, void *stream) {
-    ANCSH_REQUIRE((key_a || nprob_a <= 0) && (key_b || nprob_b <= 0), "%s: null seed pointer", who);
-    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
-    FitExtras EA, EB;
-    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
-                                 draws_b, (unsigned long long)(uintptr_t)key_b, EA, EB)) return rc;
-    return POSE_FIT_CALL(KEY_DSEED, (unsigned long long)(uintptr_t)key_a, (unsigned long long)(uintptr_t)key_b, joint_kind);
+static int lm_chunk(int nprob, int niter) { return (long)nprob * niter <= HYP_SMALL_LAUNCH ? HYP_CHUNK_SMALL : HYP_CHUNK; }
+static size_t single_finish_lds(int max_n) { return 64 * sizeof(double) + 8 * sizeof(int) + (size_t)2 * max_n * 3 * sizeof(float); }
+
+// launch_lds (pose_shared.h) of one of two twin kernels: with joint_kind (the *_kind entries) the twin that branches, block-uniformly,
+// on the problem's kind and takes the array as one more, last argument; without it the revolute-only kernel, untouched
+template <class Kernel, class KindKernel, class... Args>
+static void launch_twin(Kernel plain, KindKernel kind, const int *joint_kind, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if (joint_kind) launch_lds(kind, grid, block, lds, st, args..., joint_kind);
+    else launch_lds(plain, grid, block, lds, st, args...);
 }
 
-static int pose_fit_rec_dkey(const char *who, POSE_FIT_PARAMS(const ancsh_stream_key *), const int *joint_kind, void *stream) {
-    ANCSH_REQUIRE((key_a || nprob_a <= 0) && (key_b || nprob_b <= 0), "%s: null key pointer", who);
-    ANCSH_REQUIRE(K >= 1 && nprob_a >= 0 && nprob_a % K == 0 && nprob_a < (1 << 20), "%s: nprob_a (%d) must be a multiple of K (%d) below 2^20", who,
-                  nprob_a, K);
-    ANCSH_REQUIRE(nprob_b == 0 || (K >= 2 && nprob_b > 0 && nprob_b % (K - 1) == 0 && nprob_b < (1 << 20)),
-                  "%s: nprob_b (%d) must be a multiple of K - 1 (K = %d >= 2) below 2^20", who, nprob_b, K);
-    if (int rc = check_joint_kind(who, nprob_b, joint_kind)) return rc;
-    FitExtras EA, EB;
-    if (int rc = pose_fit_extras(who, nprob_a, nprob_b, record, K, tie_stats_a, inlier_th_a, tie_window_a, tie_stats_b, inlier_th_b, tie_window_b,
-                                 draws_b, (unsigned long long)(uintptr_t)key_b, EA, EB)) return rc;
-    return POSE_FIT_CALL(KEY_DKEY, (DKey{key_a, K}), (DKey{key_b, K - 1}), joint_kind);
+// stage A's hypothesis scores.  th_sq: the squared threshold (the kernels compare squared residuals)
+template <int KM>
+static void launch_score_a(const FitCall &c, KeyArg<KM> key, float th_sq, hipStream_t st) {
+    const StageA &a = c.a;
+    // the scalar-register kernel counts inliers as clamp((th_sq - s) * 2^126): exact while th_sq - s cannot be denormal, i.e. for any
+    // threshold a fit would use; a squared threshold below 2^-100 or >= 4 (th_sq * 2^126 must stay finite) takes the compare-based kernel
+    // (same scores by construction)
+    if (a.quads && th_sq >= 0x1p-100f && th_sq < 4.0f) {
+        const int cap = (int)single_quads_needed(a.rows, a.nprob);
+        hipLaunchKernelGGL(soa_quads_kernel, dim3((c.max_n + 7 + 255) / 256, a.nprob), dim3(256), 0, st, a.off, c.src, c.tgt, a.quads, cap);
+        hipLaunchKernelGGL(ransac_single_score_sreg_kernel<KM>, dim3((a.niter + 255) / 256, a.nprob), dim3(256), 0, st, a.off, c.src, c.tgt,
+                           (const float *)a.quads, cap, th_sq, a.niter, a.draws, key, a.scores);
+    } else {
+        hipLaunchKernelGGL(ransac_single_score_kernel<KM>, dim3((a.niter + 255) / 256, a.nprob), dim3(256), 0, st, a.off, c.src, c.tgt, th_sq,
+                           a.niter, a.draws, key, a.scores);
+    }
 }
 
-#define POSE_FIT_ARGS                                                                                                                      \
-    nprob_a, off, src, tgt, inlier_th_a, niter_a, draws_a, key_a, max_n, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,          \
-        scratch_quads, rows, tie_stats_a, tie_window_a, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, key_b, out_model_b,  \
-        out_inliers_b, out_best_b, out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b, record, K
-
-extern "C" int ancsh_pose_fit_rec(POSE_FIT_PARAMS(unsigned long long), void *stream) {
-    return pose_fit_rec("pose_fit_rec", POSE_FIT_ARGS, nullptr, stream);
-}
-extern "C" int ancsh_pose_fit_rec_dseed(POSE_FIT_PARAMS(const unsigned long long *), void *stream) {
-    return pose_fit_rec_dseed("pose_fit_rec_dseed", POSE_FIT_ARGS, nullptr, stream);
-}
-extern "C" int ancsh_pose_fit_rec_dkey(POSE_FIT_PARAMS(const ancsh_stream_key *), void *stream) {
-    return pose_fit_rec_dkey("pose_fit_rec_dkey", POSE_FIT_ARGS, nullptr, stream);
-}
-extern "C" int ancsh_pose_fit_rec_kind(POSE_FIT_PARAMS(unsigned long long), const int *joint_kind, void *stream) {
-    return pose_fit_rec("pose_fit_rec_kind", POSE_FIT_ARGS, joint_kind, stream);
-}
-extern "C" int ancsh_pose_fit_rec_dseed_kind(POSE_FIT_PARAMS(const unsigned long long *), const int *joint_kind, void *stream) {
-    return pose_fit_rec_dseed("pose_fit_rec_dseed_kind", POSE_FIT_ARGS, joint_kind, stream);
-}
-extern "C" int ancsh_pose_fit_rec_dkey_kind(POSE_FIT_PARAMS(const ancsh_stream_key *), const int *joint_kind, void *stream) {
-    return pose_fit_rec_dkey("pose_fit_rec_dkey_kind", POSE_FIT_ARGS, joint_kind, stream);
-}
-#undef POSE_FIT_PARAMS
-#undef POSE_FIT_CALL
-#undef POSE_FIT_ARGS
-
-extern "C" int ancsh_umeyama(int nprob, const int *off, const float *src, const float *tgt, double *out, void *stream) {
-    ANCSH_REQUIRE(nprob >= 0, "umeyama: negative nprob");
-    if (nprob == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(off && src && tgt && out, "umeyama: null pointer");
-    hipLaunchKernelGGL(umeyama_kernel, dim3(nprob), dim3(256), 0, (hipStream_t)stream, off, src, tgt, out);
-    return check_launch("umeyama");
+// stage A's own chain: scores, then winner and refit
+template <int KM>
+static int launch_stage_a(const FitCall &c, KeyArg<KM> key, const FitExtras &E) {
+    const StageA &a = c.a; hipStream_t st = (hipStream_t)c.stream;
+    const float th_sq = sq_threshold_f32(a.th);
+    launch_score_a<KM>(c, key, th_sq, st);
+    launch_lds(ransac_single_finish_kernel<KM>, dim3(a.nprob), dim3(256), single_finish_lds(c.max_n), st, a.off, c.src, c.tgt, th_sq, a.niter,
+               a.draws, key, a.scores, c.max_n, a.out_model, a.out_inliers, a.out_best, E);
+    return check_launch("ransac_single");
 }
 
-extern "C" int ancsh_estimate_similarity_transform(int nprob, const int *off, const float *src, const float *tgt, int niter,
-                                                   const int *draws, unsigned long long seed, double *out, int *status,
-                                                   void *stream) {
-    ANCSH_REQUIRE(nprob >= 0 && niter > 0 && niter <= 128, "estimate_similarity_transform: niter %d outside 1..128", niter);
-    if (nprob == 0) return ANCSH_OK;
-    ANCSH_REQUIRE(off && src && tgt && out && status, "estimate_similarity_transform: null pointer");
-    hipLaunchKernelGGL(ransac_umeyama5_kernel, dim3(nprob), dim3(128), 0, (hipStream_t)stream, off, src, tgt, niter, draws, seed,
-                       out, status);
-    return check_launch("estimate_similarity_transform");
+// what follows stage B's LM fits: models, verification, refit (th_sq: the squared threshold)
+template <int KM>
+static void launch_tail_b(const FitCall &c, KeyArg<KM> key, double th_sq, const FitExtras &E, hipStream_t st) {
+    const StageB &b = c.b;
+    hipLaunchKernelGGL(ransac_joint_model_kernel<KM>, dim3((b.niter + 63) / 64, b.nprob), dim3(64), 0, st, b.rng0, b.rng1, c.src, c.tgt, b.niter,
+                       b.draws, key, b.models);
+    hipLaunchKernelGGL(ransac_joint_verify_kernel, dim3((b.niter + 3) / 4, b.nprob), dim3(256), 0, st, b.rng0, b.rng1, c.src, c.tgt, th_sq,
+                       b.niter, b.models, b.scores);
+    const size_t lds = 128 * sizeof(double) + 8 * sizeof(int) + (size_t)4 * c.max_n * 3 * sizeof(float);
+    launch_twin(ransac_joint_finish_kernel<KM>, ransac_joint_finish_kind_kernel<KM>, b.joint_kind, dim3(b.nprob), dim3(256), lds, st, b.rng0,
+                b.rng1, c.src, c.tgt, b.joint_dir, th_sq, b.niter, b.scores, b.models, c.max_n, b.out_model, b.out_inliers, b.out_best,
+                b.out_score, E);
+}
+
+// stage B's own chain: hypotheses, LM fits, tail
+template <int KM>
+static int launch_stage_b(const FitCall &c, KeyArg<KM> key, const FitExtras &E) {
+    const StageB &b = c.b; hipStream_t st = (hipStream_t)c.stream;
+    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, dim3((b.niter + 63) / 64, b.nprob), dim3(64), 0, st, b.rng0, b.rng1, c.src, c.tgt, b.niter,
+                       b.draws, key, b.scores, b.models);
+    // Two schedules of the same fits (identical MINPACK state machine, results equal to ~1e-7, not to the last bit: the eight-lane
+    // callbacks are a different instruction stream and the f64 code is compiled with contraction on):
+    //   * lane per fit: least SIMD time per fit -- the throughput schedule, and what ANCSH_LM_AUTO ALWAYS takes, so that a cloud's
+    //     result does not depend on how many clouds share the launch.  Only the number of hypotheses handed to a wave follows the
+    //     launch size (a small launch spreads over 4x more waves); the order in which hypotheses run enters no result;
+    //   * eight lanes per fit (ANCSH_LM_LATENCY, explicit only): the long fits that set the launch's duration run ~1.25x faster
+    //     (measured on 64 x 200 fits: 1.27 vs 1.6 ms; the tail is MINPACK's serial lmpar on rank-deficient samples, which no lane
+    //     split shortens) at ~5 % lower pipeline throughput.
+    if (b.lm_schedule == ANCSH_LM_LATENCY) {
+        launch_twin(ransac_joint_lm_coop_kernel<KM>, ransac_joint_lm_coop_kind_kernel<KM>, b.joint_kind,
+                    dim3((b.niter + COOP_HYP_PER_WAVE - 1) / COOP_HYP_PER_WAVE, b.nprob), dim3(64), 0, st, b.rng0, b.rng1, c.src, c.tgt,
+                    b.joint_dir, b.niter, b.draws, key, b.models, b.lm_stat);
+    } else {
+        const int chunk = lm_chunk(b.nprob, b.niter);
+        launch_twin(ransac_joint_lm_kernel<KM>, ransac_joint_lm_kind_kernel<KM>, b.joint_kind, dim3((b.niter + chunk - 1) / chunk, b.nprob),
+                    dim3(64), 0, st, b.rng0, b.rng1, c.src, c.tgt, b.joint_dir, b.niter, b.draws, key, b.models, b.lm_stat, chunk);
+    }
+    launch_tail_b<KM>(c, key, sq_threshold_f64(b.th), E, st);
+    return check_launch("ransac_joint");
+}
+
+// Both stages on one stream, the LM fits and stage A's refit in ONE kernel: soa_quads, score_sreg, joint_init, pose_lm_finish_a (LM fits ||
+// stage A refit), joint_model, joint_verify, joint_finish -- seven launches where the two stages' own chains issue eight, and their bytes.
+template <int KM>
+static int launch_fused(const FitCall &c, KeyArg<KM> key_a, KeyArg<KM> key_b, const FitExtras &EA, const FitExtras &EB) {
+    const StageA &a = c.a; const StageB &b = c.b;
+    LmArgs L;
+    L.chunk = lm_chunk(b.nprob, b.niter);                               // the same rule as the LM launch of its own
+    L.chunks_per_prob = (b.niter + L.chunk - 1) / L.chunk;
+    const long n_chunks = (long)L.chunks_per_prob * b.nprob;
+    ANCSH_REQUIRE((n_chunks + 3) / 4 + a.nprob < (1L << 31), "pose_fit: %ld LM chunks + %d parts exceed one grid", n_chunks, a.nprob);
+    hipStream_t st = (hipStream_t)c.stream;                             // every check has passed: nothing above launches
+    const float th_a = sq_threshold_f32(a.th);
+    launch_score_a<KM>(c, key_a, th_a, st);
+    hipLaunchKernelGGL(ransac_joint_init_kernel<KM>, dim3((b.niter + 63) / 64, b.nprob), dim3(64), 0, st, b.rng0, b.rng1, c.src, c.tgt, b.niter,
+                       b.draws, key_b, b.scores, b.models);
+    L.rng0 = b.rng0; L.rng1 = b.rng1; L.joint_dir = b.joint_dir; L.niter = b.niter; L.draws = b.draws; L.models = b.models; L.lm_stat = b.lm_stat;
+    L.n_chunks = (int)n_chunks;
+    L.n_lm = (int)((n_chunks + 3) / 4);                                 // four waves, one chunk each, per LM block
+    FinishAArgs A;
+    A.off = a.off; A.th = th_a; A.niter = a.niter; A.draws = a.draws; A.scores = a.scores; A.max_n = c.max_n;
+    A.out_model = a.out_model; A.out_inliers = a.out_inliers; A.out_best = a.out_best;
+    const size_t lds = single_finish_lds(c.max_n);
+    const dim3 grid(L.n_lm + a.nprob);
+    // these twins take joint_kind in the middle of their arguments, so the pick is written out
+    if (b.joint_kind) launch_lds(pose_lm_finish_a_kind_kernel<KM>, grid, dim3(256), lds, st, c.src, c.tgt, L, key_b, b.joint_kind, A, key_a, EA);
+    else launch_lds(pose_lm_finish_a_kernel<KM>, grid, dim3(256), lds, st, c.src, c.tgt, L, key_b, A, key_a, EA);
+    launch_tail_b<KM>(c, key_b, sq_threshold_f64(b.th), EB, st);
+    return check_launch("pose_fit");
+}
+
+// The fused chain when both stages have problems and the schedule is not the eight-lane one (ANCSH_LM_LATENCY: another LM kernel);
+// otherwise the stages' own chains, stage B first, as PoseSolver.solve issues the two calls.
+template <int KM>
+static int launch_fit(const FitCall &c, const FitExtras &EA, const FitExtras &EB) {
+    const KeyArg<KM> key_a = key_arg<KM>(c.key_a, c.K), key_b = key_arg<KM>(c.key_b, c.K - 1);
+    const bool run_a = c.a.present && c.a.nprob != 0, run_b = c.b.present && c.b.nprob != 0;
+    if (run_a && run_b && c.b.lm_schedule != ANCSH_LM_LATENCY) return launch_fused<KM>(c, key_a, key_b, EA, EB);
+    if (int rc = run_b ? launch_stage_b<KM>(c, key_b, EB) : ANCSH_OK) return rc;
+    return run_a ? launch_stage_a<KM>(c, key_a, EA) : ANCSH_OK;
+}
+
+// The one checked path: every argument check of the stages that are present, before any launch.
+static int pose_fit(const FitCall &c) {
+    const StageA &a = c.a; const StageB &b = c.b;
+    if (int rc = check_keys(c)) return rc;
+    if (int rc = b.present ? check_joint_kind(c.who, b.nprob, b.joint_kind) : ANCSH_OK) return rc;
+    // record columns and tie counts.  In a whole fit a stage without problems writes nothing: its record geometry and window are not examined
+    FitExtras EA{}, EB{};                                   // all zero: no record, no tie counts, an empty window (no point is "borderline")
+    if (a.present && !(whole_fit(c) && a.nprob == 0))
+        if (int rc = make_extras(c, a.nprob, 1, a.tie, (double)a.th, (double)a.tie_window, EA)) return rc;
+    if (b.present && !(whole_fit(c) && b.nprob == 0))
+        if (int rc = make_extras(c, b.nprob, 2, b.tie, b.th, b.tie_window, EB)) return rc;
+    EB.draws = b.draws; EB.seed = key_word(c.key_b);       // stage B's finish kernel re-draws the contenders' samples for the tie count
+    if (int rc = a.present ? ransac_single_check(c) : ANCSH_OK) return rc;
+    if (int rc = b.present ? ransac_joint_check(c) : ANCSH_OK) return rc;
+    switch (key_mode(c)) {
+    case KEY_DSEED: return launch_fit<KEY_DSEED>(c, EA, EB);
+    case KEY_DKEY: return launch_fit<KEY_DKEY>(c, EA, EB);
+    default: return launch_fit<KEY_VALUE>(c, EA, EB);
+    }
+}
+
+// ---- the entries.  A stage's fields are filled in the order of StageA / StageB, which is the order of the parameters ------------------
+extern "C" int ancsh_ransac_single(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter, const int *draws,
+        unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores, void *stream) {
+    return pose_fit(FitCall{"ransac_single", src, tgt, max_n, nullptr, 0, stream,
+                            StageA{true, nprob, off, inlier_th, niter, draws, out_model, out_inliers, out_best, scratch_scores},
+                            FitKey{KEY_VALUE, seed}});
+}
+
+// ancsh_ransac_single with the hypotheses scored from SCALAR registers, out of a quad copy of the parts in scratch_quads: the same bits
+extern "C" int ancsh_ransac_single_ex(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter, const int *draws,
+        unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
+        long rows, void *stream) {
+    ANCSH_REQUIRE(scratch_quads, "ransac_single_ex: scratch_quads is NULL (ancsh_ransac_single is the call without it)");
+    return pose_fit(FitCall{"ransac_single_ex", src, tgt, max_n, nullptr, 0, stream,
+                            StageA{true, nprob, off, inlier_th, niter, draws, out_model, out_inliers, out_best, scratch_scores, scratch_quads, rows},
+                            FitKey{KEY_VALUE, seed}});
+}
+
+// ancsh_ransac_single_ex (scratch_quads != NULL) / ancsh_ransac_single (NULL) that ALSO writes each fit straight into the pose record
+// and / or reports how tie-sensitive it is (FitExtras above; include/ancsh_hip.h).  Everything else bit for bit as before.
+extern "C" int ancsh_ransac_single_rec(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter, const int *draws,
+        unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores, float *scratch_quads,
+        long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_single_rec", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob, off, inlier_th, niter, draws, out_model, out_inliers, out_best, scratch_scores, scratch_quads, rows,
+                                    tie_stats, tie_window}, FitKey{KEY_VALUE, seed}});
+}
+
+// ... with the generator key read from device memory (include/ancsh_hip.h): the kernels are the by-value ones instantiated with KEY_DSEED,
+// the key travels as the address in the same 64-bit argument
+extern "C" int ancsh_ransac_single_rec_dseed(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+        const int *draws, const unsigned long long *seed, int max_n, double *out_model, unsigned char *out_inliers, int *out_best,
+        int *scratch_scores, float *scratch_quads, long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_single_rec_dseed", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob, off, inlier_th, niter, draws, out_model, out_inliers, out_best, scratch_scores, scratch_quads, rows,
+                                    tie_stats, tie_window}, FitKey{KEY_DSEED, 0, seed}});
+}
+
+// ... with the key block of include/ancsh_hip.h (ancsh_stream_key): the KEY_DKEY instantiations, whose generator problem index is
+// prob + key->cloud_base * K (stage A) / prob + key->cloud_base * (K - 1) (stage B)
+extern "C" int ancsh_ransac_single_rec_dkey(int nprob, const int *off, const float *src, const float *tgt, float inlier_th, int niter,
+        const int *draws, const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers, int *out_best, int *scratch_scores,
+        float *scratch_quads, long rows, double *record, int K, int *tie_stats, float tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_single_rec_dkey", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob, off, inlier_th, niter, draws, out_model, out_inliers, out_best, scratch_scores, scratch_quads, rows,
+                                    tie_stats, tie_window}, FitKey{KEY_DKEY, 0, key}});
+}
+
+extern "C" int ancsh_ransac_joint(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, void *stream) {
+    return pose_fit(FitCall{"ransac_joint", src, tgt, max_n, nullptr, 0, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, ANCSH_LM_AUTO}, FitKey{KEY_VALUE, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_ex(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_ex", src, tgt, max_n, nullptr, 0, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule}, FitKey{KEY_VALUE, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_rec(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+        int *tie_stats, double tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window}, FitKey{KEY_VALUE, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_rec_dseed(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, const unsigned long long *seed, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+        int *tie_stats, double tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec_dseed", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window}, FitKey{KEY_DSEED, 0, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_rec_dkey(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, const ancsh_stream_key *key, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+        int *tie_stats, double tie_window, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec_dkey", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window}, FitKey{KEY_DKEY, 0, key}});
+}
+
+// The three record entries with a joint kind per problem (ABI 14, include/ancsh_hip.h): joint_kind NULL = the entry without it.
+extern "C" int ancsh_ransac_joint_rec_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt, const float *joint_dir,
+        double inlier_th, int niter, const int *draws, unsigned long long seed, int max_n, double *out_model, unsigned char *out_inliers,
+        int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule, double *record, int K,
+        int *tie_stats, double tie_window, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec_kind", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window, joint_kind},
+                            FitKey{KEY_VALUE, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_rec_dseed_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+        const float *joint_dir, double inlier_th, int niter, const int *draws, const unsigned long long *seed, int max_n, double *out_model,
+        unsigned char *out_inliers, int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule,
+        double *record, int K, int *tie_stats, double tie_window, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec_dseed_kind", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window, joint_kind},
+                            FitKey{KEY_DSEED, 0, seed}});
+}
+
+extern "C" int ancsh_ransac_joint_rec_dkey_kind(int nprob, const int *rng0, const int *rng1, const float *src, const float *tgt,
+        const float *joint_dir, double inlier_th, int niter, const int *draws, const ancsh_stream_key *key, int max_n, double *out_model,
+        unsigned char *out_inliers, int *out_best, double *out_score, double *scratch_scores, double *scratch_models, int *lm_stat, int lm_schedule,
+        double *record, int K, int *tie_stats, double tie_window, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"ransac_joint_rec_dkey_kind", src, tgt, max_n, record, K, stream, StageA{}, FitKey{},
+                            StageB{true, nprob, rng0, rng1, joint_dir, inlier_th, niter, draws, out_model, out_inliers, out_best, out_score,
+                                    scratch_scores, scratch_models, lm_stat, lm_schedule, tie_stats, tie_window, joint_kind},
+                            FitKey{KEY_DKEY, 0, key}});
+}
+
+// ---- the whole fit in one call: ancsh_ransac_single_rec*'s arguments without record / K, ancsh_ransac_joint_rec*'s without src / tgt /
+// max_n / record / K, then record, K and, in the *_kind entries, joint_kind.  Both stages are present, with or without problems.
+extern "C" int ancsh_pose_fit_rec(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a, const int *draws_a,
+        unsigned long long key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a, int *scratch_scores_a,
+        float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1, const float *joint_dir,
+        double inlier_th_b, int niter_b, const int *draws_b, unsigned long long key_b, double *out_model_b, unsigned char *out_inliers_b,
+        int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat, int lm_schedule, int *tie_stats_b,
+        double tie_window_b, double *record, int K, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_VALUE, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b},
+                            FitKey{KEY_VALUE, key_b}});
+}
+
+extern "C" int ancsh_pose_fit_rec_dseed(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const unsigned long long *key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1,
+        const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const unsigned long long *key_b, double *out_model_b,
+        unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat,
+        int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec_dseed", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_DSEED, 0, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b},
+                            FitKey{KEY_DSEED, 0, key_b}});
+}
+
+extern "C" int ancsh_pose_fit_rec_dkey(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const ancsh_stream_key *key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1,
+        const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const ancsh_stream_key *key_b, double *out_model_b,
+        unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat,
+        int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec_dkey", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_DKEY, 0, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b},
+                            FitKey{KEY_DKEY, 0, key_b}});
+}
+
+extern "C" int ancsh_pose_fit_rec_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, unsigned long long key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1,
+        const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, unsigned long long key_b, double *out_model_b,
+        unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat,
+        int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec_kind", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_VALUE, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b, joint_kind},
+                            FitKey{KEY_VALUE, key_b}});
+}
+
+extern "C" int ancsh_pose_fit_rec_dseed_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const unsigned long long *key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1,
+        const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const unsigned long long *key_b, double *out_model_b,
+        unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat,
+        int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec_dseed_kind", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_DSEED, 0, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b, joint_kind},
+                            FitKey{KEY_DSEED, 0, key_b}});
+}
+
+extern "C" int ancsh_pose_fit_rec_dkey_kind(int nprob_a, const int *off, const float *src, const float *tgt, float inlier_th_a, int niter_a,
+        const int *draws_a, const ancsh_stream_key *key_a, int max_n, double *out_model_a, unsigned char *out_inliers_a, int *out_best_a,
+        int *scratch_scores_a, float *scratch_quads, long rows, int *tie_stats_a, float tie_window_a, int nprob_b, const int *rng0, const int *rng1,
+        const float *joint_dir, double inlier_th_b, int niter_b, const int *draws_b, const ancsh_stream_key *key_b, double *out_model_b,
+        unsigned char *out_inliers_b, int *out_best_b, double *out_score_b, double *scratch_scores_b, double *scratch_models_b, int *lm_stat,
+        int lm_schedule, int *tie_stats_b, double tie_window_b, double *record, int K, const int *joint_kind, void *stream) {
+    return pose_fit(FitCall{"pose_fit_rec_dkey_kind", src, tgt, max_n, record, K, stream,
+                            StageA{true, nprob_a, off, inlier_th_a, niter_a, draws_a, out_model_a, out_inliers_a, out_best_a, scratch_scores_a,
+                                    scratch_quads, rows, tie_stats_a, tie_window_a}, FitKey{KEY_DKEY, 0, key_a},
+                            StageB{true, nprob_b, rng0, rng1, joint_dir, inlier_th_b, niter_b, draws_b, out_model_b, out_inliers_b, out_best_b,
+                                    out_score_b, scratch_scores_b, scratch_models_b, lm_stat, lm_schedule, tie_stats_b, tie_window_b, joint_kind},
+                            FitKey{KEY_DKEY, 0, key_b}});
 }

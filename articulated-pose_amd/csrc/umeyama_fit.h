@@ -1,5 +1,5 @@
 // umeyama_fit.h -- estimateSimilarityUmeyama (lib/aligning.py:580-622) for one (source, target) point set per workgroup of 256 threads,
-// float64, stated ONCE for umeyama_kernel (pose.hip, behind ancsh_umeyama) and gt_pose_kernel (gt_pose.hip, behind ancsh_gt_pose_build),
+// float64, stated ONCE for umeyama_kernel (pose_glue.hip, behind ancsh_umeyama) and gt_pose_kernel (gt_pose.hip, behind ancsh_gt_pose_build),
 // with the block reductions both use.  The passes are STATEMENT MACROS (as csrc/part_stats.h and ANCSH_JD_COMPACT): expanded in place
 // they give umeyama_kernel the statements it had before the second kernel, and the second kernel the same statements in the same order
 // -- thread t takes rows t, t + 256, ..., block_sum<6> then block_sum<10>, horn_quat / quat_to_mat on one lane -- so both write the

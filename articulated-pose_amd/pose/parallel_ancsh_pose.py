@@ -34,6 +34,23 @@ def _f32(t, dev):
 TIE_WINDOW = 32 * 2.0 ** -27      # default half-width of the tie window on the residual norm: 32 ulp of the float32 threshold 0.1 (2.4e-7)
 
 
+def _fit_entry(base, seed, seed_dev=None, key_dev=None, joint_kind=None, nprob_b=0):
+    """The entry of one family (`base`: ancsh_ransac_single_rec, ancsh_ransac_joint_rec, ancsh_pose_fit_rec) for a key mode and a joint
+    kind: key_dev -> base_dkey, seed_dev -> base_dseed, neither -> base with `seed` by value; a joint_kind array (one entry per joint
+    problem, nprob_b of them) -> ..._kind, with the array as the last argument.  -> (entry name, key argument, trailing arguments)."""
+    if key_dev is not None:
+        name, key = base + "_dkey", _lib.ptr(key_dev)
+    elif seed_dev is not None:
+        name, key = base + "_dseed", _lib.ptr(seed_dev)
+    else:
+        name, key = base, int(seed)
+    if joint_kind is None:
+        return name, key, []
+    if joint_kind.dtype != torch.int32 or joint_kind.numel() != nprob_b or not joint_kind.is_contiguous():
+        raise ValueError("joint_kind must be a contiguous int32 tensor of %d entries (one per problem)" % nprob_b)
+    return name + "_kind", key, [_lib.ptr(joint_kind)]
+
+
 def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max_n=None, scalar_points=True, record=None, K=0,
                         tie_window=None, seed_dev=None, key_dev=None):
     """Batched ransac(dataset, single_transformation_estimator, single_transformation_verifier, th, niter).
@@ -58,26 +75,19 @@ def ransac_single_batch(off, src, tgt, inlier_th, niter, draws=None, seed=0, max
     d = None if draws is None else _i32(draws, dev)
     if d is not None and d.numel() != nprob * niter * 3:
         raise ValueError("draws must have shape (nprob, niter, 3)")
-    quads, tie = None, None
-    if scalar_points:
-        quads = torch.empty((_lib.lib().ancsh_ransac_single_quads_floats(rows, nprob),), dtype=torch.float32, device=dev)
-    if key_dev is not None or seed_dev is not None:
-        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_single_rec_dkey" if key_dev is not None else "ancsh_ransac_single_rec_dseed", nprob, _lib.ptr(off),
-                  _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter), _lib.ptr(d), _lib.ptr(key_dev if key_dev is not None else seed_dev),
-                  max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores), _lib.ptr(quads),
-                  rows, _lib.ptr(record), int(K), _lib.ptr(tie), float(tie_window or 0.0))
-    elif record is not None or tie_window is not None:
-        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_single_rec", nprob, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter),
-                  _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores), _lib.ptr(quads), rows,
-                  _lib.ptr(record), int(K), _lib.ptr(tie), float(tie_window or 0.0))
-    elif scalar_points:
-        _lib.call("ancsh_ransac_single_ex", nprob, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter),
-                  _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores), _lib.ptr(quads), rows)
-    else:
-        _lib.call("ancsh_ransac_single", nprob, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter),
-                  _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores))
+    tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
+    quads = torch.empty((_lib.lib().ancsh_ransac_single_quads_floats(rows, nprob),), dtype=torch.float32, device=dev) if scalar_points else None
+    # the record entries take everything; without a record, a tie window or a device key the two older entries are called
+    rec = key_dev is not None or seed_dev is not None or record is not None or tie_window is not None
+    name, key, _ = _fit_entry("ancsh_ransac_single_rec", seed, seed_dev, key_dev) if rec else \
+        ("ancsh_ransac_single_ex" if scalar_points else "ancsh_ransac_single", int(seed), [])
+    args = [nprob, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter), _lib.ptr(d), key, max_n, _lib.ptr(model),
+            _lib.ptr(inl), _lib.ptr(best), _lib.ptr(scores)]
+    if rec or scalar_points:
+        args += [_lib.ptr(quads), rows]
+    if rec:
+        args += [_lib.ptr(record), int(K), _lib.ptr(tie), float(tie_window or 0.0)]
+    _lib.call(name, *args)
     return dict(model=model, inliers=inl, best=best, scores=scores.view(nprob, niter), tie=tie, _keep=(d, scores, quads))
 
 
@@ -142,35 +152,16 @@ def ransac_joint_batch(rng0, rng1, src, tgt, joint_dir, inlier_th, niter, draws=
     d = None if draws is None else _i32(draws, dev)
     if d is not None and d.numel() != nprob * niter * 6:
         raise ValueError("draws must have shape (nprob, niter, 6)")
-    tie = None
-    if joint_kind is not None:
-        if joint_kind.dtype != torch.int32 or joint_kind.numel() != nprob or not joint_kind.is_contiguous():
-            raise ValueError("joint_kind must be a contiguous int32 tensor of %d entries (one per problem)" % nprob)
-        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        name, key = (("ancsh_ransac_joint_rec_dkey_kind", _lib.ptr(key_dev)) if key_dev is not None else
-                     ("ancsh_ransac_joint_rec_dseed_kind", _lib.ptr(seed_dev)) if seed_dev is not None else
-                     ("ancsh_ransac_joint_rec_kind", int(seed)))
-        _lib.call(name, nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th),
-                  int(niter), _lib.ptr(d), key, max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(score), _lib.ptr(sc),
-                  _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule], _lib.ptr(record), int(K), _lib.ptr(tie),
-                  float(tie_window or 0.0), _lib.ptr(joint_kind))
-    elif key_dev is not None or seed_dev is not None:
-        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_joint_rec_dkey" if key_dev is not None else "ancsh_ransac_joint_rec_dseed", nprob, _lib.ptr(rng0),
-                  _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th), int(niter), _lib.ptr(d),
-                  _lib.ptr(key_dev if key_dev is not None else seed_dev), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
-                  _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule], _lib.ptr(record), int(K),
-                  _lib.ptr(tie), float(tie_window or 0.0))
-    elif record is not None or tie_window is not None:      # the finish kernel also fills the record's nonlinear columns / the tie counts
-        tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
-        _lib.call("ancsh_ransac_joint_rec", nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir),
-                  float(inlier_th), int(niter), _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
-                  _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule], _lib.ptr(record), int(K),
-                  _lib.ptr(tie), float(tie_window or 0.0))
-    else:
-        _lib.call("ancsh_ransac_joint_ex", nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir),
-                  float(inlier_th), int(niter), _lib.ptr(d), int(seed), max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best),
-                  _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat), LM_SCHEDULES[lm_schedule])
+    tie = torch.empty((nprob, 2), dtype=torch.int32, device=dev) if tie_window is not None else None
+    # the record entries: their finish kernel also fills the record's nonlinear columns / the tie counts
+    rec = joint_kind is not None or key_dev is not None or seed_dev is not None or record is not None or tie_window is not None
+    name, key, kind = _fit_entry("ancsh_ransac_joint_rec", seed, seed_dev, key_dev, joint_kind, nprob) if rec else ("ancsh_ransac_joint_ex", int(seed), [])
+    args = [nprob, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(joint_dir), float(inlier_th), int(niter), _lib.ptr(d),
+            key, max_n, _lib.ptr(model), _lib.ptr(inl), _lib.ptr(best), _lib.ptr(score), _lib.ptr(sc), _lib.ptr(mo), _lib.ptr(stat),
+            LM_SCHEDULES[lm_schedule]]
+    if rec:
+        args += [_lib.ptr(record), int(K), _lib.ptr(tie), float(tie_window or 0.0)] + kind
+    _lib.call(name, *args)
     return dict(model=model, inliers=inl, best=best, score=score, lm_stat=stat, hyp_models=mo, hyp_scores=sc, tie=tie, _keep=(d, joint_kind))
 
 
@@ -197,20 +188,13 @@ def pose_fit_batch(off, rng0, rng1, src, tgt, joint_dir, inlier_th, niter_a, nit
         raise ValueError("draws_a must have shape (nprob_a, niter_a, 3)")
     if db is not None and db.numel() != npb * niter_b * 6:
         raise ValueError("draws_b must have shape (nprob_b, niter_b, 6)")
-    if joint_kind is not None and (joint_kind.dtype != torch.int32 or joint_kind.numel() != npb or not joint_kind.is_contiguous()):
-        raise ValueError("joint_kind must be a contiguous int32 tensor of %d entries (one per problem)" % npb)
-    if key_dev is not None:
-        name, key_a, key_b = "ancsh_pose_fit_rec_dkey", _lib.ptr(key_dev), _lib.ptr(key_dev)
-    elif seed_dev is not None:
-        name, key_a, key_b = "ancsh_pose_fit_rec_dseed", _lib.ptr(seed_dev), _lib.ptr(seed_dev)
-    else:
-        name, key_a, key_b = "ancsh_pose_fit_rec", int(seed), int(seed) + 1
-    _lib.call(name + ("_kind" if joint_kind is not None else ""),
-              npa, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter_a), _lib.ptr(da), key_a, max_n, _lib.ptr(model_a),
-              _lib.ptr(inl_a), _lib.ptr(best_a), _lib.ptr(scores_a), _lib.ptr(quads), rows, _lib.ptr(tie_a), float(tie_window or 0.0),
-              npb, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(joint_dir), float(inlier_th), int(niter_b), _lib.ptr(db), key_b, _lib.ptr(model_b),
-              _lib.ptr(inl_b), _lib.ptr(best_b), _lib.ptr(score_b), _lib.ptr(sc_b), _lib.ptr(mo_b), _lib.ptr(stat), LM_SCHEDULES[lm_schedule],
-              _lib.ptr(tie_b), float(tie_window or 0.0), _lib.ptr(record), int(K), *([_lib.ptr(joint_kind)] if joint_kind is not None else []))
+    name, key_a, kind = _fit_entry("ancsh_pose_fit_rec", seed, seed_dev, key_dev, joint_kind, npb)
+    key_b = key_a + 1 if key_dev is None and seed_dev is None else key_a      # by value stage B takes seed + 1; on the device the kernels add it
+    _lib.call(name, npa, _lib.ptr(off), _lib.ptr(src), _lib.ptr(tgt), float(inlier_th), int(niter_a), _lib.ptr(da), key_a, max_n,
+              _lib.ptr(model_a), _lib.ptr(inl_a), _lib.ptr(best_a), _lib.ptr(scores_a), _lib.ptr(quads), rows, _lib.ptr(tie_a),
+              float(tie_window or 0.0), npb, _lib.ptr(rng0), _lib.ptr(rng1), _lib.ptr(joint_dir), float(inlier_th), int(niter_b), _lib.ptr(db),
+              key_b, _lib.ptr(model_b), _lib.ptr(inl_b), _lib.ptr(best_b), _lib.ptr(score_b), _lib.ptr(sc_b), _lib.ptr(mo_b), _lib.ptr(stat),
+              LM_SCHEDULES[lm_schedule], _lib.ptr(tie_b), float(tie_window or 0.0), _lib.ptr(record), int(K), *kind)
     return (dict(model=model_a, inliers=inl_a, best=best_a, scores=scores_a.view(npa, niter_a), tie=tie_a, _keep=(da, scores_a, quads)),
             dict(model=model_b, inliers=inl_b, best=best_b, score=score_b, lm_stat=stat, hyp_models=mo_b, hyp_scores=sc_b, tie=tie_b,
                  _keep=(db, joint_kind)))

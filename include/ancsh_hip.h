@@ -494,6 +494,25 @@ int ancsh_pose_joint_direction(int b, int n, int K, const float *joint_axis, con
 int ancsh_pose_joint_direction_pred(int b, int n, int K, int joint_channels, const float *joint_axis, const float *joint_index,
                                     float *out, void *stream);
 
+/* THE FIT ENTRIES AT A GLANCE.  Nineteen entries, one fit: each is the per-part fit (stage A, ancsh_ransac_single*), the per-joint fit
+ * (stage B, ancsh_ransac_joint*) or both in one call (ancsh_pose_fit_rec*), with the generator key passed in one of three ways and,
+ * for stage B, an optional joint kind per problem.  The blocks below state each rule once, where it first applies.
+ *
+ *   key mode    suffix   key argument                            stage A reads       stage B reads       problem index of the generator
+ *   by value    (none)   unsigned long long seed                 seed                seed (the caller    prob
+ *                                                                                    passes s + 1)
+ *   device seed _dseed   const unsigned long long *seed          *seed               *seed + 1           prob
+ *   key block   _dkey    const ancsh_stream_key *key (needs K)   key->seed           key->seed + 1       prob + key->cloud_base * K  (stage A)
+ *                                                                                                        prob + key->cloud_base * (K - 1)  (B)
+ *
+ *   stage A: ancsh_ransac_single, _ex (+ scratch_quads, rows), _rec (+ record, K, tie_stats, tie_window), _rec_dseed, _rec_dkey
+ *   stage B: ancsh_ransac_joint, _ex (+ lm_schedule), _rec (+ record, K, tie_stats, tie_window), _rec_dseed, _rec_dkey
+ *   both:    ancsh_pose_fit_rec, _rec_dseed, _rec_dkey
+ *   _kind behind any stage-B or whole-fit _rec name: one more argument, const int *joint_kind, before the stream (NULL = the entry
+ *   without the suffix).
+ * All of them are adapters over one host-side description of a fit call (csrc/pose.hip): the same argument checks in the same order,
+ * the same launches. */
+
 /* Batched replacement of ransac(dataset, single_transformation_estimator, single_transformation_verifier,
  * inlier_th, niter) (:20-54, with transform_pts / rotate_pts / scale_pts of lib/d3_utils.py:206-246).
  * Problem p = rows [off[p], off[p+1]) of src/tgt (float32 (rows,3)).  draws (nprob, niter, 3) int32 =
