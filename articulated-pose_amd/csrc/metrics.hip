@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void joint_params_kernel(int n, int K, int G, 
     __syncthreads();
     ANCSH_SORT_VOTE_COLUMNS(jp_vals, npow2, cnt)
     if (threadIdx.x < 6) {
-        ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, threadIdx.x)
+        ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, p2, threadIdx.x)
         if (threadIdx.x >= 3) o[threadIdx.x - 3] = med;            // joint point
         else if (!axis_mean) o[3 + threadIdx.x] = med;            // joint axis
     }
@@ -157,19 +157,6 @@ __global__ __launch_bounds__(256) void part_extents_kernel(int n, int K, int C, 
             scale_pred[o * 3 + k] = c > 0 ? 2.0f * np_maxf(np_maxf(smax[0][j][k], smax[1][j][k]), np_maxf(smax[2][j][k], smax[3][j][k])) : NAN;
         dynam[o] = c > 0 ? np_min(np_min(smin[0][j], smin[1][j]), np_min(smin[2][j], smin[3][j])) : NAN;
     }
-}
-
-// np.argmax of a row of C floats: the first maximum, or the first NaN (numpy and torch.argmax rank NaN above every number)
-__device__ __forceinline__ int argmax_first_nan(const float *m, int C) {
-    float best = m[0];
-    if (best != best) return 0;
-    int c = 0;
-    for (int k = 1; k < C; ++k) {
-        const float v = m[k];
-        if (v != v) return k;
-        if (v > best) { best = v; c = k; }
-    }
-    return c;
 }
 
 // ---- articulation block of the streamed step (pred side of compute_miou.py:196-222 and eval_joint_params.py:143-220) ----------------
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(256) void articulation_kernel(int n, int K, int G, 
     ANCSH_SORT_VOTE_COLUMNS(art_vals, npow2, cnt)          // ends on a barrier: sst is visible too
     __shared__ double smed[6];
     if (threadIdx.x < 6) {
-        ANCSH_VOTE_MEDIAN(med, art_vals, npow2, cnt, threadIdx.x)
+        ANCSH_VOTE_MEDIAN(med, art_vals, npow2, cnt, p2, threadIdx.x)
         smed[threadIdx.x] = med;                           // 0..2 axis, 3..5 pivot
     }
     __syncthreads();

@@ -1,5 +1,7 @@
 // part_stats.h -- per-part and per-joint statistics of one cloud, shared by the evaluation kernels of metrics.hip (joint_params_kernel,
-// part_extents_kernel, articulation_kernel) and by joint_state_kernel of joint_state.hip (workgroups of 256 threads, four waves of 64).
+// part_extents_kernel, articulation_kernel), by joint_state_kernel of joint_state.hip, gt_error_kernel of gt_errors.hip and the joint pass
+// of point_gt.hip (workgroups of 256 threads, four waves of 64).  The passes stand in for numpy calls and follow numpy at the edges:
+// np.argmax labels (argmax_first_nan), np.median of a column with a NaN (vote_above, ANCSH_VOTE_MEDIAN), np.std in two passes.
 // The passes are STATEMENT MACROS, not inline functions: a force-inlined device function is simplified on its own before it is inlined,
 // and that alone changes the code the compiler makes of the kernels that existed before this header (measured: part_extents_kernel
 // 3830 -> 3642 instructions with its unchanged body behind one inline call).  Expanded in place, the macros give those kernels the
@@ -9,13 +11,22 @@
 
 namespace ancsh {
 
-template <int K_MAX>
-__device__ __forceinline__ int argmax_row(const float *m, int K) {
-    int c = 0;
+// np.argmax of a row of C floats: the first maximum, or the first NaN (numpy and torch.argmax rank NaN above every number).  Every label
+// of the evaluation kernels -- a point's part from its mask row, its joint class from the joint-index head -- is taken with this rule.
+__device__ __forceinline__ int argmax_first_nan(const float *m, int C) {
     float best = m[0];
-    for (int k = 1; k < K; ++k) { const float v = m[k]; if (v > best) { best = v; c = k; } }    // np.argmax: first maximum
+    if (best != best) return 0;
+    int c = 0;
+    for (int k = 1; k < C; ++k) {
+        const float v = m[k];
+        if (v != v) return k;
+        if (v > best) { best = v; c = k; }
+    }
     return c;
 }
+
+// a > b in numpy's sort order: NaN above +inf (NaNs equal among themselves)
+__device__ __forceinline__ bool vote_above(float a, float b) { return a > b || (a != a && b == b); }
 
 __device__ __forceinline__ double block_sum_f64(double v, double *red) {
 #pragma unroll
@@ -36,24 +47,36 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
 // ---- similarity global NOCS -> part NOCS of part j (evaluation/eval_joint_params.py:160-171) ------------------------------------
 //   x = global NOCS (G = 3 shared or 3K per-part channels), y = part NOCS (3K) of the points whose mask row has its first maximum at j
 //   (every point is part 0 when mask is NULL):  scale_j = std(mean(y, axis=1)) / std(mean(x, axis=1)),
-//   translation_j = mean(y - scale_j * x, axis=0).  Reductions in float64 through red (4 doubles of LDS).
+//   translation_j = mean(y - scale_j * x, axis=0).  Reductions in float64 through red (4 doubles of LDS); std in two passes, so that a part
+//   whose row means are all the same float32 value has a std of exactly 0 (scale inf or NaN, as numpy's).  A NaN in a mask row is the
+//   point's label (np.argmax: the first NaN).
 // Thread 0 stores scale, translation (NaN for an empty part) to the four doubles at OUT (an expression, evaluated by thread 0 only).
 #define ANCSH_PART_SIMILARITY(n, K, G, j, p0, gocs, nocs, mask, red, OUT)                                                              \
     double sx = 0, sxx = 0, sy = 0, syy = 0, m = 0;                                                                               \
     for (int i = threadIdx.x; i < n; i += 256) {                                                                                  \
-        const int c = mask ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;                                                           \
+        const int c = mask ? argmax_first_nan(mask + (p0 + i) * K, K) : 0;                                                        \
         if (c != j) continue;                                                                                                     \
         const float *x = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * j), *y = nocs + (p0 + i) * 3 * K + 3 * j;                       \
         const float xm = ((x[0] + x[1]) + x[2]) / 3.0f, ym = ((y[0] + y[1]) + y[2]) / 3.0f;    /* np.mean(., axis=1), float32 */ \
-        sx += xm; sxx += (double)xm * xm; sy += ym; syy += (double)ym * ym; m += 1.0;                                             \
+        sx += xm; sy += ym; m += 1.0;                                                                                             \
     }                                                                                                                             \
-    sx = block_sum_f64(sx, red); sxx = block_sum_f64(sxx, red); sy = block_sum_f64(sy, red); syy = block_sum_f64(syy, red);       \
-    m = block_sum_f64(m, red);                                                                                                    \
-    const double vx = sxx / m - (sx / m) * (sx / m), vy = syy / m - (sy / m) * (sy / m);                                          \
-    const float scale = (float)sqrt(vy > 0 ? vy : 0.0) / (float)sqrt(vx > 0 ? vx : 0.0);    /* float32 / float32 (np.std) */      \
+    sx = block_sum_f64(sx, red); sy = block_sum_f64(sy, red); m = block_sum_f64(m, red);                                          \
+    /* two passes like np.std: the deviations from the mean, not sxx / m - (sx / m)^2, whose cancellation leaves a part of bit-equal */ \
+    /* row means a variance of some 1e-17 instead of 0 (m equal float32 values sum exactly in float64, and (m v) / m == v) */     \
+    const double mx = sx / m, my = sy / m;                                                                                        \
+    for (int i = threadIdx.x; i < n; i += 256) {                                                                                  \
+        const int c = mask ? argmax_first_nan(mask + (p0 + i) * K, K) : 0;                                                        \
+        if (c != j) continue;                                                                                                     \
+        const float *x = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * j), *y = nocs + (p0 + i) * 3 * K + 3 * j;                       \
+        const float xm = ((x[0] + x[1]) + x[2]) / 3.0f, ym = ((y[0] + y[1]) + y[2]) / 3.0f;                                       \
+        const double dx = (double)xm - mx, dy = (double)ym - my;                                                                  \
+        sxx += dx * dx; syy += dy * dy;                                                                                           \
+    }                                                                                                                             \
+    sxx = block_sum_f64(sxx, red); syy = block_sum_f64(syy, red);                                                                 \
+    const float scale = (float)sqrt(syy / m) / (float)sqrt(sxx / m);                        /* float32 / float32 (np.std) */      \
     double t[3] = {0, 0, 0};                                                                                                      \
     for (int i = threadIdx.x; i < n; i += 256) {                                                                                  \
-        const int c = mask ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;                                                           \
+        const int c = mask ? argmax_first_nan(mask + (p0 + i) * K, K) : 0;                                                        \
         if (c != j) continue;                                                                                                     \
         const float *x = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * j), *y = nocs + (p0 + i) * 3 * K + 3 * j;                       \
         _Pragma("unroll") for (int c3 = 0; c3 < 3; ++c3) t[c3] += (double)(y[c3] - scale * x[c3]);                               \
@@ -81,7 +104,7 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
         for (int w = 0; w < wave; ++w) start += wcnt[w];                                                                              \
         if (f) {                                                                                                                      \
             const int pos = start + __builtin_amdgcn_mbcnt_hi((unsigned)(mm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mm, 0));     \
-            const int c = (mask && G != 3) ? argmax_row<8>(mask + (p0 + i) * K, K) : 0;                                               \
+            const int c = (mask && G != 3) ? argmax_first_nan(mask + (p0 + i) * K, K) : 0;                                            \
             const float *g = gocs + (p0 + i) * G + (G == 3 ? 0 : 3 * c);                                                              \
             const float w1 = 1.0f - heatmap[p0 + i];                                                                                  \
             _Pragma("unroll") for (int c3 = 0; c3 < 3; ++c3) {                                                                        \
@@ -93,7 +116,9 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
         cnt += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];                                                                                 \
     }
 
-// pads the six columns' [cnt, next power of two) with +inf and bitonic-sorts each column in place; ends on a barrier
+// pads the six columns' [cnt, p2 = next power of two) with +inf and bitonic-sorts each column in place, in numpy's order (vote_above: NaN
+// above +inf -- with a plain `a > b` a NaN answers "no" both ways and the network no longer sorts the column); ends on a barrier.  A column
+// with a NaN vote ends with a NaN in slot p2 - 1, which is how ANCSH_VOTE_MEDIAN finds it.  Declares p2.
 #define ANCSH_SORT_VOTE_COLUMNS(jp_vals, npow2, cnt)                                                                                  \
     int p2 = 1;                                                                                                                   \
     while (p2 < cnt) p2 <<= 1;                                                                                                    \
@@ -109,7 +134,7 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
                     _Pragma("unroll") for (int c = 0; c < 6; ++c) {                                                               \
                         float *v = jp_vals + c * npow2;                                                                           \
                         const float a = v[e], bb = v[partner];                                                                    \
-                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }                                                        \
+                        if (vote_above(a, bb) == up) { v[e] = bb; v[partner] = a; }                                               \
                     }                                                                                                             \
                 }                                                                                                                 \
             }                                                                                                                     \
@@ -133,18 +158,20 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
                     _Pragma("unroll") for (int c = (C0); c < 6; ++c) {                                                            \
                         float *v = jp_vals + c * npow2;                                                                           \
                         const float a = v[e], bb = v[partner];                                                                    \
-                        if ((a > bb) == up) { v[e] = bb; v[partner] = a; }                                                        \
+                        if (vote_above(a, bb) == up) { v[e] = bb; v[partner] = a; }                                               \
                     }                                                                                                             \
                 }                                                                                                                 \
             }                                                                                                                     \
             __syncthreads();                                                                                                      \
         }
 
-// med = np.median of sorted column c: the middle element, or the float32 mean of the middle two; NaN without votes
-#define ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, c)                                                                                \
+// med = np.median of sorted column c: the middle element, or the float32 mean of the middle two; NaN without votes, and NaN when any vote of
+// the column is a NaN (the sort left it in the last of the p2 padded slots)
+#define ANCSH_VOTE_MEDIAN(med, jp_vals, npow2, cnt, p2, c)                                                                            \
     const float *med##_v = jp_vals + (c) * npow2;                                                                                     \
     float med = NAN;                                                                                                                  \
-    if (cnt > 0) med = (cnt & 1) ? med##_v[cnt / 2] : (med##_v[cnt / 2 - 1] + med##_v[cnt / 2]) * 0.5f;
+    if (cnt > 0 && med##_v[p2 - 1] == med##_v[p2 - 1])                                                                                \
+        med = (cnt & 1) ? med##_v[cnt / 2] : (med##_v[cnt / 2 - 1] + med##_v[cnt / 2]) * 0.5f;
 
 // ---- part 0's pose as the boundary pass reads it (eval_pose_err.py:253-268): R = 9 doubles row-major, t = 3 doubles, rounded to float32
 // like compose_rt (:25-30); declares r00 r10 r20 = the first column of R, t0 t1 t2 = the rounded translation and m30 = the inverse's
@@ -167,7 +194,7 @@ __device__ __forceinline__ double np_min(double a, double b) { return a != a ? a
         int cnt[KM];                                                                                                                  \
         _Pragma("unroll") for (int j = 0; j < KM; ++j) { m[j][0] = m[j][1] = m[j][2] = -INFINITY; mn[j] = INFINITY; cnt[j] = 0; }    \
         for (int i = threadIdx.x; i < n; i += 256) {                                                                                  \
-            const int c = argmax_row<KM>(mask + (p0 + i) * K, K);                                                                     \
+            const int c = argmax_first_nan(mask + (p0 + i) * K, K);                                                                  \
             const float *q = nocs + (p0 + i) * C + (C == 3 ? 0 : 3 * c);                                                              \
             const float a0 = fabsf(q[0] - 0.5f), a1 = fabsf(q[1] - 0.5f), a2 = fabsf(q[2] - 0.5f);                                    \
             double v = 0.0;                                                                                                           \

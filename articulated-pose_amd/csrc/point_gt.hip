@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void point_gt_kernel(PointGtArgs a) {
         __syncthreads();
         ANCSH_SORT_VOTE_COLUMNS_FROM(pg_vals, npow2, cnt, 3)      // the pivot's three columns: the axis is the mean taken above
         if (tid >= 3 && tid < 6) {
-            ANCSH_VOTE_MEDIAN(med, pg_vals, npow2, cnt, tid)
+            ANCSH_VOTE_MEDIAN(med, pg_vals, npow2, cnt, p2, tid)
             sjoint[j][tid - 3] = med;
         }
         __syncthreads();                             // the columns are free for the next joint; sjoint[j] is visible

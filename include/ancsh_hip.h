@@ -794,7 +794,10 @@ int ancsh_iou_3d(int npairs, int nres, const double *bbox1, const double *bbox2,
  * joint (b,K-1,6) float64: [joint point (3) | joint axis (3)] of joint j = 1..K-1 in global-NOCS space: per-channel median over
  *   the points of joint class j of  gocs + unitvec * (1 - heatmap) * 0.2  and of joint_axis (:176-187); axis_mean != 0 = the
  *   ground-truth variant (:189-199): the axis is the float32 mean instead of the median.  mask may be NULL when gocs_channels == 3.
- * Element arithmetic in float32 in numpy's order; medians are exact selections; NaN rows for a joint class without points. */
+ * Element arithmetic in float32 in numpy's order; medians are exact selections; NaN rows for a joint class without points.
+ * numpy's rules at the edges: a NaN in a mask row is that point's label (np.argmax: the first maximum, or the first NaN); a channel
+ * with a NaN vote has a NaN median (np.median; +-inf votes sort as numbers, an even count's -inf and +inf middle gives NaN); the std is
+ * taken in two passes, so a part whose row means are all the same float32 value has std exactly 0 and a scale of inf or NaN. */
 int ancsh_joint_params(int b, int n, int K, int gocs_channels, int axis_mean, const float *gocs, const float *nocs,
                        const float *mask, const float *heatmap, const float *unitvec, const float *joint_axis,
                        const int *joint_cls, double *st, double *joint, void *stream);
@@ -805,7 +808,8 @@ int ancsh_joint_params(int b, int n, int K, int gocs_channels, int axis_mean, co
  * floats whose first three are the point; pose0 (b,12) float64 = part 0's fitted rotation row-major (9) and translation (3), rounded
  * to float32 inside like the reference's compose_rt.  Outputs per (cloud, part): scale_pred (b,K,3) float32 = 2 * max |nocs - 0.5|,
  * dynam (b,K) float64 = min x of the part's points in part 0's frame (the "dynamic boundary"), count (b,K) points of the part
- * (0 -> NaN outputs; the reference drops such a frame through its bare except).  K <= 8. */
+ * (0 -> NaN outputs; the reference drops such a frame through its bare except).  K <= 8.  A NaN in a mask row is that point's label
+ * (np.argmax: the first NaN ranks above every number). */
 int ancsh_part_extents(int b, int n, int K, int nocs_channels, const float *nocs, const float *mask, const float *P, int ldp,
                        const double *pose0, float *scale_pred, double *dynam, int *count, void *stream);
 
@@ -822,7 +826,8 @@ int ancsh_part_extents(int b, int n, int K, int nocs_channels, const float *nocs
  *          (s2, t2) = part 0's similarity global -> part NOCS (ancsh_joint_params' st row 0)     (eval_joint_params.py:143-187, 214-219)
  *   9..11  (j >= 1) axis R_0 a_j: a_j = per-channel median of joint_axis over the same points, not normalised        (:176-187, 220)
  *   row 0's 6..11 NaN.  An empty part / joint class: NaN in its own columns; a NaN in part 0's nonlinear pose (a poisoned record):
- *   the cloud's whole block NaN.  K = 1: box columns only.
+ *   the cloud's whole block NaN.  K = 1: box columns only.  Labels, medians and the similarity follow ancsh_joint_params' rules: a NaN
+ *   in a mask or joint_index row is the label (first NaN), a NaN vote makes its channel's median NaN, the std is taken in two passes.
  * Optional (NULL to skip), bit-equal to the offline kernels: joint_nocs (b,K-1,6) = ancsh_joint_params' joint, st0 (b,4) = its st row 0
  * (NaN for K = 1), extent (b,K,3) float32 = ancsh_part_extents' scale_pred.  K <= 8, n <= ANCSH_ARTICULATION_MAX_N (LDS-resident medians:
  * 6 columns of the next power of two of n floats). */

@@ -25,7 +25,8 @@ def st_and_joints(gocs, nocs, mask_pred, heatmap, unitvec, orient, joint_cls, K)
         idx = np.where(joint_cls == j)[0]
         axes.append(np.median(orient[idx], axis=0))
         pts.append(np.median(joint_pts[idx], axis=0))
-    return np.array(scale), np.stack(trans), np.stack(pts), np.stack(axes)
+    none = np.zeros((0, 3), np.float32)                                           # K == 1: no joints (np.stack refuses an empty list)
+    return np.array(scale), np.stack(trans), np.stack(pts) if pts else none, np.stack(axes) if axes else none
 
 
 def gt_joints(nocs_gt_g, heatmap_gt, unitvec_gt, orient_gt, joint_cls_gt, K):      # :189-199

@@ -169,6 +169,16 @@ def test_pose_fit_under_redzones(dev, seed):
         assert np.isnan(plain["record"][0, K - 1]).all() and plain["best_a"][0, K - 1, 0] == -1
 
 
+@pytest.mark.parametrize("seed", range(0, 40, 7))
+def test_eval_kernel_sweep_under_redzones(dev, seed):
+    """ancsh_joint_params (both variants), ancsh_articulation_rec and ancsh_part_extents on the placed-vote cases of
+    tests/test_eval_kernels_sweep_gpu.py, every output guarded: st, joint, the block, its three debug outputs, extents, boundaries, counts"""
+    import test_eval_kernels_sweep_gpu as S
+    with guarded() as arena:
+        S.sweep(dev, seed)
+        assert arena.check() >= 8
+
+
 def test_metric_input_and_loss_kernels_under_redzones(dev, oracle):
     import test_eval_scripts_gpu as E
     import test_input_gpu as I
