@@ -166,6 +166,10 @@ SIGNATURES = {
     "ancsh_render_centre_crops_lib": [_c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp],
     # nframes, kin, ninst, pose, render, scene, stream
     "ancsh_pose_scene_build_lib": [_c_int, _vp, _c_int, _vp, _vp, _vp, _vp],
+    # a depth sensor's defects on the crops of annotated frames (no ABI bump, detected by their symbols): nframes, depth_type, depth_in,
+    # labels_in, pixel_capacity, geom, scene, sensor, seed (_keyed: the key block), depth_out, labels_out, stream
+    "ancsh_depth_sensor_model": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 6 + [_vp],
+    "ancsh_depth_sensor_model_keyed": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 6 + [_vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

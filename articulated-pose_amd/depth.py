@@ -21,6 +21,10 @@ frame (pack_pose: joint values and a view matrix) go in; and centres crops on th
 The last three take a LIBRARY of object instances in place of one object (the *_lib entries; reference: tools/render_synthetic.py:52, one
 render_data call per instance): pack_mesh_library concatenates the instances' meshes, the kinematics is the (ninst, 672) stack of their
 tables, and a frame names its instance in its own table (pack_pose / pack_render_scene, instance=).
+
+Between the renderer and the annotation stands an optional depth sensor (ancsh_depth_sensor_model; the reference has none: pybullet's depth
+is clean): one table per pipeline (pack_sensor) of range-dependent noise, holes, dropout at depth discontinuities and disparity steps turns
+the clean crops into the frames a real camera would deliver, in a second pair of pixel buffers.
 """
 import numpy as np
 import torch
@@ -481,8 +485,124 @@ def annotate_depth_batch(frames, scenes, depth_dtype, K, device="cuda:0"):
     return rows[:int(off[-1])].cpu().numpy(), off, cnt.cpu().numpy(), lc.cpu().numpy()
 
 
+# ---- a depth sensor's defects on the crops of annotated frames: noise, holes, edge dropout, disparity steps (ancsh_depth_sensor_model) ---
+SENSOR_WIDTH = 16       # include/ancsh_hip.h, ANCSH_SENSOR_WIDTH
+
+
+def check_sensor(table):
+    """-> table as a fresh (SENSOR_WIDTH,) float64 array; ValueError unless it is one the device entry is meant for: sigma's coefficients
+    a0 a1 a2 and edge_rel finite and >= 0, z0 finite, p_hole and p_edge in [0, 1], qd finite and >= 0, steps finite and >= 1, z_near finite,
+    z_near <= z_far (z_far may be +inf), the reserved values 0."""
+    try:
+        t = np.array(table, np.float64)
+    except (TypeError, ValueError):
+        t = np.zeros(0)
+    if t.shape != (SENSOR_WIDTH,):
+        raise ValueError("sensor: one (%d,) float64 table (depth.pack_sensor), got shape %s" % (SENSOR_WIDTH, t.shape))
+    a0, a1, a2, z0, p_hole, p_edge, edge_rel, qd, steps, z_near, z_far = t[:11].tolist()
+    for name, v in (("sigma a0", a0), ("sigma a1", a1), ("sigma a2", a2), ("edge_rel", edge_rel), ("disparity qd", qd)):
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError("sensor: %s must be finite and >= 0, got %r" % (name, v))
+    if not np.isfinite(z0):
+        raise ValueError("sensor: z0 must be finite, got %r" % z0)
+    for name, v in (("p_hole", p_hole), ("p_edge", p_edge)):
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("sensor: %s is a probability in [0, 1], got %r" % (name, v))
+    if not (np.isfinite(steps) and steps >= 1):
+        raise ValueError("sensor: disparity steps per pixel must be finite and >= 1, got %r" % steps)
+    if not (np.isfinite(z_near) and z_near <= z_far):
+        raise ValueError("sensor: z_range needs a finite z_near <= z_far (z_far may be inf), got (%r, %r)" % (z_near, z_far))
+    if (t[11:] != 0).any():
+        raise ValueError("sensor: the reserved values 11..15 must be 0")
+    return t
+
+
+def pack_sensor(sigma=(0.0, 0.0, 0.0), z0=0.0, p_hole=0.0, p_edge=0.0, edge_rel=0.05, disparity=None, z_range=(0.0, float("inf"))):
+    """The sensor table ancsh_depth_sensor_model reads, (SENSOR_WIDTH,) float64 (include/ancsh_hip.h): sigma = (a0, a1, a2), the noise's
+    standard deviation sigma(z) = a0 + a1 (z - z0) + a2 (z - z0)^2 in the cloud's length unit; p_hole: the share of surface pixels that
+    drop out; p_edge: the share of pixels at a depth discontinuity (a neighbour that is no surface, or |z_n - z| > edge_rel * z) that drop
+    out; disparity = None or (qd, steps): depth quantised to 1 / steps of a pixel of disparity, qd = focal length x baseline in length
+    units x pixels; z_range = (z_near, z_far): what the sensor sees at all.  The defaults are the identity.  ValueError: check_sensor's."""
+    try:
+        a0, a1, a2 = (float(v) for v in sigma)
+        qd, steps = (0.0, 1.0) if disparity is None else (float(v) for v in disparity)
+        z_near, z_far = (float(v) for v in z_range)
+        head = [a0, a1, a2, float(z0), float(p_hole), float(p_edge), float(edge_rel), qd, steps, z_near, z_far]
+    except (TypeError, ValueError):
+        raise ValueError("sensor: sigma = (a0, a1, a2), disparity = None or (qd, steps), z_range = (z_near, z_far), the others numbers")
+    return check_sensor(head + [0.0] * (SENSOR_WIDTH - len(head)))
+
+
+def depth_sensor_model(depth, labels, geom, scene, sensor, seed_or_key, out=None):
+    """ancsh_depth_sensor_model on device tensors (no host sync): depth (pixel_capacity,) uint16 / float32 and labels (pixel_capacity,) uint8,
+    the clean crops; geom (B, 5) int32; scene (B, SCENE_WIDTH) float64 (only depth_scale is read); sensor (SENSOR_WIDTH,) float64 on the
+    device (check_sensor's table); seed_or_key: the device seed (1,) int64, or the key block (4,) int32 (ancsh_depth_sensor_model_keyed).
+    -> (depth, labels) of the degraded frame; out = the same pair preallocated (a captured step passes slot-owned buffers), never the input
+    pair; else pixel_capacity pixels of depth 0 / label 255.  Every pixel of every crop is written, the others keep what they held."""
+    if not depth.is_cuda:
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = depth.device
+    kinds = {torch.float32: 1, torch.int16: 0}
+    if hasattr(torch, "uint16"):
+        kinds[torch.uint16] = 0
+    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
+    cap_px = int(depth.shape[0])
+    if labels is None or labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
+    B = int(geom.shape[0])
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
+            or not (geom.is_contiguous() and scene.is_contiguous()):
+        raise ValueError("geom must be (B, 5) int32 and scene (B, %d) float64, contiguous" % SCENE_WIDTH)
+    if sensor.dtype != torch.float64 or tuple(sensor.shape) != (SENSOR_WIDTH,) or not sensor.is_contiguous():
+        raise ValueError("sensor must be a contiguous (%d,) float64 tensor (depth.pack_sensor's table)" % SENSOR_WIDTH)
+    keyed = seed_or_key.dtype == torch.int32
+    if not ((keyed and tuple(seed_or_key.shape) == (4,)) or (seed_or_key.dtype == torch.int64 and tuple(seed_or_key.shape) == (1,))) \
+            or not seed_or_key.is_contiguous():
+        raise ValueError("seed_or_key must be the device seed (1,) int64 or the key block (4,) int32")
+    if out is None:
+        out = (torch.zeros((cap_px,), dtype=depth.dtype, device=dev), torch.full((cap_px,), NOT_OBJECT, dtype=torch.uint8, device=dev))
+    depth_out, labels_out = out
+    if depth_out.dtype != depth.dtype or tuple(depth_out.shape) != (cap_px,) or labels_out.dtype != torch.uint8 \
+            or tuple(labels_out.shape) != (cap_px,) or not (depth_out.is_contiguous() and labels_out.is_contiguous()):
+        raise ValueError("out must be contiguous (depth (%d,) of the input's dtype, labels (%d,) uint8)" % (cap_px, cap_px))
+    _lib.require_cuda(labels, geom, scene, sensor, seed_or_key, depth_out, labels_out)
+    _lib.call("ancsh_depth_sensor_model_keyed" if keyed else "ancsh_depth_sensor_model", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(labels),
+              cap_px, _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(sensor), _lib.ptr(seed_or_key), _lib.ptr(depth_out), _lib.ptr(labels_out))
+    return depth_out, labels_out
+
+
+def sensor_frames(frames, scenes, sensor, depth_dtype, seed=0, cloud_base=0, device="cuda:0"):
+    """Eager wrapper: the annotated frames render_depth_frames returns and annotate_depth_batch takes -- (depth_crop (h, w) of depth_dtype,
+    label_crop (h, w), (row0, col0)) -- with one scene table or one per frame (depth_scale is read), the sensor table (pack_sensor), the
+    generator seed and the global index of frame 0 -> frames of the same form as the sensor would deliver them: a dropped pixel reads depth
+    0 and label 255.  Frame f is keyed as frame cloud_base + f: the frames a streaming pipeline built with sensor= makes of the same batch
+    with the same seed and base.  One host sync; the pipeline has none."""
+    from .dataset import stream_key_words
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    table = check_sensor(sensor)
+    name = check_depth_dtype(depth_dtype)
+    depths, labels, origins, _, scenes = check_annotated_frames(frames, np.ones(len(frames)) if isinstance(frames, (list, tuple)) else None,
+                                                                scenes, depth_dtype, SCENE_MAX_LINKS)
+    cloud_base = int(cloud_base)
+    if not 0 <= cloud_base or cloud_base + len(depths) >= (1 << 20):
+        raise ValueError("cloud_base %d with %d frames: the global frame index must stay in [0, 2^20)" % (cloud_base, len(depths)))
+    total = sum(d.size for d in depths)
+    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
+    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    depth, labels = depth_sensor_model(t(pix.view(np.int16) if name == "uint16" else pix), t(lab), t(geom), t(scenes), t(table),
+                                       t(stream_key_words(seed, cloud_base)))
+    depth, labels = depth.cpu().numpy(), labels.cpu().numpy()
+    depth = depth.view(np.uint16) if name == "uint16" else depth
+    return [(depth[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(), labels[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(),
+             (int(g[3]), int(g[4]))) for g in geom]
+
+
 # ---- annotated frames, back on the pixel grid: predicted and true part / NOCS images (ancsh_depth_annotated_images) ----------------------
-GT_IMAGE_VALUES = 6     # per pixel of the ground-truth value image: [part NOCS (3) | NAOCS (3)], columns 4..9 of an 18-column row
+GT_IMAGE_VALUES = 6    # per pixel of the ground-truth value image: [part NOCS (3) | NAOCS (3)], columns 4..9 of an 18-column row
 
 
 def annotated_image_buffers(capacity, device=None):

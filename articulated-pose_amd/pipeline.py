@@ -144,7 +144,7 @@ class _Slot(object):
         self.np_base = hdr[lay.base] if self.keyed else None      # the key block's cloud_base (hdr[3], reserved, stays 0)
         unit = None
         if depth:
-            unit = self._init_depth(B, cap, depth, device, annotate=opts.link_counts, rendered=opts.render)
+            unit = self._init_depth(B, cap, depth, device, annotate=opts.link_counts, rendered=opts.render, sensor=opts.sensor)
         else:
             fill_rows(kind, self.np_rows, K)
             self.np_off[:] = np.arange(B + 1) * (cap // B)
@@ -193,7 +193,7 @@ class _Slot(object):
         img = self.outputs.get("label_images")
         self.h_img, self.h_img32 = (img.host, img.host32) if img else (None, None)
 
-    def _init_depth(self, B, capacity, depth, device, annotate=False, rendered=False):
+    def _init_depth(self, B, capacity, depth, device, annotate=False, rendered=False, sensor=False):
         """The depth front end's buffers: the pixel and mask buffers with their pinned staging, the kernel's scratch, the valid-pixel
         counts, and host / device views of the header's geometry, camera and dest blocks.  Until the first submit: B crops of random
         depths in front of a unit camera (a defined, non-degenerate input for prepare()'s passes).
@@ -203,6 +203,9 @@ class _Slot(object):
         rendered (render_mesh=, ancsh_render_depth_labels): the step writes the pixel and label buffers itself, so they have no pinned
         staging, and the slot owns the renderer's z-buffer, 8 bytes a pixel.  Until the first submit: the mesh in its model frames in
         front of the unit camera.
+        sensor (sensor=, ancsh_depth_sensor_model): a second pixel and label pair (apix, amask), 3 bytes a pixel of capacity (5 with
+        float32 depths), which the step's sensor launch writes from the first and the annotation and its inverse read; without a sensor
+        the two names are the first pair.
         -> the unit camera's six coefficients and the depth scale (what stream.unit_scene builds the slot's first scenes from)."""
         from .depth import CAM_WORDS, DEPTH_DTYPES, GEOM_WORDS, MAX_CHUNKS, SCENE_MAX_LINKS
         npt, tt, _ = DEPTH_DTYPES[depth]
@@ -211,6 +214,10 @@ class _Slot(object):
         self.h_pix = None if rendered else torch.zeros((capacity,), dtype=tt).pin_memory()
         self.h_mask = None if rendered else torch.zeros((capacity,), dtype=torch.uint8).pin_memory()
         self.zbuf = torch.zeros((capacity,), dtype=torch.int64, device=device) if rendered else None
+        self.apix, self.amask = self.pix, self.mask
+        if sensor:
+            self.apix = torch.zeros((capacity,), dtype=tt, device=device)
+            self.amask = torch.full((capacity,), 255, dtype=torch.uint8, device=device)
         self.scratch = torch.zeros((B * MAX_CHUNKS * (SCENE_MAX_LINKS if annotate else 1),), dtype=torch.int32, device=device)
         self.counts = torch.zeros((B,), dtype=torch.int32, device=device)
         lay, hdr = self.layout, self.h_hdr.numpy()
@@ -335,6 +342,11 @@ class AncshPipeline(object):
         ancsh_pose_scene_build, which writes the slot's render and scene tables from one pose per frame (depth.pack_pose: joint values and a
         view matrix), and ancsh_render_centre_crops, which centres the crops that ask for it on the projected object, in front of the
         renderer.  submit_posed / stream_posed_batches take crops and poses only: 32 doubles per frame cross PCIe.
+    sensor (those annotated frames, submitted, rendered, posed or from a library): depth.pack_sensor's table, uploaded once; one launch,
+        ancsh_depth_sensor_model, directly behind the renderer (submitted frames: behind the H2D copy) degrades every frame -- noise, holes,
+        edge dropout, disparity steps, keyed by the slot's own seed or key block -- into a second pixel pair of the slot, 3 bytes per pixel
+        of capacity (5 with float32), which the annotation and annotated_images read.  Results keep their form; counts, link counts and
+        images are the degraded frame's.  A short batch's padding frames take pixels of their own behind the batch's.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     ninst = None                                # a library's size (render_mesh=depth.pack_mesh_library(...)); None for a single object
@@ -344,7 +356,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None, kinematics=None, annotated_images=False):
+                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -352,7 +364,7 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -370,6 +382,10 @@ class AncshPipeline(object):
             self.ninst = self.mesh.ninst
         if o.posed:
             self.kin = torch.from_numpy(kinematics).to(self.device)
+        self.sensor_table = None
+        if o.sensor:                            # the sensor table (check_options has checked it): uploaded once and shared by all slots
+            from .depth import check_sensor
+            self.sensor_table = torch.from_numpy(check_sensor(sensor)).to(self.device)
         # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
@@ -461,9 +477,12 @@ class AncshPipeline(object):
         if self.render:                    # rendered frames: the mesh and the slot's render tables -> its depth and label crops, on the device
             from .depth import render_depth
             render_depth(self.mesh, sl.geom, sl.render, self.depth_dtype, out=(sl.pix, sl.mask), scratch=sl.zbuf)
+        if self.sensor:                    # a depth sensor's defects: the slot's clean crops -> its second pixel pair, keyed by the slot's own seed
+            from .depth import depth_sensor_model
+            depth_sensor_model(sl.pix, sl.mask, sl.geom, sl.scene, self.sensor_table, seed, out=(sl.apix, sl.amask))
         if self.link_counts:               # annotated depth frames: the slot's depth and label crops -> its annotated rows, offsets and counts
             from .depth import depth_annotate
-            depth_annotate(sl.pix, sl.mask, sl.geom, sl.scene, out=(sl.src_rows, off, sl.counts, sl.link_counts), scratch=sl.scratch)
+            depth_annotate(sl.apix, sl.amask, sl.geom, sl.scene, out=(sl.src_rows, off, sl.counts, sl.link_counts), scratch=sl.scratch)
         if self.build_point_gt:            # the slot's annotated rows and rigs -> its 18-column rows, in front of the unchanged sampler
             from .dataset import point_gt_build
             point_gt_build(sl.src_rows, off, sl.rig, self.K, sl.raw_rows)
@@ -538,7 +557,7 @@ class AncshPipeline(object):
             else:                        # one more launch: the rows and their ground truth back through the annotation's link-major sort.
                 # (Nothing between the annotation and here writes sl.scratch: its per-chunk histograms are what the inverse ranks with.)
                 from .depth import depth_annotated_images
-                out["annotated_images"] = depth_annotated_images(sl.pix, sl.mask, sl.geom, sl.scene, sl.dest, off, sl.counts, rl[0], rl[1],
+                out["annotated_images"] = depth_annotated_images(sl.apix, sl.amask, sl.geom, sl.scene, sl.dest, off, sl.counts, rl[0], rl[1],
                                                                  sl.raw_rows, out=sl.pick("aimg", f32), scratch=sl.scratch)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
@@ -683,7 +702,7 @@ class AncshPipeline(object):
         (depth.unprojection_from_intrinsics / unprojection_from_projmat) or one per frame; depth_scale = one value or one per frame
         (depth unit -> the cloud's unit).  The valid pixels of each crop (mask non-zero and a usable depth) become the frame's cloud on the
         device; a frame without one gives an all-NaN record and count 0.  A short batch is padded with its first frame (whose pixels are
-        not copied again), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base, gt: as submit().
+        not copied again -- with sensor=, whose draws follow the frame's index, they are, into pixels of their own), and all crops, padding included, must fit depth_capacity pixels.  seed, tag, cloud_base, gt: as submit().
         A pipeline built with point_ground_truth=True, build_point_gt=True takes annotated frames: the second element of a frame is its
         link-label crop (h, w), an integer array whose values outside [0, nlinks) are not object, and scene = one (240,) float64 table
         (depth.pack_frame_scene) or one per frame carries the camera, the depth scale and every link's map -- cameras stays None and
@@ -711,15 +730,18 @@ class AncshPipeline(object):
             else:
                 depths, masks, origins, nf, cam = check_depth_frames(frames, norm_factors, cameras, depth_scale, o.depth_dtype, self.B)
             n_valid = len(depths)
-            pixels = sum(d.size for d in depths)
-            padded = pixels + (self.B - n_valid) * depths[0].size
+            pad = self.B - n_valid if o.sensor else 0     # a sensor's draws follow the frame's index: its padding frames get pixels of their own
+            pixels = sum(d.size for d in depths) + pad * depths[0].size
+            padded = pixels + (self.B - n_valid - pad) * depths[0].size
             if padded > o.depth_capacity:
                 raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
                                  % (padded, o.depth_capacity))
 
             def stage(sl):
-                pack_depth_frames(depths, masks, origins, sl.np_pix, sl.np_mask, sl.np_geom)
-                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding clouds alias the first frame's pixels
+                pack_depth_frames(depths + depths[:1] * pad, masks + masks[:1] * pad, list(origins) + [origins[0]] * pad, sl.np_pix, sl.np_mask,
+                                  sl.np_geom)
+                if not pad:
+                    sl.np_geom[n_valid:] = sl.np_geom[0]   # the padding clouds alias the first frame's pixels
                 if not annotated:                          # (the scenes of annotated frames carry the camera)
                     sl.np_cam[:n_valid] = cam
                     sl.np_cam[n_valid:] = cam[0]
@@ -734,7 +756,7 @@ class AncshPipeline(object):
         frame, render = one (208,) float64 table (depth.pack_render_scene) or one per frame, scene and rig (both required), gt, frame,
         seed, tag, cloud_base: as submit_depth takes them for annotated frames.  Only the geometry and the tables cross to the device:
         ancsh_render_depth_labels writes the slot's depth and label crops in front of ancsh_depth_annotate_stream.  A short batch is
-        padded with its first crop (which the padding frames render again, where it lies), and all crops, padding included, must fit
+        padded with its first crop (which the padding frames render again, where it lies; with sensor=: into pixels of their own), and all crops, padding included, must fit
         depth_capacity pixels.  Bad input raises ValueError before anything is enqueued; a full in-flight window raises RuntimeError.
         Either way the pipeline stays usable."""
         o = self.opts
@@ -746,7 +768,7 @@ class AncshPipeline(object):
         refuse_built_frame(o, frame, "AncshPipeline")
 
         def front():
-            from .depth import check_crops, check_scenes, pack_crop_geometry
+            from .depth import check_crops, check_scenes
             if render is None or scene is None or rig is None:
                 raise ValueError(SIDE["render"].missing)
             shapes, origins = check_crops(crops, self.B)
@@ -762,8 +784,7 @@ class AncshPipeline(object):
                                  % (padded, o.depth_capacity))
 
             def stage(sl):
-                pack_crop_geometry(shapes, origins, sl.np_geom)
-                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and render the same bytes)
+                self._stage_crops(sl, shapes, origins)     # the padding frames alias the first frame's pixels (and render the same bytes)
                 self._stage_dest(sl, n_valid)
                 return []
             return n_valid, nf, stage, dict(scene=scenes)
@@ -785,7 +806,7 @@ class AncshPipeline(object):
         refuse_built_frame(o, frame, "AncshPipeline")
 
         def front():
-            from .depth import check_posed_crops, pack_crop_geometry
+            from .depth import check_posed_crops
             if pose is None or rig is None:
                 raise ValueError(SIDE["pose"].missing)
             shapes, origins = check_posed_crops(crops, self.B)
@@ -800,12 +821,21 @@ class AncshPipeline(object):
                                  % (padded, o.depth_capacity))
 
             def stage(sl):
-                pack_crop_geometry(shapes, origins, sl.np_geom)
-                sl.np_geom[n_valid:] = sl.np_geom[0]       # the padding frames alias the first frame's pixels (and pose: the same origin, the same bytes)
+                self._stage_crops(sl, shapes, origins)     # the padding frames alias the first frame's pixels (and pose: the same origin, the same bytes)
                 self._stage_dest(sl, n_valid)
                 return []
             return n_valid, nf, stage
         self._enqueue(front, seed, tag, cloud_base, pose=pose, gt=gt, frame=frame, rig=rig)
+
+    def _stage_crops(self, sl, shapes, origins):
+        """The geometry rows of crops the step renders: a padding frame renders the first crop again where it lies -- or, with a sensor, whose
+        draws follow the frame's index, into pixels of its own behind the batch's (the capacity check has counted them either way)."""
+        from .depth import pack_crop_geometry
+        n_valid = len(shapes)
+        pad = self.B - n_valid if self.opts.sensor else 0
+        pack_crop_geometry(shapes + shapes[:1] * pad, list(origins) + [origins[0]] * pad, sl.np_geom)
+        if not pad:
+            sl.np_geom[n_valid:] = sl.np_geom[0]
 
     def _stage_dest(self, sl, n_valid):
         """label_images / annotated_images: a valid frame's images lie where its crop does; a padding cloud writes none."""

@@ -49,6 +49,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_render_depth_labels (those crops rendered from articulated triangle meshes),
                                  *     ancsh_pose_scene_build (that renderer's and the annotation's tables built from joint values and a view),
                                  *     ancsh_render_centre_crops (crops centred on the projected object),
+                                 *     ancsh_depth_sensor_model, ancsh_depth_sensor_model_keyed (a depth sensor's noise, holes and edge dropout on those crops),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1379,6 +1380,58 @@ int ancsh_render_depth_labels_lib(int nframes, int depth_type, const float *vert
 int ancsh_render_centre_crops_lib(int nframes, const float *verts, const int *tris, const int *tri_link, int V, int T, const int *tri_off,
                                   int ninst, const double *render, int *geom, int *bounds, void *stream);
 int ancsh_pose_scene_build_lib(int nframes, const double *kin, int ninst, const double *pose, double *render, double *scene, void *stream);
+
+/* A depth sensor's defects applied to the frames above: range-dependent noise, holes, dropout at depth discontinuities and disparity
+ * quantisation -- the clean depth and link-label crops ancsh_render_depth_labels writes (or a caller submits) -> degraded crops in a SECOND
+ * pair of pixel buffers, which ancsh_depth_annotate_stream and ancsh_depth_annotated_images then read.  The reference has nothing here
+ * (pybullet's depth is clean).  The annotation computes a pixel's canonical coordinates from the depth it is given, so a displaced point gets
+ * the coordinates of the displaced point: per part the relation between camera point and NOCS stays an exact similarity, and the
+ * ground-truth poses of ancsh_gt_pose_build are unchanged in exact arithmetic.  The ABI version is unchanged; callers detect the entries
+ * by their symbols.
+ *   nframes, depth_type, pixel_capacity, geom : as the depth entries take them; geom (nframes, 5) int32 {start h w row0 col0};
+ *   depth_in, labels_in : the clean pixel buffers (pixel_capacity values of depth_type, 16-byte aligned; pixel_capacity bytes, 8-byte
+ *     aligned); depth_out, labels_out : the degraded ones, same sizes and alignments.  No input range may overlap an output range, nor the
+ *     two outputs each other (a pixel's neighbours are read from the clean input while other pixels are written): refused;
+ *   scene : (nframes, ANCSH_SCENE_WIDTH) float64, 8-byte aligned; only value 6, depth_scale, is read;
+ *   sensor : ONE table of ANCSH_SENSOR_WIDTH = 16 float64 for the launch, 8-byte aligned:
+ *     [0..3] a0 a1 a2 z0 : sigma(z) = (a0 + a1 dz) + a2 (dz dz), dz = z - z0   [4] p_hole, in [0, 1]   [5] p_edge, in [0, 1]
+ *     [6] edge_rel >= 0   [7] qd >= 0: focal length x baseline, in length units x pixels; 0 = no quantisation   [8] steps >= 1: disparity
+ *     steps per pixel   [9] z_near   [10] z_far (may be +Inf)   [11..15] reserved, 0;
+ *   seed : the device seed, 8-byte aligned (the _keyed entry: the key block, ancsh_stream_key).
+ * Everything below is float64, evaluated in exactly the written order (no contraction).  No transcendental function appears: the result is
+ * a fixed sequence of IEEE operations, byte-reproducible on the host.  Per crop pixel (i, j) of frame f, p = i w + j, g = base + f (base =
+ * key->cloud_base; 0 for the seed entry), s the seed:
+ *   1. The pixel is a SURFACE pixel when its label is not 255 and its stored depth is usable (uint16: >= 1; float32: finite and > 0).  Any
+ *      other pixel is copied verbatim, depth and label.
+ *   2. z = (double)stored * depth_scale.  The pixel is dropped unless z_near <= z && z <= z_far.
+ *   3. Draws: r_k = splitmix64(s ^ splitmix64(0xE000000000000000 | g << 36 | p << 4 | k)), u_k = (double)(r_k >> 11) * 2^-53, splitmix64 the
+ *      pose fit's generator.  The tag 0xE keeps these keys apart from the sampler's (0xF) and the draw keys' (0x0); the streams' bound
+ *      (base + B) K < 2^20 keeps g below 2^20, and p < 2^30.
+ *   4. Hole: dropped when u_0 < p_hole.
+ *   5. Edge, evaluated only when p_edge > 0: the pixel is an edge pixel when any of its four neighbours INSIDE the crop is not a surface
+ *      pixel or has |z_n - z| > edge_rel * z, z_n the neighbour's CLEAN depth from depth_in.  Neighbours outside the crop do not count.  An
+ *      edge pixel is dropped when u_1 < p_edge.
+ *   6. Noise: a, b = r_2 >> 32, r_2 & 0xFFFFFFFF and c, d likewise from r_3; S = a + b + c + d as an integer;
+ *      n = ((double)S * 2^-32 - 2.0) * 1.7320508075688772 (Irwin-Hall of four, unit variance);  z1 = z + sigma(z) * n.
+ *   7. Quantisation, when qd > 0: dq = rint((qd / z1) * steps) / steps; the pixel is dropped when !(dq > 0), otherwise z2 = qd / dq.  With
+ *      qd = 0, z2 = z1.
+ *   8. Store: when z2 has the bits of z the stored input value is copied verbatim; otherwise uint16 writes q = rint(z2 / depth_scale) when
+ *      1 <= q <= 65535 and float32 writes (float)(z2 / depth_scale) when that is finite and positive, else the pixel is dropped.  The label
+ *      is kept.
+ * A dropped pixel reads depth 0 and label 255.  Two consequences: the all-zero table with z_far = +Inf is the IDENTITY, byte for byte; and
+ * frames [lo, hi) run with cloud_base = lo give the bytes of rows [lo, hi) of the whole batch run with base 0.
+ * EVERY pixel of every crop is written (no prefill needed); pixels of no crop are left alone.  A frame with h < 1, w < 1 or a crop outside
+ * [0, pixel_capacity) writes nothing.  Crops that share pixels are written once per frame, with that frame's draws: give the frames of a
+ * launch crops of their own.  One launch on the depth entries' grid and chunking, a function of (pixel_capacity, nframes) only; no atomics,
+ * no host sync, no allocation: graph-capturable.  nframes == 0 launches nothing and returns 0.  Checked before any launch: 0 <= nframes <=
+ * 65535, depth_type, 0 <= pixel_capacity < 2^30, null pointers, the alignments, the overlaps. */
+#define ANCSH_SENSOR_WIDTH 16
+int ancsh_depth_sensor_model(int nframes, int depth_type, const void *depth_in, const unsigned char *labels_in, long pixel_capacity,
+                             const int *geom, const double *scene, const double *sensor, const unsigned long long *seed, void *depth_out,
+                             unsigned char *labels_out, void *stream);
+int ancsh_depth_sensor_model_keyed(int nframes, int depth_type, const void *depth_in, const unsigned char *labels_in, long pixel_capacity,
+                                   const int *geom, const double *scene, const double *sensor, const ancsh_stream_key *key, void *depth_out,
+                                   unsigned char *labels_out, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -9,7 +9,11 @@ tessellated boxes, one per link, under random views and openings; one SIDE x SID
        pixel more; whatever renderer made them on the host is not in the timed loop: the best case without the new entry).
 Prints one JSON line: a record, not a gate.
 
-    python tools/render_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+--sensor measures the depth sensor model (ancsh_depth_sensor_model) instead: the entry alone on one batch of 32 rendered crops with the
+identity table and with a noisy one (every term on), and two legs of the rendered stream, alternated like r and d above:
+    r: the rendered stream without the option;   s: the rendered stream built with sensor=<the noisy table>.
+
+    python tools/render_bench.py [--sensor] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ from articulated_pose_amd.pipeline import AncshPipeline  # noqa: E402
 from articulated_pose_amd.weights import synthetic_weights  # noqa: E402
 
 SCALE = 1e-3
+NOISY_SENSOR = dict(sigma=(0.001, 0.002, 0.001), z0=1.0, p_hole=0.05, p_edge=0.5, edge_rel=0.05, disparity=(35.0, 8), z_range=(0.2, 10.0))
 LO, HI = np.array([-0.16, -0.11, -0.06]), np.array([0.16, 0.11, 0.06])
 
 
@@ -65,8 +70,68 @@ def make_scene(rs, side):
             D.pack_frame_scene(V, P, pos, orn, zero, zero, zero[:2], [[0], [1], [2]], side, side, depth_scale=SCALE))
 
 
+def timed_calls(call, rounds, calls):
+    """ms per call over `calls` back-to-back calls between two HIP events, once per round, after 20 warm-up calls."""
+    for _ in range(20):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for _ in range(rounds):
+        e0.record()
+        for _ in range(calls):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / calls)
+    return ms
+
+
+def sensor_bench(args, K, B, N, dev, mesh, rbatches, d_geom, d_sc, clean, cap):
+    """--sensor: the entry alone (identity and noisy table) on `clean`, the rendered crops of one batch; the rendered stream with and without
+    sensor=noisy, alternated."""
+    seed = torch.tensor([12345], dtype=torch.int64, device=dev)
+    out = (torch.zeros_like(clean[0]), torch.zeros_like(clean[1]))
+    tables = {"identity": D.pack_sensor(), "noisy": D.pack_sensor(**NOISY_SENSOR)}
+    op_ms, dropped = {}, {}
+    for name, table in tables.items():
+        d_table = torch.from_numpy(table).to(dev)
+        op_ms[name] = timed_calls(lambda: D.depth_sensor_model(clean[0], clean[1], d_geom, d_sc, d_table, seed, out=out), args.rounds, args.calls)
+        dropped[name] = int(((out[1] == D.NOT_OBJECT) & (clean[1] != D.NOT_OBJECT)).sum())
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
+              depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
+    pipes = {"r": AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare(), "s": AncshPipeline(K, wa, wn, B, N, dev, sensor=tables["noisy"], **kw).prepare()}
+    torch.cuda.synchronize()
+
+    def leg(name, passes):
+        t0, n = time.perf_counter(), 0
+        for _ in pipes[name].stream_render_batches(rbatches[k] for _ in range(passes) for k in range(len(rbatches))):
+            n += 1
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / n
+
+    for name in "rs":
+        leg(name, 1)
+    ms = {name: [] for name in "rs"}
+    for _ in range(args.rounds):
+        for name in "rs":
+            ms[name].append(leg(name, args.passes))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    print(json.dumps({"metric": "the depth sensor model: ms per launch of the entry alone on one batch (identity / noisy table); frames/s of the "
+                                "rendered stream without (r) and with (s) sensor=noisy",
+                      "device": torch.cuda.get_device_name(0), "operator_ms_per_batch": {k: round(float(np.median(v)), 4) for k, v in op_ms.items()},
+                      "operator_ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in op_ms.items()},
+                      "operator_bytes_per_batch": 2 * 3 * cap, "object_pixels_dropped_per_batch": dropped,
+                      "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
+                      "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()}, "s_over_r": round(med["s"] / med["r"], 4),
+                      "sensor": NOISY_SENSOR, "crop_pixels_per_frame": args.side * args.side,
+                      "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(rbatches) * B,
+                                "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sensor", action="store_true", help="measure the depth sensor model instead of the renderer")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
     ap.add_argument("--slots", type=int, default=8)
@@ -95,17 +160,10 @@ def main():
     d_geom, d_rt = torch.from_numpy(geom).to(dev), torch.from_numpy(rt).to(dev)
     out = (torch.zeros(cap, dtype=torch.int16, device=dev), torch.zeros(cap, dtype=torch.uint8, device=dev))
     zbuf = torch.zeros(cap, dtype=torch.int64, device=dev)
-    for _ in range(20):
+    if args.sensor:
         D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    op_ms = []
-    for _ in range(args.rounds):
-        e0.record()
-        for _ in range(args.calls):
-            D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
-        e1.record()
-        torch.cuda.synchronize()
-        op_ms.append(e0.elapsed_time(e1) / args.calls)
+        return sensor_bench(args, K, B, N, dev, mesh, rbatches, d_geom, torch.from_numpy(sc).to(dev), out, cap)
+    op_ms = timed_calls(lambda: D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf), args.rounds, args.calls)
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16")
