@@ -170,6 +170,11 @@ SIGNATURES = {
     # labels_in, pixel_capacity, geom, scene, sensor, seed (_keyed: the key block), depth_out, labels_out, stream
     "ancsh_depth_sensor_model": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 6 + [_vp],
     "ancsh_depth_sensor_model_keyed": [_c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 6 + [_vp],
+    # render-and-compare of a pose record (no ABI bump, detected by their symbols): nframes, K, render, scene, rig, rig_ld, norm_factor, record,
+    # ld, geom, pixel_capacity, render_out, geom_out, stream
+    "ancsh_reproject_scene_build": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _c_long, _vp, _vp, _vp],
+    # nframes, K, depth_type, obs_depth, obs_labels, pixel_capacity, pred_depth, pred_labels, geom, scene, carried, ld, wide, stream
+    "ancsh_reproject_compare_rec": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -1033,6 +1033,46 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
              (int(g[3]), int(g[4]))) for g in geom]
 
 
+def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device="cuda:0"):
+    """Eager render-and-compare, the operator outside the pipeline: mesh = pack_mesh's arrays (or pack_mesh_library's), render_tables and
+    scenes = the frames' own tables (one of each, or one per frame), rigs = one dataset.pack_joint_rig table per frame, norm_factors = one
+    finite value per frame, record = the frames' (n, K, >= 26) float64 pose records (columns 0..12 the baseline pose, 13..25 the nonlinear
+    one), frames = the observed frames as render_depth_frames returns and sensor_frames degrades them: (depth_crop (h, w) of depth_dtype,
+    label_crop (h, w), (row0, col0)).  -> (columns (n, K, 15) float64, pose.reprojection.COLUMN_NAMES; predicted: per frame ((depth, labels)
+    under the baseline pose, (depth, labels) under the nonlinear pose), crops of the frame's own shape and origin -- the object where the fit
+    put it).  The three calls of the streamed step (ancsh_reproject_scene_build, the renderer on 2 n frames, ancsh_reproject_compare_rec) on
+    the same tables: a pipeline built with reprojection=True streams the same bytes.  One host sync; the pipeline has none."""
+    from .dataset import check_rigs
+    from .pose.reprojection import REPROJECTION_WIDTH, predicted_buffers, reprojection_batch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    name = check_depth_dtype(depth_dtype)
+    rec = np.ascontiguousarray(record, np.float64)
+    if rec.ndim != 3 or rec.shape[2] < 26 or not 1 <= rec.shape[1] <= 8:
+        raise ValueError("record must be (n, K, >= 26) float64 with 1 <= K <= 8, got shape %s" % (rec.shape,))
+    n, K = rec.shape[:2]
+    depths, labels, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scenes, depth_dtype, K)
+    if len(depths) != n:
+        raise ValueError("record holds %d frames, frames %d" % (n, len(depths)))
+    d_mesh = mesh_to_device(mesh, dev)
+    tables, rigs = check_render_tables(render_tables, n, d_mesh.ninst), check_rigs(rigs, n, K)
+    total = sum(d.size for d in depths)
+    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((n, GEOM_WORDS), np.int32)
+    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    pred = predicted_buffers(total, name, dev)
+    out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
+    wide = reprojection_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), t(geom), (t(pix.view(np.int16) if name == "uint16" else pix), t(lab)),
+                              t(rec), name, out_tables, pred)
+    columns = wide[:, :, rec.shape[2]:].cpu().numpy()
+    assert columns.shape == (n, K, REPROJECTION_WIDTH)
+    depth, plab = pred[0].cpu().numpy(), pred[1].cpu().numpy()
+    depth = depth.view(np.uint16) if name == "uint16" else depth
+    cut = lambda a, g, v: a[v * total + g[0]:v * total + g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy()
+    return columns, [tuple((cut(depth, g, v), cut(plab, g, v)) for v in (0, 1)) for g in geom]
+
+
 # ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred
 # on the projected object (ancsh_render_centre_crops) ---------------------------------------------------------------------------------------
 KIN_WIDTH, KIN_HEAD, KIN_LINK, POSE_WIDTH = 672, 32, 40, 32             # include/ancsh_hip.h, ANCSH_KIN_* and ANCSH_POSE_WIDTH

@@ -101,7 +101,7 @@ class _Slot(object):
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
         for inp in EVERY_INPUT:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
-        self.bounds = None
+        self.bounds = self.reproj_tables = self.reproj_pix = None
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
 
@@ -164,6 +164,12 @@ class _Slot(object):
         if opts.build_gt_pose:                 # what ancsh_gt_pose_build writes behind the sampler and the two error launches read: slot-owned,
             self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
             self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
+        if opts.reprojection:                # the predicted frames' render tables and geometry rows (ancsh_reproject_scene_build) and the pixel
+            from .depth import GEOM_WORDS, RENDER_WIDTH          # triple the renderer draws them into, two crops per frame: slot-owned, shared
+            from .pose.reprojection import predicted_buffers     # with the range guard's f32 graph (the wide record is the graph's own)
+            self.reproj_tables = (torch.zeros((2 * B, RENDER_WIDTH), dtype=torch.float64, device=device),
+                                  torch.zeros((2 * B, GEOM_WORDS), dtype=torch.int32, device=device))
+            self.reproj_pix = predicted_buffers(cap, depth, device)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -347,6 +353,12 @@ class AncshPipeline(object):
         edge dropout, disparity steps, keyed by the slot's own seed or key block -- into a second pixel pair of the slot, 3 bytes per pixel
         of capacity (5 with float32), which the annotation and annotated_images read.  Results keep their form; counts, link counts and
         images are the degraded frame's.  A short batch's padding frames take pixels of their own behind the batch's.
+    reprojection (with render_mesh, whatever else is built): render-and-compare at the step's end -- ancsh_reproject_scene_build turns the
+        record's two poses per part into two render tables per frame, the renderer draws those 2 * B predicted frames into a pixel triple of the
+        slot (22 bytes per pixel of capacity, 26 with float32), and ancsh_reproject_compare_rec scores them against the pair the annotation
+        read (with sensor=: the degraded one): out["record_reproj"], 15 columns (pose.reprojection.COLUMN_NAMES: observed pixels, then predicted
+        pixels, overlap, IoU and the depth residual's mean |d|, RMS, max and mean per pose) behind whatever the record was.  Five launches more;
+        the result tuple keeps its form.  A short batch's padding frames take pixels of their own, as with a sensor.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     ninst = None                                # a library's size (render_mesh=depth.pack_mesh_library(...)); None for a single object
@@ -356,7 +368,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None):
+                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None, reprojection=False):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -364,7 +376,8 @@ class AncshPipeline(object):
             raise ValueError("arithmetic must be None, 'f32', 'bf16x3' or 'f16x2'")
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
-                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor)
+                                      label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor,
+                                      reprojection)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -559,6 +572,13 @@ class AncshPipeline(object):
                 from .depth import depth_annotated_images
                 out["annotated_images"] = depth_annotated_images(sl.apix, sl.amask, sl.geom, sl.scene, sl.dest, off, sl.counts, rl[0], rl[1],
                                                                  sl.raw_rows, out=sl.pick("aimg", f32), scratch=sl.scratch)
+        if self.reprojection:            # the step's last three calls, behind the record's poison: the record's poses -> two render tables per
+            # frame, the renderer on 2 * B frames, and the predicted pixels against the pair the annotation read -> 15 columns behind the record
+            from .pose.reprojection import reprojection_batch
+            # (a pipeline that holds a mesh is built with point_ground_truth: its record is the widest one so far)
+            out["record_reproj"] = reprojection_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom,
+                                                      (sl.apix, sl.amask), out["record_point_gt"], self.depth_dtype, sl.reproj_tables,
+                                                      sl.reproj_pix)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:
@@ -829,10 +849,11 @@ class AncshPipeline(object):
 
     def _stage_crops(self, sl, shapes, origins):
         """The geometry rows of crops the step renders: a padding frame renders the first crop again where it lies -- or, with a sensor, whose
-        draws follow the frame's index, into pixels of its own behind the batch's (the capacity check has counted them either way)."""
+        draws follow the frame's index, into pixels of its own behind the batch's (the capacity check has counted them either way).  So it
+        does with reprojection: a padding frame is fitted under its own key, and its predicted crop is not the first frame's."""
         from .depth import pack_crop_geometry
         n_valid = len(shapes)
-        pad = self.B - n_valid if self.opts.sensor else 0
+        pad = self.B - n_valid if self.opts.sensor or self.opts.reprojection else 0
         pack_crop_geometry(shapes + shapes[:1] * pad, list(origins) + [origins[0]] * pad, sl.np_geom)
         if not pad:
             sl.np_geom[n_valid:] = sl.np_geom[0]

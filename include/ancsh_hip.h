@@ -50,6 +50,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_pose_scene_build (that renderer's and the annotation's tables built from joint values and a view),
                                  *     ancsh_render_centre_crops (crops centred on the projected object),
                                  *     ancsh_depth_sensor_model, ancsh_depth_sensor_model_keyed (a depth sensor's noise, holes and edge dropout on those crops),
+                                 *     ancsh_reproject_scene_build, ancsh_reproject_compare_rec (render-and-compare of a pose record),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1432,6 +1433,72 @@ int ancsh_depth_sensor_model(int nframes, int depth_type, const void *depth_in, 
 int ancsh_depth_sensor_model_keyed(int nframes, int depth_type, const void *depth_in, const unsigned char *labels_in, long pixel_capacity,
                                    const int *geom, const double *scene, const double *sensor, const ancsh_stream_key *key, void *depth_out,
                                    unsigned char *labels_out, void *stream);
+
+/* Render-and-compare of a pose record, two entries around the unchanged renderer (no new ABI number: callers detect them by their symbols).
+ * The object's own mesh is put where the fitted per-part poses say, rendered through the frame's camera by ancsh_render_depth_labels[_lib]
+ * as 2 * nframes frames, and the predicted pixels are scored against the frame the annotation read: the check of a pose that needs no
+ * ground truth.
+ *
+ * ancsh_reproject_scene_build: the map from a pose record back to render tables, ONE launch.
+ *   render (nframes, ANCSH_RENDER_WIDTH), scene (nframes, ANCSH_SCENE_WIDTH) : the frame's own tables, as the renderer and the annotation read
+ *     them;  rig (nframes, rig_ld = ANCSH_RIG_WIDTH(K)) : as ancsh_point_gt_build reads it;  norm_factor (nframes) float32 : the sampler's;
+ *   record (nframes, K, ld) float64, ld >= 26 : columns 0..12 of row (f, j) are part j's baseline pose [R (9) row-major | s | t (3)], columns
+ *     13..25 its nonlinear pose; the other columns are not read;
+ *   geom (nframes, 5) int32 {start h w row0 col0} : the frame's geometry rows in a pixel buffer of pixel_capacity pixels;
+ *   render_out (2 * nframes, ANCSH_RENDER_WIDTH) float64, geom_out (2 * nframes, 5) int32 : row v * nframes + f is frame f under variant v
+ *     (0: the baseline pose, 1: the nonlinear pose), for a renderer call with 2 * nframes frames and 2 * pixel_capacity pixels.
+ *   Heads: render_out[row][0..15] = render[f][0..15] bit for bit, the instance value [9] included.  geom_out[row] = geom[f] with start + v *
+ *   pixel_capacity (a negative start is copied as it is; the sum saturates at 2^31 - 1): variant v draws into the v-th half of the buffers.
+ *   Link l < nlinks (scene[14]) of part j = (int)scene link value [1], everything float64, evaluated in exactly the written order (no
+ *   contraction), C = A o B being ancsh_pose_scene_build's composition of 3 x 4 maps:
+ *     1. N = M_l o R_l : the frame's scene map composed with its render map, model frame -> canonical coordinates (= [Rc_l | offset_l] of
+ *        ancsh_pose_scene_build up to rounding; composing the two tables makes the entry work without a kinematic table);
+ *     2. Q, canonical coordinates -> part NOCS, ancsh_point_gt_build's nocs_p as a map: with sub, corner, factor, tail = part j's rig values
+ *        [0..2], [3..5], [6..8], [9..11]:  o_a = ((((0 - sub_a) - corner_a) * factor_a) + 0.5) - tail_a;  rig[3] == 0: Q[a][k] = factor_k for
+ *        a == k, else 0, Q[a][3] = o_a;  rig[3] != 0, with Rr = rig[4..12]: Q[a][k] = Rr[a][k] * factor_k,
+ *        Q[a][3] = ((Rr[a][0] (o_0 - 0.5) + Rr[a][1] (o_1 - 0.5)) + Rr[a][2] (o_2 - 0.5)) + 0.5;
+ *     3. P, part NOCS -> the scaled cloud, the record's pose of variant v: P[a][k] = s * R[a][k], P[a][3] = t_a;
+ *     T1 = Q o N;  T2 = P o T1;
+ *     4., 5. the map written: T2[a][k] / norm_factor for rows a = 0 and 2, -(T2[1][k] / norm_factor) for row 1.
+ *   Step 5 is the constant matrix diag(1, -1, 1): it takes the camera point the annotation gives a pixel, (x, y, z) of scene[0..5], to the
+ *   coordinate point (x', y', z) of scene[7..12] the renderer inverts.  The two differ by the image row's flip (v1 = row * 2 / H - 1 against
+ *   v = (H - row) * 2 / H - 1), so x' = x and y' = -y for a projection without skew whose principal point is the image centre (projMat[:2,
+ *   :2] diagonal, projMat[1][2] = 0: PyBullet's computeProjectionMatrixFOV, the reference's camera); R_l = -A_l of ancsh_pose_scene_build
+ *   is the same statement for the eye point.
+ *   A link gets an all-NaN map -- the renderer drops its triangles whole -- when it is not used (rank -1), its part is outside [0, K), one of
+ *   its pose's 13 values is not finite, or the frame's norm factor is 0 or not finite.  Links >= nlinks read 0, as in the frame's table.
+ *   One thread per (frame, variant, link), the grid a function of nframes alone; no host sync, no allocation: graph-capturable.  nframes == 0
+ *   launches nothing and returns 0.  Checked before any launch: 0 <= nframes <= 32767 (the renderer takes 65535 frames), 1 <= K <= 8, rig_ld
+ *   == ANCSH_RIG_WIDTH(K), ld >= 26, 0 <= pixel_capacity < 2^29, null pointers, the alignments (doubles 8 bytes, the others 4).
+ *
+ * ancsh_reproject_compare_rec: the pixel comparison, ONE launch behind the renderer and behind the record's poison step.
+ *   obs_depth, obs_labels (pixel_capacity) : the pair the annotation read (with a sensor: the degraded pair);  pred_depth, pred_labels (2 *
+ *   pixel_capacity) : what the renderer wrote for render_out / geom_out;  geom, scene : the frame's own;  carried (nframes, K, ld) float64 : the
+ *   record row so far, columns 0..25 the two poses;  wide (nframes, K, ld + ANCSH_REPROJECTION_WIDTH) float64 : the output, a buffer of its own.
+ *   A pixel is OBSERVED part j when its label names a used link (rank >= 0) whose part is j and its depth is usable by the annotation's rule
+ *   (uint16: d != 0; float32: 0 < d < +inf); PREDICTED part j likewise on the predicted crop of the variant.  Over the pixels that are part j
+ *   in both, d = ((double)pred - (double)obs) * depth_scale (scene[6]).  Row (f, j) of wide: columns 0..ld-1 = carried, bit for bit, then
+ *     +0 n_obs   +1 n_pred   +2 n_both   +3 IoU = n_both / (n_obs + n_pred - n_both), NaN when the union is empty   +4 mean |d|   +5 RMS d
+ *     +6 max |d|   +7 mean d (positive: the prediction lies behind the observation)      -- +1..+7 for the baseline pose --
+ *     +8..+14 the same seven for the nonlinear pose.
+ *   uint16 depths: S1 = sum |dq|, S = sum dq, S2 = sum dq^2 and the maximum over the integer quanta dq = pred - obs are int64, exact in any
+ *   order, and converted once: mean |d| = ((double)S1 * depth_scale) / n_both, RMS = sqrt((double)S2 / n_both) * depth_scale, max = (double)max
+ *   * depth_scale, mean = ((double)S * depth_scale) / n_both.  float32 depths: the float64 sums of |d|, d and d * d are added in a fixed order
+ *   -- thread t of 256 adds pixels t, t + 256, ... of the crop in that order, a wave adds its lanes with xor shuffles of 32, 16, 8, 4, 2, 1,
+ *   the four waves are added in wave order --, mean |d| = sum / n_both, RMS = sqrt(sum / n_both), mean likewise: the same bytes every run.
+ *   NaN rules: a variant whose pose (13 values) is not finite has NaN in its seven columns; n_both == 0 gives NaN in the four depth columns;
+ *   +0 is NaN when both poses are not finite -- so a frame whose record is poisoned, which includes every frame without rows, has NaN in all
+ *   15.  A frame whose crop the depth entries refuse counts no pixel.
+ *   One workgroup per (part, variant, frame); no atomics, no host sync, no allocation: graph-capturable.  nframes == 0 launches nothing and
+ *   returns 0.  Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8, depth_type, 0 <= pixel_capacity < 2^29, ld >= 26, null
+ *   pointers, the alignments, carried != wide. */
+#define ANCSH_REPROJECTION_WIDTH 15
+int ancsh_reproject_scene_build(int nframes, int K, const double *render, const double *scene, const double *rig, int rig_ld,
+                                const float *norm_factor, const double *record, int ld, const int *geom, long pixel_capacity,
+                                double *render_out, int *geom_out, void *stream);
+int ancsh_reproject_compare_rec(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
+                                long pixel_capacity, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
+                                const double *scene, const double *carried, int ld, double *wide, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

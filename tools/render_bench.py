@@ -13,7 +13,12 @@ Prints one JSON line: a record, not a gate.
 identity table and with a noisy one (every term on), and two legs of the rendered stream, alternated like r and d above:
     r: the rendered stream without the option;   s: the rendered stream built with sensor=<the noisy table>.
 
-    python tools/render_bench.py [--sensor] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+--reprojection measures render-and-compare (reprojection=True) instead: two legs of the rendered stream, alternated like r and d above:
+    r: the rendered stream without the option;   p: the rendered stream built with reprojection=True;
+and the option's three calls alone on one batch of 32 frames: ancsh_reproject_scene_build, the renderer on the 64 predicted frames, and
+ancsh_reproject_compare_rec, with the record the stream fitted for that batch.
+
+    python tools/render_bench.py [--sensor | --reprojection] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -129,9 +134,77 @@ def sensor_bench(args, K, B, N, dev, mesh, rbatches, d_geom, d_sc, clean, cap):
                                 "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
 
 
+def reprojection_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc, clean, cap):
+    """--reprojection: the rendered stream with and without reprojection=True, alternated; then the option's three calls alone (the table
+    builder, the renderer on 2 B predicted frames, the comparison) on the last batch, with the record the stream fitted for it."""
+    from articulated_pose_amd.pose import reprojection as R
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
+              depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
+    pipes = {"r": AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare(), "p": AncshPipeline(K, wa, wn, B, N, dev, reprojection=True, **kw).prepare()}
+    torch.cuda.synchronize()
+    last = {}
+
+    def leg(name, passes):
+        t0, n = time.perf_counter(), 0
+        for got in pipes[name].stream_render_batches(rbatches[k] for _ in range(passes) for k in range(len(rbatches))):
+            n += 1
+        torch.cuda.synchronize()
+        last[name] = got[2]
+        return 1e3 * (time.perf_counter() - t0) / n
+
+    for name in "rp":
+        leg(name, 1)
+    ms = {name: [] for name in "rp"}
+    for _ in range(args.rounds):
+        for name in "rp":
+            ms[name].append(leg(name, args.passes))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    W = last["r"].shape[2]
+    assert last["p"].shape[2] == W + R.REPROJECTION_WIDTH and last["p"][:, :, :W].tobytes() == last["r"].tobytes()
+    # the record the three calls are timed on: the stream's own last one with both poses of every part replaced by the pose that undoes the
+    # frame's scene map (the rig and the norm factor are the identity here: [s R | t] = D M^-1), so that every part is drawn and scored
+    # twice -- random-weight networks leave most poses NaN, and a NaN pose draws nothing
+    exact = np.ascontiguousarray(last["p"][:, :, :W])
+    sc = rbatches[-1][2]["scene"]
+    for f in range(B):
+        for j in range(K):
+            M = np.vstack([sc[f, D.SCENE_HEAD + D.SCENE_LINK * j + 2:D.SCENE_HEAD + D.SCENE_LINK * (j + 1)].reshape(3, 4), [0, 0, 0, 1.0]])
+            pose = np.diag([1.0, -1.0, 1.0, 1.0]) @ np.linalg.inv(M)
+            exact[f, j, :13] = exact[f, j, 13:26] = np.concatenate([pose[:3, :3].reshape(9), [1.0], pose[:3, 3]])
+    carried = torch.from_numpy(exact).to(dev)
+    d_rig, d_nf = torch.from_numpy(rbatches[-1][2]["rig"]).to(dev), torch.from_numpy(rbatches[-1][1]).to(dev)
+    tables = (torch.zeros((2 * B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * B, D.GEOM_WORDS), dtype=torch.int32, device=dev))
+    pred = R.predicted_buffers(cap, "uint16", dev)
+    wide = torch.empty((B, K, W + R.REPROJECTION_WIDTH), dtype=torch.float64, device=dev)
+    calls = {"scene_build": lambda: R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables),
+             "render_2B_frames": lambda: D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2]),
+             "compare": lambda: R.reproject_compare(clean[0], clean[1], pred[0], pred[1], d_geom, d_sc, carried, out=wide)}
+    op_ms = {name: timed_calls(call, args.rounds, args.calls) for name, call in calls.items()}
+    cols, timed = R.named_columns(last["p"]), R.named_columns(wide.cpu().numpy())
+    print(json.dumps({"metric": "render-and-compare: ms per batch of the rendered stream without (r) and with (p) reprojection=True; ms per call of the "
+                                "option's three calls alone on one batch",
+                      "device": torch.cuda.get_device_name(0), "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
+                      "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                      "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "added_ms_per_batch": round(med["p"] - med["r"], 4),
+                      "p_over_r": round(med["p"] / med["r"], 4), "operator_ms_per_batch": {k: round(float(np.median(v)), 4) for k, v in op_ms.items()},
+                      "operator_ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in op_ms.items()},
+                      "device_bytes_per_pixel_of_capacity_and_slot": 2 * (2 + 1 + 8),
+                      "streamed_last_batch": {"parts": B * K, "parts_with_a_finite_baseline_pose": int(np.isfinite(cols["baseline_n_pred"]).sum()),
+                                              "parts_with_a_finite_nonlinear_pose": int(np.isfinite(cols["nonlinear_n_pred"]).sum()),
+                                              "predicted_pixels": float(np.nansum(cols["baseline_n_pred"]) + np.nansum(cols["nonlinear_n_pred"]))},
+                      "operator_record": {"median_iou": float(np.median(timed["nonlinear_iou"])),
+                                          "predicted_pixels": float(timed["baseline_n_pred"].sum() + timed["nonlinear_n_pred"].sum()),
+                                          "max_abs_d": float(timed["nonlinear_max_abs"].max())},
+                      "crop_pixels_per_frame": args.side * args.side, "triangles": int(mesh[1].shape[0]),
+                      "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(rbatches) * B,
+                                "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sensor", action="store_true", help="measure the depth sensor model instead of the renderer")
+    ap.add_argument("--reprojection", action="store_true", help="measure render-and-compare (reprojection=True) instead of the renderer")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
     ap.add_argument("--slots", type=int, default=8)
@@ -163,6 +236,9 @@ def main():
     if args.sensor:
         D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
         return sensor_bench(args, K, B, N, dev, mesh, rbatches, d_geom, torch.from_numpy(sc).to(dev), out, cap)
+    if args.reprojection:
+        D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
+        return reprojection_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, torch.from_numpy(sc).to(dev), out, cap)
     op_ms = timed_calls(lambda: D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf), args.rounds, args.calls)
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
