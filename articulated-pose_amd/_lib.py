@@ -287,3 +287,18 @@ def require_cuda(*tensors):
         if t is not None and not t.is_cuda:
             raise RuntimeError("articulated-pose_amd ops run on the MI355X only: got a CPU tensor "
                                "(no CPU fallback in the product path)")
+
+
+def require_device(*on):
+    """The guard an op puts in front of everything else: `on` = the tensor that names its device, or an eager wrapper's torch.device.  A
+    RuntimeError, where every later check is a ValueError."""
+    for t in on:
+        if not (t.type == "cuda" if isinstance(t, torch.device) else t.is_cuda):
+            raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+
+
+def cuda_device(device):
+    """An eager wrapper's device argument -> the torch.device; require_device's RuntimeError unless it is a GPU."""
+    dev = torch.device(device)
+    require_device(dev)
+    return dev

@@ -48,9 +48,7 @@ def create_unit_data_batch(clouds, num_points, norm_factors, n_parts, perms=None
     (np.random.permutation(tiled_size)), else drawn on the device from `seed`.
     Returns the nocs_type 'A' record (:378-391) as (B, N, .) float32 device tensors:
     P, cls_gt, mask_array, nocs_gt, nocs_gt_g, heatmap_gt, unitvec_gt, orient_gt, joint_cls_gt, joint_cls_mask."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     packed = [c if isinstance(c, np.ndarray) else pack_cloud(c) for c in clouds]
     B = len(packed)
     if B == 0:
@@ -160,9 +158,7 @@ def sample_raw_batch(clouds, num_points, norm_factors, seed, device="cuda:0", re
     xyz_only=True: the xyz twins (ancsh_input_sample_stream_xyz / _xyz_keyed) on (n_raw, 3) clouds (a 4th column is dropped): the same
     P and perm, no joint_cls.
     -> dict(P (B,N,3) float32 = xyz * norm_factor, joint_cls (B,N) int32 [, perm (B,N) int32 = pi_b(i)]) on `device`."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     clouds, nf = check_raw_clouds(clouds, norm_factors, xyz_only=xyz_only)
     B = len(clouds)
     offsets = np.zeros(B + 1, np.int32)
@@ -202,9 +198,7 @@ def raw_point_labels(raw_rows, offsets, norm_factors, P, npcs_pred, ancsh_pred, 
     labels = the first argmax of the interpolated W (-1 for a non-finite point or W), values = [W_label | nocs of the label's part | gocs of
     the label's part (or the 3-channel gocs)], NaN with label -1.  Rows beyond offsets[B] are left as `out` holds them (freshly allocated:
     -1 / NaN).  out = (labels, values): preallocated outputs (the captured streaming step passes slot-owned buffers); no host sync."""
-    dev = P.device if torch.is_tensor(P) else torch.device("cuda:0")
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(P.device if torch.is_tensor(P) else "cuda:0")
 
     def f32(a):
         return torch.as_tensor(a).to(dev, torch.float32).contiguous()
@@ -468,9 +462,7 @@ def build_point_gt_rows(clouds7, rigs, device="cuda:0", K=None, capacity=None):
     pack_joint_rig table per cloud (all of the same K; K is read from their width unless given) -> (rows (n_total, 18) float32 device
     tensor in dataset.pack_cloud's layout, offsets (B+1,) int32 device tensor).  capacity: rows of the buffers (>= n_total); rows beyond
     n_total are left as allocated.  The host refuses a non-integer or out-of-range part column before anything touches the device."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     rigs = np.asarray(rigs, np.float64)
     if K is None:
         K = next((k for k in range(1, MAX_RIG_PARTS + 1) if rigs.ndim == 2 and RIG_WIDTH(k) == rigs.shape[1]), None)

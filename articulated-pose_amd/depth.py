@@ -69,6 +69,24 @@ def unprojection_from_projmat(projMat, height, width):
                      -2.0 * M[0, 1] / W, -2.0 * M[1, 1] / H, -((p02 - 1.0) * M[0, 1] + (p12 - 1.0) * M[1, 1])], np.float64)
 
 
+def check_norm_factors(norm_factors, n):
+    """-> the norm factors of n frames as a (n,) float32 array; ValueError unless there is one finite value per frame."""
+    nf = np.asarray(norm_factors, np.float32).reshape(-1)
+    if nf.size != n or not np.isfinite(nf).all():
+        raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n, nf.tolist()))
+    return nf
+
+
+def _per_frame(tables, n, width):
+    """One (width,) float64 table, repeated for each of n frames, or whatever array `tables` is: its caller refuses any shape but (n, width)
+    in its own words (and what is no array at all as shape (0,))."""
+    try:
+        a = np.asarray(tables, np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    return np.broadcast_to(a, (n, width)) if a.shape == (width,) else a
+
+
 def check_depth_frames(frames, norm_factors, cameras, depth_scale, depth_dtype, max_clouds=None):
     """Validate a batch of depth frames before anything is enqueued.  frames: 1..max_clouds tuples (depth_crop (h, w) of dtype
     depth_dtype, mask_crop (h, w) or None, (row0, col0)); norm_factors: one finite value per frame; cameras: one 6-vector or one per
@@ -109,15 +127,8 @@ def check_depth_frames(frames, norm_factors, cameras, depth_scale, depth_dtype, 
         masks.append(m)
         origins.append((r0, c0))
     n = len(depths)
-    nf = np.asarray(norm_factors, np.float32).reshape(-1)
-    if nf.size != n or not np.isfinite(nf).all():
-        raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n, nf.tolist()))
-    try:
-        cam64 = np.asarray(cameras, np.float64)
-    except (TypeError, ValueError):
-        cam64 = np.zeros(0)
-    if cam64.shape == (6,):
-        cam64 = np.broadcast_to(cam64, (n, 6))
+    nf = check_norm_factors(norm_factors, n)
+    cam64 = _per_frame(cameras, n, 6)
     if cam64.shape != (n, 6) or not np.isfinite(cam64).all():
         raise ValueError("cameras: one finite 6-vector (A00 A01 A02 A10 A11 A12), or one per frame (%d frames)" % n)
     try:
@@ -152,26 +163,105 @@ def pack_depth_frames(depths, masks, origins, pix, mask, geom, first=0):
     return a
 
 
+# ---- what the device wrappers below check before a launch: one function and one message template per kind of buffer.  A wrapper calls them
+# in the order its arguments are refused in; what only one wrapper takes (a sensor table, a mesh) it checks itself ---------------------------
+_DEPTH_KINDS = {torch.float32: 1, torch.int16: 0}                       # a depth tensor's dtype -> the ABI's depth_type
+if hasattr(torch, "uint16"):
+    _DEPTH_KINDS[torch.uint16] = 0
+
+
+def _depth_plane(depth, name=None):
+    """-> (depth_type, pixel_capacity) of a flat depth tensor; name: the one depth dtype ("uint16" | "float32") the caller takes."""
+    kind = _DEPTH_KINDS.get(depth.dtype)
+    if kind is None or (name is not None and kind != DEPTH_DTYPES[name][2]) or depth.dim() != 1 or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous 1-d %s tensor" % (name or "uint16 or float32"))
+    return kind, int(depth.shape[0])
+
+
+def _byte_plane(name, t, cap_px, none=None):
+    """The byte beside every depth pixel, a mask or the link labels.  none: what the wrapper makes of None -- "every pixel": it passes (a
+    mask); "refused": the ValueError of any other bad plane; by default the wrapper does not look for it."""
+    if t is None and none == "every pixel":
+        return
+    if (t is None and none == "refused") or t.dtype != torch.uint8 or tuple(t.shape) != (cap_px,) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous (%d,) uint8 tensor" % (name, cap_px))
+
+
+def _pixel_pair(what, whose, depth, labels, dtype, n):
+    """A second (depth, labels) pair of n pixels beside the one the wrapper reads."""
+    if depth.dtype != dtype or tuple(depth.shape) != (n,) or labels.dtype != torch.uint8 or tuple(labels.shape) != (n,) \
+            or not (depth.is_contiguous() and labels.is_contiguous()):
+        raise ValueError("%s must be contiguous (depth (%d,) of the %s dtype, labels (%d,) uint8)" % (what, n, whose, n))
+
+
+_CAM_TABLE = ("cam", CAM_WORDS, torch.float32)                          # _geom_table's kinds; _SCENE_TABLE and _RENDER_TABLE below
+
+
+def _geom_table(geom, table=None, kind=None):
+    """-> B, the frames of the geometry rows (B, 5) int32 and, with kind = (name, width, dtype), of the per-frame table beside them."""
+    B = int(geom.shape[0])
+    ok = geom.dtype == torch.int32 and tuple(geom.shape) == (B, GEOM_WORDS)
+    if kind is not None:
+        name, width, dtype = kind
+        ok = ok and table.dtype == dtype and tuple(table.shape) == (B, width)
+    if not (ok and geom.is_contiguous() and (kind is None or table.is_contiguous())):
+        raise ValueError("geom must be (B, 5) int32%s, contiguous"
+                         % ("" if kind is None else " and %s (B, %d) %s" % (name, width, str(dtype).replace("torch.", ""))))
+    return B
+
+
+def _int_vector(name, t, n):
+    if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous (%d,) int32 tensor" % (name, n))
+
+
+def _labelled(labels, values, columns):
+    """-> n when labels is (n,) int32 and values (n, columns) float32, both contiguous; -1 otherwise."""
+    n = int(labels.shape[0]) if labels.dim() == 1 else -1
+    if labels.dtype != torch.int32 or values.dtype != torch.float32 or n < 0 or tuple(values.shape) != (n, columns) \
+            or not (labels.is_contiguous() and values.is_contiguous()):
+        return -1
+    return n
+
+
+def _row_pair(names, labels, values):
+    """-> the row capacity of a (labels (capacity,) int32, values (capacity, 7) float32) pair, named as the wrapper's arguments are."""
+    cap = _labelled(labels, values, LABEL_VALUES)
+    if cap < 0:
+        raise ValueError("%s must be (capacity,) int32 and %s (capacity, %d) float32, contiguous" % (names[0], names[1], LABEL_VALUES))
+    return cap
+
+
+def _image_pair(img_labels, img_values):
+    """-> the image capacity of out = (img_labels (n,) int32, img_values (n, 7) float32)."""
+    icap = _labelled(img_labels, img_values, LABEL_VALUES)
+    if icap < 0:
+        raise ValueError("out must be contiguous (img_labels (n,) int32, img_values (n, %d) float32)" % LABEL_VALUES)
+    return icap
+
+
+def _scratch_given(scratch, n, wrapper):
+    """The scratch tensor an earlier wrapper filled: >= n int32, and never None."""
+    if scratch is None or scratch.dtype != torch.int32 or scratch.numel() < n or not scratch.is_contiguous():
+        raise ValueError("scratch must be the (>= %d,) int32 tensor %s() was given" % (n, wrapper))
+
+
+def _scratch_size(scratch, n, dtype=torch.int32):
+    """A caller's own working memory: >= n elements of dtype."""
+    if scratch.dtype != dtype or scratch.numel() < n or not scratch.is_contiguous():
+        raise ValueError("scratch must be a contiguous %s tensor of >= %d elements" % (str(dtype).replace("torch.", ""), n))
+
+
 def depth_unproject(depth, mask, geom, cam, capacity=None, out=None, scratch=None):
     """ancsh_depth_unproject_stream on device tensors (no host sync): depth (pixel_capacity,) uint16 / float32, mask (pixel_capacity,)
     uint8 or None, geom (B, 5) int32, cam (B, 7) float32.  -> (rows (capacity, 3) float32, offsets (B+1,) int32, counts (B,) int32);
     out = the same triple preallocated (a captured step passes slot-owned buffers); rows beyond offsets[B] keep what they held (fresh:
     zeros)."""
-    if not depth.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(depth)
     dev = depth.device
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap_px = int(depth.shape[0])
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (cap_px,) or not mask.is_contiguous()):
-        raise ValueError("mask must be a contiguous (%d,) uint8 tensor" % cap_px)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or cam.dtype != torch.float32 or tuple(cam.shape) != (B, CAM_WORDS) \
-            or not (geom.is_contiguous() and cam.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and cam (B, 7) float32, contiguous")
+    kind, cap_px = _depth_plane(depth)
+    _byte_plane("mask", mask, cap_px, none="every pixel")
+    B = _geom_table(geom, cam, _CAM_TABLE)
     if out is None:
         capacity = cap_px if capacity is None else int(capacity)
         out = (torch.zeros((capacity, 3), dtype=torch.float32, device=dev), torch.zeros((B + 1,), dtype=torch.int32, device=dev),
@@ -179,7 +269,7 @@ def depth_unproject(depth, mask, geom, cam, capacity=None, out=None, scratch=Non
     rows, offsets, counts = out
     if scratch is None:
         scratch = torch.empty((max(1, B) * MAX_CHUNKS,), dtype=torch.int32, device=dev)
-    _lib.call("ancsh_depth_unproject_stream", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(mask), cap_px, _lib.ptr(geom), _lib.ptr(cam),
+    _lib.call("ancsh_depth_unproject_stream", B, kind, _lib.ptr(depth), _lib.ptr(mask), cap_px, _lib.ptr(geom), _lib.ptr(cam),
               _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(scratch))
     return rows, offsets, counts
 
@@ -195,40 +285,22 @@ def depth_label_images(depth, mask, geom, dest, offsets, labels, values, out=Non
     image starts in the image buffers, < 0 = the cloud writes nothing.  -> (img_labels (image_capacity,) int32, img_values
     (image_capacity, 7) float32); out = the same pair preallocated (a captured step passes slot-owned buffers), else pixel_capacity
     elements prefilled with -1 / NaN.  A pixel without a row reads -1 / NaN; elements of no cloud's image keep what they held."""
-    if not depth.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(depth)
     dev = depth.device
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap_px = int(depth.shape[0])
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (cap_px,) or not mask.is_contiguous()):
-        raise ValueError("mask must be a contiguous (%d,) uint8 tensor" % cap_px)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or not geom.is_contiguous():
-        raise ValueError("geom must be (B, 5) int32, contiguous")
-    for name, t, n in (("dest", dest, B), ("offsets", offsets, B + 1)):
-        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous (%d,) int32 tensor" % (name, n))
-    cap = int(labels.shape[0]) if labels.dim() == 1 else -1
-    if labels.dtype != torch.int32 or values.dtype != torch.float32 or cap < 0 or tuple(values.shape) != (cap, LABEL_VALUES) \
-            or not (labels.is_contiguous() and values.is_contiguous()):
-        raise ValueError("labels must be (capacity,) int32 and values (capacity, %d) float32, contiguous" % LABEL_VALUES)
-    if scratch is None or scratch.dtype != torch.int32 or scratch.numel() < B * MAX_CHUNKS or not scratch.is_contiguous():
-        raise ValueError("scratch must be the (>= %d,) int32 tensor depth_unproject() was given" % (B * MAX_CHUNKS))
+    kind, cap_px = _depth_plane(depth)
+    _byte_plane("mask", mask, cap_px, none="every pixel")
+    B = _geom_table(geom)
+    _int_vector("dest", dest, B)
+    _int_vector("offsets", offsets, B + 1)
+    cap = _row_pair(("labels", "values"), labels, values)
+    _scratch_given(scratch, B * MAX_CHUNKS, "depth_unproject")
     if out is None:
         out = (torch.full((cap_px,), -1, dtype=torch.int32, device=dev),
                torch.full((cap_px, LABEL_VALUES), float("nan"), dtype=torch.float32, device=dev))
     img_labels, img_values = out
-    icap = int(img_labels.shape[0]) if img_labels.dim() == 1 else -1
-    if img_labels.dtype != torch.int32 or img_values.dtype != torch.float32 or icap < 0 or tuple(img_values.shape) != (icap, LABEL_VALUES) \
-            or not (img_labels.is_contiguous() and img_values.is_contiguous()):
-        raise ValueError("out must be contiguous (img_labels (n,) int32, img_values (n, %d) float32)" % LABEL_VALUES)
-    if any(not t.is_cuda for t in (geom, dest, offsets, labels, values, scratch, img_labels, img_values)) or (mask is not None and not mask.is_cuda):
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
-    _lib.call("ancsh_depth_label_images", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(mask), cap_px, _lib.ptr(geom), _lib.ptr(offsets),
+    icap = _image_pair(img_labels, img_values)
+    _lib.require_device(geom, dest, offsets, labels, values, scratch, img_labels, img_values, *(() if mask is None else (mask,)))
+    _lib.call("ancsh_depth_label_images", B, kind, _lib.ptr(depth), _lib.ptr(mask), cap_px, _lib.ptr(geom), _lib.ptr(offsets),
               _lib.ptr(scratch), _lib.ptr(labels), _lib.ptr(values), cap, _lib.ptr(dest), _lib.ptr(img_labels), _lib.ptr(img_values), icap)
     return img_labels, img_values
 
@@ -255,24 +327,37 @@ def cut_label_images(labels, values, shapes, first=0):
 def unproject_depth_batch(frames, cameras, depth_scale, depth_dtype, device="cuda:0"):
     """Eager wrapper: a batch of depth frames -> (clouds: list of (count, 3) float32 arrays in row-major pixel order -- a frame without a
     valid pixel gives one NaN row --, counts (n,) int32).  One host sync; the streaming pipeline (AncshPipeline.submit_depth) has none."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     depths, masks, origins, _, cam = check_depth_frames(frames, np.ones(len(frames)) if isinstance(frames, (list, tuple)) else None,
                                                         cameras, depth_scale, depth_dtype)
-    name = check_depth_dtype(depth_dtype)
-    total = sum(d.size for d in depths)
-    pix, mask, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.zeros(total, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
-    pack_depth_frames(depths, masks, origins, pix, mask, geom)
-    d_pix = torch.from_numpy(pix.view(np.int16) if name == "uint16" else pix).to(dev)
-    rows, off, cnt = depth_unproject(d_pix, torch.from_numpy(mask).to(dev), torch.from_numpy(geom).to(dev), torch.from_numpy(cam).to(dev))
+    _, _, (d_pix, d_mask, d_geom) = _stage_frames(depths, masks, origins, check_depth_dtype(depth_dtype), dev, fill=0)
+    rows, off, cnt = depth_unproject(d_pix, d_mask, d_geom, torch.from_numpy(cam).to(dev))
     rows, off, cnt = rows.cpu().numpy(), off.cpu().numpy(), cnt.cpu().numpy()
     return [rows[off[b]:off[b + 1]].copy() for b in range(len(depths))], cnt
+
+
+def _stage_frames(depths, planes, origins, name, dev, fill):
+    """What the eager wrappers stage of validated frames -> (geom (n, 5) int32 on the host, the batch's pixels, (depth, byte plane, geom) on
+    `dev`): pack_depth_frames' layout from pixel 0, uint16 depths as their int16 bits, `fill` in the byte plane of no frame."""
+    total = sum(d.size for d in depths)
+    pix, plane, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, fill, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
+    pack_depth_frames(depths, planes, origins, pix, plane, geom)
+    up = lambda a: torch.from_numpy(a).to(dev)
+    return geom, total, (up(pix.view(np.int16) if name == "uint16" else pix), up(plane), up(geom))
+
+
+def _cut_frames(depth, labels, geom, name, first=0):
+    """Flat host (depth, labels) buffers -> the frames [(depth_crop (h, w) of the dtype `name`, label_crop (h, w), (row0, col0))] of the
+    geometry rows, frame k's crop at element `first` + its start; fresh arrays."""
+    depth = depth.view(np.uint16) if name == "uint16" else depth
+    cut = lambda a, g: a[first + g[0]:first + g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy()
+    return [(cut(depth, g), cut(labels, g), (int(g[3]), int(g[4]))) for g in geom]
 
 
 # ---- annotated depth frames: depth + link labels -> the 7-column rows ancsh_point_gt_build reads (ancsh_depth_annotate_stream) -----------
 SCENE_WIDTH, SCENE_MAX_LINKS, SCENE_HEAD, SCENE_LINK = 240, 16, 16, 14      # include/ancsh_hip.h, ANCSH_SCENE_*
 NOT_OBJECT = 255                    # the label byte of a pixel of no link
+_SCENE_TABLE = ("scene", SCENE_WIDTH, torch.float64)
 
 
 def coord_unprojection_from_projmat(projMat, height, width):
@@ -312,6 +397,57 @@ def _rotation_from_rpy(roll, pitch, yaw):
     return T
 
 
+# what pack_frame_scene, pack_render_scene and pack_kinematics each need of the reference's conventions (tools/preprocess_data.py)
+def _link_poses(link_world_pos, link_world_orn):
+    """-> (pos (L, 3), orn (L, 4) [x y z w], L) float64 of 1..16 links' world poses."""
+    pos, orn = np.asarray(link_world_pos, np.float64), np.asarray(link_world_orn, np.float64)
+    L = pos.shape[0] if pos.ndim == 2 else 0
+    if not 1 <= L <= SCENE_MAX_LINKS or pos.shape != (L, 3) or orn.shape != (L, 4):
+        raise ValueError("link_world_pos must be (L, 3) and link_world_orn (L, 4) [x y z w] for 1..%d links, got %s and %s"
+                         % (SCENE_MAX_LINKS, pos.shape, orn.shape))
+    return pos, orn, L
+
+
+def _cam2world(V):
+    """pinv(viewMat.T) with its first three rows negated (:302-303)."""
+    cam2world = np.linalg.pinv(V.T)
+    cam2world[:3, :] = -cam2world[:3, :]
+    return cam2world
+
+
+def _model2world(orn, pos):
+    """A link's (4, 4) world pose from its quaternion [x y z w] -- w goes first (:247-252) -- and position."""
+    model2world = _rotation_from_quaternion(orn[3], orn[0], orn[1], orn[2])
+    model2world[:3, 3] = pos
+    return model2world
+
+
+def _link_ranks(parts_map, L):
+    """{link: (its position in the flattened parts_map, its group's index)}; ValueError unless the map names links of [0, L), each once."""
+    flat = [(int(link), j) for j, group in enumerate(parts_map) for link in group]
+    if len(set(l for l, _ in flat)) != len(flat) or any(not 0 <= l < L for l, _ in flat):
+        raise ValueError("parts_map must name each of its links once, all in [0, %d): got %r" % (L, parts_map))
+    return {l: (r, j) for r, (l, j) in enumerate(flat)}
+
+
+def _canonical_offset(l, L, urdf_link_xyz, urdf_joint_xyz):
+    """The translation of link l's canonical -> URDF map (:239-242): -urdf_link_xyz[l], but link 1 of a two-link object takes the joint's."""
+    if l == 1 and L == 2:
+        joint = np.asarray(urdf_joint_xyz, np.float64)
+        if joint.ndim != 2 or joint.shape[0] < 1 or joint.shape[1] != 3:
+            raise ValueError("urdf_joint_xyz must be (>= 1, 3) for a two-link object, got %s" % (joint.shape,))
+        return joint[0]
+    return -urdf_link_xyz[l]
+
+
+def _inverse_pixel_map(C):
+    """The six coefficients (row-major 2 x 3) of the inverse of coord_unprojection_from_projmat's affine pixel -> (s, t) map C."""
+    A = np.array([[C[0], C[1]], [C[3], C[4]]])
+    Ainv = np.linalg.inv(A)
+    shift = -(Ainv @ np.array([C[2], C[5]]))
+    return np.array([Ainv[0, 0], Ainv[0, 1], shift[0], Ainv[1, 0], Ainv[1, 1], shift[1]])
+
+
 def pack_frame_scene(viewMat, projMat, link_world_pos, link_world_orn, urdf_link_xyz, urdf_link_rpy, urdf_joint_xyz, parts_map, height,
                      width, depth_scale=1.0, min_link_pixels=10):
     """One frame's scene table (SCENE_WIDTH,) float64 for ancsh_depth_annotate_stream (include/ancsh_hip.h has its layout), from what
@@ -326,11 +462,7 @@ def pack_frame_scene(viewMat, projMat, link_world_pos, link_world_orn, urdf_link
     V, P = np.asarray(viewMat, np.float64), np.asarray(projMat, np.float64)
     if V.shape != (4, 4):
         raise ValueError("viewMat must be (4, 4), got %s" % (V.shape,))
-    pos, orn = np.asarray(link_world_pos, np.float64), np.asarray(link_world_orn, np.float64)
-    L = pos.shape[0] if pos.ndim == 2 else 0
-    if not 1 <= L <= SCENE_MAX_LINKS or pos.shape != (L, 3) or orn.shape != (L, 4):
-        raise ValueError("link_world_pos must be (L, 3) and link_world_orn (L, 4) [x y z w] for 1..%d links, got %s and %s"
-                         % (SCENE_MAX_LINKS, pos.shape, orn.shape))
+    pos, orn, L = _link_poses(link_world_pos, link_world_orn)
     xyz, rpy = np.asarray(urdf_link_xyz, np.float64), np.asarray(urdf_link_rpy, np.float64)
     if xyz.shape != (L, 3) or rpy.shape != (L, 3):
         raise ValueError("urdf_link_xyz and urdf_link_rpy must be (%d, 3), got %s and %s" % (L, xyz.shape, rpy.shape))
@@ -339,24 +471,13 @@ def pack_frame_scene(viewMat, projMat, link_world_pos, link_world_orn, urdf_link
     scene[6] = float(depth_scale)
     scene[7:13] = coord_unprojection_from_projmat(P, height, width)
     scene[13], scene[14] = float(min_link_pixels), L
-    flat = [(int(link), j) for j, group in enumerate(parts_map) for link in group]
-    if len(set(l for l, _ in flat)) != len(flat) or any(not 0 <= l < L for l, _ in flat):
-        raise ValueError("parts_map must name each of its links once, all in [0, %d): got %r" % (L, parts_map))
-    rank = {l: (r, j) for r, (l, j) in enumerate(flat)}
-    cam2world = np.linalg.pinv(V.T)                                     # :302-303
-    cam2world[:3, :] = -cam2world[:3, :]
+    rank = _link_ranks(parts_map, L)
+    cam2world = _cam2world(V)
     for l in range(L):
         at = SCENE_HEAD + SCENE_LINK * l
         scene[at], scene[at + 1] = rank.get(l, (-1, 0))
-        model2world = _rotation_from_quaternion(orn[l, 3], orn[l, 0], orn[l, 1], orn[l, 2])        # [x y z w] -> w first (:247-252)
-        model2world[:3, 3] = pos[l]
-        if l == 1 and L == 2:                                           # :239-242
-            joint = np.asarray(urdf_joint_xyz, np.float64)
-            if joint.ndim != 2 or joint.shape[0] < 1 or joint.shape[1] != 3:
-                raise ValueError("urdf_joint_xyz must be (>= 1, 3) for a two-link object, got %s" % (joint.shape,))
-            offset = joint[0]
-        else:
-            offset = -xyz[l]
+        model2world = _model2world(orn[l], pos[l])
+        offset = _canonical_offset(l, L, xyz, urdf_joint_xyz)
         canon2urdf = _rotation_from_rpy(*rpy[l])                        # :313-318
         canon2urdf[:3, 3] = offset
         # row vectors: p @ cam2world @ pinv(model2world.T) -> its first three coordinates and a one -> @ canon2urdf.T (:304-305, :319-320)
@@ -371,12 +492,7 @@ def check_scenes(scenes, n, K):
     """-> scenes as a C-contiguous (n, SCENE_WIDTH) float64 array (one table is repeated for every frame); ValueError (before anything
     touches a device) unless every table is finite, holds 1..16 links, the ranks of its used links are a permutation of 0 .. used - 1 and
     their parts lie in [0, K)."""
-    try:
-        a = np.asarray(scenes, np.float64)
-    except (TypeError, ValueError):
-        a = np.zeros(0)
-    if a.shape == (SCENE_WIDTH,):
-        a = np.broadcast_to(a, (n, SCENE_WIDTH))
+    a = _per_frame(scenes, n, SCENE_WIDTH)
     if a.shape != (n, SCENE_WIDTH):
         raise ValueError("scenes: one (%d,) table (depth.pack_frame_scene), or one per frame (%d frames), got shape %s"
                          % (SCENE_WIDTH, n, a.shape))
@@ -428,21 +544,11 @@ def depth_annotate(depth, labels, geom, scene, capacity=None, out=None, scratch=
     uint8, geom (B, 5) int32, scene (B, SCENE_WIDTH) float64.  -> (rows (capacity, 7) float32, offsets (B+1,) int32, counts (B,) int32,
     link_counts (B, 16) int32); out = the same four preallocated (a captured step passes slot-owned buffers); rows beyond offsets[B] keep
     what they held (fresh: zeros)."""
-    if not depth.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(depth)
     dev = depth.device
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap_px = int(depth.shape[0])
-    if labels is None or labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
-        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
-            or not (geom.is_contiguous() and scene.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and scene (B, %d) float64, contiguous" % SCENE_WIDTH)
+    kind, cap_px = _depth_plane(depth)
+    _byte_plane("labels", labels, cap_px, none="refused")
+    B = _geom_table(geom, scene, _SCENE_TABLE)
     if out is None:
         capacity = cap_px if capacity is None else int(capacity)
         out = (torch.zeros((capacity, 7), dtype=torch.float32, device=dev), torch.zeros((B + 1,), dtype=torch.int32, device=dev),
@@ -454,10 +560,10 @@ def depth_annotate(depth, labels, geom, scene, capacity=None, out=None, scratch=
         raise ValueError("link_counts must be a contiguous (B, %d) int32 tensor" % SCENE_MAX_LINKS)
     if scratch is None:
         scratch = torch.empty((max(1, B) * MAX_CHUNKS * SCENE_MAX_LINKS,), dtype=torch.int32, device=dev)
-    elif scratch.dtype != torch.int32 or scratch.numel() < B * MAX_CHUNKS * SCENE_MAX_LINKS or not scratch.is_contiguous():
-        raise ValueError("scratch must be a contiguous int32 tensor of >= %d elements" % (B * MAX_CHUNKS * SCENE_MAX_LINKS))
+    else:
+        _scratch_size(scratch, B * MAX_CHUNKS * SCENE_MAX_LINKS)
     _lib.require_cuda(labels, geom, scene, rows, offsets, counts, link_counts, scratch)
-    _lib.call("ancsh_depth_annotate_stream", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(labels), cap_px, _lib.ptr(geom),
+    _lib.call("ancsh_depth_annotate_stream", B, kind, _lib.ptr(depth), _lib.ptr(labels), cap_px, _lib.ptr(geom),
               _lib.ptr(scene), _lib.ptr(rows), int(rows.shape[0]), _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(link_counts),
               _lib.ptr(scratch))
     return rows, offsets, counts, link_counts
@@ -469,18 +575,11 @@ def annotate_depth_batch(frames, scenes, depth_dtype, K, device="cuda:0"):
     rows are rows7[offsets[b]:offsets[b] + counts[b]], link-major in parts_map's order as dataset.pack_annotated_cloud packs them; a frame
     without rows (no valid pixel, or a used link below the scene's minimum) owns one NaN row and counts 0.  One host sync; the streaming
     pipeline (AncshPipeline.submit_depth with scene=) has none."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     depths, labels, origins, _, scenes = check_annotated_frames(frames, np.ones(len(frames)) if isinstance(frames, (list, tuple)) else None,
                                                                 scenes, depth_dtype, K)
-    name = check_depth_dtype(depth_dtype)
-    total = sum(d.size for d in depths)
-    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
-    pack_depth_frames(depths, labels, origins, pix, lab, geom)
-    d_pix = torch.from_numpy(pix.view(np.int16) if name == "uint16" else pix).to(dev)
-    rows, off, cnt, lc = depth_annotate(d_pix, torch.from_numpy(lab).to(dev), torch.from_numpy(geom).to(dev), torch.from_numpy(scenes).to(dev),
-                                        capacity=total + len(depths))
+    _, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, check_depth_dtype(depth_dtype), dev, NOT_OBJECT)
+    rows, off, cnt, lc = depth_annotate(d_pix, d_lab, d_geom, torch.from_numpy(scenes).to(dev), capacity=total + len(depths))
     off = off.cpu().numpy()
     return rows[:int(off[-1])].cpu().numpy(), off, cnt.cpu().numpy(), lc.cpu().numpy()
 
@@ -539,21 +638,11 @@ def depth_sensor_model(depth, labels, geom, scene, sensor, seed_or_key, out=None
     device (check_sensor's table); seed_or_key: the device seed (1,) int64, or the key block (4,) int32 (ancsh_depth_sensor_model_keyed).
     -> (depth, labels) of the degraded frame; out = the same pair preallocated (a captured step passes slot-owned buffers), never the input
     pair; else pixel_capacity pixels of depth 0 / label 255.  Every pixel of every crop is written, the others keep what they held."""
-    if not depth.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(depth)
     dev = depth.device
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap_px = int(depth.shape[0])
-    if labels is None or labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
-        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
-            or not (geom.is_contiguous() and scene.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and scene (B, %d) float64, contiguous" % SCENE_WIDTH)
+    kind, cap_px = _depth_plane(depth)
+    _byte_plane("labels", labels, cap_px, none="refused")
+    B = _geom_table(geom, scene, _SCENE_TABLE)
     if sensor.dtype != torch.float64 or tuple(sensor.shape) != (SENSOR_WIDTH,) or not sensor.is_contiguous():
         raise ValueError("sensor must be a contiguous (%d,) float64 tensor (depth.pack_sensor's table)" % SENSOR_WIDTH)
     keyed = seed_or_key.dtype == torch.int32
@@ -563,11 +652,9 @@ def depth_sensor_model(depth, labels, geom, scene, sensor, seed_or_key, out=None
     if out is None:
         out = (torch.zeros((cap_px,), dtype=depth.dtype, device=dev), torch.full((cap_px,), NOT_OBJECT, dtype=torch.uint8, device=dev))
     depth_out, labels_out = out
-    if depth_out.dtype != depth.dtype or tuple(depth_out.shape) != (cap_px,) or labels_out.dtype != torch.uint8 \
-            or tuple(labels_out.shape) != (cap_px,) or not (depth_out.is_contiguous() and labels_out.is_contiguous()):
-        raise ValueError("out must be contiguous (depth (%d,) of the input's dtype, labels (%d,) uint8)" % (cap_px, cap_px))
+    _pixel_pair("out", "input's", depth_out, labels_out, depth.dtype, cap_px)
     _lib.require_cuda(labels, geom, scene, sensor, seed_or_key, depth_out, labels_out)
-    _lib.call("ancsh_depth_sensor_model_keyed" if keyed else "ancsh_depth_sensor_model", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(labels),
+    _lib.call("ancsh_depth_sensor_model_keyed" if keyed else "ancsh_depth_sensor_model", B, kind, _lib.ptr(depth), _lib.ptr(labels),
               cap_px, _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(sensor), _lib.ptr(seed_or_key), _lib.ptr(depth_out), _lib.ptr(labels_out))
     return depth_out, labels_out
 
@@ -579,9 +666,7 @@ def sensor_frames(frames, scenes, sensor, depth_dtype, seed=0, cloud_base=0, dev
     0 and label 255.  Frame f is keyed as frame cloud_base + f: the frames a streaming pipeline built with sensor= makes of the same batch
     with the same seed and base.  One host sync; the pipeline has none."""
     from .dataset import stream_key_words
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     table = check_sensor(sensor)
     name = check_depth_dtype(depth_dtype)
     depths, labels, origins, _, scenes = check_annotated_frames(frames, np.ones(len(frames)) if isinstance(frames, (list, tuple)) else None,
@@ -589,16 +674,10 @@ def sensor_frames(frames, scenes, sensor, depth_dtype, seed=0, cloud_base=0, dev
     cloud_base = int(cloud_base)
     if not 0 <= cloud_base or cloud_base + len(depths) >= (1 << 20):
         raise ValueError("cloud_base %d with %d frames: the global frame index must stay in [0, 2^20)" % (cloud_base, len(depths)))
-    total = sum(d.size for d in depths)
-    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
-    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    geom, _, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, name, dev, NOT_OBJECT)
     t = lambda a: torch.from_numpy(a).to(dev)
-    depth, labels = depth_sensor_model(t(pix.view(np.int16) if name == "uint16" else pix), t(lab), t(geom), t(scenes), t(table),
-                                       t(stream_key_words(seed, cloud_base)))
-    depth, labels = depth.cpu().numpy(), labels.cpu().numpy()
-    depth = depth.view(np.uint16) if name == "uint16" else depth
-    return [(depth[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(), labels[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(),
-             (int(g[3]), int(g[4]))) for g in geom]
+    depth, labels = depth_sensor_model(d_pix, d_lab, d_geom, t(scenes), t(table), t(stream_key_words(seed, cloud_base)))
+    return _cut_frames(depth.cpu().numpy(), labels.cpu().numpy(), geom, name)
 
 
 # ---- annotated frames, back on the pixel grid: predicted and true part / NOCS images (ancsh_depth_annotated_images) ----------------------
@@ -624,32 +703,18 @@ def depth_annotated_images(depth, labels, geom, scene, dest, offsets, counts, ro
     int32, img_values (image_capacity, 7) float32, img_gt_labels (image_capacity,) int32, img_gt_values (image_capacity, 6) float32); out =
     the same four preallocated (a captured step passes slot-owned buffers), else pixel_capacity elements prefilled with -1 / NaN.  A pixel
     without a row reads -1 / NaN in all four; elements of no cloud's image keep what they held."""
-    if not depth.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(depth)
     dev = depth.device
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if depth.dtype not in kinds or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap_px = int(depth.shape[0])
-    if labels is None or labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
-        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or scene.dtype != torch.float64 or tuple(scene.shape) != (B, SCENE_WIDTH) \
-            or not (geom.is_contiguous() and scene.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and scene (B, %d) float64, contiguous" % SCENE_WIDTH)
-    for name, t, n in (("dest", dest, B), ("offsets", offsets, B + 1), ("counts", counts, B)):
-        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous (%d,) int32 tensor" % (name, n))
-    cap = int(row_labels.shape[0]) if row_labels.dim() == 1 else -1
-    if row_labels.dtype != torch.int32 or row_values.dtype != torch.float32 or cap < 0 or tuple(row_values.shape) != (cap, LABEL_VALUES) \
-            or not (row_labels.is_contiguous() and row_values.is_contiguous()):
-        raise ValueError("row_labels must be (capacity,) int32 and row_values (capacity, %d) float32, contiguous" % LABEL_VALUES)
+    kind, cap_px = _depth_plane(depth)
+    _byte_plane("labels", labels, cap_px, none="refused")
+    B = _geom_table(geom, scene, _SCENE_TABLE)
+    _int_vector("dest", dest, B)
+    _int_vector("offsets", offsets, B + 1)
+    _int_vector("counts", counts, B)
+    cap = _row_pair(("row_labels", "row_values"), row_labels, row_values)
     if gt_rows.dtype != torch.float32 or gt_rows.dim() != 2 or gt_rows.shape[0] != cap or gt_rows.shape[1] < 10 or not gt_rows.is_contiguous():
         raise ValueError("gt_rows must be a contiguous (%d, >= 10) float32 tensor (dataset.point_gt_build's rows)" % cap)
-    if scratch is None or scratch.dtype != torch.int32 or scratch.numel() < B * MAX_CHUNKS * SCENE_MAX_LINKS or not scratch.is_contiguous():
-        raise ValueError("scratch must be the (>= %d,) int32 tensor depth_annotate() was given" % (B * MAX_CHUNKS * SCENE_MAX_LINKS))
+    _scratch_given(scratch, B * MAX_CHUNKS * SCENE_MAX_LINKS, "depth_annotate")
     if out is None:
         out = annotated_image_buffers(cap_px, dev)
     img_labels, img_values, img_gt_labels, img_gt_values = out
@@ -661,7 +726,7 @@ def depth_annotated_images(depth, labels, geom, scene, dest, offsets, counts, ro
         raise ValueError("out must be contiguous (img_labels (n,) int32, img_values (n, %d) float32, img_gt_labels (n,) int32, img_gt_values "
                          "(n, %d) float32)" % (LABEL_VALUES, GT_IMAGE_VALUES))
     _lib.require_cuda(labels, geom, scene, dest, offsets, counts, row_labels, row_values, gt_rows, scratch, *out)
-    _lib.call("ancsh_depth_annotated_images", B, kinds[depth.dtype], _lib.ptr(depth), _lib.ptr(labels), cap_px, _lib.ptr(geom), _lib.ptr(scene),
+    _lib.call("ancsh_depth_annotated_images", B, kind, _lib.ptr(depth), _lib.ptr(labels), cap_px, _lib.ptr(geom), _lib.ptr(scene),
               _lib.ptr(offsets), _lib.ptr(counts), _lib.ptr(scratch), _lib.ptr(row_labels), _lib.ptr(row_values), _lib.ptr(gt_rows),
               int(gt_rows.shape[1]), cap, _lib.ptr(dest), _lib.ptr(img_labels), _lib.ptr(img_values), _lib.ptr(img_gt_labels),
               _lib.ptr(img_gt_values), icap)
@@ -692,19 +757,14 @@ def annotated_frame_images(frames, scenes, rigs, depth_dtype, K, norm_factors=No
     (npcs_pred, ancsh_pred); every other pixel -1 / NaN, and so every pixel of a frame without rows.  P = None: no predictions, labels and
     values are -1 / NaN everywhere.  One host sync; the streaming pipeline (annotated_images=True) has none."""
     from .dataset import DENSE_VALUES, NCHAN, check_rigs, point_gt_build, raw_point_labels
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     n = len(frames) if isinstance(frames, (list, tuple)) else 0
     depths, labels, origins, nf, scenes = check_annotated_frames(frames, np.ones(n) if norm_factors is None else norm_factors, scenes,
                                                                  depth_dtype, K)
     rigs = check_rigs(rigs, len(depths), K)
-    name = check_depth_dtype(depth_dtype)
-    total = sum(d.size for d in depths)
-    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((len(depths), GEOM_WORDS), np.int32)
-    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    _, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, check_depth_dtype(depth_dtype), dev, NOT_OBJECT)
     t = lambda a: torch.from_numpy(a).to(dev)
-    d_pix, d_lab, d_geom, d_scene = t(pix.view(np.int16) if name == "uint16" else pix), t(lab), t(geom), t(scenes)
+    d_scene = t(scenes)
     cap = total + len(depths)
     scratch = torch.empty((len(depths) * MAX_CHUNKS * SCENE_MAX_LINKS,), dtype=torch.int32, device=dev)
     rows7, off, cnt, _ = depth_annotate(d_pix, d_lab, d_geom, d_scene, capacity=cap, scratch=scratch)
@@ -719,6 +779,7 @@ def annotated_frame_images(frames, scenes, rigs, depth_dtype, K, norm_factors=No
 
 # ---- rendered frames: articulated triangle meshes -> the depth and link-label crops above (ancsh_render_depth_labels) --------------------
 RENDER_WIDTH, RENDER_HEAD, RENDER_LINK = 208, 16, 12            # include/ancsh_hip.h, ANCSH_RENDER_*
+_RENDER_TABLE = ("render", RENDER_WIDTH, torch.float64)
 
 
 def pack_mesh(links):
@@ -807,27 +868,17 @@ def pack_render_scene(viewMat, projMat, link_world_pos, link_world_orn, height, 
     V, Pm = np.asarray(viewMat, np.float64), np.asarray(projMat, np.float64)
     if V.shape != (4, 4):
         raise ValueError("viewMat must be (4, 4), got %s" % (V.shape,))
-    pos, orn = np.asarray(link_world_pos, np.float64), np.asarray(link_world_orn, np.float64)
-    L = pos.shape[0] if pos.ndim == 2 else 0
-    if not 1 <= L <= SCENE_MAX_LINKS or pos.shape != (L, 3) or orn.shape != (L, 4):
-        raise ValueError("link_world_pos must be (L, 3) and link_world_orn (L, 4) [x y z w] for 1..%d links, got %s and %s"
-                         % (SCENE_MAX_LINKS, pos.shape, orn.shape))
+    pos, orn, L = _link_poses(link_world_pos, link_world_orn)
     depth_scale, z_min = float(depth_scale), float(z_min)
     if not (np.isfinite(depth_scale) and depth_scale > 0 and np.isfinite(z_min) and z_min > 0):
         raise ValueError("depth_scale and z_min must be finite and > 0, got %r and %r" % (depth_scale, z_min))
-    C = coord_unprojection_from_projmat(Pm, height, width)
-    A = np.array([[C[0], C[1]], [C[3], C[4]]])
-    Ainv = np.linalg.inv(A)
+    pixel_map = _inverse_pixel_map(coord_unprojection_from_projmat(Pm, height, width))
     table = np.zeros(RENDER_WIDTH)
-    table[0:2], table[3:5] = Ainv[0], Ainv[1]
-    table[2], table[5] = -(Ainv @ np.array([C[2], C[5]]))
+    table[0:6] = pixel_map
     table[6], table[7], table[8], table[9] = depth_scale, z_min, L, _instance_value(instance)
-    cam2world = np.linalg.pinv(V.T)
-    cam2world[:3, :] = -cam2world[:3, :]
+    cam2world = _cam2world(V)
     for l in range(L):
-        model2world = _rotation_from_quaternion(orn[l, 3], orn[l, 0], orn[l, 1], orn[l, 2])
-        model2world[:3, 3] = pos[l]
-        G = cam2world @ np.linalg.pinv(model2world.T)
+        G = cam2world @ np.linalg.pinv(_model2world(orn[l], pos[l]).T)
         table[RENDER_HEAD + RENDER_LINK * l:RENDER_HEAD + RENDER_LINK * (l + 1)] = np.linalg.inv(G).T[:3].reshape(12)
     if not np.isfinite(table).all():
         raise ValueError("the camera or a link pose is singular: the render table is not finite")
@@ -858,12 +909,7 @@ def check_render_tables(render, n, ninst=None):
     """-> render as a C-contiguous (n, RENDER_WIDTH) float64 array (one table is repeated for every frame); ValueError unless every table is
     finite with depth_scale > 0, z_min > 0, an integer nlinks in 1..16 and zero reserved values.  ninst: the tables go with a mesh library of
     ninst instances, and value 9 must name one of them (None: a single mesh, value 9 is reserved and 0)."""
-    try:
-        a = np.asarray(render, np.float64)
-    except (TypeError, ValueError):
-        a = np.zeros(0)
-    if a.shape == (RENDER_WIDTH,):
-        a = np.broadcast_to(a, (n, RENDER_WIDTH))
+    a = _per_frame(render, n, RENDER_WIDTH)
     if a.shape != (n, RENDER_WIDTH):
         raise ValueError("render must be (%d, %d): one depth.pack_render_scene table, or one per frame, got shape %s" % (n, RENDER_WIDTH, a.shape))
     a = np.ascontiguousarray(a)
@@ -956,8 +1002,7 @@ def mesh_to_device(mesh, device):
 def _check_device_mesh(mesh):
     """The checks render_depth and centre_crop_origins share -> (verts, tris, tri_link, V, T, tri_off or None, ninst, Tmax)."""
     verts, tris, tri_link, V, T = mesh
-    if not verts.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(verts)
     if verts.dtype != torch.float32 or tris.dtype != torch.int32 or tri_link.dtype != torch.int32 or verts.numel() < 3 * max(V, 1) \
             or tris.numel() < 3 * max(T, 1) or tri_link.numel() < max(T, 1) or not (verts.is_contiguous() and tris.is_contiguous() and tri_link.is_contiguous()):
         raise ValueError("mesh must be depth.mesh_to_device's (verts float32, tris int32, tri_link int32, V, T), contiguous")
@@ -977,30 +1022,21 @@ def render_depth(mesh, geom, render, depth_dtype, out=None, scratch=None, pixel_
     the same pair preallocated (a captured step passes slot-owned buffers), else pixel_capacity pixels of depth 0 / label 255; scratch: the
     (pixel_capacity,) int64 z-buffer.  Every pixel of every crop is written, the others keep what they held."""
     name = check_depth_dtype(depth_dtype)
-    _, tt, kind = DEPTH_DTYPES[name]
+    tt = DEPTH_DTYPES[name][1]
     verts, tris, tri_link, V, T, tri_off, ninst, Tmax = _check_device_mesh(mesh)
     dev = verts.device
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
-            or not (geom.is_contiguous() and render.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and render (B, %d) float64, contiguous" % RENDER_WIDTH)
+    B = _geom_table(geom, render, _RENDER_TABLE)
     if out is None:
         if pixel_capacity is None:
             raise ValueError("render_depth needs out=(depth, labels) or pixel_capacity")
         out = (torch.zeros((int(pixel_capacity),), dtype=tt, device=dev), torch.full((int(pixel_capacity),), NOT_OBJECT, dtype=torch.uint8, device=dev))
     depth, labels = out
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if kinds.get(depth.dtype) != kind or depth.dim() != 1 or not depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d %s tensor" % name)
-    cap_px = int(depth.shape[0])
-    if labels.dtype != torch.uint8 or tuple(labels.shape) != (cap_px,) or not labels.is_contiguous():
-        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap_px)
+    kind, cap_px = _depth_plane(depth, name)
+    _byte_plane("labels", labels, cap_px)
     if scratch is None:
         scratch = torch.empty((max(1, cap_px),), dtype=torch.int64, device=dev)
-    elif scratch.dtype != torch.int64 or scratch.numel() < cap_px or not scratch.is_contiguous():
-        raise ValueError("scratch must be a contiguous int64 tensor of >= %d elements" % cap_px)
+    else:
+        _scratch_size(scratch, cap_px, torch.int64)
     _lib.require_cuda(tris, tri_link, geom, render, depth, labels, scratch)
     if tri_off is not None:                # a library: the instance of a frame is its table's value 9
         _lib.call("ancsh_render_depth_labels_lib", B, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(tri_off),
@@ -1016,9 +1052,7 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
     one pack_render_scene table or one per crop, crops = a list of (h, w, (row0, col0)) -> a list of (depth_crop (h, w) of depth_dtype, label_crop (h, w) uint8, (row0, col0)): exactly the frames
     AncshPipeline.submit_depth(..., scene=, rig=) and annotate_depth_batch take.  One host sync; the streaming pipeline
     (AncshPipeline.submit_render) has none, and no pixel of it ever reaches the host."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     name = check_depth_dtype(depth_dtype)
     shapes, origins = check_crops(crops)
     d_mesh = mesh_to_device(mesh, dev)
@@ -1027,10 +1061,7 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
     total = pack_crop_geometry(shapes, origins, geom)
     depth, labels = render_depth(d_mesh, torch.from_numpy(geom).to(dev), torch.from_numpy(tables).to(dev), name,
                                  pixel_capacity=total)
-    depth, labels = depth.cpu().numpy(), labels.cpu().numpy()
-    depth = depth.view(np.uint16) if name == "uint16" else depth
-    return [(depth[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(), labels[g[0]:g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy(),
-             (int(g[3]), int(g[4]))) for g in geom]
+    return _cut_frames(depth.cpu().numpy(), labels.cpu().numpy(), geom, name)
 
 
 def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device="cuda:0"):
@@ -1044,9 +1075,7 @@ def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record,
     the same tables: a pipeline built with reprojection=True streams the same bytes.  One host sync; the pipeline has none."""
     from .dataset import check_rigs
     from .pose.reprojection import REPROJECTION_WIDTH, predicted_buffers, reprojection_batch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     name = check_depth_dtype(depth_dtype)
     rec = np.ascontiguousarray(record, np.float64)
     if rec.ndim != 3 or rec.shape[2] < 26 or not 1 <= rec.shape[1] <= 8:
@@ -1057,20 +1086,16 @@ def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record,
         raise ValueError("record holds %d frames, frames %d" % (n, len(depths)))
     d_mesh = mesh_to_device(mesh, dev)
     tables, rigs = check_render_tables(render_tables, n, d_mesh.ninst), check_rigs(rigs, n, K)
-    total = sum(d.size for d in depths)
-    pix, lab, geom = np.zeros(total, DEPTH_DTYPES[name][0]), np.full(total, NOT_OBJECT, np.uint8), np.zeros((n, GEOM_WORDS), np.int32)
-    pack_depth_frames(depths, labels, origins, pix, lab, geom)
+    geom, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, name, dev, NOT_OBJECT)
     t = lambda a: torch.from_numpy(a).to(dev)
     pred = predicted_buffers(total, name, dev)
     out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
-    wide = reprojection_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), t(geom), (t(pix.view(np.int16) if name == "uint16" else pix), t(lab)),
-                              t(rec), name, out_tables, pred)
+    wide = reprojection_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred)
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
     assert columns.shape == (n, K, REPROJECTION_WIDTH)
     depth, plab = pred[0].cpu().numpy(), pred[1].cpu().numpy()
-    depth = depth.view(np.uint16) if name == "uint16" else depth
-    cut = lambda a, g, v: a[v * total + g[0]:v * total + g[0] + g[1] * g[2]].reshape(g[1], g[2]).copy()
-    return columns, [tuple((cut(depth, g, v), cut(plab, g, v)) for v in (0, 1)) for g in geom]
+    views = [_cut_frames(depth, plab, geom, name, first=v * total) for v in (0, 1)]       # view v's crops lie `total` pixels further on
+    return columns, [tuple(view[:2] for view in frame) for frame in zip(*views)]
 
 
 # ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred
@@ -1153,14 +1178,9 @@ def pack_kinematics(projMat, height, width, parents, joint_kinds, joint_xyz, joi
     kin[6] = depth_scale
     C = kin[7:13] = coord_unprojection_from_projmat(P, height, width)
     kin[13], kin[14] = float(min_link_pixels), L
-    Ainv = np.linalg.inv(np.array([[C[0], C[1]], [C[3], C[4]]]))        # pack_render_scene's pixel map
-    kin[16:18], kin[19:21] = Ainv[0], Ainv[1]
-    kin[18], kin[21] = -(Ainv @ np.array([C[2], C[5]]))
+    kin[16:22] = _inverse_pixel_map(C)                                  # pack_render_scene's pixel map
     kin[22] = z_min
-    flat = [(int(link), j) for j, group in enumerate(parts_map) for link in group]
-    if len(set(l for l, _ in flat)) != len(flat) or any(not 0 <= l < L for l, _ in flat):
-        raise ValueError("parts_map must name each of its links once, all in [0, %d): got %r" % (L, parts_map))
-    rank = {l: (r, j) for r, (l, j) in enumerate(flat)}
+    rank = _link_ranks(parts_map, L)
     if base is None:
         T0 = np.eye(4)[:3]
     else:
@@ -1185,13 +1205,7 @@ def pack_kinematics(projMat, height, width, parents, joint_kinds, joint_xyz, joi
                     raise ValueError("link %d: a %s joint needs a non-zero, finite axis, got %s"
                                      % (l, "revolute" if kinds[l] == 1 else "prismatic", ja[l].tolist()))
                 k[16:19] = ja[l] / n
-        if l == 1 and L == 2:                                           # pack_frame_scene's rule (tools/preprocess_data.py:239-242)
-            joint = np.asarray(urdf_joint_xyz, np.float64)
-            if joint.ndim != 2 or joint.shape[0] < 1 or joint.shape[1] != 3:
-                raise ValueError("urdf_joint_xyz must be (>= 1, 3) for a two-link object, got %s" % (joint.shape,))
-            offset = joint[0]
-        else:
-            offset = -xyz[l]
+        offset = _canonical_offset(l, L, xyz, urdf_joint_xyz)           # pack_frame_scene's rule
         k[19:28] = _rotation_from_rpy(*rpy[l])[:3, :3].reshape(9)
         k[28:31] = offset
     if not np.isfinite(kin).all():
@@ -1276,12 +1290,7 @@ def check_poses(pose, n, ninst=None):
     """-> pose as a C-contiguous (n, POSE_WIDTH) float64 array (one pose is repeated for every frame); ValueError unless every pose is
     finite, its view's rotation orthonormal to 1e-9 (and proper) and its reserved values 0.  ninst: the poses go with a library of ninst
     instances, and value 28 must name one of them (None: a single object, value 28 is reserved and 0)."""
-    try:
-        a = np.asarray(pose, np.float64)
-    except (TypeError, ValueError):
-        a = np.zeros(0)
-    if a.shape == (POSE_WIDTH,):
-        a = np.broadcast_to(a, (n, POSE_WIDTH))
+    a = _per_frame(pose, n, POSE_WIDTH)
     if a.shape != (n, POSE_WIDTH):
         raise ValueError("pose must be (%d, %d): one depth.pack_pose row, or one per frame, got shape %s" % (n, POSE_WIDTH, a.shape))
     a = np.ascontiguousarray(a)
@@ -1318,8 +1327,7 @@ def pose_scene_build(kin, pose, out=None):
     """ancsh_pose_scene_build on device tensors (no host sync): kin (KIN_WIDTH,) float64, pose (B, POSE_WIDTH) float64 -> (render (B,
     RENDER_WIDTH), scene (B, SCENE_WIDTH)) float64; out = the same pair preallocated (a captured step passes slot-owned buffers).  kin (ninst,
     KIN_WIDTH), a library's stack, goes through ancsh_pose_scene_build_lib: frame b reads the table its pose's value 28 names."""
-    if not kin.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(kin)
     B = int(pose.shape[0])
     library = kin.dim() == 2               # a library's stack of tables: the instance of a frame is its pose's value 28
     if kin.dtype != torch.float64 or (tuple(kin.shape) != (KIN_WIDTH,) and not (library and kin.shape[1] == KIN_WIDTH and 1 <= kin.shape[0] <= LIBRARY_MAX_INSTANCES)) \
@@ -1343,9 +1351,7 @@ def pose_scene_tables(kin, poses, device="cuda:0"):
     """Eager wrapper: kin = one pack_kinematics table (or a library's (ninst, 672) stack: each pose's value 28 names its instance), poses =
     one pack_pose row or (n, 32) of them -> (render (n, 208), scene (n, 240))
     float64 numpy arrays read back from ancsh_pose_scene_build: what submit_render and render_depth_frames take.  One host sync."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     library = np.ndim(kin) == 2
     kin = check_kinematics_library(kin) if library else check_kinematics(kin)
     p = np.asarray(poses, np.float64)
@@ -1359,14 +1365,11 @@ def centre_crop_origins(mesh, geom, render, scratch=None):
     float64; the rows of geom whose row0 and col0 both hold CROP_CENTRE get the origin that centres their crop on the projected object, in
     place.  scratch: (B, 4) int32 of working memory.  -> geom.  A mesh library goes through ancsh_render_centre_crops_lib."""
     verts, tris, tri_link, V, T, tri_off, ninst, _ = _check_device_mesh(mesh)
-    B = int(geom.shape[0])
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or render.dtype != torch.float64 or tuple(render.shape) != (B, RENDER_WIDTH) \
-            or not (geom.is_contiguous() and render.is_contiguous()):
-        raise ValueError("geom must be (B, 5) int32 and render (B, %d) float64, contiguous" % RENDER_WIDTH)
+    B = _geom_table(geom, render, _RENDER_TABLE)
     if scratch is None:
         scratch = torch.empty((max(1, B), 4), dtype=torch.int32, device=verts.device)
-    elif scratch.dtype != torch.int32 or scratch.numel() < 4 * B or not scratch.is_contiguous():
-        raise ValueError("scratch must be a contiguous int32 tensor of >= %d elements" % (4 * B))
+    else:
+        _scratch_size(scratch, 4 * B)
     _lib.require_cuda(tris, tri_link, geom, render, scratch)
     if tri_off is not None:                # a library: the block of a frame strides over its instance's triangles only
         _lib.call("ancsh_render_centre_crops_lib", B, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(tri_off), ninst,
@@ -1392,9 +1395,7 @@ def centre_crops(mesh, render_tables, sizes, device="cuda:0"):
     """Eager wrapper: mesh = pack_mesh's arrays (or pack_mesh_library's), render_tables = one render table or one per crop, sizes = a list of (h, w) -> the (n, 2)
     int32 origins (row0, col0) that centre each h x w crop on its frame's projected object (ancsh_render_centre_crops; (0, 0) where nothing
     projects): what submit_render's crops take.  One host sync."""
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    dev = _lib.cuda_device(device)
     shapes, origins = check_posed_crops([(h, w, None) for h, w in sizes])
     d_mesh = mesh_to_device(mesh, dev)
     tables = check_render_tables(render_tables, len(shapes), d_mesh.ninst)

@@ -752,10 +752,7 @@ class AncshPipeline(object):
             n_valid = len(depths)
             pad = self.B - n_valid if o.sensor else 0     # a sensor's draws follow the frame's index: its padding frames get pixels of their own
             pixels = sum(d.size for d in depths) + pad * depths[0].size
-            padded = pixels + (self.B - n_valid - pad) * depths[0].size
-            if padded > o.depth_capacity:
-                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
-                                 % (padded, o.depth_capacity))
+            self._check_depth_capacity(pixels + (self.B - n_valid - pad) * depths[0].size)
 
             def stage(sl):
                 pack_depth_frames(depths + depths[:1] * pad, masks + masks[:1] * pad, list(origins) + [origins[0]] * pad, sl.np_pix, sl.np_mask,
@@ -791,22 +788,9 @@ class AncshPipeline(object):
             from .depth import check_crops, check_scenes
             if render is None or scene is None or rig is None:
                 raise ValueError(SIDE["render"].missing)
-            shapes, origins = check_crops(crops, self.B)
-            n_valid = len(shapes)
-            nf = np.asarray(norm_factors, np.float32).reshape(-1)
-            if nf.size != n_valid or not np.isfinite(nf).all():
-                raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n_valid, nf.tolist()))
+            n_valid, nf, padded, stage = self._crop_front(check_crops, crops, norm_factors)
             scenes = check_scenes(scene, n_valid, self.K)
-            pixels = sum(h * w for h, w in shapes)
-            padded = pixels + (self.B - n_valid) * shapes[0][0] * shapes[0][1]
-            if padded > o.depth_capacity:
-                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
-                                 % (padded, o.depth_capacity))
-
-            def stage(sl):
-                self._stage_crops(sl, shapes, origins)     # the padding frames alias the first frame's pixels (and render the same bytes)
-                self._stage_dest(sl, n_valid)
-                return []
+            self._check_depth_capacity(padded)
             return n_valid, nf, stage, dict(scene=scenes)
         self._enqueue(front, seed, tag, cloud_base, render=render, gt=gt, frame=frame, rig=rig)
 
@@ -829,23 +813,31 @@ class AncshPipeline(object):
             from .depth import check_posed_crops
             if pose is None or rig is None:
                 raise ValueError(SIDE["pose"].missing)
-            shapes, origins = check_posed_crops(crops, self.B)
-            n_valid = len(shapes)
-            nf = np.asarray(norm_factors, np.float32).reshape(-1)
-            if nf.size != n_valid or not np.isfinite(nf).all():
-                raise ValueError("norm_factors: one finite value per frame (%d frames, got %s)" % (n_valid, nf.tolist()))
-            pixels = sum(h * w for h, w in shapes)
-            padded = pixels + (self.B - n_valid) * shapes[0][0] * shapes[0][1]
-            if padded > o.depth_capacity:
-                raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
-                                 % (padded, o.depth_capacity))
-
-            def stage(sl):
-                self._stage_crops(sl, shapes, origins)     # the padding frames alias the first frame's pixels (and pose: the same origin, the same bytes)
-                self._stage_dest(sl, n_valid)
-                return []
+            n_valid, nf, padded, stage = self._crop_front(check_posed_crops, crops, norm_factors)
+            self._check_depth_capacity(padded)
             return n_valid, nf, stage
         self._enqueue(front, seed, tag, cloud_base, pose=pose, gt=gt, frame=frame, rig=rig)
+
+    def _crop_front(self, check, crops, norm_factors):
+        """What submit_render's and submit_posed's front() share: check = depth.check_crops or depth.check_posed_crops -> (valid frames, their
+        norm factors, the pixels of the batch with its padding -- for _check_depth_capacity, once the caller's own tables are checked --,
+        stage).  The padding frames alias the first frame's pixels: they render the same bytes (posed: from the same pose, to the same origin)."""
+        from .depth import check_norm_factors
+        shapes, origins = check(crops, self.B)
+        n_valid = len(shapes)
+        nf = check_norm_factors(norm_factors, n_valid)
+        padded = sum(h * w for h, w in shapes) + (self.B - n_valid) * shapes[0][0] * shapes[0][1]
+
+        def stage(sl):
+            self._stage_crops(sl, shapes, origins)
+            self._stage_dest(sl, n_valid)
+            return []
+        return n_valid, nf, padded, stage
+
+    def _check_depth_capacity(self, pixels):
+        if pixels > self.opts.depth_capacity:
+            raise ValueError("the batch needs %d pixels (short batches are padded with their first frame), depth_capacity is %d"
+                             % (pixels, self.opts.depth_capacity))
 
     def _stage_crops(self, sl, shapes, origins):
         """The geometry rows of crops the step renders: a padding frame renders the first crop again where it lies -- or, with a sensor, whose

@@ -50,8 +50,7 @@ def reproject_scene_build(render, scene, rig, norm_factor, record, geom, pixel_c
     pixels -> (render tables (2B, 208) float64, geometry rows (2B, 5) int32) of the predicted frames, row v * B + f; out = the same pair
     preallocated (a captured step passes slot-owned buffers)."""
     from ..depth import GEOM_WORDS, RENDER_WIDTH
-    if not record.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
+    _lib.require_device(record)
     K = int(record.shape[1]) if record.dim() == 3 else 0
     B = _tables(render, scene, rig, norm_factor, record, geom, K)
     if out is None:
@@ -71,19 +70,11 @@ def reproject_compare(obs_depth, obs_labels, pred_depth, pred_labels, geom, scen
     """ancsh_reproject_compare_rec on device tensors (no host sync): the observed pair (pixel_capacity,), the predicted pair (2 *
     pixel_capacity,) the renderer wrote for reproject_scene_build's tables, the frames' geometry rows and scene tables, and the record so far
     (B, K, ld) float64 -> (B, K, ld + 15) float64: the carried row bit for bit and the 15 columns behind it (COLUMN_NAMES)."""
-    if not carried.is_cuda:
-        raise RuntimeError("articulated-pose_amd ops run on the MI355X only (no CPU fallback in the product path)")
-    kinds = {torch.float32: 1, torch.int16: 0}
-    if hasattr(torch, "uint16"):
-        kinds[torch.uint16] = 0
-    if obs_depth.dtype not in kinds or obs_depth.dim() != 1 or not obs_depth.is_contiguous():
-        raise ValueError("depth must be a contiguous 1-d uint16 or float32 tensor")
-    cap = int(obs_depth.shape[0])
-    if obs_labels.dtype != torch.uint8 or tuple(obs_labels.shape) != (cap,) or not obs_labels.is_contiguous():
-        raise ValueError("labels must be a contiguous (%d,) uint8 tensor" % cap)
-    if pred_depth.dtype != obs_depth.dtype or tuple(pred_depth.shape) != (2 * cap,) or pred_labels.dtype != torch.uint8 \
-            or tuple(pred_labels.shape) != (2 * cap,) or not (pred_depth.is_contiguous() and pred_labels.is_contiguous()):
-        raise ValueError("the predicted pair must be contiguous (depth (%d,) of the observed dtype, labels (%d,) uint8)" % (2 * cap, 2 * cap))
+    from ..depth import _byte_plane, _depth_plane, _pixel_pair
+    _lib.require_device(carried)
+    kind, cap = _depth_plane(obs_depth)
+    _byte_plane("labels", obs_labels, cap)
+    _pixel_pair("the predicted pair", "observed", pred_depth, pred_labels, obs_depth.dtype, 2 * cap)
     K = int(carried.shape[1]) if carried.dim() == 3 else 0
     B = _tables(None, scene, None, None, carried, geom, K)
     ld = int(carried.shape[2])
@@ -92,7 +83,7 @@ def reproject_compare(obs_depth, obs_labels, pred_depth, pred_labels, geom, scen
     if out.dtype != torch.float64 or tuple(out.shape) != (B, K, ld + REPROJECTION_WIDTH) or not out.is_contiguous():
         raise ValueError("out must be a contiguous (%d, %d, %d) float64 tensor" % (B, K, ld + REPROJECTION_WIDTH))
     _lib.require_cuda(obs_depth, obs_labels, pred_depth, pred_labels, geom, scene, out)
-    _lib.call("ancsh_reproject_compare_rec", B, K, kinds[obs_depth.dtype], _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap, _lib.ptr(pred_depth),
+    _lib.call("ancsh_reproject_compare_rec", B, K, kind, _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap, _lib.ptr(pred_depth),
               _lib.ptr(pred_labels), _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(carried), ld, _lib.ptr(out))
     return out
 
