@@ -175,6 +175,13 @@ SIGNATURES = {
     "ancsh_reproject_scene_build": [_c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _c_long, _vp, _vp, _vp],
     # nframes, K, depth_type, obs_depth, obs_labels, pixel_capacity, pred_depth, pred_labels, geom, scene, carried, ld, wide, stream
     "ancsh_reproject_compare_rec": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp],
+    # render-and-compare ICP of a pose record (no ABI bump, detected by their symbols): nframes, K, depth_type, verts, tris, tri_link, V, T,
+    # obs_depth, obs_labels, pixel_capacity, pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, pass, is_last,
+    # pose_in, ld_in, pose_out, best, sums, stream
+    "ancsh_refine_pass": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 8 + [_c_int, _c_int, _vp, _c_int,
+                          _vp, _vp, _vp, _vp],
+    # nframes, K, best, carried, ld, wide, stream
+    "ancsh_refine_rec": [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -1098,6 +1098,40 @@ def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record,
     return columns, [tuple(view[:2] for view in frame) for frame in zip(*views)]
 
 
+def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, refine, debug=False, device="cuda:0"):
+    """Eager render-and-compare ICP, the operator outside the pipeline: reprojection_frames' arguments and refine = pose.refinement.pack_refine's
+    table.  Every part's two poses are refined on the observed depth: iters + 1 times ancsh_reproject_scene_build on the working poses, the
+    renderer on 2 n frames and ancsh_refine_pass, then ancsh_refine_rec.  -> columns (n, K, 36) float64, pose.refinement.COLUMN_NAMES: per
+    pose [R (9) | s | t (3) | cost_start | cost_best | n_used | best_pass | passes_solved]; pose.refinement.refined_record of the record with
+    these columns behind it is the (n, K, 26) record of the refined poses.  debug=True: (columns, sums (iters + 1, n, K, 2, 32)), what every
+    pass added up.  A pipeline built with refine= streams the same bytes.  One host sync; the pipeline has none."""
+    from .dataset import check_rigs
+    from .pose.reprojection import predicted_buffers
+    from .pose.refinement import REFINE_WIDTH, check_refine_table, refine_batch, refine_buffers
+    table = check_refine_table(refine)
+    iters = int(table[0])
+    dev = _lib.cuda_device(device)
+    name = check_depth_dtype(depth_dtype)
+    rec = np.ascontiguousarray(record, np.float64)
+    if rec.ndim != 3 or rec.shape[2] < 26 or not 1 <= rec.shape[1] <= 8:
+        raise ValueError("record must be (n, K, >= 26) float64 with 1 <= K <= 8, got shape %s" % (rec.shape,))
+    n, K = rec.shape[:2]
+    depths, labels, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scenes, depth_dtype, K)
+    if len(depths) != n:
+        raise ValueError("record holds %d frames, frames %d" % (n, len(depths)))
+    d_mesh = mesh_to_device(mesh, dev)
+    tables, rigs = check_render_tables(render_tables, n, d_mesh.ninst), check_rigs(rigs, n, K)
+    geom, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, name, dev, NOT_OBJECT)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    pred = predicted_buffers(total, name, dev)
+    out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
+    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1)
+    wide = refine_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred, t(table), iters, buffers)
+    columns = wide[:, :, rec.shape[2]:].cpu().numpy()
+    assert columns.shape == (n, K, REFINE_WIDTH)
+    return (columns, buffers[2].cpu().numpy()) if debug else columns
+
+
 # ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred
 # on the projected object (ancsh_render_centre_crops) ---------------------------------------------------------------------------------------
 KIN_WIDTH, KIN_HEAD, KIN_LINK, POSE_WIDTH = 672, 32, 40, 32             # include/ancsh_hip.h, ANCSH_KIN_* and ANCSH_POSE_WIDTH

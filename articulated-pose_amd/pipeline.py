@@ -101,7 +101,7 @@ class _Slot(object):
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
         for inp in EVERY_INPUT:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
-        self.bounds = self.reproj_tables = self.reproj_pix = None
+        self.bounds = self.reproj_tables = self.reproj_pix = self.refine_bufs = None
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
 
@@ -164,12 +164,15 @@ class _Slot(object):
         if opts.build_gt_pose:                 # what ancsh_gt_pose_build writes behind the sampler and the two error launches read: slot-owned,
             self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
             self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
-        if opts.reprojection:                # the predicted frames' render tables and geometry rows (ancsh_reproject_scene_build) and the pixel
+        if opts.reprojection or opts.refine:  # the predicted frames' render tables and geometry rows (ancsh_reproject_scene_build) and the pixel
             from .depth import GEOM_WORDS, RENDER_WIDTH          # triple the renderer draws them into, two crops per frame: slot-owned, shared
             from .pose.reprojection import predicted_buffers     # with the range guard's f32 graph (the wide record is the graph's own)
             self.reproj_tables = (torch.zeros((2 * B, RENDER_WIDTH), dtype=torch.float64, device=device),
                                   torch.zeros((2 * B, GEOM_WORDS), dtype=torch.int32, device=device))
             self.reproj_pix = predicted_buffers(cap, depth, device)
+        if opts.refine:                      # the loop's two working records, its best block and one pass's sums: slot-owned, shared with the
+            from .pose.refinement import refine_buffers          # range guard's f32 graph like the tables and the pixel triple above
+            self.refine_bufs = refine_buffers(B, K, device)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -359,6 +362,12 @@ class AncshPipeline(object):
         read (with sensor=: the degraded one): out["record_reproj"], 15 columns (pose.reprojection.COLUMN_NAMES: observed pixels, then predicted
         pixels, overlap, IoU and the depth residual's mean |d|, RMS, max and mean per pose) behind whatever the record was.  Five launches more;
         the result tuple keeps its form.  A short batch's padding frames take pixels of their own, as with a sensor.
+    refine (with render_mesh, whatever else is built): pose.refinement.pack_refine's table, uploaded once: render-and-compare ICP at the step's
+        end, behind reprojection's three calls when both are on (they share the slot's predicted tables and pixel triple) -- iters + 1 times
+        ancsh_reproject_scene_build on the working poses, the renderer and ancsh_refine_pass, then ancsh_refine_rec: 5 (iters + 1) + 1 launches.
+        out["record_refined"]: 36 columns (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best, n_used,
+        best_pass, passes_solved) behind whatever the record was; pose.refinement.refined_record gives the (.., 26) record of the refined
+        poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the (B, K, 2, 32) sums besides.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
 
     ninst = None                                # a library's size (render_mesh=depth.pack_mesh_library(...)); None for a single object
@@ -368,7 +377,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None, reprojection=False):
+                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None, reprojection=False, refine=None):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -377,7 +386,8 @@ class AncshPipeline(object):
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
                                       label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor,
-                                      reprojection)
+                                      reprojection, refine)
+        self.refine = o.refine
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -399,6 +409,11 @@ class AncshPipeline(object):
         if o.sensor:                            # the sensor table (check_options has checked it): uploaded once and shared by all slots
             from .depth import check_sensor
             self.sensor_table = torch.from_numpy(check_sensor(sensor)).to(self.device)
+        self.refine_table, self.refine_iters = None, 0
+        if o.refine:                            # the refinement's parameters (check_options has checked them): uploaded once and shared by all slots
+            from .pose.refinement import check_refine_table
+            table = check_refine_table(refine)
+            self.refine_table, self.refine_iters = torch.from_numpy(table).to(self.device), int(table[0])
         # the networks; both layer by layer in grouped launches (paired.py; identical outputs); ANCSH_PAIRED=0: one forward after the other
         self.ancsh = Network(num_parts, weights_ancsh, "ancsh", device)
         self.npcs = Network(num_parts, weights_npcs, "npcs", device)
@@ -579,6 +594,12 @@ class AncshPipeline(object):
             out["record_reproj"] = reprojection_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom,
                                                       (sl.apix, sl.amask), out["record_point_gt"], self.depth_dtype, sl.reproj_tables,
                                                       sl.reproj_pix)
+        if self.refine:                  # the step's last 5 (iters + 1) + 1 launches: the record's poses refined on the pair the annotation read, in
+            # the predicted tables and pixel triple reprojection has finished with -> 36 columns behind the widest record so far
+            from .pose.refinement import refine_batch
+            out["record_refined"] = refine_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom, (sl.apix, sl.amask),
+                                                 out["record_reproj" if self.reprojection else "record_point_gt"], self.depth_dtype,
+                                                 sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:
@@ -845,7 +866,7 @@ class AncshPipeline(object):
         does with reprojection: a padding frame is fitted under its own key, and its predicted crop is not the first frame's."""
         from .depth import pack_crop_geometry
         n_valid = len(shapes)
-        pad = self.B - n_valid if self.opts.sensor or self.opts.reprojection else 0
+        pad = self.B - n_valid if self.opts.sensor or self.opts.reprojection or self.opts.refine else 0
         pack_crop_geometry(shapes + shapes[:1] * pad, list(origins) + [origins[0]] * pad, sl.np_geom)
         if not pad:
             sl.np_geom[n_valid:] = sl.np_geom[0]

@@ -1,0 +1,167 @@
+"""Render-and-compare ICP of a batch of pose records (ancsh_refine_pass, ancsh_refine_rec, csrc/refinement.hip): the loop that acts on what
+pose.reprojection only scores.  Each part's mesh is rendered at its working pose, the rendered surface is compared with the observed depth
+pixel by pixel (point-to-plane on same-pixel pairs, truncated at max_dist), one damped Gauss-Newton step moves R and t about the part's
+centre, and the result is the evaluated pose of lowest cost -- never worse than the fitted pose on its own measure.  s is carried: the NOCS
+scale is the network's, and one view constrains size only weakly.  Point-to-plane on same-pixel pairs does not see the silhouette, and a part
+that shows one or two flat faces leaves directions unobservable: the damping leaves those where the fit put them."""
+import numpy as np
+import torch
+
+from .. import _lib
+
+REFINE_WIDTH = 36               # include/ancsh_hip.h, ANCSH_REFINE_WIDTH: the columns behind the carried record row, 18 per pose
+REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH_REFINE_PARAMS, ANCSH_REFINE_MAX_ITERS
+BEST_WIDTH = REFINE_WIDTH // 2
+COL_BASELINE, COL_NONLINEAR = 0, BEST_WIDTH           # counted from the end of the carried row
+POSE_COLUMNS = tuple("R%d%d" % (a, k) for a in range(3) for k in range(3)) + ("s", "tx", "ty", "tz", "cost_start", "cost_best", "n_used",
+                                                                              "best_pass", "passes_solved")
+COLUMN_NAMES = tuple("baseline_" + c for c in POSE_COLUMNS) + tuple("nonlinear_" + c for c in POSE_COLUMNS)
+SUMS_COLUMNS = dict(A=slice(0, 21), b=slice(21, 27), rr=27, n_used=28, n_obs=29, cost=30, solved=31)
+BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, render_mesh=<depth.pack_mesh(...)>"
+
+
+def check_refine_table(table):
+    """-> table as a fresh (REFINE_PARAMS,) float64 array; ValueError unless it is one pack_refine makes."""
+    try:
+        t = np.array(table, np.float64)
+    except (TypeError, ValueError):
+        t = np.zeros(0)
+    if t.shape != (REFINE_PARAMS,):
+        raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), got shape %s" % (REFINE_PARAMS, t.shape))
+    iters, max_dist, min_cos, damping, max_angle, min_pixels = t[:6].tolist()
+    if not (iters == int(iters) if np.isfinite(iters) else False) or not 1 <= iters <= MAX_ITERS:
+        raise ValueError("refine: iters must be an integer in [1, %d], got %r" % (MAX_ITERS, iters))
+    if not (np.isfinite(max_dist) and max_dist > 0):
+        raise ValueError("refine: max_dist must be finite and > 0, got %r" % max_dist)
+    if not 0.0 <= min_cos <= 1.0:
+        raise ValueError("refine: min_cos is a cosine in [0, 1], got %r" % min_cos)
+    if not (np.isfinite(damping) and damping >= 0):
+        raise ValueError("refine: damping must be finite and >= 0, got %r" % damping)
+    if not 0.0 < max_angle <= np.pi / 2:
+        raise ValueError("refine: max_angle_deg must be in (0, 90], got %r" % np.degrees(max_angle))
+    if not (np.isfinite(min_pixels) and min_pixels == int(min_pixels) and min_pixels >= 1):
+        raise ValueError("refine: min_pixels must be an integer >= 1, got %r" % min_pixels)
+    if (t[6:] != 0).any():
+        raise ValueError("refine: the reserved values 6..7 must be 0")
+    return t
+
+
+def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32):
+    """The parameter table ancsh_refine_pass reads, (REFINE_PARAMS,) float64: iters Gauss-Newton passes (1..8; one more pass evaluates the
+    last pose); max_dist: a pixel pair further apart than this counts as missed, and a step's translation is clamped to it; min_cos: pixels
+    seen at a flatter angle are left out; damping: relative Levenberg damping of the diagonal; max_angle_deg: the clamp of a step's
+    rotation; min_pixels: fewer used pixels leave the pose as it is.  Lengths are in the scaled cloud's unit, where an object's diagonal is
+    about 1.  The defaults are starting values; nobody has tuned them.  ValueError: check_refine_table's."""
+    try:
+        head = [float(iters), float(max_dist), float(min_cos), float(damping), float(np.radians(float(max_angle_deg))), float(min_pixels)]
+    except (TypeError, ValueError):
+        raise ValueError("refine: iters, max_dist, min_cos, damping, max_angle_deg and min_pixels are numbers")
+    return check_refine_table(head + [0.0] * (REFINE_PARAMS - len(head)))
+
+
+def check_refine(refine, rendered):
+    """-> the checked table or None; ValueError (before anything touches the GPU) when it is asked of a pipeline that holds no mesh to render."""
+    if refine is None:
+        return None
+    if not rendered:
+        raise ValueError("refine=<pose.refinement.pack_refine(...)> re-renders the object's mesh at the working poses and compares it with the "
+                         "frame: it needs render_mesh=<depth.pack_mesh(...)> (" + BUILT_WITH + ")")
+    return check_refine_table(refine)
+
+
+def named_columns(record):
+    """The trailing 36 columns of a streamed record (..., >= 36) -> {name: (...) array}, by COLUMN_NAMES."""
+    if record.shape[-1] < REFINE_WIDTH:
+        raise ValueError("expected at least %d trailing columns, got %d" % (REFINE_WIDTH, record.shape[-1]))
+    tail = record[..., record.shape[-1] - REFINE_WIDTH:]
+    return {name: tail[..., k] for k, name in enumerate(COLUMN_NAMES)}
+
+
+def refined_record(record):
+    """A streamed record with the refinement's columns last (..., >= 26 + 36) -> (..., 26): the two refined poses in a pose record's own
+    columns, as depth.reprojection_frames, pose.gt_errors and the other operators on a record take them.  A copy."""
+    if record.shape[-1] < 26 + REFINE_WIDTH:
+        raise ValueError("expected a record of at least %d columns, got %d" % (26 + REFINE_WIDTH, record.shape[-1]))
+    tail = record[..., record.shape[-1] - REFINE_WIDTH:]
+    cat = np.concatenate if isinstance(record, np.ndarray) else (lambda parts, axis: torch.cat(parts, dim=axis))
+    return cat([tail[..., :13], tail[..., BEST_WIDTH:BEST_WIDTH + 13]], -1)
+
+
+def _f64(name, t, shape):
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s float64 tensor" % (name, tuple(shape)))
+
+
+def refine_buffers(B, K, device, passes=1):
+    """What a slot owns for the loop: (work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2, 32)), float64."""
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
+    return (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SUMS)
+
+
+def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, pose_out,
+                best, sums):
+    """ancsh_refine_pass on device tensors (no host sync, no allocation): mesh = depth.mesh_to_device's; the observed pair (pixel_capacity,);
+    pred = pose.reprojection.predicted_buffers' triple as the renderer left it for pred_render (2B, 208), the tables of pose_in (B, K, >= 26);
+    params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out."""
+    from ..depth import GEOM_WORDS, RENDER_WIDTH, SCENE_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
+    _lib.require_device(pose_in)
+    verts, tris, tri_link, V, T = _check_device_mesh(mesh)[:5]
+    kind, cap = _depth_plane(obs_depth)
+    _byte_plane("labels", obs_labels, cap)
+    _pixel_pair("the predicted pair", "observed", pred[0], pred[1], obs_depth.dtype, 2 * cap)
+    _scratch_size(pred[2], 2 * cap, torch.int64)
+    if pose_in.dtype != torch.float64 or pose_in.dim() != 3 or pose_in.shape[2] < 26 or not pose_in.is_contiguous():
+        raise ValueError("pose_in must be a contiguous (B, K, >= 26) float64 tensor")
+    B, K, ld = (int(v) for v in pose_in.shape)
+    _f64("scene", scene, (B, SCENE_WIDTH))
+    _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
+    _f64("params", params, (REFINE_PARAMS,))
+    _f64("pose_out", pose_out, (B, K, 26))
+    _f64("best", best, (B, K, 2, BEST_WIDTH))
+    _f64("sums", sums, (B, K, 2, REFINE_SUMS))
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or not geom.is_contiguous() or norm_factor.dtype != torch.float32 \
+            or tuple(norm_factor.shape) != (B,) or not norm_factor.is_contiguous():
+        raise ValueError("geom must be a contiguous (%d, %d) int32 tensor and norm_factor a contiguous (%d,) float32 tensor" % (B, GEOM_WORDS, B))
+    _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums)
+    _lib.call("ancsh_refine_pass", B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth),
+              _lib.ptr(obs_labels), cap, _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene),
+              _lib.ptr(pred_render), _lib.ptr(norm_factor), _lib.ptr(params), int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld,
+              _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(sums))
+    return pose_out
+
+
+def refine_rec(best, carried, out=None):
+    """ancsh_refine_rec on device tensors (no host sync): best (B, K, 2, 18) and the record so far (B, K, ld) float64 -> (B, K, ld + 36): the
+    carried row bit for bit and the 36 columns behind it (COLUMN_NAMES)."""
+    _lib.require_device(carried)
+    if carried.dtype != torch.float64 or carried.dim() != 3 or carried.shape[2] < 26 or not carried.is_contiguous():
+        raise ValueError("carried must be a contiguous (B, K, >= 26) float64 tensor")
+    B, K, ld = (int(v) for v in carried.shape)
+    _f64("best", best, (B, K, 2, BEST_WIDTH))
+    if out is None:
+        out = torch.empty((B, K, ld + REFINE_WIDTH), dtype=torch.float64, device=carried.device)
+    _f64("out", out, (B, K, ld + REFINE_WIDTH))
+    _lib.require_cuda(best, out)
+    _lib.call("ancsh_refine_rec", B, K, _lib.ptr(best), _lib.ptr(carried), ld, _lib.ptr(out))
+    return out
+
+
+def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers):
+    """The captured step's sequence, no host sync and no allocation beyond the output: iters + 1 times ancsh_reproject_scene_build on the
+    working poses, the renderer, ancsh_refine_pass; then ancsh_refine_rec -- 5 (iters + 1) + 1 launches.  tables and pred are
+    pose.reprojection's slot-owned pair and triple (shared with reprojection=True, whose three calls come first); params = pack_refine's
+    table on the device and iters its first value on the host; buffers = refine_buffers'.  sums of `passes` > 1 rows keeps every pass's sums
+    (pass p in row p); one row holds the last pass's.  -> (B, K, ld + 36) float64."""
+    from ..depth import render_depth
+    from .reprojection import reproject_scene_build
+    work, best, sums = buffers
+    cap = int(obs[0].shape[0])
+    src = carried
+    for p in range(iters + 1):
+        reproject_scene_build(render, scene, rig, norm_factor, src, geom, cap, out=tables)
+        render_depth(mesh, tables[1], tables[0], depth_dtype, out=pred[:2], scratch=pred[2])
+        dst = work[p % 2]
+        refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
+                    sums[p if sums.shape[0] > 1 else 0])
+        src = dst
+    return refine_rec(best, carried)

@@ -51,6 +51,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_render_centre_crops (crops centred on the projected object),
                                  *     ancsh_depth_sensor_model, ancsh_depth_sensor_model_keyed (a depth sensor's noise, holes and edge dropout on those crops),
                                  *     ancsh_reproject_scene_build, ancsh_reproject_compare_rec (render-and-compare of a pose record),
+                                 *     ancsh_refine_pass, ancsh_refine_rec (render-and-compare ICP: that record's poses refined on the depth frame),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1499,6 +1500,67 @@ int ancsh_reproject_scene_build(int nframes, int K, const double *render, const 
 int ancsh_reproject_compare_rec(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
                                 long pixel_capacity, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                                 const double *scene, const double *carried, int ld, double *wide, void *stream);
+
+/* Render-and-compare ICP: the poses of a record refined on the depth frame, two entries around ancsh_reproject_scene_build and the unchanged
+ * renderer (no new ABI number: callers detect them by their symbols).  Each (frame f, part j, pose v: 0 the baseline pose, 1 the nonlinear
+ * pose) is refined on its own.  A pose is [R (9) row-major | s | t (3)], part NOCS -> the scaled cloud, c = s R x + t; R and t are refined, s
+ * is carried.  The caller loops, pass = 0 .. iters:  ancsh_reproject_scene_build on the working poses, the renderer on the 2 * nframes
+ * predicted frames, ancsh_refine_pass (is_last = 1 on pass == iters, which only evaluates);  then ancsh_refine_rec once.
+ *
+ * ancsh_refine_pass: one Gauss-Newton pass, ONE launch.
+ *   verts, tris, tri_link, V, T : the mesh the renderer drew (a library: all of it; a z-buffer key names a global triangle);
+ *   obs_depth, obs_labels (pixel_capacity) : the pair the annotation read;  pred_zbuf, pred_depth, pred_labels (2 * pixel_capacity) : what the
+ *   renderer left for the working poses' tables, the z-buffer included: key = (bits of the float32 depth) << 32 | triangle;
+ *   geom, scene (nframes, ..) : the frame's own;  pred_render (2 * nframes, ANCSH_RENDER_WIDTH) : ancsh_reproject_scene_build's tables for
+ *   pose_in;  norm_factor (nframes) float32;  params : ONE table of ANCSH_REFINE_PARAMS = 8 float64 for the launch:
+ *     [0] iters (the caller's; not read)  [1] max_dist  [2] min_cos  [3] damping  [4] max_angle, radians  [5] min_pixels  [6..7] reserved, 0;
+ *   pose_in (nframes, K, ld_in) float64, ld_in >= 26 : columns 0..25 the two working poses (pass 0 reads the record itself);
+ *   pose_out (nframes, K, 26) : the updated poses, a buffer of its own;  best (nframes, K, 2, 18) : the running best block, written on pass 0
+ *   and read and written on later passes;  sums (nframes, K, 2, ANCSH_REFINE_SUMS = 32) : what this pass added up.
+ * Everything is float64, evaluated in exactly the written order (no contraction); dot(a, b) = (a0 b0 + a1 b1) + a2 b2, |a| = sqrt(dot(a, a)).
+ *   Space: the scaled cloud.  With nf = (double)norm_factor[f], a camera point (x', y', z) is the cloud point (nf x', nf (-y'), nf z).  Crop
+ *   pixel (i, jj), row = row0 + i, col = col0 + jj, u = (C00 col + C01 row) + C02, w = (C10 col + C11 row) + C12 (scene[7..12]):  a depth z
+ *   gives the camera point (z u, z w, z).  Observed point q: z = (double)d_obs * depth_scale (scene[6]);  predicted point p: z = (double) the
+ *   float32 in the key's upper half.  Normal n: the key's triangle t, its link l = tri_link[t] and that link's map M of pred_render; a vertex
+ *   (v0, v1, v2) -> m_a = ((M[a][0] v0 + M[a][1] v1) + M[a][2] v2) + M[a][3] -> the cloud as above;  e1 = B - A, e2 = C - A, n = e1 x e2
+ *   (n0 = e1_1 e2_2 - e1_2 e2_1, cyclic), n = n / |n|, negated when dot(n, q) > 0.  |n| == 0 or not finite, t >= T, a vertex index outside
+ *   [0, V) or a link outside [0, 16) skips the pixel.
+ *   A pixel is OBSERVED for part j by ancsh_reproject_compare_rec's rule, and USED when the predicted pixel is part j by the same rule and
+ *   |p - q| <= max_dist and |dot(n, q)| / |q| >= min_cos.  Centre c_a = s ((R[a][0] 0.5 + R[a][1] 0.5) + R[a][2] 0.5) + t_a.  Per used pixel r =
+ *   dot(n, p - q), pc = p - c, J = [pc x n | n];  A = sum J J^T (upper triangle, row-major: 21 values), b = sum J r, sum r^2, n_used, n_obs.
+ *   Order of addition: thread t of 256 adds pixels t, t + 256, ... of the crop in that order, a wave adds its lanes with xor shuffles of 32,
+ *   16, 8, 4, 2, 1, the four waves are added in wave order: no atomics, the same bytes every run.
+ *   sums row: [A (21) | b (6) | sum r^2 | n_used | n_obs | C | solved].  Cost C = (sum r^2 + (max_dist max_dist) (n_obs - n_used)) / n_obs, the
+ *   truncated quadratic over the observed pixels; NaN when n_obs == 0.
+ *   best row: [R (9) | s | t (3) | cost_start | cost_best | n_used at the best pose | best_pass | passes_solved].  Pass 0 writes pose_in and its
+ *   C; a later pass replaces pose, cost_best, n_used and best_pass when its C is strictly lower (a NaN never is).
+ *   The solve (skipped when is_last or n_used < min_pixels): A_kk = A_kk + (damping A_kk + 1e-12);  Cholesky A = L L^T row by row, s = A_ij,
+ *   s = s - L_ik L_jk for k = 0 .. j - 1, L_ii = sqrt(s), L_ij = s / L_jj;  L y = -b forwards (s = (0 - b_i), s = s - L_ik y_k, y_i = s /
+ *   L_ii), L^T xi = y backwards (k ascending from i + 1).  It FAILS when a pivot s is not > 0 or not finite, or a value of xi is not finite.
+ *   xi = (w, dt): when |w| > max_angle or |dt| > max_dist all six are multiplied by the smaller of max_angle / |w| and max_dist / |dt| (of
+ *   those that apply).  h = w / 2, qn = sqrt(((1 + h0 h0) + h1 h1) + h2 h2), the unit quaternion (1 / qn, h / qn) = (qw, x, y, z) and its
+ *   matrix dR = [1 - 2 (y y + z z), 2 (x y - qw z), 2 (x z + qw y); 2 (x y + qw z), 1 - 2 (x x + z z), 2 (y z - qw x); 2 (x z - qw y),
+ *   2 (y z + qw x), 1 - 2 (x x + y y)] -- sqrt and division only.  R'[a][k] = (dR[a][0] R[0][k] + dR[a][1] R[1][k]) + dR[a][2] R[2][k];
+ *   t'_a = (dot(dR[a], t - c) + c_a) + dt_a;  s' = s.  solved = 1 and passes_solved grows by one; otherwise solved = 0 and pose_out = pose_in.
+ *   NaN rules: a pose with a value that is not finite, or a norm factor that is 0 or not finite, has NaN in its 18 best values and its sums
+ *   (solved = 0), and passes through pose_out as it came.
+ *   One workgroup per (part, pose, frame); no host sync, no allocation: graph-capturable.  nframes == 0 launches nothing and returns 0.
+ *   Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8, depth_type, 0 <= pixel_capacity < 2^29, 0 <= T, V < 2^24, 0 <= pass <=
+ *   ANCSH_REFINE_MAX_ITERS, is_last in {0, 1}, ld_in >= 26, null pointers, the alignments, pose_in != pose_out.
+ *
+ * ancsh_refine_rec: best (nframes, K, 2, 18) and the record row so far, carried (nframes, K, ld), -> wide (nframes, K, ld +
+ *   ANCSH_REFINE_WIDTH): columns 0..ld-1 = carried bit for bit, then the baseline pose's best row and the nonlinear pose's.  ONE launch.
+ *   Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8, 26 <= ld <= 4096, null pointers, 8-byte alignments, carried != wide. */
+#define ANCSH_REFINE_WIDTH 36
+#define ANCSH_REFINE_SUMS 32
+#define ANCSH_REFINE_PARAMS 8
+#define ANCSH_REFINE_MAX_ITERS 8
+int ancsh_refine_pass(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                      const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity, const unsigned long long *pred_zbuf,
+                      const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
+                      const double *pred_render, const float *norm_factor, const double *params, int pass, int is_last,
+                      const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
+int ancsh_refine_rec(int nframes, int K, const double *best, const double *carried, int ld, double *wide, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

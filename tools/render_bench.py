@@ -18,7 +18,12 @@ identity table and with a noisy one (every term on), and two legs of the rendere
 and the option's three calls alone on one batch of 32 frames: ancsh_reproject_scene_build, the renderer on the 64 predicted frames, and
 ancsh_reproject_compare_rec, with the record the stream fitted for that batch.
 
-    python tools/render_bench.py [--sensor | --reprojection] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+--refine N measures render-and-compare ICP (refine=pack_refine(iters=N)) instead: two legs of the rendered stream, alternated like r and d:
+    r: the rendered stream without the option;   f: the rendered stream built with refine=;
+one ancsh_refine_pass alone on one batch of 32 frames whose record draws every part (the exact poses moved by 0.01), one whole loop of the
+device wrappers (pose.refinement.refine_batch) on it, and the eager operator depth.refine_frames from host arrays.
+
+    python tools/render_bench.py [--sensor | --reprojection | --refine N] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -201,10 +206,88 @@ def reprojection_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt,
                                 "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
 
 
+def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc, clean, cap):
+    """--refine N: the rendered stream with and without refine=pack_refine(iters=N), alternated; then one ancsh_refine_pass, one whole loop on
+    device tensors and the eager operator on the last batch, with a record that draws every part 0.01 off its place."""
+    from articulated_pose_amd.pose import refinement as F, reprojection as R
+    table = F.pack_refine(iters=args.refine)
+    wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
+    kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
+              depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
+    pipes = {"r": AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare(), "f": AncshPipeline(K, wa, wn, B, N, dev, refine=table, **kw).prepare()}
+    torch.cuda.synchronize()
+    last = {}
+
+    def leg(name, passes):
+        t0, n = time.perf_counter(), 0
+        for got in pipes[name].stream_render_batches(rbatches[k] for _ in range(passes) for k in range(len(rbatches))):
+            n += 1
+        torch.cuda.synchronize()
+        last[name] = got[2]
+        return 1e3 * (time.perf_counter() - t0) / n
+
+    for name in "rf":
+        leg(name, 1)
+    ms = {name: [] for name in "rf"}
+    for _ in range(args.rounds):
+        for name in "rf":
+            ms[name].append(leg(name, args.passes))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    W = last["r"].shape[2]
+    assert last["f"].shape[2] == W + F.REFINE_WIDTH and last["f"][:, :, :W].tobytes() == last["r"].tobytes()
+    # the record the calls are timed on: the pose that undoes the frame's scene map (reprojection_bench's), moved 0.01 along the view axis
+    moved = np.ascontiguousarray(last["r"][:, :, :26])
+    sc = rbatches[-1][2]["scene"]
+    for f in range(B):
+        for j in range(K):
+            M = np.vstack([sc[f, D.SCENE_HEAD + D.SCENE_LINK * j + 2:D.SCENE_HEAD + D.SCENE_LINK * (j + 1)].reshape(3, 4), [0, 0, 0, 1.0]])
+            pose = np.diag([1.0, -1.0, 1.0, 1.0]) @ np.linalg.inv(M)
+            moved[f, j, :13] = moved[f, j, 13:26] = np.concatenate([pose[:3, :3].reshape(9), [1.0], pose[:3, 3] + [0.0, 0.0, 0.01]])
+    carried = torch.from_numpy(moved).to(dev)
+    rigs, nf = rbatches[-1][2]["rig"], rbatches[-1][1]
+    d_rig, d_nf, d_par = torch.from_numpy(rigs).to(dev), torch.from_numpy(nf).to(dev), torch.from_numpy(table).to(dev)
+    tables = (torch.zeros((2 * B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * B, D.GEOM_WORDS), dtype=torch.int32, device=dev))
+    pred = R.predicted_buffers(cap, "uint16", dev)
+    bufs = F.refine_buffers(B, K, dev)
+    R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
+    D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
+    calls = {"refine_pass": lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, carried,
+                                                  bufs[0][0], bufs[1], bufs[2][0]),
+             "refine_rec": lambda: F.refine_rec(bufs[1], carried)}
+    op_ms = {name: timed_calls(call, args.rounds, args.calls) for name, call in calls.items()}
+    used = bufs[2][0][..., 28].cpu().numpy()
+    loop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_par, args.refine, bufs)
+    op_ms["whole_loop"] = timed_calls(loop, args.rounds, max(1, args.calls // 10))
+    cols = F.named_columns(loop().cpu().numpy())
+    frames = D._cut_frames(clean[0].cpu().numpy().view(np.uint16), clean[1].cpu().numpy(), d_geom.cpu().numpy(), "uint16")
+    eager = []
+    for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        D.refine_frames(mesh, rbatches[-1][2]["render"], sc, rigs, nf, moved, frames, "uint16", table, device=dev)
+        eager.append(1e3 * (time.perf_counter() - t0))
+    print(json.dumps({"metric": "render-and-compare ICP: ms per batch of the rendered stream without (r) and with (f) refine=pack_refine(iters=N); ms "
+                                "per call of ancsh_refine_pass, ancsh_refine_rec and the whole loop alone on one batch; ms of the eager operator",
+                      "device": torch.cuda.get_device_name(0), "iters": args.refine, "launches_added": 5 * (args.refine + 1) + 1,
+                      "ms_per_batch": {k: round(v, 4) for k, v in med.items()},
+                      "ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                      "stream_frames_per_s": {k: round(1e3 * B / v, 1) for k, v in med.items()}, "added_ms_per_batch": round(med["f"] - med["r"], 4),
+                      "f_over_r": round(med["f"] / med["r"], 4), "operator_ms_per_batch": {k: round(float(np.median(v)), 4) for k, v in op_ms.items()},
+                      "operator_ms_per_batch_rounds": {k: [round(x, 4) for x in v] for k, v in op_ms.items()},
+                      "eager_operator_ms": [round(x, 3) for x in eager],
+                      "operator_record": {"pixels_used_per_part_and_pose": float(used.mean()), "median_cost_start": float(np.median(cols["baseline_cost_start"])),
+                                          "median_cost_best": float(np.median(cols["baseline_cost_best"])),
+                                          "parts_improved": int((cols["baseline_cost_best"] < cols["baseline_cost_start"]).sum()), "parts": B * K},
+                      "streamed_last_batch": {"parts": B * K, "parts_with_a_finite_refined_pose": int(np.isfinite(F.named_columns(last["f"])["baseline_s"]).sum())},
+                      "crop_pixels_per_frame": args.side * args.side, "triangles": int(mesh[1].shape[0]),
+                      "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(rbatches) * B,
+                                "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sensor", action="store_true", help="measure the depth sensor model instead of the renderer")
     ap.add_argument("--reprojection", action="store_true", help="measure render-and-compare (reprojection=True) instead of the renderer")
+    ap.add_argument("--refine", type=int, default=0, metavar="N", help="measure render-and-compare ICP (refine=pack_refine(iters=N)) instead of the renderer")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
     ap.add_argument("--slots", type=int, default=8)
@@ -239,6 +322,9 @@ def main():
     if args.reprojection:
         D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
         return reprojection_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, torch.from_numpy(sc).to(dev), out, cap)
+    if args.refine:
+        D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf)
+        return refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, torch.from_numpy(sc).to(dev), out, cap)
     op_ms = timed_calls(lambda: D.render_depth(d_mesh, d_geom, d_rt, "uint16", out=out, scratch=zbuf), args.rounds, args.calls)
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
