@@ -182,6 +182,11 @@ SIGNATURES = {
                           _vp, _vp, _vp, _vp],
     # nframes, K, best, carried, ld, wide, stream
     "ancsh_refine_rec": [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp],
+    # the silhouette term (no ABI bump, detected by their symbols): nframes, K, depth_type, obs_depth, obs_labels, pixel_capacity, geom, scene,
+    # field, stream;  ancsh_refine_pass's arguments with field behind params
+    "ancsh_silhouette_field": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
+    "ancsh_refine_pass_sil": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 9 + [_c_int, _c_int, _vp, _c_int,
+                              _vp, _vp, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -8,6 +8,9 @@
 //       its lanes with the fixed xor-shuffle tree, the four waves are added in wave order through LDS: no atomics, the same bytes every run.
 //       Thread 0 computes the truncated cost, keeps the best pose so far, solves the 6 x 6 system by Cholesky and writes the updated pose.
 //   ancsh_refine_rec  : ONE launch, the carried record row bit for bit and the 36 columns of the two best blocks behind it.
+// The silhouette term, two more entries: ancsh_silhouette_field (ONE launch in front of the loop: per crop pixel and part the offset to the
+// nearest pixel observed for the part) and ancsh_refine_pass_sil (the pass kernel's SIL instance: a predicted pixel of the part where the
+// camera saw neither the part nor anything nearer adds one row that pulls it towards that nearest observed pixel, and is charged in the cost).
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
 #include "depth_annotate_common.h"
 
@@ -16,6 +19,8 @@ namespace ancsh {
 constexpr int RF_LINKS = ANCSH_SCENE_MAX_LINKS, RF_THREADS = 256, RF_WAVES = RF_THREADS / 64, RF_WIDTH = ANCSH_REFINE_WIDTH;
 constexpr int RF_RENDER = ANCSH_RENDER_WIDTH, RF_BEST = ANCSH_REFINE_WIDTH / 2, RF_SUMS = ANCSH_REFINE_SUMS;
 constexpr int RF_ACC = 30;                                              // A (21) | b (6) | sum r^2 | n_used | n_obs: what the block adds up
+constexpr int RF_SIL_ACC = 33, RF_SIL_SUMS = ANCSH_REFINE_SIL_SUMS;     // ... | sum m^2 | n_sil | n_far: with the silhouette term
+constexpr int SF_THREADS = 256, SF_BAND = 16, SF_CHUNK = 256, SF_SPLIT = 8, SF_STEP = 8, SF_ILP = 8, SF_NONE = 0x7fffffff, SF_SENTINEL = -32768;
 
 __device__ __forceinline__ bool rf_finite(double v) { return fabs(v) < __builtin_inf(); }      // NaN fails the comparison
 
@@ -116,7 +121,9 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
     return true;
 }
 
-template <typename T>
+// SIL: ancsh_refine_pass_sil -- the overhang pixels add their rows (field: ancsh_silhouette_field's words), params holds 16 values and a sums
+// row 36; without it the kernel is ancsh_refine_pass, instruction for instruction what it was before the term existed
+template <typename T, bool SIL>
 __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, int K, const float *__restrict__ verts, const int *__restrict__ tris,
                                                                  const int *__restrict__ tri_link, int V, int ntri,
                                                                  const T *__restrict__ obs_depth, const unsigned char *__restrict__ obs_labels,
@@ -124,21 +131,22 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                                                                  const T *__restrict__ pred_depth, const unsigned char *__restrict__ pred_labels,
                                                                  const int *__restrict__ geom, const double *__restrict__ scene,
                                                                  const double *__restrict__ pred_render, const float *__restrict__ norm_factor,
-                                                                 const double *__restrict__ params, int pass, int is_last,
-                                                                 const double *__restrict__ pose_in, int ld_in, double *__restrict__ pose_out,
+                                                                 const double *__restrict__ params, const int *__restrict__ field,
+                                                                 int pass, int is_last, const double *__restrict__ pose_in, int ld_in, double *__restrict__ pose_out,
                                                                  double *__restrict__ best, double *__restrict__ sums) {
+    constexpr int NACC = SIL ? RF_SIL_ACC : RF_ACC, NSUMS = SIL ? RF_SIL_SUMS : RF_SUMS;
     __shared__ int s_part[RF_LINKS];
-    __shared__ double s_red[RF_WAVES][RF_ACC], s_tot[RF_ACC];
+    __shared__ double s_red[RF_WAVES][NACC], s_tot[NACC];
     const int j = blockIdx.x, v = blockIdx.y, f = blockIdx.z, tid = threadIdx.x;
     const double *sc = scene + (size_t)f * AN_SCENE;
     const double *pose = pose_in + ((size_t)f * K + j) * ld_in + 13 * v;
     double *po = pose_out + ((size_t)f * K + j) * 26 + 13 * v;
-    double *bb = best + (((size_t)f * K + j) * 2 + v) * RF_BEST, *ss = sums + (((size_t)f * K + j) * 2 + v) * RF_SUMS;
+    double *bb = best + (((size_t)f * K + j) * 2 + v) * RF_BEST, *ss = sums + (((size_t)f * K + j) * 2 + v) * NSUMS;
     const double nf = (double)norm_factor[f], qnan = __builtin_nan("");
     if (!rf_pose_ok(pose) || !rf_finite(nf) || nf == 0.0) {             // uniform over the block: NaN in the best block, the pose as it came
         if (tid < 13) po[tid] = pose[tid];
         if (tid < RF_BEST) bb[tid] = qnan;
-        if (tid < RF_SUMS) ss[tid] = tid == RF_SUMS - 1 ? 0.0 : qnan;
+        if (tid < NSUMS) ss[tid] = tid == RF_SUMS - 1 || tid == RF_SIL_SUMS - 1 ? 0.0 : qnan;
         return;
     }
     if (tid < RF_LINKS) {
@@ -160,14 +168,53 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     const unsigned long long *pz = pred_zbuf + (size_t)v * pixel_capacity;
     const double *rt = pred_render + ((size_t)v * nframes + f) * RF_RENDER;
     const double scale = sc[6];
-    double acc[RF_ACC];
+    double acc[NACC];
 #pragma unroll
-    for (int k = 0; k < RF_ACC; ++k) acc[k] = 0.0;
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
     for (long a = start + tid; a < start + n; a += RF_THREADS) {
         const T od = obs_depth[a], qd = pd[a];
         const unsigned long long key = pz[a];
-        const bool o = rf_pixel_part(od, obs_labels[a], s_part) == j, p = rf_pixel_part(qd, pl[a], s_part) == j;
+        const int op = rf_pixel_part(od, obs_labels[a], s_part);
+        const bool o = op == j, p = rf_pixel_part(qd, pl[a], s_part) == j;
         acc[29] += o ? 1.0 : 0.0;
+        if constexpr (SIL) {
+            if (p && !o) {                                              // an OVERHANG pixel, unless another part hides the prediction here
+                const double zp = (double)__uint_as_float((unsigned)(key >> 32));
+                if (op >= 0 && !((double)od * scale > zp)) continue;
+                const int fw = field[(size_t)j * pixel_capacity + a], di = (short)(fw & 0xffff), dj = (short)((unsigned)fw >> 16);
+                if (di == SF_SENTINEL) continue;
+                if ((double)(di * di + dj * dj) <= params[10] * params[10]) continue;
+                const long e = a - start;
+                const int ri = row0 + (int)(e / w), ci = col0 + (int)(e % w);
+                const double row = (double)ri, col = (double)ci, row2 = (double)(ri + di), col2 = (double)(ci + dj);
+                const double su = (sc[7] * col + sc[8] * row) + sc[9], sv = (sc[10] * col + sc[11] * row) + sc[12];
+                const double su2 = (sc[7] * col2 + sc[8] * row2) + sc[9], sv2 = (sc[10] * col2 + sc[11] * row2) + sc[12];
+                double pp[3], p2[3];
+                rf_cloud(zp * su, zp * sv, zp, nf, pp);
+                rf_cloud(zp * su2, zp * sv2, zp, nf, p2);
+                const double dv[3] = {pp[0] - p2[0], pp[1] - p2[1], pp[2] - p2[2]};
+                const double m = sqrt(rf_dot(dv, dv));
+                if (!(m > 0.0)) continue;
+                if (m > params[9]) {                                    // FAR: no row, charged dist^2
+                    acc[32] += 1.0;
+                    continue;
+                }
+                const double wt = params[8], g[3] = {dv[0] / m, dv[1] / m, dv[2] / m}, r = wt * m;
+                const double pc[3] = {pp[0] - c[0], pp[1] - c[1], pp[2] - c[2]};
+                const double J[6] = {wt * (pc[1] * g[2] - pc[2] * g[1]), wt * (pc[2] * g[0] - pc[0] * g[2]), wt * (pc[0] * g[1] - pc[1] * g[0]),
+                                     wt * g[0], wt * g[1], wt * g[2]};
+                int at = 0;
+#pragma unroll
+                for (int x = 0; x < 6; ++x)
+#pragma unroll
+                    for (int y = x; y < 6; ++y) acc[at++] += J[x] * J[y];
+#pragma unroll
+                for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+                acc[30] += m * m;
+                acc[31] += 1.0;
+                continue;
+            }
+        }
         if (!(o && p)) continue;
         const unsigned t = (unsigned)key;
         if (t >= (unsigned)ntri) continue;                              // a predicted pixel has a winner; a key that names none is skipped
@@ -221,19 +268,25 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
         acc[28] += 1.0;
     }
 #pragma unroll
-    for (int k = 0; k < RF_ACC; ++k) {                                  // a fixed tree: xor shuffles, then the waves in order
+    for (int k = 0; k < NACC; ++k) {                                    // a fixed tree: xor shuffles, then the waves in order
         double s = acc[k];
 #pragma unroll
         for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
         if ((tid & 63) == 0) s_red[tid >> 6][k] = s;
     }
     __syncthreads();
-    if (tid < RF_ACC) s_tot[tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    if (tid < NACC) s_tot[tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
     __syncthreads();
-    if (tid < RF_ACC) ss[tid] = s_tot[tid];
+    if (tid < NACC) ss[tid < RF_ACC ? tid : tid + 2] = s_tot[tid];     // sum m^2, n_sil, n_far lie behind C and solved
     if (tid != 0) return;
     const double n_used = s_tot[28], n_obs = s_tot[29];
-    const double C = (s_tot[27] + (max_dist * max_dist) * (n_obs - n_used)) / n_obs;      // n_obs = 0: 0 / 0 = NaN
+    double C, n_rows = n_used;
+    if constexpr (SIL) {
+        C = ((s_tot[27] + (max_dist * max_dist) * (n_obs - n_used)) + (params[8] * params[8]) * (s_tot[30] + (params[9] * params[9]) * s_tot[32])) / n_obs;
+        n_rows = n_used + s_tot[31];
+        ss[RF_SIL_SUMS - 1] = 0.0;
+    } else
+        C = (s_tot[27] + (max_dist * max_dist) * (n_obs - n_used)) / n_obs;               // n_obs = 0: 0 / 0 = NaN
     ss[30] = C;
     double solved = pass == 0 ? 0.0 : bb[17];
     if (pass == 0 || C < bb[14]) {                                      // strictly lower: ties stay with the earlier pass; NaN never wins
@@ -246,7 +299,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     }
     double nw[13];
     bool ok = false;
-    if (!is_last && n_used >= params[5]) ok = rf_solve_update(s_tot, pose, c, params[3], params[4], max_dist, nw);
+    if (!is_last && n_rows >= params[5]) ok = rf_solve_update(s_tot, pose, c, params[3], params[4], max_dist, nw);
     ss[31] = ok ? 1.0 : 0.0;
     bb[17] = ok ? solved + 1.0 : solved;
 #pragma unroll
@@ -262,48 +315,221 @@ __global__ __launch_bounds__(RF_THREADS) void refine_rec_kernel(long rows, const
     wide[e] = k < ld ? carried[r * ld + k] : best[r * RF_WIDTH + (k - ld)];     // the carried row bit for bit, the two best blocks behind it
 }
 
+// ancsh_silhouette_field: per crop pixel and part the offset (di, dj) to the nearest pixel OBSERVED for the part, ordered by (squared pixel
+// distance, row, column), all in integers.  Separable: g(i, c) = the nearest observed row of column c from row i (ties: the upper row), then
+// the minimum over the columns of (jj - c)^2 + g^2.  One workgroup per (part, row-band worker, frame): worker y takes the bands y, y +
+// SF_SPLIT, ... of SF_BAND rows; per band and per chunk of SF_CHUNK columns one thread per column walks its column (up from the band to the
+// first observed row above, through the band, down to the first below) and leaves g in LDS; then a thread takes SF_ILP pixels of one row
+// at a time and scans the chunk's columns in ascending order, one LDS read of g for all of them, an empty column skipped.  A pixel's
+// running best of a further chunk is read back from its own output word (the same thread wrote it).  No atomics; every word of a crop is
+// written exactly once per chunk by one thread, nothing outside the crops is touched.
+template <typename T>
+__global__ __launch_bounds__(SF_THREADS) void silhouette_field_kernel(int K, const T *__restrict__ obs_depth, const unsigned char *__restrict__ obs_labels,
+                                                                      long pixel_capacity, const int *__restrict__ geom,
+                                                                      const double *__restrict__ scene, int *__restrict__ field) {
+    __shared__ int s_part[RF_LINKS];
+    __shared__ int s_g[SF_BAND][SF_CHUNK];
+    const int j = blockIdx.x, f = blockIdx.z, tid = threadIdx.x;
+    const double *sc = scene + (size_t)f * AN_SCENE;
+    if (tid < RF_LINKS) {
+        const int nl = scene_nlinks(sc);
+        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
+        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
+    }
+    __syncthreads();
+    long start;
+    int w;
+    const long n = depth_crop(geom, f, pixel_capacity, start, w);       // [start, start + n) lies inside [0, pixel_capacity); 0: no crop
+    if (n == 0) return;
+    const int h = (int)(n / w);
+    int *out = field + (size_t)j * pixel_capacity;                      // part j's plane; written at [start, start + n) only
+    const bool wide = h > 32767 || w > 32767;                           // an offset would not fit its 16 bits: the sentinel everywhere
+    const int none = (int)(((unsigned)SF_SENTINEL & 0xffffu) | ((unsigned)SF_SENTINEL << 16));
+    auto seen = [&](int r, int c) {
+        const long a = start + (long)r * w + c;                         // rf_pixel_part's rule, the label first: most pixels need no depth
+        const unsigned char lab = obs_labels[a];
+        return lab < RF_LINKS && s_part[lab] == j && depth_ok(obs_depth[a]);
+    };
+    for (int i0 = (int)blockIdx.y * SF_BAND; i0 < h; i0 += SF_BAND * SF_SPLIT) {
+        const int nb = h - i0 < SF_BAND ? h - i0 : SF_BAND;
+        if (wide) {
+            for (long e = tid; e < (long)nb * w; e += SF_THREADS) out[start + (long)i0 * w + e] = none;
+            continue;
+        }
+        for (int c0 = 0; c0 < w; c0 += SF_CHUNK) {
+            const int nc = w - c0 < SF_CHUNK ? w - c0 : SF_CHUNK;
+            __syncthreads();                                            // the last chunk's readers are done with s_g
+            if (tid < nc) {
+                const int c = c0 + tid;
+                int last = -1, next = -1;
+                for (int r1 = i0; r1 > 0 && last < 0; r1 -= SF_STEP) {  // SF_STEP rows at a time, their loads in flight together, until one is seen
+                    bool s[SF_STEP];
+#pragma unroll
+                    for (int u = 0; u < SF_STEP; ++u) s[u] = r1 - 1 - u >= 0 && seen(r1 - 1 - u, c);
+#pragma unroll
+                    for (int u = SF_STEP - 1; u >= 0; --u)
+                        if (s[u]) last = r1 - 1 - u;                    // the nearest one is assigned last
+                }
+                bool in[SF_BAND];
+#pragma unroll
+                for (int k = 0; k < SF_BAND; ++k) in[k] = k < nb && seen(i0 + k, c);
+#pragma unroll
+                for (int k = 0; k < SF_BAND; ++k) {
+                    if (in[k]) last = i0 + k;
+                    if (k < nb) s_g[k][tid] = last;                     // the nearest observed row at or above, or -1
+                }
+                for (int r1 = i0 + nb; r1 < h && next < 0; r1 += SF_STEP) {
+                    bool s[SF_STEP];
+#pragma unroll
+                    for (int u = 0; u < SF_STEP; ++u) s[u] = r1 + u < h && seen(r1 + u, c);
+#pragma unroll
+                    for (int u = SF_STEP - 1; u >= 0; --u)
+                        if (s[u]) next = r1 + u;
+                }
+                for (int k = nb - 1; k >= 0; --k) {
+                    const int r = i0 + k, up = s_g[k][tid];
+                    if (up == r) next = r;
+                    int g = SF_NONE;
+                    if (up >= 0 && next >= 0) g = r - up <= next - r ? up - r : next - r;      // equal distances: the upper row
+                    else if (up >= 0) g = up - r;
+                    else if (next >= 0) g = next - r;
+                    s_g[k][tid] = g;
+                }
+            }
+            __syncthreads();
+            // one work item = SF_ILP pixels of ONE row, columns x, x + groups, ...: a column's g is read once for all of them, an empty
+            // column costs one comparison, and neighbouring lanes write neighbouring words
+            const int groups = (w + SF_ILP - 1) / SF_ILP;
+            for (int q = tid; q < nb * groups; q += SF_THREADS) {       // nb * groups <= 16 * 4096
+                const int k = q / groups, x = q - k * groups;
+                const long a0 = start + (long)(i0 + k) * w;
+                int bdi[SF_ILP], bdj[SF_ILP];
+                unsigned bd2[SF_ILP];
+#pragma unroll
+                for (int u = 0; u < SF_ILP; ++u) {
+                    const int jj = x + u * groups;
+                    bdi[u] = bdj[u] = SF_SENTINEL;
+                    bd2[u] = 0xffffffffu;                               // above every real distance: 2 * 32767^2 < 2^31
+                    if (c0 > 0 && jj < w) {
+                        const int fw = out[a0 + jj];
+                        bdi[u] = (short)(fw & 0xffff);
+                        bdj[u] = (short)((unsigned)fw >> 16);
+                        if (bdi[u] != SF_SENTINEL) bd2[u] = (unsigned)(bdi[u] * bdi[u]) + (unsigned)(bdj[u] * bdj[u]);
+                    }
+                }
+                for (int t = 0; t < nc; ++t) {
+                    const int g = s_g[k][t];
+                    if (g == SF_NONE) continue;
+                    const unsigned gg = (unsigned)__mul24(g, g);        // |g|, |dj| <= 32767: the 24-bit multiply is exact
+#pragma unroll
+                    for (int u = 0; u < SF_ILP; ++u) {
+                        const int dj = c0 + t - (x + u * groups);       // a column past the crop's width is computed and never written
+                        const unsigned d2 = gg + (unsigned)__mul24(dj, dj);
+                        if (d2 < bd2[u] || (d2 == bd2[u] && g < bdi[u])) {      // equal rows: the earlier (lower) column stays
+                            bd2[u] = d2;
+                            bdi[u] = g;
+                            bdj[u] = dj;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < SF_ILP; ++u)
+                    if (x + u * groups < w) out[a0 + x + u * groups] = (int)(((unsigned)bdi[u] & 0xffffu) | ((unsigned)bdj[u] << 16));
+            }
+        }
+    }
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
+
+// both passes' checks and launch: who = the entry's name in its messages; SIL = with the field, the 16-value table and the 36-value sums
+template <bool SIL>
+static int refine_pass_call(const char *who, int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V,
+                            int T, const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
+                            const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
+                            const double *scene, const double *pred_render, const float *norm_factor, const double *params, const int *field,
+                            int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
+    ANCSH_REQUIRE(nframes >= 0, "%s: bad shape nframes=%d", who, nframes);
+    ANCSH_REQUIRE(nframes <= 32767, "%s: %d frames exceed the 32767-frame range of ancsh_reproject_scene_build; split the batch", who, nframes);
+    ANCSH_REQUIRE(K >= 1 && K <= 8, "%s: K=%d must be in [1, 8]", who, K);
+    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
+                  "%s: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", who, depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "%s: pixel_capacity=%ld pixels out of range", who, pixel_capacity);
+    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "%s: T=%d triangles must be in [0, 2^24)", who, T);
+    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "%s: V=%d vertices must be in [0, 2^24)", who, V);
+    ANCSH_REQUIRE(pass >= 0 && pass <= ANCSH_REFINE_MAX_ITERS, "%s: pass=%d must be in [0, %d]", who, pass, ANCSH_REFINE_MAX_ITERS);
+    ANCSH_REQUIRE(is_last == 0 || is_last == 1, "%s: is_last=%d must be 0 or 1", who, is_last);
+    ANCSH_REQUIRE(ld_in >= 26, "%s: ld_in=%d, a record row holds at least the 26 pose columns", who, ld_in);
+    ANCSH_REQUIRE(verts && tris && tri_link && obs_depth && obs_labels && pred_zbuf && pred_depth && pred_labels && geom && scene &&
+                      pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || !SIL),
+                  "%s: null pointer", who);
+    const size_t item = depth_type == ANCSH_DEPTH_U16 ? 2 : 4;
+    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)pred_depth & (item - 1)) == 0 && ((size_t)verts & 3) == 0 &&
+                      ((size_t)tris & 3) == 0 && ((size_t)tri_link & 3) == 0 && ((size_t)geom & 3) == 0 && ((size_t)norm_factor & 3) == 0 &&
+                      ((size_t)pred_zbuf & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)pred_render & 7) == 0 && ((size_t)params & 7) == 0 &&
+                      ((size_t)pose_in & 7) == 0 && ((size_t)pose_out & 7) == 0 && ((size_t)best & 7) == 0 && ((size_t)sums & 7) == 0 &&
+                      ((size_t)field & 3) == 0,
+                  "%s: the depth buffers must be aligned to their element, verts, tris, tri_link, geom and norm_factor%s 4-byte, "
+                  "pred_zbuf, scene, pred_render, params, pose_in, pose_out, best and sums 8-byte aligned", who, SIL ? " and field" : "");
+    ANCSH_REQUIRE(pose_in != pose_out, "%s: pose_in and pose_out overlap (a workgroup reads its pose while another writes: two buffers)", who);
+    if (nframes == 0) return ANCSH_OK;
+    const dim3 grid(K, 2, nframes);
+    if (depth_type == ANCSH_DEPTH_U16)
+        hipLaunchKernelGGL((refine_pass_kernel<unsigned short, SIL>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris,
+                           tri_link, V, T, (const unsigned short *)obs_depth, obs_labels, pixel_capacity, pred_zbuf,
+                           (const unsigned short *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, pass, is_last,
+                           pose_in, ld_in, pose_out, best, sums);
+    else
+        hipLaunchKernelGGL((refine_pass_kernel<float, SIL>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris, tri_link, V,
+                           T, (const float *)obs_depth, obs_labels, pixel_capacity, pred_zbuf, (const float *)pred_depth, pred_labels, geom,
+                           scene, pred_render, norm_factor, params, field, pass, is_last, pose_in, ld_in, pose_out, best, sums);
+    return check_launch(who);
+}
 
 extern "C" int ancsh_refine_pass(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
                                  const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
                                  const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                                  const double *scene, const double *pred_render, const float *norm_factor, const double *params, int pass,
                                  int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "refine_pass: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "refine_pass: %d frames exceed the 32767-frame range of ancsh_reproject_scene_build; split the batch", nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "refine_pass: K=%d must be in [1, 8]", K);
+    return refine_pass_call<false>("refine_pass", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                                   pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, nullptr, pass, is_last,
+                                   pose_in, ld_in, pose_out, best, sums, stream);
+}
+
+extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                     const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
+                                     const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels,
+                                     const int *geom, const double *scene, const double *pred_render, const float *norm_factor,
+                                     const double *params, const int *field, int pass, int is_last, const double *pose_in, int ld_in,
+                                     double *pose_out, double *best, double *sums, void *stream) {
+    return refine_pass_call<true>("refine_pass_sil", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                                  pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, pass, is_last,
+                                  pose_in, ld_in, pose_out, best, sums, stream);
+}
+
+extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
+                                      long pixel_capacity, const int *geom, const double *scene, int *field, void *stream) {
+    ANCSH_REQUIRE(nframes >= 0, "silhouette_field: bad shape nframes=%d", nframes);
+    ANCSH_REQUIRE(nframes <= 32767, "silhouette_field: %d frames exceed the 32767-frame range of ancsh_refine_pass_sil; split the batch", nframes);
+    ANCSH_REQUIRE(K >= 1 && K <= 8, "silhouette_field: K=%d must be in [1, 8]", K);
     ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
-                  "refine_pass: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "refine_pass: pixel_capacity=%ld pixels out of range", pixel_capacity);
-    ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "refine_pass: T=%d triangles must be in [0, 2^24)", T);
-    ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "refine_pass: V=%d vertices must be in [0, 2^24)", V);
-    ANCSH_REQUIRE(pass >= 0 && pass <= ANCSH_REFINE_MAX_ITERS, "refine_pass: pass=%d must be in [0, %d]", pass, ANCSH_REFINE_MAX_ITERS);
-    ANCSH_REQUIRE(is_last == 0 || is_last == 1, "refine_pass: is_last=%d must be 0 or 1", is_last);
-    ANCSH_REQUIRE(ld_in >= 26, "refine_pass: ld_in=%d, a record row holds at least the 26 pose columns", ld_in);
-    ANCSH_REQUIRE(verts && tris && tri_link && obs_depth && obs_labels && pred_zbuf && pred_depth && pred_labels && geom && scene &&
-                      pred_render && norm_factor && params && pose_in && pose_out && best && sums,
-                  "refine_pass: null pointer");
+                  "silhouette_field: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
+    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "silhouette_field: pixel_capacity=%ld pixels out of range", pixel_capacity);
+    ANCSH_REQUIRE(obs_depth && obs_labels && geom && scene && field, "silhouette_field: null pointer");
     const size_t item = depth_type == ANCSH_DEPTH_U16 ? 2 : 4;
-    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)pred_depth & (item - 1)) == 0 && ((size_t)verts & 3) == 0 &&
-                      ((size_t)tris & 3) == 0 && ((size_t)tri_link & 3) == 0 && ((size_t)geom & 3) == 0 && ((size_t)norm_factor & 3) == 0 &&
-                      ((size_t)pred_zbuf & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)pred_render & 7) == 0 && ((size_t)params & 7) == 0 &&
-                      ((size_t)pose_in & 7) == 0 && ((size_t)pose_out & 7) == 0 && ((size_t)best & 7) == 0 && ((size_t)sums & 7) == 0,
-                  "refine_pass: the depth buffers must be aligned to their element, verts, tris, tri_link, geom and norm_factor 4-byte, "
-                  "pred_zbuf, scene, pred_render, params, pose_in, pose_out, best and sums 8-byte aligned");
-    ANCSH_REQUIRE(pose_in != pose_out, "refine_pass: pose_in and pose_out overlap (a workgroup reads its pose while another writes: two buffers)");
+    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)geom & 3) == 0 && ((size_t)field & 3) == 0 && ((size_t)scene & 7) == 0,
+                  "silhouette_field: obs_depth must be aligned to its element, geom and field 4-byte, scene 8-byte aligned");
     if (nframes == 0) return ANCSH_OK;
-    const dim3 grid(K, 2, nframes);
+    const dim3 grid(K, SF_SPLIT, nframes);
     if (depth_type == ANCSH_DEPTH_U16)
-        hipLaunchKernelGGL(refine_pass_kernel<unsigned short>, grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris, tri_link,
-                           V, T, (const unsigned short *)obs_depth, obs_labels, pixel_capacity, pred_zbuf, (const unsigned short *)pred_depth,
-                           pred_labels, geom, scene, pred_render, norm_factor, params, pass, is_last, pose_in, ld_in, pose_out, best, sums);
+        hipLaunchKernelGGL(silhouette_field_kernel<unsigned short>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, K,
+                           (const unsigned short *)obs_depth, obs_labels, pixel_capacity, geom, scene, field);
     else
-        hipLaunchKernelGGL(refine_pass_kernel<float>, grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris, tri_link, V, T,
-                           (const float *)obs_depth, obs_labels, pixel_capacity, pred_zbuf, (const float *)pred_depth, pred_labels, geom, scene,
-                           pred_render, norm_factor, params, pass, is_last, pose_in, ld_in, pose_out, best, sums);
-    return check_launch("refine_pass");
+        hipLaunchKernelGGL(silhouette_field_kernel<float>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, K, (const float *)obs_depth, obs_labels,
+                           pixel_capacity, geom, scene, field);
+    return check_launch("silhouette_field");
 }
 
 extern "C" int ancsh_refine_rec(int nframes, int K, const double *best, const double *carried, int ld, double *wide, void *stream) {

@@ -1104,10 +1104,12 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
     renderer on 2 n frames and ancsh_refine_pass, then ancsh_refine_rec.  -> columns (n, K, 36) float64, pose.refinement.COLUMN_NAMES: per
     pose [R (9) | s | t (3) | cost_start | cost_best | n_used | best_pass | passes_solved]; pose.refinement.refined_record of the record with
     these columns behind it is the (n, K, 26) record of the refined poses.  debug=True: (columns, sums (iters + 1, n, K, 2, 32)), what every
-    pass added up.  A pipeline built with refine= streams the same bytes.  One host sync; the pipeline has none."""
+    pass added up.  A table of pack_refine(silhouette=...) runs the loop with the silhouette term (ancsh_silhouette_field once, then
+    ancsh_refine_pass_sil): the debug sums are then (iters + 1, n, K, 2, 36).  A pipeline built with refine= streams the same bytes.  One
+    host sync; the pipeline has none."""
     from .dataset import check_rigs
     from .pose.reprojection import predicted_buffers
-    from .pose.refinement import REFINE_WIDTH, check_refine_table, refine_batch, refine_buffers
+    from .pose.refinement import REFINE_SIL_PARAMS, REFINE_WIDTH, check_refine_table, field_buffer, refine_batch, refine_buffers
     table = check_refine_table(refine)
     iters = int(table[0])
     dev = _lib.cuda_device(device)
@@ -1125,8 +1127,10 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
     t = lambda a: torch.from_numpy(a).to(dev)
     pred = predicted_buffers(total, name, dev)
     out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
-    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1)
-    wide = refine_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred, t(table), iters, buffers)
+    sil = table.shape[0] == REFINE_SIL_PARAMS
+    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=sil)
+    wide = refine_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred, t(table), iters, buffers,
+                        field=field_buffer(K, total, dev) if sil else None)
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
     assert columns.shape == (n, K, REFINE_WIDTH)
     return (columns, buffers[2].cpu().numpy()) if debug else columns

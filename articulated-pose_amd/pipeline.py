@@ -101,7 +101,7 @@ class _Slot(object):
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
         for inp in EVERY_INPUT:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
-        self.bounds = self.reproj_tables = self.reproj_pix = self.refine_bufs = None
+        self.bounds = self.reproj_tables = self.reproj_pix = self.refine_bufs = self.refine_field = None
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
 
@@ -171,8 +171,9 @@ class _Slot(object):
                                   torch.zeros((2 * B, GEOM_WORDS), dtype=torch.int32, device=device))
             self.reproj_pix = predicted_buffers(cap, depth, device)
         if opts.refine:                      # the loop's two working records, its best block and one pass's sums: slot-owned, shared with the
-            from .pose.refinement import refine_buffers          # range guard's f32 graph like the tables and the pixel triple above
-            self.refine_bufs = refine_buffers(B, K, device)
+            from .pose.refinement import field_buffer, refine_buffers      # range guard's f32 graph like the tables and the pixel triple above
+            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette)
+            self.refine_field = field_buffer(K, cap, device) if opts.silhouette else None      # the silhouette term: 4 bytes per pixel and part
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -365,6 +366,9 @@ class AncshPipeline(object):
     refine (with render_mesh, whatever else is built): pose.refinement.pack_refine's table, uploaded once: render-and-compare ICP at the step's
         end, behind reprojection's three calls when both are on (they share the slot's predicted tables and pixel triple) -- iters + 1 times
         ancsh_reproject_scene_build on the working poses, the renderer and ancsh_refine_pass, then ancsh_refine_rec: 5 (iters + 1) + 1 launches.
+        A table of pack_refine(silhouette=...) adds the silhouette term: ancsh_silhouette_field once in front of the loop and
+        ancsh_refine_pass_sil in it, 5 (iters + 1) + 2 launches and 4 bytes per pixel of depth_capacity, part and slot; poses shifted across
+        the ray come back, and cost_start / cost_best charge pixels that hang over the observed part.
         out["record_refined"]: 36 columns (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best, n_used,
         best_pass, passes_solved) behind whatever the record was; pose.refinement.refined_record gives the (.., 26) record of the refined
         poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the (B, K, 2, 32) sums besides.
@@ -599,7 +603,8 @@ class AncshPipeline(object):
             from .pose.refinement import refine_batch
             out["record_refined"] = refine_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom, (sl.apix, sl.amask),
                                                  out["record_reproj" if self.reprojection else "record_point_gt"], self.depth_dtype,
-                                                 sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs)
+                                                 sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs,
+                                                 field=sl.refine_field)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:

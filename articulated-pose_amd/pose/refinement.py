@@ -3,7 +3,10 @@ pose.reprojection only scores.  Each part's mesh is rendered at its working pose
 pixel by pixel (point-to-plane on same-pixel pairs, truncated at max_dist), one damped Gauss-Newton step moves R and t about the part's
 centre, and the result is the evaluated pose of lowest cost -- never worse than the fitted pose on its own measure.  s is carried: the NOCS
 scale is the network's, and one view constrains size only weakly.  Point-to-plane on same-pixel pairs does not see the silhouette, and a part
-that shows one or two flat faces leaves directions unobservable: the damping leaves those where the fit put them."""
+that shows one or two flat faces leaves directions unobservable: the damping leaves those where the fit put them -- unless the table is one of
+pack_refine(silhouette=...): then ancsh_silhouette_field finds, once per step, every crop pixel's nearest observed pixel of each part, and
+ancsh_refine_pass_sil adds one row per predicted pixel that hangs over the observed part's edge, pulling it back across the ray, and charges
+such pixels in the cost."""
 import numpy as np
 import torch
 
@@ -11,23 +14,28 @@ from .. import _lib
 
 REFINE_WIDTH = 36               # include/ancsh_hip.h, ANCSH_REFINE_WIDTH: the columns behind the carried record row, 18 per pose
 REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH_REFINE_PARAMS, ANCSH_REFINE_MAX_ITERS
+REFINE_SIL_SUMS, REFINE_SIL_PARAMS = 36, 16               # ANCSH_REFINE_SIL_SUMS, ANCSH_REFINE_SIL_PARAMS: with the silhouette term
+FIELD_SENTINEL = -32768                                   # both halves of a field word: the part has no observed pixel in the frame
 BEST_WIDTH = REFINE_WIDTH // 2
 COL_BASELINE, COL_NONLINEAR = 0, BEST_WIDTH           # counted from the end of the carried row
 POSE_COLUMNS = tuple("R%d%d" % (a, k) for a in range(3) for k in range(3)) + ("s", "tx", "ty", "tz", "cost_start", "cost_best", "n_used",
                                                                               "best_pass", "passes_solved")
 COLUMN_NAMES = tuple("baseline_" + c for c in POSE_COLUMNS) + tuple("nonlinear_" + c for c in POSE_COLUMNS)
 SUMS_COLUMNS = dict(A=slice(0, 21), b=slice(21, 27), rr=27, n_used=28, n_obs=29, cost=30, solved=31)
+SIL_SUMS_COLUMNS = dict(SUMS_COLUMNS, mm=32, n_sil=33, n_far=34)
 BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, render_mesh=<depth.pack_mesh(...)>"
 
 
 def check_refine_table(table):
-    """-> table as a fresh (REFINE_PARAMS,) float64 array; ValueError unless it is one pack_refine makes."""
+    """-> table as a fresh (REFINE_PARAMS,) float64 array, or (REFINE_SIL_PARAMS,) with the silhouette term; ValueError unless it is one
+    pack_refine makes."""
     try:
         t = np.array(table, np.float64)
     except (TypeError, ValueError):
         t = np.zeros(0)
-    if t.shape != (REFINE_PARAMS,):
-        raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), got shape %s" % (REFINE_PARAMS, t.shape))
+    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,)):
+        raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), or (%d,) with silhouette=, got shape %s"
+                         % (REFINE_PARAMS, REFINE_SIL_PARAMS, t.shape))
     iters, max_dist, min_cos, damping, max_angle, min_pixels = t[:6].tolist()
     if not (iters == int(iters) if np.isfinite(iters) else False) or not 1 <= iters <= MAX_ITERS:
         raise ValueError("refine: iters must be an integer in [1, %d], got %r" % (MAX_ITERS, iters))
@@ -41,22 +49,50 @@ def check_refine_table(table):
         raise ValueError("refine: max_angle_deg must be in (0, 90], got %r" % np.degrees(max_angle))
     if not (np.isfinite(min_pixels) and min_pixels == int(min_pixels) and min_pixels >= 1):
         raise ValueError("refine: min_pixels must be an integer >= 1, got %r" % min_pixels)
-    if (t[6:] != 0).any():
+    if (t[6:REFINE_PARAMS] != 0).any():
         raise ValueError("refine: the reserved values 6..7 must be 0")
+    if t.shape[0] == REFINE_SIL_PARAMS:
+        weight, dist, slack = t[8:11].tolist()
+        if not (np.isfinite(weight) and weight > 0):
+            raise ValueError("refine: silhouette weight must be finite and > 0, got %r" % weight)
+        if not (np.isfinite(dist) and dist > 0):
+            raise ValueError("refine: silhouette dist must be finite and > 0, got %r" % dist)
+        if not (np.isfinite(slack) and slack >= 0):
+            raise ValueError("refine: silhouette slack must be finite and >= 0 pixels, got %r" % slack)
+        if (t[11:] != 0).any():
+            raise ValueError("refine: the reserved values 11..15 must be 0")
     return t
 
 
-def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32):
+def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None):
     """The parameter table ancsh_refine_pass reads, (REFINE_PARAMS,) float64: iters Gauss-Newton passes (1..8; one more pass evaluates the
     last pose); max_dist: a pixel pair further apart than this counts as missed, and a step's translation is clamped to it; min_cos: pixels
     seen at a flatter angle are left out; damping: relative Levenberg damping of the diagonal; max_angle_deg: the clamp of a step's
     rotation; min_pixels: fewer used pixels leave the pose as it is.  Lengths are in the scaled cloud's unit, where an object's diagonal is
-    about 1.  The defaults are starting values; nobody has tuned them.  ValueError: check_refine_table's."""
+    about 1.  The defaults are starting values; nobody has tuned them.
+    silhouette = dict(weight=1.0, dist=<cloud units>, slack=1.0), or (weight, dist): the silhouette term, a (REFINE_SIL_PARAMS,) table.  A
+    predicted pixel of the part where the camera saw neither the part nor anything nearer is pulled towards the nearest observed pixel of
+    the part: weight scales its row against the depth rows; further than dist (at the pixel's depth) it pulls no more and is charged dist^2;
+    within slack pixels it is ignored (sensor holes, one pixel of raster disagreement).  min_pixels then counts these rows too.
+    ValueError: check_refine_table's."""
     try:
         head = [float(iters), float(max_dist), float(min_cos), float(damping), float(np.radians(float(max_angle_deg))), float(min_pixels)]
     except (TypeError, ValueError):
         raise ValueError("refine: iters, max_dist, min_cos, damping, max_angle_deg and min_pixels are numbers")
-    return check_refine_table(head + [0.0] * (REFINE_PARAMS - len(head)))
+    head = head + [0.0] * (REFINE_PARAMS - len(head))
+    if silhouette is None:
+        return check_refine_table(head)
+    if isinstance(silhouette, dict) and (set(silhouette) - {"weight", "dist", "slack"} or "dist" not in silhouette):
+        raise ValueError("refine: silhouette takes weight, dist (required) and slack, got %s" % sorted(silhouette))
+    try:
+        if isinstance(silhouette, dict):
+            tail = [float(silhouette.get("weight", 1.0)), float(silhouette["dist"]), float(silhouette.get("slack", 1.0))]
+        else:
+            weight, dist = silhouette
+            tail = [float(weight), float(dist), 1.0]
+    except (TypeError, ValueError):
+        raise ValueError("refine: silhouette is dict(weight=, dist=, slack=) or (weight, dist), of numbers")
+    return check_refine_table(head + tail + [0.0] * (REFINE_SIL_PARAMS - REFINE_PARAMS - len(tail)))
 
 
 def check_refine(refine, rendered):
@@ -92,17 +128,48 @@ def _f64(name, t, shape):
         raise ValueError("%s must be a contiguous %s float64 tensor" % (name, tuple(shape)))
 
 
-def refine_buffers(B, K, device, passes=1):
-    """What a slot owns for the loop: (work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2, 32)), float64."""
+def refine_buffers(B, K, device, passes=1, silhouette=False):
+    """What a slot owns for the loop: (work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2, 32 -- 36 with the
+    silhouette term)), float64."""
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-    return (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SUMS)
+    return (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS)
+
+
+def field_buffer(K, pixel_capacity, device):
+    """What a slot owns for the silhouette term: (K, pixel_capacity) int32, one plane per part, 4 bytes per pixel and part."""
+    return torch.zeros((K, int(pixel_capacity)), dtype=torch.int32, device=device)
+
+
+def silhouette_field(obs_depth, obs_labels, geom, scene, K, out=None):
+    """ancsh_silhouette_field on device tensors (no host sync): the observed pair (pixel_capacity,), geom (B, 5) int32, scene (B, 240) ->
+    field (K, pixel_capacity) int32: per crop pixel and part the offset to the nearest pixel observed for the part, (di & 0xffff) | (dj &
+    0xffff) << 16, FIELD_SENTINEL in both halves for a part without one.  Words outside the crops are left as they are."""
+    from ..depth import GEOM_WORDS, SCENE_WIDTH, _byte_plane, _depth_plane
+    _lib.require_device(obs_depth)
+    kind, cap = _depth_plane(obs_depth)
+    _byte_plane("labels", obs_labels, cap)
+    if not 1 <= int(K) <= 8:
+        raise ValueError("K=%d must be in [1, 8]" % K)
+    if geom.dtype != torch.int32 or geom.dim() != 2 or geom.shape[1] != GEOM_WORDS or not geom.is_contiguous():
+        raise ValueError("geom must be a contiguous (B, %d) int32 tensor" % GEOM_WORDS)
+    B = int(geom.shape[0])
+    _f64("scene", scene, (B, SCENE_WIDTH))
+    if out is None:
+        out = field_buffer(K, cap, obs_depth.device)
+    if out.dtype != torch.int32 or tuple(out.shape) != (int(K), cap) or not out.is_contiguous():
+        raise ValueError("field must be a contiguous (%d, %d) int32 tensor" % (K, cap))
+    _lib.require_cuda(obs_labels, geom, scene, out)
+    _lib.call("ancsh_silhouette_field", B, int(K), kind, _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap, _lib.ptr(geom), _lib.ptr(scene),
+              _lib.ptr(out))
+    return out
 
 
 def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, pose_out,
-                best, sums):
+                best, sums, field=None):
     """ancsh_refine_pass on device tensors (no host sync, no allocation): mesh = depth.mesh_to_device's; the observed pair (pixel_capacity,);
     pred = pose.reprojection.predicted_buffers' triple as the renderer left it for pred_render (2B, 208), the tables of pose_in (B, K, >= 26);
-    params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out."""
+    params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out.
+    field = silhouette_field's (K, pixel_capacity) planes: ancsh_refine_pass_sil, with a (16,) table and sums (B, K, 2, 36)."""
     from ..depth import GEOM_WORDS, RENDER_WIDTH, SCENE_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
     _lib.require_device(pose_in)
     verts, tris, tri_link, V, T = _check_device_mesh(mesh)[:5]
@@ -115,18 +182,25 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     B, K, ld = (int(v) for v in pose_in.shape)
     _f64("scene", scene, (B, SCENE_WIDTH))
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
-    _f64("params", params, (REFINE_PARAMS,))
+    sil = field is not None
+    _f64("params", params, (REFINE_SIL_PARAMS if sil else REFINE_PARAMS,))
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
-    _f64("sums", sums, (B, K, 2, REFINE_SUMS))
+    _f64("sums", sums, (B, K, 2, REFINE_SIL_SUMS if sil else REFINE_SUMS))
+    if sil and (field.dtype != torch.int32 or tuple(field.shape) != (K, cap) or not field.is_contiguous()):
+        raise ValueError("field must be a contiguous (%d, %d) int32 tensor" % (K, cap))
     if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or not geom.is_contiguous() or norm_factor.dtype != torch.float32 \
             or tuple(norm_factor.shape) != (B,) or not norm_factor.is_contiguous():
         raise ValueError("geom must be a contiguous (%d, %d) int32 tensor and norm_factor a contiguous (%d,) float32 tensor" % (B, GEOM_WORDS, B))
-    _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums)
-    _lib.call("ancsh_refine_pass", B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth),
-              _lib.ptr(obs_labels), cap, _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene),
-              _lib.ptr(pred_render), _lib.ptr(norm_factor), _lib.ptr(params), int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld,
-              _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(sums))
+    _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums, field)
+    head = (B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap,
+            _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
+            _lib.ptr(params))
+    tail = (int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld, _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(sums))
+    if sil:
+        _lib.call("ancsh_refine_pass_sil", *head, _lib.ptr(field), *tail)
+    else:
+        _lib.call("ancsh_refine_pass", *head, *tail)
     return pose_out
 
 
@@ -146,22 +220,25 @@ def refine_rec(best, carried, out=None):
     return out
 
 
-def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers):
+def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers, field=None):
     """The captured step's sequence, no host sync and no allocation beyond the output: iters + 1 times ancsh_reproject_scene_build on the
     working poses, the renderer, ancsh_refine_pass; then ancsh_refine_rec -- 5 (iters + 1) + 1 launches.  tables and pred are
     pose.reprojection's slot-owned pair and triple (shared with reprojection=True, whose three calls come first); params = pack_refine's
     table on the device and iters its first value on the host; buffers = refine_buffers'.  sums of `passes` > 1 rows keeps every pass's sums
-    (pass p in row p); one row holds the last pass's.  -> (B, K, ld + 36) float64."""
+    (pass p in row p); one row holds the last pass's.  field = field_buffer's planes, with a (16,) table: ancsh_silhouette_field once in
+    front of the loop and ancsh_refine_pass_sil in it -- 5 (iters + 1) + 2 launches.  -> (B, K, ld + 36) float64."""
     from ..depth import render_depth
     from .reprojection import reproject_scene_build
     work, best, sums = buffers
     cap = int(obs[0].shape[0])
     src = carried
+    if field is not None:
+        silhouette_field(obs[0], obs[1], geom, scene, int(carried.shape[1]), out=field)
     for p in range(iters + 1):
         reproject_scene_build(render, scene, rig, norm_factor, src, geom, cap, out=tables)
         render_depth(mesh, tables[1], tables[0], depth_dtype, out=pred[:2], scratch=pred[2])
         dst = work[p % 2]
         refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
-                    sums[p if sums.shape[0] > 1 else 0])
+                    sums[p if sums.shape[0] > 1 else 0], field=field)
         src = dst
     return refine_rec(best, carried)

@@ -298,7 +298,7 @@ def check_joint_source(joint_source):
 
 Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
                                  "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
-                                 "coord_regress_loss record_width record_key art_width rows inputs refine")
+                                 "coord_regress_loss record_width record_key art_width rows inputs silhouette refine")
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
 
@@ -326,7 +326,8 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     reprojection (with render_mesh, whatever else is built): the step re-renders the mesh at the fitted poses and compares it with the frame the
     annotation read; 15 columns (pose.reprojection.COLUMN_NAMES) behind whatever the record was, under the name "record_reproj".
     refine (with render_mesh, whatever else is built): pose.refinement.pack_refine's table; the step refines the record's poses on the depth
-    frame (render-and-compare ICP); 36 columns (pose.refinement.COLUMN_NAMES) behind whatever the record was, under the name "record_refined"."""
+    frame (render-and-compare ICP); 36 columns (pose.refinement.COLUMN_NAMES) behind whatever the record was, under the name "record_refined".
+        A table of pack_refine(silhouette=...) turns the silhouette term on (Options.silhouette): one more launch and 4 bytes per pixel and part."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -392,7 +393,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
             raise ValueError("sensor degrades the annotated depth frames of the step on the device: it needs depth_capacity=<pixels>, " + ANNOTATED)
         depth_mod.check_sensor(sensor)
     reprojection = reprojection_mod.check_reprojection(reprojection, render_mesh is not None)
-    refine = refinement_mod.check_refine(refine, render_mesh is not None) is not None
+    refine = refinement_mod.check_refine(refine, render_mesh is not None)
+    silhouette = refine is not None and refine.shape[0] == refinement_mod.REFINE_SIL_PARAMS      # the slot then owns the field's planes
+    refine = refine is not None
     if raw_capacity is not None:
         if not couple:
             raise ValueError("streaming (raw_capacity) feeds the pose fit from the networks: it needs couple=True")
@@ -420,7 +423,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, width, key, 20 if joint_states else 12, rows, (), refine)
+                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, width, key, 20 if joint_states else 12, rows, (), silhouette, refine)
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +

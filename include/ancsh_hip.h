@@ -52,6 +52,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_depth_sensor_model, ancsh_depth_sensor_model_keyed (a depth sensor's noise, holes and edge dropout on those crops),
                                  *     ancsh_reproject_scene_build, ancsh_reproject_compare_rec (render-and-compare of a pose record),
                                  *     ancsh_refine_pass, ancsh_refine_rec (render-and-compare ICP: that record's poses refined on the depth frame),
+                                 *     ancsh_silhouette_field, ancsh_refine_pass_sil (that loop's silhouette term: poses shifted across the ray come back),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1561,6 +1562,53 @@ int ancsh_refine_pass(int nframes, int K, int depth_type, const float *verts, co
                       const double *pred_render, const float *norm_factor, const double *params, int pass, int is_last,
                       const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
 int ancsh_refine_rec(int nframes, int K, const double *best, const double *carried, int ld, double *wide, void *stream);
+
+/* The silhouette term of render-and-compare ICP, two entries beside the two above (no new ABI number: callers detect them by their symbols).
+ * Point-to-plane on same-pixel pairs does not see a part that hangs over the edge of what the camera saw of it; these rows pull it back.
+ * The loop becomes: ancsh_silhouette_field once (the observed pair does not change between passes), then pass = 0 .. iters:
+ * ancsh_reproject_scene_build, the renderer, ancsh_refine_pass_sil; then ancsh_refine_rec, unchanged.
+ *
+ * ancsh_silhouette_field: ONE launch.  For every frame f, part j and crop pixel (i, jj): the nearest pixel (i', jj') of the same crop that is
+ *   OBSERVED for part j (ancsh_reproject_compare_rec's rule), nearest by (di di + dj dj, i', jj') in that order, di = i' - i, dj = jj' - jj,
+ *   all in integers: among equal distances the lower row, then the lower column.
+ *   field (K, pixel_capacity) int32: part j's plane is field + j * pixel_capacity, and the word of crop pixel (i, jj) of frame f lies at the
+ *   pixel's own address geom[f].start + i * w + jj:  word = (di & 0xffff) | (dj & 0xffff) << 16, two's-complement 16-bit halves.  The SENTINEL
+ *   di = dj = -32768 (word 0x80008000) stands for a part without an observed pixel in the frame, and for every pixel of a crop taller or
+ *   wider than 32767 pixels.  Words outside the crops are not written.  4 bytes per pixel and part.
+ *   One workgroup per (part, one of 8 row-band workers, frame); no atomics, the same bytes every run; no host sync, no allocation:
+ *   graph-capturable.  nframes == 0 launches nothing and returns 0.  Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8,
+ *   depth_type, 0 <= pixel_capacity < 2^29, null pointers, the alignments (obs_depth its element, geom and field 4, scene 8 bytes).
+ *
+ * ancsh_refine_pass_sil: ancsh_refine_pass with the term, ONE launch.  ancsh_refine_pass's arguments, and field (above) behind params;
+ *   params : ONE table of ANCSH_REFINE_SIL_PARAMS = 16 float64: [0..7] as above, [8] weight > 0, [9] dist > 0 (the scaled cloud's unit),
+ *   [10] slack >= 0 (pixels), [11..15] reserved, 0;  sums (nframes, K, 2, ANCSH_REFINE_SIL_SUMS = 36).
+ *   Every rule of ancsh_refine_pass holds for the pixels it uses (the DEPTH rows): used pixels, normals, the centre, the order of addition,
+ *   the solve, the clamp, the quaternion update, the NaN rules and best-of.  In addition a pixel is an OVERHANG pixel of (part j, pose v)
+ *   when the predicted pixel is part j and the observed pixel is not part j and either is no part at all (background and holes read the
+ *   same) or is another part with (double)d_obs * depth_scale > z_p, z_p = (double) the float32 in the key's upper half.  (Another part at
+ *   or in front of the prediction is an occlusion: skipped.)  With the pixel's field word (di, dj):  skipped -- it costs nothing -- when the
+ *   word is the SENTINEL or (double)(di di + dj dj) <= slack slack.  Otherwise row = row0 + i, col = col0 + jj, row' = row0 + i + di, col' =
+ *   col0 + jj + dj (integers, then converted), u, w from (row, col) and u', w' from (row', col') as above;  p = cloud(z_p u, z_p w, z_p),
+ *   p' = cloud(z_p u', z_p w', z_p);  dvec_a = p_a - p'_a (its z component is exactly 0);  m = |dvec|.  m > 0 fails (NaN included): skipped.
+ *   m > dist: the pixel is FAR, n_far grows by one, no row.  Otherwise g = dvec / m, r = weight m, pc = p - c, J = [weight (pc x g)_0,
+ *   weight (pc x g)_1, weight (pc x g)_2, weight g_0, weight g_1, weight g_2] ((pc x g)_0 = pc_1 g_2 - pc_2 g_1, cyclic): the row adds
+ *   J_x J_y into A and J_x r into b exactly like a depth row, m m into sum m^2, and n_sil grows by one.  A pixel is a depth row or an
+ *   overhang pixel, never both, so the order of addition is ancsh_refine_pass's: a thread's pixels in order, xor shuffles, waves in order.
+ *   The row is linearised at fixed image geometry: it ignores that a change of the part's depth moves its silhouette in the image.
+ *   sums row: [A (21) | b (6), both with the silhouette rows | sum r^2, n_used (the depth rows') | n_obs | C | solved | sum m^2 | n_sil |
+ *   n_far | 0].  C = ((sum r^2 + (max_dist max_dist) (n_obs - n_used)) + (weight weight) (sum m^2 + (dist dist) n_far)) / n_obs; NaN when
+ *   n_obs == 0.  n_obs does not depend on the pose, so a part's poses stay comparable, and a pose cannot lower its cost by overhanging.
+ *   The solve runs when n_used + n_sil >= min_pixels.  best row: as above (n_used: the depth rows').  NaN rules: as above, sums[31] and
+ *   sums[35] are 0.  Checked before any launch: ancsh_refine_pass's checks, field not null and 4-byte aligned. */
+#define ANCSH_REFINE_SIL_SUMS 36
+#define ANCSH_REFINE_SIL_PARAMS 16
+int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
+                           const int *geom, const double *scene, int *field, void *stream);
+int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                          const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity, const unsigned long long *pred_zbuf,
+                          const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
+                          const double *pred_render, const float *norm_factor, const double *params, const int *field, int pass, int is_last,
+                          const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

@@ -1,0 +1,378 @@
+"""GPU: the silhouette term of render-and-compare ICP.  ancsh_silhouette_field byte for byte against the mirror's brute force
+(tests/silhouette_mirror.py, validated on its own in tests/test_silhouette_cpu.py) on the smallest crops where it can go wrong, inside red
+zones; ancsh_refine_pass_sil against the mirror -- counts equal, float sums within the summation-order bound, and the mirror's thread 0 on
+the entry's OWN sums equal to pose_out byte for byte, so the loop is replayed pass by pass at the entry's own poses --; the behavioural bar of
+the CPU test on the GPU's result; the edge cases; and AncshPipeline(refine=<16-value table>) through three streams against the eager operator."""
+import numpy as np
+import pytest
+import torch
+
+import refinement_mirror as RF
+import reprojection_mirror as RP
+import silhouette_mirror as SM
+from redzone import Arena
+from test_refinement_cpu import MAX_DIST, behavioural_bars, mirror, refine_table
+from test_refinement_gpu import _check_against_eager, _flat
+from test_reprojection_cpu import DTYPES, object_links, object_mesh4, posed_object
+from test_reprojection_gpu import B_, CAP_, _bytes, _pipe, _stream_batches, _t
+from test_silhouette_cpu import CASES as SHIFT_CASES, IDS as SHIFT_IDS, WEIGHT, lateral_bar, occluded_frames, problem, refined, silhouette_table
+
+pytestmark = pytest.mark.gpu
+CASES = [(2, "uint16", False), (2, "float32", False), (3, "uint16", False), (3, "float32", False), (3, "uint16", True)]
+IDS = ["K2-uint16", "K2-float32", "K3-uint16", "K3-float32", "K3-sapien-rotation"]
+
+
+# ---- the field --------------------------------------------------------------------------------------------------------------------------------
+def _scene(K, scale, nlinks=None):
+    """Link l is part l for l < K; one more link with a rank but a part outside [0, K), and (K < 8) one without a rank."""
+    nl = K + 2 if nlinks is None else nlinks
+    sc = np.zeros(240)
+    sc[6], sc[14] = scale, nl
+    for l in range(nl):
+        sc[16 + 14 * l], sc[16 + 14 * l + 1] = (l, l) if l < K else (l, K + 3) if l == K else (-1, 0)
+    return sc
+
+
+def _field_frames(rs, K, npdt):
+    """Hand-made observed crops: 1 x 1, 1 x 7, 7 x 1, a checkerboard of two parts (ties everywhere), a part that fills its crop, a single pixel
+    in the far corner, and 24 x 40, 33 x 65, 3 x 300 (sparse: the nearest pixel often lies in the other chunk of columns) and 140 x 2 crops of
+    random blobs with holes (depth 0) and pixels of the two links that are in no part."""
+    one = np.ones((1, 1), npdt)
+    lab = lambda a: np.asarray(a, np.uint8)
+    frames = [(one, lab([[0]])), (np.ones((1, 7), npdt), lab([[255, 0, 255, 255, K - 1, 255, 0]])), (np.ones((7, 1), npdt), lab([[255], [0], [0], [255], [255], [255], [K - 1]]))]
+    frames.append((np.ones((6, 9), npdt), lab(np.indices((6, 9)).sum(0) % 2 * (K - 1))))
+    frames.append((np.full((5, 8), 3, npdt), lab(np.zeros((5, 8)))))
+    corner = np.full((7, 5), 255)
+    corner[6, 4] = K - 1
+    frames.append((np.ones((7, 5), npdt), lab(corner)))
+    for h, w in ((24, 40), (33, 65), (3, 300), (140, 2)):               # the last two: a second chunk of 256 columns, a worker's second band of rows
+        l = rs.randint(0, K + 2, (h, w))
+        l[rs.rand(h, w) < (0.6 if h * w > 900 else 0.97)] = 255
+        l[h // 3:h // 2, w // 4:w // 2] = K - 1
+        d = rs.randint(1, 900, (h, w)).astype(npdt)
+        d[rs.rand(h, w) < 0.2] = 0                                       # holes
+        frames.append((d, lab(l)))
+    return frames
+
+
+@pytest.mark.parametrize("K", [1, 8])
+@pytest.mark.parametrize("dtype", ["uint16", "float32"])
+def test_field_equals_the_brute_force_inside_red_zones(dev, K, dtype):
+    """Ten crops at unaligned starts and two padding frames (geometry rows of zeros: no crop) in one call, the output carved out of red
+    zones and pre-filled: every word of a crop equals the mirror's, every other word keeps its fill, no guard byte changes; twice, same bytes."""
+    from articulated_pose_amd.pose.refinement import silhouette_field
+    rs = np.random.RandomState(17)
+    frames = _field_frames(rs, K, DTYPES[dtype])
+    geom, a = [], 3
+    for d, l in frames:
+        geom.append((a, d.shape[0], d.shape[1], 5, -7))
+        a += d.size + 5
+    cap = a + 2
+    geom = np.asarray(geom + [(0, 0, 0, 0, 0)] * 2, np.int32)
+    scene = np.stack([_scene(K, 1e-3)] * len(geom))
+    od, ol = np.zeros(cap, DTYPES[dtype]), np.full(cap, 255, np.uint8)
+    for (s, h, w, _, _), (d, l) in zip(geom, frames):
+        od[s:s + h * w], ol[s:s + h * w] = d.reshape(-1), l.reshape(-1)
+    want = SM.field_flat([(d, l, (5, -7)) for d, l in frames], scene, geom, K, cap, fill=-1)
+    assert (want[:, geom[4][0]:geom[4][0] + 40] == 0).all() == (K == 1) and (want != -1).any()
+    arena = Arena()
+    out = arena.empty((K, cap), dtype=torch.int32, device=dev)          # the body is 0xff bytes: -1
+    args = (_t(od, dev), _t(ol, dev), _t(geom, dev), _t(scene, dev), K)
+    got = silhouette_field(*args, out=out).cpu().numpy()
+    assert _bytes(got, want), np.argwhere(got != want)[:10]
+    assert _bytes(silhouette_field(*args, out=out).cpu().numpy(), want)
+    assert arena.check() == 1
+    fresh = silhouette_field(*args).cpu().numpy()                       # its own buffer: zeros outside the crops
+    assert _bytes(fresh, SM.field_flat([(d, l, (5, -7)) for d, l in frames], scene, geom, K, cap, fill=0))
+    if K == 8:                                                           # a part of the scene without a pixel anywhere: the sentinel in every crop
+        s, h, w = (int(v) for v in geom[6][:3])
+        assert (got[3, s:s + h * w] != np.int32(-0x7fff8000)).any() and (got[:, geom[0][0]][1:] == np.int32(-0x7fff8000)).all()
+
+
+# ---- one pass ---------------------------------------------------------------------------------------------------------------------------------
+def _check_sums(got, want, bounds, where):
+    """One pass: got, want, bounds (n, K, 2, 36).  NaN places and the four counts equal; every float sum within its bound."""
+    assert got.shape == want.shape and (np.isnan(got) == np.isnan(want)).all(), where
+    ok = ~np.isnan(want[..., 29])
+    counts = [28, 29, 33, 34, 35]
+    assert ok.any() and _bytes(got[ok][:, counts], want[ok][:, counts]), (where, got[ok][:, counts], want[ok][:, counts])
+    floats = list(range(28)) + [32]
+    err, bd = np.abs(got[ok][:, floats] - want[ok][:, floats]), bounds[ok][:, floats]
+    assert (err <= bd).all(), (where, np.argwhere(err > bd), (err / np.maximum(bd, 1e-300)).max())
+    return float((err / np.maximum(bd, 1e-300)).max())
+
+
+def _replay(prob, rec, dtype, table, gpu_sums, frames=None):
+    """test_refinement_gpu's replay with the term: per pass the mirror's sums at the entry's own poses against the entry's, the cost and the
+    solve flag as the mirror's functions of the ENTRY's sums bit for bit -> (best (n, K, 2, 18), poses)."""
+    mesh, kin, render, scene, rigs, nf, geom, cap, own = prob
+    frames = own if frames is None else frames
+    n, K = rec.shape[:2]
+    iters = int(table[0])
+    fields = SM.field(frames, scene, K)
+    best, work, poses, worst = np.full((n, K, 2, RF.BEST), np.nan), rec[:, :, :26].copy(), [rec[:, :, :26].copy()], 0.0
+    for p in range(iters + 1):
+        S, Bd = SM.evaluate(mesh, render, scene, rigs, nf, work, geom, frames, table, fields)
+        worst = max(worst, _check_sums(gpu_sums[p], S, Bd, "pass %d" % p))
+        G = gpu_sums[p].copy()
+        for idx in np.ndindex(n, K, 2):
+            if not np.isnan(G[idx][29]):
+                c = SM.cost(G[idx], table)
+                assert np.array([c]).tobytes() == G[idx][30:31].tobytes() or (np.isnan(c) and np.isnan(G[idx][30])), (p, idx, c, G[idx][30])
+        flags = G[..., 31].copy()
+        work = SM.step(G, work, best, p, p == iters, table)
+        assert _bytes(G[..., 31], flags), (p, G[..., 31], flags)
+        poses.append(work.copy())
+    print("worst sum error / bound: %.3g" % worst)
+    return best, poses
+
+
+def _loop_on_device(dev, prob, rec, dtype, table, frames=None):
+    """pose.refinement.refine_batch on staged device tensors (what depth.refine_frames does behind its host checks, which refuse a zero norm
+    factor) -> (columns, sums (iters + 1, ...), the launches' names)."""
+    from articulated_pose_amd import _lib
+    from articulated_pose_amd.depth import mesh_to_device
+    from articulated_pose_amd.pose.refinement import field_buffer, refine_batch, refine_buffers
+    from articulated_pose_amd.pose.reprojection import predicted_buffers
+    mesh, kin, render, scene, rigs, nf, geom, cap, own = prob
+    n, K = rec.shape[:2]
+    iters = int(table[0])
+    od, ol = (_t(a, dev) for a in _flat(prob[:8] + (own if frames is None else frames,), dtype))
+    d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, d_par = (_t(a, dev) for a in (render, scene, rigs, nf, rec, geom, table))
+    tables = (torch.zeros((2 * n, 208), dtype=torch.float64, device=dev), torch.zeros((2 * n, 5), dtype=torch.int32, device=dev))
+    bufs = refine_buffers(n, K, dev, passes=iters + 1, silhouette=True)
+    names, real = [], _lib.call
+    _lib.call = lambda name, *a: (names.append(name), real(name, *a))[1]
+    try:
+        wide = refine_batch(mesh_to_device(mesh, dev), d_rt, d_sc, d_rig, d_nf, d_geom, (od, ol), d_rec, dtype, tables,
+                            predicted_buffers(cap, dtype, dev), d_par, iters, bufs, field=field_buffer(K, cap, dev))
+    finally:
+        _lib.call = real
+    assert _bytes(wide[:, :, :rec.shape[2]].cpu().numpy(), rec)
+    return wide[:, :, rec.shape[2]:].cpu().numpy(), bufs[2].cpu().numpy(), names
+
+
+@pytest.mark.parametrize("K,dtype,sapien", CASES, ids=IDS)
+def test_one_pass_equals_the_mirror(dev, K, dtype, sapien):
+    """Pass 0 on a record shifted across the ray by two pixels (overhang rows on every part) through the device wrappers: the field, the
+    tables, the renderer, ancsh_refine_pass_sil.  n_used, n_obs, n_sil and n_far equal the mirror's; the float sums lie within 4 n eps sum
+    |term|; the mirror's solve and update on the GPU's own sums give pose_out byte for byte.  Twice into the same buffers: the same bytes."""
+    from articulated_pose_amd.depth import mesh_to_device, render_depth
+    from articulated_pose_amd.pose.refinement import refine_buffers, refine_pass, silhouette_field
+    from articulated_pose_amd.pose.reprojection import predicted_buffers, reproject_scene_build
+    prob, rec, per, cen = problem(K, dtype, sapien)
+    mesh, kin, render, scene, rigs, nf, geom, cap, frames = prob
+    table = silhouette_table()
+    lat = SM.lateral_record(rec, cen, 0.02)
+    wide = np.concatenate([lat, np.random.RandomState(1).normal(size=lat.shape[:2] + (7,))], 2)       # ld_in = 33
+    d_mesh = mesh_to_device(mesh, dev)
+    od, ol = (_t(a, dev) for a in _flat(prob, dtype))
+    d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, d_par = (_t(a, dev) for a in (render, scene, rigs, nf, wide, geom, table))
+    field = silhouette_field(od, ol, d_geom, d_sc, K)
+    assert _bytes(field.cpu().numpy(), SM.field_flat(frames, scene, geom, K, cap))
+    pred = predicted_buffers(cap, dtype, dev)
+    tables = reproject_scene_build(d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, cap)
+    render_depth(d_mesh, tables[1], tables[0], dtype, out=pred[:2], scratch=pred[2])
+    (w0, _), best, sums = refine_buffers(3, K, dev, silhouette=True)
+    first = None
+    for _ in range(2):
+        for b in (w0, best, sums):
+            b.fill_(-7.0)
+        refine_pass(d_mesh, od, ol, pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, d_rec, w0, best, sums[0], field=field)
+        got = tuple(b.cpu().numpy() for b in (w0, best, sums[0]))
+        assert first is None or all(_bytes(a, b) for a, b in zip(got, first))
+        first = got
+    pose_out, g_best, g_sums = got
+    want, bounds = SM.evaluate(mesh, render, scene, rigs, nf, lat, geom, frames, table)
+    print("worst sum error / bound: %.3g" % _check_sums(g_sums, want, bounds, "pass 0"), "n_sil", g_sums[..., 33].ravel())
+    assert (g_sums[..., 33] > 0).sum() >= g_sums[..., 33].size // 2 and (g_sums[..., 34] == 0).all()
+    m_best = np.full((3, K, 2, RF.BEST), np.nan)
+    G = g_sums.copy()
+    m_out = SM.step(G, lat, m_best, 0, False, table)
+    assert _bytes(G, g_sums) and all(SM.cost(r, table) == r[30] for r in g_sums.reshape(-1, 36)) and _bytes(pose_out, m_out), np.argwhere(pose_out.view(np.uint64) != m_out.view(np.uint64))
+    assert _bytes(g_best, m_best) and (g_sums[..., 31] == 1).any()
+    with pytest.raises(ValueError, match="params"):                      # the plain entry does not take the wide table, nor this one the plain
+        refine_pass(d_mesh, od, ol, pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, d_rec, w0, best, sums[0])
+    with pytest.raises(ValueError, match="params"):
+        refine_pass(d_mesh, od, ol, pred, d_geom, d_sc, tables[0], d_nf, _t(refine_table(), dev), 0, False, d_rec, w0, best, sums[0], field=field)
+
+
+# ---- the full loop ----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K,dtype,sapien", CASES, ids=IDS)
+def test_full_loop_equals_the_replay_and_the_existing_perturbation_ends_lower(dev, K, dtype, sapien):
+    """depth.refine_frames(debug=True) with the 16-value table on test_refinement_cpu's perturbed record: every pass's sums within the
+    summation-order bound of the mirror's at the GPU's own poses, the 36 columns equal to the replay's best block byte for byte, cost_best <
+    cost_start for every part and pose.  A second call gives the same bytes."""
+    from articulated_pose_amd.depth import refine_frames
+    prob, rec, per, cen = problem(K, dtype, sapien)
+    mesh, kin, render, scene, rigs, nf, geom, cap, frames = prob
+    table = silhouette_table()
+    columns, sums = refine_frames(mesh, render, scene, rigs, nf, per, frames, dtype, table, debug=True, device=dev)
+    again = refine_frames(mesh, render, scene, rigs, nf, per, frames, dtype, table, device=dev)
+    assert columns.shape == (3, K, 36) and sums.shape == (int(table[0]) + 1, 3, K, 2, 36) and _bytes(columns, again)
+    best, poses = _replay(prob, per, dtype, table, sums)
+    assert _bytes(columns, best.reshape(3, K, 36)), np.argwhere(columns.view(np.uint64) != best.reshape(3, K, 36).view(np.uint64))
+    behavioural_bars(columns, strict=True)
+
+
+@pytest.mark.parametrize("K,dtype,shift", SHIFT_CASES, ids=SHIFT_IDS)
+def test_poses_shifted_across_the_ray_come_back(dev, K, dtype, shift):
+    """The behavioural bar of the CPU test on the GPU's result: the median lateral error is at most half the shift and no more triples end
+    above 1.0 than with the plain loop (also the GPU's), which does not meet the median bar."""
+    from articulated_pose_amd.depth import refine_frames
+    prob, rec, per, cen = problem(K, dtype)
+    mesh, kin, render, scene, rigs, nf, geom, cap, frames = prob
+    lat = SM.lateral_record(rec, cen, shift)
+    cols = refine_frames(mesh, render, scene, rigs, nf, lat, frames, dtype, silhouette_table(), device=dev)
+    p_cols = refine_frames(mesh, render, scene, rigs, nf, lat, frames, dtype, refine_table(), device=dev)
+    behavioural_bars(cols, strict=False)
+    r_sil, r_plain = SM.lateral_errors(rec, refined(cols), cen) / shift, SM.lateral_errors(rec, refined(p_cols), cen) / shift
+    lateral_bar(r_sil, r_plain)
+    assert not np.median(r_plain) <= 0.5, np.sort(r_plain.ravel())
+
+
+# ---- the edge cases ---------------------------------------------------------------------------------------------------------------------------
+def test_nan_poses_zero_norm_factors_unseen_parts_and_the_launch_sequence(dev):
+    """test_refinement_gpu's edge cases with the term on: a part with no observed pixel (the sentinel: no row, C = NaN), a prediction that
+    misses the crop, a NaN pose, a zero norm factor -- the columns equal the replay's byte for byte --, and the launches: the field once, then
+    iters + 1 times the table builder, the renderer and ancsh_refine_pass_sil, then ancsh_refine_rec."""
+    K, dtype = 3, "uint16"
+    prob, rec, per, cen = problem(K, dtype)
+    mesh, kin, render, scene, rigs, nf, geom, cap, frames = prob
+    table = silhouette_table(iters=2)
+    parts, _ = RP.link_parts(scene[0], K)
+    obs = [list(fr) for fr in frames]
+    obs[0][1] = np.where(np.isin(obs[0][1], np.nonzero(parts == 1)[0]), 255, obs[0][1]).astype(np.uint8)
+    obs = [tuple(o) for o in obs]
+    bad = SM.lateral_record(rec, cen, 0.02)
+    bad[1, 0, 13 + 10] += 10.0
+    bad[1, 2, 4] = np.nan
+    nf2 = nf.copy()
+    nf2[2] = 0.0
+    prob2 = prob[:5] + (nf2,) + prob[6:8] + (obs,)
+    columns, sums, names = _loop_on_device(dev, prob2, bad, dtype, table)
+    assert names == ["ancsh_silhouette_field"] + ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_refine_pass_sil"] * 3 + ["ancsh_refine_rec"]
+    best, poses = _replay(prob2, bad, dtype, table, sums)
+    assert _bytes(columns, best.reshape(3, K, 36))
+    b = columns.reshape(3, K, 2, 18)
+    assert np.isnan(b[2]).all() and np.isnan(b[1, 2, 0]).all() and np.isfinite(b[1, 2, 1]).all()
+    assert np.isnan(sums[:, 2, :, :, :31]).all() and (sums[:, 2, :, :, 31] == 0).all() and np.isnan(sums[:, 2, :, :, 32:35]).all() and (sums[:, 2, :, :, 35] == 0).all()
+    assert np.isnan(b[0, 1, :, 13:15]).all() and (b[0, 1, :, 15:] == 0).all() and _bytes(b[0, 1, :, :13].reshape(26), bad[0, 1])
+    assert (sums[:, 0, 1, :, 33:35] == 0).all() and (sums[:, 0, 1, :, 29] == 0).all()
+    assert (sums[:, 1, 0, 1, 28] == 0).all() and (sums[:, 1, 0, 1, 33:35] == 0).all() and _bytes(b[1, 0, 1, :13], bad[1, 0, 13:]) and b[1, 0, 1, 17] == 0
+    assert abs(b[1, 0, 1, 13] - MAX_DIST ** 2) <= 1e-18
+
+
+def test_far_pixels_rows_alone_and_occlusion(dev):
+    """A prediction entirely beside the observed part: with dist below the gap every overhang pixel is far -- no row, charged dist^2 --; with
+    dist above it the same pixels give rows and the pass solves on them alone (n_used = 0: min_pixels is met only through n_sil).  Another
+    part observed in front of the prediction is an occlusion and gives nothing; behind it, it is an overhang.  All against the replay."""
+    K, dtype = 3, "uint16"
+    prob, rec, per, cen = problem(K, dtype)
+    mesh, kin, render, scene, rigs, nf, geom, cap, frames = prob
+    side = SM.lateral_record(rec, cen, 0.6)
+    near = silhouette_table(iters=1, silhouette=dict(weight=WEIGHT, dist=0.05, slack=0.0))
+    wide = silhouette_table(iters=1, max_dist=2.0, min_pixels=8, silhouette=dict(weight=WEIGHT, dist=5.0, slack=0.0))
+    for table in (near, wide):
+        columns, sums, _ = _loop_on_device(dev, prob, side, dtype, table)
+        best, _ = _replay(prob, side, dtype, table, sums)
+        assert _bytes(columns, best.reshape(3, K, 36))
+        if table is near:
+            seen = sums[0, ..., 34] > 0
+            assert seen.any() and (sums[0, ..., 33][seen] == 0).all() and (sums[0, ..., 31][seen] == 0).all()
+            far = sums[0, ..., 34]
+        else:
+            rows = seen & (sums[0, ..., 33] >= 8)
+            assert rows.any() and (sums[0, ..., 33][seen] == far[seen]).all() and (sums[0, ..., 28][rows] == 0).all() and (sums[0, ..., 31][rows] == 1).all()
+    obs, hidden = occluded_frames(prob)
+    ray = cen[0, 0] / np.linalg.norm(cen[0, 0])
+    table = silhouette_table(iters=1)
+    for sign, more in ((+1.0, False), (-1.0, True)):
+        moved = rec.copy()
+        moved[0, 0, 10:13] += sign * 0.05 * ray
+        c1, s1, _ = _loop_on_device(dev, prob, moved, dtype, table, frames=obs)
+        c0, s0, _ = _loop_on_device(dev, prob, moved, dtype, table)
+        best, _ = _replay(prob, moved, dtype, table, s1, frames=obs)
+        assert _bytes(c1, best.reshape(3, K, 36))
+        n1, n0 = s1[0, 0, 0, 0, 33] + s1[0, 0, 0, 0, 34], s0[0, 0, 0, 0, 33] + s0[0, 0, 0, 0, 34]
+        assert s1[0, 0, 0, 0, 29] == s0[0, 0, 0, 0, 29] - hidden and ((n1 > n0) if more else (n1 == n0)), (sign, n1, n0)
+
+
+# ---- the streams ------------------------------------------------------------------------------------------------------------------------------
+def test_posed_keyed_stream_equals_the_eager_operator(dev):
+    """stream_posed_batches, K = 3, uint16, keyed, two slots, three padded batches, with reprojection=True as well: the step's last 5 (iters +
+    1) + 2 ABI calls are the option's; each slot owns its field planes; everything else equals the pipeline built without the option."""
+    from articulated_pose_amd.depth import render_depth_frames
+    from test_fit_quality_gpu import _launch_names
+    K, dtype = 3, "uint16"
+    rs = np.random.RandomState(41)
+    kin, _ = posed_object(rs, K, dtype)
+    mesh = object_mesh4()
+    table = silhouette_table(iters=2)
+    batches = _stream_batches(rs, K, dtype, kin, mesh, dev)
+    feed = [(crops, nf, dict(pose=ps, rig=rigs, seed=500 + 3 * k, cloud_base=4 * k), "t%d" % k) for k, (crops, nf, ps, rt, sc, rigs) in enumerate(batches)]
+    results = []
+    for refine in (table, None):
+        P = _pipe(K, dtype, render_mesh=mesh, kinematics=kin, keyed=True, fit_quality=True, reprojection=True, **(dict(refine=refine) if refine is not None else {}))
+        sl = P.slots[0]
+        if refine is not None:
+            names = _launch_names(P.prepare())
+            loop = ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_refine_pass_sil"]
+            assert names[-11:] == ["ancsh_silhouette_field"] + loop * 3 + ["ancsh_refine_rec"], names[-12:]
+            assert names[-12] == "ancsh_reproject_compare_rec" and "ancsh_refine_pass" not in names
+            assert sl.refine_field.shape == (K, CAP_) and sl.refine_field.dtype == torch.int32 and sl.refine_bufs[2].shape == (1, B_, K, 2, 36)
+            assert all(s.refine_field.data_ptr() != sl.refine_field.data_ptr() for s in P.slots[1:])
+        else:
+            assert sl.refine_field is None and sl.refine_bufs is None
+        results.append(list(P.stream_posed_batches(feed, articulation=True, link_counts=True)))
+        del P
+    observed = lambda k, crops, rt, sc, seed: render_depth_frames(mesh, rt, crops, dtype, dev)
+    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, table)
+
+
+def test_rendered_stream_with_a_sensor_equals_the_eager_operator(dev):
+    """stream_render_batches, K = 2, float32, a noisy sensor with holes and edge dropout, not keyed, without reprojection: the field is the
+    degraded frame's, holes read as background."""
+    from articulated_pose_amd.depth import pack_sensor, render_depth_frames, sensor_frames
+    K, dtype = 2, "float32"
+    rs = np.random.RandomState(43)
+    kin, _ = posed_object(rs, K, dtype)
+    mesh = object_mesh4()
+    sensor = pack_sensor(sigma=(0.002, 0.001, 0.0), z0=1.0, p_hole=0.2, p_edge=0.5, edge_rel=0.05)
+    table = silhouette_table(iters=1, max_dist=0.1, silhouette=dict(weight=0.5, dist=0.05, slack=1.0))
+    batches = _stream_batches(rs, K, dtype, kin, mesh, dev)
+    feed = [(crops, nf, dict(render=rt, scene=sc, rig=rigs, seed=900 + 5 * k), "t%d" % k) for k, (crops, nf, ps, rt, sc, rigs) in enumerate(batches)]
+    results = []
+    for refine in (table, None):
+        P = _pipe(K, dtype, render_mesh=mesh, sensor=sensor, **(dict(refine=refine) if refine is not None else {}))
+        results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
+        assert (P.slots[0].refine_field is not None) == (refine is not None)
+        del P
+    observed = lambda k, crops, rt, sc, seed: sensor_frames(render_depth_frames(mesh, rt, crops, dtype, dev), sc, sensor, dtype, seed=seed, device=dev)
+    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, table)
+
+
+def test_library_stream_under_the_range_guard_equals_the_eager_operator(dev):
+    """A two-instance library through stream_render_batches, built under the F16x2 range guard, whose f32 graph of the step shares the slot's
+    field planes and loop buffers."""
+    from articulated_pose_amd.depth import pack_mesh, pack_mesh_library, render_depth_frames
+    K, dtype = 3, "uint16"
+    rs = np.random.RandomState(47)
+    kin, _ = posed_object(rs, K, dtype)
+    mesh = object_mesh4()
+    lib = pack_mesh_library([mesh, pack_mesh([(0.9 * v, f) for v, f in object_links()])])
+    table = silhouette_table(iters=1)
+    batches = _stream_batches(rs, K, dtype, kin, mesh, dev, nbatches=2)
+    for k, b in enumerate(batches):
+        b[3][:, 9] = [(k + f) % 2 for f in range(3)]
+    feed = [(crops, nf, dict(render=rt, scene=sc, rig=rigs, seed=70 + k), "t%d" % k) for k, (crops, nf, ps, rt, sc, rigs) in enumerate(batches)]
+    results = []
+    for refine in (table, None):
+        on = refine is not None
+        P = _pipe(K, dtype, render_mesh=lib, arithmetic="f16x2", range_guard=True, **(dict(refine=refine) if on else {}))
+        results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
+        sl = P.slots[0]
+        assert sl.graph32 is not None and ("record_refined" in sl.out32) == on and (sl.refine_field is not None) == on
+        del P
+    observed = lambda k, crops, rt, sc, seed: render_depth_frames(lib, rt, crops, dtype, dev)
+    _check_against_eager(results[0], results[1], batches, lib, dtype, K, dev, observed, table)

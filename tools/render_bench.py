@@ -22,8 +22,10 @@ ancsh_reproject_compare_rec, with the record the stream fitted for that batch.
     r: the rendered stream without the option;   f: the rendered stream built with refine=;
 one ancsh_refine_pass alone on one batch of 32 frames whose record draws every part (the exact poses moved by 0.01), one whole loop of the
 device wrappers (pose.refinement.refine_batch) on it, and the eager operator depth.refine_frames from host arrays.
+--refine N --silhouette adds a third leg, s: the rendered stream built with refine=pack_refine(iters=N, silhouette=dict(weight=1, dist=0.1,
+slack=1)), and times ancsh_silhouette_field, one ancsh_refine_pass_sil and the whole loop with the term on the same batch and record.
 
-    python tools/render_bench.py [--sensor | --reprojection | --refine N] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+    python tools/render_bench.py [--sensor | --reprojection | --refine N [--silhouette]] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -211,10 +213,14 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
     device tensors and the eager operator on the last batch, with a record that draws every part 0.01 off its place."""
     from articulated_pose_amd.pose import refinement as F, reprojection as R
     table = F.pack_refine(iters=args.refine)
+    sil_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0)) if args.silhouette else None
+    legs = "rfs" if args.silhouette else "rf"
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
     pipes = {"r": AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare(), "f": AncshPipeline(K, wa, wn, B, N, dev, refine=table, **kw).prepare()}
+    if args.silhouette:
+        pipes["s"] = AncshPipeline(K, wa, wn, B, N, dev, refine=sil_table, **kw).prepare()
     torch.cuda.synchronize()
     last = {}
 
@@ -226,11 +232,11 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
         last[name] = got[2]
         return 1e3 * (time.perf_counter() - t0) / n
 
-    for name in "rf":
+    for name in legs:
         leg(name, 1)
-    ms = {name: [] for name in "rf"}
+    ms = {name: [] for name in legs}
     for _ in range(args.rounds):
-        for name in "rf":
+        for name in legs:
             ms[name].append(leg(name, args.passes))
     med = {k: float(np.median(v)) for k, v in ms.items()}
     W = last["r"].shape[2]
@@ -259,6 +265,25 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
     loop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_par, args.refine, bufs)
     op_ms["whole_loop"] = timed_calls(loop, args.rounds, max(1, args.calls // 10))
     cols = F.named_columns(loop().cpu().numpy())
+    sil = {}
+    if args.silhouette:                                                   # the same batch and record with the term: the field, one pass, the loop
+        d_spar, sbufs, field = torch.from_numpy(sil_table).to(dev), F.refine_buffers(B, K, dev, silhouette=True), F.field_buffer(K, cap, dev)
+        R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
+        D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
+        op_ms["silhouette_field"] = timed_calls(lambda: F.silhouette_field(clean[0], clean[1], d_geom, d_sc, K, out=field), args.rounds, args.calls)
+        op_ms["refine_pass_sil"] = timed_calls(lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_spar, 0, False,
+                                                                     carried, sbufs[0][0], sbufs[1], sbufs[2][0], field=field), args.rounds, args.calls)
+        s0 = sbufs[2][0].cpu().numpy()
+        sloop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_spar, args.refine, sbufs,
+                                       field=field)
+        op_ms["whole_loop_sil"] = timed_calls(sloop, args.rounds, max(1, args.calls // 10))
+        scols = F.named_columns(sloop().cpu().numpy())
+        sil = {"silhouette": {"table": sil_table[8:11].tolist(), "launches_added": 5 * (args.refine + 1) + 2, "field_bytes_per_slot": 4 * K * cap,
+                              "added_ms_per_batch_over_plain_refine": round(med["s"] - med["f"], 4), "s_over_r": round(med["s"] / med["r"], 4),
+                              "overhang_rows_per_part_and_pose": float(s0[..., 33].mean()), "far_pixels_per_part_and_pose": float(s0[..., 34].mean()),
+                              "median_cost_start": float(np.median(scols["baseline_cost_start"])),
+                              "median_cost_best": float(np.median(scols["baseline_cost_best"])),
+                              "parts_improved": int((scols["baseline_cost_best"] < scols["baseline_cost_start"]).sum()), "parts": B * K}}
     frames = D._cut_frames(clean[0].cpu().numpy().view(np.uint16), clean[1].cpu().numpy(), d_geom.cpu().numpy(), "uint16")
     eager = []
     for _ in range(args.rounds):
@@ -278,7 +303,7 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
                                           "median_cost_best": float(np.median(cols["baseline_cost_best"])),
                                           "parts_improved": int((cols["baseline_cost_best"] < cols["baseline_cost_start"]).sum()), "parts": B * K},
                       "streamed_last_batch": {"parts": B * K, "parts_with_a_finite_refined_pose": int(np.isfinite(F.named_columns(last["f"])["baseline_s"]).sum())},
-                      "crop_pixels_per_frame": args.side * args.side, "triangles": int(mesh[1].shape[0]),
+                      "crop_pixels_per_frame": args.side * args.side, "triangles": int(mesh[1].shape[0]), **sil,
                       "shape": {"K": K, "B": B, "N": N, "niter_a": 10000, "niter_b": 200, "slots": args.slots, "frames": len(rbatches) * B,
                                 "passes": args.passes, "rounds": args.rounds, "calls": args.calls}}))
 
@@ -288,6 +313,7 @@ def main():
     ap.add_argument("--sensor", action="store_true", help="measure the depth sensor model instead of the renderer")
     ap.add_argument("--reprojection", action="store_true", help="measure render-and-compare (reprojection=True) instead of the renderer")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="measure render-and-compare ICP (refine=pack_refine(iters=N)) instead of the renderer")
+    ap.add_argument("--silhouette", action="store_true", help="with --refine N: measure the silhouette term as well (a third leg and its launches)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
     ap.add_argument("--slots", type=int, default=8)
