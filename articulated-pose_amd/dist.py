@@ -318,15 +318,15 @@ class ShardedPipeline(object):
     joint_types (None | "revolute" | "prismatic" | K - 1 of them): passed to every rank's pipeline (AncshPipeline(joint_types=...)); the
     kind array repeats per cloud, so a shard's slice of it is the shard's own array and sharded streams stay byte-equal to one GPU's.
     joint_states=True (with articulation=True): the blocks are the (n_valid, K, 20) ones (AncshPipeline(joint_states=True)), gathered with
-    the records in the same single gather, 26 + 20 doubles a row.
-    fit_quality=True (with raw_capacity only): every rank's streamed record is the (n, K, 39) wide one (AncshPipeline(fit_quality=True)); the
-    gathered row is [record (39) | articulation block], still one gather, and dst returns the wide records.
+    the records in the same single gather.
+    The streamed record's blocks (pose.record.BLOCKS; self.record_layout says where each lies, as every rank's pipeline.record_layout does)
+    travel in that single gather, [record | articulation block] a row, and dst returns the whole record:
+    fit_quality=True (with raw_capacity only): every rank's pipeline is built with it (AncshPipeline(fit_quality=True)): the fit-quality block.
     ground_truth=True (with raw_capacity only): every rank's pipeline is built with ground_truth=True and submit() hands it its shard's rows
-    of the batch's (n_valid, K, 19) ground truth; the streamed record is 12 columns wider (the errors, ancsh_gt_error_rec) and travels in
-    the same single gather.
+    of the batch's (n_valid, K, 19) ground truth: the error block (ancsh_gt_error_rec).
     point_ground_truth=True (with raw_capacity and articulation=True): every rank's pipeline is built with point_ground_truth=True, takes
-    its shard's (n_raw, 18) clouds and gets its shard's rows of the batch's (n_valid, 13) frames from submit(); the streamed record is 21
-    columns wider (ancsh_point_gt_rec) and travels in the same single gather.
+    its shard's (n_raw, 18) clouds and gets its shard's rows of the batch's (n_valid, 13) frames from submit(): the point-gt block
+    (ancsh_point_gt_rec).
     build_point_gt=True (with point_ground_truth=True): every rank's pipeline builds its rows on the device (AncshPipeline(build_point_gt=
     True)) from its shard's (n_raw, 7) annotated clouds and its shard's rows of the batch's (n_valid, RIG_WIDTH) rigs, handed out as the
     frames are.
@@ -362,6 +362,7 @@ class ShardedPipeline(object):
         if dense and raw_capacity is None:
             raise ValueError("dense=True labels the raw rows of the stream (submit / retire / stream_batches): it needs raw_capacity")
         self.dense, self.joint_source, self.record_width, self.art_width = bool(dense), joint_source, o.record_width, o.art_width
+        self.record_layout = o.layout           # where each block of the streamed record lies (pose.record.RecordLayout), as every rank's pipeline has it
         self.couple = bool(pipeline_kw.get("couple", True))
         # only what differs from the default is passed on: a per-rank stand-in built before an option need not know it
         given = dict(joint_types=joint_types, joint_source=None if joint_source == "gt" else joint_source, dense=self.dense)
@@ -569,9 +570,9 @@ class ShardedPipeline(object):
         words (n_valid,) int32 on dst (None elsewhere).  The gather is one fixed-size (n_max, K, 26) float64 dist.gather over the
         default (gloo) group, padded per rank; every rank derives the valid counts from the split rule, so no count is exchanged.
         articulation=True (ShardedPipeline(..., articulation=True)): + the (n_valid, K, 12) articulation block on dst (None elsewhere) as
-        the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, 38) float64 rows (joint_states=True: the (n_valid, K, 20)
-        block, 46 a row; fit_quality=True: the record is the (n_valid, K, 39) wide one and the row 13 doubles longer; ground_truth=True: 12
-        more behind the record's columns).
+        the last element, gathered in the records' gather: each rank packs [record | block] into (n_max, K, record_width + art_width)
+        float64 rows (joint_states=True: the (n_valid, K, 20) block; fit_quality, ground_truth, point_ground_truth: the record is the
+        self.record_layout.width columns of pose.record.BLOCKS' blocks).
         dense=True (ShardedPipeline(..., dense=True)): + (labels (R,) int32, values (R, 7) float32, offsets (n_valid+1,) int64) of the
         batch's raw rows in global cloud order on dst (None elsewhere), last; one more gather (_gather_dense).
         World 1: the local pipeline's retire()."""
@@ -582,8 +583,8 @@ class ShardedPipeline(object):
             raise RuntimeError("retire(): no batch in flight")
         tag, seed, n_valid, here, sizes = self._stream.popleft()
         s, e = self.shard_of(n_valid)
-        rw = self.record_width                                         # 26, or (fit_quality) the wide record's 39; ground_truth: + 12; point_ground_truth: + 21
-        width = rw + self.art_width if self.articulation else rw      # [record (26 or 39) | articulation block (12 or 20)]: one gather either way
+        rw = self.record_width                                         # the streamed record's columns: self.record_layout.width
+        width = rw + self.art_width if self.articulation else rw      # [record | articulation block (12 or 20)]: one gather either way
         rec = np.zeros((self.n_max, self.K, width), np.float64)
         words = np.zeros((self.n_max,), np.int32)
         got = {}

@@ -315,13 +315,16 @@ class AncshPipeline(object):
         (B, K, 12) block of part boxes and camera-space joints; retire(articulation=True) returns it.
     joint_states (with articulation): one more launch (ancsh_joint_state_rec) widens that block to (B, K, 20), its 12 columns bit for bit and
         the joint state behind them.  It is still out["articulation"]: no new name in the result tuple.
-    fit_quality: one more launch behind the fit (ancsh_fit_quality_rec) leaves out["record_wide"] (B, K, 39), the record's 26 columns bit for
-        bit and the fit quality behind them.  Works with couple=False too.
+    The streamed record is the pose record and one block of columns per option below that reports something per part, each written by one
+        launch that copies the record so far bit for bit: pose.record.BLOCKS is the one table of the blocks, their order, widths, column
+        names and out[...] names, and pipe.record_layout (pose.record.RecordLayout) says where each lies in THIS pipeline's record.
+    fit_quality: one more launch behind the fit (ancsh_fit_quality_rec) leaves out["record_wide"], the record's columns bit for bit and the
+        fit-quality block behind them.  Works with couple=False too.
     ground_truth (streaming): submit(..., gt=...) brings a (K, 19) block per cloud and one more launch (ancsh_gt_error_rec) leaves
-        out["record_gt"], 12 error columns behind the record or the wide record.
+        out["record_gt"], the error block behind the record so far.
     point_ground_truth (streaming, with articulation): the rows are dataset.pack_cloud's 18 columns, submit(..., frame=...) brings part 0's
         ground-truth NAOCS pose per cloud, and the last launch of the articulation group (ancsh_point_gt_rec) leaves out["record_point_gt"]:
-        both networks' test losses (coord_regress_loss: "L2" | "L1") and the joint errors, 21 columns behind whatever the record was.
+        both networks' test losses (coord_regress_loss: "L2" | "L1") and the joint errors, the point-gt block behind the record so far.
     build_point_gt (with point_ground_truth): the stream takes (n_raw, 7) annotated clouds and one rig per cloud (submit(..., rig=...)), and the
         step's first launch (ancsh_point_gt_build) builds the 18-column rows on the device.
     build_gt_pose (with point_ground_truth): one more launch directly behind the sampler (ancsh_gt_pose_build) fits the ground-truth poses
@@ -360,8 +363,8 @@ class AncshPipeline(object):
     reprojection (with render_mesh, whatever else is built): render-and-compare at the step's end -- ancsh_reproject_scene_build turns the
         record's two poses per part into two render tables per frame, the renderer draws those 2 * B predicted frames into a pixel triple of the
         slot (22 bytes per pixel of capacity, 26 with float32), and ancsh_reproject_compare_rec scores them against the pair the annotation
-        read (with sensor=: the degraded one): out["record_reproj"], 15 columns (pose.reprojection.COLUMN_NAMES: observed pixels, then predicted
-        pixels, overlap, IoU and the depth residual's mean |d|, RMS, max and mean per pose) behind whatever the record was.  Five launches more;
+        read (with sensor=: the degraded one): out["record_reproj"], the reprojection block (pose.reprojection.COLUMN_NAMES: observed pixels, then
+        predicted pixels, overlap, IoU and the depth residual's mean |d|, RMS, max and mean per pose) behind the record so far.  Five launches more;
         the result tuple keeps its form.  A short batch's padding frames take pixels of their own, as with a sensor.
     refine (with render_mesh, whatever else is built): pose.refinement.pack_refine's table, uploaded once: render-and-compare ICP at the step's
         end, behind reprojection's three calls when both are on (they share the slot's predicted tables and pixel triple) -- iters + 1 times
@@ -369,10 +372,12 @@ class AncshPipeline(object):
         A table of pack_refine(silhouette=...) adds the silhouette term: ancsh_silhouette_field once in front of the loop and
         ancsh_refine_pass_sil in it, 5 (iters + 1) + 2 launches and 4 bytes per pixel of depth_capacity, part and slot; poses shifted across
         the ray come back, and cost_start / cost_best charge pixels that hang over the observed part.
-        out["record_refined"]: 36 columns (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best, n_used,
-        best_pass, passes_solved) behind whatever the record was; pose.refinement.refined_record gives the (.., 26) record of the refined
-        poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the (B, K, 2, 32) sums besides.
-    In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built."""
+        out["record_refined"]: the refinement block (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best,
+        n_used, best_pass, passes_solved) behind the record so far; pose.refinement.refined_record(record, layout=pipe.record_layout) gives the
+        (.., 26) record of the refined poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the
+        (B, K, 2, 32) sums besides.
+    In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built,
+    out[pipe.record_layout.key], pipe.record_layout.width columns."""
 
     ninst = None                                # a library's size (render_mesh=depth.pack_mesh_library(...)); None for a single object
 
@@ -392,6 +397,7 @@ class AncshPipeline(object):
                                       label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor,
                                       reprojection, refine)
         self.refine = o.refine
+        self.record_layout = o.layout           # where each block of the streamed record lies (pose.record.RecordLayout)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
             setattr(self, name, getattr(o, name))
         self.joint_source, self.arithmetic = joint_source, arithmetic
@@ -559,9 +565,10 @@ class AncshPipeline(object):
         sol = self.solver.solve(sl.P, nocs, mask, axis, draws_a=sl.draws_a, draws_b=sl.draws_b, seed=self.seed, seed_dev=seed_dev,
                                 key_dev=key_dev, fit_quality=self.fit_quality, ground_truth=gt_in, **assoc)
         out = dict(ancsh=a, npcs=n, pose=sol, record=sol["record"])      # (B, K, 26) float64, written by the fit's two finish kernels
-        if self.fit_quality:             # behind the fit and the record poison: (B, K, 39) float64, one launch (the solver issued it)
+        carried = self.record_layout.carried                             # block -> (the out[...] name, the width) of the record its launch copies
+        if self.fit_quality:             # behind the fit and the record poison: the fit-quality block, one launch (the solver issued it)
             out["record_wide"] = sol["record_wide"]
-        if self.ground_truth:            # behind those: (B, K, 38 or 51) float64, one launch (the solver issued it)
+        if self.ground_truth:            # behind those: the error block, one launch (the solver issued it)
             out["record_gt"] = sol["record_gt"]
         if self.articulation:            # behind the fit and the record poison: (B, K, 12) float64, one launch
             from .pose.joint_params import articulation_batch
@@ -569,11 +576,10 @@ class AncshPipeline(object):
             if self.joint_states:        # one more: the block's 12 columns and the joint state behind them, (B, K, 20) float64
                 from .pose.joint_params import joint_state_batch
                 out["articulation"] = joint_state_batch(sl.P, n, sol["record"], out["articulation"])
-            if self.point_ground_truth:  # the last of the group: the widest record so far and the 21 columns behind it, one launch
+            if self.point_ground_truth:  # the last of the group: the record so far and the point-gt block behind it, one launch
                 from .pose.point_gt import point_gt_batch
-                carried = out["record_gt"] if self.ground_truth else out["record_wide"] if self.fit_quality else out["record"]
                 out["record_point_gt"] = point_gt_batch(sl.raw_rows, sl.header(self.B)[1], sl.perm, a, n, out["articulation"], frame_in,
-                                                        carried, self.coord_regress_loss)
+                                                        out[carried("point_gt")[0]], self.coord_regress_loss)
         if self.dense or self.label_images or self.annotated_images:      # at most one: a depth pipeline refuses dense=True, annotated frames label_images
             # the last launch: every raw row of the slot's batch (label_images: its unprojected rows; annotated_images: its 18-column rows),
             # into the slot's own (capacity, .) buffers
@@ -592,17 +598,16 @@ class AncshPipeline(object):
                 out["annotated_images"] = depth_annotated_images(sl.apix, sl.amask, sl.geom, sl.scene, sl.dest, off, sl.counts, rl[0], rl[1],
                                                                  sl.raw_rows, out=sl.pick("aimg", f32), scratch=sl.scratch)
         if self.reprojection:            # the step's last three calls, behind the record's poison: the record's poses -> two render tables per
-            # frame, the renderer on 2 * B frames, and the predicted pixels against the pair the annotation read -> 15 columns behind the record
+            # frame, the renderer on 2 * B frames, and the predicted pixels against the pair the annotation read -> its block behind the record
             from .pose.reprojection import reprojection_batch
-            # (a pipeline that holds a mesh is built with point_ground_truth: its record is the widest one so far)
             out["record_reproj"] = reprojection_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom,
-                                                      (sl.apix, sl.amask), out["record_point_gt"], self.depth_dtype, sl.reproj_tables,
+                                                      (sl.apix, sl.amask), out[carried("reprojection")[0]], self.depth_dtype, sl.reproj_tables,
                                                       sl.reproj_pix)
         if self.refine:                  # the step's last 5 (iters + 1) + 1 launches: the record's poses refined on the pair the annotation read, in
-            # the predicted tables and pixel triple reprojection has finished with -> 36 columns behind the widest record so far
+            # the predicted tables and pixel triple reprojection has finished with -> its block behind the record so far
             from .pose.refinement import refine_batch
             out["record_refined"] = refine_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom, (sl.apix, sl.amask),
-                                                 out["record_reproj" if self.reprojection else "record_point_gt"], self.depth_dtype,
+                                                 out[carried("refinement")[0]], self.depth_dtype,
                                                  sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs,
                                                  field=sl.refine_field)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
@@ -930,11 +935,10 @@ class AncshPipeline(object):
 
     def retire(self, flags=False, articulation=False, dense=False, label_images=False, link_counts=False, annotated_images=False):
         """Wait for the oldest submitted batch -> (tag, seed, record): record = its valid clouds' (n_valid, K, 26) float64 pose
-        records, a fresh host array (a pipeline built with fit_quality=True: the (n_valid, K, 39) wide records -- the same 26 columns, then
-        the fit quality, include/ancsh_hip.h, ancsh_fit_quality_rec; flagged clouds take all 39 from the f32 graph; built with
-        ground_truth=True: 12 more columns behind either, the errors against the submitted ground truth, ancsh_gt_error_rec, refit
-        alike; built with point_ground_truth=True: 21 more columns behind whatever that was, both networks' test losses and the joint errors,
-        ancsh_point_gt_rec, refit alike).  Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
+        records, a fresh host array (a pipeline built with fit_quality, ground_truth, point_ground_truth, reprojection or refine: the
+        (n_valid, K, pipe.record_layout.width) records -- the same 26 columns, then the blocks those options build, in pose.record.BLOCKS'
+        order; pipe.record_layout.block(record, name) cuts one out; flagged clouds take every column from the f32 graph).
+        Range guard: when a valid cloud's flag word is non-zero, the slot's f32 graph refits the batch
         (its raw rows and header are still in the slot: a slot is reused only after it retires) and the flagged clouds' records are
         the f32 ones (pipe.f32_reruns counts these batches).  flags=True: (tag, seed, record, flag words (n_valid,) int32; zeros
         without the guard).  articulation=True (a pipeline built with articulation=True): + the (n_valid, K, 12) float64 articulation

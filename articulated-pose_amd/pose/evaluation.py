@@ -296,9 +296,11 @@ def miou_report(iou_rat, num_parts, domain, nocs):
     return lines
 
 
-def stream_tables(rows, num_parts, item, domain, nocs="ANCSH", error_skip=None, device="cpu"):
+def stream_tables(rows, num_parts, item, domain, nocs="ANCSH", error_skip=None, device="cpu", layout=None):
     """The scripts' tables from accumulated streamed rows of a ground-truth pipeline (AncshPipeline(..., ground_truth=True)): rows
-    (F, K, 38) float64 -- or (F, K, 51) with fit_quality=True --, one frame per leading index, as retire / stream_batches return them.
+    (F, K, .) float64, one frame per leading index, as retire / stream_batches return them.  layout (pose.record.RecordLayout, the
+    pipeline's record_layout): the pose and the errors are read where it says, whatever else the pipeline was built with; None: the
+    error block is the rows' last, behind the record or the fit-quality wide record.
     -> the lines error_report, miou_report and relative_report print, in that order, after the scripts' own skip rules:
       * the error tables (eval_pose_err.py:111-172) leave out, per key, a frame whose fit failed -- a NaN scale in any part, the
         poisoned record that stands for the reference's `scale is None` -- and count a NaN translation error as 0; error_skip: a
@@ -312,9 +314,13 @@ def stream_tables(rows, num_parts, item, domain, nocs="ANCSH", error_skip=None, 
         baseline line is NaN."""
     from .gt_errors import (ERR_IOU, ERR_NL_IOU, ERR_NL_REL_ROT, ERR_NL_REL_TRANS, ERR_NL_RPY, ERR_NL_XYZ, ERR_REL_ROT, ERR_RPY, ERR_XYZ,
                             GT_ERROR_WIDTH)
+    from .record import carried_widths
     rows = np.asarray(rows, np.float64)
-    if rows.ndim != 3 or rows.shape[1] != num_parts or rows.shape[2] - GT_ERROR_WIDTH not in (26, 39):
-        raise ValueError("rows must be (frames, %d, 38) or (frames, %d, 51) streamed ground-truth rows, got %s" % (num_parts, num_parts, rows.shape))
+    if layout is not None:
+        rows = layout.check(rows, "rows")[..., :layout.span("gt_errors").stop]
+    if rows.ndim != 3 or rows.shape[1] != num_parts or rows.shape[2] - GT_ERROR_WIDTH not in carried_widths("gt_errors"):
+        raise ValueError("rows must be (frames, %d, ld + %d) streamed ground-truth rows, ld in %s, got %s"
+                         % (num_parts, GT_ERROR_WIDTH, carried_widths("gt_errors"), rows.shape))
     ld = rows.shape[2] - GT_ERROR_WIDTH
     skip = np.zeros(rows.shape[0], bool) if error_skip is None else np.asarray(error_skip, bool).reshape(rows.shape[0])
     cols = {"baseline": (9, ERR_RPY, ERR_XYZ, ERR_IOU, ERR_REL_ROT, None),

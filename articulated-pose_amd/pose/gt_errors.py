@@ -8,11 +8,11 @@ import torch
 from .. import _lib
 
 GT_WIDTH = 19                   # include/ancsh_hip.h, ancsh_gt_error_rec: a ground-truth row
-GT_ERROR_WIDTH = 12             # the error columns behind the record's (26) or the fit-quality wide record's (39)
+GT_ERROR_WIDTH = 12             # the error columns behind the carried row: the record or the fit-quality wide record (pose.record)
 GT_NRES = 50                    # the reference's iou_3d grid (lib/d3_utils.py:55)
 # columns of a ground-truth row
 GT_R, GT_S, GT_T, GT_EXTENT, GT_T_NAOCS = slice(0, 9), 9, slice(10, 13), slice(13, 16), slice(16, 19)
-# the error columns, counted from the end of the carried row (ld = 26 or 39): column = ld + ERR_*
+# the error columns, counted from the block's first (pose.record: RecordLayout.span("gt_errors").start): column = ld + ERR_*
 ERR_RPY, ERR_XYZ, ERR_SCALE, ERR_IOU, ERR_REL_ROT = 0, 1, 2, 3, 4                          # the baseline pose (record columns 0..12)
 ERR_NL_RPY, ERR_NL_XYZ, ERR_NL_SCALE, ERR_NL_IOU, ERR_NL_REL_ROT = 5, 6, 7, 8, 9           # the nonlinear pose (13..25)
 ERR_NL_REL_TRANS = 10           # nonlinear pose: |(t_naocs_j - t_naocs_0) - (dynam_j - canon_j) R_0[:, 0]|
@@ -84,16 +84,17 @@ def pack_box_extents(box_extent):
 
 def gt_error_batch(P, npcs_nocs, npcs_mask, record, gt, nres=GT_NRES):
     """The errors of a batch in ONE launch: P (B, N, C >= 3) float32 sampled points, npcs_nocs (B, N, 3K) and npcs_mask (B, N, K) float32:
-    the heads the record was fitted on, record (B, K, 26) float64 -- or the (B, K, 39) fit-quality wide record --, gt (B, K, 19) float64
+    the heads the record was fitted on, record (B, K, ld) float64 -- the record or the fit-quality wide record --, gt (B, K, 19) float64
     on the device.  Returns the (B, K, ld + 12) float64 block on the device: row (c, j) = [the input row, bit for bit | rpy_err, xyz_err,
     scale_err, 3-D IoU, relative rotation error of the baseline pose | the same five of the nonlinear pose | its relative translation
     error | points of part j] (include/ancsh_hip.h has the definitions and the NaN rules).  No host synchronisation and no allocation
     beyond the output: the captured streaming step calls it."""
+    from .record import carried_widths
     _lib.require_cuda(record, gt, P, npcs_nocs, npcs_mask)
     B, K = record.shape[:2]
     ld = record.shape[2] if record.dim() == 3 else -1
-    if record.dtype != torch.float64 or record.dim() != 3 or ld not in (26, 39) or not record.is_contiguous():
-        raise ValueError("record must be a contiguous (B, K, 26) or (B, K, 39) float64 tensor")
+    if record.dtype != torch.float64 or record.dim() != 3 or ld not in carried_widths("gt_errors") or not record.is_contiguous():
+        raise ValueError("record must be a contiguous (B, K, ld) float64 tensor, ld in %s" % (carried_widths("gt_errors"),))
     if gt.dtype != torch.float64 or tuple(gt.shape) != (B, K, GT_WIDTH) or not gt.is_contiguous():
         raise ValueError("gt must be a contiguous (B, K, %d) float64 tensor" % GT_WIDTH)
     N = P.shape[1] if P.dim() == 3 else -1

@@ -291,14 +291,14 @@ class PoseSolver(object):
         Fitted as a revolute joint it gets no joint fit: every evaluation of the objective is NaN, MINPACK accepts no step, and the row
         holds the unrefined Kabsch start of the winning sample (finite, not NaN: tests/test_prismatic_gpu.py).  A prismatic joint
         (joint_types) does not read its direction and is fitted like any other.
-        fit_quality=True: one more launch behind the poison (pose.quality.fit_quality_batch) adds "record_wide" (B, K, 39) float64 -- the
-        record's 26 columns bit for bit, then per part its points, both winners' scores and the inliers / mean / RMS / median / max
-        residual of the baseline and of the nonlinear pose over all points of the part.  Without it nothing changes.
+        fit_quality=True: one more launch behind the poison (pose.quality.fit_quality_batch) adds "record_wide", float64 -- the record's
+        columns bit for bit, then per part its points, both winners' scores and the inliers / mean / RMS / median / max residual of the
+        baseline and of the nonlinear pose over all points of the part.  Without it nothing changes.
         ground_truth=gt ((B, K, 19) float64 on the device, pose.gt_errors.pack_ground_truth's rows): one more launch behind those
-        (pose.gt_errors.gt_error_batch, on P and the nocs_pred / mask_pred the fit read) adds "record_gt" (B, K, 38) float64 -- the
-        record's 26 columns bit for bit, then rpy_err / xyz_err / scale_err / 3-D IoU / relative rotation error of both poses, the
-        nonlinear pose's relative translation error and the part's points -- or, with fit_quality=True, (B, K, 51) behind the wide
-        record's 39.  "record" and "record_wide" are unchanged."""
+        (pose.gt_errors.gt_error_batch, on P and the nocs_pred / mask_pred the fit read) adds "record_gt", float64 -- the record so far
+        (the wide one with fit_quality=True) bit for bit, then rpy_err / xyz_err / scale_err / 3-D IoU / relative rotation error of both
+        poses, the nonlinear pose's relative translation error and the part's points.  "record" and "record_wide" are unchanged.
+        pose.record.BLOCKS is the table of these blocks and their columns."""
         _one_association(joint_cls, joint_index)
         if fit_quality:
             from .quality import check_fit_quality
@@ -315,8 +315,10 @@ class PoseSolver(object):
             out["record_wide"] = fit_quality_batch(out, self.th)
         if ground_truth is not None:
             from .gt_errors import gt_error_batch
+            from .record import layout_for
             P32, nocs32, mask32 = out["_inputs"]          # the contiguous float32 tensors the partition read
-            out["record_gt"] = gt_error_batch(P32, nocs32, mask32, out["record_wide"] if fit_quality else out["record"], ground_truth)
+            carried = layout_for(bool(fit_quality), True).carried("gt_errors")[0]
+            out["record_gt"] = gt_error_batch(P32, nocs32, mask32, out[carried], ground_truth)
         return out
 
     def solve_stage_a(self, P, nocs_pred, mask_pred, draws_a=None, seed=0):

@@ -8,10 +8,9 @@ import torch
 from .. import _lib
 from ..dataset import NCHAN
 
-POINT_GT_WIDTH = 21             # include/ancsh_hip.h, ancsh_point_gt_rec: the columns behind the carried row (ld = 26, 39, 38 or 51)
+POINT_GT_WIDTH = 21             # include/ancsh_hip.h, ancsh_point_gt_rec: the columns behind the carried row (ld in CARRIED_WIDTHS)
 FRAME_WIDTH = 13                # a frame row: [R (9, row-major) | s | t (3)] of the ground-truth NAOCS pose of part 0
-CARRIED_WIDTHS = (26, 39, 38, 51)
-# the columns, counted from the end of the carried row: column = ld + PGT_*
+# the columns, counted from the block's first (pose.record: RecordLayout.span("point_gt").start): column = ld + PGT_*
 PGT_ANGLE_ERR, PGT_DIST_ERR = 0, 1                      # row j >= 1: the errors of joint j
 PGT_JOINT_POINT, PGT_JOINT_AXIS = slice(2, 5), slice(5, 8)      # row j >= 1: the ground-truth joint j in camera space
 PGT_MIOU, PGT_NPCS_MIOU = 8, 9                          # miou_loss[j] of the ANCSH and of the NPCS network
@@ -24,6 +23,14 @@ POINT_GT_COLUMNS = ("angle_err", "dist_err", "joint_point_x", "joint_point_y", "
                     "orient_loss", "index_loss_0", "index_loss_1", "index_loss_2", "npcs_nocs_loss")
 RAW_COLUMNS = "x y z | cls | nocs_p 3 | nocs_g 3 | heatmap | unitvec 3 | orient 3 | joint_cls"
 _TYPE_L = {"L2": 0, "L1": 1}
+
+
+def __getattr__(name):
+    """CARRIED_WIDTHS: the widths of the carried row, from the record's table (pose.record, which reads this module's width: hence lazily)."""
+    if name == "CARRIED_WIDTHS":
+        from .record import CARRIED_WIDTHS
+        return CARRIED_WIDTHS
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def check_point_ground_truth(point_ground_truth, articulation, depth=False):
@@ -103,10 +110,11 @@ def point_gt_batch(raw_rows, offsets, perm, ancsh_pred, npcs_pred, art, frame, r
     offsets (B+1,) int32 (cloud c owns rows [offsets[c], offsets[c+1])), perm (B, N) int32 = the sampler's perm_out; ancsh_pred /
     npcs_pred = the two networks' output dicts (the ANCSH W / nocs / gocs / heatmap / unitvec / joint_axis / index heads, the NPCS W / nocs);
     art = the (B, K, 12) articulation block or the (B, K, 20) joint-state block; frame (B, 13) float64 = pack_joint_frame's rows; record
-    (B, K, ld) float64, ld in {26, 39, 38, 51}.  Returns the (B, K, ld + 21) float64 block on the device: row (c, j) = [the input row, bit
+    (B, K, ld) float64, ld in CARRIED_WIDTHS.  Returns the (B, K, ld + 21) float64 block on the device: row (c, j) = [the input row, bit
     for bit | POINT_GT_COLUMNS] (include/ancsh_hip.h has the definitions and the NaN rules).  debug=True: (block, joint_gt (B, K-1, 6)
     float64 = the ground-truth joints [point | axis] in global NOCS, bit-equal to ancsh_joint_params(axis_mean=1)).  No host
     synchronisation and no allocation beyond the outputs: the captured streaming step calls it."""
+    from .record import CARRIED_WIDTHS
     _lib.require_cuda(raw_rows, offsets, perm, art, frame, record)
     check_loss_type(coord_regress_loss)
     dev = record.device
@@ -140,16 +148,21 @@ def point_gt_batch(raw_rows, offsets, perm, ancsh_pred, npcs_pred, art, frame, r
     return (wide, joint_gt) if debug else wide
 
 
-def stream_point_tables(rows, num_parts, is_mixed=True, pred_joint=True, early_split=True, pred_joint_ind=True, network="ancsh"):
+def stream_point_tables(rows, num_parts, is_mixed=True, pred_joint=True, early_split=True, pred_joint_ind=True, network="ancsh", layout=None):
     """The closing lines of eval_joint_params.py (:262-269) and the test_loss.txt line (lib/network.py:228-243) from accumulated streamed
     rows of a point-ground-truth pipeline (AncshPipeline(..., point_ground_truth=True)): rows (F, K, ld + 21) float64, one frame per
     leading index, as retire / stream_batches return them.  -> (joint lines, loss line):
       * joint lines: the shapes line, then per joint k the 'joint k with mean angle error ... degrees, mean dist ...' line and the bare
         pair under it; a NaN error counts as 0 (:264-265) and a line is the mean absolute error over the frames;
       * loss line: every loss's mean over the frames, then loss.collect_losses and loss.format_loss_result.  network="npcs": the NPCS
-        network's line (its nocs and mIoU losses; it has no joint heads)."""
+        network's line (its nocs and mIoU losses; it has no joint heads).
+    layout (pose.record.RecordLayout, a pipeline's record_layout): rows are that pipeline's records, whatever else it was built with, and
+    the block is read where the layout says; None: the block is the rows' last."""
     from ..loss import collect_losses, format_loss_result
+    from .record import CARRIED_WIDTHS
     rows = np.asarray(rows, np.float64)
+    if layout is not None:
+        rows = layout.check(rows, "rows")[..., :layout.span("point_gt").stop]
     if rows.ndim != 3 or rows.shape[1] != num_parts or rows.shape[2] - POINT_GT_WIDTH not in CARRIED_WIDTHS:
         raise ValueError("rows must be (frames, %d, ld + %d) streamed point-ground-truth rows, ld in %s, got %s"
                          % (num_parts, POINT_GT_WIDTH, CARRIED_WIDTHS, rows.shape))

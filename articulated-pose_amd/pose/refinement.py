@@ -106,16 +106,21 @@ def check_refine(refine, rendered):
 
 
 def named_columns(record):
-    """The trailing 36 columns of a streamed record (..., >= 36) -> {name: (...) array}, by COLUMN_NAMES."""
+    """The trailing REFINE_WIDTH columns of a column block (..., >= REFINE_WIDTH) -> {name: (...) array}, by COLUMN_NAMES: what the eager
+    operators (refine_rec) return.  Of a pipeline's streamed record the block is the last only while nothing is built behind it: cut it out
+    first, named_columns(pipe.record_layout.block(record, "refinement"))."""
     if record.shape[-1] < REFINE_WIDTH:
         raise ValueError("expected at least %d trailing columns, got %d" % (REFINE_WIDTH, record.shape[-1]))
     tail = record[..., record.shape[-1] - REFINE_WIDTH:]
     return {name: tail[..., k] for k, name in enumerate(COLUMN_NAMES)}
 
 
-def refined_record(record):
-    """A streamed record with the refinement's columns last (..., >= 26 + 36) -> (..., 26): the two refined poses in a pose record's own
-    columns, as depth.reprojection_frames, pose.gt_errors and the other operators on a record take them.  A copy."""
+def refined_record(record, layout=None):
+    """A streamed record with the refinement's columns -> (..., 26): the two refined poses in a pose record's own columns, as
+    depth.reprojection_frames, pose.gt_errors and the other operators on a record take them.  A copy.  layout (pose.record.RecordLayout,
+    a pipeline's record_layout): the block is read where it says; None: it is the record's last, behind at least a pose record."""
+    if layout is not None:
+        record = layout.check(record)[..., :layout.span("refinement").stop]
     if record.shape[-1] < 26 + REFINE_WIDTH:
         raise ValueError("expected a record of at least %d columns, got %d" % (26 + REFINE_WIDTH, record.shape[-1]))
     tail = record[..., record.shape[-1] - REFINE_WIDTH:]

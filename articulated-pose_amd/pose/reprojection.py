@@ -23,7 +23,9 @@ def check_reprojection(reprojection, rendered):
 
 
 def named_columns(columns):
-    """The trailing 15 columns of a streamed record (..., >= 15) -> {name: (...) array}, by COLUMN_NAMES."""
+    """The trailing REPROJECTION_WIDTH columns of a column block (..., >= REPROJECTION_WIDTH) -> {name: (...) array}, by COLUMN_NAMES: what
+    the eager operators (reproject_compare) return.  Of a pipeline's streamed record the block is the last only while nothing is built
+    behind it (refine=): cut it out first, named_columns(pipe.record_layout.block(record, "reprojection"))."""
     if columns.shape[-1] < REPROJECTION_WIDTH:
         raise ValueError("expected at least %d trailing columns, got %d" % (REPROJECTION_WIDTH, columns.shape[-1]))
     tail = columns[..., columns.shape[-1] - REPROJECTION_WIDTH:]

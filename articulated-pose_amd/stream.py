@@ -9,6 +9,7 @@ import torch
 
 from . import dataset, depth as depth_mod
 from .pose import gt_errors, joint_params, point_gt, quality, refinement as refinement_mod, reprojection as reprojection_mod
+from .pose.record import RecordLayout
 
 # ---- the slot header ---------------------------------------------------------------------------------------------------------
 # [seed (int64 bits) -- keyed: the 16-byte key block (ancsh_stream_key: seed, cloud_base, reserved) -- | offsets (B+1) int32 |
@@ -296,9 +297,17 @@ def check_joint_source(joint_source):
     return joint_source
 
 
-Options = collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
-                                 "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
-                                 "coord_regress_loss record_width record_key art_width rows inputs silhouette refine")
+class Options(collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
+                                     "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
+                                     "coord_regress_loss record_width record_key art_width rows inputs silhouette refine")):
+    __slots__ = ()
+
+    @property
+    def layout(self):
+        """The streamed record's blocks (pose.record.RecordLayout): record_width and record_key are its width and key."""
+        return RecordLayout.of(self)
+
+
 OPTION_FLAGS = Options._fields[:Options._fields.index("record_width")]      # the flags; the rest is derived from them
 
 
@@ -308,7 +317,8 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                   coord_regress_loss="L2", build_gt_pose=False, render_mesh=None, kinematics=None, annotated_images=False, sensor=None,
                   reprojection=False, refine=None):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
-    (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under, the articulation block's
+    (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under (pose.record.BLOCKS: the one
+    table of the record's blocks; Options.layout says where each lies), the articulation block's
     width, the row kind (a ROW_KINDS entry; None without a stream) and the side inputs a submit takes (SIDE_INPUTS entries).
     raw_capacity in the result is the slots' capacity: depth_capacity's value on a depth pipeline.
     build_gt_pose (with point_ground_truth): the step fits both ground-truth pose tables itself, so `frame` is no side input and of `gt`
@@ -324,9 +334,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     sensor (annotated depth frames only, submitted, rendered, posed or from a library): depth.pack_sensor's table; the step degrades every
     frame as that depth sensor would (ancsh_depth_sensor_model) into a second pair of pixel buffers, which the annotation and the images read.
     reprojection (with render_mesh, whatever else is built): the step re-renders the mesh at the fitted poses and compares it with the frame the
-    annotation read; 15 columns (pose.reprojection.COLUMN_NAMES) behind whatever the record was, under the name "record_reproj".
+    annotation read; the record's reprojection block (pose.reprojection.COLUMN_NAMES), under the name "record_reproj".
     refine (with render_mesh, whatever else is built): pose.refinement.pack_refine's table; the step refines the record's poses on the depth
-    frame (render-and-compare ICP); 36 columns (pose.refinement.COLUMN_NAMES) behind whatever the record was, under the name "record_refined".
+    frame (render-and-compare ICP); the record's refinement block (pose.refinement.COLUMN_NAMES), under the name "record_refined".
         A table of pack_refine(silhouette=...) turns the silhouette term on (Options.silhouette): one more launch and 4 bytes per pixel and part."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
@@ -408,22 +418,13 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
         raise ValueError("dense=True labels the raw rows of a stream: it needs raw_capacity")
     if range_guard and arithmetic != "f16x2":
         raise ValueError("range_guard=True needs arithmetic='f16x2' (f32 and bf16x3 have f32's range)")
-    # the streamed record: the pose record, or (fit_quality) the wide record -- its 26 columns and the fit quality behind them --, the
-    # errors against ground truth behind either (ancsh_gt_error_rec), the per-point ground truth's columns behind whatever that was
-    width, key = (quality.FIT_QUALITY_WIDTH, "record_wide") if fit_quality else (26, "record")
-    if ground_truth:
-        width, key = width + gt_errors.GT_ERROR_WIDTH, "record_gt"
-    if point_ground_truth:
-        width, key = width + point_gt.POINT_GT_WIDTH, "record_point_gt"
-    if reprojection:                       # the render-and-compare columns behind whatever that was (ancsh_reproject_compare_rec)
-        width, key = width + reprojection_mod.REPROJECTION_WIDTH, "record_reproj"
-    if refine:                             # the refined poses and their costs behind whatever that was (ancsh_refine_rec)
-        width, key = width + refinement_mod.REFINE_WIDTH, "record_refined"
+    # the streamed record: the blocks these flags build, in pose.record.BLOCKS' order; its width and the name the step leaves it under
+    layout = RecordLayout(fit_quality, ground_truth, point_ground_truth, reprojection, refine)
     rows = None if raw_capacity is None else ROW_KINDS["annotated" if build_point_gt else "point_gt" if point_ground_truth else
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, width, key, 20 if joint_states else 12, rows, (), silhouette, refine)
+                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, 20 if joint_states else 12, rows, (), silhouette, refine)
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +

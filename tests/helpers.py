@@ -48,3 +48,21 @@ def ref_ops(key):
         with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_ops.json")) as f:
             _REF_OPS = json.load(f)
     return _REF_OPS[key]
+
+
+# ---- the streamed record's layout on a prepared pipeline (the GPU stream tests)
+def check_record_layout(pipe, names=None):
+    """A prepared streaming AncshPipeline: in every slot the tensor the record output copies is out[layout.key], layout.width columns wide,
+    every block's carried record is the out[...] entry of that width, and (names) the blocks are these.  -> the layout."""
+    L = pipe.record_layout
+    assert names is None or L.names == tuple(names), L
+    for sl in pipe.slots:
+        for f32 in (False, True) if sl.out32 is not None else (False,):
+            out = sl.pick("out", f32)
+            src = sl.outputs["record"].source(sl, f32)[0]
+            assert src is out[L.key] and src.shape[2] == L.width == sl.record_width == len(L.columns), L
+            assert out["record"].shape[2] == L.span("pose").stop == 26
+            for name in L.names[1:]:
+                key, width = L.carried(name)
+                assert out[key].shape[2] == width == L.span(name).start, (name, key, width)
+    return L

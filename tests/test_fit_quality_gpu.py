@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from fit_quality_mirror import MAX_N, WIDTH, fit_quality_reference, partition, residual_norms
-from helpers import passthrough_pose_problem
+from helpers import check_record_layout, passthrough_pose_problem
 from test_joint_states_cpu import _rotation
 
 pytestmark = pytest.mark.gpu
@@ -260,6 +260,8 @@ def test_stream_keeps_the_record_and_adds_the_quality(dev, slots):
     base = list(_pipe(pb, **kw).stream_batches(batches, articulation=True))
     pipe = _pipe(pb, fit_quality=True, **kw).prepare()
     assert pipe.slots[0].outputs["record"].host[0].shape == (B_, K_, WIDTH) and pipe.slots[0].outputs["record"].host32 is None
+    L = check_record_layout(pipe, ["pose", "fit_quality"])
+    assert (L.width, L.key, L.carried("fit_quality")) == (WIDTH, "record_wide", ("record", 26))
     graphs = [sl.graph for sl in pipe.slots]
     got = []
     for item in pipe.stream_batches(batches, articulation=True):
@@ -271,6 +273,7 @@ def test_stream_keeps_the_record_and_adds_the_quality(dev, slots):
     for (t0, s0, r0, a0), (t1, s1, r1, a1), (clouds, _) in zip(base, got, batches):
         assert (t0, s0) == (t1, s1) and r0.shape == (len(clouds), K_, 26) and r1.shape == (len(clouds), K_, WIDTH)
         assert _same(r0, r1[..., :26]) and _same(a0, a1), t0                                # the record and the articulation / joint-state block
+        assert _same(L.block(r1, "pose"), r1[..., :26]) and _same(L.block(r1, "fit_quality"), r1[..., 26:])
     w5 = got[5][2]
     assert np.isnan(w5[1, :, :26]).all() and np.isnan(w5[1, :, 28:33]).all() and np.isnan(w5[1, :, 34:39]).all()
     assert (w5[:, :, 26].sum(1) == N_).all() and np.isfinite(w5[0, :, 28:39]).all()

@@ -279,12 +279,9 @@ def test_mirror_nan_rules_and_the_wide_record():
 
 
 # ---- the tables --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["eval_scripts.pkl", "eval_scripts_drawer.pkl"])
-def test_stream_tables_print_the_scripts_tables(name):
-    """Rows built from the fixture's records -- the poses of the pickles, the errors the scripts computed from them -- give the lines the
-    product's error_report, miou_report and relative_report give on the same records (and those are pinned against the scripts' own
-    output by tests/test_eval_scripts_cpu.py)."""
-    from articulated_pose_amd.pose import evaluation as EV
+def scripts_rows(name):
+    """The (F, K, 38) streamed rows of a fixture's records -- the poses of the pickles, the errors the scripts computed from them -- and what
+    the tables are compared with: -> (G, K, rows, error_skip, (r_raw, t_raw, iou_rat, r_diff, t_diff))."""
     from test_eval_scripts_cpu import boxes_of, datas_of, loader_of
     with open(os.path.join(HERE, "golden", name), "rb") as f:
         G = pickle.load(f)
@@ -316,7 +313,17 @@ def test_stream_tables_print_the_scripts_tables(name):
                 rows[f, 1:, 30 + 5 * q] = r_diff[key][i]
                 if key == "nonlinear":
                     rows[f, 1:, 36] = t_diff[key][i]
-    lines = EV.stream_tables(rows, K, G["item"], G["domain"], "ANCSH", error_skip=[b.split("_")[0] in skip for b in names])
+    return G, K, rows, [b.split("_")[0] in skip for b in names], (r_raw, t_raw, iou_rat, r_diff, t_diff)
+
+
+@pytest.mark.parametrize("name", ["eval_scripts.pkl", "eval_scripts_drawer.pkl"])
+def test_stream_tables_print_the_scripts_tables(name):
+    """Rows built from the fixture's records -- the poses of the pickles, the errors the scripts computed from them -- give the lines the
+    product's error_report, miou_report and relative_report give on the same records (and those are pinned against the scripts' own
+    output by tests/test_eval_scripts_cpu.py)."""
+    from articulated_pose_amd.pose import evaluation as EV
+    G, K, rows, error_skip, (r_raw, t_raw, iou_rat, r_diff, t_diff) = scripts_rows(name)
+    lines = EV.stream_tables(rows, K, G["item"], G["domain"], "ANCSH", error_skip=error_skip)
     t_want = dict(t_diff, baseline=np.full((len(t_diff["baseline"]), K - 1), np.nan).tolist())      # not streamed for the baseline pose
     want = (EV.error_report(r_raw, t_raw, K, G["domain"], "ANCSH", device="cpu") + EV.miou_report(iou_rat, K, G["domain"], "ANCSH") +
             EV.relative_report(r_diff, t_want, K, G["item"], G["domain"], "ANCSH"))

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import gt_errors_mirror as GM
-from helpers import passthrough_pose_problem
+from helpers import check_record_layout, passthrough_pose_problem
 from redzone import guarded
 from test_gt_errors_cpu import _rotation, make_case
 
@@ -239,6 +239,8 @@ def _check_against_batch_call(pipe, k, rows, gt):
     out = sl.out
     carried = out["record_wide"] if pipe.fit_quality else out["record"]
     ld = carried.shape[2]
+    L = pipe.record_layout
+    assert out[L.carried("gt_errors")[0]] is carried and L.carried("gt_errors")[1] == ld and L.key == "record_gt" and L.width == rows.shape[2]
     assert out["record"].shape == (pipe.B, pipe.K, 26) and out["record_gt"].shape == (pipe.B, pipe.K, ld + 12) == (pipe.B, pipe.K, rows.shape[2])
     n = len(rows)
     dev_gt = sl.gt.cpu().numpy()
@@ -258,11 +260,13 @@ def test_stream_keeps_the_record_and_adds_the_errors(dev, fit_quality):
     pipe = _pipe(pb, fit_quality=fit_quality, ground_truth=True).prepare()
     ld = 39 if fit_quality else 26
     assert pipe.slots[0].outputs["record"].host[0].shape == (B_, K_, ld + 12) and pipe.slots[0].gt.shape == (B_, K_, 19)
+    L = check_record_layout(pipe, ["pose"] + ["fit_quality"] * fit_quality + ["gt_errors"])
     n = 0
     for k, ((t0, s0, r0), (t1, s1, r1)) in enumerate(zip(base, pipe.stream_batches(batches))):
         clouds, _, gt = batches[k]
         assert (t0, s0) == (t1, s1) == (k, 11 + 2 * k) and r1.shape == (len(clouds), K_, ld + 12)
         assert _same(r0, r1[..., :ld])                               # the record (and the fit quality) of the pipeline without the option
+        assert L.width == r1.shape[2] and _same(L.block(r1, "gt_errors"), r1[..., ld:]) and _same(L.block(r1, "pose"), r0[..., :26])
         assert _check_against_batch_call(pipe, k, r1, gt) == ld
         assert (r1[:, :, ld + 11].sum(1) == N_).all()
         if gt is None:

@@ -106,6 +106,17 @@ def test_pack_joint_frame_reads_the_pickle_shapes():
         pack_joint_frame(rt, sc[:2])
 
 
+def point_rows(ld, F=5, K=3):
+    """Hand-made (F, K, ld + 21) streamed rows: the point-gt block behind a carried row of ld columns."""
+    rs = np.random.RandomState(ld)
+    rows = rs.normal(size=(F, K, ld + 21))
+    rows[:, 0, ld:ld + 8] = np.nan
+    rows[2, 1, ld] = np.nan                                              # a NaN angle error: counts as 0
+    rows[4, 2, ld + 1] = np.nan
+    rows[:, :, ld + 12:] = rows[:, :1, ld + 12:]                         # the cloud's losses: the same on every row
+    return rows
+
+
 @pytest.mark.parametrize("ld", [26, 51])
 def test_stream_point_tables_print_the_closing_lines(ld, capsys):
     """Hand-made rows: the joint lines are the reference's closing lines (eval_joint_params.py:262-269, restated here as it prints them: a
@@ -113,13 +124,8 @@ def test_stream_point_tables_print_the_closing_lines(ld, capsys):
     from articulated_pose_amd.loss import format_loss_result
     from articulated_pose_amd.pose.point_gt import stream_point_tables
     from oracle import loss_oracle as LO
-    rs = np.random.RandomState(ld)
     F, K = 5, 3
-    rows = rs.normal(size=(F, K, ld + 21))
-    rows[:, 0, ld:ld + 8] = np.nan
-    rows[2, 1, ld] = np.nan                                              # a NaN angle error: counts as 0
-    rows[4, 2, ld + 1] = np.nan
-    rows[:, :, ld + 12:] = rows[:, :1, ld + 12:]                         # the cloud's losses: the same on every row
+    rows = point_rows(ld, F, K)
     # the reference's lines
     r_diff_arr, t_diff_arr = rows[:, 1:, ld].copy(), rows[:, 1:, ld + 1].copy()
     r_diff_arr[np.where(np.isnan(r_diff_arr))] = 0

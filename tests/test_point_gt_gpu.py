@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import passthrough_pose_problem
+from helpers import check_record_layout, passthrough_pose_problem
 from redzone import guarded
 from test_joint_params_cpu import G as GOLDEN, cases, load
 
@@ -248,6 +248,8 @@ def _check_slot(pipe, k, rows, frame, seed, cloud_base=0, f32=False):
     out = sl.out32 if f32 else sl.out
     carried = out["record_gt"] if pipe.ground_truth else out["record_wide"] if pipe.fit_quality else out["record"]
     ld, n = carried.shape[2], len(rows)
+    L = pipe.record_layout
+    assert out[L.carried("point_gt")[0]] is carried and L.carried("point_gt")[1] == ld and L.key == "record_point_gt" and L.width == rows.shape[2]
     assert out["record"].shape == (pipe.B, pipe.K, 26) and out["record_point_gt"].shape == (pipe.B, pipe.K, ld + W21) == (pipe.B, pipe.K, rows.shape[2])
     dev_fr = sl.frame.cpu().numpy()
     assert np.isnan(dev_fr[n:]).all() and (_same(dev_fr[:n], frame) if frame is not None else np.isnan(dev_fr).all())
@@ -276,10 +278,12 @@ def test_stream_keeps_the_record_and_adds_the_columns(dev, fit_quality, ground_t
     pipe = _pipe(pb, point_ground_truth=True, **kw).prepare()
     ld = 26 + (13 if fit_quality else 0) + (12 if ground_truth else 0)
     assert pipe.slots[0].outputs["record"].host[0].shape == (B_, K_, ld + W21) and pipe.slots[0].raw_rows.shape[1] == 18
+    L = check_record_layout(pipe, ["pose"] + ["fit_quality"] * fit_quality + ["gt_errors"] * ground_truth + ["point_gt"])
     n = 0
     for k, ((t0, s0, r0, a0), (t1, s1, r1, a1)) in enumerate(zip(base, pipe.stream_batches(with_gt(wide, True), articulation=True))):
         assert (t0, s0) == (t1, s1) == (k, 11 + 2 * k) and r1.shape == (len(plain[k][0]), K_, ld + W21)
         assert _same(r0, r1[..., :ld]) and _same(a0, a1)           # the record and the block of the pipeline without the option
+        assert L.width == r1.shape[2] and _same(L.block(r1, "point_gt"), r1[..., ld:]) and _same(L.block(r1, "pose"), r0[..., :26])
         got_ld, want = _check_slot(pipe, k, r1, frames[k], 11 + 2 * k)
         assert got_ld == ld and _same(r1, want)
         assert (r1[:, :, ld + 10].sum(1) <= N_).all() and (r1[:, :, ld + 11].sum(1) == N_).all()

@@ -10,6 +10,7 @@ import torch
 
 import refinement_mirror as RF
 import reprojection_mirror as RP
+from helpers import check_record_layout
 from test_refinement_cpu import MAX_DIST, behavioural_bars, refine_problem, refine_table
 from test_reprojection_cpu import DTYPES, object_links, object_mesh4, posed_object
 from test_reprojection_gpu import B_, CAP_, _bytes, _pipe, _stream_batches, _t
@@ -216,15 +217,22 @@ def _loop_on_device(dev, prob, rec, dtype, table):
 
 
 # ---- the stream -------------------------------------------------------------------------------------------------------------------------------
-def _check_against_eager(got, off, batches, mesh, dtype, K, dev, observed, table, reproj=False):
+def _check_against_eager(got, off, batches, mesh, dtype, K, dev, observed, table, reproj=False, layouts=None):
     """Every retired batch: the 36 columns equal depth.refine_frames on the same tables and the streamed record's own leading columns, byte for
-    byte; every earlier column and every other element of the tuple equal the pipeline built without the option."""
+    byte; every earlier column and every other element of the tuple equal the pipeline built without the option.  layouts = the two
+    pipelines' record_layout: the hand slices below are the layout's blocks."""
     from articulated_pose_amd.depth import refine_frames
+    from articulated_pose_amd.pose.refinement import refined_record
     assert len(got) == len(off) == len(batches)
     for k, (g, o, (crops, nf, ps, rt, sc, rigs)) in enumerate(zip(got, off, batches)):
         rec, W = g[2], o[2].shape[2]
         assert rec.shape == (3, K, W + 36) and g[:2] == o[:2] and len(g) == len(o)
         assert _bytes(rec[:, :, :W], o[2]), k
+        if layouts is not None:
+            L, Lo = layouts
+            assert L.width == rec.shape[2] and Lo.width == W == L.span("refinement").start and L.names == Lo.names + ("refinement",)
+            assert _bytes(L.block(rec, "refinement"), rec[:, :, W:]) and all(_bytes(L.block(rec, n), Lo.block(o[2], n)) for n in Lo.names)
+            assert _bytes(refined_record(rec, layout=L), refined_record(rec))
         assert all(_bytes(a, b) for a, b in zip(g[3:], o[3:])), k
         columns = refine_frames(mesh, rt, sc, rigs, nf, rec[:, :, :W], observed(k, crops, rt, sc, g[1]), dtype, table, device=dev)
         assert _bytes(rec[:, :, W:], columns), (k, rec[:, :, W:], columns)
@@ -251,6 +259,7 @@ def test_posed_keyed_stream_equals_the_eager_operator_and_the_plain_pipeline(dev
         P = _pipe(K, dtype, render_mesh=mesh, kinematics=kin, keyed=True, fit_quality=True, reprojection=True, **(dict(refine=refine) if refine is not None else {}))
         names = _launch_names(P.prepare())
         sl = P.slots[0]
+        L = check_record_layout(P, ("pose", "fit_quality", "point_gt", "reprojection") + (("refinement",) if refine is not None else ()))
         if refine is not None:
             loop = ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_refine_pass"]
             assert names[-10:] == loop * 3 + ["ancsh_refine_rec"], names[-12:]
@@ -259,17 +268,23 @@ def test_posed_keyed_stream_equals_the_eager_operator_and_the_plain_pipeline(dev
             assert sl.refine_bufs[2].shape == (1, B_, K, 2, 32) and all(s.refine_bufs[1].data_ptr() != sl.refine_bufs[1].data_ptr() for s in P.slots[1:])
             assert sl.out["record"].shape == (B_, K, 26) and sl.out["record_refined"].shape == (B_, K, 39 + 21 + 15 + 36)
             assert sl.out["record_reproj"].shape == (B_, K, 39 + 21 + 15)
+            assert (L.width, L.key, L.carried("refinement")) == (39 + 21 + 15 + 36, "record_refined", ("record_reproj", 39 + 21 + 15))
         else:
             assert sl.refine_bufs is None and not any("refine" in n for n in names) and "record_refined" not in sl.out
             assert names == results[0][1][:-10]
-        results.append((list(P.stream_posed_batches(feed, articulation=True, link_counts=True)), names))
+        results.append((list(P.stream_posed_batches(feed, articulation=True, link_counts=True)), names, L))
         del P
     P = _pipe(K, dtype, render_mesh=mesh, kinematics=kin, keyed=True, fit_quality=True)      # neither option: the launches of today
     plain = _launch_names(P.prepare())
     assert plain == results[1][1][:-3] and P.slots[0].reproj_pix is None
     del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(mesh, rt, crops, dtype, dev)
-    _check_against_eager(results[0][0], results[1][0], batches, mesh, dtype, K, dev, observed, table)
+    _check_against_eager(results[0][0], results[1][0], batches, mesh, dtype, K, dev, observed, table, layouts=(results[0][2], results[1][2]))
+    # reprojection's block lies in front of the refinement's: named through the layout it is the other pipeline's trailing 15 columns
+    from articulated_pose_amd.pose.reprojection import named_columns
+    for g, o in zip(results[0][0], results[1][0]):
+        a, b = named_columns(results[0][2].block(g[2], "reprojection")), named_columns(o[2])
+        assert all(_bytes(a[n], b[n]) for n in a)
 
 
 def test_rendered_stream_with_a_sensor_refines_on_the_degraded_frame(dev):
@@ -284,14 +299,15 @@ def test_rendered_stream_with_a_sensor_refines_on_the_degraded_frame(dev):
     table = refine_table(iters=1, max_dist=0.1)
     batches = _stream_batches(rs, K, dtype, kin, mesh, dev)
     feed = [(crops, nf, dict(render=rt, scene=sc, rig=rigs, seed=900 + 5 * k), "t%d" % k) for k, (crops, nf, ps, rt, sc, rigs) in enumerate(batches)]
-    results = []
+    results, layouts = [], []
     for refine in (table, None):
         P = _pipe(K, dtype, render_mesh=mesh, sensor=sensor, **(dict(refine=refine) if refine is not None else {}))
         results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
         assert (P.slots[0].reproj_pix is not None) == (refine is not None)
+        layouts.append(check_record_layout(P, ("pose", "point_gt") + (("refinement",) if refine is not None else ())))
         del P
     observed = lambda k, crops, rt, sc, seed: sensor_frames(render_depth_frames(mesh, rt, crops, dtype, dev), sc, sensor, dtype, seed=seed, device=dev)
-    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, table)
+    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, table, layouts=layouts)
 
 
 def test_library_stream_equals_the_eager_operator(dev):
@@ -316,6 +332,7 @@ def test_library_stream_equals_the_eager_operator(dev):
         sl = P.slots[0]
         assert sl.graph32 is not None and ("record_refined" in sl.out32) == on and ("record_refined" in sl.out) == on
         assert not on or sl.out32["record_refined"].shape == sl.out["record_refined"].shape == (B_, K, 26 + 21 + 36)
+        assert check_record_layout(P).width == 26 + 21 + (36 if on else 0)      # the f32 graph's record too
         del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(lib, rt, crops, dtype, dev)
     _check_against_eager(results[0], results[1], batches, lib, dtype, K, dev, observed, table)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import reprojection_mirror as RP
+from helpers import check_record_layout
 from test_reprojection_cpu import (DTYPES, MAPS, SCALE, SIZES, crop_origins, frames_problem, object_links, object_mesh4, posed_object, poses,
                                    predicted_frames, random_rigs)
 
@@ -227,11 +228,12 @@ def _stream_batches(rs, K, dtype, kin, mesh, dev, nbatches=3):
     return out
 
 
-def _check_against_eager(got, off, batches, mesh, dtype, K, dev, observed):
+def _check_against_eager(got, off, batches, mesh, dtype, K, dev, observed, layouts=None):
     """Every retired batch: the 15 columns equal depth.reprojection_frames on the same tables and the streamed record's own leading columns,
     byte for byte; every earlier column and every other element of the tuple equal the pipeline built without the option; n_obs equals the
-    stream's per-part pixel counts from link_counts."""
+    stream's per-part pixel counts from link_counts.  layouts = the two pipelines' record_layout: the hand slices are the layout's blocks."""
     from articulated_pose_amd.depth import reprojection_frames
+    from articulated_pose_amd.pose.reprojection import named_columns
     assert len(got) == len(off) == len(batches)
     seen = 0
     for k, (g, o, (crops, nf, ps, rt, sc, rigs)) in enumerate(zip(got, off, batches)):
@@ -239,6 +241,11 @@ def _check_against_eager(got, off, batches, mesh, dtype, K, dev, observed):
         W = o[2].shape[2]
         assert rec.shape == (3, K, W + 15) and g[:2] == o[:2] and len(g) == len(o)
         assert _bytes(rec[:, :, :W], o[2]), k
+        if layouts is not None:
+            L, Lo = layouts
+            assert L.width == rec.shape[2] and Lo.width == W == L.span("reprojection").start and L.names == Lo.names + ("reprojection",)
+            assert _bytes(L.block(rec, "reprojection"), rec[:, :, W:]) and all(_bytes(L.block(rec, n), Lo.block(o[2], n)) for n in Lo.names)
+            assert _bytes(named_columns(L.block(rec, "reprojection"))["n_obs"], rec[:, :, W]) and L.column("reprojection", "n_obs") == W
         assert all(_bytes(a, b) for a, b in zip(g[3:], o[3:])), k
         columns, pred = reprojection_frames(mesh, rt, sc, rigs, nf, rec[:, :, :W], observed(k, crops, rt, sc, g[1]), dtype, dev)
         assert _bytes(rec[:, :, W:], columns), (k, rec[:, :, W:], columns)
@@ -268,19 +275,21 @@ def test_posed_keyed_stream_equals_the_eager_chain_and_the_plain_pipeline(dev):
         P = _pipe(K, dtype, render_mesh=mesh, kinematics=kin, keyed=True, fit_quality=True, reprojection=on)
         names = _launch_names(P.prepare())
         sl = P.slots[0]
+        L = check_record_layout(P, ("pose", "fit_quality", "point_gt") + (("reprojection",) if on else ()))
         if on:
             assert names[-3:] == ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_reproject_compare_rec"], names[-5:]
             assert sl.reproj_tables[0].shape == (2 * B_, 208) and sl.reproj_tables[1].shape == (2 * B_, 5)
             assert [tuple(t.shape) for t in sl.reproj_pix] == [(2 * CAP_,)] * 3 and sl.reproj_pix[2].dtype == torch.int64
             assert all(s.reproj_pix[0].data_ptr() != sl.reproj_pix[0].data_ptr() for s in P.slots[1:])
             assert sl.out["record"].shape == (B_, K, 26) and sl.out["record_reproj"].shape == (B_, K, 39 + 21 + 15)
+            assert (L.width, L.key, L.carried("reprojection")) == (39 + 21 + 15, "record_reproj", ("record_point_gt", 39 + 21))
         else:
             assert sl.reproj_pix is None and not any("reproject" in n for n in names) and "record_reproj" not in sl.out
             assert names == results[0][1][:-3]
-        results.append((list(P.stream_posed_batches(feed, articulation=True, link_counts=True)), names))
+        results.append((list(P.stream_posed_batches(feed, articulation=True, link_counts=True)), names, L))
         del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(mesh, rt, crops, dtype, dev)
-    _check_against_eager(results[0][0], results[1][0], batches, mesh, dtype, K, dev, observed)
+    _check_against_eager(results[0][0], results[1][0], batches, mesh, dtype, K, dev, observed, layouts=(results[0][2], results[1][2]))
 
 
 def test_rendered_stream_with_a_sensor_compares_against_the_degraded_frame(dev):
@@ -294,13 +303,14 @@ def test_rendered_stream_with_a_sensor_compares_against_the_degraded_frame(dev):
     table = pack_sensor(sigma=(0.002, 0.001, 0.0), z0=1.0, p_hole=0.2, p_edge=0.5, edge_rel=0.05)
     batches = _stream_batches(rs, K, dtype, kin, mesh, dev)
     feed = [(crops, nf, dict(render=rt, scene=sc, rig=rigs, seed=900 + 5 * k), "t%d" % k) for k, (crops, nf, ps, rt, sc, rigs) in enumerate(batches)]
-    results = []
+    results, layouts = [], []
     for on in (True, False):
         P = _pipe(K, dtype, render_mesh=mesh, sensor=table, reprojection=on)
         results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
+        layouts.append(check_record_layout(P, ("pose", "point_gt") + (("reprojection",) if on else ())))
         del P
     observed = lambda k, crops, rt, sc, seed: sensor_frames(render_depth_frames(mesh, rt, crops, dtype, dev), sc, table, dtype, seed=seed, device=dev)
-    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed)
+    _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, layouts=layouts)
     clean = render_depth_frames(mesh, batches[0][3], batches[0][0], dtype, dev)
     noisy = observed(0, batches[0][0], batches[0][3], batches[0][4], results[0][0][1])
     assert sum(int((l != 255).sum()) for _, l, _ in noisy) < sum(int((l != 255).sum()) for _, l, _ in clean)
@@ -327,6 +337,7 @@ def test_library_stream_equals_the_eager_chain(dev):
         sl = P.slots[0]                                                  # the range guard's f32 graph ends with the same three calls
         assert sl.graph32 is not None and ("record_reproj" in sl.out32) == on and ("record_reproj" in sl.out) == on
         assert not on or sl.out32["record_reproj"].shape == sl.out["record_reproj"].shape == (B_, K, 26 + 21 + 15)
+        assert check_record_layout(P).width == 26 + 21 + (15 if on else 0)      # the f32 graph's record too
         del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(lib, rt, crops, dtype, dev)
     _check_against_eager(results[0], results[1], batches, lib, dtype, K, dev, observed)
