@@ -187,6 +187,9 @@ SIGNATURES = {
     "ancsh_silhouette_field": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
     "ancsh_refine_pass_sil": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 9 + [_c_int, _c_int, _vp, _c_int,
                               _vp, _vp, _vp, _vp],
+    # the joint step (no ABI bump, detected by its symbol): nframes, K, kin, ninst, scene, pred_render, norm_factor, params, pass, is_last,
+    # pose_in, ld_in, sums, sums_ld, pose_out, best, state, obj, xi, stream
+    "ancsh_refine_joint_step": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int] + [_vp] * 6,
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

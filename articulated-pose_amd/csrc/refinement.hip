@@ -11,6 +11,9 @@
 // The silhouette term, two more entries: ancsh_silhouette_field (ONE launch in front of the loop: per crop pixel and part the offset to the
 // nearest pixel observed for the part) and ancsh_refine_pass_sil (the pass kernel's SIL instance: a predicted pixel of the part where the
 // camera saw neither the part nor anything nearer adds one row that pulls it towards that nearest observed pixel, and is charged in the cost).
+// The joint step, one more entry: ancsh_refine_joint_step (ONE launch behind each pass, one wave per (pose, frame): the parts' normal
+// equations from `sums` and the rows that keep each revolute and prismatic joint's two sides on one axis, solved together by Cholesky in
+// LDS; the poses and the best block the pass wrote are overwritten, the best-of is kept per object).  The pass kernel does not know of it.
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
 #include "depth_annotate_common.h"
 
@@ -43,6 +46,32 @@ __device__ __forceinline__ void rf_cloud(double x, double y, double z, double nf
     o[0] = nf * x;
     o[1] = nf * (-y);
     o[2] = nf * z;
+}
+
+// the tail of a step, shared by the pass and the joint step: xi = (w, dt) as clamped -> the unit quaternion of w, its matrix, and the pose
+// turned about the centre c and moved by dt; s is carried
+__device__ __forceinline__ void rf_pose_step(const double *xi, const double *__restrict__ pose, const double *c, double *out) {
+    const double hx = xi[0] / 2.0, hy = xi[1] / 2.0, hz = xi[2] / 2.0;  // the unit quaternion (1, w / 2) / |(1, w / 2)|
+    const double qn = sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
+    const double w = 1.0 / qn, x = hx / qn, yq = hy / qn, z = hz / qn;
+    double dR[9];
+    dR[0] = 1.0 - 2.0 * (yq * yq + z * z);
+    dR[1] = 2.0 * (x * yq - w * z);
+    dR[2] = 2.0 * (x * z + w * yq);
+    dR[3] = 2.0 * (x * yq + w * z);
+    dR[4] = 1.0 - 2.0 * (x * x + z * z);
+    dR[5] = 2.0 * (yq * z - w * x);
+    dR[6] = 2.0 * (x * z - w * yq);
+    dR[7] = 2.0 * (yq * z + w * x);
+    dR[8] = 1.0 - 2.0 * (x * x + yq * yq);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[3 * a + k] = (dR[3 * a] * pose[k] + dR[3 * a + 1] * pose[3 + k]) + dR[3 * a + 2] * pose[6 + k];
+    out[9] = pose[9];
+    const double u[3] = {pose[10] - c[0], pose[11] - c[1], pose[12] - c[2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[10 + a] = (rf_dot(dR + 3 * a, u) + c[a]) + xi[3 + a];
 }
 
 // the 6 x 6 solve, the clamp, the quaternion and the update of one pose, all by one thread in the header's written order.  S = the block's
@@ -97,27 +126,7 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
 #pragma unroll
         for (int k = 0; k < 6; ++k) xi[k] = xi[k] * f;
     }
-    const double hx = xi[0] / 2.0, hy = xi[1] / 2.0, hz = xi[2] / 2.0;  // the unit quaternion (1, w / 2) / |(1, w / 2)|
-    const double qn = sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
-    const double w = 1.0 / qn, x = hx / qn, yq = hy / qn, z = hz / qn;
-    double dR[9];
-    dR[0] = 1.0 - 2.0 * (yq * yq + z * z);
-    dR[1] = 2.0 * (x * yq - w * z);
-    dR[2] = 2.0 * (x * z + w * yq);
-    dR[3] = 2.0 * (x * yq + w * z);
-    dR[4] = 1.0 - 2.0 * (x * x + z * z);
-    dR[5] = 2.0 * (yq * z - w * x);
-    dR[6] = 2.0 * (x * z - w * yq);
-    dR[7] = 2.0 * (yq * z + w * x);
-    dR[8] = 1.0 - 2.0 * (x * x + yq * yq);
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[3 * a + k] = (dR[3 * a] * pose[k] + dR[3 * a + 1] * pose[3 + k]) + dR[3 * a + 2] * pose[6 + k];
-    out[9] = pose[9];
-    const double u[3] = {pose[10] - c[0], pose[11] - c[1], pose[12] - c[2]};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[10 + a] = (rf_dot(dR + 3 * a, u) + c[a]) + xi[3 + a];
+    rf_pose_step(xi, pose, c, out);
     return true;
 }
 
@@ -440,6 +449,307 @@ __global__ __launch_bounds__(SF_THREADS) void silhouette_field_kernel(int K, con
     }
 }
 
+// ancsh_refine_joint_step: the parts of one object solved together through their joints, ONE wave per (pose v, frame f), launched behind the
+// pass.  The pass left every part's 6 x 6 normal equations in `sums`; this kernel adds the rows that keep each revolute or prismatic joint's
+// two sides on one axis, solves the 6 K system by Cholesky in LDS, clamps the step by one factor, overwrites the poses the pass wrote, and keeps
+// the best-of per OBJECT (state: its shadow of the best block; obj: the object's row).  include/ancsh_hip.h states every formula and order.
+constexpr int JS_THREADS = 64, JS_PARTS = 8, JS_N = 6 * JS_PARTS, JS_LD = JS_N + 1, JS_ROWS = 9, JS_COLS = 12, JS_OBJ = ANCSH_REFINE_OBJ;
+
+// link map l of a render table: x (model frame) -> the scaled cloud, nf * F (R x + t)
+__device__ __forceinline__ void js_point(const double *__restrict__ R, const double *x, double nf, double *o) {
+    double m[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) m[b] = ((R[4 * b] * x[0] + R[4 * b + 1] * x[1]) + R[4 * b + 2] * x[2]) + R[4 * b + 3];
+    rf_cloud(m[0], m[1], m[2], nf, o);
+}
+
+// ... a direction: normalise(F R d); false: its length is 0 or not finite
+__device__ __forceinline__ bool js_dir(const double *__restrict__ R, const double *d, double *o) {
+    double m[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) m[b] = (R[4 * b] * d[0] + R[4 * b + 1] * d[1]) + R[4 * b + 2] * d[2];
+    m[1] = -m[1];
+    const double len = sqrt(rf_dot(m, m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) o[b] = m[b] / len;
+    return len > 0.0 && rf_finite(len);
+}
+
+// three rows r0 + G xi of one joint into LDS: G = sc [-[e]x | id I] for the child's part (columns 0..5), sc [[h]x | -id I] for the parent's
+__device__ __forceinline__ void js_rows(double (*G)[JS_COLS], double *r0, const double *e, const double *h, const double *r, double sc, double id) {
+    const double ea[3] = {sc * e[0], sc * e[1], sc * e[2]}, ha[3] = {sc * h[0], sc * h[1], sc * h[2]};
+    G[0][0] = 0.0, G[0][1] = ea[2], G[0][2] = -ea[1], G[1][0] = -ea[2], G[1][1] = 0.0, G[1][2] = ea[0], G[2][0] = ea[1], G[2][1] = -ea[0], G[2][2] = 0.0;
+    G[0][6] = 0.0, G[0][7] = -ha[2], G[0][8] = ha[1], G[1][6] = ha[2], G[1][7] = 0.0, G[1][8] = -ha[0], G[2][6] = -ha[1], G[2][7] = ha[0], G[2][8] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) G[a][3 + k] = a == k ? id : 0.0, G[a][9 + k] = a == k ? -id : 0.0;
+        r0[a] = sc * r[a];
+    }
+}
+
+__global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nframes, int K, const double *__restrict__ kin, int ninst,
+                                                                       const double *__restrict__ scene, const double *__restrict__ pred_render,
+                                                                       const float *__restrict__ norm_factor, const double *__restrict__ params,
+                                                                       int pass, int is_last, const double *__restrict__ pose_in, int ld_in,
+                                                                       const double *__restrict__ sums, int sums_ld, double *__restrict__ pose_out,
+                                                                       double *__restrict__ best, double *__restrict__ state,
+                                                                       double *__restrict__ obj, double *__restrict__ xi_out) {
+    __shared__ double s_H[JS_N][JS_LD], s_g[JS_N], s_x[JS_N];           // 48 x 49 doubles: 18.4 KB; the odd row length spreads a column over the banks
+    __shared__ double s_G[RF_LINKS][JS_ROWS][JS_COLS], s_r0[RF_LINKS][JS_ROWS], s_rr[RF_LINKS], s_gap[RF_LINKS];      // 13.5 KB
+    __shared__ double s_c[JS_PARTS][3], s_n[JS_PARTS];
+    __shared__ int s_part[RF_LINKS], s_live[JS_PARTS], s_rows[RF_LINKS], s_pa[RF_LINKS], s_pb[RF_LINKS], s_fail;
+    const int v = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, n = 6 * K;
+    const double *sc = scene + (size_t)f * AN_SCENE, *rt = pred_render + ((size_t)v * nframes + f) * RF_RENDER;
+    const double nf = (double)norm_factor[f], qnan = __builtin_nan("");
+    const double max_dist = params[1], damping = params[3], max_angle = params[4], min_pixels = params[5], weight = params[16], axis_len = params[17];
+    const bool nf_ok = rf_finite(nf) && nf != 0.0;
+    const size_t part0 = ((size_t)f * K) * 2 + v;                       // part j's row of best, state and sums: (part0 + 2 j) * its width
+    if (tid < RF_LINKS) {                                               // the pass kernel's rule
+        const int nl = scene_nlinks(sc);
+        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
+        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
+        s_rows[tid] = 0;
+        s_rr[tid] = s_gap[tid] = 0.0;
+    }
+    if (tid == 0) s_fail = 0;
+    if (tid < JS_PARTS) {
+        bool live = false;
+        double nj = 0.0;
+        if (tid < K) {
+            const double *pose = pose_in + ((size_t)f * K + tid) * ld_in + 13 * v, *S = sums + (part0 + 2 * (size_t)tid) * sums_ld;
+            live = nf_ok && rf_pose_ok(pose);
+            if (live) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) s_c[tid][a] = pose[9] * ((pose[3 * a] * 0.5 + pose[3 * a + 1] * 0.5) + pose[3 * a + 2] * 0.5) + pose[10 + a];
+                nj = S[28];
+                if (sums_ld == RF_SIL_SUMS) nj = nj + S[33];
+            }
+        }
+        s_live[tid] = live ? 1 : 0;
+        s_n[tid] = nj;
+    }
+    __syncthreads();
+    // nbar: the mean rows of the live parts that solve on their own
+    double nsum = 0.0, ncount = 0.0;
+    for (int j = 0; j < K; ++j)
+        if (s_live[j] && s_n[j] >= min_pixels) nsum = nsum + s_n[j], ncount = ncount + 1.0;
+    const bool has_nbar = ncount > 0.0;
+    const double w2n = has_nbar ? (weight * weight) * (nsum / ncount) : 0.0;
+    // lane l: link l's joint.  Every index read from a table is checked before it is used
+    const int nl = scene_nlinks(sc);
+    const double iv = rt[9];
+    const int inst = iv >= 0.0 && iv < (double)ninst && (double)(int)iv == iv ? (int)iv : -1;
+    if (tid >= 1 && tid < nl && inst >= 0) {
+        const int l = tid;
+        const double *kl = kin + (size_t)inst * ANCSH_KIN_WIDTH + ANCSH_KIN_HEAD + ANCSH_KIN_LINK * l;
+        const double pd = kl[2], kd = kl[3];
+        const int p = pd >= 0.0 && pd < (double)l && (double)(int)pd == pd ? (int)pd : -1;
+        const int a = s_part[l], b = p >= 0 ? s_part[p] : -1;
+        if ((kd == 1.0 || kd == 2.0) && a >= 0 && b >= 0 && a != b && s_live[a] && s_live[b]) {
+            const double *Rl = rt + ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l, *Rp = rt + ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * p, *T = kl + 4;
+            const double zero[3] = {0.0, 0.0, 0.0}, org[3] = {T[3], T[7], T[11]}, ax[3] = {kl[16], kl[17], kl[18]};
+            double xc[3], xp[3], uc[3], up[3], axp[3];
+            js_point(Rl, zero, nf, xc);
+            js_point(Rp, org, nf, xp);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) axp[i] = (T[4 * i] * ax[0] + T[4 * i + 1] * ax[1]) + T[4 * i + 2] * ax[2];
+            bool ok = js_dir(Rl, ax, uc);
+            ok = js_dir(Rp, axp, up) && ok;
+            const double e[3] = {xc[0] - s_c[a][0], xc[1] - s_c[a][1], xc[2] - s_c[a][2]};
+            const double h[3] = {xp[0] - s_c[b][0], xp[1] - s_c[b][1], xp[2] - s_c[b][2]};
+            const double r[3] = {xc[0] - xp[0], xc[1] - xp[1], xc[2] - xp[2]}, du[3] = {uc[0] - up[0], uc[1] - up[1], uc[2] - up[2]};
+            double(*G)[JS_COLS] = s_G[l];
+            double *r0 = s_r0[l];
+            int rows = 6;
+            js_rows(G, r0, e, h, r, 1.0, 1.0);
+            js_rows(G + 3, r0 + 3, uc, up, du, axis_len, 0.0);
+            if (kd == 2.0) {                                            // prismatic: the position rows projected off the axis, a second direction
+                double P[3][3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) P[i][k] = (i == k ? 1.0 : 0.0) - up[i] * up[k];
+                for (int cidx = 0; cidx <= JS_COLS; ++cidx) {           // column 12: the residual
+                    const double g0 = cidx < JS_COLS ? G[0][cidx] : r0[0], g1 = cidx < JS_COLS ? G[1][cidx] : r0[1], g2 = cidx < JS_COLS ? G[2][cidx] : r0[2];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double pg = (P[i][0] * g0 + P[i][1] * g1) + P[i][2] * g2;
+                        if (cidx < JS_COLS) G[i][cidx] = pg;
+                        else r0[i] = pg;
+                    }
+                }
+                const double a0 = fabs(ax[0]), a1 = fabs(ax[1]), a2 = fabs(ax[2]);
+                const int k = a1 < a0 ? (a2 < a1 ? 2 : 1) : (a2 < a0 ? 2 : 0);                // the smallest |a_k|, ties: the lowest index
+                const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+                double bx[3] = {ax[1] * ek[2] - ax[2] * ek[1], ax[2] * ek[0] - ax[0] * ek[2], ax[0] * ek[1] - ax[1] * ek[0]}, bxp[3], vc[3], vp[3];
+                const double bl = sqrt(rf_dot(bx, bx));
+                ok = ok && bl > 0.0 && rf_finite(bl);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) bx[i] = bx[i] / bl;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) bxp[i] = (T[4 * i] * bx[0] + T[4 * i + 1] * bx[1]) + T[4 * i + 2] * bx[2];
+                ok = js_dir(Rl, bx, vc) && ok;
+                ok = js_dir(Rp, bxp, vp) && ok;
+                const double dv[3] = {vc[0] - vp[0], vc[1] - vp[1], vc[2] - vp[2]};
+                js_rows(G + 6, r0 + 6, vc, vp, dv, axis_len, 0.0);
+                rows = 9;
+            }
+            double rr = 0.0;
+            for (int i = 0; i < rows; ++i) {
+                ok = ok && rf_finite(r0[i]);
+                rr = rr + r0[i] * r0[i];
+            }
+            if (ok) {                                                   // a joint whose rows are not finite is not active
+                s_rows[l] = rows;
+                s_pa[l] = a;
+                s_pb[l] = b;
+                s_rr[l] = rr;
+                s_gap[l] = rf_dot(r0, r0);
+            }
+        }
+    }
+    __syncthreads();
+    double njoints = 0.0, sumr = 0.0, gap = 0.0;
+    for (int l = 1; l < RF_LINKS; ++l)
+        if (s_rows[l]) njoints = njoints + 1.0, sumr = sumr + s_rr[l], gap = gap + s_gap[l];
+    // the object's cost
+    double num = 0.0, den = 0.0, moved = 0.0;
+    for (int j = 0; j < K; ++j) {
+        if (!s_live[j]) continue;
+        const double *S = sums + (part0 + 2 * (size_t)j) * sums_ld;
+        if (S[29] > 0.0) num = num + S[30] * S[29], den = den + S[29];
+        if (S[31] == 1.0) moved = 1.0;
+    }
+    const bool coupled = njoints > 0.0 && has_nbar;
+    if (coupled) num = num + w2n * sumr;
+    const double Cobj = den > 0.0 ? num / den : qnan;
+    bool solved = false;
+    double fclamp = 1.0;
+    if (coupled && !is_last) {                                          // uniform over the wave
+        for (int e = tid; e < JS_N * JS_LD; e += JS_THREADS) (&s_H[0][0])[e] = 0.0;
+        __syncthreads();
+        for (int e = tid; e < 36 * K; e += JS_THREADS) {                // the parts' own blocks, damped as the pass damps them
+            const int j = e / 36, a = (e % 36) / 6, b = e % 6, lo = a < b ? a : b, hi = a < b ? b : a;
+            const double *S = sums + (part0 + 2 * (size_t)j) * sums_ld;
+            double h = a == b ? 1.0 : 0.0;
+            if (s_live[j]) {
+                h = s_n[j] >= min_pixels ? S[6 * lo - (lo * (lo - 1)) / 2 + (hi - lo)] : 0.0;
+                if (a == b) h = h + (damping * h + 1e-12);
+            }
+            s_H[6 * j + a][6 * j + b] = h;
+        }
+        if (tid < n) {
+            const int j = tid / 6;
+            s_g[tid] = s_live[j] && s_n[j] >= min_pixels ? sums[(part0 + 2 * (size_t)j) * sums_ld + 21 + tid % 6] : 0.0;
+        }
+        __syncthreads();
+        for (int l = 1; l < RF_LINKS; ++l) {                            // + weight^2 nbar G^T G, joint after joint; an element's rows in order
+            const int rows = s_rows[l];
+            if (!rows) continue;
+            const int a = s_pa[l], b = s_pb[l];
+            for (int e = tid; e < JS_COLS * JS_COLS + JS_COLS; e += JS_THREADS) {
+                const int p = e / JS_COLS, q = e % JS_COLS;
+                double t = 0.0;
+                if (p < JS_COLS) {
+                    for (int r = 0; r < rows; ++r) t = t + s_G[l][r][p] * s_G[l][r][q];
+                    double *h = &s_H[p < 6 ? 6 * a + p : 6 * b + (p - 6)][q < 6 ? 6 * a + q : 6 * b + (q - 6)];
+                    *h = *h + w2n * t;
+                } else {
+                    for (int r = 0; r < rows; ++r) t = t + s_G[l][r][q] * s_r0[l][r];
+                    double *g = &s_g[q < 6 ? 6 * a + q : 6 * b + (q - 6)];
+                    *g = *g + w2n * t;
+                }
+            }
+            __syncthreads();
+        }
+        for (int jc = 0; jc < n; ++jc) {                                // Cholesky in place, column after column; lane i owns row i
+            double s = 0.0;
+            if (tid >= jc && tid < n) {
+                s = s_H[tid][jc];
+                for (int k = 0; k < jc; ++k) s = s - s_H[tid][k] * s_H[jc][k];
+                if (tid == jc) {
+                    if (!(s > 0.0 && rf_finite(s))) s_fail = 1;
+                    s_H[jc][jc] = sqrt(s);
+                }
+            }
+            __syncthreads();
+            if (tid > jc && tid < n) s_H[tid][jc] = s / s_H[jc][jc];
+            __syncthreads();
+        }
+        double s = tid < n ? 0.0 - s_g[tid] : 0.0;                      // L y = -g: y_k as soon as it is final, k ascending
+        for (int k = 0; k < n; ++k) {
+            if (tid == k) s_x[k] = s / s_H[k][k];
+            __syncthreads();
+            if (tid > k && tid < n) s = s - s_H[tid][k] * s_x[k];
+        }
+        __syncthreads();
+        s = tid < n ? s_x[tid] : 0.0;                                   // L^T xi = y: xi_k as soon as it is final, k descending
+        __syncthreads();
+        for (int k = n - 1; k >= 0; --k) {
+            if (tid == k) s_x[k] = s / s_H[k][k];
+            __syncthreads();
+            if (tid < k) s = s - s_H[k][tid] * s_x[k];
+        }
+        __syncthreads();
+        solved = !s_fail;
+        for (int k = 0; k < n; ++k) solved = solved && rf_finite(s_x[k]);
+        if (solved) {
+            for (int j = 0; j < K; ++j) {                               // one factor for the whole object
+                if (!s_live[j]) continue;
+                const double wn = sqrt(rf_dot(s_x + 6 * j, s_x + 6 * j)), dn = sqrt(rf_dot(s_x + 6 * j + 3, s_x + 6 * j + 3));
+                if (wn > max_angle && max_angle / wn < fclamp) fclamp = max_angle / wn;
+                if (dn > max_dist && max_dist / dn < fclamp) fclamp = max_dist / dn;
+            }
+            if (tid < K && s_live[tid]) {
+                const double *pose = pose_in + ((size_t)f * K + tid) * ld_in + 13 * v;
+                double xi[6], nw[13];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) xi[k] = fclamp < 1.0 ? s_x[6 * tid + k] * fclamp : s_x[6 * tid + k];
+                rf_pose_step(xi, pose, s_c[tid], nw);
+                double *po = pose_out + ((size_t)f * K + tid) * 26 + 13 * v;
+#pragma unroll
+                for (int k = 0; k < 13; ++k) po[k] = nw[k];
+            }
+        }
+    }
+    if (xi_out && tid < JS_N) xi_out[((size_t)f * 2 + v) * JS_N + tid] = solved && tid < n ? (fclamp < 1.0 ? s_x[tid] * fclamp : s_x[tid]) : 0.0;
+    if (solved) moved = 1.0;
+    // best-of, per object: every lane reads the object's row before lane 0 rewrites it
+    double *ob = obj + ((size_t)f * 2 + v) * JS_OBJ;
+    const double cost_start = pass == 0 ? Cobj : ob[0], cost_best = pass == 0 ? Cobj : ob[1], prev_pass = pass == 0 ? 0.0 : ob[2];
+    const double prev_solved = pass == 0 ? 0.0 : ob[3];
+    const bool take = pass == 0 || Cobj < cost_best;                    // strictly lower: ties stay with the earlier pass; NaN never wins
+    const double best_pass = take ? (double)pass : prev_pass, passes_solved = prev_solved + moved;
+    __syncthreads();
+    if (tid == 0) {
+        ob[0] = cost_start;
+        ob[1] = take ? Cobj : cost_best;
+        ob[2] = best_pass;
+        ob[3] = passes_solved;
+        ob[4] = Cobj;
+        ob[5] = njoints;
+        ob[6] = solved ? 1.0 : 0.0;
+        ob[7] = njoints > 0.0 ? sqrt(gap / njoints) : qnan;
+    }
+    if (tid < K) {
+        const double *pose = pose_in + ((size_t)f * K + tid) * ld_in + 13 * v, *S = sums + (part0 + 2 * (size_t)tid) * sums_ld;
+        double *st = state + (part0 + 2 * (size_t)tid) * RF_BEST, *bb = best + (part0 + 2 * (size_t)tid) * RF_BEST;
+        const bool live = s_live[tid] != 0;
+        if (take) {
+#pragma unroll
+            for (int k = 0; k < 13; ++k) st[k] = pose[k];
+            if (pass == 0) st[13] = live ? S[30] : qnan;
+            st[14] = live ? S[30] : qnan;
+            st[15] = live ? S[28] : qnan;
+        }
+        st[16] = best_pass;
+        st[17] = passes_solved;
+#pragma unroll
+        for (int k = 0; k < RF_BEST; ++k) bb[k] = live ? st[k] : qnan;   // a part that is not live reads NaN, as the pass leaves it
+    }
+}
+
 }  // namespace ancsh
 
 using namespace ancsh;
@@ -507,6 +817,35 @@ extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const f
     return refine_pass_call<true>("refine_pass_sil", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
                                   pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, pass, is_last,
                                   pose_in, ld_in, pose_out, best, sums, stream);
+}
+
+extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, int ninst, const double *scene, const double *pred_render,
+                                       const float *norm_factor, const double *params, int pass, int is_last, const double *pose_in, int ld_in,
+                                       const double *sums, int sums_ld, double *pose_out, double *best, double *state, double *obj, double *xi,
+                                       void *stream) {
+    ANCSH_REQUIRE(nframes >= 0, "refine_joint_step: bad shape nframes=%d", nframes);
+    ANCSH_REQUIRE(nframes <= 32767, "refine_joint_step: %d frames exceed the 32767-frame range of ancsh_refine_pass; split the batch", nframes);
+    ANCSH_REQUIRE(K >= 1 && K <= 8, "refine_joint_step: K=%d must be in [1, 8]", K);
+    ANCSH_REQUIRE(ninst >= 1 && ninst <= 65535, "refine_joint_step: ninst=%d kinematic tables must be in [1, 65535]", ninst);
+    ANCSH_REQUIRE(pass >= 0 && pass <= ANCSH_REFINE_MAX_ITERS, "refine_joint_step: pass=%d must be in [0, %d]", pass, ANCSH_REFINE_MAX_ITERS);
+    ANCSH_REQUIRE(is_last == 0 || is_last == 1, "refine_joint_step: is_last=%d must be 0 or 1", is_last);
+    ANCSH_REQUIRE(ld_in >= 26, "refine_joint_step: ld_in=%d, a record row holds at least the 26 pose columns", ld_in);
+    ANCSH_REQUIRE(sums_ld == ANCSH_REFINE_SUMS || sums_ld == ANCSH_REFINE_SIL_SUMS, "refine_joint_step: sums_ld=%d must be %d (ancsh_refine_pass) or %d "
+                  "(ancsh_refine_pass_sil)", sums_ld, ANCSH_REFINE_SUMS, ANCSH_REFINE_SIL_SUMS);
+    ANCSH_REQUIRE(kin && scene && pred_render && norm_factor && params && pose_in && sums && pose_out && best && state && obj,
+                  "refine_joint_step: null pointer");
+    ANCSH_REQUIRE(((size_t)kin & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)pred_render & 7) == 0 && ((size_t)norm_factor & 3) == 0 &&
+                      ((size_t)params & 7) == 0 && ((size_t)pose_in & 7) == 0 && ((size_t)sums & 7) == 0 && ((size_t)pose_out & 7) == 0 &&
+                      ((size_t)best & 7) == 0 && ((size_t)state & 7) == 0 && ((size_t)obj & 7) == 0 && ((size_t)xi & 7) == 0,
+                  "refine_joint_step: norm_factor must be 4-byte, kin, scene, pred_render, params, pose_in, sums, pose_out, best, state, obj and xi "
+                  "8-byte aligned");
+    ANCSH_REQUIRE(pose_in != pose_out, "refine_joint_step: pose_in and pose_out overlap (the poses the pass evaluated are read while the new ones are "
+                  "written: two buffers)");
+    ANCSH_REQUIRE(best != state, "refine_joint_step: best and state overlap (state is the object's shadow of the best block: a buffer of its own)");
+    if (nframes == 0) return ANCSH_OK;
+    hipLaunchKernelGGL(refine_joint_step_kernel, dim3(2, nframes), dim3(JS_THREADS), 0, (hipStream_t)stream, nframes, K, kin, ninst, scene,
+                       pred_render, norm_factor, params, pass, is_last, pose_in, ld_in, sums, sums_ld, pose_out, best, state, obj, xi);
+    return check_launch("refine_joint_step");
 }
 
 extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,

@@ -1098,20 +1098,26 @@ def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record,
     return columns, [tuple(view[:2] for view in frame) for frame in zip(*views)]
 
 
-def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, refine, debug=False, device="cuda:0"):
+def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, refine, debug=False, device="cuda:0",
+                  kinematics=None):
     """Eager render-and-compare ICP, the operator outside the pipeline: reprojection_frames' arguments and refine = pose.refinement.pack_refine's
     table.  Every part's two poses are refined on the observed depth: iters + 1 times ancsh_reproject_scene_build on the working poses, the
     renderer on 2 n frames and ancsh_refine_pass, then ancsh_refine_rec.  -> columns (n, K, 36) float64, pose.refinement.COLUMN_NAMES: per
     pose [R (9) | s | t (3) | cost_start | cost_best | n_used | best_pass | passes_solved]; pose.refinement.refined_record of the record with
     these columns behind it is the (n, K, 26) record of the refined poses.  debug=True: (columns, sums (iters + 1, n, K, 2, 32)), what every
     pass added up.  A table of pack_refine(silhouette=...) runs the loop with the silhouette term (ancsh_silhouette_field once, then
-    ancsh_refine_pass_sil): the debug sums are then (iters + 1, n, K, 2, 36).  A pipeline built with refine= streams the same bytes.  One
-    host sync; the pipeline has none."""
+    ancsh_refine_pass_sil): the debug sums are then (iters + 1, n, K, 2, 36).  A table of pack_refine(joints=...) needs kinematics = the
+    object's pack_kinematics table (a library: the stack of its instances'): ancsh_refine_joint_step runs behind every pass, the best-of is
+    kept per object, and debug=True returns (columns, sums, obj (iters + 1, n, 2, 8)): every pass's object rows,
+    pose.refinement.OBJ_COLUMNS.  A pipeline built with refine= streams the same bytes.  One host sync; the pipeline has none."""
     from .dataset import check_rigs
     from .pose.reprojection import predicted_buffers
-    from .pose.refinement import REFINE_SIL_PARAMS, REFINE_WIDTH, check_refine_table, field_buffer, refine_batch, refine_buffers
+    from .pose.refinement import REFINE_WIDTH, check_refine_table, field_buffer, has_joints, has_silhouette, refine_batch, refine_buffers
     table = check_refine_table(refine)
     iters = int(table[0])
+    if has_joints(table) and kinematics is None:
+        raise ValueError("refine=<pose.refinement.pack_refine(joints=...)> solves an object's parts together through the joints of its "
+                         "kinematic table: it needs kinematics=<depth.pack_kinematics(...)>")
     dev = _lib.cuda_device(device)
     name = check_depth_dtype(depth_dtype)
     rec = np.ascontiguousarray(record, np.float64)
@@ -1127,13 +1133,19 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
     t = lambda a: torch.from_numpy(a).to(dev)
     pred = predicted_buffers(total, name, dev)
     out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
-    sil = table.shape[0] == REFINE_SIL_PARAMS
-    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=sil)
+    sil, kin = has_silhouette(table), None
+    if has_joints(table):
+        kin = check_kinematics_library(kinematics, K) if np.ndim(kinematics) == 2 else check_kinematics(kinematics, K)
+        if (kin.shape[0] if kin.ndim == 2 else None) != (d_mesh.ninst if is_mesh_library(mesh) else None):
+            raise ValueError("kinematics and mesh must hold the same instances (a library: the np.stack of its instances' tables)")
+    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=sil, joints=kin is not None)
     wide = refine_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred, t(table), iters, buffers,
-                        field=field_buffer(K, total, dev) if sil else None)
+                        field=field_buffer(K, total, dev) if sil else None, kin=None if kin is None else t(kin))
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
     assert columns.shape == (n, K, REFINE_WIDTH)
-    return (columns, buffers[2].cpu().numpy()) if debug else columns
+    if not debug:
+        return columns
+    return (columns, buffers[2].cpu().numpy()) + ((buffers[3][1].cpu().numpy(),) if kin is not None else ())
 
 
 # ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred

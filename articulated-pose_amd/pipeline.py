@@ -172,7 +172,7 @@ class _Slot(object):
             self.reproj_pix = predicted_buffers(cap, depth, device)
         if opts.refine:                      # the loop's two working records, its best block and one pass's sums: slot-owned, shared with the
             from .pose.refinement import field_buffer, refine_buffers      # range guard's f32 graph like the tables and the pixel triple above
-            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette)
+            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints)      # joints: state and obj too
             self.refine_field = field_buffer(K, cap, device) if opts.silhouette else None      # the silhouette term: 4 bytes per pixel and part
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
@@ -372,6 +372,11 @@ class AncshPipeline(object):
         A table of pack_refine(silhouette=...) adds the silhouette term: ancsh_silhouette_field once in front of the loop and
         ancsh_refine_pass_sil in it, 5 (iters + 1) + 2 launches and 4 bytes per pixel of depth_capacity, part and slot; poses shifted across
         the ray come back, and cost_start / cost_best charge pixels that hang over the observed part.
+        A table of pack_refine(joints=...) (with kinematics=) adds the joint step: ancsh_refine_joint_step behind every pass solves the
+        parts of an object together through its revolute and prismatic joints, 6 (iters + 1) + 1 launches (+ 1 with the silhouette field); the
+        slot holds a second (B, K, 2, 18) block and a (B, 2, 8) row per object besides, out["refine_object"] (pose.refinement.OBJ_COLUMNS; not
+        streamed).  The best-of is then kept per OBJECT: cost_best <= cost_start holds for out["refine_object"], not for each part's columns,
+        whose best_pass and passes_solved are the object's.
         out["record_refined"]: the refinement block (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best,
         n_used, best_pass, passes_solved) behind the record so far; pose.refinement.refined_record(record, layout=pipe.record_layout) gives the
         (.., 26) record of the refined poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the
@@ -609,7 +614,9 @@ class AncshPipeline(object):
             out["record_refined"] = refine_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom, (sl.apix, sl.amask),
                                                  out[carried("refinement")[0]], self.depth_dtype,
                                                  sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs,
-                                                 field=sl.refine_field)
+                                                 field=sl.refine_field, kin=self.kin if self.opts.refine_joints else None)
+            if self.opts.refine_joints:  # the joint step's row per (frame, pose): (B, 2, 8) float64, slot-owned, not streamed
+                out["refine_object"] = sl.refine_bufs[3][1][0]
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:

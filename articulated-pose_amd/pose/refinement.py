@@ -6,7 +6,9 @@ scale is the network's, and one view constrains size only weakly.  Point-to-plan
 that shows one or two flat faces leaves directions unobservable: the damping leaves those where the fit put them -- unless the table is one of
 pack_refine(silhouette=...): then ancsh_silhouette_field finds, once per step, every crop pixel's nearest observed pixel of each part, and
 ancsh_refine_pass_sil adds one row per predicted pixel that hangs over the observed part's edge, pulling it back across the ray, and charges
-such pixels in the cost."""
+such pixels in the cost.  Each part is refined on its own -- unless the table is one of pack_refine(joints=...) and the object's kinematic
+table is at hand: then ancsh_refine_joint_step runs behind every pass, solves the object's parts together through rows that keep each
+revolute and prismatic joint's two sides on one axis, and keeps the best-of per object."""
 import numpy as np
 import torch
 
@@ -15,6 +17,8 @@ from .. import _lib
 REFINE_WIDTH = 36               # include/ancsh_hip.h, ANCSH_REFINE_WIDTH: the columns behind the carried record row, 18 per pose
 REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH_REFINE_PARAMS, ANCSH_REFINE_MAX_ITERS
 REFINE_SIL_SUMS, REFINE_SIL_PARAMS = 36, 16               # ANCSH_REFINE_SIL_SUMS, ANCSH_REFINE_SIL_PARAMS: with the silhouette term
+REFINE_JOINT_PARAMS, REFINE_OBJ, JOINT_XI = 24, 8, 48       # ANCSH_REFINE_JOINT_PARAMS, ANCSH_REFINE_OBJ; the debug step's 6 * 8 values: the joint step
+OBJ_COLUMNS = ("cost_start", "cost_best", "best_pass", "passes_solved", "cost", "joints", "solved", "gap_rms")      # an obj row, per (frame, pose)
 FIELD_SENTINEL = -32768                                   # both halves of a field word: the part has no observed pixel in the frame
 BEST_WIDTH = REFINE_WIDTH // 2
 COL_BASELINE, COL_NONLINEAR = 0, BEST_WIDTH           # counted from the end of the carried row
@@ -27,13 +31,13 @@ BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=T
 
 
 def check_refine_table(table):
-    """-> table as a fresh (REFINE_PARAMS,) float64 array, or (REFINE_SIL_PARAMS,) with the silhouette term; ValueError unless it is one
-    pack_refine makes."""
+    """-> table as a fresh (REFINE_PARAMS,) float64 array, (REFINE_SIL_PARAMS,) with the silhouette term or (REFINE_JOINT_PARAMS,) with the
+    joint step (has_silhouette, has_joints); ValueError unless it is one pack_refine makes."""
     try:
         t = np.array(table, np.float64)
     except (TypeError, ValueError):
         t = np.zeros(0)
-    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,)):
+    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,), (REFINE_JOINT_PARAMS,)):
         raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), or (%d,) with silhouette=, got shape %s"
                          % (REFINE_PARAMS, REFINE_SIL_PARAMS, t.shape))
     iters, max_dist, min_cos, damping, max_angle, min_pixels = t[:6].tolist()
@@ -51,7 +55,7 @@ def check_refine_table(table):
         raise ValueError("refine: min_pixels must be an integer >= 1, got %r" % min_pixels)
     if (t[6:REFINE_PARAMS] != 0).any():
         raise ValueError("refine: the reserved values 6..7 must be 0")
-    if t.shape[0] == REFINE_SIL_PARAMS:
+    if t.shape[0] == REFINE_SIL_PARAMS or (t.shape[0] == REFINE_JOINT_PARAMS and (t[8:REFINE_SIL_PARAMS] != 0).any()):
         weight, dist, slack = t[8:11].tolist()
         if not (np.isfinite(weight) and weight > 0):
             raise ValueError("refine: silhouette weight must be finite and > 0, got %r" % weight)
@@ -59,12 +63,30 @@ def check_refine_table(table):
             raise ValueError("refine: silhouette dist must be finite and > 0, got %r" % dist)
         if not (np.isfinite(slack) and slack >= 0):
             raise ValueError("refine: silhouette slack must be finite and >= 0 pixels, got %r" % slack)
-        if (t[11:] != 0).any():
+        if (t[11:REFINE_SIL_PARAMS] != 0).any():
             raise ValueError("refine: the reserved values 11..15 must be 0")
+    if t.shape[0] == REFINE_JOINT_PARAMS:
+        weight, axis_length = t[16:18].tolist()
+        if not (np.isfinite(weight) and weight > 0):
+            raise ValueError("refine: joints weight must be finite and > 0, got %r" % weight)
+        if not (np.isfinite(axis_length) and axis_length >= 0):
+            raise ValueError("refine: joints axis_length must be finite and >= 0, got %r" % axis_length)
+        if (t[18:] != 0).any():
+            raise ValueError("refine: the reserved values 18..23 must be 0")
     return t
 
 
-def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None):
+def has_silhouette(table):
+    """A checked table: the silhouette term is on iff it holds at least REFINE_SIL_PARAMS values and value 8 (its weight) is > 0."""
+    return table is not None and table.shape[0] >= REFINE_SIL_PARAMS and bool(table[8] > 0)
+
+
+def has_joints(table):
+    """A checked table: the joint step is on iff it is the (REFINE_JOINT_PARAMS,) one."""
+    return table is not None and table.shape[0] == REFINE_JOINT_PARAMS
+
+
+def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None, joints=None):
     """The parameter table ancsh_refine_pass reads, (REFINE_PARAMS,) float64: iters Gauss-Newton passes (1..8; one more pass evaluates the
     last pose); max_dist: a pixel pair further apart than this counts as missed, and a step's translation is clamped to it; min_cos: pixels
     seen at a flatter angle are left out; damping: relative Levenberg damping of the diagonal; max_angle_deg: the clamp of a step's
@@ -74,12 +96,32 @@ def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=
     predicted pixel of the part where the camera saw neither the part nor anything nearer is pulled towards the nearest observed pixel of
     the part: weight scales its row against the depth rows; further than dist (at the pixel's depth) it pulls no more and is charged dist^2;
     within slack pixels it is ignored (sensor holes, one pixel of raster disagreement).  min_pixels then counts these rows too.
+    joints = dict(weight=1.0, axis_length=0.5), or (weight, axis_length): the joint step (ancsh_refine_joint_step), a (REFINE_JOINT_PARAMS,)
+    table: values 0..7 as above, 8..15 the silhouette values (all 0 without the term), 16 weight, 17 axis_length, 18..23 reserved.  Behind
+    every pass the parts of an object are solved together: rows that keep each revolute and prismatic joint's two sides on one axis join the
+    parts' own normal equations.  weight scales a joint row against a mean part's pixel rows (a residual in cloud units counts weight^2 *
+    the parts' mean row count times); axis_length (cloud units) turns the angle between the two sides' axis directions into a length.  It
+    needs the object's kinematic table (kinematics=).  These defaults, too, are starting values nobody has tuned.
     ValueError: check_refine_table's."""
     try:
         head = [float(iters), float(max_dist), float(min_cos), float(damping), float(np.radians(float(max_angle_deg))), float(min_pixels)]
     except (TypeError, ValueError):
         raise ValueError("refine: iters, max_dist, min_cos, damping, max_angle_deg and min_pixels are numbers")
     head = head + [0.0] * (REFINE_PARAMS - len(head))
+    if joints is not None:
+        if isinstance(joints, dict) and set(joints) - {"weight", "axis_length"}:
+            raise ValueError("refine: joints takes weight and axis_length, got %s" % sorted(joints))
+        try:
+            if isinstance(joints, dict):
+                jt = [float(joints.get("weight", 1.0)), float(joints.get("axis_length", 0.5))]
+            else:
+                weight, axis_length = joints
+                jt = [float(weight), float(axis_length)]
+        except (TypeError, ValueError):
+            raise ValueError("refine: joints is dict(weight=, axis_length=) or (weight, axis_length), of numbers")
+        sil = [0.0] * (REFINE_SIL_PARAMS - REFINE_PARAMS) if silhouette is None else \
+            pack_refine(iters, max_dist, min_cos, damping, max_angle_deg, min_pixels, silhouette=silhouette)[REFINE_PARAMS:].tolist()
+        return check_refine_table(head + sil + jt + [0.0] * (REFINE_JOINT_PARAMS - REFINE_SIL_PARAMS - len(jt)))
     if silhouette is None:
         return check_refine_table(head)
     if isinstance(silhouette, dict) and (set(silhouette) - {"weight", "dist", "slack"} or "dist" not in silhouette):
@@ -133,11 +175,13 @@ def _f64(name, t, shape):
         raise ValueError("%s must be a contiguous %s float64 tensor" % (name, tuple(shape)))
 
 
-def refine_buffers(B, K, device, passes=1, silhouette=False):
+def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False):
     """What a slot owns for the loop: (work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2, 32 -- 36 with the
-    silhouette term)), float64."""
+    silhouette term)), float64.  joints=True: a fourth element, the joint step's two buffers and its debug output: (state (B, K, 2, 18), obj
+    (passes, B, 2, 8), xi (passes, B, 2, 48) -- None with one pass)."""
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-    return (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS)
+    bufs = (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS)
+    return bufs + ((z(B, K, 2, BEST_WIDTH), z(passes, B, 2, REFINE_OBJ), z(passes, B, 2, JOINT_XI) if passes > 1 else None),) if joints else bufs
 
 
 def field_buffer(K, pixel_capacity, device):
@@ -188,7 +232,9 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     _f64("scene", scene, (B, SCENE_WIDTH))
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
     sil = field is not None
-    _f64("params", params, (REFINE_SIL_PARAMS if sil else REFINE_PARAMS,))
+    if tuple(params.shape) != (REFINE_JOINT_PARAMS,):                     # the joint step's table holds both shorter ones in front
+        _f64("params", params, (REFINE_SIL_PARAMS if sil else REFINE_PARAMS,))
+    _f64("params", params, tuple(params.shape))
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
     _f64("sums", sums, (B, K, 2, REFINE_SIL_SUMS if sil else REFINE_SUMS))
@@ -209,6 +255,40 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     return pose_out
 
 
+def refine_joint_step(kin, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, sums, pose_out, best, state, obj, xi=None):
+    """ancsh_refine_joint_step on device tensors (no host sync, no allocation), directly behind refine_pass of the same pass and on its
+    arguments: kin = the object's kinematic table (672,) or a library's (ninst, 672) on the device; params = a pack_refine(joints=...) table
+    (24,); sums (B, K, 2, 32 or 36) what the pass wrote.  Overwrites pose_out (B, K, 26) and best (B, K, 2, 18); state (B, K, 2, 18) and obj
+    (B, 2, 8; OBJ_COLUMNS) are its own, written on pass 0 and carried from pass to pass; xi (B, 2, 48) or None: the clamped step.  -> pose_out."""
+    from ..depth import KIN_WIDTH, RENDER_WIDTH, SCENE_WIDTH
+    _lib.require_device(pose_in)
+    if pose_in.dtype != torch.float64 or pose_in.dim() != 3 or pose_in.shape[2] < 26 or not pose_in.is_contiguous():
+        raise ValueError("pose_in must be a contiguous (B, K, >= 26) float64 tensor")
+    B, K, ld = (int(v) for v in pose_in.shape)
+    if kin.dtype != torch.float64 or kin.dim() not in (1, 2) or kin.shape[-1] != KIN_WIDTH or kin.shape[0] < 1 or not kin.is_contiguous():
+        raise ValueError("kin must be a contiguous (%d,) or (ninst, %d) float64 tensor (depth.pack_kinematics)" % (KIN_WIDTH, KIN_WIDTH))
+    ninst = int(kin.shape[0]) if kin.dim() == 2 else 1
+    _f64("scene", scene, (B, SCENE_WIDTH))
+    _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
+    _f64("params", params, (REFINE_JOINT_PARAMS,))
+    if sums.dim() != 4 or sums.shape[3] not in (REFINE_SUMS, REFINE_SIL_SUMS):
+        raise ValueError("sums must be a contiguous (%d, %d, 2, %d or %d) float64 tensor" % (B, K, REFINE_SUMS, REFINE_SIL_SUMS))
+    _f64("sums", sums, (B, K, 2, int(sums.shape[3])))
+    _f64("pose_out", pose_out, (B, K, 26))
+    _f64("best", best, (B, K, 2, BEST_WIDTH))
+    _f64("state", state, (B, K, 2, BEST_WIDTH))
+    _f64("obj", obj, (B, 2, REFINE_OBJ))
+    if xi is not None:
+        _f64("xi", xi, (B, 2, JOINT_XI))
+    if norm_factor.dtype != torch.float32 or tuple(norm_factor.shape) != (B,) or not norm_factor.is_contiguous():
+        raise ValueError("norm_factor must be a contiguous (%d,) float32 tensor" % B)
+    _lib.require_cuda(kin, scene, pred_render, norm_factor, params, sums, pose_out, best, state, obj, xi)
+    _lib.call("ancsh_refine_joint_step", B, K, _lib.ptr(kin), ninst, _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
+              _lib.ptr(params), int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld, _lib.ptr(sums), int(sums.shape[3]),
+              _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(state), _lib.ptr(obj), _lib.ptr(xi))
+    return pose_out
+
+
 def refine_rec(best, carried, out=None):
     """ancsh_refine_rec on device tensors (no host sync): best (B, K, 2, 18) and the record so far (B, K, ld) float64 -> (B, K, ld + 36): the
     carried row bit for bit and the 36 columns behind it (COLUMN_NAMES)."""
@@ -225,16 +305,21 @@ def refine_rec(best, carried, out=None):
     return out
 
 
-def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers, field=None):
+def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers, field=None,
+                 kin=None):
     """The captured step's sequence, no host sync and no allocation beyond the output: iters + 1 times ancsh_reproject_scene_build on the
     working poses, the renderer, ancsh_refine_pass; then ancsh_refine_rec -- 5 (iters + 1) + 1 launches.  tables and pred are
     pose.reprojection's slot-owned pair and triple (shared with reprojection=True, whose three calls come first); params = pack_refine's
     table on the device and iters its first value on the host; buffers = refine_buffers'.  sums of `passes` > 1 rows keeps every pass's sums
     (pass p in row p); one row holds the last pass's.  field = field_buffer's planes, with a (16,) table: ancsh_silhouette_field once in
-    front of the loop and ancsh_refine_pass_sil in it -- 5 (iters + 1) + 2 launches.  -> (B, K, ld + 36) float64."""
+    front of the loop and ancsh_refine_pass_sil in it -- 5 (iters + 1) + 2 launches.  kin = the kinematic table(s) on the device, with a
+    (24,) table and refine_buffers(joints=True): ancsh_refine_joint_step behind every pass -- 6 (iters + 1) + 1 launches (+ 1 with the field);
+    obj and xi of `passes` > 1 rows keep every pass's (one device copy carries the object's row on).  -> (B, K, ld + 36) float64."""
     from ..depth import render_depth
     from .reprojection import reproject_scene_build
-    work, best, sums = buffers
+    work, best, sums = buffers[:3]
+    if (kin is not None) != (len(buffers) == 4):
+        raise ValueError("the joint step takes both kin and refine_buffers(joints=True)")
     cap = int(obs[0].shape[0])
     src = carried
     if field is not None:
@@ -245,5 +330,11 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
         dst = work[p % 2]
         refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
                     sums[p if sums.shape[0] > 1 else 0], field=field)
+        if kin is not None:
+            state, obj, xi = buffers[3]
+            if p and obj.shape[0] > 1:
+                obj[p].copy_(obj[p - 1])
+            refine_joint_step(kin, scene, tables[0], norm_factor, params, p, p == iters, src, sums[p if sums.shape[0] > 1 else 0], dst, best,
+                              state, obj[p if obj.shape[0] > 1 else 0], None if xi is None else xi[p])
         src = dst
     return refine_rec(best, carried)

@@ -1610,6 +1610,74 @@ int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts
                           const double *pred_render, const float *norm_factor, const double *params, const int *field, int pass, int is_last,
                           const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
 
+/* The joint step of render-and-compare ICP: an object's parts solved TOGETHER through their joints, one entry launched directly behind
+ * ancsh_refine_pass[_sil] in every pass (no new ABI number: callers detect it by its symbol).  The pass refines each (frame, part, pose) on its
+ * own, so a part that shows one flat face slides along it, a part below min_pixels is not moved, and nothing keeps a hinge's two sides
+ * together.  This entry reads the 6 x 6 normal equations the pass left per part, adds rows that keep every revolute and prismatic joint's two
+ * sides on one axis, solves the 6 K system, overwrites the poses the pass wrote, and keeps the best-of per OBJECT.  The loop becomes, pass = 0 ..
+ * iters: ancsh_reproject_scene_build, the renderer, ancsh_refine_pass[_sil], ancsh_refine_joint_step; then ancsh_refine_rec, unchanged.
+ *
+ * ancsh_refine_joint_step: ONE launch, one workgroup of one wave per (pose v, frame f).
+ *   kin (ninst, ANCSH_KIN_WIDTH) : the object's kinematic table(s); the frame's instance is value [9] of its pred_render row (0 for a single
+ *   object), as the *_lib entries carry it;  scene, pred_render, norm_factor, pass, is_last, pose_in, ld_in : what the pass of this `pass` was
+ *   given;  params : ONE table of ANCSH_REFINE_JOINT_PARAMS = 24 float64: [0..7] ancsh_refine_pass's, [8..15] ancsh_refine_pass_sil's (all 0
+ *   without the term; not read here), [16] weight > 0, [17] axis_length >= 0 (the scaled cloud's unit), [18..23] reserved, 0;
+ *   sums (nframes, K, 2, sums_ld), sums_ld = 32 or 36 : what that pass wrote;  pose_out (nframes, K, 26) and best (nframes, K, 2, 18) : what
+ *   that pass wrote, overwritten here;  state (nframes, K, 2, 18) : this entry's own shadow of the best block, written on pass 0, read and
+ *   written later;  obj (nframes, 2, ANCSH_REFINE_OBJ = 8) : the object's row, likewise;  xi (nframes, 2, 48) or NULL : the clamped step, for
+ *   debugging (0 where nothing was solved and behind 6 K).
+ * Everything is float64 in exactly the written order (no contraction), with sqrt and division only; dot, |a|, the centre c_j, the cloud map
+ * (x', y', z) -> nf (x', -y', z) and the part of a link are ancsh_refine_pass's.
+ *   LIVE parts: part j is live when its 13 pose values are finite and nf is finite and not 0.  Its rows n_j = sums[28] (+ sums[33] when
+ *   sums_ld = 36).  With n_j < min_pixels its A_j and b_j count as 0.  nbar = (sum of n_j) / (their number) over the live parts with n_j >=
+ *   min_pixels, j ascending; with no such part nothing is solved.  w2n = (weight weight) nbar.
+ *   Link maps: M_l = the 3 x 4 map of link l in the pose's pred_render row;  C_l(x) = cloud(m), m_a = ((M[a][0] x0 + M[a][1] x1) + M[a][2] x2) +
+ *   M[a][3];  D_l(d) = u / |u| with u = (m_0, -m_1, m_2), m_a = (M[a][0] d0 + M[a][1] d1) + M[a][2] d2.
+ *   ACTIVE joints: link l, 1 <= l < nlinks (scene[14]), of the instance's table with parent p (an integer in [0, l)) and kind 1 or 2, whose
+ *   parts a = part(l) and b = part(p) are two different live parts of [0, K).  (A chain through a link of no part is not bridged; fixed joints
+ *   add nothing.)  An instance outside [0, ninst), a parent outside [0, l) or a value that is no integer makes no joint.  With T = T_l and
+ *   axis = the joint's axis (kin link values 4..15, 16..18):  x_c = C_l(0);  x_p = C_p(T[:, 3]);  u_c = D_l(axis);  u_p = D_p(T[:, :3] axis),
+ *   (T[:, :3] d)_i = (T[i][0] d0 + T[i][1] d1) + T[i][2] d2.  At poses that reproduce the frame's own tables all four agree to rounding.
+ *   Rows r0 + G xi, xi_j = (w_j, d_j) the step of part j about c_j; rows(e, h, r, sc, id): r0 = sc r;  G_a = [-[sc e]x | id I],
+ *   G_b = [[sc h]x | -id I], [e]x = {0 -e2 e1; e2 0 -e0; -e1 e0 0}.
+ *     position : rows(x_c - c_a, x_p - c_b, x_c - x_p, 1, 1);   direction : rows(u_c, u_p, u_c - u_p, axis_length, 0).
+ *     Revolute: position, direction.  Prismatic: the position rows multiplied on the left by P = I - u_p u_p^T (P_ik = d_ik - u_p,i u_p,k;
+ *     (P G)_ic = (P_i0 G_0c + P_i1 G_1c) + P_i2 G_2c, r0 likewise), the direction rows, and the direction rows of a second direction b = axis x
+ *     e_k / |axis x e_k|, k the index of the smallest |axis_k| (ties: the lowest), taken through both links as the axis is: 9 rows.
+ *     A joint with a row value r0 that is not finite, or a direction of length 0, is not active.
+ *   The system, n = 6 K:  H = blockdiag(A_j, its diagonal damped as the pass damps it: A_kk + (damping A_kk + 1e-12)), g = (b_j); a part that
+ *   is not live has the identity block and g = 0.  Then joint after joint, l ascending, with the 12 columns (a's six, b's six):  H_pq = H_pq +
+ *   w2n t, t = 0 + G_0p G_0q + G_1p G_1q + ... (rows ascending);  g_p = g_p + w2n t, t = 0 + G_0p r0_0 + ...
+ *   Cholesky H = L L^T:  element (i, j), i >= j, is s = H_ij, s = s - L_ik L_jk for k = 0 .. j - 1 (ascending, in one thread: the bytes do not
+ *   depend on how the elements are spread over the lanes), L_jj = sqrt(s), L_ij = s / L_jj.  L y = -g: s = 0 - g_i, s = s - L_ik y_k for k
+ *   ascending, y_i = s / L_ii.  L^T xi = y: s = y_i, s = s - L_ki xi_k for k = n - 1 DOWN TO i + 1, xi_i = s / L_ii.  It FAILS when a pivot s is
+ *   not > 0 or not finite, or a value of xi is not finite.
+ *   Clamp: ONE factor for the object: f = 1, then for the live parts, j ascending: |w_j| > max_angle and max_angle / |w_j| < f: f = that;
+ *   |d_j| > max_dist and max_dist / |d_j| < f: f = that.  xi = xi f when f < 1.  Update: ancsh_refine_pass's quaternion update of every live
+ *   part with (w_j, d_j), written to pose_out.
+ *   Nothing to solve -- no active joint, no nbar, is_last, or a failed solve --: pose_out stays what the pass wrote.
+ *   Object cost: num = sum C_j n_obs_j, den = sum n_obs_j over the live parts with n_obs_j > 0 (C_j = sums[30], n_obs_j = sums[29], j
+ *   ascending); with an active joint and nbar: num = num + w2n (sum over the joints, l ascending, of (0 + r0_0 r0_0 + r0_1 r0_1 + ...));
+ *   Cobj = num / den, NaN when den = 0.
+ *   Best-of, per OBJECT: on pass 0, or when Cobj is strictly lower than the object's cost_best (a NaN never is), the shadow `state` takes the
+ *   13 values of ALL K parts' pose_in, their own C_j (column 14; on pass 0 column 13 too) and n_used_j (15) -- NaN in 13..15 for a part that
+ *   is not live -- and the pass number.  Every pass then writes columns 16 = the object's best_pass and 17 = the object's passes_solved (the
+ *   passes in which a solve moved a pose of the object: this entry's, or -- where it solved nothing -- a part's own) and rewrites `best` from
+ *   the shadow; what the pass wrote there is ignored.  A part that is not live in this pass reads 18 NaN.  So cost_best <= cost_start holds for
+ *   the OBJECT (obj), no longer for each part.
+ *   obj row: [cost_start | cost_best | best_pass | passes_solved | this pass's Cobj | active joints | 1 when this entry solved | sqrt((sum of
+ *   the joints' squared position residuals |r0_0..2|^2) / joints), NaN without one].
+ *   No atomics, the same bytes every run; no host sync, no allocation: graph-capturable.  nframes == 0 launches nothing and returns 0.
+ *   Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8, 1 <= ninst <= 65535, 0 <= pass <= ANCSH_REFINE_MAX_ITERS, is_last in {0,
+ *   1}, ld_in >= 26, sums_ld in {32, 36}, null pointers (xi may be NULL), the alignments (norm_factor 4, everything else 8 bytes), pose_in !=
+ *   pose_out, best != state. */
+#define ANCSH_REFINE_JOINT_PARAMS 24
+#define ANCSH_REFINE_OBJ 8
+int ancsh_refine_joint_step(int nframes, int K, const double *kin, int ninst, const double *scene, const double *pred_render,
+                            const float *norm_factor, const double *params, int pass, int is_last, const double *pose_in, int ld_in,
+                            const double *sums, int sums_ld, double *pose_out, double *best, double *state, double *obj, double *xi,
+                            void *stream);
+
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows
  * [offsets[b], offsets[b+1]) of `rows` (capacity x nchan float32, x y z first), norm factor norm_factor[b], sampled points P (nclouds,
