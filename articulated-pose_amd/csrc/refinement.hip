@@ -15,7 +15,7 @@
 // equations from `sums` and the rows that keep each revolute and prismatic joint's two sides on one axis, solved together by Cholesky in
 // LDS; the poses and the best block the pass wrote are overwritten, the best-of is kept per object).  The pass kernel does not know of it.
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
-#include "depth_annotate_common.h"
+#include "compare_common.h"
 
 namespace ancsh {
 
@@ -24,20 +24,6 @@ constexpr int RF_RENDER = ANCSH_RENDER_WIDTH, RF_BEST = ANCSH_REFINE_WIDTH / 2, 
 constexpr int RF_ACC = 30;                                              // A (21) | b (6) | sum r^2 | n_used | n_obs: what the block adds up
 constexpr int RF_SIL_ACC = 33, RF_SIL_SUMS = ANCSH_REFINE_SIL_SUMS;     // ... | sum m^2 | n_sil | n_far: with the silhouette term
 constexpr int SF_THREADS = 256, SF_BAND = 16, SF_CHUNK = 256, SF_SPLIT = 8, SF_STEP = 8, SF_ILP = 8, SF_NONE = 0x7fffffff, SF_SENTINEL = -32768;
-
-__device__ __forceinline__ bool rf_finite(double v) { return fabs(v) < __builtin_inf(); }      // NaN fails the comparison
-
-__device__ __forceinline__ bool rf_pose_ok(const double *__restrict__ p) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) ok = ok && rf_finite(p[k]);
-    return ok;
-}
-
-template <typename T>
-__device__ __forceinline__ int rf_pixel_part(T d, unsigned char lab, const int *s_part) {      // reprojection.hip's rp_pixel_part
-    return lab < RF_LINKS && depth_ok(d) ? s_part[lab] : -1;
-}
 
 __device__ __forceinline__ double rf_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
@@ -95,7 +81,7 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
 #pragma unroll
             for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
             if (i == j) {
-                ok = ok && s > 0.0 && rf_finite(s);
+                ok = ok && s > 0.0 && finite(s);
                 L[i][i] = sqrt(s);
             } else
                 L[i][j] = s / L[j][j];
@@ -116,7 +102,7 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
         xi[i] = s / L[i][i];
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) ok = ok && rf_finite(xi[k]);
+    for (int k = 0; k < 6; ++k) ok = ok && finite(xi[k]);
     if (!ok) return false;
     const double wn = sqrt(rf_dot(xi, xi)), dn = sqrt(rf_dot(xi + 3, xi + 3));
     if (wn > max_angle || dn > max_dist) {                              // one factor for the whole step: the smaller of the two ratios
@@ -152,22 +138,17 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     double *po = pose_out + ((size_t)f * K + j) * 26 + 13 * v;
     double *bb = best + (((size_t)f * K + j) * 2 + v) * RF_BEST, *ss = sums + (((size_t)f * K + j) * 2 + v) * NSUMS;
     const double nf = (double)norm_factor[f], qnan = __builtin_nan("");
-    if (!rf_pose_ok(pose) || !rf_finite(nf) || nf == 0.0) {             // uniform over the block: NaN in the best block, the pose as it came
+    if (!pose_ok(pose) || !finite(nf) || nf == 0.0) {                   // uniform over the block: NaN in the best block, the pose as it came
         if (tid < 13) po[tid] = pose[tid];
         if (tid < RF_BEST) bb[tid] = qnan;
         if (tid < NSUMS) ss[tid] = tid == RF_SUMS - 1 || tid == RF_SIL_SUMS - 1 ? 0.0 : qnan;
         return;
     }
-    if (tid < RF_LINKS) {
-        const int nl = scene_nlinks(sc);
-        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
-        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
-    }
+    scene_part_table(sc, K, tid, s_part);
     __syncthreads();
     const double max_dist = params[1], min_cos = params[2];
-    double c[3];                                                        // the centre: s R (0.5, 0.5, 0.5) + t
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = pose[9] * ((pose[3 * a] * 0.5 + pose[3 * a + 1] * 0.5) + pose[3 * a + 2] * 0.5) + pose[10 + a];
+    double c[3];
+    pose_centre(pose, c);
     long start;
     int w;
     const long n = depth_crop(geom, f, pixel_capacity, start, w);       // [start, start + n) lies inside [0, pixel_capacity)
@@ -183,8 +164,8 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     for (long a = start + tid; a < start + n; a += RF_THREADS) {
         const T od = obs_depth[a], qd = pd[a];
         const unsigned long long key = pz[a];
-        const int op = rf_pixel_part(od, obs_labels[a], s_part);
-        const bool o = op == j, p = rf_pixel_part(qd, pl[a], s_part) == j;
+        const int op = pixel_part(od, obs_labels[a], s_part);
+        const bool o = op == j, p = pixel_part(qd, pl[a], s_part) == j;
         acc[29] += o ? 1.0 : 0.0;
         if constexpr (SIL) {
             if (p && !o) {                                              // an OVERHANG pixel, unless another part hides the prediction here
@@ -196,9 +177,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                 const long e = a - start;
                 const int ri = row0 + (int)(e / w), ci = col0 + (int)(e % w);
                 const double row = (double)ri, col = (double)ci, row2 = (double)(ri + di), col2 = (double)(ci + dj);
-                const double su = (sc[7] * col + sc[8] * row) + sc[9], sv = (sc[10] * col + sc[11] * row) + sc[12];
-                const double su2 = (sc[7] * col2 + sc[8] * row2) + sc[9], sv2 = (sc[10] * col2 + sc[11] * row2) + sc[12];
-                double pp[3], p2[3];
+                double su, sv, su2, sv2, pp[3], p2[3];
+                pixel_ray(sc, row, col, su, sv);
+                pixel_ray(sc, row2, col2, su2, sv2);
                 rf_cloud(zp * su, zp * sv, zp, nf, pp);
                 rf_cloud(zp * su2, zp * sv2, zp, nf, p2);
                 const double dv[3] = {pp[0] - p2[0], pp[1] - p2[1], pp[2] - p2[2]};
@@ -231,9 +212,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
         if (l < 0 || l >= RF_LINKS || ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) continue;
         const long e = a - start;
         const double row = (double)(row0 + (int)(e / w)), col = (double)(col0 + (int)(e % w));
-        const double su = (sc[7] * col + sc[8] * row) + sc[9], sv = (sc[10] * col + sc[11] * row) + sc[12];
+        double su, sv, q[3], pp[3], vt[3][3];
+        pixel_ray(sc, row, col, su, sv);
         const double zo = (double)od * scale, zp = (double)__uint_as_float((unsigned)(key >> 32));
-        double q[3], pp[3], vt[3][3];
         rf_cloud(zo * su, zo * sv, zo, nf, q);
         rf_cloud(zp * su, zp * sv, zp, nf, pp);
         const double *R = rt + ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l;
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
         const double e2[3] = {vt[2][0] - vt[0][0], vt[2][1] - vt[0][1], vt[2][2] - vt[0][2]};
         double nn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
         const double len = sqrt(rf_dot(nn, nn));
-        if (!(len > 0.0 && rf_finite(len))) continue;
+        if (!(len > 0.0 && finite(len))) continue;
 #pragma unroll
         for (int b = 0; b < 3; ++b) nn[b] = nn[b] / len;
         double nq = rf_dot(nn, q);
@@ -340,11 +321,7 @@ __global__ __launch_bounds__(SF_THREADS) void silhouette_field_kernel(int K, con
     __shared__ int s_g[SF_BAND][SF_CHUNK];
     const int j = blockIdx.x, f = blockIdx.z, tid = threadIdx.x;
     const double *sc = scene + (size_t)f * AN_SCENE;
-    if (tid < RF_LINKS) {
-        const int nl = scene_nlinks(sc);
-        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
-        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
-    }
+    scene_part_table(sc, K, tid, s_part);
     __syncthreads();
     long start;
     int w;
@@ -355,7 +332,7 @@ __global__ __launch_bounds__(SF_THREADS) void silhouette_field_kernel(int K, con
     const bool wide = h > 32767 || w > 32767;                           // an offset would not fit its 16 bits: the sentinel everywhere
     const int none = (int)(((unsigned)SF_SENTINEL & 0xffffu) | ((unsigned)SF_SENTINEL << 16));
     auto seen = [&](int r, int c) {
-        const long a = start + (long)r * w + c;                         // rf_pixel_part's rule, the label first: most pixels need no depth
+        const long a = start + (long)r * w + c;                         // pixel_part's rule, the label first: most pixels need no depth
         const unsigned char lab = obs_labels[a];
         return lab < RF_LINKS && s_part[lab] == j && depth_ok(obs_depth[a]);
     };
@@ -472,7 +449,7 @@ __device__ __forceinline__ bool js_dir(const double *__restrict__ R, const doubl
     const double len = sqrt(rf_dot(m, m));
 #pragma unroll
     for (int b = 0; b < 3; ++b) o[b] = m[b] / len;
-    return len > 0.0 && rf_finite(len);
+    return len > 0.0 && finite(len);
 }
 
 // three rows r0 + G xi of one joint into LDS: G = sc [-[e]x | id I] for the child's part (columns 0..5), sc [[h]x | -id I] for the parent's
@@ -503,12 +480,10 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
     const double *sc = scene + (size_t)f * AN_SCENE, *rt = pred_render + ((size_t)v * nframes + f) * RF_RENDER;
     const double nf = (double)norm_factor[f], qnan = __builtin_nan("");
     const double max_dist = params[1], damping = params[3], max_angle = params[4], min_pixels = params[5], weight = params[16], axis_len = params[17];
-    const bool nf_ok = rf_finite(nf) && nf != 0.0;
+    const bool nf_ok = finite(nf) && nf != 0.0;
     const size_t part0 = ((size_t)f * K) * 2 + v;                       // part j's row of best, state and sums: (part0 + 2 j) * its width
-    if (tid < RF_LINKS) {                                               // the pass kernel's rule
-        const int nl = scene_nlinks(sc);
-        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
-        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
+    if (tid < RF_LINKS) {                                               // scene_part_table's line, with this kernel's own tables
+        s_part[tid] = scene_link_part(sc, tid, scene_nlinks(sc), K);
         s_rows[tid] = 0;
         s_rr[tid] = s_gap[tid] = 0.0;
     }
@@ -518,10 +493,9 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
         double nj = 0.0;
         if (tid < K) {
             const double *pose = pose_in + ((size_t)f * K + tid) * ld_in + 13 * v, *S = sums + (part0 + 2 * (size_t)tid) * sums_ld;
-            live = nf_ok && rf_pose_ok(pose);
+            live = nf_ok && pose_ok(pose);
             if (live) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) s_c[tid][a] = pose[9] * ((pose[3 * a] * 0.5 + pose[3 * a + 1] * 0.5) + pose[3 * a + 2] * 0.5) + pose[10 + a];
+                pose_centre(pose, s_c[tid]);
                 nj = S[28];
                 if (sums_ld == RF_SIL_SUMS) nj = nj + S[33];
             }
@@ -538,8 +512,8 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
     const double w2n = has_nbar ? (weight * weight) * (nsum / ncount) : 0.0;
     // lane l: link l's joint.  Every index read from a table is checked before it is used
     const int nl = scene_nlinks(sc);
-    const double iv = rt[9];
-    const int inst = iv >= 0.0 && iv < (double)ninst && (double)(int)iv == iv ? (int)iv : -1;
+    const double iv = rt[9];                                            // common.h's instance_index, written out: its floor test moved this kernel's
+    const int inst = iv >= 0.0 && iv < (double)ninst && (double)(int)iv == iv ? (int)iv : -1;      // registers and cost it 0.5 %
     if (tid >= 1 && tid < nl && inst >= 0) {
         const int l = tid;
         const double *kl = kin + (size_t)inst * ANCSH_KIN_WIDTH + ANCSH_KIN_HEAD + ANCSH_KIN_LINK * l;
@@ -584,7 +558,7 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
                 const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
                 double bx[3] = {ax[1] * ek[2] - ax[2] * ek[1], ax[2] * ek[0] - ax[0] * ek[2], ax[0] * ek[1] - ax[1] * ek[0]}, bxp[3], vc[3], vp[3];
                 const double bl = sqrt(rf_dot(bx, bx));
-                ok = ok && bl > 0.0 && rf_finite(bl);
+                ok = ok && bl > 0.0 && finite(bl);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) bx[i] = bx[i] / bl;
 #pragma unroll
@@ -597,7 +571,7 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
             }
             double rr = 0.0;
             for (int i = 0; i < rows; ++i) {
-                ok = ok && rf_finite(r0[i]);
+                ok = ok && finite(r0[i]);
                 rr = rr + r0[i] * r0[i];
             }
             if (ok) {                                                   // a joint whose rows are not finite is not active
@@ -669,7 +643,7 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
                 s = s_H[tid][jc];
                 for (int k = 0; k < jc; ++k) s = s - s_H[tid][k] * s_H[jc][k];
                 if (tid == jc) {
-                    if (!(s > 0.0 && rf_finite(s))) s_fail = 1;
+                    if (!(s > 0.0 && finite(s))) s_fail = 1;
                     s_H[jc][jc] = sqrt(s);
                 }
             }
@@ -693,7 +667,7 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
         }
         __syncthreads();
         solved = !s_fail;
-        for (int k = 0; k < n; ++k) solved = solved && rf_finite(s_x[k]);
+        for (int k = 0; k < n; ++k) solved = solved && finite(s_x[k]);
         if (solved) {
             for (int j = 0; j < K; ++j) {                               // one factor for the whole object
                 if (!s_live[j]) continue;
@@ -761,28 +735,19 @@ static int refine_pass_call(const char *who, int nframes, int K, int depth_type,
                             const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                             const double *scene, const double *pred_render, const float *norm_factor, const double *params, const int *field,
                             int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "%s: bad shape nframes=%d", who, nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "%s: %d frames exceed the 32767-frame range of ancsh_reproject_scene_build; split the batch", who, nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "%s: K=%d must be in [1, 8]", who, K);
-    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
-                  "%s: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", who, depth_type);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "%s: pixel_capacity=%ld pixels out of range", who, pixel_capacity);
+    ANCSH_CHECK(batch_ok(who, nframes, K, "exceed the 32767-frame range of ancsh_reproject_scene_build"));
+    size_t item;
+    ANCSH_CHECK(depth_item(who, depth_type, item));
+    ANCSH_CHECK(capacity_ok(who, pixel_capacity));
     ANCSH_REQUIRE(T >= 0 && T < (1 << 24), "%s: T=%d triangles must be in [0, 2^24)", who, T);
     ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "%s: V=%d vertices must be in [0, 2^24)", who, V);
-    ANCSH_REQUIRE(pass >= 0 && pass <= ANCSH_REFINE_MAX_ITERS, "%s: pass=%d must be in [0, %d]", who, pass, ANCSH_REFINE_MAX_ITERS);
-    ANCSH_REQUIRE(is_last == 0 || is_last == 1, "%s: is_last=%d must be 0 or 1", who, is_last);
-    ANCSH_REQUIRE(ld_in >= 26, "%s: ld_in=%d, a record row holds at least the 26 pose columns", who, ld_in);
+    ANCSH_CHECK(pass_ok(who, pass, is_last));
+    ANCSH_CHECK(record_ld_ok(who, "ld_in", ld_in));
     ANCSH_REQUIRE(verts && tris && tri_link && obs_depth && obs_labels && pred_zbuf && pred_depth && pred_labels && geom && scene &&
                       pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || !SIL),
                   "%s: null pointer", who);
-    const size_t item = depth_type == ANCSH_DEPTH_U16 ? 2 : 4;
-    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)pred_depth & (item - 1)) == 0 && ((size_t)verts & 3) == 0 &&
-                      ((size_t)tris & 3) == 0 && ((size_t)tri_link & 3) == 0 && ((size_t)geom & 3) == 0 && ((size_t)norm_factor & 3) == 0 &&
-                      ((size_t)pred_zbuf & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)pred_render & 7) == 0 && ((size_t)params & 7) == 0 &&
-                      ((size_t)pose_in & 7) == 0 && ((size_t)pose_out & 7) == 0 && ((size_t)best & 7) == 0 && ((size_t)sums & 7) == 0 &&
-                      ((size_t)field & 3) == 0,
-                  "%s: the depth buffers must be aligned to their element, verts, tris, tri_link, geom and norm_factor%s 4-byte, "
-                  "pred_zbuf, scene, pred_render, params, pose_in, pose_out, best and sums 8-byte aligned", who, SIL ? " and field" : "");
+    ANCSH_REQUIRE(depth_aligned(item, obs_depth, pred_depth) && all_aligned<4>(verts, tris, tri_link, geom, norm_factor, field) &&
+                      all_aligned<8>(pred_zbuf, scene, pred_render, params, pose_in, pose_out, best, sums), ANCSH_ALIGNED, who);
     ANCSH_REQUIRE(pose_in != pose_out, "%s: pose_in and pose_out overlap (a workgroup reads its pose while another writes: two buffers)", who);
     if (nframes == 0) return ANCSH_OK;
     const dim3 grid(K, 2, nframes);
@@ -823,22 +788,16 @@ extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, in
                                        const float *norm_factor, const double *params, int pass, int is_last, const double *pose_in, int ld_in,
                                        const double *sums, int sums_ld, double *pose_out, double *best, double *state, double *obj, double *xi,
                                        void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "refine_joint_step: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "refine_joint_step: %d frames exceed the 32767-frame range of ancsh_refine_pass; split the batch", nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "refine_joint_step: K=%d must be in [1, 8]", K);
+    ANCSH_CHECK(batch_ok("refine_joint_step", nframes, K, "exceed the 32767-frame range of ancsh_refine_pass"));
     ANCSH_REQUIRE(ninst >= 1 && ninst <= 65535, "refine_joint_step: ninst=%d kinematic tables must be in [1, 65535]", ninst);
-    ANCSH_REQUIRE(pass >= 0 && pass <= ANCSH_REFINE_MAX_ITERS, "refine_joint_step: pass=%d must be in [0, %d]", pass, ANCSH_REFINE_MAX_ITERS);
-    ANCSH_REQUIRE(is_last == 0 || is_last == 1, "refine_joint_step: is_last=%d must be 0 or 1", is_last);
-    ANCSH_REQUIRE(ld_in >= 26, "refine_joint_step: ld_in=%d, a record row holds at least the 26 pose columns", ld_in);
+    ANCSH_CHECK(pass_ok("refine_joint_step", pass, is_last));
+    ANCSH_CHECK(record_ld_ok("refine_joint_step", "ld_in", ld_in));
     ANCSH_REQUIRE(sums_ld == ANCSH_REFINE_SUMS || sums_ld == ANCSH_REFINE_SIL_SUMS, "refine_joint_step: sums_ld=%d must be %d (ancsh_refine_pass) or %d "
                   "(ancsh_refine_pass_sil)", sums_ld, ANCSH_REFINE_SUMS, ANCSH_REFINE_SIL_SUMS);
     ANCSH_REQUIRE(kin && scene && pred_render && norm_factor && params && pose_in && sums && pose_out && best && state && obj,
                   "refine_joint_step: null pointer");
-    ANCSH_REQUIRE(((size_t)kin & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)pred_render & 7) == 0 && ((size_t)norm_factor & 3) == 0 &&
-                      ((size_t)params & 7) == 0 && ((size_t)pose_in & 7) == 0 && ((size_t)sums & 7) == 0 && ((size_t)pose_out & 7) == 0 &&
-                      ((size_t)best & 7) == 0 && ((size_t)state & 7) == 0 && ((size_t)obj & 7) == 0 && ((size_t)xi & 7) == 0,
-                  "refine_joint_step: norm_factor must be 4-byte, kin, scene, pred_render, params, pose_in, sums, pose_out, best, state, obj and xi "
-                  "8-byte aligned");
+    ANCSH_REQUIRE(all_aligned<4>(norm_factor) && all_aligned<8>(kin, scene, pred_render, params, pose_in, sums, pose_out, best, state, obj, xi),
+                  ANCSH_ALIGNED, "refine_joint_step");
     ANCSH_REQUIRE(pose_in != pose_out, "refine_joint_step: pose_in and pose_out overlap (the poses the pass evaluated are read while the new ones are "
                   "written: two buffers)");
     ANCSH_REQUIRE(best != state, "refine_joint_step: best and state overlap (state is the object's shadow of the best block: a buffer of its own)");
@@ -850,16 +809,12 @@ extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, in
 
 extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
                                       long pixel_capacity, const int *geom, const double *scene, int *field, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "silhouette_field: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "silhouette_field: %d frames exceed the 32767-frame range of ancsh_refine_pass_sil; split the batch", nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "silhouette_field: K=%d must be in [1, 8]", K);
-    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
-                  "silhouette_field: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "silhouette_field: pixel_capacity=%ld pixels out of range", pixel_capacity);
+    ANCSH_CHECK(batch_ok("silhouette_field", nframes, K, "exceed the 32767-frame range of ancsh_refine_pass_sil"));
+    size_t item;
+    ANCSH_CHECK(depth_item("silhouette_field", depth_type, item));
+    ANCSH_CHECK(capacity_ok("silhouette_field", pixel_capacity));
     ANCSH_REQUIRE(obs_depth && obs_labels && geom && scene && field, "silhouette_field: null pointer");
-    const size_t item = depth_type == ANCSH_DEPTH_U16 ? 2 : 4;
-    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)geom & 3) == 0 && ((size_t)field & 3) == 0 && ((size_t)scene & 7) == 0,
-                  "silhouette_field: obs_depth must be aligned to its element, geom and field 4-byte, scene 8-byte aligned");
+    ANCSH_REQUIRE(depth_aligned(item, obs_depth) && all_aligned<4>(geom, field) && all_aligned<8>(scene), ANCSH_ALIGNED, "silhouette_field");
     if (nframes == 0) return ANCSH_OK;
     const dim3 grid(K, SF_SPLIT, nframes);
     if (depth_type == ANCSH_DEPTH_U16)
@@ -872,13 +827,11 @@ extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const 
 }
 
 extern "C" int ancsh_refine_rec(int nframes, int K, const double *best, const double *carried, int ld, double *wide, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "refine_rec: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "refine_rec: %d frames exceed the 32767-frame range of ancsh_refine_pass; split the batch", nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "refine_rec: K=%d must be in [1, 8]", K);
-    ANCSH_REQUIRE(ld >= 26 && ld <= 4096, "refine_rec: ld=%d, a record row holds at least the 26 pose columns and at most 4096", ld);
+    ANCSH_CHECK(batch_ok("refine_rec", nframes, K, "exceed the 32767-frame range of ancsh_refine_pass"));
+    ANCSH_CHECK(record_ld_ok("refine_rec", "ld", ld));
+    ANCSH_REQUIRE(ld <= 4096, "refine_rec: ld=%d, a record row holds at most 4096 columns", ld);
     ANCSH_REQUIRE(best && carried && wide, "refine_rec: null pointer");
-    ANCSH_REQUIRE(((size_t)best & 7) == 0 && ((size_t)carried & 7) == 0 && ((size_t)wide & 7) == 0,
-                  "refine_rec: best, carried and wide must be 8-byte aligned");
+    ANCSH_REQUIRE(all_aligned<8>(best, carried, wide), ANCSH_ALIGNED, "refine_rec");
     ANCSH_REQUIRE(carried != wide, "refine_rec: carried and wide overlap (the rows have different widths: wide is a buffer of its own)");
     if (nframes == 0) return ANCSH_OK;
     const long rows = (long)nframes * K, total = rows * (ld + RF_WIDTH);               // < 2^15 * 8 * 2^13 = 2^31

@@ -12,7 +12,7 @@
 //       bytes every run.
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).  The compare kernel reads the crops pixel by pixel:
 // K workgroups share a crop through the L2, and a crop is a few thousand pixels -- the launch sits near the floor of a dependent graph node.
-#include "depth_annotate_common.h"
+#include "compare_common.h"
 
 namespace ancsh {
 
@@ -29,16 +29,6 @@ __device__ __forceinline__ void rp_compose(const double *A, const double *B, dou
             C[4 * i + j] = j == 3 ? v + A[4 * i + 3] : v;
         }
     }
-}
-
-__device__ __forceinline__ bool rp_finite(double v) { return fabs(v) < __builtin_inf(); }      // NaN fails the comparison
-
-// a pose of the record, 13 values [R (9) | s | t (3)]: usable when every value is finite
-__device__ __forceinline__ bool rp_pose_ok(const double *__restrict__ p) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) ok = ok && rp_finite(p[k]);
-    return ok;
 }
 
 __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int nframes, int K, const double *__restrict__ render,
@@ -69,10 +59,10 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int n
         return;
     }
     const double *L = sc + AN_HEAD + AN_LINK * l;
-    const double pv = L[1], nf = (double)norm_factor[f];
-    const int j = scene_rank(sc, l, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
+    const double nf = (double)norm_factor[f];
+    const int j = scene_link_part(sc, l, nl, K);
     const double *pose = record + ((size_t)f * K + (j < 0 ? 0 : j)) * ld + 13 * v;
-    if (j < 0 || !rp_pose_ok(pose) || !rp_finite(nf) || nf == 0.0) {    // the renderer drops a triangle whose vertex is not finite
+    if (j < 0 || !pose_ok(pose) || !finite(nf) || nf == 0.0) {          // the renderer drops a triangle whose vertex is not finite
         const double q = __builtin_nan("");
 #pragma unroll
         for (int k = 0; k < ANCSH_RENDER_LINK; ++k) R[k] = q;
@@ -114,12 +104,6 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int n
     for (int a = 0; a < 3; ++a)                                         // 4. / norm factor, 5. (x, y, z) -> (x', y', z) = (x, -y, z)
 #pragma unroll
         for (int k = 0; k < 4; ++k) R[4 * a + k] = a == 1 ? -(T2[4 * a + k] / nf) : T2[4 * a + k] / nf;
-}
-
-// the part of a pixel, or -1: its label names a used link (s_part: 16 parts, -1 = not used or outside [0, K)) and its depth passes depth_ok
-template <typename T>
-__device__ __forceinline__ int rp_pixel_part(T d, unsigned char lab, const int *s_part) {
-    return lab < RP_LINKS && depth_ok(d) ? s_part[lab] : -1;
 }
 
 __device__ __forceinline__ long rp_quantum(unsigned short p, unsigned short o) { return (long)p - (long)o; }
@@ -167,11 +151,7 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_compare_kernel(int K, co
     __shared__ double s_d[RP_THREADS / 64];
     const int j = blockIdx.x, v = blockIdx.y, f = blockIdx.z, tid = threadIdx.x;
     const double *sc = scene + (size_t)f * AN_SCENE;
-    if (tid < RP_LINKS) {
-        const int nl = scene_nlinks(sc);
-        const double pv = sc[AN_HEAD + AN_LINK * tid + 1];
-        s_part[tid] = scene_rank(sc, tid, nl) >= 0 && pv >= 0.0 && pv < (double)K ? (int)pv : -1;
-    }
+    scene_part_table(sc, K, tid, s_part);
     const double *in = carried + ((size_t)f * K + j) * ld;
     double *out = wide + ((size_t)f * K + j) * (ld + RP_WIDTH);
     if (v == 0)
@@ -186,7 +166,7 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_compare_kernel(int K, co
     double d_abs = 0.0, d_sum = 0.0, d_sq = 0.0, d_max = 0.0;
     for (long a = start + tid; a < start + n; a += RP_THREADS) {
         const T od = obs_depth[a], qd = pd[a];
-        const bool o = rp_pixel_part(od, obs_labels[a], s_part) == j, p = rp_pixel_part(qd, pl[a], s_part) == j;
+        const bool o = pixel_part(od, obs_labels[a], s_part) == j, p = pixel_part(qd, pl[a], s_part) == j;
         n_obs += o;
         n_pred += p;
         if (o && p) {
@@ -232,7 +212,7 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_compare_kernel(int K, co
     }
     if (tid == 0) {
         const double q = __builtin_nan("");
-        const bool ok0 = rp_pose_ok(in), ok1 = rp_pose_ok(in + 13), ok = v == 0 ? ok0 : ok1;
+        const bool ok0 = pose_ok(in), ok1 = pose_ok(in + 13), ok = v == 0 ? ok0 : ok1;
         double *o = out + ld + 1 + 7 * v;
         if (v == 0) out[ld] = ok0 || ok1 ? (double)n_obs : q;
         const long uni = n_obs + n_pred - n_both;
@@ -254,20 +234,13 @@ using namespace ancsh;
 extern "C" int ancsh_reproject_scene_build(int nframes, int K, const double *render, const double *scene, const double *rig, int rig_ld,
                                            const float *norm_factor, const double *record, int ld, const int *geom, long pixel_capacity,
                                            double *render_out, int *geom_out, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "reproject_scene_build: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "reproject_scene_build: %d frames give more than the 65535 predicted frames the renderer takes; split the batch",
-                  nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "reproject_scene_build: K=%d must be in [1, 8]", K);
+    ANCSH_CHECK(batch_ok("reproject_scene_build", nframes, K, "give more than the 65535 predicted frames the renderer takes"));
     ANCSH_REQUIRE(rig_ld == ANCSH_RIG_WIDTH(K), "reproject_scene_build: rig_ld=%d, a rig of K=%d parts is %d wide", rig_ld, K, ANCSH_RIG_WIDTH(K));
-    ANCSH_REQUIRE(ld >= 26, "reproject_scene_build: ld=%d, a record row holds at least the 26 pose columns", ld);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29),
-                  "reproject_scene_build: pixel_capacity=%ld pixels out of range (the predicted frames take twice as many, below 2^30)",
-                  pixel_capacity);
+    ANCSH_CHECK(record_ld_ok("reproject_scene_build", "ld", ld));
+    ANCSH_CHECK(capacity_ok("reproject_scene_build", pixel_capacity));
     ANCSH_REQUIRE(render && scene && rig && norm_factor && record && geom && render_out && geom_out, "reproject_scene_build: null pointer");
-    ANCSH_REQUIRE(((size_t)render & 7) == 0 && ((size_t)scene & 7) == 0 && ((size_t)rig & 7) == 0 && ((size_t)record & 7) == 0 &&
-                      ((size_t)render_out & 7) == 0 && ((size_t)norm_factor & 3) == 0 && ((size_t)geom & 3) == 0 && ((size_t)geom_out & 3) == 0,
-                  "reproject_scene_build: render, scene, rig, record and render_out must be 8-byte aligned, norm_factor, geom and geom_out "
-                  "4-byte aligned");
+    ANCSH_REQUIRE(all_aligned<8>(render, scene, rig, record, render_out) && all_aligned<4>(norm_factor, geom, geom_out), ANCSH_ALIGNED,
+                  "reproject_scene_build");
     if (nframes == 0) return ANCSH_OK;
     const unsigned blocks = (unsigned)(((long)nframes * 2 * RP_LINKS + RP_THREADS - 1) / RP_THREADS);
     hipLaunchKernelGGL(reproject_scene_build_kernel, dim3(blocks), dim3(RP_THREADS), 0, (hipStream_t)stream, nframes, K, render, scene, rig,
@@ -278,20 +251,14 @@ extern "C" int ancsh_reproject_scene_build(int nframes, int K, const double *ren
 extern "C" int ancsh_reproject_compare_rec(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
                                            long pixel_capacity, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                                            const double *scene, const double *carried, int ld, double *wide, void *stream) {
-    ANCSH_REQUIRE(nframes >= 0, "reproject_compare_rec: bad shape nframes=%d", nframes);
-    ANCSH_REQUIRE(nframes <= 32767, "reproject_compare_rec: %d frames exceed the 32767-frame range of ancsh_reproject_scene_build; split the batch",
-                  nframes);
-    ANCSH_REQUIRE(K >= 1 && K <= 8, "reproject_compare_rec: K=%d must be in [1, 8]", K);
-    ANCSH_REQUIRE(depth_type == ANCSH_DEPTH_U16 || depth_type == ANCSH_DEPTH_F32,
-                  "reproject_compare_rec: depth_type=%d must be ANCSH_DEPTH_U16 (0) or ANCSH_DEPTH_F32 (1)", depth_type);
-    ANCSH_REQUIRE(pixel_capacity >= 0 && pixel_capacity < (1L << 29), "reproject_compare_rec: pixel_capacity=%ld pixels out of range",
-                  pixel_capacity);
-    ANCSH_REQUIRE(ld >= 26, "reproject_compare_rec: ld=%d, a record row holds at least the 26 pose columns", ld);
+    ANCSH_CHECK(batch_ok("reproject_compare_rec", nframes, K, "exceed the 32767-frame range of ancsh_reproject_scene_build"));
+    size_t item;
+    ANCSH_CHECK(depth_item("reproject_compare_rec", depth_type, item));
+    ANCSH_CHECK(capacity_ok("reproject_compare_rec", pixel_capacity));
+    ANCSH_CHECK(record_ld_ok("reproject_compare_rec", "ld", ld));
     ANCSH_REQUIRE(obs_depth && obs_labels && pred_depth && pred_labels && geom && scene && carried && wide, "reproject_compare_rec: null pointer");
-    const size_t item = depth_type == ANCSH_DEPTH_U16 ? 2 : 4;
-    ANCSH_REQUIRE(((size_t)obs_depth & (item - 1)) == 0 && ((size_t)pred_depth & (item - 1)) == 0 && ((size_t)geom & 3) == 0 &&
-                      ((size_t)scene & 7) == 0 && ((size_t)carried & 7) == 0 && ((size_t)wide & 7) == 0,
-                  "reproject_compare_rec: the depth buffers must be aligned to their element, geom 4-byte, scene, carried and wide 8-byte aligned");
+    ANCSH_REQUIRE(depth_aligned(item, obs_depth, pred_depth) && all_aligned<4>(geom) && all_aligned<8>(scene, carried, wide), ANCSH_ALIGNED,
+                  "reproject_compare_rec");
     ANCSH_REQUIRE(carried != wide, "reproject_compare_rec: carried and wide overlap (the rows have different widths: wide is a buffer of its own)");
     if (nframes == 0) return ANCSH_OK;
     const dim3 grid(K, 2, nframes);

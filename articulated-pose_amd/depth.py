@@ -26,6 +26,8 @@ Between the renderer and the annotation stands an optional depth sensor (ancsh_d
 is clean): one table per pipeline (pack_sensor) of range-dependent noise, holes, dropout at depth discontinuities and disparity steps turns
 the clean crops into the frames a real camera would deliver, in a second pair of pixel buffers.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -1064,17 +1066,14 @@ def render_depth_frames(mesh, render_scenes, crops, depth_dtype, device="cuda:0"
     return _cut_frames(depth.cpu().numpy(), labels.cpu().numpy(), geom, name)
 
 
-def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device="cuda:0"):
-    """Eager render-and-compare, the operator outside the pipeline: mesh = pack_mesh's arrays (or pack_mesh_library's), render_tables and
-    scenes = the frames' own tables (one of each, or one per frame), rigs = one dataset.pack_joint_rig table per frame, norm_factors = one
-    finite value per frame, record = the frames' (n, K, >= 26) float64 pose records (columns 0..12 the baseline pose, 13..25 the nonlinear
-    one), frames = the observed frames as render_depth_frames returns and sensor_frames degrades them: (depth_crop (h, w) of depth_dtype,
-    label_crop (h, w), (row0, col0)).  -> (columns (n, K, 15) float64, pose.reprojection.COLUMN_NAMES; predicted: per frame ((depth, labels)
-    under the baseline pose, (depth, labels) under the nonlinear pose), crops of the frame's own shape and origin -- the object where the fit
-    put it).  The three calls of the streamed step (ancsh_reproject_scene_build, the renderer on 2 n frames, ancsh_reproject_compare_rec) on
-    the same tables: a pipeline built with reprojection=True streams the same bytes.  One host sync; the pipeline has none."""
+_CompareFront = namedtuple("_CompareFront", "dev name mesh rec geom total tensors tables pred")
+
+
+def _compare_front(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device):
+    """The common opening of the two eager render-and-compare operators: their host arguments checked and staged.  tensors = what
+    reprojection_batch and refine_batch take between the mesh and the dtype name; (tables, pred) = pose.reprojection.predicted_frames'."""
     from .dataset import check_rigs
-    from .pose.reprojection import REPROJECTION_WIDTH, predicted_buffers, reprojection_batch
+    from .pose.reprojection import predicted_frames
     dev = _lib.cuda_device(device)
     name = check_depth_dtype(depth_dtype)
     rec = np.ascontiguousarray(record, np.float64)
@@ -1088,11 +1087,25 @@ def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record,
     tables, rigs = check_render_tables(render_tables, n, d_mesh.ninst), check_rigs(rigs, n, K)
     geom, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, name, dev, NOT_OBJECT)
     t = lambda a: torch.from_numpy(a).to(dev)
-    pred = predicted_buffers(total, name, dev)
-    out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
-    wide = reprojection_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred)
+    return _CompareFront(dev, name, d_mesh, rec, geom, total, (t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec)),
+                         *predicted_frames(n, total, name, dev))
+
+
+def reprojection_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device="cuda:0"):
+    """Eager render-and-compare, the operator outside the pipeline: mesh = pack_mesh's arrays (or pack_mesh_library's), render_tables and
+    scenes = the frames' own tables (one of each, or one per frame), rigs = one dataset.pack_joint_rig table per frame, norm_factors = one
+    finite value per frame, record = the frames' (n, K, >= 26) float64 pose records (columns 0..12 the baseline pose, 13..25 the nonlinear
+    one), frames = the observed frames as render_depth_frames returns and sensor_frames degrades them: (depth_crop (h, w) of depth_dtype,
+    label_crop (h, w), (row0, col0)).  -> (columns (n, K, 15) float64, pose.reprojection.COLUMN_NAMES; predicted: per frame ((depth, labels)
+    under the baseline pose, (depth, labels) under the nonlinear pose), crops of the frame's own shape and origin -- the object where the fit
+    put it).  The three calls of the streamed step (ancsh_reproject_scene_build, the renderer on 2 n frames, ancsh_reproject_compare_rec) on
+    the same tables: a pipeline built with reprojection=True streams the same bytes.  One host sync; the pipeline has none."""
+    from .pose.reprojection import REPROJECTION_WIDTH, reprojection_batch
+    F = _compare_front(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device)
+    rec, geom, total, name, pred = F.rec, F.geom, F.total, F.name, F.pred
+    wide = reprojection_batch(F.mesh, *F.tensors, name, F.tables, pred)
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
-    assert columns.shape == (n, K, REPROJECTION_WIDTH)
+    assert columns.shape == rec.shape[:2] + (REPROJECTION_WIDTH,)
     depth, plab = pred[0].cpu().numpy(), pred[1].cpu().numpy()
     views = [_cut_frames(depth, plab, geom, name, first=v * total) for v in (0, 1)]       # view v's crops lie `total` pixels further on
     return columns, [tuple(view[:2] for view in frame) for frame in zip(*views)]
@@ -1110,42 +1123,28 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
     object's pack_kinematics table (a library: the stack of its instances'): ancsh_refine_joint_step runs behind every pass, the best-of is
     kept per object, and debug=True returns (columns, sums, obj (iters + 1, n, 2, 8)): every pass's object rows,
     pose.refinement.OBJ_COLUMNS.  A pipeline built with refine= streams the same bytes.  One host sync; the pipeline has none."""
-    from .dataset import check_rigs
-    from .pose.reprojection import predicted_buffers
-    from .pose.refinement import REFINE_WIDTH, check_refine_table, field_buffer, has_joints, has_silhouette, refine_batch, refine_buffers
+    from .pose.refinement import REFINE_WIDTH, check_refine_table, has_joints, has_silhouette, refine_batch, refine_buffers
     table = check_refine_table(refine)
     iters = int(table[0])
     if has_joints(table) and kinematics is None:
         raise ValueError("refine=<pose.refinement.pack_refine(joints=...)> solves an object's parts together through the joints of its "
                          "kinematic table: it needs kinematics=<depth.pack_kinematics(...)>")
-    dev = _lib.cuda_device(device)
-    name = check_depth_dtype(depth_dtype)
-    rec = np.ascontiguousarray(record, np.float64)
-    if rec.ndim != 3 or rec.shape[2] < 26 or not 1 <= rec.shape[1] <= 8:
-        raise ValueError("record must be (n, K, >= 26) float64 with 1 <= K <= 8, got shape %s" % (rec.shape,))
+    F = _compare_front(mesh, render_tables, scenes, rigs, norm_factors, record, frames, depth_dtype, device)
+    rec, d_mesh, dev, kin = F.rec, F.mesh, F.dev, None
     n, K = rec.shape[:2]
-    depths, labels, origins, nf, scenes = check_annotated_frames(frames, norm_factors, scenes, depth_dtype, K)
-    if len(depths) != n:
-        raise ValueError("record holds %d frames, frames %d" % (n, len(depths)))
-    d_mesh = mesh_to_device(mesh, dev)
-    tables, rigs = check_render_tables(render_tables, n, d_mesh.ninst), check_rigs(rigs, n, K)
-    geom, total, (d_pix, d_lab, d_geom) = _stage_frames(depths, labels, origins, name, dev, NOT_OBJECT)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    pred = predicted_buffers(total, name, dev)
-    out_tables = (torch.zeros((2 * n, RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * n, GEOM_WORDS), dtype=torch.int32, device=dev))
-    sil, kin = has_silhouette(table), None
     if has_joints(table):
         kin = check_kinematics_library(kinematics, K) if np.ndim(kinematics) == 2 else check_kinematics(kinematics, K)
         if (kin.shape[0] if kin.ndim == 2 else None) != (d_mesh.ninst if is_mesh_library(mesh) else None):
             raise ValueError("kinematics and mesh must hold the same instances (a library: the np.stack of its instances' tables)")
-    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=sil, joints=kin is not None)
-    wide = refine_batch(d_mesh, t(tables), t(scenes), t(rigs), t(nf), d_geom, (d_pix, d_lab), t(rec), name, out_tables, pred, t(table), iters, buffers,
-                        field=field_buffer(K, total, dev) if sil else None, kin=None if kin is None else t(kin))
+    t = lambda a: torch.from_numpy(a).to(dev)
+    buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=has_silhouette(table), joints=kin is not None,
+                             pixel_capacity=F.total)
+    wide = refine_batch(d_mesh, *F.tensors, F.name, F.tables, F.pred, t(table), iters, buffers, kin=None if kin is None else t(kin))
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
     assert columns.shape == (n, K, REFINE_WIDTH)
     if not debug:
         return columns
-    return (columns, buffers[2].cpu().numpy()) + ((buffers[3][1].cpu().numpy(),) if kin is not None else ())
+    return (columns, buffers.sums.cpu().numpy()) + ((buffers.obj.cpu().numpy(),) if kin is not None else ())
 
 
 # ---- posed objects: a kinematic table and joint values + a view per frame -> both tables above (ancsh_pose_scene_build), and crops centred

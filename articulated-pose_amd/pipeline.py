@@ -101,7 +101,7 @@ class _Slot(object):
         self.perm = self.src_rows = self.gt_built = self.frame_built = None
         for inp in EVERY_INPUT:                 # a side input the slot is not built with: no device buffer
             setattr(self, inp.name, None)
-        self.bounds = self.reproj_tables = self.reproj_pix = self.refine_bufs = self.refine_field = None
+        self.bounds = self.reproj_tables = self.reproj_pix = self.refine_bufs = None
         if opts.raw_capacity is not None:
             self._init_stream(B, N, K, device, opts)
 
@@ -164,16 +164,14 @@ class _Slot(object):
         if opts.build_gt_pose:                 # what ancsh_gt_pose_build writes behind the sampler and the two error launches read: slot-owned,
             self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
             self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
-        if opts.reprojection or opts.refine:  # the predicted frames' render tables and geometry rows (ancsh_reproject_scene_build) and the pixel
-            from .depth import GEOM_WORDS, RENDER_WIDTH          # triple the renderer draws them into, two crops per frame: slot-owned, shared
-            from .pose.reprojection import predicted_buffers     # with the range guard's f32 graph (the wide record is the graph's own)
-            self.reproj_tables = (torch.zeros((2 * B, RENDER_WIDTH), dtype=torch.float64, device=device),
-                                  torch.zeros((2 * B, GEOM_WORDS), dtype=torch.int32, device=device))
-            self.reproj_pix = predicted_buffers(cap, depth, device)
-        if opts.refine:                      # the loop's two working records, its best block and one pass's sums: slot-owned, shared with the
-            from .pose.refinement import field_buffer, refine_buffers      # range guard's f32 graph like the tables and the pixel triple above
-            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints)      # joints: state and obj too
-            self.refine_field = field_buffer(K, cap, device) if opts.silhouette else None      # the silhouette term: 4 bytes per pixel and part
+        # the predicted frames' tables and the pixel triple the renderer draws them into, two crops per frame; with refine= the loop's buffers
+        # (the silhouette term's field: 4 bytes per pixel and part).  Slot-owned, shared with the range guard's f32 graph.
+        if opts.reprojection or opts.refine:
+            from .pose.reprojection import predicted_frames
+            self.reproj_tables, self.reproj_pix = predicted_frames(B, cap, depth, device)
+        if opts.refine:
+            from .pose.refinement import refine_buffers
+            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints, pixel_capacity=cap)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -614,9 +612,9 @@ class AncshPipeline(object):
             out["record_refined"] = refine_batch(self.mesh, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sl.geom, (sl.apix, sl.amask),
                                                  out[carried("refinement")[0]], self.depth_dtype,
                                                  sl.reproj_tables, sl.reproj_pix, self.refine_table, self.refine_iters, sl.refine_bufs,
-                                                 field=sl.refine_field, kin=self.kin if self.opts.refine_joints else None)
+                                                 kin=self.kin if self.opts.refine_joints else None)
             if self.opts.refine_joints:  # the joint step's row per (frame, pose): (B, 2, 8) float64, slot-owned, not streamed
-                out["refine_object"] = sl.refine_bufs[3][1][0]
+                out["refine_object"] = sl.refine_bufs.obj[0]
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:

@@ -9,10 +9,13 @@ ancsh_refine_pass_sil adds one row per predicted pixel that hangs over the obser
 such pixels in the cost.  Each part is refined on its own -- unless the table is one of pack_refine(joints=...) and the object's kinematic
 table is at hand: then ancsh_refine_joint_step runs behind every pass, solves the object's parts together through rows that keep each
 revolute and prismatic joint's two sides on one axis, and keeps the best-of per object."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from .. import _lib
+from .reprojection import _tables
 
 REFINE_WIDTH = 36               # include/ancsh_hip.h, ANCSH_REFINE_WIDTH: the columns behind the carried record row, 18 per pose
 REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH_REFINE_PARAMS, ANCSH_REFINE_MAX_ITERS
@@ -27,6 +30,9 @@ POSE_COLUMNS = tuple("R%d%d" % (a, k) for a in range(3) for k in range(3)) + ("s
 COLUMN_NAMES = tuple("baseline_" + c for c in POSE_COLUMNS) + tuple("nonlinear_" + c for c in POSE_COLUMNS)
 SUMS_COLUMNS = dict(A=slice(0, 21), b=slice(21, 27), rr=27, n_used=28, n_obs=29, cost=30, solved=31)
 SIL_SUMS_COLUMNS = dict(SUMS_COLUMNS, mm=32, n_sil=33, n_far=34)
+PARAMS_LENGTHS = {"ancsh_refine_pass": (REFINE_PARAMS, REFINE_JOINT_PARAMS), "ancsh_refine_pass_sil": (REFINE_SIL_PARAMS, REFINE_JOINT_PARAMS),
+                  "ancsh_refine_joint_step": (REFINE_JOINT_PARAMS,)}      # the params table per entry: the joint step's holds both shorter ones in front
+RefineBuffers = namedtuple("RefineBuffers", "work best sums field state obj xi")      # refine_buffers' record; None = a term that is off
 BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, render_mesh=<depth.pack_mesh(...)>"
 
 
@@ -175,13 +181,23 @@ def _f64(name, t, shape):
         raise ValueError("%s must be a contiguous %s float64 tensor" % (name, tuple(shape)))
 
 
-def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False):
-    """What a slot owns for the loop: (work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2, 32 -- 36 with the
-    silhouette term)), float64.  joints=True: a fourth element, the joint step's two buffers and its debug output: (state (B, K, 2, 18), obj
-    (passes, B, 2, 8), xi (passes, B, 2, 48) -- None with one pass)."""
+def _params(entry, params):
+    if params.dtype != torch.float64 or params.dim() != 1 or int(params.shape[0]) not in PARAMS_LENGTHS[entry] or not params.is_contiguous():
+        raise ValueError("params must be a contiguous float64 table of %s values (pack_refine) for %s"
+                         % (" or ".join(str(n) for n in PARAMS_LENGTHS[entry]), entry))
+
+
+def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False, pixel_capacity=None):
+    """What a slot owns for the loop, a RefineBuffers record: work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2,
+    32 -- 36 with the silhouette term), float64; silhouette=True: field = field_buffer's planes of pixel_capacity pixels; joints=True: state
+    (B, K, 2, 18), obj (passes, B, 2, 8) and the debug output xi (passes, B, 2, 48) -- None with one pass."""
+    if silhouette and pixel_capacity is None:
+        raise ValueError("refine_buffers(silhouette=True) allocates the field with the rest: it needs pixel_capacity")
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
-    bufs = (z(B, K, 26), z(B, K, 26)), z(B, K, 2, BEST_WIDTH), z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS)
-    return bufs + ((z(B, K, 2, BEST_WIDTH), z(passes, B, 2, REFINE_OBJ), z(passes, B, 2, JOINT_XI) if passes > 1 else None),) if joints else bufs
+    return RefineBuffers(work=(z(B, K, 26), z(B, K, 26)), best=z(B, K, 2, BEST_WIDTH),
+                         sums=z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS),
+                         field=field_buffer(K, pixel_capacity, device) if silhouette else None, state=z(B, K, 2, BEST_WIDTH) if joints else None,
+                         obj=z(passes, B, 2, REFINE_OBJ) if joints else None, xi=z(passes, B, 2, JOINT_XI) if joints and passes > 1 else None)
 
 
 def field_buffer(K, pixel_capacity, device):
@@ -193,16 +209,13 @@ def silhouette_field(obs_depth, obs_labels, geom, scene, K, out=None):
     """ancsh_silhouette_field on device tensors (no host sync): the observed pair (pixel_capacity,), geom (B, 5) int32, scene (B, 240) ->
     field (K, pixel_capacity) int32: per crop pixel and part the offset to the nearest pixel observed for the part, (di & 0xffff) | (dj &
     0xffff) << 16, FIELD_SENTINEL in both halves for a part without one.  Words outside the crops are left as they are."""
-    from ..depth import GEOM_WORDS, SCENE_WIDTH, _byte_plane, _depth_plane
+    from ..depth import _byte_plane, _depth_plane
     _lib.require_device(obs_depth)
     kind, cap = _depth_plane(obs_depth)
     _byte_plane("labels", obs_labels, cap)
     if not 1 <= int(K) <= 8:
         raise ValueError("K=%d must be in [1, 8]" % K)
-    if geom.dtype != torch.int32 or geom.dim() != 2 or geom.shape[1] != GEOM_WORDS or not geom.is_contiguous():
-        raise ValueError("geom must be a contiguous (B, %d) int32 tensor" % GEOM_WORDS)
-    B = int(geom.shape[0])
-    _f64("scene", scene, (B, SCENE_WIDTH))
+    B = _tables(None, scene, None, None, None, geom, int(K))
     if out is None:
         out = field_buffer(K, cap, obs_depth.device)
     if out.dtype != torch.int32 or tuple(out.shape) != (int(K), cap) or not out.is_contiguous():
@@ -219,30 +232,24 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     pred = pose.reprojection.predicted_buffers' triple as the renderer left it for pred_render (2B, 208), the tables of pose_in (B, K, >= 26);
     params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out.
     field = silhouette_field's (K, pixel_capacity) planes: ancsh_refine_pass_sil, with a (16,) table and sums (B, K, 2, 36)."""
-    from ..depth import GEOM_WORDS, RENDER_WIDTH, SCENE_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
+    from ..depth import RENDER_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
     _lib.require_device(pose_in)
     verts, tris, tri_link, V, T = _check_device_mesh(mesh)[:5]
     kind, cap = _depth_plane(obs_depth)
     _byte_plane("labels", obs_labels, cap)
     _pixel_pair("the predicted pair", "observed", pred[0], pred[1], obs_depth.dtype, 2 * cap)
     _scratch_size(pred[2], 2 * cap, torch.int64)
-    if pose_in.dtype != torch.float64 or pose_in.dim() != 3 or pose_in.shape[2] < 26 or not pose_in.is_contiguous():
-        raise ValueError("pose_in must be a contiguous (B, K, >= 26) float64 tensor")
-    B, K, ld = (int(v) for v in pose_in.shape)
-    _f64("scene", scene, (B, SCENE_WIDTH))
+    K = int(pose_in.shape[1]) if pose_in.dim() == 3 else 0
+    B = _tables(None, scene, None, norm_factor, pose_in, geom, K, name="pose_in")
+    ld = int(pose_in.shape[2])
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
     sil = field is not None
-    if tuple(params.shape) != (REFINE_JOINT_PARAMS,):                     # the joint step's table holds both shorter ones in front
-        _f64("params", params, (REFINE_SIL_PARAMS if sil else REFINE_PARAMS,))
-    _f64("params", params, tuple(params.shape))
+    _params("ancsh_refine_pass_sil" if sil else "ancsh_refine_pass", params)
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
     _f64("sums", sums, (B, K, 2, REFINE_SIL_SUMS if sil else REFINE_SUMS))
     if sil and (field.dtype != torch.int32 or tuple(field.shape) != (K, cap) or not field.is_contiguous()):
         raise ValueError("field must be a contiguous (%d, %d) int32 tensor" % (K, cap))
-    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, GEOM_WORDS) or not geom.is_contiguous() or norm_factor.dtype != torch.float32 \
-            or tuple(norm_factor.shape) != (B,) or not norm_factor.is_contiguous():
-        raise ValueError("geom must be a contiguous (%d, %d) int32 tensor and norm_factor a contiguous (%d,) float32 tensor" % (B, GEOM_WORDS, B))
     _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums, field)
     head = (B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap,
             _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
@@ -260,17 +267,16 @@ def refine_joint_step(kin, scene, pred_render, norm_factor, params, pass_index, 
     arguments: kin = the object's kinematic table (672,) or a library's (ninst, 672) on the device; params = a pack_refine(joints=...) table
     (24,); sums (B, K, 2, 32 or 36) what the pass wrote.  Overwrites pose_out (B, K, 26) and best (B, K, 2, 18); state (B, K, 2, 18) and obj
     (B, 2, 8; OBJ_COLUMNS) are its own, written on pass 0 and carried from pass to pass; xi (B, 2, 48) or None: the clamped step.  -> pose_out."""
-    from ..depth import KIN_WIDTH, RENDER_WIDTH, SCENE_WIDTH
+    from ..depth import KIN_WIDTH, RENDER_WIDTH
     _lib.require_device(pose_in)
-    if pose_in.dtype != torch.float64 or pose_in.dim() != 3 or pose_in.shape[2] < 26 or not pose_in.is_contiguous():
-        raise ValueError("pose_in must be a contiguous (B, K, >= 26) float64 tensor")
-    B, K, ld = (int(v) for v in pose_in.shape)
+    B, K = (int(v) for v in pose_in.shape[:2]) if pose_in.dim() == 3 else (0, 0)
+    _tables(None, scene, None, norm_factor, pose_in, None, K, name="pose_in", B=B)
+    ld = int(pose_in.shape[2])
     if kin.dtype != torch.float64 or kin.dim() not in (1, 2) or kin.shape[-1] != KIN_WIDTH or kin.shape[0] < 1 or not kin.is_contiguous():
         raise ValueError("kin must be a contiguous (%d,) or (ninst, %d) float64 tensor (depth.pack_kinematics)" % (KIN_WIDTH, KIN_WIDTH))
     ninst = int(kin.shape[0]) if kin.dim() == 2 else 1
-    _f64("scene", scene, (B, SCENE_WIDTH))
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
-    _f64("params", params, (REFINE_JOINT_PARAMS,))
+    _params("ancsh_refine_joint_step", params)
     if sums.dim() != 4 or sums.shape[3] not in (REFINE_SUMS, REFINE_SIL_SUMS):
         raise ValueError("sums must be a contiguous (%d, %d, 2, %d or %d) float64 tensor" % (B, K, REFINE_SUMS, REFINE_SIL_SUMS))
     _f64("sums", sums, (B, K, 2, int(sums.shape[3])))
@@ -280,8 +286,6 @@ def refine_joint_step(kin, scene, pred_render, norm_factor, params, pass_index, 
     _f64("obj", obj, (B, 2, REFINE_OBJ))
     if xi is not None:
         _f64("xi", xi, (B, 2, JOINT_XI))
-    if norm_factor.dtype != torch.float32 or tuple(norm_factor.shape) != (B,) or not norm_factor.is_contiguous():
-        raise ValueError("norm_factor must be a contiguous (%d,) float32 tensor" % B)
     _lib.require_cuda(kin, scene, pred_render, norm_factor, params, sums, pose_out, best, state, obj, xi)
     _lib.call("ancsh_refine_joint_step", B, K, _lib.ptr(kin), ninst, _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
               _lib.ptr(params), int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld, _lib.ptr(sums), int(sums.shape[3]),
@@ -305,20 +309,20 @@ def refine_rec(best, carried, out=None):
     return out
 
 
-def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers, field=None,
-                 kin=None):
+def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred, params, iters, buffers, kin=None):
     """The captured step's sequence, no host sync and no allocation beyond the output: iters + 1 times ancsh_reproject_scene_build on the
     working poses, the renderer, ancsh_refine_pass; then ancsh_refine_rec -- 5 (iters + 1) + 1 launches.  tables and pred are
     pose.reprojection's slot-owned pair and triple (shared with reprojection=True, whose three calls come first); params = pack_refine's
     table on the device and iters its first value on the host; buffers = refine_buffers'.  sums of `passes` > 1 rows keeps every pass's sums
-    (pass p in row p); one row holds the last pass's.  field = field_buffer's planes, with a (16,) table: ancsh_silhouette_field once in
+    (pass p in row p); one row holds the last pass's.  refine_buffers(silhouette=True), with a (16,) table: ancsh_silhouette_field once in
     front of the loop and ancsh_refine_pass_sil in it -- 5 (iters + 1) + 2 launches.  kin = the kinematic table(s) on the device, with a
     (24,) table and refine_buffers(joints=True): ancsh_refine_joint_step behind every pass -- 6 (iters + 1) + 1 launches (+ 1 with the field);
     obj and xi of `passes` > 1 rows keep every pass's (one device copy carries the object's row on).  -> (B, K, ld + 36) float64."""
     from ..depth import render_depth
     from .reprojection import reproject_scene_build
-    work, best, sums = buffers[:3]
-    if (kin is not None) != (len(buffers) == 4):
+    work, best, sums, field, state, obj, xi = buffers
+    joints = kin is not None
+    if joints != (state is not None):
         raise ValueError("the joint step takes both kin and refine_buffers(joints=True)")
     cap = int(obs[0].shape[0])
     src = carried
@@ -330,8 +334,7 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
         dst = work[p % 2]
         refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
                     sums[p if sums.shape[0] > 1 else 0], field=field)
-        if kin is not None:
-            state, obj, xi = buffers[3]
+        if joints:
             if p and obj.shape[0] > 1:
                 obj[p].copy_(obj[p - 1])
             refine_joint_step(kin, scene, tables[0], norm_factor, params, p, p == iters, src, sums[p if sums.shape[0] > 1 else 0], dst, best,

@@ -5,6 +5,8 @@ a pose on the 15 columns without copying a pixel back."""
 import torch
 
 from .. import _lib
+from ..dataset import RIG_WIDTH
+from ..depth import GEOM_WORDS, RENDER_WIDTH, SCENE_WIDTH
 
 REPROJECTION_WIDTH = 15         # include/ancsh_hip.h, ANCSH_REPROJECTION_WIDTH: the columns behind the carried record row
 # the columns, counted from the end of the carried row: the observed pixels of the part, then seven per pose
@@ -32,17 +34,18 @@ def named_columns(columns):
     return {name: tail[..., k] for k, name in enumerate(COLUMN_NAMES)}
 
 
-def _tables(render, scene, rig, norm_factor, record, geom, K):
-    from ..dataset import RIG_WIDTH
-    from ..depth import GEOM_WORDS, RENDER_WIDTH, SCENE_WIDTH
-    B = int(geom.shape[0])
-    for name, t, shape, dtype in (("render", render, (B, RENDER_WIDTH), torch.float64), ("scene", scene, (B, SCENE_WIDTH), torch.float64),
-                                  ("rig", rig, (B, RIG_WIDTH(K)), torch.float64), ("norm_factor", norm_factor, (B,), torch.float32),
-                                  ("geom", geom, (B, GEOM_WORDS), torch.int32)):
+def _tables(render, scene, rig, norm_factor, record, geom, K, name="record", B=None):
+    """The family's check of device tables (pose.refinement's wrappers call it too): every table that is not None against the frame count B
+    (geom's rows unless given) and K, and `record` -- a pose record or a working pose buffer, under its argument's name -- as (B, K, >= 26)."""
+    B = (int(geom.shape[0]) if geom.dim() else 0) if B is None else B    # geom's rows; a 0-dim geom fails its shape check below
+    for what, t, shape, dtype in (("render", render, (B, RENDER_WIDTH), torch.float64), ("scene", scene, (B, SCENE_WIDTH), torch.float64),
+                                  ("rig", rig, (B, RIG_WIDTH(K)) if rig is not None else None, torch.float64),
+                                  ("norm_factor", norm_factor, (B,), torch.float32), ("geom", geom, (B, GEOM_WORDS), torch.int32)):
         if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous %s %s tensor" % (name, shape, str(dtype).replace("torch.", "")))
-    if record.dtype != torch.float64 or record.dim() != 3 or tuple(record.shape[:2]) != (B, K) or record.shape[2] < 26 or not record.is_contiguous():
-        raise ValueError("record must be a contiguous (%d, %d, >= 26) float64 tensor" % (B, K))
+            raise ValueError("%s must be a contiguous %s %s tensor" % (what, shape, str(dtype).replace("torch.", "")))
+    if record is not None and (record.dtype != torch.float64 or record.dim() != 3 or tuple(record.shape[:2]) != (B, K) or record.shape[2] < 26
+                               or not record.is_contiguous()):
+        raise ValueError("%s must be a contiguous (%d, %d, >= 26) float64 tensor" % (name, B, K))
     return B
 
 
@@ -51,7 +54,6 @@ def reproject_scene_build(render, scene, rig, norm_factor, record, geom, pixel_c
     RIG_WIDTH(K)), norm factors (B,) float32, record (B, K, >= 26) float64 and geometry rows (B, 5) int32 in a buffer of pixel_capacity
     pixels -> (render tables (2B, 208) float64, geometry rows (2B, 5) int32) of the predicted frames, row v * B + f; out = the same pair
     preallocated (a captured step passes slot-owned buffers)."""
-    from ..depth import GEOM_WORDS, RENDER_WIDTH
     _lib.require_device(record)
     K = int(record.shape[1]) if record.dim() == 3 else 0
     B = _tables(render, scene, rig, norm_factor, record, geom, K)
@@ -97,6 +99,13 @@ def predicted_buffers(capacity, depth_dtype, device):
     tt = DEPTH_DTYPES[check_depth_dtype(depth_dtype)][1]
     return (torch.zeros((2 * capacity,), dtype=tt, device=device), torch.full((2 * capacity,), NOT_OBJECT, dtype=torch.uint8, device=device),
             torch.zeros((2 * capacity,), dtype=torch.int64, device=device))
+
+
+def predicted_frames(B, capacity, depth_dtype, device):
+    """What the predicted frames of B observed ones live in, slot-owned and shared by reprojection and refinement: (tables = the pair
+    reproject_scene_build writes, render (2B, 208) float64 and geom (2B, 5) int32; pred = predicted_buffers' triple)."""
+    tables = (torch.zeros((2 * B, RENDER_WIDTH), dtype=torch.float64, device=device), torch.zeros((2 * B, GEOM_WORDS), dtype=torch.int32, device=device))
+    return tables, predicted_buffers(capacity, depth_dtype, device)
 
 
 def reprojection_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, depth_dtype, tables, pred):

@@ -7,23 +7,13 @@ import math
 import numpy as np
 
 import refinement_mirror as RF
+from reprojection_mirror import link_parts
 
 PARAMS, OBJ, XI, BEST = 24, 8, 48, 18
 KIN_WIDTH, KIN_HEAD, KIN_LINK = 672, 32, 40
-RENDER_HEAD, RENDER_LINK, SCENE_HEAD, SCENE_LINK, MAX_LINKS = 16, 12, 16, 14, 16
+RENDER_HEAD, RENDER_LINK = 16, 12
 NAN = float("nan")
 dot = RF.dot
-
-
-def link_parts(sc, K):
-    """The pass kernel's s_part rule: the part of every link, -1 for a link beyond nlinks, without a rank, or of a part outside [0, K)."""
-    nl = int(sc[14]) if 1.0 <= sc[14] <= MAX_LINKS else 0
-    out = [-1] * MAX_LINKS
-    for l in range(nl):
-        rank, pv = float(sc[SCENE_HEAD + SCENE_LINK * l]), float(sc[SCENE_HEAD + SCENE_LINK * l + 1])
-        if 0.0 <= rank < MAX_LINKS and 0.0 <= pv < K:
-            out[l] = int(pv)
-    return out, nl
 
 
 def link_map(rt, l):

@@ -71,7 +71,8 @@ def test_one_call_behind_a_rendered_pass_equals_the_mirror(dev, K, dtype):
     pred = predicted_buffers(cap, dtype, dev)
     tables = reproject_scene_build(d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, cap)
     render_depth(d_mesh, tables[1], tables[0], dtype, out=pred[:2], scratch=pred[2])
-    (w0, _), best, sums = refine_buffers(3, K, dev)[:3]
+    bufs = refine_buffers(3, K, dev)
+    w0, best, sums = bufs.work[0], bufs.best, bufs.sums
     refine_pass(d_mesh, od, ol, pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, d_rec, w0, best, sums[0])
     h_tables, h_sums, h_out = tables[0].cpu().numpy(), sums[0].cpu().numpy(), w0.cpu().numpy()
     assert _bytes(h_tables, RP.scene_tables(render, scene, rigs, nf, wide, geom, cap)[0])
@@ -167,6 +168,18 @@ def test_special_cases_equal_the_mirror(dev):
         k2 = kin.copy()
         k2[32 + 40 * 1 + 3] = value
         assert (_against_the_mirror(dev, k2, scene, tables, nf, table, 0, False, moved, S, fresh())[4][:, :, 5] == 1).all(), value
+    # the instance a table names in value 9, one frame, K = 2, one revolute joint, a 16 x 16 crop: not an integer, negative, >= ninst -> no
+    # joint is active and nothing is solved; 0 -> the joint is
+    K2, maps2 = TREES["K2-revolute-two-link-part"]
+    kin2, render2, scene2, rigs2, nf2, _, _, rec2 = tree_problem(K2, maps2)
+    render2, scene2, rigs2, nf2, rec2 = (a[:1] for a in (render2, scene2, rigs2, nf2, rec2))
+    moved2 = moved_record(rs, rec2, 0.01)
+    t2, _ = RP.scene_tables(render2, scene2, rigs2, nf2, moved2, np.array([[0, 16, 16, 0, 0]], np.int32), 256)
+    S2 = np.stack([np.stack([hand_sums(rs, K2, b_scale=1e-3) for v in range(2)], 1)])
+    for value, active in ((0.0, 1), (0.5, 0), (-1.0, 0), (1.0, 0)):
+        t2[:, 9] = value
+        o = _against_the_mirror(dev, kin2, scene2, t2, nf2, table, 0, False, moved2, S2, moved2[:, :, :26].copy())
+        assert (o[4][:, :, 5] == active).all() and (o[4][:, :, 6] == active).all() and ((o[0] == 0).all() != bool(active)), value
     # K = 1: no joint, no solve; the best-of still runs
     kin1, render1, scene1, rigs1, nf1, geom1, cap1, rec1 = tree_problem(1, [[0, 1, 2, 3]])
     t1, _ = RP.scene_tables(render1, scene1, rigs1, nf1, rec1, geom1, cap1)
@@ -253,10 +266,10 @@ def _both(K, dtype, table, plain, feed, **kw):
         P = _pipe(K, dtype, refine=refine, **kw)
         names.append(_launch_names(P.prepare()))
         sl = P.slots[0]
-        assert (len(sl.refine_bufs) == 4) == (refine is table) and P.opts.refine_joints == (refine is table)
+        assert (sl.refine_bufs.state is not None) == (refine is table) and P.opts.refine_joints == (refine is table)
         if refine is table:
-            shapes = [tuple(t.shape) for t in sl.refine_bufs[3][:2]]
-            assert sl.refine_bufs[3][2] is None and all(s.refine_bufs[3][0].data_ptr() != sl.refine_bufs[3][0].data_ptr() for s in P.slots[1:])
+            shapes = [tuple(t.shape) for t in (sl.refine_bufs.state, sl.refine_bufs.obj)]
+            assert sl.refine_bufs.xi is None and all(s.refine_bufs.state.data_ptr() != sl.refine_bufs.state.data_ptr() for s in P.slots[1:])
             assert sl.out["refine_object"].shape == (B_, 2, 8) and (sl.graph32 is None or sl.out32["refine_object"].data_ptr() == sl.out["refine_object"].data_ptr())
         else:
             assert "refine_object" not in sl.out

@@ -83,7 +83,8 @@ def test_one_pass_equals_the_mirror(dev, K, dtype, sapien):
     pred = predicted_buffers(cap, dtype, dev)
     tables = reproject_scene_build(d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, cap)
     render_depth(d_mesh, tables[1], tables[0], dtype, out=pred[:2], scratch=pred[2])
-    (w0, _), best, sums = refine_buffers(3, K, dev)
+    bufs = refine_buffers(3, K, dev)
+    w0, best, sums = bufs.work[0], bufs.best, bufs.sums
     first = None
     for _ in range(2):
         for b in (w0, best, sums):
@@ -213,7 +214,7 @@ def _loop_on_device(dev, prob, rec, dtype, table):
     wide = refine_batch(mesh_to_device(mesh, dev), d_rt, d_sc, d_rig, d_nf, d_geom, (od, ol), d_rec, dtype, tables, predicted_buffers(cap, dtype, dev),
                         d_par, iters, bufs)
     assert _bytes(wide[:, :, :rec.shape[2]].cpu().numpy(), rec)
-    return wide[:, :, rec.shape[2]:].cpu().numpy(), bufs[2].cpu().numpy()
+    return wide[:, :, rec.shape[2]:].cpu().numpy(), bufs.sums.cpu().numpy()
 
 
 # ---- the stream -------------------------------------------------------------------------------------------------------------------------------
@@ -264,8 +265,8 @@ def test_posed_keyed_stream_equals_the_eager_operator_and_the_plain_pipeline(dev
             loop = ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_refine_pass"]
             assert names[-10:] == loop * 3 + ["ancsh_refine_rec"], names[-12:]
             assert names[-13:-10] == ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_reproject_compare_rec"]
-            assert [tuple(t.shape) for t in sl.refine_bufs[0]] == [(B_, K, 26)] * 2 and sl.refine_bufs[1].shape == (B_, K, 2, 18)
-            assert sl.refine_bufs[2].shape == (1, B_, K, 2, 32) and all(s.refine_bufs[1].data_ptr() != sl.refine_bufs[1].data_ptr() for s in P.slots[1:])
+            assert [tuple(t.shape) for t in sl.refine_bufs.work] == [(B_, K, 26)] * 2 and sl.refine_bufs.best.shape == (B_, K, 2, 18)
+            assert sl.refine_bufs.sums.shape == (1, B_, K, 2, 32) and all(s.refine_bufs.best.data_ptr() != sl.refine_bufs.best.data_ptr() for s in P.slots[1:])
             assert sl.out["record"].shape == (B_, K, 26) and sl.out["record_refined"].shape == (B_, K, 39 + 21 + 15 + 36)
             assert sl.out["record_reproj"].shape == (B_, K, 39 + 21 + 15)
             assert (L.width, L.key, L.carried("refinement")) == (39 + 21 + 15 + 36, "record_refined", ("record_reproj", 39 + 21 + 15))

@@ -132,7 +132,7 @@ def _loop_on_device(dev, prob, rec, dtype, table, frames=None):
     factor) -> (columns, sums (iters + 1, ...), the launches' names)."""
     from articulated_pose_amd import _lib
     from articulated_pose_amd.depth import mesh_to_device
-    from articulated_pose_amd.pose.refinement import field_buffer, refine_batch, refine_buffers
+    from articulated_pose_amd.pose.refinement import refine_batch, refine_buffers
     from articulated_pose_amd.pose.reprojection import predicted_buffers
     mesh, kin, render, scene, rigs, nf, geom, cap, own = prob
     n, K = rec.shape[:2]
@@ -140,16 +140,16 @@ def _loop_on_device(dev, prob, rec, dtype, table, frames=None):
     od, ol = (_t(a, dev) for a in _flat(prob[:8] + (own if frames is None else frames,), dtype))
     d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, d_par = (_t(a, dev) for a in (render, scene, rigs, nf, rec, geom, table))
     tables = (torch.zeros((2 * n, 208), dtype=torch.float64, device=dev), torch.zeros((2 * n, 5), dtype=torch.int32, device=dev))
-    bufs = refine_buffers(n, K, dev, passes=iters + 1, silhouette=True)
+    bufs = refine_buffers(n, K, dev, passes=iters + 1, silhouette=True, pixel_capacity=cap)
     names, real = [], _lib.call
     _lib.call = lambda name, *a: (names.append(name), real(name, *a))[1]
     try:
         wide = refine_batch(mesh_to_device(mesh, dev), d_rt, d_sc, d_rig, d_nf, d_geom, (od, ol), d_rec, dtype, tables,
-                            predicted_buffers(cap, dtype, dev), d_par, iters, bufs, field=field_buffer(K, cap, dev))
+                            predicted_buffers(cap, dtype, dev), d_par, iters, bufs)
     finally:
         _lib.call = real
     assert _bytes(wide[:, :, :rec.shape[2]].cpu().numpy(), rec)
-    return wide[:, :, rec.shape[2]:].cpu().numpy(), bufs[2].cpu().numpy(), names
+    return wide[:, :, rec.shape[2]:].cpu().numpy(), bufs.sums.cpu().numpy(), names
 
 
 @pytest.mark.parametrize("K,dtype,sapien", CASES, ids=IDS)
@@ -173,7 +173,8 @@ def test_one_pass_equals_the_mirror(dev, K, dtype, sapien):
     pred = predicted_buffers(cap, dtype, dev)
     tables = reproject_scene_build(d_rt, d_sc, d_rig, d_nf, d_rec, d_geom, cap)
     render_depth(d_mesh, tables[1], tables[0], dtype, out=pred[:2], scratch=pred[2])
-    (w0, _), best, sums = refine_buffers(3, K, dev, silhouette=True)
+    bufs = refine_buffers(3, K, dev, silhouette=True, pixel_capacity=cap)
+    w0, best, sums = bufs.work[0], bufs.best, bufs.sums
     first = None
     for _ in range(2):
         for b in (w0, best, sums):
@@ -320,10 +321,10 @@ def test_posed_keyed_stream_equals_the_eager_operator(dev):
             loop = ["ancsh_reproject_scene_build", "ancsh_render_depth_labels", "ancsh_refine_pass_sil"]
             assert names[-11:] == ["ancsh_silhouette_field"] + loop * 3 + ["ancsh_refine_rec"], names[-12:]
             assert names[-12] == "ancsh_reproject_compare_rec" and "ancsh_refine_pass" not in names
-            assert sl.refine_field.shape == (K, CAP_) and sl.refine_field.dtype == torch.int32 and sl.refine_bufs[2].shape == (1, B_, K, 2, 36)
-            assert all(s.refine_field.data_ptr() != sl.refine_field.data_ptr() for s in P.slots[1:])
+            assert sl.refine_bufs.field.shape == (K, CAP_) and sl.refine_bufs.field.dtype == torch.int32 and sl.refine_bufs.sums.shape == (1, B_, K, 2, 36)
+            assert all(s.refine_bufs.field.data_ptr() != sl.refine_bufs.field.data_ptr() for s in P.slots[1:])
         else:
-            assert sl.refine_field is None and sl.refine_bufs is None
+            assert sl.refine_bufs is None
         results.append(list(P.stream_posed_batches(feed, articulation=True, link_counts=True)))
         del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(mesh, rt, crops, dtype, dev)
@@ -346,7 +347,7 @@ def test_rendered_stream_with_a_sensor_equals_the_eager_operator(dev):
     for refine in (table, None):
         P = _pipe(K, dtype, render_mesh=mesh, sensor=sensor, **(dict(refine=refine) if refine is not None else {}))
         results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
-        assert (P.slots[0].refine_field is not None) == (refine is not None)
+        assert (getattr(P.slots[0].refine_bufs, "field", None) is not None) == (refine is not None)
         del P
     observed = lambda k, crops, rt, sc, seed: sensor_frames(render_depth_frames(mesh, rt, crops, dtype, dev), sc, sensor, dtype, seed=seed, device=dev)
     _check_against_eager(results[0], results[1], batches, mesh, dtype, K, dev, observed, table)
@@ -372,7 +373,7 @@ def test_library_stream_under_the_range_guard_equals_the_eager_operator(dev):
         P = _pipe(K, dtype, render_mesh=lib, arithmetic="f16x2", range_guard=True, **(dict(refine=refine) if on else {}))
         results.append(list(P.stream_render_batches(feed, articulation=True, link_counts=True)))
         sl = P.slots[0]
-        assert sl.graph32 is not None and ("record_refined" in sl.out32) == on and (sl.refine_field is not None) == on
+        assert sl.graph32 is not None and ("record_refined" in sl.out32) == on and (getattr(sl.refine_bufs, "field", None) is not None) == on
         del P
     observed = lambda k, crops, rt, sc, seed: render_depth_frames(lib, rt, crops, dtype, dev)
     _check_against_eager(results[0], results[1], batches, lib, dtype, K, dev, observed, table)

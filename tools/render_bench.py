@@ -186,8 +186,7 @@ def reprojection_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt,
             exact[f, j, :13] = exact[f, j, 13:26] = np.concatenate([pose[:3, :3].reshape(9), [1.0], pose[:3, 3]])
     carried = torch.from_numpy(exact).to(dev)
     d_rig, d_nf = torch.from_numpy(rbatches[-1][2]["rig"]).to(dev), torch.from_numpy(rbatches[-1][1]).to(dev)
-    tables = (torch.zeros((2 * B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * B, D.GEOM_WORDS), dtype=torch.int32, device=dev))
-    pred = R.predicted_buffers(cap, "uint16", dev)
+    tables, pred = R.predicted_frames(B, cap, "uint16", dev)
     wide = torch.empty((B, K, W + R.REPROJECTION_WIDTH), dtype=torch.float64, device=dev)
     calls = {"scene_build": lambda: R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables),
              "render_2B_frames": lambda: D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2]),
@@ -257,30 +256,28 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
     carried = torch.from_numpy(moved).to(dev)
     rigs, nf = rbatches[-1][2]["rig"], rbatches[-1][1]
     d_rig, d_nf, d_par = torch.from_numpy(rigs).to(dev), torch.from_numpy(nf).to(dev), torch.from_numpy(table).to(dev)
-    tables = (torch.zeros((2 * B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * B, D.GEOM_WORDS), dtype=torch.int32, device=dev))
-    pred = R.predicted_buffers(cap, "uint16", dev)
+    tables, pred = R.predicted_frames(B, cap, "uint16", dev)
     bufs = F.refine_buffers(B, K, dev)
     R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
     D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
     calls = {"refine_pass": lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, carried,
-                                                  bufs[0][0], bufs[1], bufs[2][0]),
-             "refine_rec": lambda: F.refine_rec(bufs[1], carried)}
+                                                  bufs.work[0], bufs.best, bufs.sums[0]),
+             "refine_rec": lambda: F.refine_rec(bufs.best, carried)}
     op_ms = {name: timed_calls(call, args.rounds, args.calls) for name, call in calls.items()}
-    used = bufs[2][0][..., 28].cpu().numpy()
+    used = bufs.sums[0][..., 28].cpu().numpy()
     loop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_par, args.refine, bufs)
     op_ms["whole_loop"] = timed_calls(loop, args.rounds, max(1, args.calls // 10))
     cols = F.named_columns(loop().cpu().numpy())
     sil = {}
     if args.silhouette:                                                   # the same batch and record with the term: the field, one pass, the loop
-        d_spar, sbufs, field = torch.from_numpy(sil_table).to(dev), F.refine_buffers(B, K, dev, silhouette=True), F.field_buffer(K, cap, dev)
+        d_spar, sbufs = torch.from_numpy(sil_table).to(dev), F.refine_buffers(B, K, dev, silhouette=True, pixel_capacity=cap)
         R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
         D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
-        op_ms["silhouette_field"] = timed_calls(lambda: F.silhouette_field(clean[0], clean[1], d_geom, d_sc, K, out=field), args.rounds, args.calls)
+        op_ms["silhouette_field"] = timed_calls(lambda: F.silhouette_field(clean[0], clean[1], d_geom, d_sc, K, out=sbufs.field), args.rounds, args.calls)
         op_ms["refine_pass_sil"] = timed_calls(lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_spar, 0, False,
-                                                                     carried, sbufs[0][0], sbufs[1], sbufs[2][0], field=field), args.rounds, args.calls)
-        s0 = sbufs[2][0].cpu().numpy()
-        sloop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_spar, args.refine, sbufs,
-                                       field=field)
+                                                                     carried, sbufs.work[0], sbufs.best, sbufs.sums[0], field=sbufs.field), args.rounds, args.calls)
+        s0 = sbufs.sums[0].cpu().numpy()
+        sloop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_spar, args.refine, sbufs)
         op_ms["whole_loop_sil"] = timed_calls(sloop, args.rounds, max(1, args.calls // 10))
         scols = F.named_columns(sloop().cpu().numpy())
         sil = {"silhouette": {"table": sil_table[8:11].tolist(), "launches_added": 5 * (args.refine + 1) + 2, "field_bytes_per_slot": 4 * K * cap,
@@ -376,16 +373,15 @@ def joints_bench(args, K, B, N, dev, mesh, d_mesh):
     carried = torch.from_numpy(moved).to(dev)
     d_rig, d_nf, d_kin = torch.from_numpy(rigs).to(dev), torch.from_numpy(nf).to(dev), torch.from_numpy(kin).to(dev)
     d_par = torch.from_numpy(tables_on).to(dev)
-    tables = (torch.zeros((2 * B, D.RENDER_WIDTH), dtype=torch.float64, device=dev), torch.zeros((2 * B, D.GEOM_WORDS), dtype=torch.int32, device=dev))
-    pred = R.predicted_buffers(cap, "uint16", dev)
+    tables, pred = R.predicted_frames(B, cap, "uint16", dev)
     bufs = F.refine_buffers(B, K, dev, passes=args.refine + 1, joints=True)
     loop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_par, args.refine, bufs, kin=d_kin)
     op_ms = {"whole_loop_joints": timed_calls(loop, args.rounds, max(1, args.calls // 10))}
-    obj = bufs[3][1].cpu().numpy()
+    obj = bufs.obj.cpu().numpy()
     R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
     D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
-    F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, carried, bufs[0][0], bufs[1], bufs[2][0])
-    step = lambda: F.refine_joint_step(d_kin, d_sc, tables[0], d_nf, d_par, 0, False, carried, bufs[2][0], bufs[0][0], bufs[1], bufs[3][0], bufs[3][1][0])
+    F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_par, 0, False, carried, bufs.work[0], bufs.best, bufs.sums[0])
+    step = lambda: F.refine_joint_step(d_kin, d_sc, tables[0], d_nf, d_par, 0, False, carried, bufs.sums[0], bufs.work[0], bufs.best, bufs.state, bufs.obj[0])
     op_ms["refine_joint_step"] = timed_calls(step, args.rounds, args.calls)
     fell = obj[-1, :, :, 7] < obj[0, :, :, 7]
     print(json.dumps({"metric": "the joint step of render-and-compare ICP: ms per batch of the posed stream with refine=pack_refine(iters=N) without (f) "
