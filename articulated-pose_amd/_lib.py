@@ -187,6 +187,11 @@ SIGNATURES = {
     "ancsh_silhouette_field": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
     "ancsh_refine_pass_sil": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 9 + [_c_int, _c_int, _vp, _c_int,
                               _vp, _vp, _vp, _vp],
+    # the coverage term (no ABI bump, detected by their symbols): nframes, K, depth_type, pred_depth, pred_labels, pixel_capacity, geom_out,
+    # scene, cover, stream;  ancsh_refine_pass_sil's arguments with cover behind field
+    "ancsh_coverage_field": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
+    "ancsh_refine_pass_cov": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 10 + [_c_int, _c_int, _vp, _c_int,
+                              _vp, _vp, _vp, _vp],
     # the joint step (no ABI bump, detected by its symbol): nframes, K, kin, ninst, scene, pred_render, norm_factor, params, pass, is_last,
     # pose_in, ld_in, sums, sums_ld, pose_out, best, state, obj, xi, stream
     "ancsh_refine_joint_step": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int] + [_vp] * 6,

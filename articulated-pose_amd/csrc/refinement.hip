@@ -14,6 +14,9 @@
 // The joint step, one more entry: ancsh_refine_joint_step (ONE launch behind each pass, one wave per (pose, frame): the parts' normal
 // equations from `sums` and the rows that keep each revolute and prismatic joint's two sides on one axis, solved together by Cholesky in
 // LDS; the poses and the best block the pass wrote are overwritten, the best-of is kept per object).  The pass kernel does not know of it.
+// The coverage term, two more entries: ancsh_coverage_field (ONE launch behind the renderer in every pass: the field kernel on the predicted
+// pair, per crop pixel and part the offset to the nearest pixel PREDICTED for the part) and ancsh_refine_pass_cov (the pass kernel's COV
+// instance: an observed pixel of the part that the prediction leaves bare adds one row that pulls the nearest predicted pixel over it).
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
 #include "compare_common.h"
 
@@ -23,6 +26,7 @@ constexpr int RF_LINKS = ANCSH_SCENE_MAX_LINKS, RF_THREADS = 256, RF_WAVES = RF_
 constexpr int RF_RENDER = ANCSH_RENDER_WIDTH, RF_BEST = ANCSH_REFINE_WIDTH / 2, RF_SUMS = ANCSH_REFINE_SUMS;
 constexpr int RF_ACC = 30;                                              // A (21) | b (6) | sum r^2 | n_used | n_obs: what the block adds up
 constexpr int RF_SIL_ACC = 33, RF_SIL_SUMS = ANCSH_REFINE_SIL_SUMS;     // ... | sum m^2 | n_sil | n_far: with the silhouette term
+constexpr int RF_COV_ACC = 36, RF_COV_SUMS = ANCSH_REFINE_COV_SUMS;     // ... | sum m_c^2 | n_cov | n_cfar: with the coverage term as well
 constexpr int SF_THREADS = 256, SF_BAND = 16, SF_CHUNK = 256, SF_SPLIT = 8, SF_STEP = 8, SF_ILP = 8, SF_NONE = 0x7fffffff, SF_SENTINEL = -32768;
 
 __device__ __forceinline__ double rf_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -116,9 +120,10 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
     return true;
 }
 
-// SIL: ancsh_refine_pass_sil -- the overhang pixels add their rows (field: ancsh_silhouette_field's words), params holds 16 values and a sums
-// row 36; without it the kernel is ancsh_refine_pass, instruction for instruction what it was before the term existed
-template <typename T, bool SIL>
+// TERMS 1: ancsh_refine_pass_sil -- the overhang pixels add their rows (field: ancsh_silhouette_field's words), params holds 16 values and a
+// sums row 36; TERMS 0: ancsh_refine_pass, instruction for instruction what it was before the term existed; TERMS 2: ancsh_refine_pass_cov --
+// the gap pixels add their rows as well (cover: ancsh_coverage_field's words), params holds 32 values and a sums row 40
+template <typename T, int TERMS>
 __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, int K, const float *__restrict__ verts, const int *__restrict__ tris,
                                                                  const int *__restrict__ tri_link, int V, int ntri,
                                                                  const T *__restrict__ obs_depth, const unsigned char *__restrict__ obs_labels,
@@ -127,9 +132,11 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                                                                  const int *__restrict__ geom, const double *__restrict__ scene,
                                                                  const double *__restrict__ pred_render, const float *__restrict__ norm_factor,
                                                                  const double *__restrict__ params, const int *__restrict__ field,
-                                                                 int pass, int is_last, const double *__restrict__ pose_in, int ld_in, double *__restrict__ pose_out,
+                                                                 const int *__restrict__ cover, int pass, int is_last,
+                                                                 const double *__restrict__ pose_in, int ld_in, double *__restrict__ pose_out,
                                                                  double *__restrict__ best, double *__restrict__ sums) {
-    constexpr int NACC = SIL ? RF_SIL_ACC : RF_ACC, NSUMS = SIL ? RF_SIL_SUMS : RF_SUMS;
+    constexpr bool SIL = TERMS >= 1, COV = TERMS == 2;
+    constexpr int NACC = COV ? RF_COV_ACC : SIL ? RF_SIL_ACC : RF_ACC, NSUMS = COV ? RF_COV_SUMS : SIL ? RF_SIL_SUMS : RF_SUMS;
     __shared__ int s_part[RF_LINKS];
     __shared__ double s_red[RF_WAVES][NACC], s_tot[NACC];
     const int j = blockIdx.x, v = blockIdx.y, f = blockIdx.z, tid = threadIdx.x;
@@ -141,7 +148,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     if (!pose_ok(pose) || !finite(nf) || nf == 0.0) {                   // uniform over the block: NaN in the best block, the pose as it came
         if (tid < 13) po[tid] = pose[tid];
         if (tid < RF_BEST) bb[tid] = qnan;
-        if (tid < NSUMS) ss[tid] = tid == RF_SUMS - 1 || tid == RF_SIL_SUMS - 1 ? 0.0 : qnan;
+        if (tid < NSUMS) ss[tid] = tid == RF_SUMS - 1 || tid == RF_SIL_SUMS - 1 || tid == RF_COV_SUMS - 1 ? 0.0 : qnan;
         return;
     }
     scene_part_table(sc, K, tid, s_part);
@@ -165,7 +172,8 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
         const T od = obs_depth[a], qd = pd[a];
         const unsigned long long key = pz[a];
         const int op = pixel_part(od, obs_labels[a], s_part);
-        const bool o = op == j, p = pixel_part(qd, pl[a], s_part) == j;
+        const int qp = pixel_part(qd, pl[a], s_part);
+        const bool o = op == j, p = qp == j;
         acc[29] += o ? 1.0 : 0.0;
         if constexpr (SIL) {
             if (p && !o) {                                              // an OVERHANG pixel, unless another part hides the prediction here
@@ -202,6 +210,46 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                 for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
                 acc[30] += m * m;
                 acc[31] += 1.0;
+                continue;
+            }
+        }
+        if constexpr (COV) {
+            if (o && !p) {                                              // a GAP pixel, unless the prediction puts another part in front of it
+                if (qp >= 0 && !((double)__uint_as_float((unsigned)(key >> 32)) > (double)od * scale)) continue;
+                const int cw = cover[((size_t)j * 2 + v) * pixel_capacity + a], di = (short)(cw & 0xffff), dj = (short)((unsigned)cw >> 16);
+                if (di == SF_SENTINEL) continue;
+                if ((double)(di * di + dj * dj) <= params[26] * params[26]) continue;
+                const long e = a - start;
+                const int li = (int)(e / w), lj = (int)(e % w);
+                if (li + di < 0 || (long)(li + di) * w >= n || lj + dj < 0 || lj + dj >= w) continue;      // never with the field's own words
+                const double z2 = (double)__uint_as_float((unsigned)(pz[start + (long)(li + di) * w + (lj + dj)] >> 32));
+                const int ri = row0 + li, ci = col0 + lj;
+                const double row = (double)ri, col = (double)ci, row2 = (double)(ri + di), col2 = (double)(ci + dj);
+                double su, sv, su2, sv2, pn[3], pt[3];
+                pixel_ray(sc, row, col, su, sv);
+                pixel_ray(sc, row2, col2, su2, sv2);
+                rf_cloud(z2 * su2, z2 * sv2, z2, nf, pn);
+                rf_cloud(z2 * su, z2 * sv, z2, nf, pt);
+                const double dv[3] = {pn[0] - pt[0], pn[1] - pt[1], pn[2] - pt[2]};
+                const double m = sqrt(rf_dot(dv, dv));
+                if (!(m > 0.0)) continue;
+                if (m > params[25]) {                                   // FAR: no row, charged dist_c^2
+                    acc[35] += 1.0;
+                    continue;
+                }
+                const double wt = params[24], g[3] = {dv[0] / m, dv[1] / m, dv[2] / m}, r = wt * m;
+                const double pc[3] = {pn[0] - c[0], pn[1] - c[1], pn[2] - c[2]};
+                const double J[6] = {wt * (pc[1] * g[2] - pc[2] * g[1]), wt * (pc[2] * g[0] - pc[0] * g[2]), wt * (pc[0] * g[1] - pc[1] * g[0]),
+                                     wt * g[0], wt * g[1], wt * g[2]};
+                int at = 0;
+#pragma unroll
+                for (int x = 0; x < 6; ++x)
+#pragma unroll
+                    for (int y = x; y < 6; ++y) acc[at++] += J[x] * J[y];
+#pragma unroll
+                for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+                acc[33] += m * m;
+                acc[34] += 1.0;
                 continue;
             }
         }
@@ -267,11 +315,17 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     __syncthreads();
     if (tid < NACC) s_tot[tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
     __syncthreads();
-    if (tid < NACC) ss[tid < RF_ACC ? tid : tid + 2] = s_tot[tid];     // sum m^2, n_sil, n_far lie behind C and solved
+    // sum m^2, n_sil, n_far lie behind C and solved, the coverage's three behind [35]
+    if (tid < NACC) ss[tid < RF_ACC ? tid : tid < RF_SIL_ACC ? tid + 2 : tid + 3] = s_tot[tid];
     if (tid != 0) return;
     const double n_used = s_tot[28], n_obs = s_tot[29];
     double C, n_rows = n_used;
-    if constexpr (SIL) {
+    if constexpr (COV) {
+        C = (((s_tot[27] + (max_dist * max_dist) * (n_obs - n_used)) + (params[8] * params[8]) * (s_tot[30] + (params[9] * params[9]) * s_tot[32])) +
+             (params[24] * params[24]) * (s_tot[33] + (params[25] * params[25]) * s_tot[35])) / n_obs;
+        n_rows = (n_used + s_tot[31]) + s_tot[34];
+        ss[RF_SIL_SUMS - 1] = ss[RF_COV_SUMS - 1] = 0.0;
+    } else if constexpr (SIL) {
         C = ((s_tot[27] + (max_dist * max_dist) * (n_obs - n_used)) + (params[8] * params[8]) * (s_tot[30] + (params[9] * params[9]) * s_tot[32])) / n_obs;
         n_rows = n_used + s_tot[31];
         ss[RF_SIL_SUMS - 1] = 0.0;
@@ -312,15 +366,16 @@ __global__ __launch_bounds__(RF_THREADS) void refine_rec_kernel(long rows, const
 // first observed row above, through the band, down to the first below) and leaves g in LDS; then a thread takes SF_ILP pixels of one row
 // at a time and scans the chunk's columns in ascending order, one LDS read of g for all of them, an empty column skipped.  A pixel's
 // running best of a further chunk is read back from its own output word (the same thread wrote it).  No atomics; every word of a crop is
-// written exactly once per chunk by one thread, nothing outside the crops is touched.
+// written exactly once per chunk by one thread, nothing outside the crops is touched.  Frame row f reads scene row f % scene_rows:
+// ancsh_coverage_field runs it over the 2 * nframes predicted frames, whose row v * nframes + f is frame f's scene.
 template <typename T>
 __global__ __launch_bounds__(SF_THREADS) void silhouette_field_kernel(int K, const T *__restrict__ obs_depth, const unsigned char *__restrict__ obs_labels,
                                                                       long pixel_capacity, const int *__restrict__ geom,
-                                                                      const double *__restrict__ scene, int *__restrict__ field) {
+                                                                      const double *__restrict__ scene, int scene_rows, int *__restrict__ field) {
     __shared__ int s_part[RF_LINKS];
     __shared__ int s_g[SF_BAND][SF_CHUNK];
     const int j = blockIdx.x, f = blockIdx.z, tid = threadIdx.x;
-    const double *sc = scene + (size_t)f * AN_SCENE;
+    const double *sc = scene + (size_t)(f % scene_rows) * AN_SCENE;
     scene_part_table(sc, K, tid, s_part);
     __syncthreads();
     long start;
@@ -497,7 +552,8 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
             if (live) {
                 pose_centre(pose, s_c[tid]);
                 nj = S[28];
-                if (sums_ld == RF_SIL_SUMS) nj = nj + S[33];
+                if (sums_ld == RF_SIL_SUMS || sums_ld == RF_COV_SUMS) nj = nj + S[33];
+                if (sums_ld == RF_COV_SUMS) nj = nj + S[37];
             }
         }
         s_live[tid] = live ? 1 : 0;
@@ -728,13 +784,15 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
 
 using namespace ancsh;
 
-// both passes' checks and launch: who = the entry's name in its messages; SIL = with the field, the 16-value table and the 36-value sums
-template <bool SIL>
+// the three passes' checks and launch: who = the entry's name in its messages; TERMS = 1: with the field, the 16-value table and the 36-value
+// sums; 2: with cover, the 32-value table and the 40-value sums as well
+template <int TERMS>
 static int refine_pass_call(const char *who, int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V,
                             int T, const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
                             const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                             const double *scene, const double *pred_render, const float *norm_factor, const double *params, const int *field,
-                            int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
+                            const int *cover, int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums,
+                            void *stream) {
     ANCSH_CHECK(batch_ok(who, nframes, K, "exceed the 32767-frame range of ancsh_reproject_scene_build"));
     size_t item;
     ANCSH_CHECK(depth_item(who, depth_type, item));
@@ -744,22 +802,22 @@ static int refine_pass_call(const char *who, int nframes, int K, int depth_type,
     ANCSH_CHECK(pass_ok(who, pass, is_last));
     ANCSH_CHECK(record_ld_ok(who, "ld_in", ld_in));
     ANCSH_REQUIRE(verts && tris && tri_link && obs_depth && obs_labels && pred_zbuf && pred_depth && pred_labels && geom && scene &&
-                      pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || !SIL),
+                      pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || TERMS < 1) && (cover || TERMS < 2),
                   "%s: null pointer", who);
-    ANCSH_REQUIRE(depth_aligned(item, obs_depth, pred_depth) && all_aligned<4>(verts, tris, tri_link, geom, norm_factor, field) &&
+    ANCSH_REQUIRE(depth_aligned(item, obs_depth, pred_depth) && all_aligned<4>(verts, tris, tri_link, geom, norm_factor, field, cover) &&
                       all_aligned<8>(pred_zbuf, scene, pred_render, params, pose_in, pose_out, best, sums), ANCSH_ALIGNED, who);
     ANCSH_REQUIRE(pose_in != pose_out, "%s: pose_in and pose_out overlap (a workgroup reads its pose while another writes: two buffers)", who);
     if (nframes == 0) return ANCSH_OK;
     const dim3 grid(K, 2, nframes);
     if (depth_type == ANCSH_DEPTH_U16)
-        hipLaunchKernelGGL((refine_pass_kernel<unsigned short, SIL>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris,
+        hipLaunchKernelGGL((refine_pass_kernel<unsigned short, TERMS>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris,
                            tri_link, V, T, (const unsigned short *)obs_depth, obs_labels, pixel_capacity, pred_zbuf,
-                           (const unsigned short *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, pass, is_last,
-                           pose_in, ld_in, pose_out, best, sums);
+                           (const unsigned short *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass,
+                           is_last, pose_in, ld_in, pose_out, best, sums);
     else
-        hipLaunchKernelGGL((refine_pass_kernel<float, SIL>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris, tri_link, V,
+        hipLaunchKernelGGL((refine_pass_kernel<float, TERMS>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris, tri_link, V,
                            T, (const float *)obs_depth, obs_labels, pixel_capacity, pred_zbuf, (const float *)pred_depth, pred_labels, geom,
-                           scene, pred_render, norm_factor, params, field, pass, is_last, pose_in, ld_in, pose_out, best, sums);
+                           scene, pred_render, norm_factor, params, field, cover, pass, is_last, pose_in, ld_in, pose_out, best, sums);
     return check_launch(who);
 }
 
@@ -768,9 +826,9 @@ extern "C" int ancsh_refine_pass(int nframes, int K, int depth_type, const float
                                  const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                                  const double *scene, const double *pred_render, const float *norm_factor, const double *params, int pass,
                                  int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
-    return refine_pass_call<false>("refine_pass", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
-                                   pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, nullptr, pass, is_last,
-                                   pose_in, ld_in, pose_out, best, sums, stream);
+    return refine_pass_call<0>("refine_pass", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, nullptr, nullptr, pass, is_last,
+                               pose_in, ld_in, pose_out, best, sums, stream);
 }
 
 extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
@@ -779,9 +837,20 @@ extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const f
                                      const int *geom, const double *scene, const double *pred_render, const float *norm_factor,
                                      const double *params, const int *field, int pass, int is_last, const double *pose_in, int ld_in,
                                      double *pose_out, double *best, double *sums, void *stream) {
-    return refine_pass_call<true>("refine_pass_sil", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
-                                  pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, pass, is_last,
-                                  pose_in, ld_in, pose_out, best, sums, stream);
+    return refine_pass_call<1>("refine_pass_sil", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, nullptr, pass, is_last,
+                               pose_in, ld_in, pose_out, best, sums, stream);
+}
+
+extern "C" int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                     const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
+                                     const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels,
+                                     const int *geom, const double *scene, const double *pred_render, const float *norm_factor,
+                                     const double *params, const int *field, const int *cover, int pass, int is_last, const double *pose_in,
+                                     int ld_in, double *pose_out, double *best, double *sums, void *stream) {
+    return refine_pass_call<2>("refine_pass_cov", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass, is_last,
+                               pose_in, ld_in, pose_out, best, sums, stream);
 }
 
 extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, int ninst, const double *scene, const double *pred_render,
@@ -792,8 +861,9 @@ extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, in
     ANCSH_REQUIRE(ninst >= 1 && ninst <= 65535, "refine_joint_step: ninst=%d kinematic tables must be in [1, 65535]", ninst);
     ANCSH_CHECK(pass_ok("refine_joint_step", pass, is_last));
     ANCSH_CHECK(record_ld_ok("refine_joint_step", "ld_in", ld_in));
-    ANCSH_REQUIRE(sums_ld == ANCSH_REFINE_SUMS || sums_ld == ANCSH_REFINE_SIL_SUMS, "refine_joint_step: sums_ld=%d must be %d (ancsh_refine_pass) or %d "
-                  "(ancsh_refine_pass_sil)", sums_ld, ANCSH_REFINE_SUMS, ANCSH_REFINE_SIL_SUMS);
+    ANCSH_REQUIRE(sums_ld == ANCSH_REFINE_SUMS || sums_ld == ANCSH_REFINE_SIL_SUMS || sums_ld == ANCSH_REFINE_COV_SUMS,
+                  "refine_joint_step: sums_ld=%d must be %d (ancsh_refine_pass), %d (ancsh_refine_pass_sil) or %d (ancsh_refine_pass_cov)", sums_ld,
+                  ANCSH_REFINE_SUMS, ANCSH_REFINE_SIL_SUMS, ANCSH_REFINE_COV_SUMS);
     ANCSH_REQUIRE(kin && scene && pred_render && norm_factor && params && pose_in && sums && pose_out && best && state && obj,
                   "refine_joint_step: null pointer");
     ANCSH_REQUIRE(all_aligned<4>(norm_factor) && all_aligned<8>(kin, scene, pred_render, params, pose_in, sums, pose_out, best, state, obj, xi),
@@ -807,23 +877,37 @@ extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, in
     return check_launch("refine_joint_step");
 }
 
-extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
-                                      long pixel_capacity, const int *geom, const double *scene, int *field, void *stream) {
-    ANCSH_CHECK(batch_ok("silhouette_field", nframes, K, "exceed the 32767-frame range of ancsh_refine_pass_sil"));
+// both fields' checks and launch: the kernel over `halves` * nframes frames of buffers of `halves` * pixel_capacity pixels, frame row v * nframes
+// + f reading scene row f
+static int field_call(const char *who, const char *why, int halves, int nframes, int K, int depth_type, const void *depth,
+                      const unsigned char *labels, long pixel_capacity, const int *geom, const double *scene, int *field, void *stream) {
+    ANCSH_CHECK(batch_ok(who, nframes, K, why));
     size_t item;
-    ANCSH_CHECK(depth_item("silhouette_field", depth_type, item));
-    ANCSH_CHECK(capacity_ok("silhouette_field", pixel_capacity));
-    ANCSH_REQUIRE(obs_depth && obs_labels && geom && scene && field, "silhouette_field: null pointer");
-    ANCSH_REQUIRE(depth_aligned(item, obs_depth) && all_aligned<4>(geom, field) && all_aligned<8>(scene), ANCSH_ALIGNED, "silhouette_field");
+    ANCSH_CHECK(depth_item(who, depth_type, item));
+    ANCSH_CHECK(capacity_ok(who, pixel_capacity));
+    ANCSH_REQUIRE(depth && labels && geom && scene && field, "%s: null pointer", who);
+    ANCSH_REQUIRE(depth_aligned(item, depth) && all_aligned<4>(geom, field) && all_aligned<8>(scene), ANCSH_ALIGNED, who);
     if (nframes == 0) return ANCSH_OK;
-    const dim3 grid(K, SF_SPLIT, nframes);
+    const dim3 grid(K, SF_SPLIT, halves * nframes);                     // <= 2 * 32767 frames: within the grid's 65535
     if (depth_type == ANCSH_DEPTH_U16)
         hipLaunchKernelGGL(silhouette_field_kernel<unsigned short>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, K,
-                           (const unsigned short *)obs_depth, obs_labels, pixel_capacity, geom, scene, field);
+                           (const unsigned short *)depth, labels, halves * pixel_capacity, geom, scene, nframes, field);
     else
-        hipLaunchKernelGGL(silhouette_field_kernel<float>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, K, (const float *)obs_depth, obs_labels,
-                           pixel_capacity, geom, scene, field);
-    return check_launch("silhouette_field");
+        hipLaunchKernelGGL(silhouette_field_kernel<float>, grid, dim3(SF_THREADS), 0, (hipStream_t)stream, K, (const float *)depth, labels,
+                           halves * pixel_capacity, geom, scene, nframes, field);
+    return check_launch(who);
+}
+
+extern "C" int ancsh_silhouette_field(int nframes, int K, int depth_type, const void *obs_depth, const unsigned char *obs_labels,
+                                      long pixel_capacity, const int *geom, const double *scene, int *field, void *stream) {
+    return field_call("silhouette_field", "exceed the 32767-frame range of ancsh_refine_pass_sil", 1, nframes, K, depth_type, obs_depth, obs_labels,
+                      pixel_capacity, geom, scene, field, stream);
+}
+
+extern "C" int ancsh_coverage_field(int nframes, int K, int depth_type, const void *pred_depth, const unsigned char *pred_labels,
+                                    long pixel_capacity, const int *geom_out, const double *scene, int *cover, void *stream) {
+    return field_call("coverage_field", "exceed the 32767-frame range of ancsh_refine_pass_cov", 2, nframes, K, depth_type, pred_depth, pred_labels,
+                      pixel_capacity, geom_out, scene, cover, stream);
 }
 
 extern "C" int ancsh_refine_rec(int nframes, int K, const double *best, const double *carried, int ld, double *wide, void *stream) {

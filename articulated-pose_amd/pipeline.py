@@ -165,13 +165,15 @@ class _Slot(object):
             self.gt_built = torch.zeros((B, K, SIDE["gt"].shape(K)[1]), dtype=torch.float64, device=device)      # never an H2D target
             self.frame_built = torch.zeros((B,) + SIDE["frame"].shape(K), dtype=torch.float64, device=device)
         # the predicted frames' tables and the pixel triple the renderer draws them into, two crops per frame; with refine= the loop's buffers
-        # (the silhouette term's field: 4 bytes per pixel and part).  Slot-owned, shared with the range guard's f32 graph.
+        # (the silhouette term's field: 4 bytes per pixel and part; the coverage term's cover: 8).  Slot-owned, shared with the range guard's
+        # f32 graph.
         if opts.reprojection or opts.refine:
             from .pose.reprojection import predicted_frames
             self.reproj_tables, self.reproj_pix = predicted_frames(B, cap, depth, device)
         if opts.refine:
             from .pose.refinement import refine_buffers
-            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints, pixel_capacity=cap)
+            self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints, pixel_capacity=cap,
+                                              coverage=opts.refine_coverage)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -375,6 +377,9 @@ class AncshPipeline(object):
         slot holds a second (B, K, 2, 18) block and a (B, 2, 8) row per object besides, out["refine_object"] (pose.refinement.OBJ_COLUMNS; not
         streamed).  The best-of is then kept per OBJECT: cost_best <= cost_start holds for out["refine_object"], not for each part's columns,
         whose best_pass and passes_solved are the object's.
+        A table of pack_refine(silhouette=..., coverage=...) adds the coverage term: ancsh_coverage_field behind the renderer in every pass
+        and ancsh_refine_pass_cov, 6 (iters + 1) + 2 launches (7 (iters + 1) + 2 with the joint step) and 8 bytes more per pixel of
+        depth_capacity, part and slot; a part is pulled over observed pixels it leaves bare.  The record's columns are unchanged.
         out["record_refined"]: the refinement block (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best,
         n_used, best_pass, passes_solved) behind the record so far; pose.refinement.refined_record(record, layout=pipe.record_layout) gives the
         (.., 26) record of the refined poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the

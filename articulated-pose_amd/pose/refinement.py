@@ -8,7 +8,10 @@ pack_refine(silhouette=...): then ancsh_silhouette_field finds, once per step, e
 ancsh_refine_pass_sil adds one row per predicted pixel that hangs over the observed part's edge, pulling it back across the ray, and charges
 such pixels in the cost.  Each part is refined on its own -- unless the table is one of pack_refine(joints=...) and the object's kinematic
 table is at hand: then ancsh_refine_joint_step runs behind every pass, solves the object's parts together through rows that keep each
-revolute and prismatic joint's two sides on one axis, and keeps the best-of per object."""
+revolute and prismatic joint's two sides on one axis, and keeps the best-of per object.  The silhouette term is one-sided: an observed pixel
+of the part that the prediction leaves bare is only charged.  A table of pack_refine(silhouette=..., coverage=...) adds the other side:
+ancsh_coverage_field finds, behind the renderer in every pass, every crop pixel's nearest PREDICTED pixel of each part, and
+ancsh_refine_pass_cov adds one row per bare observed pixel that pulls that predicted pixel over it."""
 from collections import namedtuple
 
 import numpy as np
@@ -21,6 +24,7 @@ REFINE_WIDTH = 36               # include/ancsh_hip.h, ANCSH_REFINE_WIDTH: the c
 REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH_REFINE_PARAMS, ANCSH_REFINE_MAX_ITERS
 REFINE_SIL_SUMS, REFINE_SIL_PARAMS = 36, 16               # ANCSH_REFINE_SIL_SUMS, ANCSH_REFINE_SIL_PARAMS: with the silhouette term
 REFINE_JOINT_PARAMS, REFINE_OBJ, JOINT_XI = 24, 8, 48       # ANCSH_REFINE_JOINT_PARAMS, ANCSH_REFINE_OBJ; the debug step's 6 * 8 values: the joint step
+REFINE_COV_SUMS, REFINE_COV_PARAMS = 40, 32               # ANCSH_REFINE_COV_SUMS, ANCSH_REFINE_COV_PARAMS: with the coverage term as well
 OBJ_COLUMNS = ("cost_start", "cost_best", "best_pass", "passes_solved", "cost", "joints", "solved", "gap_rms")      # an obj row, per (frame, pose)
 FIELD_SENTINEL = -32768                                   # both halves of a field word: the part has no observed pixel in the frame
 BEST_WIDTH = REFINE_WIDTH // 2
@@ -30,20 +34,23 @@ POSE_COLUMNS = tuple("R%d%d" % (a, k) for a in range(3) for k in range(3)) + ("s
 COLUMN_NAMES = tuple("baseline_" + c for c in POSE_COLUMNS) + tuple("nonlinear_" + c for c in POSE_COLUMNS)
 SUMS_COLUMNS = dict(A=slice(0, 21), b=slice(21, 27), rr=27, n_used=28, n_obs=29, cost=30, solved=31)
 SIL_SUMS_COLUMNS = dict(SUMS_COLUMNS, mm=32, n_sil=33, n_far=34)
+COV_SUMS_COLUMNS = dict(SIL_SUMS_COLUMNS, mm_c=36, n_cov=37, n_cfar=38)
 PARAMS_LENGTHS = {"ancsh_refine_pass": (REFINE_PARAMS, REFINE_JOINT_PARAMS), "ancsh_refine_pass_sil": (REFINE_SIL_PARAMS, REFINE_JOINT_PARAMS),
-                  "ancsh_refine_joint_step": (REFINE_JOINT_PARAMS,)}      # the params table per entry: the joint step's holds both shorter ones in front
-RefineBuffers = namedtuple("RefineBuffers", "work best sums field state obj xi")      # refine_buffers' record; None = a term that is off
+                  "ancsh_refine_pass_cov": (REFINE_COV_PARAMS,),
+                  "ancsh_refine_joint_step": (REFINE_JOINT_PARAMS, REFINE_COV_PARAMS)}      # the params table per entry: a longer one holds the shorter ones in front
+RefineBuffers = namedtuple("RefineBuffers", "work best sums field state obj xi cover")      # refine_buffers' record; None = a term that is off
 BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, render_mesh=<depth.pack_mesh(...)>"
 
 
 def check_refine_table(table):
     """-> table as a fresh (REFINE_PARAMS,) float64 array, (REFINE_SIL_PARAMS,) with the silhouette term or (REFINE_JOINT_PARAMS,) with the
-    joint step (has_silhouette, has_joints); ValueError unless it is one pack_refine makes."""
+    joint step or (REFINE_COV_PARAMS,) with the coverage term (has_silhouette, has_joints, has_coverage); ValueError unless it is one
+    pack_refine makes."""
     try:
         t = np.array(table, np.float64)
     except (TypeError, ValueError):
         t = np.zeros(0)
-    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,), (REFINE_JOINT_PARAMS,)):
+    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,), (REFINE_JOINT_PARAMS,), (REFINE_COV_PARAMS,)):
         raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), or (%d,) with silhouette=, got shape %s"
                          % (REFINE_PARAMS, REFINE_SIL_PARAMS, t.shape))
     iters, max_dist, min_cos, damping, max_angle, min_pixels = t[:6].tolist()
@@ -61,7 +68,9 @@ def check_refine_table(table):
         raise ValueError("refine: min_pixels must be an integer >= 1, got %r" % min_pixels)
     if (t[6:REFINE_PARAMS] != 0).any():
         raise ValueError("refine: the reserved values 6..7 must be 0")
-    if t.shape[0] == REFINE_SIL_PARAMS or (t.shape[0] == REFINE_JOINT_PARAMS and (t[8:REFINE_SIL_PARAMS] != 0).any()):
+    if t.shape[0] == REFINE_COV_PARAMS and not (t[8:REFINE_SIL_PARAMS] != 0).any():
+        raise ValueError("refine: coverage needs the silhouette term (its rows are the other side of the overhang rows): pass silhouette= as well")
+    if t.shape[0] == REFINE_SIL_PARAMS or (t.shape[0] > REFINE_SIL_PARAMS and (t[8:REFINE_SIL_PARAMS] != 0).any()):
         weight, dist, slack = t[8:11].tolist()
         if not (np.isfinite(weight) and weight > 0):
             raise ValueError("refine: silhouette weight must be finite and > 0, got %r" % weight)
@@ -71,14 +80,24 @@ def check_refine_table(table):
             raise ValueError("refine: silhouette slack must be finite and >= 0 pixels, got %r" % slack)
         if (t[11:REFINE_SIL_PARAMS] != 0).any():
             raise ValueError("refine: the reserved values 11..15 must be 0")
-    if t.shape[0] == REFINE_JOINT_PARAMS:
+    if t.shape[0] == REFINE_JOINT_PARAMS or (t.shape[0] == REFINE_COV_PARAMS and (t[REFINE_SIL_PARAMS:REFINE_JOINT_PARAMS] != 0).any()):
         weight, axis_length = t[16:18].tolist()
         if not (np.isfinite(weight) and weight > 0):
             raise ValueError("refine: joints weight must be finite and > 0, got %r" % weight)
         if not (np.isfinite(axis_length) and axis_length >= 0):
             raise ValueError("refine: joints axis_length must be finite and >= 0, got %r" % axis_length)
-        if (t[18:] != 0).any():
+        if (t[18:REFINE_JOINT_PARAMS] != 0).any():
             raise ValueError("refine: the reserved values 18..23 must be 0")
+    if t.shape[0] == REFINE_COV_PARAMS:
+        weight, dist, slack = t[24:27].tolist()
+        if not (np.isfinite(weight) and weight > 0):
+            raise ValueError("refine: coverage weight must be finite and > 0, got %r" % weight)
+        if not (np.isfinite(dist) and dist > 0):
+            raise ValueError("refine: coverage dist must be finite and > 0, got %r" % dist)
+        if not (np.isfinite(slack) and slack >= 0):
+            raise ValueError("refine: coverage slack must be finite and >= 0 pixels, got %r" % slack)
+        if (t[27:] != 0).any():
+            raise ValueError("refine: the reserved values 27..31 must be 0")
     return t
 
 
@@ -88,11 +107,18 @@ def has_silhouette(table):
 
 
 def has_joints(table):
-    """A checked table: the joint step is on iff it is the (REFINE_JOINT_PARAMS,) one."""
-    return table is not None and table.shape[0] == REFINE_JOINT_PARAMS
+    """A checked table: the joint step is on iff it is the (REFINE_JOINT_PARAMS,) one, or the (REFINE_COV_PARAMS,) one with value 16 (the
+    joints' weight) > 0."""
+    return table is not None and (table.shape[0] == REFINE_JOINT_PARAMS or (table.shape[0] == REFINE_COV_PARAMS and bool(table[16] > 0)))
 
 
-def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None, joints=None):
+def has_coverage(table):
+    """A checked table: the coverage term is on iff it is the (REFINE_COV_PARAMS,) one."""
+    return table is not None and table.shape[0] == REFINE_COV_PARAMS
+
+
+def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None, joints=None,
+                coverage=None):
     """The parameter table ancsh_refine_pass reads, (REFINE_PARAMS,) float64: iters Gauss-Newton passes (1..8; one more pass evaluates the
     last pose); max_dist: a pixel pair further apart than this counts as missed, and a step's translation is clamped to it; min_cos: pixels
     seen at a flatter angle are left out; damping: relative Levenberg damping of the diagonal; max_angle_deg: the clamp of a step's
@@ -108,7 +134,27 @@ def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=
     parts' own normal equations.  weight scales a joint row against a mean part's pixel rows (a residual in cloud units counts weight^2 *
     the parts' mean row count times); axis_length (cloud units) turns the angle between the two sides' axis directions into a length.  It
     needs the object's kinematic table (kinematics=).  These defaults, too, are starting values nobody has tuned.
+    coverage = dict(weight=1.0, dist=<cloud units>, slack=1.0), or (weight, dist), with silhouette=: the coverage term, a (REFINE_COV_PARAMS,)
+    table: values 0..15 as above, 16..23 the joint step's (all 0 without joints=), 24 weight, 25 dist, 26 slack, 27..31 reserved.  An observed
+    pixel of the part that the prediction leaves bare pulls the nearest predicted pixel of the part over it -- the silhouette term's other
+    side, with the same three values' meaning; min_pixels counts these rows too.  Nobody has tuned these defaults either.
     ValueError: check_refine_table's."""
+    if coverage is not None:
+        if silhouette is None:
+            raise ValueError("refine: coverage needs the silhouette term (its rows are the other side of the overhang rows): pass silhouette= as well")
+        if isinstance(coverage, dict) and (set(coverage) - {"weight", "dist", "slack"} or "dist" not in coverage):
+            raise ValueError("refine: coverage takes weight, dist (required) and slack, got %s" % sorted(coverage))
+        try:
+            if isinstance(coverage, dict):
+                cov = [float(coverage.get("weight", 1.0)), float(coverage["dist"]), float(coverage.get("slack", 1.0))]
+            else:
+                weight, dist = coverage
+                cov = [float(weight), float(dist), 1.0]
+        except (TypeError, ValueError):
+            raise ValueError("refine: coverage is dict(weight=, dist=, slack=) or (weight, dist), of numbers")
+        front = pack_refine(iters, max_dist, min_cos, damping, max_angle_deg, min_pixels, silhouette=silhouette, joints=joints).tolist()
+        front = front + [0.0] * (REFINE_JOINT_PARAMS - len(front))
+        return check_refine_table(front + cov + [0.0] * (REFINE_COV_PARAMS - REFINE_JOINT_PARAMS - len(cov)))
     try:
         head = [float(iters), float(max_dist), float(min_cos), float(damping), float(np.radians(float(max_angle_deg))), float(min_pixels)]
     except (TypeError, ValueError):
@@ -187,17 +233,21 @@ def _params(entry, params):
                          % (" or ".join(str(n) for n in PARAMS_LENGTHS[entry]), entry))
 
 
-def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False, pixel_capacity=None):
+def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False, pixel_capacity=None, coverage=False):
     """What a slot owns for the loop, a RefineBuffers record: work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2,
-    32 -- 36 with the silhouette term), float64; silhouette=True: field = field_buffer's planes of pixel_capacity pixels; joints=True: state
-    (B, K, 2, 18), obj (passes, B, 2, 8) and the debug output xi (passes, B, 2, 48) -- None with one pass."""
+    32 -- 36 with the silhouette term, 40 with the coverage term), float64; silhouette=True: field = field_buffer's planes of pixel_capacity
+    pixels; joints=True: state (B, K, 2, 18), obj (passes, B, 2, 8) and the debug output xi (passes, B, 2, 48) -- None with one pass;
+    coverage=True (with silhouette=True): cover = field_buffer's planes of 2 * pixel_capacity pixels."""
     if silhouette and pixel_capacity is None:
         raise ValueError("refine_buffers(silhouette=True) allocates the field with the rest: it needs pixel_capacity")
+    if coverage and not silhouette:
+        raise ValueError("refine_buffers(coverage=True) needs silhouette=True: the coverage term runs with the silhouette term")
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
     return RefineBuffers(work=(z(B, K, 26), z(B, K, 26)), best=z(B, K, 2, BEST_WIDTH),
-                         sums=z(passes, B, K, 2, REFINE_SIL_SUMS if silhouette else REFINE_SUMS),
+                         sums=z(passes, B, K, 2, REFINE_COV_SUMS if coverage else REFINE_SIL_SUMS if silhouette else REFINE_SUMS),
                          field=field_buffer(K, pixel_capacity, device) if silhouette else None, state=z(B, K, 2, BEST_WIDTH) if joints else None,
-                         obj=z(passes, B, 2, REFINE_OBJ) if joints else None, xi=z(passes, B, 2, JOINT_XI) if joints and passes > 1 else None)
+                         obj=z(passes, B, 2, REFINE_OBJ) if joints else None, xi=z(passes, B, 2, JOINT_XI) if joints and passes > 1 else None,
+                         cover=field_buffer(K, 2 * int(pixel_capacity), device) if coverage else None)
 
 
 def field_buffer(K, pixel_capacity, device):
@@ -226,12 +276,40 @@ def silhouette_field(obs_depth, obs_labels, geom, scene, K, out=None):
     return out
 
 
+def coverage_field(pred, geom_out, scene, K, out=None):
+    """ancsh_coverage_field on device tensors (no host sync): pred = pose.reprojection.predicted_buffers' triple as the renderer left it (2 *
+    pixel_capacity pixels), geom_out (2B, 5) int32 = ancsh_reproject_scene_build's description of the predicted frames, scene (B, 240) ->
+    cover (K, 2 * pixel_capacity) int32: silhouette_field's words for the pixels PREDICTED for each part, pose v's half behind v *
+    pixel_capacity.  Words outside the crops are left as they are."""
+    from ..depth import _byte_plane, _depth_plane
+    _lib.require_device(pred[0])
+    kind, cap2 = _depth_plane(pred[0])
+    _byte_plane("labels", pred[1], cap2)
+    if not 1 <= int(K) <= 8:
+        raise ValueError("K=%d must be in [1, 8]" % K)
+    if cap2 % 2:
+        raise ValueError("the predicted pair holds two halves: an even number of pixels, got %d" % cap2)
+    B = _tables(None, scene, None, None, None, None, int(K), B=int(scene.shape[0]) if scene.dim() == 2 else 0)
+    if geom_out.dtype != torch.int32 or tuple(geom_out.shape) != (2 * B, 5) or not geom_out.is_contiguous():
+        raise ValueError("geom_out must be a contiguous (%d, 5) int32 tensor" % (2 * B))
+    if out is None:
+        out = field_buffer(K, cap2, pred[0].device)
+    if out.dtype != torch.int32 or tuple(out.shape) != (int(K), cap2) or not out.is_contiguous():
+        raise ValueError("cover must be a contiguous (%d, %d) int32 tensor" % (K, cap2))
+    _lib.require_cuda(pred[1], geom_out, scene, out)
+    _lib.call("ancsh_coverage_field", B, int(K), kind, _lib.ptr(pred[0]), _lib.ptr(pred[1]), cap2 // 2, _lib.ptr(geom_out), _lib.ptr(scene),
+              _lib.ptr(out))
+    return out
+
+
 def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, pose_out,
-                best, sums, field=None):
+                best, sums, field=None, cover=None):
     """ancsh_refine_pass on device tensors (no host sync, no allocation): mesh = depth.mesh_to_device's; the observed pair (pixel_capacity,);
     pred = pose.reprojection.predicted_buffers' triple as the renderer left it for pred_render (2B, 208), the tables of pose_in (B, K, >= 26);
     params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out.
-    field = silhouette_field's (K, pixel_capacity) planes: ancsh_refine_pass_sil, with a (16,) table and sums (B, K, 2, 36)."""
+    field = silhouette_field's (K, pixel_capacity) planes: ancsh_refine_pass_sil, with a (16,) table and sums (B, K, 2, 36).
+    cover = coverage_field's (K, 2 * pixel_capacity) planes of this pass's prediction, with field: ancsh_refine_pass_cov, with a (32,) table
+    and sums (B, K, 2, 40)."""
     from ..depth import RENDER_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
     _lib.require_device(pose_in)
     verts, tris, tri_link, V, T = _check_device_mesh(mesh)[:5]
@@ -243,19 +321,26 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     B = _tables(None, scene, None, norm_factor, pose_in, geom, K, name="pose_in")
     ld = int(pose_in.shape[2])
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
-    sil = field is not None
-    _params("ancsh_refine_pass_sil" if sil else "ancsh_refine_pass", params)
+    sil, cov = field is not None, cover is not None
+    if cov and not sil:
+        raise ValueError("cover goes with field: the coverage term runs with the silhouette term")
+    _params("ancsh_refine_pass_cov" if cov else "ancsh_refine_pass_sil" if sil else "ancsh_refine_pass", params)
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
-    _f64("sums", sums, (B, K, 2, REFINE_SIL_SUMS if sil else REFINE_SUMS))
+    _f64("sums", sums, (B, K, 2, REFINE_COV_SUMS if cov else REFINE_SIL_SUMS if sil else REFINE_SUMS))
     if sil and (field.dtype != torch.int32 or tuple(field.shape) != (K, cap) or not field.is_contiguous()):
         raise ValueError("field must be a contiguous (%d, %d) int32 tensor" % (K, cap))
-    _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums, field)
+    if cov and (cover.dtype != torch.int32 or tuple(cover.shape) != (K, 2 * cap) or not cover.is_contiguous()):
+        raise ValueError("cover must be a contiguous (%d, %d) int32 tensor" % (K, 2 * cap))
+    _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums, field,
+                      cover)
     head = (B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap,
             _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
             _lib.ptr(params))
     tail = (int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld, _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(sums))
-    if sil:
+    if cov:
+        _lib.call("ancsh_refine_pass_cov", *head, _lib.ptr(field), _lib.ptr(cover), *tail)
+    elif sil:
         _lib.call("ancsh_refine_pass_sil", *head, _lib.ptr(field), *tail)
     else:
         _lib.call("ancsh_refine_pass", *head, *tail)
@@ -265,7 +350,7 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
 def refine_joint_step(kin, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, sums, pose_out, best, state, obj, xi=None):
     """ancsh_refine_joint_step on device tensors (no host sync, no allocation), directly behind refine_pass of the same pass and on its
     arguments: kin = the object's kinematic table (672,) or a library's (ninst, 672) on the device; params = a pack_refine(joints=...) table
-    (24,); sums (B, K, 2, 32 or 36) what the pass wrote.  Overwrites pose_out (B, K, 26) and best (B, K, 2, 18); state (B, K, 2, 18) and obj
+    (24,), or (32,) with joint values; sums (B, K, 2, 32, 36 or 40) what the pass wrote.  Overwrites pose_out (B, K, 26) and best (B, K, 2, 18); state (B, K, 2, 18) and obj
     (B, 2, 8; OBJ_COLUMNS) are its own, written on pass 0 and carried from pass to pass; xi (B, 2, 48) or None: the clamped step.  -> pose_out."""
     from ..depth import KIN_WIDTH, RENDER_WIDTH
     _lib.require_device(pose_in)
@@ -277,8 +362,8 @@ def refine_joint_step(kin, scene, pred_render, norm_factor, params, pass_index, 
     ninst = int(kin.shape[0]) if kin.dim() == 2 else 1
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
     _params("ancsh_refine_joint_step", params)
-    if sums.dim() != 4 or sums.shape[3] not in (REFINE_SUMS, REFINE_SIL_SUMS):
-        raise ValueError("sums must be a contiguous (%d, %d, 2, %d or %d) float64 tensor" % (B, K, REFINE_SUMS, REFINE_SIL_SUMS))
+    if sums.dim() != 4 or sums.shape[3] not in (REFINE_SUMS, REFINE_SIL_SUMS, REFINE_COV_SUMS):
+        raise ValueError("sums must be a contiguous (%d, %d, 2, %d, %d or %d) float64 tensor" % (B, K, REFINE_SUMS, REFINE_SIL_SUMS, REFINE_COV_SUMS))
     _f64("sums", sums, (B, K, 2, int(sums.shape[3])))
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
@@ -317,10 +402,12 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
     (pass p in row p); one row holds the last pass's.  refine_buffers(silhouette=True), with a (16,) table: ancsh_silhouette_field once in
     front of the loop and ancsh_refine_pass_sil in it -- 5 (iters + 1) + 2 launches.  kin = the kinematic table(s) on the device, with a
     (24,) table and refine_buffers(joints=True): ancsh_refine_joint_step behind every pass -- 6 (iters + 1) + 1 launches (+ 1 with the field);
-    obj and xi of `passes` > 1 rows keep every pass's (one device copy carries the object's row on).  -> (B, K, ld + 36) float64."""
+    obj and xi of `passes` > 1 rows keep every pass's (one device copy carries the object's row on).  refine_buffers(coverage=True), with
+    a (32,) table: ancsh_coverage_field behind the renderer and ancsh_refine_pass_cov in every pass -- 6 (iters + 1) + 2 launches, 7 (iters +
+    1) + 2 with the joint step.  -> (B, K, ld + 36) float64."""
     from ..depth import render_depth
     from .reprojection import reproject_scene_build
-    work, best, sums, field, state, obj, xi = buffers
+    work, best, sums, field, state, obj, xi, cover = buffers
     joints = kin is not None
     if joints != (state is not None):
         raise ValueError("the joint step takes both kin and refine_buffers(joints=True)")
@@ -331,9 +418,11 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
     for p in range(iters + 1):
         reproject_scene_build(render, scene, rig, norm_factor, src, geom, cap, out=tables)
         render_depth(mesh, tables[1], tables[0], depth_dtype, out=pred[:2], scratch=pred[2])
+        if cover is not None:
+            coverage_field(pred, tables[1], scene, int(carried.shape[1]), out=cover)
         dst = work[p % 2]
         refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
-                    sums[p if sums.shape[0] > 1 else 0], field=field)
+                    sums[p if sums.shape[0] > 1 else 0], field=field, cover=cover)
         if joints:
             if p and obj.shape[0] > 1:
                 obj[p].copy_(obj[p - 1])

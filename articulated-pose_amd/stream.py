@@ -299,7 +299,7 @@ def check_joint_source(joint_source):
 
 class Options(collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
                                      "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
-                                     "coord_regress_loss record_width record_key art_width rows inputs refine_joints silhouette refine")):
+                                     "coord_regress_loss record_width record_key art_width rows inputs refine_coverage refine_joints silhouette refine")):
     __slots__ = ()
 
     @property
@@ -339,7 +339,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     frame (render-and-compare ICP); the record's refinement block (pose.refinement.COLUMN_NAMES), under the name "record_refined".
         A table of pack_refine(silhouette=...) turns the silhouette term on (Options.silhouette): one more launch and 4 bytes per pixel and part.
         A table of pack_refine(joints=...) (with kinematics) turns the joint step on (Options.refine_joints): the parts of an object are
-        solved together through their joints, one more launch per pass."""
+        solved together through their joints, one more launch per pass.
+        A table of pack_refine(silhouette=..., coverage=...) turns the coverage term on (Options.refine_coverage): one more launch per pass
+        (ancsh_coverage_field) and 8 bytes per pixel and part; with joint values it needs kinematics like a pack_refine(joints=...) table."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -408,6 +410,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     refine = refinement_mod.check_refine(refine, render_mesh is not None)
     silhouette = refinement_mod.has_silhouette(refine)                   # the slot then owns the field's planes
     refine_joints = refinement_mod.has_joints(refine)                    # ... and the joint step's two buffers
+    refine_coverage = refinement_mod.has_coverage(refine)                # ... and the predicted field's planes
     if refine_joints and kinematics is None:
         raise ValueError("refine=<pose.refinement.pack_refine(joints=...)> solves an object's parts together through the joints of its "
                          "kinematic table: it needs kinematics=<depth.pack_kinematics(...)> (" + RENDERED + ")")
@@ -430,7 +433,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, 20 if joint_states else 12, rows, (), refine_joints, silhouette, refine)
+                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, 20 if joint_states else 12, rows, (), refine_coverage, refine_joints, silhouette, refine)
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +

@@ -53,6 +53,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_reproject_scene_build, ancsh_reproject_compare_rec (render-and-compare of a pose record),
                                  *     ancsh_refine_pass, ancsh_refine_rec (render-and-compare ICP: that record's poses refined on the depth frame),
                                  *     ancsh_silhouette_field, ancsh_refine_pass_sil (that loop's silhouette term: poses shifted across the ray come back),
+                                 *     ancsh_coverage_field, ancsh_refine_pass_cov (its coverage term: a part is pulled over observed pixels it leaves bare),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1622,7 +1623,7 @@ int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts
  *   object), as the *_lib entries carry it;  scene, pred_render, norm_factor, pass, is_last, pose_in, ld_in : what the pass of this `pass` was
  *   given;  params : ONE table of ANCSH_REFINE_JOINT_PARAMS = 24 float64: [0..7] ancsh_refine_pass's, [8..15] ancsh_refine_pass_sil's (all 0
  *   without the term; not read here), [16] weight > 0, [17] axis_length >= 0 (the scaled cloud's unit), [18..23] reserved, 0;
- *   sums (nframes, K, 2, sums_ld), sums_ld = 32 or 36 : what that pass wrote;  pose_out (nframes, K, 26) and best (nframes, K, 2, 18) : what
+ *   sums (nframes, K, 2, sums_ld), sums_ld = 32 or 36 (40: below) : what that pass wrote;  pose_out (nframes, K, 26) and best (nframes, K, 2, 18) : what
  *   that pass wrote, overwritten here;  state (nframes, K, 2, 18) : this entry's own shadow of the best block, written on pass 0, read and
  *   written later;  obj (nframes, 2, ANCSH_REFINE_OBJ = 8) : the object's row, likewise;  xi (nframes, 2, 48) or NULL : the clamped step, for
  *   debugging (0 where nothing was solved and behind 6 K).
@@ -1669,7 +1670,7 @@ int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts
  *   the joints' squared position residuals |r0_0..2|^2) / joints), NaN without one].
  *   No atomics, the same bytes every run; no host sync, no allocation: graph-capturable.  nframes == 0 launches nothing and returns 0.
  *   Checked before any launch: 0 <= nframes <= 32767, 1 <= K <= 8, 1 <= ninst <= 65535, 0 <= pass <= ANCSH_REFINE_MAX_ITERS, is_last in {0,
- *   1}, ld_in >= 26, sums_ld in {32, 36}, null pointers (xi may be NULL), the alignments (norm_factor 4, everything else 8 bytes), pose_in !=
+ *   1}, ld_in >= 26, sums_ld in {32, 36, 40}, null pointers (xi may be NULL), the alignments (norm_factor 4, everything else 8 bytes), pose_in !=
  *   pose_out, best != state. */
 #define ANCSH_REFINE_JOINT_PARAMS 24
 #define ANCSH_REFINE_OBJ 8
@@ -1677,6 +1678,63 @@ int ancsh_refine_joint_step(int nframes, int K, const double *kin, int ninst, co
                             const float *norm_factor, const double *params, int pass, int is_last, const double *pose_in, int ld_in,
                             const double *sums, int sums_ld, double *pose_out, double *best, double *state, double *obj, double *xi,
                             void *stream);
+
+/* The coverage term of render-and-compare ICP, two entries beside those above (no new ABI number: callers detect them by their symbols).  The
+ * silhouette term is one-sided: a predicted pixel that hangs over the observed part's edge is pulled back, but an observed pixel of the part
+ * that the prediction leaves BARE is only charged max_dist^2, a flat charge that pulls nothing.  These rows pull the part over such pixels.
+ * They need the silhouette term.  The loop becomes: ancsh_silhouette_field once, then pass = 0 .. iters: ancsh_reproject_scene_build, the
+ * renderer, ancsh_coverage_field, ancsh_refine_pass_cov[, ancsh_refine_joint_step]; then ancsh_refine_rec, unchanged.
+ *
+ * ancsh_coverage_field: ONE launch, directly behind the renderer in every pass: ancsh_silhouette_field's computation on the PREDICTED pair.
+ *   pred_depth, pred_labels : the renderer's buffers of 2 * pixel_capacity pixels, pose v's half first pixel v * pixel_capacity;  geom_out (2 *
+ *   nframes, 5) : ancsh_reproject_scene_build's description of the 2 * nframes predicted frames, row v * nframes + f = pose v of frame f;
+ *   scene (nframes, 240) : frame row v * nframes + f reads scene row f.  For every predicted frame, part j and crop pixel (i, jj): the nearest
+ *   pixel of the same crop that is PREDICTED for part j (ancsh_reproject_compare_rec's rule on the predicted pair), by ancsh_silhouette_field's
+ *   order (di di + dj dj, then the lower row, then the lower column, in integers), in its word format and with its SENTINEL.
+ *   cover (K, 2 * pixel_capacity) int32: part j's plane is cover + j * 2 * pixel_capacity, and a crop pixel's word lies at the pixel's own
+ *   address in the predicted buffers, geom_out[v * nframes + f].start + i * w + jj.  Words outside the crops are not written.  8 bytes per
+ *   pixel of pixel_capacity and part.  The same kernel, the same grid per frame, the same bytes every run; graph-capturable.  nframes == 0
+ *   launches nothing and returns 0.  Checked before any launch: ancsh_silhouette_field's checks (pixel_capacity is the observed buffers', 0 <=
+ *   pixel_capacity < 2^29; a crop must lie inside [0, 2 * pixel_capacity) or it counts as no crop).
+ *
+ * ancsh_refine_pass_cov: ancsh_refine_pass_sil with the term, ONE launch.  ancsh_refine_pass_sil's arguments, and cover (above) behind field;
+ *   params : ONE table of ANCSH_REFINE_COV_PARAMS = 32 float64: [0..7] ancsh_refine_pass's, [8..15] ancsh_refine_pass_sil's, [16..23] the
+ *   joint step's (all 0: the joint step is off; not read here), [24] weight_c > 0, [25] dist_c > 0 (the scaled cloud's unit), [26] slack_c >= 0
+ *   (pixels), [27..31] reserved, 0;  sums (nframes, K, 2, ANCSH_REFINE_COV_SUMS = 40).
+ *   Every rule of ancsh_refine_pass_sil holds for the depth rows and the overhang pixels.  In addition crop pixel a = (i, jj) is a GAP pixel of
+ *   (part j, pose v) when the observed pixel is part j and the predicted pixel is not part j.  A pixel is a depth row, an overhang pixel or a
+ *   gap pixel, never two of them, so the order of addition is unchanged.  For a gap pixel, z_o = (double)d_obs * depth_scale, in this order (a
+ *   skipped pixel costs nothing more than the max_dist^2 it is charged as a missed pixel):
+ *   1. the predicted pixel is another part: z_q = (double) the float32 in its key's upper half;  !(z_q > z_o): the prediction puts another
+ *      part in front -- skipped (the overhang's occlusion rule, mirrored).
+ *   2. the cover word (di, dj) of part j at this pixel in pose v's half, cover[j * 2 * pixel_capacity + v * pixel_capacity + start + i * w +
+ *      jj]:  the SENTINEL (the part drew no pixel in this frame): skipped;  (double)(di di + dj dj) <= slack_c slack_c: skipped.  (A word that
+ *      points outside the crop -- never one of ancsh_coverage_field's -- is skipped.)
+ *   3. a2 = (i + di, jj + dj), the nearest predicted pixel of the part;  z_2 = (double) the float32 in a2's key's upper half;  u, w from (row,
+ *      col) = (row0 + i, col0 + jj) and u2, w2 from (row + di, col + dj), integers converted afterwards, as the overhang row does.
+ *   4. pn = cloud(z_2 u2, z_2 w2, z_2), the predicted surface point;  pt = cloud(z_2 u, z_2 w, z_2), the same depth on the bare pixel's ray;
+ *      dvec_a = pn_a - pt_a (its z component is exactly 0);  m = |dvec|.  m > 0 fails (NaN included): skipped.
+ *   5. m > dist_c: the pixel is FAR, n_cfar grows by one, no row.
+ *   6. otherwise g = dvec / m, r = weight_c m, pc = pn - c, J = weight_c [pc x g | g] in the overhang row's component order: J_x J_y into A, J_x
+ *      r into b, m m into sum m_c^2, and n_cov grows by one.
+ *   The row, like the overhang's, is linearised at fixed image geometry; it moves R and t only (s and q are carried).
+ *   sums row: [0..35] ancsh_refine_pass_sil's, A and b with the coverage rows | [36] sum m_c^2 | [37] n_cov | [38] n_cfar | [39] 0.
+ *   C = (ancsh_refine_pass_sil's numerator + (weight_c weight_c) (sum m_c^2 + (dist_c dist_c) n_cfar)) / n_obs, added last; NaN when n_obs ==
+ *   0.  The solve runs when (n_used + n_sil) + n_cov >= min_pixels.  NaN rules: as above; sums[31], sums[35] and sums[39] are 0.  The solve,
+ *   the clamp, the quaternion update and best-of are ancsh_refine_pass's.  Checked before any launch: ancsh_refine_pass_sil's checks, cover
+ *   not null and 4-byte aligned.
+ *
+ * ancsh_refine_joint_step accepts sums_ld == 40 and a 32-value table with joint values: n_j = (sums[28] + sums[33]) + sums[37]; it reads
+ *   params [16] and [17] as of a 24-value table; everything else is as stated above. */
+#define ANCSH_REFINE_COV_SUMS 40
+#define ANCSH_REFINE_COV_PARAMS 32
+int ancsh_coverage_field(int nframes, int K, int depth_type, const void *pred_depth, const unsigned char *pred_labels, long pixel_capacity,
+                         const int *geom_out, const double *scene, int *cover, void *stream);
+int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                          const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity, const unsigned long long *pred_zbuf,
+                          const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
+                          const double *pred_render, const float *norm_factor, const double *params, const int *field, const int *cover,
+                          int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

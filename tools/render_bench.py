@@ -24,13 +24,15 @@ one ancsh_refine_pass alone on one batch of 32 frames whose record draws every p
 device wrappers (pose.refinement.refine_batch) on it, and the eager operator depth.refine_frames from host arrays.
 --refine N --silhouette adds a third leg, s: the rendered stream built with refine=pack_refine(iters=N, silhouette=dict(weight=1, dist=0.1,
 slack=1)), and times ancsh_silhouette_field, one ancsh_refine_pass_sil and the whole loop with the term on the same batch and record.
+--refine N --silhouette --coverage adds a fourth leg, c: the rendered stream built with the same table and coverage=dict(weight=1, dist=0.1,
+slack=1), next to silhouette-only (s) and plain (f), and times ancsh_coverage_field, one ancsh_refine_pass_cov and the whole loop with both terms.
 --refine N --joints measures the joint step (refine=pack_refine(iters=N, joints=dict(weight=1, axis_length=0.5))) instead, on the POSED stream
 (the option needs the kinematic table: link 1 hangs on a revolute, link 2 on a prismatic joint of link 0): two legs, alternated:
     f: the posed stream built with refine=pack_refine(iters=N);   j: the same with joints=;
 ancsh_refine_joint_step alone on one batch of 32 frames whose record draws every part a different distance off its place, and the share of
 that batch's objects whose joints' position residual (obj's gap_rms) is lower at the last pass than at the first.
 
-    python tools/render_bench.py [--sensor | --reprojection | --refine N [--silhouette | --joints]] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+    python tools/render_bench.py [--sensor | --reprojection | --refine N [--silhouette [--coverage] | --joints]] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -218,13 +220,16 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
     from articulated_pose_amd.pose import refinement as F, reprojection as R
     table = F.pack_refine(iters=args.refine)
     sil_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0)) if args.silhouette else None
-    legs = "rfs" if args.silhouette else "rf"
+    cov_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0), coverage=dict(weight=1.0, dist=0.1, slack=1.0)) if args.coverage else None
+    legs = "rfsc" if args.coverage else "rfs" if args.silhouette else "rf"
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
     pipes = {"r": AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare(), "f": AncshPipeline(K, wa, wn, B, N, dev, refine=table, **kw).prepare()}
     if args.silhouette:
         pipes["s"] = AncshPipeline(K, wa, wn, B, N, dev, refine=sil_table, **kw).prepare()
+    if args.coverage:
+        pipes["c"] = AncshPipeline(K, wa, wn, B, N, dev, refine=cov_table, **kw).prepare()
     torch.cuda.synchronize()
     last = {}
 
@@ -286,6 +291,27 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
                               "median_cost_start": float(np.median(scols["baseline_cost_start"])),
                               "median_cost_best": float(np.median(scols["baseline_cost_best"])),
                               "parts_improved": int((scols["baseline_cost_best"] < scols["baseline_cost_start"]).sum()), "parts": B * K}}
+    if args.coverage:                                                     # ... and with both terms: the predicted field, one pass, the loop
+        d_cpar = torch.from_numpy(cov_table).to(dev)
+        cbufs = F.refine_buffers(B, K, dev, silhouette=True, pixel_capacity=cap, coverage=True)
+        R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
+        D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
+        F.silhouette_field(clean[0], clean[1], d_geom, d_sc, K, out=cbufs.field)
+        op_ms["coverage_field"] = timed_calls(lambda: F.coverage_field(pred, tables[1], d_sc, K, out=cbufs.cover), args.rounds, args.calls)
+        op_ms["refine_pass_cov"] = timed_calls(lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_cpar, 0, False,
+                                                                     carried, cbufs.work[0], cbufs.best, cbufs.sums[0], field=cbufs.field,
+                                                                     cover=cbufs.cover), args.rounds, args.calls)
+        c0 = cbufs.sums[0].cpu().numpy()
+        cloop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_cpar, args.refine, cbufs)
+        op_ms["whole_loop_cov"] = timed_calls(cloop, args.rounds, max(1, args.calls // 10))
+        ccols = F.named_columns(cloop().cpu().numpy())
+        sil["coverage"] = {"table": cov_table[24:27].tolist(), "launches_added": 6 * (args.refine + 1) + 2, "cover_bytes_per_slot": 8 * K * cap,
+                           "added_ms_per_batch_over_silhouette": round(med["c"] - med["s"], 4), "c_over_s": round(med["c"] / med["s"], 4),
+                           "c_over_r": round(med["c"] / med["r"], 4), "gap_rows_per_part_and_pose": float(c0[..., 37].mean()),
+                           "far_gap_pixels_per_part_and_pose": float(c0[..., 38].mean()),
+                           "median_cost_start": float(np.median(ccols["baseline_cost_start"])),
+                           "median_cost_best": float(np.median(ccols["baseline_cost_best"])),
+                           "parts_improved": int((ccols["baseline_cost_best"] < ccols["baseline_cost_start"]).sum()), "parts": B * K}
     frames = D._cut_frames(clean[0].cpu().numpy().view(np.uint16), clean[1].cpu().numpy(), d_geom.cpu().numpy(), "uint16")
     eager = []
     for _ in range(args.rounds):
@@ -413,6 +439,7 @@ def main():
     ap.add_argument("--reprojection", action="store_true", help="measure render-and-compare (reprojection=True) instead of the renderer")
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="measure render-and-compare ICP (refine=pack_refine(iters=N)) instead of the renderer")
     ap.add_argument("--silhouette", action="store_true", help="with --refine N: measure the silhouette term as well (a third leg and its launches)")
+    ap.add_argument("--coverage", action="store_true", help="with --refine N --silhouette: measure the coverage term as well (a fourth leg and its launches)")
     ap.add_argument("--joints", action="store_true", help="with --refine N: measure the joint step on the posed stream (joints= off and on, alternated)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
@@ -422,6 +449,8 @@ def main():
     ap.add_argument("--tess", type=int, default=8, help="quads per box edge: 12 tess^2 triangles per link")
     ap.add_argument("--calls", type=int, default=200, help="back-to-back calls of the operator between its two events")
     args = ap.parse_args()
+    if args.coverage and not (args.refine and args.silhouette):
+        ap.error("--coverage goes with --refine N --silhouette: the coverage term runs with the silhouette term")
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
     mesh = D.pack_mesh([tessellated_box(LO, HI, args.tess)] * K)
