@@ -195,6 +195,9 @@ SIGNATURES = {
     # the joint step (no ABI bump, detected by its symbol): nframes, K, kin, ninst, scene, pred_render, norm_factor, params, pass, is_last,
     # pose_in, ld_in, sums, sums_ld, pose_out, best, state, obj, xi, stream
     "ancsh_refine_joint_step": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int] + [_vp] * 6,
+    # the joint values behind the articulation block (no ABI bump, detected by its symbol): nframes, K, kin, ninst, pose, render, scene, rig,
+    # rig_ld, norm_factor, record, ld, refined, art, art_ld, wide, stream
+    "ancsh_joint_values_rec": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp],
     # both stages of the pose fit in one call (no ABI bump, detected by their symbols): ancsh_ransac_single_rec*'s arguments without record / K
     # (nprob_a .. tie_window_a), ancsh_ransac_joint_rec*'s without src / tgt / max_n / record / K (nprob_b .. tie_window_b), record, K,
     # [joint_kind,] stream

@@ -1,6 +1,7 @@
-// compare_common.h -- what render-and-compare's two files (reprojection.hip scores a pose record, refinement.hip acts on it) share: which
-// pixel belongs to which part, when a pose counts, the short formulas both spell -- each in the parenthesisation and operand order its callers
-// had (float64 is evaluated as written and the Python mirrors follow it operation by operation) -- and the C entries' argument checks.
+// compare_common.h -- what render-and-compare's files (reprojection.hip scores a pose record, refinement.hip acts on it, joint_values.hip reads
+// the joint values off it) share: which pixel belongs to which part, when a pose counts, the predicted map of a link under a pose, the short
+// formulas they spell -- each in the parenthesisation and operand order its callers had (float64 is evaluated as written and the Python mirrors
+// follow it operation by operation) -- and the C entries' argument checks.
 #pragma once
 #include "depth_annotate_common.h"
 
@@ -41,7 +42,61 @@ __device__ __forceinline__ void pixel_ray(const double *__restrict__ sc, double 
     sv = (sc[10] * col + sc[11] * row) + sc[12];
 }
 
-// ---- the seven entries' argument checks: each sets the error and returns false; an entry calls them through ANCSH_CHECK, who = its name
+// C = A o B of 3 x 4 maps, row-major, in ancsh_pose_scene_build's written order
+__device__ __forceinline__ void rp_compose(const double *A, const double *B, double *C) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = (A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
+            C[4 * i + j] = j == 3 ? v + A[4 * i + 3] : v;
+        }
+    }
+}
+// the predicted map of link l of part j under a 13-value pose, steps 1..5 of ancsh_reproject_scene_build (include/ancsh_hip.h): rt, sc, rg =
+// the frame's render table, scene table and rig row; R = the 12 values written.  The caller has checked l, j, the pose and nf.
+__device__ __forceinline__ void predicted_link_map(const double *__restrict__ rt, const double *__restrict__ sc, const double *__restrict__ rg,
+                                                   int K, int l, int j, const double *__restrict__ pose, double nf, double *R) {
+    const double *L = sc + AN_HEAD + AN_LINK * l;
+    double Rl[12], M[12], N[12], Q[12], P[12], T1[12], T2[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Rl[k] = rt[ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l + k], M[k] = L[2 + k];
+    rp_compose(M, Rl, N);                                               // 1. model -> canonical coordinates
+    const double *pt = rg + ANCSH_RIG_HEAD + j * ANCSH_RIG_PART(K);
+    double o[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = ((((0.0 - pt[a]) - pt[3 + a]) * pt[6 + a]) + 0.5) - pt[9 + a];        // nocs_p of c = 0
+    if (rg[3] != 0.0) {                                                 // 2. canonical -> part NOCS, with the sapien rotation
+        const double *Rr = rg + ANCSH_RIG_ROT;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) Q[4 * a + k] = Rr[3 * a + k] * pt[6 + k];
+            Q[4 * a + 3] = ((Rr[3 * a] * (o[0] - 0.5) + Rr[3 * a + 1] * (o[1] - 0.5)) + Rr[3 * a + 2] * (o[2] - 0.5)) + 0.5;
+        }
+    } else {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) Q[4 * a + k] = a == k ? pt[6 + k] : 0.0;
+            Q[4 * a + 3] = o[a];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {                                       // 3. part NOCS -> the scaled cloud: [s R | t]
+#pragma unroll
+        for (int k = 0; k < 3; ++k) P[4 * a + k] = pose[9] * pose[3 * a + k];
+        P[4 * a + 3] = pose[10 + a];
+    }
+    rp_compose(Q, N, T1);
+    rp_compose(P, T1, T2);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)                                         // 4. / norm factor, 5. (x, y, z) -> (x', y', z) = (x, -y, z)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R[4 * a + k] = a == 1 ? -(T2[4 * a + k] / nf) : T2[4 * a + k] / nf;
+}
+
+// ---- the entries' argument checks: each sets the error and returns false; an entry calls them through ANCSH_CHECK, who = its name
 #define ANCSH_ALIGNED "%s: a pointer is not aligned: the depth buffers to their element, 4-byte values 4-byte, 8-byte values 8-byte aligned"
 #define ANCSH_CHECK(ok) do { if (!(ok)) return ANCSH_EINVAL; } while (0)
 template <typename... A>

@@ -19,18 +19,6 @@ namespace ancsh {
 constexpr int RP_LINKS = ANCSH_SCENE_MAX_LINKS, RP_THREADS = 256, RP_WIDTH = ANCSH_REPROJECTION_WIDTH;
 constexpr int RP_RENDER = ANCSH_RENDER_WIDTH;
 
-// C = A o B of 3 x 4 maps, row-major, in ancsh_pose_scene_build's written order
-__device__ __forceinline__ void rp_compose(const double *A, const double *B, double *C) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double v = (A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j];
-            C[4 * i + j] = j == 3 ? v + A[4 * i + 3] : v;
-        }
-    }
-}
-
 __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int nframes, int K, const double *__restrict__ render,
                                                                            const double *__restrict__ scene, const double *__restrict__ rig,
                                                                            int rig_ld, const float *__restrict__ norm_factor,
@@ -58,7 +46,6 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int n
         for (int k = 0; k < ANCSH_RENDER_LINK; ++k) R[k] = 0.0;
         return;
     }
-    const double *L = sc + AN_HEAD + AN_LINK * l;
     const double nf = (double)norm_factor[f];
     const int j = scene_link_part(sc, l, nl, K);
     const double *pose = record + ((size_t)f * K + (j < 0 ? 0 : j)) * ld + 13 * v;
@@ -68,42 +55,7 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_scene_build_kernel(int n
         for (int k = 0; k < ANCSH_RENDER_LINK; ++k) R[k] = q;
         return;
     }
-    double Rl[12], M[12], N[12], Q[12], P[12], T1[12], T2[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) Rl[k] = rt[ANCSH_RENDER_HEAD + ANCSH_RENDER_LINK * l + k], M[k] = L[2 + k];
-    rp_compose(M, Rl, N);                                               // 1. model -> canonical coordinates
-    const double *pt = rig + (size_t)f * rig_ld + ANCSH_RIG_HEAD + j * ANCSH_RIG_PART(K), *rg = rig + (size_t)f * rig_ld;
-    double o[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) o[a] = ((((0.0 - pt[a]) - pt[3 + a]) * pt[6 + a]) + 0.5) - pt[9 + a];        // nocs_p of c = 0
-    if (rg[3] != 0.0) {                                                 // 2. canonical -> part NOCS, with the sapien rotation
-        const double *Rr = rg + ANCSH_RIG_ROT;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Q[4 * a + k] = Rr[3 * a + k] * pt[6 + k];
-            Q[4 * a + 3] = ((Rr[3 * a] * (o[0] - 0.5) + Rr[3 * a + 1] * (o[1] - 0.5)) + Rr[3 * a + 2] * (o[2] - 0.5)) + 0.5;
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Q[4 * a + k] = a == k ? pt[6 + k] : 0.0;
-            Q[4 * a + 3] = o[a];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {                                       // 3. part NOCS -> the scaled cloud: [s R | t]
-#pragma unroll
-        for (int k = 0; k < 3; ++k) P[4 * a + k] = pose[9] * pose[3 * a + k];
-        P[4 * a + 3] = pose[10 + a];
-    }
-    rp_compose(Q, N, T1);
-    rp_compose(P, T1, T2);
-#pragma unroll
-    for (int a = 0; a < 3; ++a)                                         // 4. / norm factor, 5. (x, y, z) -> (x', y', z) = (x, -y, z)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R[4 * a + k] = a == 1 ? -(T2[4 * a + k] / nf) : T2[4 * a + k] / nf;
+    predicted_link_map(rt, sc, rig + (size_t)f * rig_ld, K, l, j, pose, nf, R);      // steps 1..5: compare_common.h, shared with joint_values.hip
 }
 
 __device__ __forceinline__ long rp_quantum(unsigned short p, unsigned short o) { return (long)p - (long)o; }

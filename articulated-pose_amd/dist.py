@@ -349,6 +349,9 @@ class ShardedPipeline(object):
             raise ValueError("ShardedPipeline does not shard rendered frames: refine=<pose.refinement.pack_refine(...)> re-renders the mesh of a "
                              "pipeline built with render_mesh=<depth.pack_mesh(...)>, which AncshPipeline takes on one GPU (submit_render / "
                              "submit_posed)")
+        if pipeline_kw.get("joint_values"):
+            raise ValueError("ShardedPipeline does not shard rendered frames: joint_values=True reads the joint values off the part poses of a "
+                             "pipeline built with kinematics=<depth.pack_kinematics(...)>, which AncshPipeline takes on one GPU (submit_posed)")
         # what only the raw stream carries (step() / records(), the RCCL path, keep the 26-column record), then the rules shared with
         # AncshPipeline.  The articulation block travels with the records in the SAME gather -- one (n_max, K, record_width + art_width)
         # float64 row per rank, split on dst --, the ground truth, frames and rigs are handed out by submit(), shard by shard.

@@ -384,6 +384,12 @@ class AncshPipeline(object):
         n_used, best_pass, passes_solved) behind the record so far; pose.refinement.refined_record(record, layout=pipe.record_layout) gives the
         (.., 26) record of the refined poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the
         (B, K, 2, 32) sums besides.
+    joint_values (with kinematics= and articulation): the step's last launch (ancsh_joint_values_rec), behind ancsh_refine_rec when refine= is on,
+        inverts ancsh_pose_scene_build's forward kinematics on the part poses: per part and pose the joint value q of the part's bridging joint
+        in the kinematic table's own parametrisation, its error against the submitted q, and the angle and gap by which the two sides of the
+        joint miss one axis -- for the record's two poses and, with refine=, the two kept refined poses (NaN without).  The 24 columns
+        (pose.joint_values.COLUMN_NAMES; named_columns, joint_value_table) ride behind the articulation block's 12 or 20: it is still
+        out["articulation"], no new name in the result tuple or the record.  Works with a library.
     In every streaming mode out["record"] stays (B, K, 26); the RECORD that retire / stream_* return is the widest one built,
     out[pipe.record_layout.key], pipe.record_layout.width columns."""
 
@@ -394,7 +400,7 @@ class AncshPipeline(object):
                  arithmetic=None, raw_capacity=None, range_guard=False, keyed=False, articulation=False, dense=False, joint_source="gt",
                  joint_types=None, depth_capacity=None, depth_dtype="uint16", label_images=False, joint_states=False, fit_quality=False,
                  ground_truth=False, point_ground_truth=False, coord_regress_loss="L2", build_point_gt=False, build_gt_pose=False,
-                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None, reprojection=False, refine=None):
+                 render_mesh=None, kinematics=None, annotated_images=False, sensor=None, reprojection=False, refine=None, joint_values=False):
         # the options, checked on the host before anything touches the GPU
         from .pose.parallel_ancsh_pose import check_joint_types
         check_joint_types(joint_types, num_parts)
@@ -403,7 +409,7 @@ class AncshPipeline(object):
         self.opts = o = check_options(batch_size, num_points, couple, inlier_th, raw_capacity, depth_capacity, depth_dtype, keyed, range_guard,
                                       arithmetic, articulation, joint_states, fit_quality, ground_truth, point_ground_truth, build_point_gt, dense,
                                       label_images, joint_source, coord_regress_loss, build_gt_pose, render_mesh, kinematics, annotated_images, sensor,
-                                      reprojection, refine)
+                                      reprojection, refine, joint_values=joint_values)
         self.refine = o.refine
         self.record_layout = o.layout           # where each block of the streamed record lies (pose.record.RecordLayout)
         for name in OPTION_FLAGS:               # pipe.keyed, pipe.articulation, ...: what the step, the tools and dist.ShardedPipeline read
@@ -620,6 +626,11 @@ class AncshPipeline(object):
                                                  kin=self.kin if self.opts.refine_joints else None)
             if self.opts.refine_joints:  # the joint step's row per (frame, pose): (B, 2, 8) float64, slot-owned, not streamed
                 out["refine_object"] = sl.refine_bufs.obj[0]
+        if self.opts.joint_values:       # the step's last launch: the joint values q read off the record's two poses per part and, with refine=, the
+            # kept refined ones, against the submitted pose table -> the articulation block and the 24 columns behind it, (B, K, art_width)
+            from .pose.joint_values import joint_values_batch
+            out["articulation"] = joint_values_batch(self.kin, sl.render, sl.scene, sl.rig, sl.header(self.B)[2], sol["record"], out["articulation"],
+                                                     pose=sl.pose, refined=sl.refine_bufs.best if self.refine else None)
         if self.build_gt_pose:           # the tables the step built: (B, K, 19) and (B, 13) float64, slot-owned
             out["gt_pose"], out["gt_frame"] = sl.gt_built, sl.frame_built
         if guard:

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import dataset, depth as depth_mod
-from .pose import gt_errors, joint_params, point_gt, quality, refinement as refinement_mod, reprojection as reprojection_mod
+from .pose import gt_errors, joint_params, joint_values as joint_values_mod, point_gt, quality, refinement as refinement_mod, reprojection as reprojection_mod
 from .pose.record import RecordLayout
 
 # ---- the slot header ---------------------------------------------------------------------------------------------------------
@@ -299,7 +299,7 @@ def check_joint_source(joint_source):
 
 class Options(collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
                                      "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
-                                     "coord_regress_loss record_width record_key art_width rows inputs refine_coverage refine_joints silhouette refine")):
+                                     "coord_regress_loss record_width record_key joint_values art_width rows inputs refine_coverage refine_joints silhouette refine")):
     __slots__ = ()
 
     @property
@@ -315,7 +315,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                   keyed=False, range_guard=False, arithmetic="f16x2", articulation=False, joint_states=False, fit_quality=False,
                   ground_truth=False, point_ground_truth=False, build_point_gt=False, dense=False, label_images=False, joint_source="gt",
                   coord_regress_loss="L2", build_gt_pose=False, render_mesh=None, kinematics=None, annotated_images=False, sensor=None,
-                  reprojection=False, refine=None):
+                  reprojection=False, refine=None, joint_values=False):
     """Every rule between the options of AncshPipeline and dist.ShardedPipeline, checked on the host before anything touches the GPU
     (ValueError) -> Options: the flags, the streamed record's width and the name the step leaves it under (pose.record.BLOCKS: the one
     table of the record's blocks; Options.layout says where each lies), the articulation block's
@@ -341,7 +341,10 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
         A table of pack_refine(joints=...) (with kinematics) turns the joint step on (Options.refine_joints): the parts of an object are
         solved together through their joints, one more launch per pass.
         A table of pack_refine(silhouette=..., coverage=...) turns the coverage term on (Options.refine_coverage): one more launch per pass
-        (ancsh_coverage_field) and 8 bytes per pixel and part; with joint values it needs kinematics like a pack_refine(joints=...) table."""
+        (ancsh_coverage_field) and 8 bytes per pixel and part; with joint values it needs kinematics like a pack_refine(joints=...) table.
+    joint_values (with kinematics and articulation): the step's last launch (ancsh_joint_values_rec) reads the joint values q off the record's
+        and, with refine, the kept refined part poses; its 24 columns (pose.joint_values.COLUMN_NAMES) ride behind the articulation block
+        (Options.art_width), as the joint states do: no new name in the result tuple or the record."""
     predicted = check_joint_source(joint_source) == "predicted"
     if articulation:
         if not couple:
@@ -350,6 +353,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
             raise ValueError("articulation=True keeps the joint medians in LDS: num_points must be in [1, %d], got %d"
                              % (joint_params.ARTICULATION_MAX_N, num_points))
     joint_states = joint_params.check_joint_states(joint_states, bool(articulation))
+    joint_values = joint_values_mod.check_joint_values(joint_values, kinematics is not None, bool(articulation))
     fit_quality = quality.check_fit_quality(fit_quality, inlier_th)
     if ground_truth and raw_capacity is None and depth_capacity is None:
         raise ValueError("ground_truth=True travels in with a streamed batch (submit / submit_depth): it needs raw_capacity or "
@@ -433,7 +437,8 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
                                                        "xyz" if predicted else "labelled"]
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
-                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, 20 if joint_states else 12, rows, (), refine_coverage, refine_joints, silhouette, refine)
+                bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, joint_values,
+                (20 if joint_states else 12) + (joint_values_mod.JOINT_VALUES_WIDTH if joint_values else 0), rows, (), refine_coverage, refine_joints, silhouette, refine)
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +

@@ -54,6 +54,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_refine_pass, ancsh_refine_rec (render-and-compare ICP: that record's poses refined on the depth frame),
                                  *     ancsh_silhouette_field, ancsh_refine_pass_sil (that loop's silhouette term: poses shifted across the ray come back),
                                  *     ancsh_coverage_field, ancsh_refine_pass_cov (its coverage term: a part is pulled over observed pixels it leaves bare),
+                                 *     ancsh_joint_values_rec (the streamed joint values: q read off the fitted and refined part poses),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
                                  * 14: + ancsh_ransac_joint_rec_kind, ancsh_ransac_joint_rec_dseed_kind, ancsh_ransac_joint_rec_dkey_kind (a joint kind per
@@ -1735,6 +1736,56 @@ int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const float *verts
                           const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
                           const double *pred_render, const float *norm_factor, const double *params, const int *field, const int *cover,
                           int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
+
+/* The joint values q of a posed frame read off its part poses: ancsh_pose_scene_build's forward kinematics inverted on the predicted link
+ * maps, ONE launch at the step's end (no new ABI number: callers detect it by its symbol).  The posed stream takes q in (pose[f][l]); this
+ * entry reports it on the way out, per part and pose, with its error against the submitted value and how far the two sides of the joint are
+ * from lying on one axis.  The reference has nothing here: its joint states (ancsh_joint_state_rec) measure part j against part 0 about the
+ * network's own axis and know nothing of the object's kinematic tree.
+ *   kin (ninst, ANCSH_KIN_WIDTH), pose (nframes, ANCSH_POSE_WIDTH) or NULL, render, scene, rig (rig_ld = ANCSH_RIG_WIDTH(K)), norm_factor,
+ *     record (nframes, K, ld >= 26) : as ancsh_pose_scene_build[_lib], ancsh_reproject_scene_build and ancsh_refine_joint_step take them; the
+ *     frame's instance is render[f][9] (0 for a single object), an integer in [0, ninst);
+ *   refined (nframes, K, 2, 18) float64 or NULL : the refinement's kept poses (its best block: values 0..12 of a row are a pose);
+ *   art (nframes, K, art_ld) float64, art_ld = 12 (ancsh_articulation_rec's block) or 20 (ancsh_joint_state_rec's);
+ *   wide (nframes, K, art_ld + ANCSH_JOINT_VALUES_WIDTH = 24) float64, a buffer of its own : columns 0..art_ld-1 of row (f, j) = art's row, bit
+ *     for bit (moved as 64-bit words: a NaN keeps its payload), the 24 columns below behind them.
+ * WHICH JOINT row j reports: the bridging joint of part j, the lowest link l in [1, nlinks) such that its part (ancsh_reproject_scene_build's
+ *   rule: the link is used and scene link value [1] lies in [0, K)) is j, its kind (kin link value [3]) is 1 or 2, its parent p (kin link
+ *   value [2]) is an integer in [0, l), and the parent's part b is in [0, K) and is not j.  A row without such a joint -- the base part, a part
+ *   behind a link of no part, a part whose joints are all fixed -- is NaN in all 24 columns; so is every row of a frame whose norm factor is 0
+ *   or not finite or whose instance value is not an integer in [0, ninst).
+ * LINK MAPS: B_l = [M_l | tau_l] is exactly what ancsh_reproject_scene_build writes for link l under its part's pose (its steps 1..5, the
+ *   same device function).  Four pose groups g: record columns 0..12, record columns 13..25, refined[f][.][0][0..12], refined[f][.][1][0..12];
+ *   the child link takes part j's pose and the parent link part b's pose, both from group g.
+ * ARITHMETIC, float64 in exactly the written order (no contraction); dot(x, y) = (x0 y0 + x1 y1) + x2 y2, |x| = sqrt(dot(x, x)); Rt[a][k] =
+ *   kin link value [4 + 4a + k], org_a = value [4 + 4a + 3], a = values [16..18] of link l:
+ *     sigma_l = sqrt(S / 3), S = the nine squares M_l[a][k]^2 added to 0 in row-major order; sigma_p likewise;
+ *     E[i][k] = ((M_p[0][i] M_l[0][k] + M_p[1][i] M_l[1][k]) + M_p[2][i] M_l[2][k]) / (sigma_p * sigma_l);
+ *     G[i][k] = (Rt[0][i] E[0][k] + Rt[1][i] E[1][k]) + Rt[2][i] E[2][k];
+ *     v = ((G21 - G12) / 2, (G02 - G20) / 2, (G10 - G01) / 2);   c = (((G00 + G11) + G22) - 1) / 2;
+ *     d_i = tau_l[i] - (dot(M_p[i], org) + tau_p[i]);   ra_i = dot(Rt[i], a);   w_i = dot(M_p[i], ra);   u = w / |w|;
+ *     revolute (kind 1):  q = atan2(dot(a, v), c);  Ga_i = dot(G[i], a), x = a x Ga = (a1 Ga2 - a2 Ga1, a2 Ga0 - a0 Ga2, a0 Ga1 - a1 Ga0),
+ *       off_axis = atan2(|x|, dot(a, Ga));  gap = |d|;
+ *     prismatic (kind 2): q = dot(d, u);  off_axis = atan2(|v|, c);  r_i = d_i - q u_i, gap = |r|;
+ *     scale_ratio = sigma_l / sigma_p;   q_err = q - q_true, q_true = pose[f][l]; for a revolute joint q_err - 2 pi when it exceeds pi, else
+ *     q_err + 2 pi when it lies below -pi (one conditional step: into [-pi, pi] for |q_true| <= pi).
+ *   In exact arithmetic and for a record that reproduces the frame's own tables M_p^T M_l / (sigma_p sigma_l) = Rt Rj(q) and d = q u
+ *   (prismatic) or 0 (revolute), J_l(q) = [Rj | tj] of ancsh_pose_scene_build: q is the submitted value, off_axis and gap vanish and the ratio
+ *   is 1.  Lengths (a prismatic q, gap) are in the renderer's unit (camera = model), not the scaled cloud's: gap * norm_factor is the distance
+ *   of the two sides in the cloud's unit, ancsh_refine_joint_step's hinge gap.  Angles are radians.
+ * COLUMNS behind the carried row:  +0 link l   +1 kind   +2 parent_part b   +3 q_true   then per group g at +4 + 5 g:  q, q_err, off_axis,
+ *   gap, scale_ratio.
+ * NaN RULES: a group's five columns are NaN when the child's or the parent's pose (13 values) is not finite, or sigma_l, sigma_p or |w| is 0
+ *   or not finite; refined == NULL: both refined groups are NaN; pose == NULL: q_true and every q_err are NaN.
+ * One thread per (frame, part, group), the grid a function of nframes and K alone; every index read from a table is range-checked before it
+ * addresses anything; no atomics, no host sync, no allocation: graph-capturable, the same bytes every run.  A few hundred double operations
+ * per thread: the launch sits on the floor of a dependent graph node.  nframes == 0 launches nothing and returns 0.  Checked before any
+ * launch: 0 <= nframes <= 32767, 1 <= K <= 8, ninst >= 1, rig_ld == ANCSH_RIG_WIDTH(K), ld >= 26, art_ld 12 or 20, null pointers (pose and
+ * refined may be NULL), the alignments (doubles 8 bytes, norm_factor 4), art != wide. */
+#define ANCSH_JOINT_VALUES_WIDTH 24
+int ancsh_joint_values_rec(int nframes, int K, const double *kin, int ninst, const double *pose, const double *render, const double *scene,
+                           const double *rig, int rig_ld, const float *norm_factor, const double *record, int ld, const double *refined,
+                           const double *art, int art_ld, double *wide, void *stream);
 
 /* Per-raw-point segmentation of a streamed batch: the FP module's upsampling rule (pointnet_util.py:219-229: 3-NN, inverse-distance
  * weights, three_interpolate) from each cloud's num_points sampled points to every one of its raw rows.  Cloud b owns raw rows

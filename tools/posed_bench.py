@@ -20,9 +20,12 @@ on a pipeline built with annotated_images=True whose stream does not ask for the
 device-to-host copies are paid, the host never touches them); i on that pipeline with stream_posed_batches(..., annotated_images=True) (the
 host also cuts every batch's four image buffers into per-frame arrays); and the option's two launches alone, HIP events around each in an
 eager step of the same pipeline (three lead launches of the entry in front of the timed one).
+--joint-values: what joint_values=True costs.  The timed legs are then the posed stream two ways, alternated in one process: d as above; v on
+a pipeline built with joint_values=True (the step's one more launch, ancsh_joint_values_rec, and a 36-column articulation block to copy out);
+and that launch alone on slot 0's buffers, HIP events around --calls back-to-back calls.
 Prints one JSON line: a record, not a gate.
 
-    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8] [--instances 1] [--library] [--idle-tess 0] [--images]
+    python tools/posed_bench.py [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8] [--instances 1] [--library] [--idle-tess 0] [--images | --joint-values]
 """
 import argparse
 import json
@@ -92,7 +95,10 @@ def main():
     ap.add_argument("--library", action="store_true", help="take the library's path for --instances 1 too")
     ap.add_argument("--idle-tess", type=int, default=0, help="append an instance of this many quads per edge that no frame shows (a library only)")
     ap.add_argument("--images", action="store_true", help="time the posed stream with and without annotated_images=True (legs d, j, i)")
+    ap.add_argument("--joint-values", action="store_true", help="time the posed stream with and without joint_values=True (legs d, v)")
     args = ap.parse_args()
+    if args.images and args.joint_values:
+        ap.error("--images and --joint-values each replace the timed legs: pass one of them")
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
     rs = np.random.RandomState(0)
     P, side, ninst = projection(), args.side, args.instances
@@ -165,9 +171,10 @@ def main():
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
-    rendered = None if args.images else AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
+    rendered = None if args.images or args.joint_values else AncshPipeline(K, wa, wn, B, N, dev, **kw).prepare()
     posed = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, **kw).prepare()
     imaged = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, annotated_images=True, **kw).prepare() if args.images else None
+    valued = AncshPipeline(K, wa, wn, B, N, dev, kinematics=kin, joint_values=True, **kw).prepare() if args.joint_values else None
     torch.cuda.synchronize()
 
     def packed_in_the_loop(passes):
@@ -181,13 +188,13 @@ def main():
         poses = (pbatches[k] for _ in range(passes) for k in range(len(pbatches)))
         gen = (rendered.stream_render_batches(tbatches[k] for _ in range(passes) for k in range(len(tbatches))) if name == "b" else
                rendered.stream_render_batches(packed_in_the_loop(passes)) if name == "c" else
-               posed.stream_posed_batches(poses) if name == "d" else imaged.stream_posed_batches(poses, annotated_images=name == "i"))
+               posed.stream_posed_batches(poses) if name == "d" else valued.stream_posed_batches(poses) if name == "v" else imaged.stream_posed_batches(poses, annotated_images=name == "i"))
         for _ in gen:
             n += 1
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0) / n          # ms per batch of B frames, steady state over the slots
 
-    legs = "dji" if args.images else "bcd"
+    legs = "dji" if args.images else "dv" if args.joint_values else "bcd"
     for name in legs:                                         # warm-up: every slot replayed with real input
         leg(name, 1)
     ms = {name: [] for name in legs}
@@ -208,14 +215,32 @@ def main():
                 if name in two:
                     two[name].append(call_ms)
             eager.retire()
-    ratios = (dict(j_over_d=round(med["j"] / med["d"], 4), i_over_d=round(med["i"] / med["d"], 4), images_ms_per_batch=round(med["i"] - med["d"], 4),
+    value_ms = []
+    if args.joint_values:                                     # the launch alone, on the buffers slot 0's last replay left behind
+        from articulated_pose_amd.pose.joint_values import JOINT_VALUES_WIDTH, joint_values_batch
+        sl = valued.slots[0]
+        art = sl.out["articulation"][:, :, :12].contiguous()
+        wide = torch.empty((B, K, 12 + JOINT_VALUES_WIDTH), dtype=torch.float64, device=dev)
+        for k in range(args.rounds + 1):
+            e0.record()
+            for _ in range(args.calls):
+                joint_values_batch(valued.kin, sl.render, sl.scene, sl.rig, sl.header(B)[2], sl.out["record"], art, pose=sl.pose, out=wide)
+            e1.record()
+            torch.cuda.synchronize()
+            if k:                                             # the first round warms up
+                value_ms.append(e0.elapsed_time(e1) / args.calls)
+    ratios = (dict(v_over_d=round(med["v"] / med["d"], 4), joint_values_ms_per_batch=round(med["v"] - med["d"], 4),
+                   joint_values_launch_us=round(1e3 * float(np.median(value_ms)), 2), joint_values_launch_us_rounds=[round(1e3 * x, 2) for x in value_ms],
+                   joint_values_d2h_bytes_per_batch=8 * B * K * JOINT_VALUES_WIDTH) if args.joint_values else
+              dict(j_over_d=round(med["j"] / med["d"], 4), i_over_d=round(med["i"] / med["d"], 4), images_ms_per_batch=round(med["i"] - med["d"], 4),
                    images_d2h_bytes_per_batch=60 * cap, images_pinned_bytes=60 * cap * args.slots,
                    images_launch_us={k: round(1e3 * float(np.median(v)), 2) for k, v in two.items()},
                    images_launch_us_rounds={k: [round(1e3 * x, 2) for x in v] for k, v in two.items()}) if args.images else
               dict(d_over_b=round(med["d"] / med["b"], 4), d_over_c=round(med["d"] / med["c"], 4)))
     print(json.dumps({"metric": "frames/s: the rendered stream with tables packed before the clock (b) and inside the loop (c) vs the posed stream (d); "
                                 "the host packers (a) and the two new entries alone (e); --images: the posed stream (d) vs the same stream built "
-                                "with annotated_images=True, not asked for (j) and asked for (i)",
+                                "with annotated_images=True, not asked for (j) and asked for (i); --joint-values: the posed stream (d) vs the same stream built "
+                                "with joint_values=True (v)",
                       "device": torch.cuda.get_device_name(0), "host_pack_us_per_frame": {k: round(v, 1) for k, v in pack_us.items()},
                       "host_pack_frames_per_s_one_core": round(1e6 / sum(pack_us.values()), 1),
                       "entries_us_per_batch": round(1e3 * op, 2), "entries_us_per_batch_rounds": [round(1e3 * x, 2) for x in op_ms],
