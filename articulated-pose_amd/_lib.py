@@ -192,6 +192,9 @@ SIGNATURES = {
     "ancsh_coverage_field": [_c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp, _vp],
     "ancsh_refine_pass_cov": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 10 + [_c_int, _c_int, _vp, _c_int,
                               _vp, _vp, _vp, _vp],
+    # the scale unknown (no ABI bump, detected by its symbol): ancsh_refine_pass_cov's arguments with fitted, ld_fitted behind cover
+    "ancsh_refine_pass_scale": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_long] + [_vp] * 11 + [_c_int, _c_int, _c_int, _vp,
+                                _c_int, _vp, _vp, _vp, _vp],
     # the joint step (no ABI bump, detected by its symbol): nframes, K, kin, ninst, scene, pred_render, norm_factor, params, pass, is_last,
     # pose_in, ld_in, sums, sums_ld, pose_out, best, state, obj, xi, stream
     "ancsh_refine_joint_step": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int] + [_vp] * 6,

@@ -17,6 +17,8 @@
 // The coverage term, two more entries: ancsh_coverage_field (ONE launch behind the renderer in every pass: the field kernel on the predicted
 // pair, per crop pixel and part the offset to the nearest pixel PREDICTED for the part) and ancsh_refine_pass_cov (the pass kernel's COV
 // instance: an observed pixel of the part that the prediction leaves bare adds one row that pulls the nearest predicted pixel over it).
+// The scale unknown, one more entry: ancsh_refine_pass_scale (the pass kernel's SCALE instance: the coverage instance plus one column -- every
+// row also adds its derivative by a relative change sigma of the part's size about its centre, thread 0 solves 7 x 7 and s moves with R and t).
 // float64 arithmetic evaluated as written (the library is built with -ffp-contract=off).
 #include "compare_common.h"
 
@@ -27,6 +29,7 @@ constexpr int RF_RENDER = ANCSH_RENDER_WIDTH, RF_BEST = ANCSH_REFINE_WIDTH / 2, 
 constexpr int RF_ACC = 30;                                              // A (21) | b (6) | sum r^2 | n_used | n_obs: what the block adds up
 constexpr int RF_SIL_ACC = 33, RF_SIL_SUMS = ANCSH_REFINE_SIL_SUMS;     // ... | sum m^2 | n_sil | n_far: with the silhouette term
 constexpr int RF_COV_ACC = 36, RF_COV_SUMS = ANCSH_REFINE_COV_SUMS;     // ... | sum m_c^2 | n_cov | n_cfar: with the coverage term as well
+constexpr int RF_SCALE_ACC = 44, RF_SCALE_SUMS = ANCSH_REFINE_SCALE_SUMS;     // ... | A_0s .. A_5s | A_ss | b_s: with the scale unknown as well
 constexpr int SF_THREADS = 256, SF_BAND = 16, SF_CHUNK = 256, SF_SPLIT = 8, SF_STEP = 8, SF_ILP = 8, SF_NONE = 0x7fffffff, SF_SENTINEL = -32768;
 
 __device__ __forceinline__ double rf_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -120,10 +123,110 @@ __device__ __forceinline__ bool rf_solve_update(const double *S, const double *_
     return true;
 }
 
+// the scale instance's step: rf_pose_step with a seventh value sigma = xi[6], x' = c + (1 + sigma) dR (x - c) + d
+__device__ __forceinline__ void rf_pose_step_scale(const double *xi, const double *__restrict__ pose, const double *c, double *out) {
+    const double hx = xi[0] / 2.0, hy = xi[1] / 2.0, hz = xi[2] / 2.0;
+    const double qn = sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
+    const double w = 1.0 / qn, x = hx / qn, yq = hy / qn, z = hz / qn;
+    double dR[9];
+    dR[0] = 1.0 - 2.0 * (yq * yq + z * z);
+    dR[1] = 2.0 * (x * yq - w * z);
+    dR[2] = 2.0 * (x * z + w * yq);
+    dR[3] = 2.0 * (x * yq + w * z);
+    dR[4] = 1.0 - 2.0 * (x * x + z * z);
+    dR[5] = 2.0 * (yq * z - w * x);
+    dR[6] = 2.0 * (x * z - w * yq);
+    dR[7] = 2.0 * (yq * z + w * x);
+    dR[8] = 1.0 - 2.0 * (x * x + yq * yq);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[3 * a + k] = (dR[3 * a] * pose[k] + dR[3 * a + 1] * pose[3 + k]) + dR[3 * a + 2] * pose[6 + k];
+    const double grow = 1.0 + xi[6];
+    out[9] = pose[9] * grow;
+    const double u[3] = {pose[10] - c[0], pose[11] - c[1], pose[12] - c[2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[10 + a] = (grow * rf_dot(dR + 3 * a, u) + c[a]) + xi[3 + a];
+}
+
+// the 7 x 7 solve of the scale instance in rf_solve_update's order: rows 0..5 as there, row 6 the scale row (S[36..41] = A_0s .. A_5s, S[42] =
+// A_ss, S[43] = b_s); the clamp with max_step beside the two others, then sigma alone held to s0's band.  false (out untouched): it failed
+__device__ __forceinline__ bool rf_solve_update_scale(const double *S, const double *__restrict__ pose, const double *c, double damping,
+                                                      double max_angle, double max_dist, double max_step, double max_total, double s0,
+                                                      double *out) {
+    double A[7][7], L[7][7], y[7], xi[7], rhs[7];
+    int at = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = S[at++];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) A[a][6] = A[6][a] = S[RF_COV_ACC + a], rhs[a] = S[21 + a];
+    A[6][6] = S[RF_COV_ACC + 6];
+    rhs[6] = S[RF_COV_ACC + 7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) A[k][k] = A[k][k] + (damping * A[k][k] + 1e-12);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
+            if (i == j) {
+                ok = ok && s > 0.0 && finite(s);
+                L[i][i] = sqrt(s);
+            } else
+                L[i][j] = s / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {                                       // L y = -b
+        double s = 0.0 - rhs[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int i = 6; i >= 0; --i) {                                      // L^T xi = y
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 7; ++k) s = s - L[k][i] * xi[k];
+        xi[i] = s / L[i][i];
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) ok = ok && finite(xi[k]);
+    if (!ok) return false;
+    const double wn = sqrt(rf_dot(xi, xi)), dn = sqrt(rf_dot(xi + 3, xi + 3)), sn = fabs(xi[6]);
+    if (wn > max_angle || dn > max_dist || sn > max_step) {             // one factor for all seven: the smallest of the ratios that apply
+        double f = 1.0;
+        if (wn > max_angle) f = max_angle / wn;
+        if (dn > max_dist && max_dist / dn < f) f = max_dist / dn;
+        if (sn > max_step && max_step / sn < f) f = max_step / sn;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) xi[k] = xi[k] * f;
+    }
+    const double lo = s0 / (1.0 + max_total), hi = s0 * (1.0 + max_total), grown = pose[9] * (1.0 + xi[6]);
+    if (grown > hi) xi[6] = hi / pose[9] - 1.0;                         // sigma alone: the kept s stays in the fitted s's band
+    else if (grown < lo) xi[6] = lo / pose[9] - 1.0;
+    const double kept = pose[9] * (1.0 + xi[6]);
+    if (!(pose[9] > 0.0 && finite(kept) && kept > 0.0)) return false;
+    rf_pose_step_scale(xi, pose, c, out);
+    return true;
+}
+
+// the scale instance's two further kernel arguments, absent from the three other instances' signatures
+__device__ __forceinline__ const double *rf_fitted() { return nullptr; }
+__device__ __forceinline__ const double *rf_fitted(const double *fitted, int) { return fitted; }
+__device__ __forceinline__ int rf_fitted_ld() { return 0; }
+__device__ __forceinline__ int rf_fitted_ld(const double *, int ld) { return ld; }
+
 // TERMS 1: ancsh_refine_pass_sil -- the overhang pixels add their rows (field: ancsh_silhouette_field's words), params holds 16 values and a
 // sums row 36; TERMS 0: ancsh_refine_pass, instruction for instruction what it was before the term existed; TERMS 2: ancsh_refine_pass_cov --
-// the gap pixels add their rows as well (cover: ancsh_coverage_field's words), params holds 32 values and a sums row 40
-template <typename T, int TERMS>
+// the gap pixels add their rows as well (cover: ancsh_coverage_field's words), params holds 32 values and a sums row 40; TERMS 3:
+// ancsh_refine_pass_scale -- every row adds the scale column too, params holds 48 values and a sums row 48, and FIT = (fitted, ld_fitted)
+template <typename T, int TERMS, typename... FIT>
 __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, int K, const float *__restrict__ verts, const int *__restrict__ tris,
                                                                  const int *__restrict__ tri_link, int V, int ntri,
                                                                  const T *__restrict__ obs_depth, const unsigned char *__restrict__ obs_labels,
@@ -134,9 +237,10 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                                                                  const double *__restrict__ params, const int *__restrict__ field,
                                                                  const int *__restrict__ cover, int pass, int is_last,
                                                                  const double *__restrict__ pose_in, int ld_in, double *__restrict__ pose_out,
-                                                                 double *__restrict__ best, double *__restrict__ sums) {
-    constexpr bool SIL = TERMS >= 1, COV = TERMS == 2;
-    constexpr int NACC = COV ? RF_COV_ACC : SIL ? RF_SIL_ACC : RF_ACC, NSUMS = COV ? RF_COV_SUMS : SIL ? RF_SIL_SUMS : RF_SUMS;
+                                                                 double *__restrict__ best, double *__restrict__ sums, FIT... fit) {
+    constexpr bool SIL = TERMS >= 1, COV = TERMS >= 2, SCL = TERMS == 3;
+    constexpr int NACC = SCL ? RF_SCALE_ACC : COV ? RF_COV_ACC : SIL ? RF_SIL_ACC : RF_ACC;
+    constexpr int NSUMS = SCL ? RF_SCALE_SUMS : COV ? RF_COV_SUMS : SIL ? RF_SIL_SUMS : RF_SUMS;
     __shared__ int s_part[RF_LINKS];
     __shared__ double s_red[RF_WAVES][NACC], s_tot[NACC];
     const int j = blockIdx.x, v = blockIdx.y, f = blockIdx.z, tid = threadIdx.x;
@@ -145,7 +249,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     double *po = pose_out + ((size_t)f * K + j) * 26 + 13 * v;
     double *bb = best + (((size_t)f * K + j) * 2 + v) * RF_BEST, *ss = sums + (((size_t)f * K + j) * 2 + v) * NSUMS;
     const double nf = (double)norm_factor[f], qnan = __builtin_nan("");
-    if (!pose_ok(pose) || !finite(nf) || nf == 0.0) {                   // uniform over the block: NaN in the best block, the pose as it came
+    double s0 = 1.0;                                                    // the fitted s of this (frame, part, pose): not finite or not > 0 reads as a NaN pose
+    if constexpr (SCL) s0 = rf_fitted(fit...)[((size_t)f * K + j) * rf_fitted_ld(fit...) + 13 * v + 9];
+    if (!pose_ok(pose) || !finite(nf) || nf == 0.0 || (SCL && !(finite(s0) && s0 > 0.0))) {      // uniform over the block: NaN in the best block, the pose as it came
         if (tid < 13) po[tid] = pose[tid];
         if (tid < RF_BEST) bb[tid] = qnan;
         if (tid < NSUMS) ss[tid] = tid == RF_SUMS - 1 || tid == RF_SIL_SUMS - 1 || tid == RF_COV_SUMS - 1 ? 0.0 : qnan;
@@ -208,6 +314,13 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                     for (int y = x; y < 6; ++y) acc[at++] += J[x] * J[y];
 #pragma unroll
                 for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+                if constexpr (SCL) {
+                    const double Js = wt * rf_dot(g, pc);
+#pragma unroll
+                    for (int x = 0; x < 6; ++x) acc[RF_COV_ACC + x] += J[x] * Js;
+                    acc[RF_COV_ACC + 6] += Js * Js;
+                    acc[RF_COV_ACC + 7] += Js * r;
+                }
                 acc[30] += m * m;
                 acc[31] += 1.0;
                 continue;
@@ -248,6 +361,13 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
                     for (int y = x; y < 6; ++y) acc[at++] += J[x] * J[y];
 #pragma unroll
                 for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+                if constexpr (SCL) {
+                    const double Js = wt * rf_dot(g, pc);
+#pragma unroll
+                    for (int x = 0; x < 6; ++x) acc[RF_COV_ACC + x] += J[x] * Js;
+                    acc[RF_COV_ACC + 6] += Js * Js;
+                    acc[RF_COV_ACC + 7] += Js * r;
+                }
                 acc[33] += m * m;
                 acc[34] += 1.0;
                 continue;
@@ -302,6 +422,13 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
             for (int y = x; y < 6; ++y) acc[at++] += J[x] * J[y];
 #pragma unroll
         for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+        if constexpr (SCL) {                                            // the point moves as c + (1 + sigma)(pp - c): d r / d sigma = n . (pp - c)
+            const double Js = rf_dot(nn, pc);
+#pragma unroll
+            for (int x = 0; x < 6; ++x) acc[RF_COV_ACC + x] += J[x] * Js;
+            acc[RF_COV_ACC + 6] += Js * Js;
+            acc[RF_COV_ACC + 7] += Js * r;
+        }
         acc[27] += r * r;
         acc[28] += 1.0;
     }
@@ -316,7 +443,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     if (tid < NACC) s_tot[tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
     __syncthreads();
     // sum m^2, n_sil, n_far lie behind C and solved, the coverage's three behind [35]
-    if (tid < NACC) ss[tid < RF_ACC ? tid : tid < RF_SIL_ACC ? tid + 2 : tid + 3] = s_tot[tid];
+    if constexpr (SCL) {                                                // ... and the scale column's eight behind [39]
+        if (tid < NACC) ss[tid < RF_ACC ? tid : tid < RF_SIL_ACC ? tid + 2 : tid < RF_COV_ACC ? tid + 3 : tid + 4] = s_tot[tid];
+    } else if (tid < NACC) ss[tid < RF_ACC ? tid : tid < RF_SIL_ACC ? tid + 2 : tid + 3] = s_tot[tid];
     if (tid != 0) return;
     const double n_used = s_tot[28], n_obs = s_tot[29];
     double C, n_rows = n_used;
@@ -343,7 +472,10 @@ __global__ __launch_bounds__(RF_THREADS) void refine_pass_kernel(int nframes, in
     }
     double nw[13];
     bool ok = false;
-    if (!is_last && n_rows >= params[5]) ok = rf_solve_update(s_tot, pose, c, params[3], params[4], max_dist, nw);
+    if (!is_last && n_rows >= params[5]) {
+        if constexpr (SCL) ok = rf_solve_update_scale(s_tot, pose, c, params[3], params[4], max_dist, params[32], params[33], s0, nw);
+        else ok = rf_solve_update(s_tot, pose, c, params[3], params[4], max_dist, nw);
+    }
     ss[31] = ok ? 1.0 : 0.0;
     bb[17] = ok ? solved + 1.0 : solved;
 #pragma unroll
@@ -785,14 +917,14 @@ __global__ __launch_bounds__(JS_THREADS) void refine_joint_step_kernel(int nfram
 using namespace ancsh;
 
 // the three passes' checks and launch: who = the entry's name in its messages; TERMS = 1: with the field, the 16-value table and the 36-value
-// sums; 2: with cover, the 32-value table and the 40-value sums as well
+// sums; 2: with cover, the 32-value table and the 40-value sums as well; 3: with fitted / ld_fitted, the 48-value table and the 48-value sums
 template <int TERMS>
 static int refine_pass_call(const char *who, int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V,
                             int T, const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
                             const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels, const int *geom,
                             const double *scene, const double *pred_render, const float *norm_factor, const double *params, const int *field,
-                            const int *cover, int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums,
-                            void *stream) {
+                            const int *cover, const double *fitted, int ld_fitted, int pass, int is_last, const double *pose_in, int ld_in,
+                            double *pose_out, double *best, double *sums, void *stream) {
     ANCSH_CHECK(batch_ok(who, nframes, K, "exceed the 32767-frame range of ancsh_reproject_scene_build"));
     size_t item;
     ANCSH_CHECK(depth_item(who, depth_type, item));
@@ -801,15 +933,27 @@ static int refine_pass_call(const char *who, int nframes, int K, int depth_type,
     ANCSH_REQUIRE(V >= 0 && V < (1 << 24), "%s: V=%d vertices must be in [0, 2^24)", who, V);
     ANCSH_CHECK(pass_ok(who, pass, is_last));
     ANCSH_CHECK(record_ld_ok(who, "ld_in", ld_in));
+    if (TERMS == 3) ANCSH_CHECK(record_ld_ok(who, "ld_fitted", ld_fitted));
     ANCSH_REQUIRE(verts && tris && tri_link && obs_depth && obs_labels && pred_zbuf && pred_depth && pred_labels && geom && scene &&
-                      pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || TERMS < 1) && (cover || TERMS < 2),
-                  "%s: null pointer", who);
+                      pred_render && norm_factor && params && pose_in && pose_out && best && sums && (field || TERMS < 1) && (cover || TERMS < 2) &&
+                      (fitted || TERMS < 3), "%s: null pointer", who);
     ANCSH_REQUIRE(depth_aligned(item, obs_depth, pred_depth) && all_aligned<4>(verts, tris, tri_link, geom, norm_factor, field, cover) &&
-                      all_aligned<8>(pred_zbuf, scene, pred_render, params, pose_in, pose_out, best, sums), ANCSH_ALIGNED, who);
+                      all_aligned<8>(pred_zbuf, scene, pred_render, params, pose_in, pose_out, best, sums, fitted), ANCSH_ALIGNED, who);
     ANCSH_REQUIRE(pose_in != pose_out, "%s: pose_in and pose_out overlap (a workgroup reads its pose while another writes: two buffers)", who);
     if (nframes == 0) return ANCSH_OK;
     const dim3 grid(K, 2, nframes);
-    if (depth_type == ANCSH_DEPTH_U16)
+    if constexpr (TERMS == 3) {
+        if (depth_type == ANCSH_DEPTH_U16)
+            hipLaunchKernelGGL((refine_pass_kernel<unsigned short, TERMS, const double *, int>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream,
+                               nframes, K, verts, tris, tri_link, V, T, (const unsigned short *)obs_depth, obs_labels, pixel_capacity, pred_zbuf,
+                               (const unsigned short *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass,
+                               is_last, pose_in, ld_in, pose_out, best, sums, fitted, ld_fitted);
+        else
+            hipLaunchKernelGGL((refine_pass_kernel<float, TERMS, const double *, int>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K,
+                               verts, tris, tri_link, V, T, (const float *)obs_depth, obs_labels, pixel_capacity, pred_zbuf,
+                               (const float *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass, is_last,
+                               pose_in, ld_in, pose_out, best, sums, fitted, ld_fitted);
+    } else if (depth_type == ANCSH_DEPTH_U16)
         hipLaunchKernelGGL((refine_pass_kernel<unsigned short, TERMS>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, nframes, K, verts, tris,
                            tri_link, V, T, (const unsigned short *)obs_depth, obs_labels, pixel_capacity, pred_zbuf,
                            (const unsigned short *)pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass,
@@ -827,8 +971,8 @@ extern "C" int ancsh_refine_pass(int nframes, int K, int depth_type, const float
                                  const double *scene, const double *pred_render, const float *norm_factor, const double *params, int pass,
                                  int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream) {
     return refine_pass_call<0>("refine_pass", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
-                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, nullptr, nullptr, pass, is_last,
-                               pose_in, ld_in, pose_out, best, sums, stream);
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, nullptr, nullptr, nullptr, 0, pass,
+                               is_last, pose_in, ld_in, pose_out, best, sums, stream);
 }
 
 extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
@@ -838,8 +982,8 @@ extern "C" int ancsh_refine_pass_sil(int nframes, int K, int depth_type, const f
                                      const double *params, const int *field, int pass, int is_last, const double *pose_in, int ld_in,
                                      double *pose_out, double *best, double *sums, void *stream) {
     return refine_pass_call<1>("refine_pass_sil", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
-                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, nullptr, pass, is_last,
-                               pose_in, ld_in, pose_out, best, sums, stream);
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, nullptr, nullptr, 0, pass,
+                               is_last, pose_in, ld_in, pose_out, best, sums, stream);
 }
 
 extern "C" int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
@@ -849,8 +993,20 @@ extern "C" int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const f
                                      const double *params, const int *field, const int *cover, int pass, int is_last, const double *pose_in,
                                      int ld_in, double *pose_out, double *best, double *sums, void *stream) {
     return refine_pass_call<2>("refine_pass_cov", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
-                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, pass, is_last,
-                               pose_in, ld_in, pose_out, best, sums, stream);
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, nullptr, 0, pass,
+                               is_last, pose_in, ld_in, pose_out, best, sums, stream);
+}
+
+extern "C" int ancsh_refine_pass_scale(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                                       const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity,
+                                       const unsigned long long *pred_zbuf, const void *pred_depth, const unsigned char *pred_labels,
+                                       const int *geom, const double *scene, const double *pred_render, const float *norm_factor,
+                                       const double *params, const int *field, const int *cover, const double *fitted, int ld_fitted, int pass,
+                                       int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums,
+                                       void *stream) {
+    return refine_pass_call<3>("refine_pass_scale", nframes, K, depth_type, verts, tris, tri_link, V, T, obs_depth, obs_labels, pixel_capacity,
+                               pred_zbuf, pred_depth, pred_labels, geom, scene, pred_render, norm_factor, params, field, cover, fitted, ld_fitted,
+                               pass, is_last, pose_in, ld_in, pose_out, best, sums, stream);
 }
 
 extern "C" int ancsh_refine_joint_step(int nframes, int K, const double *kin, int ninst, const double *scene, const double *pred_render,

@@ -1120,11 +1120,13 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
     these columns behind it is the (n, K, 26) record of the refined poses.  debug=True: (columns, sums (iters + 1, n, K, 2, 32)), what every
     pass added up.  A table of pack_refine(silhouette=...) runs the loop with the silhouette term (ancsh_silhouette_field once, then
     ancsh_refine_pass_sil): the debug sums are then (iters + 1, n, K, 2, 36); with coverage= as well (ancsh_coverage_field behind the renderer
-    in every pass, ancsh_refine_pass_cov) they are (iters + 1, n, K, 2, 40).  A table of pack_refine(joints=...) needs kinematics = the
+    in every pass, ancsh_refine_pass_cov) they are (iters + 1, n, K, 2, 40); with scale= as well (ancsh_refine_pass_scale in that entry's
+    place: s is solved with R and t) they are (iters + 1, n, K, 2, 48) and column s of the result is the refined scale.  A table of pack_refine(joints=...) needs kinematics = the
     object's pack_kinematics table (a library: the stack of its instances'): ancsh_refine_joint_step runs behind every pass, the best-of is
     kept per object, and debug=True returns (columns, sums, obj (iters + 1, n, 2, 8)): every pass's object rows,
     pose.refinement.OBJ_COLUMNS.  A pipeline built with refine= streams the same bytes.  One host sync; the pipeline has none."""
-    from .pose.refinement import REFINE_WIDTH, check_refine_table, has_coverage, has_joints, has_silhouette, refine_batch, refine_buffers
+    from .pose.refinement import REFINE_WIDTH, check_refine_table, has_coverage, has_joints, has_scale, has_silhouette, refine_batch, \
+        refine_buffers
     table = check_refine_table(refine)
     iters = int(table[0])
     if has_joints(table) and kinematics is None:
@@ -1139,7 +1141,7 @@ def refine_frames(mesh, render_tables, scenes, rigs, norm_factors, record, frame
             raise ValueError("kinematics and mesh must hold the same instances (a library: the np.stack of its instances' tables)")
     t = lambda a: torch.from_numpy(a).to(dev)
     buffers = refine_buffers(n, K, dev, passes=iters + 1 if debug else 1, silhouette=has_silhouette(table), joints=kin is not None,
-                             pixel_capacity=F.total, coverage=has_coverage(table))
+                             pixel_capacity=F.total, coverage=has_coverage(table), scale=has_scale(table))
     wide = refine_batch(d_mesh, *F.tensors, F.name, F.tables, F.pred, t(table), iters, buffers, kin=None if kin is None else t(kin))
     columns = wide[:, :, rec.shape[2]:].cpu().numpy()
     assert columns.shape == (n, K, REFINE_WIDTH)

@@ -173,7 +173,7 @@ class _Slot(object):
         if opts.refine:
             from .pose.refinement import refine_buffers
             self.refine_bufs = refine_buffers(B, K, device, silhouette=opts.silhouette, joints=opts.refine_joints, pixel_capacity=cap,
-                                              coverage=opts.refine_coverage)
+                                              coverage=opts.refine_coverage, scale=opts.refine_scale)
         # the streamed outputs, in the order submit copies them out: the record first, right behind the replay.  record and
         # articulation live in the graph's pool (sl.out / sl.out32), the others in slot-owned buffers; the flag words, the depth
         # front end's valid-pixel counts and the annotated frames' valid pixels per link are not refit.
@@ -380,6 +380,8 @@ class AncshPipeline(object):
         A table of pack_refine(silhouette=..., coverage=...) adds the coverage term: ancsh_coverage_field behind the renderer in every pass
         and ancsh_refine_pass_cov, 6 (iters + 1) + 2 launches (7 (iters + 1) + 2 with the joint step) and 8 bytes more per pixel of
         depth_capacity, part and slot; a part is pulled over observed pixels it leaves bare.  The record's columns are unchanged.
+        A table of pack_refine(silhouette=..., coverage=..., scale=...) solves s with R and t: ancsh_refine_pass_scale in
+        ancsh_refine_pass_cov's place, the same launches, sums of 48 values; column s of the refinement block is then the refined scale.
         out["record_refined"]: the refinement block (pose.refinement.COLUMN_NAMES: per pose the refined [R | s | t], cost_start, cost_best,
         n_used, best_pass, passes_solved) behind the record so far; pose.refinement.refined_record(record, layout=pipe.record_layout) gives the
         (.., 26) record of the refined poses.  The slot holds two (B, K, 26) working records, the (B, K, 2, 18) best block and the

@@ -11,7 +11,10 @@ table is at hand: then ancsh_refine_joint_step runs behind every pass, solves th
 revolute and prismatic joint's two sides on one axis, and keeps the best-of per object.  The silhouette term is one-sided: an observed pixel
 of the part that the prediction leaves bare is only charged.  A table of pack_refine(silhouette=..., coverage=...) adds the other side:
 ancsh_coverage_field finds, behind the renderer in every pass, every crop pixel's nearest PREDICTED pixel of each part, and
-ancsh_refine_pass_cov adds one row per bare observed pixel that pulls that predicted pixel over it."""
+ancsh_refine_pass_cov adds one row per bare observed pixel that pulls that predicted pixel over it.  With both pixel terms on, a table of
+pack_refine(..., scale=...) stops carrying s: the overhang and the gap rows are the two that observe size, ancsh_refine_pass_scale adds every
+row's derivative by a relative change of the part's size about its centre, solves 7 x 7 and moves s with R and t, clamped per step and held
+to a band about the fitted s."""
 from collections import namedtuple
 
 import numpy as np
@@ -25,6 +28,7 @@ REFINE_SUMS, REFINE_PARAMS, MAX_ITERS = 32, 8, 8      # ANCSH_REFINE_SUMS, ANCSH
 REFINE_SIL_SUMS, REFINE_SIL_PARAMS = 36, 16               # ANCSH_REFINE_SIL_SUMS, ANCSH_REFINE_SIL_PARAMS: with the silhouette term
 REFINE_JOINT_PARAMS, REFINE_OBJ, JOINT_XI = 24, 8, 48       # ANCSH_REFINE_JOINT_PARAMS, ANCSH_REFINE_OBJ; the debug step's 6 * 8 values: the joint step
 REFINE_COV_SUMS, REFINE_COV_PARAMS = 40, 32               # ANCSH_REFINE_COV_SUMS, ANCSH_REFINE_COV_PARAMS: with the coverage term as well
+REFINE_SCALE_SUMS, REFINE_SCALE_PARAMS = 48, 48           # ANCSH_REFINE_SCALE_SUMS, ANCSH_REFINE_SCALE_PARAMS: with the scale unknown as well
 OBJ_COLUMNS = ("cost_start", "cost_best", "best_pass", "passes_solved", "cost", "joints", "solved", "gap_rms")      # an obj row, per (frame, pose)
 FIELD_SENTINEL = -32768                                   # both halves of a field word: the part has no observed pixel in the frame
 BEST_WIDTH = REFINE_WIDTH // 2
@@ -35,8 +39,9 @@ COLUMN_NAMES = tuple("baseline_" + c for c in POSE_COLUMNS) + tuple("nonlinear_"
 SUMS_COLUMNS = dict(A=slice(0, 21), b=slice(21, 27), rr=27, n_used=28, n_obs=29, cost=30, solved=31)
 SIL_SUMS_COLUMNS = dict(SUMS_COLUMNS, mm=32, n_sil=33, n_far=34)
 COV_SUMS_COLUMNS = dict(SIL_SUMS_COLUMNS, mm_c=36, n_cov=37, n_cfar=38)
+SCALE_SUMS_COLUMNS = dict(COV_SUMS_COLUMNS, A_s=slice(40, 47), b_s=47)
 PARAMS_LENGTHS = {"ancsh_refine_pass": (REFINE_PARAMS, REFINE_JOINT_PARAMS), "ancsh_refine_pass_sil": (REFINE_SIL_PARAMS, REFINE_JOINT_PARAMS),
-                  "ancsh_refine_pass_cov": (REFINE_COV_PARAMS,),
+                  "ancsh_refine_pass_cov": (REFINE_COV_PARAMS,), "ancsh_refine_pass_scale": (REFINE_SCALE_PARAMS,),
                   "ancsh_refine_joint_step": (REFINE_JOINT_PARAMS, REFINE_COV_PARAMS)}      # the params table per entry: a longer one holds the shorter ones in front
 RefineBuffers = namedtuple("RefineBuffers", "work best sums field state obj xi cover")      # refine_buffers' record; None = a term that is off
 BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=True, render_mesh=<depth.pack_mesh(...)>"
@@ -44,15 +49,25 @@ BUILT_WITH = "depth_capacity=<pixels>, point_ground_truth=True, build_point_gt=T
 
 def check_refine_table(table):
     """-> table as a fresh (REFINE_PARAMS,) float64 array, (REFINE_SIL_PARAMS,) with the silhouette term or (REFINE_JOINT_PARAMS,) with the
-    joint step or (REFINE_COV_PARAMS,) with the coverage term (has_silhouette, has_joints, has_coverage); ValueError unless it is one
-    pack_refine makes."""
+    joint step or (REFINE_COV_PARAMS,) with the coverage term or (REFINE_SCALE_PARAMS,) with the scale unknown (has_silhouette, has_joints,
+    has_coverage, has_scale); ValueError unless it is one pack_refine makes."""
     try:
         t = np.array(table, np.float64)
     except (TypeError, ValueError):
         t = np.zeros(0)
-    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,), (REFINE_JOINT_PARAMS,), (REFINE_COV_PARAMS,)):
+    if t.shape not in ((REFINE_PARAMS,), (REFINE_SIL_PARAMS,), (REFINE_JOINT_PARAMS,), (REFINE_COV_PARAMS,), (REFINE_SCALE_PARAMS,)):
         raise ValueError("refine: one (%d,) float64 table (pose.refinement.pack_refine), or (%d,) with silhouette=, got shape %s"
                          % (REFINE_PARAMS, REFINE_SIL_PARAMS, t.shape))
+    if t.shape[0] == REFINE_SCALE_PARAMS:
+        check_refine_table(_scale_front(t))                              # the coverage table in front, by its own rules and messages
+        max_step, max_total = t[32:34].tolist()
+        if not (np.isfinite(max_step) and 0.0 < max_step <= 0.5):
+            raise ValueError("refine: scale max_step must be finite and in (0, 0.5], got %r" % max_step)
+        if not (np.isfinite(max_total) and max_step <= max_total <= 1.0):
+            raise ValueError("refine: scale max_total must be finite, >= max_step and <= 1, got %r" % max_total)
+        if (t[34:] != 0).any():
+            raise ValueError("refine: the reserved values 34..47 must be 0")
+        return t
     iters, max_dist, min_cos, damping, max_angle, min_pixels = t[:6].tolist()
     if not (iters == int(iters) if np.isfinite(iters) else False) or not 1 <= iters <= MAX_ITERS:
         raise ValueError("refine: iters must be an integer in [1, %d], got %r" % (MAX_ITERS, iters))
@@ -101,6 +116,20 @@ def check_refine_table(table):
     return t
 
 
+SCALE_NEEDS = "refine: scale needs the silhouette and coverage terms (their rows are what observes size)"
+SCALE_JOINTS = ("refine: scale with joints is not built: scaling an object's parts separately opens its joints, and the joint step's 6 K system "
+                "has no scale unknown yet (pass scale= or joints=, not both)")
+
+
+def _scale_front(t):
+    """The first 32 values of a 48-value table, after the two rules that are the scale unknown's own."""
+    if not (t[8:REFINE_SIL_PARAMS] != 0).any() or not (t[REFINE_JOINT_PARAMS:REFINE_COV_PARAMS] != 0).any():
+        raise ValueError(SCALE_NEEDS)
+    if (t[REFINE_SIL_PARAMS:REFINE_JOINT_PARAMS] != 0).any():
+        raise ValueError(SCALE_JOINTS)
+    return t[:REFINE_COV_PARAMS]
+
+
 def has_silhouette(table):
     """A checked table: the silhouette term is on iff it holds at least REFINE_SIL_PARAMS values and value 8 (its weight) is > 0."""
     return table is not None and table.shape[0] >= REFINE_SIL_PARAMS and bool(table[8] > 0)
@@ -108,17 +137,22 @@ def has_silhouette(table):
 
 def has_joints(table):
     """A checked table: the joint step is on iff it is the (REFINE_JOINT_PARAMS,) one, or the (REFINE_COV_PARAMS,) one with value 16 (the
-    joints' weight) > 0."""
+    joints' weight) > 0; never with the (REFINE_SCALE_PARAMS,) one."""
     return table is not None and (table.shape[0] == REFINE_JOINT_PARAMS or (table.shape[0] == REFINE_COV_PARAMS and bool(table[16] > 0)))
 
 
 def has_coverage(table):
-    """A checked table: the coverage term is on iff it is the (REFINE_COV_PARAMS,) one."""
-    return table is not None and table.shape[0] == REFINE_COV_PARAMS
+    """A checked table: the coverage term is on iff it holds at least REFINE_COV_PARAMS values and value 24 (its weight) is > 0."""
+    return table is not None and table.shape[0] >= REFINE_COV_PARAMS and bool(table[24] > 0)
+
+
+def has_scale(table):
+    """A checked table: the scale unknown is on iff it is the (REFINE_SCALE_PARAMS,) one."""
+    return table is not None and table.shape[0] == REFINE_SCALE_PARAMS
 
 
 def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=10.0, min_pixels=32, silhouette=None, joints=None,
-                coverage=None):
+                coverage=None, scale=None):
     """The parameter table ancsh_refine_pass reads, (REFINE_PARAMS,) float64: iters Gauss-Newton passes (1..8; one more pass evaluates the
     last pose); max_dist: a pixel pair further apart than this counts as missed, and a step's translation is clamped to it; min_cos: pixels
     seen at a flatter angle are left out; damping: relative Levenberg damping of the diagonal; max_angle_deg: the clamp of a step's
@@ -138,7 +172,29 @@ def pack_refine(iters=3, max_dist=0.1, min_cos=0.1, damping=1e-3, max_angle_deg=
     table: values 0..15 as above, 16..23 the joint step's (all 0 without joints=), 24 weight, 25 dist, 26 slack, 27..31 reserved.  An observed
     pixel of the part that the prediction leaves bare pulls the nearest predicted pixel of the part over it -- the silhouette term's other
     side, with the same three values' meaning; min_pixels counts these rows too.  Nobody has tuned these defaults either.
+    scale = dict(max_step=0.05, max_total=0.25), or (max_step, max_total), with silhouette= and coverage= and without joints=: the scale
+    unknown (ancsh_refine_pass_scale), a (REFINE_SCALE_PARAMS,) table: values 0..31 as above, 32 max_step, 33 max_total, 34..47 reserved.  s
+    is solved with R and t: a step changes it by at most the factor 1 +- max_step (in (0, 0.5]), and the kept s stays within [s_0 / (1 +
+    max_total), s_0 (1 + max_total)] of the fitted s_0 (max_step <= max_total <= 1).  The overhang and the gap rows are what observes size;
+    depth rows alone cannot tell scale from depth along the ray.  These, too, are starting values nobody has tuned.
     ValueError: check_refine_table's."""
+    if scale is not None:
+        if silhouette is None or coverage is None:
+            raise ValueError(SCALE_NEEDS)
+        if joints is not None:
+            raise ValueError(SCALE_JOINTS)
+        if isinstance(scale, dict) and set(scale) - {"max_step", "max_total"}:
+            raise ValueError("refine: scale takes max_step and max_total, got %s" % sorted(scale))
+        try:
+            if isinstance(scale, dict):
+                sc = [float(scale.get("max_step", 0.05)), float(scale.get("max_total", 0.25))]
+            else:
+                max_step, max_total = scale
+                sc = [float(max_step), float(max_total)]
+        except (TypeError, ValueError):
+            raise ValueError("refine: scale is dict(max_step=, max_total=) or (max_step, max_total), of numbers")
+        front = pack_refine(iters, max_dist, min_cos, damping, max_angle_deg, min_pixels, silhouette=silhouette, coverage=coverage).tolist()
+        return check_refine_table(front + sc + [0.0] * (REFINE_SCALE_PARAMS - REFINE_COV_PARAMS - len(sc)))
     if coverage is not None:
         if silhouette is None:
             raise ValueError("refine: coverage needs the silhouette term (its rows are the other side of the overhang rows): pass silhouette= as well")
@@ -233,18 +289,20 @@ def _params(entry, params):
                          % (" or ".join(str(n) for n in PARAMS_LENGTHS[entry]), entry))
 
 
-def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False, pixel_capacity=None, coverage=False):
+def refine_buffers(B, K, device, passes=1, silhouette=False, joints=False, pixel_capacity=None, coverage=False, scale=False):
     """What a slot owns for the loop, a RefineBuffers record: work = two (B, K, 26) pose buffers, best (B, K, 2, 18), sums (passes, B, K, 2,
-    32 -- 36 with the silhouette term, 40 with the coverage term), float64; silhouette=True: field = field_buffer's planes of pixel_capacity
+    32 -- 36 with the silhouette term, 40 with the coverage term, 48 with scale=True, which needs coverage=True), float64; silhouette=True: field = field_buffer's planes of pixel_capacity
     pixels; joints=True: state (B, K, 2, 18), obj (passes, B, 2, 8) and the debug output xi (passes, B, 2, 48) -- None with one pass;
     coverage=True (with silhouette=True): cover = field_buffer's planes of 2 * pixel_capacity pixels."""
     if silhouette and pixel_capacity is None:
         raise ValueError("refine_buffers(silhouette=True) allocates the field with the rest: it needs pixel_capacity")
     if coverage and not silhouette:
         raise ValueError("refine_buffers(coverage=True) needs silhouette=True: the coverage term runs with the silhouette term")
+    if scale and not coverage:
+        raise ValueError("refine_buffers(scale=True) needs coverage=True: the scale unknown runs with both pixel terms")
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)
     return RefineBuffers(work=(z(B, K, 26), z(B, K, 26)), best=z(B, K, 2, BEST_WIDTH),
-                         sums=z(passes, B, K, 2, REFINE_COV_SUMS if coverage else REFINE_SIL_SUMS if silhouette else REFINE_SUMS),
+                         sums=z(passes, B, K, 2, REFINE_SCALE_SUMS if scale else REFINE_COV_SUMS if coverage else REFINE_SIL_SUMS if silhouette else REFINE_SUMS),
                          field=field_buffer(K, pixel_capacity, device) if silhouette else None, state=z(B, K, 2, BEST_WIDTH) if joints else None,
                          obj=z(passes, B, 2, REFINE_OBJ) if joints else None, xi=z(passes, B, 2, JOINT_XI) if joints and passes > 1 else None,
                          cover=field_buffer(K, 2 * int(pixel_capacity), device) if coverage else None)
@@ -303,13 +361,15 @@ def coverage_field(pred, geom_out, scene, K, out=None):
 
 
 def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, norm_factor, params, pass_index, is_last, pose_in, pose_out,
-                best, sums, field=None, cover=None):
+                best, sums, field=None, cover=None, fitted=None):
     """ancsh_refine_pass on device tensors (no host sync, no allocation): mesh = depth.mesh_to_device's; the observed pair (pixel_capacity,);
     pred = pose.reprojection.predicted_buffers' triple as the renderer left it for pred_render (2B, 208), the tables of pose_in (B, K, >= 26);
     params = pack_refine's table on the device.  Writes pose_out (B, K, 26), best (B, K, 2, 18) and sums (B, K, 2, 32); -> pose_out.
     field = silhouette_field's (K, pixel_capacity) planes: ancsh_refine_pass_sil, with a (16,) table and sums (B, K, 2, 36).
     cover = coverage_field's (K, 2 * pixel_capacity) planes of this pass's prediction, with field: ancsh_refine_pass_cov, with a (32,) table
-    and sums (B, K, 2, 40)."""
+    and sums (B, K, 2, 40).
+    fitted = the record the loop started from (B, K, >= 26), with field and cover: ancsh_refine_pass_scale, with a (48,) table and sums (B, K,
+    2, 48); a (48,) table needs it."""
     from ..depth import RENDER_WIDTH, _byte_plane, _check_device_mesh, _depth_plane, _pixel_pair, _scratch_size
     _lib.require_device(pose_in)
     verts, tris, tri_link, V, T = _check_device_mesh(mesh)[:5]
@@ -321,24 +381,33 @@ def refine_pass(mesh, obs_depth, obs_labels, pred, geom, scene, pred_render, nor
     B = _tables(None, scene, None, norm_factor, pose_in, geom, K, name="pose_in")
     ld = int(pose_in.shape[2])
     _f64("pred_render", pred_render, (2 * B, RENDER_WIDTH))
-    sil, cov = field is not None, cover is not None
+    sil, cov, scl = field is not None, cover is not None, fitted is not None
     if cov and not sil:
         raise ValueError("cover goes with field: the coverage term runs with the silhouette term")
-    _params("ancsh_refine_pass_cov" if cov else "ancsh_refine_pass_sil" if sil else "ancsh_refine_pass", params)
+    if scl and not cov:
+        raise ValueError("fitted goes with field and cover: the scale unknown runs with both pixel terms")
+    if not scl and params.dim() == 1 and int(params.shape[0]) == REFINE_SCALE_PARAMS:
+        raise ValueError("a (%d,) table solves s as well: it needs fitted, the record the loop started from" % REFINE_SCALE_PARAMS)
+    if scl and (fitted.dtype != torch.float64 or fitted.dim() != 3 or tuple(fitted.shape[:2]) != (B, K) or fitted.shape[2] < 26 or
+                not fitted.is_contiguous()):
+        raise ValueError("fitted must be a contiguous (%d, %d, >= 26) float64 tensor" % (B, K))
+    _params("ancsh_refine_pass_scale" if scl else "ancsh_refine_pass_cov" if cov else "ancsh_refine_pass_sil" if sil else "ancsh_refine_pass", params)
     _f64("pose_out", pose_out, (B, K, 26))
     _f64("best", best, (B, K, 2, BEST_WIDTH))
-    _f64("sums", sums, (B, K, 2, REFINE_COV_SUMS if cov else REFINE_SIL_SUMS if sil else REFINE_SUMS))
+    _f64("sums", sums, (B, K, 2, REFINE_SCALE_SUMS if scl else REFINE_COV_SUMS if cov else REFINE_SIL_SUMS if sil else REFINE_SUMS))
     if sil and (field.dtype != torch.int32 or tuple(field.shape) != (K, cap) or not field.is_contiguous()):
         raise ValueError("field must be a contiguous (%d, %d) int32 tensor" % (K, cap))
     if cov and (cover.dtype != torch.int32 or tuple(cover.shape) != (K, 2 * cap) or not cover.is_contiguous()):
         raise ValueError("cover must be a contiguous (%d, %d) int32 tensor" % (K, 2 * cap))
     _lib.require_cuda(obs_depth, obs_labels, pred[0], pred[1], pred[2], geom, scene, pred_render, norm_factor, params, pose_out, best, sums, field,
-                      cover)
+                      cover, fitted)
     head = (B, K, kind, _lib.ptr(verts), _lib.ptr(tris), _lib.ptr(tri_link), int(V), int(T), _lib.ptr(obs_depth), _lib.ptr(obs_labels), cap,
             _lib.ptr(pred[2]), _lib.ptr(pred[0]), _lib.ptr(pred[1]), _lib.ptr(geom), _lib.ptr(scene), _lib.ptr(pred_render), _lib.ptr(norm_factor),
             _lib.ptr(params))
     tail = (int(pass_index), int(bool(is_last)), _lib.ptr(pose_in), ld, _lib.ptr(pose_out), _lib.ptr(best), _lib.ptr(sums))
-    if cov:
+    if scl:
+        _lib.call("ancsh_refine_pass_scale", *head, _lib.ptr(field), _lib.ptr(cover), _lib.ptr(fitted), int(fitted.shape[2]), *tail)
+    elif cov:
         _lib.call("ancsh_refine_pass_cov", *head, _lib.ptr(field), _lib.ptr(cover), *tail)
     elif sil:
         _lib.call("ancsh_refine_pass_sil", *head, _lib.ptr(field), *tail)
@@ -404,11 +473,14 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
     (24,) table and refine_buffers(joints=True): ancsh_refine_joint_step behind every pass -- 6 (iters + 1) + 1 launches (+ 1 with the field);
     obj and xi of `passes` > 1 rows keep every pass's (one device copy carries the object's row on).  refine_buffers(coverage=True), with
     a (32,) table: ancsh_coverage_field behind the renderer and ancsh_refine_pass_cov in every pass -- 6 (iters + 1) + 2 launches, 7 (iters +
-    1) + 2 with the joint step.  -> (B, K, ld + 36) float64."""
+    1) + 2 with the joint step.  A (48,) table with refine_buffers(scale=True): ancsh_refine_pass_scale in ancsh_refine_pass_cov's place,
+    given `carried` as the fitted record -- the coverage loop's 6 (iters + 1) + 2 launches.  -> (B, K, ld + 36) float64."""
     from ..depth import render_depth
     from .reprojection import reproject_scene_build
     work, best, sums, field, state, obj, xi, cover = buffers
-    joints = kin is not None
+    joints, scale = kin is not None, int(params.shape[0]) == REFINE_SCALE_PARAMS
+    if scale != (int(sums.shape[-1]) == REFINE_SCALE_SUMS):
+        raise ValueError("the scale unknown takes both a (%d,) table and refine_buffers(scale=True)" % REFINE_SCALE_PARAMS)
     if joints != (state is not None):
         raise ValueError("the joint step takes both kin and refine_buffers(joints=True)")
     cap = int(obs[0].shape[0])
@@ -422,7 +494,7 @@ def refine_batch(mesh, render, scene, rig, norm_factor, geom, obs, carried, dept
             coverage_field(pred, tables[1], scene, int(carried.shape[1]), out=cover)
         dst = work[p % 2]
         refine_pass(mesh, obs[0], obs[1], pred, geom, scene, tables[0], norm_factor, params, p, p == iters, src, dst, best,
-                    sums[p if sums.shape[0] > 1 else 0], field=field, cover=cover)
+                    sums[p if sums.shape[0] > 1 else 0], field=field, cover=cover, fitted=carried if scale else None)
         if joints:
             if p and obj.shape[0] > 1:
                 obj[p].copy_(obj[p - 1])

@@ -299,7 +299,7 @@ def check_joint_source(joint_source):
 
 class Options(collections.namedtuple("Options", "raw_capacity depth_capacity depth_dtype keyed predicted range_guard articulation joint_states "
                                      "fit_quality ground_truth point_ground_truth build_point_gt build_gt_pose dense label_images annotated_images link_counts render posed sensor reprojection "
-                                     "coord_regress_loss record_width record_key joint_values art_width rows inputs refine_coverage refine_joints silhouette refine")):
+                                     "coord_regress_loss record_width record_key joint_values art_width rows inputs refine_scale refine_coverage refine_joints silhouette refine")):
     __slots__ = ()
 
     @property
@@ -342,6 +342,9 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
         solved together through their joints, one more launch per pass.
         A table of pack_refine(silhouette=..., coverage=...) turns the coverage term on (Options.refine_coverage): one more launch per pass
         (ancsh_coverage_field) and 8 bytes per pixel and part; with joint values it needs kinematics like a pack_refine(joints=...) table.
+        A table of pack_refine(silhouette=..., coverage=..., scale=...) turns the scale unknown on (Options.refine_scale): the loop solves
+        s with R and t (ancsh_refine_pass_scale in ancsh_refine_pass_cov's place, no further launch), and column s of the refinement block
+        is the refined scale.  It is refused together with joint values in the table.
     joint_values (with kinematics and articulation): the step's last launch (ancsh_joint_values_rec) reads the joint values q off the record's
         and, with refine, the kept refined part poses; its 24 columns (pose.joint_values.COLUMN_NAMES) ride behind the articulation block
         (Options.art_width), as the joint states do: no new name in the result tuple or the record."""
@@ -415,6 +418,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     silhouette = refinement_mod.has_silhouette(refine)                   # the slot then owns the field's planes
     refine_joints = refinement_mod.has_joints(refine)                    # ... and the joint step's two buffers
     refine_coverage = refinement_mod.has_coverage(refine)                # ... and the predicted field's planes
+    refine_scale = refinement_mod.has_scale(refine)                      # ... and sums of 48 values; check_refine_table refused it with joints
     if refine_joints and kinematics is None:
         raise ValueError("refine=<pose.refinement.pack_refine(joints=...)> solves an object's parts together through the joints of its "
                          "kinematic table: it needs kinematics=<depth.pack_kinematics(...)> (" + RENDERED + ")")
@@ -438,7 +442,7 @@ def check_options(batch_size=1, num_points=None, couple=True, inlier_th=0.1, raw
     o = Options(raw_capacity, depth_capacity, depth_dtype if depth_capacity is not None else None, bool(keyed), predicted, bool(range_guard),
                 bool(articulation), joint_states, fit_quality, bool(ground_truth), point_ground_truth, bool(build_point_gt), bool(build_gt_pose), bool(dense),
                 bool(label_images), bool(annotated_images), link_counts, render_mesh is not None, kinematics is not None, sensor is not None, reprojection, coord_regress_loss, layout.width, layout.key, joint_values,
-                (20 if joint_states else 12) + (joint_values_mod.JOINT_VALUES_WIDTH if joint_values else 0), rows, (), refine_coverage, refine_joints, silhouette, refine)
+                (20 if joint_states else 12) + (joint_values_mod.JOINT_VALUES_WIDTH if joint_values else 0), rows, (), refine_scale, refine_coverage, refine_joints, silhouette, refine)
     # (build_gt_pose: the frame is fitted on the device -- ancsh_gt_pose_build -- and no longer travels in; gt still does, for its extents)
     # (kinematics: the device builds render and scene too -- ancsh_pose_scene_build -- and the pose travels in, first)
     return o._replace(inputs=((POSE_INPUT,) if o.posed else ()) +

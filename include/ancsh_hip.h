@@ -54,6 +54,7 @@ int ancsh_abi_version(void);   /* added since without a new number (callers dete
                                  *     ancsh_refine_pass, ancsh_refine_rec (render-and-compare ICP: that record's poses refined on the depth frame),
                                  *     ancsh_silhouette_field, ancsh_refine_pass_sil (that loop's silhouette term: poses shifted across the ray come back),
                                  *     ancsh_coverage_field, ancsh_refine_pass_cov (its coverage term: a part is pulled over observed pixels it leaves bare),
+                                 *     ancsh_refine_pass_scale (its scale unknown: with both pixel terms on, s is solved with R and t),
                                  *     ancsh_joint_values_rec (the streamed joint values: q read off the fitted and refined part poses),
                                  *ancsh_pose_fit_rec, ancsh_pose_fit_rec_dseed, ancsh_pose_fit_rec_dkey and their _kind forms (both
                                  *     stages of the pose fit in one call, the LM fits and stage A's refit in one launch);
@@ -1736,6 +1737,50 @@ int ancsh_refine_pass_cov(int nframes, int K, int depth_type, const float *verts
                           const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
                           const double *pred_render, const float *norm_factor, const double *params, const int *field, const int *cover,
                           int pass, int is_last, const double *pose_in, int ld_in, double *pose_out, double *best, double *sums, void *stream);
+
+/* The scale unknown of render-and-compare ICP, one entry beside those above (no new ABI number: callers detect it by its symbol).  The loop
+ * moves R and t of every (frame, part, pose) and carries s, the network's NOCS scale; a part that is too small is then pulled over its
+ * observation by moving, not by growing.  The overhang rows (the part is drawn where the camera did not see it) and the gap rows (the camera
+ * saw the part where nothing is drawn) observe size -- depth rows alone cannot tell scale from depth along the ray -- so with both pixel terms
+ * on, this entry solves a seventh unknown sigma, the relative change of the part's size about its centre c.  The loop is the coverage loop
+ * with ancsh_refine_pass_scale in ancsh_refine_pass_cov's place; the joint step is not combined with it.
+ *
+ * ancsh_refine_pass_scale: ancsh_refine_pass_cov with the unknown, ONE launch.  ancsh_refine_pass_cov's arguments, and behind cover:
+ *   fitted (nframes, K, ld_fitted) float64, ld_fitted >= 26 : the record the loop started from; s_0 of pose v of part j of frame f is
+ *   fitted[(f K + j) ld_fitted + 13 v + 9];
+ *   params : ONE table of ANCSH_REFINE_SCALE_PARAMS = 48 float64: [0..31] ancsh_refine_pass_cov's ([16..23] all 0), [32] max_step in (0, 0.5],
+ *   [33] max_total in [max_step, 1], [34..47] reserved, 0;  sums (nframes, K, 2, ANCSH_REFINE_SCALE_SUMS = 48).
+ *   Every rule of ancsh_refine_pass_cov holds: which pixels give which rows, r and J = (J_0 .. J_5) of each, the centre, the cost C and
+ *   best-of (so costs stay comparable with and without the unknown), n_rows = (n_used + n_sil) + n_cov >= min_pixels, is_last.  In addition
+ *   every row has a seventh derivative Js, the row's r by sigma when a point x of the part moves as c + (1 + sigma) (x - c):
+ *     depth row    : Js = dot(n, pc), pc = p - c;
+ *     overhang row : Js = weight dot(g, pc), pc = p - c (that row's p and g);
+ *     gap row      : Js = weight_c dot(g, pc), pc = pn - c (that row's pn and g);
+ *   and adds, behind its J_x J_y and J_x r and in this order, J_x Js into A_xs (x = 0 .. 5), Js Js into A_ss and Js r into b_s.  These eight
+ *   are accumulators 36..43 behind the coverage pass's 36: the same pixel order, xor-shuffle tree and wave order, no atomics.
+ *   sums row: [0..39] ancsh_refine_pass_cov's | [40..45] A_0s .. A_5s | [46] A_ss | [47] b_s.
+ *   The solve: the 7 x 7 system [A (6 x 6), A_xs; A_xs^T, A_ss] xi = -[b; b_s] in ancsh_refine_pass's written order with 7 in 6's place: every
+ *   diagonal A_kk = A_kk + (damping A_kk + 1e-12), k = 0 .. 6; Cholesky row by row; L y = -b forwards; L^T xi = y backwards from row 6.  It
+ *   FAILS when a pivot is not > 0 or not finite, or one of the seven values is not finite.  xi = (w, dt, sigma).
+ *   Clamp: when |w| > max_angle or |dt| > max_dist or |sigma| > max_step, all SEVEN values are multiplied by f: f = 1; |w| > max_angle: f =
+ *   max_angle / |w|; |dt| > max_dist and max_dist / |dt| < f: f = that; |sigma| > max_step and max_step / |sigma| < f: f = that.  Then sigma
+ *   alone: lo = s_0 / (1 + max_total), hi = s_0 (1 + max_total), with s the working pose's:  s (1 + sigma) > hi: sigma = hi / s - 1;  else s (1
+ *   + sigma) < lo: sigma = lo / s - 1.  A working s that is not > 0, or a kept s (1 + sigma) that is not finite or not > 0, FAILS the solve
+ *   as well.
+ *   Update: dR from w as in ancsh_refine_pass;  R' = dR R;  s' = s * (1.0 + sigma);  t'_a = ((1.0 + sigma) * dot(dR[a], t - c) + c_a) + dt_a:
+ *   x' = c + (1 + sigma) dR (x - c) + d for every point x of the part.  With sigma = 0 and the scale sums 0 these are ancsh_refine_pass_cov's
+ *   bytes.
+ *   NaN rules: ancsh_refine_pass_cov's, sums[40..47] are NaN on that branch; a pose whose s_0 is not finite or not > 0 takes that branch too.
+ *   Checked before any launch, in ancsh_refine_pass_cov's order and under the name refine_pass_scale: its checks, ld_fitted >= 26 behind ld_in,
+ *   fitted not null and 8-byte aligned.  nframes == 0 launches nothing and returns 0. */
+#define ANCSH_REFINE_SCALE_SUMS 48
+#define ANCSH_REFINE_SCALE_PARAMS 48
+int ancsh_refine_pass_scale(int nframes, int K, int depth_type, const float *verts, const int *tris, const int *tri_link, int V, int T,
+                            const void *obs_depth, const unsigned char *obs_labels, long pixel_capacity, const unsigned long long *pred_zbuf,
+                            const void *pred_depth, const unsigned char *pred_labels, const int *geom, const double *scene,
+                            const double *pred_render, const float *norm_factor, const double *params, const int *field, const int *cover,
+                            const double *fitted, int ld_fitted, int pass, int is_last, const double *pose_in, int ld_in, double *pose_out,
+                            double *best, double *sums, void *stream);
 
 /* The joint values q of a posed frame read off its part poses: ancsh_pose_scene_build's forward kinematics inverted on the predicted link
  * maps, ONE launch at the step's end (no new ABI number: callers detect it by its symbol).  The posed stream takes q in (pose[f][l]); this

@@ -26,13 +26,15 @@ device wrappers (pose.refinement.refine_batch) on it, and the eager operator dep
 slack=1)), and times ancsh_silhouette_field, one ancsh_refine_pass_sil and the whole loop with the term on the same batch and record.
 --refine N --silhouette --coverage adds a fourth leg, c: the rendered stream built with the same table and coverage=dict(weight=1, dist=0.1,
 slack=1), next to silhouette-only (s) and plain (f), and times ancsh_coverage_field, one ancsh_refine_pass_cov and the whole loop with both terms.
+--refine N --silhouette --coverage --scale adds a fifth leg, g: the rendered stream built with the same table and scale=dict(max_step=0.05,
+max_total=0.25), alternated with the coverage-only stream (c) of the same build, and times one ancsh_refine_pass_scale and the whole loop with it.
 --refine N --joints measures the joint step (refine=pack_refine(iters=N, joints=dict(weight=1, axis_length=0.5))) instead, on the POSED stream
 (the option needs the kinematic table: link 1 hangs on a revolute, link 2 on a prismatic joint of link 0): two legs, alternated:
     f: the posed stream built with refine=pack_refine(iters=N);   j: the same with joints=;
 ancsh_refine_joint_step alone on one batch of 32 frames whose record draws every part a different distance off its place, and the share of
 that batch's objects whose joints' position residual (obj's gap_rms) is lower at the last pass than at the first.
 
-    python tools/render_bench.py [--sensor | --reprojection | --refine N [--silhouette [--coverage] | --joints]] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
+    python tools/render_bench.py [--sensor | --reprojection | --refine N [--silhouette [--coverage [--scale]] | --joints]] [--rounds 3] [--passes 4] [--slots 8] [--frames 320] [--side 128] [--tess 8]
 """
 import argparse
 import json
@@ -221,7 +223,9 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
     table = F.pack_refine(iters=args.refine)
     sil_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0)) if args.silhouette else None
     cov_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0), coverage=dict(weight=1.0, dist=0.1, slack=1.0)) if args.coverage else None
-    legs = "rfsc" if args.coverage else "rfs" if args.silhouette else "rf"
+    scl_table = F.pack_refine(iters=args.refine, silhouette=dict(weight=1.0, dist=0.1, slack=1.0), coverage=dict(weight=1.0, dist=0.1, slack=1.0),
+                              scale=dict(max_step=0.05, max_total=0.25)) if args.scale else None
+    legs = "rfscg" if args.scale else "rfsc" if args.coverage else "rfs" if args.silhouette else "rf"
     wa, wn = synthetic_weights(K, seed=0), synthetic_weights(K, mixed_pred=False, early_split_nocs=False, seed=1)
     kw = dict(couple=True, slots=args.slots, joint_source="predicted", articulation=True, point_ground_truth=True, build_point_gt=True,
               depth_capacity=cap, depth_dtype="uint16", render_mesh=mesh)
@@ -230,6 +234,8 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
         pipes["s"] = AncshPipeline(K, wa, wn, B, N, dev, refine=sil_table, **kw).prepare()
     if args.coverage:
         pipes["c"] = AncshPipeline(K, wa, wn, B, N, dev, refine=cov_table, **kw).prepare()
+    if args.scale:
+        pipes["g"] = AncshPipeline(K, wa, wn, B, N, dev, refine=scl_table, **kw).prepare()
     torch.cuda.synchronize()
     last = {}
 
@@ -312,6 +318,27 @@ def refine_bench(args, K, B, N, dev, mesh, d_mesh, rbatches, d_geom, d_rt, d_sc,
                            "median_cost_start": float(np.median(ccols["baseline_cost_start"])),
                            "median_cost_best": float(np.median(ccols["baseline_cost_best"])),
                            "parts_improved": int((ccols["baseline_cost_best"] < ccols["baseline_cost_start"]).sum()), "parts": B * K}
+    if args.scale:                                                        # ... and with s solved as well: one pass and the loop, on the same batch and record
+        d_gpar = torch.from_numpy(scl_table).to(dev)
+        gbufs = F.refine_buffers(B, K, dev, silhouette=True, pixel_capacity=cap, coverage=True, scale=True)
+        R.reproject_scene_build(d_rt, d_sc, d_rig, d_nf, carried, d_geom, cap, out=tables)
+        D.render_depth(d_mesh, tables[1], tables[0], "uint16", out=pred[:2], scratch=pred[2])
+        F.silhouette_field(clean[0], clean[1], d_geom, d_sc, K, out=gbufs.field)
+        F.coverage_field(pred, tables[1], d_sc, K, out=gbufs.cover)
+        op_ms["refine_pass_scale"] = timed_calls(lambda: F.refine_pass(d_mesh, clean[0], clean[1], pred, d_geom, d_sc, tables[0], d_nf, d_gpar, 0, False,
+                                                                       carried, gbufs.work[0], gbufs.best, gbufs.sums[0], field=gbufs.field,
+                                                                       cover=gbufs.cover, fitted=carried), args.rounds, args.calls)
+        gloop = lambda: F.refine_batch(d_mesh, d_rt, d_sc, d_rig, d_nf, d_geom, clean, carried, "uint16", tables, pred, d_gpar, args.refine, gbufs)
+        op_ms["whole_loop_scale"] = timed_calls(gloop, args.rounds, max(1, args.calls // 10))
+        gcols = F.named_columns(gloop().cpu().numpy())
+        sil["scale"] = {"table": scl_table[32:34].tolist(), "launches_added_over_coverage": 0,
+                        "added_ms_per_batch_over_coverage": round(med["g"] - med["c"], 4), "g_over_c": round(med["g"] / med["c"], 4),
+                        "g_over_r": round(med["g"] / med["r"], 4),
+                        "refine_pass_scale_over_cov": round(float(np.median(op_ms["refine_pass_scale"]) / np.median(op_ms["refine_pass_cov"])), 4),
+                        "median_s_kept_over_s_fitted": float(np.median(gcols["baseline_s"] / moved[:, :, 9])),
+                        "median_cost_start": float(np.median(gcols["baseline_cost_start"])),
+                        "median_cost_best": float(np.median(gcols["baseline_cost_best"])),
+                        "parts_improved": int((gcols["baseline_cost_best"] < gcols["baseline_cost_start"]).sum()), "parts": B * K}
     frames = D._cut_frames(clean[0].cpu().numpy().view(np.uint16), clean[1].cpu().numpy(), d_geom.cpu().numpy(), "uint16")
     eager = []
     for _ in range(args.rounds):
@@ -440,6 +467,7 @@ def main():
     ap.add_argument("--refine", type=int, default=0, metavar="N", help="measure render-and-compare ICP (refine=pack_refine(iters=N)) instead of the renderer")
     ap.add_argument("--silhouette", action="store_true", help="with --refine N: measure the silhouette term as well (a third leg and its launches)")
     ap.add_argument("--coverage", action="store_true", help="with --refine N --silhouette: measure the coverage term as well (a fourth leg and its launches)")
+    ap.add_argument("--scale", action="store_true", help="with --refine N --silhouette --coverage: measure the scale unknown as well (a fifth leg beside the coverage-only stream)")
     ap.add_argument("--joints", action="store_true", help="with --refine N: measure the joint step on the posed stream (joints= off and on, alternated)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--passes", type=int, default=4, help="passes over the frames per timed leg")
@@ -449,6 +477,8 @@ def main():
     ap.add_argument("--tess", type=int, default=8, help="quads per box edge: 12 tess^2 triangles per link")
     ap.add_argument("--calls", type=int, default=200, help="back-to-back calls of the operator between its two events")
     args = ap.parse_args()
+    if args.scale and not (args.refine and args.silhouette and args.coverage):
+        ap.error("--scale goes with --refine N --silhouette --coverage: the scale unknown runs with both pixel terms")
     if args.coverage and not (args.refine and args.silhouette):
         ap.error("--coverage goes with --refine N --silhouette: the coverage term runs with the silhouette term")
     K, B, N, dev = 3, 32, 1024, torch.device("cuda:0")
